@@ -21,11 +21,11 @@ also its row in the gathered table; weak scaling, no data-path collective); the 
                `traffic` comes from the committed rocprofv3 --pmc passes and is emitted only when the sources of
                libdgp_hip.so are the ones those passes were taken on (`source_hash` in the profile JSON).
 `cpu_baseline` the CPU oracle (a dense torch restatement of the reference's gpytorch math -- gpytorch itself is not
-               installable here) on the host cores, rank 0 / N=1 only: the torch thread count is picked by a measured,
+               a dependency) on the host cores, --full, rank 0 / N=1 only: the torch thread count is picked by a measured,
                bracketed two-stage sweep (8 ... all of the affinity mask at n/2, then the best and its neighbours at n;
                printed), then the median of `--cpu-steps` (3) NLL+gradient steps at n = 8192 fp64,
                plus the fp32 figure.
-`configs`      (default single-GPU run only) the other BASELINE.json configurations that fit one GPU, each timed here
+`configs`      (--full, default single-GPU run only) the other BASELINE.json configurations that fit one GPU, each timed here
                with its own rooflines: C1 n~300 engine iterations (both models; warm and cold predict), the engine-level
                `model.fit` iteration at n=8192, C3 rating-gp n=16384 d=2 fp32,
                C4's per-GPU share (64 sites of n=4096 in one batched plan), C5's matrix on one GPU (n=65536 fp32), and
@@ -34,6 +34,13 @@ also its row in the gathered table; weak scaling, no data-path collective); the 
 
 `--model rating` runs the headline loop on the rating-gp kernel instead (d = 2); `--config 5` is the torchrun entry
 point of the distributed factorisation + gradient of ONE matrix over all ranks (discontinuum_amd/dist_chol.py).
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps and the line, whose `roofline` is read
+from the HIP events of the timed region's last step (no run of its own; `clock_mhz` / `frac_at_clock` null).  `--full`
+adds everything else, measured after the timed region: the shader-clock probes, `gpu_state`, the batch-parity check,
+`single_site`, `configs` and `cpu_baseline` (and, for `--config 5`, the roofline's extra instrumented step).
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (dump_outputs); the inputs are seeded,
+so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -627,6 +634,25 @@ def batch_parity(batched, single, ntheta, dtype_name, lib):
     return res
 
 
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(dirname, arrays):
+    """Write `arrays` (name -> tensor) as DIR/<name>.npy, float32 / float64 as computed.  When they hold more than
+    DUMP_LIMIT_BYTES in all, each array keeps its share of that budget as a sample of its flattened elements at indices
+    drawn by a fixed seed from its size alone, so two runs with the same arguments write the same positions."""
+    os.makedirs(dirname, exist_ok=True)
+    host = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    host = {k: v if v.dtype in (np.float32, np.float64) else v.astype(np.float64) for k, v in host.items()}
+    total = sum(v.nbytes for v in host.values())
+    for name, v in host.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = int(v.size * DUMP_LIMIT_BYTES / total)
+            idx = np.sort(np.random.default_rng(0).choice(v.size, keep, replace=False))
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(dirname, f"{name}.npy"), v)
+
+
 def launch_ranks(n_ranks):
     """`python bench.py --gpus N` without a launcher: start the N ranks the way the driver does
     (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...`)
@@ -688,6 +714,11 @@ def main():
     ap.add_argument("--roofline-only", action="store_true",
                     help="run only the per-kernel timing loop of the roofline object (the command profiled with "
                          "rocprofv3 --kernel-trace --stats for profiles/)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: clock probes, gpu_state, batch parity, single_site, configs and cpu_baseline "
+                         "(--no-* options above narrow it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (at most 64 MB in all)")
     args = ap.parse_args()
     model = args.model
     d = args.d if args.d is not None else (3 if model == "loadest" else 2)
@@ -698,7 +729,7 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    sampler = GpuStateSampler() if (rank == 0 and args.config == 2 and not args.roofline_only) else None
+    sampler = GpuStateSampler() if (rank == 0 and args.config == 2 and args.full and not args.roofline_only) else None
     if args.gpus > 1 and world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launched by something else with a different rank count")
     dist = None
@@ -761,13 +792,12 @@ def main():
     # The single-site plan (latency) uses the default level 2 (early inverse on a third stream).
     level = 0 if args.no_lookahead else (1 if S > 1 else 2)
     bplan, btheta, ball, bnoise = make_plan(model, n, d, dt, dev, S, level, seed0=rank, seed_stride=world)
-    if S > 1:
-        plan, theta, y0, noise0 = make_plan(model, n, d, dt, dev, 1, 0 if args.no_lookahead else 2, seed0=rank)
-    else:
-        plan, theta, y0, noise0 = bplan, btheta, ball, bnoise
+    plan = None  # the single-site plan of --full (parity, single_site), made after the timed region
+    last = {}
 
     def batch_step():
-        out = bplan.fit_step(btheta, ball, bnoise)[0]
+        last["step"] = bplan.fit_step(btheta, ball, bnoise)  # (out, dNLL/dr, dNLL/dnoise) of every site
+        out = last["step"][0]
         return list(out) if S > 1 else [out]
 
     bplan.set_timing(True)  # HIP events around every bulk launch, on the stream it runs on (the roofline object)
@@ -815,12 +845,18 @@ def main():
     host = local.cpu().double()
     assert bool((host[:, _lib.OUT_INFO] == 0).all()) and bool(torch.isfinite(host[:, _lib.OUT_NLL]).all()), "fit step failed"
     assert table.shape[0] == world * S and bool(torch.isfinite(table[:, _lib.OUT_NLL]).all()), "a site failed"
+    if rank == 0 and args.dump_outputs:
+        # the gathered out rows of all sites (DGP_OUT_* layout: NLL, quad, log-det, info, dNLL/dtheta, ...) and this rank's
+        # per-observation gradients
+        _, dr, dnoise = last["step"]
+        dump_outputs(args.dump_outputs, {"fit_out": table.reshape(world * S, -1), "dnll_dr": dr.reshape(S, -1),
+                                         "dnll_dnoise": dnoise.reshape(S, -1)})
 
     # ---- shader clock under load, rank 0, AFTER the timed region (the probe shares a few CUs with the load): once while
     # whole fit steps run back to back, once while the dominant kernel's stage (K^^-1 = L^-T L^-1, lauum_kernel) does
     clk_step = clk_lauum = clk_potrf = clk_trtri = None
     rep = stage_report(bplan, S, args.dtype, level, _lib) if rank == 0 else None  # last step of the TIMED REGION (before any probe)
-    if rank == 0 and not args.no_clock_probe:
+    if rank == 0 and args.full and not args.no_clock_probe:
         lauum_s = max(1e-4, rep["stages_ms"]["lauum"] * 1e-3)
         clk_step = clock_probe(_lib.load(), dev, batch_step, elapsed / args.steps)
         clk_lauum = clock_probe(_lib.load(), dev, bplan.stage_lauum, lauum_s)
@@ -837,13 +873,16 @@ def main():
     # (pairs + split chain + early inverse against groups of 4), different launches, the same matrix.  Asserted: the line is
     # only printed if the batch the value was measured on reproduces the single-site result.
     parity = None
-    if rank == 0 and S > 1:
+    if rank == 0 and args.full and S > 1:
+        plan, theta, y0, noise0 = make_plan(model, n, d, dt, dev, 1, 0 if args.no_lookahead else 2, seed0=rank)
         parity = batch_parity(bplan.fit_step(btheta, ball, bnoise), plan.fit_step(theta, y0, noise0), plan.ntheta, args.dtype, _lib)
         assert parity["ok"], f"site 0 of the {S}-site batch differs from the single-site plan: {parity}"
+    elif rank == 0 and args.full:
+        plan, theta, y0, noise0 = bplan, btheta, ball, bnoise
 
     # ---- single-site loop on rank 0: latency of one fit alone on the GPU
     single_ms = None
-    if rank == 0:
+    if rank == 0 and args.full:
         ksingle = max(3, args.steps // 2)
         plan.fit_step(theta, y0, noise0)
         torch.cuda.synchronize()
@@ -922,7 +961,7 @@ def main():
             "gpu_state": sampler.window(wall0, wall1) if sampler is not None else None,
             "single_site": {"fits_per_s": 1e3 / single_ms, "ms_per_fit": single_ms,
                             "tflops": float(N) ** 3 / (single_ms * 1e-3) / 1e12,
-                            "note": "one site alone on one GPU, steps strictly sequential (a single fit loop)"},
+                            "note": "one site alone on one GPU, steps strictly sequential (a single fit loop)"} if single_ms else None,
             "roofline": roofline,
         }
         if train is not None:
@@ -930,9 +969,9 @@ def main():
         default_run = (world == 1 and (model, n, d, args.dtype) == ("loadest", 8192, 3, "f64"))
         del bplan, plan
         torch.cuda.empty_cache()
-        if default_run and not args.no_configs:
+        if args.full and default_run and not args.no_configs:
             result["configs"] = run_configs(dev, _lib, args.quick_configs)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(n, d, max(1, args.cpu_steps))
         else:
             result["cpu_baseline"] = None
@@ -969,14 +1008,16 @@ def run_config5(args, model, d, dev, world, rank, dist, barrier, lib):
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
-    ctx.set_timing(True)
-    for k in ctx.comm.calls:
-        ctx.comm.calls[k] = 0  # `collectives_issued` = what ONE fit step issues
-    ctx.fit_step(theta, rd, nd)  # every rank takes part; rank 0 reports its own stages
-    stage_ms = ctx.get_timing()
-    if rank == 0:
-        N = ctx.N
-        host = out.cpu().double()
+    if rank == 0 and args.dump_outputs:  # (the extra step below overwrites ctx.alpha / ctx.dnoise)
+        dump_outputs(args.dump_outputs, {"fit_out": out, "dnll_dr": ctx.alpha, "dnll_dnoise": ctx.dnoise})
+    roofline = None
+    if args.full:
+        ctx.set_timing(True)
+        for k in ctx.comm.calls:
+            ctx.comm.calls[k] = 0  # `collectives_issued` = what ONE fit step issues
+        ctx.fit_step(theta, rd, nd)  # every rank takes part; rank 0 reports its own stages
+        stage_ms = ctx.get_timing()
+    if rank == 0 and args.full:
         flops = ctx.stage_flops()
         dom = max(flops, key=lambda k: stage_ms[k])
         peak = PEAK_TFLOPS[args.dtype]
@@ -989,6 +1030,9 @@ def run_config5(args, model, d, dev, world, rank, dist, barrier, lib):
                     "stages_tflops": {k: (flops[k] / (stage_ms[k] * 1e-3) / 1e12 if stage_ms[k] > 0 else None) for k in flops},
                     "measured_in": "one extra fit step after the timed region, rank 0's launches",
                     "collectives_issued": dict(ctx.comm.calls)}
+    if rank == 0:
+        N = ctx.N
+        host = out.cpu().double()
         print(json.dumps({
             "metric": METRIC, "value": args.steps / elapsed, "unit": "fits/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "strong",

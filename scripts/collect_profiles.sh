@@ -26,7 +26,7 @@ run write  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$ou
 # lease, in that order); BENCH_ARGS e.g. "--no-cpu-baseline --no-configs" for a quick collection
 unset DGP_SPLIT_CHAIN
 echo "== bench" >> "$out/log.txt"
-timeout -k 10 900 python3 bench.py ${BENCH_ARGS:-} > "$out/bench_line.json" 2>> "$out/log.txt" || { echo "FAILED: bench" | tee -a "$out/log.txt"; exit 1; }
+timeout -k 10 900 python3 bench.py --full ${BENCH_ARGS:-} > "$out/bench_line.json" 2>> "$out/log.txt" || { echo "FAILED: bench" | tee -a "$out/log.txt"; exit 1; }
 ok=1
 python3 scripts/pmc_summary.py "$out/fetch" "$out/write" "$out/pmc_hbm.json" 3 32 "$commit" > "$out/pmc_hbm.txt" 2>&1 || ok=0
 python3 scripts/mfma_util.py "$out/mfma" "$out/mfma_busy.json" > "$out/mfma_busy.txt" 2>&1 || ok=0

@@ -47,7 +47,7 @@ def test_a_foreign_world_size_is_refused():
 def test_plain_gpus_2_starts_two_ranks_and_prints_one_line(gpu_device):
     """The plain command on the one-GPU box: two ranks share the card over gloo (RCCL refuses two ranks on one device)."""
     S = 3
-    cmd = [sys.executable, BENCH, "--gpus", "2", "--size", "1024", "--steps", "2", "--warmup", "1", "--sites-per-gpu", str(S),
+    cmd = [sys.executable, BENCH, "--full", "--gpus", "2", "--size", "1024", "--steps", "2", "--warmup", "1", "--sites-per-gpu", str(S),
            "--train", "4"]
     run = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900,
                          env=_clean_env(DGP_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0"))
@@ -70,8 +70,11 @@ def test_plain_gpus_2_starts_two_ranks_and_prints_one_line(gpu_device):
 
 
 @pytest.mark.gpu
-def test_plain_gpus_2_config5(gpu_device):
-    cmd = [sys.executable, BENCH, "--gpus", "2", "--config", "5", "--size", "2500", "--dtype", "f32", "--steps", "2", "--warmup", "1"]
+def test_plain_gpus_2_config5(gpu_device, tmp_path):
+    import numpy as np
+
+    cmd = [sys.executable, BENCH, "--gpus", "2", "--config", "5", "--size", "2500", "--dtype", "f32", "--steps", "2", "--warmup", "1",
+           "--dump-outputs", str(tmp_path)]
     run = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900,
                          env=_clean_env(DGP_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert run.returncode == 0, run.stderr[-3000:]
@@ -79,6 +82,35 @@ def test_plain_gpus_2_config5(gpu_device):
     assert len(lines) == 1, run.stdout
     rec = json.loads(lines[0])
     assert rec["n_gpus"] == 2 and rec["scaling"] == "strong" and rec["config"]["info"] == 0 and rec["config"]["backend"] == "gloo"
+    assert rec["roofline"] is None  # the instrumented extra step is --full's
+    out, dr, dnoise = (np.load(tmp_path / f"{k}.npy") for k in ("fit_out", "dnll_dr", "dnll_dnoise"))
+    assert out.shape == (32,) and dr.shape == dnoise.shape == (2500,) and out.dtype == dr.dtype == np.float32
+    assert float(out[0]) == rec["config"]["nll"] and np.isfinite(dr).all() and np.isfinite(dnoise).all()
+
+
+def test_dump_outputs_keeps_float_types_and_samples_within_the_budget(tmp_path, monkeypatch):
+    """bench.dump_outputs: float32 / float64 arrays as computed, anything else as float64; over the budget every array keeps
+    its share as a sample at seeded positions, the same on every call."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    arrays = {"big": torch.arange(1000, dtype=torch.float64), "small": torch.arange(10, dtype=torch.float32),
+              "info": torch.zeros(3, dtype=torch.int32)}
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "whole" / f"{k}.npy")
+        assert got.dtype == (np.float32 if k == "small" else np.float64) and (got == v.numpy()).all()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096)
+    for tag in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / tag), arrays)
+    total = 0
+    for k, v in arrays.items():
+        a, b = (np.load(tmp_path / tag / f"{k}.npy") for tag in ("a", "b"))
+        assert (a == b).all() and 0 < a.size < v.numel() and np.isin(a, v.numpy().astype(a.dtype)).all()
+        total += a.nbytes
+    assert total <= 4096
 
 
 def test_roofline_check_puts_the_three_figures_side_by_side(tmp_path):

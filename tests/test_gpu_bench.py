@@ -15,7 +15,7 @@ REQUIRED = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 
 @pytest.mark.parametrize("extra", [[], ["--dtype", "f32", "--sites-per-gpu", "1"], ["--model", "rating", "--sites-per-gpu", "4"]])
 def test_bench_prints_one_contract_line(extra, gpu_device):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--n", "1024", "--steps", "3", "--warmup", "1", "--cpu-steps", "2"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--n", "1024", "--steps", "3", "--warmup", "1", "--cpu-steps", "2"] + extra
     run = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert run.returncode == 0, run.stderr[-2000:]
     lines = [ln for ln in run.stdout.splitlines() if ln.startswith("{")]
@@ -48,6 +48,37 @@ def test_bench_prints_one_contract_line(extra, gpu_device):
     assert "gpu_state" in rec
     if rec["gpu_state"] is not None:
         assert 500 < rec["gpu_state"]["sclk_mhz"]["mean"] < 3000 and rec["gpu_state"]["samples"] >= 1
+
+
+def test_plain_bench_is_lean_and_dumps_the_last_step(tmp_path, gpu_device):
+    """Without --full the line carries the headline alone (nothing measured after the timed region); --dump-outputs writes
+    what the last timed step returned, and a second run with the same arguments writes the same arrays."""
+    import numpy as np
+
+    S, n = 4, 1024
+    recs = []
+    for tag in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--n", str(n), "--steps", "3", "--warmup", "1",
+               "--sites-per-gpu", str(S), "--dump-outputs", str(tmp_path / tag)]
+        run = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert run.returncode == 0, run.stderr[-2000:]
+        lines = [ln for ln in run.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, run.stdout
+        recs.append(json.loads(lines[0]))
+    rec = recs[0]
+    for key in REQUIRED:
+        assert key in rec, key
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["value"] > 0
+    assert abs(rec["ms_per_step"] * rec["value"] / 1e3 - S) < 1e-6
+    assert rec["cpu_baseline"] is None and rec["gpu_state"] is None and rec["single_site"] is None and "configs" not in rec
+    assert rec["config"]["parity"] is None and rec["roofline"]["clock_mhz"] is None and 0 < rec["roofline"]["frac"] < 1
+    shapes = {"fit_out": (S, 32), "dnll_dr": (S, n), "dnll_dnoise": (S, n)}
+    for name, shape in shapes.items():
+        a, b = (np.load(tmp_path / tag / f"{name}.npy") for tag in ("a", "b"))
+        assert a.shape == shape and a.dtype == np.float64 and np.isfinite(a).all(), (name, a.shape, a.dtype)
+        np.testing.assert_allclose(a, b, rtol=1e-12, atol=0)
+    out = np.load(tmp_path / "a" / "fit_out.npy")
+    assert out[0, 0] == rec["config"]["nll_site0"] and (out[:, 3] == 0).all()  # DGP_OUT_NLL, DGP_OUT_INFO
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -83,7 +114,7 @@ def test_torchrun_two_ranks_headline_line(gpu_device):
 
 
 def test_torchrun_two_ranks_config5_line(gpu_device):
-    rec = _torchrun(["--config", "5", "--size", "2500", "--dtype", "f32", "--steps", "2", "--warmup", "1"])
+    rec = _torchrun(["--full", "--config", "5", "--size", "2500", "--dtype", "f32", "--steps", "2", "--warmup", "1"])
     for key in REQUIRED:
         assert key in rec, key
     assert rec["n_gpus"] == 2 and rec["scaling"] == "strong" and rec["dtype"] == "f32"
@@ -98,7 +129,7 @@ def test_bench_forced_collectives_enter_rccl_with_one_rank(gpu_device):
     """`DGP_DIST_FORCE_COLLECTIVES=1 python bench.py --config 5`: one rank, backend nccl, every collective issued."""
     env = dict(os.environ, DGP_DIST_FORCE_COLLECTIVES="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("DGP_BENCH_BACKEND", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "5", "--size", "3000", "--dtype", "f32", "--steps", "2", "--warmup", "1"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", "5", "--size", "3000", "--dtype", "f32", "--steps", "2", "--warmup", "1"]
     run = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert run.returncode == 0, run.stderr[-3000:]
     rec = json.loads([ln for ln in run.stdout.splitlines() if ln.startswith("{")][0])
