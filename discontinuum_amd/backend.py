@@ -304,6 +304,13 @@ class GPPlan:
         self._last_z = z
         return out
 
+    def period_moments(self, cov, m: int, mu, scale2, w, groups, ngroups: int, mode: int, extra_var=None):
+        """Exact mean and covariance of period sums of the transformed posterior (``dgp_period_moments``): see the
+        module-level ``period_moments``.  Unbatched (cov (M, M), vectors (m,)) -> mean (P,), cov (P, P); batched
+        (cov (B, M, M), vectors (B, m)) -> (B, P), (B, P, P); all fp64 device tensors."""
+        with torch.cuda.device(self.device):
+            return period_moments(cov, m, mu, scale2, w, groups, ngroups, mode, extra_var)
+
     def _vjp_workspace(self, m):
         need = int(self.lib.dgp_mean_vjp_workspace_bytes(self._h, m))
         ws = getattr(self, "_vjp_ws", None)
@@ -410,3 +417,53 @@ class GPPlan:
                 "dgp_cross_gram",
             )
         return Ks[: self.n, :m]
+
+
+MODE_LINEAR, MODE_LOG = 0, 1
+
+
+def period_moments(cov: torch.Tensor, m: int, mu: torch.Tensor, scale2, w: torch.Tensor, groups: torch.Tensor, ngroups: int,
+                   mode: int, extra_var: torch.Tensor | None = None):
+    """Exact mean and covariance of the period sums L_g = sum_{i in g} w_i c_i of a transformed latent posterior
+    f ~ N(mu, C) -- c_i = exp(f'_i) (``mode`` = MODE_LOG) or c_i = f'_i (MODE_LINEAR) with f' = s f + t -- through one
+    ``dgp_period_moments`` call (no factorisation, no draws).
+
+    ``cov``: what ``GPPlan.posterior_cov`` returns -- (M, M), M = padded m, lower triangle and diagonal blocks valid -- or
+    (B, M, M) for B sites; ``mu``: the MAPPED mean s mu + t, (m,) / (B, m), the dtype of ``cov``; ``scale2``: s^2, a
+    number, or (B,) values; ``w``: weights (m,) / (B, m); ``groups``: int32 ids (m,) / (B, m) in 0 .. ngroups-1,
+    non-decreasing except for -1 (excluded) anywhere; ``extra_var``: None or (m,) / (B, m) added to the diagonal of C.
+    -> (mean (P,), cov (P, P)) or ((B, P), (B, P, P)), float64 device tensors."""
+    lib = _lib.load()
+    batched = cov.dim() == 3
+    B = cov.shape[0] if batched else 1
+    M = int(lib.dgp_padded_n(int(m)))
+    lead = (B,) if batched else ()
+    if cov.dtype not in _DTYPES or not cov.is_cuda or not cov.is_contiguous() or tuple(cov.shape) != lead + (M, M):
+        raise ValueError(f"cov must be a contiguous {lead + (M, M)} float64 / float32 CUDA tensor")
+    dev = cov.device
+
+    def vec(t, name, dtype):
+        if t is None:
+            return None
+        t = torch.as_tensor(t).to(dev, dtype).contiguous()
+        if tuple(t.shape) != lead + (int(m),):
+            raise ValueError(f"{name} must have shape {lead + (int(m),)}")
+        return t
+
+    mu_t, w_t = vec(mu, "mu", cov.dtype), vec(w, "w", torch.float64)
+    g_t, ev_t = vec(groups, "groups", torch.int32), vec(extra_var, "extra_var", cov.dtype)
+    s2 = torch.as_tensor(scale2, dtype=torch.float64).reshape(-1).to(dev).contiguous()
+    if s2.numel() != B:
+        raise ValueError(f"scale2 must hold {B} value(s)")
+    P = int(ngroups)
+    need = int(lib.dgp_period_moments_workspace_bytes(int(m), P, B))
+    work = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    mean_out = torch.empty(lead + (P,), dtype=torch.float64, device=dev)
+    cov_out = torch.empty(lead + (P, P), dtype=torch.float64, device=dev)
+    _lib.check(
+        lib.dgp_period_moments(_DTYPES[cov.dtype], int(mode), _ptr(cov), int(m), B, _ptr(mu_t), _ptr(s2), _ptr(w_t), _ptr(g_t), P,
+                               _ptr(ev_t) if ev_t is not None else None, _ptr(work), need, _ptr(mean_out), _ptr(cov_out),
+                               _stream()),
+        "dgp_period_moments",
+    )
+    return mean_out, cov_out

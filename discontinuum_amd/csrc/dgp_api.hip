@@ -1116,6 +1116,31 @@ int dgp_sample_draws(int dtype, const void* L, int64_t m, const void* Z, int64_t
   return wrap(rc, "dgp_sample_draws");
 }
 
+size_t dgp_period_moments_workspace_bytes(int64_t m, int ngroups, int batch) {
+  if (m <= 0 || m > (1 << 20) || ngroups <= 0 || ngroups > 65535 || batch <= 0 || batch > DGP_MAX_BATCH_SITES) return 0;
+  return period_moments_workspace_bytes(m, ngroups, batch);
+}
+
+int dgp_period_moments(int dtype, int mode, const void* cov, int64_t m, int batch, const void* mu, const double* scale2,
+                       const double* w, const int32_t* group, int ngroups, const void* extra_var, void* work,
+                       size_t work_bytes, double* mean_out, double* cov_out, void* stream) {
+  if (dtype != DGP_F64 && dtype != DGP_F32) return fail(DGP_E_ARG, "dgp_period_moments: dtype must be 0 (f64) or 1 (f32)");
+  if (mode != 0 && mode != 1) return fail(DGP_E_ARG, "dgp_period_moments: mode must be 0 (linear) or 1 (log)");
+  if (!cov || !mu || !scale2 || !w || !group || !mean_out || !cov_out)
+    return fail(DGP_E_ARG, "dgp_period_moments: null argument");
+  if (m <= 0 || m > (1 << 20) || ngroups <= 0 || ngroups > 65535 || batch <= 0 || batch > DGP_MAX_BATCH_SITES)
+    return fail(DGP_E_ARG, "dgp_period_moments: bad size (1 <= m <= 2^20, 1 <= ngroups <= 65535, 1 <= batch <= 1024)");
+  if (!work || work_bytes < period_moments_workspace_bytes(m, ngroups, batch))
+    return fail(DGP_E_WORKSPACE, "dgp_period_moments: workspace missing or too small");
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = dtype == DGP_F64
+                     ? period_moments<double>(mode, (const double*)cov, m, batch, (const double*)mu, scale2, w, group, ngroups,
+                                              (const double*)extra_var, (double*)work, mean_out, cov_out, s)
+                     : period_moments<float>(mode, (const float*)cov, m, batch, (const float*)mu, scale2, w, group, ngroups,
+                                             (const float*)extra_var, (double*)work, mean_out, cov_out, s);
+  return wrap(rc, "dgp_period_moments");
+}
+
 int dgp_plan_set_timing(dgp_plan* p, int enabled) {
   if (!p) return fail(DGP_E_ARG, "null plan");
   p->timing = enabled ? 1 : 0;

@@ -179,4 +179,10 @@ int posterior_cov(const T* V, long N, long M, T* cov, hipStream_t s, int B = 1, 
 template <typename T>
 int sample_draws(const T* L, long M, const T* Z, long Q, const T* mean, int m, int ndraw, T* out, hipStream_t s);
 
+// ---- dgp_aggregate.hip: exact mean / covariance of period sums of exp(s f + t) (mode 1) or s f + t (mode 0), f ~ N(mu, C)
+size_t period_moments_workspace_bytes(long m, int P, int B);
+template <typename T>
+int period_moments(int mode, const T* cov, long m, int B, const T* mu, const double* scale2, const double* w, const int* group,
+                   int P, const T* ev, double* work, double* mean_out, double* cov_out, hipStream_t s);
+
 }  // namespace dgp

@@ -653,5 +653,19 @@ class MarginalHIP(BaseModel):
         return DataArray(data, coords=dict(covariates.coords, draw=np.arange(n)),
                          dims=["draw"] + list(covariates.coords), attrs=temp.attrs)
 
+    @is_fitted
+    def aggregate(self, covariates, weights, freq="YE", ci=0.95, pred_noise=False, return_cov=False):
+        """Exact mean and covariance of the period sums sum_{i in period} weights_i target_i over the points of
+        ``covariates`` (``freq``: a resample alias -- "YE", "YE-SEP" for water years, "QE", "ME"), from the latent
+        posterior (``pred_noise=True`` adds the likelihood's predictive noise to its diagonal): what ``sample()``, a
+        product with the weights and ``resample(time=freq).sum()`` estimate by Monte Carlo, in one posterior
+        covariance and one ``dgp_period_moments`` pass.  Points with a non-finite weight are skipped.  -> Dataset on a
+        ``time`` coordinate of period-end labels with ``mean``, ``se``, ``lower`` / ``upper`` (approximate ``ci``
+        interval: lognormal / normal with the exact moments) and ``n_points``; with ``return_cov`` also the (P, P)
+        covariance.  See ``discontinuum_amd.loads``."""
+        from ..loads import aggregate
+
+        return aggregate(self, covariates, weights, freq=freq, ci=ci, pred_noise=pred_noise, return_cov=return_cov)
+
     def build_model(self, X, y, **kwargs):
         raise NotImplementedError("This method must be implemented in a subclass")

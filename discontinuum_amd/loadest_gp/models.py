@@ -15,7 +15,7 @@ from __future__ import annotations
 import torch
 
 from .. import gp
-from ..engines.base import DataMixin, ModelConfig
+from ..engines.base import DataMixin, ModelConfig, is_fitted
 from ..engines.hip import MarginalHIP
 from ..gp import kernels as K
 from ..gp.priors import GammaPrior, HalfNormalPrior, NormalPrior
@@ -68,3 +68,15 @@ class LoadestGPMarginalHIP(LoadestDataMixin, MarginalHIP):
         fixed = torch.full((1, y.shape[0]), MODEL_SPACE_NOISE, dtype=y.dtype)
         self.likelihood = gp.likelihoods.FixedNoiseGaussianLikelihood(noise=fixed, learn_additional_noise=False)
         return ExactGPModel(X, y, self.likelihood)
+
+    @is_fitted
+    def annual_flux(self, covariates, freq="YE", ci=0.95, pred_noise=False, return_cov=False):
+        """Exact period loads in kilograms -- sum over each period of concentration (mg/l) x flow (m^3/s) x time step --
+        with their standard errors and approximate ``ci`` intervals; ``covariates`` on a regular time grid (an irregular
+        one raises ``ValueError``), ``freq`` a resample alias ("YE", "YE-SEP" for water years, "QE", "ME").  Replaces
+        ``concentration_to_flux(model.sample(daily, n), daily["flow"]).resample(time="YE").sum()``
+        (src/loadest_gp/utils.py:14-103) without its sampling noise; see ``MarginalHIP.aggregate``."""
+        from ..loads import annual_flux
+
+        return annual_flux(self, covariates, freq=freq, ci=ci, pred_noise=pred_noise, return_cov=return_cov)
+

@@ -1,0 +1,309 @@
+"""Exact period sums (annual / monthly loads) of a fitted model's posterior, with their uncertainty.
+
+The reference gets annual loads by Monte Carlo: ``sim = model.sample(daily, n)`` (the full m x m posterior covariance, its
+jittered Cholesky factor, n draws), ``concentration_to_flux(sim, flow)`` and ``flux.resample(time="YE").sum()``
+(``src/loadest_gp/utils.py:14-103``).  For the two target transforms of the project the moments of a period sum
+L_g = sum_{i in g} w_i c_i have a closed form over the latent posterior f ~ N(mu, C) (model space), with s, t the target
+scaler's ``scale_`` and ``mean_``:
+
+    log      (c = exp(s f + t)):  a_i = w_i exp(s mu_i + t + s^2 C_ii / 2),   E[L_g] = sum_{i in g} a_i,
+                                  Cov(L_g, L_h) = sum_{i in g, j in h} a_i a_j expm1(s^2 C_ij)
+    standard (c = s f + t):       E[L_g] = sum_{i in g} w_i (s mu_i + t),  Cov(L_g, L_h) = s^2 sum w_i w_j C_ij
+
+computed on the device by ``dgp_period_moments`` straight from the covariance ``dgp_posterior_cov`` writes: no
+factorisation, no draws, no sampling noise.  The pipelines' clip of the data-space value (at 1e-6 for the log transform,
+at 0 for the standard one) is not part of these moments; it only matters where the posterior puts mass below the clip.
+"""
+from __future__ import annotations
+
+import re
+import warnings
+
+import numpy as np
+import pandas as pd
+import torch
+from scipy.stats import norm
+
+from . import pipeline as _pl
+from .backend import MODE_LINEAR, MODE_LOG
+from .gp.lowering import lower
+from .xr_compat import Dataset
+
+DEFAULT_MAX_BYTES = 16 * 2 ** 30  # device bytes per batch of sites in aggregate_many (posterior covariances + plan)
+
+
+# ---------------------------------------------------------------------------------------------------- grouping
+def _period_freq(freq: str) -> str:
+    """Resample alias -> period alias: "YE" -> "Y", "YE-SEP" -> "Y-SEP", "QE" -> "Q", "ME" -> "M"."""
+    return re.sub(r"^([YQM])E(?=$|-)", r"\1", freq)
+
+
+def period_groups(time, weights, freq: str = "YE"):
+    """Group the points by calendar period like ``resample(time=freq).sum()``.
+
+    -> (order, groups, labels, n_points, n_dropped): ``order`` sorts the points by period (stable), ``groups`` are the
+    int32 period ids of the sorted points (non-decreasing; -1 for a point whose weight or time is not finite -- the
+    resampled sum skips NaN), ``labels`` the period-end dates (every period from the first to the last, empty ones
+    included), ``n_points`` the points per period and ``n_dropped`` the points left out."""
+    t = pd.DatetimeIndex(np.asarray(time).reshape(-1).astype("datetime64[ns]"))
+    w = np.asarray(weights, dtype=np.float64).reshape(-1)
+    if w.shape[0] != len(t):
+        raise ValueError(f"{w.shape[0]} weights for {len(t)} points")
+    valid = np.isfinite(w) & ~t.isna()
+    if not valid.any():
+        raise ValueError("no point has a finite weight and time")
+    pfreq = _period_freq(freq)
+    ordinal = np.zeros(len(t), dtype=np.int64)
+    ordinal[valid] = t[valid].to_period(pfreq).asi8
+    first, last = ordinal[valid].min(), ordinal[valid].max()
+    ids = np.where(valid, ordinal - first, -1)
+    order = np.argsort(np.where(valid, ids, -1), kind="stable")
+    groups = ids[order].astype(np.int32)
+    P = int(last - first + 1)
+    labels = pd.period_range(start=pd.Period(ordinal=int(first), freq=pfreq), periods=P, freq=pfreq)
+    labels = labels.to_timestamp(how="end").normalize().to_numpy().astype("datetime64[ns]")
+    n_points = np.bincount(groups[groups >= 0], minlength=P)
+    return order, groups, labels, n_points, int((~valid).sum())
+
+
+def _kept(order, groups, labels, n_points, dropped):
+    """``period_groups`` without the excluded points: their covariates may be missing too (a NaN flow is both the
+    weight and a model input), so they are not evaluated at all."""
+    keep = groups >= 0
+    return order[keep], groups[keep], labels, n_points, dropped
+
+
+def target_transform(dm):
+    """(mode, s, t) of a fitted target pipeline: ``log`` + ``scaler`` steps -> log mode, ``StandardPipeline`` -> linear
+    mode; anything else raises ``NotImplementedError``."""
+    pipe = dm.target_pipeline
+    steps = dict(getattr(pipe, "steps", []))
+    names = [name for name, _ in getattr(pipe, "steps", [])]
+    scaler = steps.get("scaler")
+    if not isinstance(scaler, _pl.StandardScaler):
+        raise NotImplementedError(f"period moments need a standardised target, not {type(pipe).__name__}")
+    s = float(np.asarray(scaler.scale_).reshape(-1)[0]) if scaler.with_std else 1.0
+    t = float(np.asarray(scaler.mean_).reshape(-1)[0]) if scaler.with_mean else 0.0
+    if names == ["metadata", "clip", "log", "scaler"]:
+        return MODE_LOG, s, t
+    if isinstance(pipe, _pl.StandardPipeline):
+        return MODE_LINEAR, s, t
+    raise NotImplementedError(f"period moments are exact for the log and standard transforms only, not {type(pipe).__name__}")
+
+
+def intervals(mode, mean, var, ci=0.95):
+    """Approximate central ``ci`` intervals from exact moments: a lognormal with the same mean and variance
+    (Fenton-Wilkinson) for log-mode sums of lognormals, the normal for linear-mode sums."""
+    lo_q, hi_q = (1 - ci) / 2, 1 - (1 - ci) / 2
+    mean, var = np.asarray(mean, dtype=np.float64), np.clip(np.asarray(var, dtype=np.float64), 0.0, None)
+    if mode == MODE_LINEAR:
+        se = np.sqrt(var)
+        return mean + norm.ppf(lo_q) * se, mean + norm.ppf(hi_q) * se
+    with np.errstate(divide="ignore", invalid="ignore"):
+        sig2 = np.log1p(var / mean ** 2)
+        mu_ln = np.log(mean) - sig2 / 2
+        lower = np.exp(mu_ln + norm.ppf(lo_q) * np.sqrt(sig2))
+        upper = np.exp(mu_ln + norm.ppf(hi_q) * np.sqrt(sig2))
+    pos = mean > 0
+    return np.where(pos, lower, mean), np.where(pos, upper, mean)
+
+
+def _dataset(mode, mean, cov, labels, n_points, attrs, ci):
+    var = np.clip(np.diagonal(cov), 0.0, None)
+    lower, upper = intervals(mode, mean, var, ci)
+    attrs = dict(attrs)
+    return Dataset(
+        {
+            "mean": ("time", mean, attrs),
+            "se": ("time", np.sqrt(var), attrs),
+            "lower": ("time", lower, dict(attrs, ci=ci)),
+            "upper": ("time", upper, dict(attrs, ci=ci)),
+            "n_points": ("time", n_points),
+        },
+        coords={"time": labels},
+        attrs=attrs,
+    )
+
+
+def _target_attrs(dm):
+    meta = dict(getattr(dm.target_pipeline, "steps", [])).get("metadata")
+    return dict(getattr(meta, "attrs_", {}) or {})
+
+
+# ---------------------------------------------------------------------------------------------------- one site
+def aggregate(model, covariates, weights, freq="YE", ci=0.95, pred_noise=False, return_cov=False, attrs=None):
+    """``MarginalHIP.aggregate``: exact mean / covariance of sum_{i in period} w_i c_i over the points of
+    ``covariates`` (c = the model's target in data space), one ``dgp_posterior_cov`` + one ``dgp_period_moments``."""
+    mode, s, t = target_transform(model.dm)
+    order, groups, labels, n_points, _dropped = _kept(*period_groups(covariates.coords["time"].values, np.asarray(weights), freq))
+    w = np.asarray(weights, dtype=np.float64).reshape(-1)[order]
+    Xnew = torch.tensor(model.dm.Xnew(covariates), dtype=model.dtype)[torch.as_tensor(order)].to(model.device).contiguous()
+    m = Xnew.shape[0]
+    model._device_ready()
+    model.model.eval()
+    model.likelihood.eval()
+    with torch.no_grad():
+        if hasattr(model.model, "prepare_eval"):
+            model.model.prepare_eval(model._train_x, Xnew)
+        model._ensure_factor()
+        kmean, cov = model._plan.posterior_cov(model._factor_theta, Xnew)
+        mu = kmean + model.model.prior_mean(Xnew)
+        extra = model.likelihood.predictive_noise(m, Xnew.device, model.dtype) if pred_noise else None
+        mean_d, cov_d = model._plan.period_moments(cov, m, (s * mu + t).contiguous(), s * s, w, groups, len(labels),
+                                                   mode, extra_var=extra)
+    mean, pcov = mean_d.cpu().numpy(), cov_d.cpu().numpy()
+    ds = _dataset(mode, mean, pcov, labels, n_points, _target_attrs(model.dm) if attrs is None else attrs, ci)
+    return (ds, pcov) if return_cov else ds
+
+
+# ---------------------------------------------------------------------------------------------------- many sites
+def _site_bytes(n, m, esz):
+    N, M = -(-n // 128) * 128, -(-m // 128) * 128
+    return esz * (M * M + 2 * N * M + 3 * N * N) + 8 * M * 8
+
+
+def aggregate_many(models, covariates_list, weights_list, freq="YE", ci=0.95, pred_noise=False, return_cov=False,
+                   max_bytes: int = DEFAULT_MAX_BYTES, attrs_list=None):
+    """``aggregate`` for many fitted sites (different n and m allowed) like ``multisite_fit.predict_many``: per batch of
+    sites ONE batched plan, one batched ``dgp_factorize``, one batched ``dgp_posterior_cov`` and one
+    ``dgp_period_moments`` launch (gridDim.z = sites); pad points carry group -1.  Sites are cut into consecutive
+    batches whose device footprint -- B x (M^2 + 2 N M + 3 N^2) elements for the covariances, the cross terms and the
+    plan -- stays under ``max_bytes`` (default 16 GiB; one site at m = 11 323 already needs 1 GB for its covariance)."""
+    from .backend import GPPlan
+    from . import _lib
+
+    if not (len(models) == len(covariates_list) == len(weights_list)) or not models:
+        raise ValueError("aggregate_many needs one covariates object and one weight vector per model")
+    for mdl in models:
+        if not mdl.is_fitted:
+            raise RuntimeError("The model hasn't been fitted yet, call .fit().")
+    dtype, device = models[0].dtype, torch.device(models[0].device)
+    esz = torch.empty((), dtype=dtype).element_size()
+    sites = []
+    with torch.no_grad():
+        for b, (mdl, cov, wts) in enumerate(zip(models, covariates_list, weights_list)):
+            mdl.model.eval()
+            mdl.likelihood.eval()
+            mode, s, t = target_transform(mdl.dm)
+            order, groups, labels, n_points, _ = _kept(*period_groups(cov.coords["time"].values, np.asarray(wts), freq))
+            w = np.asarray(wts, dtype=np.float64).reshape(-1)[order]
+            x = torch.tensor(mdl.dm.X, dtype=dtype)
+            xn = torch.tensor(mdl.dm.Xnew(cov), dtype=dtype)[torch.as_tensor(order)]
+            if hasattr(mdl.model, "prepare_eval"):
+                mdl.model.prepare_eval(x, xn)
+            name, theta_fn = lower(mdl.model.covar_module, x.shape[1])
+            sites.append(dict(mode=mode, s=s, t=t, groups=groups, labels=labels, n_points=n_points, w=w, x=x, xn=xn,
+                              y=torch.tensor(mdl.dm.y, dtype=dtype), name=(name, x.shape[1]),
+                              theta=theta_fn().detach().to(torch.float64), prior=mdl.model.prior_mean(x).detach().to(dtype),
+                              noise=mdl.likelihood.train_noise(torch.device("cpu"), dtype).detach().reshape(-1),
+                              xmean=mdl.model.prior_mean(xn).detach().to(dtype),
+                              extra=(mdl.likelihood.predictive_noise(xn.shape[0], torch.device("cpu"), dtype)
+                                     if pred_noise else None)))
+    if len({st["name"] for st in sites}) != 1 or len({st["mode"] for st in sites}) != 1:
+        raise ValueError("aggregate_many needs sites of one model family, one input dimension and one target transform")
+    batches, cur, n_max, m_max = [], [], 0, 0
+    for b, st in enumerate(sites):
+        n2, m2 = max(n_max, st["x"].shape[0]), max(m_max, st["xn"].shape[0])
+        if cur and (len(cur) + 1) * _site_bytes(n2, m2, esz) > max_bytes:
+            batches.append(cur)
+            cur, n2, m2 = [], st["x"].shape[0], st["xn"].shape[0]
+        cur.append(b)
+        n_max, m_max = n2, m2
+    batches.append(cur)
+
+    results = [None] * len(sites)
+    for idx in batches:
+        group = [sites[b] for b in idx]
+        B = len(group)
+        (name, d), mode = group[0]["name"], group[0]["mode"]
+        sizes, msizes = [st["x"].shape[0] for st in group], [st["xn"].shape[0] for st in group]
+        n, mm = max(sizes), max(msizes)
+        plan = GPPlan(name, n, d, dtype=dtype, device=device, lookahead=1 if B > 1 else 2, batch=B)
+        if B > 1:
+            plan.set_site_sizes(sizes)
+
+        def slots(ts, width, fill=0.0, dt=dtype):
+            out = torch.full((B, width) + tuple(ts[0].shape[1:]), fill, dtype=dt)
+            for k, v in enumerate(ts):
+                out[k, : v.shape[0]] = torch.as_tensor(v, dtype=dt)
+            return out
+
+        X = slots([st["x"] for st in group], n).to(device).contiguous()
+        R = slots([st["y"] - st["prior"] for st in group], n).to(device).contiguous()
+        Nz = slots([st["noise"] for st in group], n, 1.0).to(device).contiguous()
+        Xs = torch.stack([torch.cat([st["xn"], st["xn"][-1:].expand(mm - st["xn"].shape[0], -1)]) for st in group])
+        Xs = Xs.to(device).contiguous()
+        theta = torch.stack([st["theta"] for st in group])
+        single = B == 1
+        one = (lambda v: v[0].contiguous()) if single else (lambda v: v)
+        with torch.no_grad():
+            plan.set_inputs(one(X))
+            out = plan.factorize(one(theta), one(R), one(Nz))
+            info = out.reshape(B, -1)[:, _lib.OUT_INFO].cpu()
+            if bool((info != 0).any()):
+                bad = int(torch.nonzero(info)[0])
+                raise RuntimeError(f"site {idx[bad]}: matrix not positive definite (Cholesky pivot {int(info[bad])})")
+            kmean, cov = plan.posterior_cov(one(theta), one(Xs))
+            mu = kmean.reshape(B, mm) + slots([st["xmean"] for st in group], mm).to(device)
+            sv = torch.tensor([st["s"] for st in group], dtype=dtype, device=device)
+            tv = torch.tensor([st["t"] for st in group], dtype=dtype, device=device)
+            mapped = (sv[:, None] * mu + tv[:, None]).contiguous()
+            W = slots([st["w"] for st in group], mm, dt=torch.float64)
+            G = slots([st["groups"] for st in group], mm, -1, dt=torch.int32)
+            EV = slots([st["extra"] for st in group], mm).to(device).contiguous() if pred_noise else None
+            P = max(len(st["labels"]) for st in group)
+            mean_d, cov_d = plan.period_moments(cov, mm, one(mapped), (sv.double() ** 2).cpu(), one(W), one(G), P, mode,
+                                                extra_var=one(EV) if EV is not None else None)
+        mean_h, cov_h = mean_d.reshape(B, P).cpu().numpy(), cov_d.reshape(B, P, P).cpu().numpy()
+        del plan, cov
+        for k, b in enumerate(idx):
+            st = sites[b]
+            p = len(st["labels"])
+            attrs = _target_attrs(models[b].dm) if attrs_list is None else attrs_list[b]
+            ds = _dataset(mode, mean_h[k, :p], cov_h[k, :p, :p], st["labels"], st["n_points"], attrs, ci)
+            results[b] = (ds, cov_h[k, :p, :p].copy()) if return_cov else ds
+    return results
+
+
+# ---------------------------------------------------------------------------------------------------- loads
+def flux_weights(covariates, concentration_attrs):
+    """w_i = Q_i dt 1e-3 (flow in m^3/s, dt in s, mg/l -> kg) for a regular time grid, with ``concentration_to_flux``'s
+    unit warnings; an irregular grid raises ``ValueError``."""
+    time = np.asarray(covariates.coords["time"].values).astype("datetime64[ns]")
+    dt = np.unique(np.diff(time).astype("timedelta64[ns]").astype(np.int64)) / 1e9
+    if len(dt) != 1:
+        raise ValueError("annual_flux needs a regular time grid (one constant time step)")
+    flow = covariates["flow"]
+    if getattr(flow, "attrs", {}).get("units") != "cubic meters per second":
+        warnings.warn("Check that flow is 'cubic meters per second'. Set flow.units = 'cubic meters per second' to silence.",
+                      UserWarning, stacklevel=3)
+    if "mg/l" not in str(concentration_attrs.get("units", "")):
+        warnings.warn("Check that concentration is in 'mg/l'. Set concentration.units = 'mg/l' to silence.",
+                      UserWarning, stacklevel=3)
+    return np.asarray(flow.values, dtype=np.float64).reshape(-1) * dt[0] * 1e-3
+
+
+def _flux_attrs(model):
+    attrs = _target_attrs(model.dm)
+    attrs["units"] = "kilograms"
+    attrs["standard_name"] = "flux"
+    return attrs
+
+
+def annual_flux(model, covariates, freq="YE", ci=0.95, pred_noise=False, return_cov=False):
+    """``LoadestGP.annual_flux``: exact period loads (kg) and their uncertainty."""
+    w = flux_weights(covariates, _target_attrs(model.dm))
+    return aggregate(model, covariates, w, freq=freq, ci=ci, pred_noise=pred_noise, return_cov=return_cov,
+                     attrs=_flux_attrs(model))
+
+
+def annual_flux_many(models, covariates_list, freq="YE", ci=0.95, pred_noise=False, return_cov=False,
+                     max_bytes: int = DEFAULT_MAX_BYTES):
+    """``annual_flux`` for many sites through ``aggregate_many`` (batched device work, byte-budgeted batches)."""
+    weights = [flux_weights(cov, _target_attrs(m.dm)) for m, cov in zip(models, covariates_list)]
+    return aggregate_many(models, covariates_list, weights, freq=freq, ci=ci, pred_noise=pred_noise, return_cov=return_cov,
+                          max_bytes=max_bytes, attrs_list=[_flux_attrs(m) for m in models])
+
+
+__all__ = ["aggregate", "aggregate_many", "annual_flux", "annual_flux_many", "period_groups", "target_transform",
+           "intervals", "DEFAULT_MAX_BYTES"]

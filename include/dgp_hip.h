@@ -214,6 +214,29 @@ int dgp_posterior_cov(dgp_plan* plan, const double* theta_host, const void* Xs_d
 int dgp_sample_draws(int dtype, const void* L_dev, int64_t m, const void* Z_dev, int64_t ndraw, const void* mean_dev,
                      void* out_dev, void* stream);
 
+/* Exact mean and covariance of PERIOD SUMS of a transformed posterior -- annual / monthly loads with their uncertainty,
+ * which the reference estimates by Monte Carlo: sample() (engines/gpytorch.py:551-593) -> concentration_to_flux
+ * (src/loadest_gp/utils.py:14-56) -> flux.resample(time="YE").sum() (utils.py:59-103).  With f ~ N(mu, C) per site,
+ * s2 = s^2, the mean mu_dev ALREADY mapped (mu_i <- s mu_i + t) and c_i the data-space value:
+ *   mode 1 (log,    c_i = exp(s f_i + t)):  a_i = w_i exp(mu_i + s2 C_ii / 2)
+ *            mean[g] = sum_{i in g} a_i          cov[g][h] = sum_{i in g, j in h} a_i a_j expm1(s2 C_ij)
+ *   mode 0 (linear, c_i = s f_i + t):       mean[g] = sum_{i in g} w_i mu_i   cov[g][h] = s2 sum_{i in g, j in h} w_i w_j C_ij
+ * cov_dev    `dtype` elements, per site M x M (M = dgp_padded_n(m)) at stride M M: exactly what dgp_posterior_cov writes; only
+ *            the lower triangle (j <= i) is read; accumulation is in double;
+ * mu_dev     batch x m, `dtype`;  scale2_dev: batch doubles (s^2);  w_dev: batch x m doubles;
+ * group_dev  batch x m int32 group ids in 0 .. ngroups-1, NON-DECREASING along the points except for -1 (excluded) anywhere
+ *            (a violation gives wrong numbers, never an access out of bounds);
+ * extra_var_dev  NULL or batch x m `dtype`, added to C_ii (predictive noise);
+ * mean_out_dev   batch x ngroups doubles;  cov_out_dev  batch x ngroups x ngroups doubles (exactly symmetric).
+ * work_dev: dgp_period_moments_workspace_bytes(m, ngroups, batch) bytes (m P + 2 m doubles per site; 0 for bad sizes).
+ * Four launches (gridDim.z = batch); no floating-point atomics: bitwise repeatable, and a site's result does not depend on
+ * the batch it is in.  Needs no plan. */
+size_t dgp_period_moments_workspace_bytes(int64_t m, int ngroups, int batch);
+int dgp_period_moments(int dtype, int mode, const void* cov_dev, int64_t m, int batch, const void* mu_dev,
+                       const double* scale2_dev, const double* w_dev, const int32_t* group_dev, int ngroups,
+                       const void* extra_var_dev, void* work_dev, size_t work_bytes, double* mean_out_dev,
+                       double* cov_out_dev, void* stream);
+
 /* Predictive mean only, and its vector-Jacobian product -- what the rating-gp monotonicity penalty
  * differentiates (src/rating_gp/models/gpytorch.py:130-187: mean of likelihood(model(x_grid)) with grad).
  *   dgp_predict_mean : mean_dev[j] = K(x*_j, X) alpha                                  (m entries)
