@@ -311,6 +311,58 @@ class GPPlan:
         with torch.cuda.device(self.device):
             return period_moments(cov, m, mu, scale2, w, groups, ngroups, mode, extra_var)
 
+    def posterior_period_moments(self, theta, Xs: torch.Tensor, mu, scale2, w, groups, ngroups: int, mode: int, extra_var=None):
+        """``period_moments`` of the posterior at Xs straight from the held factorisation (``dgp_posterior_period_moments``):
+        the (M, M) covariance is never formed.  Xs (m, d) -- (batch, m, d) for a batched plan, theta (batch, ntheta) --; the
+        other arguments as for ``period_moments``.  The work area (2 N M plan-dtype elements + M P doubles per site) is kept
+        between calls; a ``RuntimeError`` names its bytes when it exceeds the free device memory."""
+        lead = () if self.batch == 1 else (self.batch,)
+        if not (torch.is_tensor(Xs) and Xs.is_cuda and Xs.dtype == self.dtype and Xs.dim() == 2 + len(lead)
+                and Xs.shape[-1] == self.d and tuple(Xs.shape[:-2]) == lead):
+            raise ValueError(f"Xs must be a {lead + ('m', self.d)} {self.dtype} CUDA tensor")
+        th = _theta_array(theta, self.ntheta * self.batch)
+        m, P = int(Xs.shape[-2]), int(ngroups)
+        need = int(self.lib.dgp_posterior_period_moments_workspace_bytes(self._h, m, P))
+        if need == 0:
+            raise ValueError(f"bad size: m = {m}, ngroups = {P} (1 <= m <= 2^20, 1 <= ngroups <= 65535)")
+        dev = self.device
+
+        def vec(t, name, dtype):
+            if t is None:
+                return None
+            t = torch.as_tensor(t).to(dev, dtype).contiguous()
+            if tuple(t.shape) != lead + (m,):
+                raise ValueError(f"{name} must have shape {lead + (m,)}")
+            return t
+
+        with torch.cuda.device(dev):
+            mu_t, w_t = vec(mu, "mu", self.dtype), vec(w, "w", torch.float64)
+            g_t, ev_t = vec(groups, "groups", torch.int32), vec(extra_var, "extra_var", self.dtype)
+            s2 = torch.as_tensor(scale2, dtype=torch.float64).reshape(-1).to(dev).contiguous()
+            if s2.numel() != self.batch:
+                raise ValueError(f"scale2 must hold {self.batch} value(s)")
+            ws = getattr(self, "_ppm_ws", None)
+            if ws is None or ws.numel() < need + 256:
+                self._ppm_ws = None
+                del ws  # (its bytes return to torch's cache, which counts as free here)
+                free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+                if need + 256 > free:
+                    raise RuntimeError(f"dgp_posterior_period_moments needs a work area of {need} bytes; "
+                                       f"{free} bytes of device memory are free")
+                ws = self._ppm_ws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
+            base = ws.data_ptr()
+            base += (-base) % 256
+            xs = Xs.contiguous()
+            mean_out = torch.empty(lead + (P,), dtype=torch.float64, device=dev)
+            cov_out = torch.empty(lead + (P, P), dtype=torch.float64, device=dev)
+            _lib.check(
+                self.lib.dgp_posterior_period_moments(self._h, th, _ptr(xs), m, int(mode), _ptr(mu_t), _ptr(s2), _ptr(w_t), _ptr(g_t), P,
+                                                      _ptr(ev_t) if ev_t is not None else None, C.c_void_p(base), need,
+                                                      _ptr(mean_out), _ptr(cov_out), _stream()),
+                "dgp_posterior_period_moments",
+            )
+        return mean_out, cov_out
+
     def _vjp_workspace(self, m):
         need = int(self.lib.dgp_mean_vjp_workspace_bytes(self._h, m))
         ws = getattr(self, "_vjp_ws", None)

@@ -16,16 +16,35 @@
 //   reduce  one workgroup per (64 columns h, group g): cov_gh = sum_{i in g} a_i Y[i][h] for h >= g, written to both
 //           (g, h) and (h, g) -- the output is exactly symmetric; mean_g beside it.
 // Every sum runs in a fixed order, so results are bitwise repeatable and a site's numbers do not depend on its batch.
+//
+// dgp_posterior_period_moments: the same moments with C = K(Xs, Xs) - V^T V (V = L^-1 K(X, Xs), left in the work area by the
+// prediction's first stages) folded in tile by tile and never stored.  The rows pass is replaced by ppm_rows_kernel:
+//   one workgroup per (128-row block I, group h) -- a block whose rows all lie in groups above h (excluded rows included)
+//   writes zeros to Y[., h] and leaves: the reduce pass only needs Y[i][h] for h >= g(i), and reads the rest times a_i = 0 --
+//   looping over h's 64-column tiles J in ascending order:
+//     acc = V_I^T V_J   (the tile-GEMM core of posterior_cov_kernel, TileGemm, on 128 x 64 tiles: 64 accumulator registers
+//                        per lane, so that the per-entry epilogue below fits beside them at two workgroups per CU without
+//                        spilling -- on 128 x 128 tiles the 128 accumulators left too little room in fp64)
+//     per 16 x 16 sub-tile of acc: C_ij = k(x_i, x_j) - acc_ij (+ extra_var_i on the diagonal), a_j phi(C_ij) for the
+//     columns j of group h (a select: anything else -- pad, excluded, other groups -- adds an exact zero), summed over
+//     the sub-tile's columns by a fixed butterfly, then over the two wave columns and the tiles J in order.
+//   k(x_i, x_j) is gram_sym_kernel's evaluation (per-point features in LDS, the model's pair<false>); the row strip stays
+//   in LDS for the whole loop, the column strip of each J goes into the operand tiles the k-loop has just finished with.
+// Visits about m^2 / 2 (1 + 1/P) entries, 2 N flop each on the MFMA pipe; no floating-point atomics.
 #include <climits>
 
 #include "dgp_common.h"
+#include "dgp_gemm_dma.h"
+#include "dgp_gram_shared.h"
 #include "dgp_internal.h"
+#include "dgp_models.h"
 
 namespace dgp {
 
 namespace {
 
 constexpr int PM_ROWS = 128;  // rows of a workgroup of the rows pass (== DGP_TILE_HOST, the cov buffer's block size)
+constexpr int PM_COLS = 64;   // columns of a tile of the streamed rows pass (ppm_rows_kernel)
 
 // per-site work area, in doubles: a[M], mean term[M], Y[M x P], then 2 P ints (group start / end)
 __host__ __device__ inline long pm_site_doubles(long M, int P) { return 2 * M + M * (long)P + P; }
@@ -58,11 +77,13 @@ __global__ __launch_bounds__(256) void pm_init_kernel(double* work, long ws, lon
   se[2 * g + 1] = 0;
 }
 
+// C_jj of site z sits at diag[z dsite + j dstep]: the diagonal of the dense covariance (dsite = M M, dstep = M + 1), or the
+// predicted variance the streamed pass finds in its work area (dsite = that area's site stride, dstep = 1)
 template <typename T, int MODE>
-__global__ __launch_bounds__(256) void pm_prep_kernel(const T* __restrict__ cov, long M, int m, int P, const T* __restrict__ mu,
-                                                      const double* __restrict__ scale2, const double* __restrict__ w,
-                                                      const int* __restrict__ group, const T* __restrict__ ev, double* work,
-                                                      long ws) {
+__global__ __launch_bounds__(256) void pm_prep_kernel(const T* __restrict__ diag, long dsite, long dstep, long M, int m, int P,
+                                                      const T* __restrict__ mu, const double* __restrict__ scale2,
+                                                      const double* __restrict__ w, const int* __restrict__ group,
+                                                      const T* __restrict__ ev, double* work, long ws) {
   const long j = (long)blockIdx.x * 256 + threadIdx.x;
   const int z = blockIdx.z;
   if (j >= M) return;
@@ -76,7 +97,7 @@ __global__ __launch_bounds__(256) void pm_prep_kernel(const T* __restrict__ cov,
     if (g >= 0 && g < P) {
       const double wj = w[k], muj = (double)mu[k];
       if constexpr (MODE == 1) {
-        double cjj = (double)cov[(long)z * M * M + j * M + j];
+        double cjj = (double)diag[(long)z * dsite + j * dstep];
         if (ev) cjj += (double)ev[k];
         av = wj * exp(muj + 0.5 * scale2[z] * cjj);
         amv = av;
@@ -183,13 +204,159 @@ __global__ __launch_bounds__(256) void pm_reduce_kernel(long M, int P, const dou
   }
 }
 
+// Workgroups per CU the streamed rows kernel is compiled for: two, except for the two fp64 evaluators whose covariance
+// evaluation is too large for the registers two workgroups leave beside the accumulators (measured at two: rating 84 bytes
+// of scratch per lane, loadest d = 6 12 bytes) -- they get one, and the register file of a whole SIMD, instead of spilling.
+template <typename T, typename Mod>
+struct PpmOcc {
+  static constexpr int value = 2;
+};
+template <>
+struct PpmOcc<double, Rating<double>> {
+  static constexpr int value = 1;
+};
+template <>
+struct PpmOcc<double, Loadest<double, 6>> {
+  static constexpr int value = 1;
+};
+
+// Y[i][h] = sum_{j in h} a_j phi(C_ij), C = K(Xs, Xs) - V^T V from V (N x Mp, site stride wbs) and the test points' SoA
+// coordinates Xst (d x Mp, same stride); see the file header.
+template <typename T, typename Mod, int MODE>
+__global__ __launch_bounds__(256, (PpmOcc<T, Mod>::value)) void ppm_rows_kernel(const T* __restrict__ V, long N, long Mp, int m, int P,
+                                                          const T* __restrict__ Xst, long wbs, const PreBatch<Mod> pb,
+                                                          const double* __restrict__ scale2, const int* __restrict__ group,
+                                                          const T* __restrict__ ev, double* __restrict__ work, long ws) {
+  using K = TileCore<T, false, false, PM_ROWS, PM_COLS>;  // the register-staged core (TileGemm) on 128 x 64 tiles
+  using G = typename K::G;
+  static_assert(!K::DMA && G::MI == 4 && G::NI == 2, "128 x 64 tile, 2 x 2 waves of 64 x 32");
+  static_assert(Mod::NF * PM_COLS * sizeof(T) + PM_COLS * sizeof(double) <= K::SMEM_ELEMS * sizeof(T),
+                "the column strip does not fit the operand tiles");
+  const int rb = blockIdx.x, h = blockIdx.y, z = blockIdx.z;
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int r0 = rb * PM_ROWS;
+  const int* gz = group + (long)z * m;
+  exp_table_init<T>();
+  // rows of this block in a group <= h: otherwise no entry of Y[., h] here is ever read (the barrier also publishes the table)
+  int need = 0;
+  if (t < PM_ROWS && r0 + t < m) {
+    const int g = gz[r0 + t];
+    need = g >= 0 && g <= h;
+  }
+  double* base = work + (long)z * ws;
+  const double* a = base;
+  double* Y = base + 2 * Mp;
+  if (!__syncthreads_or(need)) {
+    // The reduce pass reads Y[i][h] for every i in a group's column range, excluded points included (a_i = 0 there): a
+    // block of excluded points inside a range -- a gap of 128 or more -- must still leave numbers, not the work area's past
+    if (t < PM_ROWS && r0 + t < m) Y[(long)(r0 + t) * P + h] = 0.0;
+    return;
+  }
+
+  __shared__ __attribute__((aligned(16))) T smem[K::SMEM_ELEMS];
+  __shared__ T sfi[Mod::NF][PM_ROWS];
+  __shared__ double red[2][PM_ROWS];
+  V = site(V, wbs);
+  Xst = site(Xst, wbs);
+  int c0, c1;
+  pm_range((const int*)(base + 2 * Mp + Mp * (long)P), h, c0, c1);
+  const T* evz = ev ? ev + (long)z * m : nullptr;
+  const double s2 = scale2[z];
+  const typename Mod::Pre& pre = pb.get();
+  if (t < PM_ROWS) {
+    T x[Mod::NX], f[Mod::NF];
+#pragma unroll
+    for (int c = 0; c < Mod::NX; ++c) x[c] = Xst[(long)c * Mp + r0 + t];
+    Mod::features(x, pre, f);
+#pragma unroll
+    for (int c = 0; c < Mod::NF; ++c) sfi[c][t] = f[c];
+  }
+  // (the first barrier of the k-loop publishes the row strip)
+  T(*sfj)[PM_COLS] = reinterpret_cast<T(*)[PM_COLS]>(smem);
+  double* saj = reinterpret_cast<double*>(smem + Mod::NF * PM_COLS);
+  const int wm = (w >> 1) * (PM_ROWS / 2), wn = (w & 1) * (PM_COLS / 2);
+  double racc = 0.0;  // thread t < 128: row r0 + t
+  T dummy[Mod::NTHETA];
+  for (int jb = c0 / PM_COLS; jb * PM_COLS < c1; ++jb) {
+    typename G::acc_t acc[G::MI][G::NI];
+    G::zero(acc);
+    K::run(V + r0, Mp, V + (long)jb * PM_COLS, Mp, (int)(N / 16), smem, acc);
+    __syncthreads();  // every wave is done with the operand tiles
+    if (t < PM_COLS) {
+      const int j = jb * PM_COLS + t;
+      T x[Mod::NX], f[Mod::NF];
+#pragma unroll
+      for (int c = 0; c < Mod::NX; ++c) x[c] = Xst[(long)c * Mp + j];
+      Mod::features(x, pre, f);
+#pragma unroll
+      for (int c = 0; c < Mod::NF; ++c) sfj[c][t] = f[c];
+      saj[t] = (j < m && gz[j] == h) ? a[j] : 0.0;
+    }
+    __syncthreads();
+    // One entry at a time, features from LDS per entry.  The loops over the 16-row groups, a group's sub-tiles and a lane's
+    // four entries of a sub-tile stay rolled: the next group / sub-tile / entry is rotated to the front (register moves), so
+    // that the accumulators and the four row sums keep constant indices and only ONE covariance evaluation is in flight --
+    // unrolled, the compiler interleaves several and spills in fp64 (measured: 172-408 bytes per lane with four in flight).
+#pragma unroll 1
+    for (int mi = 0; mi < G::MI; ++mi) {
+      typename G::acc_t row[G::NI];  // this 16-row group's sub-tiles; the later groups move up
+#pragma unroll
+      for (int k = 0; k < G::NI; ++k) row[k] = acc[0][k];
+#pragma unroll
+      for (int q = 0; q + 1 < G::MI; ++q)
+#pragma unroll
+        for (int k = 0; k < G::NI; ++k) acc[q][k] = acc[q + 1][k];
+      dgp_d4 part = {0.0, 0.0, 0.0, 0.0};  // the row sums of this lane's four rows r, rotated with the entries
+#pragma unroll 1
+      for (int ni = 0; ni < G::NI; ++ni) {
+        typename G::acc_t cur = row[0];
+#pragma unroll
+        for (int k = 0; k + 1 < G::NI; ++k) row[k] = row[k + 1];
+        const int cj = wn + ni * 16 + (lane & 15);
+        const long gj = (long)jb * PM_COLS + cj;
+        T fj[Mod::NF];
+#pragma unroll
+        for (int c = 0; c < Mod::NF; ++c) fj[c] = sfj[c][cj];
+        const double aj = saj[cj];
+#pragma unroll 1
+        for (int r = 0; r < 4; ++r) {
+          const double vr = (double)cur[0];
+          cur = cur.yzwx;
+          const int ri = wm + mi * 16 + Mfma<T>::crow(lane, r);
+          const long gi = (long)r0 + ri;
+          T fi[Mod::NF];
+#pragma unroll
+          for (int c = 0; c < Mod::NF; ++c) fi[c] = sfi[c][ri];
+          double cij = (double)Mod::template pair<false>(fi, fj, pre, T(0), dummy) - vr;
+          if (gi == gj && evz && gi < m) cij += (double)evz[gi];
+          const double v = aj * pm_phi<MODE>(s2, cij);
+          part.x += aj != 0.0 ? v : 0.0;
+          part = part.yzwx;  // four rotations per sub-tile: back in row order
+        }
+      }
+      // the 16 columns of the sub-tile (lanes of one lane >> 4 group), a fixed butterfly
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        double pr = part[r];
+#pragma unroll
+        for (int off = 1; off < 16; off <<= 1) pr += __shfl_xor(pr, off, 64);
+        if ((lane & 15) == 0) red[w & 1][wm + mi * 16 + Mfma<T>::crow(lane, r)] = pr;
+      }
+    }
+    __syncthreads();
+    if (t < PM_ROWS) racc += red[0][t] + red[1][t];
+    // (the next tile's k-loop starts with a barrier before anything rewrites the operand tiles or red)
+  }
+  if (t < PM_ROWS && r0 + t < m) Y[(long)(r0 + t) * P + h] = gz[r0 + t] >= 0 ? racc : 0.0;
+}
+
 template <typename T, int MODE>
 int period_moments_mode(const T* cov, long M, int m, int B, const T* mu, const double* scale2, const double* w,
                         const int* group, int P, const T* ev, double* work, double* mean_out, double* cov_out, hipStream_t s) {
   const long ws = pm_site_doubles(M, P);
   pm_init_kernel<<<dim3((unsigned)((P + 255) / 256), 1, (unsigned)B), 256, 0, s>>>(work, ws, M, P);
-  pm_prep_kernel<T, MODE><<<dim3((unsigned)((M + 255) / 256), 1, (unsigned)B), 256, 0, s>>>(cov, M, m, P, mu, scale2, w, group,
-                                                                                          ev, work, ws);
+  pm_prep_kernel<T, MODE><<<dim3((unsigned)((M + 255) / 256), 1, (unsigned)B), 256, 0, s>>>(cov, M * M, M + 1, M, m, P, mu, scale2,
+                                                                                          w, group, ev, work, ws);
   pm_rows_kernel<T, MODE><<<dim3((unsigned)(M / PM_ROWS), (unsigned)P, (unsigned)B), 256, 0, s>>>(cov, M, m, P, scale2, ev, work, ws);
   pm_reduce_kernel<<<dim3((unsigned)((P + 63) / 64), (unsigned)P, (unsigned)B), 256, 0, s>>>(M, P, work, ws, mean_out, cov_out);
   return (int)hipGetLastError();
@@ -213,5 +380,43 @@ template int period_moments<double>(int, const double*, long, int, const double*
                                     const double*, double*, double*, double*, hipStream_t);
 template int period_moments<float>(int, const float*, long, int, const float*, const double*, const double*, const int*, int,
                                    const float*, double*, double*, double*, hipStream_t);
+
+namespace {
+template <typename T, int MODE>
+int posterior_period_moments_mode(int model, int d, const T* V, long N, long Mp, int m, int B, const T* Xst, const T* var, long wbs,
+                                  const double* theta, const T* mu, const double* scale2, const double* w, const int* group, int P,
+                                  const T* ev, double* work, double* mean_out, double* cov_out, hipStream_t s, void* pre_scratch) {
+  const int nt = model_ntheta(model, d);
+  if (nt < 0) return -2;
+  const long ws = pm_site_doubles(Mp, P);
+  pm_init_kernel<<<dim3((unsigned)((P + 255) / 256), 1, (unsigned)B), 256, 0, s>>>(work, ws, Mp, P);
+  pm_prep_kernel<T, MODE><<<dim3((unsigned)((Mp + 255) / 256), 1, (unsigned)B), 256, 0, s>>>(var, wbs, 1, Mp, m, P, mu, scale2, w,
+                                                                                           group, ev, work, ws);
+  const dim3 grid((unsigned)(Mp / PM_ROWS), (unsigned)P, (unsigned)B);
+  DGP_DISPATCH_MODEL(model, d, (ppm_rows_kernel<T, M, MODE><<<grid, 256, 0, s>>>(
+                                   V, N, Mp, m, P, Xst, wbs, prepare_batch<M>(theta, nt, B, pre_scratch, false, s), scale2, group,
+                                   ev, work, ws)));
+  pm_reduce_kernel<<<dim3((unsigned)((P + 63) / 64), (unsigned)P, (unsigned)B), 256, 0, s>>>(Mp, P, work, ws, mean_out, cov_out);
+  return (int)hipGetLastError();
+}
+}  // namespace
+
+template <typename T>
+int posterior_period_moments(int mode, int model, int d, const T* V, long N, long m, int B, const T* Xst, const T* var, long wbs,
+                             const double* theta, const T* mu, const double* scale2, const double* w, const int* group, int P,
+                             const T* ev, double* work, double* mean_out, double* cov_out, hipStream_t s, void* pre_scratch) {
+  const long Mp = round_up(m, DGP_TILE_HOST);
+  return mode == 1 ? posterior_period_moments_mode<T, 1>(model, d, V, N, Mp, (int)m, B, Xst, var, wbs, theta, mu, scale2, w, group,
+                                                          P, ev, work, mean_out, cov_out, s, pre_scratch)
+                   : posterior_period_moments_mode<T, 0>(model, d, V, N, Mp, (int)m, B, Xst, var, wbs, theta, mu, scale2, w, group,
+                                                          P, ev, work, mean_out, cov_out, s, pre_scratch);
+}
+
+template int posterior_period_moments<double>(int, int, int, const double*, long, long, int, const double*, const double*, long,
+                                              const double*, const double*, const double*, const double*, const int*, int,
+                                              const double*, double*, double*, double*, hipStream_t, void*);
+template int posterior_period_moments<float>(int, int, int, const float*, long, long, int, const float*, const float*, long,
+                                             const double*, const float*, const double*, const double*, const int*, int,
+                                             const float*, double*, double*, double*, hipStream_t, void*);
 
 }  // namespace dgp

@@ -1003,6 +1003,22 @@ static int mean_vjp(dgp_plan* p, const double* theta, const void* Xs, int64_t m,
                           beta, (const T*)wts, (T*)(w + L.part), (T*)dtheta, s, bt, wbs, p->B > 1 ? p->ntheta : 0, p->pre, slot.staging);
 }
 
+// streamed period moments: the prediction's work area (its first stages leave V, Xs's SoA copy and the predicted variance
+// there), then the moment pass's work area
+template <typename T>
+static int post_period(dgp_plan* p, const double* theta, const void* Xs, int64_t m, int mode, const void* mu, const double* scale2,
+                       const double* w, const int32_t* group, int P, const void* ev, void* work, double* mean_out, double* cov_out,
+                       hipStream_t s) {
+  double* pm = (double*)((char*)work + predict_site_bytes(p, m) * (size_t)p->B);
+  T *V, *Xst, *vpad;
+  long wbs;
+  // the latent mean the prediction also writes (B x m elements) lands in the moment pass's area, which its first launch resets
+  int rc = predict_common<T>(p, theta, Xs, m, work, pm, &V, &Xst, &vpad, &wbs, s);
+  if (rc) return rc;
+  return posterior_period_moments<T>(mode, p->model, p->d, V, p->N, (long)m, p->B, Xst, vpad, wbs, theta, (const T*)mu, scale2, w,
+                                     group, P, (const T*)ev, pm, mean_out, cov_out, s, p->pre);
+}
+
 #define DGP_BY_DTYPE(p, CALL64, CALL32) ((p)->dtype == DGP_F64 ? (CALL64) : (CALL32))
 #define DGP_CHECK_PLAN(p)                                                        \
   if (!(p)) return fail(DGP_E_ARG, "null plan");                                 \
@@ -1139,6 +1155,30 @@ int dgp_period_moments(int dtype, int mode, const void* cov, int64_t m, int batc
                      : period_moments<float>(mode, (const float*)cov, m, batch, (const float*)mu, scale2, w, group, ngroups,
                                              (const float*)extra_var, (double*)work, mean_out, cov_out, s);
   return wrap(rc, "dgp_period_moments");
+}
+
+size_t dgp_posterior_period_moments_workspace_bytes(const dgp_plan* p, int64_t m, int ngroups) {
+  if (!p || m <= 0 || m > (1 << 20) || ngroups <= 0 || ngroups > 65535) return 0;
+  return predict_site_bytes(p, m) * (size_t)p->B + period_moments_workspace_bytes(m, ngroups, p->B);
+}
+
+int dgp_posterior_period_moments(dgp_plan* p, const double* theta, const void* Xs, int64_t m, int mode, const void* mu,
+                                 const double* scale2, const double* w, const int32_t* group, int ngroups, const void* extra_var,
+                                 void* work, size_t work_bytes, double* mean_out, double* cov_out, void* stream) {
+  if (!p) return fail(DGP_E_ARG, "null plan");
+  if (mode != 0 && mode != 1) return fail(DGP_E_ARG, "dgp_posterior_period_moments: mode must be 0 (linear) or 1 (log)");
+  if (!theta || !Xs || !mu || !scale2 || !w || !group || !mean_out || !cov_out)
+    return fail(DGP_E_ARG, "dgp_posterior_period_moments: null argument");
+  if (m <= 0 || m > (1 << 20) || ngroups <= 0 || ngroups > 65535)
+    return fail(DGP_E_ARG, "dgp_posterior_period_moments: bad size (1 <= m <= 2^20, 1 <= ngroups <= 65535)");
+  if (!p->have_factor) return fail(DGP_E_STATE, "dgp_posterior_period_moments: no factorisation in the plan (call dgp_factorize)");
+  DGP_CHECK_PLAN(p);
+  if (!work || work_bytes < dgp_posterior_period_moments_workspace_bytes(p, m, ngroups))
+    return fail(DGP_E_WORKSPACE, "dgp_posterior_period_moments: workspace missing or too small");
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = DGP_BY_DTYPE(p, post_period<double>(p, theta, Xs, m, mode, mu, scale2, w, group, ngroups, extra_var, work, mean_out, cov_out, s),
+                              post_period<float>(p, theta, Xs, m, mode, mu, scale2, w, group, ngroups, extra_var, work, mean_out, cov_out, s));
+  return wrap(rc, "dgp_posterior_period_moments");
 }
 
 int dgp_plan_set_timing(dgp_plan* p, int enabled) {

@@ -30,6 +30,10 @@ static const CompositeDesc* composite_get(int model) {
   const int slot = model - DGP_MODEL_COMPOSITE_BASE;
   return (slot >= 0 && slot < g_ncomp) ? &g_comp[slot] : nullptr;
 }
+bool composite_select(int model, int d) {  // DGP_DISPATCH_MODEL (dgp_gram_shared.h), in every translation unit
+  g_comp_cur = composite_get(model);
+  return g_comp_cur && g_comp_cur->d == d;
+}
 
 // spec: [d, nterms, then per term: scaled (0/1), nfac, then per factor: type, 2 nu, ard (0/1), ndims, dims...].
 // theta order: per term [outputscale if scaled], per factor [lengthscale(s)], [period if periodic].
@@ -586,36 +590,6 @@ __global__ __launch_bounds__(256) void resid_reduce_kernel(const double* __restr
 }
 
 // ------------------------------------------------------------------------------------------
-#define DGP_DISPATCH_MODEL(model, d, CALL)                   \
-  switch (model) {                                           \
-    case DGP_MODEL_LOADEST:                                  \
-      switch (d) {                                           \
-        case 2: { using M = Loadest<T, 2>; CALL; } break;    \
-        case 3: { using M = Loadest<T, 3>; CALL; } break;    \
-        case 4: { using M = Loadest<T, 4>; CALL; } break;    \
-        case 5: { using M = Loadest<T, 5>; CALL; } break;    \
-        case 6: { using M = Loadest<T, 6>; CALL; } break;    \
-        default: return -2;                                  \
-      }                                                      \
-      break;                                                 \
-    case DGP_MODEL_RATING:                                   \
-      if (d != 2) return -2;                                 \
-      { using M = Rating<T>; CALL; }                         \
-      break;                                                 \
-    default:                                                 \
-      g_comp_cur = composite_get(model);                     \
-      if (!g_comp_cur || g_comp_cur->d != d) return -2;      \
-      switch (d) {                                           \
-        case 1: { using M = Composite<T, 1>; CALL; } break;  \
-        case 2: { using M = Composite<T, 2>; CALL; } break;  \
-        case 3: { using M = Composite<T, 3>; CALL; } break;  \
-        case 4: { using M = Composite<T, 4>; CALL; } break;  \
-        case 5: { using M = Composite<T, 5>; CALL; } break;  \
-        case 6: { using M = Composite<T, 6>; CALL; } break;  \
-        default: return -2;                                  \
-      }                                                      \
-  }
-
 template <typename T>
 int pack_x(const T* X, int n, int d, long N, T* Xt, hipStream_t s, Batch bt) {
   pack_x_kernel<T><<<dim3((unsigned)((N + 255) / 256), 1, (unsigned)bt.B), dim3(256), 0, s>>>(X, n, d, N, Xt, bt.ws, bt.ns);

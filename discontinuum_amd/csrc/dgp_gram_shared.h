@@ -6,6 +6,37 @@
 
 namespace dgp {
 
+// Every (model, d) the library evaluates: `CALL` runs with `M` = the per-pair evaluator (dgp_models.h).  Launchers in any
+// translation unit dispatch through this one list (dgp_gram.hip, dgp_aggregate.hip).
+#define DGP_DISPATCH_MODEL(model, d, CALL)                   \
+  switch (model) {                                           \
+    case DGP_MODEL_LOADEST:                                  \
+      switch (d) {                                           \
+        case 2: { using M = Loadest<T, 2>; CALL; } break;    \
+        case 3: { using M = Loadest<T, 3>; CALL; } break;    \
+        case 4: { using M = Loadest<T, 4>; CALL; } break;    \
+        case 5: { using M = Loadest<T, 5>; CALL; } break;    \
+        case 6: { using M = Loadest<T, 6>; CALL; } break;    \
+        default: return -2;                                  \
+      }                                                      \
+      break;                                                 \
+    case DGP_MODEL_RATING:                                   \
+      if (d != 2) return -2;                                 \
+      { using M = Rating<T>; CALL; }                         \
+      break;                                                 \
+    default:                                                 \
+      if (!composite_select(model, d)) return -2;            \
+      switch (d) {                                           \
+        case 1: { using M = Composite<T, 1>; CALL; } break;  \
+        case 2: { using M = Composite<T, 2>; CALL; } break;  \
+        case 3: { using M = Composite<T, 3>; CALL; } break;  \
+        case 4: { using M = Composite<T, 4>; CALL; } break;  \
+        case 5: { using M = Composite<T, 5>; CALL; } break;  \
+        case 6: { using M = Composite<T, 6>; CALL; } break;  \
+        default: return -2;                                  \
+      }                                                      \
+  }
+
 template <typename T, typename M>
 __device__ __forceinline__ void stage_strip(const T* __restrict__ Xt, long N, long base, const typename M::Pre& pre,
                                             T (*sf)[64], int lane) {

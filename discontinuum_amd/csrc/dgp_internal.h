@@ -41,6 +41,7 @@ struct Batch {
 };
 int model_ntheta(int model, int d);  // number of constrained kernel hyperparameters, -1 if unsupported
 int composite_define(const int* spec, int nspec);  // register a generic composite model (dgp_models.h), -> model id or < 0
+bool composite_select(int model, int d);  // make `model` the composite the next Composite<T, d>::prepare reads; false if it is none
 
 // ---- dgp_gram.hip ---------------------------------------------------------------------------
 template <typename T>
@@ -184,5 +185,12 @@ size_t period_moments_workspace_bytes(long m, int P, int B);
 template <typename T>
 int period_moments(int mode, const T* cov, long m, int B, const T* mu, const double* scale2, const double* w, const int* group,
                    int P, const T* ev, double* work, double* mean_out, double* cov_out, hipStream_t s);
+// the same moments with C = K(Xs, Xs) - V^T V never stored: V (N x M), the test points' SoA coordinates Xst (d x M) and their
+// predicted variance var (M) as the prediction leaves them in its work area (site stride wbs elements); `work` as above
+// (period_moments_workspace_bytes); pre_scratch: the plan's hyperparameter scratch, already filled by this call's gram_cross
+template <typename T>
+int posterior_period_moments(int mode, int model, int d, const T* V, long N, long m, int B, const T* Xst, const T* var, long wbs,
+                             const double* theta, const T* mu, const double* scale2, const double* w, const int* group, int P,
+                             const T* ev, double* work, double* mean_out, double* cov_out, hipStream_t s, void* pre_scratch);
 
 }  // namespace dgp

@@ -654,7 +654,7 @@ class MarginalHIP(BaseModel):
                          dims=["draw"] + list(covariates.coords), attrs=temp.attrs)
 
     @is_fitted
-    def aggregate(self, covariates, weights, freq="YE", ci=0.95, pred_noise=False, return_cov=False):
+    def aggregate(self, covariates, weights, freq="YE", ci=0.95, pred_noise=False, return_cov=False, max_bytes=None):
         """Exact mean and covariance of the period sums sum_{i in period} weights_i target_i over the points of
         ``covariates`` (``freq``: a resample alias -- "YE", "YE-SEP" for water years, "QE", "ME"), from the latent
         posterior (``pred_noise=True`` adds the likelihood's predictive noise to its diagonal): what ``sample()``, a
@@ -662,10 +662,12 @@ class MarginalHIP(BaseModel):
         covariance and one ``dgp_period_moments`` pass.  Points with a non-finite weight are skipped.  -> Dataset on a
         ``time`` coordinate of period-end labels with ``mean``, ``se``, ``lower`` / ``upper`` (approximate ``ci``
         interval: lognormal / normal with the exact moments) and ``n_points``; with ``return_cov`` also the (P, P)
-        covariance.  See ``discontinuum_amd.loads``."""
-        from ..loads import aggregate
+        covariance.  ``max_bytes`` (default ``loads.DEFAULT_MAX_BYTES``): device budget of the dense path; a record whose
+        m x m covariance does not fit it takes the streamed ``dgp_posterior_period_moments``.  See ``discontinuum_amd.loads``."""
+        from ..loads import DEFAULT_MAX_BYTES, aggregate
 
-        return aggregate(self, covariates, weights, freq=freq, ci=ci, pred_noise=pred_noise, return_cov=return_cov)
+        return aggregate(self, covariates, weights, freq=freq, ci=ci, pred_noise=pred_noise, return_cov=return_cov,
+                         max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes)
 
     def build_model(self, X, y, **kwargs):
         raise NotImplementedError("This method must be implemented in a subclass")

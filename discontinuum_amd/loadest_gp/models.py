@@ -70,13 +70,35 @@ class LoadestGPMarginalHIP(LoadestDataMixin, MarginalHIP):
         return ExactGPModel(X, y, self.likelihood)
 
     @is_fitted
-    def annual_flux(self, covariates, freq="YE", ci=0.95, pred_noise=False, return_cov=False):
+    def annual_flux(self, covariates, freq="YE", ci=0.95, pred_noise=False, return_cov=False, max_bytes=None):
         """Exact period loads in kilograms -- sum over each period of concentration (mg/l) x flow (m^3/s) x time step --
         with their standard errors and approximate ``ci`` intervals; ``covariates`` on a regular time grid (an irregular
         one raises ``ValueError``), ``freq`` a resample alias ("YE", "YE-SEP" for water years, "QE", "ME").  Replaces
         ``concentration_to_flux(model.sample(daily, n), daily["flow"]).resample(time="YE").sum()``
-        (src/loadest_gp/utils.py:14-103) without its sampling noise; see ``MarginalHIP.aggregate``."""
-        from ..loads import annual_flux
+        (src/loadest_gp/utils.py:14-103) without its sampling noise; see ``MarginalHIP.aggregate`` (also for
+        ``max_bytes``)."""
+        from ..loads import DEFAULT_MAX_BYTES, annual_flux
 
-        return annual_flux(self, covariates, freq=freq, ci=ci, pred_noise=pred_noise, return_cov=return_cov)
+        return annual_flux(self, covariates, freq=freq, ci=ci, pred_noise=pred_noise, return_cov=return_cov,
+                           max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes)
+
+    def flow_normalized_flux(self, daily, freq="YE", flow_window=None, ci=0.95, pred_noise=False, return_cov=False,
+                             max_bytes=None):
+        """Flow-normalized period loads (kg) with exact uncertainty -- WRTDS's FN flux: each day's load averaged over
+        every flow seen on its calendar day in the record (or in ``flow_window``, an inclusive (start, end) pair).
+        ``daily`` on a daily grid; see ``loads.flow_normalized`` and, for trends, ``loads.period_change``."""
+        from ..loads import DEFAULT_MAX_BYTES, flow_normalized
+
+        return flow_normalized(self, daily, kind="flux", freq=freq, flow_window=flow_window, ci=ci, pred_noise=pred_noise,
+                               return_cov=return_cov, max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes)
+
+    def flow_normalized_concentration(self, daily, freq="YE", flow_window=None, ci=0.95, pred_noise=False,
+                                      return_cov=False, max_bytes=None):
+        """Flow-normalized period mean concentration (the target's units) with exact uncertainty; see
+        ``flow_normalized_flux``."""
+        from ..loads import DEFAULT_MAX_BYTES, flow_normalized
+
+        return flow_normalized(self, daily, kind="concentration", freq=freq, flow_window=flow_window, ci=ci,
+                               pred_noise=pred_noise, return_cov=return_cov,
+                               max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes)
 

@@ -108,7 +108,8 @@ def intervals(mode, mean, var, ci=0.95):
     return np.where(pos, lower, mean), np.where(pos, upper, mean)
 
 
-def _dataset(mode, mean, cov, labels, n_points, attrs, ci):
+def _dataset(mode, mean, cov, labels, n_points, attrs, ci, freq=None):
+    """-> the result Dataset; its own attrs also carry the period ``freq`` (``period_change`` reads it)."""
     var = np.clip(np.diagonal(cov), 0.0, None)
     lower, upper = intervals(mode, mean, var, ci)
     attrs = dict(attrs)
@@ -121,7 +122,7 @@ def _dataset(mode, mean, cov, labels, n_points, attrs, ci):
             "n_points": ("time", n_points),
         },
         coords={"time": labels},
-        attrs=attrs,
+        attrs=attrs if freq is None else dict(attrs, freq=freq),
     )
 
 
@@ -131,35 +132,80 @@ def _target_attrs(dm):
 
 
 # ---------------------------------------------------------------------------------------------------- one site
-def aggregate(model, covariates, weights, freq="YE", ci=0.95, pred_noise=False, return_cov=False, attrs=None):
+def aggregate(model, covariates, weights, freq="YE", ci=0.95, pred_noise=False, return_cov=False, attrs=None,
+              max_bytes: int = DEFAULT_MAX_BYTES):
     """``MarginalHIP.aggregate``: exact mean / covariance of sum_{i in period} w_i c_i over the points of
-    ``covariates`` (c = the model's target in data space), one ``dgp_posterior_cov`` + one ``dgp_period_moments``."""
-    mode, s, t = target_transform(model.dm)
+    ``covariates`` (c = the model's target in data space).  A site whose dense footprint (``_site_bytes``) fits
+    ``max_bytes`` takes one ``dgp_posterior_cov`` + one ``dgp_period_moments``; a larger one the streamed
+    ``dgp_posterior_period_moments``, which never forms the m x m covariance."""
     order, groups, labels, n_points, _dropped = _kept(*period_groups(covariates.coords["time"].values, np.asarray(weights), freq))
     w = np.asarray(weights, dtype=np.float64).reshape(-1)[order]
-    Xnew = torch.tensor(model.dm.Xnew(covariates), dtype=model.dtype)[torch.as_tensor(order)].to(model.device).contiguous()
+    Xnew = torch.tensor(model.dm.Xnew(covariates), dtype=model.dtype)[torch.as_tensor(order)]
+    return point_moments(model, Xnew, w, groups, labels, n_points, ci=ci, pred_noise=pred_noise, return_cov=return_cov,
+                         attrs=attrs, max_bytes=max_bytes, freq=freq)
+
+
+def point_moments(model, Xnew, w, groups, labels, n_points, ci=0.95, pred_noise=False, return_cov=False, attrs=None,
+                  max_bytes: int = DEFAULT_MAX_BYTES, freq=None):
+    """The moment core of ``aggregate`` on model-space inputs: design rows ``Xnew`` (m, d), weights ``w`` (m,), int32
+    period ids ``groups`` (non-decreasing, -1 = excluded), period ``labels`` and ``n_points`` per period -- what
+    ``aggregate`` builds from a covariates record and ``flow_normalized`` from its (day, flow) pairs."""
+    mode, s, t = target_transform(model.dm)
+    Xnew = Xnew.to(model.device).contiguous()
     m = Xnew.shape[0]
     model._device_ready()
     model.model.eval()
     model.likelihood.eval()
+    esz = torch.empty((), dtype=model.dtype).element_size()
     with torch.no_grad():
         if hasattr(model.model, "prepare_eval"):
             model.model.prepare_eval(model._train_x, Xnew)
         model._ensure_factor()
-        kmean, cov = model._plan.posterior_cov(model._factor_theta, Xnew)
-        mu = kmean + model.model.prior_mean(Xnew)
-        extra = model.likelihood.predictive_noise(m, Xnew.device, model.dtype) if pred_noise else None
-        mean_d, cov_d = model._plan.period_moments(cov, m, (s * mu + t).contiguous(), s * s, w, groups, len(labels),
-                                                   mode, extra_var=extra)
+        if _site_bytes(model.dm.X.shape[0], m, esz) <= max_bytes:
+            kmean, cov = model._plan.posterior_cov(model._factor_theta, Xnew)
+            mu = kmean + model.model.prior_mean(Xnew)
+            extra = model.likelihood.predictive_noise(m, Xnew.device, model.dtype) if pred_noise else None
+            mean_d, cov_d = model._plan.period_moments(cov, m, (s * mu + t).contiguous(), s * s, w, groups, len(labels),
+                                                       mode, extra_var=extra)
+        else:
+            mu = model._plan.predict_mean(model._factor_theta, Xnew) + model.model.prior_mean(Xnew)
+            extra = model.likelihood.predictive_noise(m, Xnew.device, model.dtype) if pred_noise else None
+            mean_d, cov_d = model._plan.posterior_period_moments(model._factor_theta, Xnew, (s * mu + t).contiguous(), s * s, w,
+                                                                 groups, len(labels), mode, extra_var=extra)
     mean, pcov = mean_d.cpu().numpy(), cov_d.cpu().numpy()
-    ds = _dataset(mode, mean, pcov, labels, n_points, _target_attrs(model.dm) if attrs is None else attrs, ci)
+    ds = _dataset(mode, mean, pcov, labels, n_points, _target_attrs(model.dm) if attrs is None else attrs, ci, freq)
     return (ds, pcov) if return_cov else ds
 
 
 # ---------------------------------------------------------------------------------------------------- many sites
 def _site_bytes(n, m, esz):
+    """Device bytes of the dense path for one site: the (M, M) covariance, the prediction's cross terms, the plan."""
     N, M = -(-n // 128) * 128, -(-m // 128) * 128
     return esz * (M * M + 2 * N * M + 3 * N * N) + 8 * M * 8
+
+
+def _streamed_bytes(n, m, P, d, esz):
+    """Device bytes of the streamed path for one site: the plan, the prediction's work area (coordinates, cross Gram, V,
+    vectors, partial sums) and the moment pass's M P + 2 M + P doubles -- nothing of order M^2."""
+    N, M = -(-n // 128) * 128, -(-m // 128) * 128
+    return esz * (3 * N * N + 2 * N * M + (d + 3 + 64) * M) + 8 * (M * P + 2 * M + P) + 8 * M * 8
+
+
+def _batches(idx, nbytes, sizes, max_bytes):
+    """Consecutive batches of the sites ``idx`` whose footprint ``len(batch) x nbytes(max n, max m)`` stays under
+    ``max_bytes``; a site over budget on its own runs alone."""
+    batches, cur, n_max, m_max = [], [], 0, 0
+    for b in idx:
+        n, m = sizes[b]
+        n2, m2 = max(n_max, n), max(m_max, m)
+        if cur and (len(cur) + 1) * nbytes(n2, m2) > max_bytes:
+            batches.append(cur)
+            cur, n2, m2 = [], n, m
+        cur.append(b)
+        n_max, m_max = n2, m2
+    if cur:
+        batches.append(cur)
+    return batches
 
 
 def aggregate_many(models, covariates_list, weights_list, freq="YE", ci=0.95, pred_noise=False, return_cov=False,
@@ -168,7 +214,9 @@ def aggregate_many(models, covariates_list, weights_list, freq="YE", ci=0.95, pr
     sites ONE batched plan, one batched ``dgp_factorize``, one batched ``dgp_posterior_cov`` and one
     ``dgp_period_moments`` launch (gridDim.z = sites); pad points carry group -1.  Sites are cut into consecutive
     batches whose device footprint -- B x (M^2 + 2 N M + 3 N^2) elements for the covariances, the cross terms and the
-    plan -- stays under ``max_bytes`` (default 16 GiB; one site at m = 11 323 already needs 1 GB for its covariance)."""
+    plan -- stays under ``max_bytes`` (default 16 GiB; one site at m = 11 323 already needs 1 GB for its covariance).
+    Sites whose dense footprint alone exceeds ``max_bytes`` take the streamed ``dgp_posterior_period_moments`` instead,
+    in batches of their own cut by the streamed footprint (``_streamed_bytes``: nothing of order M^2)."""
     from .backend import GPPlan
     from . import _lib
 
@@ -201,18 +249,17 @@ def aggregate_many(models, covariates_list, weights_list, freq="YE", ci=0.95, pr
                                      if pred_noise else None)))
     if len({st["name"] for st in sites}) != 1 or len({st["mode"] for st in sites}) != 1:
         raise ValueError("aggregate_many needs sites of one model family, one input dimension and one target transform")
-    batches, cur, n_max, m_max = [], [], 0, 0
-    for b, st in enumerate(sites):
-        n2, m2 = max(n_max, st["x"].shape[0]), max(m_max, st["xn"].shape[0])
-        if cur and (len(cur) + 1) * _site_bytes(n2, m2, esz) > max_bytes:
-            batches.append(cur)
-            cur, n2, m2 = [], st["x"].shape[0], st["xn"].shape[0]
-        cur.append(b)
-        n_max, m_max = n2, m2
-    batches.append(cur)
+    # sites whose dense footprint fits the budget keep the dense batches; the others go the streamed way in batches of
+    # their own, cut by the streamed footprint
+    sizes = [(st["x"].shape[0], st["xn"].shape[0]) for st in sites]
+    dense = [b for b, (n, m) in enumerate(sizes) if _site_bytes(n, m, esz) <= max_bytes]
+    rest = [b for b in range(len(sites)) if b not in set(dense)]
+    P_all, d_all = max(len(st["labels"]) for st in sites), sites[0]["name"][1]
+    batches = [(idx, False) for idx in _batches(dense, lambda n, m: _site_bytes(n, m, esz), sizes, max_bytes)]
+    batches += [(idx, True) for idx in _batches(rest, lambda n, m: _streamed_bytes(n, m, P_all, d_all, esz), sizes, max_bytes)]
 
     results = [None] * len(sites)
-    for idx in batches:
+    for idx, streamed in batches:
         group = [sites[b] for b in idx]
         B = len(group)
         (name, d), mode = group[0]["name"], group[0]["mode"]
@@ -243,7 +290,10 @@ def aggregate_many(models, covariates_list, weights_list, freq="YE", ci=0.95, pr
             if bool((info != 0).any()):
                 bad = int(torch.nonzero(info)[0])
                 raise RuntimeError(f"site {idx[bad]}: matrix not positive definite (Cholesky pivot {int(info[bad])})")
-            kmean, cov = plan.posterior_cov(one(theta), one(Xs))
+            if streamed:
+                kmean, cov = plan.predict_mean(one(theta), one(Xs)), None
+            else:
+                kmean, cov = plan.posterior_cov(one(theta), one(Xs))
             mu = kmean.reshape(B, mm) + slots([st["xmean"] for st in group], mm).to(device)
             sv = torch.tensor([st["s"] for st in group], dtype=dtype, device=device)
             tv = torch.tensor([st["t"] for st in group], dtype=dtype, device=device)
@@ -252,15 +302,19 @@ def aggregate_many(models, covariates_list, weights_list, freq="YE", ci=0.95, pr
             G = slots([st["groups"] for st in group], mm, -1, dt=torch.int32)
             EV = slots([st["extra"] for st in group], mm).to(device).contiguous() if pred_noise else None
             P = max(len(st["labels"]) for st in group)
-            mean_d, cov_d = plan.period_moments(cov, mm, one(mapped), (sv.double() ** 2).cpu(), one(W), one(G), P, mode,
-                                                extra_var=one(EV) if EV is not None else None)
+            if streamed:
+                mean_d, cov_d = plan.posterior_period_moments(one(theta), one(Xs), one(mapped), (sv.double() ** 2).cpu(), one(W),
+                                                              one(G), P, mode, extra_var=one(EV) if EV is not None else None)
+            else:
+                mean_d, cov_d = plan.period_moments(cov, mm, one(mapped), (sv.double() ** 2).cpu(), one(W), one(G), P, mode,
+                                                    extra_var=one(EV) if EV is not None else None)
         mean_h, cov_h = mean_d.reshape(B, P).cpu().numpy(), cov_d.reshape(B, P, P).cpu().numpy()
         del plan, cov
         for k, b in enumerate(idx):
             st = sites[b]
             p = len(st["labels"])
             attrs = _target_attrs(models[b].dm) if attrs_list is None else attrs_list[b]
-            ds = _dataset(mode, mean_h[k, :p], cov_h[k, :p, :p], st["labels"], st["n_points"], attrs, ci)
+            ds = _dataset(mode, mean_h[k, :p], cov_h[k, :p, :p], st["labels"], st["n_points"], attrs, ci, freq)
             results[b] = (ds, cov_h[k, :p, :p].copy()) if return_cov else ds
     return results
 
@@ -274,13 +328,17 @@ def flux_weights(covariates, concentration_attrs):
     if len(dt) != 1:
         raise ValueError("annual_flux needs a regular time grid (one constant time step)")
     flow = covariates["flow"]
+    _unit_warnings(flow, concentration_attrs, stacklevel=4)
+    return np.asarray(flow.values, dtype=np.float64).reshape(-1) * dt[0] * 1e-3
+
+
+def _unit_warnings(flow, concentration_attrs, stacklevel):
     if getattr(flow, "attrs", {}).get("units") != "cubic meters per second":
         warnings.warn("Check that flow is 'cubic meters per second'. Set flow.units = 'cubic meters per second' to silence.",
-                      UserWarning, stacklevel=3)
+                      UserWarning, stacklevel=stacklevel)
     if "mg/l" not in str(concentration_attrs.get("units", "")):
         warnings.warn("Check that concentration is in 'mg/l'. Set concentration.units = 'mg/l' to silence.",
-                      UserWarning, stacklevel=3)
-    return np.asarray(flow.values, dtype=np.float64).reshape(-1) * dt[0] * 1e-3
+                      UserWarning, stacklevel=stacklevel)
 
 
 def _flux_attrs(model):
@@ -290,11 +348,120 @@ def _flux_attrs(model):
     return attrs
 
 
-def annual_flux(model, covariates, freq="YE", ci=0.95, pred_noise=False, return_cov=False):
+def annual_flux(model, covariates, freq="YE", ci=0.95, pred_noise=False, return_cov=False, max_bytes: int = DEFAULT_MAX_BYTES):
     """``LoadestGP.annual_flux``: exact period loads (kg) and their uncertainty."""
     w = flux_weights(covariates, _target_attrs(model.dm))
     return aggregate(model, covariates, w, freq=freq, ci=ci, pred_noise=pred_noise, return_cov=return_cov,
-                     attrs=_flux_attrs(model))
+                     attrs=_flux_attrs(model), max_bytes=max_bytes)
+
+
+# ---------------------------------------------------------------------------------------------------- flow normalization
+DAY_NS = 86_400 * 10 ** 9
+
+
+def day_keys(time):
+    """Calendar key 0..364 of each day on a 365-day year: 29 Feb folds onto 28 Feb, the later days of a leap year shift
+    back by one."""
+    t = pd.DatetimeIndex(np.asarray(time).reshape(-1).astype("datetime64[ns]"))
+    doy = t.dayofyear.to_numpy() - 1
+    return np.where(t.is_leap_year & (doy >= 59), doy - 1, doy).astype(np.int64)
+
+
+def flow_normalized_points(daily, kind="flux", freq="YE", flow_window=None):
+    """The point set of flow-normalized (FN) period values: day t contributes (t, q) for every q in S(key(t)), the finite
+    flows on all days with t's calendar key (inside ``flow_window`` = an inclusive (start, end) pair of date-likes, if
+    given); days with an empty set are dropped.  Weights: ``kind="flux"`` q 86400 1e-3 / |S| (kg per mg/l), a day's
+    average load; ``"concentration"`` 1 / (|S| D_p), D_p the contributing days of the period, a period mean.
+    -> dict of point arrays ``time``, ``flow``, ``key``, ``set_size``, ``weight``, ``group`` (int32, non-decreasing) and
+    per period ``labels`` and ``n_points`` (contributing days); ``daily`` must be on a daily grid (else ``ValueError``)."""
+    if kind not in ("flux", "concentration"):
+        raise ValueError(f"kind must be 'flux' or 'concentration', not {kind!r}")
+    time = np.asarray(daily.coords["time"].values).reshape(-1).astype("datetime64[ns]")
+    if len(time) < 2 or np.any(np.diff(time).astype(np.int64) != DAY_NS):
+        raise ValueError("flow normalization needs a daily grid (one point per day, no gaps)")
+    flow = np.asarray(daily["flow"].values, dtype=np.float64).reshape(-1)
+    keys = day_keys(time)
+    pool = np.isfinite(flow)
+    if flow_window is not None:
+        lo, hi = (np.datetime64(pd.Timestamp(v).to_datetime64(), "ns") for v in flow_window)
+        pool &= (time >= lo) & (time <= hi)
+    if not pool.any():
+        raise ValueError("no finite flow to normalize with (check flow_window)")
+    srt = np.argsort(keys[pool], kind="stable")
+    pool_q = flow[pool][srt]
+    count = np.bincount(keys[pool], minlength=365)
+    start = np.cumsum(count) - count
+    order, dgroups, labels, _n, _d = period_groups(time, np.ones(len(time)), freq)
+    live = count[keys[order]] > 0
+    days, groups = order[live], dgroups[live]
+    size = count[keys[days]]
+    n_points = np.bincount(groups, minlength=len(labels))
+    day_of = np.repeat(np.arange(len(days)), size)                       # point -> contributing day
+    within = np.arange(day_of.shape[0]) - np.repeat(np.cumsum(size) - size, size)
+    q = pool_q[start[keys[days]][day_of] + within]
+    g = groups[day_of].astype(np.int32)
+    ns = size[day_of].astype(np.float64)
+    w = q * 86400 * 1e-3 / ns if kind == "flux" else 1.0 / (ns * n_points[g])
+    return {"time": time[days][day_of], "flow": q, "key": keys[days][day_of], "set_size": size[day_of], "weight": w,
+            "group": g, "labels": labels, "n_points": n_points}
+
+
+def flow_normalized(model, daily, kind="flux", freq="YE", flow_window=None, ci=0.95, pred_noise=False, return_cov=False,
+                    max_bytes: int = DEFAULT_MAX_BYTES):
+    """Flow-normalized (FN) period flux (kg, ``kind="flux"``) or mean concentration (``"concentration"``) -- WRTDS's FN
+    values, with exact moments:  FN(p) = sum_{t in p} 1/|S(t)| sum_{q in S(t)} c(t, q) w(q), S(t) the flows seen on t's
+    calendar day over the record (or over ``flow_window``: loads under a base period's flows, the counterfactual of the
+    reference's ``time_substitution``, src/discontinuum/utils.py:36-67).  The points are those of
+    ``flow_normalized_points`` -- about 365 Y^2 for Y years, which the streamed path takes once the dense one exceeds
+    ``max_bytes``.  The model's design must be exactly (time, flow).  -> ``annual_flux``'s layout (+ the (P, P)
+    covariance with ``return_cov``), the period change of which ``period_change`` gives."""
+    if not model.is_fitted:
+        raise RuntimeError("The model hasn't been fitted yet, call .fit().")
+    names = tuple(model.dm.covariate_pipelines)
+    if names != ("time", "flow"):
+        raise ValueError(f"flow normalization needs a model of exactly (time, flow), not {names}")
+    pts = flow_normalized_points(daily, kind=kind, freq=freq, flow_window=flow_window)
+    if kind == "flux":
+        _unit_warnings(daily["flow"], _target_attrs(model.dm), stacklevel=4)
+        attrs = _flux_attrs(model)
+    else:
+        attrs = _target_attrs(model.dm)
+    attrs["long_name"] = f"Flow-normalized {attrs.get('long_name', kind)}".strip()
+    points = Dataset({"flow": ("time", pts["flow"])}, coords={"time": pts["time"]})
+    Xnew = torch.tensor(model.dm.Xnew(points), dtype=model.dtype)
+    return point_moments(model, Xnew, pts["weight"], pts["group"], pts["labels"], pts["n_points"], ci=ci,
+                         pred_noise=pred_noise, return_cov=return_cov, attrs=attrs, max_bytes=max_bytes, freq=freq)
+
+
+def period_change(ds, cov, start, end, ci=0.95, freq=None):
+    """Change between two periods of an ``aggregate`` / ``annual_flux`` / ``flow_normalized`` result and its (P, P)
+    covariance: ``start`` / ``end`` are date-likes, each selecting the period that contains it ("1995" = 1 Jan 1995) at the
+    result's own frequency (its ``freq`` attribute, or ``freq``).  -> dict(start, end (period labels), change =
+    mean[end] - mean[start], se = sqrt(C_ee + C_ss - 2 C_se), lower, upper (normal ``ci`` interval))."""
+    freq = freq or dict(getattr(ds, "attrs", None) or {}).get("freq")
+    if freq is None:
+        raise ValueError("period_change needs the period frequency: pass freq= (aggregate / annual_flux / flow_normalized "
+                         "results carry it)")
+    pfreq = _period_freq(freq)
+    labels = pd.DatetimeIndex(np.asarray(ds.coords["time"].values).reshape(-1).astype("datetime64[ns]"))
+    periods = labels.to_period(pfreq)
+    mean, cov = np.asarray(ds["mean"].values, dtype=np.float64), np.asarray(cov, dtype=np.float64)
+    if cov.shape != (len(labels), len(labels)):
+        raise ValueError(f"cov must be ({len(labels)}, {len(labels)})")
+
+    def index(x):
+        p = pd.Timestamp(x).to_period(pfreq)
+        hit = np.nonzero(periods == p)[0]
+        if not len(hit):
+            raise ValueError(f"{pd.Timestamp(x).date()} lies in none of the periods {periods[0]} .. {periods[-1]}")
+        return int(hit[0])
+
+    s, e = index(start), index(end)
+    change = mean[e] - mean[s]
+    se = float(np.sqrt(max(cov[e, e] + cov[s, s] - 2.0 * cov[s, e], 0.0)))
+    z = norm.ppf(1 - (1 - ci) / 2)
+    return {"start": labels[s].to_datetime64(), "end": labels[e].to_datetime64(), "change": float(change), "se": se,
+            "lower": float(change - z * se), "upper": float(change + z * se)}
 
 
 def annual_flux_many(models, covariates_list, freq="YE", ci=0.95, pred_noise=False, return_cov=False,
@@ -306,4 +473,5 @@ def annual_flux_many(models, covariates_list, freq="YE", ci=0.95, pred_noise=Fal
 
 
 __all__ = ["aggregate", "aggregate_many", "annual_flux", "annual_flux_many", "period_groups", "target_transform",
-           "intervals", "DEFAULT_MAX_BYTES"]
+           "intervals", "point_moments", "day_keys", "flow_normalized_points", "flow_normalized", "period_change",
+           "DEFAULT_MAX_BYTES"]

@@ -237,6 +237,25 @@ int dgp_period_moments(int dtype, int mode, const void* cov_dev, int64_t m, int 
                        const void* extra_var_dev, void* work_dev, size_t work_bytes, double* mean_out_dev,
                        double* cov_out_dev, void* stream);
 
+/* The same period moments straight from the factorisation the plan holds: C = K(Xs, Xs) - V^T V, V = L^-1 K(X, Xs), is
+ * folded into the ngroups x ngroups moments tile by tile and never stored -- for records whose m x m covariance does not fit
+ * the device (30 years of daily points: m ~ 330 000, 870 GB in fp64), and for flow-normalized loads (EGRET's FN flux, which
+ * the reference's WRTDS lineage points to: README.md, src/discontinuum/utils.py:36-67), whose point sets grow with the
+ * square of the record length.
+ *   Xs_dev     m x d row-major (batch x m x d for batched plans), as for dgp_posterior_cov; mode, mu_dev (mapped), scale2_dev,
+ *              w_dev, group_dev, ngroups, extra_var_dev, mean_out_dev, cov_out_dev: as for dgp_period_moments.
+ * work_dev: dgp_posterior_period_moments_workspace_bytes(plan, m, ngroups) bytes -- per site the prediction's work area
+ * (2 N M + O(M) plan-dtype elements) and M ngroups + O(M) doubles; no buffer grows with M^2.  0 for bad sizes.
+ * One MFMA pass over about m^2 / 2 (1 + 1/ngroups) entries (2 N flop each) with the covariance function evaluated per entry,
+ * no floating-point atomics: bitwise repeatable, a site's result does not depend on its batch.  DGP_E_STATE without a
+ * factorisation.  Every (model, d) of dgp_posterior_cov, batched plans included (gridDim.z = sites). */
+size_t dgp_posterior_period_moments_workspace_bytes(const dgp_plan* plan, int64_t m, int ngroups);
+int dgp_posterior_period_moments(dgp_plan* plan, const double* theta_host, const void* Xs_dev, int64_t m, int mode,
+                                 const void* mu_dev, const double* scale2_dev, const double* w_dev,
+                                 const int32_t* group_dev, int ngroups, const void* extra_var_dev,
+                                 void* work_dev, size_t work_bytes, double* mean_out_dev, double* cov_out_dev,
+                                 void* stream);
+
 /* Predictive mean only, and its vector-Jacobian product -- what the rating-gp monotonicity penalty
  * differentiates (src/rating_gp/models/gpytorch.py:130-187: mean of likelihood(model(x_grid)) with grad).
  *   dgp_predict_mean : mean_dev[j] = K(x*_j, X) alpha                                  (m entries)
