@@ -136,6 +136,7 @@ class GPPlan:
         arr = (C.c_int64 * self.batch)(*vals)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.dgp_plan_set_site_sizes(self._h, arr, _stream()), "dgp_plan_set_site_sizes")
+        self._site_sizes = vals
 
     # ------------------------------------------------------------------ hot path
     def set_dr_weights(self, w):
@@ -221,6 +222,48 @@ class GPPlan:
                     mean[:, lo:hi] = mo
                     var[:, lo:hi] = vo
         return mean, var
+
+    # ------------------------------------------------------------------ cross-validation
+    def cross_validate(self, groups, max_group=None):
+        """Exact leave-group-out cross-validation at the hyperparameters of the factorisation the plan holds
+        (``dgp_cross_validate``; no fold is refitted).  ``groups``: an integer tensor / array (n,) -- (batch, n) for a
+        batched plan -- of fold ids >= 0, -1 for an observation that is never held out; a site of a ragged batch uses its
+        first ``sizes[b]`` entries.  -> (resid, var, lpd, info): held-out residual y_i - E[y_i | other folds] and held-out
+        predictive variance of the OBSERVATION (its own noise included), both (n,) fp64 in model space and 0 where
+        ``groups`` is -1; ``lpd`` (ngroups,) the joint log predictive density of every fold (0 for a fold id nobody uses);
+        ``info`` (ngroups,) int32, 0 or the failing pivot.  ngroups = 1 + the largest fold id of any site.
+        ``max_group``: an upper bound of the fold sizes handed to the library instead of the largest fold found -- the
+        bound selects the device route and its block order, so results are bitwise comparable between calls (a site alone
+        and the same site inside a batch) only under the same bound."""
+        return cross_validate_folds(self, groups, self._cv_launch, max_group)
+
+    def _cv_launch(self, order, start, ngroups, max_group):
+        lead = () if self.batch == 1 else (self.batch,)
+        need = int(self.lib.dgp_cross_validate_workspace_bytes(self._h, ngroups, max_group))
+        if need == 0:
+            raise ValueError(f"bad size: ngroups = {ngroups}, max_group = {max_group} (both in 1..n)")
+        with torch.cuda.device(self.device):
+            ws = getattr(self, "_cv_ws", None)
+            if ws is None or ws.numel() < need + 256:
+                self._cv_ws = None
+                try:
+                    self._cv_ws = ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+                except torch.OutOfMemoryError as e:
+                    raise RuntimeError(f"cross-validation work area of {need} bytes does not fit the device") from e
+            base = ws.data_ptr()
+            base += (-base) % 256
+            order = order.to(self.device).contiguous()
+            start = start.to(self.device).contiguous()
+            resid = torch.empty(lead + (self.n,), dtype=torch.float64, device=self.device)
+            var = torch.empty_like(resid)
+            lpd = torch.empty(lead + (ngroups,), dtype=torch.float64, device=self.device)
+            info = torch.empty(lead + (ngroups,), dtype=torch.int32, device=self.device)
+            _lib.check(
+                self.lib.dgp_cross_validate(self._h, _ptr(order), _ptr(start), ngroups, max_group, C.c_void_p(base), need,
+                                            _ptr(resid), _ptr(var), _ptr(lpd), _ptr(info), _stream()),
+                "dgp_cross_validate",
+            )
+        return resid, var, lpd, info
 
     # ------------------------------------------------------------------ sample(): posterior covariance, factor, draws
     def _jitter_ladder(self):
@@ -519,3 +562,44 @@ def period_moments(cov: torch.Tensor, m: int, mu: torch.Tensor, scale2, w: torch
         "dgp_period_moments",
     )
     return mean_out, cov_out
+
+
+def cross_validate_folds(plan, groups, launch, max_group_bound=None):
+    """Host half of ``GPPlan.cross_validate``: validate the fold ids, sort every site's observations by fold (held-out
+    ones first, stable) and hand ``launch(order, start, ngroups, max_group)`` the int32 CPU tensors ``order`` (batch, n)
+    / ``start`` (batch, ngroups + 1) -- (n,) / (ngroups + 1,) for an unbatched plan."""
+    g = torch.as_tensor(groups)
+    if g.dtype.is_floating_point or g.dtype == torch.bool:
+        raise ValueError("fold ids must be integers")
+    g = g.detach().to("cpu", torch.int64)
+    batch, n = plan.batch, plan.n
+    if tuple(g.shape) != ((n,) if batch == 1 else (batch, n)):
+        raise ValueError(f"groups must have shape {(n,) if batch == 1 else (batch, n)}, got {tuple(g.shape)}")
+    g = g.reshape(batch, n).clone()
+    sizes = getattr(plan, "_site_sizes", None) or getattr(plan, "_sizes", None) or [n] * batch
+    for b in range(batch):
+        g[b, int(sizes[b]):] = -1
+    if int(g.min()) < -1:
+        raise ValueError("fold ids must be >= 0, or -1 for observations that are never held out")
+    if int(g.max()) < 0:
+        raise ValueError("no observation is held out")
+    ngroups = int(g.max()) + 1
+    if ngroups > n:
+        raise ValueError(f"fold ids must be below n = {n}")
+    order = torch.empty(batch, n, dtype=torch.int32)
+    start = torch.empty(batch, ngroups + 1, dtype=torch.int32)
+    max_group = 1
+    for b in range(batch):
+        key = torch.where(g[b] >= 0, g[b], torch.full_like(g[b], ngroups))
+        order[b] = torch.argsort(key, stable=True).to(torch.int32)
+        counts = torch.bincount(g[b][g[b] >= 0], minlength=ngroups)
+        start[b, 0] = 0
+        start[b, 1:] = torch.cumsum(counts, 0).to(torch.int32)
+        max_group = max(max_group, int(counts.max()))
+    if max_group_bound is not None:
+        if not max_group <= int(max_group_bound) <= n:
+            raise ValueError(f"max_group = {max_group_bound} must be between the largest fold ({max_group}) and n = {n}")
+        max_group = int(max_group_bound)
+    if batch == 1:
+        order, start = order[0], start[0]
+    return launch(order, start, ngroups, max_group)

@@ -1181,6 +1181,37 @@ int dgp_posterior_period_moments(dgp_plan* p, const double* theta, const void* X
   return wrap(rc, "dgp_posterior_period_moments");
 }
 
+static bool cv_sizes_ok(const dgp_plan* p, int ngroups, int64_t max_group) {
+  return p && ngroups >= 1 && ngroups <= p->n && max_group >= 1 && max_group <= p->n;
+}
+size_t dgp_cross_validate_workspace_bytes(const dgp_plan* p, int ngroups, int64_t max_group) {
+  if (!cv_sizes_ok(p, ngroups, max_group)) return 0;
+  return cross_validate_workspace_bytes(p->N, p->B, ngroups, max_group);
+}
+
+int dgp_cross_validate(dgp_plan* p, const int32_t* order, const int32_t* start, int ngroups, int64_t max_group, void* work,
+                       size_t work_bytes, double* resid, double* var, double* lpd, int32_t* info, void* stream) {
+  if (!p) return fail(DGP_E_ARG, "null plan");
+  if (!order || !start || !resid || !var || !lpd || !info) return fail(DGP_E_ARG, "dgp_cross_validate: null argument");
+  if (!cv_sizes_ok(p, ngroups, max_group))
+    return fail(DGP_E_ARG, "dgp_cross_validate: bad size (1 <= ngroups <= n, 1 <= max_group <= n)");
+  DGP_CHECK_PLAN(p);
+  if (!p->have_factor) return fail(DGP_E_STATE, "dgp_cross_validate: no factorisation in the plan (call dgp_factorize or dgp_fit_step)");
+  if (!work || work_bytes < dgp_cross_validate_workspace_bytes(p, ngroups, max_group))
+    return fail(DGP_E_WORKSPACE, "dgp_cross_validate: workspace missing or too small");
+  if (((uintptr_t)work & 255) != 0) return fail(DGP_E_ARG, "dgp_cross_validate: the work area must be 256-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  // K^^-1 (S) is read when the last step left it valid and never written; after a bare dgp_factorize it is dead and ignored
+  const void* S = p->have_inverse ? p->S : nullptr;
+  const int rc = DGP_BY_DTYPE(
+      p,
+      cross_validate<double>((const double*)p->Tm, (const double*)S, (const double*)p->alpha, p->N, (int)p->n, order, start, ngroups,
+                             max_group, work, resid, var, lpd, info, s, batch_of<double>(p)),
+      cross_validate<float>((const float*)p->Tm, (const float*)S, (const float*)p->alpha, p->N, (int)p->n, order, start, ngroups, max_group,
+                            work, resid, var, lpd, info, s, batch_of<float>(p)));
+  return wrap(rc, "dgp_cross_validate");
+}
+
 int dgp_plan_set_timing(dgp_plan* p, int enabled) {
   if (!p) return fail(DGP_E_ARG, "null plan");
   p->timing = enabled ? 1 : 0;
@@ -1227,17 +1258,21 @@ int dgp_stage_gram(dgp_plan* p, const double* theta, const void* noise, void* st
 int dgp_stage_potrf(dgp_plan* p, void* stream) {
   DGP_CHECK_PLAN(p);
   hipStream_t s = (hipStream_t)stream;
+  p->have_inverse = 0;  // S is the factorisation's scratch
   return wrap(DGP_BY_DTYPE(p, run_potrf<double>(p, s), run_potrf<float>(p, s)), "dgp_stage_potrf");
 }
 int dgp_stage_trtri(dgp_plan* p, void* stream) {
   DGP_CHECK_PLAN(p);
   hipStream_t s = (hipStream_t)stream;
+  p->have_inverse = 0;  // S is the inverse's scratch
   return wrap(DGP_BY_DTYPE(p, run_trtri<double>(p, s), run_trtri<float>(p, s)), "dgp_stage_trtri");
 }
 int dgp_stage_lauum(dgp_plan* p, void* stream) {
   DGP_CHECK_PLAN(p);
   hipStream_t s = (hipStream_t)stream;
-  return wrap(DGP_BY_DTYPE(p, run_lauum<double>(p, s), run_lauum<float>(p, s)), "dgp_stage_lauum");
+  const int rc = DGP_BY_DTYPE(p, run_lauum<double>(p, s), run_lauum<float>(p, s));
+  if (!rc) p->have_inverse = 1;
+  return wrap(rc, "dgp_stage_lauum");
 }
 int dgp_stage_solve(dgp_plan* p, const void* r, void* stream) {
   DGP_CHECK_PLAN(p);

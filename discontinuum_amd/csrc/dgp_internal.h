@@ -193,4 +193,13 @@ int posterior_period_moments(int mode, int model, int d, const T* V, long N, lon
                              const double* theta, const T* mu, const double* scale2, const double* w, const int* group, int P,
                              const T* ev, double* work, double* mean_out, double* cov_out, hipStream_t s, void* pre_scratch);
 
+// ---- dgp_crossval.hip: exact leave-one-out / leave-group-out cross-validation from T = L^-1, alpha and -- when it is valid --
+// S = K^^-1 (null otherwise).  order [B][n] / start [B][ngroups + 1]: group g of a site = order[start[g] .. start[g + 1]); every
+// group has at most max_group members.  resid / var [B][n], lpd / info [B][ngroups], all double / int whatever T is; `work`:
+// cross_validate_workspace_bytes.  Reads T, S, alpha only.
+size_t cross_validate_workspace_bytes(long N, int B, int ngroups, long max_group);
+template <typename T>
+int cross_validate(const T* Tm, const T* S, const T* alpha, long N, int n, const int* order, const int* start, int ngroups,
+                   long max_group, void* work, double* resid, double* var, double* lpd, int* info, hipStream_t s, Batch bt);
+
 }  // namespace dgp

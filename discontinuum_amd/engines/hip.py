@@ -669,5 +669,17 @@ class MarginalHIP(BaseModel):
         return aggregate(self, covariates, weights, freq=freq, ci=ci, pred_noise=pred_noise, return_cov=return_cov,
                          max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes)
 
+    @is_fitted
+    def cross_validate(self, folds="loo", ci=0.95, return_folds=False):
+        """Exact leave-one-out / leave-group-out cross-validation of the training observations at the fitted
+        hyperparameters, from the factorisation the engine holds (no refit; ``dgp_cross_validate``).  ``folds``: "loo", a
+        resample alias ("YE", "YE-SEP", "QE", "ME": one fold per period), an int k (contiguous blocks in time), ``("random",
+        k, seed)`` or an explicit array of fold ids.  -> Dataset of ``observed`` / ``predicted`` / ``se`` / ``lower`` /
+        ``upper`` / ``z`` / ``fold`` with ``elpd``, ``rmse``, ``coverage`` among its attributes; see
+        ``discontinuum_amd.validation.cross_validate``."""
+        from ..validation import cross_validate
+
+        return cross_validate(self, folds=folds, ci=ci, return_folds=return_folds)
+
     def build_model(self, X, y, **kwargs):
         raise NotImplementedError("This method must be implemented in a subclass")

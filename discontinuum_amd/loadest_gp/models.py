@@ -82,6 +82,15 @@ class LoadestGPMarginalHIP(LoadestDataMixin, MarginalHIP):
         return annual_flux(self, covariates, freq=freq, ci=ci, pred_noise=pred_noise, return_cov=return_cov,
                            max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes)
 
+    @is_fitted
+    def flux_bias(self, cv=None, folds="loo"):
+        """WRTDS's flux bias statistic on the sampled days, (sum P - sum O) / sum P with O the observed and P the
+        cross-validated mean concentration x flow; ``cv``: a Dataset from ``cross_validate`` (default: run it with
+        ``folds``).  See ``discontinuum_amd.validation.flux_bias``."""
+        from ..validation import flux_bias
+
+        return flux_bias(self, cv=cv, folds=folds)
+
     def flow_normalized_flux(self, daily, freq="YE", flow_window=None, ci=0.95, pred_noise=False, return_cov=False,
                              max_bytes=None):
         """Flow-normalized period loads (kg) with exact uncertainty -- WRTDS's FN flux: each day's load averaged over

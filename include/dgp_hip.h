@@ -256,6 +256,35 @@ int dgp_posterior_period_moments(dgp_plan* plan, const double* theta_host, const
                                  void* work_dev, size_t work_bytes, double* mean_out_dev, double* cov_out_dev,
                                  void* stream);
 
+/* Exact leave-one-out / leave-group-out cross-validation at FIXED hyperparameters from the factorisation the plan holds (after
+ * dgp_factorize or dgp_fit_step; DGP_E_STATE without one) -- no fold is refitted.  The reference has no counterpart: with
+ * gpytorch every fold is a new factorisation behind the `predict` call site (src/discontinuum/engines/gpytorch.py:599-626).
+ * With T = L^-1, alpha = K^^-1 r and a held-out index set B of b observations (Rasmussen & Williams 5.4.2, block form):
+ *     G_B = (K^^-1)_BB = T[:, B]^T T[:, B]       e_B = y_B - E[y_B | y_-B] = G_B^-1 alpha_B       C_B = Cov[y_B | y_-B] = G_B^-1
+ *     lpd_B = log p(y_B | y_-B) = -1/2 alpha_B^T e_B + 1/2 log|G_B| - b/2 log 2 pi
+ * (C_B is the covariance of the held-out OBSERVATIONS: their own noise is in K^).
+ *   order_dev  [batch][n] int32: observation indices sorted by group, held-out ones first (the rest of a row is ignored)
+ *   start_dev  [batch][ngroups + 1] int32: group g = order[start[g] .. start[g + 1]); empty groups are allowed (lpd 0)
+ *   max_group  an upper bound of every group's size (1 .. n); it selects the route and sizes the work area:
+ *              1: one pass over the lower triangle of T (column sums of squares, K^^-1 never formed);  <= 64: one workgroup
+ *              per (group, site) with G_B, its factor and the solves in LDS;  larger: blocks of order round_up(max_group, 128)
+ *              in the work area -- T[k0:, B] packed, G_B on the MFMA tile core (k-tiles last to first), the library's batched
+ *              potrf / trtri -- in chunks of at most 1024 groups.  When the last step was a dgp_fit_step, G_B is a gather of the
+ *              plan's K^^-1 instead; after a bare dgp_factorize that buffer is dead and is not touched.
+ *   resid_dev / var_dev [batch][n] doubles: e_i and diag C_B at the observations' own positions, 0 for observations no group
+ *              holds;  lpd_dev [batch][ngroups] doubles;  info_dev [batch][ngroups] int32: 0, or the 1-based failing pivot of G_B
+ *              (the group's results are then NaN).
+ * The indices are the caller's to validate (discontinuum_amd.backend.GPPlan.cross_validate does): the kernels clamp what they
+ * read from order / start, so bad content gives wrong numbers or a set info, never an access out of bounds.  The plan's L, T,
+ * alpha and (valid) K^^-1 are only read: dgp_predict, dgp_mean_vjp, dgp_stage_grad answer bitwise the same before and after.
+ * All results are double whatever the plan's dtype (float32 plans: only the operands T, alpha are float32).  Batched plans:
+ * gridDim.z = sites, dgp_plan_set_site_sizes respected, a site's result does not depend on its batch.  No floating-point
+ * atomics: bitwise repeatable.  DGP_E_ARG for bad sizes (1 <= ngroups <= n, 1 <= max_group <= n; the query then returns 0). */
+size_t dgp_cross_validate_workspace_bytes(const dgp_plan* plan, int ngroups, int64_t max_group);
+int dgp_cross_validate(dgp_plan* plan, const int32_t* order_dev, const int32_t* start_dev, int ngroups, int64_t max_group,
+                       void* work_dev, size_t work_bytes, double* resid_dev, double* var_dev, double* lpd_dev, int32_t* info_dev,
+                       void* stream);
+
 /* Predictive mean only, and its vector-Jacobian product -- what the rating-gp monotonicity penalty
  * differentiates (src/rating_gp/models/gpytorch.py:130-187: mean of likelihood(model(x_grid)) with grad).
  *   dgp_predict_mean : mean_dev[j] = K(x*_j, X) alpha                                  (m entries)
