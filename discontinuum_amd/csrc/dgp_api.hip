@@ -130,6 +130,8 @@ static int default_lookahead() { return 2; }  // lookahead on: the group-ahead s
 // gain from a longer K per read-modify-write pass over the trailing matrix (measured, one site: n = 16384 fp32 43.1 -> 42.1 ms
 // per fit step with groups of 4, fp64 79.2 -> 77.2; n = 65536 fp32 2305 -> 2239 (4) -> 2216 ms (8); n = 8192: 12.44 -> 12.50
 // with 4).  Batched plans: 4, 6 and 8 give the same factorisation time (n = 8192 x 32: 101.7 / 101.9 / 102.5 ms).
+// Batched fp64 plans of 32 sites or more run these groups LEFT-LOOKING (dgp_chol.hip::potrf_scheduled, potrf_schedule_auto): each group
+// of 4 columns is updated once, with everything to its left, instead of every trailing tile once per group at K = 512.
 static int group_size(int lookahead, int batch, long nbk) {
   if (!lookahead) return 0;
   if (const char* e = getenv("DGP_GROUP")) return atoi(e) < 2 ? 2 : atoi(e);
@@ -318,6 +320,26 @@ int dgp_plan_set_option(dgp_plan* p, int key, int64_t value) {
     case DGP_OPT_GROUP_GEMM:
       p->tune.group_gemm = value ? 1 : 0;
       return 0;
+    case DGP_OPT_POTRF_SCHEDULE:
+      if (value < 0 || value > 1) return fail(DGP_E_ARG, "dgp_plan_set_option: value out of range");
+      p->tune.potrf_schedule = (int)value;
+      return 0;
+    case DGP_OPT_POTRF_SWEEP:
+    case DGP_OPT_POTRF_TAIL:
+    case DGP_OPT_POTRF_TAIL_SWEEP:
+      if (value < 0 || value > (1 << 20)) return fail(DGP_E_ARG, "dgp_plan_set_option: value out of range");
+      (key == DGP_OPT_POTRF_SWEEP ? p->tune.potrf_sweep : key == DGP_OPT_POTRF_TAIL ? p->tune.potrf_tail : p->tune.potrf_tail_sweep) = (int)value;
+      return 0;
+    case DGP_OPT_POTRF_SOLVE:
+      p->tune.potrf_solve = value ? 1 : 0;
+      return 0;
+    case DGP_OPT_POTRF_OVERLAP:
+      p->tune.potrf_overlap = value ? 1 : 0;
+      return 0;
+    case DGP_OPT_POTRF_SLOTS:
+      if (value < 1 || value > (1 << 20)) return fail(DGP_E_ARG, "dgp_plan_set_option: value out of range");
+      p->tune.potrf_slots = (int)value;
+      return 0;
     case DGP_OPT_REFINE:
       if (p->dtype != DGP_F32 && value) return fail(DGP_E_ARG, "dgp_plan_set_option: refinement applies to float32 plans");
       p->refine = value ? 1 : 0;
@@ -338,6 +360,15 @@ int dgp_plan_get_option(const dgp_plan* p, int key, int64_t* value) {
     case DGP_OPT_CHAIN_YIELD: *value = p->tune.chain_yield; return 0;
     case DGP_OPT_FUSED_GRAD: *value = p->tune.fused_grad; return 0;
     case DGP_OPT_GROUP_GEMM: *value = p->tune.group_gemm; return 0;
+    case DGP_OPT_POTRF_SCHEDULE:  // (the selector's choice for this plan's shape unless set)
+      *value = p->tune.potrf_schedule < 0 ? (p->B >= 4 ? potrf_schedule_auto(p->B, p->N / DGP_TILE_HOST, p->elem) : 0) : p->tune.potrf_schedule;
+      return 0;
+    case DGP_OPT_POTRF_SWEEP: *value = p->tune.potrf_sweep; return 0;
+    case DGP_OPT_POTRF_SOLVE: *value = p->tune.potrf_solve; return 0;
+    case DGP_OPT_POTRF_OVERLAP: *value = p->tune.potrf_overlap; return 0;
+    case DGP_OPT_POTRF_SLOTS: *value = p->tune.potrf_slots; return 0;
+    case DGP_OPT_POTRF_TAIL: *value = p->tune.potrf_tail; return 0;
+    case DGP_OPT_POTRF_TAIL_SWEEP: *value = p->tune.potrf_tail_sweep; return 0;
     default: return fail(DGP_E_ARG, "dgp_plan_get_option: unknown option");
   }
 }

@@ -15,11 +15,13 @@
 // Flops per fit: N^3/3 (potrf) + N^3/3 (trtri) + N^3/3 (lauum) -- MFMA roofline.
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <mutex>
 #include "dgp_diag.h"
 #include "dgp_gemm.h"
 #include "dgp_gemm_dma.h"
 #include "dgp_internal.h"
+#include "dgp_schedule.h"
 
 namespace dgp {
 
@@ -206,11 +208,32 @@ const Tuning& default_tuning() {
     // per step, 32 x n = 8192 280.2 / 280.1, 128 x n = 2048 26.1 / 26.0 (scripts/env_ab.py, one box): the factorisation's wall
     // time is the SUM of its full-GPU kernels at their rates whichever way the chain is cut (EXPERIMENTS.md, round 5)
     v.group_gemm = getenv("DGP_GROUP_GEMM") ? atoi(getenv("DGP_GROUP_GEMM")) : 0;
+    // the batched factorisation from a schedule (potrf_scheduled): 0 = the group-ahead schedule
+    v.potrf_schedule = getenv("DGP_POTRF_SCHEDULE") ? (atoi(getenv("DGP_POTRF_SCHEDULE")) != 0 ? 1 : 0) : -1;  // -1: potrf_schedule_auto
+    v.potrf_sweep = getenv("DGP_POTRF_SWEEP") ? std::max(0, atoi(getenv("DGP_POTRF_SWEEP"))) : 0;
+    v.potrf_tail = getenv("DGP_POTRF_TAIL") ? std::max(0, atoi(getenv("DGP_POTRF_TAIL"))) : 0;
+    v.potrf_tail_sweep = getenv("DGP_POTRF_TAIL_SWEEP") ? std::max(0, atoi(getenv("DGP_POTRF_TAIL_SWEEP"))) : 0;
+    v.potrf_solve = getenv("DGP_POTRF_SOLVE") ? atoi(getenv("DGP_POTRF_SOLVE")) : 0;
+    v.potrf_overlap = getenv("DGP_POTRF_OVERLAP") ? atoi(getenv("DGP_POTRF_OVERLAP")) : 0;
+    v.potrf_slots = getenv("DGP_POTRF_SLOTS") ? std::max(1, atoi(getenv("DGP_POTRF_SLOTS"))) : 768;
     if (v.syrk_slots < 1) v.syrk_slots = 1;
     return v;
   }();
   return t;
 }
+// The selector of the batched factorisation's schedule (Tuning::potrf_schedule < 0): 1 = left-looking (potrf_scheduled) where it
+// was measured to win, 0 = group-ahead elsewhere.  Measured on one box in alternating processes (scripts/env_ab.py, wall ms per fit
+// step, group-ahead / left-looking with the panel chain; EXPERIMENTS.md "Left-looking group updates"):
+//   fp64  32 x n = 8192 277.4 / 272.9   64 x 4096 79.77 / 78.02   128 x 2048 25.98 / 25.10   256 x 1024 8.79 / 8.44      wins 1.6-4 %
+//         8 x 8192 72.27 / 74.38   4 x 8192 38.82 / 40.57   4 x 16384 265.4 / 272.4                                      LOSES 2.6-4.5 %
+// The schedule runs everything on one stream: the diagonal blocks (one workgroup per site, ~37 us each, nbk of them) are no longer
+// hidden under a bulk launch, a cost per panel that does not shrink with the batch, while the gain (long-K tiles stored once,
+// chain kernels that no longer share the GPU with a bulk launch) grows with it -- hence a rule on the batch size: from 32 sites,
+// the smallest batch measured to win (8 loses; nothing between was measured).
+//   fp32  32 x 8192 145.75 / 144.33, 64 x 4096 44.92 / 44.00 (wins 1-2 %), but fp32 tiles sum each pass from zero and subtract once:
+//         one pass of K = 7680 instead of fifteen of K = 512 rounds the NLL of 32 x 8192 to 4.6e-6 of the fp64 value instead of
+//         4e-8 (inside the fp32 bounds, 1e-4 n / 1024, but a hundred times today's error): fp32 plans keep the group-ahead schedule.
+int potrf_schedule_auto(int B, long nbk, int elem) { return (elem == 8 && B >= 32 && nbk > 4) ? 1 : 0; }
 // grid shape of one bulk launch: whole rounds of full tiles + the remainder cut into `split` pieces
 struct SyrkShape {
   int nfull, split;
@@ -267,6 +290,49 @@ __global__ __launch_bounds__(256, (TileCore<T, true, true>::OCC)) void syrk_col1
   const int jc = jcol + (int)blockIdx.z % ncol;
   if ((int)blockIdx.x >= nbk - jc) return;  // the later columns are shorter
   syrk_tile<T, 128, 128, false, CMODE>(A, ld, k, nk, (long)(jc + (int)blockIdx.x) * NB, (long)jc * NB, smem);
+}
+
+// UPDATE of a column STRIP (dgp_schedule.h; the batched left-looking schedule): block columns [c0, c0 + ncol), block rows
+// [max(r0, column), r1), all k-blocks [k, k + nk) in ONE pass -- K = 128 nk is as long as everything left of the strip, and each
+// tile of C is read and stored once.  r0 == c0 (the strip with its diagonal block: `ntri` tiles of the triangle, then whole rows)
+// or r0 >= c0 + ncol (whole rows only, ntri = 0).  `nt` tiles per site.
+// ONE grid over the tiles of ALL sites (site-major, no blockIdx.z): every tile of a launch costs the same and is long (at
+// n = 8192 a round of tiles is 0.18 ms per group to the left), so the partial last round is what the launch loses -- the cut
+// remainder (SyrkShape over the whole batch, Tuning::potrf_slots) must be the LAST workgroups dispatched, not each site's.
+// Tile order: row by row, the ncol column tiles of a row block adjacent -- they share their A operand (128 x K), and every row
+// of a site shares the ncol B operands -- and consecutive on ONE XCD (xcd_remap): at 16 flop per operand byte a tile without
+// reuse would ask HBM for ~4.5 TB/s.
+template <typename T>
+__global__ __launch_bounds__(256, (TileCore<T, true, true>::OCC)) void syrk_strip_kernel(T* __restrict__ A, long ld, int k, int nk, int c0, int ncol,
+                                                                                         int rrect, int ntri, int nt, int nfull, int split, long bs) {
+  __shared__ T smem[TileCore<T, true, true>::SMEM_ELEMS];
+  static_assert(TileCore<T, true, true, 64, 128>::SMEM_ELEMS <= TileCore<T, true, true>::SMEM_ELEMS &&
+                    TileCore<T, true, true, 64, 64>::SMEM_ELEMS <= TileCore<T, true, true>::SMEM_ELEMS,
+                "the cut remainder's register-staged tiles must fit the ring's LDS");
+  const int b = (int)blockIdx.x;
+  const int l = b < nfull ? xcd_remap(b, nfull) : nfull + (b - nfull) / split;  // < sites x nt (the grid: nfull + split (sites nt - nfull))
+  const int t = l % nt;
+  A += (long)(l / nt) * bs;
+  int bi, bj;
+  if (t < ntri) {
+    tri_decode(t, bi, bj);
+    bi += c0;
+  } else {
+    bi = rrect + (t - ntri) / ncol;
+    bj = (t - ntri) % ncol;
+  }
+  const long row0 = (long)bi * NB, col0 = (long)(c0 + bj) * NB;
+  if (b < nfull) {
+    syrk_tile<T, 128, 128>(A, ld, k, nk, row0, col0, smem);
+    return;
+  }
+  const int part = (b - nfull) % split;
+  if (split == 2) {
+    syrk_tile<T, 64, 128>(A, ld, k, nk, row0 + 64 * part, col0, smem);
+  } else {
+    if (row0 == col0 && part == 1) return;  // strictly upper quadrant of a diagonal tile
+    syrk_tile<T, 64, 64>(A, ld, k, nk, row0 + 64 * (part >> 1), col0 + 64 * (part & 1), smem);
+  }
 }
 
 // launch the LDS-resident diagonal-block kernel (needs > 64 KB of dynamic LDS: opt in once per instantiation).
@@ -421,6 +487,81 @@ __global__ __launch_bounds__(256, (TileCore<T, true, true>::OCC)) void trsm_grou
 template <typename T>
 static void trtri_group(const T* L, T* Tm, T* W, long N, int k0, int G, hipStream_t s, Batch bt);
 
+// ---- the factorisation of a batch from a schedule (dgp_schedule.h; DGP_OPT_POTRF_SCHEDULE = 1) -------------------------------
+// Today's group-ahead schedule below is right-looking in groups: every trailing tile is read, updated and written once per
+// group at K = 128 G.  Here each group of columns is updated ONCE, just before it is factored, with everything to its left
+// (left-looking at group level: K = 128 k0, each tile stored once), optionally in super-groups with a right-looking sweep
+// between them (Tuning::potrf_sweep).  Every tile still receives its k-blocks in ascending gap-free order, so with the
+// panel-by-panel chain (potrf_solve = 0) the fp64 factor is BITWISE the group-ahead schedule's (tests/test_gpu_potrf_schedule.py);
+// sched::check() asserts that order for the schedule that is about to run.  fp32 sums each pass from zero: fewer, longer passes
+// round differently, within the same bounds.
+template <typename T>
+static int potrf_scheduled(T* A, long N, T* Tinv, T* logdet, int* info, int G, hipStream_t s, hipStream_t s2, hipEvent_t* ev,
+                           hipEvent_t* syrk_ev, int* n_syrk, double* syrk_flop, const Batch& bt) {
+  const int nbk = (int)(N / NB);
+  sched::Cut cut;
+  cut.sweep = bt.tuning().potrf_sweep;
+  cut.tail = bt.tuning().potrf_tail;
+  cut.tail_sweep = bt.tuning().potrf_tail_sweep;
+  cut.solve = bt.tuning().potrf_solve && bt.W != nullptr;
+  cut.overlap = bt.tuning().potrf_overlap;
+  const std::vector<sched::Op> ops = sched::left_looking(nbk, G, cut);
+  if (!sched::check(ops, nbk).empty()) return (int)hipErrorInvalidValue;  // (a generator bug: never run an unchecked schedule)
+  const unsigned Bz = (unsigned)bt.B;
+  const double tile_flop = 2.0 * NB * NB * NB;
+  hipStream_t st[2] = {s, s2};
+  int ns = 0, nsync = 0;
+  double flop = 0.0;
+  for (const sched::Op& o : ops) {
+    hipStream_t so = st[o.stream];
+    switch (o.kind) {
+      case sched::SYNC:
+        hipEventRecord(ev[nsync], so);  // (at most two per group: the pool holds 3 nbk)
+        hipStreamWaitEvent(st[o.c0], ev[nsync], 0);
+        ++nsync;
+        break;
+      case sched::UPDATE: {
+        const long nt = sched::update_tiles(o);
+        const bool timed = syrk_ev != nullptr && ns < nbk;  // (the pool holds 2 nbk events)
+        if (timed) hipEventRecord(syrk_ev[2 * ns], so);
+        {
+          // (a sweep of the whole trailing triangle is the strip of all remaining columns: its triangle only, row by row)
+          const SyrkShape sh((int)(nt * bt.B), bt.tuning().potrf_slots);
+          const int ncol = o.c1 - o.c0, h = (o.r0 == o.c0) ? std::min(o.r1, o.c1) - o.c0 : 0;
+          syrk_strip_kernel<T><<<dim3(sh.grid, 1, 1), 256, 0, so>>>(A, N, o.ka, o.kb - o.ka, o.c0, ncol, std::max(o.r0, o.c1), h * (h + 1) / 2, (int)nt,
+                                                                     sh.nfull, sh.split, bt.ws);
+        }
+        if (timed) {
+          hipEventRecord(syrk_ev[2 * ns + 1], so);
+          flop += tile_flop * (double)nt * (o.kb - o.ka) * bt.B;
+          ++ns;
+        }
+        break;
+      }
+      case sched::PANELS:
+        for (int k = o.c0; k < o.c1; ++k) {
+          if (k > o.c0) syrk_col_kernel<T><<<dim3(2 * (o.r1 - k), 2, Bz), 256, 0, so>>>(A, N, o.c0, k - o.c0, k, o.r1, 1, bt.ws);
+          launch_diag<T>(A, N, (long)k * NB, Tinv, logdet, info, so, bt, k == 0);
+          if (k + 1 < o.r1) trsm_kernel<T><<<dim3(2 * (o.r1 - k - 1), 1, Bz), 256, 0, so>>>(A, Tinv, N, k, bt.ws);
+        }
+        break;
+      case sched::SOLVE:
+        trtri_group<T>(A, Tinv, (T*)bt.W, N, o.c0, o.c1 - o.c0, so, bt);
+        trsm_group_kernel<T><<<dim3((unsigned)(o.r1 - o.r0), 1, Bz), 256, 0, so>>>(A, Tinv, N, o.c0, o.c1 - o.c0, bt.ws);
+        break;
+    }
+  }
+  if (n_syrk) *n_syrk = ns;
+  if (syrk_flop) *syrk_flop = flop;
+  return (int)hipGetLastError();
+}
+// where the schedule above applies: batched plans (the sites fill each other's gaps; one site keeps pairs, the split chain and
+// the early inverse), groups of at least 4 panels, no checkpoints, no hand-over
+static bool scheduled_applies(const Batch& bt, long nbk, int elem, int G, int nck, int q_stop, const PotrfCarry* carry, hipStream_t s2, hipEvent_t* ev) {
+  const int mode = bt.tuning().potrf_schedule < 0 ? potrf_schedule_auto(bt.B, nbk, elem) : bt.tuning().potrf_schedule;
+  return bt.B >= 4 && mode != 0 && G >= 4 && nbk > G && nck == 0 && q_stop < 0 && carry == nullptr && s2 != nullptr && ev != nullptr;
+}
+
 template <typename T>
 int potrf(T* A, long N, T* Tinv, T* logdet, int* info, int lookahead, hipStream_t s, hipStream_t s2, hipEvent_t* ev,
           hipEvent_t* syrk_ev, int* n_syrk, double* syrk_flop, int nck, const int* ck_blocks, hipEvent_t* ck_ev,
@@ -461,6 +602,8 @@ int potrf(T* A, long N, T* Tinv, T* logdet, int* info, int lookahead, hipStream_
     if (syrk_flop) *syrk_flop = flop;
     return (int)hipGetLastError();
   }
+  if (scheduled_applies(bt, nbk, (int)sizeof(T), lookahead, nck, q_stop, carry, s2, ev))
+    return potrf_scheduled<T>(A, N, Tinv, logdet, info, lookahead > 8 ? 8 : lookahead, s, s2, ev, syrk_ev, n_syrk, syrk_flop, bt);
   {
     // GROUP-AHEAD schedule.  Group q = G consecutive panels (G = 2: pairs, for one site; G = 4 for batched plans,
     // where the chain is shared by the batch and the bulk update gains from K = 512).  The chain on stream s factors

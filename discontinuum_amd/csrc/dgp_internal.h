@@ -28,8 +28,17 @@ struct Tuning {
   int fused_grad;         // the gradient contraction runs in the epilogue of K^^-1's 128 x 128 tiles (dgp_fused.hip) when it applies (1)
   int group_gemm;         // batched plans: a panel group's rows below its diagonal block are solved by ONE GEMM against the inverted
                           // G x G-block diagonal block instead of G trsm + G - 1 column-update launches (dgp_chol.hip::potrf)
+  int potrf_schedule;     // batched plans: -1 = by shape (potrf_schedule_auto), 0 = the group-ahead schedule (right-looking, K = 128 G passes), 1 = the left-looking family of
+                          // dgp_schedule.h (each column group updated once, K = everything to its left); the three below are its cut points
+  int potrf_sweep;        // panels per super-group (right-looking sweeps between them), 0 = none: pure left-looking
+  int potrf_tail;         // the last potrf_tail block columns form a super-group of their own (0 = none): few, long tiles otherwise
+  int potrf_tail_sweep;   // panels per super-group inside that tail (0 = the whole tail)
+  int potrf_solve;        // the rows below a group's diagonal block by ONE GEMM (trsm_group_kernel) -- not bitwise the panel chain
+  int potrf_slots;        // workgroup slots of a round of that schedule's strip UPDATEs, over the whole batch (768: three per CU)
+  int potrf_overlap;      // with potrf_solve: the part of a group's update below its diagonal block runs on the bulk stream beside the block's panels
 };
 const Tuning& default_tuning();
+int potrf_schedule_auto(int B, long nbk, int elem);  // the schedule a batched plan of B sites of nbk block columns (elem bytes per element) runs when Tuning::potrf_schedule < 0
 struct Batch {
   int B = 1;
   long ws = 0;

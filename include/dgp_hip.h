@@ -161,6 +161,21 @@ int dgp_plan_set_lookahead(dgp_plan* plan, int level);
  * association of the same sums: results agree to rounding (fp64 ~1e-13).  Replaces part of what gpytorch's Cholesky does
  * at engines/gpytorch.py:350-353. */
 #define DGP_OPT_GROUP_GEMM 8
+/* batched plans of 4 or more sites, the SCHEDULE of the factorisation: 0 = group-ahead (right-looking: every trailing tile is
+ * read, updated and stored once per group of 4 panels, K = 512), 1 = left-looking at group level (each group of columns is
+ * updated once, just before it is factored, with everything to its left: long K, each tile stored once; csrc/dgp_schedule.h).
+ * Every tile receives its k-blocks in ascending gap-free order either way: with DGP_OPT_POTRF_SOLVE = 0 the float64 results
+ * are bitwise the same.  DGP_OPT_POTRF_SWEEP: panels per super-group (right-looking sweeps between super-groups, left-looking
+ * inside; 0 = none).  DGP_OPT_POTRF_SOLVE = 1: the rows below a group's diagonal block by one GEMM (as DGP_OPT_GROUP_GEMM;
+ * agrees to rounding).  DGP_OPT_POTRF_OVERLAP = 1 (with SOLVE): that part of the group's update runs beside the block's panels.
+ * The Cholesky inside the reference's mll(output, y), engines/gpytorch.py:350-353. */
+#define DGP_OPT_POTRF_SCHEDULE 9
+#define DGP_OPT_POTRF_SWEEP 10
+#define DGP_OPT_POTRF_SOLVE 11
+#define DGP_OPT_POTRF_OVERLAP 12
+#define DGP_OPT_POTRF_SLOTS 13 /* workgroup slots of a round of the strip updates, whole batch (768); tests force small rounds */
+#define DGP_OPT_POTRF_TAIL 14       /* the last this-many block columns are a super-group of their own (0 = none) */
+#define DGP_OPT_POTRF_TAIL_SWEEP 15 /* panels per super-group inside that tail (0 = the whole tail) */
 int dgp_plan_set_option(dgp_plan* plan, int key, int64_t value);
 int dgp_plan_get_option(const dgp_plan* plan, int key, int64_t* value_out);
 int dgp_plan_buffer(const dgp_plan* plan, int which, void** dev_ptr, int64_t* ld);
