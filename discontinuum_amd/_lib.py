@@ -90,6 +90,9 @@ SIGNATURES = {
     "dgp_posterior_period_moments": (_i, [_vp, _dp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp, _vp, _vp]),
     "dgp_cross_validate_workspace_bytes": (_sz, [_vp, _i, _i64]),
     "dgp_cross_validate": (_i, [_vp, _vp, _vp, _i, _i64, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "dgp_model_nterms": (_i, [_i, _i]),
+    "dgp_predict_terms_workspace_bytes": (_sz, [_vp, _i64]),
+    "dgp_predict_terms": (_i, [_vp, _dp, _vp, _i64, _vp, _sz, _vp, _vp, _vp]),
     "dgp_mean_vjp_workspace_bytes": (_sz, [_vp, _i64]),
     "dgp_predict_mean": (_i, [_vp, _dp, _vp, _i64, _vp, _sz, _vp, _vp]),
     "dgp_mean_vjp": (_i, [_vp, _dp, _vp, _i64, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),

@@ -65,6 +65,7 @@ class GPPlan:
         if self.ntheta < 0:
             raise ValueError(f"model {model!r} does not support d={d}")
         self.N = int(self.lib.dgp_padded_n(self.n))
+        self.nterms = int(self.lib.dgp_model_nterms(mid, self.d))  # additive parts of the covariance (predict_terms)
         handle = C.c_void_p()
         _lib.check(self.lib.dgp_plan_create(mid, _DTYPES[dtype], self.n, self.d, C.byref(handle)), "dgp_plan_create")
         self._h = handle
@@ -222,6 +223,53 @@ class GPPlan:
                     mean[:, lo:hi] = mo
                     var[:, lo:hi] = vo
         return mean, var
+
+    def predict_terms(self, theta, Xs: torch.Tensor, chunk: int | None = None, return_cov: bool = True):
+        """Latent posterior of every ADDITIVE PART of the covariance at Xs (m, d) from the held factorisation
+        (``dgp_predict_terms``): -> (mean (C, m), cov (C (C + 1) / 2, m)) with C = ``self.nterms`` parts in the model's
+        order (loadest: seasonal, covariates, residual; rating: shift_1, shift_2, bend, base, periodic; composite: its
+        terms).  ``cov[c (c + 1) / 2 + c']`` (c' <= c) is the posterior covariance of parts c and c' at each point; the
+        means sum to ``predict``'s mean and the full C x C covariance to its variance.  Batched plans: Xs (batch, m, d),
+        theta (batch, ntheta) -> (batch, C, m), (batch, C (C + 1) / 2, m).  ``return_cov=False`` -> (mean, None).
+        ``chunk`` = points per launch sequence; the work area is batch x 2 C N x chunk elements, so the default is
+        16384 // (batch C) rounded down to a multiple of 128 (at least 128)."""
+        Cn = self.nterms
+        Pn = Cn * (Cn + 1) // 2
+        if chunk is None:
+            chunk = max(128, (16384 // (self.batch * Cn)) // 128 * 128)
+        lead = () if self.batch == 1 else (self.batch,)
+        if not (torch.is_tensor(Xs) and Xs.is_cuda and Xs.dtype == self.dtype and Xs.dim() == 2 + len(lead)
+                and Xs.shape[-1] == self.d and tuple(Xs.shape[:-2]) == lead):
+            raise ValueError(f"Xs must be a {lead + ('m', self.d)} {self.dtype} CUDA tensor")
+        th = _theta_array(theta, self.ntheta * self.batch)
+        m = Xs.shape[-2]
+        mean = torch.empty(lead + (Cn, m), dtype=self.dtype, device=self.device)
+        cov = torch.empty(lead + (Pn, m), dtype=self.dtype, device=self.device) if return_cov else None
+        with torch.cuda.device(self.device):
+            for lo in range(0, m, chunk):
+                hi = min(lo + chunk, m)
+                whole = lo == 0 and hi == m
+                xs = Xs[..., lo:hi, :].contiguous()
+                need = int(self.lib.dgp_predict_terms_workspace_bytes(self._h, hi - lo))
+                ws = getattr(self, "_terms_ws", None)
+                if ws is None or ws.numel() < need + 256:
+                    self._terms_ws = None
+                    self._terms_ws = ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+                base = ws.data_ptr()
+                base += (-base) % 256
+                # a chunk is a column range of the (..., C, m) results: stage it
+                mo = mean if whole else torch.empty(lead + (Cn, hi - lo), dtype=self.dtype, device=self.device)
+                co = cov if (whole or cov is None) else torch.empty(lead + (Pn, hi - lo), dtype=self.dtype, device=self.device)
+                _lib.check(
+                    self.lib.dgp_predict_terms(self._h, th, _ptr(xs), hi - lo, C.c_void_p(base), need, _ptr(mo),
+                                               _ptr(co) if co is not None else None, _stream()),
+                    "dgp_predict_terms",
+                )
+                if not whole:
+                    mean[..., lo:hi] = mo
+                    if cov is not None:
+                        cov[..., lo:hi] = co
+        return mean, cov
 
     # ------------------------------------------------------------------ cross-validation
     def cross_validate(self, groups, max_group=None):

@@ -1050,6 +1050,55 @@ static int post_period(dgp_plan* p, const double* theta, const void* Xs, int64_t
                                      group, P, (const T*)ev, pm, mean_out, cov_out, s, p->pre);
 }
 
+// ---- the posterior of the covariance's additive parts (dgp_terms.hip).  Work area per site: the test points' SoA copy, the C
+// cross Grams side by side (N x C M), V = T Ks of the same shape, the parts' prior variances (C M) and the slab partials.
+struct TermsLayout {
+  size_t Xst, Ks, V, kss, part, total;
+};
+static TermsLayout terms_layout(const dgp_plan* p, int64_t m) {
+  const size_t M = (size_t)round_up(m, DGP_TILE_HOST), e = p->elem, N = (size_t)p->N;
+  const size_t C = (size_t)model_nterms(p->model, p->d);
+  TermsLayout L;
+  size_t o = 0;
+  L.Xst = o; o += align_up(e * M * p->d);
+  L.Ks = o; o += align_up(e * N * C * M);
+  L.V = o; o += align_up(e * N * C * M);
+  L.kss = o; o += align_up(e * C * M);
+  L.part = o; o += align_up(e * (size_t)terms_partials((int)C, (long)M));
+  L.total = o;
+  return L;
+}
+
+template <typename T>
+static int predict_terms(dgp_plan* p, const double* theta, const void* Xs, int64_t m, void* work, void* mean, void* cov,
+                         hipStream_t s) {
+  const TermsLayout L = terms_layout(p, m);
+  const long M = round_up(m, DGP_TILE_HOST);
+  const int C = model_nterms(p->model, p->d);
+  const long wbs = p->B > 1 ? (long)(L.total / sizeof(T)) : 0;
+  const Batch bt = batch_of<T>(p);
+  char* w = (char*)work;
+  T* Xst = (T*)(w + L.Xst);
+  T* Ks = (T*)(w + L.Ks);
+  T* V = (T*)(w + L.V);
+  T* kss = (T*)(w + L.kss);
+  Batch wb;  // the test points: [B][m][d] -> SoA in the work area
+  wb.B = p->B;
+  wb.ws = wbs;
+  int rc = pack_x<T>((const T*)Xs, (int)m, p->d, M, Xst, s, wb);
+  if (rc) return rc;
+  {
+    PreSlot slot(p, s);
+    if ((rc = gram_cross_terms<T>(p->model, p->d, (const T*)p->Xt, p->N, (int)p->n, Xst, M, (int)m, theta, Ks, s, bt, wbs, p->pre,
+                                  slot.staging)))
+      return rc;
+  }
+  wb.ws = 0;
+  if ((rc = gram_diag_terms<T>(p->model, p->d, Xst, M, (int)m, theta, kss, s, wb, wbs, p->pre))) return rc;
+  if ((rc = predict_v<T>((const T*)p->Tm, p->N, Ks, (long)C * M, V, s, bt, wbs))) return rc;
+  return terms_reduce<T>(C, V, Ks, p->N, M, (int)m, (const T*)p->alpha, kss, (T*)(w + L.part), (T*)mean, (T*)cov, s, bt, wbs);
+}
+
 #define DGP_BY_DTYPE(p, CALL64, CALL32) ((p)->dtype == DGP_F64 ? (CALL64) : (CALL32))
 #define DGP_CHECK_PLAN(p)                                                        \
   if (!(p)) return fail(DGP_E_ARG, "null plan");                                 \
@@ -1123,6 +1172,25 @@ int dgp_posterior_cov(dgp_plan* p, const double* theta, const void* Xs, int64_t 
   int rc = DGP_BY_DTYPE(p, post_cov<double>(p, theta, Xs, m, work, mean, cov, s),
                         post_cov<float>(p, theta, Xs, m, work, mean, cov, s));
   return wrap(rc, "dgp_posterior_cov");
+}
+
+int dgp_model_nterms(int model, int d) { return model_nterms(model, d); }
+
+size_t dgp_predict_terms_workspace_bytes(const dgp_plan* p, int64_t m) {
+  return (p && m > 0) ? terms_layout(p, m).total * (size_t)p->B : 0;
+}
+
+int dgp_predict_terms(dgp_plan* p, const double* theta, const void* Xs, int64_t m, void* work, size_t work_bytes, void* mean,
+                      void* cov, void* stream) {
+  if (!p) return fail(DGP_E_ARG, "dgp_predict_terms: null plan");
+  if (!theta || !Xs || !work || !mean || m <= 0) return fail(DGP_E_ARG, "dgp_predict_terms: null argument or m <= 0");
+  if (!p->ws) return fail(DGP_E_WORKSPACE, "plan has no workspace: call dgp_plan_set_workspace");
+  if (!p->have_factor) return fail(DGP_E_STATE, "dgp_predict_terms: no factorisation in the plan (call dgp_factorize)");
+  if (work_bytes < dgp_predict_terms_workspace_bytes(p, m)) return fail(DGP_E_WORKSPACE, "dgp_predict_terms: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = DGP_BY_DTYPE(p, predict_terms<double>(p, theta, Xs, m, work, mean, cov, s),
+                              predict_terms<float>(p, theta, Xs, m, work, mean, cov, s));
+  return wrap(rc, "dgp_predict_terms");
 }
 
 size_t dgp_mean_vjp_workspace_bytes(const dgp_plan* p, int64_t m) { return (p && m > 0) ? vjp_layout(p, m).total * (size_t)p->B : 0; }

@@ -1665,11 +1665,17 @@ __global__ __launch_bounds__(256) void predict_finish_kernel(const T* __restrict
 }
 
 template <typename T>
+int predict_v(const T* Tm, long N, const T* Ks, long M, T* V, hipStream_t s, Batch bt, long wbs) {
+  dim3 grid((unsigned)(M / NB), (unsigned)(N / NB), (unsigned)bt.B);
+  predict_v_kernel<T><<<grid, 256, 0, s>>>(Tm, N, Ks, M, V, bt.ws, wbs);
+  return (int)hipGetLastError();
+}
+
+template <typename T>
 int predict_var(const T* Tm, long N, const T* Ks, long M, T* V, const T* alpha, const T* kss, T* part, T* mean, T* var,
                 hipStream_t s, Batch bt, long wbs) {
   const unsigned Bz = (unsigned)bt.B;
-  dim3 grid((unsigned)(M / NB), (unsigned)(N / NB), Bz);
-  predict_v_kernel<T><<<grid, 256, 0, s>>>(Tm, N, Ks, M, V, bt.ws, wbs);
+  (void)predict_v<T>(Tm, N, Ks, M, V, s, bt, wbs);
   predict_partial_kernel<T><<<dim3((unsigned)(M / 64), PREDICT_SPLIT, Bz), 256, 0, s>>>(V, Ks, N, M, alpha, part, bt.ws, wbs);
   predict_finish_kernel<T><<<dim3((unsigned)((M + 255) / 256), 1, Bz), 256, 0, s>>>(part, M, kss, mean, var, wbs);
   return (int)hipGetLastError();
@@ -1745,6 +1751,7 @@ int sample_draws(const T* L, long M, const T* Z, long Q, const T* mean, int m, i
   template int solve<T>(const T*, long, const T*, int, T*, T*, T*, T*, hipStream_t, Batch);                           \
   template int refine_solve<T>(const T*, long, const T*, int, const double*, const T*, T*, T*, T*, T*, T*, hipStream_t, Batch, long, long); \
   template int finish<T>(const T*, const T*, long, int, T*, hipStream_t, Batch);                                      \
+  template int predict_v<T>(const T*, long, const T*, long, T*, hipStream_t, Batch, long);                                  \
   template int predict_var<T>(const T*, long, const T*, long, T*, const T*, const T*, T*, T*, T*, hipStream_t, Batch, long);
 DGP_INST(double)
 DGP_INST(float)

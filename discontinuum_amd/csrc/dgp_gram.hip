@@ -89,6 +89,13 @@ int model_ntheta(int model, int d) {
   return -1;
 }
 
+int model_nterms(int model, int d) {
+  if (model == DGP_MODEL_LOADEST) return (d >= 2 && d <= 6) ? 3 : -1;
+  if (model == DGP_MODEL_RATING) return d == 2 ? 5 : -1;
+  if (const CompositeDesc* c = composite_get(model)) return c->d == d ? c->nterms : -1;
+  return -1;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void pack_x_kernel(const T* __restrict__ X, int n, int d, long N, T* __restrict__ Xt,
                                                      long bs, const int* __restrict__ ns) {

@@ -49,6 +49,7 @@ struct Batch {
   const Tuning& tuning() const { return tune ? *tune : default_tuning(); }
 };
 int model_ntheta(int model, int d);  // number of constrained kernel hyperparameters, -1 if unsupported
+int model_nterms(int model, int d);  // number of additive parts of the covariance (Model::terms), -1 if unsupported
 int composite_define(const int* spec, int nspec);  // register a generic composite model (dgp_models.h), -> model id or < 0
 bool composite_select(int model, int d);  // make `model` the composite the next Composite<T, d>::prepare reads; false if it is none
 
@@ -159,6 +160,9 @@ int refine_solve(const T* Tm, long N, const T* r, int n, const double* rho64, co
 template <typename T>
 int predict_var(const T* Tm, long N, const T* Ks, long M, T* V, const T* alpha, const T* kss, T* part, T* mean, T* var,
                 hipStream_t s, Batch bt = Batch(), long wbs = 0);
+// V = T Ks alone (Ks, V: N x M row-major in the caller's work area, M % 128 == 0): predict_var's first launch
+template <typename T>
+int predict_v(const T* Tm, long N, const T* Ks, long M, T* V, hipStream_t s, Batch bt = Batch(), long wbs = 0);
 long solve_partials(long N);
 // ---- one matrix over several GPUs (dgp_dist.hip): the panel chain of W block columns on a slab-addressed matrix
 template <typename T>
@@ -201,6 +205,20 @@ template <typename T>
 int posterior_period_moments(int mode, int model, int d, const T* V, long N, long m, int B, const T* Xst, const T* var, long wbs,
                              const double* theta, const T* mu, const double* scale2, const double* w, const int* group, int P,
                              const T* ev, double* work, double* mean_out, double* cov_out, hipStream_t s, void* pre_scratch);
+
+// ---- dgp_terms.hip: the posterior of the covariance's additive parts (C = model_nterms).  Ks / V: N x (C Mp) row-major, term c
+// of test point j in column c Mp + j; kss: C Mp; part: terms_partials(C, Mp) elements; mean [B][C][m], cov [B][C (C + 1) / 2][m]
+// (entry (c, c'), c' <= c, at c (c + 1) / 2 + c'; null: not wanted) in the caller's arrays.
+template <typename T>
+int gram_cross_terms(int model, int d, const T* Xt, long N, int n, const T* Xst, long Mp, int m, const double* theta, T* Ks,
+                     hipStream_t s, Batch bt = Batch(), long wbs = 0, void* pre_scratch = nullptr, void* pre_staging = nullptr);
+template <typename T>
+int gram_diag_terms(int model, int d, const T* Xst, long Mp, int m, const double* theta, T* kss, hipStream_t s, Batch bt = Batch(),
+                    long wbs = 0, void* pre_scratch = nullptr);
+long terms_partials(int C, long Mp);
+template <typename T>
+int terms_reduce(int C, const T* V, const T* Ks, long N, long Mp, int m, const T* alpha, const T* kss, T* part, T* mean, T* cov,
+                 hipStream_t s, Batch bt = Batch(), long wbs = 0);
 
 // ---- dgp_crossval.hip: exact leave-one-out / leave-group-out cross-validation from T = L^-1, alpha and -- when it is valid --
 // S = K^^-1 (null otherwise).  order [B][n] / start [B][ngroups + 1]: group g of a site = order[start[g] .. start[g + 1]); every

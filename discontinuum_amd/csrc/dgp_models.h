@@ -192,6 +192,33 @@ struct Loadest {
     }
     return k1 + k2 + p.os3 * base3;
   }
+  // The additive parts of pair<false>, each with its own outputscale: k[0] seasonal, k[1] covariates, k[2] residual.
+  // Same expressions as pair<false>; its return value is (k[0] + k[1]) + k[2] with the products contracted into the adds
+  // (hipcc's default -ffp-contract=fast), so the in-order sum of the ROUNDED parts agrees with it to a few ulp, not bitwise.
+  static constexpr int NTERMS = 3;
+  static __device__ __forceinline__ void terms(const T (&fi)[NF], const T (&fj)[NF], const Pre& p, T (&k)[NTERMS]) {
+    const T dt = fi[0] - fj[0];
+    const T s = fi[D] * fj[D + 1] - fi[D + 1] * fj[D];  // sin(pi dt / p)
+    const T s2 = s * s;
+    const MaternTerm<T> m5 = matern52(fabs(dt), p.inv_lm);
+    const T e1 = exp_nonpos(T(-2) * s2 * p.inv_lp - m5.q);
+    const T base1 = e1 * m5.poly;
+    const T z30 = dt * p.inv_l3[0];
+    T sq2 = T(0), sq3 = z30 * z30;
+#pragma unroll
+    for (int j = 1; j < D; ++j) {
+      const T d = fi[j] - fj[j];
+      const T z2 = d * p.inv_l2[j - 1], z3 = d * p.inv_l3[j];
+      sq2 += z2 * z2;
+      sq3 += z3 * z3;
+    }
+    const T base2 = exp_nonpos(T(-0.5) * sq2);
+    const MaternTerm<T> m3 = matern32_q(T(1.73205080756887729353) * sqrt_nonneg(sq3));
+    const T base3 = m3.poly * exp_nonpos(-m3.q);
+    k[0] = p.os1 * base1;
+    k[1] = p.os2 * base2;
+    k[2] = p.os3 * base3;
+  }
   // the pair-independent factors of the derivative sums (see pair<true>)
   static __device__ __forceinline__ void finalize(T (&acc)[NTHETA], const Pre& p) {
     acc[1] *= p.os1 * T(2) * p.inv_lp * p.inv_lp;
@@ -294,6 +321,35 @@ struct Rating {
       acc[15] += (w * ep) * pm.dpoly;
     }
     return gg * lower + hh * upper + p.os_b * baseb + kp;
+  }
+  // The additive parts of pair<false>: k[0], k[1] the two gated shifts g_i g_j os_a base_a, k[2] the bend
+  // (1 - g_i)(1 - g_j) os_u base_u, k[3] base, k[4] periodic.  pair<false> gates the SUM of the two shifts and contracts its
+  // products into the adds; the in-order sum of the rounded parts agrees with it to a few ulp (all parts are >= 0).
+  static constexpr int NTERMS = 5;
+  static __device__ __forceinline__ void terms(const T (&fi)[NF], const T (&fj)[NF], const Pre& p, T (&k)[NTERMS]) {
+    const T dt = fi[0] - fj[0], adt = fabs(dt), adw = fabs(fi[1] - fj[1]);
+    const T gi = fi[2], gj = fj[2], hi = T(1) - gi, hj = T(1) - gj;
+    const T gg = gi * gj, hh = hi * hj;
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+      const MaternTerm<T> ms = matern52(adw, p.inv_ls_a[a]);
+      const MaternTerm<T> mt = matern32_q(T(1.73205080756887729353) * adt * p.inv_lt_a[a]);
+      const T e = exp_nonpos(-ms.q - mt.q);
+      const T base = e * ms.poly * mt.poly;
+      k[a] = gg * (p.os_a[a] * base);
+    }
+    const MaternTerm<T> us = matern52(adw, p.inv_ls_u), ut = matern52(adt, p.inv_lt_u);
+    const T eu = exp_nonpos(-us.q - ut.q);
+    const T baseu = eu * us.poly * ut.poly;
+    k[2] = hh * (p.os_u * baseu);
+    const MaternTerm<T> bs = matern52(adw, p.inv_ls_b);
+    const T eb = exp_nonpos(-bs.q);
+    k[3] = p.os_b * (eb * bs.poly);
+    const T s = fi[3] * fj[4] - fi[4] * fj[3];  // sin(pi dt / p)
+    const T s2 = s * s;
+    const MaternTerm<T> pm = matern52(adt, p.inv_lm);
+    const T ep = exp_nonpos(T(-2) * s2 * p.inv_lp - pm.q);
+    k[4] = p.os_p * (ep * pm.poly);
   }
   static __device__ __forceinline__ void finalize(T (&acc)[NTHETA], const Pre& p) {
 #pragma unroll
@@ -442,6 +498,50 @@ struct Composite {
       }
     }
     return k;
+  }
+  // factor()'s value alone (same expressions, none of the derivative weights).  The points' features come through
+  // accessors fi(column), fj(column): the column is a descriptor entry, and a register array indexed by it lives in scratch
+  // memory from D = 3 on in double -- kernels hand in accessors that read their LDS strips instead.
+  template <typename FI, typename FJ>
+  static __device__ __forceinline__ T factor_value(const CompositeDesc::Fac& fc, const FI& fi, const FJ& fj, const T* pv) {
+    if (fc.type == DGP_FAC_PERIODIC) {
+      const T dt = fi(fc.dims[0]) - fj(fc.dims[0]);
+      double sd, cd;
+      sincospi((double)dt * (double)pv[fc.period], &sd, &cd);
+      const T s = (T)sd;
+      return exp_nonpos(T(-2) * s * s * pv[fc.ls]);
+    }
+    T sq = T(0);
+    for (int j = 0; j < fc.ndims; ++j) {
+      const T z = (fi(fc.dims[j]) - fj(fc.dims[j])) * pv[fc.ls + (fc.ard ? j : 0)];
+      sq += z * z;
+    }
+    if (fc.type == DGP_FAC_RBF) return exp_nonpos(T(-0.5) * sq);
+    const T r = sqrt_nonneg(sq);
+    if (fc.nu2 == 1) return exp_nonpos(-r);
+    if (fc.nu2 == 3) {
+      const T q = T(1.73205080756887729353) * r;
+      return (T(1) + q) * exp_nonpos(-q);
+    }
+    const T q = T(2.23606797749978969641) * r;
+    return (T(1) + q + q * q * T(1.0 / 3.0)) * exp_nonpos(-q);
+  }
+  // term t < desc.nterms alone: sigma_t^2 prod_f k_tf (an unscaled term counts sigma^2 = 1).  Kernels loop over t with this
+  // one (a rolled loop, one copy of the interpreter) instead of indexing terms()'s array by a runtime t.
+  template <typename FI, typename FJ>
+  static __device__ __forceinline__ T term(int t, const FI& fi, const FJ& fj, const Pre& p) {
+    const CompositeDesc::Term& tm = p.desc.term[t];
+    T prod = T(1);
+    for (int f = 0; f < tm.nfac; ++f) prod *= factor_value(tm.fac[f], fi, fj, p.pv);
+    return (tm.os >= 0 ? p.pv[tm.os] : T(1)) * prod;
+  }
+  // the terms in descriptor order; 0 from desc.nterms on
+  static constexpr int NTERMS = DGP_C_TMAX;
+  static __device__ __forceinline__ void terms(const T (&fi)[NF], const T (&fj)[NF], const Pre& p, T (&k)[NTERMS]) {
+    const auto ai = [&](int c) { return fi[c]; };
+    const auto aj = [&](int c) { return fj[c]; };
+#pragma unroll
+    for (int t = 0; t < DGP_C_TMAX; ++t) k[t] = t < p.desc.nterms ? term(t, ai, aj, p) : T(0);
   }
   static __device__ __forceinline__ void finalize(T (&)[NTHETA], const Pre&) {}  // the interpreter applies every factor per entry
 };

@@ -681,5 +681,17 @@ class MarginalHIP(BaseModel):
 
         return cross_validate(self, folds=folds, ci=ci, return_folds=return_folds)
 
+    @is_fitted
+    def decompose(self, covariates, groups=None, ci=0.95, return_cov=False):
+        """Exact posterior of every additive part of the covariance at the points of ``covariates``, with the
+        cross-covariances between the parts (``dgp_predict_terms``; one pass, from the factorisation the engine holds).
+        -> Dataset on (``component``, the covariates' coordinate) with ``mean`` and ``se`` in the units of the transformed
+        target, for log targets also the multiplicative ``factor`` with its exact ``ci`` interval; the components are the
+        model's ``component_names`` plus the deterministic prior mean ``"mean"``.  ``groups={"shift": ("shift_1",
+        "shift_2")}`` merges parts (variance from the cross-covariances).  See ``discontinuum_amd.components.decompose``."""
+        from ..components import decompose
+
+        return decompose(self, covariates, groups=groups, ci=ci, return_cov=return_cov)
+
     def build_model(self, X, y, **kwargs):
         raise NotImplementedError("This method must be implemented in a subclass")

@@ -59,6 +59,8 @@ class LoadestGPMarginalHIP(LoadestDataMixin, MarginalHIP):
     """LOAD ESTimation as an exact GP (marginal likelihood) on the MI355X engine.  The reference class also mixes in
     its plotting helpers; they sit outside the hot path and would compose in the same MRO slot, before the engine."""
 
+    component_names = ("seasonal", "covariates", "residual")  # the covariance's additive parts, in ``decompose``'s order
+
     def __init__(self, model_config: ModelConfig | None = None):
         config = model_config or ModelConfig()
         super().__init__(model_config=config)

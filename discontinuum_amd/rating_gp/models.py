@@ -243,6 +243,8 @@ class RatingDataMixin(DataMixin):
 class RatingGPMarginalHIP(RatingDataMixin, MarginalHIP):
     """Stage-discharge rating curve as an exact GP (marginal likelihood), on the MI355X engine."""
 
+    component_names = ("shift_1", "shift_2", "bend", "base", "periodic")  # the covariance's additive parts (``decompose``)
+
     def __init__(self, model_config: ModelConfig | None = None):
         config = model_config or ModelConfig()
         super().__init__(model_config=config)

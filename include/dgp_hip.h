@@ -300,6 +300,25 @@ int dgp_cross_validate(dgp_plan* plan, const int32_t* order_dev, const int32_t* 
                        void* work_dev, size_t work_bytes, double* resid_dev, double* var_dev, double* lpd_dev, int32_t* info_dev,
                        void* stream);
 
+/* The posterior of the covariance's ADDITIVE PARTS.  Both fused covariances and every generic one are sums of named terms,
+ *   loadest: seasonal + covariates + residual;  rating: shift_1 + shift_2 + bend + base + periodic (the shifts and the bend
+ *   carry their gates);  composite: its terms in descriptor order (an unscaled term counts outputscale 1),
+ * C = dgp_model_nterms(model, d) of them (3 / 5 / the descriptor's count; < 0 for an unsupported (model, d); needs no device).
+ * With T = L^-1, alpha = K^^-1 r from the held factorisation, K_c the Gram of part c and V_c = T K_c(X, X*):
+ *     mean_dev[site][c][j]            = K_c(x*_j, X) alpha                                   E[f_c(x*_j) | y]
+ *     cov_dev[site][c(c+1)/2 + c'][j] = delta_cc' k_c(x*_j, x*_j) - V_c[:, j]^T V_c'[:, j]   Cov[f_c, f_c' | y](x*_j), c' <= c
+ * in the plan's dtype.  The C means sum to dgp_predict's latent mean and the full C x C covariance at a point (off-diagonal
+ * entries twice) to its variance; the cross-covariances give the variance of any merged part.  One pair evaluation per matrix
+ * entry for all parts, the prediction's GEMM at width C M, one pass over V and Ks; fixed summation orders (bitwise repeatable).
+ * Preconditions and arguments as dgp_predict (single-site, batched and ragged plans; Xs[batch][m][d], theta[batch][ntheta]);
+ * cov_dev may be NULL (means only).  work_dev: dgp_predict_terms_workspace_bytes(plan, m) bytes, about
+ * batch x 2 C N M elements.  DGP_E_ARG / DGP_E_WORKSPACE / DGP_E_STATE before any launch for a null plan or argument, m <= 0,
+ * a plan without workspace or factorisation, a work area that is too small. */
+int dgp_model_nterms(int model, int d);
+size_t dgp_predict_terms_workspace_bytes(const dgp_plan* plan, int64_t m);
+int dgp_predict_terms(dgp_plan* plan, const double* theta_host, const void* Xs_dev, int64_t m, void* work_dev,
+                      size_t work_bytes, void* mean_dev, void* cov_dev, void* stream);
+
 /* Predictive mean only, and its vector-Jacobian product -- what the rating-gp monotonicity penalty
  * differentiates (src/rating_gp/models/gpytorch.py:130-187: mean of likelihood(model(x_grid)) with grad).
  *   dgp_predict_mean : mean_dev[j] = K(x*_j, X) alpha                                  (m entries)
