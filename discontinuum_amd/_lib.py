@@ -93,6 +93,9 @@ SIGNATURES = {
     "dgp_model_nterms": (_i, [_i, _i]),
     "dgp_predict_terms_workspace_bytes": (_sz, [_vp, _i64]),
     "dgp_predict_terms": (_i, [_vp, _dp, _vp, _i64, _vp, _sz, _vp, _vp, _vp]),
+    "dgp_model_input_differentiable": (_i, [_i, _i, _i]),
+    "dgp_predict_slopes_workspace_bytes": (_sz, [_vp, _i64, _i]),
+    "dgp_predict_slopes": (_i, [_vp, _dp, _vp, _i64, C.POINTER(_i), _i, _vp, _sz, _vp, _vp, _vp]),
     "dgp_mean_vjp_workspace_bytes": (_sz, [_vp, _i64]),
     "dgp_predict_mean": (_i, [_vp, _dp, _vp, _i64, _vp, _sz, _vp, _vp]),
     "dgp_mean_vjp": (_i, [_vp, _dp, _vp, _i64, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),

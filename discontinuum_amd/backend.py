@@ -271,6 +271,61 @@ class GPPlan:
                         cov[..., lo:hi] = co
         return mean, cov
 
+    def predict_slopes(self, theta, Xs: torch.Tensor, cols, chunk: int | None = None, return_cov: bool = True):
+        """Latent posterior of the fit and of its DERIVATIVES with respect to the raw input columns ``cols`` (distinct, in
+        0 .. d - 1) at Xs (m, d) from the held factorisation (``dgp_predict_slopes``): -> (mean (P, m), cov (P (P + 1) / 2,
+        m)) with P = 1 + len(cols) planes -- plane 0 the value (``predict``'s mean and variance), plane q + 1 the slope in
+        column ``cols[q]`` per unit of that model-space input.  ``cov[a (a + 1) / 2 + b]`` (b <= a) is the posterior covariance
+        of planes a and b at each point.  Batched plans: Xs (batch, m, d), theta (batch, ntheta) -> (batch, P, m), (batch,
+        P (P + 1) / 2, m).  ``return_cov=False`` -> (mean, None).  A column the covariance is not differentiable in (a
+        Matern-1/2 factor of a composite) raises.  ``chunk`` = points per launch sequence; the work area is batch x 2 P N x
+        chunk elements, so the default is 16384 // (batch P) rounded down to a multiple of 128 (at least 128)."""
+        cols = [int(c) for c in cols]
+        if not 1 <= len(cols) <= self.d or len(set(cols)) != len(cols) or min(cols) < 0 or max(cols) >= self.d:
+            raise ValueError(f"cols must be 1 .. {self.d} distinct columns in 0 .. {self.d - 1}, got {cols}")
+        mid = model_id(self.model)
+        for c in cols:
+            if int(self.lib.dgp_model_input_differentiable(mid, self.d, c)) != 1:
+                raise ValueError(f"the covariance is not differentiable in column {c} (Matern-1/2 factor)")
+        Pn = 1 + len(cols)
+        Qn = Pn * (Pn + 1) // 2
+        if chunk is None:
+            chunk = max(128, (16384 // (self.batch * Pn)) // 128 * 128)
+        lead = () if self.batch == 1 else (self.batch,)
+        if not (torch.is_tensor(Xs) and Xs.is_cuda and Xs.dtype == self.dtype and Xs.dim() == 2 + len(lead)
+                and Xs.shape[-1] == self.d and tuple(Xs.shape[:-2]) == lead):
+            raise ValueError(f"Xs must be a {lead + ('m', self.d)} {self.dtype} CUDA tensor")
+        th = _theta_array(theta, self.ntheta * self.batch)
+        carr = (C.c_int * len(cols))(*cols)
+        m = Xs.shape[-2]
+        mean = torch.empty(lead + (Pn, m), dtype=self.dtype, device=self.device)
+        cov = torch.empty(lead + (Qn, m), dtype=self.dtype, device=self.device) if return_cov else None
+        with torch.cuda.device(self.device):
+            for lo in range(0, m, chunk):
+                hi = min(lo + chunk, m)
+                whole = lo == 0 and hi == m
+                xs = Xs[..., lo:hi, :].contiguous()
+                need = int(self.lib.dgp_predict_slopes_workspace_bytes(self._h, hi - lo, len(cols)))
+                ws = getattr(self, "_slopes_ws", None)
+                if ws is None or ws.numel() < need + 256:
+                    self._slopes_ws = None
+                    self._slopes_ws = ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+                base = ws.data_ptr()
+                base += (-base) % 256
+                # a chunk is a column range of the (..., P, m) results: stage it
+                mo = mean if whole else torch.empty(lead + (Pn, hi - lo), dtype=self.dtype, device=self.device)
+                co = cov if (whole or cov is None) else torch.empty(lead + (Qn, hi - lo), dtype=self.dtype, device=self.device)
+                _lib.check(
+                    self.lib.dgp_predict_slopes(self._h, th, _ptr(xs), hi - lo, carr, len(cols), C.c_void_p(base), need,
+                                                _ptr(mo), _ptr(co) if co is not None else None, _stream()),
+                    "dgp_predict_slopes",
+                )
+                if not whole:
+                    mean[..., lo:hi] = mo
+                    if cov is not None:
+                        cov[..., lo:hi] = co
+        return mean, cov
+
     # ------------------------------------------------------------------ cross-validation
     def cross_validate(self, groups, max_group=None):
         """Exact leave-group-out cross-validation at the hyperparameters of the factorisation the plan holds

@@ -1099,6 +1099,52 @@ static int predict_terms(dgp_plan* p, const double* theta, const void* Xs, int64
   return terms_reduce<T>(C, V, Ks, p->N, M, (int)m, (const T*)p->alpha, kss, (T*)(w + L.part), (T*)mean, (T*)cov, s, bt, wbs);
 }
 
+// ---- the posterior of the input derivatives (dgp_slopes.hip).  Work area per site as TermsLayout with P = 1 + ncols planes
+// and the packed P (P + 1) / 2 prior block in place of the parts' prior variances.
+static TermsLayout slopes_layout(const dgp_plan* p, int64_t m, int ncols) {
+  const size_t M = (size_t)round_up(m, DGP_TILE_HOST), e = p->elem, N = (size_t)p->N;
+  const size_t P = (size_t)(1 + ncols);
+  TermsLayout L;
+  size_t o = 0;
+  L.Xst = o; o += align_up(e * M * p->d);
+  L.Ks = o; o += align_up(e * N * P * M);
+  L.V = o; o += align_up(e * N * P * M);
+  L.kss = o; o += align_up(e * (P * (P + 1) / 2) * M);
+  L.part = o; o += align_up(e * (size_t)terms_partials((int)P, (long)M));
+  L.total = o;
+  return L;
+}
+
+template <typename T>
+static int predict_slopes(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const int* cols, int ncols, void* work,
+                          void* mean, void* cov, hipStream_t s) {
+  const TermsLayout L = slopes_layout(p, m, ncols);
+  const long M = round_up(m, DGP_TILE_HOST);
+  const int P = 1 + ncols;
+  const long wbs = p->B > 1 ? (long)(L.total / sizeof(T)) : 0;
+  const Batch bt = batch_of<T>(p);
+  char* w = (char*)work;
+  T* Xst = (T*)(w + L.Xst);
+  T* Ks = (T*)(w + L.Ks);
+  T* V = (T*)(w + L.V);
+  T* prior = (T*)(w + L.kss);
+  Batch wb;  // the test points: [B][m][d] -> SoA in the work area
+  wb.B = p->B;
+  wb.ws = wbs;
+  int rc = pack_x<T>((const T*)Xs, (int)m, p->d, M, Xst, s, wb);
+  if (rc) return rc;
+  {
+    PreSlot slot(p, s);
+    if ((rc = gram_cross_slopes<T>(p->model, p->d, (const T*)p->Xt, p->N, (int)p->n, Xst, M, (int)m, theta, cols, ncols, Ks, s, bt,
+                                   wbs, p->pre, slot.staging)))
+      return rc;
+  }
+  wb.ws = 0;
+  if ((rc = gram_prior_slopes<T>(p->model, p->d, Xst, M, (int)m, theta, cols, ncols, prior, s, wb, wbs, p->pre))) return rc;
+  if ((rc = predict_v<T>((const T*)p->Tm, p->N, Ks, (long)P * M, V, s, bt, wbs))) return rc;
+  return slopes_reduce<T>(P, V, Ks, p->N, M, (int)m, (const T*)p->alpha, prior, (T*)(w + L.part), (T*)mean, (T*)cov, s, bt, wbs);
+}
+
 #define DGP_BY_DTYPE(p, CALL64, CALL32) ((p)->dtype == DGP_F64 ? (CALL64) : (CALL32))
 #define DGP_CHECK_PLAN(p)                                                        \
   if (!(p)) return fail(DGP_E_ARG, "null plan");                                 \
@@ -1191,6 +1237,35 @@ int dgp_predict_terms(dgp_plan* p, const double* theta, const void* Xs, int64_t 
   const int rc = DGP_BY_DTYPE(p, predict_terms<double>(p, theta, Xs, m, work, mean, cov, s),
                               predict_terms<float>(p, theta, Xs, m, work, mean, cov, s));
   return wrap(rc, "dgp_predict_terms");
+}
+
+int dgp_model_input_differentiable(int model, int d, int col) { return model_input_differentiable(model, d, col); }
+
+size_t dgp_predict_slopes_workspace_bytes(const dgp_plan* p, int64_t m, int ncols) {
+  return (p && m > 0 && ncols >= 1 && ncols <= p->d) ? slopes_layout(p, m, ncols).total * (size_t)p->B : 0;
+}
+
+int dgp_predict_slopes(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const int* cols, int ncols, void* work,
+                       size_t work_bytes, void* mean, void* cov, void* stream) {
+  if (!p) return fail(DGP_E_ARG, "dgp_predict_slopes: null plan");
+  if (!theta || !Xs || !cols || !work || !mean || m <= 0) return fail(DGP_E_ARG, "dgp_predict_slopes: null argument or m <= 0");
+  if (ncols < 1 || ncols > p->d) return fail(DGP_E_ARG, "dgp_predict_slopes: ncols must be in 1 .. d");
+  for (int q = 0; q < ncols; ++q) {
+    if (cols[q] < 0 || cols[q] >= p->d) return fail(DGP_E_ARG, "dgp_predict_slopes: column outside 0 .. d - 1");
+    for (int r = 0; r < q; ++r)
+      if (cols[r] == cols[q]) return fail(DGP_E_ARG, "dgp_predict_slopes: repeated column");
+  }
+  for (int q = 0; q < ncols; ++q)
+    if (model_input_differentiable(p->model, p->d, cols[q]) != 1)
+      return fail(DGP_E_MODEL, "dgp_predict_slopes: the covariance is not differentiable in a requested column (Matern-1/2 factor)");
+  if (!p->ws) return fail(DGP_E_WORKSPACE, "plan has no workspace: call dgp_plan_set_workspace");
+  if (!p->have_factor) return fail(DGP_E_STATE, "dgp_predict_slopes: no factorisation in the plan (call dgp_factorize)");
+  if (work_bytes < dgp_predict_slopes_workspace_bytes(p, m, ncols))
+    return fail(DGP_E_WORKSPACE, "dgp_predict_slopes: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = DGP_BY_DTYPE(p, predict_slopes<double>(p, theta, Xs, m, cols, ncols, work, mean, cov, s),
+                              predict_slopes<float>(p, theta, Xs, m, cols, ncols, work, mean, cov, s));
+  return wrap(rc, "dgp_predict_slopes");
 }
 
 size_t dgp_mean_vjp_workspace_bytes(const dgp_plan* p, int64_t m) { return (p && m > 0) ? vjp_layout(p, m).total * (size_t)p->B : 0; }

@@ -96,6 +96,21 @@ int model_nterms(int model, int d) {
   return -1;
 }
 
+// mean-square differentiability of the covariance in raw input column `col`: every shipped factor but Matern-1/2
+int model_input_differentiable(int model, int d, int col) {
+  if (model_ntheta(model, d) < 0 || col < 0 || col >= d) return -1;
+  const CompositeDesc* c = composite_get(model);
+  if (!c) return 1;
+  for (int t = 0; t < c->nterms; ++t)
+    for (int f = 0; f < c->term[t].nfac; ++f) {
+      const CompositeDesc::Fac& fc = c->term[t].fac[f];
+      if (fc.type != DGP_FAC_MATERN || fc.nu2 != 1) continue;
+      for (int j = 0; j < fc.ndims; ++j)
+        if (fc.dims[j] == col) return 0;
+    }
+  return 1;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void pack_x_kernel(const T* __restrict__ X, int n, int d, long N, T* __restrict__ Xt,
                                                      long bs, const int* __restrict__ ns) {

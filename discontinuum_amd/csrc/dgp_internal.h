@@ -220,6 +220,27 @@ template <typename T>
 int terms_reduce(int C, const T* V, const T* Ks, long N, long Mp, int m, const T* alpha, const T* kss, T* part, T* mean, T* cov,
                  hipStream_t s, Batch bt = Batch(), long wbs = 0);
 
+// ---- dgp_slopes.hip: the posterior of the fit's derivatives w.r.t. the raw input columns cols[0 .. ncols) of the test point
+// (distinct, in 0 .. d - 1).  P = 1 + ncols planes, plane 0 the value: Ks / V N x (P Mp) row-major, plane a of test point j in
+// column a Mp + j; prior: the packed P (P + 1) / 2 block D_a D'_b k(x*, x*) per point, entry (a, b <= a) at
+// (a (a + 1) / 2 + b) Mp + j; part: terms_partials(P, Mp); mean [B][P][m], cov [B][P (P + 1) / 2][m] (null: not wanted).
+struct SlopeCols {        // kernel argument
+  int ncols;
+  signed char plane[7];   // of (value, column 0 .. 5): the plane it is written to, -1 = not requested
+  unsigned char col[6];   // of plane q + 1: its column
+};
+int model_input_differentiable(int model, int d, int col);  // 1 / 0, -1 for an unsupported (model, d) or a column outside 0 .. d - 1
+template <typename T>
+int gram_cross_slopes(int model, int d, const T* Xt, long N, int n, const T* Xst, long Mp, int m, const double* theta,
+                      const int* cols, int ncols, T* Ks, hipStream_t s, Batch bt = Batch(), long wbs = 0,
+                      void* pre_scratch = nullptr, void* pre_staging = nullptr);
+template <typename T>
+int gram_prior_slopes(int model, int d, const T* Xst, long Mp, int m, const double* theta, const int* cols, int ncols, T* prior,
+                      hipStream_t s, Batch bt = Batch(), long wbs = 0, void* pre_scratch = nullptr);
+template <typename T>
+int slopes_reduce(int P, const T* V, const T* Ks, long N, long Mp, int m, const T* alpha, const T* prior, T* part, T* mean, T* cov,
+                  hipStream_t s, Batch bt = Batch(), long wbs = 0);  // dgp_terms.hip: shares its reduction kernels
+
 // ---- dgp_crossval.hip: exact leave-one-out / leave-group-out cross-validation from T = L^-1, alpha and -- when it is valid --
 // S = K^^-1 (null otherwise).  order [B][n] / start [B][ngroups + 1]: group g of a site = order[start[g] .. start[g + 1]); every
 // group has at most max_group members.  resid / var [B][n], lpd / info [B][ngroups], all double / int whatever T is; `work`:

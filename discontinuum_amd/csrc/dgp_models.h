@@ -98,6 +98,17 @@ __device__ __forceinline__ void phase_features(T t, double inv_p, T* s, T* c) {
   *c = (T)cd;
 }
 
+// sin(pi (t_i - t_j) / p) from the points' phase features with the two products ROUNDED before the subtraction: exactly 0
+// for two points with the same features (Model::slopes promises an exactly vanishing slope at coincident points; the
+// contracted a b - round(c d) of pair / terms leaves the product's rounding error there instead, ~1e-17, which is harmless
+// for a value but is the whole of a derivative that should vanish)
+template <typename T>
+__device__ __forceinline__ T phase_sin_rounded(T si, T ci, T sj, T cj) {
+#pragma clang fp contract(off)
+  const T a = si * cj, b = ci * sj;
+  return a - b;
+}
+
 template <typename T>
 struct MaternTerm {  // value = poly * exp(-q); d value / d lengthscale = dpoly * exp(-q) / l
   T q, poly, dpoly;
@@ -218,6 +229,57 @@ struct Loadest {
     k[0] = p.os1 * base1;
     k[1] = p.os2 * base2;
     k[2] = p.os3 * base3;
+  }
+  // Value and INPUT derivatives for one (train point i, test point j): k[0] = pair<false>'s value, k[1 + c] = d k / d x*_c
+  // with x* the raw coordinates of the TEST point j (posterior slopes, dgp_slopes.hip).  With z_c = (x_i - x*)_c / l_c every
+  // derivative is a product with z_c, never a quotient by the distance: RBF k z_c / l_c, Matern-3/2 3 e^-q z_c / l_c,
+  // Matern-5/2 (5/3)(1 + q) e^-q z_c / l_c, Periodic (4 pi / (p l)) s c k -- the weights of the lengthscale gradients
+  // (pair<true>) -- and all of them are exactly 0 at coincident points.  gj: slope_features of the test point (none here).
+  static constexpr int NSF = 1;
+  static __device__ __forceinline__ void slope_features(const T (&)[NX], const T (&)[NF], const Pre&, T (&g)[NSF]) { g[0] = T(0); }
+  static __device__ __forceinline__ void slopes(const T (&fi)[NF], const T (&fj)[NF], const T (&)[NSF], const Pre& p,
+                                                T (&k)[1 + NX]) {
+    const T dt = fi[0] - fj[0];
+    const T s = phase_sin_rounded(fi[D], fi[D + 1], fj[D], fj[D + 1]);
+    const T c = fi[D + 1] * fj[D + 1] + fi[D] * fj[D];
+    const MaternTerm<T> m5 = matern52(fabs(dt), p.inv_lm);
+    const T e1 = exp_nonpos(T(-2) * (s * s) * p.inv_lp - m5.q);
+    const T base1 = e1 * m5.poly;
+    const T d1 = base1 * (T(4.0 * 3.14159265358979323846) * p.inv_lp * p.inv_p) * (s * c) +
+                 e1 * (T(5.0 / 3.0) * (T(1) + m5.q)) * (dt * p.inv_lm) * p.inv_lm;
+    T z3[D], z2[D - 1];
+    z3[0] = dt * p.inv_l3[0];
+    T sq2 = T(0), sq3 = z3[0] * z3[0];
+#pragma unroll
+    for (int j = 1; j < D; ++j) {
+      const T d = fi[j] - fj[j];
+      z2[j - 1] = d * p.inv_l2[j - 1];
+      z3[j] = d * p.inv_l3[j];
+      sq2 += z2[j - 1] * z2[j - 1];
+      sq3 += z3[j] * z3[j];
+    }
+    const T k2 = p.os2 * exp_nonpos(T(-0.5) * sq2);
+    const MaternTerm<T> m3 = matern32_q(T(1.73205080756887729353) * sqrt_nonneg(sq3));
+    const T e3 = exp_nonpos(-m3.q);
+    const T w3 = T(3) * p.os3 * e3;
+    k[0] = p.os1 * base1 + k2 + p.os3 * (m3.poly * e3);
+    k[1] = p.os1 * d1 + w3 * (z3[0] * p.inv_l3[0]);
+#pragma unroll
+    for (int j = 1; j < D; ++j) k[1 + j] = k2 * (z2[j - 1] * p.inv_l2[j - 1]) + w3 * (z3[j] * p.inv_l3[j]);
+  }
+  // D_a D'_b k(x, x') at x = x' for a, b over (value, the NX columns), packed lower triangle (a, b <= a) at a (a + 1) / 2 + b.
+  // Mixed second derivatives at 0: RBF 1 / l_c^2, Matern-3/2 3 / l_c^2, Matern-5/2 5 / (3 l_c^2), Periodic 4 pi^2 / (p^2 l);
+  // products by the Leibniz rule (first derivatives vanish at 0).  Stationary: no value-slope and no cross-column entries.
+  static constexpr int NPRIOR = (1 + NX) * (2 + NX) / 2;
+  static __device__ __forceinline__ void prior_slopes(const T (&)[NF], const T (&)[NSF], const Pre& p, T (&pr)[NPRIOR]) {
+#pragma unroll
+    for (int q = 0; q < NPRIOR; ++q) pr[q] = T(0);
+    pr[0] = p.os1 + p.os2 + p.os3;
+    pr[2] = p.os1 * (T(4.0 * 9.86960440108935861883) * p.inv_p * p.inv_p * p.inv_lp + T(5.0 / 3.0) * p.inv_lm * p.inv_lm) +
+            T(3) * p.os3 * p.inv_l3[0] * p.inv_l3[0];
+#pragma unroll
+    for (int j = 1; j < D; ++j)
+      pr[(j + 1) * (j + 2) / 2 + j + 1] = p.os2 * p.inv_l2[j - 1] * p.inv_l2[j - 1] + T(3) * p.os3 * p.inv_l3[j] * p.inv_l3[j];
   }
   // the pair-independent factors of the derivative sums (see pair<true>)
   static __device__ __forceinline__ void finalize(T (&acc)[NTHETA], const Pre& p) {
@@ -350,6 +412,66 @@ struct Rating {
     const MaternTerm<T> pm = matern52(adt, p.inv_lm);
     const T ep = exp_nonpos(T(-2) * s2 * p.inv_lp - pm.q);
     k[4] = p.os_p * (ep * pm.poly);
+  }
+  // Value and input derivatives (Loadest::slopes): k[1] = d k / d t*, k[2] = d k / d stage* of the test point j.  The stage
+  // enters through the log warp and the gate; their derivatives at the test point are its slope_features
+  // gj = (1 / (stage + 1e-6), g'(stage) = -20 g (1 - g)), chained here.
+  static constexpr int NSF = 2;
+  static __device__ __forceinline__ void slope_features(const T (&x)[NX], const T (&f)[NF], const Pre&, T (&g)[NSF]) {
+    g[0] = T(1) / (x[1] + T(1e-6));
+    g[1] = T(-20) * f[2] * (T(1) - f[2]);
+  }
+  static __device__ __forceinline__ void slopes(const T (&fi)[NF], const T (&fj)[NF], const T (&gj)[NSF], const Pre& p,
+                                                T (&k)[1 + NX]) {
+    const T dt = fi[0] - fj[0], adt = fabs(dt), dw = fi[1] - fj[1], adw = fabs(dw);
+    const T gi = fi[2], gjv = fj[2], hi = T(1) - gi, hj = T(1) - gjv;
+    const T gg = gi * gjv, hh = hi * hj;
+    T lo = T(0), lo_t = T(0), lo_w = T(0);
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+      const MaternTerm<T> ms = matern52(adw, p.inv_ls_a[a]);
+      const MaternTerm<T> mt = matern32_q(T(1.73205080756887729353) * adt * p.inv_lt_a[a]);
+      const T e = p.os_a[a] * exp_nonpos(-ms.q - mt.q);
+      lo += e * ms.poly * mt.poly;
+      lo_t += e * ms.poly * (T(3) * (dt * p.inv_lt_a[a]) * p.inv_lt_a[a]);
+      lo_w += e * mt.poly * (T(5.0 / 3.0) * (T(1) + ms.q) * (dw * p.inv_ls_a[a]) * p.inv_ls_a[a]);
+    }
+    const MaternTerm<T> us = matern52(adw, p.inv_ls_u), ut = matern52(adt, p.inv_lt_u);
+    const T eu = p.os_u * exp_nonpos(-us.q - ut.q);
+    const T up = eu * us.poly * ut.poly;
+    const T up_t = eu * us.poly * (T(5.0 / 3.0) * (T(1) + ut.q) * (dt * p.inv_lt_u) * p.inv_lt_u);
+    const T up_w = eu * ut.poly * (T(5.0 / 3.0) * (T(1) + us.q) * (dw * p.inv_ls_u) * p.inv_ls_u);
+    const MaternTerm<T> bs = matern52(adw, p.inv_ls_b);
+    const T eb = p.os_b * exp_nonpos(-bs.q);
+    const T ba_w = eb * (T(5.0 / 3.0) * (T(1) + bs.q) * (dw * p.inv_ls_b) * p.inv_ls_b);
+    const T s = phase_sin_rounded(fi[3], fi[4], fj[3], fj[4]);
+    const T c = fi[4] * fj[4] + fi[3] * fj[3];
+    const MaternTerm<T> pm = matern52(adt, p.inv_lm);
+    const T ep = p.os_p * exp_nonpos(T(-2) * (s * s) * p.inv_lp - pm.q);
+    const T kp = ep * pm.poly;
+    const T kp_t = kp * (T(4.0 * 3.14159265358979323846) * p.inv_lp * p.inv_p) * (s * c) +
+                   ep * (T(5.0 / 3.0) * (T(1) + pm.q)) * (dt * p.inv_lm) * p.inv_lm;
+    k[0] = gg * lo + hh * up + eb * bs.poly + kp;
+    k[1] = gg * lo_t + hh * up_t + kp_t;
+    k[2] = gj[1] * (gi * lo - hi * up) + gj[0] * (gg * lo_w + hh * up_w + ba_w);
+  }
+  // D_a D'_b k(x, x') at x = x' over (value, t, stage), packed like Loadest::prior_slopes.  NOT diagonal: the gates are not
+  // stationary, d/ds'[g(s) g(s') A] at s' = s is g g' A(0), so the value and the stage slope are correlated a priori.
+  static constexpr int NPRIOR = 6;
+  static __device__ __forceinline__ void prior_slopes(const T (&f)[NF], const T (&g)[NSF], const Pre& p, T (&pr)[NPRIOR]) {
+    const T gv = f[2], hv = T(1) - gv, wp = g[0], gp = g[1];
+    const T lo0 = p.os_a[0] + p.os_a[1];
+    const T lo_tt = T(3) * (p.os_a[0] * p.inv_lt_a[0] * p.inv_lt_a[0] + p.os_a[1] * p.inv_lt_a[1] * p.inv_lt_a[1]);
+    const T lo_ww = T(5.0 / 3.0) * (p.os_a[0] * p.inv_ls_a[0] * p.inv_ls_a[0] + p.os_a[1] * p.inv_ls_a[1] * p.inv_ls_a[1]);
+    const T up_tt = T(5.0 / 3.0) * p.os_u * p.inv_lt_u * p.inv_lt_u, up_ww = T(5.0 / 3.0) * p.os_u * p.inv_ls_u * p.inv_ls_u;
+    const T ba_ww = T(5.0 / 3.0) * p.os_b * p.inv_ls_b * p.inv_ls_b;
+    const T pe_tt = p.os_p * (T(4.0 * 9.86960440108935861883) * p.inv_p * p.inv_p * p.inv_lp + T(5.0 / 3.0) * p.inv_lm * p.inv_lm);
+    pr[0] = gv * gv * lo0 + hv * hv * p.os_u + p.os_b + p.os_p;
+    pr[1] = T(0);
+    pr[2] = gv * gv * lo_tt + hv * hv * up_tt + pe_tt;
+    pr[3] = gp * (gv * lo0 - hv * p.os_u);
+    pr[4] = T(0);
+    pr[5] = gp * gp * (lo0 + p.os_u) + wp * wp * (gv * gv * lo_ww + hv * hv * up_ww + ba_ww);
   }
   static __device__ __forceinline__ void finalize(T (&acc)[NTHETA], const Pre& p) {
 #pragma unroll
@@ -534,6 +656,86 @@ struct Composite {
     T prod = T(1);
     for (int f = 0; f < tm.nfac; ++f) prod *= factor_value(tm.fac[f], fi, fj, p.pv);
     return (tm.os >= 0 ? p.pv[tm.os] : T(1)) * prod;
+  }
+  // One requested column at a time for the interpreter (posterior slopes): -> d k / d x*_col of the test point j, *kval =
+  // the value.  Value and derivative of a term's product are carried together (dprod = dprod v + prod dv), so nothing is
+  // indexed by a loop counter.  The factor derivatives are the aux z / l weights of factor() -- no division by the distance
+  // (a Matern-1/2 factor has none to offer: model_input_differentiable refuses its columns before any launch).
+  static constexpr int NSF = 1;
+  static __device__ __forceinline__ void slope_features(const T (&)[NX], const T (&)[NF], const Pre&, T (&g)[NSF]) { g[0] = T(0); }
+  template <typename FI, typename FJ>
+  static __device__ __forceinline__ T slope_col(int col, const FI& fi, const FJ& fj, const Pre& p, T* kval) {
+    T k = T(0), dk = T(0);
+    for (int t = 0; t < p.desc.nterms; ++t) {
+      const CompositeDesc::Term& tm = p.desc.term[t];
+      T prod = tm.os >= 0 ? p.pv[tm.os] : T(1), dprod = T(0);
+      for (int f = 0; f < tm.nfac; ++f) {
+        const CompositeDesc::Fac& fc = tm.fac[f];
+        T v, dv = T(0);
+        if (fc.type == DGP_FAC_PERIODIC) {
+          const T dt = fi(fc.dims[0]) - fj(fc.dims[0]);
+          double sd, cd;
+          sincospi((double)dt * (double)p.pv[fc.period], &sd, &cd);
+          const T s = (T)sd;
+          v = exp_nonpos(T(-2) * s * s * p.pv[fc.ls]);
+          if (fc.dims[0] == col) dv = v * (T(4.0 * 3.14159265358979323846) * p.pv[fc.ls] * p.pv[fc.period]) * (s * (T)cd);
+        } else {
+          T sq = T(0), zl = T(0);
+          for (int j = 0; j < fc.ndims; ++j) {
+            const T il = p.pv[fc.ls + (fc.ard ? j : 0)];
+            const T z = (fi(fc.dims[j]) - fj(fc.dims[j])) * il;
+            sq += z * z;
+            if (fc.dims[j] == col) zl = z * il;
+          }
+          T aux;
+          if (fc.type == DGP_FAC_RBF) {
+            v = aux = exp_nonpos(T(-0.5) * sq);
+          } else {
+            const T r = sqrt_nonneg(sq);
+            if (fc.nu2 == 1) {  // not differentiable at 0: its columns are never requested, the others see only its value
+              v = exp_nonpos(-r);
+              aux = T(0);
+            } else if (fc.nu2 == 3) {
+              const T q = T(1.73205080756887729353) * r;
+              const T e = exp_nonpos(-q);
+              aux = T(3) * e;
+              v = (T(1) + q) * e;
+            } else {
+              const T q = T(2.23606797749978969641) * r;
+              const T e = exp_nonpos(-q);
+              aux = T(5.0 / 3.0) * (T(1) + q) * e;
+              v = (T(1) + q + q * q * T(1.0 / 3.0)) * e;
+            }
+          }
+          dv = aux * zl;
+        }
+        dprod = dprod * v + prod * dv;
+        prod *= v;
+      }
+      k += prod;
+      dk += dprod;
+    }
+    *kval = k;
+    return dk;
+  }
+  // D D' k at x = x' for one column (col < 0: the value itself); every other entry of a stationary covariance's block is 0
+  static __device__ __forceinline__ T prior_col(int col, const Pre& p) {
+    T k = T(0);
+    for (int t = 0; t < p.desc.nterms; ++t) {
+      const CompositeDesc::Term& tm = p.desc.term[t];
+      T w = T(0);
+      for (int f = 0; f < tm.nfac; ++f) {
+        const CompositeDesc::Fac& fc = tm.fac[f];
+        for (int j = 0; j < fc.ndims; ++j) {
+          if (fc.dims[j] != col) continue;
+          const T il = p.pv[fc.ls + (fc.ard ? j : 0)];
+          if (fc.type == DGP_FAC_PERIODIC) w += T(4.0 * 9.86960440108935861883) * p.pv[fc.period] * p.pv[fc.period] * il;
+          else w += (fc.type == DGP_FAC_RBF ? T(1) : fc.nu2 == 3 ? T(3) : T(5.0 / 3.0)) * il * il;
+        }
+      }
+      k += (tm.os >= 0 ? p.pv[tm.os] : T(1)) * (col < 0 ? T(1) : w);
+    }
+    return k;
   }
   // the terms in descriptor order; 0 from desc.nterms on
   static constexpr int NTERMS = DGP_C_TMAX;

@@ -12,6 +12,7 @@
 //   terms_partial /    two-stage column reduction (predict_partial / predict_finish extended): per point and row slab the
 //   terms_finish       C sums Ks[i, c Mp + j] alpha_i and the C (C + 1) / 2 sums V[i, c Mp + j] V[i, c' Mp + j], c' <= c; the
 //                      finish pass adds the slabs in slab order and subtracts from delta_cc' kss.  V and Ks are read once.
+//                      slopes_reduce (dgp_slopes.hip's planes) runs the same two kernels against a packed prior block.
 // Fixed summation orders, no floating-point atomics: bitwise repeatable.
 #include "dgp_internal.h"
 #include "dgp_models.h"
@@ -174,8 +175,10 @@ __global__ __launch_bounds__(256) void terms_partial_kernel(const T* __restrict_
   }
 }
 
-// mean [site][C][m] and cov [site][C (C + 1) / 2][m] (null: not wanted) straight into the caller's arrays
-template <typename T, int C>
+// mean [site][C][m] and cov [site][C (C + 1) / 2][m] (null: not wanted) straight into the caller's arrays.  The prior the sums
+// are subtracted from: PACKED = false delta_cc' kss[c Mp + j] (independent parts), PACKED = true a full packed block
+// kss[(c (c + 1) / 2 + c') Mp + j] (dgp_slopes.hip: value and input derivatives are correlated a priori).
+template <typename T, int C, bool PACKED>
 __global__ __launch_bounds__(256) void terms_finish_kernel(const T* __restrict__ part, long Mp, int m, const T* __restrict__ kss,
                                                            T* __restrict__ mean, T* __restrict__ cov, long wbs) {
   constexpr int P = C + C * (C + 1) / 2;
@@ -199,7 +202,7 @@ __global__ __launch_bounds__(256) void terms_finish_kernel(const T* __restrict__
       const int q = c * (c + 1) / 2 + e;
       T s = T(0);
       for (int z = 0; z < PREDICT_SPLIT; ++z) s += part[((long)(C + q) * PREDICT_SPLIT + z) * Mp + j];
-      cov[(long)q * m + j] = (e == c ? kss[(long)c * Mp + j] : T(0)) - s;
+      cov[(long)q * m + j] = (PACKED ? kss[(long)q * Mp + j] : e == c ? kss[(long)c * Mp + j] : T(0)) - s;
     }
 }
 
@@ -230,12 +233,12 @@ int gram_diag_terms(int model, int d, const T* Xst, long Mp, int m, const double
 
 long terms_partials(int C, long Mp) { return (long)(C + C * (C + 1) / 2) * PREDICT_SPLIT * Mp; }
 
-template <typename T, int C>
+template <typename T, int C, bool PACKED = false>
 static void terms_reduce_launch(const T* V, const T* Ks, long N, long Mp, int m, const T* alpha, const T* kss, T* part, T* mean,
                                 T* cov, hipStream_t s, Batch bt, long wbs) {
   const unsigned Bz = (unsigned)bt.B;
   terms_partial_kernel<T, C><<<dim3((unsigned)(Mp / 64), PREDICT_SPLIT, Bz), 256, 0, s>>>(V, Ks, N, Mp, alpha, part, bt.ws, wbs);
-  terms_finish_kernel<T, C><<<dim3((unsigned)((m + 255) / 256), 1, Bz), 256, 0, s>>>(part, Mp, m, kss, mean, cov, wbs);
+  terms_finish_kernel<T, C, PACKED><<<dim3((unsigned)((m + 255) / 256), 1, Bz), 256, 0, s>>>(part, Mp, m, kss, mean, cov, wbs);
 }
 
 template <typename T>
@@ -253,11 +256,28 @@ int terms_reduce(int C, const T* V, const T* Ks, long N, long Mp, int m, const T
   return (int)hipGetLastError();
 }
 
+// P planes of dgp_slopes.hip (1 + ncols <= 1 + DGP_C_DMAX) against the packed prior block `prior` (P (P + 1) / 2 x Mp)
+template <typename T>
+int slopes_reduce(int P, const T* V, const T* Ks, long N, long Mp, int m, const T* alpha, const T* prior, T* part, T* mean, T* cov,
+                  hipStream_t s, Batch bt, long wbs) {
+  switch (P) {
+    case 2: terms_reduce_launch<T, 2, true>(V, Ks, N, Mp, m, alpha, prior, part, mean, cov, s, bt, wbs); break;
+    case 3: terms_reduce_launch<T, 3, true>(V, Ks, N, Mp, m, alpha, prior, part, mean, cov, s, bt, wbs); break;
+    case 4: terms_reduce_launch<T, 4, true>(V, Ks, N, Mp, m, alpha, prior, part, mean, cov, s, bt, wbs); break;
+    case 5: terms_reduce_launch<T, 5, true>(V, Ks, N, Mp, m, alpha, prior, part, mean, cov, s, bt, wbs); break;
+    case 6: terms_reduce_launch<T, 6, true>(V, Ks, N, Mp, m, alpha, prior, part, mean, cov, s, bt, wbs); break;
+    case 7: terms_reduce_launch<T, 7, true>(V, Ks, N, Mp, m, alpha, prior, part, mean, cov, s, bt, wbs); break;
+    default: return -2;
+  }
+  return (int)hipGetLastError();
+}
+
 #define DGP_INST(T)                                                                                                              \
   template int gram_cross_terms<T>(int, int, const T*, long, int, const T*, long, int, const double*, T*, hipStream_t, Batch, long, \
                                    void*, void*);                                                                                 \
   template int gram_diag_terms<T>(int, int, const T*, long, int, const double*, T*, hipStream_t, Batch, long, void*);              \
-  template int terms_reduce<T>(int, const T*, const T*, long, long, int, const T*, const T*, T*, T*, T*, hipStream_t, Batch, long);
+  template int terms_reduce<T>(int, const T*, const T*, long, long, int, const T*, const T*, T*, T*, T*, hipStream_t, Batch, long); \
+  template int slopes_reduce<T>(int, const T*, const T*, long, long, int, const T*, const T*, T*, T*, T*, hipStream_t, Batch, long);
 DGP_INST(double)
 DGP_INST(float)
 

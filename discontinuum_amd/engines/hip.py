@@ -693,5 +693,17 @@ class MarginalHIP(BaseModel):
 
         return decompose(self, covariates, groups=groups, ci=ci, return_cov=return_cov)
 
+    @is_fitted
+    def slope(self, covariates, wrt=None, ci=0.95, return_cov=False):
+        """Exact posterior of the DERIVATIVES of the fitted surface with respect to its covariates at the points of
+        ``covariates`` (``dgp_predict_slopes``; one pass, from the factorisation the engine holds): d ln C / d ln Q, the
+        trend rate d ln C / dt, d ln Q / d stage.  ``wrt``: a covariate name or a list of names (default: all).  -> Dataset
+        on (``wrt``, the covariates' coordinate) with ``mean``, ``se``, ``lower`` / ``upper`` (exact central ``ci`` interval)
+        and ``prob_positive``, in units of the transformed target per unit of the covariate (of its logarithm for log
+        covariates, per year for time).  See ``discontinuum_amd.slopes.slope``."""
+        from ..slopes import slope
+
+        return slope(self, covariates, wrt=wrt, ci=ci, return_cov=return_cov)
+
     def build_model(self, X, y, **kwargs):
         raise NotImplementedError("This method must be implemented in a subclass")

@@ -19,7 +19,7 @@ import torch
 from torch import nn
 
 from .. import gp
-from ..engines.base import DataMixin, ModelConfig
+from ..engines.base import DataMixin, ModelConfig, is_fitted
 from .. import _lib
 from ..engines.hip import MarginalHIP, MeanShortcut
 from ..gp import kernels as K
@@ -257,6 +257,15 @@ class RatingGPMarginalHIP(RatingDataMixin, MarginalHIP):
         self.likelihood = gp.likelihoods.FixedNoiseGaussianLikelihood(
             noise=fixed, learn_additional_noise=True, noise_prior=HalfNormalPrior(scale=0.03))
         return ExactGPModel(X, y, self.likelihood)
+
+    @is_fitted
+    def rating_exponent(self, covariates, ci=0.95):
+        """The local rating exponent d ln Q / d ln h = h d ln Q / d stage at the points of ``covariates``, with its standard
+        error, exact ``ci`` interval and ``prob_positive`` -- the posterior probability that the rating is increasing there,
+        which the monotonicity penalty only encourages while it trains.  See ``discontinuum_amd.slopes.rating_exponent``."""
+        from ..slopes import rating_exponent
+
+        return rating_exponent(self, covariates, ci=ci)
 
     def _mean_shortcut(self):
         lik = self.likelihood

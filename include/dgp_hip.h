@@ -319,6 +319,30 @@ size_t dgp_predict_terms_workspace_bytes(const dgp_plan* plan, int64_t m);
 int dgp_predict_terms(dgp_plan* plan, const double* theta_host, const void* Xs_dev, int64_t m, void* work_dev,
                       size_t work_bytes, void* mean_dev, void* cov_dev, void* stream);
 
+/* The posterior of the fit's INPUT DERIVATIVES (slopes).  The derivative of a GP is a GP: with D_0 = id, D_q = d / d x*_{c_q}
+ * acting on the test point (c_q = cols_host[q - 1], raw input columns as in Xs; P = 1 + ncols), T = L^-1, alpha = K^^-1 r and
+ * V_a = T (D_a K)(X, X*):
+ *     mean_dev[site][a][j]           = (D_a K)(x*_j, X) alpha                                         E[D_a f(x*_j) | y]
+ *     cov_dev[site][a(a+1)/2 + b][j] = D_a D'_b k(x, x')|x=x'=x*_j - V_a[:, j]^T V_b[:, j],  b <= a    Cov[D_a f, D_b f | y](x*_j)
+ * in the plan's dtype; plane 0 is dgp_predict's latent mean and variance, the rest the slopes in the model's input units and
+ * their covariances with each other and with the value.  This is what a user of the reference can only approximate by
+ * differencing two calls of its predict (src/discontinuum/engines/gpytorch.py:599-626), without a standard error, and the
+ * a-posteriori reading of the monotonicity that rating-gp only penalises while it trains
+ * (src/rating_gp/models/gpytorch.py:130-187): P(d ln Q / d stage > 0) at any stage and time.
+ * Every shipped covariance is mean-square differentiable in every column except through a Matern-1/2 factor of a composite:
+ * dgp_model_input_differentiable(model, d, col) -> 1 / 0, < 0 for an unsupported (model, d) or a column outside 0 .. d - 1
+ * (needs no device).  The prior block is not diagonal for rating (the gates correlate value and stage slope).
+ * One pair evaluation per matrix entry for all planes, the prediction's GEMM at width P M, one pass over V and Ks; fixed
+ * summation orders (bitwise repeatable); the plan is only read.  Preconditions and arguments as dgp_predict_terms
+ * (single-site, batched and ragged plans); cols: distinct, in 0 .. d - 1, 1 <= ncols <= d; cov_dev may be NULL.  work_dev:
+ * dgp_predict_slopes_workspace_bytes(plan, m, ncols) bytes (0 for bad arguments), about batch x 2 P N M elements.
+ * DGP_E_ARG / DGP_E_WORKSPACE / DGP_E_STATE before any launch as for dgp_predict_terms, DGP_E_ARG for bad cols,
+ * DGP_E_MODEL for a column that is not differentiable. */
+int dgp_model_input_differentiable(int model, int d, int col);
+size_t dgp_predict_slopes_workspace_bytes(const dgp_plan* plan, int64_t m, int ncols);
+int dgp_predict_slopes(dgp_plan* plan, const double* theta_host, const void* Xs_dev, int64_t m, const int* cols_host, int ncols,
+                       void* work_dev, size_t work_bytes, void* mean_dev, void* cov_dev, void* stream);
+
 /* Predictive mean only, and its vector-Jacobian product -- what the rating-gp monotonicity penalty
  * differentiates (src/rating_gp/models/gpytorch.py:130-187: mean of likelihood(model(x_grid)) with grad).
  *   dgp_predict_mean : mean_dev[j] = K(x*_j, X) alpha                                  (m entries)
