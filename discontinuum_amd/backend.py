@@ -457,6 +457,13 @@ class GPPlan:
         with torch.cuda.device(self.device):
             return period_moments(cov, m, mu, scale2, w, groups, ngroups, mode, extra_var)
 
+    def exceedance_moments(self, cov, m: int, mu, thresh, w, groups, ngroups: int, extra_var=None):
+        """Exact mean and covariance of threshold-exceedance counts of the posterior (``dgp_exceedance_moments``): see the
+        module-level ``exceedance_moments``.  Unbatched (cov (M, M), vectors (m,), thresh (L, m)) -> mean (L, P), cov
+        (L, P, P); batched (cov (B, M, M), vectors (B, m), thresh (B, L, m)) -> (B, L, P), (B, L, P, P); fp64 device tensors."""
+        with torch.cuda.device(self.device):
+            return exceedance_moments(cov, m, mu, thresh, w, groups, ngroups, extra_var)
+
     def posterior_period_moments(self, theta, Xs: torch.Tensor, mu, scale2, w, groups, ngroups: int, mode: int, extra_var=None):
         """``period_moments`` of the posterior at Xs straight from the held factorisation (``dgp_posterior_period_moments``):
         the (M, M) covariance is never formed.  Xs (m, d) -- (batch, m, d) for a batched plan, theta (batch, ntheta) --; the
@@ -665,6 +672,70 @@ def period_moments(cov: torch.Tensor, m: int, mu: torch.Tensor, scale2, w: torch
         "dgp_period_moments",
     )
     return mean_out, cov_out
+
+
+def exceedance_moments(cov: torch.Tensor, m: int, mu: torch.Tensor, thresh: torch.Tensor, w: torch.Tensor, groups: torch.Tensor,
+                       ngroups: int, extra_var: torch.Tensor | None = None):
+    """Exact mean and covariance of the counts N_g = sum_{i in g} w_i 1[f_i > u_i] of a latent posterior f ~ N(mu, C), per
+    threshold level, through one ``dgp_exceedance_moments`` call (no factorisation, no draws): E N_g = sum w_i Phi(z_i),
+    Cov(N_g, N_h) = sum w_i w_j (Phi2(z_i, z_j; rho_ij) - Phi(z_i) Phi(z_j)), z = (mu - u) / sigma.
+
+    ``cov``: what ``GPPlan.posterior_cov`` returns -- (M, M), M = padded m, lower triangle and diagonal blocks valid -- or
+    (B, M, M) for B sites; ``mu``: the MODEL-space mean, (m,) / (B, m), the dtype of ``cov``; ``thresh``: model-space
+    thresholds, (L, m) / (B, L, m) with 1 <= L <= 64, +-inf allowed; ``w``: weights (m,) / (B, m); ``groups``: int32 ids
+    (m,) / (B, m) in 0 .. ngroups-1, non-decreasing except for -1 (excluded) anywhere; ``extra_var``: None or (m,) / (B, m)
+    added to the variances (never to the covariances).
+    -> (mean (L, P), cov (L, P, P)) or ((B, L, P), (B, L, P, P)), float64 device tensors; levels do not interact."""
+    lib = _lib.load()
+    batched = cov.dim() == 3
+    B = cov.shape[0] if batched else 1
+    M = int(lib.dgp_padded_n(int(m)))
+    lead = (B,) if batched else ()
+    if cov.dtype not in _DTYPES or not cov.is_cuda or not cov.is_contiguous() or tuple(cov.shape) != lead + (M, M):
+        raise ValueError(f"cov must be a contiguous {lead + (M, M)} float64 / float32 CUDA tensor")
+    dev = cov.device
+
+    def vec(t, name, dtype):
+        if t is None:
+            return None
+        t = torch.as_tensor(t).to(dev, dtype).contiguous()
+        if tuple(t.shape) != lead + (int(m),):
+            raise ValueError(f"{name} must have shape {lead + (int(m),)}")
+        return t
+
+    mu_t, w_t = vec(mu, "mu", cov.dtype), vec(w, "w", torch.float64)
+    g_t, ev_t = vec(groups, "groups", torch.int32), vec(extra_var, "extra_var", cov.dtype)
+    u_t = torch.as_tensor(thresh).to(dev, torch.float64).contiguous()
+    if u_t.dim() != len(lead) + 2 or tuple(u_t.shape[:-2]) != lead or u_t.shape[-1] != int(m):
+        raise ValueError(f"thresh must have shape {lead + ('L', int(m))}")
+    P, L = int(ngroups), int(u_t.shape[-2])
+    need = int(lib.dgp_exceedance_moments_workspace_bytes(int(m), P, L, B))
+    if need == 0:
+        raise ValueError(f"bad size: m = {int(m)}, ngroups = {P}, levels = {L}, batch = {B} "
+                         "(1 <= m <= 2^20, 1 <= ngroups <= 65535, 1 <= levels <= 64, 1 <= batch <= 1024)")
+    work = torch.empty(need, dtype=torch.uint8, device=dev)
+    mean_out = torch.empty(lead + (L, P), dtype=torch.float64, device=dev)
+    cov_out = torch.empty(lead + (L, P, P), dtype=torch.float64, device=dev)
+    _lib.check(
+        lib.dgp_exceedance_moments(_DTYPES[cov.dtype], _ptr(cov), int(m), B, _ptr(mu_t), _ptr(u_t), L, _ptr(w_t), _ptr(g_t), P,
+                                   _ptr(ev_t) if ev_t is not None else None, _ptr(work), need, _ptr(mean_out), _ptr(cov_out),
+                                   _stream()),
+        "dgp_exceedance_moments",
+    )
+    return mean_out, cov_out
+
+
+def bvn_excess(h: torch.Tensor, k: torch.Tensor, rho: torch.Tensor):
+    """Phi2(h, k; rho) - Phi(h) Phi(k) pointwise on the device (``dgp_debug_bvn_excess``): the pair function of
+    ``exceedance_moments``, for tests.  Float64 CUDA tensors of one shape."""
+    lib = _lib.load()
+    if not (h.is_cuda and h.dtype == k.dtype == rho.dtype == torch.float64 and h.shape == k.shape == rho.shape):
+        raise ValueError("h, k, rho must be float64 CUDA tensors of one shape")
+    h, k, rho = h.contiguous(), k.contiguous(), rho.contiguous()
+    out = torch.empty_like(h)
+    with torch.cuda.device(h.device):
+        _lib.check(lib.dgp_debug_bvn_excess(_ptr(h), _ptr(k), _ptr(rho), h.numel(), _ptr(out), _stream()), "dgp_debug_bvn_excess")
+    return out
 
 
 def cross_validate_folds(plan, groups, launch, max_group_bound=None):

@@ -1355,6 +1355,41 @@ int dgp_posterior_period_moments(dgp_plan* p, const double* theta, const void* X
   return wrap(rc, "dgp_posterior_period_moments");
 }
 
+static bool ex_sizes_ok(int64_t m, int ngroups, int nlevels, int batch) {
+  return m > 0 && m <= (1 << 20) && ngroups > 0 && ngroups <= 65535 && nlevels >= 1 && nlevels <= 64 && batch > 0 &&
+         batch <= DGP_MAX_BATCH_SITES;
+}
+size_t dgp_exceedance_moments_workspace_bytes(int64_t m, int ngroups, int nlevels, int batch) {
+  if (!ex_sizes_ok(m, ngroups, nlevels, batch)) return 0;
+  return exceedance_moments_workspace_bytes(m, ngroups, nlevels, batch);
+}
+
+int dgp_exceedance_moments(int dtype, const void* cov, int64_t m, int batch, const void* mu, const double* thresh, int nlevels,
+                           const double* w, const int32_t* group, int ngroups, const void* extra_var, void* work,
+                           size_t work_bytes, double* mean_out, double* cov_out, void* stream) {
+  if (dtype != DGP_F64 && dtype != DGP_F32) return fail(DGP_E_ARG, "dgp_exceedance_moments: dtype must be 0 (f64) or 1 (f32)");
+  if (!cov || !mu || !thresh || !w || !group || !mean_out || !cov_out)
+    return fail(DGP_E_ARG, "dgp_exceedance_moments: null argument");
+  if (!ex_sizes_ok(m, ngroups, nlevels, batch))
+    return fail(DGP_E_ARG,
+                "dgp_exceedance_moments: bad size (1 <= m <= 2^20, 1 <= ngroups <= 65535, 1 <= nlevels <= 64, 1 <= batch <= 1024)");
+  if (!work || work_bytes < exceedance_moments_workspace_bytes(m, ngroups, nlevels, batch))
+    return fail(DGP_E_WORKSPACE, "dgp_exceedance_moments: workspace missing or too small");
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = dtype == DGP_F64
+                     ? exceedance_moments<double>((const double*)cov, m, batch, (const double*)mu, thresh, nlevels, w, group, ngroups,
+                                                  (const double*)extra_var, (double*)work, mean_out, cov_out, s)
+                     : exceedance_moments<float>((const float*)cov, m, batch, (const float*)mu, thresh, nlevels, w, group, ngroups,
+                                                 (const float*)extra_var, (double*)work, mean_out, cov_out, s);
+  return wrap(rc, "dgp_exceedance_moments");
+}
+
+int dgp_debug_bvn_excess(const double* h, const double* k, const double* rho, int64_t count, double* out, void* stream) {
+  if (!h || !k || !rho || !out || count <= 0 || count > (1ll << 31))
+    return fail(DGP_E_ARG, "dgp_debug_bvn_excess: null argument / bad count");
+  return wrap(debug_bvn_excess(h, k, rho, count, out, (hipStream_t)stream), "dgp_debug_bvn_excess");
+}
+
 static bool cv_sizes_ok(const dgp_plan* p, int ngroups, int64_t max_group) {
   return p && ngroups >= 1 && ngroups <= p->n && max_group >= 1 && max_group <= p->n;
 }

@@ -1,0 +1,487 @@
+// dgp_exceed.hip -- exact moments of threshold-exceedance counts of a Gaussian posterior (dgp_exceedance_moments).
+//
+// f ~ N(mu, C) over m points (C: the matrix dgp_posterior_cov leaves; only its lower triangle is read), per level l a
+// threshold u_il in model space, weights w_i and group ids g_i (non-decreasing, -1 = excluded).  With
+//     sigma_i^2 = C_ii (+ extra_var_i),  z_il = (mu_i - u_il) / sigma_i,  p_il = Phi(z_il),  rho_ij = C_ij / (sigma_i sigma_j)
+// the count N_g = sum_{i in g} w_i 1[f_i > u_il] has
+//     mean_g = sum_{i in g} w_i p_il,   cov_gh = sum_{i in g} sum_{j in h} w_i w_j D(z_il, z_jl, rho_ij),
+//     D(h, k, rho) = Phi2(h, k; rho) - Phi(h) Phi(k)  (= p (1 - p) on the diagonal).
+//
+// The pair function is Genz's bivariate normal algorithm (Numerical computation of rectangular bivariate and trivariate
+// normal and t probabilities, Statistics and Computing 14, 2004) rearranged to return D:
+//   |rho| < 0.925   D = asin(rho) / (4 pi) sum_n w_n exp((s_n h k - (h^2 + k^2) / 2) / (1 - s_n^2)),  s_n = sin(asin(rho) (1 +- x_n) / 2),
+//                   Gauss-Legendre with 6 (|rho| < 0.3), 12 (< 0.75) or 20 nodes: the integral IS D, nothing is subtracted; every
+//                   exponent is <= 0 (exp_nonpos).  The two nodes +-x_n share sin / cos of asin(rho) / 2 and asin(rho) x_n / 2
+//                   (angle addition; all angles below 0.6, so a short Taylor polynomial needs no range reduction), and
+//                   1 - s_n^2 is the square of the angle's cosine, which the same products give without cancellation.
+//   0.925 <= |rho| < 1  the expansion about |rho| = 1 plus a 20-node rule for its remainder.
+//   |rho| = 1       min(Phi(h), Phi(k)) - Phi(h) Phi(k)  /  max(0, Phi(h) + Phi(k) - 1) - Phi(h) Phi(k).
+// What depends on rho alone -- the nodes' sines and 1 / (1 - s_n^2), the expansion's abscissae and roots -- is computed once
+// per pair, in the node loop, whose inner loop runs over the levels of the chunk (LC = 8, 4, 2 or 1 levels in registers).
+//
+// Launches (gridDim.z = sites), no floating-point atomics: a tiny init and a prep once, then per chunk of levels
+//   prep    one thread per point: w_i (0 if excluded), 1 / sigma_i, z_il and p_il for every level, each group's column range.
+//           A point is DECIDED at a level when sigma_i^2 <= 0 or u_il = +-inf: z = +-inf (a tie mu = u is "not exceeded"),
+//           p = 1 / 0 and D = 0 with every other point; so is an excluded point (w = 0).  NaN stays NaN.
+//   pairs   one workgroup per (64-row block, group h): Y[l][i][h] = sum_j w_j D(z_il, z_jl, rho_ij) over the j of h that the
+//           reduce needs -- j < i for g(i) = h, read as C[i][j] (a wave per row, lanes along j); all j of h for g(i) < h, read
+//           as C[j][i] (lanes along i, the four waves take every fourth j); nothing for g(i) > h.  Every unordered pair is
+//           evaluated once.  Lanes of a wave see neighbouring points, hence similar rho: the branch on |rho| is mostly
+//           wave-uniform.
+//   reduce  one workgroup per (64 columns h, level, group g): cov_gh = sum_{i in g} w_i Y[l][i][h] for h > g, twice that plus
+//           sum_i w_i^2 p_il (1 - p_il) for h = g, written to (g, h) and (h, g) from one value; mean_g beside it.
+// Every sum runs in a fixed order: bitwise repeatable, and a site's numbers do not depend on its batch.  All arithmetic
+// after the loads of C and mu is double.
+#include <climits>
+#include <cmath>
+
+#include "dgp_common.h"
+#include "dgp_internal.h"
+#include "dgp_models.h"
+
+namespace dgp {
+
+namespace {
+
+constexpr int EX_ROWS = 64;    // rows of a workgroup of the pairs pass (divides DGP_TILE_HOST, the cov buffer's padding)
+constexpr int EX_CHUNK = 8;    // most levels a pairs / reduce pass takes at once
+constexpr double EX_ZDET = 38.0;  // |z| beyond which a point is decided: Phi(-38) = 3e-316
+
+// per-site work area, in doubles: w[M], 1 / sigma[M], z[L][M], p[L][M], Y[min(L, EX_CHUNK)][M][P], then 2 P ints
+__host__ __device__ inline long ex_site_doubles(long M, int P, int L) {
+  return 2 * M + 2 * (long)L * M + (long)(L < EX_CHUNK ? L : EX_CHUNK) * M * P + P;
+}
+
+// Gauss-Legendre abscissae |x_n| and weights on [-1, 1], one of each +- pair: 6-, 12- and 20-point rules
+__constant__ double ex_gl_c[2][19] = {
+    {0.932469514203152, 0.6612093864662645, 0.23861918608319693,
+     0.9815606342467192, 0.9041172563704748, 0.7699026741943047, 0.5873179542866175, 0.3678314989981802, 0.1252334085114689,
+     0.9931285991850949, 0.9639719272779138, 0.9122344282513258, 0.8391169718222188, 0.7463319064601508, 0.636053680726515,
+     0.5108670019508271, 0.37370608871541955, 0.2277858511416451, 0.07652652113349734},
+    {0.17132449237916975, 0.36076157304813894, 0.46791393457269137,
+     0.04717533638651202, 0.10693932599531888, 0.1600783285433461, 0.20316742672306565, 0.23349253653835464, 0.2491470458134027,
+     0.017614007139153273, 0.04060142980038622, 0.06267204833410944, 0.08327674157670467, 0.10193011981724026,
+     0.11819453196151825, 0.13168863844917653, 0.14209610931838187, 0.14917298647260366, 0.15275338713072578}};
+__shared__ double ex_gl[2][19];
+
+// the tables of the pair function (Gauss-Legendre, exp_nonpos); a barrier must follow before the first bvn_excess
+__device__ __forceinline__ void ex_tables_init() {
+  exp_table_init<double>();
+  if (threadIdx.x >= 64 && threadIdx.x < 64 + 38) (&ex_gl[0][0])[threadIdx.x - 64] = (&ex_gl_c[0][0])[threadIdx.x - 64];
+}
+
+__device__ __forceinline__ double ex_phi(double x) { return 0.5 * erfc(-0.70710678118654752440 * x); }
+
+// sin and cos of |t| <= 0.6 by their Taylor series (next terms t^17 / 17! < 5e-19, t^16 / 16! < 2e-17)
+__device__ __forceinline__ void ex_sincos_small(double t, double& s, double& c) {
+  const double q = t * t;
+  double ps = -1.0 / 1307674368000.0;
+  ps = __builtin_fma(ps, q, 1.0 / 6227020800.0);
+  ps = __builtin_fma(ps, q, -1.0 / 39916800.0);
+  ps = __builtin_fma(ps, q, 1.0 / 362880.0);
+  ps = __builtin_fma(ps, q, -1.0 / 5040.0);
+  ps = __builtin_fma(ps, q, 1.0 / 120.0);
+  ps = __builtin_fma(ps, q, -1.0 / 6.0);
+  s = __builtin_fma(ps * q, t, t);
+  double pc = -1.0 / 87178291200.0;
+  pc = __builtin_fma(pc, q, 1.0 / 479001600.0);
+  pc = __builtin_fma(pc, q, -1.0 / 3628800.0);
+  pc = __builtin_fma(pc, q, 1.0 / 40320.0);
+  pc = __builtin_fma(pc, q, -1.0 / 720.0);
+  pc = __builtin_fma(pc, q, 1.0 / 24.0);
+  pc = __builtin_fma(pc, q, -0.5);
+  c = __builtin_fma(pc, q, 1.0);
+}
+
+// D(h_l, k_l, rho) for the LC levels of a chunk; ph / pk = Phi(h) / Phi(k) as prep left them (read above |rho| = 0.925 only)
+template <int LC>
+__device__ __forceinline__ void bvn_excess(const double (&h)[LC], const double (&k)[LC], const double (&ph)[LC],
+                                           const double (&pk)[LC], double r, double (&D)[LC]) {
+  bool live = false;
+#pragma unroll
+  for (int l = 0; l < LC; ++l) live |= !(fabs(h[l]) > EX_ZDET || fabs(k[l]) > EX_ZDET);
+  if (!live) {  // decided at every level (an excluded point, a zero variance)
+#pragma unroll
+    for (int l = 0; l < LC; ++l) D[l] = 0.0;
+    return;
+  }
+  r = r > 1.0 ? 1.0 : (r < -1.0 ? -1.0 : r);  // (comparisons: a NaN stays)
+  const double ar = fabs(r);
+  if (ar < 0.925) {
+    const int n0 = ar < 0.3 ? 0 : (ar < 0.75 ? 3 : 9), n1 = ar < 0.3 ? 3 : (ar < 0.75 ? 9 : 19);
+    const double asr = asin(r), half = 0.5 * asr;
+    double s0, c0;
+    ex_sincos_small(half, s0, c0);
+    double hk[LC], hs[LC], acc[LC];
+#pragma unroll
+    for (int l = 0; l < LC; ++l) {
+      hk[l] = h[l] * k[l];
+      hs[l] = 0.5 * (h[l] * h[l] + k[l] * k[l]);
+      acc[l] = 0.0;
+    }
+    for (int n = n0; n < n1; ++n) {
+      double st, ct;
+      ex_sincos_small(half * ex_gl[0][n], st, ct);
+      const double wn = ex_gl[1][n];
+      const double sa = s0 * ct, sb = c0 * st, ca = c0 * ct, cb = s0 * st;
+      const double snp = sa + sb, csp = ca - cb, snm = sa - sb, csm = ca + cb;  // the angles half (1 + x), half (1 - x)
+      const double ip = 1.0 / (csp * csp), im = 1.0 / (csm * csm);
+#pragma unroll
+      for (int l = 0; l < LC; ++l) {
+        const double e = exp_nonpos(__builtin_fma(snp, hk[l], -hs[l]) * ip) + exp_nonpos(__builtin_fma(snm, hk[l], -hs[l]) * im);
+        acc[l] = __builtin_fma(wn, e, acc[l]);
+      }
+    }
+#pragma unroll
+    for (int l = 0; l < LC; ++l) D[l] = acc[l] * asr * 0.07957747154594767280;  // 1 / (4 pi)
+  } else {
+    const bool neg = r < 0.0;
+    double kk[LC], hk[LC], bvn[LC];
+#pragma unroll
+    for (int l = 0; l < LC; ++l) {
+      kk[l] = neg ? -k[l] : k[l];
+      hk[l] = h[l] * kk[l];
+      bvn[l] = 0.0;
+    }
+    if (ar < 1.0) {
+      const double as = (1.0 - ar) * (1.0 + ar), a = sqrt(as), ias = 1.0 / as;
+      double bs[LC], c[LC], d[LC];
+#pragma unroll
+      for (int l = 0; l < LC; ++l) {
+        const double df = h[l] - kk[l];
+        bs[l] = df * df;
+        c[l] = (4.0 - hk[l]) * 0.125;
+        d[l] = (12.0 - hk[l]) * 0.0625;
+        const double asr = -0.5 * (bs[l] * ias + hk[l]);
+        if (asr > -100.0)
+          bvn[l] = a * exp(asr) * (1.0 - c[l] * (bs[l] - as) * (1.0 - d[l] * bs[l] * 0.2) * (1.0 / 3.0) + c[l] * d[l] * as * as * 0.2);
+        if (hk[l] > -100.0) {
+          const double b = sqrt(bs[l]);
+          bvn[l] -= exp(-0.5 * hk[l]) * 2.50662827463100050242 * ex_phi(-b / a) * b *
+                    (1.0 - c[l] * bs[l] * (1.0 - d[l] * bs[l] * 0.2) * (1.0 / 3.0));
+        }
+      }
+      const double a2 = 0.5 * a;
+      for (int n = 9; n < 19; ++n) {
+        const double xn = ex_gl[0][n], wn = a2 * ex_gl[1][n];
+#pragma unroll
+        for (int sg = 0; sg < 2; ++sg) {
+          const double ax = a2 * (sg ? 1.0 + xn : 1.0 - xn);
+          const double xs = ax * ax, rs = sqrt(1.0 - xs), ixs = 1.0 / xs, irs = 1.0 / rs;
+          const double q = -0.5 * xs / ((1.0 + rs) * (1.0 + rs));
+#pragma unroll
+          for (int l = 0; l < LC; ++l) {
+            const double asr = -0.5 * (bs[l] * ixs + hk[l]);
+            if (asr > -100.0) bvn[l] += wn * exp(asr) * (exp(hk[l] * q) * irs - (1.0 + c[l] * xs * (1.0 + d[l] * xs)));
+          }
+        }
+      }
+#pragma unroll
+      for (int l = 0; l < LC; ++l) bvn[l] *= -0.15915494309189533577;  // -1 / (2 pi)
+    }
+#pragma unroll
+    for (int l = 0; l < LC; ++l) {
+      double v;
+      if (!neg) {
+        v = bvn[l] + (ph[l] < pk[l] ? ph[l] : pk[l]);
+      } else {
+        v = -bvn[l];
+        if (k[l] > -h[l]) v += (ph[l] + pk[l]) - 1.0;
+      }
+      D[l] = v - ph[l] * pk[l];
+    }
+  }
+#pragma unroll
+  for (int l = 0; l < LC; ++l) {
+    if (h[l] != h[l] || k[l] != k[l] || r != r) D[l] = __builtin_nan("");
+    if (fabs(h[l]) > EX_ZDET || fabs(k[l]) > EX_ZDET) D[l] = 0.0;
+  }
+}
+
+__device__ __forceinline__ double ex_wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+__device__ __forceinline__ void ex_range(const int* se, int g, int& c0, int& c1) {
+  c0 = se[2 * g];
+  c1 = se[2 * g + 1];
+  if (c1 <= c0) c0 = c1 = 0;  // empty group (start still INT_MAX)
+}
+
+struct ExWork {  // the parts of a site's work area
+  double *w, *sinv, *z, *p, *Y;
+  int* se;
+  __device__ ExWork(double* work, long ws, long M, int P, int L) {
+    w = work + (long)blockIdx.z * ws;
+    sinv = w + M;
+    z = sinv + M;
+    p = z + (long)L * M;
+    Y = p + (long)L * M;
+    se = (int*)(Y + (long)(L < EX_CHUNK ? L : EX_CHUNK) * M * P);
+  }
+};
+
+__global__ __launch_bounds__(256) void ex_init_kernel(double* work, long ws, long M, int P, int L) {
+  const int g = blockIdx.x * 256 + threadIdx.x;
+  if (g >= P) return;
+  const ExWork wk(work, ws, M, P, L);
+  wk.se[2 * g] = INT_MAX;
+  wk.se[2 * g + 1] = 0;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void ex_prep_kernel(const T* __restrict__ cov, long M, int m, int P, int L,
+                                                      const T* __restrict__ mu, const double* __restrict__ thresh,
+                                                      const double* __restrict__ w, const int* __restrict__ group,
+                                                      const T* __restrict__ ev, double* work, long ws) {
+  const long j = (long)blockIdx.x * 256 + threadIdx.x;
+  const int z = blockIdx.z;
+  if (j >= M) return;
+  const ExWork wk(work, ws, M, P, L);
+  bool in = false;
+  double wj = 0.0, sinv = 0.0, var = 0.0, muj = 0.0;
+  if (j < m) {
+    const long k = (long)z * m + j;
+    const int g = group[k];
+    if (g >= 0 && g < P) {
+      in = true;
+      wj = w[k];
+      muj = (double)mu[k];
+      var = (double)cov[(long)z * M * M + j * (M + 1)];
+      if (ev) var += (double)ev[k];
+      sinv = var > 0.0 ? 1.0 / sqrt(var) : (var != var ? var : 0.0);
+      atomicMin(&wk.se[2 * g], (int)j);
+      atomicMax(&wk.se[2 * g + 1], (int)j + 1);
+    }
+  }
+  wk.w[j] = wj;
+  wk.sinv[j] = sinv;
+  for (int l = 0; l < L; ++l) {
+    double zl = -INFINITY;  // excluded / pad: decided, p = 0
+    if (in) {
+      const double u = thresh[((long)z * L + l) * m + j];
+      if (var <= 0.0 || isinf(u))
+        zl = (muj != muj || u != u) ? __builtin_nan("") : (muj > u ? INFINITY : -INFINITY);
+      else
+        zl = (muj - u) * sinv;
+    }
+    wk.z[(long)l * M + j] = zl;
+    wk.p[(long)l * M + j] = ex_phi(zl);
+  }
+}
+
+// levels l0 .. l0 + LC of Y; see the file header
+template <typename T, int LC>
+__global__ __launch_bounds__(256) void ex_pairs_kernel(const T* __restrict__ cov, long M, int m, int P, int L, int l0,
+                                                       const int* __restrict__ group, double* __restrict__ work, long ws) {
+  const int rb = blockIdx.x, h = blockIdx.y, z = blockIdx.z;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const ExWork wk(work, ws, M, P, L);
+  const int r0 = rb * EX_ROWS;
+  int c0, c1;
+  ex_range(wk.se, h, c0, c1);
+  if (r0 >= c1) {  // every row here lies in a later group (or h is empty): nothing the reduce uses, but it reads numbers
+    if (tid < EX_ROWS)
+#pragma unroll
+      for (int l = 0; l < LC; ++l) wk.Y[((long)l * M + r0 + tid) * P + h] = 0.0;
+    return;
+  }
+  ex_tables_init();
+  __shared__ double low[LC][EX_ROWS], up[4][LC][EX_ROWS];
+  const T* C = cov + (long)z * M * M;
+  const int* gz = group + (long)z * m;
+  const double* zs = wk.z + (long)l0 * M;
+  const double* ps = wk.p + (long)l0 * M;
+  __syncthreads();
+
+  // g(i) = h: the j < i of the group, C[i][j]; a wave per row, lanes along the row
+  for (int ii = wave; ii < EX_ROWS; ii += 4) {
+    const int i = r0 + ii;
+    double acc[LC];
+#pragma unroll
+    for (int l = 0; l < LC; ++l) acc[l] = 0.0;
+    if (i < m && gz[i] == h) {
+      const T* row = C + (long)i * M;
+      const double si = wk.sinv[i];
+      double zi[LC], pi[LC];
+#pragma unroll
+      for (int l = 0; l < LC; ++l) {
+        zi[l] = zs[(long)l * M + i];
+        pi[l] = ps[(long)l * M + i];
+      }
+      for (int j = c0 + lane; j < i; j += 64) {
+        double zj[LC], pj[LC], D[LC];
+#pragma unroll
+        for (int l = 0; l < LC; ++l) {
+          zj[l] = zs[(long)l * M + j];
+          pj[l] = ps[(long)l * M + j];
+        }
+        bvn_excess<LC>(zi, zj, pi, pj, (double)row[j] * si * wk.sinv[j], D);
+        const double wj = wk.w[j];
+#pragma unroll
+        for (int l = 0; l < LC; ++l) acc[l] = __builtin_fma(wj, D[l], acc[l]);
+      }
+    }
+#pragma unroll
+    for (int l = 0; l < LC; ++l) {
+      const double v = ex_wave_sum(acc[l]);
+      if (lane == 0) low[l][ii] = v;
+    }
+  }
+
+  // 0 <= g(i) < h: every j of the group (all beyond i), C[j][i]; lanes along i, wave q takes j = c0 + q, c0 + q + 4, ...
+  {
+    const int i = r0 + lane;
+    double acc[LC];
+#pragma unroll
+    for (int l = 0; l < LC; ++l) acc[l] = 0.0;
+    const int gi = i < m ? gz[i] : -1;
+    if (gi >= 0 && gi < h) {
+      const T* col = C + i;
+      const double si = wk.sinv[i];
+      double zi[LC], pi[LC];
+#pragma unroll
+      for (int l = 0; l < LC; ++l) {
+        zi[l] = zs[(long)l * M + i];
+        pi[l] = ps[(long)l * M + i];
+      }
+      for (int j = c0 + wave; j < c1; j += 4) {
+        double zj[LC], pj[LC], D[LC];
+#pragma unroll
+        for (int l = 0; l < LC; ++l) {
+          zj[l] = zs[(long)l * M + j];
+          pj[l] = ps[(long)l * M + j];
+        }
+        bvn_excess<LC>(zi, zj, pi, pj, (double)col[(long)j * M] * si * wk.sinv[j], D);
+        const double wj = wk.w[j];
+#pragma unroll
+        for (int l = 0; l < LC; ++l) acc[l] = __builtin_fma(wj, D[l], acc[l]);
+      }
+    }
+#pragma unroll
+    for (int l = 0; l < LC; ++l) up[wave][l][lane] = acc[l];
+  }
+  __syncthreads();
+  if (tid < EX_ROWS)
+#pragma unroll
+    for (int l = 0; l < LC; ++l)
+      wk.Y[((long)l * M + r0 + tid) * P + h] = low[l][tid] + ((up[0][l][tid] + up[1][l][tid]) + (up[2][l][tid] + up[3][l][tid]));
+}
+
+// blockIdx.x = (64-column chunk of h) * LC + level of the chunk
+__global__ __launch_bounds__(256) void ex_reduce_kernel(long M, int P, int L, int l0, int LC, double* __restrict__ work, long ws,
+                                                        double* __restrict__ mean_out, double* __restrict__ cov_out) {
+  const int hc = blockIdx.x / LC, lc = blockIdx.x % LC, g = blockIdx.y, z = blockIdx.z;
+  if (hc > 0 && hc * 64 + 63 < g) return;  // every h of this chunk is < g: the (h, g) workgroup writes those entries
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const ExWork wk(work, ws, M, P, L);
+  const double* Y = wk.Y + (long)lc * M * P;
+  const double* p = wk.p + (long)(l0 + lc) * M;
+  int c0, c1;
+  ex_range(wk.se, g, c0, c1);
+  __shared__ double red[4][64];
+  __shared__ double mred[256], dred[256];
+  const int h = hc * 64 + lane;
+  double acc = 0.0;
+  if (h < P) {
+#pragma unroll 4
+    for (int i = c0 + wave; i < c1; i += 4) acc += wk.w[i] * Y[(long)i * P + h];
+  }
+  red[wave][lane] = acc;
+  const bool own = g >= hc * 64 && g < hc * 64 + 64;  // this workgroup holds (g, g): it needs the diagonal terms
+  if (hc == 0 || own) {
+    double s = 0.0, d = 0.0;
+    for (int i = c0 + tid; i < c1; i += 256) {
+      const double wi = wk.w[i], pi = p[i];
+      s += wi * pi;
+      d += wi * wi * (pi * (1.0 - pi));
+    }
+    mred[tid] = s;
+    dred[tid] = d;
+  }
+  __syncthreads();
+  if (hc == 0 || own) {
+    for (int s = 128; s > 0; s >>= 1) {
+      if (tid < s) {
+        mred[tid] += mred[tid + s];
+        dred[tid] += dred[tid + s];
+      }
+      __syncthreads();
+    }
+  }
+  if (wave == 0 && h < P && h >= g) {
+    double v = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
+    if (h == g) v = 2.0 * v + dred[0];
+    double* out = cov_out + ((long)z * L + l0 + lc) * P * P;
+    out[(long)g * P + h] = v;
+    out[(long)h * P + g] = v;
+  }
+  if (hc == 0 && tid == 0) mean_out[((long)z * L + l0 + lc) * P + g] = mred[0];
+}
+
+template <typename T, int LC>
+void ex_chunk(const T* cov, long M, int m, int B, int P, int L, int l0, const int* group, double* work, long ws, double* mean_out,
+              double* cov_out, hipStream_t s) {
+  ex_pairs_kernel<T, LC><<<dim3((unsigned)(M / EX_ROWS), (unsigned)P, (unsigned)B), 256, 0, s>>>(cov, M, m, P, L, l0, group, work, ws);
+  ex_reduce_kernel<<<dim3((unsigned)(((P + 63) / 64) * LC), (unsigned)P, (unsigned)B), 256, 0, s>>>(M, P, L, l0, LC, work, ws, mean_out,
+                                                                                                  cov_out);
+}
+
+__global__ __launch_bounds__(256) void ex_debug_kernel(const double* __restrict__ h, const double* __restrict__ k,
+                                                       const double* __restrict__ rho, long count, double* __restrict__ out) {
+  ex_tables_init();
+  __syncthreads();
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= count) return;
+  const double hv[1] = {h[i]}, kv[1] = {k[i]}, ph[1] = {ex_phi(hv[0])}, pk[1] = {ex_phi(kv[0])};
+  double D[1];
+  bvn_excess<1>(hv, kv, ph, pk, rho[i], D);
+  out[i] = D[0];
+}
+
+}  // namespace
+
+size_t exceedance_moments_workspace_bytes(long m, int P, int L, int B) {
+  return sizeof(double) * (size_t)B * (size_t)ex_site_doubles(round_up(m, DGP_TILE_HOST), P, L);
+}
+
+template <typename T>
+int exceedance_moments(const T* cov, long m, int B, const T* mu, const double* thresh, int L, const double* w, const int* group,
+                       int P, const T* ev, double* work, double* mean_out, double* cov_out, hipStream_t s) {
+  const long M = round_up(m, DGP_TILE_HOST);
+  const long ws = ex_site_doubles(M, P, L);
+  ex_init_kernel<<<dim3((unsigned)((P + 255) / 256), 1, (unsigned)B), 256, 0, s>>>(work, ws, M, P, L);
+  ex_prep_kernel<T><<<dim3((unsigned)((M + 255) / 256), 1, (unsigned)B), 256, 0, s>>>(cov, M, (int)m, P, L, mu, thresh, w, group, ev,
+                                                                                    work, ws);
+  for (int l0 = 0; l0 < L;) {  // chunks of 8, then 4, 2, 1 levels: a function of L alone
+    const int left = L - l0;
+    if (left >= 8) {
+      ex_chunk<T, 8>(cov, M, (int)m, B, P, L, l0, group, work, ws, mean_out, cov_out, s);
+      l0 += 8;
+    } else if (left >= 4) {
+      ex_chunk<T, 4>(cov, M, (int)m, B, P, L, l0, group, work, ws, mean_out, cov_out, s);
+      l0 += 4;
+    } else if (left >= 2) {
+      ex_chunk<T, 2>(cov, M, (int)m, B, P, L, l0, group, work, ws, mean_out, cov_out, s);
+      l0 += 2;
+    } else {
+      ex_chunk<T, 1>(cov, M, (int)m, B, P, L, l0, group, work, ws, mean_out, cov_out, s);
+      l0 += 1;
+    }
+  }
+  return (int)hipGetLastError();
+}
+
+template int exceedance_moments<double>(const double*, long, int, const double*, const double*, int, const double*, const int*, int,
+                                        const double*, double*, double*, double*, hipStream_t);
+template int exceedance_moments<float>(const float*, long, int, const float*, const double*, int, const double*, const int*, int,
+                                       const float*, double*, double*, double*, hipStream_t);
+
+int debug_bvn_excess(const double* h, const double* k, const double* rho, long count, double* out, hipStream_t s) {
+  ex_debug_kernel<<<dim3((unsigned)((count + 255) / 256)), 256, 0, s>>>(h, k, rho, count, out);
+  return (int)hipGetLastError();
+}
+
+}  // namespace dgp

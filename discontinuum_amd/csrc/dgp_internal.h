@@ -206,6 +206,15 @@ int posterior_period_moments(int mode, int model, int d, const T* V, long N, lon
                              const double* theta, const T* mu, const double* scale2, const double* w, const int* group, int P,
                              const T* ev, double* work, double* mean_out, double* cov_out, hipStream_t s, void* pre_scratch);
 
+// ---- dgp_exceed.hip: exact mean / covariance of the counts sum_{i in g} w_i 1[f_i > u_il], f ~ N(mu, C), per level l.  thresh
+// [B][L][m] in model space; mean_out [B][L][P], cov_out [B][L][P][P]; `work`: exceedance_moments_workspace_bytes
+size_t exceedance_moments_workspace_bytes(long m, int P, int L, int B);
+template <typename T>
+int exceedance_moments(const T* cov, long m, int B, const T* mu, const double* thresh, int L, const double* w, const int* group,
+                       int P, const T* ev, double* work, double* mean_out, double* cov_out, hipStream_t s);
+// out[i] = Phi2(h_i, k_i; rho_i) - Phi(h_i) Phi(k_i): the pair function of the pass above, pointwise
+int debug_bvn_excess(const double* h, const double* k, const double* rho, long count, double* out, hipStream_t s);
+
 // ---- dgp_terms.hip: the posterior of the covariance's additive parts (C = model_nterms).  Ks / V: N x (C Mp) row-major, term c
 // of test point j in column c Mp + j; kss: C Mp; part: terms_partials(C, Mp) elements; mean [B][C][m], cov [B][C (C + 1) / 2][m]
 // (entry (c, c'), c' <= c, at c (c + 1) / 2 + c'; null: not wanted) in the caller's arrays.

@@ -670,6 +670,44 @@ class MarginalHIP(BaseModel):
                          max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes)
 
     @is_fitted
+    def exceedance(self, covariates, threshold=None, threshold_series=None, freq="YE", above=True, fraction=False, ci=0.95,
+                   pred_noise=False, return_cov=False, max_bytes=None):
+        """Expected number of points per period of ``freq`` at which the target exceeds a data-space threshold -- days per
+        year above a criterion, for a daily record -- with its exact standard error: what ``sample()``, a comparison and a
+        count per period estimate by Monte Carlo, in one posterior covariance and one ``dgp_exceedance_moments`` pass.
+        ``threshold``: a number or a list of levels; ``threshold_series``: one threshold per point, (m,) or (L, m); exactly
+        one of them.  ``above=False``: the complement; ``fraction=True``: divided by the points of the period.  -> Dataset
+        on (``level``, ``time``) with ``mean``, ``se``, ``lower`` / ``upper`` (approximate ``ci`` interval: a beta
+        distribution with the exact moments) and ``n_points``; with ``return_cov`` also the (L, P, P) covariance.  A record
+        whose m x m covariance does not fit ``max_bytes`` (default ``loads.DEFAULT_MAX_BYTES``) raises ``ValueError``.  See
+        ``discontinuum_amd.exceedance``."""
+        from ..exceedance import exceedance
+        from ..loads import DEFAULT_MAX_BYTES
+
+        return exceedance(self, covariates, threshold=threshold, threshold_series=threshold_series, freq=freq, above=above,
+                          fraction=fraction, ci=ci, pred_noise=pred_noise, return_cov=return_cov,
+                          max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes)
+
+    @is_fitted
+    def duration_curve(self, covariates, levels=None, above=True, ci=0.95, pred_noise=False):
+        """Fraction of the record ``covariates`` on which the target exceeds each of ``levels`` (default: 21 quantiles of
+        the posterior mean), with the exact standard error of that fraction and approximate ``ci`` intervals -- for a
+        rating model over a stage record, the flow-duration curve.  -> Dataset on ``level`` with ``mean``, ``se``,
+        ``lower``, ``upper``.  See ``discontinuum_amd.exceedance.duration_curve``."""
+        from ..exceedance import duration_curve
+
+        return duration_curve(self, covariates, levels=levels, above=above, ci=ci, pred_noise=pred_noise)
+
+    @is_fitted
+    def exceedance_probability(self, covariates, threshold, above=True, pred_noise=False):
+        """Pointwise probability that the target exceeds ``threshold`` (a data-space number or one value per point) at each
+        point of ``covariates``, from the prediction's mean and variance.  -> DataArray on the covariates' coordinate.  See
+        ``discontinuum_amd.exceedance.exceedance_probability``."""
+        from ..exceedance import exceedance_probability
+
+        return exceedance_probability(self, covariates, threshold, above=above, pred_noise=pred_noise)
+
+    @is_fitted
     def cross_validate(self, folds="loo", ci=0.95, return_folds=False):
         """Exact leave-one-out / leave-group-out cross-validation of the training observations at the fitted
         hyperparameters, from the factorisation the engine holds (no refit; ``dgp_cross_validate``).  ``folds``: "loo", a

@@ -85,6 +85,26 @@ class LoadestGPMarginalHIP(LoadestDataMixin, MarginalHIP):
                            max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes)
 
     @is_fitted
+    def exceedance(self, covariates, threshold=None, threshold_series=None, kind="concentration", freq="YE", above=True,
+                   fraction=False, ci=0.95, pred_noise=False, return_cov=False, max_bytes=None):
+        """Days per period above a criterion, with exact uncertainty (``MarginalHIP.exceedance``).  ``kind="concentration"``:
+        the threshold is a concentration; ``kind="flux"``: ``threshold`` is a daily load in kg per day (a number or a list),
+        turned into the per-day concentration threshold limit / w_i with the flux weights of ``annual_flux`` (regular time
+        grid; a day with a non-positive or missing flow is excluded)."""
+        if kind not in ("concentration", "flux"):
+            raise ValueError(f"kind must be 'concentration' or 'flux', not {kind!r}")
+        if kind == "concentration":
+            return super().exceedance(covariates, threshold=threshold, threshold_series=threshold_series, freq=freq, above=above,
+                                      fraction=fraction, ci=ci, pred_noise=pred_noise, return_cov=return_cov, max_bytes=max_bytes)
+        if threshold is None or threshold_series is not None:
+            raise ValueError("kind='flux' takes threshold = the daily load limit in kg per day")
+        from ..exceedance import flux_exceedance
+        from ..loads import DEFAULT_MAX_BYTES
+
+        return flux_exceedance(self, covariates, threshold, freq=freq, above=above, fraction=fraction, ci=ci, pred_noise=pred_noise,
+                               return_cov=return_cov, max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes)
+
+    @is_fitted
     def flux_bias(self, cv=None, folds="loo"):
         """WRTDS's flux bias statistic on the sampled days, (sum P - sum O) / sum P with O the observed and P the
         cross-validated mean concentration x flow; ``cv``: a Dataset from ``cross_validate`` (default: run it with

@@ -271,6 +271,38 @@ int dgp_posterior_period_moments(dgp_plan* plan, const double* theta_host, const
                                  void* work_dev, size_t work_bytes, double* mean_out_dev, double* cov_out_dev,
                                  void* stream);
 
+/* Exact mean and covariance of THRESHOLD-EXCEEDANCE COUNTS of a posterior -- days per year above a criterion, the fraction
+ * of a record above a level (duration curves) -- which the reference can only estimate by Monte Carlo: sample()
+ * (engines/gpytorch.py:551-593), compare every draw with the threshold, count per period.  With f ~ N(mu, C) per site, per
+ * level l a threshold u_il in MODEL space, sigma_i^2 = C_ii (+ extra_var_i), z_il = (mu_i - u_il) / sigma_i,
+ * rho_ij = C_ij / (sigma_i sigma_j) and N_g = sum_{i in g} w_i 1[f_i > u_il]:
+ *   mean[l][g] = sum_{i in g} w_i Phi(z_il)
+ *   cov[l][g][h] = sum_{i in g, j in h} w_i w_j (Phi2(z_il, z_jl; rho_ij) - Phi(z_il) Phi(z_jl)),  Phi (1 - Phi) for i = j
+ * Phi2 the standard bivariate normal distribution function (Genz 2004: a Gauss-Legendre rule in asin(rho) below
+ * |rho| = 0.925, the expansion about |rho| = 1 above; absolute error of the order of 1e-15 per pair).  Levels do not interact: the
+ * covariance between counts at different levels is not computed.
+ * cov_dev, mu_dev, w_dev, group_dev, extra_var_dev, batch and the padding: as for dgp_period_moments (only the lower triangle
+ *            of cov_dev is read; group -1 = excluded; extra_var_dev enters sigma only, never rho's numerator);
+ * thresh_dev batch x nlevels x m doubles, 1 <= nlevels <= 64; +-inf allowed (never / always exceeded);
+ * mean_out_dev  batch x nlevels x ngroups doubles;  cov_out_dev  batch x nlevels x ngroups x ngroups doubles (exactly
+ *            symmetric).  All arithmetic after the loads of C and mu is double, for float32 covariances too.
+ * A point with sigma_i^2 <= 0 or an infinite threshold is decided (Phi = 0 or 1, a tie mu = u counting as not exceeded, no
+ * covariance with any point); NaN inputs come out as NaN.
+ * work_dev: dgp_exceedance_moments_workspace_bytes(m, ngroups, nlevels, batch) bytes -- per site M ngroups min(nlevels, 8)
+ * + 2 M (nlevels + 1) doubles, nothing of order M^2; 0 for bad sizes.
+ * Two launches, then two per chunk of 8 / 4 / 2 / 1 levels (gridDim.z = batch); every unordered pair is evaluated once, about
+ * m^2 / 2 bivariate probabilities per level on the fp64 vector pipe; no floating-point atomics: bitwise repeatable, and a
+ * site's result does not depend on the batch it is in.  Needs no plan. */
+size_t dgp_exceedance_moments_workspace_bytes(int64_t m, int ngroups, int nlevels, int batch);
+int dgp_exceedance_moments(int dtype, const void* cov_dev, int64_t m, int batch, const void* mu_dev,
+                           const double* thresh_dev, int nlevels, const double* w_dev, const int32_t* group_dev,
+                           int ngroups, const void* extra_var_dev, void* work_dev, size_t work_bytes,
+                           double* mean_out_dev, double* cov_out_dev, void* stream);
+/* out[i] = Phi2(h_i, k_i; rho_i) - Phi(h_i) Phi(k_i), the pair function of dgp_exceedance_moments pointwise (rho clamped to
+ * [-1, 1]; |h| or |k| above 38 gives 0): for tests.  All arrays `count` doubles on the device. */
+int dgp_debug_bvn_excess(const double* h_dev, const double* k_dev, const double* rho_dev, int64_t count, double* out_dev,
+                         void* stream);
+
 /* Exact leave-one-out / leave-group-out cross-validation at FIXED hyperparameters from the factorisation the plan holds (after
  * dgp_factorize or dgp_fit_step; DGP_E_STATE without one) -- no fold is refitted.  The reference has no counterpart: with
  * gpytorch every fold is a new factorisation behind the `predict` call site (src/discontinuum/engines/gpytorch.py:599-626).
