@@ -41,7 +41,7 @@ def _stream():
 
 
 def _ptr(t):
-    return C.c_void_p(t.data_ptr())
+    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 class GPPlan:
@@ -76,12 +76,10 @@ class GPPlan:
         with torch.cuda.device(self.device):
             self._ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
             off = (-self._ws.data_ptr()) % 256
-            self._ws_off = off
             _lib.check(
                 self.lib.dgp_plan_set_workspace(self._h, C.c_void_p(self._ws.data_ptr() + off), nbytes),
                 "dgp_plan_set_workspace",
             )
-            self._pred_ws = None
         self.set_lookahead(lookahead)
 
     def __del__(self):
@@ -113,6 +111,37 @@ class GPPlan:
         length = (self.n if length is None else length) * self.batch
         if not (torch.is_tensor(t) and t.is_cuda and t.dtype == self.dtype and t.is_contiguous() and t.numel() == length):
             raise ValueError(f"{name} must be a contiguous {self.dtype} CUDA tensor with {length} elements")
+
+    def _check_xs(self, Xs):
+        """The test points of an inference call: (m, d) -- (batch, m, d) for a batched plan -- in the plan's dtype, on the
+        device.  -> (lead, m), ``lead`` = the batch dimensions every result of the call starts with."""
+        lead = () if self.batch == 1 else (self.batch,)
+        if not (torch.is_tensor(Xs) and Xs.is_cuda and Xs.dtype == self.dtype and Xs.dim() == 2 + len(lead)
+                and Xs.shape[-1] == self.d and tuple(Xs.shape[:-2]) == lead):
+            raise ValueError(f"Xs must be a {lead + ('m', self.d)} {self.dtype} CUDA tensor")
+        return lead, int(Xs.shape[-2])
+
+    def _work_area(self, attr, need, what, check_free=False):
+        """256-byte aligned base of the entry point's cached work area ``self.<attr>``, grown to ``need`` bytes: an area
+        that is too small is released BEFORE its replacement is allocated, and one that does not fit the device raises a
+        ``RuntimeError`` that names ``what`` and the bytes.  ``check_free``: raise before trying when the free device memory
+        (torch's cache included) cannot hold it."""
+        ws = getattr(self, attr, None)
+        if ws is None or ws.numel() < need + 256:
+            setattr(self, attr, None)
+            del ws  # (its bytes return to torch's cache, which counts as free here)
+            if check_free:
+                dev = self.device
+                free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+                if need + 256 > free:
+                    raise RuntimeError(f"{what} needs a work area of {need} bytes; {free} bytes of device memory are free")
+            try:
+                ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+            except torch.OutOfMemoryError as e:
+                raise RuntimeError(f"{what} work area of {need} bytes does not fit the device") from e
+            setattr(self, attr, ws)
+        base = ws.data_ptr()
+        return C.c_void_p(base + (-base) % 256)
 
     def buffer(self, which: int, site: int = 0) -> torch.Tensor:
         """Tensor view of a plan buffer (tests / profiling); ``site``: which site's copy of a batched plan."""
@@ -149,7 +178,7 @@ class GPPlan:
                     and w.is_contiguous()):
                 raise ValueError(f"dr weights must be a contiguous {shape} {self.dtype} CUDA tensor")
         self._dr_w = w
-        _lib.check(self.lib.dgp_plan_set_dr_weights(self._h, _ptr(w) if w is not None else None), "dgp_plan_set_dr_weights")
+        _lib.check(self.lib.dgp_plan_set_dr_weights(self._h, _ptr(w)), "dgp_plan_set_dr_weights")
 
     def set_inputs(self, X: torch.Tensor):
         self._check_vec(X, "X", self.n * self.d)
@@ -192,12 +221,8 @@ class GPPlan:
         batched prediction then needs no more work memory than a single site's (n = 8192 fp64: 2.1 GB)."""
         if chunk is None:
             chunk = max(128, (16384 // self.batch) // 128 * 128)
-        lead = () if self.batch == 1 else (self.batch,)
-        if not (torch.is_tensor(Xs) and Xs.is_cuda and Xs.dtype == self.dtype and Xs.dim() == 2 + len(lead)
-                and Xs.shape[-1] == self.d and tuple(Xs.shape[:-2]) == lead):
-            raise ValueError(f"Xs must be a {lead + ('m', self.d)} {self.dtype} CUDA tensor")
+        lead, m = self._check_xs(Xs)
         th = _theta_array(theta, self.ntheta * self.batch)
-        m = Xs.shape[-2]
         mean = torch.empty(lead + (m,), dtype=self.dtype, device=self.device)
         var = torch.empty(lead + (m,), dtype=self.dtype, device=self.device)
         with torch.cuda.device(self.device):
@@ -206,23 +231,47 @@ class GPPlan:
                 whole = lo == 0 and hi == m
                 xs = Xs[..., lo:hi, :].contiguous()
                 need = int(self.lib.dgp_predict_workspace_bytes(self._h, hi - lo))
-                if self._pred_ws is None or self._pred_ws.numel() < need + 256:
-                    self._pred_ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-                base = self._pred_ws.data_ptr()
-                base += (-base) % 256
+                work = self._work_area("_pred_ws", need, "prediction")
                 # a chunk of a batched prediction is not contiguous inside (batch, m): stage it
                 mo = mean if (whole or not lead) else torch.empty(lead + (hi - lo,), dtype=self.dtype, device=self.device)
                 vo = var if (whole or not lead) else torch.empty_like(mo)
                 mp = mo if (whole or lead) else mean[lo:hi]
                 vp = vo if (whole or lead) else var[lo:hi]
-                _lib.check(
-                    self.lib.dgp_predict(self._h, th, _ptr(xs), hi - lo, C.c_void_p(base), need, _ptr(mp), _ptr(vp), _stream()),
-                    "dgp_predict",
-                )
+                _lib.check(self.lib.dgp_predict(self._h, th, _ptr(xs), hi - lo, work, need, _ptr(mp), _ptr(vp), _stream()),
+                           "dgp_predict")
                 if lead and not whole:
                     mean[:, lo:hi] = mo
                     var[:, lo:hi] = vo
         return mean, var
+
+    def _predict_planes(self, call, ws_attr, ws_bytes, theta, Xs, planes, packed, chunk, return_cov):
+        """The chunk loop of the per-point posterior products that return ``planes`` mean rows and ``packed`` rows of a packed
+        covariance per point: -> (mean (..., planes, m), cov (..., packed, m) or None).  ``ws_bytes(m)``: bytes of the work
+        area for m points, kept in ``self.<ws_attr>``; ``call(th, xs, m, work, need, mean_ptr, cov_ptr)``: the checked
+        library call for one chunk.  ``chunk`` None: 16384 // (batch planes) rounded down to a multiple of 128 (at least
+        128) -- the work area is batch x 2 planes N x chunk elements."""
+        if chunk is None:
+            chunk = max(128, (16384 // (self.batch * planes)) // 128 * 128)
+        lead, m = self._check_xs(Xs)
+        th = _theta_array(theta, self.ntheta * self.batch)
+        mean = torch.empty(lead + (planes, m), dtype=self.dtype, device=self.device)
+        cov = torch.empty(lead + (packed, m), dtype=self.dtype, device=self.device) if return_cov else None
+        with torch.cuda.device(self.device):
+            for lo in range(0, m, chunk):
+                hi = min(lo + chunk, m)
+                whole = lo == 0 and hi == m
+                xs = Xs[..., lo:hi, :].contiguous()
+                need = int(ws_bytes(hi - lo))
+                work = self._work_area(ws_attr, need, "prediction")
+                # a chunk is a column range of the (..., planes, m) results: stage it
+                mo = mean if whole else torch.empty(lead + (planes, hi - lo), dtype=self.dtype, device=self.device)
+                co = cov if (whole or cov is None) else torch.empty(lead + (packed, hi - lo), dtype=self.dtype, device=self.device)
+                call(th, xs, hi - lo, work, need, _ptr(mo), _ptr(co))
+                if not whole:
+                    mean[..., lo:hi] = mo
+                    if cov is not None:
+                        cov[..., lo:hi] = co
+        return mean, cov
 
     def predict_terms(self, theta, Xs: torch.Tensor, chunk: int | None = None, return_cov: bool = True):
         """Latent posterior of every ADDITIVE PART of the covariance at Xs (m, d) from the held factorisation
@@ -234,42 +283,13 @@ class GPPlan:
         ``chunk`` = points per launch sequence; the work area is batch x 2 C N x chunk elements, so the default is
         16384 // (batch C) rounded down to a multiple of 128 (at least 128)."""
         Cn = self.nterms
-        Pn = Cn * (Cn + 1) // 2
-        if chunk is None:
-            chunk = max(128, (16384 // (self.batch * Cn)) // 128 * 128)
-        lead = () if self.batch == 1 else (self.batch,)
-        if not (torch.is_tensor(Xs) and Xs.is_cuda and Xs.dtype == self.dtype and Xs.dim() == 2 + len(lead)
-                and Xs.shape[-1] == self.d and tuple(Xs.shape[:-2]) == lead):
-            raise ValueError(f"Xs must be a {lead + ('m', self.d)} {self.dtype} CUDA tensor")
-        th = _theta_array(theta, self.ntheta * self.batch)
-        m = Xs.shape[-2]
-        mean = torch.empty(lead + (Cn, m), dtype=self.dtype, device=self.device)
-        cov = torch.empty(lead + (Pn, m), dtype=self.dtype, device=self.device) if return_cov else None
-        with torch.cuda.device(self.device):
-            for lo in range(0, m, chunk):
-                hi = min(lo + chunk, m)
-                whole = lo == 0 and hi == m
-                xs = Xs[..., lo:hi, :].contiguous()
-                need = int(self.lib.dgp_predict_terms_workspace_bytes(self._h, hi - lo))
-                ws = getattr(self, "_terms_ws", None)
-                if ws is None or ws.numel() < need + 256:
-                    self._terms_ws = None
-                    self._terms_ws = ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-                base = ws.data_ptr()
-                base += (-base) % 256
-                # a chunk is a column range of the (..., C, m) results: stage it
-                mo = mean if whole else torch.empty(lead + (Cn, hi - lo), dtype=self.dtype, device=self.device)
-                co = cov if (whole or cov is None) else torch.empty(lead + (Pn, hi - lo), dtype=self.dtype, device=self.device)
-                _lib.check(
-                    self.lib.dgp_predict_terms(self._h, th, _ptr(xs), hi - lo, C.c_void_p(base), need, _ptr(mo),
-                                               _ptr(co) if co is not None else None, _stream()),
-                    "dgp_predict_terms",
-                )
-                if not whole:
-                    mean[..., lo:hi] = mo
-                    if cov is not None:
-                        cov[..., lo:hi] = co
-        return mean, cov
+
+        def call(th, xs, m, work, need, mean_ptr, cov_ptr):
+            _lib.check(self.lib.dgp_predict_terms(self._h, th, _ptr(xs), m, work, need, mean_ptr, cov_ptr, _stream()),
+                       "dgp_predict_terms")
+
+        return self._predict_planes(call, "_terms_ws", lambda m: self.lib.dgp_predict_terms_workspace_bytes(self._h, m),
+                                    theta, Xs, Cn, Cn * (Cn + 1) // 2, chunk, return_cov)
 
     def predict_slopes(self, theta, Xs: torch.Tensor, cols, chunk: int | None = None, return_cov: bool = True):
         """Latent posterior of the fit and of its DERIVATIVES with respect to the raw input columns ``cols`` (distinct, in
@@ -287,44 +307,14 @@ class GPPlan:
         for c in cols:
             if int(self.lib.dgp_model_input_differentiable(mid, self.d, c)) != 1:
                 raise ValueError(f"the covariance is not differentiable in column {c} (Matern-1/2 factor)")
-        Pn = 1 + len(cols)
-        Qn = Pn * (Pn + 1) // 2
-        if chunk is None:
-            chunk = max(128, (16384 // (self.batch * Pn)) // 128 * 128)
-        lead = () if self.batch == 1 else (self.batch,)
-        if not (torch.is_tensor(Xs) and Xs.is_cuda and Xs.dtype == self.dtype and Xs.dim() == 2 + len(lead)
-                and Xs.shape[-1] == self.d and tuple(Xs.shape[:-2]) == lead):
-            raise ValueError(f"Xs must be a {lead + ('m', self.d)} {self.dtype} CUDA tensor")
-        th = _theta_array(theta, self.ntheta * self.batch)
-        carr = (C.c_int * len(cols))(*cols)
-        m = Xs.shape[-2]
-        mean = torch.empty(lead + (Pn, m), dtype=self.dtype, device=self.device)
-        cov = torch.empty(lead + (Qn, m), dtype=self.dtype, device=self.device) if return_cov else None
-        with torch.cuda.device(self.device):
-            for lo in range(0, m, chunk):
-                hi = min(lo + chunk, m)
-                whole = lo == 0 and hi == m
-                xs = Xs[..., lo:hi, :].contiguous()
-                need = int(self.lib.dgp_predict_slopes_workspace_bytes(self._h, hi - lo, len(cols)))
-                ws = getattr(self, "_slopes_ws", None)
-                if ws is None or ws.numel() < need + 256:
-                    self._slopes_ws = None
-                    self._slopes_ws = ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-                base = ws.data_ptr()
-                base += (-base) % 256
-                # a chunk is a column range of the (..., P, m) results: stage it
-                mo = mean if whole else torch.empty(lead + (Pn, hi - lo), dtype=self.dtype, device=self.device)
-                co = cov if (whole or cov is None) else torch.empty(lead + (Qn, hi - lo), dtype=self.dtype, device=self.device)
-                _lib.check(
-                    self.lib.dgp_predict_slopes(self._h, th, _ptr(xs), hi - lo, carr, len(cols), C.c_void_p(base), need,
-                                                _ptr(mo), _ptr(co) if co is not None else None, _stream()),
-                    "dgp_predict_slopes",
-                )
-                if not whole:
-                    mean[..., lo:hi] = mo
-                    if cov is not None:
-                        cov[..., lo:hi] = co
-        return mean, cov
+        Pn, carr = 1 + len(cols), (C.c_int * len(cols))(*cols)
+
+        def call(th, xs, m, work, need, mean_ptr, cov_ptr):
+            _lib.check(self.lib.dgp_predict_slopes(self._h, th, _ptr(xs), m, carr, len(cols), work, need, mean_ptr, cov_ptr,
+                                                   _stream()), "dgp_predict_slopes")
+
+        return self._predict_planes(call, "_slopes_ws", lambda m: self.lib.dgp_predict_slopes_workspace_bytes(self._h, m, len(cols)),
+                                    theta, Xs, Pn, Pn * (Pn + 1) // 2, chunk, return_cov)
 
     # ------------------------------------------------------------------ cross-validation
     def cross_validate(self, groups, max_group=None):
@@ -346,15 +336,7 @@ class GPPlan:
         if need == 0:
             raise ValueError(f"bad size: ngroups = {ngroups}, max_group = {max_group} (both in 1..n)")
         with torch.cuda.device(self.device):
-            ws = getattr(self, "_cv_ws", None)
-            if ws is None or ws.numel() < need + 256:
-                self._cv_ws = None
-                try:
-                    self._cv_ws = ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-                except torch.OutOfMemoryError as e:
-                    raise RuntimeError(f"cross-validation work area of {need} bytes does not fit the device") from e
-            base = ws.data_ptr()
-            base += (-base) % 256
+            work = self._work_area("_cv_ws", need, "cross-validation")
             order = order.to(self.device).contiguous()
             start = start.to(self.device).contiguous()
             resid = torch.empty(lead + (self.n,), dtype=torch.float64, device=self.device)
@@ -362,7 +344,7 @@ class GPPlan:
             lpd = torch.empty(lead + (ngroups,), dtype=torch.float64, device=self.device)
             info = torch.empty(lead + (ngroups,), dtype=torch.int32, device=self.device)
             _lib.check(
-                self.lib.dgp_cross_validate(self._h, _ptr(order), _ptr(start), ngroups, max_group, C.c_void_p(base), need,
+                self.lib.dgp_cross_validate(self._h, _ptr(order), _ptr(start), ngroups, max_group, work, need,
                                             _ptr(resid), _ptr(var), _ptr(lpd), _ptr(info), _stream()),
                 "dgp_cross_validate",
             )
@@ -379,24 +361,17 @@ class GPPlan:
         """(K*^T alpha, latent posterior covariance K** - V^T V) at Xs (m, d): the covariance as an (M, M) tensor,
         M = padded m, lower triangle valid (diagonal 128-blocks complete), identity pad -- ``dgp_posterior_cov``.
         Batched plans: Xs (batch, m, d), theta (batch, ntheta) -> mean (batch, m), cov (batch, M, M), one launch sequence."""
-        lead = () if self.batch == 1 else (self.batch,)
-        if not (torch.is_tensor(Xs) and Xs.is_cuda and Xs.dtype == self.dtype and Xs.dim() == 2 + len(lead)
-                and Xs.shape[-1] == self.d and tuple(Xs.shape[:-2]) == lead):
-            raise ValueError(f"Xs must be a {lead + ('m', self.d)} {self.dtype} CUDA tensor")
+        lead, m = self._check_xs(Xs)
         th = _theta_array(theta, self.ntheta * self.batch)
-        m = Xs.shape[-2]
         M = int(self.lib.dgp_padded_n(m))
         with torch.cuda.device(self.device):
             xs = Xs.contiguous()
             need = int(self.lib.dgp_predict_workspace_bytes(self._h, m))
-            if self._pred_ws is None or self._pred_ws.numel() < need + 256:
-                self._pred_ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-            base = self._pred_ws.data_ptr()
-            base += (-base) % 256
+            work = self._work_area("_pred_ws", need, "prediction")
             mean = torch.empty(lead + (m,), dtype=self.dtype, device=self.device)
             cov = torch.empty(lead + (M, M), dtype=self.dtype, device=self.device)
             _lib.check(
-                self.lib.dgp_posterior_cov(self._h, th, _ptr(xs), m, C.c_void_p(base), need, _ptr(mean), _ptr(cov), _stream()),
+                self.lib.dgp_posterior_cov(self._h, th, _ptr(xs), m, work, need, _ptr(mean), _ptr(cov), _stream()),
                 "dgp_posterior_cov",
             )
         return mean, cov
@@ -444,7 +419,7 @@ class GPPlan:
         with torch.cuda.device(self.device):
             z = torch.randn(M, Q, dtype=self.dtype, device=self.device, generator=generator)
             out = torch.empty(ndraw, m, dtype=self.dtype, device=self.device)
-            mp = _ptr(mean.contiguous()) if mean is not None else None
+            mp = _ptr(mean.contiguous() if mean is not None else None)
             _lib.check(self.lib.dgp_sample_draws(_DTYPES[self.dtype], _ptr(Lbuf), m, _ptr(z), ndraw, mp, _ptr(out), _stream()),
                        "dgp_sample_draws")
         self._last_z = z
@@ -469,68 +444,34 @@ class GPPlan:
         the (M, M) covariance is never formed.  Xs (m, d) -- (batch, m, d) for a batched plan, theta (batch, ntheta) --; the
         other arguments as for ``period_moments``.  The work area (2 N M plan-dtype elements + M P doubles per site) is kept
         between calls; a ``RuntimeError`` names its bytes when it exceeds the free device memory."""
-        lead = () if self.batch == 1 else (self.batch,)
-        if not (torch.is_tensor(Xs) and Xs.is_cuda and Xs.dtype == self.dtype and Xs.dim() == 2 + len(lead)
-                and Xs.shape[-1] == self.d and tuple(Xs.shape[:-2]) == lead):
-            raise ValueError(f"Xs must be a {lead + ('m', self.d)} {self.dtype} CUDA tensor")
+        lead, m = self._check_xs(Xs)
         th = _theta_array(theta, self.ntheta * self.batch)
-        m, P = int(Xs.shape[-2]), int(ngroups)
+        P = int(ngroups)
         need = int(self.lib.dgp_posterior_period_moments_workspace_bytes(self._h, m, P))
         if need == 0:
             raise ValueError(f"bad size: m = {m}, ngroups = {P} (1 <= m <= 2^20, 1 <= ngroups <= 65535)")
         dev = self.device
-
-        def vec(t, name, dtype):
-            if t is None:
-                return None
-            t = torch.as_tensor(t).to(dev, dtype).contiguous()
-            if tuple(t.shape) != lead + (m,):
-                raise ValueError(f"{name} must have shape {lead + (m,)}")
-            return t
-
         with torch.cuda.device(dev):
-            mu_t, w_t = vec(mu, "mu", self.dtype), vec(w, "w", torch.float64)
-            g_t, ev_t = vec(groups, "groups", torch.int32), vec(extra_var, "extra_var", self.dtype)
-            s2 = torch.as_tensor(scale2, dtype=torch.float64).reshape(-1).to(dev).contiguous()
-            if s2.numel() != self.batch:
-                raise ValueError(f"scale2 must hold {self.batch} value(s)")
-            ws = getattr(self, "_ppm_ws", None)
-            if ws is None or ws.numel() < need + 256:
-                self._ppm_ws = None
-                del ws  # (its bytes return to torch's cache, which counts as free here)
-                free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
-                if need + 256 > free:
-                    raise RuntimeError(f"dgp_posterior_period_moments needs a work area of {need} bytes; "
-                                       f"{free} bytes of device memory are free")
-                ws = self._ppm_ws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
-            base = ws.data_ptr()
-            base += (-base) % 256
+            mu_t, w_t, g_t, ev_t, s2 = _moment_inputs(dev, self.dtype, lead, m, mu, w, groups, extra_var, scale2)
+            work = self._work_area("_ppm_ws", need, "dgp_posterior_period_moments", check_free=True)
             xs = Xs.contiguous()
             mean_out = torch.empty(lead + (P,), dtype=torch.float64, device=dev)
             cov_out = torch.empty(lead + (P, P), dtype=torch.float64, device=dev)
             _lib.check(
                 self.lib.dgp_posterior_period_moments(self._h, th, _ptr(xs), m, int(mode), _ptr(mu_t), _ptr(s2), _ptr(w_t), _ptr(g_t), P,
-                                                      _ptr(ev_t) if ev_t is not None else None, C.c_void_p(base), need,
-                                                      _ptr(mean_out), _ptr(cov_out), _stream()),
+                                                      _ptr(ev_t), work, need, _ptr(mean_out), _ptr(cov_out), _stream()),
                 "dgp_posterior_period_moments",
             )
         return mean_out, cov_out
 
     def _vjp_workspace(self, m):
         need = int(self.lib.dgp_mean_vjp_workspace_bytes(self._h, m))
-        ws = getattr(self, "_vjp_ws", None)
-        if ws is None or ws.numel() < need + 256:
-            self._vjp_ws = ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-        base = ws.data_ptr()
-        return C.c_void_p(base + (-base) % 256), need
+        return self._work_area("_vjp_ws", need, "mean / vjp"), need
 
     def predict_mean(self, theta, Xs: torch.Tensor):
         """K(X*, X) alpha from the held factorisation (no variance work).  Batched plans: Xs (batch, m, d) -> (batch, m)."""
         th = _theta_array(theta, self.ntheta * self.batch)
-        lead = () if self.batch == 1 else (self.batch,)
-        if Xs.dim() != 2 + len(lead) or tuple(Xs.shape[:-2]) != lead or Xs.shape[-1] != self.d:
-            raise ValueError(f"Xs must have shape {lead + ('m', self.d)}")
-        m = Xs.shape[-2]
+        lead, m = self._check_xs(Xs)
         with torch.cuda.device(self.device):
             xs = Xs.contiguous()
             work, need = self._vjp_workspace(m)
@@ -542,10 +483,7 @@ class GPPlan:
         """Vector-Jacobian product of ``predict_mean``: (dtheta[P], dr[n], dnoise[n]) for upstream w[m].  Batched plans:
         Xs (batch, m, d), w (batch, m) -> dtheta (batch, P), dr (batch, n), dnoise (batch, n), one launch sequence for all sites."""
         th = _theta_array(theta, self.ntheta * self.batch)
-        lead = () if self.batch == 1 else (self.batch,)
-        if Xs.dim() != 2 + len(lead) or tuple(Xs.shape[:-2]) != lead or Xs.shape[-1] != self.d:
-            raise ValueError(f"Xs must have shape {lead + ('m', self.d)}")
-        m = Xs.shape[-2]
+        lead, m = self._check_xs(Xs)
         self._check_vec(w, "w", m)
         with torch.cuda.device(self.device):
             xs = Xs.contiguous()
@@ -567,9 +505,9 @@ class GPPlan:
 
     def _info_offset(self):
         # the int info slot sits right after the 16-element scalar block that follows the partials;
-        # recover it from the ALPHA buffer pointer is fragile, so the library exposes it as buffer 6
+        # recover it from the ALPHA buffer pointer is fragile, so the library exposes it as buffer BUF_INFO
         p, ld = C.c_void_p(), C.c_int64()
-        _lib.check(self.lib.dgp_plan_buffer(self._h, 6, C.byref(p), C.byref(ld)), "dgp_plan_buffer")
+        _lib.check(self.lib.dgp_plan_buffer(self._h, _lib.BUF_INFO, C.byref(p), C.byref(ld)), "dgp_plan_buffer")
         return p.value - self._ws.data_ptr()
 
     def set_timing(self, enabled: bool):
@@ -627,6 +565,29 @@ class GPPlan:
 MODE_LINEAR, MODE_LOG = 0, 1
 
 
+def _moment_inputs(dev, dtype, lead, m, mu, w, groups, extra_var, scale2=None):
+    """The per-point inputs of the moment passes as contiguous device tensors of shape ``lead + (m,)``: -> (mu in ``dtype``, w
+    in float64, groups in int32, extra_var in ``dtype`` or None, scale2 as one float64 per site, or None when not given)."""
+
+    def vec(t, name, dt):
+        if t is None:
+            return None
+        t = torch.as_tensor(t).to(dev, dt).contiguous()
+        if tuple(t.shape) != lead + (m,):
+            raise ValueError(f"{name} must have shape {lead + (m,)}")
+        return t
+
+    mu_t, w_t = vec(mu, "mu", dtype), vec(w, "w", torch.float64)
+    g_t, ev_t = vec(groups, "groups", torch.int32), vec(extra_var, "extra_var", dtype)
+    s2 = None
+    if scale2 is not None:
+        B = lead[0] if lead else 1
+        s2 = torch.as_tensor(scale2, dtype=torch.float64).reshape(-1).to(dev).contiguous()
+        if s2.numel() != B:
+            raise ValueError(f"scale2 must hold {B} value(s)")
+    return mu_t, w_t, g_t, ev_t, s2
+
+
 def period_moments(cov: torch.Tensor, m: int, mu: torch.Tensor, scale2, w: torch.Tensor, groups: torch.Tensor, ngroups: int,
                    mode: int, extra_var: torch.Tensor | None = None):
     """Exact mean and covariance of the period sums L_g = sum_{i in g} w_i c_i of a transformed latent posterior
@@ -646,20 +607,7 @@ def period_moments(cov: torch.Tensor, m: int, mu: torch.Tensor, scale2, w: torch
     if cov.dtype not in _DTYPES or not cov.is_cuda or not cov.is_contiguous() or tuple(cov.shape) != lead + (M, M):
         raise ValueError(f"cov must be a contiguous {lead + (M, M)} float64 / float32 CUDA tensor")
     dev = cov.device
-
-    def vec(t, name, dtype):
-        if t is None:
-            return None
-        t = torch.as_tensor(t).to(dev, dtype).contiguous()
-        if tuple(t.shape) != lead + (int(m),):
-            raise ValueError(f"{name} must have shape {lead + (int(m),)}")
-        return t
-
-    mu_t, w_t = vec(mu, "mu", cov.dtype), vec(w, "w", torch.float64)
-    g_t, ev_t = vec(groups, "groups", torch.int32), vec(extra_var, "extra_var", cov.dtype)
-    s2 = torch.as_tensor(scale2, dtype=torch.float64).reshape(-1).to(dev).contiguous()
-    if s2.numel() != B:
-        raise ValueError(f"scale2 must hold {B} value(s)")
+    mu_t, w_t, g_t, ev_t, s2 = _moment_inputs(dev, cov.dtype, lead, int(m), mu, w, groups, extra_var, scale2)
     P = int(ngroups)
     need = int(lib.dgp_period_moments_workspace_bytes(int(m), P, B))
     work = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
@@ -667,7 +615,7 @@ def period_moments(cov: torch.Tensor, m: int, mu: torch.Tensor, scale2, w: torch
     cov_out = torch.empty(lead + (P, P), dtype=torch.float64, device=dev)
     _lib.check(
         lib.dgp_period_moments(_DTYPES[cov.dtype], int(mode), _ptr(cov), int(m), B, _ptr(mu_t), _ptr(s2), _ptr(w_t), _ptr(g_t), P,
-                               _ptr(ev_t) if ev_t is not None else None, _ptr(work), need, _ptr(mean_out), _ptr(cov_out),
+                               _ptr(ev_t), _ptr(work), need, _ptr(mean_out), _ptr(cov_out),
                                _stream()),
         "dgp_period_moments",
     )
@@ -694,17 +642,7 @@ def exceedance_moments(cov: torch.Tensor, m: int, mu: torch.Tensor, thresh: torc
     if cov.dtype not in _DTYPES or not cov.is_cuda or not cov.is_contiguous() or tuple(cov.shape) != lead + (M, M):
         raise ValueError(f"cov must be a contiguous {lead + (M, M)} float64 / float32 CUDA tensor")
     dev = cov.device
-
-    def vec(t, name, dtype):
-        if t is None:
-            return None
-        t = torch.as_tensor(t).to(dev, dtype).contiguous()
-        if tuple(t.shape) != lead + (int(m),):
-            raise ValueError(f"{name} must have shape {lead + (int(m),)}")
-        return t
-
-    mu_t, w_t = vec(mu, "mu", cov.dtype), vec(w, "w", torch.float64)
-    g_t, ev_t = vec(groups, "groups", torch.int32), vec(extra_var, "extra_var", cov.dtype)
+    mu_t, w_t, g_t, ev_t, _ = _moment_inputs(dev, cov.dtype, lead, int(m), mu, w, groups, extra_var)
     u_t = torch.as_tensor(thresh).to(dev, torch.float64).contiguous()
     if u_t.dim() != len(lead) + 2 or tuple(u_t.shape[:-2]) != lead or u_t.shape[-1] != int(m):
         raise ValueError(f"thresh must have shape {lead + ('L', int(m))}")
@@ -718,7 +656,7 @@ def exceedance_moments(cov: torch.Tensor, m: int, mu: torch.Tensor, thresh: torc
     cov_out = torch.empty(lead + (L, P, P), dtype=torch.float64, device=dev)
     _lib.check(
         lib.dgp_exceedance_moments(_DTYPES[cov.dtype], _ptr(cov), int(m), B, _ptr(mu_t), _ptr(u_t), L, _ptr(w_t), _ptr(g_t), P,
-                                   _ptr(ev_t) if ev_t is not None else None, _ptr(work), need, _ptr(mean_out), _ptr(cov_out),
+                                   _ptr(ev_t), _ptr(work), need, _ptr(mean_out), _ptr(cov_out),
                                    _stream()),
         "dgp_exceedance_moments",
     )

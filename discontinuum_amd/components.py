@@ -90,14 +90,9 @@ def merge_matrix(names, groups):
 
 def model_space(model, Xnew):
     """(names, mean (C, m), cov (C, C, m), prior mean (m,)) of the parts at model-space points ``Xnew``, as float64 numpy."""
-    model._device_ready()
-    model.model.eval()
-    model.likelihood.eval()
     x = Xnew.to(model.device, model.dtype).contiguous()
+    model._eval_ready(x)
     with torch.no_grad():
-        if hasattr(model.model, "prepare_eval"):
-            model.model.prepare_eval(model._train_x, x)  # data-dependent clamps see [X; X*], as in predict
-        model._ensure_factor()
         mean, packed = model._plan.predict_terms(model._factor_theta, x)
         prior = model.model.prior_mean(x)
     mean = mean.detach().to("cpu", torch.float64).numpy()

@@ -655,17 +655,21 @@ static int run_gram(dgp_plan* p, const double* theta, const void* noise, hipStre
   if (staging) p->ring.commit(s);
   return rc;
 }
+// The factorisation, by the split chain or the group schedule.  nck > 0: after block column ck[c] is final the schedule
+// records ck_ev[c] and calls on_ck(ctx, c) from its enqueue loop (fit_step's early inverse).
 template <typename T>
-static int run_potrf(dgp_plan* p, hipStream_t s) {
+static int run_potrf(dgp_plan* p, hipStream_t s, int nck = 0, const int* ck = nullptr, hipEvent_t* ck_ev = nullptr,
+                     void (*on_ck)(void*, int) = nullptr, void* ctx = nullptr) {
   int rc = ensure_async(p, s);
   if (rc) return rc;
   if ((rc = ensure_timing(p)) || (rc = ensure_split(p, s))) return rc;
+  const int group = group_size(p->lookahead, p->B, p->N / DGP_TILE_HOST);
+  hipEvent_t* sev = p->timing ? p->sev : nullptr;
   if (split_applies(p) && p->sc)
-    return potrf_split<T>((T*)p->A, p->N, (T*)p->Tm, (T*)p->scal, p->info, (T*)p->snap, s, p->sc, p->s2, p->ev,
-                          p->timing ? p->sev : nullptr, &p->n_syrk, &p->syrk_flop, 0, nullptr, nullptr, nullptr, nullptr, split_start(p), group_size(p->lookahead, p->B, p->N / DGP_TILE_HOST), &p->tune);
-  return potrf<T>((T*)p->A, p->N, (T*)p->Tm, (T*)p->scal, p->info, group_size(p->lookahead, p->B, p->N / DGP_TILE_HOST), s, p->s2, p->ev,
-                  p->timing ? p->sev : nullptr, &p->n_syrk, &p->syrk_flop, 0, nullptr, nullptr, nullptr, nullptr,
-                  batch_of<T>(p));
+    return potrf_split<T>((T*)p->A, p->N, (T*)p->Tm, (T*)p->scal, p->info, (T*)p->snap, s, p->sc, p->s2, p->ev, sev, &p->n_syrk,
+                          &p->syrk_flop, nck, ck, ck_ev, on_ck, ctx, split_start(p), group, &p->tune);
+  return potrf<T>((T*)p->A, p->N, (T*)p->Tm, (T*)p->scal, p->info, group, s, p->s2, p->ev, sev, &p->n_syrk, &p->syrk_flop, nck, ck,
+                  ck_ev, on_ck, ctx, batch_of<T>(p));
 }
 template <typename T>
 static int run_trtri(dgp_plan* p, hipStream_t s) {
@@ -785,14 +789,7 @@ static int fit_step(dgp_plan* p, const double* theta, const void* r, const void*
                                       EARLY_RESERVED_CUS, batch_of<T>(e->p));
       if (rc && !e->rc) e->rc = rc;
     };
-    if ((rc = ensure_timing(p)) || (rc = ensure_split(p, s))) return rc;
-    if (split_applies(p) && p->sc)
-      rc = potrf_split<T>((T*)p->A, p->N, (T*)p->Tm, (T*)p->scal, p->info, (T*)p->snap, s, p->sc, p->s2, p->ev,
-                          p->timing ? p->sev : nullptr, &p->n_syrk, &p->syrk_flop, 3, ctx.ck, p->xev, on_ck, &ctx, split_start(p), group_size(p->lookahead, p->B, p->N / DGP_TILE_HOST), &p->tune);
-    else
-      rc = potrf<T>((T*)p->A, p->N, (T*)p->Tm, (T*)p->scal, p->info, group_size(p->lookahead, p->B, p->N / DGP_TILE_HOST), s, p->s2, p->ev,
-                    p->timing ? p->sev : nullptr, &p->n_syrk, &p->syrk_flop, 3, ctx.ck, p->xev, on_ck, &ctx, bt);
-    if (rc || (rc = ctx.rc)) return rc;
+    if ((rc = run_potrf<T>(p, s, 3, ctx.ck, p->xev, on_ck, &ctx)) || (rc = ctx.rc)) return rc;
     tick(p, TS_POTRF, 1, s);
     tick(p, TS_TRTRI, 0, s);
     hipEventRecord(p->xev[3], s);  // factorisation complete (s has joined the bulk stream)
@@ -1050,99 +1047,88 @@ static int post_period(dgp_plan* p, const double* theta, const void* Xs, int64_t
                                      group, P, (const T*)ev, pm, mean_out, cov_out, s, p->pre);
 }
 
-// ---- the posterior of the covariance's additive parts (dgp_terms.hip).  Work area per site: the test points' SoA copy, the C
-// cross Grams side by side (N x C M), V = T Ks of the same shape, the parts' prior variances (C M) and the slab partials.
-struct TermsLayout {
-  size_t Xst, Ks, V, kss, part, total;
+// ---- posterior products of `planes` side-by-side cross Grams per test point: the covariance's additive parts (dgp_terms.hip,
+// planes = C) and the value with its input derivatives (dgp_slopes.hip, planes = P = 1 + ncols).  Work area per site: the test
+// points' SoA copy, the cross Grams side by side (N x planes M), V = T Ks of the same shape, `prior_rows` rows of M prior
+// (co)variances -- the parts' C variances, or the derivatives' packed P (P + 1) / 2 block -- and the slab partials.
+struct PlanesLayout {
+  size_t Xst, Ks, V, prior, part, total;
 };
-static TermsLayout terms_layout(const dgp_plan* p, int64_t m) {
+static PlanesLayout planes_layout(const dgp_plan* p, int64_t m, int planes, int prior_rows) {
   const size_t M = (size_t)round_up(m, DGP_TILE_HOST), e = p->elem, N = (size_t)p->N;
-  const size_t C = (size_t)model_nterms(p->model, p->d);
-  TermsLayout L;
+  PlanesLayout L;
   size_t o = 0;
   L.Xst = o; o += align_up(e * M * p->d);
-  L.Ks = o; o += align_up(e * N * C * M);
-  L.V = o; o += align_up(e * N * C * M);
-  L.kss = o; o += align_up(e * C * M);
-  L.part = o; o += align_up(e * (size_t)terms_partials((int)C, (long)M));
+  L.Ks = o; o += align_up(e * N * (size_t)planes * M);
+  L.V = o; o += align_up(e * N * (size_t)planes * M);
+  L.prior = o; o += align_up(e * (size_t)prior_rows * M);
+  L.part = o; o += align_up(e * (size_t)terms_partials(planes, (long)M));
   L.total = o;
   return L;
+}
+
+// The driver: pack the test points, fill the cross planes, the prior rows, V = T Ks at width planes x M, reduce.  The three
+// launchers that differ between the products are callables:
+//   cross(Xst, M, Ks, bt, wbs, staging)      prior(Xst, M, prior, wb, wbs)      reduce(V, Ks, M, prior, part, bt, wbs)
+template <typename T, typename Cross, typename Prior, typename Reduce>
+static int predict_planes(dgp_plan* p, const void* Xs, int64_t m, const PlanesLayout& L, int planes, void* work, hipStream_t s,
+                          Cross cross, Prior prior, Reduce reduce) {
+  const long M = round_up(m, DGP_TILE_HOST);
+  const long wbs = p->B > 1 ? (long)(L.total / sizeof(T)) : 0;
+  const Batch bt = batch_of<T>(p);
+  char* w = (char*)work;
+  T* Xst = (T*)(w + L.Xst);
+  T* Ks = (T*)(w + L.Ks);
+  T* V = (T*)(w + L.V);
+  T* pr = (T*)(w + L.prior);
+  Batch wb;  // the test points: [B][m][d] -> SoA in the work area
+  wb.B = p->B;
+  wb.ws = wbs;
+  int rc = pack_x<T>((const T*)Xs, (int)m, p->d, M, Xst, s, wb);
+  if (rc) return rc;
+  {
+    PreSlot slot(p, s);
+    if ((rc = cross(Xst, M, Ks, bt, wbs, slot.staging))) return rc;
+  }
+  wb.ws = 0;
+  if ((rc = prior(Xst, M, pr, wb, wbs))) return rc;
+  if ((rc = predict_v<T>((const T*)p->Tm, p->N, Ks, (long)planes * M, V, s, bt, wbs))) return rc;
+  return reduce(V, Ks, M, pr, (T*)(w + L.part), bt, wbs);
 }
 
 template <typename T>
 static int predict_terms(dgp_plan* p, const double* theta, const void* Xs, int64_t m, void* work, void* mean, void* cov,
                          hipStream_t s) {
-  const TermsLayout L = terms_layout(p, m);
-  const long M = round_up(m, DGP_TILE_HOST);
   const int C = model_nterms(p->model, p->d);
-  const long wbs = p->B > 1 ? (long)(L.total / sizeof(T)) : 0;
-  const Batch bt = batch_of<T>(p);
-  char* w = (char*)work;
-  T* Xst = (T*)(w + L.Xst);
-  T* Ks = (T*)(w + L.Ks);
-  T* V = (T*)(w + L.V);
-  T* kss = (T*)(w + L.kss);
-  Batch wb;  // the test points: [B][m][d] -> SoA in the work area
-  wb.B = p->B;
-  wb.ws = wbs;
-  int rc = pack_x<T>((const T*)Xs, (int)m, p->d, M, Xst, s, wb);
-  if (rc) return rc;
-  {
-    PreSlot slot(p, s);
-    if ((rc = gram_cross_terms<T>(p->model, p->d, (const T*)p->Xt, p->N, (int)p->n, Xst, M, (int)m, theta, Ks, s, bt, wbs, p->pre,
-                                  slot.staging)))
-      return rc;
-  }
-  wb.ws = 0;
-  if ((rc = gram_diag_terms<T>(p->model, p->d, Xst, M, (int)m, theta, kss, s, wb, wbs, p->pre))) return rc;
-  if ((rc = predict_v<T>((const T*)p->Tm, p->N, Ks, (long)C * M, V, s, bt, wbs))) return rc;
-  return terms_reduce<T>(C, V, Ks, p->N, M, (int)m, (const T*)p->alpha, kss, (T*)(w + L.part), (T*)mean, (T*)cov, s, bt, wbs);
-}
-
-// ---- the posterior of the input derivatives (dgp_slopes.hip).  Work area per site as TermsLayout with P = 1 + ncols planes
-// and the packed P (P + 1) / 2 prior block in place of the parts' prior variances.
-static TermsLayout slopes_layout(const dgp_plan* p, int64_t m, int ncols) {
-  const size_t M = (size_t)round_up(m, DGP_TILE_HOST), e = p->elem, N = (size_t)p->N;
-  const size_t P = (size_t)(1 + ncols);
-  TermsLayout L;
-  size_t o = 0;
-  L.Xst = o; o += align_up(e * M * p->d);
-  L.Ks = o; o += align_up(e * N * P * M);
-  L.V = o; o += align_up(e * N * P * M);
-  L.kss = o; o += align_up(e * (P * (P + 1) / 2) * M);
-  L.part = o; o += align_up(e * (size_t)terms_partials((int)P, (long)M));
-  L.total = o;
-  return L;
+  return predict_planes<T>(
+      p, Xs, m, planes_layout(p, m, C, C), C, work, s,
+      [&](const T* Xst, long M, T* Ks, const Batch& bt, long wbs, void* staging) {
+        return gram_cross_terms<T>(p->model, p->d, (const T*)p->Xt, p->N, (int)p->n, Xst, M, (int)m, theta, Ks, s, bt, wbs, p->pre, staging);
+      },
+      [&](const T* Xst, long M, T* kss, const Batch& wb, long wbs) {
+        return gram_diag_terms<T>(p->model, p->d, Xst, M, (int)m, theta, kss, s, wb, wbs, p->pre);
+      },
+      [&](const T* V, const T* Ks, long M, const T* kss, T* part, const Batch& bt, long wbs) {
+        return terms_reduce<T>(C, V, Ks, p->N, M, (int)m, (const T*)p->alpha, kss, part, (T*)mean, (T*)cov, s, bt, wbs);
+      });
 }
 
 template <typename T>
 static int predict_slopes(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const int* cols, int ncols, void* work,
                           void* mean, void* cov, hipStream_t s) {
-  const TermsLayout L = slopes_layout(p, m, ncols);
-  const long M = round_up(m, DGP_TILE_HOST);
   const int P = 1 + ncols;
-  const long wbs = p->B > 1 ? (long)(L.total / sizeof(T)) : 0;
-  const Batch bt = batch_of<T>(p);
-  char* w = (char*)work;
-  T* Xst = (T*)(w + L.Xst);
-  T* Ks = (T*)(w + L.Ks);
-  T* V = (T*)(w + L.V);
-  T* prior = (T*)(w + L.kss);
-  Batch wb;  // the test points: [B][m][d] -> SoA in the work area
-  wb.B = p->B;
-  wb.ws = wbs;
-  int rc = pack_x<T>((const T*)Xs, (int)m, p->d, M, Xst, s, wb);
-  if (rc) return rc;
-  {
-    PreSlot slot(p, s);
-    if ((rc = gram_cross_slopes<T>(p->model, p->d, (const T*)p->Xt, p->N, (int)p->n, Xst, M, (int)m, theta, cols, ncols, Ks, s, bt,
-                                   wbs, p->pre, slot.staging)))
-      return rc;
-  }
-  wb.ws = 0;
-  if ((rc = gram_prior_slopes<T>(p->model, p->d, Xst, M, (int)m, theta, cols, ncols, prior, s, wb, wbs, p->pre))) return rc;
-  if ((rc = predict_v<T>((const T*)p->Tm, p->N, Ks, (long)P * M, V, s, bt, wbs))) return rc;
-  return slopes_reduce<T>(P, V, Ks, p->N, M, (int)m, (const T*)p->alpha, prior, (T*)(w + L.part), (T*)mean, (T*)cov, s, bt, wbs);
+  return predict_planes<T>(
+      p, Xs, m, planes_layout(p, m, P, P * (P + 1) / 2), P, work, s,
+      [&](const T* Xst, long M, T* Ks, const Batch& bt, long wbs, void* staging) {
+        return gram_cross_slopes<T>(p->model, p->d, (const T*)p->Xt, p->N, (int)p->n, Xst, M, (int)m, theta, cols, ncols, Ks, s, bt, wbs,
+                                    p->pre, staging);
+      },
+      [&](const T* Xst, long M, T* prior, const Batch& wb, long wbs) {
+        return gram_prior_slopes<T>(p->model, p->d, Xst, M, (int)m, theta, cols, ncols, prior, s, wb, wbs, p->pre);
+      },
+      [&](const T* V, const T* Ks, long M, const T* prior, T* part, const Batch& bt, long wbs) {
+        return slopes_reduce<T>(P, V, Ks, p->N, M, (int)m, (const T*)p->alpha, prior, part, (T*)mean, (T*)cov, s, bt, wbs);
+      });
 }
 
 #define DGP_BY_DTYPE(p, CALL64, CALL32) ((p)->dtype == DGP_F64 ? (CALL64) : (CALL32))
@@ -1223,7 +1209,9 @@ int dgp_posterior_cov(dgp_plan* p, const double* theta, const void* Xs, int64_t 
 int dgp_model_nterms(int model, int d) { return model_nterms(model, d); }
 
 size_t dgp_predict_terms_workspace_bytes(const dgp_plan* p, int64_t m) {
-  return (p && m > 0) ? terms_layout(p, m).total * (size_t)p->B : 0;
+  if (!p || m <= 0) return 0;
+  const int C = model_nterms(p->model, p->d);
+  return planes_layout(p, m, C, C).total * (size_t)p->B;
 }
 
 int dgp_predict_terms(dgp_plan* p, const double* theta, const void* Xs, int64_t m, void* work, size_t work_bytes, void* mean,
@@ -1242,7 +1230,9 @@ int dgp_predict_terms(dgp_plan* p, const double* theta, const void* Xs, int64_t 
 int dgp_model_input_differentiable(int model, int d, int col) { return model_input_differentiable(model, d, col); }
 
 size_t dgp_predict_slopes_workspace_bytes(const dgp_plan* p, int64_t m, int ncols) {
-  return (p && m > 0 && ncols >= 1 && ncols <= p->d) ? slopes_layout(p, m, ncols).total * (size_t)p->B : 0;
+  if (!p || m <= 0 || ncols < 1 || ncols > p->d) return 0;
+  const int P = 1 + ncols;
+  return planes_layout(p, m, P, P * (P + 1) / 2).total * (size_t)p->B;
 }
 
 int dgp_predict_slopes(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const int* cols, int ncols, void* work,

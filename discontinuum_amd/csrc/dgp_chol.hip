@@ -1578,24 +1578,6 @@ int refine_solve(const T* Tm, long N, const T* r, int n, const double* rho64, co
   return (int)hipGetLastError();
 }
 
-// dNLL/dnoise_i = 1/2 (S_ii - alpha_i^2)
-template <typename T>
-__global__ __launch_bounds__(256) void dnoise_kernel(const T* __restrict__ S, const T* __restrict__ alpha, long N,
-                                                     int n, T* __restrict__ dnoise, long bs, const int* __restrict__ ns) {
-  S = site(S, bs);
-  alpha = site(alpha, bs);
-  dnoise = site(dnoise, (long)n);
-  const int nb = site_n(ns, n);
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) dnoise[i] = i < nb ? T(0.5) * (S[i * N + i] - alpha[i] * alpha[i]) : T(0);
-}
-
-template <typename T>
-int finish(const T* S, const T* alpha, long N, int n, T* dnoise, hipStream_t s, Batch bt) {
-  dnoise_kernel<T><<<dim3((unsigned)((n + 255) / 256), 1, (unsigned)bt.B), 256, 0, s>>>(S, alpha, N, n, dnoise, bt.ws, bt.ns);
-  return (int)hipGetLastError();
-}
-
 // ------------------------------------------------------------------------------------------
 // prediction: V = T Ks (N x M, Ks = K(X, X*) padded to M % 128 == 0), var_j = kss_j - sum_i V_ij^2,
 // mean_j = sum_i Ks_ij alpha_i      (src/discontinuum/engines/gpytorch.py:621-624)
@@ -1750,7 +1732,6 @@ int sample_draws(const T* L, long M, const T* Z, long Q, const T* mean, int m, i
   template int lauum<T>(const T*, long, T*, hipStream_t, Batch);                                                      \
   template int solve<T>(const T*, long, const T*, int, T*, T*, T*, T*, hipStream_t, Batch);                           \
   template int refine_solve<T>(const T*, long, const T*, int, const double*, const T*, T*, T*, T*, T*, T*, hipStream_t, Batch, long, long); \
-  template int finish<T>(const T*, const T*, long, int, T*, hipStream_t, Batch);                                      \
   template int predict_v<T>(const T*, long, const T*, long, T*, hipStream_t, Batch, long);                                  \
   template int predict_var<T>(const T*, long, const T*, long, T*, const T*, const T*, T*, T*, T*, hipStream_t, Batch, long);
 DGP_INST(double)

@@ -146,8 +146,6 @@ int lauum(const T* Tm, long N, T* S, hipStream_t s, Batch bt = Batch());
 template <typename T>
 int solve(const T* Tm, long N, const T* r, int n, T* z, T* alpha, T* partials, T* quad, hipStream_t s,
           Batch bt = Batch());
-template <typename T>
-int finish(const T* S, const T* alpha, long N, int n, T* dnoise, hipStream_t s, Batch bt = Batch());
 // fp32 plans, after solve(): one step of iterative refinement with an fp64 residual (dgp_gram.hip::gram_residual).
 //   delta = T^T (T rho32)  (the fp32 factor),  alpha <- alpha + delta,  quad = r^T alpha0 + rho^T (alpha0 + delta) in double
 // (second-order accurate in the error of delta).  z and `partials` are solve()'s scratch; rho32 / delta: N elements each.

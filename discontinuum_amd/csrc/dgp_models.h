@@ -748,6 +748,14 @@ struct Composite {
   static __device__ __forceinline__ void finalize(T (&)[NTHETA], const Pre&) {}  // the interpreter applies every factor per entry
 };
 
+// the interpreted evaluator (Composite) is instantiated ONCE per kernel, in rolled loops over entries and terms
+// (Composite::term), and reads the points' features from the LDS strips: unrolled copies of its body pass the unroller's
+// size limit, and register arrays indexed by a loop counter or a descriptor entry would live in scratch memory
+template <typename M>
+struct Interpreted { static constexpr bool value = false; };
+template <typename T, int D>
+struct Interpreted<Composite<T, D>> { static constexpr bool value = true; };
+
 // Hyperparameters of a batch, blockIdx.z selects the site: up to DGP_MAX_BATCH sites travel by value in the kernel
 // argument segment (SGPR loads, nothing to upload); larger batches read them from a device array (`dev`) that the
 // launcher fills with one small asynchronous copy per fit step.

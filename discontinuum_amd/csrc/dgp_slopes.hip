@@ -18,11 +18,6 @@
 
 namespace dgp {
 
-template <typename M>
-struct InterpretedSlopes { static constexpr bool value = false; };
-template <typename T, int D>
-struct InterpretedSlopes<Composite<T, D>> { static constexpr bool value = true; };
-
 // test strip: the features and the slope features (derivatives of the per-point warps at the test point)
 template <typename T, typename M>
 __device__ __forceinline__ void stage_slope_strip(const T* __restrict__ Xst, long Mp, long base, const typename M::Pre& pre,
@@ -57,7 +52,7 @@ __global__ __launch_bounds__(256) void gram_cross_slopes_kernel(const T* __restr
   __syncthreads();
   const int ty = t >> 4, tx = t & 15;
   const long ld = (long)(1 + sc.ncols) * Mp;
-  if constexpr (InterpretedSlopes<M>::value) {
+  if constexpr (Interpreted<M>::value) {
     // one entry and one requested column at a time, element stores; every column's call also gives the value
 #pragma unroll 1
     for (int e = 0; e < 16; ++e) {  // one flat loop over the thread's 4 x 4 entries: fewer live scalars than two nested ones
@@ -121,7 +116,7 @@ __global__ __launch_bounds__(256) void gram_prior_slopes_kernel(const T* __restr
   const long j = (long)blockIdx.x * 256 + threadIdx.x;
   if (j >= Mp) return;
   const bool live = j < m;
-  if constexpr (InterpretedSlopes<M>::value) {
+  if constexpr (Interpreted<M>::value) {
 #pragma unroll 1
     for (int a = 0; a <= sc.ncols; ++a) {
       const T v = M::prior_col(a == 0 ? -1 : (int)sc.col[a - 1], pre);

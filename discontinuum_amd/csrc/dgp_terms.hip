@@ -20,14 +20,6 @@
 
 namespace dgp {
 
-// the interpreted evaluator (Composite) is instantiated ONCE per kernel, in rolled loops over entries and terms
-// (Composite::term), and reads the points' features from the LDS strips: unrolled copies of its body pass the unroller's
-// size limit, and register arrays indexed by a loop counter or a descriptor entry would live in scratch memory
-template <typename M>
-struct Interpreted { static constexpr bool value = false; };
-template <typename T, int D>
-struct Interpreted<Composite<T, D>> { static constexpr bool value = true; };
-
 // C planes of the live terms: the fused models write all of M::NTERMS, a composite its descriptor's count (<= DGP_C_TMAX)
 template <typename T, typename M>
 __global__ __launch_bounds__(256) void gram_cross_terms_kernel(const T* __restrict__ Xt, long N, int n,

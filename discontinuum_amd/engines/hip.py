@@ -587,16 +587,24 @@ class MarginalHIP(BaseModel):
             self._factor_key = key
             self._factor_theta = spec.theta.detach()
 
-    def _model_space_predict(self, x: torch.Tensor):
-        """(mu, var) in model space -- ``__gpytorch_predict`` of the reference (engines/gpytorch.py:599-626)."""
+    def _eval_ready(self, x=None):
+        """What every product computed from the held factorisation starts with: the device state, eval mode, the model's
+        data-dependent clamps for the model-space points ``x``, then the factorisation at the (clamped) hyperparameters --
+        in this order: the parameter key ``_ensure_factor`` compares may depend on the clamps."""
         self._device_ready()
         self.model.eval()
         self.likelihood.eval()
-        x = x.to(self.device, self.dtype).contiguous()
         with torch.no_grad():
             if hasattr(self.model, "prepare_eval"):
-                self.model.prepare_eval(self._train_x, x)  # data-dependent clamps see [X; X*] (SURVEY A.8)
+                # data-dependent clamps see [X; X*] (SURVEY A.8); without test points, the training rows only
+                self.model.prepare_eval(self._train_x, self._train_x if x is None else x)
             self._ensure_factor()
+
+    def _model_space_predict(self, x: torch.Tensor):
+        """(mu, var) in model space -- ``__gpytorch_predict`` of the reference (engines/gpytorch.py:599-626)."""
+        x = x.to(self.device, self.dtype).contiguous()
+        self._eval_ready(x)
+        with torch.no_grad():
             kmean, kvar = self._plan.predict(self._factor_theta, x)
             mu = kmean + self.model.prior_mean(x)
             var = kvar + self.likelihood.predictive_noise(x.shape[0], x.device, self.dtype)
@@ -638,13 +646,8 @@ class MarginalHIP(BaseModel):
         K** - V^T V with V = L^-1 K(X, X*), its Cholesky factor (our blocked HIP potrf, psd_safe_cholesky's jitter
         policy) times N(0, I) (``dgp_sample_draws``)."""
         Xnew = torch.tensor(self.dm.Xnew(covariates), dtype=self.dtype).to(self.device).contiguous()
-        self._device_ready()
-        self.model.eval()
-        self.likelihood.eval()
+        self._eval_ready(Xnew)
         with torch.no_grad():
-            if hasattr(self.model, "prepare_eval"):
-                self.model.prepare_eval(self._train_x, Xnew)
-            self._ensure_factor()
             mean, factor, _jitter = self._plan.posterior_factor(self._factor_theta, Xnew)
             mean = mean + self.model.prior_mean(Xnew)
             sim = self._plan.sample_draws(factor, Xnew.shape[0], mean, n)  # (n, m) = mean + (L z)^T, one HIP launch

@@ -73,19 +73,14 @@ def count_moments(model, Xnew, u, w, groups, ngroups, pred_noise=False, max_byte
     Xnew = Xnew.to(model.device).contiguous()
     m = Xnew.shape[0]
     u = np.ascontiguousarray(np.asarray(u, dtype=np.float64).reshape(-1, m))
-    model._device_ready()
-    model.model.eval()
-    model.likelihood.eval()
     esz = torch.empty((), dtype=model.dtype).element_size()
     need = _site_bytes(model.dm.X.shape[0], m, esz) + _work_bytes(m, ngroups, min(u.shape[0], MAX_LEVELS))
     if need > max_bytes:
         raise ValueError(f"exceedance statistics need the dense posterior covariance: a footprint of {need} bytes for "
                          f"m = {m} points exceeds max_bytes = {max_bytes}")
     means, covs = [], []
+    model._eval_ready(Xnew)
     with torch.no_grad():
-        if hasattr(model.model, "prepare_eval"):
-            model.model.prepare_eval(model._train_x, Xnew)
-        model._ensure_factor()
         kmean, cov = model._plan.posterior_cov(model._factor_theta, Xnew)
         mu = (kmean + model.model.prior_mean(Xnew)).contiguous()
         extra = model.likelihood.predictive_noise(m, Xnew.device, model.dtype) if pred_noise else None

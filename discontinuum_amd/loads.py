@@ -153,14 +153,9 @@ def point_moments(model, Xnew, w, groups, labels, n_points, ci=0.95, pred_noise=
     mode, s, t = target_transform(model.dm)
     Xnew = Xnew.to(model.device).contiguous()
     m = Xnew.shape[0]
-    model._device_ready()
-    model.model.eval()
-    model.likelihood.eval()
+    model._eval_ready(Xnew)
     esz = torch.empty((), dtype=model.dtype).element_size()
     with torch.no_grad():
-        if hasattr(model.model, "prepare_eval"):
-            model.model.prepare_eval(model._train_x, Xnew)
-        model._ensure_factor()
         if _site_bytes(model.dm.X.shape[0], m, esz) <= max_bytes:
             kmean, cov = model._plan.posterior_cov(model._factor_theta, Xnew)
             mu = kmean + model.model.prior_mean(Xnew)

@@ -86,8 +86,6 @@ def prior_mean_slopes(model, x, cols):
 def model_space(model, Xnew, cols):
     """(mean (P, m), cov (P, P, m), prior-mean slopes (P - 1, m)) in model space, P = 1 + len(cols), as float64 numpy."""
     model._device_ready()
-    model.model.eval()
-    model.likelihood.eval()
     plan = model._plan
     mid = model_id(plan.model)
     lib = _lib.load()
@@ -95,10 +93,8 @@ def model_space(model, Xnew, cols):
         if int(lib.dgp_model_input_differentiable(mid, int(plan.d), int(c))) != 1:
             raise ValueError(f"the covariance is not differentiable in covariate column {c} (Matern-1/2 factor): no slope exists")
     x = Xnew.to(model.device, model.dtype).contiguous()
+    model._eval_ready(x)
     with torch.no_grad():
-        if hasattr(model.model, "prepare_eval"):
-            model.model.prepare_eval(model._train_x, x)  # data-dependent clamps see [X; X*], as in predict
-        model._ensure_factor()
         mean, packed = plan.predict_slopes(model._factor_theta, x, cols)
     dprior = prior_mean_slopes(model, x, cols)
     mean = mean.detach().to("cpu", torch.float64).numpy()

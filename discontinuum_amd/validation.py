@@ -94,14 +94,10 @@ def _scheme_name(folds):
 def model_space(model, groups):
     """(y, mu, var, lpd) in model space for the fold ids ``groups`` (n,): the observations, their held-out predictive mean
     and variance (NaN / NaN where the observation is never held out) and the per-fold joint log density, as numpy arrays."""
-    model._device_ready()
-    model.model.eval()
-    model.likelihood.eval()
+    if hasattr(model.model, "prepare_eval"):
+        model._factor_key = None  # a model with data-dependent clamps is factorised afresh
+    model._eval_ready()  # no test points: the clamps see the training rows only
     with torch.no_grad():
-        if hasattr(model.model, "prepare_eval"):
-            model.model.prepare_eval(model._train_x, model._train_x)  # data-dependent clamps see the training rows only
-            model._factor_key = None
-        model._ensure_factor()
         resid, var, lpd, info = model._plan.cross_validate(torch.as_tensor(np.asarray(groups), dtype=torch.int64))
         y = model._train_y.detach().to("cpu", torch.float64).numpy()
     resid, var = resid.detach().cpu().numpy(), var.detach().cpu().numpy()

@@ -1,0 +1,127 @@
+#!/usr/bin/env python
+"""Bitwise record of everything a ``GPPlan`` computes from a held factorisation, for refactors of the host glue that must not
+move a number: seeded inputs, one fit, and the outputs of ``fit_step``, ``factorize``, ``predict``, ``predict_mean``,
+``mean_vjp``, ``predict_terms`` / ``predict_slopes`` (with and without ``return_cov``), ``posterior_cov``,
+``posterior_period_moments``, ``period_moments``, ``exceedance_moments`` and ``cross_validate``.
+
+    python scripts/inference_snapshot.py --write before.pt      # on the commit to compare against
+    python scripts/inference_snapshot.py --compare before.pt    # on the new one: exit status 1 unless every tensor is equal
+
+Shapes: n = 300 (N = 384), m = 200 (M = 256: pad columns exist), every chunked call once whole and once with ``chunk=128``
+(two staged chunks); loadest d = 3 in float64 and rating d = 2 in float32 (refinement on); one site, a ragged batch of three
+(300, 257, 129 rows) and a batch of nine (hyperparameters through the plan's device scratch and a pinned staging slot).
+``--root`` selects the tree whose package is imported.  One JSON line per run."""
+import argparse
+import json
+import os
+import sys
+
+M_POINTS, N_ROWS, GROUPS, LEVELS = 200, 300, 4, 2
+CONFIGS = [(model, d, dtype, sizes)
+           for model, d, dtype in (("loadest", 3, "f64"), ("rating", 2, "f32"))
+           for sizes in ((300,), (300, 257, 129), (300,) * 9)]
+
+
+def run_config(torch, GPPlan, backend, make_case, model, d, dtype, sizes, dev):
+    """-> {name: CPU tensor} of one configuration."""
+    B, n, m = len(sizes), N_ROWS, M_POINTS
+    lead = () if B == 1 else (B,)
+    cases = [make_case(model, d, n, seed=10 + b, perturb=0.2) for b in range(B)]
+    tests = [make_case(model, d, m, seed=40 + b)[0] for b in range(B)]
+
+    def stack(parts, dt):
+        t = torch.stack([p.to(dt) for p in parts]) if B > 1 else parts[0].to(dt)
+        return t.to(dev).contiguous()
+
+    X, r, noise = (stack([c[k] for c in cases], dtype) for k in range(3))
+    theta = torch.stack([c[3] for c in cases]) if B > 1 else cases[0][3]
+    Xs = stack(tests, dtype)
+    g = torch.Generator().manual_seed(7)
+    wv = stack([torch.randn(m, generator=g, dtype=torch.float64) for _ in range(B)], dtype)
+    mu = stack([0.3 * torch.randn(m, generator=g, dtype=torch.float64) for _ in range(B)], dtype)
+    extra = stack([0.01 + 0.02 * torch.rand(m, generator=g, dtype=torch.float64) for _ in range(B)], dtype)
+    w = stack([0.5 + torch.rand(m, generator=g, dtype=torch.float64) for _ in range(B)], torch.float64)
+    thresh = stack([torch.randn(LEVELS, m, generator=g, dtype=torch.float64) for _ in range(B)], torch.float64)
+    ids = (torch.arange(m) * GROUPS // m).to(torch.int32)
+    ids[5::17] = -1
+    groups = ids.expand(lead + (m,)).contiguous()
+    scale2 = 0.25 if B == 1 else [0.25 + 0.05 * b for b in range(B)]
+    folds = torch.arange(n) % 5
+    folds[3::29] = -1
+    folds = folds.expand(lead + (n,)).contiguous()
+
+    plan = GPPlan(model, n, d, dtype=dtype, device=dev, batch=B)
+    if B > 1:
+        plan.set_site_sizes(sizes)
+    plan.set_inputs(X)
+    cols = [c for c in range(d) if int(plan.lib.dgp_model_input_differentiable(backend.model_id(model), d, c)) == 1]
+    out = {}
+
+    def keep(name, value):
+        for i, t in enumerate(value if isinstance(value, (tuple, list)) else (value,)):
+            if t is not None:
+                out[f"{name}.{i}"] = t.detach().cpu()
+
+    keep("fit_step", plan.fit_step(theta, r, noise))
+    keep("mean_vjp", plan.mean_vjp(theta, Xs, wv))
+    keep("cross_validate_after_fit_step", plan.cross_validate(folds))
+    keep("factorize", plan.factorize(theta, r, noise))
+    keep("predict", plan.predict(theta, Xs))
+    keep("predict_chunk128", plan.predict(theta, Xs, chunk=128))
+    keep("predict_mean", plan.predict_mean(theta, Xs))
+    for return_cov in (True, False):
+        for chunk in (None, 128):
+            tag = f"{'cov' if return_cov else 'mean'}_{'whole' if chunk is None else 'chunk128'}"
+            keep(f"predict_terms_{tag}", plan.predict_terms(theta, Xs, chunk=chunk, return_cov=return_cov))
+            keep(f"predict_slopes_{tag}", plan.predict_slopes(theta, Xs, cols, chunk=chunk, return_cov=return_cov))
+    kmean, cov = plan.posterior_cov(theta, Xs)
+    keep("posterior_cov", (kmean, torch.tril(cov)[..., :m, :m]))  # the part the layout defines
+    keep("period_moments", plan.period_moments(cov, m, mu, scale2, w, groups, GROUPS, backend.MODE_LOG, extra_var=extra))
+    keep("exceedance_moments", plan.exceedance_moments(cov, m, mu, thresh, w, groups, GROUPS, extra_var=extra))
+    keep("posterior_period_moments_log", plan.posterior_period_moments(theta, Xs, mu, scale2, w, groups, GROUPS, backend.MODE_LOG))
+    keep("posterior_period_moments_linear",
+         plan.posterior_period_moments(theta, Xs, mu, scale2, w, groups, GROUPS, backend.MODE_LINEAR, extra_var=extra))
+    keep("cross_validate", plan.cross_validate(folds))
+    torch.cuda.synchronize(dev)
+    return out
+
+
+def same_bits(torch, a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(a.reshape(-1).view(torch.uint8), b.reshape(-1).view(torch.uint8))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    what = ap.add_mutually_exclusive_group(required=True)
+    what.add_argument("--write", metavar="FILE")
+    what.add_argument("--compare", metavar="FILE")
+    ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    args = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(args.root))
+    import torch
+
+    from discontinuum_amd import backend
+    from discontinuum_amd.backend import GPPlan
+    from tests.test_gpu_stages import make_case
+
+    dev = torch.device("cuda:0")
+    snap = {}
+    for model, d, dtype, sizes in CONFIGS:
+        tensors = run_config(torch, GPPlan, backend, make_case, model, d, torch.float64 if dtype == "f64" else torch.float32, sizes, dev)
+        for name, t in tensors.items():
+            snap[f"{model}-{dtype}-batch{len(sizes)}/{name}"] = t
+    result = {"root": os.path.abspath(args.root), "tensors": len(snap), "bytes": sum(t.numel() * t.element_size() for t in snap.values()),
+              "device": torch.cuda.get_device_name(dev)}
+    if args.write:
+        torch.save(snap, args.write)
+        result["written"] = args.write
+    else:
+        ref = torch.load(args.compare)
+        differ = sorted(k for k in set(ref) | set(snap) if k not in ref or k not in snap or not same_bits(torch, ref[k], snap[k]))
+        result.update(compared=args.compare, differ=differ, bitwise_equal=not differ)
+    print(json.dumps(result))
+    return 0 if args.write or not differ else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
