@@ -439,6 +439,13 @@ class GPPlan:
         with torch.cuda.device(self.device):
             return exceedance_moments(cov, m, mu, thresh, w, groups, ngroups, extra_var)
 
+    def sample_value(self, cov, m: int, a, scale2, groups, ngroups: int, obs_var=None, rows=None, nterms=None):
+        """Expected reduction of every period sum's variance by one more sample on each day (``dgp_sample_value``): see the
+        module-level ``sample_value``.  Unbatched (cov (M, M), vectors (m,), rows (nrows, m)) -> gain (P, m), var (m,);
+        batched (cov (B, M, M), vectors (B, m), rows (B, nrows, m)) -> (B, P, m), (B, m); fp64 device tensors."""
+        with torch.cuda.device(self.device):
+            return sample_value(cov, m, a, scale2, groups, ngroups, obs_var=obs_var, rows=rows, nterms=nterms)
+
     def posterior_period_moments(self, theta, Xs: torch.Tensor, mu, scale2, w, groups, ngroups: int, mode: int, extra_var=None):
         """``period_moments`` of the posterior at Xs straight from the held factorisation (``dgp_posterior_period_moments``):
         the (M, M) covariance is never formed.  Xs (m, d) -- (batch, m, d) for a batched plan, theta (batch, ntheta) --; the
@@ -661,6 +668,89 @@ def exceedance_moments(cov: torch.Tensor, m: int, mu: torch.Tensor, thresh: torc
         "dgp_exceedance_moments",
     )
     return mean_out, cov_out
+
+
+MAX_SERIES_TERMS = 64  # the largest ``nterms`` of ``dgp_sample_value``
+
+
+def series_terms(beta: float) -> int:
+    """Terms of the exponential series ``sample_value`` needs: the smallest K <= 64 with sum_{k>K} beta^k / k! <= 2^-53 beta,
+    beta = s^2 max_i C_ii -- the truncation then stays below the rounding of the first term.  Raises ``ValueError`` naming
+    beta when 64 terms do not suffice (beta above about 14.7, however large) or beta is not a finite number >= 0."""
+    beta = float(beta)
+    if not (beta >= 0.0) or beta == float("inf"):
+        raise ValueError(f"sample_value: beta = s^2 max C_ii = {beta} is not a finite number >= 0")
+    if beta == 0.0:
+        return 1
+    too_many = ValueError(f"sample_value: beta = s^2 max C_ii = {beta:.6g} needs more than {MAX_SERIES_TERMS} terms of the "
+                          "exponential series")
+    if beta > MAX_SERIES_TERMS:  # the terms beta^k / k! still grow at k = 64: decided without running the series
+        raise too_many
+    terms, t = [], 1.0
+    for k in range(1, 5 * MAX_SERIES_TERMS + 1):  # beta <= 64: beta^k / k! < 1e-49 beta from k = 320 on
+        t *= beta / k
+        terms.append(t)
+    tail = 0.0
+    tails = [0.0] * (len(terms) + 1)  # tails[K] = sum_{k>K} beta^k / k!
+    for k in range(len(terms), 0, -1):
+        tails[k - 1] = tail = tail + terms[k - 1]
+    for K in range(1, MAX_SERIES_TERMS + 1):
+        if tails[K] <= 2.0 ** -53 * beta:
+            return K
+    raise too_many
+
+
+def sample_value(cov: torch.Tensor, m: int, a: torch.Tensor, scale2, groups: torch.Tensor, ngroups: int,
+                 obs_var: torch.Tensor | None = None, rows: torch.Tensor | None = None, nterms: int | None = None):
+    """Expected reduction gain[p, c] = Var(E[L_p | y_c]) of the variance of every period sum L_p = sum_{i in p} w_i c_i
+    (``period_moments``' setting) by ONE more sample y_c = f_c + eps on day c, for every day c at once, through one
+    ``dgp_sample_value`` call: sum_k (s^2)^k / k! (sum_{i in p} A_i b_ic^k)^2 with b_ic = C'_ic / sqrt(v'_c),
+    v'_c = C'_cc + obs_var_c and C' = C - rows^T rows the covariance after the samples already decided.
+
+    ``cov``: what ``GPPlan.posterior_cov`` returns, (M, M) or (B, M, M), never modified; ``a``: A_i = w_i exp(s mu_i + t +
+    s^2 C_ii / 2) for a log target, w_i for a linear one, (m,) / (B, m); ``scale2``: s^2, a number or (B,) values;
+    ``groups``: int32 ids (m,) / (B, m) in 0 .. ngroups-1, non-decreasing except for -1 (excluded) anywhere -- excluded
+    days are candidates too; ``obs_var``: None or (m,) / (B, m), the noise variance of the hypothetical sample;
+    ``rows``: None or (nrows, m) / (B, nrows, m) float64 with nrows <= 64, the conditioning rows B of the pivoted-Cholesky
+    recurrence; ``nterms``: the series length K (1 = a linear target, exactly); None picks ``series_terms`` of
+    beta = s^2 max C_ii over the included days, read from the buffer's diagonal.
+    -> (gain (P, m), var (m,)) or ((B, P, m), (B, m)), float64 device tensors; var is v'_c (0 where it is not > 0: such a
+    candidate has gain 0)."""
+    lib = _lib.load()
+    batched = cov.dim() == 3
+    B = cov.shape[0] if batched else 1
+    M = int(lib.dgp_padded_n(int(m)))
+    lead = (B,) if batched else ()
+    if cov.dtype not in _DTYPES or not cov.is_cuda or not cov.is_contiguous() or tuple(cov.shape) != lead + (M, M):
+        raise ValueError(f"cov must be a contiguous {lead + (M, M)} float64 / float32 CUDA tensor")
+    dev = cov.device
+    _, a_t, g_t, ov_t, s2 = _moment_inputs(dev, cov.dtype, lead, int(m), None, a, groups, obs_var, scale2)
+    nrows, rows_t = 0, None
+    if rows is not None:
+        rows_t = torch.as_tensor(rows).to(dev, torch.float64).contiguous()
+        if rows_t.dim() != len(lead) + 2 or tuple(rows_t.shape[:-2]) != lead or rows_t.shape[-1] != int(m):
+            raise ValueError(f"rows must have shape {lead + ('nrows', int(m))}")
+        nrows = int(rows_t.shape[-2])
+        if nrows == 0:
+            rows_t = None
+    if nterms is None:
+        diag = torch.diagonal(cov, dim1=-2, dim2=-1)[..., : int(m)].double()
+        top = torch.where(g_t >= 0, diag, torch.zeros_like(diag)).reshape(B, -1).amax(dim=1)
+        nterms = series_terms(float((s2 * top).max()))
+    P, K = int(ngroups), int(nterms)
+    need = int(lib.dgp_sample_value_workspace_bytes(int(m), P, nrows, K, B))
+    if need == 0:
+        raise ValueError(f"bad size: m = {int(m)}, ngroups = {P}, nrows = {nrows}, nterms = {K}, batch = {B} (1 <= m <= 2^20, "
+                         "1 <= ngroups <= 65535, 0 <= nrows <= 64, 1 <= nterms <= 64, 1 <= batch <= 1024)")
+    work = torch.empty(need, dtype=torch.uint8, device=dev)
+    gain = torch.empty(lead + (P, int(m)), dtype=torch.float64, device=dev)
+    var = torch.empty(lead + (int(m),), dtype=torch.float64, device=dev)
+    _lib.check(
+        lib.dgp_sample_value(_DTYPES[cov.dtype], _ptr(cov), int(m), B, _ptr(a_t), _ptr(s2), _ptr(g_t), P, _ptr(ov_t), _ptr(rows_t),
+                             nrows, K, _ptr(work), need, _ptr(gain), _ptr(var), _stream()),
+        "dgp_sample_value",
+    )
+    return gain, var
 
 
 def bvn_excess(h: torch.Tensor, k: torch.Tensor, rho: torch.Tensor):

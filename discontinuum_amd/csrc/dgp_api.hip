@@ -1374,6 +1374,35 @@ int dgp_exceedance_moments(int dtype, const void* cov, int64_t m, int batch, con
   return wrap(rc, "dgp_exceedance_moments");
 }
 
+static bool sv_sizes_ok(int64_t m, int ngroups, int nrows, int nterms, int batch) {
+  return m > 0 && m <= (1 << 20) && ngroups > 0 && ngroups <= 65535 && nrows >= 0 && nrows <= 64 && nterms >= 1 && nterms <= 64 &&
+         batch > 0 && batch <= DGP_MAX_BATCH_SITES;
+}
+size_t dgp_sample_value_workspace_bytes(int64_t m, int ngroups, int nrows, int nterms, int batch) {
+  if (!sv_sizes_ok(m, ngroups, nrows, nterms, batch)) return 0;
+  return sample_value_workspace_bytes(m, ngroups, nterms, batch);
+}
+
+int dgp_sample_value(int dtype, const void* cov, int64_t m, int batch, const double* a, const double* scale2, const int32_t* group,
+                     int ngroups, const void* obs_var, const double* rows, int nrows, int nterms, void* work, size_t work_bytes,
+                     double* gain_out, double* var_out, void* stream) {
+  if (dtype != DGP_F64 && dtype != DGP_F32) return fail(DGP_E_ARG, "dgp_sample_value: dtype must be 0 (f64) or 1 (f32)");
+  if (!cov || !a || !scale2 || !group || !gain_out || !var_out) return fail(DGP_E_ARG, "dgp_sample_value: null argument");
+  if (!sv_sizes_ok(m, ngroups, nrows, nterms, batch))
+    return fail(DGP_E_ARG,
+                "dgp_sample_value: bad size (1 <= m <= 2^20, 1 <= ngroups <= 65535, 0 <= nrows <= 64, 1 <= nterms <= 64, "
+                "1 <= batch <= 1024)");
+  if (nrows > 0 && !rows) return fail(DGP_E_ARG, "dgp_sample_value: null argument (rows with nrows > 0)");
+  if (!work || work_bytes < sample_value_workspace_bytes(m, ngroups, nterms, batch))
+    return fail(DGP_E_WORKSPACE, "dgp_sample_value: workspace missing or too small");
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = dtype == DGP_F64 ? sample_value<double>((const double*)cov, m, batch, a, scale2, group, ngroups, (const double*)obs_var,
+                                                         rows, nrows, nterms, (double*)work, gain_out, var_out, s)
+                                  : sample_value<float>((const float*)cov, m, batch, a, scale2, group, ngroups, (const float*)obs_var,
+                                                        rows, nrows, nterms, (double*)work, gain_out, var_out, s);
+  return wrap(rc, "dgp_sample_value");
+}
+
 int dgp_debug_bvn_excess(const double* h, const double* k, const double* rho, int64_t count, double* out, void* stream) {
   if (!h || !k || !rho || !out || count <= 0 || count > (1ll << 31))
     return fail(DGP_E_ARG, "dgp_debug_bvn_excess: null argument / bad count");

@@ -213,6 +213,14 @@ int exceedance_moments(const T* cov, long m, int B, const T* mu, const double* t
 // out[i] = Phi2(h_i, k_i; rho_i) - Phi(h_i) Phi(k_i): the pair function of the pass above, pointwise
 int debug_bvn_excess(const double* h, const double* k, const double* rho, long count, double* out, hipStream_t s);
 
+// ---- dgp_design.hip: the expected reduction of Var(L_p) by one more sample on each day c, after `nrows` conditioning rows
+// (rows [B][nrows][m], null when nrows == 0; a [B][m] the A_i; ov: the candidates' noise variance or null).  gain_out [B][P][m],
+// var_out [B][m]; `work`: sample_value_workspace_bytes
+size_t sample_value_workspace_bytes(long m, int P, int K, int B);
+template <typename T>
+int sample_value(const T* cov, long m, int B, const double* a, const double* scale2, const int* group, int P, const T* ov,
+                 const double* rows, int nrows, int K, double* work, double* gain_out, double* var_out, hipStream_t s);
+
 // ---- dgp_terms.hip: the posterior of the covariance's additive parts (C = model_nterms).  Ks / V: N x (C Mp) row-major, term c
 // of test point j in column c Mp + j; kss: C Mp; part: terms_partials(C, Mp) elements; mean [B][C][m], cov [B][C (C + 1) / 2][m]
 // (entry (c, c'), c' <= c, at c (c + 1) / 2 + c'; null: not wanted) in the caller's arrays.

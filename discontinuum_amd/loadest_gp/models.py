@@ -104,6 +104,31 @@ class LoadestGPMarginalHIP(LoadestDataMixin, MarginalHIP):
         return flux_exceedance(self, covariates, threshold, freq=freq, above=above, fraction=fraction, ci=ci, pred_noise=pred_noise,
                                return_cov=return_cov, max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes)
 
+    def _flux_weights(self, daily):
+        from ..loads import _target_attrs, flux_weights
+
+        return flux_weights(daily, _target_attrs(self.dm))
+
+    @is_fitted
+    def sample_value(self, daily, freq="YE", sample_var=None, given=None, ci=0.95, max_bytes=None):
+        """By how much one more concentration sample on each day of ``daily`` is expected to reduce the variance of each
+        period's LOAD (kg; the flux weights of ``annual_flux``): ``MarginalHIP.sample_value``."""
+        return super().sample_value(daily, self._flux_weights(daily), freq=freq, sample_var=sample_var, given=given, ci=ci,
+                                    max_bytes=max_bytes)
+
+    @is_fitted
+    def design_value(self, daily, samples, freq="YE", sample_var=None, return_cov=False, max_bytes=None):
+        """The exact expected value of sampling the days ``samples`` for the period loads (kg): ``MarginalHIP.design_value``."""
+        return super().design_value(daily, self._flux_weights(daily), samples, freq=freq, sample_var=sample_var,
+                                    return_cov=return_cov, max_bytes=max_bytes)
+
+    @is_fitted
+    def design(self, daily, k, objective="relative", candidates=None, replicates=False, given=None, freq="YE", sample_var=None,
+               max_bytes=None):
+        """Greedy choice of ``k`` sampling days for the period loads (kg): ``MarginalHIP.design``."""
+        return super().design(daily, self._flux_weights(daily), k, objective=objective, candidates=candidates,
+                              replicates=replicates, given=given, freq=freq, sample_var=sample_var, max_bytes=max_bytes)
+
     @is_fitted
     def flux_bias(self, cv=None, folds="loo"):
         """WRTDS's flux bias statistic on the sampled days, (sum P - sum O) / sum P with O the observed and P the

@@ -303,6 +303,37 @@ int dgp_exceedance_moments(int dtype, const void* cov_dev, int64_t m, int batch,
 int dgp_debug_bvn_excess(const double* h_dev, const double* k_dev, const double* rho_dev, int64_t count, double* out_dev,
                          void* stream);
 
+/* Exact VALUE OF ONE MORE SAMPLE for the variance of period sums -- monitoring design -- which the reference could only
+ * estimate by refitting on simulated data.  Setting of dgp_period_moments: f ~ N(mu, C) per site, c_i = exp(s f_i + t) (or
+ * s f_i + t), L_p = sum_{i in p} w_i c_i.  A hypothetical observation y_c = f_c + eps, Var eps = tau_c^2, on day c moves the
+ * covariance deterministically and the mean randomly; with conditioning rows B (nrows x m, C' = C - B^T B: the samples
+ * already decided),
+ *   v'_c = C_cc - sum_t B_tc^2 + tau_c^2,   b_ic = (C_ic - sum_t B_ti B_tc) / sqrt(v'_c),
+ *   gain[p][c] = Var(E[L_p | y_c]) = sum_{i,j in p} A_i A_j expm1(s^2 b_ic b_jc)
+ *              = sum_{k=1..nterms} (s^2)^k / k! (sum_{i in p} A_i b_ic^k)^2           (the exponential series; every term >= 0)
+ * with A_i = w_i exp(s mu_i + t + s^2 C_ii / 2) for a log target; A_i = w_i and nterms = 1 is the linear target exactly.  By
+ * the law of total variance Var(L_p) - gain[p][c] = E[Var(L_p | y_c)].  Since b_ic^2 <= C_ii, the tail after K terms is at
+ * most (sum_{i in p} |A_i|)^2 sum_{k>K} beta^k / k!, beta = s^2 max_i C_ii: the caller picks nterms.
+ * cov_dev, group_dev, batch and the padding: as for dgp_period_moments (each site M x M, M = dgp_padded_n(m); only the lower
+ *            triangle is used; group -1 = excluded, ids non-decreasing otherwise -- a violation gives wrong numbers, never an
+ *            access out of bounds).  The covariance is never modified and never copied: C' is formed on the fly.
+ * a_dev      batch x m doubles, the A_i (computed by the host);  scale2_dev: batch doubles (s^2);
+ * obs_var_dev  NULL or batch x m `dtype` (tau_c^2);
+ * rows_dev   NULL or batch x nrows x m doubles, 0 <= nrows <= 64;  nterms: 1 <= K <= 64;
+ * gain_out_dev  batch x ngroups x m doubles;  var_out_dev  batch x m doubles (v'_c: what the next row is divided by).
+ * EVERY day is a candidate, excluded days included: a sample outside the periods of interest still informs them.  A candidate
+ * whose v'_c is not > 0 gets gain 0 in every period and var 0, never NaN; NaN inputs come out as NaN.  All arithmetic after
+ * the loads is double, for float32 buffers too.
+ * work_dev: dgp_sample_value_workspace_bytes(m, ngroups, nrows, nterms, batch) bytes -- per site M + ngroups doubles, plus
+ * ngroups Q nterms M doubles of partial sums when a group's days are cut into Q > 1 slabs (few groups: the launch fills the
+ * device whatever ngroups is; Q depends on M and ngroups alone); 0 for bad sizes.
+ * One pass of O(m^2 nterms) multiply-adds over about M^2 elements read (every lower-triangle entry twice); no floating-point
+ * atomics: bitwise repeatable, and a site's result does not depend on the batch it is in.  Needs no plan. */
+size_t dgp_sample_value_workspace_bytes(int64_t m, int ngroups, int nrows, int nterms, int batch);
+int dgp_sample_value(int dtype, const void* cov_dev, int64_t m, int batch, const double* a_dev, const double* scale2_dev,
+                     const int32_t* group_dev, int ngroups, const void* obs_var_dev, const double* rows_dev, int nrows,
+                     int nterms, void* work_dev, size_t work_bytes, double* gain_out_dev, double* var_out_dev, void* stream);
+
 /* Exact leave-one-out / leave-group-out cross-validation at FIXED hyperparameters from the factorisation the plan holds (after
  * dgp_factorize or dgp_fit_step; DGP_E_STATE without one) -- no fold is refitted.  The reference has no counterpart: with
  * gpytorch every fold is a new factorisation behind the `predict` call site (src/discontinuum/engines/gpytorch.py:599-626).

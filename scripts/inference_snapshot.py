@@ -2,7 +2,7 @@
 """Bitwise record of everything a ``GPPlan`` computes from a held factorisation, for refactors of the host glue that must not
 move a number: seeded inputs, one fit, and the outputs of ``fit_step``, ``factorize``, ``predict``, ``predict_mean``,
 ``mean_vjp``, ``predict_terms`` / ``predict_slopes`` (with and without ``return_cov``), ``posterior_cov``,
-``posterior_period_moments``, ``period_moments``, ``exceedance_moments`` and ``cross_validate``.
+``posterior_period_moments``, ``period_moments``, ``exceedance_moments``, ``sample_value`` and ``cross_validate``.
 
     python scripts/inference_snapshot.py --write before.pt      # on the commit to compare against
     python scripts/inference_snapshot.py --compare before.pt    # on the new one: exit status 1 unless every tensor is equal
@@ -78,6 +78,9 @@ def run_config(torch, GPPlan, backend, make_case, model, d, dtype, sizes, dev):
     keep("posterior_cov", (kmean, torch.tril(cov)[..., :m, :m]))  # the part the layout defines
     keep("period_moments", plan.period_moments(cov, m, mu, scale2, w, groups, GROUPS, backend.MODE_LOG, extra_var=extra))
     keep("exceedance_moments", plan.exceedance_moments(cov, m, mu, thresh, w, groups, GROUPS, extra_var=extra))
+    given = stack([0.05 * torch.randn(3, m, generator=g, dtype=torch.float64) for _ in range(B)], torch.float64)
+    keep("sample_value", plan.sample_value(cov, m, w, scale2, groups, GROUPS, obs_var=extra, rows=given, nterms=12))
+    keep("sample_value_linear", plan.sample_value(cov, m, w, scale2, groups, GROUPS, nterms=1))
     keep("posterior_period_moments_log", plan.posterior_period_moments(theta, Xs, mu, scale2, w, groups, GROUPS, backend.MODE_LOG))
     keep("posterior_period_moments_linear",
          plan.posterior_period_moments(theta, Xs, mu, scale2, w, groups, GROUPS, backend.MODE_LINEAR, extra_var=extra))
@@ -117,8 +120,9 @@ def main():
         result["written"] = args.write
     else:
         ref = torch.load(args.compare)
-        differ = sorted(k for k in set(ref) | set(snap) if k not in ref or k not in snap or not same_bits(torch, ref[k], snap[k]))
-        result.update(compared=args.compare, differ=differ, bitwise_equal=not differ)
+        differ = sorted(k for k in ref if k not in snap or not same_bits(torch, ref[k], snap[k]))
+        added = sorted(k for k in snap if k not in ref)  # a product the compared commit did not have yet
+        result.update(compared=args.compare, differ=differ, added=added, bitwise_equal=not differ)
     print(json.dumps(result))
     return 0 if args.write or not differ else 1
 
