@@ -350,6 +350,48 @@ class GPPlan:
             )
         return resid, var, lpd, info
 
+    # ------------------------------------------------------------------ Fisher information of the hyperparameters
+    def fisher(self, theta, diag=None, max_bytes: int | None = None):
+        """Exact Fisher information F_ab = 1/2 tr(K^^-1 D_a K^^-1 D_b) of the hyperparameters at the factorisation the plan
+        holds (``dgp_fisher``; nothing is refactored, the plan is only read).  Directions: first the ``ntheta`` kernel
+        directions dK/dtheta_p at ``theta`` (constrained values, as for ``fit_step``), then the E rows of ``diag`` -- (E, n),
+        or (batch, E, n) for a batched plan, E <= 8, in the plan's dtype on the device -- as diagonal directions diag(d_e)
+        (derivatives of learned noise terms; None: none).  -> (P + E, P + E) -- (batch, P + E, P + E) -- float64 device
+        tensor, bitwise symmetric, in un-normalised log-likelihood units.  The work area of (P + E + 1) N^2 elements per
+        site is kept between calls; ``max_bytes``: raise ``ValueError`` naming the bytes instead of allocating more."""
+        lead = () if self.batch == 1 else (self.batch,)
+        th = _theta_array(theta, self.ntheta * self.batch)
+        E = 0
+        if diag is not None:
+            if not (torch.is_tensor(diag) and diag.is_cuda and diag.dtype == self.dtype and diag.dim() == 2 + len(lead)
+                    and tuple(diag.shape[:-2]) == lead and diag.shape[-1] == self.n):
+                raise ValueError(f"diag must be a {lead + ('E', self.n)} {self.dtype} CUDA tensor")
+            E = int(diag.shape[-2])
+            if E > 8:
+                raise ValueError(f"at most 8 diagonal directions, got {E}")
+            diag = diag.contiguous() if E else None
+        need = int(self.lib.dgp_fisher_workspace_bytes(self._h, E))
+        if max_bytes is not None and need > int(max_bytes):
+            raise ValueError(f"the Fisher information of {self.ntheta + E} directions at n = {self.n} (batch {self.batch}) needs a "
+                             f"work area of {need} bytes, which exceeds max_bytes = {int(max_bytes)}")
+        nd = self.ntheta + E
+        with torch.cuda.device(self.device):
+            work = self._work_area("_fisher_ws", need, "dgp_fisher")
+            out = torch.empty(lead + (nd, nd), dtype=torch.float64, device=self.device)
+            _lib.check(self.lib.dgp_fisher(self._h, th, _ptr(diag), E, work, need, _ptr(out), _stream()), "dgp_fisher")
+        return out
+
+    def whiten(self, cols: torch.Tensor, site: int = 0):
+        """L^-1 cols through the inverse factor T the plan holds, for the few columns of a prior-mean Jacobian:
+        (L^-1 J)^T (L^-1 J) = J^T K^^-1 J, the mean block of the Fisher information.  ``cols`` (n_site, k) on the device
+        -> (n_site, k) float64.  One triangular n x n by n x k product; reads T only."""
+        ns = int((getattr(self, "_site_sizes", None) or [self.n] * self.batch)[site])
+        if not (torch.is_tensor(cols) and cols.is_cuda and cols.dim() == 2 and cols.shape[0] == ns):
+            raise ValueError(f"cols must be a ({ns}, k) CUDA tensor")
+        with torch.cuda.device(self.device):
+            T = torch.tril(self.buffer(_lib.BUF_T, site)[:ns, :ns]).double()
+            return T @ cols.double()
+
     # ------------------------------------------------------------------ sample(): posterior covariance, factor, draws
     def _jitter_ladder(self):
         """linear_operator's ``psd_safe_cholesky`` policy: first no jitter at all, then the

@@ -1440,6 +1440,41 @@ int dgp_cross_validate(dgp_plan* p, const int32_t* order, const int32_t* start, 
   return wrap(rc, "dgp_cross_validate");
 }
 
+#define DGP_FISHER_MAX_DIAG 8
+size_t dgp_fisher_workspace_bytes(const dgp_plan* p, int ndiag) {
+  if (!p || ndiag < 0 || ndiag > DGP_FISHER_MAX_DIAG) return 0;
+  return fisher_site_bytes(p->N, p->ntheta + ndiag, p->elem) * (size_t)p->B;
+}
+
+int dgp_fisher(dgp_plan* p, const double* theta, const void* diag, int ndiag, void* work, size_t work_bytes, double* fisher_out,
+               void* stream) {
+  if (!p) return fail(DGP_E_ARG, "null plan");
+  if (!theta || !fisher_out) return fail(DGP_E_ARG, "dgp_fisher: null argument");
+  if (ndiag < 0 || ndiag > DGP_FISHER_MAX_DIAG) return fail(DGP_E_ARG, "dgp_fisher: ndiag must be 0..8");
+  if (ndiag > 0 && !diag) return fail(DGP_E_ARG, "dgp_fisher: ndiag > 0 needs the diagonal directions");
+  DGP_CHECK_PLAN(p);
+  if (!p->have_factor) return fail(DGP_E_STATE, "dgp_fisher: no factorisation in the plan (call dgp_factorize or dgp_fit_step)");
+  if (!work || work_bytes < dgp_fisher_workspace_bytes(p, ndiag)) return fail(DGP_E_WORKSPACE, "dgp_fisher: workspace missing or too small");
+  if (((uintptr_t)work & 255) != 0) return fail(DGP_E_ARG, "dgp_fisher: the work area must be 256-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  {  // a failed factorisation leaves no T to read: the sites' status words, before any launch
+    std::vector<int> info((size_t)p->B, 0);
+    hipError_t e = hipMemcpy2DAsync(info.data(), sizeof(int), p->info, p->site_bytes, sizeof(int), (size_t)p->B, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hipfail(e, "dgp_fisher");
+    for (int b = 0; b < p->B; ++b)
+      if (info[(size_t)b] != 0) return fail(DGP_E_STATE, "dgp_fisher: the factorisation the plan holds failed (matrix not positive definite)");
+  }
+  PreSlot slot(p, s);
+  const int rc = DGP_BY_DTYPE(
+      p,
+      fisher<double>(p->model, p->d, (const double*)p->Xt, (const double*)p->Tm, p->N, (int)p->n, theta, (const double*)diag, ndiag, work,
+                     fisher_out, s, batch_of<double>(p), p->pre, slot.staging),
+      fisher<float>(p->model, p->d, (const float*)p->Xt, (const float*)p->Tm, p->N, (int)p->n, theta, (const float*)diag, ndiag, work,
+                    fisher_out, s, batch_of<float>(p), p->pre, slot.staging));
+  return wrap(rc, "dgp_fisher");
+}
+
 int dgp_plan_set_timing(dgp_plan* p, int enabled) {
   if (!p) return fail(DGP_E_ARG, "null plan");
   p->timing = enabled ? 1 : 0;

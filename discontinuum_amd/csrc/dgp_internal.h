@@ -265,4 +265,12 @@ template <typename T>
 int cross_validate(const T* Tm, const T* S, const T* alpha, long N, int n, const int* order, const int* start, int ngroups,
                    long max_group, void* work, double* resid, double* var, double* lpd, int* info, hipStream_t s, Batch bt);
 
+// ---- dgp_fisher.hip: F_ab = 1/2 tr(K^^-1 D_a K^^-1 D_b) over the nt kernel directions dK/dtheta_p and `ndiag` diagonal
+// directions diag [B][ndiag][n], from T = L^-1.  `work`: fisher_site_bytes per site; F [B][nt + ndiag][nt + ndiag] doubles.
+// Reads Xt and T only.
+size_t fisher_site_bytes(long N, int nd, size_t elem);
+template <typename T>
+int fisher(int model, int d, const T* Xt, const T* Tm, long N, int n, const double* theta, const T* diag, int ndiag, void* work,
+           double* F, hipStream_t s, Batch bt, void* pre_scratch, void* pre_staging);
+
 }  // namespace dgp

@@ -784,5 +784,17 @@ class MarginalHIP(BaseModel):
 
         return slope(self, covariates, wrt=wrt, ci=ci, return_cov=return_cov)
 
+    @is_fitted
+    def hyperparameter_uncertainty(self, ci=0.95, prior=True):
+        """How well the data determine the hyperparameters: standard errors, ``ci`` intervals and correlations of every
+        trainable parameter from the exact Fisher information of the marginal likelihood at the fitted values (``dgp_fisher``
+        on the factorisation the engine holds; no refit, no second derivatives).  ``prior=True`` adds the curvature of the
+        priors.  -> Dataset indexed by ``parameter`` with ``estimate``, ``se``, ``lower`` / ``upper``, ``se_raw``, ``active``,
+        ``cov_raw``, ``corr``, ``information`` and the ``unidentified`` directions, in un-normalised log-likelihood units
+        (the training objective is this divided by n).  See ``discontinuum_amd.hyperpar.hyperparameter_uncertainty``."""
+        from ..hyperpar import hyperparameter_uncertainty
+
+        return hyperparameter_uncertainty(self, ci=ci, prior=prior)
+
     def build_model(self, X, y, **kwargs):
         raise NotImplementedError("This method must be implemented in a subclass")

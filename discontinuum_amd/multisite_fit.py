@@ -33,6 +33,7 @@ from __future__ import annotations
 
 import time
 
+import numpy as np
 import torch
 from torch import nn
 from torch.func import functional_call, vmap
@@ -952,4 +953,87 @@ def predict_many(models, covariates_list):
     return results
 
 
-__all__ = ["fit_many", "fit_many_distributed", "predict_many", "FitManyState"]
+def hyperparameter_uncertainty_many(models, ci=0.95, prior=True, max_bytes=None):
+    """``models[i].hyperparameter_uncertainty(ci, prior)`` for many fitted sites through ONE batched device plan: one
+    batched factorisation and ONE batched ``dgp_fisher`` (gridDim.z = sites; ragged sizes) for all sites, the host algebra
+    of ``discontinuum_amd.hyperpar`` -- forward-mode Jacobians of raw -> (theta, prior mean, noise), the mean block through
+    the held factor, the prior's curvature, the inversion on the identified subspace -- per site.  Returns one Dataset per
+    model.  ``max_bytes`` bounds the Fisher work area of the whole batch ((P + E + 1) N^2 elements per site), else
+    ``ValueError`` naming the bytes."""
+    from . import hyperpar as hp
+
+    if not models:
+        raise ValueError("hyperparameter_uncertainty_many needs at least one model")
+    for m in models:
+        if not m.is_fitted:
+            raise RuntimeError("The model hasn't been fitted yet, call .fit().")
+    B = len(models)
+    dtype, device = models[0].dtype, torch.device(models[0].device)
+    sites, names = [], set()
+    for m in models:
+        m.model.eval()
+        m.likelihood.eval()
+        x = torch.tensor(m.dm.X, dtype=dtype)
+        with torch.no_grad():
+            if hasattr(m.model, "prepare_eval"):
+                m.model.prepare_eval(x, x)  # no test points: the data-dependent clamps see the training rows
+        name, theta_fn = lower(m.model.covar_module, x.shape[1])
+        names.add((name, x.shape[1]))
+        xd = x.to(device)
+        params = hp.leaves(m)
+        J_theta, J_m, J_noise = hp.jacobians(m, params, x=xd, theta_fn=theta_fn)
+        dirs, rows = hp.noise_directions(J_noise)
+        with torch.no_grad():
+            sites.append(dict(x=x, xd=xd, y=torch.tensor(m.dm.y, dtype=dtype), params=params, J_theta=J_theta, J_m=J_m,
+                              dirs=dirs, rows=rows, theta=theta_fn().detach().to(torch.float64),
+                              mean=m.model.prior_mean(x).detach().to(dtype),
+                              noise=m.likelihood.train_noise(torch.device("cpu"), dtype).detach().reshape(-1)))
+    if len(names) != 1:
+        raise ValueError("hyperparameter_uncertainty_many needs sites of one model family and one input dimension")
+    (name, d), = names
+    sizes = [st["x"].shape[0] for st in sites]
+    n, E = max(sizes), max(st["rows"].shape[0] for st in sites)
+    plan = GPPlan(name, n, d, dtype=dtype, device=device, lookahead=1 if B > 1 else 2, batch=B)
+    if B > 1:
+        plan.set_site_sizes(sizes)
+
+    def slots(ts, width, fill=0.0):
+        out = torch.full((B, width) + tuple(ts[0].shape[1:]), fill, dtype=dtype)
+        for b, t in enumerate(ts):
+            out[b, : t.shape[0]] = t
+        return out
+
+    X = slots([st["x"] for st in sites], n).to(device).contiguous()
+    R = slots([st["y"] - st["mean"] for st in sites], n).to(device).contiguous()
+    Nz = slots([st["noise"] for st in sites], n, 1.0).to(device).contiguous()
+    D = None
+    if E:  # a site with fewer learned noise terms gets zero directions (and zero rows of its Jacobian)
+        D = torch.zeros(B, E, n, dtype=dtype, device=device)
+        for b, st in enumerate(sites):
+            if st["dirs"] is not None:
+                D[b, : st["dirs"].shape[0], : sizes[b]] = st["dirs"].to(dtype)
+    theta = torch.stack([st["theta"] for st in sites])
+    one = (lambda v: v[0].contiguous()) if B == 1 else (lambda v: v)
+    with torch.no_grad():
+        plan.set_inputs(one(X))
+        out = plan.factorize(one(theta), one(R), one(Nz))
+        info = out.reshape(B, -1)[:, _lib.OUT_INFO].cpu()
+        if bool((info != 0).any()):
+            bad = int(torch.nonzero(info)[0])
+            raise RuntimeError(f"site {bad}: matrix not positive definite (Cholesky pivot {int(info[bad])})")
+        F = plan.fisher(one(theta), None if D is None else one(D), max_bytes=max_bytes)
+        F = F.reshape(B, F.shape[-2], F.shape[-1]).to("cpu", torch.float64).numpy()
+    results = []
+    for b, (m, st) in enumerate(zip(models, sites)):
+        rows = np.zeros((E, st["rows"].shape[1]))
+        rows[: st["rows"].shape[0]] = st["rows"]
+        with torch.no_grad():
+            W = plan.whiten(st["J_m"], b) if bool((st["J_m"] != 0).any()) else st["J_m"]
+        F_raw, active = hp.assemble(F[b], np.concatenate([st["J_theta"].numpy(), rows], axis=0),
+                                    W.detach().to("cpu", torch.float64).numpy(), hp._on_clamp(m, st["params"], st["xd"]))
+        H = hp.prior_hessian(m, st["params"]).numpy() if prior else np.zeros_like(F_raw)
+        results.append(hp.summarise(m, st["params"], F_raw, active, H, ci, prior))
+    return results
+
+
+__all__ = ["fit_many", "fit_many_distributed", "predict_many", "hyperparameter_uncertainty_many", "FitManyState"]

@@ -114,6 +114,11 @@ class ExactGPModel(gp.ExactGP):
         """gpytorch's eval mode runs ``forward`` on [X; X*]: the c-clamp then sees the test stages too."""
         self.powerlaw.clamp_c(torch.minimum(train_x[:, STAGE].min(), x[:, STAGE].min()))
 
+    def parameter_clamps(self, train_x):
+        """The data clamps of ``prior_mean`` on the training rows as {parameter name: (lo, hi)} (None: unbounded): a value
+        sitting on one is reset on every call, so the likelihood does not move with it (``hyperpar``)."""
+        return {"powerlaw.b": (1.2, 2.5), "powerlaw.c": (None, float(train_x[:, STAGE].min()) - 1e-6)}
+
 
 class _PowerLawShortcut(MeanShortcut):
     """Host-side form of rating-gp's mean and noise for the marginal likelihood: mu_i = a + b log(s_i - c) and

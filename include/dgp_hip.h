@@ -363,6 +363,33 @@ int dgp_cross_validate(dgp_plan* plan, const int32_t* order_dev, const int32_t* 
                        void* work_dev, size_t work_bytes, double* resid_dev, double* var_dev, double* lpd_dev, int32_t* info_dev,
                        void* stream);
 
+/* Exact FISHER INFORMATION of the hyperparameters from the factorisation the plan holds (after dgp_factorize or dgp_fit_step):
+ * how well the data determine them.  The reference has no counterpart.  For the Gaussian marginal likelihood the expected
+ * information of the covariance parameters is (Mardia & Marshall 1984)
+ *     F_ab = 1/2 tr(K^^-1 D_a K^^-1 D_b) = 1/2 <G_a, G_b>_F,      G_a = T D_a T^T,  T = L^-1,
+ * over P + E DIRECTIONS D_a (symmetric derivative matrices of K^): first the P = dgp_model_ntheta kernel directions
+ * dK/dtheta_p at theta_host (constrained values, as for dgp_fit_step), then E = ndiag diagonal directions diag(d_e) --
+ * derivatives of learned noise terms -- with d_e = diag_dev[site][e][0 .. n) in the plan's dtype (entries beyond a ragged
+ * site's own size are ignored).  0 <= ndiag <= 8; diag_dev may be NULL when ndiag = 0.  Only first derivatives of the
+ * kernel are needed and F is positive semi-definite by construction -- the observed Hessian is neither.
+ *   fisher_dev  [batch][P + E][P + E] doubles whatever the plan's dtype, bitwise symmetric, in un-normalised
+ *               log-likelihood units (the fit step's NLL is not divided by n either).
+ * Passes: all P derivative matrices in one sweep of pair evaluations; per direction V = T D (the prediction's GEMM at width
+ * N; a column scaling of T for a diagonal direction) and the lower triangle of G = V T^T on the MFMA tile cores (128 x 128
+ * direct-to-LDS tiles, 64 x 64 ones while a launch has too few: DGP_OPT_LAUUM64_MAX_TILES; k-tiles last to first); then
+ * the pairwise contraction in double, two stages, fixed order.  (P + E) (4/3) N^3 flop.  No floating-point atomics: bitwise
+ * repeatable; batched plans: gridDim.z = sites, dgp_plan_set_site_sizes respected.  The plan is only read -- no refactoring;
+ * A, T, K^^-1, alpha and every later dgp_predict / dgp_stage_grad answer are bitwise what they were.
+ * work_dev: dgp_fisher_workspace_bytes(plan, ndiag) bytes, 256-byte aligned: per site (P + E + 1) N^2 plan-dtype elements
+ * (the directions' matrices -- D_a lives in G_a's slot until its own product overwrites it -- and V) plus
+ * (N/64)(N/64 + 1)/2 (P + E)^2 doubles of tile partials; 0 for a null plan or a bad ndiag.
+ * DGP_E_ARG (null plan / result, ndiag outside 0 .. 8, ndiag > 0 without diag_dev, misaligned work area), DGP_E_WORKSPACE
+ * (work area missing or too small), DGP_E_STATE (no factorisation in the plan, or the factorisation it holds failed: the
+ * status word of every site is read back, which synchronises the stream) -- all before any launch. */
+size_t dgp_fisher_workspace_bytes(const dgp_plan* plan, int ndiag);
+int dgp_fisher(dgp_plan* plan, const double* theta_host, const void* diag_dev, int ndiag, void* work_dev, size_t work_bytes,
+               double* fisher_dev, void* stream);
+
 /* The posterior of the covariance's ADDITIVE PARTS.  Both fused covariances and every generic one are sums of named terms,
  *   loadest: seasonal + covariates + residual;  rating: shift_1 + shift_2 + bend + base + periodic (the shifts and the bend
  *   carry their gates);  composite: its terms in descriptor order (an unscaled term counts outputscale 1),
