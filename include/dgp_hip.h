@@ -37,6 +37,7 @@ extern "C" {
 #define DGP_E_MODEL (-2)     /* unsupported (model, d) */
 #define DGP_E_WORKSPACE (-3) /* workspace missing or too small */
 #define DGP_E_STATE (-4)     /* call order violated (e.g. predict before factorize) */
+#define DGP_E_FULL (-5)      /* dgp_composite_define: all 64 slots of the process hold other structures */
 
 /* output vector of dgp_fit_step / dgp_factorize, in elements of the plan dtype */
 #define DGP_OUT_NLL 0    /* 1/2 r^T K^^-1 r + 1/2 log|K^| + n/2 log 2 pi */
@@ -75,7 +76,9 @@ int dgp_model_ntheta(int model, int d);
  * (<= 6 terms, Periodic factors on one column).  The constrained hyperparameters follow the same order: per term
  * [outputscale if scaled], per factor [lengthscale: one, or one per column if ard], [period if Periodic]; at most 24.
  * *model_out (>= 16) is then accepted wherever a model id is (dgp_plan_create, dgp_dist_create, dgp_model_ntheta).  An
- * interpreted evaluator: slower per matrix entry than the two fused models, same kernels otherwise. */
+ * interpreted evaluator: slower per matrix entry than the two fused models, same kernels otherwise.
+ * Returns 0, DGP_E_MODEL for a malformed or unsupported description, DGP_E_FULL when the process already holds 64 distinct
+ * structures (an identical description reuses its id and never needs a slot); *model_out is written on success only. */
 int dgp_composite_define(const int* spec_host, int nspec, int* model_out);
 /* padded order N = round_up(n, 128) used by every N x N buffer */
 int64_t dgp_padded_n(int64_t n);

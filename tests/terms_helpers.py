@@ -48,11 +48,15 @@ def term_grams(gram, os_idx):
     return [part(c) for c in range(len(os_idx))]
 
 
-def terms_reference(gram, os_idx, X, r, noise, theta, Xs):
+def terms_reference(gram, parts, X, r, noise, theta, Xs):
     """-> (mean (C, m), cov (C, C, m), scale): the parts' posterior means, their point covariances and the largest TOTAL
-    prior variance max_j k(x*_j, x*_j), the scale every variance / covariance bound is taken against."""
+    prior variance max_j k(x*_j, x*_j), the scale every variance / covariance bound is taken against.  ``parts``: the
+    positions of the parts' outputscales in theta (``outputscale_indices``; the zeroed-outputscale construction), or one
+    Gram function (X1, X2, theta) per part -- a composite with an unscaled term has no outputscale to zero
+    (tests/composite_helpers.py builds its parts from one-term descriptions)."""
     X, r, noise, theta, Xs = (torch.as_tensor(v, dtype=torch.float64) for v in (X, r, noise, theta, Xs))
-    parts = term_grams(gram, os_idx)
+    parts = list(parts)
+    parts = parts if parts and callable(parts[0]) else term_grams(gram, parts)
     L = torch.linalg.cholesky(gram(X, X, theta) + torch.diag(noise))
     alpha = torch.cholesky_solve(r.unsqueeze(1), L).squeeze(1)
     Ks = [g(X, Xs, theta) for g in parts]
