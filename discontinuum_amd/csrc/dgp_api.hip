@@ -140,18 +140,9 @@ static int group_size(int lookahead, int batch, long nbk) {
 }
 
 // workgroups the EARLY inverse launches may occupy (one per CU): they share the GPU with the panel chain
-static int early_wg_cap() {
-  const char* e = getenv("DGP_EARLY_WG_CAP");
-  return e ? atoi(e) : 384;
-}
-#define EARLY_WG_CAP early_wg_cap()
-// compute units those launches leave to the panel chain (0 = none); DGP_EARLY_RESERVED_CUS overrides (tuning only)
-static int early_reserved_cus() {
-  const char* e = getenv("DGP_EARLY_RESERVED_CUS");
-  const int v = e ? atoi(e) : 64;
-  return v < 0 ? 0 : (v > 128 ? 128 : v);
-}
-#define EARLY_RESERVED_CUS early_reserved_cus()
+#define EARLY_WG_CAP 384
+// compute units those launches leave to the panel chain
+#define EARLY_RESERVED_CUS 64
 
 extern "C" {
 
@@ -617,7 +608,7 @@ __global__ __launch_bounds__(256) void finish_kernel(const T* scal, int* info, l
   }
   __syncthreads();
   if (t == 0) {
-    // fp32 plans: the log-determinant (mixed-precision panel, dgp_diag.h) and the quadratic form were accumulated in
+    // fp32 plans: the log-determinant (summed over the diagonal blocks in double, dgp_diag.h) and the quadratic form were accumulated in
     // double and sit unrounded in the scalar block's double slots (elements 2..3 and 4..5); the three terms of the NLL
     // -- which cancel to a small number when the noise is small -- are added in double and rounded once
     double logdet = (double)scal[0], quad = (double)scal[1];
@@ -664,12 +655,22 @@ static int run_potrf(dgp_plan* p, hipStream_t s, int nck = 0, const int* ck = nu
   if (rc) return rc;
   if ((rc = ensure_timing(p)) || (rc = ensure_split(p, s))) return rc;
   const int group = group_size(p->lookahead, p->B, p->N / DGP_TILE_HOST);
-  hipEvent_t* sev = p->timing ? p->sev : nullptr;
+  PotrfObservers obs;
+  obs.syrk_ev = p->timing ? p->sev : nullptr;
+  obs.syrk_pool = p->nsev / 2;
+  obs.nck = nck;
+  obs.ck_blocks = ck;
+  obs.ck_ev = ck_ev;
+  obs.on_ck = on_ck;
+  obs.ck_ctx = ctx;
   if (split_applies(p) && p->sc)
-    return potrf_split<T>((T*)p->A, p->N, (T*)p->Tm, (T*)p->scal, p->info, (T*)p->snap, s, p->sc, p->s2, p->ev, sev, &p->n_syrk,
-                          &p->syrk_flop, nck, ck, ck_ev, on_ck, ctx, split_start(p), group, &p->tune);
-  return potrf<T>((T*)p->A, p->N, (T*)p->Tm, (T*)p->scal, p->info, group, s, p->s2, p->ev, sev, &p->n_syrk, &p->syrk_flop, nck, ck,
-                  ck_ev, on_ck, ctx, batch_of<T>(p));
+    rc = potrf_split<T>((T*)p->A, p->N, (T*)p->Tm, (T*)p->scal, p->info, (T*)p->snap, s, p->sc, p->s2, p->ev, &obs, split_start(p), group,
+                        &p->tune);
+  else
+    rc = potrf<T>((T*)p->A, p->N, (T*)p->Tm, (T*)p->scal, p->info, group, s, p->s2, p->ev, &obs, batch_of<T>(p));
+  p->n_syrk = obs.n_syrk;
+  p->syrk_flop = obs.syrk_flop;
+  return rc;
 }
 template <typename T>
 static int run_trtri(dgp_plan* p, hipStream_t s) {
@@ -722,32 +723,20 @@ static int run_grad(dgp_plan* p, const double* theta, void* dtheta, hipStream_t 
                       (T*)p->gpart, (T*)dtheta, s, batch_of<T>(p), DGP_OUT_LEN, p->pre, p->pre_ready != 0);
 }
 
-// DGP_SOLVE_OVERLAP: 0 = solves in front of lauum on the caller's stream (the order until round 4); 1 (default) = on the bulk
-// stream (lowest priority: the trmv workgroups fill whatever slots lauum's grid leaves); 2 = on the rest stream (highest
-// priority).  Needs the plan's event pool (lookahead >= 1).  Measured on one box in alternating processes
-// (scripts/env_ab.py, wall ms per step, 0 / 1 / 2): 32 x n = 8192 274.3 / 273.8 / 274.4 (lauum itself 81.0 -> 83.3 with the
-// solves beside it: its three workgroups per CU leave a trmv wave no registers, so the solves take slots, not idle
-// resources), 64 x n = 4096 80.56 / 79.30 / 79.59 (-1.6 %), one site n = 8192 11.85 / 11.84 / 11.81; bitwise the same results.
-// By default only for 1024 <= N <= 6144: at the headline size the step gains 0.2 % (below the 1 % bar) while lauum -- the kernel the
-// roofline is quoted on -- reads 3-4 % slower for sharing the GPU (84.8 against 82.4 ms alone, profiles/r05_lauum_three_ways.txt);
-// an explicit DGP_SOLVE_OVERLAP applies to every size.
+// Whether the two solves run BESIDE lauum on the bulk stream (lowest priority: the trmv workgroups fill whatever slots lauum's grid
+// leaves) instead of in front of it on the caller's stream.  Needs the plan's event pool (lookahead >= 1).  Measured on one box in
+// alternating processes (scripts/env_ab.py, wall ms per step, in front / bulk stream / a highest-priority stream of their own):
+// 32 x n = 8192 274.3 / 273.8 / 274.4 (lauum itself 81.0 -> 83.3 with the solves beside it: its three workgroups per CU leave a trmv
+// wave no registers, so the solves take slots, not idle resources), 64 x n = 4096 80.56 / 79.30 / 79.59 (-1.6 %), one site n = 8192
+// 11.85 / 11.84 / 11.81; bitwise the same results.  Hence only for 1024 <= N <= 6144: at the headline size the step gains 0.2 %
+// (below the 1 % bar) while lauum -- the kernel the roofline is quoted on -- reads 3-4 % slower for sharing the GPU (84.8 against
+// 82.4 ms alone, profiles/r05_lauum_three_ways.txt); and not below N = 1024: at the reference's own site size, n = 300, the step is
+// ~0.3 ms of launches and the two cross-stream dependencies cost more than the overlap gains: 0.306 -> 0.334 ms; n = 1024
+// 0.705 -> 0.681, 2048 1.319 -> 1.270, 128 x n = 2048 26.24 -> 25.62.
 template <typename T>
-static int solve_overlap_mode(dgp_plan* p, hipStream_t s, hipStream_t* out) {
-  static const int env = getenv("DGP_SOLVE_OVERLAP") ? atoi(getenv("DGP_SOLVE_OVERLAP")) : -1;
-  // (and not below N = 1024: at the reference's own site size, n = 300, the step is ~0.3 ms of launches and the two cross-stream
-  // dependencies cost more than the overlap gains: 0.306 -> 0.334 ms; n = 1024 0.705 -> 0.681, 2048 1.319 -> 1.270,
-  // 128 x n = 2048 26.24 -> 25.62)
-  const int mode = env >= 0 ? env : ((p->N >= 1024 && p->N <= 6144) ? 1 : 0);
-  if (mode <= 0 || !p->lookahead || !p->ev || p->nev < 2) return 0;
-  if (sizeof(T) == 4 && p->refine) return 0;
-  if (mode == 1 && p->s2) {
-    *out = p->s2;
-    return 1;
-  }
-  StreamSet* st = stream_set(s);
-  if (!st || make_stream(&st->rest, true)) return 0;
-  *out = st->rest;
-  return 2;
+static bool solve_overlap(const dgp_plan* p) {
+  if (p->N < 1024 || p->N > 6144 || !p->lookahead || !p->ev || p->nev < 2 || !p->s2) return false;
+  return !(sizeof(T) == 4 && p->refine);
 }
 
 template <typename T>
@@ -773,14 +762,6 @@ static int fit_step(dgp_plan* p, const double* theta, const void* r, const void*
       TrtriProgress st;
       int rc;
     } ctx{p, {nbk / 2, 3 * nbk / 4, 7 * nbk / 8}, {}, 0};
-    if (const char* e = getenv("DGP_EARLY_CK")) {  // tuning: three checkpoints in sixteenths of the columns
-      int a16 = 8, b16 = 12, c16 = 14;
-      if (sscanf(e, "%d,%d,%d", &a16, &b16, &c16) == 3) {
-        ctx.ck[0] = a16 * nbk / 16;
-        ctx.ck[1] = b16 * nbk / 16;
-        ctx.ck[2] = c16 * nbk / 16;
-      }
-    }
     auto on_ck = [](void* v, int c) {  // runs inside the factorisation's enqueue loop, right after checkpoint c
       Early* e = (Early*)v;
       hipStreamWaitEvent(e->p->s3, e->p->xev[c], 0);
@@ -812,8 +793,8 @@ static int fit_step(dgp_plan* p, const double* theta, const void* r, const void*
   // (the FUSED kernel -- K^^-1 with the gradient contraction in its epilogue, dgp_fused.hip -- needs alpha before it
   // starts: the solves then stay in front of it on the caller's stream)
   const bool fused = with_grad && p->tune.fused_grad && lauum_grad_applies(p->model, p->N, bt);
-  hipStream_t ss = s;
-  const int ov = (with_grad && !fused) ? solve_overlap_mode<T>(p, s, &ss) : 0;
+  const bool ov = with_grad && !fused && solve_overlap<T>(p);
+  hipStream_t ss = ov ? p->s2 : s;
   if (ov) {
     hipEventRecord(p->ev[0], s);
     hipStreamWaitEvent(ss, p->ev[0], 0);

@@ -28,7 +28,8 @@ namespace dgp {
 static constexpr int NB = DGP_TILE;
 static constexpr int SMID_TABLE = 4096;  // covers the XCC | SE | CU id bits of __smid()
 // k-tiles of register prefetch (TileGemm::run<PF>) for the kernels whose operands mostly miss L2
-// (measured at n = 8192: fp64 lauum 2.99 -> 2.87 ms with 2; fp64 trtri gets SLOWER with 2 -- 256 VGPRs; fp32 has room)
+// (measured at n = 8192: fp64 lauum 2.99 -> 2.87 ms with 2; fp64 trtri gets SLOWER with 2 -- 256 VGPRs; fp32 has room).  Only the
+// register-staged core reads it (TileGemm::run<PF>): the 128 x 128 tiles of the direct-to-LDS core prefetch through their ring.
 template <typename T>
 struct Prefetch {
   static constexpr bool F64 = sizeof(T) == 8;
@@ -124,46 +125,48 @@ struct YieldHook {
     yield_refresh(word, (unsigned)(size_t)(dgp_lds_ptr)copy);
   }
 };
-#ifndef DGP_BULK_C_DEFAULT
-#define DGP_BULK_C_DEFAULT 0
-#endif
-#ifndef DGP_COL_C_DEFAULT
-#define DGP_COL_C_DEFAULT 0
-#endif
-// CMODE: how the tile of C moves (dgp_gemm.h::trailing_begin): bit 0 = non-temporal loads / stores (STREAM), bit 1 = 16-byte
-// accesses with a lane-pair swap (WIDE, fp64) -- the bulk update's tiles
-template <typename T, int BM, int BN, bool POLITE = false, int CMODE = 0, int RING = 3>
+template <typename T, int BM, int BN, bool POLITE = false>
 __device__ __forceinline__ void syrk_tile(T* __restrict__ A, long ld, int k, int nk, long row0, long col0,
                                           T* __restrict__ smem, const unsigned* yield_word = nullptr, unsigned me = 0,
                                           const unsigned* yield_copy = nullptr) {
-  using K = TileCore<T, true, true, BM, BN, (BM == 128 && BN == 128) ? Prefetch<T>::SYRK : 1, true, false, RING>;
+  using K = TileCore<T, true, true, BM, BN, (BM == 128 && BN == 128) ? Prefetch<T>::SYRK : 1>;
   using G = typename K::G;
   typename G::acc_t acc[G::MI][G::NI];
   T* C = A + row0 * ld + col0;
   typename G::acc_t keep[G::MI][G::NI];
-  constexpr bool STREAM = (CMODE & 1) != 0, WIDE = (CMODE & 2) != 0;
-  trailing_begin<T, G, K::DMA, STREAM, WIDE>(acc, keep, C, ld);
+  trailing_begin<T, G, K::DMA>(acc, keep, C, ld);
   if constexpr (POLITE)
     K::run_hooked(A + row0 * ld + (long)k * NB, ld, A + col0 * ld + (long)k * NB, ld, nk * (NB / 16), smem, acc, YieldHook{yield_word, me, yield_copy});
   else
     K::run(A + row0 * ld + (long)k * NB, ld, A + col0 * ld + (long)k * NB, ld, nk * (NB / 16), smem, acc);
-  trailing_end<T, G, K::DMA, STREAM, WIDE>(acc, keep, C, ld);
+  trailing_end<T, G, K::DMA>(acc, keep, C, ld);
+}
+// the cut remainder of a launch (SyrkShape): piece `part` of the `split` pieces of the tile at (row0, col0) -- 64 x 128 halves, or
+// 64 x 64 quarters without the strictly upper quadrant of a diagonal tile (register-staged tiles in the ring's LDS)
+template <typename T>
+__device__ __forceinline__ void syrk_cut_tile(T* __restrict__ A, long ld, int k, int nk, long row0, long col0, int split, int part,
+                                              T* __restrict__ smem) {
+  static_assert(TileCore<T, true, true, 64, 128>::SMEM_ELEMS <= TileCore<T, true, true>::SMEM_ELEMS &&
+                    TileCore<T, true, true, 64, 64>::SMEM_ELEMS <= TileCore<T, true, true>::SMEM_ELEMS,
+                "the cut remainder's register-staged tiles must fit the ring's LDS");
+  if (split == 2) {
+    syrk_tile<T, 64, 128>(A, ld, k, nk, row0 + 64 * part, col0, smem);
+  } else {
+    if (row0 == col0 && part == 1) return;  // strictly upper quadrant of a diagonal tile
+    syrk_tile<T, 64, 64>(A, ld, k, nk, row0 + 64 * (part >> 1), col0 + 64 * (part & 1), smem);
+  }
 }
 
-// RING = 2 (experiment, DGP_BULK_RING=2 with the group panel solve): a 32 KB ring, so that a CU with three of these workgroups
-// has 64 KB of LDS free and the diagonal-block kernel (94.5 KB, one workgroup per site, the only chain kernel that must run
-// BESIDE a bulk launch) would fit as soon as ONE of them retires.  Measured: it does not change when that kernel is placed --
-// the second diagonal block of a group still waits for the bulk launch to drain (2.9 ms at 64 x n = 4096 with either ring,
-// profiles/r05_experiments_group_gemm.txt), and two bulk workgroups per CU (DGP_BULK_PAD_BATCH) do not either
-template <typename T, bool POLITE = false, int CMODE = 0, int RING = 3>
+// (the ring stays at three chunks: a 32 KB ring of two, which leaves a CU with three of these workgroups 64 KB of LDS for the
+// 94.5 KB diagonal-block kernel as soon as ONE of them retires, does not change when that kernel is placed -- the second diagonal
+// block of a group still waits for the bulk launch to drain, 2.9 ms at 64 x n = 4096 with either ring,
+// profiles/r05_experiments_group_gemm.txt -- and neither do two bulk workgroups per CU)
+template <typename T, bool POLITE = false>
 __global__ __launch_bounds__(256, (TileCore<T, true, true>::OCC)) void syrk_kernel(T* __restrict__ A, long ld, int k, int nk, int jbeg, int nfull,
                                                                                    int split, long bs, int nt = 0, int super = 0,
                                                                                    const unsigned* yield_word = nullptr) {
   A = site(A, bs);
-  __shared__ T smem[TileCore<T, true, true, 128, 128, 1, true, false, RING>::SMEM_ELEMS];
-  static_assert(TileCore<T, true, true, 64, 128>::SMEM_ELEMS <= TileCore<T, true, true, 128, 128, 1, true, false, RING>::SMEM_ELEMS &&
-                    TileCore<T, true, true, 64, 64>::SMEM_ELEMS <= TileCore<T, true, true, 128, 128, 1, true, false, RING>::SMEM_ELEMS,
-                "the cut remainder's register-staged tiles must fit the ring's LDS");
+  __shared__ T smem[TileCore<T, true, true>::SMEM_ELEMS];
   __shared__ unsigned yield_copy[POLITE ? 4 * 64 : 1];  // per wave: its copy of the yield word (YieldHook)
   const int b = (int)blockIdx.x;
   int bi, bj;
@@ -171,21 +174,14 @@ __global__ __launch_bounds__(256, (TileCore<T, true, true>::OCC)) void syrk_kern
     // all tiles cost the same: remap freely -- consecutive logical tiles on one XCD; `super` picks the logical order
     if (super > 0) super_decode(xcd_remap(b, nfull), nt, super, bi, bj);
     else tri_decode(xcd_remap(b, nfull), bi, bj);
-    syrk_tile<T, 128, 128, POLITE, CMODE, RING>(A, ld, k, nk, (long)(bi + jbeg) * NB, (long)(bj + jbeg) * NB, smem, yield_word, POLITE ? cu_code() : 0u,
+    syrk_tile<T, 128, 128, POLITE>(A, ld, k, nk, (long)(bi + jbeg) * NB, (long)(bj + jbeg) * NB, smem, yield_word, POLITE ? cu_code() : 0u,
                                    yield_copy + (POLITE ? 64 * __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6) : 0));
     return;
   }
   const int sub = b - nfull;
   if (super > 0) super_decode(nfull + sub / split, nt, super, bi, bj);
   else tri_decode(nfull + sub / split, bi, bj);
-  const long row0 = (long)(bi + jbeg) * NB, col0 = (long)(bj + jbeg) * NB;
-  const int part = sub % split;
-  if (split == 2) {
-    syrk_tile<T, 64, 128, false, CMODE>(A, ld, k, nk, row0 + 64 * part, col0, smem);
-  } else {
-    if (bi == bj && part == 1) return;  // strictly upper quadrant of a diagonal tile
-    syrk_tile<T, 64, 64, false, CMODE>(A, ld, k, nk, row0 + 64 * (part >> 1), col0 + 64 * (part & 1), smem);
-  }
+  syrk_cut_tile<T>(A, ld, k, nk, (long)(bi + jbeg) * NB, (long)(bj + jbeg) * NB, split, sub % split, smem);
 }
 
 // The selectors' defaults (Tuning, dgp_internal.h).  syrk_slots: 512 measured best for both precisions -- with the
@@ -204,7 +200,7 @@ const Tuning& default_tuning() {
     // launch what it cost alone (lauum 81.0 -> 85.9 ms for 5.8 ms of gram_grad): it does not hide under the other
     // workgroups' MFMAs
     v.fused_grad = getenv("DGP_FUSED_GRAD") ? atoi(getenv("DGP_FUSED_GRAD")) : 0;
-    // off: built, parity-green (tests/test_gpu_stages.py with the option on) and measured neutral -- 64 x n = 4096 80.8 / 80.3 ms
+    // off: built, parity-green (tests/test_gpu_bigtile.py, tests/test_gpu_fullsize.py with the option on) and measured neutral -- 64 x n = 4096 80.8 / 80.3 ms
     // per step, 32 x n = 8192 280.2 / 280.1, 128 x n = 2048 26.1 / 26.0 (scripts/env_ab.py, one box): the factorisation's wall
     // time is the SUM of its full-GPU kernels at their rates whichever way the chain is cut (EXPERIMENTS.md, round 5)
     v.group_gemm = getenv("DGP_GROUP_GEMM") ? atoi(getenv("DGP_GROUP_GEMM")) : 0;
@@ -282,14 +278,14 @@ __global__ __launch_bounds__(256, 2) void syrk_col_kernel(T* __restrict__ A, lon
 
 // the same columns in 128 x 128 tiles of the direct-to-LDS core, for batched plans: there the group's column update is
 // thousands of tiles and not latency-critical (the sites fill each other's gaps); bitwise the same sums
-template <typename T, int CMODE = 0>
+template <typename T>
 __global__ __launch_bounds__(256, (TileCore<T, true, true>::OCC)) void syrk_col128_kernel(T* __restrict__ A, long ld, int k, int nk, int jcol,
                                                                                           int nbk, int ncol, long bs) {
   __shared__ T smem[TileCore<T, true, true>::SMEM_ELEMS];
   A += (long)((int)blockIdx.z / ncol) * bs;
   const int jc = jcol + (int)blockIdx.z % ncol;
   if ((int)blockIdx.x >= nbk - jc) return;  // the later columns are shorter
-  syrk_tile<T, 128, 128, false, CMODE>(A, ld, k, nk, (long)(jc + (int)blockIdx.x) * NB, (long)jc * NB, smem);
+  syrk_tile<T, 128, 128>(A, ld, k, nk, (long)(jc + (int)blockIdx.x) * NB, (long)jc * NB, smem);
 }
 
 // UPDATE of a column STRIP (dgp_schedule.h; the batched left-looking schedule): block columns [c0, c0 + ncol), block rows
@@ -306,9 +302,6 @@ template <typename T>
 __global__ __launch_bounds__(256, (TileCore<T, true, true>::OCC)) void syrk_strip_kernel(T* __restrict__ A, long ld, int k, int nk, int c0, int ncol,
                                                                                          int rrect, int ntri, int nt, int nfull, int split, long bs) {
   __shared__ T smem[TileCore<T, true, true>::SMEM_ELEMS];
-  static_assert(TileCore<T, true, true, 64, 128>::SMEM_ELEMS <= TileCore<T, true, true>::SMEM_ELEMS &&
-                    TileCore<T, true, true, 64, 64>::SMEM_ELEMS <= TileCore<T, true, true>::SMEM_ELEMS,
-                "the cut remainder's register-staged tiles must fit the ring's LDS");
   const int b = (int)blockIdx.x;
   const int l = b < nfull ? xcd_remap(b, nfull) : nfull + (b - nfull) / split;  // < sites x nt (the grid: nfull + split (sites nt - nfull))
   const int t = l % nt;
@@ -326,21 +319,11 @@ __global__ __launch_bounds__(256, (TileCore<T, true, true>::OCC)) void syrk_stri
     syrk_tile<T, 128, 128>(A, ld, k, nk, row0, col0, smem);
     return;
   }
-  const int part = (b - nfull) % split;
-  if (split == 2) {
-    syrk_tile<T, 64, 128>(A, ld, k, nk, row0 + 64 * part, col0, smem);
-  } else {
-    if (row0 == col0 && part == 1) return;  // strictly upper quadrant of a diagonal tile
-    syrk_tile<T, 64, 64>(A, ld, k, nk, row0 + 64 * (part >> 1), col0 + 64 * (part & 1), smem);
-  }
+  syrk_cut_tile<T>(A, ld, k, nk, row0, col0, split, (b - nfull) % split, smem);
 }
 
-// launch the LDS-resident diagonal-block kernel (needs > 64 KB of dynamic LDS: opt in once per instantiation).
-// DGP_F32_DIAG64=1 factors the diagonal blocks of fp32 matrices with the MIXED-PRECISION instantiation (block promoted
-// to fp64 in LDS, dgp_diag.h).  Off by default -- measured over 18 matrices (profiles/r03_fp32_error_sources.txt): once
-// the trailing updates sum from zero (dgp_gemm.h::trailing_begin) the fp64 block changes neither the log-determinant
-// nor the quadratic form's error (which is then set by L being STORED in fp32), and costs 2 % (n = 16384) to 12 %
-// (n = 2048) of a fit step.  Kept as a measurement knob.
+// The LDS-resident diagonal-block kernel (launch_diag) and the split chain's crit_kernel need > 64 KB of dynamic LDS: an opt-in, once
+// per instantiation and device.
 // Runs `configure` once per device (the calling thread's current one) UNDER the lock and marks the device configured only
 // when it returned hipSuccess: a second host thread that drives the same device (thread ranks, two Python threads with a
 // plan each) either finds the opt-in done or waits for it -- it can never launch with > 64 KB of dynamic LDS before the
@@ -359,16 +342,12 @@ struct DeviceOnce {
     return e;
   }
 };
-static bool f32_diag64() {
-  static const bool v = [] {
-    const char* e = getenv("DGP_F32_DIAG64");
-    return e ? atoi(e) != 0 : false;
-  }();
-  return v;
-}
 // single-site plans: the bulk update's waves yield their CU to the diagonal-block kernel (dgp_common.h: yield_if_asked)
 static bool yields(const Batch& bt) { return bt.B == 1 && bt.tuning().chain_yield != 0; }
-// one bulk launch of the trailing update (SyrkShape), polite or not
+// lower-triangle tile count of m block columns, and the flops of one 128 x 128 tile per 128 of k
+static inline unsigned tri(int m) { return (unsigned)(m * (m + 1) / 2); }
+static constexpr double TILE_FLOP = 2.0 * NB * NB * NB;
+// one bulk launch of the trailing update (SyrkShape), polite (single-site plans) or plain
 template <typename T>
 static void launch_bulk(T* A, long N, int k, int nk, int jbeg, const SyrkShape& sh, int nt, int* info, hipStream_t s, const Batch& bt) {
   const int nbk = (int)(N / NB);
@@ -378,63 +357,14 @@ static void launch_bulk(T* A, long N, int k, int nk, int jbeg, const SyrkShape& 
   // panel of a pair at n = 8192: trsm 59 -> 33 us, column update 77 -> 30).  Measured (step, ms): n = 6144 6.72 -> 6.69,
   // 8192 11.93 -> 11.89, 12288 33.3 -> 32.7, 16384 fp64 71.6 -> 70.9, 16384 fp32 38.95 -> 38.55; n >= 24576 (bound by the
   // bulk launches) and n <= 4096 (one round of tiles anyway): nothing or slightly worse -- hence the window.
-  static const int pad_env = getenv("DGP_BULK_LDS_PAD") ? std::min(16384, std::max(0, atoi(getenv("DGP_BULK_LDS_PAD")))) : 14336;
   // (batched plans: 64 x 4096 797 -> 789 fits/s, 32 x 8192 115.6 -> 115.0, 128 x 2048 no change -- their chain kernels are wide enough)
-  const size_t pad = (bt.B == 1 && nbk >= 40 && nbk <= 160) ? (size_t)pad_env : 0;
-  // DGP_BULK_C: how the tiles of C move -- 0 plain 8-byte accesses (the form until round 4), 1 non-temporal, 2 16-byte accesses with
-  // a lane-pair swap (fp64), 3 both.  Measured on the tile alone (scripts/syrk_persist.hip, fp64, TFLOP/s at K = 512 / 256): 64.0 /
-  // 52.7, 68.6 / 60.9, 69.7 / 62.2, 70.6 / 64.1 -- the read-modify-write of C, not the dispatch or the ring fill, is what
-  // separates a short-K tile from the long-K rate (74.4 with no C traffic).  In situ every variant ties or LOSES (default 0):
-  // the non-temporal form moves the bulk launches' sum 79.2 -> 75.7 ms and the step not at all; the 16-byte form needs a
-  // lane-pair swap on 128 live accumulator registers, which this kernel (168 registers, 20 already spilled) only affords by
-  // spilling 99 registers around every tile (400 bytes of scratch per lane -- as much traffic as the tile itself): bulk sum
-  // 77.3 -> 82.4 ms, step 275.4 -> 280.2 (32 x n = 8192), 11.90 -> 12.55 ms (one site).  EXPERIMENTS.md round 5.
-  static const int cmode_env = getenv("DGP_BULK_C") ? atoi(getenv("DGP_BULK_C")) & 3 : DGP_BULK_C_DEFAULT;
-  const int cmode = sizeof(T) == 8 ? cmode_env : (cmode_env & 1);  // (fp32 tiles read C in the epilogue: no wide form)
-  const unsigned* yw = reinterpret_cast<const unsigned*>(info + CHAIN_YIELD);
-  // batched plans on the group panel solve: the 32 KB ring (syrk_kernel: RING) when DGP_BULK_RING=2 (experiment)
-  static const int ring_env = getenv("DGP_BULK_RING") ? atoi(getenv("DGP_BULK_RING")) : 3;
-  static const int pad_batch = getenv("DGP_BULK_PAD_BATCH") ? std::min(65536, std::max(0, atoi(getenv("DGP_BULK_PAD_BATCH")))) : 0;  // experiment
-  if (bt.B >= 4 && bt.tuning().group_gemm && bt.W != nullptr && ring_env == 2) {
-    syrk_kernel<T, false, 0, 2><<<grid, 256, (size_t)pad_batch, s>>>(A, N, k, nk, jbeg, sh.nfull, sh.split, bt.ws, nt, bt.tuning().syrk_super, nullptr);
-    return;
-  }
-  const size_t lds_pad = (bt.B >= 4 && pad_batch > 0) ? (size_t)pad_batch : pad;
-#define DGP_LAUNCH_BULK(POLITE_, CM_)                                                                                              \
-  syrk_kernel<T, POLITE_, CM_><<<grid, 256, lds_pad, s>>>(A, N, k, nk, jbeg, sh.nfull, sh.split, bt.ws, nt, bt.tuning().syrk_super, \
-                                                         POLITE_ ? yw : nullptr)
-  if (yields(bt)) {
-    switch (cmode) {
-      case 1: DGP_LAUNCH_BULK(true, 1); break;
-      case 2: DGP_LAUNCH_BULK(true, 2); break;
-      case 3: DGP_LAUNCH_BULK(true, 3); break;
-      default: DGP_LAUNCH_BULK(true, 0);
-    }
-  } else {
-    switch (cmode) {
-      case 1: DGP_LAUNCH_BULK(false, 1); break;
-      case 2: DGP_LAUNCH_BULK(false, 2); break;
-      case 3: DGP_LAUNCH_BULK(false, 3); break;
-      default: DGP_LAUNCH_BULK(false, 0);
-    }
-  }
-#undef DGP_LAUNCH_BULK
-}
-template <typename TS, typename TC>
-static void launch_diag_as(TS* A, long N, long k0, TS* Tinv, TS* logdet, int* info, hipStream_t s, Batch bt, bool init,
-                           double* logdet_hi, int done_index, int done_value) {
-  // the opt-in for > 64 KB of dynamic LDS belongs to the CURRENT DEVICE's function object: keyed by device, so that a
-  // process that drives plans on several GPUs opts in on each (a failure surfaces as the launch error below it)
-  const size_t bytes = potrf_diag_fast_smem<TC>();
-  static DeviceOnce configured;
-  // (a failed opt-in is retried by the next call and surfaces here as the launch error: invalid value for > 64 KB)
-  (void)configured.run([&] {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&potrf_diag_fast_kernel<TS, TC>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-  });
-  potrf_diag_fast_kernel<TS, TC><<<dim3(1, 1, (unsigned)bt.B), 256, bytes, s>>>(
-      A, N, k0, Tinv, logdet, info, bt.ws, bt.ws * (long)sizeof(TS) / (long)sizeof(int), init ? 1 : 0, POTRF_INFO_INTS, logdet_hi,
-      done_index, done_value, yields(bt) ? CHAIN_YIELD : -1);
+  const size_t lds_pad = (bt.B == 1 && nbk >= 40 && nbk <= 160) ? 14336 : 0;
+  const int super = bt.tuning().syrk_super;
+  if (yields(bt))
+    syrk_kernel<T, true><<<grid, 256, lds_pad, s>>>(A, N, k, nk, jbeg, sh.nfull, sh.split, bt.ws, nt, super,
+                                                    reinterpret_cast<const unsigned*>(info + CHAIN_YIELD));
+  else
+    syrk_kernel<T, false><<<grid, 256, lds_pad, s>>>(A, N, k, nk, jbeg, sh.nfull, sh.split, bt.ws, nt, super, nullptr);
 }
 // the fp32 plans' unrounded log-determinant lives in the scalar block right behind (log-det, quad): element 2..3 as ONE double
 template <typename T>
@@ -444,10 +374,18 @@ static double* logdet_hi_slot(T* logdet) {
 template <typename T>
 static void launch_diag(T* A, long N, long k0, T* Tinv, T* logdet, int* info, hipStream_t s, Batch bt, bool init = false,
                         int done_index = -1, int done_value = 0) {
-  if (sizeof(T) == 4 && f32_diag64())
-    launch_diag_as<T, double>(A, N, k0, Tinv, logdet, info, s, bt, init, logdet_hi_slot(logdet), done_index, done_value);
-  else
-    launch_diag_as<T, T>(A, N, k0, Tinv, logdet, info, s, bt, init, logdet_hi_slot(logdet), done_index, done_value);
+  // the opt-in for > 64 KB of dynamic LDS belongs to the CURRENT DEVICE's function object: keyed by device, so that a
+  // process that drives plans on several GPUs opts in on each (a failure surfaces as the launch error below it)
+  const size_t bytes = potrf_diag_fast_smem<T>();
+  static DeviceOnce configured;
+  // (a failed opt-in is retried by the next call and surfaces here as the launch error: invalid value for > 64 KB)
+  (void)configured.run([&] {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&potrf_diag_fast_kernel<T>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  });
+  potrf_diag_fast_kernel<T><<<dim3(1, 1, (unsigned)bt.B), 256, bytes, s>>>(
+      A, N, k0, Tinv, logdet, info, bt.ws, bt.ws * (long)sizeof(T) / (long)sizeof(int), init ? 1 : 0, POTRF_INFO_INTS,
+      logdet_hi_slot(logdet), done_index, done_value, yields(bt) ? CHAIN_YIELD : -1);
 }
 
 // ---- the group's panel solve as ONE GEMM (round 5; batched plans) ---------------------------------------------------------
@@ -462,7 +400,7 @@ static void launch_diag(T* A, long N, long k0, T* Tinv, T* logdet, int* info, hi
 // -- the same flops (G (G + 1) / 2 tile products of K = 128 per row tile) in ONE launch of 128 x 128 tiles on the direct-to-LDS
 // core with k-ranges of 128 .. 128 G, in place (column block j is written after every product that reads it; j descends).
 // Not bitwise the panel-by-panel chain (a different association of the same sums): batched plans against single-site plans
-// agree to rounding, ~1e-13 relative in fp64 (tests/test_gpu_stages.py, test_gpu_headline_shape.py hold 1e-11).
+// agree to rounding, ~1e-13 relative in fp64 (tests/test_gpu_bigtile.py, tests/test_gpu_fullsize.py, test_gpu_headline_shape.py hold 1e-11).
 template <typename T>
 __global__ __launch_bounds__(256, (TileCore<T, true, true>::OCC)) void trsm_group_kernel(T* __restrict__ A, const T* __restrict__ Tm, long ld,
                                                                                          int k0, int G, long bs) {
@@ -497,7 +435,7 @@ static void trtri_group(const T* L, T* Tm, T* W, long N, int k0, int G, hipStrea
 // round differently, within the same bounds.
 template <typename T>
 static int potrf_scheduled(T* A, long N, T* Tinv, T* logdet, int* info, int G, hipStream_t s, hipStream_t s2, hipEvent_t* ev,
-                           hipEvent_t* syrk_ev, int* n_syrk, double* syrk_flop, const Batch& bt) {
+                           PotrfObservers* obs, const Batch& bt) {
   const int nbk = (int)(N / NB);
   sched::Cut cut;
   cut.sweep = bt.tuning().potrf_sweep;
@@ -508,10 +446,8 @@ static int potrf_scheduled(T* A, long N, T* Tinv, T* logdet, int* info, int G, h
   const std::vector<sched::Op> ops = sched::left_looking(nbk, G, cut);
   if (!sched::check(ops, nbk).empty()) return (int)hipErrorInvalidValue;  // (a generator bug: never run an unchecked schedule)
   const unsigned Bz = (unsigned)bt.B;
-  const double tile_flop = 2.0 * NB * NB * NB;
   hipStream_t st[2] = {s, s2};
-  int ns = 0, nsync = 0;
-  double flop = 0.0;
+  int nsync = 0;
   for (const sched::Op& o : ops) {
     hipStream_t so = st[o.stream];
     switch (o.kind) {
@@ -522,8 +458,7 @@ static int potrf_scheduled(T* A, long N, T* Tinv, T* logdet, int* info, int G, h
         break;
       case sched::UPDATE: {
         const long nt = sched::update_tiles(o);
-        const bool timed = syrk_ev != nullptr && ns < nbk;  // (the pool holds 2 nbk events)
-        if (timed) hipEventRecord(syrk_ev[2 * ns], so);
+        const bool timed = obs->bulk_begin(so);  // (this schedule counts the launches it times, as many as the event pool holds)
         {
           // (a sweep of the whole trailing triangle is the strip of all remaining columns: its triangle only, row by row)
           const SyrkShape sh((int)(nt * bt.B), bt.tuning().potrf_slots);
@@ -531,11 +466,7 @@ static int potrf_scheduled(T* A, long N, T* Tinv, T* logdet, int* info, int G, h
           syrk_strip_kernel<T><<<dim3(sh.grid, 1, 1), 256, 0, so>>>(A, N, o.ka, o.kb - o.ka, o.c0, ncol, std::max(o.r0, o.c1), h * (h + 1) / 2, (int)nt,
                                                                      sh.nfull, sh.split, bt.ws);
         }
-        if (timed) {
-          hipEventRecord(syrk_ev[2 * ns + 1], so);
-          flop += tile_flop * (double)nt * (o.kb - o.ka) * bt.B;
-          ++ns;
-        }
+        if (timed) obs->bulk_end(so, TILE_FLOP * (double)nt * (o.kb - o.ka) * bt.B);
         break;
       }
       case sched::PANELS:
@@ -551,59 +482,39 @@ static int potrf_scheduled(T* A, long N, T* Tinv, T* logdet, int* info, int G, h
         break;
     }
   }
-  if (n_syrk) *n_syrk = ns;
-  if (syrk_flop) *syrk_flop = flop;
   return (int)hipGetLastError();
 }
 // where the schedule above applies: batched plans (the sites fill each other's gaps; one site keeps pairs, the split chain and
 // the early inverse), groups of at least 4 panels, no checkpoints, no hand-over
-static bool scheduled_applies(const Batch& bt, long nbk, int elem, int G, int nck, int q_stop, const PotrfCarry* carry, hipStream_t s2, hipEvent_t* ev) {
+static bool scheduled_applies(const Batch& bt, long nbk, int elem, int G, int nck, int q_stop, hipStream_t s2, hipEvent_t* ev) {
   const int mode = bt.tuning().potrf_schedule < 0 ? potrf_schedule_auto(bt.B, nbk, elem) : bt.tuning().potrf_schedule;
-  return bt.B >= 4 && mode != 0 && G >= 4 && nbk > G && nck == 0 && q_stop < 0 && carry == nullptr && s2 != nullptr && ev != nullptr;
+  return bt.B >= 4 && mode != 0 && G >= 4 && nbk > G && nck == 0 && q_stop < 0 && s2 != nullptr && ev != nullptr;
 }
 
 template <typename T>
 int potrf(T* A, long N, T* Tinv, T* logdet, int* info, int lookahead, hipStream_t s, hipStream_t s2, hipEvent_t* ev,
-          hipEvent_t* syrk_ev, int* n_syrk, double* syrk_flop, int nck, const int* ck_blocks, hipEvent_t* ck_ev,
-          void (*on_ck)(void*, int), void* ck_ctx, Batch bt, int q_stop, PotrfCarry* carry) {
+          PotrfObservers* obs, Batch bt, int q_stop) {
   const int nbk = (int)(N / NB);
-  // checkpoint c: recorded on s once the first ck_blocks[c] block columns of L are final (every schedule records
-  // every checkpoint, at the latest when the factorisation is complete)
-  int ck_next = carry ? carry->ck_next : 0;
-  auto checkpoint = [&](int cols_final) {
-    while (ck_next < nck && ck_blocks[ck_next] <= cols_final) {
-      hipEventRecord(ck_ev[ck_next], s);
-      if (on_ck) on_ck(ck_ctx, ck_next);  // the caller enqueues its dependent work NOW, not after the whole schedule
-      ++ck_next;
-    }
-  };
-  int ns = 0;
-  double flop = 0.0;
+  PotrfObservers none;
+  if (!obs) obs = &none;
+  const int nck = obs->nck;
   const unsigned Bz = (unsigned)bt.B;
-  auto tri = [](int m) { return (unsigned)(m * (m + 1) / 2); };
-  const double tile_flop = 2.0 * NB * NB * NB;
   if (!lookahead || nbk < 4 || s2 == nullptr || ev == nullptr) {
     for (int k = 0; k < nbk; ++k) {
       launch_diag<T>(A, N, (long)k * NB, Tinv, logdet, info, s, bt, k == 0);
       if (k + 1 < nbk) {
         trsm_kernel<T><<<dim3(2 * (nbk - k - 1), 1, Bz), 256, 0, s>>>(A, Tinv, N, k, bt.ws);
-        if (syrk_ev) hipEventRecord(syrk_ev[2 * ns], s);
-        {
-          const SyrkShape sh((int)tri(nbk - k - 1), bt.tuning().syrk_slots / bt.B);
-          syrk_kernel<T><<<dim3(sh.grid, 1, Bz), 256, 0, s>>>(A, N, k, 1, k + 1, sh.nfull, sh.split, bt.ws, nbk - k - 1, bt.tuning().syrk_super);  // (same stream as the chain: nothing to yield to)
-        }
-        if (syrk_ev) hipEventRecord(syrk_ev[2 * ns + 1], s);
-        flop += tile_flop * tri(nbk - k - 1) * bt.B;
-        ++ns;
+        obs->bulk_begin(s);
+        const SyrkShape sh((int)tri(nbk - k - 1), bt.tuning().syrk_slots / bt.B);
+        syrk_kernel<T><<<dim3(sh.grid, 1, Bz), 256, 0, s>>>(A, N, k, 1, k + 1, sh.nfull, sh.split, bt.ws, nbk - k - 1, bt.tuning().syrk_super);  // (same stream as the chain: nothing to yield to)
+        obs->bulk_end(s, TILE_FLOP * tri(nbk - k - 1) * bt.B);
       }
     }
-    checkpoint(nbk);
-    if (n_syrk) *n_syrk = ns;
-    if (syrk_flop) *syrk_flop = flop;
+    obs->checkpoint(nbk, s);
     return (int)hipGetLastError();
   }
-  if (scheduled_applies(bt, nbk, (int)sizeof(T), lookahead, nck, q_stop, carry, s2, ev))
-    return potrf_scheduled<T>(A, N, Tinv, logdet, info, lookahead > 8 ? 8 : lookahead, s, s2, ev, syrk_ev, n_syrk, syrk_flop, bt);
+  if (scheduled_applies(bt, nbk, (int)sizeof(T), lookahead, nck, q_stop, s2, ev))
+    return potrf_scheduled<T>(A, N, Tinv, logdet, info, lookahead > 8 ? 8 : lookahead, s, s2, ev, obs, bt);
   {
     // GROUP-AHEAD schedule.  Group q = G consecutive panels (G = 2: pairs, for one site; G = 4 for batched plans,
     // where the chain is shared by the batch and the bulk update gains from K = 512).  The chain on stream s factors
@@ -629,31 +540,17 @@ int potrf(T* A, long N, T* Tinv, T* logdet, int* info, int lookahead, hipStream_
       const int k0 = G * q, ncol = nbk - k0 < G ? nbk - k0 : G;
       if (q >= 2) hipStreamWaitEvent(s, U[q - 2], 0);  // bulk(q-2) exists whenever chain(q) does
       if (q >= 1) {
-        static const int col128 = getenv("DGP_COL128") ? atoi(getenv("DGP_COL128")) : 4;  // batch size from which the group's columns use 128-tiles
-        if (bt.B >= col128) {
-          // DGP_COL_C: the group's look-ahead column update likewise (its tiles ARE re-read soon, by the chain: only the wide form, 2, is a candidate)
-          static const int ccol = getenv("DGP_COL_C") ? atoi(getenv("DGP_COL_C")) & 3 : DGP_COL_C_DEFAULT;
-          const dim3 cgrid(nbk - k0, 1, ncol * Bz);
-          switch (sizeof(T) == 8 ? ccol : (ccol & 1)) {
-            case 1: syrk_col128_kernel<T, 1><<<cgrid, 256, 0, s>>>(A, N, k0 - G, G, k0, nbk, ncol, bt.ws); break;
-            case 2: syrk_col128_kernel<T, 2><<<cgrid, 256, 0, s>>>(A, N, k0 - G, G, k0, nbk, ncol, bt.ws); break;
-            case 3: syrk_col128_kernel<T, 3><<<cgrid, 256, 0, s>>>(A, N, k0 - G, G, k0, nbk, ncol, bt.ws); break;
-            default: syrk_col128_kernel<T, 0><<<cgrid, 256, 0, s>>>(A, N, k0 - G, G, k0, nbk, ncol, bt.ws);
-          }
-        }
+        if (bt.B >= 4)  // batched plans: the group's columns in 128-tiles (syrk_col128_kernel)
+          syrk_col128_kernel<T><<<dim3(nbk - k0, 1, ncol * Bz), 256, 0, s>>>(A, N, k0 - G, G, k0, nbk, ncol, bt.ws);
         else syrk_col_kernel<T><<<dim3(2 * (nbk - k0), 2, ncol * Bz), 256, 0, s>>>(A, N, k0 - G, G, k0, nbk, ncol, bt.ws);
       }
       if (q >= 1 && k0 + G < nbk) {  // bulk(q-1): columns >= G(q+1) exist
         hipEventRecord(P[q - 1], s);
         hipStreamWaitEvent(s2, P[q - 1], 0);
-        if (syrk_ev) hipEventRecord(syrk_ev[2 * ns], s2);
-        {
-          const SyrkShape sh((int)tri(nbk - k0 - G), bt.tuning().syrk_slots / bt.B);
-          launch_bulk<T>(A, N, k0 - G, G, k0 + G, sh, nbk - k0 - G, info, s2, bt);
-        }
-        if (syrk_ev) hipEventRecord(syrk_ev[2 * ns + 1], s2);
-        flop += (double)G * tile_flop * tri(nbk - k0 - G) * bt.B;
-        ++ns;
+        obs->bulk_begin(s2);
+        const SyrkShape sh((int)tri(nbk - k0 - G), bt.tuning().syrk_slots / bt.B);
+        launch_bulk<T>(A, N, k0 - G, G, k0 + G, sh, nbk - k0 - G, info, s2, bt);
+        obs->bulk_end(s2, (double)G * TILE_FLOP * tri(nbk - k0 - G) * bt.B);
         hipEventRecord(U[q - 1], s2);
       }
       // the group's panel solve as one GEMM (trsm_group_kernel): batches from 4 sites (the chain is then wide enough to be
@@ -668,23 +565,16 @@ int potrf(T* A, long N, T* Tinv, T* logdet, int* info, int lookahead, hipStream_
         if (h >= 1) syrk_col_kernel<T><<<dim3(2 * (kend - k), 2, Bz), 256, 0, s>>>(A, N, k0, h, k, kend, 1, bt.ws);
         launch_diag<T>(A, N, (long)k * NB, Tinv, logdet, info, s, bt, k == 0);
         if (k + 1 < kend) trsm_kernel<T><<<dim3(2 * (kend - k - 1), 1, Bz), 256, 0, s>>>(A, Tinv, N, k, bt.ws);
-        if (!group_gemm) checkpoint(k + 1);
+        if (!group_gemm) obs->checkpoint(k + 1, s);
       }
       if (group_gemm) {
         trtri_group<T>(A, Tinv, (T*)bt.W, N, k0, G, s, bt);
         trsm_group_kernel<T><<<dim3((unsigned)(nbk - k0 - G), 1, Bz), 256, 0, s>>>(A, Tinv, N, k0, G, bt.ws);
-        checkpoint(k0 + G);
+        obs->checkpoint(k0 + G, s);
       }
     }
     // bulk(q) exists for q <= Q-3 and chain(q+2) has waited on every one of them: s is joined
-    if (Qrun == Q) checkpoint(nbk);
-    if (carry) {
-      carry->ck_next = ck_next;
-      carry->ns = ns;
-      carry->flop = flop;
-    }
-    if (n_syrk) *n_syrk = ns;
-    if (syrk_flop) *syrk_flop = flop;
+    if (Qrun == Q) obs->checkpoint(nbk, s);
     return (int)hipGetLastError();
   }
 }
@@ -900,8 +790,7 @@ __global__ __launch_bounds__(256, 2) void chain_col_kernel(T* __restrict__ A, lo
 // it like every other chain kernel -- and the split chain takes over from there.
 template <typename T>
 int potrf_split(T* A, long N, T* Tinv, T* logdet, int* info, T* snap, hipStream_t s, hipStream_t c2, hipStream_t s2,
-                hipEvent_t* ev /* 3 nbk */, hipEvent_t* syrk_ev, int* n_syrk, double* syrk_flop, int nck, const int* ck_blocks,
-                hipEvent_t* ck_ev, void (*on_ck)(void*, int), void* ck_ctx, int k_start, int G_old, const Tuning* tune) {
+                hipEvent_t* ev /* 3 nbk */, PotrfObservers* obs, int k_start, int G_old, const Tuning* tune) {
   const int nbk = (int)(N / NB);
   Batch bt;
   bt.tune = tune;
@@ -909,8 +798,9 @@ int potrf_split(T* A, long N, T* Tinv, T* logdet, int* info, T* snap, hipStream_
   if (k_start < 0) k_start = 0;
   k_start = (k_start + G_old - 1) / G_old * G_old;  // a group boundary of the schedule that runs first (G_old is even)
   if (k_start + 4 > nbk)  // nothing left for the split chain
-    return potrf<T>(A, N, Tinv, logdet, info, G_old, s, s2, ev, syrk_ev, n_syrk, syrk_flop, nck, ck_blocks, ck_ev, on_ck, ck_ctx, bt);
-  PotrfCarry carry;
+    return potrf<T>(A, N, Tinv, logdet, info, G_old, s, s2, ev, obs, bt);
+  PotrfObservers none;
+  if (!obs) obs = &none;
   hipEvent_t* ED = ev;            // diag(k) done, on s
   hipEvent_t* ER = ev + nbk;      // R(k) done, on c2
   hipEvent_t* U = ev + 2 * nbk;   // bulk(q) done, on s2
@@ -922,28 +812,13 @@ int potrf_split(T* A, long N, T* Tinv, T* logdet, int* info, T* snap, hipStream_
     });
     if (ce != hipSuccess) return (int)ce;
   }
-  int ck_next = 0;
-  int ns = 0, last_u = -1;
-  double flop = 0.0;
+  int last_u = -1;
   int* flags = info + CHAIN_FLAG0;  // zeroed with the other status words by the first diagonal-block kernel
   if (k_start > 0) {
     const int q0 = k_start / G_old;
-    const int rc = potrf<T>(A, N, Tinv, logdet, info, G_old, s, s2, ev, syrk_ev, n_syrk, syrk_flop, nck, ck_blocks, ck_ev, on_ck,
-                            ck_ctx, bt, q0, &carry);
+    const int rc = potrf<T>(A, N, Tinv, logdet, info, G_old, s, s2, ev, obs, bt, q0);
     if (rc) return rc;
-    ck_next = carry.ck_next;
-    ns = carry.ns;
-    flop = carry.flop;
   }
-  auto checkpoint = [&](int cols_final, hipStream_t st) {
-    while (ck_next < nck && ck_blocks[ck_next] <= cols_final) {
-      hipEventRecord(ck_ev[ck_next], st);
-      if (on_ck) on_ck(ck_ctx, ck_next);
-      ++ck_next;
-    }
-  };
-  auto tri = [](int m) { return (unsigned)(m * (m + 1) / 2); };
-  const double tile_flop = 2.0 * NB * NB * NB;
   auto bulk_exists = [&](int q) { return q >= 0 && 2 * q + 4 < nbk; };
   // block columns >= 2q + 4 <- panels kfirst .. kfirst + nk - 1 (pair q: kfirst = 2q, nk = 2; at the hand-over the last
   // group of the schedule that ran first), behind the rest step recorded in ER[2q + 1]
@@ -951,12 +826,10 @@ int potrf_split(T* A, long N, T* Tinv, T* logdet, int* info, T* snap, hipStream_
     const int k = 2 * q + 1;
     if (kfirst < 0) kfirst = k - 1;
     hipStreamWaitEvent(s2, ER[k], 0);
-    if (syrk_ev) hipEventRecord(syrk_ev[2 * ns], s2);
+    obs->bulk_begin(s2);
     const SyrkShape sh((int)tri(nbk - k - 3), bt.tuning().syrk_slots);
     launch_bulk<T>(A, N, kfirst, nk, k + 3, sh, nbk - k - 3, info, s2, bt);
-    if (syrk_ev) hipEventRecord(syrk_ev[2 * ns + 1], s2);
-    flop += (double)nk * tile_flop * tri(nbk - k - 3);
-    ++ns;
+    obs->bulk_end(s2, (double)nk * TILE_FLOP * tri(nbk - k - 3));
     chain_signal_kernel<<<1, 64, 0, s2>>>(flags + 1, q + 1);  // bulk(q) finished
     hipEventRecord(U[q], s2);
     last_u = q;
@@ -1024,15 +897,13 @@ int potrf_split(T* A, long N, T* Tinv, T* logdet, int* info, T* snap, hipStream_
     }
     if (k + 2 >= nbk) chain_signal_kernel<<<1, 64, 0, c2>>>(flags, k + 1);  // R(k) finished (otherwise chain_col's last workgroup says so)
     hipEventRecord(ER[k], c2);
-    checkpoint(k + 1, c2);
+    obs->checkpoint(k + 1, c2);
     if ((k & 1) == 1 && k + 3 < nbk) bulk(q);  // released behind the chain's own updates
   }
   // every R(k) was waited for by crit(k+2) except the last one; every bulk launch by the crit of a later even block or not at all
   if (nbk >= 2) hipStreamWaitEvent(s, ER[nbk - 2], 0);
   if (last_u >= 0) hipStreamWaitEvent(s, U[last_u], 0);  // s2 runs its launches in order
-  checkpoint(nbk, s);
-  if (n_syrk) *n_syrk = ns;
-  if (syrk_flop) *syrk_flop = flop;
+  obs->checkpoint(nbk, s);
   return (int)hipGetLastError();
 }
 
@@ -1516,15 +1387,20 @@ int symv_lower(const T* S, long N, const T* g, int n, const T* alpha, T* beta, T
 
 long solve_partials(long N) { return (N + trmv_chunk(N) - 1) / trmv_chunk(N) * N; }
 
+// z = T r (r at site stride rs), out = T^T z (at site stride os; < 0: the workspace stride), quad = z^T z unless null
 template <typename T>
-int solve(const T* Tm, long N, const T* r, int n, T* z, T* alpha, T* partials, T* quad, hipStream_t s, Batch bt) {
+static void solve_pair(const T* Tm, long N, const T* r, long rs, int n, T* z, T* out, long os, T* partials, T* quad, hipStream_t s,
+                       const Batch& bt) {
   const unsigned Bz = (unsigned)bt.B;
-  trmv_n_kernel<T><<<dim3((unsigned)(N / 4), 1, Bz), 256, 0, s>>>(Tm, N, r, n, z, bt.ws, bt.ns, (long)n);
+  trmv_n_kernel<T><<<dim3((unsigned)(N / 4), 1, Bz), 256, 0, s>>>(Tm, N, r, n, z, bt.ws, bt.ns, rs);
   const int chunk = trmv_chunk(N), nchunks = (int)((N + chunk - 1) / chunk);
   dim3 grid((unsigned)(N / 64), (unsigned)nchunks, Bz);
   trmv_t_kernel<T><<<grid, 256, 0, s>>>(Tm, N, z, partials, bt.ws, chunk);
-  trmv_t_reduce_kernel<T><<<dim3((unsigned)((N + 255) / 256) + 1, 1, Bz), 256, 0, s>>>(partials, N, nchunks, alpha, bt.ws, chunk,
-                                                                                   z, quad);
+  trmv_t_reduce_kernel<T><<<dim3((unsigned)((N + 255) / 256) + 1, 1, Bz), 256, 0, s>>>(partials, N, nchunks, out, bt.ws, chunk, z, quad, os);
+}
+template <typename T>
+int solve(const T* Tm, long N, const T* r, int n, T* z, T* alpha, T* partials, T* quad, hipStream_t s, Batch bt) {
+  solve_pair<T>(Tm, N, r, (long)n, n, z, alpha, -1, partials, quad, s, bt);
   return (int)hipGetLastError();
 }
 
@@ -1566,15 +1442,9 @@ __global__ __launch_bounds__(256) void refine_finish_kernel(T* __restrict__ alph
 template <typename T>
 int refine_solve(const T* Tm, long N, const T* r, int n, const double* rho64, const T* rho32, T* z, T* delta, T* alpha,
                  T* partials, T* quad, hipStream_t s, Batch bt, long ps, long rs) {
-  const unsigned Bz = (unsigned)bt.B;
-  trmv_n_kernel<T><<<dim3((unsigned)(N / 4), 1, Bz), 256, 0, s>>>(Tm, N, rho32, n, z, bt.ws, bt.ns, rs);
-  const int chunk = trmv_chunk(N), nchunks = (int)((N + chunk - 1) / chunk);
-  dim3 grid((unsigned)(N / 64), (unsigned)nchunks, Bz);
-  trmv_t_kernel<T><<<grid, 256, 0, s>>>(Tm, N, z, partials, bt.ws, chunk);
-  // delta sits in the caller's scratch at site stride rs: the reduce kernel strides its output by `bs`
-  trmv_t_reduce_kernel<T><<<dim3((unsigned)((N + 255) / 256) + 1, 1, Bz), 256, 0, s>>>(partials, N, nchunks, delta, bt.ws, chunk,
-                                                                                   z, nullptr, rs);
-  refine_finish_kernel<T><<<dim3(1, 1, Bz), 256, 0, s>>>(alpha, delta, rho64, r, n, quad, bt.ws, ps, rs, bt.ns);
+  // delta sits in the caller's scratch at site stride rs; the quadratic form comes from refine_finish_kernel
+  solve_pair<T>(Tm, N, rho32, rs, n, z, delta, rs, partials, nullptr, s, bt);
+  refine_finish_kernel<T><<<dim3(1, 1, (unsigned)bt.B), 256, 0, s>>>(alpha, delta, rho64, r, n, quad, bt.ws, ps, rs, bt.ns);
   return (int)hipGetLastError();
 }
 
@@ -1722,10 +1592,9 @@ int sample_draws(const T* L, long M, const T* Z, long Q, const T* mean, int m, i
   template int posterior_cov<T>(const T*, long, long, T*, hipStream_t, int, long);                                          \
   template int sample_draws<T>(const T*, long, const T*, long, const T*, int, int, T*, hipStream_t);             \
   template int symv_lower<T>(const T*, long, const T*, int, const T*, T*, T*, T*, hipStream_t, Batch, long);     \
-  template int potrf<T>(T*, long, T*, T*, int*, int, hipStream_t, hipStream_t, hipEvent_t*, hipEvent_t*, int*, double*, int, \
-                        const int*, hipEvent_t*, void (*)(void*, int), void*, Batch, int, PotrfCarry*);                                                                                        \
-  template int potrf_split<T>(T*, long, T*, T*, int*, T*, hipStream_t, hipStream_t, hipStream_t, hipEvent_t*, hipEvent_t*, int*, double*, \
-                              int, const int*, hipEvent_t*, void (*)(void*, int), void*, int, int, const Tuning*);         \
+  template int potrf<T>(T*, long, T*, T*, int*, int, hipStream_t, hipStream_t, hipEvent_t*, PotrfObservers*, Batch, int);               \
+  template int potrf_split<T>(T*, long, T*, T*, int*, T*, hipStream_t, hipStream_t, hipStream_t, hipEvent_t*, PotrfObservers*, int, int,  \
+                              const Tuning*);                                                                                             \
   template int potrf_group<T>(T*, long, int, T*, T*, int*, int, int, hipStream_t);                                \
   template int trtri_advance<T>(const T*, long, T*, T*, int, TrtriProgress*, hipStream_t, int, int*, int, int, Batch, long);                   \
   template int trtri<T>(const T*, const T*, long, T*, T*, hipStream_t, Batch, long);                                        \

@@ -536,8 +536,7 @@ int cross_validate(const T* Tm, const T* S, const T* alpha, long N, int n, const
       cv_pad_kernel<<<dim3(1, 1, Z), 256, 0, s>>>(ck, sl, bt.ns, order, start, slots);
     }
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    int rc = potrf<double>(slots + sl.A, M, slots + sl.Tm, slots + sl.scal, (int*)(slots + sl.info), 0, s, nullptr, nullptr, nullptr,
-                           nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, bb);
+    int rc = potrf<double>(slots + sl.A, M, slots + sl.Tm, slots + sl.scal, (int*)(slots + sl.info), 0, s, nullptr, nullptr, nullptr, bb);
     if (rc) return rc;
     if ((rc = trtri<double>(slots + sl.A, nullptr, M, slots + sl.Tm, slots + sl.W, s, bb))) return rc;
     cv_trmv_kernel<<<dim3((unsigned)(M / 4), 1, Z), 256, 0, s>>>(sl, slots);

@@ -99,24 +99,48 @@ template <typename T>
 int gemv_rows(const T* Ks, long N, long Mp, int m, const T* w, T* out, hipStream_t s, int B = 1, long wbs = 0);
 
 // ---- dgp_chol.hip ---------------------------------------------------------------------------
-struct PotrfCarry {  // state of a factorisation that one schedule hands to the next (potrf with q_stop -> potrf_split)
-  int ck_next = 0, ns = 0;
-  double flop = 0.0;
+// What watches a factorisation from outside: the timing of its bulk launches (dgp_plan_get_timing) and the checkpoints behind which
+// the caller enqueues dependent work (fit_step's early inverse).  One per factorisation: a schedule that hands over to another
+// (potrf with q_stop -> potrf_split) passes it on, counters and next checkpoint included.
+struct PotrfObservers {
+  hipEvent_t* syrk_ev = nullptr;  // 2 per timed bulk launch, or null: launches are counted but not timed
+  int syrk_pool = 0;              // bulk launches the event pool can time
+  int n_syrk = 0;                 // bulk launches so far, and their flops
+  double syrk_flop = 0.0;
+  int nck = 0;                    // checkpoint c is due once the first ck_blocks[c] (ascending) block columns of L are final
+  const int* ck_blocks = nullptr;
+  hipEvent_t* ck_ev = nullptr;
+  void (*on_ck)(void* ctx, int idx) = nullptr;  // called right after checkpoint idx is recorded
+  void* ck_ctx = nullptr;
+  int ck_next = 0;
+
+  bool bulk_begin(hipStream_t s) {  // -> whether this launch is timed
+    const bool timed = syrk_ev != nullptr && n_syrk < syrk_pool;
+    if (timed) hipEventRecord(syrk_ev[2 * n_syrk], s);
+    return timed;
+  }
+  void bulk_end(hipStream_t s, double flop) {
+    if (syrk_ev != nullptr && n_syrk < syrk_pool) hipEventRecord(syrk_ev[2 * n_syrk + 1], s);
+    syrk_flop += flop;
+    ++n_syrk;
+  }
+  // every checkpoint due at cols_final, on `s` (every schedule records every checkpoint, at the latest when the factorisation is complete)
+  void checkpoint(int cols_final, hipStream_t s) {
+    while (ck_next < nck && ck_blocks[ck_next] <= cols_final) {
+      hipEventRecord(ck_ev[ck_next], s);
+      if (on_ck) on_ck(ck_ctx, ck_next);  // the caller enqueues its dependent work NOW, not after the whole schedule
+      ++ck_next;
+    }
+  }
 };
 template <typename T>
 int potrf(T* A, long N, T* Dinv, T* logdet, int* info, int lookahead, hipStream_t s, hipStream_t s2, hipEvent_t* ev,
-          hipEvent_t* syrk_ev /* 2 per bulk launch, or null */, int* n_syrk, double* syrk_flop,
-          int nck = 0, const int* ck_blocks = nullptr /* ascending */, hipEvent_t* ck_ev = nullptr,
-          void (*on_ck)(void* ctx, int idx) = nullptr /* called right after checkpoint idx is recorded */,
-          void* ck_ctx = nullptr, Batch bt = Batch(), int q_stop = -1 /* stop after chain(q_stop - 1): potrf_split */,
-          struct PotrfCarry* carry = nullptr);
+          PotrfObservers* obs = nullptr /* null: none */, Batch bt = Batch(), int q_stop = -1 /* stop after chain(q_stop - 1): potrf_split */);
 // the split panel chain (one site, fewer than 96 block columns): critical tile on `s`, rest of the chain on `c2`,
 // bulk updates on `s2`; ev holds 3 N/128 events; snap = 2 x 128 x 128 elements of workspace
 template <typename T>
 int potrf_split(T* A, long N, T* Dinv, T* logdet, int* info, T* snap, hipStream_t s, hipStream_t c2, hipStream_t s2,
-                hipEvent_t* ev, hipEvent_t* syrk_ev, int* n_syrk, double* syrk_flop, int nck = 0,
-                const int* ck_blocks = nullptr, hipEvent_t* ck_ev = nullptr, void (*on_ck)(void* ctx, int idx) = nullptr,
-                void* ck_ctx = nullptr, int k_start = 0 /* block columns before it by the single-stream group schedule */,
+                hipEvent_t* ev, PotrfObservers* obs = nullptr, int k_start = 0 /* block columns before it by the single-stream group schedule */,
                 int G_old = 2 /* panels per group of that schedule */, const Tuning* tune = nullptr);
 // progress of the level recursion of trtri when it is issued piecewise (trtri_advance)
 struct TrtriProgress {

@@ -329,7 +329,7 @@ class DistributedFit:
         started BEFORE the bulk of ``consume(g)``, through ``consume``'s first phase.
 
         Buffer reuse: payload g lives in ``_panels[g % 2]``, so the broadcast of g + 2 overwrites what ``consume(g)``
-        read.  That is safe only if every access is STREAM-ORDERED before that broadcast: ``produce`` and ``consume``
+        read.  That is safe only if every access is stream-ordered before that broadcast: ``produce`` and ``consume``
         launch on torch's current stream; under "nccl" ``work.wait()`` makes the current stream wait for the collective
         and the collective's own stream waits for the current stream at the time ``dist.broadcast`` is called
         (ProcessGroupNCCL semantics) -- which is after ``consume(g)`` was enqueued, because ``start(g + 2)`` is only

@@ -67,7 +67,7 @@ int main() {
   CK(hipStreamCreateWithPriority(&s1, hipStreamNonBlocking, greatest)); CK(hipStreamCreateWithPriority(&s2, hipStreamNonBlocking, least));
   CK(hipStreamCreateWithFlags(&s3, hipStreamNonBlocking));
   const size_t bytes = potrf_diag_fast_smem<double>();
-  CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&potrf_diag_fast_kernel<double, double>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&potrf_diag_fast_kernel<double>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
   const int reps = 200;
   for (int mode = 0; mode < 3; ++mode) {
     CK(hipMemset(flag, 0, 4)); CK(hipMemset(info, 0, 4096));
@@ -80,7 +80,7 @@ int main() {
     CK(hipEventRecord(e0, s1));
     for (int i = 0; i < reps; ++i) {
       restore_block<<<1, 256, 0, s1>>>(B0, A0, ld);
-      potrf_diag_fast_kernel<double, double><<<1, 256, bytes, s1>>>(A0, ld, 0, Tm, logdet, info, 0, 0, 1, 16, nullptr);
+      potrf_diag_fast_kernel<double><<<1, 256, bytes, s1>>>(A0, ld, 0, Tm, logdet, info, 0, 0, 1, 16, nullptr, -1, 0);
     }
     CK(hipEventRecord(e1, s1));
     CK(hipEventSynchronize(e1));

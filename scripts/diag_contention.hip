@@ -1,6 +1,6 @@
 // How much does a saturating GEMM launch slow the diagonal-block factorisation of a RESIDENT workgroup -- sharing its CU
 // with one GEMM workgroup (96.7 KB of LDS) or owning the CU (140 KB of LDS: no GEMM workgroup fits beside it)?
-// Built against csrc + scripts/persistent_chain.patch (potrf_diag_block as a device function).
+// Built against csrc + the persistent-chain patch (potrf_diag_block as a device function; removed; last in the tree at 39a63aa).
 #include <stdio.h>
 #include <vector>
 #include "dgp_diag.h"

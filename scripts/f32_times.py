@@ -1,5 +1,6 @@
 """fp32 fit-step times of the shapes that matter (config 3, config 5 on one GPU, n = 8192 / 4096 single site, a batch):
-run once per setting of DGP_F32_DIAG64 to A/B the mixed-precision panel.  usage: python scripts/f32_times.py [big]"""
+how the mixed-precision diagonal block was measured against the plain one (profiles/r03_fp32_error_sources.txt; that form and its switch are
+removed).  usage: python scripts/f32_times.py [big]"""
 import json, sys
 import torch
 sys.path.insert(0, ".")
