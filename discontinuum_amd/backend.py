@@ -381,6 +381,58 @@ class GPPlan:
             _lib.check(self.lib.dgp_fisher(self._h, th, _ptr(diag), E, work, need, _ptr(out), _stream()), "dgp_fisher")
         return out
 
+    # ------------------------------------------------------------------ Jacobians of the prediction w.r.t. the hyperparameters
+    def _check_columns(self, cols, name, lead):
+        """A (K, n) -- (batch, K, n) -- device tensor of per-training-row columns in the plan's dtype, K <= 8 -> (tensor or None, K)."""
+        if cols is None:
+            return None, 0
+        if not (torch.is_tensor(cols) and cols.is_cuda and cols.dtype == self.dtype and cols.dim() == 2 + len(lead)
+                and tuple(cols.shape[:-2]) == lead and cols.shape[-1] == self.n):
+            raise ValueError(f"{name} must be a {lead + ('K', self.n)} {self.dtype} CUDA tensor")
+        K = int(cols.shape[-2])
+        if K > 8:
+            raise ValueError(f"at most 8 rows of {name}, got {K}")
+        return (cols.contiguous() if K else None), K
+
+    def predict_sensitivity(self, theta, Xs: torch.Tensor, diag=None, rhs=None, chunk: int | None = None, return_var: bool = True):
+        """Exact Jacobians of the latent posterior mean and variance at Xs (m, d) with respect to the hyperparameter
+        DIRECTIONS, from the factorisation the plan holds (``dgp_predict_sensitivity``; the plan is only read): first the
+        P = ``ntheta`` kernel directions at ``theta`` (constrained values), then the E rows of ``diag`` as diagonal
+        directions diag(d_e) of K^ (learned noise terms), then -- for the mean only -- the C rows of ``rhs`` as directions
+        g_c of the prior mean at the training rows (the caller adds the prior mean's own derivative at the test rows).
+        ``diag`` (E, n) / ``rhs`` (C, n), (batch, ., n) for a batched plan, E, C <= 8, plan dtype, on the device; None: none.
+        -> (dmean (P + E + C, m), dvar (P + E, m) or None with ``return_var=False``) in float64; batched plans: Xs
+        (batch, m, d), theta (batch, ntheta) and a leading batch dimension on both results.  The Jacobians are exact; what a
+        caller builds from them and a covariance of the hyperparameters is first order in that covariance (delta method).
+        ``chunk`` = points per launch sequence: the chunks' results are independent, so their concatenation is exact.  The
+        work area is batch x (P N^2 + 3 N chunk) elements; default chunk as for ``predict``."""
+        if chunk is None:
+            chunk = max(128, (16384 // self.batch) // 128 * 128)
+        lead, m = self._check_xs(Xs)
+        th = _theta_array(theta, self.ntheta * self.batch)
+        diag, E = self._check_columns(diag, "diag", lead)
+        rhs, Cn = self._check_columns(rhs, "rhs", lead)
+        R, Rv = self.ntheta + E + Cn, self.ntheta + E
+        dmean = torch.empty(lead + (R, m), dtype=torch.float64, device=self.device)
+        dvar = torch.empty(lead + (Rv, m), dtype=torch.float64, device=self.device) if return_var else None
+        with torch.cuda.device(self.device):
+            for lo in range(0, m, chunk):
+                hi = min(lo + chunk, m)
+                whole = lo == 0 and hi == m
+                xs = Xs[..., lo:hi, :].contiguous()
+                need = int(self.lib.dgp_predict_sensitivity_workspace_bytes(self._h, hi - lo, E, Cn))
+                work = self._work_area("_sens_ws", need, "dgp_predict_sensitivity")
+                # a chunk is a column range of the (..., rows, m) results: stage it
+                mo = dmean if whole else torch.empty(lead + (R, hi - lo), dtype=torch.float64, device=self.device)
+                vo = dvar if (whole or dvar is None) else torch.empty(lead + (Rv, hi - lo), dtype=torch.float64, device=self.device)
+                _lib.check(self.lib.dgp_predict_sensitivity(self._h, th, _ptr(xs), hi - lo, _ptr(diag), E, _ptr(rhs), Cn, work, need,
+                                                            _ptr(mo), _ptr(vo), _stream()), "dgp_predict_sensitivity")
+                if not whole:
+                    dmean[..., lo:hi] = mo
+                    if dvar is not None:
+                        dvar[..., lo:hi] = vo
+        return dmean, dvar
+
     def whiten(self, cols: torch.Tensor, site: int = 0):
         """L^-1 cols through the inverse factor T the plan holds, for the few columns of a prior-mean Jacobian:
         (L^-1 J)^T (L^-1 J) = J^T K^^-1 J, the mean block of the Fisher information.  ``cols`` (n_site, k) on the device

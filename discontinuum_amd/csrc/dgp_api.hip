@@ -1456,6 +1456,61 @@ int dgp_fisher(dgp_plan* p, const double* theta, const void* diag, int ndiag, vo
   return wrap(rc, "dgp_fisher");
 }
 
+}  // extern "C"
+
+#define DGP_SENS_MAX_COLS 8
+static bool sens_sizes_ok(const dgp_plan* p, int64_t m, int ndiag, int nrhs) {
+  return p && m > 0 && m <= 0x7fffffffLL - DGP_TILE_HOST && ndiag >= 0 && ndiag <= DGP_SENS_MAX_COLS && nrhs >= 0 && nrhs <= DGP_SENS_MAX_COLS;
+}
+template <typename T>
+static int sensitivity(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const void* diag, int ndiag, const void* rhs, int nrhs,
+                       void* work, double* dmean, double* dvar, hipStream_t s) {
+  const long M = round_up(m, DGP_TILE_HOST);
+  const SensLayout L = sens_layout(p->N, M, p->d, p->ntheta, ndiag, nrhs, p->elem);
+  char* w = (char*)work;
+  const int rc = cross<T>(p, theta, Xs, m, w + L.Xst, w + L.Ks, s, (long)(L.total / sizeof(T)));
+  if (rc) return rc;
+  return predict_sensitivity<T>(p->model, p->d, (const T*)p->Xt, (const T*)p->Tm, (const T*)p->alpha, p->N, (int)p->n, theta, M, (int)m,
+                                (const T*)diag, ndiag, (const T*)rhs, nrhs, work, L, dmean, dvar, s, batch_of<T>(p), p->pre);
+}
+
+extern "C" {
+
+size_t dgp_predict_sensitivity_workspace_bytes(const dgp_plan* p, int64_t m, int ndiag, int nrhs) {
+  if (!sens_sizes_ok(p, m, ndiag, nrhs)) return 0;
+  return sens_layout(p->N, round_up(m, DGP_TILE_HOST), p->d, p->ntheta, ndiag, nrhs, p->elem).total * (size_t)p->B;
+}
+
+int dgp_predict_sensitivity(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const void* diag, int ndiag, const void* rhs,
+                            int nrhs, void* work, size_t work_bytes, double* dmean, double* dvar, void* stream) {
+  if (!p) return fail(DGP_E_ARG, "null plan");
+  if (!theta || !Xs || !dmean) return fail(DGP_E_ARG, "dgp_predict_sensitivity: null argument");
+  if (m <= 0 || m > 0x7fffffffLL - DGP_TILE_HOST) return fail(DGP_E_ARG, "dgp_predict_sensitivity: m must be positive");
+  if (ndiag < 0 || ndiag > DGP_SENS_MAX_COLS) return fail(DGP_E_ARG, "dgp_predict_sensitivity: ndiag must be 0..8");
+  if (nrhs < 0 || nrhs > DGP_SENS_MAX_COLS) return fail(DGP_E_ARG, "dgp_predict_sensitivity: nrhs must be 0..8");
+  if (ndiag > 0 && !diag) return fail(DGP_E_ARG, "dgp_predict_sensitivity: ndiag > 0 needs the diagonal directions");
+  if (nrhs > 0 && !rhs) return fail(DGP_E_ARG, "dgp_predict_sensitivity: nrhs > 0 needs the right-hand-side columns");
+  DGP_CHECK_PLAN(p);
+  if (!p->have_factor)
+    return fail(DGP_E_STATE, "dgp_predict_sensitivity: no factorisation in the plan (call dgp_factorize or dgp_fit_step)");
+  if (!work || work_bytes < dgp_predict_sensitivity_workspace_bytes(p, m, ndiag, nrhs))
+    return fail(DGP_E_WORKSPACE, "dgp_predict_sensitivity: workspace missing or too small");
+  if (((uintptr_t)work & 255) != 0) return fail(DGP_E_ARG, "dgp_predict_sensitivity: the work area must be 256-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  {  // a failed factorisation leaves no T to read: the sites' status words, before any launch
+    std::vector<int> info((size_t)p->B, 0);
+    hipError_t e = hipMemcpy2DAsync(info.data(), sizeof(int), p->info, p->site_bytes, sizeof(int), (size_t)p->B, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hipfail(e, "dgp_predict_sensitivity");
+    for (int b = 0; b < p->B; ++b)
+      if (info[(size_t)b] != 0)
+        return fail(DGP_E_STATE, "dgp_predict_sensitivity: the factorisation the plan holds failed (matrix not positive definite)");
+  }
+  const int rc = DGP_BY_DTYPE(p, sensitivity<double>(p, theta, Xs, m, diag, ndiag, rhs, nrhs, work, dmean, dvar, s),
+                              sensitivity<float>(p, theta, Xs, m, diag, ndiag, rhs, nrhs, work, dmean, dvar, s));
+  return wrap(rc, "dgp_predict_sensitivity");
+}
+
 int dgp_plan_set_timing(dgp_plan* p, int enabled) {
   if (!p) return fail(DGP_E_ARG, "null plan");
   p->timing = enabled ? 1 : 0;

@@ -209,6 +209,20 @@ size_t fisher_site_bytes(long N, int nd, size_t elem) {
          fisher_align(sizeof(double) * (size_t)fisher_tiles(N) * (size_t)nd * (size_t)nd);
 }
 
+// the sweep's launch, shared with dgp_sensitivity.hip: slot p of G (slot stride N^2, site stride wbs) <- D_p, p < ntheta.
+// upload = false: the hyperparameters of a batch of more than 8 are already in pre_scratch (an earlier launcher of the same call).
+template <typename T>
+int fisher_dk(int model, int d, const T* Xt, long N, int n, const double* theta, T* G, hipStream_t s, Batch bt, long wbs,
+              void* pre_scratch, void* pre_staging, bool upload) {
+  const int nt = model_ntheta(model, d);
+  if (nt < 0) return -2;
+  const long nb64 = N / 64;
+  DGP_DISPATCH_MODEL(model, d, (fisher_dk_kernel<T, M><<<dim3((unsigned)(nb64 * nb64), 1, (unsigned)bt.B), dim3(256), 0, s>>>(
+                                   Xt, N, n, nt, prepare_batch<M>(theta, nt, bt.B, pre_scratch, upload, s, pre_staging), G, bt.ws, wbs,
+                                   bt.ns)));
+  return (int)hipGetLastError();
+}
+
 template <typename T>
 int fisher(int model, int d, const T* Xt, const T* Tm, long N, int n, const double* theta, const T* diag, int ndiag, void* work,
            double* F, hipStream_t s, Batch bt, void* pre_scratch, void* pre_staging) {
@@ -223,11 +237,7 @@ int fisher(int model, int d, const T* Xt, const T* Tm, long N, int n, const doub
   T* V = G + (long)nd * slot;
   double* part = (double*)((char*)work + (size_t)(nd + 1) * fisher_align(sizeof(T) * (size_t)slot));
   const unsigned Bz = (unsigned)bt.B;
-  const long nb64 = N / 64;
-  DGP_DISPATCH_MODEL(model, d, (fisher_dk_kernel<T, M><<<dim3((unsigned)(nb64 * nb64), 1, Bz), dim3(256), 0, s>>>(
-                                   Xt, N, n, nt, prepare_batch<M>(theta, nt, bt.B, pre_scratch, true, s, pre_staging), G, bt.ws, wbs,
-                                   bt.ns)));
-  int rc = (int)hipGetLastError();
+  int rc = fisher_dk<T>(model, d, Xt, N, n, theta, G, s, bt, wbs, pre_scratch, pre_staging, true);
   if (rc) return rc;
   const int nbk = (int)(N / DGP_TILE);
   const int tiles = nbk * (nbk + 1) / 2;
@@ -248,6 +258,8 @@ int fisher(int model, int d, const T* Xt, const T* Tm, long N, int n, const doub
   return (int)hipGetLastError();
 }
 
+template int fisher_dk<double>(int, int, const double*, long, int, const double*, double*, hipStream_t, Batch, long, void*, void*, bool);
+template int fisher_dk<float>(int, int, const float*, long, int, const double*, float*, hipStream_t, Batch, long, void*, void*, bool);
 template int fisher<double>(int, int, const double*, const double*, long, int, const double*, const double*, int, void*, double*,
                             hipStream_t, Batch, void*, void*);
 template int fisher<float>(int, int, const float*, const float*, long, int, const double*, const float*, int, void*, double*,

@@ -296,5 +296,23 @@ size_t fisher_site_bytes(long N, int nd, size_t elem);
 template <typename T>
 int fisher(int model, int d, const T* Xt, const T* Tm, long N, int n, const double* theta, const T* diag, int ndiag, void* work,
            double* F, hipStream_t s, Batch bt, void* pre_scratch, void* pre_staging);
+// its first pass alone: D_p = dK/dtheta_p for every p < ntheta, slot p (N^2 elements) of G at site stride wbs
+template <typename T>
+int fisher_dk(int model, int d, const T* Xt, long N, int n, const double* theta, T* G, hipStream_t s, Batch bt, long wbs,
+              void* pre_scratch, void* pre_staging, bool upload);
+
+// ---- dgp_sensitivity.hip: dmean [B][nt + ndiag + nrhs][m] and dvar [B][nt + ndiag][m] (null: not wanted) = the Jacobians of the
+// posterior mean / variance at the m test points with respect to the nt kernel directions, `ndiag` diagonal directions diag
+// [B][ndiag][n] and `nrhs` right-hand-side columns rhs [B][nrhs][n], from T = L^-1 and alpha.  `work`: a sens_layout slice per site,
+// its Xst (the test points, SoA, padded to Mp) and Ks (K(X, X*), N x Mp) already filled.  Reads Xt, T and alpha only.
+#define SENS_SPLIT 32  // row slabs of its column reductions
+struct SensLayout {
+  size_t Xst, D, Ks, V, beta, G, pc, pg, pq, total;  // byte offsets into a site's slice
+};
+SensLayout sens_layout(long N, long Mp, int d, int nt, int ndiag, int nrhs, size_t elem);
+template <typename T>
+int predict_sensitivity(int model, int d, const T* Xt, const T* Tm, const T* alpha, long N, int n, const double* theta, long Mp, int m,
+                        const T* diag, int ndiag, const T* rhs, int nrhs, void* work, const SensLayout& L, double* dmean, double* dvar,
+                        hipStream_t s, Batch bt, void* pre_scratch);
 
 }  // namespace dgp

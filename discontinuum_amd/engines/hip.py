@@ -657,7 +657,8 @@ class MarginalHIP(BaseModel):
                          dims=["draw"] + list(covariates.coords), attrs=temp.attrs)
 
     @is_fitted
-    def aggregate(self, covariates, weights, freq="YE", ci=0.95, pred_noise=False, return_cov=False, max_bytes=None):
+    def aggregate(self, covariates, weights, freq="YE", ci=0.95, pred_noise=False, return_cov=False, max_bytes=None,
+                  hyperparameters=False, prior=True):
         """Exact mean and covariance of the period sums sum_{i in period} weights_i target_i over the points of
         ``covariates`` (``freq``: a resample alias -- "YE", "YE-SEP" for water years, "QE", "ME"), from the latent
         posterior (``pred_noise=True`` adds the likelihood's predictive noise to its diagonal): what ``sample()``, a
@@ -666,11 +667,14 @@ class MarginalHIP(BaseModel):
         ``time`` coordinate of period-end labels with ``mean``, ``se``, ``lower`` / ``upper`` (approximate ``ci``
         interval: lognormal / normal with the exact moments) and ``n_points``; with ``return_cov`` also the (P, P)
         covariance.  ``max_bytes`` (default ``loads.DEFAULT_MAX_BYTES``): device budget of the dense path; a record whose
-        m x m covariance does not fit it takes the streamed ``dgp_posterior_period_moments``.  See ``discontinuum_amd.loads``."""
+        m x m covariance does not fit it takes the streamed ``dgp_posterior_period_moments``.  ``hyperparameters=True`` adds
+        ``se_hyper``, ``se_total`` and ``lower_total`` / ``upper_total`` (with ``return_cov`` also ``cov_hyper``): the
+        hyperparameters' uncertainty propagated to FIRST ORDER (delta method) through the exact period Jacobian and the exact
+        inverse Fisher information (``prior``: with the priors' curvature).  See ``discontinuum_amd.loads``."""
         from ..loads import DEFAULT_MAX_BYTES, aggregate
 
         return aggregate(self, covariates, weights, freq=freq, ci=ci, pred_noise=pred_noise, return_cov=return_cov,
-                         max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes)
+                         max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes, hyperparameters=hyperparameters, prior=prior)
 
     @is_fitted
     def exceedance(self, covariates, threshold=None, threshold_series=None, freq="YE", above=True, fraction=False, ci=0.95,
@@ -795,6 +799,20 @@ class MarginalHIP(BaseModel):
         from ..hyperpar import hyperparameter_uncertainty
 
         return hyperparameter_uncertainty(self, ci=ci, prior=prior)
+
+    @is_fitted
+    def predict_marginalized(self, covariates, ci=0.95, prior=True, pred_noise=False):
+        """``predict`` with the hyperparameters' uncertainty propagated to FIRST ORDER (delta method): Var_total[f*] =
+        Var[f* | fitted] + J_mu Sigma_raw J_mu^T, J_mu the exact Jacobian of the posterior mean at every prediction point
+        (one ``dgp_predict_sensitivity`` on the factorisation the engine holds; no refit) and Sigma_raw the exact inverse
+        Fisher information of ``hyperparameter_uncertainty`` (``prior=True``: with the priors' curvature; inactive, clamped
+        and unidentified directions contribute zero).  -> Dataset on the covariates' coordinates with ``mean``,
+        ``se_plugin`` (``predict``'s, bitwise), ``se_hyper``, ``se`` (total), ``lower`` / ``upper``, ``inflation``,
+        ``var_plugin`` / ``var_hyper``.  Second-order terms are not included.  See
+        ``discontinuum_amd.hyperpar.predict_marginalized``."""
+        from ..hyperpar import predict_marginalized
+
+        return predict_marginalized(self, covariates, ci=ci, prior=prior, pred_noise=pred_noise)
 
     def build_model(self, X, y, **kwargs):
         raise NotImplementedError("This method must be implemented in a subclass")

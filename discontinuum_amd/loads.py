@@ -108,22 +108,27 @@ def intervals(mode, mean, var, ci=0.95):
     return np.where(pos, lower, mean), np.where(pos, upper, mean)
 
 
-def _dataset(mode, mean, cov, labels, n_points, attrs, ci, freq=None):
-    """-> the result Dataset; its own attrs also carry the period ``freq`` (``period_change`` reads it)."""
+def _dataset(mode, mean, cov, labels, n_points, attrs, ci, freq=None, cov_hyper=None):
+    """-> the result Dataset; its own attrs also carry the period ``freq`` (``period_change`` reads it).  ``cov_hyper``: the
+    first-order contribution of the hyperparameters' uncertainty (``hyperparameters=True``), which adds ``se_hyper``,
+    ``se_total`` and ``lower_total`` / ``upper_total`` (the same interval rule at the summed variance)."""
     var = np.clip(np.diagonal(cov), 0.0, None)
     lower, upper = intervals(mode, mean, var, ci)
     attrs = dict(attrs)
-    return Dataset(
-        {
-            "mean": ("time", mean, attrs),
-            "se": ("time", np.sqrt(var), attrs),
-            "lower": ("time", lower, dict(attrs, ci=ci)),
-            "upper": ("time", upper, dict(attrs, ci=ci)),
-            "n_points": ("time", n_points),
-        },
-        coords={"time": labels},
-        attrs=attrs if freq is None else dict(attrs, freq=freq),
-    )
+    data = {
+        "mean": ("time", mean, attrs),
+        "se": ("time", np.sqrt(var), attrs),
+        "lower": ("time", lower, dict(attrs, ci=ci)),
+        "upper": ("time", upper, dict(attrs, ci=ci)),
+        "n_points": ("time", n_points),
+    }
+    if cov_hyper is not None:
+        var_h = np.clip(np.diagonal(cov_hyper), 0.0, None)
+        lower_t, upper_t = intervals(mode, mean, var + var_h, ci)
+        note = dict(attrs, order="first (delta method)")
+        data.update({"se_hyper": ("time", np.sqrt(var_h), note), "se_total": ("time", np.sqrt(var + var_h), note),
+                     "lower_total": ("time", lower_t, dict(note, ci=ci)), "upper_total": ("time", upper_t, dict(note, ci=ci))})
+    return Dataset(data, coords={"time": labels}, attrs=attrs if freq is None else dict(attrs, freq=freq))
 
 
 def _target_attrs(dm):
@@ -133,20 +138,28 @@ def _target_attrs(dm):
 
 # ---------------------------------------------------------------------------------------------------- one site
 def aggregate(model, covariates, weights, freq="YE", ci=0.95, pred_noise=False, return_cov=False, attrs=None,
-              max_bytes: int = DEFAULT_MAX_BYTES):
+              max_bytes: int = DEFAULT_MAX_BYTES, hyperparameters=False, prior=True):
     """``MarginalHIP.aggregate``: exact mean / covariance of sum_{i in period} w_i c_i over the points of
     ``covariates`` (c = the model's target in data space).  A site whose dense footprint (``_site_bytes``) fits
     ``max_bytes`` takes one ``dgp_posterior_cov`` + one ``dgp_period_moments``; a larger one the streamed
-    ``dgp_posterior_period_moments``, which never forms the m x m covariance."""
+    ``dgp_posterior_period_moments``, which never forms the m x m covariance.
+
+    ``hyperparameters=True`` also propagates the hyperparameters' uncertainty to FIRST ORDER (delta method): with G the
+    exact Jacobian of the period means with respect to the raw parameters (``hyperpar.period_hyper_covariance``, from one
+    ``dgp_predict_sensitivity``) and Sigma_raw the exact inverse Fisher information (``prior``: with the priors' curvature),
+    cov_hyper = G Sigma_raw G^T.  It adds ``se_hyper``, ``se_total`` = sqrt(se^2 + se_hyper^2) and ``lower_total`` /
+    ``upper_total``; with ``return_cov`` the result is (ds, cov, cov_hyper).  It works on the dense and the streamed path
+    alike (the Jacobian needs no m x m buffer).  Second-order terms are not included; ``flow_normalized``, ``exceedance`` and
+    the ``*_many`` wrappers do not propagate.  ``False`` returns exactly the variables it always did."""
     order, groups, labels, n_points, _dropped = _kept(*period_groups(covariates.coords["time"].values, np.asarray(weights), freq))
     w = np.asarray(weights, dtype=np.float64).reshape(-1)[order]
     Xnew = torch.tensor(model.dm.Xnew(covariates), dtype=model.dtype)[torch.as_tensor(order)]
     return point_moments(model, Xnew, w, groups, labels, n_points, ci=ci, pred_noise=pred_noise, return_cov=return_cov,
-                         attrs=attrs, max_bytes=max_bytes, freq=freq)
+                         attrs=attrs, max_bytes=max_bytes, freq=freq, hyperparameters=hyperparameters, prior=prior)
 
 
 def point_moments(model, Xnew, w, groups, labels, n_points, ci=0.95, pred_noise=False, return_cov=False, attrs=None,
-                  max_bytes: int = DEFAULT_MAX_BYTES, freq=None):
+                  max_bytes: int = DEFAULT_MAX_BYTES, freq=None, hyperparameters=False, prior=True):
     """The moment core of ``aggregate`` on model-space inputs: design rows ``Xnew`` (m, d), weights ``w`` (m,), int32
     period ids ``groups`` (non-decreasing, -1 = excluded), period ``labels`` and ``n_points`` per period -- what
     ``aggregate`` builds from a covariates record and ``flow_normalized`` from its (day, flow) pairs."""
@@ -167,9 +180,24 @@ def point_moments(model, Xnew, w, groups, labels, n_points, ci=0.95, pred_noise=
             extra = model.likelihood.predictive_noise(m, Xnew.device, model.dtype) if pred_noise else None
             mean_d, cov_d = model._plan.posterior_period_moments(model._factor_theta, Xnew, (s * mu + t).contiguous(), s * s, w,
                                                                  groups, len(labels), mode, extra_var=extra)
+        if hyperparameters:  # the per-point factors a_i of the period Jacobian need the pointwise variance on both paths
+            _kmean, kvar = model._plan.predict(model._factor_theta, Xnew)
+            var = kvar.double() + (extra.double() if extra is not None else 0.0)
+            mapped = (s * mu + t).double()
+            a_pt = torch.as_tensor(w, dtype=torch.float64, device=Xnew.device)
+            if mode == MODE_LOG:
+                a_pt = a_pt * torch.exp(mapped + 0.5 * s * s * var)
+            a_pt = a_pt.cpu().numpy()
     mean, pcov = mean_d.cpu().numpy(), cov_d.cpu().numpy()
-    ds = _dataset(mode, mean, pcov, labels, n_points, _target_attrs(model.dm) if attrs is None else attrs, ci, freq)
-    return (ds, pcov) if return_cov else ds
+    cov_hyper = None
+    if hyperparameters:
+        from .hyperpar import period_hyper_covariance
+
+        cov_hyper, _G = period_hyper_covariance(model, Xnew, a_pt, groups, len(labels), mode, s, prior=prior, pred_noise=pred_noise)
+    ds = _dataset(mode, mean, pcov, labels, n_points, _target_attrs(model.dm) if attrs is None else attrs, ci, freq, cov_hyper)
+    if return_cov:
+        return (ds, pcov, cov_hyper) if hyperparameters else (ds, pcov)
+    return ds
 
 
 # ---------------------------------------------------------------------------------------------------- many sites
@@ -343,11 +371,13 @@ def _flux_attrs(model):
     return attrs
 
 
-def annual_flux(model, covariates, freq="YE", ci=0.95, pred_noise=False, return_cov=False, max_bytes: int = DEFAULT_MAX_BYTES):
-    """``LoadestGP.annual_flux``: exact period loads (kg) and their uncertainty."""
+def annual_flux(model, covariates, freq="YE", ci=0.95, pred_noise=False, return_cov=False, max_bytes: int = DEFAULT_MAX_BYTES,
+                hyperparameters=False, prior=True):
+    """``LoadestGP.annual_flux``: exact period loads (kg) and their uncertainty.  ``hyperparameters=True``: also the
+    first-order (delta method) contribution of the hyperparameters' uncertainty, see ``aggregate``."""
     w = flux_weights(covariates, _target_attrs(model.dm))
     return aggregate(model, covariates, w, freq=freq, ci=ci, pred_noise=pred_noise, return_cov=return_cov,
-                     attrs=_flux_attrs(model), max_bytes=max_bytes)
+                     attrs=_flux_attrs(model), max_bytes=max_bytes, hyperparameters=hyperparameters, prior=prior)
 
 
 # ---------------------------------------------------------------------------------------------------- flow normalization

@@ -393,6 +393,38 @@ size_t dgp_fisher_workspace_bytes(const dgp_plan* plan, int ndiag);
 int dgp_fisher(dgp_plan* plan, const double* theta_host, const void* diag_dev, int ndiag, void* work_dev, size_t work_bytes,
                double* fisher_dev, void* stream);
 
+/* Exact JACOBIANS of the posterior mean and variance with respect to the hyperparameter directions, at all m test points, from
+ * the factorisation the plan holds: what a first-order (delta-method) propagation of the hyperparameters' uncertainty into
+ * predictions and loads needs beside dgp_fisher's covariance.  The Jacobians are exact; any propagation built on them is
+ * first order in that covariance.  The reference has no counterpart (it could only refit).  With T = L^-1, alpha = K^^-1 r,
+ * K* = K(X, X*) and beta = T^T T K* = K^^-1 K*, over dgp_fisher's P kernel and E = ndiag diagonal directions plus C = nrhs
+ * RIGHT-HAND-SIDE columns g_c = rhs_dev[site][c][0 .. n) (derivatives of the prior mean at the training rows, plan dtype):
+ *     dmean[p][j]         = sum_i dK*_ij/dtheta_p alpha_i - sum_i beta_ij (D_p alpha)_i
+ *     dvar [p][j]         = dk(x*_j, x*_j)/dtheta_p - 2 sum_i beta_ij dK*_ij/dtheta_p + beta_j^T D_p beta_j
+ *     dmean[P + e][j]     = -sum_i beta_ij d_e,i alpha_i,        dvar[P + e][j] = sum_i beta_ij^2 d_e,i
+ *     dmean[P + E + c][j] = -sum_i beta_ij g_c,i   (the caller adds dm(x*_j)/draw_c; the variance does not depend on it)
+ *   dmean_dev [batch][P + E + C][m], dvar_dev [batch][P + E][m]: doubles whatever the plan's dtype.  dvar_dev may be NULL
+ *   (means only): the quadratic-form pass is then skipped.  0 <= ndiag, nrhs <= 8; diag_dev / rhs_dev may be NULL when their
+ *   count is 0; entries beyond a ragged site's own size are ignored.
+ * Passes: dgp_fisher's sweep for all D_p; K* and V = T K* (the prediction's launches); beta = T^T V on the MFMA tile cores (T
+ * as the k-major operand, triangular k-range, last k-tile first; 128 x 128 direct-to-LDS tiles, 64 x 64 ones while a launch
+ * has too few: DGP_OPT_LAUUM64_MAX_TILES); G = [D_p alpha | d_e o alpha | g_c] by an HBM-bound multi-slot matvec; a cross sweep
+ * with ONE derivative pair evaluation per (i, j) accumulated in double against alpha_i and beta_ij; -beta^T G and beta^2 d;
+ * the quadratic forms as the products D_p beta on the tile cores, contracted with beta in the tile epilogue (the dominant
+ * cost: 2 P N^2 M flop); all column sums in double, two stages, fixed order.  No floating-point atomics: bitwise repeatable;
+ * batched plans: gridDim.z = sites, dgp_plan_set_site_sizes respected.  The plan is only read: A, T, K^^-1, alpha and every
+ * later answer are bitwise what they were.
+ * work_dev: dgp_predict_sensitivity_workspace_bytes(plan, m, ndiag, nrhs) bytes, 256-byte aligned: per site P N^2 + 3 N M
+ * plan-dtype elements (the D_p, K*, V, beta; M = m rounded up to 128) plus doubles: (P + E + C) N of G,
+ * 32 (3 P + 2 E + C) M of slab partials and P (N/64) M of row-tile partials; 0 for a null plan or bad sizes.
+ * DGP_E_ARG (null plan / theta / Xs / dmean_dev, m <= 0, ndiag or nrhs outside 0 .. 8, a positive count without its array,
+ * misaligned work area), DGP_E_WORKSPACE (work area missing or too small), DGP_E_STATE (no factorisation in the plan, or the
+ * one it holds failed: the status word of every site is read back, which synchronises the stream) -- all before any launch. */
+size_t dgp_predict_sensitivity_workspace_bytes(const dgp_plan* plan, int64_t m, int ndiag, int nrhs);
+int dgp_predict_sensitivity(dgp_plan* plan, const double* theta_host, const void* Xs_dev, int64_t m, const void* diag_dev, int ndiag,
+                            const void* rhs_dev, int nrhs, void* work_dev, size_t work_bytes, double* dmean_dev, double* dvar_dev,
+                            void* stream);
+
 /* The posterior of the covariance's ADDITIVE PARTS.  Both fused covariances and every generic one are sums of named terms,
  *   loadest: seasonal + covariates + residual;  rating: shift_1 + shift_2 + bend + base + periodic (the shifts and the bend
  *   carry their gates);  composite: its terms in descriptor order (an unscaled term counts outputscale 1),
