@@ -99,6 +99,8 @@ SIGNATURES = {
     "dgp_fisher": (_i, [_vp, _dp, _vp, _i, _vp, _sz, _vp, _vp]),
     "dgp_predict_sensitivity_workspace_bytes": (_sz, [_vp, _i64, _i, _i]),
     "dgp_predict_sensitivity": (_i, [_vp, _dp, _vp, _i64, _vp, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp]),
+    "dgp_deletion_influence_workspace_bytes": (_sz, [_vp, _i64, _i, _i64, _i]),
+    "dgp_deletion_influence": (_i, [_vp, _dp, _vp, _i64, _vp, _vp, _i, _i64, _i, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "dgp_model_nterms": (_i, [_i, _i]),
     "dgp_predict_terms_workspace_bytes": (_sz, [_vp, _i64]),
     "dgp_predict_terms": (_i, [_vp, _dp, _vp, _i64, _vp, _sz, _vp, _vp, _vp]),

@@ -433,6 +433,59 @@ class GPPlan:
                         dvar[..., lo:hi] = vo
         return dmean, dvar
 
+    # ------------------------------------------------------------------ influence of the held samples on the period sums
+    def deletion_influence(self, theta, Xs: torch.Tensor, groups, a, scale, periods, nperiods: int, mode: int, inv_sd=None,
+                           max_bytes: int | None = None, max_group=None):
+        """Exact change of every period sum when a fold of training observations is deleted, for all folds at once, at the
+        hyperparameters of the factorisation the plan holds (``dgp_deletion_influence``; nothing is refitted, the plan is only
+        read).  ``groups``: fold ids per observation as ``cross_validate`` takes them ((n,) / (batch, n) integers >= 0, -1 =
+        in no fold); ``max_group``: as there, an upper bound of the fold sizes handed to the library in place of the largest fold
+        found -- a ROUTE SELECTOR (1: leave-one-out, <= 64: LDS, larger: blocks of that order rounded up to 128), for callers that
+        compare a site alone with the same site in a batch; ``Xs`` (m, d) / (batch, m, d) the test points, ``theta`` as for ``predict``;
+        ``a`` (m,) / (batch, m): w_j exp(s mu_j + t + s^2 C_jj / 2) for a log target (``mode`` = MODE_LOG), s w_j for a linear
+        one; ``scale``: s, a number or (batch,) values; ``periods`` int32 ids (m,) / (batch, m) in 0 .. nperiods - 1,
+        non-decreasing, -1 = excluded; ``inv_sd`` None or (m,) / (batch, m): 1 / sigma_j of the posterior at the test points.
+        -> (dload (F, P), dvar (F, P) for a linear target else None, shift (F,) = max_j |dmu_Fj| inv_sd_j or None without
+        ``inv_sd``, info (F,) int32: 0 or the failing pivot of the fold's block, whose results are NaN), F = 1 + the largest
+        fold id, with a leading batch dimension for a batched plan; float64.  Sign: the sum WITHOUT the fold minus the sum with
+        it.  The call is never cut into chunks of test points (sums over chunks would not be bitwise chunk-invariant): a work
+        area above ``max_bytes`` raises ``ValueError`` naming the bytes."""
+        lead, m = self._check_xs(Xs)
+        th = _theta_array(theta, self.ntheta * self.batch)
+        P, mode = int(nperiods), int(mode)
+        if mode not in (MODE_LINEAR, MODE_LOG):
+            raise ValueError(f"mode must be {MODE_LINEAR} (linear) or {MODE_LOG} (log)")
+
+        def launch(order, start, nfolds, max_fold):
+            need = int(self.lib.dgp_deletion_influence_workspace_bytes(self._h, m, nfolds, max_fold, P))
+            if need == 0:
+                raise ValueError(f"bad size: m = {m}, nfolds = {nfolds}, max_fold = {max_fold}, nperiods = {P} "
+                                 "(1 <= m <= 2^20, 1 <= nfolds, max_fold <= n, 1 <= nperiods <= 65535)")
+            if max_bytes is not None and need > int(max_bytes):
+                raise ValueError(f"the influence of {nfolds} folds on m = {m} points at n = {self.n} (batch {self.batch}) needs a "
+                                 f"work area of {need} bytes, which exceeds max_bytes = {int(max_bytes)}")
+            dev = self.device
+            with torch.cuda.device(dev):
+                _mu, a_t, g_t, _ev, s_t = _moment_inputs(dev, self.dtype, lead, m, None, a, periods, None, scale)
+                sd_t = None if inv_sd is None else torch.as_tensor(inv_sd).to(dev, torch.float64).contiguous()
+                if sd_t is not None and tuple(sd_t.shape) != lead + (m,):
+                    raise ValueError(f"inv_sd must have shape {lead + (m,)}")
+                work = self._work_area("_influence_ws", need, "dgp_deletion_influence", check_free=True)
+                order, start, xs = order.to(dev).contiguous(), start.to(dev).contiguous(), Xs.contiguous()
+                dload = torch.empty(lead + (nfolds, P), dtype=torch.float64, device=dev)
+                dvar = torch.empty_like(dload) if mode == MODE_LINEAR else None
+                shift = torch.empty(lead + (nfolds,), dtype=torch.float64, device=dev) if sd_t is not None else None
+                info = torch.empty(lead + (nfolds,), dtype=torch.int32, device=dev)
+                _lib.check(
+                    self.lib.dgp_deletion_influence(self._h, th, _ptr(xs), m, _ptr(order), _ptr(start), nfolds, max_fold, mode, _ptr(a_t),
+                                                    _ptr(s_t), _ptr(g_t), P, _ptr(sd_t), work, need, _ptr(dload), _ptr(dvar), _ptr(shift),
+                                                    _ptr(info), _stream()),
+                    "dgp_deletion_influence",
+                )
+            return dload, dvar, shift, info
+
+        return cross_validate_folds(self, groups, launch, max_group)
+
     def whiten(self, cols: torch.Tensor, site: int = 0):
         """L^-1 cols through the inverse factor T the plan holds, for the few columns of a prior-mean Jacobian:
         (L^-1 J)^T (L^-1 J) = J^T K^^-1 J, the mean block of the Fisher information.  ``cols`` (n_site, k) on the device

@@ -1511,6 +1511,71 @@ int dgp_predict_sensitivity(dgp_plan* p, const double* theta, const void* Xs, in
   return wrap(rc, "dgp_predict_sensitivity");
 }
 
+}  // extern "C"
+
+static bool influence_sizes_ok(const dgp_plan* p, int64_t m, int nfolds, int64_t max_fold, int ngroups) {
+  return p && m >= 1 && m <= (1 << 20) && nfolds >= 1 && nfolds <= p->n && max_fold >= 1 && max_fold <= p->n && ngroups >= 1 &&
+         ngroups <= 65535;
+}
+static InfluenceLayout influence_layout_of(const dgp_plan* p, int64_t m, int nfolds, int64_t max_fold, int ngroups) {
+  return influence_layout(p->N, p->B, (int)p->n, p->d, round_up(m, DGP_TILE_HOST), (int)m, nfolds, max_fold, ngroups, p->elem);
+}
+template <typename T>
+static int influence(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const int32_t* order, const int32_t* start, int nfolds,
+                     int64_t max_fold, int mode, const double* a, const double* scale, const int32_t* group, int ngroups,
+                     const double* inv_sd, void* work, double* dload, double* dvar, double* shift, int32_t* info, hipStream_t s) {
+  const InfluenceLayout L = influence_layout_of(p, m, nfolds, max_fold, ngroups);
+  char* w = (char*)work;
+  const int rc = cross<T>(p, theta, Xs, m, w + L.Xst, w + L.Ks, s, (long)(L.slice / sizeof(T)));
+  if (rc) return rc;
+  const void* S = p->have_inverse ? p->S : nullptr;  // as dgp_cross_validate: read when the last step left it valid
+  return deletion_influence<T>((const T*)p->Tm, (const T*)S, (const T*)p->alpha, p->N, (int)p->n, round_up(m, DGP_TILE_HOST), (int)m, order,
+                               start, nfolds, max_fold, mode, a, scale, group, ngroups, inv_sd, work, L, dload, dvar, shift, info, s,
+                               batch_of<T>(p));
+}
+
+extern "C" {
+
+size_t dgp_deletion_influence_workspace_bytes(const dgp_plan* p, int64_t m, int nfolds, int64_t max_fold, int ngroups) {
+  if (!influence_sizes_ok(p, m, nfolds, max_fold, ngroups)) return 0;
+  return influence_layout_of(p, m, nfolds, max_fold, ngroups).total;
+}
+
+int dgp_deletion_influence(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const int32_t* order, const int32_t* start,
+                           int nfolds, int64_t max_fold, int mode, const double* a, const double* scale, const int32_t* group, int ngroups,
+                           const double* inv_sd, void* work, size_t work_bytes, double* dload, double* dvar, double* shift,
+                           int32_t* info, void* stream) {
+  if (!p) return fail(DGP_E_ARG, "null plan");
+  if (!theta || !Xs || !order || !start || !a || !scale || !group || !dload || !info)
+    return fail(DGP_E_ARG, "dgp_deletion_influence: null argument");
+  if (!influence_sizes_ok(p, m, nfolds, max_fold, ngroups))
+    return fail(DGP_E_ARG, "dgp_deletion_influence: bad size (1 <= m <= 2^20, 1 <= nfolds <= n, 1 <= max_fold <= n, 1 <= ngroups <= 65535)");
+  if (mode != 0 && mode != 1) return fail(DGP_E_ARG, "dgp_deletion_influence: mode must be 0 (linear) or 1 (log)");
+  if (mode == 1 && dvar) return fail(DGP_E_ARG, "dgp_deletion_influence: the variance change is exact for mode 0 only (dvar_dev must be NULL)");
+  if (shift && !inv_sd) return fail(DGP_E_ARG, "dgp_deletion_influence: shift_dev needs inv_sd_dev");
+  DGP_CHECK_PLAN(p);
+  if (!p->have_factor) return fail(DGP_E_STATE, "dgp_deletion_influence: no factorisation in the plan (call dgp_factorize or dgp_fit_step)");
+  if (!work || work_bytes < dgp_deletion_influence_workspace_bytes(p, m, nfolds, max_fold, ngroups))
+    return fail(DGP_E_WORKSPACE, "dgp_deletion_influence: workspace missing or too small");
+  if (((uintptr_t)work & 255) != 0) return fail(DGP_E_ARG, "dgp_deletion_influence: the work area must be 256-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  {  // a failed factorisation leaves no T to read: the sites' status words, before any launch
+    std::vector<int> st((size_t)p->B, 0);
+    hipError_t e = hipMemcpy2DAsync(st.data(), sizeof(int), p->info, p->site_bytes, sizeof(int), (size_t)p->B, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hipfail(e, "dgp_deletion_influence");
+    for (int b = 0; b < p->B; ++b)
+      if (st[(size_t)b] != 0)
+        return fail(DGP_E_STATE, "dgp_deletion_influence: the factorisation the plan holds failed (matrix not positive definite)");
+  }
+  const int rc = DGP_BY_DTYPE(p,
+                              influence<double>(p, theta, Xs, m, order, start, nfolds, max_fold, mode, a, scale, group, ngroups, inv_sd, work,
+                                                dload, dvar, shift, info, s),
+                              influence<float>(p, theta, Xs, m, order, start, nfolds, max_fold, mode, a, scale, group, ngroups, inv_sd, work,
+                                               dload, dvar, shift, info, s));
+  return wrap(rc, "dgp_deletion_influence");
+}
+
 int dgp_plan_set_timing(dgp_plan* p, int enabled) {
   if (!p) return fail(DGP_E_ARG, "null plan");
   p->timing = enabled ? 1 : 0;

@@ -32,16 +32,6 @@ constexpr int CV_SLAB = 128;   // rows per slab of the leave-one-out pass
 constexpr int CV_SMALL = 64;   // largest group of the fused LDS kernel
 constexpr int CV_MAX_CHUNK = 1024;
 
-// group g of a site = order[s0 .. s0 + b): bounds clamped to the site and to the route's largest group
-__device__ __forceinline__ void cv_bounds(const int* __restrict__ start, int g, int n, int cap, int& s0, int& b) {
-  int a = start[g], e = start[g + 1];
-  a = min(max(a, 0), n);
-  e = min(max(e, a), n);
-  s0 = a;
-  b = min(e - a, cap);
-}
-__device__ __forceinline__ int cv_index(const int* __restrict__ order, int p, int n) { return min(max(order[p], 0), n - 1); }
-
 // ---- leave-one-out: part[slab][j] = sum over the slab's rows k >= j of T[k][j]^2 ------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void cv_colss_kernel(const T* __restrict__ Tm, long N, long bs, double* __restrict__ part, long ps) {
@@ -101,7 +91,7 @@ __global__ __launch_bounds__(256) void cv_small_kernel(const T* __restrict__ Tm,
                                                        const T* __restrict__ alpha, const int* __restrict__ ns, int n,
                                                        const int* __restrict__ order, const int* __restrict__ start, int ngroups,
                                                        double* __restrict__ resid, double* __restrict__ var, double* __restrict__ lpd,
-                                                       int* __restrict__ info) {
+                                                       int* __restrict__ info, double* __restrict__ minv, long ld) {
   constexpr int LD = CV_SMALL + 1;
   __shared__ double sG[CV_SMALL * LD];  // G_B, then M (lower) with M^-1 transposed above the diagonal
   __shared__ double sP[16 * CV_SMALL];  // 16 rows of the group's columns of T
@@ -231,6 +221,13 @@ __global__ __launch_bounds__(256) void cv_small_kernel(const T* __restrict__ Tm,
     var[sIdx[j]] = ss;
   }
   __syncthreads();
+  if (minv && b <= ld) {  // the tap: M^-1 (lower, row-major, leading dimension ld) of this fold for the caller's own passes
+    double* out = minv + ((long)blockIdx.z * ngroups + g) * ld * ld;
+    for (int e = t; e < b * b; e += 256) {
+      const int i = e / b, j = e % b;
+      out[(long)i * ld + j] = i == j ? sD[i] : (i > j ? sG[j * LD + i] : 0.0);
+    }
+  }
   if (t < b) {  // u = M^-1 alpha_B
     double u = sD[t] * sA[t];
     for (int j = 0; j < t; ++j) u += sG[j * LD + t] * sA[j];
@@ -480,6 +477,10 @@ size_t cv_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
 
+int cross_validate_chunk_groups(long N, int B, int ngroups, long max_group) {
+  return max_group <= CV_SMALL ? 0 : cv_chunk_groups(N, B, ngroups, cv_block_order(max_group));
+}
+
 size_t cross_validate_workspace_bytes(long N, int B, int ngroups, long max_group) {
   if (max_group <= 1) return cv_align(sizeof(double) * (size_t)(N / CV_SLAB) * (size_t)N * (size_t)B);
   if (max_group <= CV_SMALL) return 256;
@@ -491,7 +492,7 @@ size_t cross_validate_workspace_bytes(long N, int B, int ngroups, long max_group
 
 template <typename T>
 int cross_validate(const T* Tm, const T* S, const T* alpha, long N, int n, const int* order, const int* start, int ngroups,
-                   long max_group, void* work, double* resid, double* var, double* lpd, int* info, hipStream_t s, Batch bt) {
+                   long max_group, void* work, double* resid, double* var, double* lpd, int* info, hipStream_t s, Batch bt, const CvTap* tap) {
   const unsigned Bz = (unsigned)bt.B;
   hipError_t e;
   // observations that no group holds out keep zeros
@@ -507,7 +508,7 @@ int cross_validate(const T* Tm, const T* S, const T* alpha, long N, int n, const
   }
   if (max_group <= CV_SMALL) {
     cv_small_kernel<T><<<dim3((unsigned)ngroups, 1, Bz), 256, 0, s>>>(Tm, S, N, bt.ws, alpha, bt.ns, n, order, start, ngroups, resid, var,
-                                                                      lpd, info);
+                                                                      lpd, info, tap ? tap->minv : nullptr, tap ? tap->ld : 0);
     return (int)hipGetLastError();
   }
   const long M = cv_block_order(max_group);
@@ -543,13 +544,17 @@ int cross_validate(const T* Tm, const T* S, const T* alpha, long N, int n, const
     cv_cols_kernel<<<dim3((unsigned)((M + 255) / 256), 1, Z), 256, 0, s>>>(ck, sl, bt.ns, order, start, slots, resid, var);
     cv_lpd_kernel<<<dim3(1, 1, Z), 256, 0, s>>>(ck, sl, bt.ns, order, start, slots, lpd, info);
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
+    if (tap && tap->chunk) {  // the chunk's blocks are complete on the stream: the caller's passes on them, before the next chunk
+      const CvBlocks cb{slots + sl.Tm, slots + sl.e, sl.elems, M, g0, C};
+      if ((rc = tap->chunk(tap->ctx, cb))) return rc;
+    }
   }
   return 0;
 }
 
 template int cross_validate<double>(const double*, const double*, const double*, long, int, const int*, const int*, int, long, void*,
-                                    double*, double*, double*, int*, hipStream_t, Batch);
+                                    double*, double*, double*, int*, hipStream_t, Batch, const CvTap*);
 template int cross_validate<float>(const float*, const float*, const float*, long, int, const int*, const int*, int, long, void*, double*,
-                                   double*, double*, int*, hipStream_t, Batch);
+                                   double*, double*, int*, hipStream_t, Batch, const CvTap*);
 
 }  // namespace dgp

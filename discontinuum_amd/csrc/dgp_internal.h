@@ -285,9 +285,40 @@ int slopes_reduce(int P, const T* V, const T* Ks, long N, long Mp, int m, const 
 // group has at most max_group members.  resid / var [B][n], lpd / info [B][ngroups], all double / int whatever T is; `work`:
 // cross_validate_workspace_bytes.  Reads T, S, alpha only.
 size_t cross_validate_workspace_bytes(long N, int B, int ngroups, long max_group);
+// A TAP on the fold algebra for passes that need more of a fold than cross_validate's own results (dgp_influence.hip): the factor
+// M of G_B = M M^T, inverted.  Groups of up to 64 (the LDS route): M^-1 of fold g of a site is written lower, row-major, to
+// minv[(site ngroups + g) ld ld ...] (ld >= max_group; a failed fold writes nothing).  Larger groups (the block route): `chunk`
+// is called once per chunk of C folds g0 .. g0 + C - 1, after the chunk's launches are on the stream and before the next chunk
+// reuses the blocks; it enqueues its own work on the same stream and returns 0 or an error.  Neither changes what
+// cross_validate computes.
+struct CvBlocks {
+  const double* minv;  // slot z = site C + c: M^-1 (M x M row-major, lower, identity pad) at minv + z stride
+  const double* e;     // e_B = G_B^-1 alpha_B in the fold's own order (M entries) at e + z stride
+  long stride, M;
+  int g0, C;
+};
+struct CvTap {
+  double* minv = nullptr;
+  long ld = 0;
+  int (*chunk)(void* ctx, const CvBlocks& blocks) = nullptr;
+  void* ctx = nullptr;
+};
+int cross_validate_chunk_groups(long N, int B, int ngroups, long max_group);  // folds per chunk of the block route (0: another route)
 template <typename T>
 int cross_validate(const T* Tm, const T* S, const T* alpha, long N, int n, const int* order, const int* start, int ngroups,
-                   long max_group, void* work, double* resid, double* var, double* lpd, int* info, hipStream_t s, Batch bt);
+                   long max_group, void* work, double* resid, double* var, double* lpd, int* info, hipStream_t s, Batch bt,
+                   const CvTap* tap = nullptr);
+#ifdef __HIPCC__
+// group g of a site = order[s0 .. s0 + b): bounds clamped to the site and to the route's largest group
+__device__ __forceinline__ void cv_bounds(const int* __restrict__ start, int g, int n, int cap, int& s0, int& b) {
+  int a = start[g], e = start[g + 1];
+  a = min(max(a, 0), n);
+  e = min(max(e, a), n);
+  s0 = a;
+  b = min(e - a, cap);
+}
+__device__ __forceinline__ int cv_index(const int* __restrict__ order, int p, int n) { return min(max(order[p], 0), n - 1); }
+#endif
 
 // ---- dgp_fisher.hip: F_ab = 1/2 tr(K^^-1 D_a K^^-1 D_b) over the nt kernel directions dK/dtheta_p and `ndiag` diagonal
 // directions diag [B][ndiag][n], from T = L^-1.  `work`: fisher_site_bytes per site; F [B][nt + ndiag][nt + ndiag] doubles.
@@ -310,9 +341,32 @@ struct SensLayout {
   size_t Xst, D, Ks, V, beta, G, pc, pg, pq, total;  // byte offsets into a site's slice
 };
 SensLayout sens_layout(long N, long Mp, int d, int nt, int ndiag, int nrhs, size_t elem);
+// its beta = T^T V alone (V, beta: N x Mp row-major at site stride wbs): 128 x 128 tiles, 64 x 64 ones while the launch has too few
+// (sens_small_tiles: lauum's rule and selector)
+inline bool sens_small_tiles(long N, long Mp, const Batch& bt) {
+  return (N / DGP_TILE_HOST) * (Mp / DGP_TILE_HOST) * bt.B <= bt.tuning().lauum64_max_tiles;
+}
+template <typename T>
+int sens_beta(const T* Tm, long N, const T* V, long Mp, T* beta, hipStream_t s, Batch bt, long wbs);
 template <typename T>
 int predict_sensitivity(int model, int d, const T* Xt, const T* Tm, const T* alpha, long N, int n, const double* theta, long Mp, int m,
                         const T* diag, int ndiag, const T* rhs, int nrhs, void* work, const SensLayout& L, double* dmean, double* dvar,
                         hipStream_t s, Batch bt, void* pre_scratch);
+
+// ---- dgp_influence.hip: the exact change of every period sum (and, for a linear target, of its variance) when a fold of
+// observations is deleted at fixed hyperparameters.  `work`: an influence_layout; its per-site slices' Xst and Ks are already
+// filled (pack_x + gram_cross).  Reads Tm, S (when valid, else null) and alpha only; every result is double.
+struct InfluenceLayout {
+  size_t Xst, Ks, V, beta, slice;                                   // byte offsets inside a site's slice, and its size
+  size_t resid, var, lpd, part, pmax, bg, cv, minv, panel, z, total;  // byte offsets of the shared areas behind the B slices
+  int nslab, slab_len, chunk;                                       // slabs of test points per fold; folds per chunk (block route)
+  long order;                                                       // block order of the block route
+};
+InfluenceLayout influence_layout(long N, int B, int n, int d, long Mp, int m, int nfolds, long max_fold, int ngroups, size_t elem);
+template <typename T>
+int deletion_influence(const T* Tm, const T* S, const T* alpha, long N, int n, long Mp, int m, const int* order, const int* start,
+                       int nfolds, long max_fold, int mode, const double* a, const double* scale, const int* group, int ngroups,
+                       const double* inv_sd, void* work, const InfluenceLayout& L, double* dload, double* dvar, double* shift,
+                       int* info, hipStream_t s, Batch bt);
 
 }  // namespace dgp

@@ -364,6 +364,18 @@ __global__ __launch_bounds__(256) void sens_finish_kernel(const T* __restrict__ 
   for (int e = 0; e < nvar; ++e) dvar[(long)(nt + e) * m + j] = slabs(R + e);
 }
 
+template <typename T>
+int sens_beta(const T* Tm, long N, const T* V, long Mp, T* beta, hipStream_t s, Batch bt, long wbs) {
+  const unsigned Bz = (unsigned)bt.B;
+  if (sens_small_tiles(N, Mp, bt))  // fewer 128-tiles than CUs: lauum's rule
+    sens_beta64_kernel<T><<<dim3((unsigned)(Mp / 64), (unsigned)(N / 64), Bz), 256, 0, s>>>(Tm, N, V, Mp, beta, bt.ws, wbs);
+  else
+    sens_beta_kernel<T><<<dim3((unsigned)(Mp / DGP_TILE), (unsigned)(N / DGP_TILE), Bz), 256, 0, s>>>(Tm, N, V, Mp, beta, bt.ws, wbs);
+  return (int)hipGetLastError();
+}
+template int sens_beta<double>(const double*, long, const double*, long, double*, hipStream_t, Batch, long);
+template int sens_beta<float>(const float*, long, const float*, long, float*, hipStream_t, Batch, long);
+
 // ------------------------------------------------------------------------------------------
 // `work`: one site's slice (sens_layout), Xst and Ks already filled by the caller (pack_x + gram_cross: the hyperparameters of a
 // batch of more than 8 are in pre_scratch).  wbs / ps: the slices' stride in plan-dtype elements / doubles.
@@ -391,9 +403,8 @@ int predict_sensitivity(int model, int d, const T* Xt, const T* Tm, const T* alp
   int rc = fisher_dk<T>(model, d, Xt, N, n, theta, D, s, bt, wbs, pre_scratch, nullptr, false);
   if (rc) return rc;
   if ((rc = predict_v<T>(Tm, N, Ks, Mp, V, s, bt, wbs))) return rc;
-  const bool small = nbk * (Mp / DGP_TILE) * bt.B <= bt.tuning().lauum64_max_tiles;  // fewer 128-tiles than CUs: lauum's rule
-  if (small) sens_beta64_kernel<T><<<dim3((unsigned)(Mp / 64), (unsigned)nb64, Bz), 256, 0, s>>>(Tm, N, V, Mp, beta, bt.ws, wbs);
-  else sens_beta_kernel<T><<<dim3((unsigned)(Mp / DGP_TILE), (unsigned)nbk, Bz), 256, 0, s>>>(Tm, N, V, Mp, beta, bt.ws, wbs);
+  const bool small = sens_small_tiles(N, Mp, bt);
+  if ((rc = sens_beta<T>(Tm, N, V, Mp, beta, s, bt, wbs))) return rc;
   sens_gcols_kernel<T><<<dim3((unsigned)(N / 4), (unsigned)R, Bz), 256, 0, s>>>(D, N, n, nt, ndiag, alpha, diag, rhs, (long)ndiag * n,
                                                                               (long)nrhs * n, G, bt.ws, wbs, ps, bt.ns);
   const dim3 slabs((unsigned)(Mp / 64), SENS_SPLIT, Bz);

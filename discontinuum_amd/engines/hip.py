@@ -734,6 +734,19 @@ class MarginalHIP(BaseModel):
                       given=given, freq=freq, sample_var=sample_var, max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes)
 
     @is_fitted
+    def influence(self, covariates, weights, folds="loo", freq="YE", max_bytes=None):
+        """What the samples in hand were worth: for every fold of training observations (``folds``: everything
+        ``cross_validate`` accepts) the exact change of every period sum sum_{i in period} weights_i target_i over the points of
+        ``covariates`` had that fold not been sampled -- case deletion at fixed hyperparameters in one ``predict`` and one
+        ``dgp_deletion_influence`` pass, where the reference would refit once per deletion.  -> Dataset on (``fold``,
+        ``period``) with ``load_change`` (without the fold minus with it), ``relative_change``, ``load_without``,
+        ``fold_size``, ``max_shift``, ``info``, ``se_jackknife`` and, for linear targets, ``var_change`` / ``se_without``.
+        See ``discontinuum_amd.influence.influence``."""
+        from ..influence import influence
+
+        return influence(self, covariates, weights, folds=folds, freq=freq, max_bytes=max_bytes)
+
+    @is_fitted
     def duration_curve(self, covariates, levels=None, above=True, ci=0.95, pred_noise=False):
         """Fraction of the record ``covariates`` on which the target exceeds each of ``levels`` (default: 21 quantiles of
         the posterior mean), with the exact standard error of that fraction and approximate ``ci`` intervals -- for a

@@ -120,6 +120,13 @@ class LoadestGPMarginalHIP(LoadestDataMixin, MarginalHIP):
                                     max_bytes=max_bytes)
 
     @is_fitted
+    def sample_influence(self, daily, folds="loo", freq="YE", max_bytes=None):
+        """What the samples in hand were worth: the exact change of every period's LOAD (kg; the flux weights of
+        ``annual_flux``) had each fold of observations not been sampled -- ``MarginalHIP.influence``, named to mirror
+        ``sample_value``."""
+        return super().influence(daily, self._flux_weights(daily), folds=folds, freq=freq, max_bytes=max_bytes)
+
+    @is_fitted
     def design_value(self, daily, samples, freq="YE", sample_var=None, return_cov=False, max_bytes=None):
         """The exact expected value of sampling the days ``samples`` for the period loads (kg): ``MarginalHIP.design_value``."""
         return super().design_value(daily, self._flux_weights(daily), samples, freq=freq, sample_var=sample_var,

@@ -425,6 +425,46 @@ int dgp_predict_sensitivity(dgp_plan* plan, const double* theta_host, const void
                             const void* rhs_dev, int nrhs, void* work_dev, size_t work_bytes, double* dmean_dev, double* dvar_dev,
                             void* stream);
 
+/* Exact INFLUENCE of the samples a fit already has: the change of every period sum when a fold of training observations is
+ * DELETED, for all folds at once, at the hyperparameters of the factorisation the plan holds -- the case-deletion diagnostic of
+ * regression and the delete-a-group jackknife of WRTDS practice, which the reference can only answer by one refit per deletion.
+ * With S = K^^-1 = T^T T, alpha = S r, beta = S K* and, for a fold F of f rows, G_F = S_FF = M M^T, u = M^-1 alpha_F,
+ * z_j = M^-1 beta_{F,j} (an f-vector per test point), the posterior without F is exactly
+ *     mu'_j = mu_j - z_j^T u,      C'_jl = C_jl + z_j^T z_l      (sigma'^2_j = sigma^2_j + |z_j|^2)
+ * and for the period sums of dgp_period_moments / dgp_sample_value over the m test points:
+ *     mode 1 (log target),    a_j = w_j exp(s mu_j + t + s^2 C_jj / 2):  dload[F][g] = sum_{j in g} a_j expm1(s dmu_Fj + s^2 dsigma^2_Fj / 2)
+ *     mode 0 (linear target), a_j = s w_j:                               dload[F][g] = sum_{j in g} a_j dmu_Fj
+ *                                                                        dvar [F][g] = |sum_{j in g} a_j z_j|^2    (always >= 0)
+ * Sign: the sum WITHOUT the fold minus the sum with it.  Hyperparameters, prior mean and transforms are held fixed.
+ *   theta_host, Xs_dev [batch][m][d]: as for dgp_predict_sensitivity.  order_dev [batch][n], start_dev [batch][nfolds + 1], nfolds,
+ *   max_fold: dgp_cross_validate's fold description (fold g of a site = order[start[g] .. start[g + 1]); empty folds and
+ *   observations in no fold are allowed; max_fold >= the largest fold selects the route).  a_dev [batch][m] doubles, scale_dev
+ *   [batch] doubles (s; read in mode 1), group_dev [batch][m] int32 in 0 .. ngroups - 1, non-decreasing, -1 = excluded (a violation
+ *   gives wrong numbers, never an access out of bounds), inv_sd_dev NULL or [batch][m] doubles (1 / sigma_j).
+ *   dload_dev [batch][nfolds][ngroups]; dvar_dev NULL or [batch][nfolds][ngroups] (mode 0 only); shift_dev NULL or [batch][nfolds]:
+ *   max_j |dmu_Fj| inv_sd_j over all m points (a DFFITS-style screen; needs inv_sd_dev); info_dev [batch][nfolds] int32: 0, or the
+ *   1-based failing pivot of G_F -- that fold's results are then NaN.  All results are doubles whatever the plan's dtype.
+ * Passes: K*, V = T K*, beta = T^T V (the launchers of dgp_predict_sensitivity, DGP_OPT_LAUUM64_MAX_TILES included); the fold
+ * algebra by dgp_cross_validate's three routes (max_fold == 1: column sums of squares of T, K^^-1 is never formed; <= 64: G_F, M,
+ * M^-1 in LDS; larger: blocks of order round_up(max_fold, 128) with the batched potrf / trtri, then Z = M^-1 beta_F as one product
+ * per fold on the double tile core); one sweep over (fold, test point) -- a wave per (fold, slab of points), beta read along j,
+ * expm1, a segmented sum into the periods by shuffles -- and a finish kernel that adds the slabs in order.  No floating-point
+ * atomics, fixed orders: bitwise repeatable; a site's result depends on its batch only through nfolds (it sets the slab cut of
+ * the test points), max_fold (the route) and the tile selector of beta: bitwise under the same three, to rounding otherwise;
+ * gridDim.z = sites, dgp_plan_set_site_sizes respected.  The plan is only read.
+ * work_dev: dgp_deletion_influence_workspace_bytes(plan, m, nfolds, max_fold, ngroups) bytes, 256-byte aligned: per site 3 N M
+ * plan-dtype elements (K*, V, beta; M = m rounded up to 128) plus doubles: the slab partials, n ngroups row sums,
+ * dgp_cross_validate's own area, nfolds max_fold^2 (LDS route) or 2 chunk order M (block route: panel and Z); 0 for a null plan or
+ * bad sizes (1 <= m <= 2^20, 1 <= nfolds, max_fold <= n, 1 <= ngroups <= 65535).
+ * DGP_E_ARG (null plan / argument, bad sizes, mode outside 0 / 1, dvar_dev in mode 1, shift_dev without inv_sd_dev, misaligned
+ * work area), DGP_E_WORKSPACE (work area missing or too small), DGP_E_STATE (no factorisation in the plan, or the one it holds
+ * failed: the status word of every site is read back, which synchronises the stream) -- all before any launch. */
+size_t dgp_deletion_influence_workspace_bytes(const dgp_plan* plan, int64_t m, int nfolds, int64_t max_fold, int ngroups);
+int dgp_deletion_influence(dgp_plan* plan, const double* theta_host, const void* Xs_dev, int64_t m, const int32_t* order_dev,
+                           const int32_t* start_dev, int nfolds, int64_t max_fold, int mode, const double* a_dev, const double* scale_dev,
+                           const int32_t* group_dev, int ngroups, const double* inv_sd_dev, void* work_dev, size_t work_bytes,
+                           double* dload_dev, double* dvar_dev, double* shift_dev, int32_t* info_dev, void* stream);
+
 /* The posterior of the covariance's ADDITIVE PARTS.  Both fused covariances and every generic one are sums of named terms,
  *   loadest: seasonal + covariates + residual;  rating: shift_1 + shift_2 + bend + base + periodic (the shifts and the bend
  *   carry their gates);  composite: its terms in descriptor order (an unscaled term counts outputscale 1),
