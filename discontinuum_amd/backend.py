@@ -618,6 +618,59 @@ class GPPlan:
             )
         return mean_out, cov_out
 
+    def posterior_exceedance_moments(self, theta, Xs: torch.Tensor, mu, thresh, w, groups, ngroups: int, extra_var=None,
+                                     panel_rows=None, max_bytes=None):
+        """``exceedance_moments`` of the posterior at Xs straight from the held factorisation
+        (``dgp_posterior_exceedance_moments``): the covariance is produced ``panel_rows`` rows at a time and the (M, M) matrix
+        is never formed.  Xs (m, d) -- (batch, m, d) for a batched plan, theta (batch, ntheta) --; ``mu``, ``thresh`` (L, m)
+        with 1 <= L <= 64, ``w``, ``groups``, ``ngroups``, ``extra_var`` and the results as for ``exceedance_moments``.
+        ``panel_rows``: a positive multiple of 128, or None: ``exceedance_panel_rows`` of ``max_bytes`` -- the largest panel,
+        at most M rows, whose work area fits; a ``ValueError`` names the bytes when 128 rows do not.  Short panels cost time:
+        every chunk of 8 levels produces all panels again (N m^2 matrix-core flop per chunk), and a panel launch only has the
+        parallelism of its own rows -- measured 3 x the dense path's time with 512-row panels at m = 14 610 (EXPERIMENTS.md) --
+        so give ``max_bytes`` what the device can spare, above all with many levels.  The work area (2 N M + R M plan-dtype elements and M P min(L, 8) + 2 M (L + 1) doubles per
+        site) is kept between calls; a ``RuntimeError`` names its bytes when it exceeds the free device memory."""
+        lead, m = self._check_xs(Xs)
+        th = _theta_array(theta, self.ntheta * self.batch)
+        P = int(ngroups)
+        dev = self.device
+        with torch.cuda.device(dev):
+            mu_t, w_t, g_t, ev_t, _ = _moment_inputs(dev, self.dtype, lead, m, mu, w, groups, extra_var)
+            u_t = torch.as_tensor(thresh).to(dev, torch.float64).contiguous()
+            if u_t.dim() != len(lead) + 2 or tuple(u_t.shape[:-2]) != lead or u_t.shape[-1] != m:
+                raise ValueError(f"thresh must have shape {lead + ('L', m)}")
+            L = int(u_t.shape[-2])
+            R = self.exceedance_panel_rows(m, P, L, max_bytes) if panel_rows is None else int(panel_rows)
+            if R <= 0 or R % 128:
+                raise ValueError(f"panel_rows must be a positive multiple of 128, not {panel_rows}")
+            need = int(self.lib.dgp_posterior_exceedance_moments_workspace_bytes(self._h, m, P, L, R))
+            if need == 0:
+                raise ValueError(f"bad size: m = {m}, ngroups = {P}, levels = {L} (1 <= m <= 2^20, 1 <= ngroups <= 65535, "
+                                 "1 <= levels <= 64)")
+            work = self._work_area("_pex_ws", need, "dgp_posterior_exceedance_moments", check_free=True)
+            xs = Xs.contiguous()
+            mean_out = torch.empty(lead + (L, P), dtype=torch.float64, device=dev)
+            cov_out = torch.empty(lead + (L, P, P), dtype=torch.float64, device=dev)
+            _lib.check(
+                self.lib.dgp_posterior_exceedance_moments(self._h, th, _ptr(xs), m, _ptr(mu_t), _ptr(u_t), L, _ptr(w_t), _ptr(g_t), P,
+                                                          _ptr(ev_t), R, work, need, _ptr(mean_out), _ptr(cov_out), _stream()),
+                "dgp_posterior_exceedance_moments",
+            )
+        return mean_out, cov_out
+
+    def exceedance_panel_rows(self, m: int, ngroups: int, nlevels: int, max_bytes=None) -> int:
+        """The panel height ``posterior_exceedance_moments`` picks for m points, ``ngroups`` groups and ``nlevels`` levels under
+        ``max_bytes`` (default ``loads.DEFAULT_MAX_BYTES``): ``stream_panel_rows`` on the sizes
+        ``dgp_posterior_exceedance_moments_workspace_bytes`` reports."""
+        if max_bytes is None:
+            from .loads import DEFAULT_MAX_BYTES as max_bytes
+        size = lambda R: int(self.lib.dgp_posterior_exceedance_moments_workspace_bytes(self._h, int(m), int(ngroups), int(nlevels), R))  # noqa: E731
+        if size(128) == 0:
+            raise ValueError(f"bad size: m = {m}, ngroups = {ngroups}, levels = {nlevels} (1 <= m <= 2^20, 1 <= ngroups <= 65535, "
+                             "1 <= levels <= 64)")
+        M = int(self.lib.dgp_padded_n(int(m)))
+        return stream_panel_rows(size(128), size(256) - size(128) if M > 128 else 0, M, max_bytes)
+
     def _vjp_workspace(self, m):
         need = int(self.lib.dgp_mean_vjp_workspace_bytes(self._h, m))
         return self._work_area("_vjp_ws", need, "mean / vjp"), need
@@ -774,6 +827,21 @@ def period_moments(cov: torch.Tensor, m: int, mu: torch.Tensor, scale2, w: torch
         "dgp_period_moments",
     )
     return mean_out, cov_out
+
+
+def stream_panel_rows(need128: int, step: int, M: int, max_bytes: int) -> int:
+    """Rows of the covariance panel ``GPPlan.posterior_exceedance_moments`` picks for a byte budget: the work area is
+    ``need128`` bytes with a panel of 128 rows and grows by ``step`` bytes per further 128 rows (one panel row block of
+    every site), so the answer is 128 min(M / 128, 1 + (max_bytes - need128) // step) -- the largest multiple of 128, at
+    most the padded record length ``M``, whose work area fits ``max_bytes``.  ``ValueError`` naming the bytes when
+    ``need128`` itself exceeds the budget."""
+    if need128 > max_bytes:
+        raise ValueError(f"the streamed exceedance pass needs a work area of {need128} bytes with the smallest panel (128 "
+                         f"rows), which exceeds max_bytes = {max_bytes}")
+    blocks = M // 128
+    if step > 0:
+        blocks = min(blocks, 1 + (int(max_bytes) - need128) // step)
+    return 128 * blocks
 
 
 def exceedance_moments(cov: torch.Tensor, m: int, mu: torch.Tensor, thresh: torch.Tensor, w: torch.Tensor, groups: torch.Tensor,

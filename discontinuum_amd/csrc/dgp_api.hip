@@ -1028,6 +1028,27 @@ static int post_period(dgp_plan* p, const double* theta, const void* Xs, int64_t
                                      group, P, (const T*)ev, pm, mean_out, cov_out, s, p->pre);
 }
 
+// streamed exceedance moments: the prediction's work area as for post_period, one covariance panel of R x M elements per site,
+// then the moment pass's work area
+static size_t exceed_panel_bytes(const dgp_plan* p, int64_t m, int panel_rows) {
+  return align_up(p->elem * (size_t)exceedance_panel_rows((long)m, panel_rows) * (size_t)round_up(m, DGP_TILE_HOST));
+}
+template <typename T>
+static int post_exceed(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const void* mu, const double* thresh, int L,
+                       const double* w, const int32_t* group, int P, const void* ev, int panel_rows, void* work, double* mean_out,
+                       double* cov_out, hipStream_t s) {
+  const size_t pb = exceed_panel_bytes(p, m, panel_rows);
+  T* panel = (T*)((char*)work + predict_site_bytes(p, m) * (size_t)p->B);
+  double* ex = (double*)((char*)panel + pb * (size_t)p->B);
+  T *V, *Xst, *vpad;
+  long wbs;
+  // the latent mean the prediction also writes (B x m elements) lands in the moment pass's area, which its first launches reset
+  int rc = predict_common<T>(p, theta, Xs, m, work, ex, &V, &Xst, &vpad, &wbs, s);
+  if (rc) return rc;
+  return posterior_exceedance_moments<T>(p->model, p->d, V, p->N, (long)m, p->B, Xst, vpad, wbs, theta, (const T*)mu, thresh, L, w, group,
+                                         P, (const T*)ev, panel_rows, panel, (long)(pb / sizeof(T)), ex, mean_out, cov_out, s, p->pre);
+}
+
 // ---- posterior products of `planes` side-by-side cross Grams per test point: the covariance's additive parts (dgp_terms.hip,
 // planes = C) and the value with its input derivatives (dgp_slopes.hip, planes = P = 1 + ncols).  Work area per site: the test
 // points' SoA copy, the cross Grams side by side (N x planes M), V = T Ks of the same shape, `prior_rows` rows of M prior
@@ -1353,6 +1374,43 @@ int dgp_exceedance_moments(int dtype, const void* cov, int64_t m, int batch, con
                      : exceedance_moments<float>((const float*)cov, m, batch, (const float*)mu, thresh, nlevels, w, group, ngroups,
                                                  (const float*)extra_var, (double*)work, mean_out, cov_out, s);
   return wrap(rc, "dgp_exceedance_moments");
+}
+
+size_t dgp_posterior_exceedance_moments_workspace_bytes(const dgp_plan* p, int64_t m, int ngroups, int nlevels, int panel_rows) {
+  if (!p || !ex_sizes_ok(m, ngroups, nlevels, p->B) || panel_rows <= 0 || panel_rows % DGP_TILE_HOST != 0) return 0;
+  return (predict_site_bytes(p, m) + exceed_panel_bytes(p, m, panel_rows)) * (size_t)p->B +
+         exceedance_moments_workspace_bytes(m, ngroups, nlevels, p->B);
+}
+
+int dgp_posterior_exceedance_moments(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const void* mu, const double* thresh,
+                                     int nlevels, const double* w, const int32_t* group, int ngroups, const void* extra_var,
+                                     int panel_rows, void* work, size_t work_bytes, double* mean_out, double* cov_out, void* stream) {
+  if (!p) return fail(DGP_E_ARG, "null plan");
+  if (!theta || !Xs || !mu || !thresh || !w || !group || !mean_out || !cov_out)
+    return fail(DGP_E_ARG, "dgp_posterior_exceedance_moments: null argument");
+  if (!ex_sizes_ok(m, ngroups, nlevels, p->B))
+    return fail(DGP_E_ARG, "dgp_posterior_exceedance_moments: bad size (1 <= m <= 2^20, 1 <= ngroups <= 65535, 1 <= nlevels <= 64)");
+  if (panel_rows <= 0 || panel_rows % DGP_TILE_HOST != 0)
+    return fail(DGP_E_ARG, "dgp_posterior_exceedance_moments: panel_rows must be a positive multiple of 128");
+  if (!p->have_factor)
+    return fail(DGP_E_STATE, "dgp_posterior_exceedance_moments: no factorisation in the plan (call dgp_factorize or dgp_fit_step)");
+  DGP_CHECK_PLAN(p);
+  if (!work || work_bytes < dgp_posterior_exceedance_moments_workspace_bytes(p, m, ngroups, nlevels, panel_rows))
+    return fail(DGP_E_WORKSPACE, "dgp_posterior_exceedance_moments: workspace missing or too small");
+  if (((uintptr_t)work & 255) != 0) return fail(DGP_E_ARG, "dgp_posterior_exceedance_moments: the work area must be 256-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  {  // a failed factorisation leaves no T to read: the sites' status words, before any launch
+    std::vector<int> info((size_t)p->B, 0);
+    hipError_t e = hipMemcpy2DAsync(info.data(), sizeof(int), p->info, p->site_bytes, sizeof(int), (size_t)p->B, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hipfail(e, "dgp_posterior_exceedance_moments");
+    for (int b = 0; b < p->B; ++b)
+      if (info[(size_t)b] != 0)
+        return fail(DGP_E_STATE, "dgp_posterior_exceedance_moments: the factorisation the plan holds failed (matrix not positive definite)");
+  }
+  const int rc = DGP_BY_DTYPE(p, post_exceed<double>(p, theta, Xs, m, mu, thresh, nlevels, w, group, ngroups, extra_var, panel_rows, work, mean_out, cov_out, s),
+                              post_exceed<float>(p, theta, Xs, m, mu, thresh, nlevels, w, group, ngroups, extra_var, panel_rows, work, mean_out, cov_out, s));
+  return wrap(rc, "dgp_posterior_exceedance_moments");
 }
 
 static bool sv_sizes_ok(int64_t m, int ngroups, int nrows, int nterms, int batch) {

@@ -1533,18 +1533,20 @@ int predict_var(const T* Tm, long N, const T* Ks, long M, T* V, const T* alpha, 
   return (int)hipGetLastError();
 }
 
-// cov[i,j] = Kss[i,j] - sum_k V[k,i] V[k,j]  (i >= j tiles), k over all N rows of V (N x M)
+// cov[i,j] = Kss[i,j] - sum_k V[k,i] V[k,j]  (i >= j tiles), k over all N rows of V (N x M).  A row range: the tiles t0, t0 + 1,
+// ... of the row-major triangle (whole tile rows from bi0 on) into a buffer whose first row is tile row bi0 (site stride cs).
 template <typename T>
-__global__ __launch_bounds__(256, (TileCore<T, false, false>::OCC)) void posterior_cov_kernel(const T* __restrict__ V, long N, long M, T* __restrict__ cov, long wbs) {
+__global__ __launch_bounds__(256, (TileCore<T, false, false>::OCC)) void posterior_cov_kernel(const T* __restrict__ V, long N, long M, T* __restrict__ cov, long wbs,
+                                                                                             long cs, int t0, int bi0) {
   using K = TileCore<T, false, false>;
   using G = typename K::G;
   __shared__ T smem[K::SMEM_ELEMS];
   V = site(V, wbs);  // batched plans: V in the caller's work area, cov [batch][M][M]
-  cov = site(cov, M * M);
+  cov = site(cov, cs);
   int bi, bj;
-  tri_decode(blockIdx.x, bi, bj);
+  tri_decode((int)blockIdx.x + t0, bi, bj);
   typename G::acc_t acc[G::MI][G::NI];
-  T* C = cov + (long)bi * NB * M + (long)bj * NB;
+  T* C = cov + (long)(bi - bi0) * NB * M + (long)bj * NB;
   typename G::acc_t keep[G::MI][G::NI];
   trailing_begin<T, G, K::DMA>(acc, keep, C, M);
   K::run(V + (long)bi * NB, M, V + (long)bj * NB, M, (int)(N / 16), smem, acc);
@@ -1553,8 +1555,14 @@ __global__ __launch_bounds__(256, (TileCore<T, false, false>::OCC)) void posteri
 
 template <typename T>
 int posterior_cov(const T* V, long N, long M, T* cov, hipStream_t s, int B, long wbs) {
-  const int nb = (int)(M / NB);
-  posterior_cov_kernel<T><<<dim3((unsigned)(nb * (nb + 1) / 2), 1, (unsigned)B), 256, 0, s>>>(V, N, M, cov, wbs);
+  return posterior_cov_panel<T>(V, N, M, cov, 0, M, M * M, s, B, wbs);
+}
+
+template <typename T>
+int posterior_cov_panel(const T* V, long N, long M, T* panel, long row0, long row1, long panel_stride, hipStream_t s, int B, long wbs) {
+  const long b0 = row0 / NB, b1 = row1 / NB;
+  const long t0 = b0 * (b0 + 1) / 2, t1 = b1 * (b1 + 1) / 2;
+  posterior_cov_kernel<T><<<dim3((unsigned)(t1 - t0), 1, (unsigned)B), 256, 0, s>>>(V, N, M, panel, wbs, panel_stride, (int)t0, (int)b0);
   return (int)hipGetLastError();
 }
 
@@ -1590,6 +1598,7 @@ int sample_draws(const T* L, long M, const T* Z, long Q, const T* mean, int m, i
 
 #define DGP_INST(T)                                                                                              \
   template int posterior_cov<T>(const T*, long, long, T*, hipStream_t, int, long);                                          \
+  template int posterior_cov_panel<T>(const T*, long, long, T*, long, long, long, hipStream_t, int, long);                                          \
   template int sample_draws<T>(const T*, long, const T*, long, const T*, int, int, T*, hipStream_t);             \
   template int symv_lower<T>(const T*, long, const T*, int, const T*, T*, T*, T*, hipStream_t, Batch, long);     \
   template int potrf<T>(T*, long, T*, T*, int*, int, hipStream_t, hipStream_t, hipEvent_t*, PotrfObservers*, Batch, int);               \

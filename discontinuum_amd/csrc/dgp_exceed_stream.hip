@@ -1,0 +1,206 @@
+// dgp_exceed_stream.hip -- the moments of dgp_exceedance_moments straight from the held factorisation, with the posterior
+// covariance C = K(Xs, Xs) - V^T V produced R rows at a time and never stored whole (dgp_posterior_exceedance_moments).
+//
+// V = L^-1 K(X, Xs), the test points' SoA coordinates and the predicted variance are what the prediction's first stages leave in
+// the work area (as for dgp_posterior_period_moments).  Panel q holds the rows [q R, (q + 1) R) of C and the columns
+// 0 .. (q + 1) R - 1, in a buffer of R x M elements: gram_sym's tiles of K(Xs, Xs) followed by posterior_cov's trailing update,
+// both on the tile rows of the panel only -- the launches, the k order and hence (fp64) the bits of dgp_posterior_cov.  Every
+// unordered pair (i < j) lies in exactly one panel, j's.  Launches (gridDim.z = sites, one stream, no floating-point atomics):
+//   init, prep   dgp_exceed.hip's, once; the diagonal is the predicted variance (sigma never comes from the panel)
+//   per chunk of levels (8 / 4 / 2 / 1, a function of L alone):
+//     zero       Y[l][i][h] = 0 for the levels of the chunk: the reduce pass finds numbers wherever it reads, whatever the work
+//                area held before and however many excluded rows a panel has
+//     per panel, in ascending order:
+//       gram, cov   the panel of C
+//       pairs       one workgroup per (64-row block below the panel's end, group h): Y[l][i][h] += sum_j w_j D(z_il, z_jl, rho_ij)
+//                   over the j of h that ex_pairs_kernel takes for row i and whose pair (i, j) lies in this panel: for g(i) = h
+//                   the j < i, when i is a row of the panel (read as C[i][j]); for g(i) < h the j of h among the panel's rows
+//                   (read as C[j][i]).  One workgroup owns an entry of Y in a launch and the launches are ordered: a plain
+//                   read-modify-write, every sum in a fixed order.
+//     reduce     dgp_exceed.hip's
+// Repeated calls are bitwise equal and a site's numbers do not depend on its batch; different R regroup the sums over j.
+// The quadrature never runs beside live MFMA accumulators: it reads C back from the panel (L2 / HBM, R M elements).
+#include "dgp_bvn.h"
+#include "dgp_internal.h"
+
+namespace dgp {
+
+namespace {
+
+__global__ __launch_bounds__(256) void exs_zero_kernel(double* work, long ws, long M, int P, int L, int LC) {
+  const ExWork wk(work, ws, M, P, L);
+  const long count = (long)LC * M * P;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long)gridDim.x * 256) wk.Y[i] = 0.0;
+}
+
+// levels l0 .. l0 + LC of Y, the pairs of the panel of rows [p0, p1) (row i of C at panel[(i - p0) M]); see the file header
+template <typename T, int LC>
+__global__ __launch_bounds__(256) void exs_pairs_kernel(const T* __restrict__ panel, long pstride, long M, int m, int P, int L, int l0,
+                                                        int p0, int p1, const int* __restrict__ group, double* __restrict__ work,
+                                                        long ws) {
+  const int rb = blockIdx.x, h = blockIdx.y, z = blockIdx.z;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const ExWork wk(work, ws, M, P, L);
+  const int r0 = rb * EX_ROWS;
+  int c0, c1;
+  ex_range(wk.se, h, c0, c1);
+  const int j0 = c0 > p0 ? c0 : p0, j1 = c1 < p1 ? c1 : p1;  // the j of h among the panel's rows
+  const bool lowp = r0 >= p0 && r0 < c1 && r0 + EX_ROWS > c0;  // rows of the panel that may lie in h
+  const bool upp = j0 < j1 && r0 < c0;                        // rows of earlier groups, and h has rows in the panel
+  if (!lowp && !upp) return;
+  ex_tables_init();
+  __shared__ double low[LC][EX_ROWS], up[4][LC][EX_ROWS];
+  const T* C = panel + (long)z * pstride;
+  const int* gz = group + (long)z * m;
+  const double* zs = wk.z + (long)l0 * M;
+  const double* ps = wk.p + (long)l0 * M;
+  __syncthreads();
+
+  // g(i) = h, i a row of the panel: the j < i of the group, C[i][j]; a wave per row, lanes along the row
+  for (int ii = wave; ii < EX_ROWS; ii += 4) {
+    const int i = r0 + ii;
+    double acc[LC];
+#pragma unroll
+    for (int l = 0; l < LC; ++l) acc[l] = 0.0;
+    if (lowp && i < m && gz[i] == h) {
+      const T* row = C + (long)(i - p0) * M;
+      const double si = wk.sinv[i];
+      double zi[LC], pi[LC];
+#pragma unroll
+      for (int l = 0; l < LC; ++l) {
+        zi[l] = zs[(long)l * M + i];
+        pi[l] = ps[(long)l * M + i];
+      }
+      for (int j = c0 + lane; j < i; j += 64) {
+        double zj[LC], pj[LC], D[LC];
+#pragma unroll
+        for (int l = 0; l < LC; ++l) {
+          zj[l] = zs[(long)l * M + j];
+          pj[l] = ps[(long)l * M + j];
+        }
+        bvn_excess<LC>(zi, zj, pi, pj, (double)row[j] * si * wk.sinv[j], D);
+        const double wj = wk.w[j];
+#pragma unroll
+        for (int l = 0; l < LC; ++l) acc[l] = __builtin_fma(wj, D[l], acc[l]);
+      }
+    }
+#pragma unroll
+    for (int l = 0; l < LC; ++l) {
+      const double v = ex_wave_sum(acc[l]);
+      if (lane == 0) low[l][ii] = v;
+    }
+  }
+
+  // 0 <= g(i) < h: the j of the group among the panel's rows (all beyond i), C[j][i]; lanes along i, wave q takes
+  // j = j0 + q, j0 + q + 4, ...
+  {
+    const int i = r0 + lane;
+    double acc[LC];
+#pragma unroll
+    for (int l = 0; l < LC; ++l) acc[l] = 0.0;
+    const int gi = i < m ? gz[i] : -1;
+    if (upp && gi >= 0 && gi < h) {
+      const T* col = C + i;
+      const double si = wk.sinv[i];
+      double zi[LC], pi[LC];
+#pragma unroll
+      for (int l = 0; l < LC; ++l) {
+        zi[l] = zs[(long)l * M + i];
+        pi[l] = ps[(long)l * M + i];
+      }
+      for (int j = j0 + wave; j < j1; j += 4) {
+        double zj[LC], pj[LC], D[LC];
+#pragma unroll
+        for (int l = 0; l < LC; ++l) {
+          zj[l] = zs[(long)l * M + j];
+          pj[l] = ps[(long)l * M + j];
+        }
+        bvn_excess<LC>(zi, zj, pi, pj, (double)col[(long)(j - p0) * M] * si * wk.sinv[j], D);
+        const double wj = wk.w[j];
+#pragma unroll
+        for (int l = 0; l < LC; ++l) acc[l] = __builtin_fma(wj, D[l], acc[l]);
+      }
+    }
+#pragma unroll
+    for (int l = 0; l < LC; ++l) up[wave][l][lane] = acc[l];
+  }
+  __syncthreads();
+  if (tid < EX_ROWS)
+#pragma unroll
+    for (int l = 0; l < LC; ++l)
+      wk.Y[((long)l * M + r0 + tid) * P + h] += low[l][tid] + ((up[0][l][tid] + up[1][l][tid]) + (up[2][l][tid] + up[3][l][tid]));
+}
+
+template <typename T, int LC>
+int exs_chunk(int model, int d, const T* V, long N, long M, int m, int B, const T* Xst, const T* zero, long wbs, const double* theta,
+              long R, T* panel, long pstride, int P, int L, int l0, const int* group, double* work, long ws, double* mean_out,
+              double* cov_out, hipStream_t s, void* pre_scratch) {
+  const long count = (long)LC * M * P;
+  const long zb = (count + 255) / 256;
+  exs_zero_kernel<<<dim3((unsigned)(zb < 65536 ? zb : 65536), 1, (unsigned)B), 256, 0, s>>>(work, ws, M, P, L, LC);
+  Batch wb;
+  wb.B = B;
+  wb.ws = wbs;
+  for (long p0 = 0; p0 < M; p0 += R) {
+    const long p1 = p0 + R < M ? p0 + R : M;
+    int rc = gram_sym_panel<T>(model, d, Xst, M, m, theta, zero, panel, p0, p1, s, wb, pre_scratch, pstride, wbs);
+    if (rc) return rc;
+    if ((rc = posterior_cov_panel<T>(V, N, M, panel, p0, p1, pstride, s, B, wbs))) return rc;
+    exs_pairs_kernel<T, LC><<<dim3((unsigned)(p1 / EX_ROWS), (unsigned)P, (unsigned)B), 256, 0, s>>>(panel, pstride, M, m, P, L, l0,
+                                                                                                   (int)p0, (int)p1, group, work, ws);
+  }
+  exceedance_reduce(M, B, P, L, l0, LC, work, mean_out, cov_out, s);
+  return (int)hipGetLastError();
+}
+
+}  // namespace
+
+long exceedance_panel_rows(long m, long R) {
+  const long M = round_up(m, DGP_TILE_HOST);
+  return R < M ? R : M;
+}
+
+template <typename T>
+int posterior_exceedance_moments(int model, int d, const T* V, long N, long m, int B, const T* Xst, T* var, long wbs,
+                                 const double* theta, const T* mu, const double* thresh, int L, const double* w, const int* group,
+                                 int P, const T* ev, long R, T* panel, long pstride, double* work, double* mean_out, double* cov_out,
+                                 hipStream_t s, void* pre_scratch) {
+  const long M = round_up(m, DGP_TILE_HOST);
+  const long ws = (long)(exceedance_moments_workspace_bytes(m, P, L, 1) / sizeof(double));
+  R = exceedance_panel_rows(m, R);
+  exceedance_prepare<T>(var, wbs, 1, m, B, mu, thresh, L, w, group, P, ev, work, s);
+  // the variances are read: their place now holds the zero "noise" of K(Xs, Xs), as for dgp_posterior_cov
+  hipError_t he = hipMemset2DAsync(var, sizeof(T) * (size_t)(wbs > 0 ? wbs : M), 0, sizeof(T) * M, (size_t)B, s);
+  if (he != hipSuccess) return (int)he;
+  int rc = 0;
+  for (int l0 = 0; l0 < L && !rc;) {  // chunks of 8, then 4, 2, 1 levels: a function of L alone
+    const int left = L - l0;
+    if (left >= 8) {
+      rc = exs_chunk<T, 8>(model, d, V, N, M, (int)m, B, Xst, var, wbs, theta, R, panel, pstride, P, L, l0, group, work, ws, mean_out,
+                           cov_out, s, pre_scratch);
+      l0 += 8;
+    } else if (left >= 4) {
+      rc = exs_chunk<T, 4>(model, d, V, N, M, (int)m, B, Xst, var, wbs, theta, R, panel, pstride, P, L, l0, group, work, ws, mean_out,
+                           cov_out, s, pre_scratch);
+      l0 += 4;
+    } else if (left >= 2) {
+      rc = exs_chunk<T, 2>(model, d, V, N, M, (int)m, B, Xst, var, wbs, theta, R, panel, pstride, P, L, l0, group, work, ws, mean_out,
+                           cov_out, s, pre_scratch);
+      l0 += 2;
+    } else {
+      rc = exs_chunk<T, 1>(model, d, V, N, M, (int)m, B, Xst, var, wbs, theta, R, panel, pstride, P, L, l0, group, work, ws, mean_out,
+                           cov_out, s, pre_scratch);
+      l0 += 1;
+    }
+  }
+  return rc ? rc : (int)hipGetLastError();
+}
+
+template int posterior_exceedance_moments<double>(int, int, const double*, long, long, int, const double*, double*, long, const double*,
+                                                  const double*, const double*, int, const double*, const int*, int, const double*,
+                                                  long, double*, long, double*, double*, double*, hipStream_t, void*);
+template int posterior_exceedance_moments<float>(int, int, const float*, long, long, int, const float*, float*, long, const double*,
+                                                 const float*, const double*, int, const double*, const int*, int, const float*, long,
+                                                 float*, long, double*, double*, double*, hipStream_t, void*);
+
+}  // namespace dgp

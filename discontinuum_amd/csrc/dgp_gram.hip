@@ -123,10 +123,12 @@ __global__ __launch_bounds__(256) void pack_x_kernel(const T* __restrict__ X, in
 }
 
 // ------------------------------------------------------------------------------------------
-template <typename T, typename M>
+// PANEL: the tiles t0, t0 + 1, ... of the same row-major triangle (whole tile rows) into a buffer whose first row is row `row0`
+template <typename T, typename M, bool PANEL = false>
 __global__ __launch_bounds__(256) void gram_sym_kernel(const T* __restrict__ Xt, long N, int n, const PreBatch<M> pb,
                                                        const T* __restrict__ noise, T* __restrict__ K, long bs,
-                                                       const int* __restrict__ ns, long ks, long noise_stride) {
+                                                       const int* __restrict__ ns, long ks, long noise_stride, int t0 = 0,
+                                                       long row0 = 0) {
   const typename M::Pre& pre = pb.get();
   Xt = site(Xt, bs);
   K = site(K, ks);
@@ -134,7 +136,7 @@ __global__ __launch_bounds__(256) void gram_sym_kernel(const T* __restrict__ Xt,
   n = site_n(ns, n);
   __shared__ T sfi[M::NF][64], sfj[M::NF][64];
   int bi, bj;
-  tri_decode(blockIdx.x, bi, bj);
+  tri_decode(PANEL ? (int)blockIdx.x + t0 : (int)blockIdx.x, bi, bj);
   const int t = threadIdx.x;
   exp_table_init<T>();
   if (t < 64) stage_strip<T, M>(Xt, N, (long)bi * 64, pre, sfi, t);
@@ -170,7 +172,7 @@ __global__ __launch_bounds__(256) void gram_sym_kernel(const T* __restrict__ Xt,
         out[b] = v;
       }
     }
-    store4<T>(K + gi * N + (long)bj * 64 + tx * 4, out);
+    store4<T>(K + (PANEL ? gi - row0 : gi) * N + (long)bj * 64 + tx * 4, out);
   }
 }
 
@@ -633,6 +635,19 @@ int gram_sym(int model, int d, const T* Xt, long N, int n, const double* theta, 
 }
 
 template <typename T>
+int gram_sym_panel(int model, int d, const T* Xt, long N, int n, const double* theta, const T* noise, T* K, long row0, long row1,
+                   hipStream_t s, Batch bt, void* pre_scratch, long k_stride, long noise_stride) {
+  const int nt = model_ntheta(model, d);
+  if (nt < 0) return -2;
+  const long b0 = row0 / 64, b1 = row1 / 64;
+  const long t0 = b0 * (b0 + 1) / 2, t1 = b1 * (b1 + 1) / 2;
+  DGP_DISPATCH_MODEL(model, d, (gram_sym_kernel<T, M, true><<<dim3((unsigned)(t1 - t0), 1, (unsigned)bt.B), dim3(256), 0, s>>>(
+                                   Xt, N, n, prepare_batch<M>(theta, nt, bt.B, pre_scratch, false, s), noise, K, bt.ws, bt.ns, k_stride,
+                                   noise_stride, (int)t0, row0)));
+  return (int)hipGetLastError();
+}
+
+template <typename T>
 int gram_cross(int model, int d, const T* Xt, long N, int n, const T* Xst, long Mp, int m, const double* theta,
                T* Ks, hipStream_t s, Batch bt, long wbs, void* pre_scratch, void* pre_staging) {
   const int nt = model_ntheta(model, d);
@@ -761,6 +776,7 @@ template int gram_residual<float>(int, int, const float*, long, int, const doubl
 #define DGP_INST(T)                                                                                              \
   template int pack_x<T>(const T*, int, int, long, T*, hipStream_t, Batch);                                      \
   template int gram_sym<T>(int, int, const T*, long, int, const double*, const T*, T*, hipStream_t, Batch, void*, void*, long, long, bool); \
+  template int gram_sym_panel<T>(int, int, const T*, long, int, const double*, const T*, T*, long, long, hipStream_t, Batch, void*, long, long); \
   template int gram_cross<T>(int, int, const T*, long, int, const T*, long, int, const double*, T*, hipStream_t, Batch, long, void*, void*); \
   template int gram_diag<T>(int, int, const T*, long, int, const double*, T*, hipStream_t, Batch, long, void*);    \
   template int gram_grad<T>(int, int, const T*, long, int, const double*, const T*, const T*, T*, T*, hipStream_t, Batch, \

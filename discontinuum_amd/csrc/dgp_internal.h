@@ -62,6 +62,12 @@ int gram_sym(int model, int d, const T* Xt, long N, int n, const double* theta, 
              void* pre_staging = nullptr /* pinned host memory of the same size that outlives the copy, or null: blocking copy */,
              long k_stride = -1 /* site stride of K (default bt.ws) */, long noise_stride = -1 /* of noise (default n) */,
              bool pre_ready = false /* pre_scratch already holds this theta (gram_cross of the same call) */);
+// The tile rows [row0, row1) (multiples of 64) of the same lower triangle, columns 0 .. row1 - 1, into a panel buffer whose first
+// row is row `row0` of K (leading dimension N, site stride k_stride): gram_sym's kernel and values on a row range.  The
+// hyperparameters of a batch of more than 8 must already be in pre_scratch.
+template <typename T>
+int gram_sym_panel(int model, int d, const T* Xt, long N, int n, const double* theta, const T* noise, T* K, long row0, long row1,
+                   hipStream_t s, Batch bt, void* pre_scratch, long k_stride, long noise_stride);
 // The inference launchers take a Batch like the fit-step ones (gridDim.z = sites): training-side arrays at the plan's
 // site stride bt.ws, everything in the caller's work area (test coordinates, cross Gram, partials ...) at `wbs` elements.
 template <typename T>
@@ -210,6 +216,11 @@ int symv_lower(const T* S, long N, const T* g, int n, const T* alpha, T* beta, T
 // cov (M x M) = Kss - V^T V, lower tiles; Kss already holds K(Xs, Xs) (identity pad)
 template <typename T>
 int posterior_cov(const T* V, long N, long M, T* cov, hipStream_t s, int B = 1, long wbs = 0);
+// the tile rows [row0, row1) (multiples of 128) of the same update, into a panel buffer whose first row is row `row0` of the
+// matrix (leading dimension M, site stride panel_stride elements): the same kernel, tiles, k order and values on a row range
+template <typename T>
+int posterior_cov_panel(const T* V, long N, long M, T* panel, long row0, long row1, long panel_stride, hipStream_t s, int B = 1,
+                        long wbs = 0);
 
 // out (ndraw x m) = mean + (L Z)^T : L is M x M lower (identity pad), Z is M x Q standard normals, Q % 128 == 0
 template <typename T>
@@ -234,6 +245,21 @@ size_t exceedance_moments_workspace_bytes(long m, int P, int L, int B);
 template <typename T>
 int exceedance_moments(const T* cov, long m, int B, const T* mu, const double* thresh, int L, const double* w, const int* group,
                        int P, const T* ev, double* work, double* mean_out, double* cov_out, hipStream_t s);
+// the passes before and after the pairs pass, for dgp_exceed_stream.hip: init + prep (C_jj of site z at diag[z dsite + j dstep]),
+// and the reduce pass of the levels l0 .. l0 + LC
+template <typename T>
+void exceedance_prepare(const T* diag, long dsite, long dstep, long m, int B, const T* mu, const double* thresh, int L, const double* w,
+                        const int* group, int P, const T* ev, double* work, hipStream_t s);
+void exceedance_reduce(long M, int B, int P, int L, int l0, int LC, double* work, double* mean_out, double* cov_out, hipStream_t s);
+// ---- dgp_exceed_stream.hip: the same moments with C = K(Xs, Xs) - V^T V produced R rows at a time (R a multiple of 128; the
+// pass uses exceedance_panel_rows(m, R) = min(R, M)) into `panel` (R x M elements per site, site stride pstride) and never
+// stored whole.  V, Xst, var (overwritten), wbs, pre_scratch as for posterior_period_moments; `work` as for exceedance_moments
+long exceedance_panel_rows(long m, long R);
+template <typename T>
+int posterior_exceedance_moments(int model, int d, const T* V, long N, long m, int B, const T* Xst, T* var, long wbs,
+                                 const double* theta, const T* mu, const double* thresh, int L, const double* w, const int* group,
+                                 int P, const T* ev, long R, T* panel, long pstride, double* work, double* mean_out, double* cov_out,
+                                 hipStream_t s, void* pre_scratch);
 // out[i] = Phi2(h_i, k_i; rho_i) - Phi(h_i) Phi(k_i): the pair function of the pass above, pointwise
 int debug_bvn_excess(const double* h, const double* k, const double* rho, long count, double* out, hipStream_t s);
 

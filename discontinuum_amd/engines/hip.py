@@ -678,7 +678,7 @@ class MarginalHIP(BaseModel):
 
     @is_fitted
     def exceedance(self, covariates, threshold=None, threshold_series=None, freq="YE", above=True, fraction=False, ci=0.95,
-                   pred_noise=False, return_cov=False, max_bytes=None):
+                   pred_noise=False, return_cov=False, max_bytes=None, streamed=False):
         """Expected number of points per period of ``freq`` at which the target exceeds a data-space threshold -- days per
         year above a criterion, for a daily record -- with its exact standard error: what ``sample()``, a comparison and a
         count per period estimate by Monte Carlo, in one posterior covariance and one ``dgp_exceedance_moments`` pass.
@@ -686,14 +686,15 @@ class MarginalHIP(BaseModel):
         one of them.  ``above=False``: the complement; ``fraction=True``: divided by the points of the period.  -> Dataset
         on (``level``, ``time``) with ``mean``, ``se``, ``lower`` / ``upper`` (approximate ``ci`` interval: a beta
         distribution with the exact moments) and ``n_points``; with ``return_cov`` also the (L, P, P) covariance.  A record
-        whose m x m covariance does not fit ``max_bytes`` (default ``loads.DEFAULT_MAX_BYTES``) raises ``ValueError``.  See
-        ``discontinuum_amd.exceedance``."""
+        whose m x m covariance does not fit ``max_bytes`` (default ``loads.DEFAULT_MAX_BYTES``) raises ``ValueError``;
+        ``streamed=True`` produces the covariance a panel of rows at a time instead (``dgp_posterior_exceedance_moments``) and
+        works at any record length, with ``max_bytes`` bounding its work area.  See ``discontinuum_amd.exceedance``."""
         from ..exceedance import exceedance
         from ..loads import DEFAULT_MAX_BYTES
 
         return exceedance(self, covariates, threshold=threshold, threshold_series=threshold_series, freq=freq, above=above,
                           fraction=fraction, ci=ci, pred_noise=pred_noise, return_cov=return_cov,
-                          max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes)
+                          max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes, streamed=streamed)
 
     @is_fitted
     def sample_value(self, covariates, weights, freq="YE", sample_var=None, given=None, ci=0.95, max_bytes=None):
@@ -747,14 +748,17 @@ class MarginalHIP(BaseModel):
         return influence(self, covariates, weights, folds=folds, freq=freq, max_bytes=max_bytes)
 
     @is_fitted
-    def duration_curve(self, covariates, levels=None, above=True, ci=0.95, pred_noise=False):
+    def duration_curve(self, covariates, levels=None, above=True, ci=0.95, pred_noise=False, max_bytes=None, streamed=False):
         """Fraction of the record ``covariates`` on which the target exceeds each of ``levels`` (default: 21 quantiles of
         the posterior mean), with the exact standard error of that fraction and approximate ``ci`` intervals -- for a
         rating model over a stage record, the flow-duration curve.  -> Dataset on ``level`` with ``mean``, ``se``,
-        ``lower``, ``upper``.  See ``discontinuum_amd.exceedance.duration_curve``."""
+        ``lower``, ``upper``.  ``max_bytes`` / ``streamed``: as for ``exceedance``.  See
+        ``discontinuum_amd.exceedance.duration_curve``."""
         from ..exceedance import duration_curve
+        from ..loads import DEFAULT_MAX_BYTES
 
-        return duration_curve(self, covariates, levels=levels, above=above, ci=ci, pred_noise=pred_noise)
+        return duration_curve(self, covariates, levels=levels, above=above, ci=ci, pred_noise=pred_noise,
+                              max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes, streamed=streamed)
 
     @is_fitted
     def exceedance_probability(self, covariates, threshold, above=True, pred_noise=False):

@@ -10,7 +10,9 @@ N_g = sum_{i in g} w_i 1[f_i > u_i] have a closed form,
     Cov(N_g, N_h) = sum_{i in g} sum_{j in h} w_i w_j (Phi2(z_i, z_j; rho_ij) - Phi(z_i) Phi(z_j)),
 
 with Phi2 the bivariate normal distribution function, computed on the device by ``dgp_exceedance_moments`` straight from
-the covariance ``dgp_posterior_cov`` writes: no factorisation, no draws, no sampling noise.  The target transforms of the
+the covariance ``dgp_posterior_cov`` writes: no factorisation, no draws, no sampling noise.  ``streamed=True`` takes
+``dgp_posterior_exceedance_moments`` instead, which produces that covariance a panel of rows at a time from the held
+factorisation and never stores it: the same numbers (to rounding) at any record length.  The target transforms of the
 project are monotone (log + standardise, or standardise), so a data-space threshold tau maps EXACTLY to the model-space
 u = (ln tau - t) / s or (tau - t) / s (s, t the target scaler's ``scale_`` and ``mean_``): unlike the loads, nothing
 lognormal is approximated.  The pipelines' clip of the data-space value is not part of the statistics.
@@ -64,21 +66,35 @@ def _work_bytes(m, P, L):
     return 8 * (2 * M * (L + 1) + M * P * min(L, 8) + P)
 
 
-def count_moments(model, Xnew, u, w, groups, ngroups, pred_noise=False, max_bytes: int = DEFAULT_MAX_BYTES):
+def count_moments(model, Xnew, u, w, groups, ngroups, pred_noise=False, max_bytes: int = DEFAULT_MAX_BYTES, streamed=False):
     """The device core: design rows ``Xnew`` (m, d), model-space thresholds ``u`` (L, m), weights ``w`` (m,), int32 group
     ids (non-decreasing, -1 = excluded) -> numpy (mean (L, P), cov (L, P, P)) from ONE ``posterior_cov`` and one
     ``exceedance_moments`` per 64 levels, taken the way ``loads.point_moments`` takes its dense branch.  A record whose
     dense footprint -- ``loads._site_bytes`` plus the moment pass's own work area (``_work_bytes``) -- exceeds
-    ``max_bytes`` raises ``ValueError``: there is no streamed variant."""
+    ``max_bytes`` raises ``ValueError``.  ``streamed=True`` (never chosen automatically): the latent mean from
+    ``predict_mean`` like ``point_moments``' streamed branch, then one ``posterior_exceedance_moments`` per 64 levels, whose
+    work area -- with the largest covariance panel that fits -- ``max_bytes`` bounds instead."""
     Xnew = Xnew.to(model.device).contiguous()
     m = Xnew.shape[0]
     u = np.ascontiguousarray(np.asarray(u, dtype=np.float64).reshape(-1, m))
+    means, covs = [], []
+    if streamed:
+        model._eval_ready(Xnew)
+        with torch.no_grad():
+            mu = (model._plan.predict_mean(model._factor_theta, Xnew) + model.model.prior_mean(Xnew)).contiguous()
+            extra = model.likelihood.predictive_noise(m, Xnew.device, model.dtype) if pred_noise else None
+            for l0 in range(0, u.shape[0], MAX_LEVELS):
+                mean_d, cov_d = model._plan.posterior_exceedance_moments(
+                    model._factor_theta, Xnew, mu, torch.from_numpy(u[l0:l0 + MAX_LEVELS]), w, groups, ngroups, extra_var=extra,
+                    max_bytes=max_bytes)
+                means.append(mean_d.cpu().numpy())
+                covs.append(cov_d.cpu().numpy())
+        return np.concatenate(means), np.concatenate(covs)
     esz = torch.empty((), dtype=model.dtype).element_size()
     need = _site_bytes(model.dm.X.shape[0], m, esz) + _work_bytes(m, ngroups, min(u.shape[0], MAX_LEVELS))
     if need > max_bytes:
         raise ValueError(f"exceedance statistics need the dense posterior covariance: a footprint of {need} bytes for "
-                         f"m = {m} points exceeds max_bytes = {max_bytes}")
-    means, covs = [], []
+                         f"m = {m} points exceeds max_bytes = {max_bytes}; pass streamed=True")
     model._eval_ready(Xnew)
     with torch.no_grad():
         kmean, cov = model._plan.posterior_cov(model._factor_theta, Xnew)
@@ -108,7 +124,7 @@ def _finish(mean, cov, total, above, fraction, ci):
 
 
 def exceedance(model, covariates, threshold=None, threshold_series=None, freq="YE", above=True, fraction=False, ci=0.95,
-               pred_noise=False, return_cov=False, max_bytes: int = DEFAULT_MAX_BYTES):
+               pred_noise=False, return_cov=False, max_bytes: int = DEFAULT_MAX_BYTES, streamed=False):
     """``MarginalHIP.exceedance``: per period of ``freq`` the expected number of points of ``covariates`` at which the
     target exceeds a threshold -- days per year above a criterion, for a daily record -- with its exact standard error.
 
@@ -121,13 +137,14 @@ def exceedance(model, covariates, threshold=None, threshold_series=None, freq="Y
     ``lower`` / ``upper`` are APPROXIMATE ``ci`` intervals -- the quantiles of a beta distribution for N / sum w matched
     to the exact mean and variance (the mean itself where the variance is 0) --, mean and se are exact.  With
     ``return_cov`` also the (L, P, P) covariance between the periods, level by level.  A record whose dense footprint
-    exceeds ``max_bytes`` raises ``ValueError``."""
+    exceeds ``max_bytes`` raises ``ValueError``; ``streamed=True`` never forms the m x m covariance (``count_moments``)."""
     return _exceedance(model, covariates, threshold, threshold_series, freq=freq, above=above, fraction=fraction, ci=ci,
-                       pred_noise=pred_noise, return_cov=return_cov, max_bytes=max_bytes)
+                       pred_noise=pred_noise, return_cov=return_cov, max_bytes=max_bytes, streamed=streamed)
 
 
 def _exceedance(model, covariates, threshold=None, threshold_series=None, *, weights=None, level_labels=None, freq="YE",
-                above=True, fraction=False, ci=0.95, pred_noise=False, return_cov=False, max_bytes: int = DEFAULT_MAX_BYTES):
+                above=True, fraction=False, ci=0.95, pred_noise=False, return_cov=False, max_bytes: int = DEFAULT_MAX_BYTES,
+                streamed=False):
     """The body of ``exceedance`` with what ``flux_exceedance`` adds: per-point ``weights`` of the count (default 1; a
     point with a non-finite weight is dropped like ``aggregate`` drops it) and ``level_labels`` for the ``level``
     coordinate of a per-point series."""
@@ -153,7 +170,7 @@ def _exceedance(model, covariates, threshold=None, threshold_series=None, *, wei
     u = model_space_threshold(model.dm, series[:, order])
     w = w_all[order]
     Xnew = torch.tensor(model.dm.Xnew(covariates), dtype=model.dtype)[torch.as_tensor(order)]
-    mean, cov = count_moments(model, Xnew, u, w, groups, len(labels), pred_noise=pred_noise, max_bytes=max_bytes)
+    mean, cov = count_moments(model, Xnew, u, w, groups, len(labels), pred_noise=pred_noise, max_bytes=max_bytes, streamed=streamed)
     total = np.bincount(groups, weights=w, minlength=len(labels))
     mean, se, lower, upper, cov = _finish(mean, cov, total, above, fraction, ci)
     attrs = dict(_target_attrs(model.dm), above=bool(above), fraction=bool(fraction))
@@ -175,7 +192,7 @@ def _exceedance(model, covariates, threshold=None, threshold_series=None, *, wei
 def flux_exceedance(model, covariates, limit, **kwargs):
     """``LoadestGP.exceedance(kind="flux")``: days on which the daily LOAD exceeds ``limit`` (kg per day; a number or a
     list): the per-day concentration threshold tau_i = limit / w_i with w_i the flux weights of ``annual_flux``; a day
-    with w_i <= 0 (or a missing flow) is excluded."""
+    with w_i <= 0 (or a missing flow) is excluded.  ``streamed`` and the other keywords go to ``_exceedance``."""
     wf = flux_weights(covariates, _target_attrs(model.dm))
     limits = np.atleast_1d(np.asarray(limit, dtype=np.float64))
     if limits.ndim != 1 or not np.all(np.isfinite(limits)):
@@ -196,11 +213,13 @@ def _latent_predict(model, covariates, pred_noise):
     return mu.double().cpu().numpy(), var.double().cpu().numpy()
 
 
-def duration_curve(model, covariates, levels=None, above=True, ci=0.95, pred_noise=False, max_bytes: int = DEFAULT_MAX_BYTES):
+def duration_curve(model, covariates, levels=None, above=True, ci=0.95, pred_noise=False, max_bytes: int = DEFAULT_MAX_BYTES,
+                   streamed=False):
     """``MarginalHIP.duration_curve``: the fraction of the record -- all points of ``covariates`` as ONE group -- on which
     the target exceeds each of ``levels`` (data space), with the exact standard error of that fraction and approximate
     ``ci`` intervals (``count_intervals``); for a rating model over a stage record, the flow-duration curve.  Default
     ``levels``: the 21 quantiles 2 %, 6.8 %, ... 98 % of the data-space posterior mean over the record.
+    ``streamed=True``: without the m x m covariance, for records of any length (``count_moments``).
     -> Dataset on ``level`` with ``mean``, ``se``, ``lower``, ``upper``; ``n_points`` among its attributes."""
     Xall = np.asarray(model.dm.Xnew(covariates))
     keep = np.nonzero(np.all(np.isfinite(Xall), axis=1))[0]
@@ -215,7 +234,7 @@ def duration_curve(model, covariates, levels=None, above=True, ci=0.95, pred_noi
     u = np.broadcast_to(model_space_threshold(model.dm, levels)[:, None], (levels.size, m))
     Xnew = torch.tensor(Xall[keep], dtype=model.dtype)
     mean, cov = count_moments(model, Xnew, u, np.ones(m), np.zeros(m, dtype=np.int32), 1, pred_noise=pred_noise,
-                              max_bytes=max_bytes)
+                              max_bytes=max_bytes, streamed=streamed)
     mean, se, lower, upper, _cov = _finish(mean, cov, np.array([float(m)]), above, True, ci)
     attrs = dict(_target_attrs(model.dm), above=bool(above), n_points=m)
     return Dataset(

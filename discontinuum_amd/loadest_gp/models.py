@@ -89,7 +89,7 @@ class LoadestGPMarginalHIP(LoadestDataMixin, MarginalHIP):
 
     @is_fitted
     def exceedance(self, covariates, threshold=None, threshold_series=None, kind="concentration", freq="YE", above=True,
-                   fraction=False, ci=0.95, pred_noise=False, return_cov=False, max_bytes=None):
+                   fraction=False, ci=0.95, pred_noise=False, return_cov=False, max_bytes=None, streamed=False):
         """Days per period above a criterion, with exact uncertainty (``MarginalHIP.exceedance``).  ``kind="concentration"``:
         the threshold is a concentration; ``kind="flux"``: ``threshold`` is a daily load in kg per day (a number or a list),
         turned into the per-day concentration threshold limit / w_i with the flux weights of ``annual_flux`` (regular time
@@ -98,14 +98,16 @@ class LoadestGPMarginalHIP(LoadestDataMixin, MarginalHIP):
             raise ValueError(f"kind must be 'concentration' or 'flux', not {kind!r}")
         if kind == "concentration":
             return super().exceedance(covariates, threshold=threshold, threshold_series=threshold_series, freq=freq, above=above,
-                                      fraction=fraction, ci=ci, pred_noise=pred_noise, return_cov=return_cov, max_bytes=max_bytes)
+                                      fraction=fraction, ci=ci, pred_noise=pred_noise, return_cov=return_cov, max_bytes=max_bytes,
+                                      streamed=streamed)
         if threshold is None or threshold_series is not None:
             raise ValueError("kind='flux' takes threshold = the daily load limit in kg per day")
         from ..exceedance import flux_exceedance
         from ..loads import DEFAULT_MAX_BYTES
 
         return flux_exceedance(self, covariates, threshold, freq=freq, above=above, fraction=fraction, ci=ci, pred_noise=pred_noise,
-                               return_cov=return_cov, max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes)
+                               return_cov=return_cov, max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes,
+                               streamed=streamed)
 
     def _flux_weights(self, daily):
         from ..loads import _target_attrs, flux_weights

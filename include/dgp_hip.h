@@ -301,6 +301,30 @@ int dgp_exceedance_moments(int dtype, const void* cov_dev, int64_t m, int batch,
                            const double* thresh_dev, int nlevels, const double* w_dev, const int32_t* group_dev,
                            int ngroups, const void* extra_var_dev, void* work_dev, size_t work_bytes,
                            double* mean_out_dev, double* cov_out_dev, void* stream);
+/* The same exceedance moments straight from the factorisation the plan holds, for records whose m x m covariance does not fit
+ * the device (a multi-year 15-minute stage record: m ~ 140 000, 157 GB in fp64).  C = K(Xs, Xs) - V^T V is produced panel_rows
+ * rows at a time -- the tiles, the k order and (fp64) the bits of dgp_posterior_cov -- into one panel buffer; every unordered
+ * pair (i < j) lies in exactly one panel, j's, and is evaluated there; the panels run in order on the stream.
+ *   Xs_dev     m x d row-major (batch x m x d for batched plans), as for dgp_posterior_cov;
+ *   mu_dev, thresh_dev, nlevels, w_dev, group_dev, ngroups, extra_var_dev, mean_out_dev, cov_out_dev: as for
+ *              dgp_exceedance_moments; sigma_i^2 is the predicted variance (+ extra_var_i), never read from a panel;
+ *   panel_rows a positive multiple of 128; the pass uses min(panel_rows, M).
+ * work_dev: dgp_posterior_exceedance_moments_workspace_bytes(plan, m, ngroups, nlevels, panel_rows) bytes, 256-byte aligned --
+ * per site the prediction's work area (2 N M + O(M) plan-dtype elements), the panel (min(panel_rows, M) M plan-dtype elements)
+ * and dgp_exceedance_moments' doubles; no buffer grows with M^2.  0 for bad sizes.
+ * Per chunk of 8 / 4 / 2 / 1 levels every panel is produced again (N m^2 matrix-core flop, small beside the m^2 / 2 bivariate
+ * probabilities per level).  No floating-point atomics: bitwise repeatable, a site's result does not depend on its batch;
+ * different panel_rows group the sums differently (equal to rounding).  DGP_E_ARG: a null argument, a bad size, panel_rows not
+ * a positive multiple of 128, a misaligned work area; DGP_E_WORKSPACE: a work area too small; DGP_E_STATE: no factorisation
+ * or a failed one.  Every (model, d) of dgp_posterior_cov, batched plans included (gridDim.z = sites).  The plan's
+ * factorisation and every later product are left bitwise intact. */
+size_t dgp_posterior_exceedance_moments_workspace_bytes(const dgp_plan* plan, int64_t m, int ngroups, int nlevels,
+                                                        int panel_rows);
+int dgp_posterior_exceedance_moments(dgp_plan* plan, const double* theta_host, const void* Xs_dev, int64_t m,
+                                     const void* mu_dev, const double* thresh_dev, int nlevels, const double* w_dev,
+                                     const int32_t* group_dev, int ngroups, const void* extra_var_dev, int panel_rows,
+                                     void* work_dev, size_t work_bytes, double* mean_out_dev, double* cov_out_dev,
+                                     void* stream);
 /* out[i] = Phi2(h_i, k_i; rho_i) - Phi(h_i) Phi(k_i), the pair function of dgp_exceedance_moments pointwise (rho clamped to
  * [-1, 1]; |h| or |k| above 38 gives 0): for tests.  All arrays `count` doubles on the device. */
 int dgp_debug_bvn_excess(const double* h_dev, const double* k_dev, const double* rho_dev, int64_t count, double* out_dev,

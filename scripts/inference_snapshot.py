@@ -2,7 +2,8 @@
 """Bitwise record of everything a ``GPPlan`` computes from a held factorisation, for refactors of the host glue that must not
 move a number: seeded inputs, one fit, and the outputs of ``fit_step``, ``factorize``, ``predict``, ``predict_mean``,
 ``mean_vjp``, ``predict_terms`` / ``predict_slopes`` (with and without ``return_cov``), ``posterior_cov``,
-``posterior_period_moments``, ``period_moments``, ``exceedance_moments``, ``sample_value`` and ``cross_validate``.
+``posterior_period_moments``, ``period_moments``, ``exceedance_moments``, ``posterior_exceedance_moments``, ``sample_value``
+and ``cross_validate``.
 
     python scripts/inference_snapshot.py --write before.pt      # on the commit to compare against
     python scripts/inference_snapshot.py --compare before.pt    # on the new one: exit status 1 unless every tensor is equal
@@ -78,6 +79,8 @@ def run_config(torch, GPPlan, backend, make_case, model, d, dtype, sizes, dev):
     keep("posterior_cov", (kmean, torch.tril(cov)[..., :m, :m]))  # the part the layout defines
     keep("period_moments", plan.period_moments(cov, m, mu, scale2, w, groups, GROUPS, backend.MODE_LOG, extra_var=extra))
     keep("exceedance_moments", plan.exceedance_moments(cov, m, mu, thresh, w, groups, GROUPS, extra_var=extra))
+    keep("posterior_exceedance_moments",  # two panels of 128 rows
+         plan.posterior_exceedance_moments(theta, Xs, mu, thresh, w, groups, GROUPS, extra_var=extra, panel_rows=128))
     given = stack([0.05 * torch.randn(3, m, generator=g, dtype=torch.float64) for _ in range(B)], torch.float64)
     keep("sample_value", plan.sample_value(cov, m, w, scale2, groups, GROUPS, obs_var=extra, rows=given, nterms=12))
     keep("sample_value_linear", plan.sample_value(cov, m, w, scale2, groups, GROUPS, nterms=1))
