@@ -22,6 +22,9 @@ OPT_POTRF_SCHEDULE, OPT_POTRF_SWEEP, OPT_POTRF_SOLVE, OPT_POTRF_OVERLAP, OPT_POT
 TIME_GRAM, TIME_POTRF, TIME_SYRK_SUM, TIME_SYRK_N, TIME_TRTRI, TIME_LAUUM, TIME_SOLVE, TIME_GRAD, TIME_SYRK_FLOP, TIME_COUNT = range(10)
 
 
+E_ARG, E_MODEL, E_WORKSPACE, E_STATE, E_FULL, E_NOCONV = -1, -2, -3, -4, -5, -6
+
+
 class DGPLibraryError(RuntimeError):
     pass
 
@@ -80,6 +83,11 @@ SIGNATURES = {
     "dgp_set_inputs": (_i, [_vp, _vp, _vp]),
     "dgp_fit_step": (_i, [_vp, _dp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dgp_factorize": (_i, [_vp, _dp, _vp, _vp, _vp, _vp]),
+    "dgp_laplace_workspace_bytes": (_sz, [_vp]),
+    "dgp_laplace_fit_step": (_i, [_vp, _dp, _vp, _vp, _vp, _vp, _vp, _i, C.c_double, _vp, _sz, _vp, _vp, _dp, _vp]),
+    "dgp_laplace_factorize": (_i, [_vp, _dp, _vp, _vp, _vp, _vp, _vp, _i, C.c_double, _vp, _sz, _vp, _dp, _vp]),
+    "dgp_debug_censored_terms": (_i, [_vp, _i64, _vp, _vp]),
+    "dgp_debug_bilinear": (_i, [_vp, _dp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "dgp_predict_workspace_bytes": (_sz, [_vp, _i64]),
     "dgp_predict": (_i, [_vp, _dp, _vp, _i64, _vp, _sz, _vp, _vp, _vp]),
     "dgp_posterior_cov": (_i, [_vp, _dp, _vp, _i64, _vp, _sz, _vp, _vp, _vp]),

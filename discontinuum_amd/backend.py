@@ -212,6 +212,70 @@ class GPPlan:
             _lib.check(self.lib.dgp_factorize(self._h, th, _ptr(r), _ptr(noise), _ptr(out), _stream()), "dgp_factorize")
         return out
 
+    # ------------------------------------------------------------------ censored observations (Laplace)
+    def _laplace(self, with_grad, theta, y, mean, noise, side, f, maxit, tol):
+        name = "dgp_laplace_fit_step" if with_grad else "dgp_laplace_factorize"
+        if self.batch != 1 or self.dtype != torch.float64:
+            raise ValueError(f"{name}: censored fits need a float64 single-site plan")
+        for t, what in ((y, "y"), (mean, "mean"), (noise, "noise")):
+            self._check_vec(t, what)
+        if not (torch.is_tensor(side) and side.is_cuda and side.dtype == torch.int32 and side.is_contiguous() and side.numel() == self.n):
+            raise ValueError(f"side must be a contiguous int32 CUDA tensor with {self.n} elements")
+        if f is None:
+            f = mean.clone()  # cold start
+        else:
+            self._check_vec(f, "f")
+            f = f.clone()
+        th = _theta_array(theta, self.ntheta)
+        stat = (C.c_double * 4)()
+        with torch.cuda.device(self.device):
+            need = int(self.lib.dgp_laplace_workspace_bytes(self._h))
+            work = self._work_area("_laplace_ws", need, name)
+            out = torch.empty(_lib.OUT_LEN, dtype=self.dtype, device=self.device)
+            dr = torch.empty(self.n, dtype=self.dtype, device=self.device) if with_grad else None
+            args = (self._h, th, _ptr(y), _ptr(mean), _ptr(noise), _ptr(side), _ptr(f), int(maxit), float(tol), work, need, _ptr(out))
+            if with_grad:
+                rc = self.lib.dgp_laplace_fit_step(*args, _ptr(dr), stat, _stream())
+            else:
+                rc = self.lib.dgp_laplace_factorize(*args, stat, _stream())
+        self.laplace_stat = tuple(float(v) for v in stat)  # kept for a caller that catches E_NOCONV
+        _lib.check(rc, name)
+        return (out, dr, f, self.laplace_stat) if with_grad else (out, f, self.laplace_stat)
+
+    def laplace_fit_step(self, theta, y, mean, noise, side, f=None, maxit=50, tol=1e-10):
+        """One fit step with censored rows (``side`` int32: -1 the truth is below the limit in ``y``, 0 observed, +1 above) by
+        the Laplace approximation: Newton's mode search from ``f`` (None: the prior mean), then the step at the mode.
+        -> (out[32], dr[n], f_hat[n], stat) with ``out[OUT_NLL]`` the Laplace NLL, ``out[OUT_DTHETA:]`` its gradient,
+        dr = alpha - u and stat = (Newton iterations, final max |df|, halvings, capped rows); the plan holds the
+        pseudo-data system's factorisation.  ``DGPError`` with code ``E_NOCONV`` when ``maxit`` does not suffice
+        (``self.laplace_stat`` is set either way)."""
+        return self._laplace(True, theta, y, mean, noise, side, f, maxit, tol)
+
+    def laplace_factorize(self, theta, y, mean, noise, side, f=None, maxit=50, tol=1e-10):
+        """The same without gradients (the prediction-time cache build) -> (out[32], f_hat[n], stat)."""
+        return self._laplace(False, theta, y, mean, noise, side, f, maxit, tol)
+
+    def censored_terms(self, z: torch.Tensor):
+        """(4, count): log Phi(z), h = phi / Phi, h (z + h), h [1 - (z + h)(z + 2 h)] as the censored fit evaluates them."""
+        if not (torch.is_tensor(z) and z.is_cuda and z.dtype == torch.float64 and z.is_contiguous() and z.dim() == 1 and z.numel() > 0):
+            raise ValueError("z must be a non-empty contiguous 1-d float64 CUDA tensor")
+        with torch.cuda.device(z.device):
+            out = torch.empty((4, z.numel()), dtype=torch.float64, device=z.device)
+            _lib.check(self.lib.dgp_debug_censored_terms(_ptr(z), z.numel(), _ptr(out), _stream()), "dgp_debug_censored_terms")
+        return out
+
+    def bilinear(self, theta, u: torch.Tensor, alpha: torch.Tensor):
+        """sum_ij u_i dK_ij/dtheta_p alpha_j for every p (ntheta,): the censored fit's pair sweep alone (tests)."""
+        self._check_vec(u, "u")
+        self._check_vec(alpha, "alpha")
+        th = _theta_array(theta, self.ntheta)
+        with torch.cuda.device(self.device):
+            need = int(self.lib.dgp_laplace_workspace_bytes(self._h))
+            work = self._work_area("_laplace_ws", need, "dgp_debug_bilinear")
+            out = torch.empty(self.ntheta, dtype=self.dtype, device=self.device)
+            _lib.check(self.lib.dgp_debug_bilinear(self._h, th, _ptr(u), _ptr(alpha), work, need, _ptr(out), _stream()), "dgp_debug_bilinear")
+        return out
+
     def predict(self, theta, Xs: torch.Tensor, chunk: int | None = None):
         """Latent posterior (K*^T alpha, diag(K** - K*^T K^^-1 K*)) at Xs (m, d) from the held factorisation.
         Batched plans: Xs (batch, m, d), theta (batch, ntheta) -> mean, var (batch, m); every site predicts at its own

@@ -1180,6 +1180,146 @@ int dgp_factorize(dgp_plan* p, const double* theta, const void* r, const void* n
   return wrap(rc, "dgp_factorize");
 }
 
+}  // extern "C"
+
+// ---- censored observations: Newton's mode search on the factorise path, then one step at the mode (dgp_censored.hip).
+// Returns 0, a HIP error (> 0), or DGP_E_ARG / DGP_E_NOCONV with the error text already set.
+static int laplace(dgp_plan* p, const double* theta, const double* y, const double* mean, const double* noise, const int* side,
+                   double* f, int maxit, double tol, char* work, double* out, double* dr, double* stat, int with_grad,
+                   const char* where, hipStream_t s) {
+  const CensoredLayout L = censored_layout(p->N, p->n);
+  auto D = [&](size_t off) { return (double*)(work + off); };
+  const int n = (int)p->n;
+  const double* alpha = (const double*)p->alpha;
+  double st[CEN_ST_LEN];
+  auto read_status = [&]() -> int {
+    hipError_t e = hipMemcpyAsync(st, D(L.status), sizeof(st), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    return (int)e;
+  };
+  int rc;
+  stat[0] = stat[1] = stat[2] = stat[3] = 0.0;
+  if ((rc = censored_terms(f, y, side, noise, mean, n, work, L, s)) || (rc = read_status())) return rc;
+  if (st[CEN_ST_BAD] != 0.0) {
+    snprintf(g_err, sizeof(g_err), "%s: side values must be -1, 0 or +1", where);
+    return DGP_E_ARG;
+  }
+  if (st[CEN_ST_NCENS] == 0.0) {  // nothing censored: the plain step on (y - m, v), bit for bit
+    if ((rc = fit_step<double>(p, theta, D(L.rt), D(L.nn), out, with_grad ? dr : nullptr, with_grad ? D(L.dnoise) : nullptr, with_grad, s)))
+      return rc;
+    return censored_mode(f, mean, alpha, n, work, L, s);
+  }
+  if ((rc = (int)hipMemsetAsync(D(L.acur), 0, sizeof(double) * (size_t)p->N, s))) return rc;
+  int it = 0;
+  bool converged = false, failed = false;
+  for (;;) {
+    if ((rc = fit_step<double>(p, theta, D(L.rt), D(L.nn), D(L.out), nullptr, nullptr, 0, s))) return rc;
+    if ((rc = censored_newton_update(f, y, side, noise, mean, alpha, n, it == 0, tol, work, L, s)) || (rc = read_status())) return rc;
+    ++it;
+    stat[0] = (double)it;
+    stat[1] = st[CEN_ST_DMAX];
+    stat[2] += st[CEN_ST_HALVINGS];
+    if (st[CEN_ST_INFO] != 0.0) {  // not positive definite: f did not move; the step below reports it through DGP_OUT_INFO
+      failed = true;
+      break;
+    }
+    if ((rc = censored_terms(f, y, side, noise, mean, n, work, L, s))) return rc;  // the next system, or the one at the mode
+    if (st[CEN_ST_DMAX] <= tol) {
+      converged = true;
+      break;
+    }
+    if (it >= maxit) break;
+  }
+  if ((rc = fit_step<double>(p, theta, D(L.rt), D(L.nn), out, nullptr, with_grad ? D(L.dnoise) : nullptr, with_grad, s))) return rc;
+  if (with_grad) {
+    if ((rc = censored_weights(alpha, n, p->N, work, L, s))) return rc;
+    // u = T^T (T w) into the work area: the plan's z, alpha and result row stay as the step left them
+    if ((rc = solve<double>((const double*)p->Tm, p->N, D(L.w), n, D(L.z), D(L.u), D(L.spart), D(L.quad), s))) return rc;
+    if ((rc = gram_bilinear<double>(p->model, p->d, (const double*)p->Xt, p->N, n, theta, D(L.u), alpha, D(L.gpart),
+                                    out + DGP_OUT_DTHETA, 1, s)))
+      return rc;
+  }
+  if ((rc = censored_result(alpha, side, (const double*)p->dr_w, n, with_grad, out, dr, work, L, s)) || (rc = read_status())) return rc;
+  stat[3] = st[CEN_ST_CAPPED];
+  if (!converged && !failed) {
+    snprintf(g_err, sizeof(g_err), "%s: the mode search did not converge in %d Newton iterations (max |df| = %.3g)", where, it, stat[1]);
+    return DGP_E_NOCONV;
+  }
+  return 0;
+}
+static int laplace_entry(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise, const int32_t* side,
+                         void* f, int maxit, double tol, void* work, size_t work_bytes, void* out, void* dr, double* stat,
+                         int with_grad, const char* where, void* stream) {
+  char msg[160];
+  if (!p) return fail(DGP_E_ARG, "null plan");
+  if (p->dtype != DGP_F64 || p->B != 1) {
+    snprintf(msg, sizeof(msg), "%s: censored fits need a float64 single-site plan (fp32 and batched plans are not supported)", where);
+    return fail(DGP_E_ARG, msg);
+  }
+  if (!theta || !y || !mean || !noise || !side || !f || !out || !stat || maxit < 1 || !(tol >= 0.0)) {
+    snprintf(msg, sizeof(msg), "%s: null argument (f_dev included), maxit < 1 or a negative tol", where);
+    return fail(DGP_E_ARG, msg);
+  }
+  DGP_CHECK_PLAN(p);
+  if (!p->have_inputs) return fail(DGP_E_STATE, "dgp_laplace_*: call dgp_set_inputs first");
+  if (!work || work_bytes < dgp_laplace_workspace_bytes(p)) {
+    snprintf(msg, sizeof(msg), "%s: workspace missing or too small", where);
+    return fail(DGP_E_WORKSPACE, msg);
+  }
+  if (((uintptr_t)work & 255) != 0) return fail(DGP_E_ARG, "dgp_laplace_*: the work area must be 256-byte aligned");
+  const int rc = laplace(p, theta, (const double*)y, (const double*)mean, (const double*)noise, (const int*)side, (double*)f, maxit, tol,
+                         (char*)work, (double*)out, (double*)dr, stat, with_grad, where, (hipStream_t)stream);
+  if (rc == DGP_E_ARG || rc == DGP_E_NOCONV) return rc;  // text set where it arose
+  return wrap(rc, where);
+}
+
+extern "C" {
+
+size_t dgp_laplace_workspace_bytes(const dgp_plan* p) {
+  if (!p || p->dtype != DGP_F64 || p->B != 1) return 0;
+  return censored_layout(p->N, p->n).total;
+}
+
+int dgp_laplace_fit_step(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise, const int32_t* side,
+                         void* f, int maxit, double tol, void* work, size_t work_bytes, void* out, void* dr, double* stat,
+                         void* stream) {
+  return laplace_entry(p, theta, y, mean, noise, side, f, maxit, tol, work, work_bytes, out, dr, stat, 1, "dgp_laplace_fit_step", stream);
+}
+
+int dgp_laplace_factorize(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise, const int32_t* side,
+                          void* f, int maxit, double tol, void* work, size_t work_bytes, void* out, double* stat, void* stream) {
+  return laplace_entry(p, theta, y, mean, noise, side, f, maxit, tol, work, work_bytes, out, nullptr, stat, 0, "dgp_laplace_factorize",
+                       stream);
+}
+
+int dgp_debug_censored_terms(const double* z, int64_t count, double* out, void* stream) {
+  if (!z || !out || count <= 0 || count > (1ll << 29)) return fail(DGP_E_ARG, "dgp_debug_censored_terms: null argument / bad count");
+  return wrap(debug_censored_terms(z, count, out, (hipStream_t)stream), "dgp_debug_censored_terms");
+}
+
+int dgp_debug_bilinear(dgp_plan* p, const double* theta, const void* u, const void* alpha, void* work, size_t work_bytes, double* dtheta,
+                       void* stream) {
+  if (!p) return fail(DGP_E_ARG, "null plan");
+  if (p->dtype != DGP_F64 || p->B != 1) return fail(DGP_E_ARG, "dgp_debug_bilinear: needs a float64 single-site plan");
+  if (!theta || !u || !alpha || !dtheta) return fail(DGP_E_ARG, "dgp_debug_bilinear: null argument");
+  DGP_CHECK_PLAN(p);
+  if (!p->have_inputs) return fail(DGP_E_STATE, "dgp_debug_bilinear: call dgp_set_inputs first");
+  if (!work || work_bytes < dgp_laplace_workspace_bytes(p)) return fail(DGP_E_WORKSPACE, "dgp_debug_bilinear: workspace missing or too small");
+  if (((uintptr_t)work & 255) != 0) return fail(DGP_E_ARG, "dgp_debug_bilinear: the work area must be 256-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const CensoredLayout L = censored_layout(p->N, p->n);
+  double *up = (double*)((char*)work + L.u), *ap = (double*)((char*)work + L.w);
+  const size_t nb = sizeof(double) * (size_t)p->n, Nb = sizeof(double) * (size_t)p->N;
+  hipError_t e = hipMemsetAsync(up, 0, Nb, s);
+  if (e == hipSuccess) e = hipMemsetAsync(ap, 0, Nb, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(up, u, nb, hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(ap, alpha, nb, hipMemcpyDeviceToDevice, s);
+  if (e != hipSuccess) return hipfail(e, "dgp_debug_bilinear");
+  return wrap(gram_bilinear<double>(p->model, p->d, (const double*)p->Xt, p->N, (int)p->n, theta, up, ap,
+                                    (double*)((char*)work + L.gpart), dtheta, 0, s),
+              "dgp_debug_bilinear");
+}
+
 size_t dgp_predict_workspace_bytes(const dgp_plan* p, int64_t m) {
   if (!p || m <= 0) return 0;
   return predict_site_bytes(p, m) * (size_t)p->B;

@@ -1,0 +1,422 @@
+// dgp_censored.hip -- censored observations (non-detects): the Laplace approximation of a GP with a Tobit likelihood.
+//
+// Row i of a single-site fp64 plan is either observed (side 0: Gaussian, variance v_i) or censored at the limit l_i
+// (side s_i = -1: the truth lies below it, +1: above):  log p_i = log Phi(z_i),  z_i = s_i (f_i - l_i) / sigma_i.
+// With h = phi(z) / Phi(z),
+//     g_i  =  d log p_i / d f_i     =  s_i h / sigma_i
+//     W_i  = -d^2 log p_i / d f_i^2 =  h (z + h) / v_i               in (0, 1 / v_i)
+//     d3_i =  d^3 log p_i / d f_i^3 = -(s_i / sigma_i^3) h [1 - (z + h)(z + 2 h)]
+// and at the mode the posterior of f is the exact GP posterior for the pseudo-targets y~_i = f_i + g_i / W_i with the
+// pseudo-noise n~_i = 1 / W_i (observed rows: y~ = y, n~ = v).  A Newton step is therefore ONE factorisation with the
+// residual r~ = y~ - m and the noise n~:  a = (K + diag n~)^-1 r~,  f_new = m + K a = y~ - n~ o a  (no product with K).
+//
+//   cen_terms_kernel    one elementwise pass: r~, n~, g, W, d3 and the per-row part of the NLL correction; block partials
+//   cen_search_kernel   the proposal f_new, max |f_new - f| and Psi(t) = sum log p_i(f(t)) - 1/2 a(t)^T (f(t) - m) on
+//                       t in {0, 1, 1/2, .., 1/64} in one pass (f and a are linear in t); block partials
+//   cen_*_finish        one workgroup, fixed order: no floating-point atomics anywhere, every result repeats bitwise
+//   gram_bilinear       sum_ij u_i dK_ij/dtheta_p a_j for all p in one sweep over the lower triangle (sibling of
+//                       dgp_gram.hip::gram_grad_kernel: same tiling, staging and two-stage reduction; weights
+//                       u_i a_j + u_j a_i, the diagonal once) -- dK/dtheta is never stored
+// The non-destructive solve u = T^T (T w) is dgp_chol.hip::solve on buffers of the caller's work area.
+// Roofline: the elementwise passes are O(n) and latency-bound; the sweep is VALU-bound like gram_grad (one derivative pair
+// evaluation per entry of the triangle, nothing streamed from HBM but the two vectors).
+#include "dgp_gram_shared.h"
+#include "dgp_internal.h"
+#include "dgp_models.h"
+
+namespace dgp {
+
+// ---- the four functions of z.  Negative side through erfcx (no underflow, no cancellation in Phi), positive side through
+// erfc / log1p.  q = h (z + h) and c3 = h [1 - (z + h)(z + 2 h)] inherit the cancellation of z + h for z << 0 (relative
+// error ~ z^2 eps).
+struct CenFn {
+  double logphi, h, q, c3;
+};
+__device__ __forceinline__ CenFn cen_fn(double z) {
+  CenFn o;
+  if (z < 0.0) {
+    const double e = erfcx(-z * 0.70710678118654752440);
+    o.h = 0.79788456080286535588 / e;
+    o.logphi = -0.5 * z * z + log(0.5 * e);
+  } else {
+    const double tail = 0.5 * erfc(z * 0.70710678118654752440);
+    o.h = 0.39894228040143267794 * exp(-0.5 * z * z) / (1.0 - tail);
+    o.logphi = log1p(-tail);
+  }
+  const double zh = z + o.h;
+  o.q = o.h * zh;
+  o.c3 = o.h * (1.0 - zh * (zh + o.h));
+  return o;
+}
+__device__ __forceinline__ double cen_logphi(double z) {
+  if (z < 0.0) return -0.5 * z * z + log(0.5 * erfcx(-z * 0.70710678118654752440));
+  return log1p(-0.5 * erfc(z * 0.70710678118654752440));
+}
+
+__global__ __launch_bounds__(256) void cen_debug_kernel(const double* __restrict__ z, long count, double* __restrict__ out) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= count) return;
+  const CenFn o = cen_fn(z[i]);
+  out[i] = o.logphi;
+  out[count + i] = o.h;
+  out[2 * count + i] = o.q;
+  out[3 * count + i] = o.c3;
+}
+
+int debug_censored_terms(const double* z, long count, double* out, hipStream_t s) {
+  cen_debug_kernel<<<dim3((unsigned)((count + 255) / 256)), 256, 0, s>>>(z, count, out);
+  return (int)hipGetLastError();
+}
+
+// block sums of K <= CEN_PART values per thread (column `maxcol`, if any, is a maximum), lane order then wave order
+template <int K>
+__device__ __forceinline__ void cen_block_reduce(double (&v)[K], int maxcol, double* __restrict__ part) {
+  __shared__ double red[4][K];
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+#pragma unroll
+  for (int q = 0; q < K; ++q) {
+    double x = v[q];
+    if (q == maxcol) {
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) x = fmax(x, __shfl_down(x, off, 64));
+    } else {
+      x = wave_sum(x);
+    }
+    if (lane == 0) red[wv][q] = x;
+  }
+  __syncthreads();
+  if (t < K)
+    part[(long)blockIdx.x * CEN_PART + t] = t == maxcol ? fmax(fmax(red[0][t], red[1][t]), fmax(red[2][t], red[3][t]))
+                                                        : red[0][t] + red[1][t] + red[2][t] + red[3][t];
+}
+// the second stage: one workgroup, column q of nblk rows of partials -> tot[q], fixed strided order + fixed tree
+__device__ __forceinline__ void cen_total(const double* __restrict__ part, int nblk, int K, int maxcol, double* tot /* LDS [CEN_PART] */) {
+  __shared__ double red[256];
+  const int t = threadIdx.x;
+  for (int q = 0; q < K; ++q) {
+    double v = 0.0;
+    for (int b = t; b < nblk; b += 256) v = q == maxcol ? fmax(v, part[(long)b * CEN_PART + q]) : v + part[(long)b * CEN_PART + q];
+    red[t] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+      if (t < s) red[t] = q == maxcol ? fmax(red[t], red[t + s]) : red[t] + red[t + s];
+      __syncthreads();
+    }
+    if (t == 0) tot[q] = red[0];
+    __syncthreads();
+  }
+}
+
+// ---- terms at the current f.  y holds the observation (side 0) or the limit (side +-1).  Capped rows (W v < cap: the limit
+// says nothing) get n~ = v / cap and d3 = 0.  corr: the row's part of the NLL correction that does not involve alpha.
+__global__ __launch_bounds__(256) void cen_terms_kernel(const double* __restrict__ f, const double* __restrict__ y,
+                                                        const int* __restrict__ side, const double* __restrict__ v,
+                                                        const double* __restrict__ m, int n, double cap, double* __restrict__ rt,
+                                                        double* __restrict__ nn, double* __restrict__ g, double* __restrict__ W,
+                                                        double* __restrict__ d3, double* __restrict__ corr, double* __restrict__ logp,
+                                                        double* __restrict__ part) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};  // correction, capped rows, bad side values, censored rows
+  if (i < n) {
+    const int s = side[i];
+    const double vi = v[i], mi = m[i], yi = y[i], fi = f[i];
+    if (s == 0 || (s != 1 && s != -1)) {
+      const double e = yi - fi;
+      rt[i] = yi - mi;
+      nn[i] = vi;
+      g[i] = e / vi;
+      W[i] = 1.0 / vi;
+      d3[i] = 0.0;
+      corr[i] = 0.0;
+      logp[i] = -0.5 * e * e / vi - 0.5 * log(6.28318530717958647692 * vi);
+      acc[2] = s == 0 ? 0.0 : 1.0;
+    } else {
+      const double sg = sqrt(vi), sd = (double)s;
+      const CenFn o = cen_fn(sd * (fi - yi) / sg);
+      const bool capped = !(o.q >= cap);
+      const double ni = capped ? vi / cap : vi / o.q, wi = 1.0 / ni, gi = sd * o.h / sg;
+      rt[i] = (fi + gi * ni) - mi;
+      nn[i] = ni;
+      g[i] = gi;
+      W[i] = wi;
+      d3[i] = capped ? 0.0 : -(sd / (sg * vi)) * o.c3;
+      const double c = -o.logphi + 0.5 * log(wi) - 0.5 * 1.83787706640934548356;
+      corr[i] = c;
+      logp[i] = o.logphi;
+      acc[0] = c;
+      acc[1] = capped ? 1.0 : 0.0;
+      acc[3] = 1.0;
+    }
+  }
+  cen_block_reduce<4>(acc, -1, part);
+}
+__global__ __launch_bounds__(256) void cen_terms_finish_kernel(const double* __restrict__ part, int nblk, double* __restrict__ status) {
+  __shared__ double tot[CEN_PART];
+  cen_total(part, nblk, 4, -1, tot);
+  if (threadIdx.x < 4) status[CEN_ST_CORR + threadIdx.x] = tot[threadIdx.x];
+}
+
+// ---- proposal and line search.  anew: the plan's alpha of the factorisation at (r~, n~); acur: the a of the current f (f - m =
+// K acur), which the first step from a caller's f does not know.
+__global__ __launch_bounds__(256) void cen_search_kernel(const double* __restrict__ f, const double* __restrict__ y,
+                                                         const int* __restrict__ side, const double* __restrict__ v,
+                                                         const double* __restrict__ m, const double* __restrict__ rt,
+                                                         const double* __restrict__ nn, const double* __restrict__ anew,
+                                                         const double* __restrict__ acur, int n, double* __restrict__ delta,
+                                                         double* __restrict__ part) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  double acc[CEN_NT + 1];
+#pragma unroll
+  for (int j = 0; j <= CEN_NT; ++j) acc[j] = 0.0;
+  if (i < n) {
+    const int s = side[i];
+    const double vi = v[i], mi = m[i], yi = y[i], fi = f[i], an = anew[i], ac = acur[i];
+    const double dlt = (mi + rt[i] - nn[i] * an) - fi, da = an - ac, sg = sqrt(vi);
+    delta[i] = dlt;
+    acc[CEN_NT] = fabs(dlt);
+    double t = 0.0;
+#pragma unroll  // (acc[j] stays in registers)
+    for (int j = 0; j < CEN_NT; ++j) {
+      const double ft = fi + t * dlt, at = ac + t * da;
+      double lp;
+      if (s == 0) {
+        const double e = yi - ft;
+        lp = -0.5 * e * e / vi - 0.5 * log(6.28318530717958647692 * vi);
+      } else {
+        lp = cen_logphi((double)s * (ft - yi) / sg);
+      }
+      acc[j] = lp - 0.5 * at * (ft - mi);
+      t = j == 0 ? 1.0 : 0.5 * t;
+    }
+  }
+  cen_block_reduce<CEN_NT + 1>(acc, CEN_NT, part);
+}
+// chooses the step: the whole step when `first` or when it is below tol, else the largest t of the set that does not lower Psi
+// (slack: rounding of the sums).  status: max |delta|, t, halvings, the factorisation's info, Psi(0), Psi(t).
+__global__ __launch_bounds__(256) void cen_search_finish_kernel(const double* __restrict__ part, int nblk, int first, double tol,
+                                                                const double* __restrict__ outblk, double* __restrict__ status) {
+  __shared__ double tot[CEN_PART];
+  cen_total(part, nblk, CEN_NT + 1, CEN_NT, tot);
+  if (threadIdx.x != 0) return;
+  const double dmax = tot[CEN_NT], info = outblk[3];
+  int j = 1;
+  if (!first && !(dmax <= tol)) {
+    const double floor_ = tot[0] - 1e-9 * (1.0 + fabs(tot[0]));
+    while (j < CEN_NT - 1 && !(tot[j] >= floor_)) ++j;
+  }
+  double t = 1.0;
+  for (int k = 1; k < j; ++k) t *= 0.5;
+  status[CEN_ST_DMAX] = (info == 0.0 && dmax == dmax) ? dmax : __builtin_inf();
+  status[CEN_ST_T] = t;
+  status[CEN_ST_HALVINGS] = (double)(j - 1);
+  status[CEN_ST_INFO] = info;
+  status[CEN_ST_PSI0] = tot[0];
+  status[CEN_ST_PSI] = tot[j];
+}
+// f <- f + t delta, acur <- acur + t (anew - acur); nothing moves when the factorisation failed
+__global__ __launch_bounds__(256) void cen_update_kernel(double* __restrict__ f, const double* __restrict__ delta,
+                                                         double* __restrict__ acur, const double* __restrict__ anew,
+                                                         const double* __restrict__ status, int n) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n || status[CEN_ST_INFO] != 0.0) return;
+  const double t = status[CEN_ST_T];
+  f[i] = t == 1.0 ? f[i] + delta[i] : f[i] + t * delta[i];
+  acur[i] = t == 1.0 ? anew[i] : acur[i] + t * (anew[i] - acur[i]);
+}
+// the mode of the system just solved: f = m + r~ - n~ o alpha (no censored row: the exact posterior mean at the samples)
+__global__ __launch_bounds__(256) void cen_mode_kernel(double* __restrict__ f, const double* __restrict__ m,
+                                                       const double* __restrict__ rt, const double* __restrict__ nn,
+                                                       const double* __restrict__ alpha, int n) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) f[i] = m[i] + rt[i] - nn[i] * alpha[i];
+}
+
+// ---- gradient.  (K^^-1)_ii = 2 dnoise_i + alpha_i^2;  Sigma_ii = n~_i - n~_i^2 (K^^-1)_ii;  t_i = -1/2 Sigma_ii d3_i;  w = n~ o t
+__global__ __launch_bounds__(256) void cen_weight_kernel(const double* __restrict__ nn, const double* __restrict__ d3,
+                                                         const double* __restrict__ dnoise, const double* __restrict__ alpha, int n,
+                                                         long N, double* __restrict__ w) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= N) return;
+  double wi = 0.0;
+  if (i < n && d3[i] != 0.0) {
+    const double a = alpha[i], kii = 2.0 * dnoise[i] + a * a, ni = nn[i];
+    wi = ni * (-0.5 * (ni - ni * ni * kii) * d3[i]);
+  }
+  w[i] = wi;
+}
+// dr = alpha - u (u null: alpha) and the sums of the result row that depend on it; the NLL correction with its alpha part
+__global__ __launch_bounds__(256) void cen_result_kernel(const double* __restrict__ alpha, const double* __restrict__ u,
+                                                         const double* __restrict__ nn, const double* __restrict__ corr,
+                                                         const int* __restrict__ side, const double* __restrict__ wts, int n,
+                                                         double* __restrict__ dr, double* __restrict__ part) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};  // correction, sum dr, sum dr w0, sum dr w1
+  if (i < n) {
+    const double a = alpha[i], d = u ? a - u[i] : a;
+    if (dr) dr[i] = d;
+    if (side[i] != 0) acc[0] = corr[i] - 0.5 * nn[i] * a * a;
+    acc[1] = d;
+    if (wts) {
+      acc[2] = d * wts[i];
+      acc[3] = d * wts[(long)n + i];
+    }
+  }
+  cen_block_reduce<4>(acc, -1, part);
+}
+__global__ __launch_bounds__(256) void cen_result_finish_kernel(const double* __restrict__ part, int nblk, int with_grad,
+                                                                double* __restrict__ out, double* __restrict__ status) {
+  __shared__ double tot[CEN_PART];
+  cen_total(part, nblk, 4, -1, tot);
+  if (threadIdx.x != 0) return;
+  out[0] += tot[0];  // DGP_OUT_NLL
+  status[CEN_ST_NLL_CORR] = tot[0];
+  if (with_grad) {
+    out[28] = tot[1];  // DGP_OUT_SUM_DR, DGP_OUT_DR_W0, + 1
+    out[29] = tot[2];
+    out[30] = tot[3];
+  }
+}
+
+CensoredLayout censored_layout(long N, long n) {
+  CensoredLayout L;
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t vec = al(sizeof(double) * (size_t)N);
+  size_t o = 0;
+  L.rt = o; o += vec;
+  L.nn = o; o += vec;
+  L.g = o; o += vec;
+  L.W = o; o += vec;
+  L.d3 = o; o += vec;
+  L.corr = o; o += vec;
+  L.logp = o; o += vec;
+  L.delta = o; o += vec;
+  L.acur = o; o += vec;
+  L.w = o; o += vec;
+  L.u = o; o += vec;
+  L.z = o; o += vec;
+  L.dnoise = o; o += vec;
+  L.spart = o; o += al(sizeof(double) * (size_t)solve_partials(N));
+  L.gpart = o; o += al(sizeof(double) * (size_t)gram_grad_partials(N));
+  L.nblk = (int)((n + 255) / 256);
+  L.part = o; o += al(sizeof(double) * (size_t)L.nblk * CEN_PART);
+  L.status = o; o += al(sizeof(double) * CEN_ST_LEN);
+  L.out = o; o += al(sizeof(double) * 32);
+  L.quad = o; o += al(sizeof(double) * 8);
+  L.total = o;
+  return L;
+}
+
+int censored_terms(const double* f, const double* y, const int* side, const double* v, const double* m, int n, char* work,
+                   const CensoredLayout& L, hipStream_t s) {
+  auto D = [&](size_t off) { return (double*)(work + off); };
+  cen_terms_kernel<<<dim3((unsigned)L.nblk), 256, 0, s>>>(f, y, side, v, m, n, CEN_CAP, D(L.rt), D(L.nn), D(L.g), D(L.W), D(L.d3),
+                                                          D(L.corr), D(L.logp), D(L.part));
+  cen_terms_finish_kernel<<<1, 256, 0, s>>>(D(L.part), L.nblk, D(L.status));
+  return (int)hipGetLastError();
+}
+
+int censored_newton_update(double* f, const double* y, const int* side, const double* v, const double* m, const double* anew, int n,
+                           int first, double tol, char* work, const CensoredLayout& L, hipStream_t s) {
+  auto D = [&](size_t off) { return (double*)(work + off); };
+  cen_search_kernel<<<dim3((unsigned)L.nblk), 256, 0, s>>>(f, y, side, v, m, D(L.rt), D(L.nn), anew, D(L.acur), n, D(L.delta),
+                                                           D(L.part));
+  cen_search_finish_kernel<<<1, 256, 0, s>>>(D(L.part), L.nblk, first, tol, D(L.out), D(L.status));
+  cen_update_kernel<<<dim3((unsigned)L.nblk), 256, 0, s>>>(f, D(L.delta), D(L.acur), anew, D(L.status), n);
+  return (int)hipGetLastError();
+}
+
+int censored_mode(double* f, const double* m, const double* alpha, int n, char* work, const CensoredLayout& L, hipStream_t s) {
+  cen_mode_kernel<<<dim3((unsigned)L.nblk), 256, 0, s>>>(f, m, (const double*)(work + L.rt), (const double*)(work + L.nn), alpha, n);
+  return (int)hipGetLastError();
+}
+
+int censored_weights(const double* alpha, int n, long N, char* work, const CensoredLayout& L, hipStream_t s) {
+  auto D = [&](size_t off) { return (double*)(work + off); };
+  cen_weight_kernel<<<dim3((unsigned)((N + 255) / 256)), 256, 0, s>>>(D(L.nn), D(L.d3), D(L.dnoise), alpha, n, N, D(L.w));
+  return (int)hipGetLastError();
+}
+
+int censored_result(const double* alpha, const int* side, const double* wts, int n, int with_grad, double* out, double* dr, char* work,
+                    const CensoredLayout& L, hipStream_t s) {
+  auto D = [&](size_t off) { return (double*)(work + off); };
+  cen_result_kernel<<<dim3((unsigned)L.nblk), 256, 0, s>>>(alpha, with_grad ? D(L.u) : nullptr, D(L.nn), D(L.corr), side,
+                                                           with_grad ? wts : nullptr, n, with_grad ? dr : nullptr, D(L.part));
+  cen_result_finish_kernel<<<1, 256, 0, s>>>(D(L.part), L.nblk, with_grad, out, D(L.status));
+  return (int)hipGetLastError();
+}
+
+// ---- the bilinear derivative sweep: partials[tile][p] = sum over the tile's entries (i >= j) of
+// (u_i a_j + u_j a_i) dK_ij/dtheta_p, the diagonal at half weight; summed by grad_reduce_kernel in fixed order.
+template <typename T, typename M>
+__global__ __launch_bounds__(256) void gram_bilinear_kernel(const T* __restrict__ Xt, long N, int n, const PreBatch<M> pb,
+                                                            const T* __restrict__ u, const T* __restrict__ alpha,
+                                                            T* __restrict__ partials) {
+  const typename M::Pre& pre = pb.get();
+  __shared__ T sfi[M::NF][64], sfj[M::NF][64], sai[64], saj[64], sui[64], suj[64];
+  __shared__ T red[4][M::NTHETA];
+  int bi, bj;
+  tri_decode(blockIdx.x, bi, bj);
+  const int t = threadIdx.x;
+  exp_table_init<T>();
+  if (t < 64) {
+    stage_strip<T, M>(Xt, N, (long)bi * 64, pre, sfi, t);
+    sai[t] = alpha[(long)bi * 64 + t];
+    sui[t] = u[(long)bi * 64 + t];
+  } else if (t < 128) {
+    stage_strip<T, M>(Xt, N, (long)bj * 64, pre, sfj, t - 64);
+    saj[t - 64] = alpha[(long)bj * 64 + t - 64];
+    suj[t - 64] = u[(long)bj * 64 + t - 64];
+  }
+  __syncthreads();
+  const int ty = t >> 4, tx = t & 15;
+  T acc[M::NTHETA];
+#pragma unroll
+  for (int p = 0; p < M::NTHETA; ++p) acc[p] = T(0);
+  // one entry at a time, the column point's features from LDS per entry (see gram_grad_kernel)
+#pragma unroll 1
+  for (int a = 0; a < 4; ++a) {
+    const long gi = (long)bi * 64 + ty * 4 + a;
+    T fi[M::NF];
+#pragma unroll
+    for (int c = 0; c < M::NF; ++c) fi[c] = sfi[c][ty * 4 + a];
+    const T ai = sai[ty * 4 + a], ui = sui[ty * 4 + a];
+#pragma unroll 1
+    for (int b = 0; b < 4; ++b) {
+      const int cj = tx * 4 + b;
+      const long gj = (long)bj * 64 + cj;
+      T fj[M::NF];
+#pragma unroll
+      for (int c = 0; c < M::NF; ++c) fj[c] = sfj[c][cj];
+      T w = ui * saj[cj] + suj[cj] * ai;
+      w = (gj > gi || gi >= n) ? T(0) : (gj == gi ? T(0.5) * w : w);
+      (void)M::template pair<true>(fi, fj, pre, w, acc);
+    }
+  }
+  M::finalize(acc, pre);
+  const int lane = t & 63, wv = t >> 6;
+#pragma unroll
+  for (int p = 0; p < M::NTHETA; ++p) {
+    T v = wave_sum(acc[p]);
+    if (lane == 0) red[wv][p] = v;
+  }
+  __syncthreads();
+  if (t < M::NTHETA) partials[(long)blockIdx.x * DGP_MAX_THETA + t] = red[0][t] + red[1][t] + red[2][t] + red[3][t];
+}
+
+template <typename T>
+int gram_bilinear(int model, int d, const T* Xt, long N, int n, const double* theta, const T* u, const T* alpha, T* partials,
+                  T* dtheta, int accumulate, hipStream_t s) {
+  const int nt = model_ntheta(model, d);
+  if (nt < 0) return -2;
+  const long nb = N / 64;
+  const long nblk = nb * (nb + 1) / 2;
+  DGP_DISPATCH_MODEL(model, d,
+                     (gram_bilinear_kernel<T, M><<<dim3((unsigned)nblk), dim3(256), 0, s>>>(
+                         Xt, N, n, prepare_batch<M>(theta, nt, 1, nullptr, false, s, nullptr), u, alpha, partials)));
+  grad_reduce_kernel<T><<<dim3((unsigned)nt), dim3(256), 0, s>>>(partials, nblk, nt, dtheta, accumulate, 0, 0);
+  return (int)hipGetLastError();
+}
+template int gram_bilinear<double>(int, int, const double*, long, int, const double*, const double*, const double*, double*, double*,
+                                   int, hipStream_t);
+
+}  // namespace dgp

@@ -395,4 +395,46 @@ int deletion_influence(const T* Tm, const T* S, const T* alpha, long N, int n, l
                        const double* inv_sd, void* work, const InfluenceLayout& L, double* dload, double* dvar, double* shift,
                        int* info, hipStream_t s, Batch bt);
 
+// ---- dgp_censored.hip: censored rows (Tobit likelihood) by the Laplace approximation -- a GP regression on pseudo-data (r~, n~).
+// Single-site fp64 plans.  The caller's work area is a CensoredLayout; `status` is the small block the host reads once per
+// Newton iteration.
+#define CEN_PART 16    // doubles per workgroup of the block partials
+#define CEN_NT 8       // step lengths of the line search: 0, 1, 1/2, .. 1/64
+#define CEN_CAP 1e-12  // a censored row with W v below this is uninformative: n~ = v / CEN_CAP, d3 = 0
+enum {
+  CEN_ST_CORR = 0,   // alpha-free part of the NLL correction; then capped rows, bad side values, censored rows (cen_terms)
+  CEN_ST_CAPPED,
+  CEN_ST_BAD,
+  CEN_ST_NCENS,
+  CEN_ST_DMAX,       // max |f_new - f| of the proposal (inf when the factorisation failed)
+  CEN_ST_T,          // step length taken
+  CEN_ST_HALVINGS,
+  CEN_ST_INFO,       // DGP_OUT_INFO of the iteration's factorisation
+  CEN_ST_PSI0,
+  CEN_ST_PSI,
+  CEN_ST_NLL_CORR,   // the whole correction NLL_L - NLL_engine
+  CEN_ST_LEN = 16
+};
+struct CensoredLayout {
+  size_t rt, nn, g, W, d3, corr, logp, delta, acur, w, u, z, dnoise, spart, gpart, part, status, out, quad, total;  // byte offsets
+  int nblk;  // workgroups of the elementwise passes
+};
+CensoredLayout censored_layout(long N, long n);
+// the terms at f: r~, n~, g, W, d3, per-row correction and log p into the work area, their sums into status[CEN_ST_CORR ..]
+int censored_terms(const double* f, const double* y, const int* side, const double* v, const double* m, int n, char* work,
+                   const CensoredLayout& L, hipStream_t s);
+// after the factorisation at (r~, n~) left `anew` in the plan: proposal, line search, f and the work area's a updated in place
+int censored_newton_update(double* f, const double* y, const int* side, const double* v, const double* m, const double* anew, int n,
+                           int first, double tol, char* work, const CensoredLayout& L, hipStream_t s);
+int censored_mode(double* f, const double* m, const double* alpha, int n, char* work, const CensoredLayout& L, hipStream_t s);
+int censored_weights(const double* alpha, int n, long N, char* work, const CensoredLayout& L, hipStream_t s);  // w = n~ o t
+int censored_result(const double* alpha, const int* side, const double* wts, int n, int with_grad, double* out, double* dr, char* work,
+                    const CensoredLayout& L, hipStream_t s);
+// dtheta[p] (+)= sum_ij u_i dK_ij/dtheta_p alpha_j; partials: gram_grad_partials(N) elements.  Reads Xt, u, alpha only.
+template <typename T>
+int gram_bilinear(int model, int d, const T* Xt, long N, int n, const double* theta, const T* u, const T* alpha, T* partials,
+                  T* dtheta, int accumulate, hipStream_t s);
+// out [4][count]: log Phi(z), h = phi / Phi, h (z + h), h [1 - (z + h)(z + 2 h)]
+int debug_censored_terms(const double* z, long count, double* out, hipStream_t s);
+
 }  // namespace dgp

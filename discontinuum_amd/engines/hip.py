@@ -211,14 +211,44 @@ class ConstantMeanShortcut(MeanShortcut):
         return (-row[_lib.OUT_SUM_DR],)
 
 
+class CensorState:
+    """The censoring of a fit: ``side`` (device int32, -1 = the target value is a limit and the truth lies below it, +1 =
+    above, 0 = observed), the latest mode ``f`` of the Laplace approximation (device; None = cold start from the prior mean)
+    and the ``status`` of the last mode search (Newton iterations, final max |df|, halvings, capped rows)."""
+
+    def __init__(self, side, maxit=50, tol=1e-10):
+        self.side, self.f, self.status, self.maxit, self.tol = side, None, None, int(maxit), float(tol)
+
+    def update(self, f, status):
+        self.f, self.status = f.detach(), tuple(status)
+
+
+def censor_sides(censored, n):
+    """``fit(censored=...)`` as an int32 array of -1 / 0 / +1, or None when nothing is censored.  Booleans: True = the
+    reported value is a detection limit and the truth is below it."""
+    if censored is None:
+        return None
+    a = np.asarray(getattr(censored, "values", censored))
+    if a.shape != (n,):
+        raise ValueError(f"censored must align with the target: expected shape ({n},), got {a.shape}")
+    if a.dtype == bool:
+        side = np.where(a, -1, 0).astype(np.int32)
+    else:
+        if not np.all(np.isin(a, (-1, 0, 1))):
+            raise ValueError("censored must be boolean or hold -1 (below the limit), 0 (observed), +1 (above the limit)")
+        side = a.astype(np.int32)
+    return side if side.any() else None
+
+
 class PriorSpec:
     """What ``self.model(train_x)`` hands to the marginal likelihood: the device plan, the constrained kernel
     hyperparameters (host, with grad), the prior mean and the noise diagonal (device, with grad; evaluated when
-    read), and -- for mean / noise models that have one -- the host-side ``shortcut`` the marginal likelihood uses
-    instead of them."""
+    read), -- for mean / noise models that have one -- the host-side ``shortcut`` the marginal likelihood uses
+    instead of them, and the ``CensorState`` of a fit with censored observations."""
 
-    def __init__(self, plan, theta, mean, noise, shortcut=None):
+    def __init__(self, plan, theta, mean, noise, shortcut=None, censored=None):
         self.plan, self.theta, self._mean, self._noise, self.shortcut = plan, theta, mean, noise, shortcut
+        self.censored = censored
 
     @property
     def mean(self):
@@ -248,6 +278,8 @@ class MarginalHIP(BaseModel):
         self._plan = None
         self._factor_key = None
         self._pending_device = None  # (train_x, train_y) whose upload is deferred to the first prediction (fit_many)
+        self._censor = None  # CensorState of a fit with censored observations
+        self.laplace_status_ = None
 
     # ------------------------------------------------------------------ device plumbing
     def _tensor(self, a):
@@ -275,7 +307,31 @@ class MarginalHIP(BaseModel):
             mean=lambda: self.model.prior_mean(self._train_x),
             noise=lambda: self.likelihood.train_noise(self._train_x.device, self.dtype),
             shortcut=self._mean_shortcut(),
+            censored=getattr(self, "_censor", None),
         )
+
+    _CENSOR_REFUSAL = ("{what} is not available for a fit with censored observations: it reads the pseudo-data of the Laplace "
+                       "approximation as if they were samples")
+
+    def _refuse_censored(self, what):
+        if getattr(self, "_censor", None) is not None:
+            raise NotImplementedError(self._CENSOR_REFUSAL.format(what=what))
+
+    def _set_censoring(self, censored, n):
+        """Parse ``censored`` (see ``fit``) and keep it on the engine; the side vector goes to the device with the data."""
+        side = censor_sides(censored, n)
+        self._censor_host = side
+        self._censor = None
+        self.laplace_status_ = None
+        if side is None:
+            return
+        if getattr(self.likelihood, "second_noise_covar", None) is not None:
+            raise NotImplementedError("censored observations need a fixed-noise likelihood: the Laplace fit produces no gradient "
+                                      "for a learned noise term (rating-gp is not supported)")
+        self._censor = CensorState(torch.as_tensor(side, dtype=torch.int32).to(self.device).contiguous(),
+                                   maxit=self.laplace_maxit, tol=self.laplace_tol)
+
+    laplace_maxit, laplace_tol = 50, 1e-10  # Newton's mode search of a censored fit
 
     def _mean_shortcut(self):
         """The host-side form of this model's prior mean and noise (``MeanShortcut``) or None.  Here: a learned
@@ -344,6 +400,7 @@ class MarginalHIP(BaseModel):
             "extra": extra or {},
             "model_state_dict": self.model.state_dict(),
             "likelihood_state_dict": self.likelihood.state_dict(),
+            "censored": None if getattr(self, "_censor_host", None) is None else torch.as_tensor(self._censor_host, dtype=torch.int8),
             "optimizer_state_dict": None, "optimizer_name": None, "optimizer_lr": None,
             "scheduler_state_dict": None, "scheduler_name": None,
         }
@@ -379,7 +436,7 @@ class MarginalHIP(BaseModel):
                                f"unexpected parameters {unexpected}")
 
     @classmethod
-    def load(cls, f, covariates, target, target_unc=None):
+    def load(cls, f, covariates, target, target_unc=None, censored=None):
         """A model restored from ``save()`` output and re-attached to its data: ready to predict, or to continue
         training with ``fit(..., resume=True)`` (engines/gpytorch.py:47-105).  The file is read with
         ``weights_only=True`` (nothing in it is executed); checkpoints of earlier versions that pickled the
@@ -400,6 +457,9 @@ class MarginalHIP(BaseModel):
         self._current_iteration = record.get("current_iteration", 0)
         self._resume_info = {key: record.get(key) for key in cls._OPTIMIZER_KEYS}
         self._resume_info["current_iteration"] = self._current_iteration
+        if censored is None and record.get("censored") is not None:
+            censored = record["censored"].numpy().astype(np.int32)  # the side vector the checkpoint carries
+        self._set_censoring(censored, y.shape[0])
         self._setup_device(x, y)
         self.is_fitted = True
         return self
@@ -426,11 +486,18 @@ class MarginalHIP(BaseModel):
 
     def fit(self, covariates, target, target_unc=None, iterations: int = 100, optimizer: str | None = None,
             learning_rate: float | None = None, early_stopping: bool = False, patience: int = 60,
-            scheduler: bool = True, resume: bool = False, penalty_callback=None, penalty_weight: float = 0.0):
+            scheduler: bool = True, resume: bool = False, penalty_callback=None, penalty_weight: float = 0.0, censored=None):
         """Train the hyperparameters; arguments and behaviour as ``MarginalGPyTorch.fit``
         (engines/gpytorch.py:162-458): Adam (default lr 0.05) or AdamW, gradient clipping to norm 1, optional
         ReduceLROnPlateau, NaN iterations skipped (more than ten in a row raise), optional early stopping, resume from a
-        checkpoint (``load``) or from an interrupted call (``resume=True``), optional penalty term."""
+        checkpoint (``load``) or from an interrupted call (``resume=True``), optional penalty term.
+
+        ``censored``: array-like aligned with ``target``, boolean (True = the reported value is a detection limit and the
+        truth is below it) or -1 / 0 / +1 (below / observed / above the reported limit).  The limits pass through the target
+        pipeline like any value (it is monotone); the marginal likelihood becomes the Laplace approximation of the Tobit
+        likelihood (``dgp_laplace_fit_step``) and every product that reads the held factorisation sees the Laplace
+        posterior.  None or no censored row: the plain fit, bit for bit.  ``laplace_status_`` keeps the last mode search's
+        (Newton iterations, final max |df|, halvings, capped rows)."""
         trained = bool(getattr(self, "model", None) is not None and getattr(self, "likelihood", None) is not None
                        and self.is_fitted)
         from_checkpoint = trained and self._resume_info is not None
@@ -444,7 +511,11 @@ class MarginalHIP(BaseModel):
                 restore = False
         if not restore:
             self._fresh_model(x, y, unc)
+        if censored is not None or not restore:
+            self._set_censoring(censored, y.shape[0])
         self._setup_device(x, y)
+        if self._censor is not None:
+            self._censor.f = None
         self.model.train()
         self.likelihood.train()
 
@@ -485,7 +556,7 @@ class MarginalHIP(BaseModel):
         # penalty callback is an autograd expression and keeps the autograd path
         closed_penalty = use_penalty and hasattr(penalty_callback, "explicit_terms")
         explicit = (ExplicitObjective.build(self, mll._priors)
-                    if self.explicit_host_algebra and (not use_penalty or closed_penalty) else None)
+                    if self.explicit_host_algebra and (not use_penalty or closed_penalty) and self._censor is None else None)
         try:
             for i in bar:
                 self._current_iteration = first + i
@@ -497,6 +568,8 @@ class MarginalHIP(BaseModel):
                             penalty_weight=float(penalty_weight) if use_penalty else 0.0)], dtype=torch.float64)
                     else:
                         objective = -mll(self._prior(), self._train_y)
+                        if self._censor is not None:
+                            self.laplace_status_ = self._censor.status
                 except Exception:
                     bad_in_a_row += 1
                     if bad_in_a_row > 10:
@@ -579,8 +652,16 @@ class MarginalHIP(BaseModel):
         if self._factor_key != key:
             with torch.no_grad():
                 spec = self._prior()
-                r = (self._train_y - spec.mean).contiguous()
-                out = self._plan.factorize(spec.theta, r, spec.noise.contiguous())
+                if spec.censored is not None:  # the Laplace posterior's pseudo-data system, warm-started at the last mode
+                    cs = spec.censored
+                    out, f_hat, stat = self._plan.laplace_factorize(
+                        spec.theta, self._train_y, spec.mean.contiguous(), spec.noise.contiguous(), cs.side, f=cs.f,
+                        maxit=cs.maxit, tol=cs.tol)
+                    cs.update(f_hat, stat)
+                    self.laplace_status_ = cs.status
+                else:
+                    r = (self._train_y - spec.mean).contiguous()
+                    out = self._plan.factorize(spec.theta, r, spec.noise.contiguous())
                 info = int(out[3].item())
             if info != 0:
                 raise NotPSDError(f"Matrix not positive definite: Cholesky pivot {info} is not positive")
@@ -673,6 +754,8 @@ class MarginalHIP(BaseModel):
         inverse Fisher information (``prior``: with the priors' curvature).  See ``discontinuum_amd.loads``."""
         from ..loads import DEFAULT_MAX_BYTES, aggregate
 
+        if hyperparameters:
+            self._refuse_censored("aggregate(hyperparameters=True)")
         return aggregate(self, covariates, weights, freq=freq, ci=ci, pred_noise=pred_noise, return_cov=return_cov,
                          max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes, hyperparameters=hyperparameters, prior=prior)
 
@@ -745,6 +828,7 @@ class MarginalHIP(BaseModel):
         See ``discontinuum_amd.influence.influence``."""
         from ..influence import influence
 
+        self._refuse_censored("influence")
         return influence(self, covariates, weights, folds=folds, freq=freq, max_bytes=max_bytes)
 
     @is_fitted
@@ -779,6 +863,7 @@ class MarginalHIP(BaseModel):
         ``discontinuum_amd.validation.cross_validate``."""
         from ..validation import cross_validate
 
+        self._refuse_censored("cross_validate")
         return cross_validate(self, folds=folds, ci=ci, return_folds=return_folds)
 
     @is_fitted
@@ -815,6 +900,7 @@ class MarginalHIP(BaseModel):
         (the training objective is this divided by n).  See ``discontinuum_amd.hyperpar.hyperparameter_uncertainty``."""
         from ..hyperpar import hyperparameter_uncertainty
 
+        self._refuse_censored("hyperparameter_uncertainty")
         return hyperparameter_uncertainty(self, ci=ci, prior=prior)
 
     @is_fitted
@@ -829,6 +915,7 @@ class MarginalHIP(BaseModel):
         ``discontinuum_amd.hyperpar.predict_marginalized``."""
         from ..hyperpar import predict_marginalized
 
+        self._refuse_censored("predict_marginalized")
         return predict_marginalized(self, covariates, ci=ci, prior=prior, pred_noise=pred_noise)
 
     def build_model(self, X, y, **kwargs):

@@ -73,6 +73,47 @@ class _RowNLL(torch.autograd.Function):
         return (None, (dtheta * g).to(ctx.dtypes[0]), None, None) + grads
 
 
+class _LaplaceNLL(torch.autograd.Function):
+    """The data term of a fit with censored rows: the Laplace approximation of the Tobit marginal likelihood, value and
+    gradients from one ``dgp_laplace_fit_step`` (Newton's mode search on the factorise path, one step at the mode, one
+    extra derivative sweep).  ``state`` (``engines/hip.py::CensorState``) carries the side vector and the warm start, and
+    receives the mode and the search's status.  With a ``shortcut`` the mean parameters' gradients come from the result
+    row (recomputed there from dr = alpha - u); otherwise d NLL / d mean = -dr.  The noise gets no gradient: the
+    likelihood is fixed-noise by construction (the engine refuses anything else)."""
+
+    @staticmethod
+    def forward(ctx, plan, theta, y, mean, noise, state, shortcut, *params):
+        out, dr, f_hat, stat = plan.laplace_fit_step(theta, y, mean.detach().contiguous(), noise.detach().contiguous(), state.side,
+                                                     f=state.f, maxit=state.maxit, tol=state.tol)
+        host = out.to("cpu", torch.float64)
+        info = int(host[_lib.OUT_INFO].item())
+        if info != 0:
+            raise NotPSDError(f"Matrix not positive definite: Cholesky pivot {info} is not positive")
+        state.update(f_hat, stat)
+        ctx.save_for_backward(host[_lib.OUT_DTHETA:_lib.OUT_DTHETA + plan.ntheta].clone(), dr)
+        ctx.param_grads = shortcut.grads(host) if shortcut is not None else ()
+        ctx.dtypes = (theta.dtype,) + tuple(p.dtype for p in params)
+        ctx.shapes = tuple(p.shape for p in params)
+        return host[_lib.OUT_NLL].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        dtheta, dr = ctx.saved_tensors
+        need = ctx.needs_input_grad  # (plan, theta, y, mean, noise, state, shortcut, *params)
+        dmean = -dr * g.to(dr.device, dr.dtype) if need[3] else None
+        grads = tuple((torch.as_tensor(v, dtype=torch.float64) * g).to(dt).reshape(shape)
+                      for v, dt, shape in zip(ctx.param_grads, ctx.dtypes[1:], ctx.shapes))
+        return (None, (dtheta * g).to(ctx.dtypes[0]) if need[1] else None, None, dmean, None, None, None) + grads
+
+
+def laplace_gp_nll(plan, theta, y, mean, noise, state, shortcut):
+    """The censored data term behind the same jitter-retry policy as ``exact_gp_nll``."""
+    params = shortcut.params if shortcut is not None else ()
+    return _with_jitter_retries(
+        plan, lambda: _LaplaceNLL.apply(plan, theta, y, mean, noise, state, shortcut, *params),
+        lambda jitter: _LaplaceNLL.apply(plan, theta, y, mean, noise + jitter, state, shortcut, *params))
+
+
 class _PredictiveMean(torch.autograd.Function):
     """K(X*, X; theta) K^^-1 r as a differentiable function of (theta, r, noise): forward is
     ``dgp_predict_mean``, backward ``dgp_mean_vjp``.  Both read the factorisation the plan holds from the
@@ -193,6 +234,15 @@ class ExactMarginalLogLikelihood:
         """``output`` is the engine's prior spec (plan, theta, mean on device, noise on device)."""
         n = target.shape[0]
         shortcut = getattr(output, "shortcut", None)
+        censored = getattr(output, "censored", None)
+        if censored is not None:  # censored rows: the Laplace approximation (its own launches; the priors run beside them)
+            if shortcut is not None:
+                r, noise = shortcut.residual_and_noise(output.plan, target)
+                mean = (target - r).contiguous()  # the shortcut's constant mean as a device vector
+            else:
+                mean, noise = output.mean.contiguous(), output.noise.contiguous()
+            nll = laplace_gp_nll(output.plan, output.theta, target, mean, noise, censored, shortcut)
+            return ((-nll + self.log_prior()) / n).reshape(1)
         if shortcut is not None:  # mean / noise parameters on the host: device vectors without autograd
             r, noise = shortcut.residual_and_noise(output.plan, target)
         else:

@@ -126,6 +126,7 @@ class LoadestGPMarginalHIP(LoadestDataMixin, MarginalHIP):
         """What the samples in hand were worth: the exact change of every period's LOAD (kg; the flux weights of
         ``annual_flux``) had each fold of observations not been sampled -- ``MarginalHIP.influence``, named to mirror
         ``sample_value``."""
+        self._refuse_censored("sample_influence")
         return super().influence(daily, self._flux_weights(daily), folds=folds, freq=freq, max_bytes=max_bytes)
 
     @is_fitted
@@ -148,6 +149,7 @@ class LoadestGPMarginalHIP(LoadestDataMixin, MarginalHIP):
         ``folds``).  See ``discontinuum_amd.validation.flux_bias``."""
         from ..validation import flux_bias
 
+        self._refuse_censored("flux_bias")
         return flux_bias(self, cv=cv, folds=folds)
 
     def flow_normalized_flux(self, daily, freq="YE", flow_window=None, ci=0.95, pred_noise=False, return_cov=False,

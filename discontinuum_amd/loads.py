@@ -163,6 +163,8 @@ def point_moments(model, Xnew, w, groups, labels, n_points, ci=0.95, pred_noise=
     """The moment core of ``aggregate`` on model-space inputs: design rows ``Xnew`` (m, d), weights ``w`` (m,), int32
     period ids ``groups`` (non-decreasing, -1 = excluded), period ``labels`` and ``n_points`` per period -- what
     ``aggregate`` builds from a covariates record and ``flow_normalized`` from its (day, flow) pairs."""
+    if hyperparameters and hasattr(model, "_refuse_censored"):
+        model._refuse_censored("the hyperparameters' uncertainty of period sums (hyperparameters=True)")
     mode, s, t = target_transform(model.dm)
     Xnew = Xnew.to(model.device).contiguous()
     m = Xnew.shape[0]

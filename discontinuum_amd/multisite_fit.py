@@ -411,6 +411,16 @@ def _per_site_clip(raw_grads: dict, B: int, max_norm: float = 1.0):
     return coef, grads
 
 
+def _refuse_censored_records(datasets, what):
+    """A record may carry a fourth entry, the ``censored`` argument of ``MarginalHIP.fit``: batched plans have no Laplace
+    mode search, so a record with a censored row is refused (train that site with its own ``fit(censored=...)``)."""
+    for record in datasets:
+        record = tuple(record)
+        if len(record) > 3 and record[3] is not None and np.asarray(getattr(record[3], "values", record[3])).any():
+            raise NotImplementedError(f"{what} does not support censored observations (batched plans have no Laplace mode "
+                                      "search): fit that site with its own fit(censored=...)")
+
+
 def fit_many(models, datasets, iterations: int = 100, learning_rate: float = 0.05, patience: int = 60,
              scheduler: bool = True, progress: bool = False, early_stopping: bool = False,
              monotonic_penalty_weight: float = 0.0, grid_size: int = 64, monotonic_penalty_interval: int = 1,
@@ -449,6 +459,7 @@ def fit_many(models, datasets, iterations: int = 100, learning_rate: float = 0.0
     sites were built before it; with them it depends on the site alone (``fit_many_distributed`` relies on that)."""
     if site_seeds is not None and len(site_seeds) != len(models):
         raise ValueError("site_seeds needs one seed per model")
+    _refuse_censored_records(datasets, "fit_many")
     t_enter = time.perf_counter()
     if optimizer not in ("adam", "adamw"):
         raise ValueError(f"Unsupported optimizer: {optimizer!r}. Supported optimizers are 'adam' and 'adamw'.")
@@ -805,6 +816,7 @@ def fit_many_distributed(models, datasets, group=None, load: str = "all", seed: 
 
     if load not in ("all", "rank0", "own"):
         raise ValueError("load must be 'all', 'rank0' or 'own'")
+    _refuse_censored_records(datasets, "fit_many_distributed")
     if "resume" in kw or kw.get("return_state") or "site_seeds" in kw:
         raise ValueError("fit_many_distributed: resume / return_state are per-rank; use fit_many on each rank's share")
     if len(models) != len(datasets) or not models:

@@ -38,6 +38,7 @@ extern "C" {
 #define DGP_E_WORKSPACE (-3) /* workspace missing or too small */
 #define DGP_E_STATE (-4)     /* call order violated (e.g. predict before factorize) */
 #define DGP_E_FULL (-5)      /* dgp_composite_define: all 64 slots of the process hold other structures */
+#define DGP_E_NOCONV (-6)    /* dgp_laplace_*: the mode search did not converge within maxit Newton iterations */
 
 /* output vector of dgp_fit_step / dgp_factorize, in elements of the plan dtype */
 #define DGP_OUT_NLL 0    /* 1/2 r^T K^^-1 r + 1/2 log|K^| + n/2 log 2 pi */
@@ -205,6 +206,57 @@ int dgp_fit_step(dgp_plan* plan, const double* theta_host, const void* r_dev, co
  * This is the eval-mode cache build of ExactGP (engines/gpytorch.py:618-622). */
 int dgp_factorize(dgp_plan* plan, const double* theta_host, const void* r_dev, const void* noise_dev,
                   void* out_dev, void* stream);
+
+/* CENSORED OBSERVATIONS (non-detects) by the Laplace approximation of a GP with a Tobit likelihood.  Row i is observed
+ * (side 0: y_i, Gaussian with variance v_i = noise_i) or censored at the limit l_i = y_i (side -1: the truth is below it,
+ * +1: above): log p_i = log Phi(z_i), z_i = s_i (f_i - l_i) / sigma_i.  With h = phi(z) / Phi(z):
+ *   g_i = s_i h / sigma_i,   W_i = h (z + h) / v_i,   d3_i = -(s_i / sigma_i^3) h [1 - (z + h)(z + 2 h)]
+ * (observed rows: W = 1 / v, d3 = 0).  At the mode the posterior of the latent f is the exact GP posterior for the
+ * pseudo-targets y~_i = f_i + g_i / W_i with the diagonal pseudo-noise n~_i = 1 / W_i, so
+ *   a Newton step   = one dgp_factorize pass with r~ = y~ - m and n~:  a = (K + diag n~)^-1 r~,  f_new = y~ - n~ o a
+ *                     (no product with K).  The first step from the caller's f is taken whole (the a with f - m = K a is
+ *                     not known for it); later steps are halved, t in {1, 1/2, .. 1/64}, until the objective
+ *                     Psi(t) = sum_i log p_i(f(t)) - 1/2 a(t)^T (f(t) - m) does not fall (f and a are linear in t: O(n)).
+ *   at the mode     NLL_L = NLL_engine + sum_{censored} [-log Phi(z_i) - 1/2 n~_i alpha_i^2 + 1/2 log W_i - 1/2 log 2 pi],
+ *                   Sigma_ii = n~_i - n~_i^2 (K^^-1)_ii,  t_i = -1/2 Sigma_ii d3_i,  u = K^^-1 (n~ o t) = T^T (T (n~ o t)),
+ *                   dNLL_L/dtheta_p = dtheta_engine[p] + u^T dK/dtheta_p alpha  (one pair sweep over the lower triangle for
+ *                   all p, dK/dtheta never stored),   dNLL_L/dr = alpha - u.
+ * Guards: the functions of z go through erfcx for z < 0 and erfc / log1p for z >= 0; a censored row with W_i v_i < 1e-12 (an
+ * uninformative limit, about z > 7.5) is CAPPED: n~_i = 1e12 v_i, d3_i = 0.
+ *   y_dev / mean_dev / noise_dev   n doubles: observation or limit, prior mean m, noise variance v (model space)
+ *   side_dev    n int32: -1 / 0 / +1
+ *   f_dev       n doubles, in: the start of the mode search (m for a cold start), out: the mode
+ *   out_dev     DGP_OUT_* layout: NLL = NLL_L, DTHETA the total gradient, SUM_DR / DR_W0.. from dr = alpha - u; QUAD, LOGDET
+ *               and INFO are those of the pseudo-data system (a non-positive pivot is reported through INFO as by dgp_fit_step)
+ *   dr_dev      alpha - u (n doubles, or null)
+ *   stat_host   4 doubles: Newton iterations (factorise passes of the search), final max |f_new - f|, halvings, capped rows
+ * Passes: terms (elementwise) -> status read; per Newton iteration: dgp_factorize's launches, proposal + line search +
+ * update (elementwise, two-stage fixed-order sums), terms; then dgp_fit_step's launches at the mode, two triangular products
+ * for u, the pair sweep, one result pass.  The host reads one small status block per Newton iteration: ONE STREAM
+ * SYNCHRONISATION PER ITERATION, and one more before returning.  No floating-point atomics: bitwise repeatable.
+ * With no censored row both entries launch exactly what dgp_fit_step / dgp_factorize launch on (y - m, v) -- the same bits
+ * in out_dev, dr_dev and the plan -- report 0 iterations and set f = m + K alpha.
+ * float64 single-site plans only.  Before any launch: DGP_E_ARG (null plan / argument, f_dev included; an fp32 or batched
+ * plan; maxit < 1; tol < 0; misaligned work area), DGP_E_WORKSPACE (work area missing or smaller than
+ * dgp_laplace_workspace_bytes), DGP_E_STATE (no inputs).  After the first pass: DGP_E_ARG for a side value outside -1 / 0 / +1.
+ * DGP_E_NOCONV when max |f_new - f| > tol after maxit iterations: the step at the last iterate has still run, the results
+ * and stat_host are filled and the plan holds that system.  dgp_laplace_fit_step leaves L, L^-1, K^^-1 and alpha of the
+ * pseudo-data system in the plan; dgp_laplace_factorize (value only, dtheta = 0: the prediction-time cache build) L, L^-1
+ * and alpha -- every product that reads the held factorisation then sees the Laplace posterior. */
+size_t dgp_laplace_workspace_bytes(const dgp_plan* plan);
+int dgp_laplace_fit_step(dgp_plan* plan, const double* theta_host, const void* y_dev, const void* mean_dev, const void* noise_dev,
+                         const int32_t* side_dev, void* f_dev, int maxit, double tol, void* work_dev, size_t work_bytes,
+                         void* out_dev, void* dr_dev, double* stat_host, void* stream);
+int dgp_laplace_factorize(dgp_plan* plan, const double* theta_host, const void* y_dev, const void* mean_dev, const void* noise_dev,
+                          const int32_t* side_dev, void* f_dev, int maxit, double tol, void* work_dev, size_t work_bytes,
+                          void* out_dev, double* stat_host, void* stream);
+/* out [4][count] = log Phi(z), h = phi(z) / Phi(z), h (z + h), h [1 - (z + h)(z + 2 h)]: the pointwise functions of the
+ * entries above, for tests.  z_dev: count doubles on the device. */
+int dgp_debug_censored_terms(const double* z_dev, int64_t count, double* out_dev, void* stream);
+/* dtheta_dev[p] = sum_ij u_i dK_ij/dtheta_p alpha_j, p < ntheta: the pair sweep of dgp_laplace_fit_step alone, for tests (u_dev,
+ * alpha_dev: n doubles; work area as for dgp_laplace_fit_step).  Reads the plan's inputs only. */
+int dgp_debug_bilinear(dgp_plan* plan, const double* theta_host, const void* u_dev, const void* alpha_dev, void* work_dev,
+                       size_t work_bytes, double* dtheta_dev, void* stream);
 
 /* Workspace for dgp_predict on m test points. */
 size_t dgp_predict_workspace_bytes(const dgp_plan* plan, int64_t m);
