@@ -214,31 +214,35 @@ class GPPlan:
 
     # ------------------------------------------------------------------ censored observations (Laplace)
     def _laplace(self, with_grad, theta, y, mean, noise, side, f, maxit, tol):
-        name = "dgp_laplace_fit_step" if with_grad else "dgp_laplace_factorize"
-        if self.batch != 1 or self.dtype != torch.float64:
-            raise ValueError(f"{name}: censored fits need a float64 single-site plan")
+        B = self.batch
+        name = ("dgp_laplace_fit_step" if with_grad else "dgp_laplace_factorize") if B == 1 else (
+            "dgp_laplace_batched_fit_step" if with_grad else "dgp_laplace_batched_factorize")
+        if self.dtype != torch.float64:
+            raise ValueError(f"{name}: censored fits need a float64 " + ("single-site plan" if B == 1 else "plan"))
         for t, what in ((y, "y"), (mean, "mean"), (noise, "noise")):
             self._check_vec(t, what)
-        if not (torch.is_tensor(side) and side.is_cuda and side.dtype == torch.int32 and side.is_contiguous() and side.numel() == self.n):
-            raise ValueError(f"side must be a contiguous int32 CUDA tensor with {self.n} elements")
+        if not (torch.is_tensor(side) and side.is_cuda and side.dtype == torch.int32 and side.is_contiguous()
+                and side.numel() == self.n * B):
+            raise ValueError(f"side must be a contiguous int32 CUDA tensor with {self.n * B} elements")
         if f is None:
             f = mean.clone()  # cold start
         else:
             self._check_vec(f, "f")
             f = f.clone()
-        th = _theta_array(theta, self.ntheta)
-        stat = (C.c_double * 4)()
+        th = _theta_array(theta, self.ntheta * B)
+        stat = (C.c_double * (4 * B))()
+        shape = (lambda k: (k,)) if B == 1 else (lambda k: (B, k))
+        fn = getattr(self.lib, name)
         with torch.cuda.device(self.device):
-            need = int(self.lib.dgp_laplace_workspace_bytes(self._h))
+            need = int((self.lib.dgp_laplace_workspace_bytes if B == 1 else self.lib.dgp_laplace_batched_workspace_bytes)(self._h))
             work = self._work_area("_laplace_ws", need, name)
-            out = torch.empty(_lib.OUT_LEN, dtype=self.dtype, device=self.device)
-            dr = torch.empty(self.n, dtype=self.dtype, device=self.device) if with_grad else None
+            out = torch.empty(shape(_lib.OUT_LEN), dtype=self.dtype, device=self.device)
+            dr = torch.empty(shape(self.n), dtype=self.dtype, device=self.device) if with_grad else None
             args = (self._h, th, _ptr(y), _ptr(mean), _ptr(noise), _ptr(side), _ptr(f), int(maxit), float(tol), work, need, _ptr(out))
-            if with_grad:
-                rc = self.lib.dgp_laplace_fit_step(*args, _ptr(dr), stat, _stream())
-            else:
-                rc = self.lib.dgp_laplace_factorize(*args, stat, _stream())
-        self.laplace_stat = tuple(float(v) for v in stat)  # kept for a caller that catches E_NOCONV
+            rc = fn(*args, _ptr(dr), stat, _stream()) if with_grad else fn(*args, stat, _stream())
+        vals = [float(v) for v in stat]
+        # kept for a caller that catches E_NOCONV; a batched plan: one 4-tuple per site
+        self.laplace_stat = tuple(vals) if B == 1 else tuple(tuple(vals[4 * b:4 * b + 4]) for b in range(B))
         _lib.check(rc, name)
         return (out, dr, f, self.laplace_stat) if with_grad else (out, f, self.laplace_stat)
 
@@ -248,7 +252,12 @@ class GPPlan:
         -> (out[32], dr[n], f_hat[n], stat) with ``out[OUT_NLL]`` the Laplace NLL, ``out[OUT_DTHETA:]`` its gradient,
         dr = alpha - u and stat = (Newton iterations, final max |df|, halvings, capped rows); the plan holds the
         pseudo-data system's factorisation.  ``DGPError`` with code ``E_NOCONV`` when ``maxit`` does not suffice
-        (``self.laplace_stat`` is set either way)."""
+        (``self.laplace_stat`` is set either way).
+        A batched plan (``batch`` > 1, ragged or not) takes batch-major arrays -- theta (batch, ntheta), y / mean / noise / f
+        (batch, n), side int32 (batch, n) -- and returns out (batch, 32), dr (batch, n), f_hat (batch, n) and stat as a tuple of
+        ``batch`` 4-tuples: Newton's iterations run in lockstep, a finished site is frozen, and every site's mode, iteration
+        count and halvings are its own (``dgp_laplace_batched_fit_step``).  ``E_NOCONV`` when any censored site is not
+        converged after ``maxit``; a site that is not positive definite reports it in its own ``out[b, OUT_INFO]``."""
         return self._laplace(True, theta, y, mean, noise, side, f, maxit, tol)
 
     def laplace_factorize(self, theta, y, mean, noise, side, f=None, maxit=50, tol=1e-10):
@@ -265,15 +274,18 @@ class GPPlan:
         return out
 
     def bilinear(self, theta, u: torch.Tensor, alpha: torch.Tensor):
-        """sum_ij u_i dK_ij/dtheta_p alpha_j for every p (ntheta,): the censored fit's pair sweep alone (tests)."""
+        """sum_ij u_i dK_ij/dtheta_p alpha_j for every p (ntheta,): the censored fit's pair sweep alone (tests).  A batched plan:
+        u, alpha (batch, n), theta (batch, ntheta) -> (batch, ntheta)."""
         self._check_vec(u, "u")
         self._check_vec(alpha, "alpha")
-        th = _theta_array(theta, self.ntheta)
+        B = self.batch
+        th = _theta_array(theta, self.ntheta * B)
+        name = "dgp_debug_bilinear" if B == 1 else "dgp_debug_bilinear_batched"
         with torch.cuda.device(self.device):
-            need = int(self.lib.dgp_laplace_workspace_bytes(self._h))
-            work = self._work_area("_laplace_ws", need, "dgp_debug_bilinear")
-            out = torch.empty(self.ntheta, dtype=self.dtype, device=self.device)
-            _lib.check(self.lib.dgp_debug_bilinear(self._h, th, _ptr(u), _ptr(alpha), work, need, _ptr(out), _stream()), "dgp_debug_bilinear")
+            need = int((self.lib.dgp_laplace_workspace_bytes if B == 1 else self.lib.dgp_laplace_batched_workspace_bytes)(self._h))
+            work = self._work_area("_laplace_ws", need, name)
+            out = torch.empty(self.ntheta if B == 1 else (B, self.ntheta), dtype=self.dtype, device=self.device)
+            _lib.check(getattr(self.lib, name)(self._h, th, _ptr(u), _ptr(alpha), work, need, _ptr(out), _stream()), name)
         return out
 
     def predict(self, theta, Xs: torch.Tensor, chunk: int | None = None):

@@ -1183,77 +1183,111 @@ int dgp_factorize(dgp_plan* p, const double* theta, const void* r, const void* n
 }  // extern "C"
 
 // ---- censored observations: Newton's mode search on the factorise path, then one step at the mode (dgp_censored.hip).
+// One code path for a single-site plan and for a batch: every Newton iteration factorises ALL sites in lockstep; a site is done when
+// it has no censored row, its proposal is within tol or its factorisation failed, and a done site is frozen on the device
+// (CEN_ST_DONE), so that it rides through the remaining factorisations on unchanged pseudo-data.  The host reads the B status
+// blocks in one copy per iteration.  stat: [B][4].  `batched`: the entry's texts name the site.
 // Returns 0, a HIP error (> 0), or DGP_E_ARG / DGP_E_NOCONV with the error text already set.
 static int laplace(dgp_plan* p, const double* theta, const double* y, const double* mean, const double* noise, const int* side,
-                   double* f, int maxit, double tol, char* work, double* out, double* dr, double* stat, int with_grad,
+                   double* f, int maxit, double tol, char* work, double* out, double* dr, double* stat, int with_grad, int batched,
                    const char* where, hipStream_t s) {
-  const CensoredLayout L = censored_layout(p->N, p->n);
+  const int B = p->B;
+  const CensoredLayout L = censored_layout(p->N, p->n, B);
+  const Batch bt = batch_of<double>(p);
   auto D = [&](size_t off) { return (double*)(work + off); };
   const int n = (int)p->n;
+  const long wss = (long)(L.slice / sizeof(double));
   const double* alpha = (const double*)p->alpha;
-  double st[CEN_ST_LEN];
+  std::vector<double> st((size_t)B * CEN_ST_LEN);
+  auto S = [&](int b, int k) -> double { return st[(size_t)b * CEN_ST_LEN + k]; };
   auto read_status = [&]() -> int {
-    hipError_t e = hipMemcpyAsync(st, D(L.status), sizeof(st), hipMemcpyDeviceToHost, s);
+    hipError_t e = hipMemcpyAsync(st.data(), D(L.status), sizeof(double) * st.size(), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     return (int)e;
   };
   int rc;
-  stat[0] = stat[1] = stat[2] = stat[3] = 0.0;
-  if ((rc = censored_terms(f, y, side, noise, mean, n, work, L, s)) || (rc = read_status())) return rc;
-  if (st[CEN_ST_BAD] != 0.0) {
-    snprintf(g_err, sizeof(g_err), "%s: side values must be -1, 0 or +1", where);
-    return DGP_E_ARG;
+  for (int k = 0; k < 4 * B; ++k) stat[k] = 0.0;
+  if ((rc = censored_terms(f, y, side, noise, mean, n, 1, 0, work, L, s, bt)) || (rc = read_status())) return rc;
+  bool any = false, any_plain = false;
+  for (int b = 0; b < B; ++b) {
+    if (S(b, CEN_ST_BAD) != 0.0) {
+      if (batched)
+        snprintf(g_err, sizeof(g_err), "%s: side values must be -1, 0 or +1 (site %d)", where, b);
+      else
+        snprintf(g_err, sizeof(g_err), "%s: side values must be -1, 0 or +1", where);
+      return DGP_E_ARG;
+    }
+    (S(b, CEN_ST_NCENS) != 0.0 ? any : any_plain) = true;
   }
-  if (st[CEN_ST_NCENS] == 0.0) {  // nothing censored: the plain step on (y - m, v), bit for bit
+  if (!any) {  // nothing censored: the plain step on (y - m, v), bit for bit
     if ((rc = fit_step<double>(p, theta, D(L.rt), D(L.nn), out, with_grad ? dr : nullptr, with_grad ? D(L.dnoise) : nullptr, with_grad, s)))
       return rc;
-    return censored_mode(f, mean, alpha, n, work, L, s);
+    return censored_mode(f, mean, alpha, n, work, L, s, bt);
   }
-  if ((rc = (int)hipMemsetAsync(D(L.acur), 0, sizeof(double) * (size_t)p->N, s))) return rc;
+  if ((rc = (int)hipMemsetAsync(D(L.acur), 0, sizeof(double) * (size_t)B * (size_t)n, s))) return rc;
+  std::vector<char> active((size_t)B);
+  for (int b = 0; b < B; ++b) active[b] = S(b, CEN_ST_DONE) == 0.0;
   int it = 0;
-  bool converged = false, failed = false;
   for (;;) {
     if ((rc = fit_step<double>(p, theta, D(L.rt), D(L.nn), D(L.out), nullptr, nullptr, 0, s))) return rc;
-    if ((rc = censored_newton_update(f, y, side, noise, mean, alpha, n, it == 0, tol, work, L, s)) || (rc = read_status())) return rc;
     ++it;
-    stat[0] = (double)it;
-    stat[1] = st[CEN_ST_DMAX];
-    stat[2] += st[CEN_ST_HALVINGS];
-    if (st[CEN_ST_INFO] != 0.0) {  // not positive definite: f did not move; the step below reports it through DGP_OUT_INFO
-      failed = true;
-      break;
+    // proposal, line search, update; then the next system (or the one at the mode) of every site that moved
+    if ((rc = censored_newton_update(f, y, side, noise, mean, alpha, n, it, tol, work, L, s, bt)) ||
+        (rc = censored_terms(f, y, side, noise, mean, n, 0, it, work, L, s, bt)) || (rc = read_status()))
+      return rc;
+    bool all_done = true;
+    for (int b = 0; b < B; ++b) {
+      if (!active[b]) continue;
+      stat[4 * b] = (double)it;
+      stat[4 * b + 1] = S(b, CEN_ST_DMAX);
+      stat[4 * b + 2] += S(b, CEN_ST_HALVINGS);
+      if (S(b, CEN_ST_DONE) != 0.0)
+        active[b] = 0;  // converged, or not positive definite: f did not move; the step below reports it through DGP_OUT_INFO
+      else
+        all_done = false;
     }
-    if ((rc = censored_terms(f, y, side, noise, mean, n, work, L, s))) return rc;  // the next system, or the one at the mode
-    if (st[CEN_ST_DMAX] <= tol) {
-      converged = true;
-      break;
-    }
-    if (it >= maxit) break;
+    if (all_done || it >= maxit) break;
   }
   if ((rc = fit_step<double>(p, theta, D(L.rt), D(L.nn), out, nullptr, with_grad ? D(L.dnoise) : nullptr, with_grad, s))) return rc;
   if (with_grad) {
-    if ((rc = censored_weights(alpha, n, p->N, work, L, s))) return rc;
-    // u = T^T (T w) into the work area: the plan's z, alpha and result row stay as the step left them
-    if ((rc = solve<double>((const double*)p->Tm, p->N, D(L.w), n, D(L.z), D(L.u), D(L.spart), D(L.quad), s))) return rc;
-    if ((rc = gram_bilinear<double>(p->model, p->d, (const double*)p->Xt, p->N, n, theta, D(L.u), alpha, D(L.gpart),
-                                    out + DGP_OUT_DTHETA, 1, s)))
+    if ((rc = censored_weights(alpha, n, p->N, work, L, s, bt))) return rc;
+    // u = T^T (T w) in the work area: the plan's z, alpha and result rows stay as the step left them
+    if ((rc = solve_work<double>((const double*)p->Tm, p->N, D(L.slices + L.w), n, D(L.slices + L.z), D(L.slices + L.u),
+                                 D(L.slices + L.spart), D(L.slices + L.quad), wss, s, bt)))
+      return rc;
+    // (the step's Gram build left this theta in the plan's hyperparameter scratch)
+    if ((rc = gram_bilinear<double>(p->model, p->d, (const double*)p->Xt, p->N, n, theta, D(L.slices + L.u), alpha,
+                                    D(L.slices + L.gpart), out + DGP_OUT_DTHETA, 1, s, bt, wss, bt.ws, wss, DGP_OUT_LEN, p->pre, false,
+                                    nullptr)))
       return rc;
   }
-  if ((rc = censored_result(alpha, side, (const double*)p->dr_w, n, with_grad, out, dr, work, L, s)) || (rc = read_status())) return rc;
-  stat[3] = st[CEN_ST_CAPPED];
-  if (!converged && !failed) {
-    snprintf(g_err, sizeof(g_err), "%s: the mode search did not converge in %d Newton iterations (max |df| = %.3g)", where, it, stat[1]);
+  if (any_plain && (rc = censored_mode(f, mean, alpha, n, work, L, s, bt))) return rc;  // the batch-mates without a censored row
+  if ((rc = censored_result(alpha, side, (const double*)p->dr_w, n, with_grad, out, dr, work, L, s, bt)) || (rc = read_status())) return rc;
+  int open_site = -1;
+  for (int b = 0; b < B; ++b) {
+    stat[4 * b + 3] = S(b, CEN_ST_CAPPED);
+    if (active[b] && open_site < 0) open_site = b;
+  }
+  if (open_site >= 0) {
+    if (batched)
+      snprintf(g_err, sizeof(g_err), "%s: the mode search of site %d did not converge in %d Newton iterations (max |df| = %.3g)", where,
+               open_site, it, stat[4 * open_site + 1]);
+    else
+      snprintf(g_err, sizeof(g_err), "%s: the mode search did not converge in %d Newton iterations (max |df| = %.3g)", where, it, stat[1]);
     return DGP_E_NOCONV;
   }
   return 0;
 }
 static int laplace_entry(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise, const int32_t* side,
                          void* f, int maxit, double tol, void* work, size_t work_bytes, void* out, void* dr, double* stat,
-                         int with_grad, const char* where, void* stream) {
+                         int with_grad, int batched, const char* where, void* stream) {
   char msg[160];
   if (!p) return fail(DGP_E_ARG, "null plan");
-  if (p->dtype != DGP_F64 || p->B != 1) {
-    snprintf(msg, sizeof(msg), "%s: censored fits need a float64 single-site plan (fp32 and batched plans are not supported)", where);
+  if (batched ? p->dtype != DGP_F64 : (p->dtype != DGP_F64 || p->B != 1)) {
+    if (batched)
+      snprintf(msg, sizeof(msg), "%s: censored fits need a float64 plan (fp32 plans are not supported)", where);
+    else
+      snprintf(msg, sizeof(msg), "%s: censored fits need a float64 single-site plan (fp32 and batched plans are not supported)", where);
     return fail(DGP_E_ARG, msg);
   }
   if (!theta || !y || !mean || !noise || !side || !f || !out || !stat || maxit < 1 || !(tol >= 0.0)) {
@@ -1262,13 +1296,13 @@ static int laplace_entry(dgp_plan* p, const double* theta, const void* y, const 
   }
   DGP_CHECK_PLAN(p);
   if (!p->have_inputs) return fail(DGP_E_STATE, "dgp_laplace_*: call dgp_set_inputs first");
-  if (!work || work_bytes < dgp_laplace_workspace_bytes(p)) {
+  if (!work || work_bytes < (batched ? dgp_laplace_batched_workspace_bytes(p) : dgp_laplace_workspace_bytes(p))) {
     snprintf(msg, sizeof(msg), "%s: workspace missing or too small", where);
     return fail(DGP_E_WORKSPACE, msg);
   }
   if (((uintptr_t)work & 255) != 0) return fail(DGP_E_ARG, "dgp_laplace_*: the work area must be 256-byte aligned");
   const int rc = laplace(p, theta, (const double*)y, (const double*)mean, (const double*)noise, (const int*)side, (double*)f, maxit, tol,
-                         (char*)work, (double*)out, (double*)dr, stat, with_grad, where, (hipStream_t)stream);
+                         (char*)work, (double*)out, (double*)dr, stat, with_grad, batched, where, (hipStream_t)stream);
   if (rc == DGP_E_ARG || rc == DGP_E_NOCONV) return rc;  // text set where it arose
   return wrap(rc, where);
 }
@@ -1277,19 +1311,38 @@ extern "C" {
 
 size_t dgp_laplace_workspace_bytes(const dgp_plan* p) {
   if (!p || p->dtype != DGP_F64 || p->B != 1) return 0;
-  return censored_layout(p->N, p->n).total;
+  return censored_layout(p->N, p->n, 1).total;
+}
+size_t dgp_laplace_batched_workspace_bytes(const dgp_plan* p) {
+  if (!p || p->dtype != DGP_F64) return 0;
+  return censored_layout(p->N, p->n, p->B).total;
 }
 
 int dgp_laplace_fit_step(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise, const int32_t* side,
                          void* f, int maxit, double tol, void* work, size_t work_bytes, void* out, void* dr, double* stat,
                          void* stream) {
-  return laplace_entry(p, theta, y, mean, noise, side, f, maxit, tol, work, work_bytes, out, dr, stat, 1, "dgp_laplace_fit_step", stream);
+  return laplace_entry(p, theta, y, mean, noise, side, f, maxit, tol, work, work_bytes, out, dr, stat, 1, 0, "dgp_laplace_fit_step",
+                       stream);
 }
 
 int dgp_laplace_factorize(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise, const int32_t* side,
                           void* f, int maxit, double tol, void* work, size_t work_bytes, void* out, double* stat, void* stream) {
-  return laplace_entry(p, theta, y, mean, noise, side, f, maxit, tol, work, work_bytes, out, nullptr, stat, 0, "dgp_laplace_factorize",
+  return laplace_entry(p, theta, y, mean, noise, side, f, maxit, tol, work, work_bytes, out, nullptr, stat, 0, 0, "dgp_laplace_factorize",
                        stream);
+}
+
+int dgp_laplace_batched_fit_step(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise,
+                                 const int32_t* side, void* f, int maxit, double tol, void* work, size_t work_bytes, void* out, void* dr,
+                                 double* stat, void* stream) {
+  return laplace_entry(p, theta, y, mean, noise, side, f, maxit, tol, work, work_bytes, out, dr, stat, 1, 1,
+                       "dgp_laplace_batched_fit_step", stream);
+}
+
+int dgp_laplace_batched_factorize(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise,
+                                  const int32_t* side, void* f, int maxit, double tol, void* work, size_t work_bytes, void* out,
+                                  double* stat, void* stream) {
+  return laplace_entry(p, theta, y, mean, noise, side, f, maxit, tol, work, work_bytes, out, nullptr, stat, 0, 1,
+                       "dgp_laplace_batched_factorize", stream);
 }
 
 int dgp_debug_censored_terms(const double* z, int64_t count, double* out, void* stream) {
@@ -1297,27 +1350,59 @@ int dgp_debug_censored_terms(const double* z, int64_t count, double* out, void* 
   return wrap(debug_censored_terms(z, count, out, (hipStream_t)stream), "dgp_debug_censored_terms");
 }
 
+// u_dev / alpha_dev [B][n] -> dtheta_dev [B][ntheta]; B = 1: the single-site sweep
+static int debug_bilinear(dgp_plan* p, const double* theta, const void* u, const void* alpha, void* work, size_t work_bytes, double* dtheta,
+                          int batched, const char* where, void* stream) {
+  char msg[160];
+  if (!p) return fail(DGP_E_ARG, "null plan");
+  if (p->dtype != DGP_F64 || (!batched && p->B != 1)) {
+    snprintf(msg, sizeof(msg), batched ? "%s: needs a float64 plan" : "%s: needs a float64 single-site plan", where);
+    return fail(DGP_E_ARG, msg);
+  }
+  if (!theta || !u || !alpha || !dtheta) {
+    snprintf(msg, sizeof(msg), "%s: null argument", where);
+    return fail(DGP_E_ARG, msg);
+  }
+  DGP_CHECK_PLAN(p);
+  if (!p->have_inputs) {
+    snprintf(msg, sizeof(msg), "%s: call dgp_set_inputs first", where);
+    return fail(DGP_E_STATE, msg);
+  }
+  if (!work || work_bytes < (batched ? dgp_laplace_batched_workspace_bytes(p) : dgp_laplace_workspace_bytes(p))) {
+    snprintf(msg, sizeof(msg), "%s: workspace missing or too small", where);
+    return fail(DGP_E_WORKSPACE, msg);
+  }
+  if (((uintptr_t)work & 255) != 0) {
+    snprintf(msg, sizeof(msg), "%s: the work area must be 256-byte aligned", where);
+    return fail(DGP_E_ARG, msg);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int B = p->B;
+  const CensoredLayout L = censored_layout(p->N, p->n, B);
+  char* slices = (char*)work + L.slices;
+  double *up = (double*)(slices + L.u), *ap = (double*)(slices + L.w);
+  const size_t nb = sizeof(double) * (size_t)p->n;
+  hipError_t e = hipMemsetAsync(slices, 0, L.slice * (size_t)B, s);
+  if (e == hipSuccess) e = hipMemcpy2DAsync(up, L.slice, u, nb, nb, (size_t)B, hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess) e = hipMemcpy2DAsync(ap, L.slice, alpha, nb, nb, (size_t)B, hipMemcpyDeviceToDevice, s);
+  if (e != hipSuccess) return hipfail(e, where);
+  const long wss = (long)(L.slice / sizeof(double));
+  void* staging = p->pre ? p->ring.acquire(pre_scratch_bytes(B)) : nullptr;
+  const int rc = gram_bilinear<double>(p->model, p->d, (const double*)p->Xt, p->N, (int)p->n, theta, up, ap, (double*)(slices + L.gpart),
+                                       dtheta, 0, s, batch_of<double>(p), wss, wss, wss, p->ntheta, p->pre, true, staging);
+  if (staging) p->ring.commit(s);
+  p->pre_ready = 0;
+  return wrap(rc, where);
+}
+
 int dgp_debug_bilinear(dgp_plan* p, const double* theta, const void* u, const void* alpha, void* work, size_t work_bytes, double* dtheta,
                        void* stream) {
-  if (!p) return fail(DGP_E_ARG, "null plan");
-  if (p->dtype != DGP_F64 || p->B != 1) return fail(DGP_E_ARG, "dgp_debug_bilinear: needs a float64 single-site plan");
-  if (!theta || !u || !alpha || !dtheta) return fail(DGP_E_ARG, "dgp_debug_bilinear: null argument");
-  DGP_CHECK_PLAN(p);
-  if (!p->have_inputs) return fail(DGP_E_STATE, "dgp_debug_bilinear: call dgp_set_inputs first");
-  if (!work || work_bytes < dgp_laplace_workspace_bytes(p)) return fail(DGP_E_WORKSPACE, "dgp_debug_bilinear: workspace missing or too small");
-  if (((uintptr_t)work & 255) != 0) return fail(DGP_E_ARG, "dgp_debug_bilinear: the work area must be 256-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  const CensoredLayout L = censored_layout(p->N, p->n);
-  double *up = (double*)((char*)work + L.u), *ap = (double*)((char*)work + L.w);
-  const size_t nb = sizeof(double) * (size_t)p->n, Nb = sizeof(double) * (size_t)p->N;
-  hipError_t e = hipMemsetAsync(up, 0, Nb, s);
-  if (e == hipSuccess) e = hipMemsetAsync(ap, 0, Nb, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(up, u, nb, hipMemcpyDeviceToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(ap, alpha, nb, hipMemcpyDeviceToDevice, s);
-  if (e != hipSuccess) return hipfail(e, "dgp_debug_bilinear");
-  return wrap(gram_bilinear<double>(p->model, p->d, (const double*)p->Xt, p->N, (int)p->n, theta, up, ap,
-                                    (double*)((char*)work + L.gpart), dtheta, 0, s),
-              "dgp_debug_bilinear");
+  return debug_bilinear(p, theta, u, alpha, work, work_bytes, dtheta, 0, "dgp_debug_bilinear", stream);
+}
+
+int dgp_debug_bilinear_batched(dgp_plan* p, const double* theta, const void* u, const void* alpha, void* work, size_t work_bytes,
+                               double* dtheta, void* stream) {
+  return debug_bilinear(p, theta, u, alpha, work, work_bytes, dtheta, 1, "dgp_debug_bilinear_batched", stream);
 }
 
 size_t dgp_predict_workspace_bytes(const dgp_plan* p, int64_t m) {

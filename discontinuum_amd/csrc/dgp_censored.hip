@@ -1,6 +1,6 @@
 // dgp_censored.hip -- censored observations (non-detects): the Laplace approximation of a GP with a Tobit likelihood.
 //
-// Row i of a single-site fp64 plan is either observed (side 0: Gaussian, variance v_i) or censored at the limit l_i
+// Row i of a site of an fp64 plan (single-site or batched: blockIdx.z = site, ragged sizes through site_n) is either observed (side 0: Gaussian, variance v_i) or censored at the limit l_i
 // (side s_i = -1: the truth lies below it, +1: above):  log p_i = log Phi(z_i),  z_i = s_i (f_i - l_i) / sigma_i.
 // With h = phi(z) / Phi(z),
 //     g_i  =  d log p_i / d f_i     =  s_i h / sigma_i
@@ -13,11 +13,12 @@
 //   cen_terms_kernel    one elementwise pass: r~, n~, g, W, d3 and the per-row part of the NLL correction; block partials
 //   cen_search_kernel   the proposal f_new, max |f_new - f| and Psi(t) = sum log p_i(f(t)) - 1/2 a(t)^T (f(t) - m) on
 //                       t in {0, 1, 1/2, .., 1/64} in one pass (f and a are linear in t); block partials
-//   cen_*_finish        one workgroup, fixed order: no floating-point atomics anywhere, every result repeats bitwise
+//   cen_*_finish        one workgroup per site, fixed order: no floating-point atomics anywhere, every result repeats bitwise
 //   gram_bilinear       sum_ij u_i dK_ij/dtheta_p a_j for all p in one sweep over the lower triangle (sibling of
 //                       dgp_gram.hip::gram_grad_kernel: same tiling, staging and two-stage reduction; weights
 //                       u_i a_j + u_j a_i, the diagonal once) -- dK/dtheta is never stored
-// The non-destructive solve u = T^T (T w) is dgp_chol.hip::solve on buffers of the caller's work area.
+// The non-destructive solve u = T^T (T w) is dgp_chol.hip::solve_work: z, u and the partials in the caller's work area.
+// A batch runs Newton's iterations in lockstep (each factorises all sites); a site that has finished is frozen (CEN_ST_DONE).
 // Roofline: the elementwise passes are O(n) and latency-bound; the sweep is VALU-bound like gram_grad (one derivative pair
 // evaluation per entry of the triangle, nothing streamed from HBM but the two vectors).
 #include "dgp_gram_shared.h"
@@ -107,14 +108,31 @@ __device__ __forceinline__ void cen_total(const double* __restrict__ part, int n
   }
 }
 
+// ---- per-site control.  status: the site's CEN_ST_* block.  A site that finished in an earlier iteration than `it` (or has no
+// censored row) is frozen; the one that finishes in `it` still takes its step and has its terms evaluated at the mode.
+__device__ __forceinline__ bool cen_frozen(const double* __restrict__ status, int it) {
+  const double d = status[CEN_ST_DONE];
+  return d != 0.0 && d != (double)it;
+}
+
 // ---- terms at the current f.  y holds the observation (side 0) or the limit (side +-1).  Capped rows (W v < cap: the limit
 // says nothing) get n~ = v / cap and d3 = 0.  corr: the row's part of the NLL correction that does not involve alpha.
+// Every elementwise vector is [site][nfull]; `part` [site][nblk][CEN_PART]; status [site][CEN_ST_LEN].
 __global__ __launch_bounds__(256) void cen_terms_kernel(const double* __restrict__ f, const double* __restrict__ y,
                                                         const int* __restrict__ side, const double* __restrict__ v,
-                                                        const double* __restrict__ m, int n, double cap, double* __restrict__ rt,
-                                                        double* __restrict__ nn, double* __restrict__ g, double* __restrict__ W,
-                                                        double* __restrict__ d3, double* __restrict__ corr, double* __restrict__ logp,
-                                                        double* __restrict__ part) {
+                                                        const double* __restrict__ m, int n, const int* __restrict__ ns, double cap,
+                                                        double* __restrict__ rt, double* __restrict__ nn, double* __restrict__ g,
+                                                        double* __restrict__ W, double* __restrict__ d3, double* __restrict__ corr,
+                                                        double* __restrict__ logp, double* __restrict__ part,
+                                                        const double* __restrict__ status, int init, int it) {
+  status = site(status, (long)CEN_ST_LEN);
+  if (!init && (cen_frozen(status, it) || status[CEN_ST_INFO] != 0.0)) return;
+  const long nfull = n;
+  n = site_n(ns, n);
+  f = site(f, nfull); y = site(y, nfull); side = site(side, nfull); v = site(v, nfull); m = site(m, nfull);
+  rt = site(rt, nfull); nn = site(nn, nfull); g = site(g, nfull); W = site(W, nfull); d3 = site(d3, nfull);
+  corr = site(corr, nfull); logp = site(logp, nfull);
+  part = site(part, (long)gridDim.x * CEN_PART);
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   double acc[4] = {0.0, 0.0, 0.0, 0.0};  // correction, capped rows, bad side values, censored rows
   if (i < n) {
@@ -150,10 +168,16 @@ __global__ __launch_bounds__(256) void cen_terms_kernel(const double* __restrict
   }
   cen_block_reduce<4>(acc, -1, part);
 }
-__global__ __launch_bounds__(256) void cen_terms_finish_kernel(const double* __restrict__ part, int nblk, double* __restrict__ status) {
+__global__ __launch_bounds__(256) void cen_terms_finish_kernel(const double* __restrict__ part, int nblk, double* __restrict__ status,
+                                                               int init, int it) {
+  status = site(status, (long)CEN_ST_LEN);
+  if (!init && (cen_frozen(status, it) || status[CEN_ST_INFO] != 0.0)) return;
+  part = site(part, (long)nblk * CEN_PART);
   __shared__ double tot[CEN_PART];
   cen_total(part, nblk, 4, -1, tot);
   if (threadIdx.x < 4) status[CEN_ST_CORR + threadIdx.x] = tot[threadIdx.x];
+  if (init && threadIdx.x >= 4 && threadIdx.x < CEN_ST_LEN)
+    status[threadIdx.x] = (threadIdx.x == CEN_ST_DONE && tot[3] == 0.0) ? -1.0 : 0.0;
 }
 
 // ---- proposal and line search.  anew: the plan's alpha of the factorisation at (r~, n~); acur: the a of the current f (f - m =
@@ -161,9 +185,17 @@ __global__ __launch_bounds__(256) void cen_terms_finish_kernel(const double* __r
 __global__ __launch_bounds__(256) void cen_search_kernel(const double* __restrict__ f, const double* __restrict__ y,
                                                          const int* __restrict__ side, const double* __restrict__ v,
                                                          const double* __restrict__ m, const double* __restrict__ rt,
-                                                         const double* __restrict__ nn, const double* __restrict__ anew,
-                                                         const double* __restrict__ acur, int n, double* __restrict__ delta,
-                                                         double* __restrict__ part) {
+                                                         const double* __restrict__ nn, const double* __restrict__ anew, long as,
+                                                         const double* __restrict__ acur, int n, const int* __restrict__ ns,
+                                                         double* __restrict__ delta, double* __restrict__ part,
+                                                         const double* __restrict__ status) {
+  if (site(status, (long)CEN_ST_LEN)[CEN_ST_DONE] != 0.0) return;
+  const long nfull = n;
+  n = site_n(ns, n);
+  f = site(f, nfull); y = site(y, nfull); side = site(side, nfull); v = site(v, nfull); m = site(m, nfull);
+  rt = site(rt, nfull); nn = site(nn, nfull); acur = site(acur, nfull); delta = site(delta, nfull);
+  anew = site(anew, as);
+  part = site(part, (long)gridDim.x * CEN_PART);
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   double acc[CEN_NT + 1];
 #pragma unroll
@@ -191,50 +223,75 @@ __global__ __launch_bounds__(256) void cen_search_kernel(const double* __restric
   }
   cen_block_reduce<CEN_NT + 1>(acc, CEN_NT, part);
 }
-// chooses the step: the whole step when `first` or when it is below tol, else the largest t of the set that does not lower Psi
-// (slack: rounding of the sums).  status: max |delta|, t, halvings, the factorisation's info, Psi(0), Psi(t).
-__global__ __launch_bounds__(256) void cen_search_finish_kernel(const double* __restrict__ part, int nblk, int first, double tol,
+// chooses the step: the whole step in the first iteration or when it is below tol, else the largest t of the set that does not
+// lower Psi (slack: rounding of the sums).  status: max |delta|, t, halvings, the factorisation's info, Psi(0), Psi(t); the site is
+// done (CEN_ST_DONE = it) when the proposal is within tol or the factorisation failed.
+__global__ __launch_bounds__(256) void cen_search_finish_kernel(const double* __restrict__ part, int nblk, int it, double tol,
                                                                 const double* __restrict__ outblk, double* __restrict__ status) {
+  status = site(status, (long)CEN_ST_LEN);
+  if (status[CEN_ST_DONE] != 0.0) return;
+  part = site(part, (long)nblk * CEN_PART);
+  outblk = site(outblk, 32L);
   __shared__ double tot[CEN_PART];
   cen_total(part, nblk, CEN_NT + 1, CEN_NT, tot);
   if (threadIdx.x != 0) return;
   const double dmax = tot[CEN_NT], info = outblk[3];
   int j = 1;
-  if (!first && !(dmax <= tol)) {
+  if (it != 1 && !(dmax <= tol)) {
     const double floor_ = tot[0] - 1e-9 * (1.0 + fabs(tot[0]));
     while (j < CEN_NT - 1 && !(tot[j] >= floor_)) ++j;
   }
   double t = 1.0;
   for (int k = 1; k < j; ++k) t *= 0.5;
-  status[CEN_ST_DMAX] = (info == 0.0 && dmax == dmax) ? dmax : __builtin_inf();
+  const double dm = (info == 0.0 && dmax == dmax) ? dmax : __builtin_inf();
+  status[CEN_ST_DMAX] = dm;
   status[CEN_ST_T] = t;
   status[CEN_ST_HALVINGS] = (double)(j - 1);
   status[CEN_ST_INFO] = info;
   status[CEN_ST_PSI0] = tot[0];
   status[CEN_ST_PSI] = tot[j];
+  if (info != 0.0 || dm <= tol) status[CEN_ST_DONE] = (double)it;
 }
-// f <- f + t delta, acur <- acur + t (anew - acur); nothing moves when the factorisation failed
+// f <- f + t delta, acur <- acur + t (anew - acur); nothing moves when the factorisation failed or the site is frozen
 __global__ __launch_bounds__(256) void cen_update_kernel(double* __restrict__ f, const double* __restrict__ delta,
-                                                         double* __restrict__ acur, const double* __restrict__ anew,
-                                                         const double* __restrict__ status, int n) {
+                                                         double* __restrict__ acur, const double* __restrict__ anew, long as,
+                                                         const double* __restrict__ status, int n, const int* __restrict__ ns, int it) {
+  status = site(status, (long)CEN_ST_LEN);
+  const long nfull = n;
+  n = site_n(ns, n);
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n || status[CEN_ST_INFO] != 0.0) return;
+  if (i >= n || status[CEN_ST_INFO] != 0.0 || cen_frozen(status, it)) return;
+  f = site(f, nfull); delta = site(delta, nfull); acur = site(acur, nfull);
+  anew = site(anew, as);
   const double t = status[CEN_ST_T];
   f[i] = t == 1.0 ? f[i] + delta[i] : f[i] + t * delta[i];
   acur[i] = t == 1.0 ? anew[i] : acur[i] + t * (anew[i] - acur[i]);
 }
-// the mode of the system just solved: f = m + r~ - n~ o alpha (no censored row: the exact posterior mean at the samples)
+// the mode of the system just solved, for the sites without a censored row: f = m + r~ - n~ o alpha (the exact posterior mean at
+// the samples)
 __global__ __launch_bounds__(256) void cen_mode_kernel(double* __restrict__ f, const double* __restrict__ m,
                                                        const double* __restrict__ rt, const double* __restrict__ nn,
-                                                       const double* __restrict__ alpha, int n) {
+                                                       const double* __restrict__ alpha, long as, int n, const int* __restrict__ ns,
+                                                       const double* __restrict__ status) {
+  if (site(status, (long)CEN_ST_LEN)[CEN_ST_DONE] != -1.0) return;
+  const long nfull = n;
+  n = site_n(ns, n);
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) f[i] = m[i] + rt[i] - nn[i] * alpha[i];
+  if (i >= n) return;
+  f = site(f, nfull); m = site(m, nfull); rt = site(rt, nfull); nn = site(nn, nfull);
+  alpha = site(alpha, as);
+  f[i] = m[i] + rt[i] - nn[i] * alpha[i];
 }
 
 // ---- gradient.  (K^^-1)_ii = 2 dnoise_i + alpha_i^2;  Sigma_ii = n~_i - n~_i^2 (K^^-1)_ii;  t_i = -1/2 Sigma_ii d3_i;  w = n~ o t
 __global__ __launch_bounds__(256) void cen_weight_kernel(const double* __restrict__ nn, const double* __restrict__ d3,
-                                                         const double* __restrict__ dnoise, const double* __restrict__ alpha, int n,
-                                                         long N, double* __restrict__ w) {
+                                                         const double* __restrict__ dnoise, const double* __restrict__ alpha, long as,
+                                                         int n, const int* __restrict__ ns, long N, double* __restrict__ w, long ws) {
+  const long nfull = n;
+  n = site_n(ns, n);
+  nn = site(nn, nfull); d3 = site(d3, nfull); dnoise = site(dnoise, nfull);
+  alpha = site(alpha, as);
+  w = site(w, ws);
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= N) return;
   double wi = 0.0;
@@ -245,10 +302,18 @@ __global__ __launch_bounds__(256) void cen_weight_kernel(const double* __restric
   w[i] = wi;
 }
 // dr = alpha - u (u null: alpha) and the sums of the result row that depend on it; the NLL correction with its alpha part
-__global__ __launch_bounds__(256) void cen_result_kernel(const double* __restrict__ alpha, const double* __restrict__ u,
+__global__ __launch_bounds__(256) void cen_result_kernel(const double* __restrict__ alpha, long as, const double* __restrict__ u, long us,
                                                          const double* __restrict__ nn, const double* __restrict__ corr,
                                                          const int* __restrict__ side, const double* __restrict__ wts, int n,
-                                                         double* __restrict__ dr, double* __restrict__ part) {
+                                                         const int* __restrict__ ns, double* __restrict__ dr, double* __restrict__ part) {
+  const long nfull = n;
+  n = site_n(ns, n);
+  alpha = site(alpha, as);
+  if (u) u = site(u, us);
+  nn = site(nn, nfull); corr = site(corr, nfull); side = site(side, nfull);
+  if (wts) wts = site(wts, 2 * nfull);  // [site][2][n]
+  if (dr) dr = site(dr, nfull);
+  part = site(part, (long)gridDim.x * CEN_PART);
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   double acc[4] = {0.0, 0.0, 0.0, 0.0};  // correction, sum dr, sum dr w0, sum dr w1
   if (i < n) {
@@ -258,13 +323,18 @@ __global__ __launch_bounds__(256) void cen_result_kernel(const double* __restric
     acc[1] = d;
     if (wts) {
       acc[2] = d * wts[i];
-      acc[3] = d * wts[(long)n + i];
+      acc[3] = d * wts[nfull + i];
     }
+  } else if (i < nfull && dr) {
+    dr[i] = 0.0;  // the unused rows of a ragged site
   }
   cen_block_reduce<4>(acc, -1, part);
 }
 __global__ __launch_bounds__(256) void cen_result_finish_kernel(const double* __restrict__ part, int nblk, int with_grad,
                                                                 double* __restrict__ out, double* __restrict__ status) {
+  part = site(part, (long)nblk * CEN_PART);
+  out = site(out, 32L);
+  status = site(status, (long)CEN_ST_LEN);
   __shared__ double tot[CEN_PART];
   cen_total(part, nblk, 4, -1, tot);
   if (threadIdx.x != 0) return;
@@ -277,13 +347,14 @@ __global__ __launch_bounds__(256) void cen_result_finish_kernel(const double* __
   }
 }
 
-CensoredLayout censored_layout(long N, long n) {
+CensoredLayout censored_layout(long N, long n, int B) {
   CensoredLayout L;
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t vec = al(sizeof(double) * (size_t)N);
+  const size_t vec = al(sizeof(double) * (size_t)B * (size_t)n);
   size_t o = 0;
   L.rt = o; o += vec;
   L.nn = o; o += vec;
+  L.dnoise = o; o += vec;
   L.g = o; o += vec;
   L.W = o; o += vec;
   L.d3 = o; o += vec;
@@ -291,67 +362,86 @@ CensoredLayout censored_layout(long N, long n) {
   L.logp = o; o += vec;
   L.delta = o; o += vec;
   L.acur = o; o += vec;
-  L.w = o; o += vec;
-  L.u = o; o += vec;
-  L.z = o; o += vec;
-  L.dnoise = o; o += vec;
-  L.spart = o; o += al(sizeof(double) * (size_t)solve_partials(N));
-  L.gpart = o; o += al(sizeof(double) * (size_t)gram_grad_partials(N));
   L.nblk = (int)((n + 255) / 256);
-  L.part = o; o += al(sizeof(double) * (size_t)L.nblk * CEN_PART);
-  L.status = o; o += al(sizeof(double) * CEN_ST_LEN);
-  L.out = o; o += al(sizeof(double) * 32);
-  L.quad = o; o += al(sizeof(double) * 8);
-  L.total = o;
+  L.part = o; o += al(sizeof(double) * (size_t)B * (size_t)L.nblk * CEN_PART);
+  L.status = o; o += al(sizeof(double) * (size_t)B * CEN_ST_LEN);
+  L.out = o; o += al(sizeof(double) * (size_t)B * 32);
+  L.slices = o;
+  const size_t nvec = al(sizeof(double) * (size_t)N);
+  size_t q = 0;
+  L.w = q; q += nvec;
+  L.u = q; q += nvec;
+  L.z = q; q += nvec;
+  L.spart = q; q += al(sizeof(double) * (size_t)solve_partials(N));
+  L.gpart = q; q += al(sizeof(double) * (size_t)gram_grad_partials(N));
+  L.quad = q; q += al(sizeof(double) * 8);
+  L.slice = q;
+  L.total = o + q * (size_t)B;
+  L.B = B;
+  L.n = n;
   return L;
 }
 
-int censored_terms(const double* f, const double* y, const int* side, const double* v, const double* m, int n, char* work,
-                   const CensoredLayout& L, hipStream_t s) {
+int censored_terms(const double* f, const double* y, const int* side, const double* v, const double* m, int n, int init, int it,
+                   char* work, const CensoredLayout& L, hipStream_t s, Batch bt) {
   auto D = [&](size_t off) { return (double*)(work + off); };
-  cen_terms_kernel<<<dim3((unsigned)L.nblk), 256, 0, s>>>(f, y, side, v, m, n, CEN_CAP, D(L.rt), D(L.nn), D(L.g), D(L.W), D(L.d3),
-                                                          D(L.corr), D(L.logp), D(L.part));
-  cen_terms_finish_kernel<<<1, 256, 0, s>>>(D(L.part), L.nblk, D(L.status));
+  const unsigned Bz = (unsigned)bt.B;
+  cen_terms_kernel<<<dim3((unsigned)L.nblk, 1, Bz), 256, 0, s>>>(f, y, side, v, m, n, bt.ns, CEN_CAP, D(L.rt), D(L.nn), D(L.g), D(L.W),
+                                                                 D(L.d3), D(L.corr), D(L.logp), D(L.part), D(L.status), init, it);
+  cen_terms_finish_kernel<<<dim3(1, 1, Bz), 256, 0, s>>>(D(L.part), L.nblk, D(L.status), init, it);
   return (int)hipGetLastError();
 }
 
 int censored_newton_update(double* f, const double* y, const int* side, const double* v, const double* m, const double* anew, int n,
-                           int first, double tol, char* work, const CensoredLayout& L, hipStream_t s) {
+                           int it, double tol, char* work, const CensoredLayout& L, hipStream_t s, Batch bt) {
   auto D = [&](size_t off) { return (double*)(work + off); };
-  cen_search_kernel<<<dim3((unsigned)L.nblk), 256, 0, s>>>(f, y, side, v, m, D(L.rt), D(L.nn), anew, D(L.acur), n, D(L.delta),
-                                                           D(L.part));
-  cen_search_finish_kernel<<<1, 256, 0, s>>>(D(L.part), L.nblk, first, tol, D(L.out), D(L.status));
-  cen_update_kernel<<<dim3((unsigned)L.nblk), 256, 0, s>>>(f, D(L.delta), D(L.acur), anew, D(L.status), n);
+  const unsigned Bz = (unsigned)bt.B;
+  cen_search_kernel<<<dim3((unsigned)L.nblk, 1, Bz), 256, 0, s>>>(f, y, side, v, m, D(L.rt), D(L.nn), anew, bt.ws, D(L.acur), n, bt.ns,
+                                                                  D(L.delta), D(L.part), D(L.status));
+  cen_search_finish_kernel<<<dim3(1, 1, Bz), 256, 0, s>>>(D(L.part), L.nblk, it, tol, D(L.out), D(L.status));
+  cen_update_kernel<<<dim3((unsigned)L.nblk, 1, Bz), 256, 0, s>>>(f, D(L.delta), D(L.acur), anew, bt.ws, D(L.status), n, bt.ns, it);
   return (int)hipGetLastError();
 }
 
-int censored_mode(double* f, const double* m, const double* alpha, int n, char* work, const CensoredLayout& L, hipStream_t s) {
-  cen_mode_kernel<<<dim3((unsigned)L.nblk), 256, 0, s>>>(f, m, (const double*)(work + L.rt), (const double*)(work + L.nn), alpha, n);
+int censored_mode(double* f, const double* m, const double* alpha, int n, char* work, const CensoredLayout& L, hipStream_t s, Batch bt) {
+  cen_mode_kernel<<<dim3((unsigned)L.nblk, 1, (unsigned)bt.B), 256, 0, s>>>(f, m, (const double*)(work + L.rt),
+                                                                            (const double*)(work + L.nn), alpha, bt.ws, n, bt.ns,
+                                                                            (const double*)(work + L.status));
   return (int)hipGetLastError();
 }
 
-int censored_weights(const double* alpha, int n, long N, char* work, const CensoredLayout& L, hipStream_t s) {
+int censored_weights(const double* alpha, int n, long N, char* work, const CensoredLayout& L, hipStream_t s, Batch bt) {
   auto D = [&](size_t off) { return (double*)(work + off); };
-  cen_weight_kernel<<<dim3((unsigned)((N + 255) / 256)), 256, 0, s>>>(D(L.nn), D(L.d3), D(L.dnoise), alpha, n, N, D(L.w));
+  cen_weight_kernel<<<dim3((unsigned)((N + 255) / 256), 1, (unsigned)bt.B), 256, 0, s>>>(
+      D(L.nn), D(L.d3), D(L.dnoise), alpha, bt.ws, n, bt.ns, N, D(L.slices + L.w), (long)(L.slice / sizeof(double)));
   return (int)hipGetLastError();
 }
 
 int censored_result(const double* alpha, const int* side, const double* wts, int n, int with_grad, double* out, double* dr, char* work,
-                    const CensoredLayout& L, hipStream_t s) {
+                    const CensoredLayout& L, hipStream_t s, Batch bt) {
   auto D = [&](size_t off) { return (double*)(work + off); };
-  cen_result_kernel<<<dim3((unsigned)L.nblk), 256, 0, s>>>(alpha, with_grad ? D(L.u) : nullptr, D(L.nn), D(L.corr), side,
-                                                           with_grad ? wts : nullptr, n, with_grad ? dr : nullptr, D(L.part));
-  cen_result_finish_kernel<<<1, 256, 0, s>>>(D(L.part), L.nblk, with_grad, out, D(L.status));
+  const unsigned Bz = (unsigned)bt.B;
+  cen_result_kernel<<<dim3((unsigned)L.nblk, 1, Bz), 256, 0, s>>>(alpha, bt.ws, with_grad ? D(L.slices + L.u) : nullptr,
+                                                                  (long)(L.slice / sizeof(double)), D(L.nn), D(L.corr), side,
+                                                                  with_grad ? wts : nullptr, n, bt.ns, with_grad ? dr : nullptr, D(L.part));
+  cen_result_finish_kernel<<<dim3(1, 1, Bz), 256, 0, s>>>(D(L.part), L.nblk, with_grad, out, D(L.status));
   return (int)hipGetLastError();
 }
 
 // ---- the bilinear derivative sweep: partials[tile][p] = sum over the tile's entries (i >= j) of
-// (u_i a_j + u_j a_i) dK_ij/dtheta_p, the diagonal at half weight; summed by grad_reduce_kernel in fixed order.
+// (u_i a_j + u_j a_i) dK_ij/dtheta_p, the diagonal at half weight; summed by grad_reduce_kernel in fixed order.  Batched like
+// dgp_gram.hip::gram_grad_kernel: blockIdx.z = site, its hyperparameters from the PreBatch, u / alpha / partials at their strides.
 template <typename T, typename M>
 __global__ __launch_bounds__(256) void gram_bilinear_kernel(const T* __restrict__ Xt, long N, int n, const PreBatch<M> pb,
                                                             const T* __restrict__ u, const T* __restrict__ alpha,
-                                                            T* __restrict__ partials) {
+                                                            T* __restrict__ partials, long bs, const int* __restrict__ ns, long us,
+                                                            long as, long ps) {
+  n = site_n(ns, n);
   const typename M::Pre& pre = pb.get();
+  Xt = site(Xt, bs);
+  u = site(u, us);
+  alpha = site(alpha, as);
+  partials = site(partials, ps);
   __shared__ T sfi[M::NF][64], sfj[M::NF][64], sai[64], saj[64], sui[64], suj[64];
   __shared__ T red[4][M::NTHETA];
   int bi, bj;
@@ -405,18 +495,21 @@ __global__ __launch_bounds__(256) void gram_bilinear_kernel(const T* __restrict_
 
 template <typename T>
 int gram_bilinear(int model, int d, const T* Xt, long N, int n, const double* theta, const T* u, const T* alpha, T* partials,
-                  T* dtheta, int accumulate, hipStream_t s) {
+                  T* dtheta, int accumulate, hipStream_t s, Batch bt, long us, long as, long ps, long dstride, void* pre_scratch,
+                  bool upload, void* pre_staging) {
   const int nt = model_ntheta(model, d);
   if (nt < 0) return -2;
   const long nb = N / 64;
   const long nblk = nb * (nb + 1) / 2;
+  const unsigned Bz = (unsigned)bt.B;
   DGP_DISPATCH_MODEL(model, d,
-                     (gram_bilinear_kernel<T, M><<<dim3((unsigned)nblk), dim3(256), 0, s>>>(
-                         Xt, N, n, prepare_batch<M>(theta, nt, 1, nullptr, false, s, nullptr), u, alpha, partials)));
-  grad_reduce_kernel<T><<<dim3((unsigned)nt), dim3(256), 0, s>>>(partials, nblk, nt, dtheta, accumulate, 0, 0);
+                     (gram_bilinear_kernel<T, M><<<dim3((unsigned)nblk, 1, Bz), dim3(256), 0, s>>>(
+                         Xt, N, n, prepare_batch<M>(theta, nt, bt.B, pre_scratch, upload, s, pre_staging), u, alpha, partials, bt.ws,
+                         bt.ns, us, as, ps)));
+  grad_reduce_kernel<T><<<dim3((unsigned)nt, 1, Bz), dim3(256), 0, s>>>(partials, nblk, nt, dtheta, accumulate, ps, dstride);
   return (int)hipGetLastError();
 }
 template int gram_bilinear<double>(int, int, const double*, long, int, const double*, const double*, const double*, double*, double*,
-                                   int, hipStream_t);
+                                   int, hipStream_t, Batch, long, long, long, long, void*, bool, void*);
 
 }  // namespace dgp

@@ -1245,9 +1245,10 @@ int lauum(const T* Tm, long N, T* S, hipStream_t s, Batch bt) {
 // z_i = sum_{j <= i} T[i][j] r_j : one wave per row (coalesced along j)
 template <typename T>
 __global__ __launch_bounds__(256) void trmv_n_kernel(const T* __restrict__ Tm, long ld, const T* __restrict__ r, int n,
-                                                     T* __restrict__ z, long bs, const int* __restrict__ ns, long rs) {
+                                                     T* __restrict__ z, long bs, const int* __restrict__ ns, long rs,
+                                                     long zs = -1 /* site stride of z if it is not the workspace's */) {
   Tm = site(Tm, bs);
-  z = site(z, bs);
+  z = site(z, zs >= 0 ? zs : bs);
   r = site(r, rs);  // site stride of r: n for the caller's residuals, the scratch stride for the refinement's rho
   n = site_n(ns, n);
   const int lane = threadIdx.x & 63;
@@ -1267,10 +1268,10 @@ __global__ __launch_bounds__(256) void trmv_n_kernel(const T* __restrict__ Tm, l
 static inline int trmv_chunk(long N) { return N < 2048 ? 128 : DGP_TRMV_CHUNK; }
 template <typename T>
 __global__ __launch_bounds__(256) void trmv_t_kernel(const T* __restrict__ Tm, long ld, const T* __restrict__ z,
-                                                     T* __restrict__ partial, long bs, int chunk) {
+                                                     T* __restrict__ partial, long bs, int chunk, long zs = -1) {
   Tm = site(Tm, bs);
-  z = site(z, bs);
-  partial = site(partial, bs);
+  z = site(z, zs >= 0 ? zs : bs);
+  partial = site(partial, zs >= 0 ? zs : bs);
   __shared__ T red[4][64];
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   const long j = (long)blockIdx.x * 64 + tx;
@@ -1288,7 +1289,9 @@ __global__ __launch_bounds__(256) void trmv_t_kernel(const T* __restrict__ Tm, l
 template <typename T>
 __global__ __launch_bounds__(256) void trmv_t_reduce_kernel(const T* __restrict__ partial, long N, int nchunks,
                                                             T* __restrict__ alpha, long bs, int chunk,
-                                                            const T* __restrict__ z, T* __restrict__ quad, long as = -1) {
+                                                            const T* __restrict__ z, T* __restrict__ quad, long as = -1,
+                                                            long zs = -1 /* site stride of partial, z and quad (default bs) */) {
+  if (zs >= 0) bs = zs;
   if (blockIdx.x == gridDim.x - 1) {
     if (quad == nullptr) return;
     z = site(z, bs);
@@ -1401,6 +1404,19 @@ static void solve_pair(const T* Tm, long N, const T* r, long rs, int n, T* z, T*
 template <typename T>
 int solve(const T* Tm, long N, const T* r, int n, T* z, T* alpha, T* partials, T* quad, hipStream_t s, Batch bt) {
   solve_pair<T>(Tm, N, r, (long)n, n, z, alpha, -1, partials, quad, s, bt);
+  return (int)hipGetLastError();
+}
+// the same launches with r, z, the result, the partials and quad all in the caller's work area at ONE site stride `wss`: the
+// plan's own z and alpha are neither read nor written (dgp_censored.hip: u = T^T (T w) beside the fit step's alpha)
+template <typename T>
+int solve_work(const T* Tm, long N, const T* r, int n, T* z, T* out, T* partials, T* quad, long wss, hipStream_t s, Batch bt) {
+  const unsigned Bz = (unsigned)bt.B;
+  trmv_n_kernel<T><<<dim3((unsigned)(N / 4), 1, Bz), 256, 0, s>>>(Tm, N, r, n, z, bt.ws, bt.ns, wss, wss);
+  const int chunk = trmv_chunk(N), nchunks = (int)((N + chunk - 1) / chunk);
+  dim3 grid((unsigned)(N / 64), (unsigned)nchunks, Bz);
+  trmv_t_kernel<T><<<grid, 256, 0, s>>>(Tm, N, z, partials, bt.ws, chunk, wss);
+  trmv_t_reduce_kernel<T><<<dim3((unsigned)((N + 255) / 256) + 1, 1, Bz), 256, 0, s>>>(partials, N, nchunks, out, bt.ws, chunk, z, quad, wss,
+                                                                                      wss);
   return (int)hipGetLastError();
 }
 
@@ -1609,6 +1625,7 @@ int sample_draws(const T* L, long M, const T* Z, long Q, const T* mean, int m, i
   template int trtri<T>(const T*, const T*, long, T*, T*, hipStream_t, Batch, long);                                        \
   template int lauum<T>(const T*, long, T*, hipStream_t, Batch);                                                      \
   template int solve<T>(const T*, long, const T*, int, T*, T*, T*, T*, hipStream_t, Batch);                           \
+  template int solve_work<T>(const T*, long, const T*, int, T*, T*, T*, T*, long, hipStream_t, Batch);                \
   template int refine_solve<T>(const T*, long, const T*, int, const double*, const T*, T*, T*, T*, T*, T*, hipStream_t, Batch, long, long); \
   template int predict_v<T>(const T*, long, const T*, long, T*, hipStream_t, Batch, long);                                  \
   template int predict_var<T>(const T*, long, const T*, long, T*, const T*, const T*, T*, T*, T*, hipStream_t, Batch, long);

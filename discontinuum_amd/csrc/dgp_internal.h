@@ -191,6 +191,9 @@ int predict_var(const T* Tm, long N, const T* Ks, long M, T* V, const T* alpha, 
 // V = T Ks alone (Ks, V: N x M row-major in the caller's work area, M % 128 == 0): predict_var's first launch
 template <typename T>
 int predict_v(const T* Tm, long N, const T* Ks, long M, T* V, hipStream_t s, Batch bt = Batch(), long wbs = 0);
+// solve() with r, z, the result, the partials and quad in the caller's work area at one site stride wss: the plan's z / alpha untouched
+template <typename T>
+int solve_work(const T* Tm, long N, const T* r, int n, T* z, T* out, T* partials, T* quad, long wss, hipStream_t s, Batch bt = Batch());
 long solve_partials(long N);
 // ---- one matrix over several GPUs (dgp_dist.hip): the panel chain of W block columns on a slab-addressed matrix
 template <typename T>
@@ -396,8 +399,8 @@ int deletion_influence(const T* Tm, const T* S, const T* alpha, long N, int n, l
                        int* info, hipStream_t s, Batch bt);
 
 // ---- dgp_censored.hip: censored rows (Tobit likelihood) by the Laplace approximation -- a GP regression on pseudo-data (r~, n~).
-// Single-site fp64 plans.  The caller's work area is a CensoredLayout; `status` is the small block the host reads once per
-// Newton iteration.
+// fp64 plans, single-site or batched (blockIdx.z = site, ragged sizes through site_n).  The caller's work area is a
+// CensoredLayout; `status` holds one CEN_ST_* block per site, which the host reads in one copy per Newton iteration.
 #define CEN_PART 16    // doubles per workgroup of the block partials
 #define CEN_NT 8       // step lengths of the line search: 0, 1, 1/2, .. 1/64
 #define CEN_CAP 1e-12  // a censored row with W v below this is uninformative: n~ = v / CEN_CAP, d3 = 0
@@ -413,27 +416,45 @@ enum {
   CEN_ST_PSI0,
   CEN_ST_PSI,
   CEN_ST_NLL_CORR,   // the whole correction NLL_L - NLL_engine
+  CEN_ST_DONE,       // 0: the site's mode search is running; -1: it has no censored row (done before the first iteration);
+                     // k > 0: it finished in Newton iteration k (converged or not positive definite).  A site that finished in an
+                     // EARLIER iteration is frozen: cen_search, cen_update and cen_terms leave everything of it untouched
   CEN_ST_LEN = 16
 };
+// Byte offsets into the work area.  rt (r~), nn (n~) and dnoise are [B][n] at stride n, as fit_step<double> reads its caller
+// arrays, and so are the other elementwise vectors; w, u, z (N entries), the partials of the solve and of the sweep and quad form
+// one slice per site (`slice` bytes, the first at `slices`): ONE site stride for everything solve_work touches.
 struct CensoredLayout {
-  size_t rt, nn, g, W, d3, corr, logp, delta, acur, w, u, z, dnoise, spart, gpart, part, status, out, quad, total;  // byte offsets
-  int nblk;  // workgroups of the elementwise passes
+  size_t rt, nn, dnoise, g, W, d3, corr, logp, delta, acur, part, status, out, slices, total;
+  size_t w, u, z, spart, gpart, quad, slice;  // inside a site's slice
+  int nblk;  // workgroups per site of the elementwise passes
+  int B;
+  long n;
 };
-CensoredLayout censored_layout(long N, long n);
-// the terms at f: r~, n~, g, W, d3, per-row correction and log p into the work area, their sums into status[CEN_ST_CORR ..]
-int censored_terms(const double* f, const double* y, const int* side, const double* v, const double* m, int n, char* work,
-                   const CensoredLayout& L, hipStream_t s);
+CensoredLayout censored_layout(long N, long n, int B = 1);
+// the terms at f: r~, n~, g, W, d3, per-row correction and log p into the work area, their sums into status[CEN_ST_CORR ..];
+// init: the first pass of a call, which also sets every site's CEN_ST_DONE (0 or -1) and clears the search's fields;
+// otherwise `it` = the Newton iteration just taken (1-based): sites that finished before it, or failed in it, are skipped
+int censored_terms(const double* f, const double* y, const int* side, const double* v, const double* m, int n, int init, int it,
+                   char* work, const CensoredLayout& L, hipStream_t s, Batch bt = Batch());
 // after the factorisation at (r~, n~) left `anew` in the plan: proposal, line search, f and the work area's a updated in place
+// (Newton iteration `it`, 1-based; frozen sites untouched)
 int censored_newton_update(double* f, const double* y, const int* side, const double* v, const double* m, const double* anew, int n,
-                           int first, double tol, char* work, const CensoredLayout& L, hipStream_t s);
-int censored_mode(double* f, const double* m, const double* alpha, int n, char* work, const CensoredLayout& L, hipStream_t s);
-int censored_weights(const double* alpha, int n, long N, char* work, const CensoredLayout& L, hipStream_t s);  // w = n~ o t
+                           int it, double tol, char* work, const CensoredLayout& L, hipStream_t s, Batch bt = Batch());
+// f = m + r~ - n~ o alpha for the sites without a censored row
+int censored_mode(double* f, const double* m, const double* alpha, int n, char* work, const CensoredLayout& L, hipStream_t s,
+                  Batch bt = Batch());
+int censored_weights(const double* alpha, int n, long N, char* work, const CensoredLayout& L, hipStream_t s,
+                     Batch bt = Batch());  // w = n~ o t
 int censored_result(const double* alpha, const int* side, const double* wts, int n, int with_grad, double* out, double* dr, char* work,
-                    const CensoredLayout& L, hipStream_t s);
-// dtheta[p] (+)= sum_ij u_i dK_ij/dtheta_p alpha_j; partials: gram_grad_partials(N) elements.  Reads Xt, u, alpha only.
+                    const CensoredLayout& L, hipStream_t s, Batch bt = Batch());
+// dtheta[p] (+)= sum_ij u_i dK_ij/dtheta_p alpha_j per site (dtheta at site stride dstride); u, alpha and the partials
+// (gram_grad_partials(N) elements) at the site strides us / as / ps.  pre_scratch / upload / staging as for gram_grad (a batch of
+// more than 8).  Reads Xt, u, alpha only.
 template <typename T>
 int gram_bilinear(int model, int d, const T* Xt, long N, int n, const double* theta, const T* u, const T* alpha, T* partials,
-                  T* dtheta, int accumulate, hipStream_t s);
+                  T* dtheta, int accumulate, hipStream_t s, Batch bt = Batch(), long us = 0, long as = 0, long ps = 0, long dstride = 0,
+                  void* pre_scratch = nullptr, bool upload = false, void* pre_staging = nullptr);
 // out [4][count]: log Phi(z), h = phi / Phi, h (z + h), h [1 - (z + h)(z + 2 h)]
 int debug_censored_terms(const double* z, long count, double* out, hipStream_t s);
 

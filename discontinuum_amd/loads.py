@@ -241,7 +241,9 @@ def aggregate_many(models, covariates_list, weights_list, freq="YE", ci=0.95, pr
     batches whose device footprint -- B x (M^2 + 2 N M + 3 N^2) elements for the covariances, the cross terms and the
     plan -- stays under ``max_bytes`` (default 16 GiB; one site at m = 11 323 already needs 1 GB for its covariance).
     Sites whose dense footprint alone exceeds ``max_bytes`` take the streamed ``dgp_posterior_period_moments`` instead,
-    in batches of their own cut by the streamed footprint (``_streamed_bytes``: nothing of order M^2)."""
+    in batches of their own cut by the streamed footprint (``_streamed_bytes``: nothing of order M^2).  A batch in which a
+    model carries censoring (``fit(censored=)`` / ``fit_many(censored=)``) builds its cache with the batched
+    ``laplace_factorize`` (``multisite_fit.censored_cache_build``): the Laplace posterior, not the limits taken for samples."""
     from .backend import GPPlan
     from . import _lib
 
@@ -310,7 +312,13 @@ def aggregate_many(models, covariates_list, weights_list, freq="YE", ci=0.95, pr
         one = (lambda v: v[0].contiguous()) if single else (lambda v: v)
         with torch.no_grad():
             plan.set_inputs(one(X))
-            out = plan.factorize(one(theta), one(R), one(Nz))
+            if any(getattr(models[b], "_censor", None) is not None for b in idx):  # the Laplace posterior, not the limits as samples
+                from .multisite_fit import censored_cache_build
+
+                out = censored_cache_build(plan, [models[b] for b in idx], theta, [st["y"] for st in group],
+                                           [st["prior"] for st in group], [st["noise"] for st in group], sizes, n)
+            else:
+                out = plan.factorize(one(theta), one(R), one(Nz))
             info = out.reshape(B, -1)[:, _lib.OUT_INFO].cpu()
             if bool((info != 0).any()):
                 bad = int(torch.nonzero(info)[0])

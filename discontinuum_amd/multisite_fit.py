@@ -22,6 +22,8 @@ Early stopping is per site; the rating-gp monotonicity penalty (``monotonic_pena
 site's posterior mean at its own random grid through ONE batched ``dgp_predict_mean`` / ``dgp_mean_vjp`` per iteration;
 ``return_state=True`` / ``resume=state`` continue a run where it stopped (optimiser moments, schedules, counters);
 ``penalty_callback`` / ``penalty_weight`` add the reference's generic penalty term per site (``:362-373``).
+``censored=[mask or None per site]`` trains sites with non-detects: the device step becomes ONE batched Laplace fit step
+(``dgp_laplace_batched_fit_step``; loadest-gp, fixed noise, float64), and ``predict_many`` builds the Laplace cache for such models.
 
 Across the GPUs of a node: ``fit_many_distributed`` -- site i trains on rank i mod G (``sites.site_partition``), every rank
 runs ``fit_many`` on its share on its own GPU, and ONE collective at the end of the fit (an ``all_gather`` of the fitted raw
@@ -95,6 +97,60 @@ class _BatchedNLL(torch.autograd.Function):
         dtheta, dextras = ctx.saved_tensors
         g = torch.nan_to_num(g, nan=0.0)[:, None]
         return None, (dtheta * g).to(ctx.dtypes[0]), None, None, (dextras * g).to(ctx.dtypes[1]), None
+
+
+class _BatchedCensor:
+    """The censoring of a batch: ``side`` (B, n) device int32 (0 in the unused slots), the latest modes ``f`` (B, n) of the
+    Laplace approximation (None = cold start from the prior means) and the per-site ``status`` of the last mode search."""
+
+    def __init__(self, side, maxit, tol):
+        self.side, self.f, self.status, self.maxit, self.tol = side, None, None, int(maxit), float(tol)
+
+
+def _laplace_step(plan, theta, y, mean, noise, state):
+    """One batched ``laplace_fit_step`` from the previous iteration's modes -> result rows (B, OUT_LEN) on the device.  A site
+    whose factorisation failed starts cold the next time; ``E_NOCONV`` becomes a ``RuntimeError`` naming the site, as the single
+    engine's fit raises."""
+    one = plan.batch == 1
+    pick = (lambda v: v[0].contiguous()) if one else (lambda v: v)
+    mean = mean.contiguous()
+    warm = mean if state.f is None else state.f
+    try:
+        out, _dr, f_hat, stat = plan.laplace_fit_step(pick(theta), pick(y), pick(mean), pick(noise), pick(state.side), f=pick(warm),
+                                                      maxit=state.maxit, tol=state.tol)
+    except _lib.DGPError as e:
+        if e.code != _lib.E_NOCONV:
+            raise
+        stat = (plan.laplace_stat,) if one else plan.laplace_stat
+        bad = next((b for b, st in enumerate(stat) if st[0] >= state.maxit and not st[1] <= state.tol), 0)
+        raise RuntimeError(f"site {bad}: the mode search of the censored fit did not converge in {state.maxit} Newton "
+                           f"iterations (max |df| = {stat[bad][1]:.3g})") from e
+    out, f_hat = out.reshape(theta.shape[0], -1), f_hat.reshape(mean.shape)
+    failed = (out[:, _lib.OUT_INFO] != 0) | ~torch.isfinite(out[:, _lib.OUT_NLL])
+    state.f = torch.where(failed[:, None], mean, f_hat)
+    state.status = (tuple(stat),) if one else tuple(stat)
+    return out
+
+
+class _BatchedLaplaceNLL(torch.autograd.Function):
+    """``_BatchedNLL`` for a batch with censored rows: the data terms of B sites from one batched ``dgp_laplace_batched_fit_step``
+    (``state``: a ``_BatchedCensor``; each site's mode search starts from its previous mode).  ``OUT_SUM_DR`` of a row is already the
+    sum of the Laplace dr = alpha - u, so the mean parameters' gradients are read off the row as before (d NLL / d mean = -dr);
+    the noise gets no gradient (fixed noise by construction)."""
+
+    @staticmethod
+    def forward(ctx, plan, theta, y, mean, noise, extras, family, state):
+        host = _laplace_step(plan, theta.detach(), y, mean, noise, state).to("cpu", torch.float64)
+        _ok, nll, dtheta, dextras = _row_terms(host, plan.ntheta, family, None)
+        ctx.save_for_backward(dtheta, dextras)
+        ctx.dtypes = (theta.dtype, extras.dtype)
+        return nll
+
+    @staticmethod
+    def backward(ctx, g):
+        dtheta, dextras = ctx.saved_tensors
+        g = torch.nan_to_num(g, nan=0.0)[:, None]
+        return None, (dtheta * g).to(ctx.dtypes[0]), None, None, None, (dextras * g).to(ctx.dtypes[1]), None, None
 
 
 class _BatchedGPMean(torch.autograd.Function):
@@ -412,13 +468,33 @@ def _per_site_clip(raw_grads: dict, B: int, max_norm: float = 1.0):
 
 
 def _refuse_censored_records(datasets, what):
-    """A record may carry a fourth entry, the ``censored`` argument of ``MarginalHIP.fit``: batched plans have no Laplace
-    mode search, so a record with a censored row is refused (train that site with its own ``fit(censored=...)``)."""
+    """A record with a fourth entry (the ``censored`` argument of ``MarginalHIP.fit``) that has a censored row is refused: the
+    censoring of a batch goes through the ``censored=`` argument, one entry per site."""
     for record in datasets:
         record = tuple(record)
         if len(record) > 3 and record[3] is not None and np.asarray(getattr(record[3], "values", record[3])).any():
-            raise NotImplementedError(f"{what} does not support censored observations (batched plans have no Laplace mode "
-                                      "search): fit that site with its own fit(censored=...)")
+            raise NotImplementedError(f"{what} does not read censored observations from a record's fourth entry: pass them "
+                                      "through the censored= argument (one entry per site)")
+
+
+def _site_sides(models, censored, sizes, what):
+    """``censored`` (None, or one entry per site: None, a boolean mask, or -1 / 0 / +1) as a list of int32 side vectors / None,
+    through ``engines.hip.censor_sides``; refuses what the censored fit does not serve."""
+    from .engines.hip import censor_sides
+
+    if censored is None:
+        return [None] * len(models)
+    if len(censored) != len(models):
+        raise ValueError(f"{what}: censored needs one entry per site (None for a site without censored rows)")
+    sides = [censor_sides(c, nb) for c, nb in zip(censored, sizes)]
+    if any(sd is not None for sd in sides):
+        for m in models:
+            if hasattr(m.model, "powerlaw") or getattr(m.likelihood, "second_noise_covar", None) is not None:
+                raise NotImplementedError(f"{what}: censored observations need loadest-gp with a fixed-noise likelihood: the "
+                                          "Laplace fit produces no gradient for a learned noise term (rating-gp is not supported)")
+            if m.dtype != torch.float64:
+                raise NotImplementedError(f"{what}: censored observations need float64 models (fp32 plans have no Laplace fit)")
+    return sides
 
 
 def fit_many(models, datasets, iterations: int = 100, learning_rate: float = 0.05, patience: int = 60,
@@ -426,7 +502,7 @@ def fit_many(models, datasets, iterations: int = 100, learning_rate: float = 0.0
              monotonic_penalty_weight: float = 0.0, grid_size: int = 64, monotonic_penalty_interval: int = 1,
              resume: FitManyState | None = None, return_state: bool = False, generator: torch.Generator | None = None,
              optimizer: str = "adam", penalty_callback=None, penalty_weight: float = 0.0, site_seeds=None,
-             closed_form: bool = True, _penalty_uniforms=None):
+             closed_form: bool = True, censored=None, _penalty_uniforms=None):
     """Fit ``models[i]`` to ``datasets[i] = (covariates, target[, target_unc])`` for all i at once.  Returns the
     per-site final objectives (a float64 tensor) -- with ``return_state=True`` the pair (objectives, ``FitManyState``);
     the models are updated in place (``is_fitted``, parameters, device state).
@@ -456,7 +532,19 @@ def fit_many(models, datasets, iterations: int = 100, learning_rate: float = 0.0
     ``site_seeds`` (one int per site): site b's model is built under ``torch.manual_seed(site_seeds[b])`` (inside a forked
     RNG scope) -- the rating-gp power law and gate start from random draws like the reference's
     (src/rating_gp/models/gpytorch.py:30-33, kernels.py:276), so without seeds a site's trajectory depends on how many
-    sites were built before it; with them it depends on the site alone (``fit_many_distributed`` relies on that)."""
+    sites were built before it; with them it depends on the site alone (``fit_many_distributed`` relies on that).
+
+    ``censored``: a sequence with one entry per site -- None, a boolean mask aligned with that site's target (True = the
+    reported value is a detection limit and the truth lies below it) or -1 / 0 / +1, as ``MarginalHIP.fit(censored=...)``.  With a
+    censored row anywhere the device step of an iteration is ONE batched ``dgp_laplace_batched_fit_step`` (Newton's mode searches
+    of all sites in lockstep, each warm-started from its previous mode; uncensored sites ride along) in both host paths; a site
+    whose matrix is not positive definite follows the non-finite-objective policy, a mode search that does not converge raises
+    ``RuntimeError`` naming the site.  Afterwards every model carries its censoring (``_set_censoring``) and its last
+    ``laplace_status_``, so its own ``predict`` / ``annual_flux`` / ... see the Laplace posterior, as after ``fit(censored=)``.
+    loadest-gp, fixed noise, float64 only (``NotImplementedError`` otherwise).  None, or no censored row: the plain path, bit for
+    bit.  ``resume`` cold-starts the modes (``FitManyState`` does not carry them): the mode is a function of the
+    hyperparameters and the warm start only saves Newton iterations, so a resumed censored run equals the uninterrupted one to
+    the mode tolerance, not bitwise."""
     if site_seeds is not None and len(site_seeds) != len(models):
         raise ValueError("site_seeds needs one seed per model")
     _refuse_censored_records(datasets, "fit_many")
@@ -489,9 +577,17 @@ def fit_many(models, datasets, iterations: int = 100, learning_rate: float = 0.0
                                       "train this model with its own fit()")
     sizes = [x.shape[0] for x in xs]
     n = max(sizes)
+    sides = _site_sides(models, censored, sizes, "fit_many")
     plan = GPPlan(hosts[0].name, n, d, dtype=dtype, device=device, lookahead=1 if B > 1 else 2, batch=B)
     if B > 1:
         plan.set_site_sizes(sizes)
+    cstate = None
+    if any(sd is not None for sd in sides):
+        side_all = torch.zeros((B, n), dtype=torch.int32)
+        for b, sd in enumerate(sides):
+            if sd is not None:
+                side_all[b, : sizes[b]] = torch.as_tensor(sd, dtype=torch.int32)
+        cstate = _BatchedCensor(side_all.to(device).contiguous(), models[0].laplace_maxit, models[0].laplace_tol)
 
     def slots(ts):
         out = torch.zeros((B, n) + tuple(ts[0].shape[1:]), dtype=dtype)
@@ -633,12 +729,13 @@ def fit_many(models, datasets, iterations: int = 100, learning_rate: float = 0.0
                 x, slope = cf.transform(flat.numpy())
                 theta, extras = torch.from_numpy(x[:, cf.theta_src]), torch.from_numpy(x[:, cf.extras_src])
                 mean, noise = mean_and_noise(extras)
-                r = (Y - mean).contiguous()
                 noise = noise.contiguous()
-                if plan.batch == 1:
-                    out = plan.fit_step(theta[0], r[0].contiguous(), noise[0].contiguous())[0].reshape(1, -1)
+                if cstate is not None:
+                    out = _laplace_step(plan, theta, Y, mean, noise, cstate)
+                elif plan.batch == 1:
+                    out = plan.fit_step(theta[0], (Y - mean)[0].contiguous(), noise[0].contiguous())[0].reshape(1, -1)
                 else:
-                    out = plan.fit_step(theta, r, noise)[0]
+                    out = plan.fit_step(theta, (Y - mean).contiguous(), noise)[0]
                 lp_np, dlp = cf.log_prior(x)  # the host's share runs under the device step
                 _ok_row, nll, dtheta, dextras = _row_terms(out.to("cpu", torch.float64), plan.ntheta, family,
                                                           extras[:, 1] if family == "rating" else None)
@@ -653,9 +750,11 @@ def fit_many(models, datasets, iterations: int = 100, learning_rate: float = 0.0
                         pc.copy_(torch.minimum(pc, stage_floor.reshape(pc.shape)))
                 theta, lp, extras = host_all(params, buffers)
                 mean, noise = mean_and_noise(extras)
-                r = (Y - mean).contiguous()
                 noise = noise.contiguous()
-                nll = _BatchedNLL.apply(plan, theta, r, noise, extras, family)
+                if cstate is not None:
+                    nll = _BatchedLaplaceNLL.apply(plan, theta, Y, mean, noise, extras, family, cstate)
+                else:
+                    nll = _BatchedNLL.apply(plan, theta, (Y - mean).contiguous(), noise, extras, family)
                 obj = (nll - lp) / nvec
             if use_penalty and (it + 1) % interval == 0:
                 # posterior mean of every site on its grid = GP part (device, batched, differentiable through
@@ -747,6 +846,8 @@ def fit_many(models, datasets, iterations: int = 100, learning_rate: float = 0.0
     # ---- hand the fitted parameters back to the per-site models
     for b, (m, own) in enumerate(zip(models, own_params)):
         _hand_back(m, own, {k: v[b] for k, v in params.items()}, int(last_iteration[b]), xs[b], ys[b])
+        if censored is not None:
+            _hand_back_censoring(m, sides[b], sizes[b], cstate, b)
     if return_state:
         state = FitManyState(params={k: v.detach().clone() for k, v in params.items()}, m1=m1, m2=m2, step=step, lr=lr, best=best,
                              num_bad=num_bad, cooldown=cooldown, es_best=es_best, stale=stale, live=live, last_obj=last_obj,
@@ -780,11 +881,20 @@ def _hand_back(m, own, values, last_iteration, tx, ty):
     m.is_fitted = True
 
 
+def _hand_back_censoring(m, side, nb, cstate, b):
+    """The site's censoring onto its model, as ``fit(censored=)`` leaves it: the side vector, and -- from a batch's state -- the
+    last mode (the warm start of the model's own cache build) and the last mode search's status."""
+    m._set_censoring(side, nb)
+    if m._censor is not None and cstate is not None and cstate.f is not None:
+        m._censor.update(cstate.f[b, :nb].clone(), cstate.status[b])
+        m.laplace_status_ = m._censor.status
+
+
 # stop reasons in the gathered table of fit_many_distributed
 STOP_BUDGET, STOP_EARLY, STOP_FAILED = 0.0, 1.0, 2.0
 
 
-def fit_many_distributed(models, datasets, group=None, load: str = "all", seed: int | None = 0, **kw):
+def fit_many_distributed(models, datasets, group=None, load: str = "all", seed: int | None = 0, censored=None, **kw):
     """``fit_many`` over the ranks of a ``torch.distributed`` process group (one rank per GPU).
 
     Every rank passes the SAME ``models`` / ``datasets`` lists (like the reference's ``iterdata`` list,
@@ -807,6 +917,9 @@ def fit_many_distributed(models, datasets, group=None, load: str = "all", seed: 
     ``site_seeds``), so the result of a site does not depend on the number of ranks or on which rank trained it -- a
     single-process ``fit_many(..., site_seeds=[seed + i ...])`` gives the same bits.
 
+    ``censored``: as in ``fit_many``, one entry per site of the WHOLE list; it is sliced by ``site_partition`` like the datasets,
+    and a rank that loads a site it does not own also sets that site's censoring on its model.  The gathered table is unchanged.
+
     Without an initialised process group (or world 1) this is ``fit_many`` plus the table.  ``resume`` / ``return_state``
     are per-rank notions and not supported here.  Returns ``(objectives (n_sites,), table (n_sites, P_raw + 3))``, float64,
     identical on every rank."""
@@ -821,6 +934,8 @@ def fit_many_distributed(models, datasets, group=None, load: str = "all", seed: 
         raise ValueError("fit_many_distributed: resume / return_state are per-rank; use fit_many on each rank's share")
     if len(models) != len(datasets) or not models:
         raise ValueError("fit_many_distributed needs one (covariates, target) pair per model")
+    if censored is not None and len(censored) != len(models):
+        raise ValueError("fit_many_distributed: censored needs one entry per site (None for a site without censored rows)")
     n_sites = len(models)
     active = dist.is_available() and dist.is_initialized()
     world = dist.get_world_size(group) if active else 1
@@ -832,7 +947,8 @@ def fit_many_distributed(models, datasets, group=None, load: str = "all", seed: 
     if mine:
         try:
             objs, state = fit_many([models[i] for i in mine], [datasets[i] for i in mine], return_state=True,
-                                   site_seeds=None if seed is None else [seed + i for i in mine], **kw)
+                                   site_seeds=None if seed is None else [seed + i for i in mine],
+                                   censored=None if censored is None else [censored[i] for i in mine], **kw)
         except Exception as e:  # noqa: BLE001 -- reported after the collective, on every rank
             error = e
 
@@ -889,7 +1005,39 @@ def fit_many_distributed(models, datasets, group=None, load: str = "all", seed: 
                 values[k] = table[i, o:o + w].to(own[k].dtype)
                 o += w
             _hand_back(models[i], own, values, int(table[i, P + 1]) - 1, tx, ty)
+            if censored is not None:
+                _hand_back_censoring(models[i], _site_sides([models[i]], [censored[i]], [tx.shape[0]], "fit_many_distributed")[0],
+                                     tx.shape[0], None, 0)
     return table[:, P].clone(), table
+
+
+def censored_cache_build(plan, models, theta, ys, means, noises, sizes, n):
+    """The batched cache build of sites of which some carry censoring (``_censor``): ONE ``laplace_factorize`` on the batched
+    plan -- uncensored sites ride along with side 0, a model's last mode is its warm start -- instead of ``factorize`` on y - mean,
+    which would take the detection limits for samples.  -> the result rows (B, OUT_LEN); the models' modes and statuses are
+    updated.  ``ys`` / ``means`` / ``noises``: per-site host vectors."""
+    B, dtype, device = len(models), plan.dtype, plan.device
+
+    def slots(ts, fill=0.0, dt=dtype):
+        out = torch.full((B, n), fill, dtype=dt)
+        for b, t in enumerate(ts):
+            out[b, : t.shape[0]] = torch.as_tensor(t, dtype=dt).cpu()
+        return out.to(device).contiguous()
+
+    cens = [getattr(m, "_censor", None) for m in models]
+    side = slots([torch.zeros(nb, dtype=torch.int32) if c is None else c.side for c, nb in zip(cens, sizes)], 0, torch.int32)
+    mean = slots(means)
+    start = slots([mu if c is None or c.f is None else c.f for c, mu in zip(cens, means)])
+    first = next(c for c in cens if c is not None)
+    one = (lambda v: v[0].contiguous()) if B == 1 else (lambda v: v)
+    out, f_hat, stat = plan.laplace_factorize(one(theta), one(slots(ys)), one(mean), one(slots(noises, 1.0)), one(side), f=one(start),
+                                              maxit=first.maxit, tol=first.tol)
+    f_hat, stat = f_hat.reshape(B, n), ((tuple(stat),) if B == 1 else stat)
+    for b, (m, c) in enumerate(zip(models, cens)):
+        if c is not None:
+            c.update(f_hat[b, : sizes[b]].clone(), stat[b])
+            m.laplace_status_ = c.status
+    return out.reshape(B, -1)
 
 
 def predict_many(models, covariates_list):
@@ -898,7 +1046,8 @@ def predict_many(models, covariates_list):
     factorisation and a prediction per site (the reference fans predictions out per site / per date:
     ``examples/nwqn-loadest-example/nwqn-loadest-example.py:38-125``, ``src/rating_gp/plot.py:259-285``).
     Returns ``[(target, se), ...]`` in the original data space, like ``MarginalHIP.predict``.  Sites may differ in the
-    number of observations and of prediction points (ragged batch; shorter sites are padded)."""
+    number of observations and of prediction points (ragged batch; shorter sites are padded).  When a model carries censoring
+    (``fit(censored=)`` / ``fit_many(censored=)``) the batched cache build is ``laplace_factorize`` (``censored_cache_build``)."""
     if len(models) != len(covariates_list) or not models:
         raise ValueError("predict_many needs one covariates object per model")
     for m in models:
@@ -946,7 +1095,10 @@ def predict_many(models, covariates_list):
     theta = torch.stack(thetas)
     single = B == 1
     plan.set_inputs(X[0].contiguous() if single else X)
-    out = plan.factorize(theta[0] if single else theta, R[0].contiguous() if single else R, Nz[0].contiguous() if single else Nz)
+    if any(getattr(m, "_censor", None) is not None for m in models):
+        out = censored_cache_build(plan, models, theta, ys, means, noises, sizes, n)
+    else:
+        out = plan.factorize(theta[0] if single else theta, R[0].contiguous() if single else R, Nz[0].contiguous() if single else Nz)
     info = out.reshape(B, -1)[:, _lib.OUT_INFO].cpu()
     if bool((info != 0).any()):
         bad = int(torch.nonzero(info)[0])
@@ -979,6 +1131,8 @@ def hyperparameter_uncertainty_many(models, ci=0.95, prior=True, max_bytes=None)
     for m in models:
         if not m.is_fitted:
             raise RuntimeError("The model hasn't been fitted yet, call .fit().")
+        if hasattr(m, "_refuse_censored"):
+            m._refuse_censored("hyperparameter_uncertainty_many")
     B = len(models)
     dtype, device = models[0].dtype, torch.device(models[0].device)
     sites, names = [], set()

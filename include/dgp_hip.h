@@ -250,6 +250,30 @@ int dgp_laplace_fit_step(dgp_plan* plan, const double* theta_host, const void* y
 int dgp_laplace_factorize(dgp_plan* plan, const double* theta_host, const void* y_dev, const void* mean_dev, const void* noise_dev,
                           const int32_t* side_dev, void* f_dev, int maxit, double tol, void* work_dev, size_t work_bytes,
                           void* out_dev, double* stat_host, void* stream);
+/* The same for EVERY plan of float64, batched and ragged ones included (gridDim.z = sites).  Arrays are batch-major: theta_host
+ * [B][ntheta], y / mean / noise / f / dr [B][n], side int32 [B][n], out [B][DGP_OUT_LEN], stat_host [B][4] = per site (its Newton
+ * iterations, its final max |f_new - f|, its halvings, its capped rows).  Rows >= sizes[b] of a ragged site are ignored in every
+ * input (side values there may be anything) and its f tail is left untouched.
+ * Newton's iterations run in LOCKSTEP: each one factorises all B sites.  A site is done when it has no censored row (before the
+ * first iteration), when its proposal satisfied max |f_new - f| <= tol, or when its factorisation failed; a done site is FROZEN on
+ * the device -- its f, its a, its pseudo-data (r~, n~) and its status are left untouched -- so it rides through the remaining
+ * factorisations on unchanged pseudo-data and its mode, iteration count and halvings are its own, whatever its batch-mates need.
+ * The host reads all B status blocks in one copy per iteration and stops when every site is done or at maxit.  Then ONE
+ * dgp_fit_step pass at the modes, u = T^T (T w) per site in the work area (the plan's z / alpha untouched), the pair sweep
+ * (hyperparameters by value up to 8 sites, through the plan's scratch above) and the result pass.  No floating-point atomics.
+ * Return: 0; DGP_E_ARG for a side value outside -1 / 0 / +1 (the text names the first such site); DGP_E_NOCONV when a censored
+ * site is not done after maxit (all results filled, stat_host says which sites, the text names the first); DGP_E_WORKSPACE /
+ * DGP_E_STATE / DGP_E_ARG before any launch as above (fp32 plans are refused).  A site whose matrix is not positive definite
+ * reports that in its own out[DGP_OUT_INFO]: the return code stays 0 and the other sites are unaffected.
+ * On a plan of one site these entries return bitwise what dgp_laplace_* return; with no censored row in any site they launch
+ * exactly what dgp_fit_step / dgp_factorize launch on (y - m, v) and set every f = m + r - v o alpha. */
+size_t dgp_laplace_batched_workspace_bytes(const dgp_plan* plan); /* 0 for null / fp32 */
+int dgp_laplace_batched_fit_step(dgp_plan* plan, const double* theta_host, const void* y_dev, const void* mean_dev,
+                                 const void* noise_dev, const int32_t* side_dev, void* f_dev, int maxit, double tol, void* work_dev,
+                                 size_t work_bytes, void* out_dev, void* dr_dev, double* stat_host, void* stream);
+int dgp_laplace_batched_factorize(dgp_plan* plan, const double* theta_host, const void* y_dev, const void* mean_dev,
+                                  const void* noise_dev, const int32_t* side_dev, void* f_dev, int maxit, double tol, void* work_dev,
+                                  size_t work_bytes, void* out_dev, double* stat_host, void* stream);
 /* out [4][count] = log Phi(z), h = phi(z) / Phi(z), h (z + h), h [1 - (z + h)(z + 2 h)]: the pointwise functions of the
  * entries above, for tests.  z_dev: count doubles on the device. */
 int dgp_debug_censored_terms(const double* z_dev, int64_t count, double* out_dev, void* stream);
@@ -257,6 +281,11 @@ int dgp_debug_censored_terms(const double* z_dev, int64_t count, double* out_dev
  * alpha_dev: n doubles; work area as for dgp_laplace_fit_step).  Reads the plan's inputs only. */
 int dgp_debug_bilinear(dgp_plan* plan, const double* theta_host, const void* u_dev, const void* alpha_dev, void* work_dev,
                        size_t work_bytes, double* dtheta_dev, void* stream);
+
+/* The same sweep for every site of a batched float64 plan: u_dev / alpha_dev [B][n], dtheta_dev [B][ntheta], theta_host
+ * [B][ntheta]; work area as for dgp_laplace_batched_fit_step. */
+int dgp_debug_bilinear_batched(dgp_plan* plan, const double* theta_host, const void* u_dev, const void* alpha_dev, void* work_dev,
+                               size_t work_bytes, double* dtheta_dev, void* stream);
 
 /* Workspace for dgp_predict on m test points. */
 size_t dgp_predict_workspace_bytes(const dgp_plan* plan, int64_t m);
