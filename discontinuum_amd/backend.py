@@ -213,13 +213,15 @@ class GPPlan:
         return out
 
     # ------------------------------------------------------------------ censored observations (Laplace)
-    def _laplace(self, with_grad, theta, y, mean, noise, side, f, maxit, tol):
+    def _laplace(self, with_grad, theta, y, mean, noise, side, f, maxit, tol, upper=None):
         B = self.batch
         name = ("dgp_laplace_fit_step" if with_grad else "dgp_laplace_factorize") if B == 1 else (
             "dgp_laplace_batched_fit_step" if with_grad else "dgp_laplace_batched_factorize")
+        if upper is not None:  # rows of side 2 (the truth in [y, upper]): one pair of entries for every float64 plan
+            name = "dgp_laplace_interval_fit_step" if with_grad else "dgp_laplace_interval_factorize"
         if self.dtype != torch.float64:
             raise ValueError(f"{name}: censored fits need a float64 " + ("single-site plan" if B == 1 else "plan"))
-        for t, what in ((y, "y"), (mean, "mean"), (noise, "noise")):
+        for t, what in ((y, "y"), (mean, "mean"), (noise, "noise")) + (() if upper is None else ((upper, "upper"),)):
             self._check_vec(t, what)
         if not (torch.is_tensor(side) and side.is_cuda and side.dtype == torch.int32 and side.is_contiguous()
                 and side.numel() == self.n * B):
@@ -238,7 +240,8 @@ class GPPlan:
             work = self._work_area("_laplace_ws", need, name)
             out = torch.empty(shape(_lib.OUT_LEN), dtype=self.dtype, device=self.device)
             dr = torch.empty(shape(self.n), dtype=self.dtype, device=self.device) if with_grad else None
-            args = (self._h, th, _ptr(y), _ptr(mean), _ptr(noise), _ptr(side), _ptr(f), int(maxit), float(tol), work, need, _ptr(out))
+            args = (self._h, th, _ptr(y), _ptr(mean), _ptr(noise), _ptr(side)) + (() if upper is None else (_ptr(upper),)) + (
+                _ptr(f), int(maxit), float(tol), work, need, _ptr(out))
             rc = fn(*args, _ptr(dr), stat, _stream()) if with_grad else fn(*args, stat, _stream())
         vals = [float(v) for v in stat]
         # kept for a caller that catches E_NOCONV; a batched plan: one 4-tuple per site
@@ -246,7 +249,7 @@ class GPPlan:
         _lib.check(rc, name)
         return (out, dr, f, self.laplace_stat) if with_grad else (out, f, self.laplace_stat)
 
-    def laplace_fit_step(self, theta, y, mean, noise, side, f=None, maxit=50, tol=1e-10):
+    def laplace_fit_step(self, theta, y, mean, noise, side, f=None, maxit=50, tol=1e-10, upper=None):
         """One fit step with censored rows (``side`` int32: -1 the truth is below the limit in ``y``, 0 observed, +1 above) by
         the Laplace approximation: Newton's mode search from ``f`` (None: the prior mean), then the step at the mode.
         -> (out[32], dr[n], f_hat[n], stat) with ``out[OUT_NLL]`` the Laplace NLL, ``out[OUT_DTHETA:]`` its gradient,
@@ -257,12 +260,29 @@ class GPPlan:
         (batch, n), side int32 (batch, n) -- and returns out (batch, 32), dr (batch, n), f_hat (batch, n) and stat as a tuple of
         ``batch`` 4-tuples: Newton's iterations run in lockstep, a finished site is frozen, and every site's mode, iteration
         count and halvings are its own (``dgp_laplace_batched_fit_step``).  ``E_NOCONV`` when any censored site is not
-        converged after ``maxit``; a site that is not positive definite reports it in its own ``out[b, OUT_INFO]``."""
-        return self._laplace(True, theta, y, mean, noise, side, f, maxit, tol)
+        converged after ``maxit``; a site that is not positive definite reports it in its own ``out[b, OUT_INFO]``.
+        ``upper`` (shaped like ``y``): the upper ends of the INTERVAL-censored rows, side 2 -- the truth of such a row lies in
+        [y, upper] -- read on those rows only (``dgp_laplace_interval_fit_step``, every float64 plan).  None: the entries
+        above, for which 2 is a bad side value; with ``upper`` and no row of side 2 the results are bitwise theirs."""
+        return self._laplace(True, theta, y, mean, noise, side, f, maxit, tol, upper)
 
-    def laplace_factorize(self, theta, y, mean, noise, side, f=None, maxit=50, tol=1e-10):
+    def laplace_factorize(self, theta, y, mean, noise, side, f=None, maxit=50, tol=1e-10, upper=None):
         """The same without gradients (the prediction-time cache build) -> (out[32], f_hat[n], stat)."""
-        return self._laplace(False, theta, y, mean, noise, side, f, maxit, tol)
+        return self._laplace(False, theta, y, mean, noise, side, f, maxit, tol, upper)
+
+    def interval_terms(self, za: torch.Tensor, delta: torch.Tensor):
+        """(4, count): log P, sigma g, W v, sigma^3 d3 of the brackets [za, za + delta] as the interval-censored fit evaluates
+        them (P = Phi(zb) - Phi(za))."""
+        for t in (za, delta):
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.dim() == 1 and t.numel() > 0):
+                raise ValueError("za and delta must be non-empty contiguous 1-d float64 CUDA tensors")
+        if za.numel() != delta.numel() or za.device != delta.device:
+            raise ValueError("za and delta must have the same length and device")
+        with torch.cuda.device(za.device):
+            out = torch.empty((4, za.numel()), dtype=torch.float64, device=za.device)
+            _lib.check(self.lib.dgp_debug_interval_terms(_ptr(za), _ptr(delta), za.numel(), _ptr(out), _stream()),
+                       "dgp_debug_interval_terms")
+        return out
 
     def censored_terms(self, z: torch.Tensor):
         """(4, count): log Phi(z), h = phi / Phi, h (z + h), h [1 - (z + h)(z + 2 h)] as the censored fit evaluates them."""

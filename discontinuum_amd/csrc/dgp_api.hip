@@ -1190,7 +1190,7 @@ int dgp_factorize(dgp_plan* p, const double* theta, const void* r, const void* n
 // Returns 0, a HIP error (> 0), or DGP_E_ARG / DGP_E_NOCONV with the error text already set.
 static int laplace(dgp_plan* p, const double* theta, const double* y, const double* mean, const double* noise, const int* side,
                    double* f, int maxit, double tol, char* work, double* out, double* dr, double* stat, int with_grad, int batched,
-                   const char* where, hipStream_t s) {
+                   const char* where, hipStream_t s, const double* upper = nullptr, int interval = 0) {
   const int B = p->B;
   const CensoredLayout L = censored_layout(p->N, p->n, B);
   const Batch bt = batch_of<double>(p);
@@ -1207,9 +1207,20 @@ static int laplace(dgp_plan* p, const double* theta, const double* y, const doub
   };
   int rc;
   for (int k = 0; k < 4 * B; ++k) stat[k] = 0.0;
-  if ((rc = censored_terms(f, y, side, noise, mean, n, 1, 0, work, L, s, bt)) || (rc = read_status())) return rc;
+  if ((rc = censored_terms(f, y, side, noise, mean, n, 1, 0, work, L, s, bt, upper)) || (rc = read_status())) return rc;
   bool any = false, any_plain = false;
   for (int b = 0; b < B; ++b) {
+    if (interval && S(b, CEN_ST_BAD) != 0.0) {
+      snprintf(g_err, sizeof(g_err), upper ? "%s: side values must be -1, 0, +1 or 2 (site %d)"
+                                           : "%s: a row of side 2 needs upper_dev; other side values must be -1, 0 or +1 (site %d)",
+               where, b);
+      return DGP_E_ARG;
+    }
+    if (S(b, CEN_ST_BADBRK) != 0.0) {
+      snprintf(g_err, sizeof(g_err), "%s: %d bad bracket(s) in site %d: a row of side 2 needs a finite upper above its y", where,
+               (int)S(b, CEN_ST_BADBRK), b);
+      return DGP_E_ARG;
+    }
     if (S(b, CEN_ST_BAD) != 0.0) {
       if (batched)
         snprintf(g_err, sizeof(g_err), "%s: side values must be -1, 0 or +1 (site %d)", where, b);
@@ -1232,8 +1243,8 @@ static int laplace(dgp_plan* p, const double* theta, const double* y, const doub
     if ((rc = fit_step<double>(p, theta, D(L.rt), D(L.nn), D(L.out), nullptr, nullptr, 0, s))) return rc;
     ++it;
     // proposal, line search, update; then the next system (or the one at the mode) of every site that moved
-    if ((rc = censored_newton_update(f, y, side, noise, mean, alpha, n, it, tol, work, L, s, bt)) ||
-        (rc = censored_terms(f, y, side, noise, mean, n, 0, it, work, L, s, bt)) || (rc = read_status()))
+    if ((rc = censored_newton_update(f, y, side, noise, mean, alpha, n, it, tol, work, L, s, bt, upper)) ||
+        (rc = censored_terms(f, y, side, noise, mean, n, 0, it, work, L, s, bt, upper)) || (rc = read_status()))
       return rc;
     bool all_done = true;
     for (int b = 0; b < B; ++b) {
@@ -1280,7 +1291,7 @@ static int laplace(dgp_plan* p, const double* theta, const double* y, const doub
 }
 static int laplace_entry(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise, const int32_t* side,
                          void* f, int maxit, double tol, void* work, size_t work_bytes, void* out, void* dr, double* stat,
-                         int with_grad, int batched, const char* where, void* stream) {
+                         int with_grad, int batched, const char* where, void* stream, const void* upper = nullptr, int interval = 0) {
   char msg[160];
   if (!p) return fail(DGP_E_ARG, "null plan");
   if (batched ? p->dtype != DGP_F64 : (p->dtype != DGP_F64 || p->B != 1)) {
@@ -1302,7 +1313,8 @@ static int laplace_entry(dgp_plan* p, const double* theta, const void* y, const 
   }
   if (((uintptr_t)work & 255) != 0) return fail(DGP_E_ARG, "dgp_laplace_*: the work area must be 256-byte aligned");
   const int rc = laplace(p, theta, (const double*)y, (const double*)mean, (const double*)noise, (const int*)side, (double*)f, maxit, tol,
-                         (char*)work, (double*)out, (double*)dr, stat, with_grad, batched, where, (hipStream_t)stream);
+                         (char*)work, (double*)out, (double*)dr, stat, with_grad, batched, where, (hipStream_t)stream,
+                         (const double*)upper, interval);
   if (rc == DGP_E_ARG || rc == DGP_E_NOCONV) return rc;  // text set where it arose
   return wrap(rc, where);
 }
@@ -1343,6 +1355,26 @@ int dgp_laplace_batched_factorize(dgp_plan* p, const double* theta, const void* 
                                   double* stat, void* stream) {
   return laplace_entry(p, theta, y, mean, noise, side, f, maxit, tol, work, work_bytes, out, nullptr, stat, 0, 1,
                        "dgp_laplace_batched_factorize", stream);
+}
+
+int dgp_laplace_interval_fit_step(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise,
+                                  const int32_t* side, const void* upper, void* f, int maxit, double tol, void* work, size_t work_bytes,
+                                  void* out, void* dr, double* stat, void* stream) {
+  return laplace_entry(p, theta, y, mean, noise, side, f, maxit, tol, work, work_bytes, out, dr, stat, 1, 1,
+                       "dgp_laplace_interval_fit_step", stream, upper, 1);
+}
+
+int dgp_laplace_interval_factorize(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise,
+                                   const int32_t* side, const void* upper, void* f, int maxit, double tol, void* work,
+                                   size_t work_bytes, void* out, double* stat, void* stream) {
+  return laplace_entry(p, theta, y, mean, noise, side, f, maxit, tol, work, work_bytes, out, nullptr, stat, 0, 1,
+                       "dgp_laplace_interval_factorize", stream, upper, 1);
+}
+
+int dgp_debug_interval_terms(const double* za, const double* delta, int64_t count, double* out, void* stream) {
+  if (!za || !delta || !out || count <= 0 || count > (1ll << 29))
+    return fail(DGP_E_ARG, "dgp_debug_interval_terms: null argument / bad count");
+  return wrap(debug_interval_terms(za, delta, count, out, (hipStream_t)stream), "dgp_debug_interval_terms");
 }
 
 int dgp_debug_censored_terms(const double* z, int64_t count, double* out, void* stream) {

@@ -6,7 +6,10 @@
 //     g_i  =  d log p_i / d f_i     =  s_i h / sigma_i
 //     W_i  = -d^2 log p_i / d f_i^2 =  h (z + h) / v_i               in (0, 1 / v_i)
 //     d3_i =  d^3 log p_i / d f_i^3 = -(s_i / sigma_i^3) h [1 - (z + h)(z + 2 h)]
-// and at the mode the posterior of f is the exact GP posterior for the pseudo-targets y~_i = f_i + g_i / W_i with the
+// A fourth kind, side 2, is INTERVAL-censored: the truth lies in [y_i, upper_i], log p_i = log[Phi(zb) - Phi(za)] (iv_fn below:
+// the same three derivatives, the same Newton / pseudo-data / correction / sweep machinery; `upper` is an optional pointer of the
+// terms and search kernels, and without it 2 is a bad side value and every bit is what it was).
+// At the mode the posterior of f is the exact GP posterior for the pseudo-targets y~_i = f_i + g_i / W_i with the
 // pseudo-noise n~_i = 1 / W_i (observed rows: y~ = y, n~ = v).  A Newton step is therefore ONE factorisation with the
 // residual r~ = y~ - m and the noise n~:  a = (K + diag n~)^-1 r~,  f_new = m + K a = y~ - n~ o a  (no product with K).
 //
@@ -69,6 +72,130 @@ int debug_censored_terms(const double* z, long count, double* out, hipStream_t s
   return (int)hipGetLastError();
 }
 
+// ---- interval-censored rows (side 2): the truth lies in [y, upper], standardised [za, zb], Delta = zb - za > 0.
+//     P = Phi(zb) - Phi(za),  ra = phi(za) / P,  rb = phi(zb) / P
+//     log p = log P,   mu = sigma g = ra - rb,   wv = W v = zb rb - za ra + mu^2  in (0, 1],
+//     d3 = sigma^3 d^3 log p / d f^3 = ra (za^2 - 1) - rb (zb^2 - 1) - mu (za ra - zb rb) + 2 mu wv
+// = mean, 1 - variance and third central moment of a standard normal truncated to [za, zb].  None of this can be evaluated as
+// written (P underflows and cancels in a tail; for Delta << 1 wv is a sum of O(1 / Delta^2) terms).  A bracket whose centre c lies
+// right of 0 is reflected (mu and d3 change sign); then, with h = Delta / 2,
+//   narrow    h <= 1 and |c| h <= 2:  P = h phi(c) I,  I = int_-1^1 exp(-c h t - h^2 t^2 / 2) dt by a fixed 12-point Gauss-Legendre
+//             rule (its error for these exponents is below 1e-18); mu = c + h E[t], wv = 1 - h^2 Var[t], d3 = h^3 E[(t - E t)^3]
+//             with the central moments taken about the computed mean: nothing cancels as Delta -> 0
+//   tail      zb <= 0 (then |c| h > 1):  P = phi(zb) D,  D = M(zb) - rho M(za),  M = Phi / phi = sqrt(pi / 2) erfcx(-z / sqrt 2),
+//             rho = phi(za) / phi(zb) = exp(Delta c) <= e^-2: D does not cancel; rb = 1 / D, ra = rho / D, mu = expm1(Delta c) / D
+//   straddle  za < 0 < zb (then h > 1):  P = [erf(zb / sqrt 2) + erf(-za / sqrt 2)] / 2, a sum of positive terms
+// The tail's wv and d3 keep the cancellation of the one-sided functions above (relative error ~ z^2 eps and z^3 eps).
+struct IntFn {
+  double logp, mu, wv, d3;
+};
+constexpr double IV_T[6] = {0.12523340851146891547, 0.36783149899818019375, 0.58731795428661744730,
+                            0.76990267419430468704, 0.90411725637047485668, 0.98156063424671925069};
+constexpr double IV_W[6] = {0.24914704581340278500, 0.23349253653835480876, 0.20316742672306592175,
+                            0.16007832854334622633, 0.10693932599531843096, 0.04717533638651182719};
+#define IV_LOGSQRT2PI 0.91893853320467274178
+#define IV_NARROW_H 1.0
+#define IV_NARROW_A 2.0
+// the reflected bracket [a, b] with centre c <= 0; -> true when the caller's bracket was reflected
+__device__ __forceinline__ bool iv_reflect(double za, double zb, double delta, double& a, double& b, double& c) {
+  const bool flip = za + zb > 0.0;
+  a = flip ? -zb : za;
+  b = flip ? -za : zb;
+  c = flip ? -(za + 0.5 * delta) : za + 0.5 * delta;
+  return flip;
+}
+// the weighted integrand at the twelve nodes (fully unrolled: registers) and its sum
+__device__ __forceinline__ double iv_nodes(double c, double h, double (&f)[12]) {
+  const double p = -c * h, q = -0.5 * h * h;
+  double tot = 0.0;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const double t = IV_T[k], qt = q * t * t;
+    f[2 * k] = IV_W[k] * exp(qt + p * t);
+    f[2 * k + 1] = IV_W[k] * exp(qt - p * t);
+    tot += f[2 * k] + f[2 * k + 1];
+  }
+  return tot;
+}
+__device__ __forceinline__ double iv_logp(double za, double zb, double delta) {
+  double a, b, c;
+  (void)iv_reflect(za, zb, delta, a, b, c);
+  const double h = 0.5 * delta;
+  if (h <= IV_NARROW_H && -c * h <= IV_NARROW_A) {
+    double f[12];
+    return log(h) - 0.5 * c * c - IV_LOGSQRT2PI + log(iv_nodes(c, h, f));
+  }
+  if (b <= 0.0) {
+    const double D = 1.25331413731550025121 * (erfcx(-b * 0.70710678118654752440) - exp(delta * c) * erfcx(-a * 0.70710678118654752440));
+    return -0.5 * b * b - IV_LOGSQRT2PI + log(D);
+  }
+  return log(0.5 * (erf(b * 0.70710678118654752440) + erf(-a * 0.70710678118654752440)));
+}
+__device__ __forceinline__ IntFn iv_fn(double za, double zb, double delta) {
+  IntFn o;
+  double a, b, c;
+  const bool flip = iv_reflect(za, zb, delta, a, b, c);
+  const double h = 0.5 * delta;
+  if (h <= IV_NARROW_H && -c * h <= IV_NARROW_A) {
+    double f[12];
+    const double tot = iv_nodes(c, h, f);
+    double s1 = 0.0, s2 = 0.0, s3 = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) s1 += IV_T[k] * (f[2 * k] - f[2 * k + 1]);
+    const double m1 = s1 / tot;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      const double dp = IV_T[k] - m1, dm = -IV_T[k] - m1;
+      s2 += f[2 * k] * dp * dp + f[2 * k + 1] * dm * dm;
+      s3 += f[2 * k] * dp * dp * dp + f[2 * k + 1] * dm * dm * dm;
+    }
+    o.logp = log(h) - 0.5 * c * c - IV_LOGSQRT2PI + log(tot);
+    o.mu = c + h * m1;
+    o.wv = 1.0 - h * h * (s2 / tot);
+    o.d3 = h * h * h * (s3 / tot);
+  } else {
+    double ra, rb;
+    if (b <= 0.0) {
+      const double e1 = expm1(delta * c), rho = 1.0 + e1;
+      const double D = 1.25331413731550025121 * (erfcx(-b * 0.70710678118654752440) - rho * erfcx(-a * 0.70710678118654752440));
+      ra = rho / D;
+      rb = 1.0 / D;
+      o.mu = e1 / D;
+      o.logp = -0.5 * b * b - IV_LOGSQRT2PI + log(D);
+    } else {
+      const double P = 0.5 * (erf(b * 0.70710678118654752440) + erf(-a * 0.70710678118654752440));
+      ra = exp(-0.5 * a * a - IV_LOGSQRT2PI) / P;
+      rb = exp(-0.5 * b * b - IV_LOGSQRT2PI) / P;
+      o.mu = ra - rb;
+      o.logp = log(P);
+    }
+    const double A = b * rb - a * ra;
+    o.wv = fmin(A + o.mu * o.mu, 1.0);
+    o.d3 = ra * (a * a - 1.0) - rb * (b * b - 1.0) + o.mu * A + 2.0 * o.mu * o.wv;
+  }
+  if (flip) {
+    o.mu = -o.mu;
+    o.d3 = -o.d3;
+  }
+  return o;
+}
+
+__global__ __launch_bounds__(256) void iv_debug_kernel(const double* __restrict__ za, const double* __restrict__ delta, long count,
+                                                       double* __restrict__ out) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= count) return;
+  const IntFn o = iv_fn(za[i], za[i] + delta[i], delta[i]);
+  out[i] = o.logp;
+  out[count + i] = o.mu;
+  out[2 * count + i] = o.wv;
+  out[3 * count + i] = o.d3;
+}
+
+int debug_interval_terms(const double* za, const double* delta, long count, double* out, hipStream_t s) {
+  iv_debug_kernel<<<dim3((unsigned)((count + 255) / 256)), 256, 0, s>>>(za, delta, count, out);
+  return (int)hipGetLastError();
+}
+
 // block sums of K <= CEN_PART values per thread (column `maxcol`, if any, is a maximum), lane order then wave order
 template <int K>
 __device__ __forceinline__ void cen_block_reduce(double (&v)[K], int maxcol, double* __restrict__ part) {
@@ -115,7 +242,8 @@ __device__ __forceinline__ bool cen_frozen(const double* __restrict__ status, in
   return d != 0.0 && d != (double)it;
 }
 
-// ---- terms at the current f.  y holds the observation (side 0) or the limit (side +-1).  Capped rows (W v < cap: the limit
+// ---- terms at the current f.  y holds the observation (side 0), the limit (side +-1) or a bracket's lower end (side 2, with
+// `upper`: its upper end; a bracket whose upper end is NaN, infinite or not above y is counted in the fifth sum).  Capped rows (W v < cap: the limit
 // says nothing) get n~ = v / cap and d3 = 0.  corr: the row's part of the NLL correction that does not involve alpha.
 // Every elementwise vector is [site][nfull]; `part` [site][nblk][CEN_PART]; status [site][CEN_ST_LEN].
 __global__ __launch_bounds__(256) void cen_terms_kernel(const double* __restrict__ f, const double* __restrict__ y,
@@ -124,7 +252,8 @@ __global__ __launch_bounds__(256) void cen_terms_kernel(const double* __restrict
                                                         double* __restrict__ rt, double* __restrict__ nn, double* __restrict__ g,
                                                         double* __restrict__ W, double* __restrict__ d3, double* __restrict__ corr,
                                                         double* __restrict__ logp, double* __restrict__ part,
-                                                        const double* __restrict__ status, int init, int it) {
+                                                        const double* __restrict__ status, int init, int it,
+                                                        const double* __restrict__ upper) {
   status = site(status, (long)CEN_ST_LEN);
   if (!init && (cen_frozen(status, it) || status[CEN_ST_INFO] != 0.0)) return;
   const long nfull = n;
@@ -132,13 +261,32 @@ __global__ __launch_bounds__(256) void cen_terms_kernel(const double* __restrict
   f = site(f, nfull); y = site(y, nfull); side = site(side, nfull); v = site(v, nfull); m = site(m, nfull);
   rt = site(rt, nfull); nn = site(nn, nfull); g = site(g, nfull); W = site(W, nfull); d3 = site(d3, nfull);
   corr = site(corr, nfull); logp = site(logp, nfull);
+  if (upper) upper = site(upper, nfull);
   part = site(part, (long)gridDim.x * CEN_PART);
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  double acc[4] = {0.0, 0.0, 0.0, 0.0};  // correction, capped rows, bad side values, censored rows
+  double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};  // correction, capped rows, bad side values, censored rows, bad brackets
   if (i < n) {
     const int s = side[i];
     const double vi = v[i], mi = m[i], yi = y[i], fi = f[i];
-    if (s == 0 || (s != 1 && s != -1)) {
+    const bool brk = s == 2 && upper != nullptr;  // (without `upper`, 2 is a bad side value)
+    const double ui = brk ? upper[i] : 0.0;
+    if (brk && ui > yi && ui < __builtin_inf()) {
+      const double sg = sqrt(vi);
+      const IntFn o = iv_fn((yi - fi) / sg, (ui - fi) / sg, (ui - yi) / sg);
+      const bool capped = !(o.wv >= cap);
+      const double ni = capped ? vi / cap : vi / o.wv, wi = 1.0 / ni, gi = o.mu / sg;
+      rt[i] = (fi + gi * ni) - mi;
+      nn[i] = ni;
+      g[i] = gi;
+      W[i] = wi;
+      d3[i] = capped ? 0.0 : o.d3 / (sg * vi);
+      const double c = -o.logp + 0.5 * log(wi) - 0.5 * 1.83787706640934548356;
+      corr[i] = c;
+      logp[i] = o.logp;
+      acc[0] = c;
+      acc[1] = capped ? 1.0 : 0.0;
+      acc[3] = 1.0;
+    } else if (s == 0 || (s != 1 && s != -1)) {
       const double e = yi - fi;
       rt[i] = yi - mi;
       nn[i] = vi;
@@ -147,7 +295,8 @@ __global__ __launch_bounds__(256) void cen_terms_kernel(const double* __restrict
       d3[i] = 0.0;
       corr[i] = 0.0;
       logp[i] = -0.5 * e * e / vi - 0.5 * log(6.28318530717958647692 * vi);
-      acc[2] = s == 0 ? 0.0 : 1.0;
+      acc[2] = (s == 0 || brk) ? 0.0 : 1.0;
+      acc[4] = brk ? 1.0 : 0.0;  // NaN, infinite or not above y
     } else {
       const double sg = sqrt(vi), sd = (double)s;
       const CenFn o = cen_fn(sd * (fi - yi) / sg);
@@ -166,7 +315,7 @@ __global__ __launch_bounds__(256) void cen_terms_kernel(const double* __restrict
       acc[3] = 1.0;
     }
   }
-  cen_block_reduce<4>(acc, -1, part);
+  cen_block_reduce<5>(acc, -1, part);
 }
 __global__ __launch_bounds__(256) void cen_terms_finish_kernel(const double* __restrict__ part, int nblk, double* __restrict__ status,
                                                                int init, int it) {
@@ -174,10 +323,10 @@ __global__ __launch_bounds__(256) void cen_terms_finish_kernel(const double* __r
   if (!init && (cen_frozen(status, it) || status[CEN_ST_INFO] != 0.0)) return;
   part = site(part, (long)nblk * CEN_PART);
   __shared__ double tot[CEN_PART];
-  cen_total(part, nblk, 4, -1, tot);
+  cen_total(part, nblk, 5, -1, tot);
   if (threadIdx.x < 4) status[CEN_ST_CORR + threadIdx.x] = tot[threadIdx.x];
   if (init && threadIdx.x >= 4 && threadIdx.x < CEN_ST_LEN)
-    status[threadIdx.x] = (threadIdx.x == CEN_ST_DONE && tot[3] == 0.0) ? -1.0 : 0.0;
+    status[threadIdx.x] = (threadIdx.x == CEN_ST_DONE && tot[3] == 0.0) ? -1.0 : (threadIdx.x == CEN_ST_BADBRK ? tot[4] : 0.0);
 }
 
 // ---- proposal and line search.  anew: the plan's alpha of the factorisation at (r~, n~); acur: the a of the current f (f - m =
@@ -188,13 +337,14 @@ __global__ __launch_bounds__(256) void cen_search_kernel(const double* __restric
                                                          const double* __restrict__ nn, const double* __restrict__ anew, long as,
                                                          const double* __restrict__ acur, int n, const int* __restrict__ ns,
                                                          double* __restrict__ delta, double* __restrict__ part,
-                                                         const double* __restrict__ status) {
+                                                         const double* __restrict__ status, const double* __restrict__ upper) {
   if (site(status, (long)CEN_ST_LEN)[CEN_ST_DONE] != 0.0) return;
   const long nfull = n;
   n = site_n(ns, n);
   f = site(f, nfull); y = site(y, nfull); side = site(side, nfull); v = site(v, nfull); m = site(m, nfull);
   rt = site(rt, nfull); nn = site(nn, nfull); acur = site(acur, nfull); delta = site(delta, nfull);
   anew = site(anew, as);
+  if (upper) upper = site(upper, nfull);
   part = site(part, (long)gridDim.x * CEN_PART);
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   double acc[CEN_NT + 1];
@@ -204,6 +354,8 @@ __global__ __launch_bounds__(256) void cen_search_kernel(const double* __restric
     const int s = side[i];
     const double vi = v[i], mi = m[i], yi = y[i], fi = f[i], an = anew[i], ac = acur[i];
     const double dlt = (mi + rt[i] - nn[i] * an) - fi, da = an - ac, sg = sqrt(vi);
+    const bool brk = s == 2 && upper != nullptr;  // (a bad bracket has ended the call after the first pass)
+    const double ui = brk ? upper[i] : 0.0, dz = (ui - yi) / sg;
     delta[i] = dlt;
     acc[CEN_NT] = fabs(dlt);
     double t = 0.0;
@@ -214,6 +366,8 @@ __global__ __launch_bounds__(256) void cen_search_kernel(const double* __restric
       if (s == 0) {
         const double e = yi - ft;
         lp = -0.5 * e * e / vi - 0.5 * log(6.28318530717958647692 * vi);
+      } else if (brk) {
+        lp = iv_logp((yi - ft) / sg, (ui - ft) / sg, dz);
       } else {
         lp = cen_logphi((double)s * (ft - yi) / sg);
       }
@@ -383,21 +537,21 @@ CensoredLayout censored_layout(long N, long n, int B) {
 }
 
 int censored_terms(const double* f, const double* y, const int* side, const double* v, const double* m, int n, int init, int it,
-                   char* work, const CensoredLayout& L, hipStream_t s, Batch bt) {
+                   char* work, const CensoredLayout& L, hipStream_t s, Batch bt, const double* upper) {
   auto D = [&](size_t off) { return (double*)(work + off); };
   const unsigned Bz = (unsigned)bt.B;
   cen_terms_kernel<<<dim3((unsigned)L.nblk, 1, Bz), 256, 0, s>>>(f, y, side, v, m, n, bt.ns, CEN_CAP, D(L.rt), D(L.nn), D(L.g), D(L.W),
-                                                                 D(L.d3), D(L.corr), D(L.logp), D(L.part), D(L.status), init, it);
+                                                                 D(L.d3), D(L.corr), D(L.logp), D(L.part), D(L.status), init, it, upper);
   cen_terms_finish_kernel<<<dim3(1, 1, Bz), 256, 0, s>>>(D(L.part), L.nblk, D(L.status), init, it);
   return (int)hipGetLastError();
 }
 
 int censored_newton_update(double* f, const double* y, const int* side, const double* v, const double* m, const double* anew, int n,
-                           int it, double tol, char* work, const CensoredLayout& L, hipStream_t s, Batch bt) {
+                           int it, double tol, char* work, const CensoredLayout& L, hipStream_t s, Batch bt, const double* upper) {
   auto D = [&](size_t off) { return (double*)(work + off); };
   const unsigned Bz = (unsigned)bt.B;
   cen_search_kernel<<<dim3((unsigned)L.nblk, 1, Bz), 256, 0, s>>>(f, y, side, v, m, D(L.rt), D(L.nn), anew, bt.ws, D(L.acur), n, bt.ns,
-                                                                  D(L.delta), D(L.part), D(L.status));
+                                                                  D(L.delta), D(L.part), D(L.status), upper);
   cen_search_finish_kernel<<<dim3(1, 1, Bz), 256, 0, s>>>(D(L.part), L.nblk, it, tol, D(L.out), D(L.status));
   cen_update_kernel<<<dim3((unsigned)L.nblk, 1, Bz), 256, 0, s>>>(f, D(L.delta), D(L.acur), anew, bt.ws, D(L.status), n, bt.ns, it);
   return (int)hipGetLastError();

@@ -419,6 +419,7 @@ enum {
   CEN_ST_DONE,       // 0: the site's mode search is running; -1: it has no censored row (done before the first iteration);
                      // k > 0: it finished in Newton iteration k (converged or not positive definite).  A site that finished in an
                      // EARLIER iteration is frozen: cen_search, cen_update and cen_terms leave everything of it untouched
+  CEN_ST_BADBRK,     // rows of side 2 whose `upper` is NaN, infinite or not above y (set by the first pass of a call)
   CEN_ST_LEN = 16
 };
 // Byte offsets into the work area.  rt (r~), nn (n~) and dnoise are [B][n] at stride n, as fit_step<double> reads its caller
@@ -434,13 +435,16 @@ struct CensoredLayout {
 CensoredLayout censored_layout(long N, long n, int B = 1);
 // the terms at f: r~, n~, g, W, d3, per-row correction and log p into the work area, their sums into status[CEN_ST_CORR ..];
 // init: the first pass of a call, which also sets every site's CEN_ST_DONE (0 or -1) and clears the search's fields;
-// otherwise `it` = the Newton iteration just taken (1-based): sites that finished before it, or failed in it, are skipped
+// otherwise `it` = the Newton iteration just taken (1-based): sites that finished before it, or failed in it, are skipped.
+// upper ([B][n], or null): the upper ends of the rows of side 2 (interval-censored: the truth lies in [y, upper]); with a null
+// `upper` 2 is a bad side value and both passes give the bits they gave before brackets existed
 int censored_terms(const double* f, const double* y, const int* side, const double* v, const double* m, int n, int init, int it,
-                   char* work, const CensoredLayout& L, hipStream_t s, Batch bt = Batch());
+                   char* work, const CensoredLayout& L, hipStream_t s, Batch bt = Batch(), const double* upper = nullptr);
 // after the factorisation at (r~, n~) left `anew` in the plan: proposal, line search, f and the work area's a updated in place
 // (Newton iteration `it`, 1-based; frozen sites untouched)
 int censored_newton_update(double* f, const double* y, const int* side, const double* v, const double* m, const double* anew, int n,
-                           int it, double tol, char* work, const CensoredLayout& L, hipStream_t s, Batch bt = Batch());
+                           int it, double tol, char* work, const CensoredLayout& L, hipStream_t s, Batch bt = Batch(),
+                           const double* upper = nullptr);
 // f = m + r~ - n~ o alpha for the sites without a censored row
 int censored_mode(double* f, const double* m, const double* alpha, int n, char* work, const CensoredLayout& L, hipStream_t s,
                   Batch bt = Batch());
@@ -457,5 +461,7 @@ int gram_bilinear(int model, int d, const T* Xt, long N, int n, const double* th
                   void* pre_scratch = nullptr, bool upload = false, void* pre_staging = nullptr);
 // out [4][count]: log Phi(z), h = phi / Phi, h (z + h), h [1 - (z + h)(z + 2 h)]
 int debug_censored_terms(const double* z, long count, double* out, hipStream_t s);
+// out [4][count]: log P, sigma g, W v, sigma^3 d3 of the bracket [za, za + delta]
+int debug_interval_terms(const double* za, const double* delta, long count, double* out, hipStream_t s);
 
 }  // namespace dgp

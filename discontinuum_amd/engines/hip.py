@@ -213,19 +213,28 @@ class ConstantMeanShortcut(MeanShortcut):
 
 class CensorState:
     """The censoring of a fit: ``side`` (device int32, -1 = the target value is a limit and the truth lies below it, +1 =
-    above, 0 = observed), the latest mode ``f`` of the Laplace approximation (device; None = cold start from the prior mean)
-    and the ``status`` of the last mode search (Newton iterations, final max |df|, halvings, capped rows)."""
+    above, 0 = observed, 2 = the truth lies between the target value and ``upper``), ``upper`` (device, model space, read on
+    the rows of side 2 only; None when there is no such row), the latest mode ``f`` of the Laplace approximation (device;
+    None = cold start from the prior mean) and the ``status`` of the last mode search (Newton iterations, final max |df|,
+    halvings, capped rows)."""
 
-    def __init__(self, side, maxit=50, tol=1e-10):
+    def __init__(self, side, maxit=50, tol=1e-10, upper=None):
         self.side, self.f, self.status, self.maxit, self.tol = side, None, None, int(maxit), float(tol)
+        self.upper = upper
+
+    def kwargs(self):
+        """The keyword arguments of ``GPPlan.laplace_*`` that the bracketed rows add (none without such a row: the
+        entry points of the one-sided fit, bit for bit)."""
+        return {} if self.upper is None else {"upper": self.upper}
 
     def update(self, f, status):
         self.f, self.status = f.detach(), tuple(status)
 
 
-def censor_sides(censored, n):
+def censor_sides(censored, n, bracketed=False):
     """``fit(censored=...)`` as an int32 array of -1 / 0 / +1, or None when nothing is censored.  Booleans: True = the
-    reported value is a detection limit and the truth is below it."""
+    reported value is a detection limit and the truth is below it.  ``bracketed`` (the caller has a ``target_upper``): the
+    code 2 -- the truth lies between the target value and the upper end -- is accepted too."""
     if censored is None:
         return None
     a = np.asarray(getattr(censored, "values", censored))
@@ -234,10 +243,44 @@ def censor_sides(censored, n):
     if a.dtype == bool:
         side = np.where(a, -1, 0).astype(np.int32)
     else:
-        if not np.all(np.isin(a, (-1, 0, 1))):
-            raise ValueError("censored must be boolean or hold -1 (below the limit), 0 (observed), +1 (above the limit)")
+        if bracketed:
+            if not np.all(np.isin(a, (-1, 0, 1, 2))):
+                raise ValueError("censored must be boolean or hold -1 (below the limit), 0 (observed), +1 (above the limit), "
+                                 "2 (between the target value and target_upper)")
+        elif not np.all(np.isin(a, (-1, 0, 1))):
+            raise ValueError("censored must be boolean or hold -1 (below the limit), 0 (observed), +1 (above the limit); the code "
+                             "2 (between the target value and an upper end) needs target_upper")
         side = a.astype(np.int32)
     return side if side.any() else None
+
+
+MIDPOINT_WIDTH = 1e-6  # a bracket narrower than this many sigma is an observation at its midpoint
+
+
+class _Values:
+    """The least a target pipeline's first step reads of a labelled array."""
+
+    def __init__(self, values):
+        self.values = values
+
+
+def bracket_ends(side, y, upper_model, sigma):
+    """The model-space ends of the bracketed rows (``side`` == 2) from the transformed lower ends ``y`` and upper ends
+    ``upper_model``: a decreasing target transform has swapped them, so the ends are sorted; a bracket narrower than
+    ``MIDPOINT_WIDTH`` sigma becomes an observation (side 0) at its midpoint.  -> (side, y, upper) as new numpy arrays; upper
+    is NaN off the bracketed rows, or None when no bracketed row is left."""
+    side = np.array(side, dtype=np.int32)
+    y = np.array(y, dtype=np.float64)
+    br = side == 2
+    lo = np.where(br, np.minimum(y, upper_model), y)
+    hi = np.where(br, np.maximum(y, upper_model), np.nan)
+    if not np.all(np.isfinite(lo[br]) & np.isfinite(hi[br])):
+        raise ValueError("target_upper (and the target) must be finite in model space on every row with censored == 2")
+    narrow = br & ~(hi - lo >= MIDPOINT_WIDTH * sigma)
+    y = np.where(narrow, 0.5 * (lo + hi), lo)
+    side[narrow] = 0
+    hi = np.where(narrow, np.nan, hi)
+    return side, y, (hi if (side == 2).any() else None)
 
 
 class PriorSpec:
@@ -249,6 +292,7 @@ class PriorSpec:
     def __init__(self, plan, theta, mean, noise, shortcut=None, censored=None):
         self.plan, self.theta, self._mean, self._noise, self.shortcut = plan, theta, mean, noise, shortcut
         self.censored = censored
+        self.upper = getattr(censored, "upper", None)  # the upper ends of the bracketed rows (model space) or None
 
     @property
     def mean(self):
@@ -279,6 +323,7 @@ class MarginalHIP(BaseModel):
         self._factor_key = None
         self._pending_device = None  # (train_x, train_y) whose upload is deferred to the first prediction (fit_many)
         self._censor = None  # CensorState of a fit with censored observations
+        self._y_model = None
         self.laplace_status_ = None
 
     # ------------------------------------------------------------------ device plumbing
@@ -310,6 +355,12 @@ class MarginalHIP(BaseModel):
             censored=getattr(self, "_censor", None),
         )
 
+    def model_space_targets(self):
+        """The model-space targets the fit ran on (numpy): ``dm.y``, with the entries of bracketed rows as ``fit`` placed them
+        (the lower end in model space, or the midpoint of a very narrow bracket)."""
+        own = getattr(self, "_y_model", None)
+        return self.dm.y if own is None else own
+
     _CENSOR_REFUSAL = ("{what} is not available for a fit with censored observations: it reads the pseudo-data of the Laplace "
                        "approximation as if they were samples")
 
@@ -317,19 +368,45 @@ class MarginalHIP(BaseModel):
         if getattr(self, "_censor", None) is not None:
             raise NotImplementedError(self._CENSOR_REFUSAL.format(what=what))
 
-    def _set_censoring(self, censored, n):
-        """Parse ``censored`` (see ``fit``) and keep it on the engine; the side vector goes to the device with the data."""
-        side = censor_sides(censored, n)
-        self._censor_host = side
+    def _set_censoring(self, censored, n, target_upper=None, y=None):
+        """Parse ``censored`` and ``target_upper`` (see ``fit``) and keep them on the engine; the side vector (and the upper
+        ends) go to the device with the data.  ``y``: the model-space targets (needed with ``target_upper``).  -> the
+        model-space targets the fit runs on: ``y`` itself unless a bracketed row changed its entry (a decreasing transform
+        swaps a bracket's ends; a very narrow bracket becomes an observation at its midpoint)."""
+        side = censor_sides(censored, n, bracketed=target_upper is not None)
+        self._censor_host = side  # as given: what a checkpoint carries
+        self._upper_host = None   # data space, as given
+        self._y_model = None      # the model-space targets of a fit with bracketed rows (numpy), where they differ from dm.y
         self._censor = None
         self.laplace_status_ = None
         if side is None:
-            return
+            return y
         if getattr(self.likelihood, "second_noise_covar", None) is not None:
             raise NotImplementedError("censored observations need a fixed-noise likelihood: the Laplace fit produces no gradient "
                                       "for a learned noise term (rating-gp is not supported)")
+        upper = None
+        if (side == 2).any():
+            raw = np.asarray(getattr(target_upper, "values", target_upper), dtype=np.float64)
+            if raw.shape != (n,):
+                raise ValueError(f"target_upper must align with the target: expected shape ({n},), got {raw.shape}")
+            if y is None:
+                raise ValueError("bracketed rows need the model-space targets")
+            self._upper_host = raw
+            br = side == 2
+            # through the target pipeline as it was fitted on the target (never refitted); rows without a bracket are not read
+            filled = np.where(br, raw, raw[br][0])
+            upper_model = np.asarray(self.dm.target_pipeline.transform(_Values(filled)), dtype=np.float64).reshape(-1)
+            noise = self.likelihood.train_noise(torch.device("cpu"), torch.float64)
+            sigma = np.broadcast_to(np.sqrt(np.asarray(noise.detach().cpu().numpy(), dtype=np.float64)).reshape(-1), (n,))
+            side, y_model, upper = bracket_ends(side, y.detach().cpu().numpy(), upper_model, sigma)
+            self._y_model = y_model
+            y = torch.as_tensor(y_model, dtype=y.dtype)
+            if not side.any():
+                return y
         self._censor = CensorState(torch.as_tensor(side, dtype=torch.int32).to(self.device).contiguous(),
-                                   maxit=self.laplace_maxit, tol=self.laplace_tol)
+                                   maxit=self.laplace_maxit, tol=self.laplace_tol,
+                                   upper=None if upper is None else self._tensor(upper))
+        return y
 
     laplace_maxit, laplace_tol = 50, 1e-10  # Newton's mode search of a censored fit
 
@@ -401,6 +478,8 @@ class MarginalHIP(BaseModel):
             "model_state_dict": self.model.state_dict(),
             "likelihood_state_dict": self.likelihood.state_dict(),
             "censored": None if getattr(self, "_censor_host", None) is None else torch.as_tensor(self._censor_host, dtype=torch.int8),
+            "target_upper": (None if getattr(self, "_upper_host", None) is None
+                             else torch.as_tensor(self._upper_host, dtype=torch.float64)),
             "optimizer_state_dict": None, "optimizer_name": None, "optimizer_lr": None,
             "scheduler_state_dict": None, "scheduler_name": None,
         }
@@ -436,9 +515,10 @@ class MarginalHIP(BaseModel):
                                f"unexpected parameters {unexpected}")
 
     @classmethod
-    def load(cls, f, covariates, target, target_unc=None, censored=None):
+    def load(cls, f, covariates, target, target_unc=None, censored=None, target_upper=None):
         """A model restored from ``save()`` output and re-attached to its data: ready to predict, or to continue
-        training with ``fit(..., resume=True)`` (engines/gpytorch.py:47-105).  The file is read with
+        training with ``fit(..., resume=True)`` (engines/gpytorch.py:47-105).  ``censored`` / ``target_upper``: as in
+        ``fit``; None takes what the checkpoint carries (the codes and the brackets' upper ends).  The file is read with
         ``weights_only=True`` (nothing in it is executed); checkpoints of earlier versions that pickled the
         ``ModelConfig`` dataclass load under an allow-list of exactly that class."""
         with torch.serialization.safe_globals([ModelConfig]):
@@ -459,7 +539,9 @@ class MarginalHIP(BaseModel):
         self._resume_info["current_iteration"] = self._current_iteration
         if censored is None and record.get("censored") is not None:
             censored = record["censored"].numpy().astype(np.int32)  # the side vector the checkpoint carries
-        self._set_censoring(censored, y.shape[0])
+            if target_upper is None and record.get("target_upper") is not None:
+                target_upper = record["target_upper"].numpy()  # and the brackets' upper ends (data space)
+        y = self._set_censoring(censored, y.shape[0], target_upper, y)
         self._setup_device(x, y)
         self.is_fitted = True
         return self
@@ -486,7 +568,8 @@ class MarginalHIP(BaseModel):
 
     def fit(self, covariates, target, target_unc=None, iterations: int = 100, optimizer: str | None = None,
             learning_rate: float | None = None, early_stopping: bool = False, patience: int = 60,
-            scheduler: bool = True, resume: bool = False, penalty_callback=None, penalty_weight: float = 0.0, censored=None):
+            scheduler: bool = True, resume: bool = False, penalty_callback=None, penalty_weight: float = 0.0, censored=None,
+            target_upper=None):
         """Train the hyperparameters; arguments and behaviour as ``MarginalGPyTorch.fit``
         (engines/gpytorch.py:162-458): Adam (default lr 0.05) or AdamW, gradient clipping to norm 1, optional
         ReduceLROnPlateau, NaN iterations skipped (more than ten in a row raise), optional early stopping, resume from a
@@ -497,7 +580,17 @@ class MarginalHIP(BaseModel):
         pipeline like any value (it is monotone); the marginal likelihood becomes the Laplace approximation of the Tobit
         likelihood (``dgp_laplace_fit_step``) and every product that reads the held factorisation sees the Laplace
         posterior.  None or no censored row: the plain fit, bit for bit.  ``laplace_status_`` keeps the last mode search's
-        (Newton iterations, final max |df|, halvings, capped rows)."""
+        (Newton iterations, final max |df|, halvings, capped rows).
+
+        ``target_upper``: array-like aligned with ``target`` (data space), the upper ends of INTERVAL-censored rows.  A row
+        with the code 2 in ``censored`` says that the truth lies between its ``target`` value and its ``target_upper`` value
+        (EGRET's ConcLow / ConcHigh; ``loadest_gp.censoring_from_bounds`` builds the three arguments from such a pair); the
+        code 2 is accepted only together with ``target_upper``, which is read on those rows alone.  The upper ends pass
+        through the target pipeline AS FITTED ON ``target`` (it is never refitted on them); a decreasing pipeline swaps a
+        bracket's ends, which are then sorted in model space.  A bracket narrower than 1e-6 sigma (the row's noise standard
+        deviation in model space) is taken as an observation at its midpoint: the likelihood of so narrow a bracket is the
+        Gaussian density there times the width, so this shifts the reported NLL by the constant -sum log(width_i) over
+        those rows and leaves the mode and every gradient unchanged to O(width^2 / sigma^2)."""
         trained = bool(getattr(self, "model", None) is not None and getattr(self, "likelihood", None) is not None
                        and self.is_fitted)
         from_checkpoint = trained and self._resume_info is not None
@@ -512,7 +605,9 @@ class MarginalHIP(BaseModel):
         if not restore:
             self._fresh_model(x, y, unc)
         if censored is not None or not restore:
-            self._set_censoring(censored, y.shape[0])
+            y = self._set_censoring(censored, y.shape[0], target_upper, y)
+        elif getattr(self, "_upper_host", None) is not None:  # a resumed fit keeps its brackets
+            y = self._set_censoring(self._censor_host, y.shape[0], self._upper_host, y)
         self._setup_device(x, y)
         if self._censor is not None:
             self._censor.f = None
@@ -656,7 +751,7 @@ class MarginalHIP(BaseModel):
                     cs = spec.censored
                     out, f_hat, stat = self._plan.laplace_factorize(
                         spec.theta, self._train_y, spec.mean.contiguous(), spec.noise.contiguous(), cs.side, f=cs.f,
-                        maxit=cs.maxit, tol=cs.tol)
+                        maxit=cs.maxit, tol=cs.tol, **cs.kwargs())
                     cs.update(f_hat, stat)
                     self.laplace_status_ = cs.status
                 else:

@@ -83,8 +83,9 @@ class _LaplaceNLL(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, plan, theta, y, mean, noise, state, shortcut, *params):
+        extra = state.kwargs() if hasattr(state, "kwargs") else {}  # the upper ends of bracketed rows (side 2), if any
         out, dr, f_hat, stat = plan.laplace_fit_step(theta, y, mean.detach().contiguous(), noise.detach().contiguous(), state.side,
-                                                     f=state.f, maxit=state.maxit, tol=state.tol)
+                                                     f=state.f, maxit=state.maxit, tol=state.tol, **extra)
         host = out.to("cpu", torch.float64)
         info = int(host[_lib.OUT_INFO].item())
         if info != 0:

@@ -12,6 +12,7 @@ The module tree (and so every ``state_dict`` key) is the reference's: ``covar_mo
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from .. import gp
@@ -22,6 +23,39 @@ from ..gp.priors import GammaPrior, HalfNormalPrior, NormalPrior
 from ..pipeline import LogStandardPipeline, TimePipeline
 
 MODEL_SPACE_NOISE = 0.1 ** 2  # fixed observation variance (gpytorch.py:51-54)
+
+
+def censoring_from_bounds(low, high):
+    """A record of (low, high) pairs -- EGRET's ``ConcLow`` / ``ConcHigh``: the truth of sample i lies in [low_i, high_i] --
+    as the three arguments of ``LoadestGP.fit``: -> (target, censored, target_upper).  Per row:
+
+        low missing (NaN) or <= 0          censored -1 at high   (a non-detect: "< high")
+        high missing (NaN) or infinite     censored +1 at low    ("> low")
+        low == high                        observed
+        otherwise                          censored 2, target = low, target_upper = high   (the truth lies in the bracket)
+
+    ``target`` has the type of ``high`` (a labelled array keeps its dims, coords, name and attrs; anything else gives a
+    numpy array); ``censored`` is an int32 array and ``target_upper`` a float64 array that is NaN off the bracketed rows
+    (None when there is no bracketed row).  A row with both ends missing, or with low > high, is an error."""
+    lo = np.asarray(getattr(low, "values", low), dtype=np.float64).reshape(-1)
+    hi = np.asarray(getattr(high, "values", high), dtype=np.float64).reshape(-1)
+    if lo.shape != hi.shape:
+        raise ValueError(f"low and high must align: {lo.shape} against {hi.shape}")
+    below = np.isnan(lo) | (lo <= 0.0)
+    above = np.isnan(hi) | np.isposinf(hi)
+    if np.any(below & above):
+        raise ValueError("a row has neither a lower nor an upper bound")
+    both = ~below & ~above
+    if np.any(both & (lo > hi)):
+        raise ValueError("a row has low > high")
+    bracket = both & (lo < hi)
+    censored = np.where(below, -1, np.where(above, 1, np.where(bracket, 2, 0))).astype(np.int32)
+    values = np.where(below, hi, lo)
+    upper = np.where(bracket, hi, np.nan) if bracket.any() else None
+    template = high if hasattr(high, "dims") else (low if hasattr(low, "dims") else None)
+    if template is not None:
+        values = type(template)(values, dims=template.dims, coords=template.coords, name=template.name, attrs=template.attrs)
+    return values, censored, upper
 
 
 def loadest_covariance(n_columns: int):

@@ -268,7 +268,8 @@ def aggregate_many(models, covariates_list, weights_list, freq="YE", ci=0.95, pr
                 mdl.model.prepare_eval(x, xn)
             name, theta_fn = lower(mdl.model.covar_module, x.shape[1])
             sites.append(dict(mode=mode, s=s, t=t, groups=groups, labels=labels, n_points=n_points, w=w, x=x, xn=xn,
-                              y=torch.tensor(mdl.dm.y, dtype=dtype), name=(name, x.shape[1]),
+                              y=torch.tensor(mdl.model_space_targets() if hasattr(mdl, "model_space_targets") else mdl.dm.y,
+                                             dtype=dtype), name=(name, x.shape[1]),
                               theta=theta_fn().detach().to(torch.float64), prior=mdl.model.prior_mean(x).detach().to(dtype),
                               noise=mdl.likelihood.train_noise(torch.device("cpu"), dtype).detach().reshape(-1),
                               xmean=mdl.model.prior_mean(xn).detach().to(dtype),

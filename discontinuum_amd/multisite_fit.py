@@ -103,8 +103,9 @@ class _BatchedCensor:
     """The censoring of a batch: ``side`` (B, n) device int32 (0 in the unused slots), the latest modes ``f`` (B, n) of the
     Laplace approximation (None = cold start from the prior means) and the per-site ``status`` of the last mode search."""
 
-    def __init__(self, side, maxit, tol):
+    def __init__(self, side, maxit, tol, upper=None):
         self.side, self.f, self.status, self.maxit, self.tol = side, None, None, int(maxit), float(tol)
+        self.upper = upper  # (B, n) device, model space: the upper ends of the rows of side 2, or None without such a row
 
 
 def _laplace_step(plan, theta, y, mean, noise, state):
@@ -115,9 +116,10 @@ def _laplace_step(plan, theta, y, mean, noise, state):
     pick = (lambda v: v[0].contiguous()) if one else (lambda v: v)
     mean = mean.contiguous()
     warm = mean if state.f is None else state.f
+    extra = {} if getattr(state, "upper", None) is None else {"upper": pick(state.upper)}
     try:
         out, _dr, f_hat, stat = plan.laplace_fit_step(pick(theta), pick(y), pick(mean), pick(noise), pick(state.side), f=pick(warm),
-                                                      maxit=state.maxit, tol=state.tol)
+                                                      maxit=state.maxit, tol=state.tol, **extra)
     except _lib.DGPError as e:
         if e.code != _lib.E_NOCONV:
             raise
@@ -477,16 +479,20 @@ def _refuse_censored_records(datasets, what):
                                       "through the censored= argument (one entry per site)")
 
 
-def _site_sides(models, censored, sizes, what):
-    """``censored`` (None, or one entry per site: None, a boolean mask, or -1 / 0 / +1) as a list of int32 side vectors / None,
-    through ``engines.hip.censor_sides``; refuses what the censored fit does not serve."""
+def _site_sides(models, censored, sizes, what, target_upper=None):
+    """``censored`` (None, or one entry per site: None, a boolean mask, or -1 / 0 / +1; 2 for a site with a ``target_upper``
+    entry) as a list of int32 side vectors / None, through ``engines.hip.censor_sides``; refuses what the censored fit does not
+    serve."""
     from .engines.hip import censor_sides
 
+    if target_upper is not None and (censored is None or len(target_upper) != len(models)):
+        raise ValueError(f"{what}: target_upper needs one entry per site (None for a site without bracketed rows) and censored=")
     if censored is None:
         return [None] * len(models)
     if len(censored) != len(models):
         raise ValueError(f"{what}: censored needs one entry per site (None for a site without censored rows)")
-    sides = [censor_sides(c, nb) for c, nb in zip(censored, sizes)]
+    uppers = [None] * len(models) if target_upper is None else target_upper
+    sides = [censor_sides(c, nb, bracketed=u is not None) for c, nb, u in zip(censored, sizes, uppers)]
     if any(sd is not None for sd in sides):
         for m in models:
             if hasattr(m.model, "powerlaw") or getattr(m.likelihood, "second_noise_covar", None) is not None:
@@ -502,7 +508,7 @@ def fit_many(models, datasets, iterations: int = 100, learning_rate: float = 0.0
              monotonic_penalty_weight: float = 0.0, grid_size: int = 64, monotonic_penalty_interval: int = 1,
              resume: FitManyState | None = None, return_state: bool = False, generator: torch.Generator | None = None,
              optimizer: str = "adam", penalty_callback=None, penalty_weight: float = 0.0, site_seeds=None,
-             closed_form: bool = True, censored=None, _penalty_uniforms=None):
+             closed_form: bool = True, censored=None, target_upper=None, _penalty_uniforms=None):
     """Fit ``models[i]`` to ``datasets[i] = (covariates, target[, target_unc])`` for all i at once.  Returns the
     per-site final objectives (a float64 tensor) -- with ``return_state=True`` the pair (objectives, ``FitManyState``);
     the models are updated in place (``is_fitted``, parameters, device state).
@@ -544,7 +550,13 @@ def fit_many(models, datasets, iterations: int = 100, learning_rate: float = 0.0
     loadest-gp, fixed noise, float64 only (``NotImplementedError`` otherwise).  None, or no censored row: the plain path, bit for
     bit.  ``resume`` cold-starts the modes (``FitManyState`` does not carry them): the mode is a function of the
     hyperparameters and the warm start only saves Newton iterations, so a resumed censored run equals the uninterrupted one to
-    the mode tolerance, not bitwise."""
+    the mode tolerance, not bitwise.
+
+    ``target_upper``: a sequence with one entry per site -- None, or the upper ends of that site's INTERVAL-censored rows (data
+    space, aligned with its target; read on the rows whose ``censored`` code is 2), as ``MarginalHIP.fit(target_upper=...)``: the
+    same pipeline rule (the site's target pipeline as fitted on its target), the same sorting of the ends under a decreasing
+    transform and the same midpoint rule for brackets narrower than 1e-6 sigma.  The device step is then ONE batched
+    ``dgp_laplace_interval_fit_step``; afterwards every model carries its brackets like after its own ``fit``."""
     if site_seeds is not None and len(site_seeds) != len(models):
         raise ValueError("site_seeds needs one seed per model")
     _refuse_censored_records(datasets, "fit_many")
@@ -577,7 +589,24 @@ def fit_many(models, datasets, iterations: int = 100, learning_rate: float = 0.0
                                       "train this model with its own fit()")
     sizes = [x.shape[0] for x in xs]
     n = max(sizes)
-    sides = _site_sides(models, censored, sizes, "fit_many")
+    sides = _site_sides(models, censored, sizes, "fit_many", target_upper)
+    # bracketed rows: every model parses its own (pipeline, swap and midpoint rules of MarginalHIP._set_censoring); the batch runs
+    # on the sides, targets and upper ends the models then hold
+    ys_given, upper_all = list(ys), None
+    if target_upper is not None and any(sd is not None and (sd == 2).any() for sd in sides):
+        upper_all = torch.full((B, n), float("nan"), dtype=dtype)
+        for b, m in enumerate(models):
+            if sides[b] is None or not (sides[b] == 2).any():
+                continue
+            ys[b] = m._set_censoring(censored[b], sizes[b], target_upper[b], ys_given[b])
+            if m._censor is None:  # every bracket of the site was narrower than the midpoint rule's width
+                sides[b] = None
+                continue
+            sides[b] = m._censor.side.cpu().numpy()
+            if m._censor.upper is not None:
+                upper_all[b, : sizes[b]] = m._censor.upper.cpu()
+        if not bool(torch.isfinite(upper_all).any()):
+            upper_all = None
     plan = GPPlan(hosts[0].name, n, d, dtype=dtype, device=device, lookahead=1 if B > 1 else 2, batch=B)
     if B > 1:
         plan.set_site_sizes(sizes)
@@ -587,7 +616,8 @@ def fit_many(models, datasets, iterations: int = 100, learning_rate: float = 0.0
         for b, sd in enumerate(sides):
             if sd is not None:
                 side_all[b, : sizes[b]] = torch.as_tensor(sd, dtype=torch.int32)
-        cstate = _BatchedCensor(side_all.to(device).contiguous(), models[0].laplace_maxit, models[0].laplace_tol)
+        cstate = _BatchedCensor(side_all.to(device).contiguous(), models[0].laplace_maxit, models[0].laplace_tol,
+                                upper=None if upper_all is None else upper_all.to(device).contiguous())
 
     def slots(ts):
         out = torch.zeros((B, n) + tuple(ts[0].shape[1:]), dtype=dtype)
@@ -847,7 +877,8 @@ def fit_many(models, datasets, iterations: int = 100, learning_rate: float = 0.0
     for b, (m, own) in enumerate(zip(models, own_params)):
         _hand_back(m, own, {k: v[b] for k, v in params.items()}, int(last_iteration[b]), xs[b], ys[b])
         if censored is not None:
-            _hand_back_censoring(m, sides[b], sizes[b], cstate, b)
+            _hand_back_censoring(m, censored[b] if target_upper is not None else sides[b], sizes[b], cstate, b,
+                                 None if target_upper is None else target_upper[b], ys_given[b])
     if return_state:
         state = FitManyState(params={k: v.detach().clone() for k, v in params.items()}, m1=m1, m2=m2, step=step, lr=lr, best=best,
                              num_bad=num_bad, cooldown=cooldown, es_best=es_best, stale=stale, live=live, last_obj=last_obj,
@@ -881,10 +912,13 @@ def _hand_back(m, own, values, last_iteration, tx, ty):
     m.is_fitted = True
 
 
-def _hand_back_censoring(m, side, nb, cstate, b):
-    """The site's censoring onto its model, as ``fit(censored=)`` leaves it: the side vector, and -- from a batch's state -- the
-    last mode (the warm start of the model's own cache build) and the last mode search's status."""
-    m._set_censoring(side, nb)
+def _hand_back_censoring(m, side, nb, cstate, b, target_upper=None, y=None):
+    """The site's censoring onto its model, as ``fit(censored=)`` leaves it: the side vector (with ``target_upper`` and the
+    model-space targets ``y`` as given: the brackets), and -- from a batch's state -- the last mode (the warm start of the model's
+    own cache build) and the last mode search's status."""
+    y_fit = m._set_censoring(side, nb, target_upper, y)
+    if y_fit is not None and getattr(m, "_pending_device", None) is not None:
+        m._pending_device = (m._pending_device[0], y_fit)  # the targets the fit ran on (a bracket's lower end or midpoint)
     if m._censor is not None and cstate is not None and cstate.f is not None:
         m._censor.update(cstate.f[b, :nb].clone(), cstate.status[b])
         m.laplace_status_ = m._censor.status
@@ -894,7 +928,8 @@ def _hand_back_censoring(m, side, nb, cstate, b):
 STOP_BUDGET, STOP_EARLY, STOP_FAILED = 0.0, 1.0, 2.0
 
 
-def fit_many_distributed(models, datasets, group=None, load: str = "all", seed: int | None = 0, censored=None, **kw):
+def fit_many_distributed(models, datasets, group=None, load: str = "all", seed: int | None = 0, censored=None, target_upper=None,
+                         **kw):
     """``fit_many`` over the ranks of a ``torch.distributed`` process group (one rank per GPU).
 
     Every rank passes the SAME ``models`` / ``datasets`` lists (like the reference's ``iterdata`` list,
@@ -919,6 +954,8 @@ def fit_many_distributed(models, datasets, group=None, load: str = "all", seed: 
 
     ``censored``: as in ``fit_many``, one entry per site of the WHOLE list; it is sliced by ``site_partition`` like the datasets,
     and a rank that loads a site it does not own also sets that site's censoring on its model.  The gathered table is unchanged.
+    ``target_upper``: as in ``fit_many`` (the upper ends of bracketed rows, one entry per site of the whole list), sliced and
+    handed back the same way.
 
     Without an initialised process group (or world 1) this is ``fit_many`` plus the table.  ``resume`` / ``return_state``
     are per-rank notions and not supported here.  Returns ``(objectives (n_sites,), table (n_sites, P_raw + 3))``, float64,
@@ -936,6 +973,8 @@ def fit_many_distributed(models, datasets, group=None, load: str = "all", seed: 
         raise ValueError("fit_many_distributed needs one (covariates, target) pair per model")
     if censored is not None and len(censored) != len(models):
         raise ValueError("fit_many_distributed: censored needs one entry per site (None for a site without censored rows)")
+    if target_upper is not None and (censored is None or len(target_upper) != len(models)):
+        raise ValueError("fit_many_distributed: target_upper needs one entry per site and censored=")
     n_sites = len(models)
     active = dist.is_available() and dist.is_initialized()
     world = dist.get_world_size(group) if active else 1
@@ -948,7 +987,8 @@ def fit_many_distributed(models, datasets, group=None, load: str = "all", seed: 
         try:
             objs, state = fit_many([models[i] for i in mine], [datasets[i] for i in mine], return_state=True,
                                    site_seeds=None if seed is None else [seed + i for i in mine],
-                                   censored=None if censored is None else [censored[i] for i in mine], **kw)
+                                   censored=None if censored is None else [censored[i] for i in mine],
+                                   target_upper=None if target_upper is None else [target_upper[i] for i in mine], **kw)
         except Exception as e:  # noqa: BLE001 -- reported after the collective, on every rank
             error = e
 
@@ -1006,8 +1046,9 @@ def fit_many_distributed(models, datasets, group=None, load: str = "all", seed: 
                 o += w
             _hand_back(models[i], own, values, int(table[i, P + 1]) - 1, tx, ty)
             if censored is not None:
-                _hand_back_censoring(models[i], _site_sides([models[i]], [censored[i]], [tx.shape[0]], "fit_many_distributed")[0],
-                                     tx.shape[0], None, 0)
+                up = None if target_upper is None else target_upper[i]
+                _site_sides([models[i]], [censored[i]], [tx.shape[0]], "fit_many_distributed", None if up is None else [up])
+                _hand_back_censoring(models[i], censored[i], tx.shape[0], None, 0, up, ty)
     return table[:, P].clone(), table
 
 
@@ -1030,8 +1071,12 @@ def censored_cache_build(plan, models, theta, ys, means, noises, sizes, n):
     start = slots([mu if c is None or c.f is None else c.f for c, mu in zip(cens, means)])
     first = next(c for c in cens if c is not None)
     one = (lambda v: v[0].contiguous()) if B == 1 else (lambda v: v)
+    extra = {}
+    if any(c is not None and c.upper is not None for c in cens):  # bracketed rows (side 2) somewhere: their upper ends
+        extra["upper"] = one(slots([torch.full((nb,), float("nan"), dtype=dtype) if c is None or c.upper is None else c.upper
+                                    for c, nb in zip(cens, sizes)], float("nan")))
     out, f_hat, stat = plan.laplace_factorize(one(theta), one(slots(ys)), one(mean), one(slots(noises, 1.0)), one(side), f=one(start),
-                                              maxit=first.maxit, tol=first.tol)
+                                              maxit=first.maxit, tol=first.tol, **extra)
     f_hat, stat = f_hat.reshape(B, n), ((tuple(stat),) if B == 1 else stat)
     for b, (m, c) in enumerate(zip(models, cens)):
         if c is not None:
@@ -1061,7 +1106,7 @@ def predict_many(models, covariates_list):
             m.model.eval()
             m.likelihood.eval()
             x = torch.tensor(m.dm.X, dtype=dtype)
-            y = torch.tensor(m.dm.y, dtype=dtype)
+            y = torch.tensor(m.model_space_targets() if hasattr(m, "model_space_targets") else m.dm.y, dtype=dtype)
             xn = torch.tensor(m.dm.Xnew(cov), dtype=dtype)
             if hasattr(m.model, "prepare_eval"):
                 m.model.prepare_eval(x, xn)  # data-dependent clamps see [X; X*]

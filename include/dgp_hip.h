@@ -274,6 +274,41 @@ int dgp_laplace_batched_fit_step(dgp_plan* plan, const double* theta_host, const
 int dgp_laplace_batched_factorize(dgp_plan* plan, const double* theta_host, const void* y_dev, const void* mean_dev,
                                   const void* noise_dev, const int32_t* side_dev, void* f_dev, int maxit, double tol, void* work_dev,
                                   size_t work_bytes, void* out_dev, double* stat_host, void* stream);
+/* INTERVAL-CENSORED OBSERVATIONS: a fourth row kind, side 2 -- the truth of row i lies in [y_i, upper_i] (model space,
+ * upper_i > y_i; EGRET's ConcLow / ConcHigh).  With za = (y_i - f_i) / sigma_i, zb = (upper_i - f_i) / sigma_i, Delta = zb - za,
+ * P = Phi(zb) - Phi(za), ra = phi(za) / P, rb = phi(zb) / P:
+ *   log p_i = log P,   g_i = (ra - rb) / sigma_i,   W_i v_i = zb rb - za ra + (ra - rb)^2   in (0, 1],
+ *   d3_i = { ra (za^2 - 1) - rb (zb^2 - 1) - (ra - rb)(za ra - zb rb) + 2 (ra - rb) W_i v_i } / sigma_i^3
+ * i.e. sigma g, 1 - W v and sigma^3 d3 are the mean, the variance and the third central moment of a standard normal truncated
+ * to [za, zb].  log P is concave in f, so Newton's search, the pseudo-data identity, the NLL correction (with log P in place of
+ * log Phi) and the implicit gradient sweep are those of the one-sided rows above, unchanged.
+ * Regimes (none of the formulas can be evaluated as written: P underflows and cancels in a tail, and for Delta << 1 W v is a sum
+ * of O(1 / Delta^2) terms).  A bracket whose centre c = (za + zb) / 2 lies right of 0 is reflected; then, with h = Delta / 2,
+ *   narrow    h <= 1 and |c| h <= 2: P = h phi(c) I with I = int_-1^1 exp(-c h t - h^2 t^2 / 2) dt and the moments of that tilted
+ *             density by a fixed 12-point Gauss-Legendre rule, central moments about the computed mean (no cancellation as
+ *             Delta -> 0: W v -> 1 - Delta^2 / 12)
+ *   tail      zb <= 0: P = phi(zb) [M(zb) - rho M(za)], M = Phi / phi through erfcx, rho = exp(Delta c) <= e^-2 through expm1
+ *   straddle  za < 0 < zb: P = [erf(zb / sqrt 2) + erf(-za / sqrt 2)] / 2, a sum of positive terms
+ * Guards: W v is clamped to <= 1; the capping rule is that of the one-sided rows (W v < 1e-12: n~ = 1e12 v, d3 = 0).
+ * Measured against a 600-digit fixture on za in [-40, 38], Delta in [1e-6, 30], relative to max(1, |value|): see DESIGN.md.
+ * The two entries serve EVERY float64 plan (single-site, batched, ragged); their arguments, workspace query
+ * (dgp_laplace_batched_workspace_bytes), stat_host layout, passes and error rules are dgp_laplace_batched_*'s, plus
+ *   upper_dev   [B][n] doubles, read only on the rows of side 2 (anything elsewhere, NaN included); may be null when no row has
+ *               side 2.
+ * DGP_E_ARG in addition: a row of side 2 with a null upper_dev, or a BAD BRACKET (upper NaN, infinite or not above y) -- both
+ * reported after the first pass, as bad side values are, the text naming the first such site.  With no row of side 2 they launch
+ * exactly what dgp_laplace_batched_* launch and give the same bits in every output and plan buffer.  The entries above are
+ * unchanged: for them 2 stays a bad side value. */
+int dgp_laplace_interval_fit_step(dgp_plan* plan, const double* theta_host, const void* y_dev, const void* mean_dev,
+                                  const void* noise_dev, const int32_t* side_dev, const void* upper_dev, void* f_dev, int maxit,
+                                  double tol, void* work_dev, size_t work_bytes, void* out_dev, void* dr_dev, double* stat_host,
+                                  void* stream);
+int dgp_laplace_interval_factorize(dgp_plan* plan, const double* theta_host, const void* y_dev, const void* mean_dev,
+                                   const void* noise_dev, const int32_t* side_dev, const void* upper_dev, void* f_dev, int maxit,
+                                   double tol, void* work_dev, size_t work_bytes, void* out_dev, double* stat_host, void* stream);
+/* out [4][count] = log P, sigma g, W v, sigma^3 d3 of the brackets [za, za + Delta]: the pointwise functions of the two entries
+ * above, for tests.  za_dev, delta_dev: count doubles on the device (Delta > 0). */
+int dgp_debug_interval_terms(const double* za_dev, const double* delta_dev, int64_t count, double* out_dev, void* stream);
 /* out [4][count] = log Phi(z), h = phi(z) / Phi(z), h (z + h), h [1 - (z + h)(z + 2 h)]: the pointwise functions of the
  * entries above, for tests.  z_dev: count doubles on the device. */
 int dgp_debug_censored_terms(const double* z_dev, int64_t count, double* out_dev, void* stream);
