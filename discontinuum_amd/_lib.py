@@ -17,6 +17,7 @@ MODEL_LOADEST, MODEL_RATING = 0, 1
 OUT_NLL, OUT_QUAD, OUT_LOGDET, OUT_INFO, OUT_DTHETA, OUT_SUM_DR, OUT_DR_W0, OUT_SUM_DNOISE, OUT_LEN = 0, 1, 2, 3, 4, 28, 29, 31, 32
 BUF_XT, BUF_A, BUF_T, BUF_S, BUF_Z, BUF_ALPHA = range(6)
 BUF_INFO, BUF_SCAL = 6, 7
+LCV_PLANE_NAMES = ("mu", "var", "lpd", "pit_lower", "pit_upper", "dlp", "tilt")  # DGP_LCV_*: dgp_laplace_cross_validate's planes
 OPT_LAUUM64_MAX_TILES, OPT_SYRK_SLOTS, OPT_TRTRI_SMALL, OPT_REFINE, OPT_SYRK_ORDER, OPT_LAUUM_ORDER, OPT_CHAIN_YIELD, OPT_FUSED_GRAD, OPT_GROUP_GEMM = range(9)
 OPT_POTRF_SCHEDULE, OPT_POTRF_SWEEP, OPT_POTRF_SOLVE, OPT_POTRF_OVERLAP, OPT_POTRF_SLOTS, OPT_POTRF_TAIL, OPT_POTRF_TAIL_SWEEP = range(9, 16)
 TIME_GRAM, TIME_POTRF, TIME_SYRK_SUM, TIME_SYRK_N, TIME_TRTRI, TIME_LAUUM, TIME_SOLVE, TIME_GRAD, TIME_SYRK_FLOP, TIME_COUNT = range(10)
@@ -112,6 +113,8 @@ SIGNATURES = {
     "dgp_debug_bvn_excess": (_i, [_vp, _vp, _vp, _i64, _vp, _vp]),
     "dgp_cross_validate_workspace_bytes": (_sz, [_vp, _i, _i64]),
     "dgp_cross_validate": (_i, [_vp, _vp, _vp, _i, _i64, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "dgp_laplace_cross_validate_workspace_bytes": (_sz, [_vp, _i, _i64]),
+    "dgp_laplace_cross_validate": (_i, [_vp, _dp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i64, C.c_double, _vp, _sz, _vp, _vp, _vp]),
     "dgp_fisher_workspace_bytes": (_sz, [_vp, _i]),
     "dgp_fisher": (_i, [_vp, _dp, _vp, _i, _vp, _sz, _vp, _vp]),
     "dgp_predict_sensitivity_workspace_bytes": (_sz, [_vp, _i64, _i, _i]),

@@ -446,6 +446,48 @@ class GPPlan:
             )
         return resid, var, lpd, info
 
+    def laplace_cross_validate(self, theta, y, mean, noise, side, f, groups, upper=None, shift=0.0, max_group=None):
+        """Cross-validation of a CENSORED fit by Laplace cavity folds (``dgp_laplace_cross_validate``), from the factorisation
+        of the pseudo-data system that ``laplace_factorize`` / ``laplace_fit_step`` left in the plan; no fold is refitted.
+        ``y`` / ``mean`` / ``noise`` / ``side`` / ``upper``: what the fit was given; ``f``: the mode it returned; ``groups`` /
+        ``max_group``: as for ``cross_validate``.  -> dict of (n,) fp64 tensors ``mu`` / ``var`` (the held-out predictive of
+        the OBSERVATION, as ``cross_validate``'s y - resid / var), ``lpd`` (pointwise: the Gaussian density of an observed
+        row, the probability of a censored row's bracket), ``pit_lower`` / ``pit_upper``, ``dlp`` (d lpd / d mu) and ``tilt``
+        (log of the bracket's probability with both ends shifted by -``shift`` sd, minus lpd; 0 on observed rows) -- all 0
+        where ``groups`` is -1 -- plus ``info`` (ngroups,) int32.  The pseudo-data of the rows that stay are held at the
+        full-data mode: an approximation on top of Laplace's.  float64 single-site plans only."""
+        if self.batch != 1:
+            raise NotImplementedError("laplace_cross_validate: batched plans are not supported (validate each site on its own plan)")
+        if self.dtype != torch.float64:
+            raise ValueError("laplace_cross_validate: censored fits need a float64 single-site plan")
+        for t, what in ((y, "y"), (mean, "mean"), (noise, "noise"), (f, "f")) + (() if upper is None else ((upper, "upper"),)):
+            self._check_vec(t, what)
+        if not (torch.is_tensor(side) and side.is_cuda and side.dtype == torch.int32 and side.is_contiguous() and side.numel() == self.n):
+            raise ValueError(f"side must be a contiguous int32 CUDA tensor with {self.n} elements")
+        th = _theta_array(theta, self.ntheta)
+
+        def launch(order, start, ngroups, mg):
+            need = int(self.lib.dgp_laplace_cross_validate_workspace_bytes(self._h, ngroups, mg))
+            if need == 0:
+                raise ValueError(f"bad size: ngroups = {ngroups}, max_group = {mg} (both in 1..n)")
+            with torch.cuda.device(self.device):
+                work = self._work_area("_lcv_ws", need, "cross-validation of a censored fit")
+                order = order.to(self.device).contiguous()
+                start = start.to(self.device).contiguous()
+                out = torch.empty((len(_lib.LCV_PLANE_NAMES), self.n), dtype=torch.float64, device=self.device)
+                info = torch.empty(ngroups, dtype=torch.int32, device=self.device)
+                _lib.check(
+                    self.lib.dgp_laplace_cross_validate(self._h, th, _ptr(y), _ptr(mean), _ptr(noise), _ptr(side), _ptr(upper), _ptr(f),
+                                                        _ptr(order), _ptr(start), ngroups, mg, float(shift), work, need, _ptr(out),
+                                                        _ptr(info), _stream()),
+                    "dgp_laplace_cross_validate",
+                )
+            res = {name: out[k] for k, name in enumerate(_lib.LCV_PLANE_NAMES)}
+            res["info"] = info
+            return res
+
+        return cross_validate_folds(self, groups, launch, max_group)
+
     # ------------------------------------------------------------------ Fisher information of the hyperparameters
     def fisher(self, theta, diag=None, max_bytes: int | None = None):
         """Exact Fisher information F_ab = 1/2 tr(K^^-1 D_a K^^-1 D_b) of the hyperparameters at the factorisation the plan

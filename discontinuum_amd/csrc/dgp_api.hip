@@ -1736,6 +1736,48 @@ int dgp_cross_validate(dgp_plan* p, const int32_t* order, const int32_t* start, 
   return wrap(rc, "dgp_cross_validate");
 }
 
+static bool lcv_plan_ok(const dgp_plan* p) { return p && p->dtype == DGP_F64 && p->B == 1; }
+size_t dgp_laplace_cross_validate_workspace_bytes(const dgp_plan* p, int ngroups, int64_t max_group) {
+  if (!lcv_plan_ok(p) || !cv_sizes_ok(p, ngroups, max_group)) return 0;
+  return laplace_cv_layout(p->N, p->n, ngroups, max_group).total;
+}
+
+int dgp_laplace_cross_validate(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise, const int32_t* side,
+                               const void* upper, const void* f, const int32_t* order, const int32_t* start, int ngroups,
+                               int64_t max_group, double shift, void* work, size_t work_bytes, double* out, int32_t* info, void* stream) {
+  const char* where = "dgp_laplace_cross_validate";
+  if (!p) return fail(DGP_E_ARG, "null plan");
+  if (!lcv_plan_ok(p))
+    return fail(DGP_E_ARG, "dgp_laplace_cross_validate: needs a float64 single-site plan (fp32 and batched plans are not supported)");
+  if (!theta || !y || !mean || !noise || !side || !f || !order || !start || !out || !info || !(shift == shift))
+    return fail(DGP_E_ARG, "dgp_laplace_cross_validate: null argument (f_dev included) or a NaN shift");
+  if (!cv_sizes_ok(p, ngroups, max_group))
+    return fail(DGP_E_ARG, "dgp_laplace_cross_validate: bad size (1 <= ngroups <= n, 1 <= max_group <= n)");
+  DGP_CHECK_PLAN(p);
+  if (!p->have_factor)
+    return fail(DGP_E_STATE, "dgp_laplace_cross_validate: no factorisation in the plan (call dgp_laplace_factorize or dgp_laplace_fit_step)");
+  if (!work || work_bytes < dgp_laplace_cross_validate_workspace_bytes(p, ngroups, max_group))
+    return fail(DGP_E_WORKSPACE, "dgp_laplace_cross_validate: workspace missing or too small");
+  if (((uintptr_t)work & 255) != 0) return fail(DGP_E_ARG, "dgp_laplace_cross_validate: the work area must be 256-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const LaplaceCvLayout L = laplace_cv_layout(p->N, p->n, ngroups, max_group);
+  // the terms pass and its read-back first: the staging slot below is not held across the synchronisation
+  int rc = laplace_cv_terms(p->N, (int)p->n, (const double*)y, (const double*)mean, (const double*)noise, side, (const double*)upper,
+                            (const double*)f, (char*)work, L, s);
+  if (rc == 0) {
+    PreSlot slot(p, s);
+    rc = laplace_cross_validate(p->model, p->d, (const double*)p->Xt, (const double*)p->Tm, (const double*)p->alpha, p->N, (int)p->n, theta,
+                                (const double*)y, (const double*)noise, side, (const double*)upper, (const double*)f, order, start,
+                                ngroups, shift, (char*)work, L, out, info, s, batch_of<double>(p), p->pre, slot.staging);
+  }
+  if (rc == LCV_E_SIDE_NO_UPPER)
+    return fail(DGP_E_ARG, "dgp_laplace_cross_validate: a row of side 2 needs upper_dev; other side values must be -1, 0 or +1");
+  if (rc == LCV_E_SIDE) return fail(DGP_E_ARG, "dgp_laplace_cross_validate: side values must be -1, 0, +1 or 2");
+  if (rc == LCV_E_BRACKET)
+    return fail(DGP_E_ARG, "dgp_laplace_cross_validate: bad bracket(s): a row of side 2 needs a finite upper above its y");
+  return wrap(rc, where);
+}
+
 #define DGP_FISHER_MAX_DIAG 8
 size_t dgp_fisher_workspace_bytes(const dgp_plan* p, int ndiag) {
   if (!p || ndiag < 0 || ndiag > DGP_FISHER_MAX_DIAG) return 0;

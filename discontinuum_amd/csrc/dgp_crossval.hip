@@ -29,7 +29,7 @@ namespace {
 
 constexpr double CV_HALF_LOG_2PI = 0.91893853320467274178;
 constexpr int CV_SLAB = 128;   // rows per slab of the leave-one-out pass
-constexpr int CV_SMALL = 64;   // largest group of the fused LDS kernel
+constexpr int CV_SMALL = CV_SMALL_GROUP;  // largest group of the fused LDS kernel
 constexpr int CV_MAX_CHUNK = 1024;
 
 // ---- leave-one-out: part[slab][j] = sum over the slab's rows k >= j of T[k][j]^2 ------------------------------------------------

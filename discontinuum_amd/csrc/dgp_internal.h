@@ -313,6 +313,7 @@ int slopes_reduce(int P, const T* V, const T* Ks, long N, long Mp, int m, const 
 // S = K^^-1 (null otherwise).  order [B][n] / start [B][ngroups + 1]: group g of a site = order[start[g] .. start[g + 1]); every
 // group has at most max_group members.  resid / var [B][n], lpd / info [B][ngroups], all double / int whatever T is; `work`:
 // cross_validate_workspace_bytes.  Reads T, S, alpha only.
+#define CV_SMALL_GROUP 64  // largest group of cross_validate's fused LDS route; larger groups take the block route (and its tap)
 size_t cross_validate_workspace_bytes(long N, int B, int ngroups, long max_group);
 // A TAP on the fold algebra for passes that need more of a fold than cross_validate's own results (dgp_influence.hip): the factor
 // M of G_B = M M^T, inverted.  Groups of up to 64 (the LDS route): M^-1 of fold g of a site is written lower, row-major, to
@@ -463,5 +464,26 @@ int gram_bilinear(int model, int d, const T* Xt, long N, int n, const double* th
 int debug_censored_terms(const double* z, long count, double* out, hipStream_t s);
 // out [4][count]: log P, sigma g, W v, sigma^3 d3 of the bracket [za, za + delta]
 int debug_interval_terms(const double* za, const double* delta, long count, double* out, hipStream_t s);
+
+// ---- dgp_censored_cv.hip: cross-validation of a censored fit by cavity folds, from the factorisation of the pseudo-data system
+// at the mode `f`.  fp64, one site.  out [LCV_PLANES][n] (== DGP_LCV_* of dgp_hip.h), info [ngroups]; folds as for cross_validate.
+enum { LCV_MU = 0, LCV_VAR, LCV_LPD, LCV_PLO, LCV_PHI, LCV_DLP, LCV_TILT, LCV_PLANES };
+// what the terms pass found, before any other launch: a bad side value (without / with `upper`), a bad bracket
+enum { LCV_E_SIDE_NO_UPPER = -100, LCV_E_SIDE = -101, LCV_E_BRACKET = -102 };
+struct LaplaceCvLayout {
+  size_t cen, resid, var, lpd, Ks, V, kss, mean, svar, part, cvw, ginv, h, total;  // byte offsets into the work area
+  long route_group, M;  // the bound handed to cross_validate (1: leave-one-out; else >= 65: its block route) and the block order
+  int C;                // folds per chunk of the block route
+};
+LaplaceCvLayout laplace_cv_layout(long N, long n, int ngroups, long max_group);
+// first the terms pass (W, g at f into the work area; reads its sums back, which synchronises the stream: 0, a HIP error or LCV_E_*),
+// then everything else, asynchronous on the stream
+int laplace_cv_terms(long N, int n, const double* y, const double* mean, const double* noise, const int* side, const double* upper,
+                     const double* f, char* work, const LaplaceCvLayout& L, hipStream_t s);
+int laplace_cross_validate(int model, int d, const double* Xt, const double* Tm, const double* alpha, long N, int n, const double* theta,
+                           const double* y, const double* noise, const int* side, const double* upper,
+                           const double* f, const int* order, const int* start, int ngroups, double shift, char* work,
+                           const LaplaceCvLayout& L, double* out, int* info, hipStream_t s, Batch bt, void* pre_scratch,
+                           void* pre_staging);
 
 }  // namespace dgp

@@ -364,9 +364,9 @@ class MarginalHIP(BaseModel):
     _CENSOR_REFUSAL = ("{what} is not available for a fit with censored observations: it reads the pseudo-data of the Laplace "
                        "approximation as if they were samples")
 
-    def _refuse_censored(self, what):
+    def _refuse_censored(self, what, hint=""):
         if getattr(self, "_censor", None) is not None:
-            raise NotImplementedError(self._CENSOR_REFUSAL.format(what=what))
+            raise NotImplementedError(self._CENSOR_REFUSAL.format(what=what) + hint)
 
     def _set_censoring(self, censored, n, target_upper=None, y=None):
         """Parse ``censored`` and ``target_upper`` (see ``fit``) and keep them on the engine; the side vector (and the upper
@@ -949,17 +949,19 @@ class MarginalHIP(BaseModel):
         return exceedance_probability(self, covariates, threshold, above=above, pred_noise=pred_noise)
 
     @is_fitted
-    def cross_validate(self, folds="loo", ci=0.95, return_folds=False):
+    def cross_validate(self, folds="loo", ci=0.95, return_folds=False, laplace=None):
         """Exact leave-one-out / leave-group-out cross-validation of the training observations at the fitted
         hyperparameters, from the factorisation the engine holds (no refit; ``dgp_cross_validate``).  ``folds``: "loo", a
         resample alias ("YE", "YE-SEP", "QE", "ME": one fold per period), an int k (contiguous blocks in time), ``("random",
         k, seed)`` or an explicit array of fold ids.  -> Dataset of ``observed`` / ``predicted`` / ``se`` / ``lower`` /
         ``upper`` / ``z`` / ``fold`` with ``elpd``, ``rmse``, ``coverage`` among its attributes; see
-        ``discontinuum_amd.validation.cross_validate``."""
+        ``discontinuum_amd.validation.cross_validate``.  A fit with censored observations is refused unless
+        ``laplace="cavity"`` asks for the Laplace cavity folds (``dgp_laplace_cross_validate``): approximate -- the pseudo-data
+        of the rows that stay are held at the full-data mode -- with a pointwise ``elpd``, PIT intervals for censored rows and
+        ``rmse`` / ``coverage`` over the observed rows only."""
         from ..validation import cross_validate
 
-        self._refuse_censored("cross_validate")
-        return cross_validate(self, folds=folds, ci=ci, return_folds=return_folds)
+        return cross_validate(self, folds=folds, ci=ci, return_folds=return_folds, laplace=laplace)
 
     @is_fitted
     def decompose(self, covariates, groups=None, ci=0.95, return_cov=False):

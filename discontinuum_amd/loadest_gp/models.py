@@ -177,14 +177,14 @@ class LoadestGPMarginalHIP(LoadestDataMixin, MarginalHIP):
                               replicates=replicates, given=given, freq=freq, sample_var=sample_var, max_bytes=max_bytes)
 
     @is_fitted
-    def flux_bias(self, cv=None, folds="loo"):
+    def flux_bias(self, cv=None, folds="loo", laplace=None):
         """WRTDS's flux bias statistic on the sampled days, (sum P - sum O) / sum P with O the observed and P the
         cross-validated mean concentration x flow; ``cv``: a Dataset from ``cross_validate`` (default: run it with
-        ``folds``).  See ``discontinuum_amd.validation.flux_bias``."""
+        ``folds``).  A fit with censored observations needs ``laplace="cavity"`` (approximate; O of a censored row is then
+        the expected concentration inside its bracket).  See ``discontinuum_amd.validation.flux_bias``."""
         from ..validation import flux_bias
 
-        self._refuse_censored("flux_bias")
-        return flux_bias(self, cv=cv, folds=folds)
+        return flux_bias(self, cv=cv, folds=folds, laplace=laplace)
 
     def flow_normalized_flux(self, daily, freq="YE", flow_window=None, ci=0.95, pred_noise=False, return_cov=False,
                              max_bytes=None):

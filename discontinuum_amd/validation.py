@@ -111,7 +111,122 @@ def model_space(model, groups):
     return y, mu, var, lpd
 
 
-def cross_validate(model, folds="loo", ci=0.95, return_folds=False):
+CAVITY_HINT = ('; pass laplace="cavity" for the cross-validation by Laplace cavity folds, which is approximate (the pseudo-data of '
+               "the rows that stay are held at the full-data mode)")
+
+
+def _wants_cavity(model, laplace, what):
+    """Validate the ``laplace`` keyword of ``what``; -> whether the call takes the cavity path.  A censored fit is refused
+    unless the caller asks for the approximation by name; on a fit without censoring ``"cavity"`` is the plain path."""
+    if laplace not in (None, "cavity"):
+        raise ValueError(f'laplace must be None or "cavity", got {laplace!r}')
+    if getattr(model, "_censor", None) is None:
+        return False
+    if laplace is None:
+        model._refuse_censored(what, hint=CAVITY_HINT)
+    return True
+
+
+def cavity_space(model, groups, shift=0.0):
+    """The planes of ``GPPlan.laplace_cross_validate`` for the fold ids ``groups`` of a censored fit, in model space, as a
+    dict of numpy arrays (``mu`` and ``var`` NaN where the observation is never held out), plus ``y``, ``side`` and ``upper``
+    (NaN off the bracketed rows) as the fit ran on them."""
+    if hasattr(model.model, "prepare_eval"):
+        model._factor_key = None
+    model._eval_ready()
+    groups = np.asarray(groups)
+    with torch.no_grad():
+        spec = model._prior()
+        cs = spec.censored
+        res = model._plan.laplace_cross_validate(model._factor_theta, model._train_y, spec.mean.contiguous(), spec.noise.contiguous(),
+                                                 cs.side, cs.f, torch.as_tensor(groups, dtype=torch.int64), upper=cs.upper,
+                                                 shift=float(shift))
+    out = {k: v.detach().cpu().numpy() for k, v in res.items()}
+    info = out.pop("info")
+    if (info != 0).any():
+        g = int(np.nonzero(info)[0][0])
+        raise NotPSDError(f"cross-validation: the held-out block of fold {g} is not positive definite (pivot {int(info[g])})")
+    held = groups >= 0
+    out["mu"] = np.where(held, out["mu"], np.nan)
+    out["var"] = np.where(held, out["var"], np.nan)
+    out["y"] = model._train_y.detach().to("cpu", torch.float64).numpy()
+    out["side"] = cs.side.detach().cpu().numpy().astype(np.int64)
+    n = out["y"].shape[0]
+    out["upper"] = np.full(n, np.nan) if cs.upper is None else np.where(out["side"] == 2, cs.upper.detach().cpu().numpy(), np.nan)
+    return out
+
+
+def _cross_validate_cavity(model, folds, ci, return_folds):
+    """``cross_validate`` of a fit with censored observations: see there."""
+    target = model.dm.data.target
+    time = np.asarray(target.coords["time"].values)
+    groups, labels = cv_folds(time, folds)
+    try:
+        mode, s, _t = target_transform(model.dm)
+    except NotImplementedError:
+        mode, s = None, 0.0
+    shift = s if mode == MODE_LOG else 0.0  # the tilt of the lognormal mean (flux_bias); 0: the tilt plane is not needed
+    cav = cavity_space(model, groups, shift)
+    y, mu, var, side = cav["y"], cav["mu"], cav["var"], cav["side"]
+    held = groups >= 0
+    plain = held & (side == 0)
+    sd = np.sqrt(var)
+    q = norm.ppf(1 - (1 - ci) / 2)
+    z = np.where(side == 0, (y - mu) / sd, np.nan)
+    observed = np.asarray(target.values, dtype=np.float64).reshape(-1)
+    upper_host = getattr(model, "_upper_host", None)
+    observed_upper = np.full(observed.shape, np.nan)
+    if upper_host is not None:
+        observed_upper = np.where(side == 2, np.asarray(upper_host, dtype=np.float64).reshape(-1), np.nan)
+    predicted = model.dm.y_t(mu)
+    attrs = dict(getattr(predicted, "attrs", {}) or {})
+    lower = np.asarray(model.dm.y_t(mu - q * sd).values).reshape(-1)
+    upper = np.asarray(model.dm.y_t(mu + q * sd).values).reshape(-1)
+    se = np.asarray(model.dm.error_pipeline.inverse_transform(var).values).reshape(-1)
+    inside = (observed >= lower) & (observed <= upper)
+    counts = np.bincount(groups[held], minlength=len(labels))
+    lpd = np.where(held, cav["lpd"], np.nan)
+    ds = Dataset(
+        {
+            "observed": ("time", observed, attrs),
+            "observed_upper": ("time", observed_upper, attrs),
+            "censored": ("time", side),
+            "predicted": ("time", np.asarray(predicted.values).reshape(-1), attrs),
+            "se": ("time", se, attrs),
+            "lower": ("time", lower, dict(attrs, ci=ci)),
+            "upper": ("time", upper, dict(attrs, ci=ci)),
+            "z": ("time", z),
+            "mu": ("time", mu),
+            "var": ("time", var),
+            "fold": ("time", groups),
+            "lpd": ("time", lpd),
+            "pit_lower": ("time", np.where(held, cav["pit_lower"], np.nan)),
+            "pit_upper": ("time", np.where(held, cav["pit_upper"], np.nan)),
+            "dlp": ("time", np.where(held, cav["dlp"], np.nan)),
+            "tilt": ("time", np.where(held, cav["tilt"], np.nan)),
+        },
+        coords={"time": time},
+        attrs={
+            "elpd": float(lpd[held].sum()),
+            "elpd_kind": "pointwise",
+            "rmse": float(np.sqrt(np.mean((y - mu)[plain] ** 2))) if plain.any() else float("nan"),
+            "coverage": float(inside[plain].mean()) if plain.any() else float("nan"),
+            "n_censored": int((side != 0).sum()),
+            "approximation": "laplace-cavity",
+            "tilt_shift": float(shift),
+            "n_folds": int((counts > 0).sum()),
+            "scheme": _scheme_name(folds),
+            "ci": ci,
+        },
+    )
+    if not return_folds:
+        return ds
+    fold_lpd = np.bincount(groups[held], weights=lpd[held], minlength=len(labels))
+    per_fold = Dataset({"lpd": ("fold", fold_lpd), "n_points": ("fold", counts)}, coords={"fold": labels})
+    return ds, per_fold
+
+
+def cross_validate(model, folds="loo", ci=0.95, return_folds=False, laplace=None):
     """Held-out predictions of every training observation of a fitted model (``cv_folds`` schemes), from the engine's own
     factorisation.  -> Dataset on the observations' ``time`` coordinate with ``observed``; ``predicted`` -- what
     ``predict`` would have returned for the observation had its fold been absent (through ``dm.y_t``; fitted transform
@@ -122,9 +237,23 @@ def cross_validate(model, folds="loo", ci=0.95, return_folds=False):
     them; ``fold``.  Attributes: ``elpd`` (sum of the folds' joint log predictive densities,
     model space), ``rmse`` (model space), ``coverage`` (share of the held-out observations inside their interval),
     ``n_folds``, ``scheme``.  ``return_folds``: also a Dataset of per-fold ``lpd`` / ``n_points`` on a ``fold`` coordinate
-    of the folds' labels.  See the module docstring for what is held fixed."""
+    of the folds' labels.  See the module docstring for what is held fixed.
+
+    A fit with CENSORED observations is refused (``NotImplementedError``) unless ``laplace="cavity"`` asks for the Laplace
+    cavity folds by name (``GPPlan.laplace_cross_validate``; on a fit without censoring the keyword changes nothing): the
+    fold's Gaussian sites are taken out of the Laplace posterior in closed form, no fold is refitted, and -- the
+    approximation -- the pseudo-data of the rows that stay are held at the full-data mode.  The Dataset then also has
+    ``observed_upper`` (NaN where there is none), ``censored`` (the codes -1 / 0 / +1 / 2), the pointwise ``lpd`` (the Gaussian
+    density of an observed row, the probability of a censored row's bracket), ``pit_lower`` / ``pit_upper`` (the
+    observation's probability integral transform, an interval for censored rows), ``dlp`` / ``tilt`` (what ``flux_bias``
+    needs for the expected concentration inside a bracket); ``z`` is NaN on censored rows; ``elpd`` is the sum of the
+    pointwise ``lpd`` (``elpd_kind="pointwise"``: the joint density of a fold with several censored rows is an orthant
+    probability and is not attempted); ``rmse`` and ``coverage`` run over the observed held-out rows only; ``n_censored``;
+    ``approximation="laplace-cavity"``.  ``return_folds``: the per-fold SUM of the pointwise ``lpd``."""
     if not 0.0 < ci < 1.0:
         raise ValueError("ci must be in (0, 1)")
+    if _wants_cavity(model, laplace, "cross_validate"):
+        return _cross_validate_cavity(model, folds, ci, return_folds)
     target = model.dm.data.target
     time = np.asarray(target.coords["time"].values)
     groups, labels = cv_folds(time, folds)
@@ -169,19 +298,38 @@ def cross_validate(model, folds="loo", ci=0.95, return_folds=False):
     return ds, per_fold
 
 
-def flux_bias(model, cv=None, folds="loo"):
+def flux_bias(model, cv=None, folds="loo", laplace=None):
     """WRTDS's flux bias statistic on the sampled days, B = (sum P - sum O) / sum P: O_i the observed concentration x flow,
     P_i the cross-validated MEAN concentration x flow -- for the log transform the lognormal mean exp(s mu + t + s^2 var / 2),
     not the median ``cross_validate`` reports as ``predicted``.  Flow comes from the model's own training covariates.
     ``cv``: a Dataset ``cross_validate`` returned (default: ``cross_validate(model, folds)``); observations that are never
-    held out are left out."""
+    held out are left out.
+
+    ``laplace="cavity"``: a fit with censored observations (refused otherwise; ``cv``, when given, must then come from
+    ``cross_validate(..., laplace="cavity")``).  P_i is the same on every held-out row; O_i of a censored row is the
+    EXPECTATION of the concentration given the row's bracket under its own held-out predictive N(mu, var): for the log
+    transform exp(s mu + t + s^2 var / 2 + tilt), tilt = log of the bracket's probability under N(mu + s var, var) minus that
+    under N(mu, var); for a linear target s (mu + var dlp) + t with dlp = d log P / d mu."""
+    cavity = _wants_cavity(model, laplace, "flux_bias")
     if cv is None:
-        cv = cross_validate(model, folds)
+        cv = cross_validate(model, folds, laplace=laplace)
     mu, var = (np.asarray(cv[k].values, dtype=np.float64).reshape(-1) for k in ("mu", "var"))
     held = np.asarray(cv["fold"].values).reshape(-1) >= 0
     mode, s, t = target_transform(model.dm)
     mean = np.exp(s * mu + t + 0.5 * s * s * var) if mode == MODE_LOG else s * mu + t
     flow = np.asarray(model.dm.data.covariates["flow"].values, dtype=np.float64).reshape(-1)
     observed = np.asarray(model.dm.data.target.values, dtype=np.float64).reshape(-1)
+    if cavity:
+        if cv.attrs.get("approximation") != "laplace-cavity":
+            raise ValueError('flux_bias(laplace="cavity") needs the Dataset of cross_validate(..., laplace="cavity")')
+        cens = np.asarray(cv["censored"].values).reshape(-1) != 0
+        dlp, tilt = (np.asarray(cv[k].values, dtype=np.float64).reshape(-1) for k in ("dlp", "tilt"))
+        if mode == MODE_LOG:
+            if cv.attrs.get("tilt_shift") != s:
+                raise ValueError("the cross-validation Dataset was computed for another target transform")
+            expected = np.exp(s * mu + t + 0.5 * s * s * var + tilt)
+        else:
+            expected = s * (mu + var * dlp) + t
+        observed = np.where(cens, expected, observed)
     P, O = float((mean * flow)[held].sum()), float((observed * flow)[held].sum())
     return (P - O) / P

@@ -506,6 +506,50 @@ int dgp_cross_validate(dgp_plan* plan, const int32_t* order_dev, const int32_t* 
                        void* work_dev, size_t work_bytes, double* resid_dev, double* var_dev, double* lpd_dev, int32_t* info_dev,
                        void* stream);
 
+/* CROSS-VALIDATION OF A CENSORED FIT by Laplace CAVITY folds (the LA-LOO of Vehtari et al. 2016, in block form), from the
+ * factorisation of the pseudo-data system that dgp_laplace_*factorize / *_fit_step left in the plan; no fold is refitted.
+ * dgp_cross_validate on that plan would read the pseudo-data (y~, n~ = 1 / W) as if they were samples.  With f the mode, W and
+ * g = d log p / d f the terms of the fit at f, G_F = (K^^-1)_FF and Sigma_FF = K_FF - V_F^T V_F (V = T K(X, X): the latent
+ * posterior covariance at the fold's own rows), the latent distribution of a fold F with its own sites removed is exactly
+ *     V_c = G_F^-1 diag(W_F) Sigma_FF  (its diagonal is used),      mu_c = f_F - V_c g_F
+ * -- nothing of the size of n~ is subtracted, so rows whose limit is uninformative (n~ capped at 1e12 v) keep full accuracy.
+ * What is approximate: the pseudo-data of the rows that STAY are held at the full-data mode (a refit would move them).
+ *   y / mean / noise / side / upper: what the fit was given (upper_dev: the upper ends of the rows of side 2, or NULL -- 2 is
+ *   then a bad side value);  f_dev: the mode the held factorisation was built at;  order / start / ngroups / max_group: as for
+ *   dgp_cross_validate (max_group == 1: leave-one-out, G_ii from one pass over T and Sigma_ii from the prediction's variance
+ *   pass at Xs = X; larger: blocks of order round_up(max(max_group, 65), 128) -- G_F from T's columns in every plan state, the
+ *   batched potrf / trtri, Sigma as lower 128-tiles in the work area).
+ *   out_dev [7][n] doubles, row i of plane q at out[q n + i]; with s_p^2 = v_c + noise_i (the held-out predictive of the
+ *   OBSERVATION, as dgp_cross_validate's y - resid / var), za = (y - mu_c) / s_p, zb = (upper - mu_c) / s_p:
+ *     DGP_LCV_MU    mu_c                       DGP_LCV_VAR   s_p^2
+ *     DGP_LCV_LPD   log N(y; mu_c, s_p^2) | log Phi(za) (side -1) | log Phi(-za) (+1) | log [Phi(zb) - Phi(za)] (2)
+ *     DGP_LCV_PLO / DGP_LCV_PHI   the observation's PIT, an interval for censored rows: Phi(za), Phi(za) | 0, Phi(za) |
+ *                   Phi(za), 1 | Phi(za), Phi(zb)
+ *     DGP_LCV_DLP   d LPD / d mu_c             DGP_LCV_TILT  log P(both ends shifted by -shift s_p) - log P (0 on observed
+ *                   rows and when shift == 0): E[exp(shift c) | the row's bracket] = exp(shift mu_c + shift^2 s_p^2 / 2 + TILT)
+ *   Rows that no fold holds are 0 in every plane.  info_dev [ngroups] int32: 0, or the failing pivot of G_F (the fold's rows NaN).
+ * The log probabilities go through the fit's own erfcx / three-regime functions, never through a difference of cdfs.  The
+ * plan's L, T, alpha are only read; no floating-point atomics, fixed orders: bitwise repeatable; indices read from order / start
+ * are clamped.  work_dev: dgp_laplace_cross_validate_workspace_bytes bytes, 256-byte aligned (2 N^2 doubles for K(X, X) and V,
+ * the fit's terms area, dgp_cross_validate's own area and chunk x order^2 for the folds' G_F^-1); 0 for a null, float32 or
+ * batched plan or bad sizes.
+ * DGP_E_ARG (float32 or batched plan, null argument, bad sizes, misaligned work area), DGP_E_STATE (no factorisation),
+ * DGP_E_WORKSPACE -- all before any launch; DGP_E_ARG after the terms pass alone (its sums are read back, which synchronises the
+ * stream) for a bad side value, a row of side 2 without upper_dev or a bad bracket. */
+#define DGP_LCV_MU 0
+#define DGP_LCV_VAR 1
+#define DGP_LCV_LPD 2
+#define DGP_LCV_PLO 3
+#define DGP_LCV_PHI 4
+#define DGP_LCV_DLP 5
+#define DGP_LCV_TILT 6
+#define DGP_LCV_PLANES 7
+size_t dgp_laplace_cross_validate_workspace_bytes(const dgp_plan* plan, int ngroups, int64_t max_group);
+int dgp_laplace_cross_validate(dgp_plan* plan, const double* theta_host, const void* y_dev, const void* mean_dev, const void* noise_dev,
+                               const int32_t* side_dev, const void* upper_dev, const void* f_dev, const int32_t* order_dev,
+                               const int32_t* start_dev, int ngroups, int64_t max_group, double shift, void* work_dev,
+                               size_t work_bytes, double* out_dev, int32_t* info_dev, void* stream);
+
 /* Exact FISHER INFORMATION of the hyperparameters from the factorisation the plan holds (after dgp_factorize or dgp_fit_step):
  * how well the data determine them.  The reference has no counterpart.  For the Gaussian marginal likelihood the expected
  * information of the covariance parameters is (Mardia & Marshall 1984)
