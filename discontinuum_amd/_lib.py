@@ -104,6 +104,8 @@ SIGNATURES = {
     "dgp_period_moments": (_i, [_i, _i, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp, _vp, _vp]),
     "dgp_posterior_period_moments_workspace_bytes": (_sz, [_vp, _i64, _i]),
     "dgp_posterior_period_moments": (_i, [_vp, _dp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "dgp_window_moments_workspace_bytes": (_sz, [_i64, _i64, _i]),
+    "dgp_window_moments": (_i, [_i, _i, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _sz, _vp, _vp, _vp]),
     "dgp_exceedance_moments_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
     "dgp_exceedance_moments": (_i, [_i, _vp, _i64, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp, _vp, _vp]),
     "dgp_posterior_exceedance_moments_workspace_bytes": (_sz, [_vp, _i64, _i, _i, _i]),

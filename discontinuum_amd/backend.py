@@ -724,6 +724,13 @@ class GPPlan:
         with torch.cuda.device(self.device):
             return exceedance_moments(cov, m, mu, thresh, w, groups, ngroups, extra_var)
 
+    def window_moments(self, cov, m: int, mu, lo, hi, a=None, mode: int = 0, scale2=None):
+        """Exact mean and covariance of rolling-window means of the posterior (``dgp_window_moments``): see the module-level
+        ``window_moments``.  Unbatched (cov (M, M), mu (m,), lo / hi (q,)) -> mean (q,), cov (Q, Q); batched (cov (B, M, M),
+        vectors (B, .)) -> (B, q), (B, Q, Q); fp64 device tensors, ``cov`` in the layout of ``posterior_cov``."""
+        with torch.cuda.device(self.device):
+            return window_moments(cov, m, mu, lo, hi, a=a, mode=mode, scale2=scale2)
+
     def sample_value(self, cov, m: int, a, scale2, groups, ngroups: int, obs_var=None, rows=None, nterms=None):
         """Expected reduction of every period sum's variance by one more sample on each day (``dgp_sample_value``): see the
         module-level ``sample_value``.  Unbatched (cov (M, M), vectors (m,), rows (nrows, m)) -> gain (P, m), var (m,);
@@ -1019,6 +1026,70 @@ def exceedance_moments(cov: torch.Tensor, m: int, mu: torch.Tensor, thresh: torc
                                    _ptr(ev_t), _ptr(work), need, _ptr(mean_out), _ptr(cov_out),
                                    _stream()),
         "dgp_exceedance_moments",
+    )
+    return mean_out, cov_out
+
+
+def _window_bounds(lo, hi, lead, m):
+    """``lo`` / ``hi`` of ``window_moments`` checked on the host: int32, shape ``lead + (q,)``, 0 <= lo <= hi <= m, both
+    non-decreasing along the windows.  -> (lo, hi) as contiguous host int32 tensors and q.  ``ValueError`` otherwise."""
+    out = []
+    for name, t in (("lo", lo), ("hi", hi)):
+        t = torch.as_tensor(t)
+        if t.dtype != torch.int32:
+            raise ValueError(f"{name} must be int32, not {t.dtype}")
+        if t.dim() != len(lead) + 1 or tuple(t.shape[:-1]) != lead or t.shape[-1] < 1:
+            raise ValueError(f"{name} must have shape {lead + ('q',)}, not {tuple(t.shape)}")
+        out.append(t.detach().cpu().contiguous())
+    lo_h, hi_h = out
+    if lo_h.shape != hi_h.shape:
+        raise ValueError(f"lo and hi must have the same shape {lead + ('q',)}")
+    if bool((lo_h < 0).any()) or bool((hi_h < lo_h).any()) or bool((hi_h > int(m)).any()):
+        raise ValueError(f"window bounds out of range: they must satisfy 0 <= lo <= hi <= m = {int(m)}")
+    if bool((lo_h[..., 1:] < lo_h[..., :-1]).any()) or bool((hi_h[..., 1:] < hi_h[..., :-1]).any()):
+        raise ValueError("lo and hi must both be non-decreasing along the windows")
+    return lo_h, hi_h, int(lo_h.shape[-1])
+
+
+def window_moments(cov: torch.Tensor, m: int, mu: torch.Tensor, lo, hi, a=None, mode: int = MODE_LINEAR, scale2=None):
+    """Exact mean and covariance of the rolling-window means sum_j W_ij f'_j of a latent posterior f ~ N(mu, C) --
+    W_ij = a_j / sum_{k in window i} a_k over the window ``lo[i] <= j < hi[i]`` -- through one ``dgp_window_moments`` call (no
+    factorisation, no draws).  MODE_LINEAR: f' = f, the statistic is exactly Gaussian, N(W mu, W C W^T) (``scale2`` unused);
+    MODE_LOG: the arithmetic window mean of exp(f'), f' = s f + t, with ``mu`` the MAPPED mean s mu + t and ``scale2`` = s^2.
+
+    ``cov``: what ``GPPlan.posterior_cov`` returns -- (M, M), M = padded m, lower triangle and diagonal blocks valid -- or
+    (B, M, M) for B sites; ``mu``: (m,) / (B, m), the dtype of ``cov``; ``lo`` / ``hi``: int32 (q,) / (B, q), both
+    non-decreasing with 0 <= lo <= hi <= m (checked here; ``ValueError``); ``a``: None (= 1) or non-negative weights (m,) /
+    (B, m).  An empty window or a zero weight sum gives mean 0 and a zero row and column.
+    -> (mean (q,), cov (Q, Q)) or ((B, q), (B, Q, Q)), float64 device tensors; ``cov`` has the layout of ``posterior_cov``
+    (Q = padded q, lower triangle and diagonal 128-blocks valid, identity pad; blocks above the block diagonal hold zeros) and
+    goes into ``exceedance_moments`` / ``period_moments`` / ``sample_value`` as a float64 covariance."""
+    lib = _lib.load()
+    batched = cov.dim() == 3
+    B = cov.shape[0] if batched else 1
+    M = int(lib.dgp_padded_n(int(m)))
+    lead = (B,) if batched else ()
+    lo_h, hi_h, q = _window_bounds(lo, hi, lead, int(m))
+    if mode not in (MODE_LINEAR, MODE_LOG):
+        raise ValueError(f"mode must be MODE_LINEAR or MODE_LOG, not {mode!r}")
+    if mode == MODE_LOG and scale2 is None:
+        raise ValueError("MODE_LOG needs scale2 = s^2")
+    if cov.dtype not in _DTYPES or not cov.is_cuda or not cov.is_contiguous() or tuple(cov.shape) != lead + (M, M):
+        raise ValueError(f"cov must be a contiguous {lead + (M, M)} float64 / float32 CUDA tensor")
+    dev = cov.device
+    mu_t, a_t, _g, _ev, s2 = _moment_inputs(dev, cov.dtype, lead, int(m), mu, a, None, None, scale2 if mode == MODE_LOG else None)
+    need = int(lib.dgp_window_moments_workspace_bytes(int(m), q, B))
+    if need == 0:
+        raise ValueError(f"bad size: m = {int(m)}, q = {q}, batch = {B} (1 <= m, q <= 2^20, 1 <= batch <= 1024)")
+    Q = int(lib.dgp_padded_n(q))
+    lo_t, hi_t = lo_h.to(dev), hi_h.to(dev)
+    work = torch.empty(need, dtype=torch.uint8, device=dev)
+    mean_out = torch.empty(lead + (q,), dtype=torch.float64, device=dev)
+    cov_out = torch.zeros(lead + (Q, Q), dtype=torch.float64, device=dev)
+    _lib.check(
+        lib.dgp_window_moments(_DTYPES[cov.dtype], int(mode), _ptr(cov), int(m), B, _ptr(mu_t), _ptr(s2), _ptr(a_t), _ptr(lo_t),
+                               _ptr(hi_t), q, _ptr(work), need, _ptr(mean_out), _ptr(cov_out), _stream()),
+        "dgp_window_moments",
     )
     return mean_out, cov_out
 

@@ -1604,6 +1604,34 @@ int dgp_posterior_period_moments(dgp_plan* p, const double* theta, const void* X
   return wrap(rc, "dgp_posterior_period_moments");
 }
 
+static bool wm_sizes_ok(int64_t m, int64_t q, int batch) {
+  return m > 0 && m <= (1 << 20) && q > 0 && q <= (1 << 20) && batch > 0 && batch <= DGP_MAX_BATCH_SITES;
+}
+size_t dgp_window_moments_workspace_bytes(int64_t m, int64_t q, int batch) {
+  if (!wm_sizes_ok(m, q, batch)) return 0;
+  return window_moments_workspace_bytes(m, q, batch);
+}
+
+int dgp_window_moments(int dtype, int mode, const void* cov, int64_t m, int batch, const void* mu, const double* scale2,
+                       const double* a, const int32_t* lo, const int32_t* hi, int64_t q, void* work, size_t work_bytes,
+                       double* mean_out, double* cov_out, void* stream) {
+  if (dtype != DGP_F64 && dtype != DGP_F32) return fail(DGP_E_ARG, "dgp_window_moments: dtype must be 0 (f64) or 1 (f32)");
+  if (mode != 0 && mode != 1) return fail(DGP_E_ARG, "dgp_window_moments: mode must be 0 (linear) or 1 (log)");
+  if (!cov || !mu || !lo || !hi || !mean_out || !cov_out || (mode == 1 && !scale2))
+    return fail(DGP_E_ARG, "dgp_window_moments: null argument");
+  if (!wm_sizes_ok(m, q, batch))
+    return fail(DGP_E_ARG, "dgp_window_moments: bad size (1 <= m <= 2^20, 1 <= q <= 2^20, 1 <= batch <= 1024)");
+  if (!work || work_bytes < window_moments_workspace_bytes(m, q, batch))
+    return fail(DGP_E_WORKSPACE, "dgp_window_moments: workspace missing or too small");
+  if (((uintptr_t)work & 7) != 0) return fail(DGP_E_ARG, "dgp_window_moments: the work area must be 8-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = dtype == DGP_F64 ? window_moments<double>(mode, (const double*)cov, m, batch, (const double*)mu, scale2, a, lo, hi, q,
+                                                           (double*)work, mean_out, cov_out, s)
+                                  : window_moments<float>(mode, (const float*)cov, m, batch, (const float*)mu, scale2, a, lo, hi, q,
+                                                          (double*)work, mean_out, cov_out, s);
+  return wrap(rc, "dgp_window_moments");
+}
+
 static bool ex_sizes_ok(int64_t m, int ngroups, int nlevels, int batch) {
   return m > 0 && m <= (1 << 20) && ngroups > 0 && ngroups <= 65535 && nlevels >= 1 && nlevels <= 64 && batch > 0 &&
          batch <= DGP_MAX_BATCH_SITES;

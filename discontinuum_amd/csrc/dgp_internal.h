@@ -242,6 +242,14 @@ int posterior_period_moments(int mode, int model, int d, const T* V, long N, lon
                              const double* theta, const T* mu, const double* scale2, const double* w, const int* group, int P,
                              const T* ev, double* work, double* mean_out, double* cov_out, hipStream_t s, void* pre_scratch);
 
+// ---- dgp_window.hip: exact mean / covariance of rolling-window means W f (mode 0) or W exp(f) (mode 1), f ~ N(mu, C); windows
+// [lo_i, hi_i) per site ([B][q], non-decreasing), weights a [B][m] or null; mean_out [B][q], cov_out [B][Q][Q] in the layout of
+// posterior_cov (Q = round_up(q, 128)); `work`: window_moments_workspace_bytes
+size_t window_moments_workspace_bytes(long m, long q, int B);
+template <typename T>
+int window_moments(int mode, const T* cov, long m, int B, const T* mu, const double* scale2, const double* a, const int* lo,
+                   const int* hi, long q, double* work, double* mean_out, double* cov_out, hipStream_t s);
+
 // ---- dgp_exceed.hip: exact mean / covariance of the counts sum_{i in g} w_i 1[f_i > u_il], f ~ N(mu, C), per level l.  thresh
 // [B][L][m] in model space; mean_out [B][L][P], cov_out [B][L][P][P]; `work`: exceedance_moments_workspace_bytes
 size_t exceedance_moments_workspace_bytes(long m, int P, int L, int B);

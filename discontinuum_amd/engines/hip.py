@@ -856,7 +856,8 @@ class MarginalHIP(BaseModel):
 
     @is_fitted
     def exceedance(self, covariates, threshold=None, threshold_series=None, freq="YE", above=True, fraction=False, ci=0.95,
-                   pred_noise=False, return_cov=False, max_bytes=None, streamed=False):
+                   pred_noise=False, return_cov=False, max_bytes=None, streamed=False, window=None, align="right",
+                   min_periods=None, statistic=None):
         """Expected number of points per period of ``freq`` at which the target exceeds a data-space threshold -- days per
         year above a criterion, for a daily record -- with its exact standard error: what ``sample()``, a comparison and a
         count per period estimate by Monte Carlo, in one posterior covariance and one ``dgp_exceedance_moments`` pass.
@@ -866,13 +867,36 @@ class MarginalHIP(BaseModel):
         distribution with the exact moments) and ``n_points``; with ``return_cov`` also the (L, P, P) covariance.  A record
         whose m x m covariance does not fit ``max_bytes`` (default ``loads.DEFAULT_MAX_BYTES``) raises ``ValueError``;
         ``streamed=True`` produces the covariance a panel of rows at a time instead (``dgp_posterior_exceedance_moments``) and
-        works at any record length, with ``max_bytes`` bounding its work area.  See ``discontinuum_amd.exceedance``."""
+        works at any record length, with ``max_bytes`` bounding its work area.  ``window`` ("30D", "7D", ...; with ``align`` and
+        ``min_periods`` as in ``rolling_mean``): the days on which the ROLLING mean over that averaging period -- the geometric
+        mean for a log target -- exceeds the threshold, from one more pass (``dgp_window_moments``) between the two; without it
+        the product is what it always was.  See ``discontinuum_amd.exceedance``."""
         from ..exceedance import exceedance
         from ..loads import DEFAULT_MAX_BYTES
 
         return exceedance(self, covariates, threshold=threshold, threshold_series=threshold_series, freq=freq, above=above,
                           fraction=fraction, ci=ci, pred_noise=pred_noise, return_cov=return_cov,
-                          max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes, streamed=streamed)
+                          max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes, streamed=streamed, window=window,
+                          align=align, min_periods=min_periods, statistic=statistic)
+
+    @is_fitted
+    def rolling_mean(self, covariates, window, statistic=None, align="right", min_periods=None, ci=0.95, return_cov=False,
+                     max_bytes=None):
+        """The rolling mean of the target over ``window`` ("30D", "7D", "96h" or a ``numpy.timedelta64``; membership by time,
+        so gaps and irregular records are handled) with its exact uncertainty: what ``sample()`` and a rolling mean of every
+        draw estimate by Monte Carlo, in one posterior covariance and one ``dgp_window_moments`` pass.  ``statistic=None`` is
+        the model-space mean -- the GEOMETRIC mean for a log target, exactly lognormal, with an exact ``ci`` interval; the
+        plain mean for a linear one --; ``statistic="mean"`` on a log target is the arithmetic n-day mean (mean and se exact,
+        interval approximate).  ``align="right"``: the trailing window (t - window, t]; ``"center"``: [t - window / 2,
+        t + window / 2).  ``min_periods=None``: the largest point count any window of the record holds, so that leading
+        partial windows and windows over gaps are left out.  -> Dataset on the qualifying outputs' ``time`` with ``mean``,
+        ``se``, ``lower``, ``upper`` and ``n_points``; with ``return_cov`` also the (q, q) covariance.  See
+        ``discontinuum_amd.rolling``."""
+        from ..loads import DEFAULT_MAX_BYTES
+        from ..rolling import rolling_mean
+
+        return rolling_mean(self, covariates, window, statistic=statistic, align=align, min_periods=min_periods, ci=ci,
+                            return_cov=return_cov, max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes)
 
     @is_fitted
     def sample_value(self, covariates, weights, freq="YE", sample_var=None, given=None, ci=0.95, max_bytes=None):
@@ -927,26 +951,32 @@ class MarginalHIP(BaseModel):
         return influence(self, covariates, weights, folds=folds, freq=freq, max_bytes=max_bytes)
 
     @is_fitted
-    def duration_curve(self, covariates, levels=None, above=True, ci=0.95, pred_noise=False, max_bytes=None, streamed=False):
+    def duration_curve(self, covariates, levels=None, above=True, ci=0.95, pred_noise=False, max_bytes=None, streamed=False,
+                       window=None, align="right", min_periods=None, statistic=None):
         """Fraction of the record ``covariates`` on which the target exceeds each of ``levels`` (default: 21 quantiles of
         the posterior mean), with the exact standard error of that fraction and approximate ``ci`` intervals -- for a
         rating model over a stage record, the flow-duration curve.  -> Dataset on ``level`` with ``mean``, ``se``,
-        ``lower``, ``upper``.  ``max_bytes`` / ``streamed``: as for ``exceedance``.  See
-        ``discontinuum_amd.exceedance.duration_curve``."""
+        ``lower``, ``upper``.  ``max_bytes`` / ``streamed``, ``window`` / ``align`` / ``min_periods``: as for ``exceedance``.
+        See ``discontinuum_amd.exceedance.duration_curve``."""
         from ..exceedance import duration_curve
         from ..loads import DEFAULT_MAX_BYTES
 
         return duration_curve(self, covariates, levels=levels, above=above, ci=ci, pred_noise=pred_noise,
-                              max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes, streamed=streamed)
+                              max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes, streamed=streamed, window=window,
+                              align=align, min_periods=min_periods, statistic=statistic)
 
     @is_fitted
-    def exceedance_probability(self, covariates, threshold, above=True, pred_noise=False):
+    def exceedance_probability(self, covariates, threshold, above=True, pred_noise=False, window=None, align="right",
+                               min_periods=None, max_bytes=None):
         """Pointwise probability that the target exceeds ``threshold`` (a data-space number or one value per point) at each
         point of ``covariates``, from the prediction's mean and variance.  -> DataArray on the covariates' coordinate.  See
-        ``discontinuum_amd.exceedance.exceedance_probability``."""
+        ``discontinuum_amd.exceedance.exceedance_probability``.  ``window``: the same for the rolling mean over that window, on the
+        qualifying outputs' ``time``."""
         from ..exceedance import exceedance_probability
+        from ..loads import DEFAULT_MAX_BYTES
 
-        return exceedance_probability(self, covariates, threshold, above=above, pred_noise=pred_noise)
+        return exceedance_probability(self, covariates, threshold, above=above, pred_noise=pred_noise, window=window, align=align,
+                                      min_periods=min_periods, max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes)
 
     @is_fitted
     def cross_validate(self, folds="loo", ci=0.95, return_folds=False, laplace=None):

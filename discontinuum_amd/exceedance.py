@@ -66,14 +66,21 @@ def _work_bytes(m, P, L):
     return 8 * (2 * M * (L + 1) + M * P * min(L, 8) + P)
 
 
-def count_moments(model, Xnew, u, w, groups, ngroups, pred_noise=False, max_bytes: int = DEFAULT_MAX_BYTES, streamed=False):
+def count_moments(model, Xnew, u, w, groups, ngroups, pred_noise=False, max_bytes: int = DEFAULT_MAX_BYTES, streamed=False,
+                  windows=None):
     """The device core: design rows ``Xnew`` (m, d), model-space thresholds ``u`` (L, m), weights ``w`` (m,), int32 group
     ids (non-decreasing, -1 = excluded) -> numpy (mean (L, P), cov (L, P, P)) from ONE ``posterior_cov`` and one
     ``exceedance_moments`` per 64 levels, taken the way ``loads.point_moments`` takes its dense branch.  A record whose
     dense footprint -- ``loads._site_bytes`` plus the moment pass's own work area (``_work_bytes``) -- exceeds
     ``max_bytes`` raises ``ValueError``.  ``streamed=True`` (never chosen automatically): the latent mean from
     ``predict_mean`` like ``point_moments``' streamed branch, then one ``posterior_exceedance_moments`` per 64 levels, whose
-    work area -- with the largest covariance panel that fits -- ``max_bytes`` bounds instead."""
+    work area -- with the largest covariance panel that fits -- ``max_bytes`` bounds instead.
+
+    ``windows=(lo, hi)`` (int32, (q,) each: ``rolling.time_windows``): the counts are of the ROLLING MEANS over the windows
+    ``lo[i] <= j < hi[i]`` of the points -- one ``window_moments`` between ``posterior_cov`` and ``exceedance_moments``;
+    ``u``, ``w`` and ``groups`` are then per OUTPUT (q).  See ``_windowed_count_moments``."""
+    if windows is not None:
+        return _windowed_count_moments(model, Xnew, u, w, groups, ngroups, windows, pred_noise, max_bytes, streamed)
     Xnew = Xnew.to(model.device).contiguous()
     m = Xnew.shape[0]
     u = np.ascontiguousarray(np.asarray(u, dtype=np.float64).reshape(-1, m))
@@ -108,6 +115,73 @@ def count_moments(model, Xnew, u, w, groups, ngroups, pred_noise=False, max_byte
     return np.concatenate(means), np.concatenate(covs)
 
 
+WINDOW_REFUSALS = {
+    "streamed": "a window needs the dense posterior covariance: the streamed pass produces it a panel of rows at a time, and a "
+                "window reaches across panels (a streamed form needs a row halo); drop streamed=True",
+    "pred_noise": "pred_noise=True has no meaning for a rolling mean: the noise of an averaged hypothetical observation is not "
+                  "defined here",
+    "flux": "kind='flux' with a window is not implemented: a rolling mean of daily loads is a weighted sum of lognormals, not "
+            "a Gaussian in model space",
+    "statistic": "exceedance of the arithmetic rolling mean of a log target is not implemented: that mean is a sum of "
+                 "lognormals, not a Gaussian; use the model-space statistic (the geometric mean)",
+}
+
+
+def _check_window_request(model, statistic, pred_noise, streamed):
+    """The refusals of a windowed count, each saying why; -> nothing."""
+    if streamed:
+        raise NotImplementedError(WINDOW_REFUSALS["streamed"])
+    if pred_noise:
+        raise ValueError(WINDOW_REFUSALS["pred_noise"])
+    mode, _s, _t = target_transform(model.dm)
+    model_space = "geometric_mean" if mode == MODE_LOG else "mean"
+    if statistic is not None and statistic not in ("mean", "geometric_mean"):
+        raise ValueError(f"statistic must be 'mean' or 'geometric_mean', not {statistic!r}")
+    if statistic == "mean" and mode == MODE_LOG:
+        raise NotImplementedError(WINDOW_REFUSALS["statistic"])
+    if statistic is not None and statistic != model_space:
+        raise ValueError(f"the model-space statistic of this target is {model_space!r}, not {statistic!r}")
+
+
+def _windowed_count_moments(model, Xnew, u, w, groups, ngroups, windows, pred_noise, max_bytes, streamed):
+    """``count_moments`` of rolling means: ``Xnew`` (m, d) the points in time order, ``windows=(lo, hi)`` the q outputs'
+    index windows, ``u`` (L, q), ``w`` (q,) and ``groups`` (q,; -1 = excluded) per output.  One ``posterior_cov``, one
+    ``window_moments`` (mode 0: W mu and W C W^T in the covariance's own layout), then ``exceedance_moments`` on that.  The
+    dense footprint grows by the (Q, Q) result and the pass's work area (``rolling.window_bytes``)."""
+    from .rolling import check_window_budget
+
+    if streamed:
+        raise NotImplementedError(WINDOW_REFUSALS["streamed"])
+    if pred_noise:
+        raise ValueError(WINDOW_REFUSALS["pred_noise"])
+    lo, hi = (np.ascontiguousarray(np.asarray(v, dtype=np.int32)) for v in windows)
+    Xnew = Xnew.to(model.device).contiguous()
+    m, q = Xnew.shape[0], len(lo)
+    u = np.ascontiguousarray(np.asarray(u, dtype=np.float64).reshape(-1, q))
+    check_window_budget(model, m, q, _work_bytes(q, ngroups, min(u.shape[0], MAX_LEVELS)), max_bytes,
+                        "exceedance statistics of a rolling mean")
+    means, covs = [], []
+    model._eval_ready(Xnew)
+    with torch.no_grad():
+        kmean, cov = model._plan.posterior_cov(model._factor_theta, Xnew)
+        mu = (kmean + model.model.prior_mean(Xnew)).contiguous()
+        wmean, S = model._plan.window_moments(cov, m, mu, torch.from_numpy(lo), torch.from_numpy(hi))
+        for l0 in range(0, u.shape[0], MAX_LEVELS):
+            mean_d, cov_d = model._plan.exceedance_moments(S, q, wmean, torch.from_numpy(u[l0:l0 + MAX_LEVELS]), w, groups, ngroups)
+            means.append(mean_d.cpu().numpy())
+            covs.append(cov_d.cpu().numpy())
+    return np.concatenate(means), np.concatenate(covs)
+
+
+def _output_groups(times, keep, freq):
+    """Period ids of the outputs in TIME order: an output belongs to the period of its own time stamp, one that does not
+    qualify gets -1.  -> (groups int32, labels, n_points): the periods run from the first to the last qualifying output."""
+    order, groups, labels, n_points, _dropped = period_groups(times, np.where(keep, 1.0, np.nan), freq)
+    g = np.empty(len(times), dtype=np.int32)
+    g[order] = groups
+    return g, labels, n_points
+
+
 def _finish(mean, cov, total, above, fraction, ci):
     """Complement / fraction on the host, then se and intervals: -> (mean, se, lower, upper, cov), each per level."""
     total = np.asarray(total, dtype=np.float64)
@@ -124,7 +198,8 @@ def _finish(mean, cov, total, above, fraction, ci):
 
 
 def exceedance(model, covariates, threshold=None, threshold_series=None, freq="YE", above=True, fraction=False, ci=0.95,
-               pred_noise=False, return_cov=False, max_bytes: int = DEFAULT_MAX_BYTES, streamed=False):
+               pred_noise=False, return_cov=False, max_bytes: int = DEFAULT_MAX_BYTES, streamed=False, window=None,
+               align="right", min_periods=None, statistic=None):
     """``MarginalHIP.exceedance``: per period of ``freq`` the expected number of points of ``covariates`` at which the
     target exceeds a threshold -- days per year above a criterion, for a daily record -- with its exact standard error.
 
@@ -137,23 +212,47 @@ def exceedance(model, covariates, threshold=None, threshold_series=None, freq="Y
     ``lower`` / ``upper`` are APPROXIMATE ``ci`` intervals -- the quantiles of a beta distribution for N / sum w matched
     to the exact mean and variance (the mean itself where the variance is 0) --, mean and se are exact.  With
     ``return_cov`` also the (L, P, P) covariance between the periods, level by level.  A record whose dense footprint
-    exceeds ``max_bytes`` raises ``ValueError``; ``streamed=True`` never forms the m x m covariance (``count_moments``)."""
+    exceeds ``max_bytes`` raises ``ValueError``; ``streamed=True`` never forms the m x m covariance (``count_moments``).
+
+    ``window`` ("30D", "7D", a ``numpy.timedelta64``; with ``align`` and ``min_periods``: ``rolling.time_windows``): the
+    days on which the ROLLING mean of the target over that window -- the model-space mean: the geometric mean for a log
+    target -- exceeds the threshold, which is how criteria on an averaging period are written.  An output belongs to the
+    period of its own time stamp, the threshold is the one of its own day, outputs whose window does not qualify are left
+    out and ``n_points`` counts the rest.  Refused with a window: ``streamed=True``, ``pred_noise=True``, the arithmetic
+    ``statistic="mean"`` of a log target.  ``window=None`` (default) is the daily product, unchanged."""
     return _exceedance(model, covariates, threshold, threshold_series, freq=freq, above=above, fraction=fraction, ci=ci,
-                       pred_noise=pred_noise, return_cov=return_cov, max_bytes=max_bytes, streamed=streamed)
+                       pred_noise=pred_noise, return_cov=return_cov, max_bytes=max_bytes, streamed=streamed, window=window,
+                       align=align, min_periods=min_periods, statistic=statistic)
 
 
 def _exceedance(model, covariates, threshold=None, threshold_series=None, *, weights=None, level_labels=None, freq="YE",
                 above=True, fraction=False, ci=0.95, pred_noise=False, return_cov=False, max_bytes: int = DEFAULT_MAX_BYTES,
-                streamed=False):
+                streamed=False, window=None, align="right", min_periods=None, statistic=None):
     """The body of ``exceedance`` with what ``flux_exceedance`` adds: per-point ``weights`` of the count (default 1; a
     point with a non-finite weight is dropped like ``aggregate`` drops it) and ``level_labels`` for the ``level``
-    coordinate of a per-point series."""
+    coordinate of a per-point series.  With ``window`` the points are the record in time order, the outputs sit on them
+    and the groups come from ``_output_groups``."""
     if (threshold is None) == (threshold_series is None):
         raise ValueError("give exactly one of threshold and threshold_series")
     time = np.asarray(covariates.coords["time"].values).reshape(-1)
     m_all = len(time)
-    w_all = np.ones(m_all) if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
-    order, groups, labels, n_points, _dropped = _kept(*period_groups(time, w_all, freq))
+    windows = None
+    if window is not None:
+        from .rolling import time_windows
+
+        if weights is not None:
+            raise NotImplementedError(WINDOW_REFUSALS["flux"])
+        _check_window_request(model, statistic, pred_noise, streamed)
+        w_all = np.ones(m_all)
+        Xall = np.asarray(model.dm.Xnew(covariates))
+        order, lo, hi, keep = time_windows(time, window, align, min_periods, valid=np.all(np.isfinite(Xall), axis=1))
+        if not keep.any():
+            raise ValueError(f"no window of the record holds min_periods = {min_periods} points")
+        groups, labels, n_points = _output_groups(time[order], keep, freq)
+        windows = (lo, hi)
+    else:
+        w_all = np.ones(m_all) if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
+        order, groups, labels, n_points, _dropped = _kept(*period_groups(time, w_all, freq))
     if threshold is not None:
         levels = np.atleast_1d(np.asarray(threshold, dtype=np.float64))
         if levels.ndim != 1 or levels.size == 0:
@@ -170,10 +269,17 @@ def _exceedance(model, covariates, threshold=None, threshold_series=None, *, wei
     u = model_space_threshold(model.dm, series[:, order])
     w = w_all[order]
     Xnew = torch.tensor(model.dm.Xnew(covariates), dtype=model.dtype)[torch.as_tensor(order)]
-    mean, cov = count_moments(model, Xnew, u, w, groups, len(labels), pred_noise=pred_noise, max_bytes=max_bytes, streamed=streamed)
-    total = np.bincount(groups, weights=w, minlength=len(labels))
+    if windows is None:
+        mean, cov = count_moments(model, Xnew, u, w, groups, len(labels), pred_noise=pred_noise, max_bytes=max_bytes, streamed=streamed)
+        total = np.bincount(groups, weights=w, minlength=len(labels))
+    else:
+        mean, cov = count_moments(model, Xnew, u, w, groups, len(labels), pred_noise=pred_noise, max_bytes=max_bytes, streamed=streamed,
+                                  windows=windows)
+        total = np.bincount(groups[groups >= 0], weights=w[groups >= 0], minlength=len(labels))
     mean, se, lower, upper, cov = _finish(mean, cov, total, above, fraction, ci)
     attrs = dict(_target_attrs(model.dm), above=bool(above), fraction=bool(fraction))
+    if windows is not None:
+        attrs.update(window=str(window), align=align, statistic="geometric_mean" if target_transform(model.dm)[0] == MODE_LOG else "mean")
     dims = ("level", "time")
     ds = Dataset(
         {
@@ -213,14 +319,66 @@ def _latent_predict(model, covariates, pred_noise):
     return mu.double().cpu().numpy(), var.double().cpu().numpy()
 
 
+def _data_space(model, f):
+    """Model-space values -> data space through the target transform alone (exp(s f + t) or s f + t; no clip)."""
+    mode, s, t = target_transform(model.dm)
+    return np.exp(s * f + t) if mode == MODE_LOG else s * f + t
+
+
+def _windowed_duration_curve(model, covariates, levels, above, ci, pred_noise, max_bytes, streamed, window, align, min_periods,
+                             statistic):
+    """``duration_curve`` of the rolling mean: the qualifying outputs as ONE group.  Default ``levels``: the 21 quantiles of
+    the data-space rolling posterior mean (W mu, mapped) over those outputs."""
+    from .rolling import time_windows
+
+    _check_window_request(model, statistic, pred_noise, streamed)
+    time = np.asarray(covariates.coords["time"].values).reshape(-1)
+    Xall = np.asarray(model.dm.Xnew(covariates))
+    order, lo, hi, keep = time_windows(time, window, align, min_periods, valid=np.all(np.isfinite(Xall), axis=1))
+    if not keep.any():
+        raise ValueError(f"no window of the record holds min_periods = {min_periods} points")
+    if levels is None:
+        mu, _var = _latent_predict(model, covariates, False)
+        cs = np.concatenate([[0.0], np.cumsum(mu[order])])
+        wm = (cs[hi[keep]] - cs[lo[keep]]) / (hi[keep] - lo[keep])
+        levels = np.quantile(_data_space(model, wm), np.linspace(0.02, 0.98, 21))
+    levels = np.atleast_1d(np.asarray(levels, dtype=np.float64))
+    if levels.ndim != 1 or levels.size == 0:
+        raise ValueError("levels must be a 1-D list of data-space levels")
+    q, n = len(lo), int(keep.sum())
+    u = np.broadcast_to(model_space_threshold(model.dm, levels)[:, None], (levels.size, q))
+    Xnew = torch.tensor(Xall[order], dtype=model.dtype)
+    mean, cov = count_moments(model, Xnew, u, np.ones(q), np.where(keep, 0, -1).astype(np.int32), 1, max_bytes=max_bytes,
+                              windows=(lo, hi))
+    mean, se, lower, upper, _cov = _finish(mean, cov, np.array([float(n)]), above, True, ci)
+    attrs = dict(_target_attrs(model.dm), above=bool(above), n_points=n, window=str(window), align=align,
+                 statistic="geometric_mean" if target_transform(model.dm)[0] == MODE_LOG else "mean")
+    return Dataset(
+        {
+            "mean": ("level", mean[:, 0], attrs),
+            "se": ("level", se[:, 0], attrs),
+            "lower": ("level", lower[:, 0], dict(attrs, ci=ci)),
+            "upper": ("level", upper[:, 0], dict(attrs, ci=ci)),
+        },
+        coords={"level": levels},
+        attrs=attrs,
+    )
+
+
 def duration_curve(model, covariates, levels=None, above=True, ci=0.95, pred_noise=False, max_bytes: int = DEFAULT_MAX_BYTES,
-                   streamed=False):
+                   streamed=False, window=None, align="right", min_periods=None, statistic=None):
     """``MarginalHIP.duration_curve``: the fraction of the record -- all points of ``covariates`` as ONE group -- on which
     the target exceeds each of ``levels`` (data space), with the exact standard error of that fraction and approximate
     ``ci`` intervals (``count_intervals``); for a rating model over a stage record, the flow-duration curve.  Default
     ``levels``: the 21 quantiles 2 %, 6.8 %, ... 98 % of the data-space posterior mean over the record.
     ``streamed=True``: without the m x m covariance, for records of any length (``count_moments``).
-    -> Dataset on ``level`` with ``mean``, ``se``, ``lower``, ``upper``; ``n_points`` among its attributes."""
+    -> Dataset on ``level`` with ``mean``, ``se``, ``lower``, ``upper``; ``n_points`` among its attributes.
+    ``window`` (with ``align``, ``min_periods``): the duration curve of the ROLLING mean over that window instead -- the
+    fraction of the qualifying outputs on which it exceeds each level (``exceedance`` explains the keyword and its
+    refusals)."""
+    if window is not None:
+        return _windowed_duration_curve(model, covariates, levels, above, ci, pred_noise, max_bytes, streamed, window, align,
+                                        min_periods, statistic)
     Xall = np.asarray(model.dm.Xnew(covariates))
     keep = np.nonzero(np.all(np.isfinite(Xall), axis=1))[0]
     if levels is None:
@@ -249,11 +407,51 @@ def duration_curve(model, covariates, levels=None, above=True, ci=0.95, pred_noi
     )
 
 
-def exceedance_probability(model, covariates, threshold, above=True, pred_noise=False):
+def _windowed_exceedance_probability(model, covariates, threshold, above, pred_noise, window, align, min_periods, max_bytes):
+    """``exceedance_probability`` of the rolling mean: Phi(((W mu)_i - u_i) / sqrt(S_ii)) from the diagonal of S = W C W^T,
+    on the qualifying outputs' ``time`` coordinate; a per-point threshold is read at the output's own time stamp."""
+    from .rolling import check_window_budget, time_windows
+
+    if pred_noise:
+        raise ValueError(WINDOW_REFUSALS["pred_noise"])
+    time = np.asarray(covariates.coords["time"].values).reshape(-1)
+    m_all = len(time)
+    Xall = np.asarray(model.dm.Xnew(covariates))
+    order, lo, hi, keep = time_windows(time, window, align, min_periods, valid=np.all(np.isfinite(Xall), axis=1))
+    out = np.nonzero(keep)[0]
+    if out.size == 0:
+        raise ValueError(f"no window of the record holds min_periods = {min_periods} points")
+    tau = np.broadcast_to(np.asarray(threshold, dtype=np.float64), (m_all,))[order][out]
+    u = model_space_threshold(model.dm, tau)
+    Xnew = torch.tensor(Xall[order], dtype=model.dtype).to(model.device).contiguous()
+    m, q = Xnew.shape[0], len(out)
+    check_window_budget(model, m, q, 0, max_bytes, "the exceedance probability of a rolling mean")
+    model._eval_ready(Xnew)
+    with torch.no_grad():
+        kmean, cov = model._plan.posterior_cov(model._factor_theta, Xnew)
+        mu = (kmean + model.model.prior_mean(Xnew)).contiguous()
+        wmean, S = model._plan.window_moments(cov, m, mu, torch.from_numpy(np.ascontiguousarray(lo[out])),
+                                              torch.from_numpy(np.ascontiguousarray(hi[out])))
+        wm = wmean.double().cpu().numpy()
+        var = torch.diagonal(S)[:q].double().cpu().numpy()
+    with np.errstate(divide="ignore", invalid="ignore"):
+        z = np.where(var > 0, (wm - u) / np.sqrt(np.where(var > 0, var, 1.0)), np.where(wm > u, np.inf, -np.inf))
+    z = np.where(np.isinf(u), np.where(u < 0, np.inf, -np.inf), z)
+    p = norm.cdf(z if above else -z)
+    attrs = dict(_target_attrs(model.dm), long_name="Exceedance probability" if above else "Non-exceedance probability",
+                 units="1", window=str(window), align=align)
+    return DataArray(p, coords={"time": time[order][out].astype("datetime64[ns]")}, dims=["time"], attrs=attrs)
+
+
+def exceedance_probability(model, covariates, threshold, above=True, pred_noise=False, window=None, align="right",
+                           min_periods=None, max_bytes: int = DEFAULT_MAX_BYTES):
     """``MarginalHIP.exceedance_probability``: the pointwise probability Phi((mu_i - u_i) / sigma_i) that the target
     exceeds ``threshold`` (a data-space number, or one value per point) at each point of ``covariates`` -- host-side, from
     the plan's existing prediction.  A point with zero variance gives 1 or 0 (a tie counts as not exceeded).
-    -> DataArray on the covariates' coordinate."""
+    -> DataArray on the covariates' coordinate.  ``window`` (with ``align``, ``min_periods``): the probability that the ROLLING
+    mean over that window exceeds it, from the diagonal of the windowed covariance, on the qualifying outputs' ``time``."""
+    if window is not None:
+        return _windowed_exceedance_probability(model, covariates, threshold, above, pred_noise, window, align, min_periods, max_bytes)
     mu, var = _latent_predict(model, covariates, pred_noise)
     tau = np.broadcast_to(np.asarray(threshold, dtype=np.float64), mu.shape)
     u = model_space_threshold(model.dm, tau)

@@ -123,17 +123,23 @@ class LoadestGPMarginalHIP(LoadestDataMixin, MarginalHIP):
 
     @is_fitted
     def exceedance(self, covariates, threshold=None, threshold_series=None, kind="concentration", freq="YE", above=True,
-                   fraction=False, ci=0.95, pred_noise=False, return_cov=False, max_bytes=None, streamed=False):
+                   fraction=False, ci=0.95, pred_noise=False, return_cov=False, max_bytes=None, streamed=False, window=None,
+                   align="right", min_periods=None, statistic=None):
         """Days per period above a criterion, with exact uncertainty (``MarginalHIP.exceedance``).  ``kind="concentration"``:
         the threshold is a concentration; ``kind="flux"``: ``threshold`` is a daily load in kg per day (a number or a list),
         turned into the per-day concentration threshold limit / w_i with the flux weights of ``annual_flux`` (regular time
-        grid; a day with a non-positive or missing flow is excluded)."""
+        grid; a day with a non-positive or missing flow is excluded).  ``window`` (``kind="concentration"`` only): days on
+        which the rolling geometric mean over that averaging period exceeds the criterion (``MarginalHIP.exceedance``)."""
         if kind not in ("concentration", "flux"):
             raise ValueError(f"kind must be 'concentration' or 'flux', not {kind!r}")
         if kind == "concentration":
             return super().exceedance(covariates, threshold=threshold, threshold_series=threshold_series, freq=freq, above=above,
                                       fraction=fraction, ci=ci, pred_noise=pred_noise, return_cov=return_cov, max_bytes=max_bytes,
-                                      streamed=streamed)
+                                      streamed=streamed, window=window, align=align, min_periods=min_periods, statistic=statistic)
+        if window is not None:
+            from ..exceedance import WINDOW_REFUSALS
+
+            raise NotImplementedError(WINDOW_REFUSALS["flux"])
         if threshold is None or threshold_series is not None:
             raise ValueError("kind='flux' takes threshold = the daily load limit in kg per day")
         from ..exceedance import flux_exceedance

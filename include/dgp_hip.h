@@ -390,6 +390,33 @@ int dgp_posterior_period_moments(dgp_plan* plan, const double* theta_host, const
                                  void* work_dev, size_t work_bytes, double* mean_out_dev, double* cov_out_dev,
                                  void* stream);
 
+/* Exact mean and covariance of ROLLING-WINDOW MEANS of a posterior -- the 30-day geometric mean, the 4-day average, the 7-day
+ * mean flow that water-quality criteria are written on -- which the reference can only estimate by Monte Carlo: sample()
+ * (engines/gpytorch.py:551-593), roll every draw, average.  With f ~ N(mu, C) per site, window i the points lo[i] <= j < hi[i]
+ * and W_ij = a_j / sum_{k in window i} a_k, the statistic W f is exactly Gaussian:
+ *   mode 0 (linear):  mean[i] = sum_j W_ij mu_j        cov[i][k] = sum_j sum_l W_ij W_kl C_jl   (scale2_dev ignored, may be NULL)
+ *   mode 1 (log, the ARITHMETIC mean of exp(s f + t); mu_dev ALREADY mapped, as for dgp_period_moments):
+ *           e_j = exp(mu_j + s2 C_jj / 2),  mean[i] = sum_j W_ij e_j,  cov[i][k] = sum_j sum_l W_ij W_kl e_j e_l expm1(s2 C_jl)
+ * cov_dev, mu_dev, batch and the padding: as for dgp_period_moments (per site M x M, M = dgp_padded_n(m); only the lower
+ *            triangle is read, an entry above the diagonal is taken from its mirror);
+ * a_dev      batch x m non-negative doubles, or NULL for 1;
+ * lo_dev, hi_dev  batch x q int32, both NON-DECREASING in i, 0 <= lo <= hi <= m; the device clamps them to [0, m] (a violation
+ *            gives wrong numbers, never an access out of bounds);
+ * mean_out_dev  batch x q doubles;  cov_out_dev  batch x Q x Q doubles, Q = dgp_padded_n(q), in the layout dgp_posterior_cov
+ *            writes -- lower triangle and diagonal 128-blocks valid, those blocks exactly symmetric, identity pad, blocks above
+ *            the block diagonal not written -- so that it goes into dgp_exceedance_moments, dgp_period_moments and
+ *            dgp_sample_value as an fp64 covariance.  An empty window or a zero weight sum gives mean 0 and a zero row and column.
+ * work_dev: dgp_window_moments_workspace_bytes(m, q, batch) bytes, 8-byte aligned (M Q + 2 M + 2 Q doubles per site; 0 for bad
+ * sizes).  Four launches (gridDim.z = batch): T = C_sym W^T, then S = W T on the lower block triangle; all arithmetic after the
+ * loads is double, every sum runs in one thread in ascending order: no floating-point atomics, bitwise repeatable, and a
+ * site's result does not depend on the batch it is in.  DGP_E_ARG: a null argument, a bad dtype / mode / size (1 <= m, q <=
+ * 2^20, 1 <= batch <= 1024), a misaligned work area; DGP_E_WORKSPACE: a work area too small.  Needs no plan. */
+size_t dgp_window_moments_workspace_bytes(int64_t m, int64_t q, int batch);
+int dgp_window_moments(int dtype, int mode, const void* cov_dev, int64_t m, int batch, const void* mu_dev,
+                       const double* scale2_dev, const double* a_dev, const int32_t* lo_dev, const int32_t* hi_dev,
+                       int64_t q, void* work_dev, size_t work_bytes, double* mean_out_dev, double* cov_out_dev,
+                       void* stream);
+
 /* Exact mean and covariance of THRESHOLD-EXCEEDANCE COUNTS of a posterior -- days per year above a criterion, the fraction
  * of a record above a level (duration curves) -- which the reference can only estimate by Monte Carlo: sample()
  * (engines/gpytorch.py:551-593), compare every draw with the threshold, count per period.  With f ~ N(mu, C) per site, per

@@ -2,8 +2,8 @@
 """Bitwise record of everything a ``GPPlan`` computes from a held factorisation, for refactors of the host glue that must not
 move a number: seeded inputs, one fit, and the outputs of ``fit_step``, ``factorize``, ``predict``, ``predict_mean``,
 ``mean_vjp``, ``predict_terms`` / ``predict_slopes`` (with and without ``return_cov``), ``posterior_cov``,
-``posterior_period_moments``, ``period_moments``, ``exceedance_moments``, ``posterior_exceedance_moments``, ``sample_value``
-and ``cross_validate``.
+``posterior_period_moments``, ``period_moments``, ``exceedance_moments``, ``posterior_exceedance_moments``, ``sample_value``,
+``window_moments`` and ``cross_validate``.
 
     python scripts/inference_snapshot.py --write before.pt      # on the commit to compare against
     python scripts/inference_snapshot.py --compare before.pt    # on the new one: exit status 1 unless every tensor is equal
@@ -84,6 +84,13 @@ def run_config(torch, GPPlan, backend, make_case, model, d, dtype, sizes, dev):
     given = stack([0.05 * torch.randn(3, m, generator=g, dtype=torch.float64) for _ in range(B)], torch.float64)
     keep("sample_value", plan.sample_value(cov, m, w, scale2, groups, GROUPS, obs_var=extra, rows=given, nterms=12))
     keep("sample_value_linear", plan.sample_value(cov, m, w, scale2, groups, GROUPS, nterms=1))
+    i = torch.arange(m)
+    lo = (i - 29).clamp_min(0).to(torch.int32).expand(lead + (m,)).contiguous()  # trailing windows of 30 points
+    hi = (i + 1).to(torch.int32).expand(lead + (m,)).contiguous()
+    wmean, wcov = plan.window_moments(cov, m, mu, lo, hi, a=w)
+    keep("window_moments_linear", (wmean, torch.tril(wcov)[..., :m, :m]))
+    wmean, wcov = plan.window_moments(cov, m, mu, lo, hi, a=w, mode=backend.MODE_LOG, scale2=scale2)
+    keep("window_moments_log", (wmean, torch.tril(wcov)[..., :m, :m]))
     keep("posterior_period_moments_log", plan.posterior_period_moments(theta, Xs, mu, scale2, w, groups, GROUPS, backend.MODE_LOG))
     keep("posterior_period_moments_linear",
          plan.posterior_period_moments(theta, Xs, mu, scale2, w, groups, GROUPS, backend.MODE_LINEAR, extra_var=extra))
