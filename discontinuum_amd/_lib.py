@@ -142,6 +142,8 @@ SIGNATURES = {
     "dgp_stage_grad": (_i, [_vp, _dp, _vp, _vp]),
     "dgp_cross_gram": (_i, [_vp, _dp, _vp, _i64, _vp, _vp, _vp]),
     "dgp_debug_clock_probe": (_i, [_vp, _i, C.c_double, _vp]),
+    "dgp_debug_solve": (_i, [_i, _i, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "dgp_debug_solve_partials": (_i64, [_i64]),
     "dgp_debug_tile_gemm": (_i, [_i, _i, _i, _i, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i, _i, _i, _i, _vp]),
 }
 

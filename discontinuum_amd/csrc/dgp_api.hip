@@ -723,7 +723,7 @@ static int run_grad(dgp_plan* p, const double* theta, void* dtheta, hipStream_t 
                       (T*)p->gpart, (T*)dtheta, s, batch_of<T>(p), DGP_OUT_LEN, p->pre, p->pre_ready != 0);
 }
 
-// Whether the two solves run BESIDE lauum on the bulk stream (lowest priority: the trmv workgroups fill whatever slots lauum's grid
+// Whether the two solves run BESIDE lauum on the bulk stream (lowest priority: the solve's workgroups fill whatever slots lauum's grid
 // leaves) instead of in front of it on the caller's stream.  Needs the plan's event pool (lookahead >= 1).  Measured on one box in
 // alternating processes (scripts/env_ab.py, wall ms per step, in front / bulk stream / a highest-priority stream of their own):
 // 32 x n = 8192 274.3 / 273.8 / 274.4 (lauum itself 81.0 -> 83.3 with the solves beside it: its three workgroups per CU leave a trmv
@@ -732,7 +732,8 @@ static int run_grad(dgp_plan* p, const double* theta, void* dtheta, hipStream_t 
 // (below the 1 % bar) while lauum -- the kernel the roofline is quoted on -- reads 3-4 % slower for sharing the GPU (84.8 against
 // 82.4 ms alone, profiles/r05_lauum_three_ways.txt); and not below N = 1024: at the reference's own site size, n = 300, the step is
 // ~0.3 ms of launches and the two cross-stream dependencies cost more than the overlap gains: 0.306 -> 0.334 ms; n = 1024
-// 0.705 -> 0.681, 2048 1.319 -> 1.270, 128 x n = 2048 26.24 -> 25.62.
+// 0.705 -> 0.681, 2048 1.319 -> 1.270, 128 x n = 2048 26.24 -> 25.62.  (Figures of the two-pass trmv kernels.  With the one-pass
+// row kernel, dgp_chol.hip::trsv_rows_kernel, the window stands: 64 x n = 4096 steps 77.78 -> 76.67 ms with it on the bulk stream.)
 template <typename T>
 static bool solve_overlap(const dgp_plan* p) {
   if (p->N < 1024 || p->N > 6144 || !p->lookahead || !p->ev || p->nev < 2 || !p->s2) return false;
@@ -787,7 +788,7 @@ static int fit_step(dgp_plan* p, const double* theta, const void* r, const void*
     if ((rc = run_trtri<T>(p, s))) return rc;
     tick(p, TS_TRTRI, 1, s);
   }
-  // The two triangular solves (HBM-bound: z = T r, alpha = T^T z read T twice) need T and r only, and K^^-1 = T^T T
+  // The two triangular solves (HBM-bound: z = T r and alpha = T^T z from one read of T) need T and r only, and K^^-1 = T^T T
   // (MFMA-bound) needs T only: with a second stream at hand the solves run BESIDE lauum instead of in front of it and join
   // before the gradient contraction, which needs both.  fp32 plans with the refinement keep the order: its scratch is S.
   // (the FUSED kernel -- K^^-1 with the gradient contraction in its epilogue, dgp_fused.hip -- needs alpha before it

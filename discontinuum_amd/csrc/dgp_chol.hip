@@ -1242,55 +1242,179 @@ int lauum(const T* Tm, long N, T* S, hipStream_t s, Batch bt) {
 }
 
 // ------------------------------------------------------------------------------------------
-// z_i = sum_{j <= i} T[i][j] r_j : one wave per row (coalesced along j)
+// Both triangular solves from ONE read of T = L^-1:  z = T r  and the partial sums of  alpha = T^T z.
+// Row i of T is all that z_i = T[i,:] r needs AND all that row i adds to alpha (z_i T[i,:]): a workgroup takes the rows
+// of the pairs (p, N - 1 - p), p = g, g + G, g + 2G, ... of one site (every workgroup gets the same bytes to within one pair), and per row
+//   * holds the row ONCE in registers, 16 bytes per lane per load (columns 16/sizeof(T) * (512 k + thread), k < KT), the next
+//     row's loads in flight while this one is reduced (two register buffers, ping-pong);
+//   * z_i: wave sums, then the eight waves' sums through LDS in a fixed order (one barrier per row, two red slots by parity);
+//   * adds z_i T[i,j] to its own per-column accumulators (registers).
+// r sits in LDS (zero beyond n) when N elements fit in 64 KB, otherwise it is read through the cache.  Only the lower
+// triangle up to the end of the diagonal 128-block is read (the block is zero above its diagonal; beyond it T is not
+// initialised everywhere).  Columns beyond the register capacity 512 * 16/sizeof(T) * KT (fp64: N > 8192) are streamed for
+// z_i, then read again -- from L2, 64 KB ago -- and added into the workgroup's own partials row in memory (no other
+// workgroup touches that row, and a column is always the same thread's).  No atomics: every sum's order is fixed by N alone.
+// a wave's sum in EVERY lane, in a fixed order: an xor butterfly inside each half through ds_swizzle (the lane pattern is an
+// immediate: no index registers, which __shfl_down's bpermute keeps live across the row loop), then the two halves by readlane
 template <typename T>
-__global__ __launch_bounds__(256) void trmv_n_kernel(const T* __restrict__ Tm, long ld, const T* __restrict__ r, int n,
-                                                     T* __restrict__ z, long bs, const int* __restrict__ ns, long rs,
-                                                     long zs = -1 /* site stride of z if it is not the workspace's */) {
+__device__ __forceinline__ T wave_sum_all(T v) {
+  constexpr int NWORD = sizeof(T) / 4;
+  union U {
+    T t;
+    int w[NWORD];
+  };
+#define DGP_SWZ_STEP(XOR)                                                                         \
+  {                                                                                               \
+    U a, b;                                                                                       \
+    a.t = v;                                                                                      \
+    _Pragma("unroll") for (int q = 0; q < NWORD; ++q) b.w[q] = __builtin_amdgcn_ds_swizzle(a.w[q], ((XOR) << 10) | 0x1f); \
+    v += b.t;                                                                                     \
+  }
+  DGP_SWZ_STEP(16) DGP_SWZ_STEP(8) DGP_SWZ_STEP(4) DGP_SWZ_STEP(2) DGP_SWZ_STEP(1)
+#undef DGP_SWZ_STEP
+  U a, lo, hi;
+  a.t = v;
+#pragma unroll
+  for (int q = 0; q < NWORD; ++q) {
+    lo.w[q] = __builtin_amdgcn_readlane(a.w[q], 0);
+    hi.w[q] = __builtin_amdgcn_readlane(a.w[q], 32);
+  }
+  return lo.t + hi.t;
+}
+// 16-byte groups per thread held in registers: rows of up to 8192 columns in either precision (fp32 with 8 groups, twice the
+// columns, does not fit three times -- two rows and the sums -- in the 128 registers of two workgroups per CU)
+#define DGP_SOLVE_KT(T) (int)(sizeof(T) == 8 ? 8 : 4)
+#define DGP_SOLVE_NT 512  // threads of a row workgroup: 8 waves, two workgroups per CU
+template <typename T>
+struct alignas(16) SolvePack {
+  T e[16 / sizeof(T)];
+};
+template <typename T, int KT, bool RL, bool TAIL>
+__global__ __launch_bounds__(DGP_SOLVE_NT, RL ? 4 : 2) void trsv_rows_kernel(const T* __restrict__ Tm, long ld, const T* __restrict__ r, int n,
+                                                           T* __restrict__ z, T* __restrict__ partial, long bs,
+                                                           const int* __restrict__ ns, long rs, long zs, int G) {
+  using P = SolvePack<T>;
+  constexpr int W = 16 / sizeof(T), NT = DGP_SOLVE_NT, NW = NT / 64, SEG = NT * W;
+  constexpr long CAP = (long)KT * SEG;
+  extern __shared__ __attribute__((aligned(16))) unsigned char trsv_smem[];
+  T* red = reinterpret_cast<T*>(trsv_smem);      // [2][NW]
+  T* rl = reinterpret_cast<T*>(trsv_smem + 128);  // [ld] if RL
   Tm = site(Tm, bs);
   z = site(z, zs >= 0 ? zs : bs);
+  partial = site(partial, zs >= 0 ? zs : bs) + (long)blockIdx.x * ld;
   r = site(r, rs);  // site stride of r: n for the caller's residuals, the scratch stride for the refinement's rho
   n = site_n(ns, n);
-  const int lane = threadIdx.x & 63;
-  const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const long jend = (i / NB + 1) * NB;  // the diagonal block is zero above the diagonal
-  const T* row = Tm + i * ld;
-  T acc = T(0);
-  for (long j = lane; j < jend; j += 64) acc += row[j] * (j < n ? r[j] : T(0));
-  acc = wave_sum(acc);
-  if (lane == 0) z[i] = acc;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const long j0 = (long)tid * W;
+  // r in LDS: all KT 16-byte groups of every thread (and the tail's), zero beyond n
+  const long rlen = ld > CAP ? (ld + SEG - 1) / SEG * SEG : CAP;
+  if (RL) {
+    for (long j = tid; j < rlen; j += NT) rl[j] = j < n ? r[j] : T(0);
+    __syncthreads();
+  }
+  auto rvec = [&](long j) {
+    P v;
+    if (RL) {
+      v = *reinterpret_cast<const P*>(rl + j);
+    } else {
+#pragma unroll
+      for (int e = 0; e < W; ++e) v.e[e] = j + e < n ? r[j + e] : T(0);
+    }
+    return v;
+  };
+  P acc[KT];
+#pragma unroll
+  for (int k = 0; k < KT; ++k)
+#pragma unroll
+    for (int e = 0; e < W; ++e) acc[k].e[e] = T(0);
+  for (long j = CAP + j0; TAIL && j < ld; j += SEG) *reinterpret_cast<P*>(partial + j) = acc[0];  // the tail's sums live in memory
+
+  // A row through a buffer descriptor of its own: base and length (the row's bytes up to the end of its diagonal block, < 2^32)
+  // are workgroup-uniform, the lane's part is a 32-bit offset, and a group beyond the row's end reads as zero by the
+  // descriptor's range check -- no 64-bit address per load, no branches.  (The whole offset goes into the VGPR operand: the
+  // range check covers the vector and the immediate offset, not the scalar one.)
+  const int voff = (int)(j0 * (long)sizeof(T));
+  auto load = [&](P(&v)[KT], long i) {
+    const long jend = (i / NB + 1) * NB;  // a multiple of 128: a 16-byte group is inside or outside as a whole
+    const long jreg = jend < CAP ? jend : CAP;
+    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(Tm + i * ld), 0, (int)(jreg * (long)sizeof(T)), 0x00020000);
+#pragma unroll
+    for (int k = 0; k < KT; ++k)
+      v[k] = __builtin_bit_cast(P, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff + k * SEG * (int)sizeof(T), 0, 0));
+  };
+  auto consume = [&](const P(&v)[KT], long i, int par) {
+    const long jend = (i / NB + 1) * NB;
+    const T* row = Tm + i * ld;
+    T d = T(0);
+#pragma unroll
+    for (int k = 0; k < KT; ++k) {  // (groups outside the row hold zeros)
+      const P rr = rvec(j0 + (long)k * SEG);
+#pragma unroll
+      for (int e = 0; e < W; ++e) d += v[k].e[e] * rr.e[e];
+      __builtin_amdgcn_sched_barrier(0);  // one group of r in registers at a time: all KT at once do not fit beside the rows
+    }
+    for (long j = CAP + j0; TAIL && j < jend; j += SEG) {
+      const P t = *reinterpret_cast<const P*>(row + j), rr = rvec(j);
+#pragma unroll
+      for (int e = 0; e < W; ++e) d += t.e[e] * rr.e[e];
+    }
+    d = wave_sum_all(d);
+    if (lane == 0) red[par * NW + wv] = d;
+    __syncthreads();  // the only barrier of a row: the slot written two rows on is read before the barrier in between
+    T zi = T(0);
+#pragma unroll
+    for (int w = 0; w < NW; ++w) zi += red[par * NW + w];
+    if (tid == 0) z[i] = zi;
+#pragma unroll
+    for (int k = 0; k < KT; ++k)
+#pragma unroll
+      for (int e = 0; e < W; ++e) acc[k].e[e] += zi * v[k].e[e];
+    for (long j = CAP + j0; TAIL && j < jend; j += SEG) {
+      const P t = *reinterpret_cast<const P*>(row + j);
+      P a = *reinterpret_cast<P*>(partial + j);
+#pragma unroll
+      for (int e = 0; e < W; ++e) a.e[e] += zi * t.e[e];
+      *reinterpret_cast<P*>(partial + j) = a;
+    }
+  };
+
+  // Rows in pairs (p, N - 1 - p), p = g, g + G, ... < N / 2: a short row and a long one alternate, so every workgroup reads
+  // the same bytes to within one pair AND has about one full row's bytes in flight from its first pair to its last.
+  const long half = ld / 2;
+  auto rowat = [&](long m) {  // the m-th row of this workgroup, or -1 behind the last
+    const long p = (long)blockIdx.x + (m >> 1) * G;
+    return p < half ? ((m & 1) ? ld - 1 - p : p) : -1L;
+  };
+  P va[KT], vb[KT];
+  long m = 0, i = rowat(0), inext;
+  if (i >= 0) load(va, i);
+  while (i >= 0) {
+    if ((inext = rowat(m + 1)) >= 0) load(vb, inext);
+    consume(va, i, 0);
+    if ((i = inext) < 0) break;
+    if ((inext = rowat(m + 2)) >= 0) load(va, inext);
+    consume(vb, i, 1);
+    i = inext;
+    m += 2;
+  }
+#pragma unroll
+  for (int k = 0; k < KT; ++k)
+    if (j0 + (long)k * SEG < ld) *reinterpret_cast<P*>(partial + j0 + (long)k * SEG) = acc[k];
 }
 
-// partial[c][j] = sum_{i in chunk c, i >= blockrow(j)} T[i][j] z_i  (64 columns per workgroup).  Row chunks of 512 for
-// large matrices; 128 below N = 2048, where the 4 x N/128 dependent loads per thread of a 512-chunk are the whole
-// latency of the kernel (N = 384: 19 -> 6 us)
-#define DGP_TRMV_CHUNK 512
-static inline int trmv_chunk(long N) { return N < 2048 ? 128 : DGP_TRMV_CHUNK; }
-template <typename T>
-__global__ __launch_bounds__(256) void trmv_t_kernel(const T* __restrict__ Tm, long ld, const T* __restrict__ z,
-                                                     T* __restrict__ partial, long bs, int chunk, long zs = -1) {
-  Tm = site(Tm, bs);
-  z = site(z, zs >= 0 ? zs : bs);
-  partial = site(partial, zs >= 0 ? zs : bs);
-  __shared__ T red[4][64];
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const long j = (long)blockIdx.x * 64 + tx;
-  const long r0 = (long)blockIdx.y * chunk, r1 = min(r0 + (long)chunk, ld);
-  const long rstart = max(r0, ((long)blockIdx.x * 64 / NB) * NB);
-  T acc = T(0);
-  for (long i = rstart + ty; i < r1; i += 4) acc += Tm[i * ld + j] * z[i];
-  red[ty][tx] = acc;
-  __syncthreads();
-  if (ty == 0) partial[(long)blockIdx.y * ld + j] = red[0][tx] + red[1][tx] + red[2][tx] + red[3][tx];
-}
+// Row groups per site: N / 4 of them (four rows each: a small site's solve is a chain of row latencies) up to 128, where the
+// partial rows cost 2 x 128 / (N / 2) of the triangle's bytes (6 % at N = 8192) and one site still has 128 workgroups reading;
+// a batch of 32 brings 4096.  From N ALONE, not from the batch size: the grouping fixes alpha's summation order, and a site of a
+// batched plan must compute bitwise what the single-site plan computes.
+static inline int solve_groups(long N) { return (int)(N / 4 < 128 ? N / 4 : 128); }
 
-// alpha[j] = sum over the row chunks; the LAST workgroup instead computes quad = z^T z (one launch less; quad == null:
-// the refinement's second solve, whose quadratic form comes from refine_finish_kernel)
+// alpha[j] = the row groups' partial sums in a fixed order (64 columns x 4 group lanes per workgroup, lanes combined in order);
+// the LAST workgroup instead computes quad = z^T z (one launch less; quad == null: the refinement's second solve, whose
+// quadratic form comes from refine_finish_kernel)
 template <typename T>
-__global__ __launch_bounds__(256) void trmv_t_reduce_kernel(const T* __restrict__ partial, long N, int nchunks,
-                                                            T* __restrict__ alpha, long bs, int chunk,
-                                                            const T* __restrict__ z, T* __restrict__ quad, long as = -1,
-                                                            long zs = -1 /* site stride of partial, z and quad (default bs) */) {
+__global__ __launch_bounds__(256) void trsv_reduce_kernel(const T* __restrict__ partial, long N, int G, T* __restrict__ alpha,
+                                                          long bs, const T* __restrict__ z, T* __restrict__ quad, long as = -1,
+                                                          long zs = -1 /* site stride of partial, z and quad (default bs) */) {
   if (zs >= 0) bs = zs;
   if (blockIdx.x == gridDim.x - 1) {
     if (quad == nullptr) return;
@@ -1315,14 +1439,17 @@ __global__ __launch_bounds__(256) void trmv_t_reduce_kernel(const T* __restrict_
   }
   partial = site(partial, bs);
   alpha = site(alpha, as >= 0 ? as : bs);
-  const long j = (long)blockIdx.x * 256 + threadIdx.x;
-  if (j >= N) return;
+  __shared__ T part[4][64];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const long j = (long)blockIdx.x * 64 + tx;  // N % 64 == 0
   T acc = T(0);
-  const int c0 = (int)((j / NB) * NB / chunk);
-  for (int c = c0; c < nchunks; ++c) acc += partial[(long)c * N + j];
-  alpha[j] = acc;
+  for (int g = ty; g < G; g += 4) acc += partial[(long)g * N + j];
+  part[ty][tx] = acc;
+  __syncthreads();
+  if (ty == 0) alpha[j] = (part[0][tx] + part[1][tx]) + (part[2][tx] + part[3][tx]);
 }
 
+#define DGP_TRMV_CHUNK 512  // rows per partial sum of symv_col_kernel
 // beta = S g for a symmetric matrix stored in its lower triangle (nothing above the diagonal is read):
 // row part  sum_{j <= i} S[i][j] g_j  +  column part  sum_{i > j} S[i][j] g_i
 template <typename T>
@@ -1388,36 +1515,56 @@ int symv_lower(const T* S, long N, const T* g, int n, const T* alpha, T* beta, T
   return (int)hipGetLastError();
 }
 
-long solve_partials(long N) { return (N + trmv_chunk(N) - 1) / trmv_chunk(N) * N; }
+static inline long symv_chunks(long N) { return (N + DGP_TRMV_CHUNK - 1) / DGP_TRMV_CHUNK; }
+// one partials row per row group; never fewer than symv_lower's chunk rows, which mean_vjp keeps in a buffer of this size
+long solve_partials(long N) { return (solve_groups(N) > symv_chunks(N) ? solve_groups(N) : symv_chunks(N)) * N; }
 
-// z = T r (r at site stride rs), out = T^T z (at site stride os; < 0: the workspace stride), quad = z^T z unless null
-template <typename T>
-static void solve_pair(const T* Tm, long N, const T* r, long rs, int n, T* z, T* out, long os, T* partials, T* quad, hipStream_t s,
-                       const Batch& bt) {
-  const unsigned Bz = (unsigned)bt.B;
-  trmv_n_kernel<T><<<dim3((unsigned)(N / 4), 1, Bz), 256, 0, s>>>(Tm, N, r, n, z, bt.ws, bt.ns, rs);
-  const int chunk = trmv_chunk(N), nchunks = (int)((N + chunk - 1) / chunk);
-  dim3 grid((unsigned)(N / 64), (unsigned)nchunks, Bz);
-  trmv_t_kernel<T><<<grid, 256, 0, s>>>(Tm, N, z, partials, bt.ws, chunk);
-  trmv_t_reduce_kernel<T><<<dim3((unsigned)((N + 255) / 256) + 1, 1, Bz), 256, 0, s>>>(partials, N, nchunks, out, bt.ws, chunk, z, quad, os);
+// z = T r (r at site stride rs), out = T^T z (at site stride os; < 0: the workspace stride), quad = z^T z unless null;
+// zs >= 0: z, the partials and quad at that site stride instead of the workspace's.  kt: the register capacity in 16-byte
+// groups per thread (0: DGP_SOLVE_KT(T); 1 only from the diagnostic entry point, to reach the beyond-capacity path at small N)
+template <typename T, int KT, bool RL, bool TAIL>
+static int launch_trsv_rows(const T* Tm, long N, const T* r, int n, T* z, T* partials, long rs, long zs, int G, hipStream_t s,
+                            const Batch& bt) {
+  constexpr long SEG = DGP_SOLVE_NT * 16 / (long)sizeof(T), CAP = KT * SEG;
+  const size_t bytes = 128 + (RL ? (size_t)(N > CAP ? (N + SEG - 1) / SEG * SEG : CAP) * sizeof(T) : 0);
+  if (bytes > 64 * 1024) {  // the opt-in for > 64 KB of dynamic LDS belongs to the current device's function object
+    static DeviceOnce configured;
+    (void)configured.run([&] {
+      return hipFuncSetAttribute(reinterpret_cast<const void*>(&trsv_rows_kernel<T, KT, RL, TAIL>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, 128 + 64 * 1024);
+    });
+  }
+  trsv_rows_kernel<T, KT, RL, TAIL><<<dim3((unsigned)G, 1, (unsigned)bt.B), DGP_SOLVE_NT, bytes, s>>>(Tm, N, r, n, z, partials, bt.ws, bt.ns, rs, zs, G);
+  return (int)hipGetLastError();
 }
 template <typename T>
-int solve(const T* Tm, long N, const T* r, int n, T* z, T* alpha, T* partials, T* quad, hipStream_t s, Batch bt) {
-  solve_pair<T>(Tm, N, r, (long)n, n, z, alpha, -1, partials, quad, s, bt);
+static int solve_pair(const T* Tm, long N, const T* r, long rs, int n, T* z, T* out, long os, T* partials, T* quad, long zs,
+                      hipStream_t s, const Batch& bt, int kt = 0) {
+  const int G = solve_groups(N);
+  // r in LDS while N elements fit in 64 KB (fp64: N <= 8192, exactly the sizes whose rows fit the registers; fp32: 16384)
+  const bool rl = (size_t)N * sizeof(T) <= 64 * 1024;
+  constexpr int KT = DGP_SOLVE_KT(T);
+  const bool tail = N > (long)KT * DGP_SOLVE_NT * 16 / (long)sizeof(T);  // fp64: never with r in LDS
+  int rc;
+  if (kt == 1) rc = rl ? launch_trsv_rows<T, 1, true, true>(Tm, N, r, n, z, partials, rs, zs, G, s, bt)
+                       : launch_trsv_rows<T, 1, false, true>(Tm, N, r, n, z, partials, rs, zs, G, s, bt);
+  else if (!rl) rc = launch_trsv_rows<T, KT, false, true>(Tm, N, r, n, z, partials, rs, zs, G, s, bt);
+  else if (!tail) rc = launch_trsv_rows<T, KT, true, false>(Tm, N, r, n, z, partials, rs, zs, G, s, bt);
+  else if constexpr (sizeof(T) == 4) rc = launch_trsv_rows<T, KT, true, true>(Tm, N, r, n, z, partials, rs, zs, G, s, bt);
+  else return (int)hipErrorInvalidValue;  // (unreachable: 8192 doubles are 64 KB)
+  if (rc) return rc;
+  trsv_reduce_kernel<T><<<dim3((unsigned)(N / 64) + 1, 1, (unsigned)bt.B), 256, 0, s>>>(partials, N, G, out, bt.ws, z, quad, os, zs);
   return (int)hipGetLastError();
+}
+template <typename T>
+int solve(const T* Tm, long N, const T* r, int n, T* z, T* alpha, T* partials, T* quad, hipStream_t s, Batch bt, int kt) {
+  return solve_pair<T>(Tm, N, r, (long)n, n, z, alpha, -1, partials, quad, -1, s, bt, kt);
 }
 // the same launches with r, z, the result, the partials and quad all in the caller's work area at ONE site stride `wss`: the
 // plan's own z and alpha are neither read nor written (dgp_censored.hip: u = T^T (T w) beside the fit step's alpha)
 template <typename T>
 int solve_work(const T* Tm, long N, const T* r, int n, T* z, T* out, T* partials, T* quad, long wss, hipStream_t s, Batch bt) {
-  const unsigned Bz = (unsigned)bt.B;
-  trmv_n_kernel<T><<<dim3((unsigned)(N / 4), 1, Bz), 256, 0, s>>>(Tm, N, r, n, z, bt.ws, bt.ns, wss, wss);
-  const int chunk = trmv_chunk(N), nchunks = (int)((N + chunk - 1) / chunk);
-  dim3 grid((unsigned)(N / 64), (unsigned)nchunks, Bz);
-  trmv_t_kernel<T><<<grid, 256, 0, s>>>(Tm, N, z, partials, bt.ws, chunk, wss);
-  trmv_t_reduce_kernel<T><<<dim3((unsigned)((N + 255) / 256) + 1, 1, Bz), 256, 0, s>>>(partials, N, nchunks, out, bt.ws, chunk, z, quad, wss,
-                                                                                      wss);
-  return (int)hipGetLastError();
+  return solve_pair<T>(Tm, N, r, wss, n, z, out, wss, partials, quad, wss, s, bt);
 }
 
 // ---- iterative refinement of the fp32 solve (dgp_internal.h::refine_solve) ------------------------------------------
@@ -1459,7 +1606,7 @@ template <typename T>
 int refine_solve(const T* Tm, long N, const T* r, int n, const double* rho64, const T* rho32, T* z, T* delta, T* alpha,
                  T* partials, T* quad, hipStream_t s, Batch bt, long ps, long rs) {
   // delta sits in the caller's scratch at site stride rs; the quadratic form comes from refine_finish_kernel
-  solve_pair<T>(Tm, N, rho32, rs, n, z, delta, rs, partials, nullptr, s, bt);
+  if (int rc = solve_pair<T>(Tm, N, rho32, rs, n, z, delta, rs, partials, nullptr, -1, s, bt)) return rc;
   refine_finish_kernel<T><<<dim3(1, 1, (unsigned)bt.B), 256, 0, s>>>(alpha, delta, rho64, r, n, quad, bt.ws, ps, rs, bt.ns);
   return (int)hipGetLastError();
 }
@@ -1624,7 +1771,7 @@ int sample_draws(const T* L, long M, const T* Z, long Q, const T* mean, int m, i
   template int trtri_advance<T>(const T*, long, T*, T*, int, TrtriProgress*, hipStream_t, int, int*, int, int, Batch, long);                   \
   template int trtri<T>(const T*, const T*, long, T*, T*, hipStream_t, Batch, long);                                        \
   template int lauum<T>(const T*, long, T*, hipStream_t, Batch);                                                      \
-  template int solve<T>(const T*, long, const T*, int, T*, T*, T*, T*, hipStream_t, Batch);                           \
+  template int solve<T>(const T*, long, const T*, int, T*, T*, T*, T*, hipStream_t, Batch, int);                           \
   template int solve_work<T>(const T*, long, const T*, int, T*, T*, T*, T*, long, hipStream_t, Batch);                \
   template int refine_solve<T>(const T*, long, const T*, int, const double*, const T*, T*, T*, T*, T*, T*, hipStream_t, Batch, long, long); \
   template int predict_v<T>(const T*, long, const T*, long, T*, hipStream_t, Batch, long);                                  \

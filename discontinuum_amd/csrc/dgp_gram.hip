@@ -241,6 +241,28 @@ __global__ __launch_bounds__(256) void gram_diag_kernel(const T* __restrict__ Xs
 // ------------------------------------------------------------------------------------------
 // MODE 0: weights W_ij = S_ij - a_i a_j            (marginal likelihood:  1/2 tr((K^-1 - a a^T) dK))
 // MODE 1: weights W_ij = -(b_i a_j + b_j a_i)       (predictive-mean VJP:  -b^T dK a, symmetrised; S unused)
+// A workgroup walks a RUN of up to DGP_GRAD_RUN consecutive 64 x 64 tiles of one tile row of the lower triangle: the row
+// strip's features, alpha_i, beta_i, the exponent table and ALL the run's column strips are staged once, up front (the four
+// waves share the 1 + RUN strips; nothing else is live in registers while the features are evaluated), then the tiles are
+// summed back to back with no barrier between them, the NTHETA sums carried across the run in registers; finalize, the wave
+// sums and the partials row happen once per run.  Tiles strictly below the diagonal whose rows are all real take a path
+// without the padding / diagonal selects (workgroup-uniform).  Runs of 8: a row of the triangle is cut into runs of equal
+// length but the last, so the workgroups stay balanced; 8 column strips are 28 KB of LDS (loadest d = 3, fp64).
+#define DGP_GRAD_RUN 8
+// the idx-th run, rows in order: the rows 8 q .. 8 q + 7 have q + 1 runs each, 4 q (q + 1) runs lie before them
+__device__ __forceinline__ void grad_run_decode(int idx, int& bi, int& run) {
+  int q = (int)((sqrtf((float)idx + 1.0f) - 1.0f) * 0.5f);
+  while ((DGP_GRAD_RUN / 2) * (q + 1) * (q + 2) <= idx) ++q;
+  while ((DGP_GRAD_RUN / 2) * q * (q + 1) > idx) --q;
+  const int rem = idx - (DGP_GRAD_RUN / 2) * q * (q + 1);
+  bi = DGP_GRAD_RUN * q + rem / (q + 1);
+  run = rem % (q + 1);
+}
+static long grad_runs(long nb) {
+  long total = 0;
+  for (long bi = 0; bi < nb; ++bi) total += bi / DGP_GRAD_RUN + 1;
+  return total;
+}
 template <typename T, typename M, int MODE>
 __global__ __launch_bounds__(256) void gram_grad_kernel(const T* __restrict__ Xt, long N, int n, const PreBatch<M> pb,
                                                         const T* __restrict__ S, const T* __restrict__ alpha,
@@ -253,20 +275,26 @@ __global__ __launch_bounds__(256) void gram_grad_kernel(const T* __restrict__ Xt
   alpha = site(alpha, bs);
   partials = site(partials, MODE == 0 ? bs : wbs);
   if (MODE == 1) beta = site(beta, wbs);
-  __shared__ T sfi[M::NF][64], sfj[M::NF][64], sai[64], saj[64], sbi[64], sbj[64];
+  __shared__ T sfi[M::NF][64], sfj[DGP_GRAD_RUN][M::NF][64], sai[64], saj[DGP_GRAD_RUN][64], sbi[64], sbj[DGP_GRAD_RUN][64];
   __shared__ T red[4][M::NTHETA];
-  int bi, bj;
-  tri_decode(blockIdx.x, bi, bj);
+  int bi, run;
+  grad_run_decode(blockIdx.x, bi, run);
+  const int bj0 = run * DGP_GRAD_RUN, bj1 = min(bj0 + DGP_GRAD_RUN, bi + 1);
   const int t = threadIdx.x;
   exp_table_init<T>();
-  if (t < 64) {
-    stage_strip<T, M>(Xt, N, (long)bi * 64, pre, sfi, t);
-    sai[t] = alpha[(long)bi * 64 + t];
-    sbi[t] = MODE == 1 ? beta[(long)bi * 64 + t] : T(0);
-  } else if (t < 128) {
-    stage_strip<T, M>(Xt, N, (long)bj * 64, pre, sfj, t - 64);
-    saj[t - 64] = alpha[(long)bj * 64 + t - 64];
-    sbj[t - 64] = MODE == 1 ? beta[(long)bj * 64 + t - 64] : T(0);
+  // strip 0 = the row strip, strip 1 + k = the run's k-th column strip: wave w stages the strips w, w + 4, w + 8
+  for (int strip = t >> 6; strip <= bj1 - bj0; strip += 4) {
+    const int l = t & 63;
+    if (strip == 0) {
+      stage_strip<T, M>(Xt, N, (long)bi * 64, pre, sfi, l);
+      sai[l] = alpha[(long)bi * 64 + l];
+      sbi[l] = MODE == 1 ? beta[(long)bi * 64 + l] : T(0);
+    } else {
+      const long base = (long)(bj0 + strip - 1) * 64;
+      stage_strip<T, M>(Xt, N, base, pre, sfj[strip - 1], l);
+      saj[strip - 1][l] = alpha[base + l];
+      sbj[strip - 1][l] = MODE == 1 ? beta[base + l] : T(0);
+    }
   }
   __syncthreads();
   const int ty = t >> 4, tx = t & 15;
@@ -276,29 +304,37 @@ __global__ __launch_bounds__(256) void gram_grad_kernel(const T* __restrict__ Xt
   // one entry at a time: the derivative expressions are register-hungry, occupancy hides latency.  The column
   // point's features come from LDS per entry -- a register array indexed by the rolled loop's counter would live in
   // scratch memory.
+  auto tile = [&](auto interior, int bj, int buf) {
+    constexpr bool INTERIOR = decltype(interior)::value;
 #pragma unroll 1
-  for (int a = 0; a < 4; ++a) {
-    const long gi = (long)bi * 64 + ty * 4 + a;
-    T fi[M::NF];
+    for (int a = 0; a < 4; ++a) {
+      const long gi = (long)bi * 64 + ty * 4 + a;
+      T fi[M::NF];
 #pragma unroll
-    for (int c = 0; c < M::NF; ++c) fi[c] = sfi[c][ty * 4 + a];
-    const T ai = sai[ty * 4 + a], bi_ = sbi[ty * 4 + a];
-    T sv[4] = {T(0), T(0), T(0), T(0)};
-    if (MODE == 0) load4<T>(S + gi * N + (long)bj * 64 + tx * 4, sv);
+      for (int c = 0; c < M::NF; ++c) fi[c] = sfi[c][ty * 4 + a];
+      const T ai = sai[ty * 4 + a], bi_ = sbi[ty * 4 + a];
+      T sv[4] = {T(0), T(0), T(0), T(0)};
+      if (MODE == 0) load4<T>(S + gi * N + (long)bj * 64 + tx * 4, sv);
 #pragma unroll 1
-    for (int b = 0; b < 4; ++b) {
-      const int cj = tx * 4 + b;
-      const long gj = (long)bj * 64 + cj;
-      T fj[M::NF];
+      for (int b = 0; b < 4; ++b) {
+        const int cj = tx * 4 + b;
+        const long gj = (long)bj * 64 + cj;
+        T fj[M::NF];
 #pragma unroll
-      for (int c = 0; c < M::NF; ++c) fj[c] = sfj[c][cj];
-      const T aj = saj[cj];
-      const T svb = b == 0 ? sv[0] : (b == 1 ? sv[1] : (b == 2 ? sv[2] : sv[3]));
-      // lower triangle counted once with weight 1 (= 1/2 * 2), diagonal with 1/2, pad with 0
-      T w = MODE == 0 ? svb - ai * aj : -(bi_ * aj + sbj[cj] * ai);
-      w = (gj > gi || gi >= n) ? T(0) : (gj == gi ? T(0.5) * w : w);
-      (void)M::template pair<true>(fi, fj, pre, w, acc);
+        for (int c = 0; c < M::NF; ++c) fj[c] = sfj[buf][c][cj];
+        const T aj = saj[buf][cj];
+        const T svb = b == 0 ? sv[0] : (b == 1 ? sv[1] : (b == 2 ? sv[2] : sv[3]));
+        // lower triangle counted once with weight 1 (= 1/2 * 2), diagonal with 1/2, pad with 0
+        T w = MODE == 0 ? svb - ai * aj : -(bi_ * aj + sbj[buf][cj] * ai);
+        if (!INTERIOR) w = (gj > gi || gi >= n) ? T(0) : (gj == gi ? T(0.5) * w : w);
+        (void)M::template pair<true>(fi, fj, pre, w, acc);
+      }
     }
+  };
+  const bool rows_real = ((long)bi + 1) * 64 <= n;
+  for (int bj = bj0; bj < bj1; ++bj) {
+    if (rows_real && bj < bi) tile(std::true_type{}, bj, bj - bj0);
+    else tile(std::false_type{}, bj, bj - bj0);
   }
   M::finalize(acc, pre);  // the pair-independent factors of the derivative sums, once per thread
   const int lane = t & 63, wv = t >> 6;
@@ -682,8 +718,7 @@ int gram_grad(int model, int d, const T* Xt, long N, int n, const double* theta,
               void* pre_staging) {
   const int nt = model_ntheta(model, d);
   if (nt < 0) return -2;
-  const long nb = N / 64;
-  const long nblk = nb * (nb + 1) / 2;
+  const long nblk = grad_runs(N / 64);  // (gram_grad_partials: one row per TILE, more than the runs need)
   DGP_DISPATCH_MODEL(model, d,
                      (gram_grad_kernel<T, M, 0><<<dim3((unsigned)nblk, 1, (unsigned)bt.B), dim3(256), 0, s>>>(
                          Xt, N, n, prepare_batch<M>(theta, nt, bt.B, pre_scratch, !pre_ready, s, pre_staging), S, alpha, nullptr,
@@ -701,8 +736,7 @@ int mean_vjp_grad(int model, int d, const T* Xt, long N, int n, const T* Xst, lo
                   long dstride, void* pre_scratch, void* pre_staging) {
   const int nt = model_ntheta(model, d);
   if (nt < 0) return -2;
-  const long nb = N / 64;
-  const long nblk = nb * (nb + 1) / 2;
+  const long nblk = grad_runs(N / 64);
   const unsigned Bz = (unsigned)bt.B;
   DGP_DISPATCH_MODEL(model, d,
                      (gram_grad_kernel<T, M, 1><<<dim3((unsigned)nblk, 1, Bz), dim3(256), 0, s>>>(

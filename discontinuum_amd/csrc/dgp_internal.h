@@ -175,7 +175,7 @@ template <typename T>
 int lauum(const T* Tm, long N, T* S, hipStream_t s, Batch bt = Batch());
 template <typename T>
 int solve(const T* Tm, long N, const T* r, int n, T* z, T* alpha, T* partials, T* quad, hipStream_t s,
-          Batch bt = Batch());
+          Batch bt = Batch(), int kt = 0 /* diagnostic: register capacity of the row kernel, dgp_chol.hip::solve_pair */);
 // fp32 plans, after solve(): one step of iterative refinement with an fp64 residual (dgp_gram.hip::gram_residual).
 //   delta = T^T (T rho32)  (the fp32 factor),  alpha <- alpha + delta,  quad = r^T alpha0 + rho^T (alpha0 + delta) in double
 // (second-order accurate in the error of delta).  z and `partials` are solve()'s scratch; rho32 / delta: N elements each.

@@ -1,4 +1,5 @@
-// dgp_selftest.hip -- diagnostic entry point of the C ABI: a grid of 128 x 128 output tiles through EITHER tile-GEMM core.
+// dgp_selftest.hip -- diagnostic entry points of the C ABI: a grid of 128 x 128 output tiles through EITHER tile-GEMM core, and
+// the fit step's solve kernels on the caller's arrays (dgp_debug_solve, at the end).
 //
 // The O(n^3) stages run on two cores with one contract (dgp_gemm.h::TileGemm, register-staged, and
 // dgp_gemm_dma.h::DmaGemm, direct-to-LDS at three workgroups per CU): same accumulator layout, same order of the k-sum,
@@ -10,6 +11,7 @@
 #include "../../include/dgp_hip.h"
 #include "dgp_gemm.h"
 #include "dgp_gemm_dma.h"
+#include "dgp_internal.h"
 
 namespace dgp {
 
@@ -78,4 +80,24 @@ extern "C" int dgp_debug_tile_gemm(int dtype, int core, int a_kc, int b_kc, cons
   if (dtype == DGP_F64)
     return launch_variant<double>(core, variant, a_kc, b_kc, (const double*)A, lda, (const double*)B, ldb, kt, (double*)C, ldc, grid, s, reverse);
   return launch_variant<float>(core, variant, a_kc, b_kc, (const float*)A, lda, (const float*)B, ldb, kt, (float*)C, ldc, grid, s, reverse);
+}
+
+// The one-pass solve (dgp_chol.hip::solve) outside a plan: the row kernel's path for rows longer than its registers hold is
+// reached by plans only above n = 8192 -- `capacity` = 1 runs it at test sizes (tests/test_gpu_solve_onepass.py).
+extern "C" int64_t dgp_debug_solve_partials(int64_t N) {
+  return (N < 128 || N % 128 != 0 || N > 65536) ? (int64_t)DGP_E_ARG : (int64_t)dgp::solve_partials((long)N);
+}
+extern "C" int dgp_debug_solve(int dtype, int capacity, const void* Tm, int64_t N, const void* r, int64_t n, void* z, void* alpha,
+                               void* partials, void* quad, void* stream) {
+  using namespace dgp;
+  if ((dtype != DGP_F64 && dtype != DGP_F32) || (capacity != 0 && capacity != 1) || !Tm || !r || !z || !alpha || !partials || !quad ||
+      N < 128 || N % 128 != 0 || N > 65536 || n < 1 || n > N || ((uintptr_t)Tm & 15) || ((uintptr_t)partials & 15) || ((uintptr_t)quad & 7))
+    return DGP_E_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == DGP_F64)
+    return solve<double>((const double*)Tm, (long)N, (const double*)r, (int)n, (double*)z, (double*)alpha, (double*)partials, (double*)quad, s,
+                         Batch(), capacity);
+  // fp32: the plan's scalar-block layout -- the rounded value at quad[1], the unrounded double 3 floats on (8-byte aligned)
+  return solve<float>((const float*)Tm, (long)N, (const float*)r, (int)n, (float*)z, (float*)alpha, (float*)partials, (float*)quad + 1, s,
+                      Batch(), capacity);
 }

@@ -842,6 +842,17 @@ int dgp_debug_tile_gemm(int dtype, int core, int a_kc, int b_kc, const void* A_d
  * `roofline.clock_mhz`; no product kernel carries a stamp. */
 int dgp_debug_clock_probe(void* out_dev, int nwg, double seconds, void* stream);
 
+/* The fit step's two triangular solves on caller-supplied device arrays (dtype DGP_F64 / DGP_F32): with T = Tm_dev (N x N
+ * row-major, N % 128 == 0, 128 <= N <= 65536, 16-byte aligned; read up to the end of each row's diagonal 128-block only),
+ *   z = T r (r_j = 0 for j >= n),  alpha = T^T z,  quad[0] = z^T z   (quad holds 8 elements, 8-byte aligned; fp32: the value
+ * rounded to float at quad[1] and, summed in double and unrounded, as ONE double in quad[4..5] -- a plan's scalar block).
+ * `partials_dev`: scratch of dgp_debug_solve_partials(N) elements, 16-byte aligned.  `capacity` 0 runs the kernels exactly as a
+ * plan does; 1 shrinks the row kernel's register capacity to one 16-byte group per thread, so that the path for rows longer
+ * than the registers hold (fp64: N > 8192 in a plan) runs at small N.  DGP_E_ARG on a bad argument, before any launch. */
+int dgp_debug_solve(int dtype, int capacity, const void* Tm_dev, int64_t N, const void* r_dev, int64_t n, void* z_dev,
+                    void* alpha_dev, void* partials_dev, void* quad_dev, void* stream);
+int64_t dgp_debug_solve_partials(int64_t N);
+
 #ifdef __cplusplus
 }
 #endif
