@@ -270,6 +270,65 @@ class GPPlan:
         """The same without gradients (the prediction-time cache build) -> (out[32], f_hat[n], stat)."""
         return self._laplace(False, theta, y, mean, noise, side, f, maxit, tol, upper)
 
+    # ------------------------------------------------------------------ censored observations (expectation propagation)
+    def _ep(self, with_grad, theta, y, mean, noise, side, sites, maxit, tol, damping, upper):
+        name = "dgp_ep_fit_step" if with_grad else "dgp_ep_factorize"
+        if self.dtype != torch.float64 or self.batch != 1:
+            raise ValueError(f"{name}: expectation propagation needs a float64 single-site plan")
+        for t, what in ((y, "y"), (mean, "mean"), (noise, "noise")) + (() if upper is None else ((upper, "upper"),)):
+            self._check_vec(t, what)
+        if not (torch.is_tensor(side) and side.is_cuda and side.dtype == torch.int32 and side.is_contiguous()
+                and side.numel() == self.n):
+            raise ValueError(f"side must be a contiguous int32 CUDA tensor with {self.n} elements")
+        if sites is None:  # cold start
+            yt, nt = torch.empty_like(y), torch.empty_like(noise)
+        else:
+            yt, nt = sites
+            self._check_vec(yt, "sites[0]")
+            self._check_vec(nt, "sites[1]")
+            yt, nt = yt.clone(), nt.clone()
+        th = _theta_array(theta, self.ntheta)
+        stat = (C.c_double * 6)()
+        with torch.cuda.device(self.device):
+            need = int(self.lib.dgp_ep_workspace_bytes(self._h))
+            work = self._work_area("_ep_ws", need, name)
+            out = torch.empty(_lib.OUT_LEN, dtype=self.dtype, device=self.device)
+            dr = torch.empty(self.n, dtype=self.dtype, device=self.device) if with_grad else None
+            aux = torch.empty((3, self.n), dtype=self.dtype, device=self.device)
+            args = (self._h, th, _ptr(y), _ptr(mean), _ptr(noise), _ptr(side), _ptr(upper), _ptr(yt), _ptr(nt), int(sites is None),
+                    int(maxit), float(tol), float(damping), work, need, _ptr(out))
+            tail = (stat, _ptr(aux[0]), _ptr(aux[1]), _ptr(aux[2]), _stream())
+            rc = getattr(self.lib, name)(*args, _ptr(dr), *tail) if with_grad else getattr(self.lib, name)(*args, *tail)
+        self.ep_stat = tuple(float(v) for v in stat)  # kept for a caller that catches E_NOCONV
+        self.ep_aux = {"cav_mean": aux[0], "cav_var": aux[1], "logz": aux[2]}
+        self.ep_sites = (yt, nt)
+        _lib.check(rc, name)
+        return (out, dr, (yt, nt), self.ep_stat) if with_grad else (out, (yt, nt), self.ep_stat)
+
+    def ep_fit_step(self, theta, y, mean, noise, side, sites=None, maxit=100, tol=1e-10, damping=1.0, upper=None):
+        """One fit step with censored rows (``side`` / ``upper`` as for ``laplace_fit_step``) by EXPECTATION PROPAGATION
+        (``dgp_ep_fit_step``): parallel sweeps of moment matching from ``sites`` = (y~, n~) (None: cold, from the Laplace terms at
+        the prior mean), each one factorisation, then the step at the final sites.  -> (out[32], dr[n], (y~, n~), stat) with
+        ``out[OUT_NLL]`` = -log Z_EP, ``out[OUT_DTHETA:]`` its gradient (the engine's explicit gradient at the fixed point),
+        dr = alpha and stat = (sweeps, final max |dmu|, final max v |dtau|, capped rows, rows held back, censored rows).  The plan
+        holds the factorisation of the pseudo-data system (y~ - mean, n~), and ``self.ep_aux`` the cavities and log Z^ of that
+        state.  ``DGPError`` with code ``E_NOCONV`` when ``maxit`` sweeps do not suffice (``self.ep_stat`` / ``self.ep_sites`` are set
+        either way).  float64 single-site plans only."""
+        return self._ep(True, theta, y, mean, noise, side, sites, maxit, tol, damping, upper)
+
+    def ep_factorize(self, theta, y, mean, noise, side, sites=None, maxit=100, tol=1e-10, damping=1.0, upper=None):
+        """The same without gradients (the prediction-time cache build) -> (out[32], (y~, n~), stat)."""
+        return self._ep(False, theta, y, mean, noise, side, sites, maxit, tol, damping, upper)
+
+    def ep_diag(self):
+        """diag((K^)^-1) (n,) of the factorisation the plan holds, as an EP sweep computes it from L^-1 (``dgp_ep_diag``)."""
+        with torch.cuda.device(self.device):
+            need = int(self.lib.dgp_ep_workspace_bytes(self._h))
+            work = self._work_area("_ep_ws", need, "dgp_ep_diag")
+            k = torch.empty(self.n, dtype=self.dtype, device=self.device)
+            _lib.check(self.lib.dgp_ep_diag(self._h, _ptr(k), work, need, _stream()), "dgp_ep_diag")
+        return k
+
     def interval_terms(self, za: torch.Tensor, delta: torch.Tensor):
         """(4, count): log P, sigma g, W v, sigma^3 d3 of the brackets [za, za + delta] as the interval-censored fit evaluates
         them (P = Phi(zb) - Phi(za))."""

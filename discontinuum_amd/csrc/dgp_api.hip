@@ -1320,7 +1320,148 @@ static int laplace_entry(dgp_plan* p, const double* theta, const void* y, const 
   return wrap(rc, where);
 }
 
+// ---- censored observations by expectation propagation (dgp_ep.hip): parallel sweeps on the factorise path, then (fit step) one
+// step at the final sites, whose explicit gradient IS the gradient at the fixed point.  The host reads one status block per sweep.
+// The sites that were factorised last are the result (a converged or last sweep's proposal is not applied), so the plan's
+// factorisation, k, the cavities and log Z^ belong to one state.  stat: [6].
+static int ep(dgp_plan* p, const double* theta, const double* y, const double* mean, const double* noise, const int* side,
+              const double* upper, double* yt, double* nt, int cold, int maxit, double tol, double damping, char* work, double* out,
+              double* dr, double* stat, double* cav_mean, double* cav_var, double* logz, int with_grad, const char* where, hipStream_t s) {
+  const EpLayout L = ep_layout(p->N, p->n);
+  const Batch bt = batch_of<double>(p);
+  auto D = [&](size_t off) { return (double*)(work + off); };
+  const int n = (int)p->n;
+  const double* alpha = (const double*)p->alpha;
+  const double* Tm = (const double*)p->Tm;
+  double st[CEN_ST_LEN > EP_ST_LEN ? CEN_ST_LEN : EP_ST_LEN];
+  auto read_status = [&](size_t off, int len) -> int {
+    hipError_t e = hipMemcpyAsync(st, D(off), sizeof(double) * (size_t)len, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    return (int)e;
+  };
+  int rc;
+  for (int k = 0; k < 6; ++k) stat[k] = 0.0;
+  // the Laplace terms at f = m: the rows are checked as the Laplace entries check them, and a cold start is their pseudo-data
+  if ((rc = censored_terms(mean, y, side, noise, mean, n, 1, 0, work, L.cen, s, bt, upper)) || (rc = read_status(L.cen.status, CEN_ST_LEN)))
+    return rc;
+  if (st[CEN_ST_BAD] != 0.0) {
+    snprintf(g_err, sizeof(g_err),
+             upper ? "%s: side values must be -1, 0, +1 or 2" : "%s: a row of side 2 needs upper_dev; other side values must be -1, 0 or +1",
+             where);
+    return DGP_E_ARG;
+  }
+  if (st[CEN_ST_BADBRK] != 0.0) {
+    snprintf(g_err, sizeof(g_err), "%s: %d bad bracket(s): a row of side 2 needs a finite upper above its y", where, (int)st[CEN_ST_BADBRK]);
+    return DGP_E_ARG;
+  }
+  const double ncens = st[CEN_ST_NCENS];
+  stat[5] = ncens;
+  const bool aux = cav_mean || cav_var || logz;
+  if (ncens == 0.0) {  // nothing censored: the plain step on (y - m, v), bit for bit; the sites are (y, v)
+    if ((rc = fit_step<double>(p, theta, D(L.cen.rt), D(L.cen.nn), out, with_grad ? dr : nullptr, with_grad ? D(L.cen.dnoise) : nullptr,
+                               with_grad, s)) ||
+        (rc = ep_init(y, side, noise, mean, yt, nt, n, 1, work, L, s)))
+      return rc;
+    if (aux && ((rc = ep_diag(Tm, p->N, n, D(L.kdiag), work, L, s)) ||
+                (rc = ep_result(alpha, y, side, noise, upper, yt, nt, n, nullptr, cav_mean, cav_var, logz, work, L, s))))
+      return rc;
+    return 0;
+  }
+  if ((rc = ep_init(y, side, noise, mean, yt, nt, n, cold, work, L, s))) return rc;
+  int it = 0;
+  bool conv = false;
+  for (;;) {
+    if ((rc = fit_step<double>(p, theta, D(L.cen.rt), nt, D(L.cen.out), nullptr, nullptr, 0, s))) return rc;
+    ++it;
+    if ((rc = ep_sweep(Tm, p->N, alpha, y, side, noise, mean, upper, yt, nt, n, it, it >= maxit, tol, damping, work, L, s)) ||
+        (rc = read_status(L.status, EP_ST_LEN)))
+      return rc;
+    stat[0] = (double)it;
+    stat[1] = st[EP_ST_DMU];
+    stat[2] = st[EP_ST_DTAU];
+    stat[3] = st[EP_ST_CAPPED];
+    stat[4] = st[EP_ST_HELD];
+    conv = st[EP_ST_DONE] != 0.0;  // converged, or not positive definite: the result row reports that through DGP_OUT_INFO
+    if (conv || it >= maxit) break;
+  }
+  if (with_grad) {
+    // the same system once more with K^^-1 and the gradient contraction: the same T and alpha, so k stays valid
+    if ((rc = fit_step<double>(p, theta, D(L.cen.rt), nt, out, dr, D(L.cen.dnoise), 1, s))) return rc;
+  } else if ((rc = (int)hipMemcpyAsync(out, D(L.cen.out), sizeof(double) * DGP_OUT_LEN, hipMemcpyDeviceToDevice, s))) {
+    return rc;
+  }
+  if ((rc = ep_result(alpha, y, side, noise, upper, yt, nt, n, out, cav_mean, cav_var, logz, work, L, s)) || (rc = (int)hipStreamSynchronize(s)))
+    return rc;
+  if (!conv) {
+    snprintf(g_err, sizeof(g_err), "%s: expectation propagation did not converge in %d sweeps (max |dmu| = %.3g, max v |dtau| = %.3g)",
+             where, it, stat[1], stat[2]);
+    return DGP_E_NOCONV;
+  }
+  return 0;
+}
+static int ep_entry(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise, const int32_t* side,
+                    const void* upper, void* yt, void* nt, int cold, int maxit, double tol, double damping, void* work, size_t work_bytes,
+                    void* out, void* dr, double* stat, void* cav_mean, void* cav_var, void* logz, int with_grad, const char* where,
+                    void* stream) {
+  char msg[200];
+  if (!p) return fail(DGP_E_ARG, "null plan");
+  if (p->dtype != DGP_F64 || p->B != 1) {
+    snprintf(msg, sizeof(msg), "%s: expectation propagation needs a float64 single-site plan (fp32 and batched plans are not supported)", where);
+    return fail(DGP_E_ARG, msg);
+  }
+  if (!theta || !y || !mean || !noise || !side || !yt || !nt || !out || !stat || maxit < 1 || !(tol >= 0.0)) {
+    snprintf(msg, sizeof(msg), "%s: null argument (ytilde_dev / ntilde_dev included), maxit < 1 or a negative tol", where);
+    return fail(DGP_E_ARG, msg);
+  }
+  if (!(damping > 0.0 && damping <= 1.0)) {
+    snprintf(msg, sizeof(msg), "%s: damping must lie in (0, 1]", where);
+    return fail(DGP_E_ARG, msg);
+  }
+  DGP_CHECK_PLAN(p);
+  if (!p->have_inputs) return fail(DGP_E_STATE, "dgp_ep_*: call dgp_set_inputs first");
+  if (!work || work_bytes < dgp_ep_workspace_bytes(p)) {
+    snprintf(msg, sizeof(msg), "%s: workspace missing or too small", where);
+    return fail(DGP_E_WORKSPACE, msg);
+  }
+  if (((uintptr_t)work & 255) != 0) return fail(DGP_E_ARG, "dgp_ep_*: the work area must be 256-byte aligned");
+  const int rc = ep(p, theta, (const double*)y, (const double*)mean, (const double*)noise, (const int*)side, (const double*)upper,
+                    (double*)yt, (double*)nt, cold, maxit, tol, damping, (char*)work, (double*)out, (double*)dr, stat, (double*)cav_mean,
+                    (double*)cav_var, (double*)logz, with_grad, where, (hipStream_t)stream);
+  if (rc == DGP_E_ARG || rc == DGP_E_NOCONV) return rc;  // text set where it arose
+  return wrap(rc, where);
+}
+
 extern "C" {
+
+size_t dgp_ep_workspace_bytes(const dgp_plan* p) {
+  if (!p || p->dtype != DGP_F64 || p->B != 1) return 0;
+  return ep_layout(p->N, p->n).total;
+}
+
+int dgp_ep_fit_step(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise, const int32_t* side,
+                    const void* upper, void* ytilde, void* ntilde, int cold_start, int maxit, double tol, double damping, void* work,
+                    size_t work_bytes, void* out, void* dr, double* stat, void* cav_mean, void* cav_var, void* logz, void* stream) {
+  return ep_entry(p, theta, y, mean, noise, side, upper, ytilde, ntilde, cold_start, maxit, tol, damping, work, work_bytes, out, dr, stat,
+                  cav_mean, cav_var, logz, 1, "dgp_ep_fit_step", stream);
+}
+
+int dgp_ep_factorize(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise, const int32_t* side,
+                     const void* upper, void* ytilde, void* ntilde, int cold_start, int maxit, double tol, double damping, void* work,
+                     size_t work_bytes, void* out, double* stat, void* cav_mean, void* cav_var, void* logz, void* stream) {
+  return ep_entry(p, theta, y, mean, noise, side, upper, ytilde, ntilde, cold_start, maxit, tol, damping, work, work_bytes, out, nullptr,
+                  stat, cav_mean, cav_var, logz, 0, "dgp_ep_factorize", stream);
+}
+
+int dgp_ep_diag(dgp_plan* p, void* k, void* work, size_t work_bytes, void* stream) {
+  if (!p || p->dtype != DGP_F64 || p->B != 1) return fail(DGP_E_ARG, "dgp_ep_diag: needs a float64 single-site plan");
+  if (!k) return fail(DGP_E_ARG, "dgp_ep_diag: null argument");
+  DGP_CHECK_PLAN(p);
+  if (!p->have_factor) return fail(DGP_E_STATE, "dgp_ep_diag: no factorisation in the plan");
+  if (!work || work_bytes < dgp_ep_workspace_bytes(p)) return fail(DGP_E_WORKSPACE, "dgp_ep_diag: workspace missing or too small");
+  if (((uintptr_t)work & 255) != 0) return fail(DGP_E_ARG, "dgp_ep_diag: the work area must be 256-byte aligned");
+  return wrap(ep_diag((const double*)p->Tm, p->N, (int)p->n, (double*)k, (char*)work, ep_layout(p->N, p->n), (hipStream_t)stream),
+              "dgp_ep_diag");
+}
 
 size_t dgp_laplace_workspace_bytes(const dgp_plan* p) {
   if (!p || p->dtype != DGP_F64 || p->B != 1) return 0;

@@ -494,4 +494,43 @@ int laplace_cross_validate(int model, int d, const double* Xt, const double* Tm,
                            const LaplaceCvLayout& L, double* out, int* info, hipStream_t s, Batch bt, void* pre_scratch,
                            void* pre_staging);
 
+// ---- dgp_ep.hip: censored rows by expectation propagation -- Gaussian sites (y~, n~) found by parallel sweeps, each ONE
+// factorisation of the pseudo-data system plus O(n) passes and the diagonal of the inverse.  fp64, one site.  The work area is an
+// EpLayout: a CensoredLayout first (the terms pass at f = m validates the rows and gives the cold start; its rt holds r~, its
+// `out` the result row of the sweep's factorisation), then the proposals, the previous means, k and the partials.
+#define EP_PART 8  // doubles per workgroup of the block partials
+enum {
+  EP_ST_DMU = 0,  // max |mu - mu_prev| of the sweep (first sweep: max v |nu' - nu~|); inf when the factorisation failed
+  EP_ST_DTAU,     // max v |tau' - tau~|
+  EP_ST_CAPPED,   // proposals at the cap
+  EP_ST_HELD,     // rows held back by the guard (v_c <= 0 or 1 - W v_c <= 0)
+  EP_ST_NCENS,
+  EP_ST_DONE,     // 0: the sweeps go on; k > 0: ended in sweep k (converged, or not positive definite)
+  EP_ST_INFO,     // DGP_OUT_INFO of the sweep's factorisation
+  EP_ST_CONV,     // 1: both tests passed
+  EP_ST_CORR,     // NLL_EP - NLL_engine (ep_result)
+  EP_ST_LEN = 16
+};
+struct EpLayout {
+  CensoredLayout cen;
+  size_t yprop, nprop, muprev, kdiag, kpart, part, status, total;  // byte offsets
+  int nchunk, nblk;
+};
+EpLayout ep_layout(long N, long n);
+// the sites before the first sweep, after censored_terms(f = m, init) has filled L.cen: cold != 0: every censored row from the
+// Laplace terms at m; else the caller's (a row without a usable site starts cold).  Rows of side 0: (y, v).  Writes r~ to L.cen.rt.
+int ep_init(const double* y, const int* side, const double* v, const double* m, double* yt, double* nt, int n, int cold, char* work,
+            const EpLayout& L, hipStream_t s);
+// k_i = sum_{j >= i} T_ji^2, i < n, from the row-major lower triangle T = L^-1 (leading dimension N)
+int ep_diag(const double* Tm, long N, int n, double* k, char* work, const EpLayout& L, hipStream_t s);
+// after the factorisation at (r~, n~) left T and alpha in the plan and its result row in L.cen.out: k, proposals, test, status; the
+// proposals replace the sites (and r~) only when the sweep neither converged nor is the last
+int ep_sweep(const double* Tm, long N, const double* alpha, const double* y, const int* side, const double* v, const double* m,
+             const double* upper, double* yt, double* nt, int n, int sweep, int last, double tol, double damping, char* work,
+             const EpLayout& L, hipStream_t s);
+// out[DGP_OUT_NLL] += NLL_EP - NLL_engine (out null: not wanted) from alpha and L.kdiag; cavities and log Z^ (n doubles each, nullable)
+int ep_result(const double* alpha, const double* y, const int* side, const double* v, const double* upper, const double* yt,
+              const double* nt, int n, double* out, double* cav_mean, double* cav_var, double* logz, char* work, const EpLayout& L,
+              hipStream_t s);
+
 }  // namespace dgp

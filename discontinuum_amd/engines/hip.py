@@ -216,11 +216,14 @@ class CensorState:
     above, 0 = observed, 2 = the truth lies between the target value and ``upper``), ``upper`` (device, model space, read on
     the rows of side 2 only; None when there is no such row), the latest mode ``f`` of the Laplace approximation (device;
     None = cold start from the prior mean) and the ``status`` of the last mode search (Newton iterations, final max |df|,
-    halvings, capped rows)."""
+    halvings, capped rows).  ``approximation`` = "ep": the fit runs expectation propagation instead; ``sites`` = (y~, n~) are then
+    the warm start between training iterations (None = cold) and ``status`` the last call's (sweeps, final max |dmu|, final max
+    v |dtau|, capped rows, rows held back, censored rows)."""
 
-    def __init__(self, side, maxit=50, tol=1e-10, upper=None):
+    def __init__(self, side, maxit=50, tol=1e-10, upper=None, approximation="laplace", ep_maxit=100, damping=1.0):
         self.side, self.f, self.status, self.maxit, self.tol = side, None, None, int(maxit), float(tol)
         self.upper = upper
+        self.approximation, self.sites, self.ep_maxit, self.damping = approximation, None, int(ep_maxit), float(damping)
 
     def kwargs(self):
         """The keyword arguments of ``GPPlan.laplace_*`` that the bracketed rows add (none without such a row: the
@@ -229,6 +232,9 @@ class CensorState:
 
     def update(self, f, status):
         self.f, self.status = f.detach(), tuple(status)
+
+    def update_sites(self, sites, status):
+        self.sites, self.status = tuple(t.detach() for t in sites), tuple(status)
 
 
 def censor_sides(censored, n, bracketed=False):
@@ -252,6 +258,14 @@ def censor_sides(censored, n, bracketed=False):
                              "2 (between the target value and an upper end) needs target_upper")
         side = a.astype(np.int32)
     return side if side.any() else None
+
+
+def _approximation_name(approximation):
+    """``fit(approximation=...)`` as "laplace" or "ep" (None: "laplace")."""
+    name = "laplace" if approximation is None else approximation
+    if name not in ("laplace", "ep"):
+        raise ValueError(f'approximation must be "laplace" or "ep", got {approximation!r}')
+    return name
 
 
 MIDPOINT_WIDTH = 1e-6  # a bracket narrower than this many sigma is an observation at its midpoint
@@ -325,6 +339,8 @@ class MarginalHIP(BaseModel):
         self._censor = None  # CensorState of a fit with censored observations
         self._y_model = None
         self.laplace_status_ = None
+        self.ep_status_ = None
+        self._approximation = "laplace"
 
     # ------------------------------------------------------------------ device plumbing
     def _tensor(self, a):
@@ -366,19 +382,26 @@ class MarginalHIP(BaseModel):
 
     def _refuse_censored(self, what, hint=""):
         if getattr(self, "_censor", None) is not None:
-            raise NotImplementedError(self._CENSOR_REFUSAL.format(what=what) + hint)
+            text = self._CENSOR_REFUSAL.format(what=what)
+            if self._censor.approximation == "ep":
+                text = text.replace("the Laplace approximation", "expectation propagation")
+            raise NotImplementedError(text + hint)
 
-    def _set_censoring(self, censored, n, target_upper=None, y=None):
+    def _set_censoring(self, censored, n, target_upper=None, y=None, approximation=None):
         """Parse ``censored`` and ``target_upper`` (see ``fit``) and keep them on the engine; the side vector (and the upper
         ends) go to the device with the data.  ``y``: the model-space targets (needed with ``target_upper``).  -> the
         model-space targets the fit runs on: ``y`` itself unless a bracketed row changed its entry (a decreasing transform
-        swaps a bracket's ends; a very narrow bracket becomes an observation at its midpoint)."""
+        swaps a bracket's ends; a very narrow bracket becomes an observation at its midpoint).  ``approximation``: "laplace" or
+        "ep" (None: what the engine holds, "laplace" unless a fit or a checkpoint said otherwise)."""
+        if approximation is not None:
+            self._approximation = _approximation_name(approximation)
         side = censor_sides(censored, n, bracketed=target_upper is not None)
         self._censor_host = side  # as given: what a checkpoint carries
         self._upper_host = None   # data space, as given
         self._y_model = None      # the model-space targets of a fit with bracketed rows (numpy), where they differ from dm.y
         self._censor = None
         self.laplace_status_ = None
+        self.ep_status_ = None
         if side is None:
             return y
         if getattr(self.likelihood, "second_noise_covar", None) is not None:
@@ -405,10 +428,20 @@ class MarginalHIP(BaseModel):
                 return y
         self._censor = CensorState(torch.as_tensor(side, dtype=torch.int32).to(self.device).contiguous(),
                                    maxit=self.laplace_maxit, tol=self.laplace_tol,
-                                   upper=None if upper is None else self._tensor(upper))
+                                   upper=None if upper is None else self._tensor(upper),
+                                   approximation=getattr(self, "_approximation", "laplace"), ep_maxit=self.ep_maxit,
+                                   damping=self.ep_damping)
         return y
 
     laplace_maxit, laplace_tol = 50, 1e-10  # Newton's mode search of a censored fit
+    ep_maxit, ep_damping = 100, 1.0         # the sweeps of a censored fit by expectation propagation (tolerance: laplace_tol)
+
+    def _record_censor_status(self):
+        if self._censor is not None:
+            if self._censor.approximation == "ep":
+                self.ep_status_ = self._censor.status
+            else:
+                self.laplace_status_ = self._censor.status
 
     def _mean_shortcut(self):
         """The host-side form of this model's prior mean and noise (``MeanShortcut``) or None.  Here: a learned
@@ -480,6 +513,7 @@ class MarginalHIP(BaseModel):
             "censored": None if getattr(self, "_censor_host", None) is None else torch.as_tensor(self._censor_host, dtype=torch.int8),
             "target_upper": (None if getattr(self, "_upper_host", None) is None
                              else torch.as_tensor(self._upper_host, dtype=torch.float64)),
+            "approximation": getattr(self, "_approximation", "laplace"),
             "optimizer_state_dict": None, "optimizer_name": None, "optimizer_lr": None,
             "scheduler_state_dict": None, "scheduler_name": None,
         }
@@ -515,10 +549,11 @@ class MarginalHIP(BaseModel):
                                f"unexpected parameters {unexpected}")
 
     @classmethod
-    def load(cls, f, covariates, target, target_unc=None, censored=None, target_upper=None):
+    def load(cls, f, covariates, target, target_unc=None, censored=None, target_upper=None, approximation=None):
         """A model restored from ``save()`` output and re-attached to its data: ready to predict, or to continue
         training with ``fit(..., resume=True)`` (engines/gpytorch.py:47-105).  ``censored`` / ``target_upper``: as in
-        ``fit``; None takes what the checkpoint carries (the codes and the brackets' upper ends).  The file is read with
+        ``fit``; None takes what the checkpoint carries (the codes and the brackets' upper ends).  ``approximation``: None takes
+        the checkpoint's ("laplace" for a checkpoint written before expectation propagation existed).  The file is read with
         ``weights_only=True`` (nothing in it is executed); checkpoints of earlier versions that pickled the
         ``ModelConfig`` dataclass load under an allow-list of exactly that class."""
         with torch.serialization.safe_globals([ModelConfig]):
@@ -541,7 +576,9 @@ class MarginalHIP(BaseModel):
             censored = record["censored"].numpy().astype(np.int32)  # the side vector the checkpoint carries
             if target_upper is None and record.get("target_upper") is not None:
                 target_upper = record["target_upper"].numpy()  # and the brackets' upper ends (data space)
-        y = self._set_censoring(censored, y.shape[0], target_upper, y)
+        if approximation is None:
+            approximation = record.get("approximation") or "laplace"
+        y = self._set_censoring(censored, y.shape[0], target_upper, y, approximation)
         self._setup_device(x, y)
         self.is_fitted = True
         return self
@@ -569,7 +606,7 @@ class MarginalHIP(BaseModel):
     def fit(self, covariates, target, target_unc=None, iterations: int = 100, optimizer: str | None = None,
             learning_rate: float | None = None, early_stopping: bool = False, patience: int = 60,
             scheduler: bool = True, resume: bool = False, penalty_callback=None, penalty_weight: float = 0.0, censored=None,
-            target_upper=None):
+            target_upper=None, approximation="laplace"):
         """Train the hyperparameters; arguments and behaviour as ``MarginalGPyTorch.fit``
         (engines/gpytorch.py:162-458): Adam (default lr 0.05) or AdamW, gradient clipping to norm 1, optional
         ReduceLROnPlateau, NaN iterations skipped (more than ten in a row raise), optional early stopping, resume from a
@@ -590,7 +627,16 @@ class MarginalHIP(BaseModel):
         bracket's ends, which are then sorted in model space.  A bracket narrower than 1e-6 sigma (the row's noise standard
         deviation in model space) is taken as an observation at its midpoint: the likelihood of so narrow a bracket is the
         Gaussian density there times the width, so this shifts the reported NLL by the constant -sum log(width_i) over
-        those rows and leaves the mode and every gradient unchanged to O(width^2 / sigma^2)."""
+        those rows and leaves the mode and every gradient unchanged to O(width^2 / sigma^2).
+
+        ``approximation``: "laplace" (the default; None means the same) or "ep".  With "ep" the censored rows are fitted by
+        EXPECTATION PROPAGATION (``dgp_ep_fit_step``): Gaussian sites matched to the moments of the tilted distributions instead of
+        a Gaussian at the posterior's mode -- the better approximation when most rows are censored far below their limits and
+        the posterior is one-sided.  The sites are warm-started between training iterations; ``ep_status_`` keeps the last call's
+        (sweeps, final max |dmu|, final max v |dtau|, capped rows, rows held back, censored rows).  Every product that reads the
+        held factorisation then sees the EP posterior.  Without a censored row "ep" is the plain fit.  The keyword of THIS call
+        decides: a resumed fit (or one that continues a loaded checkpoint) states it again."""
+        approximation = _approximation_name(approximation)
         trained = bool(getattr(self, "model", None) is not None and getattr(self, "likelihood", None) is not None
                        and self.is_fitted)
         from_checkpoint = trained and self._resume_info is not None
@@ -605,12 +651,15 @@ class MarginalHIP(BaseModel):
         if not restore:
             self._fresh_model(x, y, unc)
         if censored is not None or not restore:
-            y = self._set_censoring(censored, y.shape[0], target_upper, y)
+            y = self._set_censoring(censored, y.shape[0], target_upper, y, approximation)
         elif getattr(self, "_upper_host", None) is not None:  # a resumed fit keeps its brackets
-            y = self._set_censoring(self._censor_host, y.shape[0], self._upper_host, y)
+            y = self._set_censoring(self._censor_host, y.shape[0], self._upper_host, y, approximation)
+        elif self._censor is not None and self._censor.approximation != approximation:
+            y = self._set_censoring(self._censor_host, y.shape[0], None, y, approximation)
         self._setup_device(x, y)
         if self._censor is not None:
             self._censor.f = None
+            self._censor.sites = None
         self.model.train()
         self.likelihood.train()
 
@@ -663,8 +712,7 @@ class MarginalHIP(BaseModel):
                             penalty_weight=float(penalty_weight) if use_penalty else 0.0)], dtype=torch.float64)
                     else:
                         objective = -mll(self._prior(), self._train_y)
-                        if self._censor is not None:
-                            self.laplace_status_ = self._censor.status
+                        self._record_censor_status()
                 except Exception:
                     bad_in_a_row += 1
                     if bad_in_a_row > 10:
@@ -747,7 +795,14 @@ class MarginalHIP(BaseModel):
         if self._factor_key != key:
             with torch.no_grad():
                 spec = self._prior()
-                if spec.censored is not None:  # the Laplace posterior's pseudo-data system, warm-started at the last mode
+                if spec.censored is not None and spec.censored.approximation == "ep":  # the EP posterior's pseudo-data system
+                    cs = spec.censored
+                    out, sites, stat = self._plan.ep_factorize(
+                        spec.theta, self._train_y, spec.mean.contiguous(), spec.noise.contiguous(), cs.side, sites=cs.sites,
+                        maxit=cs.ep_maxit, tol=cs.tol, damping=cs.damping, **cs.kwargs())
+                    cs.update_sites(sites, stat)
+                    self.ep_status_ = cs.status
+                elif spec.censored is not None:  # the Laplace posterior's pseudo-data system, warm-started at the last mode
                     cs = spec.censored
                     out, f_hat, stat = self._plan.laplace_factorize(
                         spec.theta, self._train_y, spec.mean.contiguous(), spec.noise.contiguous(), cs.side, f=cs.f,

@@ -115,6 +115,40 @@ def laplace_gp_nll(plan, theta, y, mean, noise, state, shortcut):
         lambda jitter: _LaplaceNLL.apply(plan, theta, y, mean, noise + jitter, state, shortcut, *params))
 
 
+class _EPNLL(torch.autograd.Function):
+    """The data term of a censored fit by expectation propagation: -log Z_EP and its gradients from one ``dgp_ep_fit_step``
+    (parallel sweeps on the factorise path, one step at the final sites).  At the fixed point the gradient with respect to the
+    kernel hyperparameters is the engine's explicit gradient at the sites and d NLL / d r = alpha: no implicit term.  ``state``
+    (``engines/hip.py::CensorState``) carries the side vector and the sites of the warm start, and receives the final sites and
+    the sweeps' status.  Mean parameters as in ``_LaplaceNLL``; the noise gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, plan, theta, y, mean, noise, state, shortcut, *params):
+        out, dr, sites, stat = plan.ep_fit_step(theta, y, mean.detach().contiguous(), noise.detach().contiguous(), state.side,
+                                                sites=state.sites, maxit=state.ep_maxit, tol=state.tol, damping=state.damping,
+                                                **state.kwargs())
+        host = out.to("cpu", torch.float64)
+        info = int(host[_lib.OUT_INFO].item())
+        if info != 0:
+            raise NotPSDError(f"Matrix not positive definite: Cholesky pivot {info} is not positive")
+        state.update_sites(sites, stat)
+        ctx.save_for_backward(host[_lib.OUT_DTHETA:_lib.OUT_DTHETA + plan.ntheta].clone(), dr)
+        ctx.param_grads = shortcut.grads(host) if shortcut is not None else ()
+        ctx.dtypes = (theta.dtype,) + tuple(p.dtype for p in params)
+        ctx.shapes = tuple(p.shape for p in params)
+        return host[_lib.OUT_NLL].clone()
+
+    backward = staticmethod(_LaplaceNLL.backward)
+
+
+def ep_gp_nll(plan, theta, y, mean, noise, state, shortcut):
+    """The EP data term behind the same jitter-retry policy as ``exact_gp_nll``."""
+    params = shortcut.params if shortcut is not None else ()
+    return _with_jitter_retries(
+        plan, lambda: _EPNLL.apply(plan, theta, y, mean, noise, state, shortcut, *params),
+        lambda jitter: _EPNLL.apply(plan, theta, y, mean, noise + jitter, state, shortcut, *params))
+
+
 class _PredictiveMean(torch.autograd.Function):
     """K(X*, X; theta) K^^-1 r as a differentiable function of (theta, r, noise): forward is
     ``dgp_predict_mean``, backward ``dgp_mean_vjp``.  Both read the factorisation the plan holds from the
@@ -242,7 +276,8 @@ class ExactMarginalLogLikelihood:
                 mean = (target - r).contiguous()  # the shortcut's constant mean as a device vector
             else:
                 mean, noise = output.mean.contiguous(), output.noise.contiguous()
-            nll = laplace_gp_nll(output.plan, output.theta, target, mean, noise, censored, shortcut)
+            data_term = ep_gp_nll if getattr(censored, "approximation", "laplace") == "ep" else laplace_gp_nll
+            nll = data_term(output.plan, output.theta, target, mean, noise, censored, shortcut)
             return ((-nll + self.log_prior()) / n).reshape(1)
         if shortcut is not None:  # mean / noise parameters on the host: device vectors without autograd
             r, noise = shortcut.residual_and_noise(output.plan, target)

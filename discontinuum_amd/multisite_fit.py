@@ -479,6 +479,15 @@ def _refuse_censored_records(datasets, what):
                                       "through the censored= argument (one entry per site)")
 
 
+def _refuse_ep(approximation, what):
+    if approximation not in (None, "laplace", "ep"):
+        raise ValueError(f'approximation must be "laplace" or "ep", got {approximation!r}')
+    if approximation == "ep":
+        raise NotImplementedError(f'{what}: approximation="ep" is not available for a batch of sites: expectation propagation runs on '
+                                  "single-site plans only (its lockstep batched form does not exist yet); fit the sites one by one "
+                                  'with fit(approximation="ep")')
+
+
 def _site_sides(models, censored, sizes, what, target_upper=None):
     """``censored`` (None, or one entry per site: None, a boolean mask, or -1 / 0 / +1; 2 for a site with a ``target_upper``
     entry) as a list of int32 side vectors / None, through ``engines.hip.censor_sides``; refuses what the censored fit does not
@@ -508,7 +517,7 @@ def fit_many(models, datasets, iterations: int = 100, learning_rate: float = 0.0
              monotonic_penalty_weight: float = 0.0, grid_size: int = 64, monotonic_penalty_interval: int = 1,
              resume: FitManyState | None = None, return_state: bool = False, generator: torch.Generator | None = None,
              optimizer: str = "adam", penalty_callback=None, penalty_weight: float = 0.0, site_seeds=None,
-             closed_form: bool = True, censored=None, target_upper=None, _penalty_uniforms=None):
+             closed_form: bool = True, censored=None, target_upper=None, approximation="laplace", _penalty_uniforms=None):
     """Fit ``models[i]`` to ``datasets[i] = (covariates, target[, target_unc])`` for all i at once.  Returns the
     per-site final objectives (a float64 tensor) -- with ``return_state=True`` the pair (objectives, ``FitManyState``);
     the models are updated in place (``is_fitted``, parameters, device state).
@@ -556,7 +565,11 @@ def fit_many(models, datasets, iterations: int = 100, learning_rate: float = 0.0
     space, aligned with its target; read on the rows whose ``censored`` code is 2), as ``MarginalHIP.fit(target_upper=...)``: the
     same pipeline rule (the site's target pipeline as fitted on its target), the same sorting of the ends under a decreasing
     transform and the same midpoint rule for brackets narrower than 1e-6 sigma.  The device step is then ONE batched
-    ``dgp_laplace_interval_fit_step``; afterwards every model carries its brackets like after its own ``fit``."""
+    ``dgp_laplace_interval_fit_step``; afterwards every model carries its brackets like after its own ``fit``.
+
+    ``approximation``: "laplace" only.  "ep" (``MarginalHIP.fit(approximation="ep")``) is refused: expectation propagation runs
+    on single-site plans; its lockstep batched form does not exist yet."""
+    _refuse_ep(approximation, "fit_many")
     if site_seeds is not None and len(site_seeds) != len(models):
         raise ValueError("site_seeds needs one seed per model")
     _refuse_censored_records(datasets, "fit_many")
@@ -598,7 +611,7 @@ def fit_many(models, datasets, iterations: int = 100, learning_rate: float = 0.0
         for b, m in enumerate(models):
             if sides[b] is None or not (sides[b] == 2).any():
                 continue
-            ys[b] = m._set_censoring(censored[b], sizes[b], target_upper[b], ys_given[b])
+            ys[b] = m._set_censoring(censored[b], sizes[b], target_upper[b], ys_given[b], "laplace")
             if m._censor is None:  # every bracket of the site was narrower than the midpoint rule's width
                 sides[b] = None
                 continue
@@ -916,7 +929,7 @@ def _hand_back_censoring(m, side, nb, cstate, b, target_upper=None, y=None):
     """The site's censoring onto its model, as ``fit(censored=)`` leaves it: the side vector (with ``target_upper`` and the
     model-space targets ``y`` as given: the brackets), and -- from a batch's state -- the last mode (the warm start of the model's
     own cache build) and the last mode search's status."""
-    y_fit = m._set_censoring(side, nb, target_upper, y)
+    y_fit = m._set_censoring(side, nb, target_upper, y, "laplace")
     if y_fit is not None and getattr(m, "_pending_device", None) is not None:
         m._pending_device = (m._pending_device[0], y_fit)  # the targets the fit ran on (a bracket's lower end or midpoint)
     if m._censor is not None and cstate is not None and cstate.f is not None:
@@ -967,6 +980,7 @@ def fit_many_distributed(models, datasets, group=None, load: str = "all", seed: 
     if load not in ("all", "rank0", "own"):
         raise ValueError("load must be 'all', 'rank0' or 'own'")
     _refuse_censored_records(datasets, "fit_many_distributed")
+    _refuse_ep(kw.get("approximation"), "fit_many_distributed")
     if "resume" in kw or kw.get("return_state") or "site_seeds" in kw:
         raise ValueError("fit_many_distributed: resume / return_state are per-rank; use fit_many on each rank's share")
     if len(models) != len(datasets) or not models:
@@ -1066,6 +1080,10 @@ def censored_cache_build(plan, models, theta, ys, means, noises, sizes, n):
         return out.to(device).contiguous()
 
     cens = [getattr(m, "_censor", None) for m in models]
+    if any(c is not None and getattr(c, "approximation", "laplace") == "ep" for c in cens):
+        raise NotImplementedError('the batched products (predict_many, annual_flux_many, aggregate_many) cannot serve a model fitted '
+                                  'with approximation="ep": their cache build is the batched Laplace factorisation, which would put a '
+                                  "Laplace mode under EP hyperparameters; use the model's own predict / annual_flux")
     side = slots([torch.zeros(nb, dtype=torch.int32) if c is None else c.side for c, nb in zip(cens, sizes)], 0, torch.int32)
     mean = slots(means)
     start = slots([mu if c is None or c.f is None else c.f for c, mu in zip(cens, means)])

@@ -122,6 +122,11 @@ def _wants_cavity(model, laplace, what):
         raise ValueError(f'laplace must be None or "cavity", got {laplace!r}')
     if getattr(model, "_censor", None) is None:
         return False
+    if getattr(model._censor, "approximation", "laplace") == "ep":
+        raise NotImplementedError(
+            f'{what} is not available for a fit with approximation="ep": the cavity folds hold the pseudo-data at a Laplace MODE, '
+            "which would be computed at hyperparameters trained for the EP posterior (the cross-validation of an EP fit, from the "
+            "cavities dgp_ep_* returns, does not exist yet)")
     if laplace is None:
         model._refuse_censored(what, hint=CAVITY_HINT)
     return True

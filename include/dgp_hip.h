@@ -306,6 +306,63 @@ int dgp_laplace_interval_fit_step(dgp_plan* plan, const double* theta_host, cons
 int dgp_laplace_interval_factorize(dgp_plan* plan, const double* theta_host, const void* y_dev, const void* mean_dev,
                                    const void* noise_dev, const int32_t* side_dev, const void* upper_dev, void* f_dev, int maxit,
                                    double tol, void* work_dev, size_t work_bytes, void* out_dev, double* stat_host, void* stream);
+/* CENSORED OBSERVATIONS BY EXPECTATION PROPAGATION.  The Laplace approximation above centres the Gaussian on the MODE of the
+ * posterior; with most rows censored far below their limits that posterior is one-sided and its mean lies well away from the
+ * mode.  EP keeps a Gaussian SITE (pseudo-target y~_i, pseudo-noise n~_i; tau~ = 1 / n~, nu~ = y~ / n~) on every censored row
+ * (side -1 / +1 / 2 as above) and matches moments; rows of side 0 keep their exact site (y, v).  An EP state is a GP regression on
+ * (y~, n~), so the plan holds the result exactly as it holds a Laplace mode, and every product reads it unchanged.
+ *   a sweep         = one dgp_factorize pass with r~ = y~ - m and n~: alpha, T = L^-1, k_i = [(K + diag n~)^-1]_ii = sum_{j >= i} T_ji^2;
+ *                     the cavity  v_c = 1 / k - n~,  mu_c = y~ - alpha / k  (the leave-one-out predictive of that regression);
+ *                     log Z^, g = d log Z^ / d mu_c, W = -d2 log Z^ / d mu_c^2 by the pointwise functions above at the standard
+ *                     deviation s = sqrt(v + v_c) (one-sided: z = side (mu_c - l) / s; bracket: za = (y - mu_c) / s, zb = (upper -
+ *                     mu_c) / s; g and W scale by 1 / s and 1 / s^2);  tau' = W / (1 - W v_c),  y' = mu_c + g / W;  damped in the
+ *                     natural parameters: tau~ <- (1 - damping) tau~ + damping tau', nu~ likewise.  All censored rows at once.
+ *   guards          CAP: tau' v < 1e-12 -> tau' = 1e-12 / v, y' kept, the row is counted.  HOLD: v_c <= 0 or 1 - W v_c <= 0 (or not
+ *                   a number) -> the row keeps its site for this sweep and is counted.
+ *   convergence     max_i |mu_i - mu_i^prev| <= tol over all rows, mu = y~ - n~ o alpha the posterior mean at the samples (in the
+ *                   first sweep, which has no previous mean: max v |nu' - nu~| over the censored rows), AND max v |tau' - tau~| <= tol.
+ *                   (Sigma_ii = n~ - n~^2 k is not tested: pure cancellation for nearly uninformative rows.)
+ *   final state     the proposal of the sweep that converged -- or of the last sweep -- is NOT applied: the sites returned are the
+ *                   ones that were factorised, so the plan's factorisation, the cavities and log Z^ belong to one state.
+ *   value           NLL_EP = NLL_engine(r~, n~) - sum_censored [log Z^_i + 1/2 log 2 pi - 1/2 log k_i + alpha_i^2 / (2 k_i)]
+ *   gradient        at the fixed point dNLL_EP / dtheta is the engine's explicit gradient at the sites and dNLL_EP / dr = alpha:
+ *                   dgp_ep_fit_step ends with one dgp_fit_step pass at the final sites and returns its DTHETA, SUM_DR, DR_W0.. and
+ *                   dr as they are.  No implicit term, no pair sweep.
+ *   y_dev / mean_dev / noise_dev / side_dev / upper_dev   as for dgp_laplace_interval_* (upper_dev may be null without a row of side 2)
+ *   ytilde_dev, ntilde_dev   n doubles each, in: the sites of a warm start (read on the censored rows; a row without a finite y~ and
+ *               a positive finite n~ starts cold), out: the final sites of every row
+ *   cold_start  != 0: ignore their contents and start every censored row from the Laplace terms at f = m (n~ = 1 / W(m),
+ *               y~ = m + g / W, with the Laplace cap)
+ *   maxit, tol, damping   sweeps at most (>= 1), the tolerance of both tests (>= 0), damping in (0, 1]
+ *   out_dev     DGP_OUT_* layout: NLL = NLL_EP; QUAD, LOGDET, INFO and (fit step) DTHETA, SUM_DR, DR_W0.., SUM_DNOISE those of the
+ *               pseudo-data system; dgp_ep_factorize: the row of the last sweep's factorisation, dtheta = 0
+ *   dr_dev      alpha (n doubles, or null)
+ *   stat_host   6 doubles: sweeps, final max |dmu|, final max v |dtau|, capped rows, rows held back, censored rows (the counts are
+ *               those of the last sweep)
+ *   cav_mean_dev, cav_var_dev, logz_dev   n doubles each or null: mu_c, v_c and log Z^ of the final state (rows of side 0: their
+ *               leave-one-out predictive and log N(y | mu_c, v + v_c))
+ * Passes: the Laplace terms at m (row checks, cold start) -> status read; per sweep: dgp_factorize's launches, k (n^2 / 2 doubles read
+ * once, coalesced along the columns of the row-major T), sites, finish -> status read: ONE STREAM SYNCHRONISATION PER SWEEP; then
+ * (fit step) dgp_fit_step's launches, the result pass and one more synchronisation.  No floating-point atomics: bitwise repeatable.
+ * With no censored row both entries launch exactly what dgp_fit_step / dgp_factorize launch on (y - m, v) -- the same bits in
+ * out_dev, dr_dev and the plan -- report 0 sweeps and return the sites (y, v).
+ * float64 single-site plans only.  Before any launch: DGP_E_ARG (null plan / argument; an fp32 or batched plan -- the text says
+ * so; maxit < 1; tol < 0; damping outside (0, 1]; misaligned work area), DGP_E_WORKSPACE, DGP_E_STATE (no inputs).  After the first
+ * pass: DGP_E_ARG for a bad side value or a bad bracket, as for dgp_laplace_interval_*.  DGP_E_NOCONV when the tests still fail
+ * after maxit sweeps: everything is filled, the sites are those of the last factorisation.  A matrix that is not positive definite
+ * ends the sweeps and is reported through out[DGP_OUT_INFO], return code 0. */
+size_t dgp_ep_workspace_bytes(const dgp_plan* plan); /* 0 for null / fp32 / batched */
+int dgp_ep_fit_step(dgp_plan* plan, const double* theta_host, const void* y_dev, const void* mean_dev, const void* noise_dev,
+                    const int32_t* side_dev, const void* upper_dev, void* ytilde_dev, void* ntilde_dev, int cold_start, int maxit,
+                    double tol, double damping, void* work_dev, size_t work_bytes, void* out_dev, void* dr_dev, double* stat_host,
+                    void* cav_mean_dev, void* cav_var_dev, void* logz_dev, void* stream);
+int dgp_ep_factorize(dgp_plan* plan, const double* theta_host, const void* y_dev, const void* mean_dev, const void* noise_dev,
+                     const int32_t* side_dev, const void* upper_dev, void* ytilde_dev, void* ntilde_dev, int cold_start, int maxit,
+                     double tol, double damping, void* work_dev, size_t work_bytes, void* out_dev, double* stat_host,
+                     void* cav_mean_dev, void* cav_var_dev, void* logz_dev, void* stream);
+/* k_dev[i] = [(K^)^-1]_ii = sum_{j >= i} T_ji^2, i < n, from the factorisation the plan holds (any of the entries above): the
+ * diagonal pass of an EP sweep alone, for tests and timing.  work_dev: dgp_ep_workspace_bytes.  DGP_E_STATE without a factorisation. */
+int dgp_ep_diag(dgp_plan* plan, void* k_dev, void* work_dev, size_t work_bytes, void* stream);
 /* out [4][count] = log P, sigma g, W v, sigma^3 d3 of the brackets [za, za + Delta]: the pointwise functions of the two entries
  * above, for tests.  za_dev, delta_dev: count doubles on the device (Delta > 0). */
 int dgp_debug_interval_terms(const double* za_dev, const double* delta_dev, int64_t count, double* out_dev, void* stream);
