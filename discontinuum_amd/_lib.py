@@ -96,6 +96,10 @@ SIGNATURES = {
     "dgp_ep_fit_step": (_i, [_vp, _dp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, C.c_double, _vp, _sz, _vp, _vp, _dp, _vp, _vp, _vp, _vp]),
     "dgp_ep_factorize": (_i, [_vp, _dp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, C.c_double, _vp, _sz, _vp, _dp, _vp, _vp, _vp, _vp]),
     "dgp_ep_diag": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "dgp_loo_workspace_bytes": (_sz, [_vp]),
+    "dgp_loo_value_workspace_bytes": (_sz, [_vp]),
+    "dgp_loo_fit_step": (_i, [_vp, _dp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "dgp_loo_value": (_i, [_vp, _vp, _sz, _vp, _vp]),
     "dgp_debug_interval_terms": (_i, [_vp, _vp, _i64, _vp, _vp]),
     "dgp_debug_censored_terms": (_i, [_vp, _i64, _vp, _vp]),
     "dgp_debug_bilinear": (_i, [_vp, _dp, _vp, _vp, _vp, _sz, _vp, _vp]),

@@ -212,6 +212,39 @@ class GPPlan:
             _lib.check(self.lib.dgp_factorize(self._h, th, _ptr(r), _ptr(noise), _ptr(out), _stream()), "dgp_factorize")
         return out
 
+    # ------------------------------------------------------------------ leave-one-out training objective
+    def loo_fit_step(self, theta, r: torch.Tensor, noise: torch.Tensor):
+        """The fit step of the leave-one-out predictive likelihood L_LOO = -elpd of ``cross_validate`` with folds of one:
+        -> (out, dr, dnoise) with exactly the shapes and slots of ``fit_step``, ``out[OUT_NLL]`` = L_LOO and every gradient
+        slot that of L_LOO; QUAD, LOGDET, INFO are the factorisation's.  The plan holds afterwards what ``fit_step`` with the
+        same arguments leaves.  float64 plans (include/dgp_hip.h ``dgp_loo_fit_step``)."""
+        self._check_vec(r, "r")
+        self._check_vec(noise, "noise")
+        th = _theta_array(theta, self.ntheta * self.batch)
+        shape = (lambda k: (k,)) if self.batch == 1 else (lambda k: (self.batch, k))
+        with torch.cuda.device(self.device):
+            need = int(self.lib.dgp_loo_workspace_bytes(self._h))
+            work = self._work_area("_loo_ws", need, "dgp_loo_fit_step")
+            out = torch.empty(shape(_lib.OUT_LEN), dtype=self.dtype, device=self.device)
+            dr = torch.empty(shape(self.n), dtype=self.dtype, device=self.device)
+            dnoise = torch.empty(shape(self.n), dtype=self.dtype, device=self.device)
+            _lib.check(
+                self.lib.dgp_loo_fit_step(self._h, th, _ptr(r), _ptr(noise), work, need, _ptr(out), _ptr(dr), _ptr(dnoise),
+                                          _stream()),
+                "dgp_loo_fit_step",
+            )
+        return out, dr, dnoise
+
+    def loo_value(self):
+        """(L_LOO, info) -- (batch, 2) for a batched plan -- as float64 device tensor, from the factorisation the plan holds
+        when the last step left K^^-1 in it (``fit_step`` / ``loo_fit_step``)."""
+        with torch.cuda.device(self.device):
+            need = int(self.lib.dgp_loo_value_workspace_bytes(self._h))
+            work = self._work_area("_loo_ws", need, "dgp_loo_value")
+            out = torch.empty(2 if self.batch == 1 else (self.batch, 2), dtype=torch.float64, device=self.device)
+            _lib.check(self.lib.dgp_loo_value(self._h, work, need, _ptr(out), _stream()), "dgp_loo_value")
+        return out
+
     # ------------------------------------------------------------------ censored observations (Laplace)
     def _laplace(self, with_grad, theta, y, mean, noise, side, f, maxit, tol, upper=None):
         B = self.batch

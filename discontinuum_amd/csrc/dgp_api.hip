@@ -2203,4 +2203,55 @@ int dgp_debug_clock_probe(void* out_dev, int nwg, double seconds, void* stream) 
   return wrap((int)hipGetLastError(), "dgp_debug_clock_probe");
 }
 
+// ---- the leave-one-out predictive likelihood as a training objective (dgp_loo.hip): dgp_fit_step's launches, untouched, into a
+// scratch result row, then the passes that read the S and alpha it left.  The plan's A / T / S / z / alpha stay as the step left them.
+static LooLayout loo_layout_of(const dgp_plan* p, bool value_only) {
+  const Layout L = layout(p);
+  return loo_layout(p->N, p->B, value_only ? 0 : p->site_bytes, L.A, L.Tm, L.S, L.alpha, L.gpart);
+}
+static const char* const LOO_F64 =
+    "dgp_loo_*: the leave-one-out objective needs a float64 plan (its bilinear gradient pass exists for float64 only: fp32 plans are "
+    "not supported)";
+
+size_t dgp_loo_workspace_bytes(const dgp_plan* p) {
+  if (!p || p->dtype != DGP_F64) return 0;
+  return loo_layout_of(p, false).total;
+}
+size_t dgp_loo_value_workspace_bytes(const dgp_plan* p) {
+  if (!p || p->dtype != DGP_F64) return 0;
+  return loo_layout_of(p, true).total;
+}
+
+int dgp_loo_fit_step(dgp_plan* p, const double* theta, const void* r, const void* noise, void* work, size_t work_bytes, void* out,
+                     void* dr, void* dnoise, void* stream) {
+  if (!p) return fail(DGP_E_ARG, "null plan");
+  if (p->dtype != DGP_F64) return fail(DGP_E_ARG, LOO_F64);
+  DGP_CHECK_PLAN(p);
+  if (!theta || !r || !noise || !out) return fail(DGP_E_ARG, "dgp_loo_fit_step: null argument");
+  if (!p->have_inputs) return fail(DGP_E_STATE, "dgp_loo_fit_step: call dgp_set_inputs first");
+  if (!work || work_bytes < dgp_loo_workspace_bytes(p)) return fail(DGP_E_WORKSPACE, "dgp_loo_fit_step: workspace missing or too small");
+  if (((uintptr_t)work & 255) != 0) return fail(DGP_E_ARG, "dgp_loo_fit_step: the work area must be 256-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const LooLayout L = loo_layout_of(p, false);
+  int rc = fit_step<double>(p, theta, r, noise, (char*)work + L.out0, dr, dnoise, 1, s);
+  if (rc) return wrap(rc, "dgp_loo_fit_step");
+  rc = loo_gradient(p->model, p->d, (const double*)p->Xt, (const double*)p->S, (const double*)p->alpha, p->N, (int)p->n, theta,
+                    (const double*)p->dr_w, (char*)work, L, (double*)out, (double*)dr, (double*)dnoise, s, batch_of<double>(p), p->pre);
+  return wrap(rc, "dgp_loo_fit_step");
+}
+
+int dgp_loo_value(dgp_plan* p, void* work, size_t work_bytes, void* out2, void* stream) {
+  if (!p) return fail(DGP_E_ARG, "null plan");
+  if (p->dtype != DGP_F64) return fail(DGP_E_ARG, LOO_F64);
+  DGP_CHECK_PLAN(p);
+  if (!out2) return fail(DGP_E_ARG, "dgp_loo_value: null argument");
+  if (!p->have_factor || !p->have_inverse)
+    return fail(DGP_E_STATE, "dgp_loo_value: needs the K^^-1 a fit step leaves in the plan (dgp_fit_step or dgp_loo_fit_step; dgp_factorize does not form it)");
+  if (!work || work_bytes < dgp_loo_value_workspace_bytes(p)) return fail(DGP_E_WORKSPACE, "dgp_loo_value: workspace missing or too small");
+  if (((uintptr_t)work & 255) != 0) return fail(DGP_E_ARG, "dgp_loo_value: the work area must be 256-byte aligned");
+  const int rc = loo_value((const double*)p->S, (const double*)p->alpha, p->info, p->N, (int)p->n, (char*)work, loo_layout_of(p, true),
+                           (double*)out2, (hipStream_t)stream, batch_of<double>(p));
+  return wrap(rc, "dgp_loo_value");
+}
+
 }  // extern "C"

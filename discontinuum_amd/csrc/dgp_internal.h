@@ -533,4 +533,27 @@ int ep_result(const double* alpha, const double* y, const int* side, const doubl
               const double* nt, int n, double* out, double* cav_mean, double* cav_var, double* logz, char* work, const EpLayout& L,
               hipStream_t s);
 
+// ---- dgp_loo.hip: the leave-one-out predictive likelihood L_LOO = -elpd of cross_validate("loo") and its gradient, from S = K^^-1
+// and alpha as a fit step leaves them.  fp64, single-site or batched.  The work area holds one SLICE per site that mirrors the plan's
+// site (same size, same offsets: F where the plan has A, G where it has T, 2 M where it has S, a zero vector where it has alpha, the
+// contraction's partials where it has its own -- gram_grad addresses all of them at ONE site stride), then the sites' vectors, then
+// the step's own result rows.
+struct LooLayout {
+  size_t slice, F, G, M, zero, gpart;          // a site's slice and the byte offsets inside it
+  size_t w, c, b, negb, spart, part, vec;      // byte offsets inside a site's vectors, and their size
+  size_t vecs, out0, total;                    // byte offsets of the vectors and of the scratch result rows [B][DGP_OUT_LEN]
+  int nblk;                                    // workgroups per site of the row passes
+};
+LooLayout loo_layout(long N, int B, size_t site_bytes, size_t offA, size_t offT, size_t offS, size_t offalpha, size_t offgpart);
+// out2 [B][2] = (L_LOO, info): info = the factorisation's status `info` ([0] of a site's block) if non-zero, else the 1-based index of
+// the first row whose k_i is not a positive finite number (0: none); the value is NaN unless info == 0.  Reads S and alpha only.
+int loo_value(const double* S, const double* alpha, const int* info, long N, int n, char* work, const LooLayout& L, double* out2,
+              hipStream_t s, Batch bt);
+// after fit_step(with_grad) wrote its result rows to work + L.out0: the LOO result rows `out` (NLL = L_LOO, DTHETA and the reduced
+// slots those of L_LOO; QUAD, LOGDET, INFO the step's own unless a row is bad), dr = b, dnoise.  wts: the plan's dr weights or null.
+// Reads Xt, S and alpha only; the step's Gram build must have left theta in pre_scratch (a batch of more than 8).
+int loo_gradient(int model, int d, const double* Xt, const double* S, const double* alpha, long N, int n, const double* theta,
+                 const double* wts, char* work, const LooLayout& L, double* out, double* dr, double* dnoise, hipStream_t s, Batch bt,
+                 void* pre_scratch);
+
 }  // namespace dgp

@@ -26,7 +26,7 @@ from .. import _lib
 from ..backend import GPPlan
 from ..gp.explicit import ExplicitObjective
 from ..gp.lowering import lower
-from ..gp.mll import ExactMarginalLogLikelihood, NotPSDError, predictive_mean
+from ..gp.mll import ExactMarginalLogLikelihood, NotPSDError, objective_name, predictive_mean
 from ..xr_compat import DataArray
 from .base import BaseModel, ModelConfig, is_fitted
 
@@ -303,9 +303,10 @@ class PriorSpec:
     read), -- for mean / noise models that have one -- the host-side ``shortcut`` the marginal likelihood uses
     instead of them, and the ``CensorState`` of a fit with censored observations."""
 
-    def __init__(self, plan, theta, mean, noise, shortcut=None, censored=None):
+    def __init__(self, plan, theta, mean, noise, shortcut=None, censored=None, objective="mll"):
         self.plan, self.theta, self._mean, self._noise, self.shortcut = plan, theta, mean, noise, shortcut
         self.censored = censored
+        self.objective = objective  # "mll" or "loo": which data term the marginal-likelihood object evaluates
         self.upper = getattr(censored, "upper", None)  # the upper ends of the bracketed rows (model space) or None
 
     @property
@@ -341,6 +342,7 @@ class MarginalHIP(BaseModel):
         self.laplace_status_ = None
         self.ep_status_ = None
         self._approximation = "laplace"
+        self.objective_ = "mll"  # the training objective of the last fit: "mll" or "loo"
 
     # ------------------------------------------------------------------ device plumbing
     def _tensor(self, a):
@@ -369,6 +371,7 @@ class MarginalHIP(BaseModel):
             noise=lambda: self.likelihood.train_noise(self._train_x.device, self.dtype),
             shortcut=self._mean_shortcut(),
             censored=getattr(self, "_censor", None),
+            objective=getattr(self, "objective_", "mll"),
         )
 
     def model_space_targets(self):
@@ -514,6 +517,7 @@ class MarginalHIP(BaseModel):
             "target_upper": (None if getattr(self, "_upper_host", None) is None
                              else torch.as_tensor(self._upper_host, dtype=torch.float64)),
             "approximation": getattr(self, "_approximation", "laplace"),
+            **({} if getattr(self, "objective_", "mll") == "mll" else {"objective": self.objective_}),
             "optimizer_state_dict": None, "optimizer_name": None, "optimizer_lr": None,
             "scheduler_state_dict": None, "scheduler_name": None,
         }
@@ -578,6 +582,7 @@ class MarginalHIP(BaseModel):
                 target_upper = record["target_upper"].numpy()  # and the brackets' upper ends (data space)
         if approximation is None:
             approximation = record.get("approximation") or "laplace"
+        self.objective_ = objective_name(record.get("objective"))  # a checkpoint without the key was trained on "mll"
         y = self._set_censoring(censored, y.shape[0], target_upper, y, approximation)
         self._setup_device(x, y)
         self.is_fitted = True
@@ -606,7 +611,7 @@ class MarginalHIP(BaseModel):
     def fit(self, covariates, target, target_unc=None, iterations: int = 100, optimizer: str | None = None,
             learning_rate: float | None = None, early_stopping: bool = False, patience: int = 60,
             scheduler: bool = True, resume: bool = False, penalty_callback=None, penalty_weight: float = 0.0, censored=None,
-            target_upper=None, approximation="laplace"):
+            target_upper=None, approximation="laplace", objective="mll"):
         """Train the hyperparameters; arguments and behaviour as ``MarginalGPyTorch.fit``
         (engines/gpytorch.py:162-458): Adam (default lr 0.05) or AdamW, gradient clipping to norm 1, optional
         ReduceLROnPlateau, NaN iterations skipped (more than ten in a row raise), optional early stopping, resume from a
@@ -635,8 +640,20 @@ class MarginalHIP(BaseModel):
         the posterior is one-sided.  The sites are warm-started between training iterations; ``ep_status_`` keeps the last call's
         (sweeps, final max |dmu|, final max v |dtau|, capped rows, rows held back, censored rows).  Every product that reads the
         held factorisation then sees the EP posterior.  Without a censored row "ep" is the plain fit.  The keyword of THIS call
-        decides: a resumed fit (or one that continues a loaded checkpoint) states it again."""
+        decides: a resumed fit (or one that continues a loaded checkpoint) states it again.
+
+        ``objective``: "mll" (the default; None means the same) minimises (NLL - log prior) / n, the marginal likelihood.
+        "loo" minimises (L_LOO - log prior) / n with L_LOO = -sum_i log p(y_i | y_-i, theta), the exact leave-one-out predictive
+        likelihood (``dgp_loo_fit_step``; minus the ``elpd`` that ``cross_validate("loo")`` reports) -- the more robust choice
+        when the noise is fixed rather than learned to fit.  Priors, constraints, clamps, the jitter retries, the optimiser, the
+        scheduler, early stopping and the penalty are the same; ``objective_`` records the choice.  Together with ``censored``
+        it is refused: the pseudo-data of a censored fit are not samples, and leaving one out predicts nothing observed."""
         approximation = _approximation_name(approximation)
+        objective = objective_name(objective)
+        if objective == "loo" and censored is not None and np.asarray(getattr(censored, "values", censored)).any():
+            raise NotImplementedError('objective="loo" is not available together with censored observations: the pseudo-data of '
+                                      "a censored fit are not samples, so their leave-one-out predictive likelihood is not the "
+                                      "likelihood of anything observed (the reason influence() refuses them)")
         trained = bool(getattr(self, "model", None) is not None and getattr(self, "likelihood", None) is not None
                        and self.is_fitted)
         from_checkpoint = trained and self._resume_info is not None
@@ -656,6 +673,10 @@ class MarginalHIP(BaseModel):
             y = self._set_censoring(self._censor_host, y.shape[0], self._upper_host, y, approximation)
         elif self._censor is not None and self._censor.approximation != approximation:
             y = self._set_censoring(self._censor_host, y.shape[0], None, y, approximation)
+        if objective == "loo" and self._censor is not None:  # (the censoring a resumed fit or a checkpoint carries)
+            raise NotImplementedError('objective="loo" is not available together with censored observations: the pseudo-data of '
+                                      "a censored fit are not samples")
+        self.objective_ = objective
         self._setup_device(x, y)
         if self._censor is not None:
             self._censor.f = None

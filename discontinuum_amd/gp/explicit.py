@@ -25,7 +25,7 @@ import torch
 
 from .. import _lib
 from .constraints import GreaterThan, Interval, Positive
-from .mll import NotPSDError
+from .mll import NotPSDError, data_step
 from .priors import GammaPrior, HalfNormalPrior, NormalPrior
 
 _HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
@@ -195,9 +195,10 @@ class ExplicitObjective:
     def _row(self, theta, r, noise):
         """The fit step's result row on the host, with the reference's jitter policy for a matrix that is not p.d."""
         plan = self.engine._plan
+        step = data_step(plan, getattr(self.engine, "objective_", "mll"))  # fit_step, or loo_fit_step with the same row layout
         jitter0 = 1e-8 if plan.dtype == torch.float64 else 1e-6
         for attempt in range(4):
-            out = plan.fit_step(theta, r, noise if attempt == 0 else noise + jitter0 * 10 ** (attempt - 1))[0]
+            out = step(theta, r, noise if attempt == 0 else noise + jitter0 * 10 ** (attempt - 1))[0]
             if attempt == 0:
                 yield None  # the device runs: the caller does its own host work now, then asks for the row
             row = out.to("cpu", torch.float64).numpy()

@@ -189,18 +189,41 @@ def _with_jitter_retries(plan, first, again):
         raise
 
 
-def exact_gp_nll(plan, theta, r, noise, pending=None):
+OBJECTIVES = ("mll", "loo")
+
+
+def objective_name(objective):
+    """``fit(objective=...)`` as "mll" (the default; None means the same) or "loo"."""
+    name = "mll" if objective is None else str(objective).lower()
+    if name not in OBJECTIVES:
+        raise ValueError(f"objective must be one of {OBJECTIVES}, got {objective!r}")
+    return name
+
+
+def data_step(plan, objective="mll"):
+    """The plan method that evaluates the data term of ``objective`` and its gradients into one result row: ``fit_step`` (the
+    marginal likelihood) or ``loo_fit_step`` (the leave-one-out predictive likelihood; same arguments, same row layout)."""
+    return plan.loo_fit_step if objective == "loo" else plan.fit_step
+
+
+def exact_gp_nll(plan, theta, r, noise, pending=None, objective="mll"):
     """Differentiable data term with gpytorch's jitter-retry policy. Returns a 0-dim CPU float64 tensor."""
+    if objective == "loo":  # the same autograd function on the other step's (out, dr, dnoise)
+        step = data_step(plan, objective)
+        return _with_jitter_retries(plan, lambda: _ExactGPNLL.apply(plan, theta, r, noise, pending),
+                                    lambda jitter: _ExactGPNLL.apply(plan, theta, r, noise + jitter,
+                                                                     step(theta, r.detach(), (noise + jitter).detach().contiguous())))
     return _with_jitter_retries(plan, lambda: _ExactGPNLL.apply(plan, theta, r, noise, pending),
                                 lambda jitter: _ExactGPNLL.apply(plan, theta, r, noise + jitter))
 
 
-def exact_gp_nll_row(plan, theta, r, noise, pending, shortcut):
+def exact_gp_nll_row(plan, theta, r, noise, pending, shortcut, objective="mll"):
     """``exact_gp_nll`` for a host-side mean / noise model: gradients from the result row (``_RowNLL``)."""
     params = shortcut.params
+    step = data_step(plan, objective)
     return _with_jitter_retries(
         plan, lambda: _RowNLL.apply(plan, theta, pending, shortcut, *params),
-        lambda jitter: _RowNLL.apply(plan, theta, plan.fit_step(theta, r, noise + jitter), shortcut, *params))
+        lambda jitter: _RowNLL.apply(plan, theta, step(theta, r, noise + jitter), shortcut, *params))
 
 
 class ExactMarginalLogLikelihood:
@@ -283,10 +306,11 @@ class ExactMarginalLogLikelihood:
             r, noise = shortcut.residual_and_noise(output.plan, target)
         else:
             r, noise = (target - output.mean).contiguous(), output.noise.contiguous()
-        pending = output.plan.fit_step(output.theta, r, noise)  # asynchronous: the device starts now ...
+        objective = getattr(output, "objective", "mll")  # "loo": the leave-one-out predictive likelihood takes the data term's place
+        pending = data_step(output.plan, objective)(output.theta, r, noise)  # asynchronous: the device starts now ...
         lp = self.log_prior()                                   # ... and the O(P) host algebra runs under it
         if shortcut is not None:
-            nll = exact_gp_nll_row(output.plan, output.theta, r, noise, pending, shortcut)
+            nll = exact_gp_nll_row(output.plan, output.theta, r, noise, pending, shortcut, objective)
         else:
-            nll = exact_gp_nll(output.plan, output.theta, r, noise, pending)
+            nll = exact_gp_nll(output.plan, output.theta, r, noise, pending, objective)
         return ((-nll + lp) / n).reshape(1)  # shape (1,) like the reference's (1, n)-noise batch

@@ -44,6 +44,7 @@ from . import _lib
 from .backend import GPPlan
 from .gp.kernels import prior_closures
 from .gp.lowering import lower
+from .gp.mll import data_step, objective_name
 
 
 LAST_TIMING: dict = {}  # diagnostics of the most recent fit_many call in this process (set-up / loop seconds, iterations)
@@ -81,11 +82,12 @@ class _BatchedNLL(torch.autograd.Function):
     engine (``engines/hip.py::MeanShortcut``): no device-side autograd, one device->host copy per iteration."""
 
     @staticmethod
-    def forward(ctx, plan, theta, r, noise, extras, family):
+    def forward(ctx, plan, theta, r, noise, extras, family, objective="mll"):
+        step = data_step(plan, objective)  # fit_step, or loo_fit_step with the same row layout
         if plan.batch == 1:
-            out = plan.fit_step(theta[0], r[0].contiguous(), noise[0].contiguous())[0].reshape(1, -1)
+            out = step(theta[0], r[0].contiguous(), noise[0].contiguous())[0].reshape(1, -1)
         else:
-            out = plan.fit_step(theta, r, noise)[0]
+            out = step(theta, r, noise)[0]
         host = out.to("cpu", torch.float64)
         _ok, nll, dtheta, dextras = _row_terms(host, plan.ntheta, family, extras[:, 1].detach() if family == "rating" else None)
         ctx.save_for_backward(dtheta, dextras)
@@ -96,7 +98,7 @@ class _BatchedNLL(torch.autograd.Function):
     def backward(ctx, g):
         dtheta, dextras = ctx.saved_tensors
         g = torch.nan_to_num(g, nan=0.0)[:, None]
-        return None, (dtheta * g).to(ctx.dtypes[0]), None, None, (dextras * g).to(ctx.dtypes[1]), None
+        return None, (dtheta * g).to(ctx.dtypes[0]), None, None, (dextras * g).to(ctx.dtypes[1]), None, None
 
 
 class _BatchedCensor:
@@ -517,7 +519,8 @@ def fit_many(models, datasets, iterations: int = 100, learning_rate: float = 0.0
              monotonic_penalty_weight: float = 0.0, grid_size: int = 64, monotonic_penalty_interval: int = 1,
              resume: FitManyState | None = None, return_state: bool = False, generator: torch.Generator | None = None,
              optimizer: str = "adam", penalty_callback=None, penalty_weight: float = 0.0, site_seeds=None,
-             closed_form: bool = True, censored=None, target_upper=None, approximation="laplace", _penalty_uniforms=None):
+             closed_form: bool = True, censored=None, target_upper=None, approximation="laplace", objective="mll",
+             _penalty_uniforms=None):
     """Fit ``models[i]`` to ``datasets[i] = (covariates, target[, target_unc])`` for all i at once.  Returns the
     per-site final objectives (a float64 tensor) -- with ``return_state=True`` the pair (objectives, ``FitManyState``);
     the models are updated in place (``is_fitted``, parameters, device state).
@@ -568,8 +571,13 @@ def fit_many(models, datasets, iterations: int = 100, learning_rate: float = 0.0
     ``dgp_laplace_interval_fit_step``; afterwards every model carries its brackets like after its own ``fit``.
 
     ``approximation``: "laplace" only.  "ep" (``MarginalHIP.fit(approximation="ep")``) is refused: expectation propagation runs
-    on single-site plans; its lockstep batched form does not exist yet."""
+    on single-site plans; its lockstep batched form does not exist yet.
+
+    ``objective``: "mll" (the default; None means the same) or "loo", as ``MarginalHIP.fit(objective=...)``: with "loo" the device
+    step of an iteration is ONE batched ``dgp_loo_fit_step`` and every site minimises (L_LOO - log prior) / n, in both host paths;
+    every model then records it in ``objective_``.  Refused together with a censored row (``NotImplementedError``)."""
     _refuse_ep(approximation, "fit_many")
+    objective = objective_name(objective)
     if site_seeds is not None and len(site_seeds) != len(models):
         raise ValueError("site_seeds needs one seed per model")
     _refuse_censored_records(datasets, "fit_many")
@@ -624,6 +632,9 @@ def fit_many(models, datasets, iterations: int = 100, learning_rate: float = 0.0
     if B > 1:
         plan.set_site_sizes(sizes)
     cstate = None
+    if objective == "loo" and any(sd is not None for sd in sides):
+        raise NotImplementedError('fit_many: objective="loo" is not available together with censored observations: the '
+                                  "pseudo-data of a censored fit are not samples")
     if any(sd is not None for sd in sides):
         side_all = torch.zeros((B, n), dtype=torch.int32)
         for b, sd in enumerate(sides):
@@ -758,6 +769,7 @@ def fit_many(models, datasets, iterations: int = 100, learning_rate: float = 0.0
     # then spin while every following small operation waits for a core: measured 19.9 ms per iteration for 256 sites of n = 300
     # in the closed-form path against 0.66 ms with ONE thread (8 threads: 0.94; the autograd path: 1.94 -> 1.44).  One thread
     # for the loop; the caller's setting is restored behind it.
+    device_step = data_step(plan, objective)  # the closed-form path's device step: fit_step, or loo_fit_step with the same row layout
     host_threads = torch.get_num_threads()
     torch.set_num_threads(1)
     t_loop = time.perf_counter()
@@ -776,9 +788,9 @@ def fit_many(models, datasets, iterations: int = 100, learning_rate: float = 0.0
                 if cstate is not None:
                     out = _laplace_step(plan, theta, Y, mean, noise, cstate)
                 elif plan.batch == 1:
-                    out = plan.fit_step(theta[0], (Y - mean)[0].contiguous(), noise[0].contiguous())[0].reshape(1, -1)
+                    out = device_step(theta[0], (Y - mean)[0].contiguous(), noise[0].contiguous())[0].reshape(1, -1)
                 else:
-                    out = plan.fit_step(theta, (Y - mean).contiguous(), noise)[0]
+                    out = device_step(theta, (Y - mean).contiguous(), noise)[0]
                 lp_np, dlp = cf.log_prior(x)  # the host's share runs under the device step
                 _ok_row, nll, dtheta, dextras = _row_terms(out.to("cpu", torch.float64), plan.ntheta, family,
                                                           extras[:, 1] if family == "rating" else None)
@@ -797,7 +809,7 @@ def fit_many(models, datasets, iterations: int = 100, learning_rate: float = 0.0
                 if cstate is not None:
                     nll = _BatchedLaplaceNLL.apply(plan, theta, Y, mean, noise, extras, family, cstate)
                 else:
-                    nll = _BatchedNLL.apply(plan, theta, (Y - mean).contiguous(), noise, extras, family)
+                    nll = _BatchedNLL.apply(plan, theta, (Y - mean).contiguous(), noise, extras, family, objective)
                 obj = (nll - lp) / nvec
             if use_penalty and (it + 1) % interval == 0:
                 # posterior mean of every site on its grid = GP part (device, batched, differentiable through
@@ -889,6 +901,7 @@ def fit_many(models, datasets, iterations: int = 100, learning_rate: float = 0.0
     # ---- hand the fitted parameters back to the per-site models
     for b, (m, own) in enumerate(zip(models, own_params)):
         _hand_back(m, own, {k: v[b] for k, v in params.items()}, int(last_iteration[b]), xs[b], ys[b])
+        m.objective_ = objective
         if censored is not None:
             _hand_back_censoring(m, censored[b] if target_upper is not None else sides[b], sizes[b], cstate, b,
                                  None if target_upper is None else target_upper[b], ys_given[b])
@@ -968,7 +981,7 @@ def fit_many_distributed(models, datasets, group=None, load: str = "all", seed: 
     ``censored``: as in ``fit_many``, one entry per site of the WHOLE list; it is sliced by ``site_partition`` like the datasets,
     and a rank that loads a site it does not own also sets that site's censoring on its model.  The gathered table is unchanged.
     ``target_upper``: as in ``fit_many`` (the upper ends of bracketed rows, one entry per site of the whole list), sliced and
-    handed back the same way.
+    handed back the same way.  ``objective``: as in ``fit_many``; every model a rank loads records it too.
 
     Without an initialised process group (or world 1) this is ``fit_many`` plus the table.  ``resume`` / ``return_state``
     are per-rank notions and not supported here.  Returns ``(objectives (n_sites,), table (n_sites, P_raw + 3))``, float64,
@@ -981,6 +994,7 @@ def fit_many_distributed(models, datasets, group=None, load: str = "all", seed: 
         raise ValueError("load must be 'all', 'rank0' or 'own'")
     _refuse_censored_records(datasets, "fit_many_distributed")
     _refuse_ep(kw.get("approximation"), "fit_many_distributed")
+    objective = objective_name(kw.get("objective"))  # passed on to fit_many with the other keywords
     if "resume" in kw or kw.get("return_state") or "site_seeds" in kw:
         raise ValueError("fit_many_distributed: resume / return_state are per-rank; use fit_many on each rank's share")
     if len(models) != len(datasets) or not models:
@@ -1059,6 +1073,7 @@ def fit_many_distributed(models, datasets, group=None, load: str = "all", seed: 
                 values[k] = table[i, o:o + w].to(own[k].dtype)
                 o += w
             _hand_back(models[i], own, values, int(table[i, P + 1]) - 1, tx, ty)
+            models[i].objective_ = objective
             if censored is not None:
                 up = None if target_upper is None else target_upper[i]
                 _site_sides([models[i]], [censored[i]], [tx.shape[0]], "fit_many_distributed", None if up is None else [up])

@@ -363,6 +363,29 @@ int dgp_ep_factorize(dgp_plan* plan, const double* theta_host, const void* y_dev
 /* k_dev[i] = [(K^)^-1]_ii = sum_{j >= i} T_ji^2, i < n, from the factorisation the plan holds (any of the entries above): the
  * diagonal pass of an EP sweep alone, for tests and timing.  work_dev: dgp_ep_workspace_bytes.  DGP_E_STATE without a factorisation. */
 int dgp_ep_diag(dgp_plan* plan, void* k_dev, void* work_dev, size_t work_bytes, void* stream);
+
+/* ---- The exact leave-one-out predictive likelihood as a training objective.
+ * With S = (K^)^-1, alpha = S r and k_i = S_ii the leave-one-out predictive of row i is N(y_i - alpha_i / k_i, 1 / k_i) and
+ *     L_LOO = sum_i [ 1/2 log 2 pi - 1/2 log k_i + alpha_i^2 / (2 k_i) ]        (minus the elpd of dgp_cross_validate's folds of one)
+ * dgp_loo_fit_step has the arguments, shapes and batching of dgp_fit_step plus a work area (dgp_loo_workspace_bytes: three N x N
+ * matrices per site and change).  It runs dgp_fit_step's launches unchanged into a result row of its own, then
+ *     w = (1 + alpha^2 / k) / (2 k),  c = alpha / k,  M = S diag(w) S (one symmetric N^3 product on the MFMA tile cores, lower tiles,
+ *     k ascending; 64 x 64 tiles while a launch has too few: DGP_OPT_LAUUM64_MAX_TILES),  b = S c
+ *     dL/dtheta_p = 1/2 tr((2 M - b alpha^T - alpha b^T) dK/dtheta_p),  dL/dr = b,  dL/dnoise_i = M_ii - b_i alpha_i
+ * out_dev: DGP_OUT_* layout with NLL = L_LOO and DTHETA, SUM_DR, DR_W0.., SUM_DNOISE its gradients; QUAD, LOGDET and INFO are those of
+ * the factorisation.  A site one of whose k_i is not a positive finite number reports the 1-based index of the first such row in its
+ * INFO (when the factorisation's own status is 0) and NaN as its value: the return code stays 0 and the other sites are unaffected.
+ * The plan holds afterwards exactly what dgp_fit_step with the same arguments leaves (factor, inverse, z, alpha): every inference
+ * entry point works on it unchanged.  No floating-point atomics: bitwise repeatable, a site's result does not depend on its batch.
+ * dgp_loo_value: out2_dev [batch][2] doubles = (L_LOO, info) from the factorisation the plan holds, when the last step left S in it
+ * (dgp_fit_step / dgp_loo_fit_step; DGP_E_STATE otherwise); work area: dgp_loo_value_workspace_bytes.
+ * float64 plans, single-site or batched.  Before any launch: DGP_E_ARG (null plan / argument; a float32 plan -- the text says so;
+ * misaligned work area), DGP_E_WORKSPACE (work area missing or too small), DGP_E_STATE (no inputs / no inverse). */
+size_t dgp_loo_workspace_bytes(const dgp_plan* plan);
+size_t dgp_loo_value_workspace_bytes(const dgp_plan* plan);
+int dgp_loo_fit_step(dgp_plan* plan, const double* theta_host, const void* r_dev, const void* noise_dev, void* work_dev,
+                     size_t work_bytes, void* out_dev, void* dr_dev, void* dnoise_dev, void* stream);
+int dgp_loo_value(dgp_plan* plan, void* work_dev, size_t work_bytes, void* out2_dev, void* stream);
 /* out [4][count] = log P, sigma g, W v, sigma^3 d3 of the brackets [za, za + Delta]: the pointwise functions of the two entries
  * above, for tests.  za_dev, delta_dev: count doubles on the device (Delta > 0). */
 int dgp_debug_interval_terms(const double* za_dev, const double* delta_dev, int64_t count, double* out_dev, void* stream);
