@@ -36,7 +36,7 @@
 #include "dgp_common.h"
 #include "dgp_gemm_dma.h"
 #include "dgp_gram_shared.h"
-#include "dgp_internal.h"
+#include "dgp_plan.h"
 #include "dgp_models.h"
 
 namespace dgp {
@@ -364,22 +364,18 @@ int period_moments_mode(const T* cov, long M, int m, int B, const T* mu, const d
 
 }  // namespace
 
-size_t period_moments_workspace_bytes(long m, int P, int B) {
+static size_t period_moments_workspace_bytes(long m, int P, int B) {
   return sizeof(double) * (size_t)B * (size_t)pm_site_doubles(round_up(m, DGP_TILE_HOST), P);
 }
 
+// exact mean / covariance of period sums of exp(s f + t) (mode 1) or s f + t (mode 0), f ~ N(mu, C)
 template <typename T>
-int period_moments(int mode, const T* cov, long m, int B, const T* mu, const double* scale2, const double* w, const int* group,
+static int period_moments(int mode, const T* cov, long m, int B, const T* mu, const double* scale2, const double* w, const int* group,
                    int P, const T* ev, double* work, double* mean_out, double* cov_out, hipStream_t s) {
   const long M = round_up(m, DGP_TILE_HOST);
   return mode == 1 ? period_moments_mode<T, 1>(cov, M, (int)m, B, mu, scale2, w, group, P, ev, work, mean_out, cov_out, s)
                    : period_moments_mode<T, 0>(cov, M, (int)m, B, mu, scale2, w, group, P, ev, work, mean_out, cov_out, s);
 }
-
-template int period_moments<double>(int, const double*, long, int, const double*, const double*, const double*, const int*, int,
-                                    const double*, double*, double*, double*, hipStream_t);
-template int period_moments<float>(int, const float*, long, int, const float*, const double*, const double*, const int*, int,
-                                   const float*, double*, double*, double*, hipStream_t);
 
 namespace {
 template <typename T, int MODE>
@@ -401,10 +397,13 @@ int posterior_period_moments_mode(int model, int d, const T* V, long N, long Mp,
 }
 }  // namespace
 
+// the same moments with C = K(Xs, Xs) - V^T V never stored: V (N x M), the test points' SoA coordinates Xst (d x M) and their
+// predicted variance var (M) as the prediction leaves them in its work area (site stride wbs elements); `work` as above
+// (period_moments_workspace_bytes); pre_scratch: the plan's hyperparameter scratch, already filled by this call's gram_cross
 template <typename T>
-int posterior_period_moments(int mode, int model, int d, const T* V, long N, long m, int B, const T* Xst, const T* var, long wbs,
-                             const double* theta, const T* mu, const double* scale2, const double* w, const int* group, int P,
-                             const T* ev, double* work, double* mean_out, double* cov_out, hipStream_t s, void* pre_scratch) {
+static int posterior_period_moments(int mode, int model, int d, const T* V, long N, long m, int B, const T* Xst, const T* var, long wbs,
+                                    const double* theta, const T* mu, const double* scale2, const double* w, const int* group, int P,
+                                    const T* ev, double* work, double* mean_out, double* cov_out, hipStream_t s, void* pre_scratch) {
   const long Mp = round_up(m, DGP_TILE_HOST);
   return mode == 1 ? posterior_period_moments_mode<T, 1>(model, d, V, N, Mp, (int)m, B, Xst, var, wbs, theta, mu, scale2, w, group,
                                                           P, ev, work, mean_out, cov_out, s, pre_scratch)
@@ -412,11 +411,75 @@ int posterior_period_moments(int mode, int model, int d, const T* V, long N, lon
                                                           P, ev, work, mean_out, cov_out, s, pre_scratch);
 }
 
-template int posterior_period_moments<double>(int, int, int, const double*, long, long, int, const double*, const double*, long,
-                                              const double*, const double*, const double*, const double*, const int*, int,
-                                              const double*, double*, double*, double*, hipStream_t, void*);
-template int posterior_period_moments<float>(int, int, int, const float*, long, long, int, const float*, const float*, long,
-                                             const double*, const float*, const double*, const double*, const int*, int,
-                                             const float*, double*, double*, double*, hipStream_t, void*);
-
 }  // namespace dgp
+
+using namespace dgp;
+
+// streamed period moments: the prediction's work area (its first stages leave V, Xs's SoA copy and the predicted variance
+// there), then the moment pass's work area
+template <typename T>
+static int post_period(dgp_plan* p, const double* theta, const void* Xs, int64_t m, int mode, const void* mu, const double* scale2,
+                       const double* w, const int32_t* group, int P, const void* ev, void* work, double* mean_out, double* cov_out,
+                       hipStream_t s) {
+  double* pm = (double*)((char*)work + predict_layout(p, m).total * (size_t)p->B);
+  T *V, *Xst, *vpad;
+  long wbs;
+  // the latent mean the prediction also writes (B x m elements) lands in the moment pass's area, which its first launch resets
+  int rc = predict_common<T>(p, theta, Xs, m, work, pm, &V, &Xst, &vpad, &wbs, s);
+  if (rc) return rc;
+  return posterior_period_moments<T>(mode, p->model, p->d, V, p->N, (long)m, p->B, Xst, vpad, wbs, theta, (const T*)mu, scale2, w,
+                                     group, P, (const T*)ev, pm, mean_out, cov_out, s, p->pre);
+}
+
+extern "C" {
+
+size_t dgp_period_moments_workspace_bytes(int64_t m, int ngroups, int batch) {
+  if (m <= 0 || m > (1 << 20) || ngroups <= 0 || ngroups > 65535 || batch <= 0 || batch > DGP_MAX_BATCH_SITES) return 0;
+  return period_moments_workspace_bytes(m, ngroups, batch);
+}
+
+int dgp_period_moments(int dtype, int mode, const void* cov, int64_t m, int batch, const void* mu, const double* scale2,
+                       const double* w, const int32_t* group, int ngroups, const void* extra_var, void* work,
+                       size_t work_bytes, double* mean_out, double* cov_out, void* stream) {
+  if (dtype != DGP_F64 && dtype != DGP_F32) return fail(DGP_E_ARG, "dgp_period_moments: dtype must be 0 (f64) or 1 (f32)");
+  if (mode != 0 && mode != 1) return fail(DGP_E_ARG, "dgp_period_moments: mode must be 0 (linear) or 1 (log)");
+  if (!cov || !mu || !scale2 || !w || !group || !mean_out || !cov_out)
+    return fail(DGP_E_ARG, "dgp_period_moments: null argument");
+  if (m <= 0 || m > (1 << 20) || ngroups <= 0 || ngroups > 65535 || batch <= 0 || batch > DGP_MAX_BATCH_SITES)
+    return fail(DGP_E_ARG, "dgp_period_moments: bad size (1 <= m <= 2^20, 1 <= ngroups <= 65535, 1 <= batch <= 1024)");
+  if (!work || work_bytes < period_moments_workspace_bytes(m, ngroups, batch))
+    return fail(DGP_E_WORKSPACE, "dgp_period_moments: workspace missing or too small");
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = dtype == DGP_F64
+                     ? period_moments<double>(mode, (const double*)cov, m, batch, (const double*)mu, scale2, w, group, ngroups,
+                                              (const double*)extra_var, (double*)work, mean_out, cov_out, s)
+                     : period_moments<float>(mode, (const float*)cov, m, batch, (const float*)mu, scale2, w, group, ngroups,
+                                             (const float*)extra_var, (double*)work, mean_out, cov_out, s);
+  return wrap(rc, "dgp_period_moments");
+}
+
+size_t dgp_posterior_period_moments_workspace_bytes(const dgp_plan* p, int64_t m, int ngroups) {
+  if (!p || m <= 0 || m > (1 << 20) || ngroups <= 0 || ngroups > 65535) return 0;
+  return predict_layout(p, m).total * (size_t)p->B + period_moments_workspace_bytes(m, ngroups, p->B);
+}
+
+int dgp_posterior_period_moments(dgp_plan* p, const double* theta, const void* Xs, int64_t m, int mode, const void* mu,
+                                 const double* scale2, const double* w, const int32_t* group, int ngroups, const void* extra_var,
+                                 void* work, size_t work_bytes, double* mean_out, double* cov_out, void* stream) {
+  if (!p) return fail(DGP_E_ARG, "null plan");
+  if (mode != 0 && mode != 1) return fail(DGP_E_ARG, "dgp_posterior_period_moments: mode must be 0 (linear) or 1 (log)");
+  if (!theta || !Xs || !mu || !scale2 || !w || !group || !mean_out || !cov_out)
+    return fail(DGP_E_ARG, "dgp_posterior_period_moments: null argument");
+  if (m <= 0 || m > (1 << 20) || ngroups <= 0 || ngroups > 65535)
+    return fail(DGP_E_ARG, "dgp_posterior_period_moments: bad size (1 <= m <= 2^20, 1 <= ngroups <= 65535)");
+  if (int rc = need_factor(p, "dgp_posterior_period_moments", "call dgp_factorize")) return rc;
+  DGP_CHECK_PLAN(p);
+  if (!work || work_bytes < dgp_posterior_period_moments_workspace_bytes(p, m, ngroups))
+    return fail(DGP_E_WORKSPACE, "dgp_posterior_period_moments: workspace missing or too small");
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = DGP_BY_DTYPE(p, post_period<double>(p, theta, Xs, m, mode, mu, scale2, w, group, ngroups, extra_var, work, mean_out, cov_out, s),
+                              post_period<float>(p, theta, Xs, m, mode, mu, scale2, w, group, ngroups, extra_var, work, mean_out, cov_out, s));
+  return wrap(rc, "dgp_posterior_period_moments");
+}
+
+}  // extern "C"

@@ -1,4 +1,6 @@
-// dgp_api.hip -- the C ABI declared in include/dgp_hip.h: plan bookkeeping and stage sequencing.
+// dgp_api.hip -- the plan and the fit step: lifecycle, options, batch and site sizes, buffers, timing, the stream sets and the
+// stage sequencing of dgp_fit_step / dgp_factorize.  Every other entry point of include/dgp_hip.h lives beside the launchers it
+// drives (dgp_predict.hip, dgp_censored.hip, dgp_ep.hip, ...) and reaches the plan through dgp_plan.h.
 #include <mutex>
 #include <new>
 #include <stdio.h>
@@ -7,122 +9,40 @@
 #include <utility>
 #include <vector>
 
-#include "../../include/dgp_hip.h"
 #include "dgp_common.h"
-#include "dgp_internal.h"
+#include "dgp_plan.h"
 
 using namespace dgp;
 
-static thread_local char g_err[256] = "";
-static int fail(int code, const char* msg) {
+static thread_local char g_err[256] = "";  // the one error text of dgp_last_error() (dgp_plan.h: fail / hipfail / failf)
+namespace dgp {
+int fail(int code, const char* msg) {
   snprintf(g_err, sizeof(g_err), "%s", msg);
   return code;
 }
-static int hipfail(hipError_t e, const char* where) {
+int hipfail(hipError_t e, const char* where) {
   snprintf(g_err, sizeof(g_err), "%s: %s", where, hipGetErrorString(e));
   return (int)e;
 }
-
-// Small host -> device uploads (site sizes, the hyperparameters of large batches) go through PINNED staging slots that
-// the plan owns: an asynchronous copy from pageable memory is only safe while the runtime happens to stage it before
-// returning.  A slot is reused after the event recorded behind its last copy has completed.
-struct PinnedRing {
-  static constexpr int SLOTS = 4;
-  void* buf[SLOTS];
-  size_t cap[SLOTS];
-  hipEvent_t ev[SLOTS];
-  int busy[SLOTS], have_ev[SLOTS], next;
-  void* acquire(size_t bytes) {
-    const int i = next;
-    if (busy[i]) {
-      (void)hipEventSynchronize(ev[i]);
-      busy[i] = 0;
-    }
-    if (cap[i] < bytes) {
-      if (buf[i]) (void)hipHostFree(buf[i]);
-      buf[i] = nullptr;
-      cap[i] = 0;
-      if (hipHostMalloc(&buf[i], bytes, hipHostMallocDefault) != hipSuccess) return nullptr;
-      cap[i] = bytes;
-    }
-    return buf[i];
-  }
-  void commit(hipStream_t s) {  // after the copy out of the slot handed out last has been enqueued on s
-    const int i = next;
-    if (!have_ev[i]) have_ev[i] = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) == hipSuccess;
-    if (have_ev[i] && hipEventRecord(ev[i], s) == hipSuccess) busy[i] = 1;
-    else (void)hipStreamSynchronize(s);
-    next = (next + 1) % SLOTS;
-  }
-  void destroy() {
-    for (int i = 0; i < SLOTS; ++i) {
-      if (busy[i]) (void)hipEventSynchronize(ev[i]);
-      if (have_ev[i]) (void)hipEventDestroy(ev[i]);
-      if (buf[i]) (void)hipHostFree(buf[i]);
-    }
-  }
-};
-
-struct dgp_plan {
-  int model, dtype, d, ntheta;
-  PinnedRing ring;
-  int* nsite_host;        // host copy of the sites' sizes (B > 1): the inference entry points walk the sites on the host
-  int B;                  // sites carried in lockstep (1 = plain plan); site b's buffers sit b * site_bytes further on
-  size_t site_bytes;
-  void* pre;              // device scratch for the batch's hyperparameters (B > 8), after the last site
-  void* pre2;             // a second one for the fp64 evaluator of the refinement (fp32 plans), so that `pre` stays valid
-  int pre_ready;          // the Gram build of the current step has uploaded them
-  Tuning tune;            // tile-shape selectors (dgp_plan_set_option)
-  int refine;             // fp32 plans: one step of iterative refinement with an fp64 residual after the solves
-  int* nsite;             // device: the sites' own sizes (B > 1), after the hyperparameter scratch
-  const void* dr_w;       // caller's [2][n] weight vectors for the out[DGP_OUT_DR_W0..] reductions, or null
-  int64_t n, N;
-  size_t elem;
-  char* ws;
-  size_t ws_bytes;
-  // carved workspace
-  void *Xt, *A, *Tm, *S, *z, *alpha, *gpart, *spart, *scal, *snap;
-  int* info;
-  hipStream_t sc;         // rest of the split panel chain (dgp_chol.hip::potrf_split)
-  int lookahead, early;   // potrf schedule; issue the inverse's level recursion behind the factorisation's checkpoints
-  int have_inputs, have_factor, have_inverse;
-  hipStream_t s2, s3;     // bulk trailing updates; early inverse work
-  hipEvent_t xev[8];      // checkpoints of the factorisation and fork/join events for s3
-  int have_xev;
-  hipEvent_t* ev;
-  int nev;
-  // optional HIP-event timing of the fit-step stages
-  int timing, n_syrk, timed_valid;
-  double syrk_flop;
-  hipEvent_t* tev;   // 2 per stage (start, stop)
-  hipEvent_t* sev;   // 2 per bulk syrk launch
-  int nsev;
-};
-enum { TS_GRAM = 0, TS_POTRF, TS_TRTRI, TS_LAUUM, TS_SOLVE, TS_GRAD, TS_COUNT };
-
-static size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct Layout {
-  size_t Xt, A, Tm, S, z, alpha, gpart, spart, scal, info, snap, total;
-};
-static Layout layout(const dgp_plan* p) {
-  Layout L;
-  const size_t e = p->elem, N = (size_t)p->N;
-  size_t o = 0;
-  L.Xt = o; o += align_up(e * N * p->d);
-  L.A = o; o += align_up(e * N * N);
-  L.Tm = o; o += align_up(e * N * N);
-  L.S = o; o += align_up(e * N * N);
-  L.z = o; o += align_up(e * N);
-  L.alpha = o; o += align_up(e * N);
-  L.gpart = o; o += align_up(e * (size_t)gram_grad_partials(p->N));
-  L.spart = o; o += align_up(e * (size_t)solve_partials(p->N));
-  L.scal = o; o += align_up(e * 16);
-  L.info = o; o += align_up(sizeof(int) * POTRF_INFO_INTS);
-  L.snap = o; o += align_up(e * 2 * DGP_TILE_HOST * DGP_TILE_HOST);  // the split chain's two snapshot blocks
-  L.total = o;
-  return L;
+int failf(int code, const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_err, sizeof(g_err), fmt, ap);
+  va_end(ap);
+  return code;
 }
+int factor_ok(dgp_plan* p, hipStream_t s, const char* where) {
+  std::vector<int> info((size_t)p->B, 0);
+  hipError_t e = hipMemcpy2DAsync(info.data(), sizeof(int), p->info, p->site_bytes, sizeof(int), (size_t)p->B, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return hipfail(e, where);
+  for (int b = 0; b < p->B; ++b)
+    if (info[(size_t)b] != 0) return failf(DGP_E_STATE, "%s: the factorisation the plan holds failed (matrix not positive definite)", where);
+  return 0;
+}
+}  // namespace dgp
+
+enum { TS_GRAM = 0, TS_POTRF, TS_TRTRI, TS_LAUUM, TS_SOLVE, TS_GRAD, TS_COUNT };
 
 static int default_lookahead() { return 2; }  // lookahead on: the group-ahead schedule of dgp_chol.hip::potrf
 // panels per group of that schedule: pairs for one site (chain-bound), larger groups (K = 512 bulk updates) for a batch
@@ -206,10 +126,7 @@ int dgp_plan_destroy(dgp_plan* p) {
   return 0;
 }
 
-size_t dgp_plan_workspace_bytes(const dgp_plan* p) {
-  return p ? layout(p).total * (size_t)p->B + 2 * align_up(pre_scratch_bytes(p->B)) + (p->B > 1 ? align_up(sizeof(int) * p->B) : 0)
-           : 0;
-}
+size_t dgp_plan_workspace_bytes(const dgp_plan* p) { return p ? layout(p).ws_total : 0; }
 
 int dgp_plan_set_batch(dgp_plan* p, int batch) {
   if (!p) return fail(DGP_E_ARG, "null plan");
@@ -248,8 +165,7 @@ int dgp_plan_set_dr_weights(dgp_plan* p, const void* w_dev) {
 int dgp_plan_set_workspace(dgp_plan* p, void* dev_ptr, size_t bytes) {
   if (!p || !dev_ptr) return fail(DGP_E_ARG, "dgp_plan_set_workspace: null");
   const Layout L = layout(p);
-  if (bytes < dgp_plan_workspace_bytes(p))
-    return fail(DGP_E_WORKSPACE, "dgp_plan_set_workspace: workspace too small");
+  if (bytes < L.ws_total) return fail(DGP_E_WORKSPACE, "dgp_plan_set_workspace: workspace too small");
   p->site_bytes = L.total;
   if (((uintptr_t)dev_ptr & 255) != 0) return fail(DGP_E_ARG, "dgp_plan_set_workspace: pointer must be 256-byte aligned");
   p->ws = (char*)dev_ptr;
@@ -265,12 +181,12 @@ int dgp_plan_set_workspace(dgp_plan* p, void* dev_ptr, size_t bytes) {
   p->scal = p->ws + L.scal;
   p->info = (int*)(p->ws + L.info);
   p->snap = p->ws + L.snap;
-  p->pre = pre_scratch_bytes(p->B) ? (void*)(p->ws + L.total * (size_t)p->B) : nullptr;
-  p->pre2 = p->pre ? (void*)((char*)p->pre + align_up(pre_scratch_bytes(p->B))) : nullptr;
+  p->pre = pre_scratch_bytes(p->B) ? (void*)(p->ws + L.pre) : nullptr;
+  p->pre2 = p->pre ? (void*)(p->ws + L.pre2) : nullptr;
   p->nsite = nullptr;
   p->dr_w = nullptr;
   if (p->B > 1) {  // every site starts at the full size n
-    p->nsite = (int*)(p->ws + L.total * (size_t)p->B + 2 * align_up(pre_scratch_bytes(p->B)));
+    p->nsite = (int*)(p->ws + L.nsite);
     delete[] p->nsite_host;
     p->nsite_host = new (std::nothrow) int[(size_t)p->B];
     if (!p->nsite_host) return fail(DGP_E_ARG, "dgp_plan_set_workspace: out of host memory");
@@ -628,16 +544,6 @@ __global__ __launch_bounds__(256) void finish_kernel(const T* scal, int* info, l
 
 
 template <typename T>
-static Batch batch_of(const dgp_plan* p) {
-  Batch bt;
-  bt.B = p->B;
-  bt.ws = (long)(p->site_bytes / sizeof(T));  // layout offsets are multiples of 256 bytes
-  bt.ns = p->nsite;
-  bt.tune = &p->tune;
-  bt.W = p->S;  // scratch of the factorisation's group inverse (S is free until trtri / lauum use it)
-  return bt;
-}
-template <typename T>
 static int run_gram(dgp_plan* p, const double* theta, const void* noise, hipStream_t s) {
   p->pre_ready = 1;
   void* staging = p->pre ? p->ring.acquire(pre_scratch_bytes(p->B)) : nullptr;
@@ -740,9 +646,21 @@ static bool solve_overlap(const dgp_plan* p) {
   return !(sizeof(T) == 4 && p->refine);
 }
 
+// While the solves run beside lauum on the bulk stream they read the caller's r: a step that leaves early still has to order the
+// caller's stream behind them (ev[1]), or the caller may reuse r under the side stream.  Armed once ev[1] is recorded, disarmed
+// where the step waits for it itself; nothing is enqueued on the path of a step that succeeds.
+struct SolveJoin {
+  hipStream_t s;
+  hipEvent_t ev;
+  bool armed = false;
+  ~SolveJoin() {
+    if (armed) (void)hipStreamWaitEvent(s, ev, 0);
+  }
+};
+
 template <typename T>
-static int fit_step(dgp_plan* p, const double* theta, const void* r, const void* noise, void* out, void* dr,
-                    void* dnoise, int with_grad, hipStream_t s) {
+int dgp::fit_step(dgp_plan* p, const double* theta, const void* r, const void* noise, void* out, void* dr, void* dnoise, int with_grad,
+                  hipStream_t s) {
   int rc;
   if ((rc = ensure_timing(p))) return rc;
   tick(p, TS_GRAM, 0, s);
@@ -804,10 +722,18 @@ static int fit_step(dgp_plan* p, const double* theta, const void* r, const void*
   if ((rc = run_solve<T>(p, r, ss))) return rc;
   if ((rc = run_refine<T>(p, theta, r, noise, ss))) return rc;
   tick(p, TS_SOLVE, 1, ss);
-  if (ov) hipEventRecord(p->ev[1], ss);
+  SolveJoin join{s, nullptr};
+  if (ov) {
+    hipEventRecord(p->ev[1], ss);
+    join.ev = p->ev[1];
+    join.armed = true;
+  }
   p->timed_valid = 0;
   p->have_inverse = 0;
-  if (!with_grad && ov) hipStreamWaitEvent(s, p->ev[1], 0);
+  if (!with_grad && ov) {
+    hipStreamWaitEvent(s, p->ev[1], 0);
+    join.armed = false;
+  }
   if (fused) {
     // TIME_LAUUM then covers the fused launch (N^3/3 flop on MFMA + the contraction's vector work beside it), TIME_GRAD the
     // second reduction stage alone
@@ -828,6 +754,7 @@ static int fit_step(dgp_plan* p, const double* theta, const void* r, const void*
     if ((rc = run_lauum<T>(p, s))) return rc;
     tick(p, TS_LAUUM, 1, s);
     if (ov) hipStreamWaitEvent(s, p->ev[1], 0);
+    join.armed = false;
     tick(p, TS_GRAD, 0, s);
     if ((rc = run_grad<T>(p, theta, (T*)out + DGP_OUT_DTHETA, s))) return rc;
     tick(p, TS_GRAD, 1, s);
@@ -842,28 +769,12 @@ static int fit_step(dgp_plan* p, const double* theta, const void* r, const void*
   p->have_factor = 1;
   return (int)hipGetLastError();
 }
+template int dgp::fit_step<double>(dgp_plan*, const double*, const void*, const void*, void*, void*, void*, int, hipStream_t);
+template int dgp::fit_step<float>(dgp_plan*, const double*, const void*, const void*, void*, void*, void*, int, hipStream_t);
 
-// ---- inference on the factorisation a plan holds.  Batched plans run every launch once for all sites (gridDim.z =
-// sites, like the fit step): the caller's work area holds one slice per site (site stride = the single-site size).
-static size_t predict_site_bytes(const dgp_plan* p, int64_t m) {
-  const size_t M = (size_t)round_up(m, DGP_TILE_HOST), e = p->elem;
-  return align_up(e * M * p->d) + 2 * align_up(e * (size_t)p->N * M) + 3 * align_up(e * M) + align_up(e * 2 * PREDICT_SPLIT * M);
-}
-// hyperparameters of a batch of more than 8 sites travel through the plan's device scratch + a pinned staging slot
-struct PreSlot {
-  dgp_plan* p;
-  void* staging;
-  hipStream_t s;
-  PreSlot(dgp_plan* plan, hipStream_t st) : p(plan), staging(plan->pre ? plan->ring.acquire(pre_scratch_bytes(plan->B)) : nullptr), s(st) {
-    plan->pre_ready = 0;  // the fit step's copy of the hyperparameters is overwritten
-  }
-  ~PreSlot() {
-    if (staging) p->ring.commit(s);
-  }
-};
-
+// K(X, X*) for the inference entries of the other units: the test points [B][m][d] to SoA at `work`, the cross Gram to Ks
 template <typename T>
-static int cross(dgp_plan* p, const double* theta, const void* Xs, int64_t m, void* work, void* Ks, hipStream_t s, long wbs = 0) {
+int dgp::cross(dgp_plan* p, const double* theta, const void* Xs, int64_t m, void* work, void* Ks, hipStream_t s, long wbs) {
   const long M = round_up(m, DGP_TILE_HOST);
   Batch wb;  // the test points: [B][m][d] -> SoA in the work area
   wb.B = p->B;
@@ -874,278 +785,8 @@ static int cross(dgp_plan* p, const double* theta, const void* Xs, int64_t m, vo
   return gram_cross<T>(p->model, p->d, (const T*)p->Xt, p->N, (int)p->n, (const T*)work, M, (int)m, theta, (T*)Ks, s, batch_of<T>(p), wbs,
                        p->pre, slot.staging);
 }
-
-template <typename T>
-__global__ void copy_rows_kernel(const T* src, long n, T* dst, long src_stride) {  // dst [site][n] <- src at src_stride
-  src = site(src, src_stride);
-  dst = site(dst, n);
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) dst[i] = src[i];
-}
-
-template <typename T>
-static int predict_common(dgp_plan* p, const double* theta, const void* Xs, int64_t m, void* work, void* mean, T** V_out, T** Xst_out,
-                          T** vpad_out, long* wbs_out, hipStream_t s) {
-  const long M = round_up(m, DGP_TILE_HOST);
-  const size_t e = sizeof(T);
-  const long wbs = p->B > 1 ? (long)(predict_site_bytes(p, m) / e) : 0;
-  char* w = (char*)work;
-  T* Xst = (T*)w; w += align_up(e * M * p->d);
-  T* Ks = (T*)w; w += align_up(e * (size_t)p->N * M);
-  T* V = (T*)w; w += align_up(e * (size_t)p->N * M);
-  T* kss = (T*)w; w += align_up(e * M);
-  T* mpad = (T*)w; w += align_up(e * M);
-  T* vpad = (T*)w; w += align_up(e * M);
-  T* part = (T*)w;
-  const unsigned Bz = (unsigned)p->B;
-  int rc = cross<T>(p, theta, Xs, m, Xst, Ks, s, wbs);
-  if (rc) return rc;
-  Batch wb;
-  wb.B = p->B;
-  if ((rc = gram_diag<T>(p->model, p->d, Xst, M, (int)m, theta, kss, s, wb, wbs, p->pre))) return rc;
-  if ((rc = predict_var<T>((const T*)p->Tm, p->N, Ks, M, V, (const T*)p->alpha, kss, part, mpad, vpad, s, batch_of<T>(p), wbs))) return rc;
-  copy_rows_kernel<T><<<dim3((unsigned)((m + 255) / 256), 1, Bz), 256, 0, s>>>(mpad, m, (T*)mean, wbs);
-  *V_out = V;
-  *Xst_out = Xst;
-  *vpad_out = vpad;
-  *wbs_out = wbs;
-  return (int)hipGetLastError();
-}
-
-template <typename T>
-static int predict(dgp_plan* p, const double* theta, const void* Xs, int64_t m, void* work, void* mean, void* var,
-                   hipStream_t s) {
-  T *V, *Xst, *vpad;
-  long wbs;
-  int rc = predict_common<T>(p, theta, Xs, m, work, mean, &V, &Xst, &vpad, &wbs, s);
-  if (rc) return rc;
-  copy_rows_kernel<T><<<dim3((unsigned)((m + 255) / 256), 1, (unsigned)p->B), 256, 0, s>>>(vpad, m, (T*)var, wbs);
-  return (int)hipGetLastError();
-}
-
-template <typename T>
-static int post_cov(dgp_plan* p, const double* theta, const void* Xs, int64_t m, void* work, void* mean, void* cov,
-                    hipStream_t s) {
-  const long M = round_up(m, DGP_TILE_HOST);
-  T *V, *Xst, *vpad;
-  long wbs;
-  int rc = predict_common<T>(p, theta, Xs, m, work, mean, &V, &Xst, &vpad, &wbs, s);
-  if (rc) return rc;
-  // zero "noise" for K(Xs, Xs); a batched plan's sites keep theirs at the work area's site stride
-  hipError_t he = hipMemset2DAsync(vpad, sizeof(T) * (size_t)(wbs > 0 ? wbs : M), 0, sizeof(T) * M, (size_t)p->B, s);
-  if (he != hipSuccess) return (int)he;
-  Batch wb;
-  wb.B = p->B;
-  wb.ws = wbs;
-  if ((rc = gram_sym<T>(p->model, p->d, Xst, M, (int)m, theta, vpad, (T*)cov, s, wb, p->pre, nullptr, M * M, wbs, true))) return rc;
-  return posterior_cov<T>(V, p->N, M, (T*)cov, s, p->B, wbs);
-}
-
-struct VjpLayout {
-  size_t Xst, Ks, g, beta, part, spart, total;
-};
-static VjpLayout vjp_layout(const dgp_plan* p, int64_t m) {
-  const size_t M = (size_t)round_up(m, DGP_TILE_HOST), e = p->elem, N = (size_t)p->N;
-  const size_t nb = N / 64, blocks_sym = nb * (nb + 1) / 2, blocks_cross = (M / 64) * nb;
-  VjpLayout L;
-  size_t o = 0;
-  L.Xst = o; o += align_up(e * M * p->d);
-  L.Ks = o; o += align_up(e * N * M);
-  L.g = o; o += align_up(e * (N > M ? N : M));
-  L.beta = o; o += align_up(e * N);
-  L.part = o; o += align_up(e * 24 * (blocks_sym > blocks_cross ? blocks_sym : blocks_cross));
-  L.spart = o; o += align_up(e * (size_t)solve_partials(p->N));
-  L.total = o;
-  return L;
-}
-
-template <typename T>
-__global__ void matvec_cols_kernel(const T* Ks, long N, long Mp, int n, const T* alpha, T* out, long bs, long wbs, const int* ns) {
-  // out[j] = sum_i Ks[i][j] alpha_i : one thread per column, coalesced across columns
-  Ks = site(Ks, wbs);
-  out = site(out, wbs);
-  alpha = site(alpha, bs);
-  n = site_n(ns, n);
-  const long j = (long)blockIdx.x * 256 + threadIdx.x;
-  if (j >= Mp) return;
-  T acc = T(0);
-  for (long i = 0; i < n; ++i) acc += Ks[i * Mp + j] * alpha[i];
-  out[j] = acc;
-}
-
-template <typename T>
-static int predict_mean(dgp_plan* p, const double* theta, const void* Xs, int64_t m, void* work, void* mean,
-                        hipStream_t s) {
-  const VjpLayout L = vjp_layout(p, m);
-  const long M = round_up(m, DGP_TILE_HOST);
-  const long wbs = p->B > 1 ? (long)(L.total / sizeof(T)) : 0;
-  const Batch bt = batch_of<T>(p);
-  char* w = (char*)work;
-  int rc = cross<T>(p, theta, Xs, m, w + L.Xst, w + L.Ks, s, wbs);
-  if (rc) return rc;
-  matvec_cols_kernel<T><<<dim3((unsigned)((M + 255) / 256), 1, (unsigned)p->B), 256, 0, s>>>((const T*)(w + L.Ks), p->N, M, (int)p->n,
-                                                                                           (const T*)p->alpha, (T*)(w + L.g), bt.ws, wbs, bt.ns);
-  copy_rows_kernel<T><<<dim3((unsigned)((m + 255) / 256), 1, (unsigned)p->B), 256, 0, s>>>((const T*)(w + L.g), m, (T*)mean, wbs);
-  return (int)hipGetLastError();
-}
-
-template <typename T>
-static int mean_vjp(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const void* wts, void* work,
-                    void* dtheta, void* dr, void* dnoise, hipStream_t s) {
-  const VjpLayout L = vjp_layout(p, m);
-  const long M = round_up(m, DGP_TILE_HOST);
-  const long wbs = p->B > 1 ? (long)(L.total / sizeof(T)) : 0;
-  const Batch bt = batch_of<T>(p);
-  char* w = (char*)work;
-  T* Xst = (T*)(w + L.Xst);
-  T* Ks = (T*)(w + L.Ks);
-  T* g = (T*)(w + L.g);
-  T* beta = (T*)(w + L.beta);
-  int rc = cross<T>(p, theta, Xs, m, Xst, Ks, s, wbs);
-  if (rc) return rc;
-  if ((rc = gemv_rows<T>(Ks, p->N, M, (int)m, (const T*)wts, g, s, p->B, wbs))) return rc;   // g = K(X, X*) w
-  if ((rc = symv_lower<T>((const T*)p->S, p->N, g, (int)p->n, (const T*)p->alpha, beta, (T*)(w + L.spart),
-                          (T*)dnoise, s, bt, wbs)))                                         // beta = K^^-1 g
-    return rc;
-  if (dr) copy_rows_kernel<T><<<dim3((unsigned)((p->n + 255) / 256), 1, (unsigned)p->B), 256, 0, s>>>(beta, p->n, (T*)dr, wbs);
-  PreSlot slot(p, s);
-  return mean_vjp_grad<T>(p->model, p->d, (const T*)p->Xt, p->N, (int)p->n, Xst, M, (int)m, theta, (const T*)p->alpha,
-                          beta, (const T*)wts, (T*)(w + L.part), (T*)dtheta, s, bt, wbs, p->B > 1 ? p->ntheta : 0, p->pre, slot.staging);
-}
-
-// streamed period moments: the prediction's work area (its first stages leave V, Xs's SoA copy and the predicted variance
-// there), then the moment pass's work area
-template <typename T>
-static int post_period(dgp_plan* p, const double* theta, const void* Xs, int64_t m, int mode, const void* mu, const double* scale2,
-                       const double* w, const int32_t* group, int P, const void* ev, void* work, double* mean_out, double* cov_out,
-                       hipStream_t s) {
-  double* pm = (double*)((char*)work + predict_site_bytes(p, m) * (size_t)p->B);
-  T *V, *Xst, *vpad;
-  long wbs;
-  // the latent mean the prediction also writes (B x m elements) lands in the moment pass's area, which its first launch resets
-  int rc = predict_common<T>(p, theta, Xs, m, work, pm, &V, &Xst, &vpad, &wbs, s);
-  if (rc) return rc;
-  return posterior_period_moments<T>(mode, p->model, p->d, V, p->N, (long)m, p->B, Xst, vpad, wbs, theta, (const T*)mu, scale2, w,
-                                     group, P, (const T*)ev, pm, mean_out, cov_out, s, p->pre);
-}
-
-// streamed exceedance moments: the prediction's work area as for post_period, one covariance panel of R x M elements per site,
-// then the moment pass's work area
-static size_t exceed_panel_bytes(const dgp_plan* p, int64_t m, int panel_rows) {
-  return align_up(p->elem * (size_t)exceedance_panel_rows((long)m, panel_rows) * (size_t)round_up(m, DGP_TILE_HOST));
-}
-template <typename T>
-static int post_exceed(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const void* mu, const double* thresh, int L,
-                       const double* w, const int32_t* group, int P, const void* ev, int panel_rows, void* work, double* mean_out,
-                       double* cov_out, hipStream_t s) {
-  const size_t pb = exceed_panel_bytes(p, m, panel_rows);
-  T* panel = (T*)((char*)work + predict_site_bytes(p, m) * (size_t)p->B);
-  double* ex = (double*)((char*)panel + pb * (size_t)p->B);
-  T *V, *Xst, *vpad;
-  long wbs;
-  // the latent mean the prediction also writes (B x m elements) lands in the moment pass's area, which its first launches reset
-  int rc = predict_common<T>(p, theta, Xs, m, work, ex, &V, &Xst, &vpad, &wbs, s);
-  if (rc) return rc;
-  return posterior_exceedance_moments<T>(p->model, p->d, V, p->N, (long)m, p->B, Xst, vpad, wbs, theta, (const T*)mu, thresh, L, w, group,
-                                         P, (const T*)ev, panel_rows, panel, (long)(pb / sizeof(T)), ex, mean_out, cov_out, s, p->pre);
-}
-
-// ---- posterior products of `planes` side-by-side cross Grams per test point: the covariance's additive parts (dgp_terms.hip,
-// planes = C) and the value with its input derivatives (dgp_slopes.hip, planes = P = 1 + ncols).  Work area per site: the test
-// points' SoA copy, the cross Grams side by side (N x planes M), V = T Ks of the same shape, `prior_rows` rows of M prior
-// (co)variances -- the parts' C variances, or the derivatives' packed P (P + 1) / 2 block -- and the slab partials.
-struct PlanesLayout {
-  size_t Xst, Ks, V, prior, part, total;
-};
-static PlanesLayout planes_layout(const dgp_plan* p, int64_t m, int planes, int prior_rows) {
-  const size_t M = (size_t)round_up(m, DGP_TILE_HOST), e = p->elem, N = (size_t)p->N;
-  PlanesLayout L;
-  size_t o = 0;
-  L.Xst = o; o += align_up(e * M * p->d);
-  L.Ks = o; o += align_up(e * N * (size_t)planes * M);
-  L.V = o; o += align_up(e * N * (size_t)planes * M);
-  L.prior = o; o += align_up(e * (size_t)prior_rows * M);
-  L.part = o; o += align_up(e * (size_t)terms_partials(planes, (long)M));
-  L.total = o;
-  return L;
-}
-
-// The driver: pack the test points, fill the cross planes, the prior rows, V = T Ks at width planes x M, reduce.  The three
-// launchers that differ between the products are callables:
-//   cross(Xst, M, Ks, bt, wbs, staging)      prior(Xst, M, prior, wb, wbs)      reduce(V, Ks, M, prior, part, bt, wbs)
-template <typename T, typename Cross, typename Prior, typename Reduce>
-static int predict_planes(dgp_plan* p, const void* Xs, int64_t m, const PlanesLayout& L, int planes, void* work, hipStream_t s,
-                          Cross cross, Prior prior, Reduce reduce) {
-  const long M = round_up(m, DGP_TILE_HOST);
-  const long wbs = p->B > 1 ? (long)(L.total / sizeof(T)) : 0;
-  const Batch bt = batch_of<T>(p);
-  char* w = (char*)work;
-  T* Xst = (T*)(w + L.Xst);
-  T* Ks = (T*)(w + L.Ks);
-  T* V = (T*)(w + L.V);
-  T* pr = (T*)(w + L.prior);
-  Batch wb;  // the test points: [B][m][d] -> SoA in the work area
-  wb.B = p->B;
-  wb.ws = wbs;
-  int rc = pack_x<T>((const T*)Xs, (int)m, p->d, M, Xst, s, wb);
-  if (rc) return rc;
-  {
-    PreSlot slot(p, s);
-    if ((rc = cross(Xst, M, Ks, bt, wbs, slot.staging))) return rc;
-  }
-  wb.ws = 0;
-  if ((rc = prior(Xst, M, pr, wb, wbs))) return rc;
-  if ((rc = predict_v<T>((const T*)p->Tm, p->N, Ks, (long)planes * M, V, s, bt, wbs))) return rc;
-  return reduce(V, Ks, M, pr, (T*)(w + L.part), bt, wbs);
-}
-
-template <typename T>
-static int predict_terms(dgp_plan* p, const double* theta, const void* Xs, int64_t m, void* work, void* mean, void* cov,
-                         hipStream_t s) {
-  const int C = model_nterms(p->model, p->d);
-  return predict_planes<T>(
-      p, Xs, m, planes_layout(p, m, C, C), C, work, s,
-      [&](const T* Xst, long M, T* Ks, const Batch& bt, long wbs, void* staging) {
-        return gram_cross_terms<T>(p->model, p->d, (const T*)p->Xt, p->N, (int)p->n, Xst, M, (int)m, theta, Ks, s, bt, wbs, p->pre, staging);
-      },
-      [&](const T* Xst, long M, T* kss, const Batch& wb, long wbs) {
-        return gram_diag_terms<T>(p->model, p->d, Xst, M, (int)m, theta, kss, s, wb, wbs, p->pre);
-      },
-      [&](const T* V, const T* Ks, long M, const T* kss, T* part, const Batch& bt, long wbs) {
-        return terms_reduce<T>(C, V, Ks, p->N, M, (int)m, (const T*)p->alpha, kss, part, (T*)mean, (T*)cov, s, bt, wbs);
-      });
-}
-
-template <typename T>
-static int predict_slopes(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const int* cols, int ncols, void* work,
-                          void* mean, void* cov, hipStream_t s) {
-  const int P = 1 + ncols;
-  return predict_planes<T>(
-      p, Xs, m, planes_layout(p, m, P, P * (P + 1) / 2), P, work, s,
-      [&](const T* Xst, long M, T* Ks, const Batch& bt, long wbs, void* staging) {
-        return gram_cross_slopes<T>(p->model, p->d, (const T*)p->Xt, p->N, (int)p->n, Xst, M, (int)m, theta, cols, ncols, Ks, s, bt, wbs,
-                                    p->pre, staging);
-      },
-      [&](const T* Xst, long M, T* prior, const Batch& wb, long wbs) {
-        return gram_prior_slopes<T>(p->model, p->d, Xst, M, (int)m, theta, cols, ncols, prior, s, wb, wbs, p->pre);
-      },
-      [&](const T* V, const T* Ks, long M, const T* prior, T* part, const Batch& bt, long wbs) {
-        return slopes_reduce<T>(P, V, Ks, p->N, M, (int)m, (const T*)p->alpha, prior, part, (T*)mean, (T*)cov, s, bt, wbs);
-      });
-}
-
-#define DGP_BY_DTYPE(p, CALL64, CALL32) ((p)->dtype == DGP_F64 ? (CALL64) : (CALL32))
-#define DGP_CHECK_PLAN(p)                                                        \
-  if (!(p)) return fail(DGP_E_ARG, "null plan");                                 \
-  if (!(p)->ws) return fail(DGP_E_WORKSPACE, "plan has no workspace: call dgp_plan_set_workspace")
-#define DGP_SINGLE_SITE(p) \
-  if ((p)->B != 1)         \
-  return fail(DGP_E_STATE, "batched plans support dgp_set_inputs / dgp_fit_step / dgp_factorize / dgp_predict / dgp_predict_mean / dgp_mean_vjp only")
-static int wrap(int rc, const char* where) {
-  if (rc > 0) return hipfail((hipError_t)rc, where);
-  if (rc < 0) return fail(rc, where);
-  return 0;
-}
+template int dgp::cross<double>(dgp_plan*, const double*, const void*, int64_t, void*, void*, hipStream_t, long);
+template int dgp::cross<float>(dgp_plan*, const double*, const void*, int64_t, void*, void*, hipStream_t, long);
 
 extern "C" {
 
@@ -1179,928 +820,6 @@ int dgp_factorize(dgp_plan* p, const double* theta, const void* r, const void* n
   int rc = DGP_BY_DTYPE(p, fit_step<double>(p, theta, r, noise, out, nullptr, nullptr, 0, s),
                         fit_step<float>(p, theta, r, noise, out, nullptr, nullptr, 0, s));
   return wrap(rc, "dgp_factorize");
-}
-
-}  // extern "C"
-
-// ---- censored observations: Newton's mode search on the factorise path, then one step at the mode (dgp_censored.hip).
-// One code path for a single-site plan and for a batch: every Newton iteration factorises ALL sites in lockstep; a site is done when
-// it has no censored row, its proposal is within tol or its factorisation failed, and a done site is frozen on the device
-// (CEN_ST_DONE), so that it rides through the remaining factorisations on unchanged pseudo-data.  The host reads the B status
-// blocks in one copy per iteration.  stat: [B][4].  `batched`: the entry's texts name the site.
-// Returns 0, a HIP error (> 0), or DGP_E_ARG / DGP_E_NOCONV with the error text already set.
-static int laplace(dgp_plan* p, const double* theta, const double* y, const double* mean, const double* noise, const int* side,
-                   double* f, int maxit, double tol, char* work, double* out, double* dr, double* stat, int with_grad, int batched,
-                   const char* where, hipStream_t s, const double* upper = nullptr, int interval = 0) {
-  const int B = p->B;
-  const CensoredLayout L = censored_layout(p->N, p->n, B);
-  const Batch bt = batch_of<double>(p);
-  auto D = [&](size_t off) { return (double*)(work + off); };
-  const int n = (int)p->n;
-  const long wss = (long)(L.slice / sizeof(double));
-  const double* alpha = (const double*)p->alpha;
-  std::vector<double> st((size_t)B * CEN_ST_LEN);
-  auto S = [&](int b, int k) -> double { return st[(size_t)b * CEN_ST_LEN + k]; };
-  auto read_status = [&]() -> int {
-    hipError_t e = hipMemcpyAsync(st.data(), D(L.status), sizeof(double) * st.size(), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    return (int)e;
-  };
-  int rc;
-  for (int k = 0; k < 4 * B; ++k) stat[k] = 0.0;
-  if ((rc = censored_terms(f, y, side, noise, mean, n, 1, 0, work, L, s, bt, upper)) || (rc = read_status())) return rc;
-  bool any = false, any_plain = false;
-  for (int b = 0; b < B; ++b) {
-    if (interval && S(b, CEN_ST_BAD) != 0.0) {
-      snprintf(g_err, sizeof(g_err), upper ? "%s: side values must be -1, 0, +1 or 2 (site %d)"
-                                           : "%s: a row of side 2 needs upper_dev; other side values must be -1, 0 or +1 (site %d)",
-               where, b);
-      return DGP_E_ARG;
-    }
-    if (S(b, CEN_ST_BADBRK) != 0.0) {
-      snprintf(g_err, sizeof(g_err), "%s: %d bad bracket(s) in site %d: a row of side 2 needs a finite upper above its y", where,
-               (int)S(b, CEN_ST_BADBRK), b);
-      return DGP_E_ARG;
-    }
-    if (S(b, CEN_ST_BAD) != 0.0) {
-      if (batched)
-        snprintf(g_err, sizeof(g_err), "%s: side values must be -1, 0 or +1 (site %d)", where, b);
-      else
-        snprintf(g_err, sizeof(g_err), "%s: side values must be -1, 0 or +1", where);
-      return DGP_E_ARG;
-    }
-    (S(b, CEN_ST_NCENS) != 0.0 ? any : any_plain) = true;
-  }
-  if (!any) {  // nothing censored: the plain step on (y - m, v), bit for bit
-    if ((rc = fit_step<double>(p, theta, D(L.rt), D(L.nn), out, with_grad ? dr : nullptr, with_grad ? D(L.dnoise) : nullptr, with_grad, s)))
-      return rc;
-    return censored_mode(f, mean, alpha, n, work, L, s, bt);
-  }
-  if ((rc = (int)hipMemsetAsync(D(L.acur), 0, sizeof(double) * (size_t)B * (size_t)n, s))) return rc;
-  std::vector<char> active((size_t)B);
-  for (int b = 0; b < B; ++b) active[b] = S(b, CEN_ST_DONE) == 0.0;
-  int it = 0;
-  for (;;) {
-    if ((rc = fit_step<double>(p, theta, D(L.rt), D(L.nn), D(L.out), nullptr, nullptr, 0, s))) return rc;
-    ++it;
-    // proposal, line search, update; then the next system (or the one at the mode) of every site that moved
-    if ((rc = censored_newton_update(f, y, side, noise, mean, alpha, n, it, tol, work, L, s, bt, upper)) ||
-        (rc = censored_terms(f, y, side, noise, mean, n, 0, it, work, L, s, bt, upper)) || (rc = read_status()))
-      return rc;
-    bool all_done = true;
-    for (int b = 0; b < B; ++b) {
-      if (!active[b]) continue;
-      stat[4 * b] = (double)it;
-      stat[4 * b + 1] = S(b, CEN_ST_DMAX);
-      stat[4 * b + 2] += S(b, CEN_ST_HALVINGS);
-      if (S(b, CEN_ST_DONE) != 0.0)
-        active[b] = 0;  // converged, or not positive definite: f did not move; the step below reports it through DGP_OUT_INFO
-      else
-        all_done = false;
-    }
-    if (all_done || it >= maxit) break;
-  }
-  if ((rc = fit_step<double>(p, theta, D(L.rt), D(L.nn), out, nullptr, with_grad ? D(L.dnoise) : nullptr, with_grad, s))) return rc;
-  if (with_grad) {
-    if ((rc = censored_weights(alpha, n, p->N, work, L, s, bt))) return rc;
-    // u = T^T (T w) in the work area: the plan's z, alpha and result rows stay as the step left them
-    if ((rc = solve_work<double>((const double*)p->Tm, p->N, D(L.slices + L.w), n, D(L.slices + L.z), D(L.slices + L.u),
-                                 D(L.slices + L.spart), D(L.slices + L.quad), wss, s, bt)))
-      return rc;
-    // (the step's Gram build left this theta in the plan's hyperparameter scratch)
-    if ((rc = gram_bilinear<double>(p->model, p->d, (const double*)p->Xt, p->N, n, theta, D(L.slices + L.u), alpha,
-                                    D(L.slices + L.gpart), out + DGP_OUT_DTHETA, 1, s, bt, wss, bt.ws, wss, DGP_OUT_LEN, p->pre, false,
-                                    nullptr)))
-      return rc;
-  }
-  if (any_plain && (rc = censored_mode(f, mean, alpha, n, work, L, s, bt))) return rc;  // the batch-mates without a censored row
-  if ((rc = censored_result(alpha, side, (const double*)p->dr_w, n, with_grad, out, dr, work, L, s, bt)) || (rc = read_status())) return rc;
-  int open_site = -1;
-  for (int b = 0; b < B; ++b) {
-    stat[4 * b + 3] = S(b, CEN_ST_CAPPED);
-    if (active[b] && open_site < 0) open_site = b;
-  }
-  if (open_site >= 0) {
-    if (batched)
-      snprintf(g_err, sizeof(g_err), "%s: the mode search of site %d did not converge in %d Newton iterations (max |df| = %.3g)", where,
-               open_site, it, stat[4 * open_site + 1]);
-    else
-      snprintf(g_err, sizeof(g_err), "%s: the mode search did not converge in %d Newton iterations (max |df| = %.3g)", where, it, stat[1]);
-    return DGP_E_NOCONV;
-  }
-  return 0;
-}
-static int laplace_entry(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise, const int32_t* side,
-                         void* f, int maxit, double tol, void* work, size_t work_bytes, void* out, void* dr, double* stat,
-                         int with_grad, int batched, const char* where, void* stream, const void* upper = nullptr, int interval = 0) {
-  char msg[160];
-  if (!p) return fail(DGP_E_ARG, "null plan");
-  if (batched ? p->dtype != DGP_F64 : (p->dtype != DGP_F64 || p->B != 1)) {
-    if (batched)
-      snprintf(msg, sizeof(msg), "%s: censored fits need a float64 plan (fp32 plans are not supported)", where);
-    else
-      snprintf(msg, sizeof(msg), "%s: censored fits need a float64 single-site plan (fp32 and batched plans are not supported)", where);
-    return fail(DGP_E_ARG, msg);
-  }
-  if (!theta || !y || !mean || !noise || !side || !f || !out || !stat || maxit < 1 || !(tol >= 0.0)) {
-    snprintf(msg, sizeof(msg), "%s: null argument (f_dev included), maxit < 1 or a negative tol", where);
-    return fail(DGP_E_ARG, msg);
-  }
-  DGP_CHECK_PLAN(p);
-  if (!p->have_inputs) return fail(DGP_E_STATE, "dgp_laplace_*: call dgp_set_inputs first");
-  if (!work || work_bytes < (batched ? dgp_laplace_batched_workspace_bytes(p) : dgp_laplace_workspace_bytes(p))) {
-    snprintf(msg, sizeof(msg), "%s: workspace missing or too small", where);
-    return fail(DGP_E_WORKSPACE, msg);
-  }
-  if (((uintptr_t)work & 255) != 0) return fail(DGP_E_ARG, "dgp_laplace_*: the work area must be 256-byte aligned");
-  const int rc = laplace(p, theta, (const double*)y, (const double*)mean, (const double*)noise, (const int*)side, (double*)f, maxit, tol,
-                         (char*)work, (double*)out, (double*)dr, stat, with_grad, batched, where, (hipStream_t)stream,
-                         (const double*)upper, interval);
-  if (rc == DGP_E_ARG || rc == DGP_E_NOCONV) return rc;  // text set where it arose
-  return wrap(rc, where);
-}
-
-// ---- censored observations by expectation propagation (dgp_ep.hip): parallel sweeps on the factorise path, then (fit step) one
-// step at the final sites, whose explicit gradient IS the gradient at the fixed point.  The host reads one status block per sweep.
-// The sites that were factorised last are the result (a converged or last sweep's proposal is not applied), so the plan's
-// factorisation, k, the cavities and log Z^ belong to one state.  stat: [6].
-static int ep(dgp_plan* p, const double* theta, const double* y, const double* mean, const double* noise, const int* side,
-              const double* upper, double* yt, double* nt, int cold, int maxit, double tol, double damping, char* work, double* out,
-              double* dr, double* stat, double* cav_mean, double* cav_var, double* logz, int with_grad, const char* where, hipStream_t s) {
-  const EpLayout L = ep_layout(p->N, p->n);
-  const Batch bt = batch_of<double>(p);
-  auto D = [&](size_t off) { return (double*)(work + off); };
-  const int n = (int)p->n;
-  const double* alpha = (const double*)p->alpha;
-  const double* Tm = (const double*)p->Tm;
-  double st[CEN_ST_LEN > EP_ST_LEN ? CEN_ST_LEN : EP_ST_LEN];
-  auto read_status = [&](size_t off, int len) -> int {
-    hipError_t e = hipMemcpyAsync(st, D(off), sizeof(double) * (size_t)len, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    return (int)e;
-  };
-  int rc;
-  for (int k = 0; k < 6; ++k) stat[k] = 0.0;
-  // the Laplace terms at f = m: the rows are checked as the Laplace entries check them, and a cold start is their pseudo-data
-  if ((rc = censored_terms(mean, y, side, noise, mean, n, 1, 0, work, L.cen, s, bt, upper)) || (rc = read_status(L.cen.status, CEN_ST_LEN)))
-    return rc;
-  if (st[CEN_ST_BAD] != 0.0) {
-    snprintf(g_err, sizeof(g_err),
-             upper ? "%s: side values must be -1, 0, +1 or 2" : "%s: a row of side 2 needs upper_dev; other side values must be -1, 0 or +1",
-             where);
-    return DGP_E_ARG;
-  }
-  if (st[CEN_ST_BADBRK] != 0.0) {
-    snprintf(g_err, sizeof(g_err), "%s: %d bad bracket(s): a row of side 2 needs a finite upper above its y", where, (int)st[CEN_ST_BADBRK]);
-    return DGP_E_ARG;
-  }
-  const double ncens = st[CEN_ST_NCENS];
-  stat[5] = ncens;
-  const bool aux = cav_mean || cav_var || logz;
-  if (ncens == 0.0) {  // nothing censored: the plain step on (y - m, v), bit for bit; the sites are (y, v)
-    if ((rc = fit_step<double>(p, theta, D(L.cen.rt), D(L.cen.nn), out, with_grad ? dr : nullptr, with_grad ? D(L.cen.dnoise) : nullptr,
-                               with_grad, s)) ||
-        (rc = ep_init(y, side, noise, mean, yt, nt, n, 1, work, L, s)))
-      return rc;
-    if (aux && ((rc = ep_diag(Tm, p->N, n, D(L.kdiag), work, L, s)) ||
-                (rc = ep_result(alpha, y, side, noise, upper, yt, nt, n, nullptr, cav_mean, cav_var, logz, work, L, s))))
-      return rc;
-    return 0;
-  }
-  if ((rc = ep_init(y, side, noise, mean, yt, nt, n, cold, work, L, s))) return rc;
-  int it = 0;
-  bool conv = false;
-  for (;;) {
-    if ((rc = fit_step<double>(p, theta, D(L.cen.rt), nt, D(L.cen.out), nullptr, nullptr, 0, s))) return rc;
-    ++it;
-    if ((rc = ep_sweep(Tm, p->N, alpha, y, side, noise, mean, upper, yt, nt, n, it, it >= maxit, tol, damping, work, L, s)) ||
-        (rc = read_status(L.status, EP_ST_LEN)))
-      return rc;
-    stat[0] = (double)it;
-    stat[1] = st[EP_ST_DMU];
-    stat[2] = st[EP_ST_DTAU];
-    stat[3] = st[EP_ST_CAPPED];
-    stat[4] = st[EP_ST_HELD];
-    conv = st[EP_ST_DONE] != 0.0;  // converged, or not positive definite: the result row reports that through DGP_OUT_INFO
-    if (conv || it >= maxit) break;
-  }
-  if (with_grad) {
-    // the same system once more with K^^-1 and the gradient contraction: the same T and alpha, so k stays valid
-    if ((rc = fit_step<double>(p, theta, D(L.cen.rt), nt, out, dr, D(L.cen.dnoise), 1, s))) return rc;
-  } else if ((rc = (int)hipMemcpyAsync(out, D(L.cen.out), sizeof(double) * DGP_OUT_LEN, hipMemcpyDeviceToDevice, s))) {
-    return rc;
-  }
-  if ((rc = ep_result(alpha, y, side, noise, upper, yt, nt, n, out, cav_mean, cav_var, logz, work, L, s)) || (rc = (int)hipStreamSynchronize(s)))
-    return rc;
-  if (!conv) {
-    snprintf(g_err, sizeof(g_err), "%s: expectation propagation did not converge in %d sweeps (max |dmu| = %.3g, max v |dtau| = %.3g)",
-             where, it, stat[1], stat[2]);
-    return DGP_E_NOCONV;
-  }
-  return 0;
-}
-static int ep_entry(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise, const int32_t* side,
-                    const void* upper, void* yt, void* nt, int cold, int maxit, double tol, double damping, void* work, size_t work_bytes,
-                    void* out, void* dr, double* stat, void* cav_mean, void* cav_var, void* logz, int with_grad, const char* where,
-                    void* stream) {
-  char msg[200];
-  if (!p) return fail(DGP_E_ARG, "null plan");
-  if (p->dtype != DGP_F64 || p->B != 1) {
-    snprintf(msg, sizeof(msg), "%s: expectation propagation needs a float64 single-site plan (fp32 and batched plans are not supported)", where);
-    return fail(DGP_E_ARG, msg);
-  }
-  if (!theta || !y || !mean || !noise || !side || !yt || !nt || !out || !stat || maxit < 1 || !(tol >= 0.0)) {
-    snprintf(msg, sizeof(msg), "%s: null argument (ytilde_dev / ntilde_dev included), maxit < 1 or a negative tol", where);
-    return fail(DGP_E_ARG, msg);
-  }
-  if (!(damping > 0.0 && damping <= 1.0)) {
-    snprintf(msg, sizeof(msg), "%s: damping must lie in (0, 1]", where);
-    return fail(DGP_E_ARG, msg);
-  }
-  DGP_CHECK_PLAN(p);
-  if (!p->have_inputs) return fail(DGP_E_STATE, "dgp_ep_*: call dgp_set_inputs first");
-  if (!work || work_bytes < dgp_ep_workspace_bytes(p)) {
-    snprintf(msg, sizeof(msg), "%s: workspace missing or too small", where);
-    return fail(DGP_E_WORKSPACE, msg);
-  }
-  if (((uintptr_t)work & 255) != 0) return fail(DGP_E_ARG, "dgp_ep_*: the work area must be 256-byte aligned");
-  const int rc = ep(p, theta, (const double*)y, (const double*)mean, (const double*)noise, (const int*)side, (const double*)upper,
-                    (double*)yt, (double*)nt, cold, maxit, tol, damping, (char*)work, (double*)out, (double*)dr, stat, (double*)cav_mean,
-                    (double*)cav_var, (double*)logz, with_grad, where, (hipStream_t)stream);
-  if (rc == DGP_E_ARG || rc == DGP_E_NOCONV) return rc;  // text set where it arose
-  return wrap(rc, where);
-}
-
-extern "C" {
-
-size_t dgp_ep_workspace_bytes(const dgp_plan* p) {
-  if (!p || p->dtype != DGP_F64 || p->B != 1) return 0;
-  return ep_layout(p->N, p->n).total;
-}
-
-int dgp_ep_fit_step(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise, const int32_t* side,
-                    const void* upper, void* ytilde, void* ntilde, int cold_start, int maxit, double tol, double damping, void* work,
-                    size_t work_bytes, void* out, void* dr, double* stat, void* cav_mean, void* cav_var, void* logz, void* stream) {
-  return ep_entry(p, theta, y, mean, noise, side, upper, ytilde, ntilde, cold_start, maxit, tol, damping, work, work_bytes, out, dr, stat,
-                  cav_mean, cav_var, logz, 1, "dgp_ep_fit_step", stream);
-}
-
-int dgp_ep_factorize(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise, const int32_t* side,
-                     const void* upper, void* ytilde, void* ntilde, int cold_start, int maxit, double tol, double damping, void* work,
-                     size_t work_bytes, void* out, double* stat, void* cav_mean, void* cav_var, void* logz, void* stream) {
-  return ep_entry(p, theta, y, mean, noise, side, upper, ytilde, ntilde, cold_start, maxit, tol, damping, work, work_bytes, out, nullptr,
-                  stat, cav_mean, cav_var, logz, 0, "dgp_ep_factorize", stream);
-}
-
-int dgp_ep_diag(dgp_plan* p, void* k, void* work, size_t work_bytes, void* stream) {
-  if (!p || p->dtype != DGP_F64 || p->B != 1) return fail(DGP_E_ARG, "dgp_ep_diag: needs a float64 single-site plan");
-  if (!k) return fail(DGP_E_ARG, "dgp_ep_diag: null argument");
-  DGP_CHECK_PLAN(p);
-  if (!p->have_factor) return fail(DGP_E_STATE, "dgp_ep_diag: no factorisation in the plan");
-  if (!work || work_bytes < dgp_ep_workspace_bytes(p)) return fail(DGP_E_WORKSPACE, "dgp_ep_diag: workspace missing or too small");
-  if (((uintptr_t)work & 255) != 0) return fail(DGP_E_ARG, "dgp_ep_diag: the work area must be 256-byte aligned");
-  return wrap(ep_diag((const double*)p->Tm, p->N, (int)p->n, (double*)k, (char*)work, ep_layout(p->N, p->n), (hipStream_t)stream),
-              "dgp_ep_diag");
-}
-
-size_t dgp_laplace_workspace_bytes(const dgp_plan* p) {
-  if (!p || p->dtype != DGP_F64 || p->B != 1) return 0;
-  return censored_layout(p->N, p->n, 1).total;
-}
-size_t dgp_laplace_batched_workspace_bytes(const dgp_plan* p) {
-  if (!p || p->dtype != DGP_F64) return 0;
-  return censored_layout(p->N, p->n, p->B).total;
-}
-
-int dgp_laplace_fit_step(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise, const int32_t* side,
-                         void* f, int maxit, double tol, void* work, size_t work_bytes, void* out, void* dr, double* stat,
-                         void* stream) {
-  return laplace_entry(p, theta, y, mean, noise, side, f, maxit, tol, work, work_bytes, out, dr, stat, 1, 0, "dgp_laplace_fit_step",
-                       stream);
-}
-
-int dgp_laplace_factorize(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise, const int32_t* side,
-                          void* f, int maxit, double tol, void* work, size_t work_bytes, void* out, double* stat, void* stream) {
-  return laplace_entry(p, theta, y, mean, noise, side, f, maxit, tol, work, work_bytes, out, nullptr, stat, 0, 0, "dgp_laplace_factorize",
-                       stream);
-}
-
-int dgp_laplace_batched_fit_step(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise,
-                                 const int32_t* side, void* f, int maxit, double tol, void* work, size_t work_bytes, void* out, void* dr,
-                                 double* stat, void* stream) {
-  return laplace_entry(p, theta, y, mean, noise, side, f, maxit, tol, work, work_bytes, out, dr, stat, 1, 1,
-                       "dgp_laplace_batched_fit_step", stream);
-}
-
-int dgp_laplace_batched_factorize(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise,
-                                  const int32_t* side, void* f, int maxit, double tol, void* work, size_t work_bytes, void* out,
-                                  double* stat, void* stream) {
-  return laplace_entry(p, theta, y, mean, noise, side, f, maxit, tol, work, work_bytes, out, nullptr, stat, 0, 1,
-                       "dgp_laplace_batched_factorize", stream);
-}
-
-int dgp_laplace_interval_fit_step(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise,
-                                  const int32_t* side, const void* upper, void* f, int maxit, double tol, void* work, size_t work_bytes,
-                                  void* out, void* dr, double* stat, void* stream) {
-  return laplace_entry(p, theta, y, mean, noise, side, f, maxit, tol, work, work_bytes, out, dr, stat, 1, 1,
-                       "dgp_laplace_interval_fit_step", stream, upper, 1);
-}
-
-int dgp_laplace_interval_factorize(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise,
-                                   const int32_t* side, const void* upper, void* f, int maxit, double tol, void* work,
-                                   size_t work_bytes, void* out, double* stat, void* stream) {
-  return laplace_entry(p, theta, y, mean, noise, side, f, maxit, tol, work, work_bytes, out, nullptr, stat, 0, 1,
-                       "dgp_laplace_interval_factorize", stream, upper, 1);
-}
-
-int dgp_debug_interval_terms(const double* za, const double* delta, int64_t count, double* out, void* stream) {
-  if (!za || !delta || !out || count <= 0 || count > (1ll << 29))
-    return fail(DGP_E_ARG, "dgp_debug_interval_terms: null argument / bad count");
-  return wrap(debug_interval_terms(za, delta, count, out, (hipStream_t)stream), "dgp_debug_interval_terms");
-}
-
-int dgp_debug_censored_terms(const double* z, int64_t count, double* out, void* stream) {
-  if (!z || !out || count <= 0 || count > (1ll << 29)) return fail(DGP_E_ARG, "dgp_debug_censored_terms: null argument / bad count");
-  return wrap(debug_censored_terms(z, count, out, (hipStream_t)stream), "dgp_debug_censored_terms");
-}
-
-// u_dev / alpha_dev [B][n] -> dtheta_dev [B][ntheta]; B = 1: the single-site sweep
-static int debug_bilinear(dgp_plan* p, const double* theta, const void* u, const void* alpha, void* work, size_t work_bytes, double* dtheta,
-                          int batched, const char* where, void* stream) {
-  char msg[160];
-  if (!p) return fail(DGP_E_ARG, "null plan");
-  if (p->dtype != DGP_F64 || (!batched && p->B != 1)) {
-    snprintf(msg, sizeof(msg), batched ? "%s: needs a float64 plan" : "%s: needs a float64 single-site plan", where);
-    return fail(DGP_E_ARG, msg);
-  }
-  if (!theta || !u || !alpha || !dtheta) {
-    snprintf(msg, sizeof(msg), "%s: null argument", where);
-    return fail(DGP_E_ARG, msg);
-  }
-  DGP_CHECK_PLAN(p);
-  if (!p->have_inputs) {
-    snprintf(msg, sizeof(msg), "%s: call dgp_set_inputs first", where);
-    return fail(DGP_E_STATE, msg);
-  }
-  if (!work || work_bytes < (batched ? dgp_laplace_batched_workspace_bytes(p) : dgp_laplace_workspace_bytes(p))) {
-    snprintf(msg, sizeof(msg), "%s: workspace missing or too small", where);
-    return fail(DGP_E_WORKSPACE, msg);
-  }
-  if (((uintptr_t)work & 255) != 0) {
-    snprintf(msg, sizeof(msg), "%s: the work area must be 256-byte aligned", where);
-    return fail(DGP_E_ARG, msg);
-  }
-  hipStream_t s = (hipStream_t)stream;
-  const int B = p->B;
-  const CensoredLayout L = censored_layout(p->N, p->n, B);
-  char* slices = (char*)work + L.slices;
-  double *up = (double*)(slices + L.u), *ap = (double*)(slices + L.w);
-  const size_t nb = sizeof(double) * (size_t)p->n;
-  hipError_t e = hipMemsetAsync(slices, 0, L.slice * (size_t)B, s);
-  if (e == hipSuccess) e = hipMemcpy2DAsync(up, L.slice, u, nb, nb, (size_t)B, hipMemcpyDeviceToDevice, s);
-  if (e == hipSuccess) e = hipMemcpy2DAsync(ap, L.slice, alpha, nb, nb, (size_t)B, hipMemcpyDeviceToDevice, s);
-  if (e != hipSuccess) return hipfail(e, where);
-  const long wss = (long)(L.slice / sizeof(double));
-  void* staging = p->pre ? p->ring.acquire(pre_scratch_bytes(B)) : nullptr;
-  const int rc = gram_bilinear<double>(p->model, p->d, (const double*)p->Xt, p->N, (int)p->n, theta, up, ap, (double*)(slices + L.gpart),
-                                       dtheta, 0, s, batch_of<double>(p), wss, wss, wss, p->ntheta, p->pre, true, staging);
-  if (staging) p->ring.commit(s);
-  p->pre_ready = 0;
-  return wrap(rc, where);
-}
-
-int dgp_debug_bilinear(dgp_plan* p, const double* theta, const void* u, const void* alpha, void* work, size_t work_bytes, double* dtheta,
-                       void* stream) {
-  return debug_bilinear(p, theta, u, alpha, work, work_bytes, dtheta, 0, "dgp_debug_bilinear", stream);
-}
-
-int dgp_debug_bilinear_batched(dgp_plan* p, const double* theta, const void* u, const void* alpha, void* work, size_t work_bytes,
-                               double* dtheta, void* stream) {
-  return debug_bilinear(p, theta, u, alpha, work, work_bytes, dtheta, 1, "dgp_debug_bilinear_batched", stream);
-}
-
-size_t dgp_predict_workspace_bytes(const dgp_plan* p, int64_t m) {
-  if (!p || m <= 0) return 0;
-  return predict_site_bytes(p, m) * (size_t)p->B;
-}
-
-int dgp_predict(dgp_plan* p, const double* theta, const void* Xs, int64_t m, void* work, size_t work_bytes,
-                void* mean, void* var, void* stream) {
-  DGP_CHECK_PLAN(p);
-  if (!theta || !Xs || !work || !mean || !var || m <= 0) return fail(DGP_E_ARG, "dgp_predict: null argument");
-  if (!p->have_factor) return fail(DGP_E_STATE, "dgp_predict: no factorisation in the plan (call dgp_factorize)");
-  if (work_bytes < dgp_predict_workspace_bytes(p, m)) return fail(DGP_E_WORKSPACE, "dgp_predict: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  const int rc = DGP_BY_DTYPE(p, predict<double>(p, theta, Xs, m, work, mean, var, s), predict<float>(p, theta, Xs, m, work, mean, var, s));
-  return wrap(rc, "dgp_predict");
-}
-
-int dgp_posterior_cov(dgp_plan* p, const double* theta, const void* Xs, int64_t m, void* work, size_t work_bytes,
-                      void* mean, void* cov, void* stream) {
-  DGP_CHECK_PLAN(p);
-  if (!theta || !Xs || !work || !mean || !cov || m <= 0) return fail(DGP_E_ARG, "dgp_posterior_cov: null argument");
-  if (!p->have_factor) return fail(DGP_E_STATE, "dgp_posterior_cov: no factorisation in the plan (call dgp_factorize)");
-  if (work_bytes < dgp_predict_workspace_bytes(p, m)) return fail(DGP_E_WORKSPACE, "dgp_posterior_cov: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  int rc = DGP_BY_DTYPE(p, post_cov<double>(p, theta, Xs, m, work, mean, cov, s),
-                        post_cov<float>(p, theta, Xs, m, work, mean, cov, s));
-  return wrap(rc, "dgp_posterior_cov");
-}
-
-int dgp_model_nterms(int model, int d) { return model_nterms(model, d); }
-
-size_t dgp_predict_terms_workspace_bytes(const dgp_plan* p, int64_t m) {
-  if (!p || m <= 0) return 0;
-  const int C = model_nterms(p->model, p->d);
-  return planes_layout(p, m, C, C).total * (size_t)p->B;
-}
-
-int dgp_predict_terms(dgp_plan* p, const double* theta, const void* Xs, int64_t m, void* work, size_t work_bytes, void* mean,
-                      void* cov, void* stream) {
-  if (!p) return fail(DGP_E_ARG, "dgp_predict_terms: null plan");
-  if (!theta || !Xs || !work || !mean || m <= 0) return fail(DGP_E_ARG, "dgp_predict_terms: null argument or m <= 0");
-  if (!p->ws) return fail(DGP_E_WORKSPACE, "plan has no workspace: call dgp_plan_set_workspace");
-  if (!p->have_factor) return fail(DGP_E_STATE, "dgp_predict_terms: no factorisation in the plan (call dgp_factorize)");
-  if (work_bytes < dgp_predict_terms_workspace_bytes(p, m)) return fail(DGP_E_WORKSPACE, "dgp_predict_terms: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  const int rc = DGP_BY_DTYPE(p, predict_terms<double>(p, theta, Xs, m, work, mean, cov, s),
-                              predict_terms<float>(p, theta, Xs, m, work, mean, cov, s));
-  return wrap(rc, "dgp_predict_terms");
-}
-
-int dgp_model_input_differentiable(int model, int d, int col) { return model_input_differentiable(model, d, col); }
-
-size_t dgp_predict_slopes_workspace_bytes(const dgp_plan* p, int64_t m, int ncols) {
-  if (!p || m <= 0 || ncols < 1 || ncols > p->d) return 0;
-  const int P = 1 + ncols;
-  return planes_layout(p, m, P, P * (P + 1) / 2).total * (size_t)p->B;
-}
-
-int dgp_predict_slopes(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const int* cols, int ncols, void* work,
-                       size_t work_bytes, void* mean, void* cov, void* stream) {
-  if (!p) return fail(DGP_E_ARG, "dgp_predict_slopes: null plan");
-  if (!theta || !Xs || !cols || !work || !mean || m <= 0) return fail(DGP_E_ARG, "dgp_predict_slopes: null argument or m <= 0");
-  if (ncols < 1 || ncols > p->d) return fail(DGP_E_ARG, "dgp_predict_slopes: ncols must be in 1 .. d");
-  for (int q = 0; q < ncols; ++q) {
-    if (cols[q] < 0 || cols[q] >= p->d) return fail(DGP_E_ARG, "dgp_predict_slopes: column outside 0 .. d - 1");
-    for (int r = 0; r < q; ++r)
-      if (cols[r] == cols[q]) return fail(DGP_E_ARG, "dgp_predict_slopes: repeated column");
-  }
-  for (int q = 0; q < ncols; ++q)
-    if (model_input_differentiable(p->model, p->d, cols[q]) != 1)
-      return fail(DGP_E_MODEL, "dgp_predict_slopes: the covariance is not differentiable in a requested column (Matern-1/2 factor)");
-  if (!p->ws) return fail(DGP_E_WORKSPACE, "plan has no workspace: call dgp_plan_set_workspace");
-  if (!p->have_factor) return fail(DGP_E_STATE, "dgp_predict_slopes: no factorisation in the plan (call dgp_factorize)");
-  if (work_bytes < dgp_predict_slopes_workspace_bytes(p, m, ncols))
-    return fail(DGP_E_WORKSPACE, "dgp_predict_slopes: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  const int rc = DGP_BY_DTYPE(p, predict_slopes<double>(p, theta, Xs, m, cols, ncols, work, mean, cov, s),
-                              predict_slopes<float>(p, theta, Xs, m, cols, ncols, work, mean, cov, s));
-  return wrap(rc, "dgp_predict_slopes");
-}
-
-size_t dgp_mean_vjp_workspace_bytes(const dgp_plan* p, int64_t m) { return (p && m > 0) ? vjp_layout(p, m).total * (size_t)p->B : 0; }
-
-int dgp_predict_mean(dgp_plan* p, const double* theta, const void* Xs, int64_t m, void* work, size_t work_bytes,
-                     void* mean, void* stream) {
-  DGP_CHECK_PLAN(p);
-  if (!theta || !Xs || !work || !mean || m <= 0) return fail(DGP_E_ARG, "dgp_predict_mean: null argument");
-  if (!p->have_factor) return fail(DGP_E_STATE, "dgp_predict_mean: no factorisation in the plan");
-  if (work_bytes < dgp_mean_vjp_workspace_bytes(p, m)) return fail(DGP_E_WORKSPACE, "dgp_predict_mean: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  const int rc = DGP_BY_DTYPE(p, predict_mean<double>(p, theta, Xs, m, work, mean, s), predict_mean<float>(p, theta, Xs, m, work, mean, s));
-  return wrap(rc, "dgp_predict_mean");
-}
-
-int dgp_mean_vjp(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const void* wts, void* work,
-                 size_t work_bytes, void* dtheta, void* dr, void* dnoise, void* stream) {
-  DGP_CHECK_PLAN(p);
-  if (!theta || !Xs || !wts || !work || !dtheta || m <= 0) return fail(DGP_E_ARG, "dgp_mean_vjp: null argument");
-  if (!p->have_factor || !p->have_inverse)
-    return fail(DGP_E_STATE, "dgp_mean_vjp: needs K^^-1 and alpha from dgp_fit_step at the same theta");
-  if (work_bytes < dgp_mean_vjp_workspace_bytes(p, m)) return fail(DGP_E_WORKSPACE, "dgp_mean_vjp: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  return wrap(DGP_BY_DTYPE(p, mean_vjp<double>(p, theta, Xs, m, wts, work, dtheta, dr, dnoise, s),
-                           mean_vjp<float>(p, theta, Xs, m, wts, work, dtheta, dr, dnoise, s)), "dgp_mean_vjp");
-}
-
-int dgp_sample_draws(int dtype, const void* L, int64_t m, const void* Z, int64_t ndraw, const void* mean, void* out,
-                     void* stream) {
-  if (dtype != DGP_F64 && dtype != DGP_F32) return fail(DGP_E_ARG, "dgp_sample_draws: dtype must be 0 (f64) or 1 (f32)");
-  if (!L || !Z || !out || m <= 0 || ndraw <= 0 || m > (1 << 20) || ndraw > (1 << 24))
-    return fail(DGP_E_ARG, "dgp_sample_draws: null argument / bad size");
-  const long M = round_up(m, DGP_TILE_HOST), Q = round_up(ndraw, DGP_TILE_HOST);
-  hipStream_t s = (hipStream_t)stream;
-  const int rc = dtype == DGP_F64
-                     ? sample_draws<double>((const double*)L, M, (const double*)Z, Q, (const double*)mean, (int)m, (int)ndraw, (double*)out, s)
-                     : sample_draws<float>((const float*)L, M, (const float*)Z, Q, (const float*)mean, (int)m, (int)ndraw, (float*)out, s);
-  return wrap(rc, "dgp_sample_draws");
-}
-
-size_t dgp_period_moments_workspace_bytes(int64_t m, int ngroups, int batch) {
-  if (m <= 0 || m > (1 << 20) || ngroups <= 0 || ngroups > 65535 || batch <= 0 || batch > DGP_MAX_BATCH_SITES) return 0;
-  return period_moments_workspace_bytes(m, ngroups, batch);
-}
-
-int dgp_period_moments(int dtype, int mode, const void* cov, int64_t m, int batch, const void* mu, const double* scale2,
-                       const double* w, const int32_t* group, int ngroups, const void* extra_var, void* work,
-                       size_t work_bytes, double* mean_out, double* cov_out, void* stream) {
-  if (dtype != DGP_F64 && dtype != DGP_F32) return fail(DGP_E_ARG, "dgp_period_moments: dtype must be 0 (f64) or 1 (f32)");
-  if (mode != 0 && mode != 1) return fail(DGP_E_ARG, "dgp_period_moments: mode must be 0 (linear) or 1 (log)");
-  if (!cov || !mu || !scale2 || !w || !group || !mean_out || !cov_out)
-    return fail(DGP_E_ARG, "dgp_period_moments: null argument");
-  if (m <= 0 || m > (1 << 20) || ngroups <= 0 || ngroups > 65535 || batch <= 0 || batch > DGP_MAX_BATCH_SITES)
-    return fail(DGP_E_ARG, "dgp_period_moments: bad size (1 <= m <= 2^20, 1 <= ngroups <= 65535, 1 <= batch <= 1024)");
-  if (!work || work_bytes < period_moments_workspace_bytes(m, ngroups, batch))
-    return fail(DGP_E_WORKSPACE, "dgp_period_moments: workspace missing or too small");
-  hipStream_t s = (hipStream_t)stream;
-  const int rc = dtype == DGP_F64
-                     ? period_moments<double>(mode, (const double*)cov, m, batch, (const double*)mu, scale2, w, group, ngroups,
-                                              (const double*)extra_var, (double*)work, mean_out, cov_out, s)
-                     : period_moments<float>(mode, (const float*)cov, m, batch, (const float*)mu, scale2, w, group, ngroups,
-                                             (const float*)extra_var, (double*)work, mean_out, cov_out, s);
-  return wrap(rc, "dgp_period_moments");
-}
-
-size_t dgp_posterior_period_moments_workspace_bytes(const dgp_plan* p, int64_t m, int ngroups) {
-  if (!p || m <= 0 || m > (1 << 20) || ngroups <= 0 || ngroups > 65535) return 0;
-  return predict_site_bytes(p, m) * (size_t)p->B + period_moments_workspace_bytes(m, ngroups, p->B);
-}
-
-int dgp_posterior_period_moments(dgp_plan* p, const double* theta, const void* Xs, int64_t m, int mode, const void* mu,
-                                 const double* scale2, const double* w, const int32_t* group, int ngroups, const void* extra_var,
-                                 void* work, size_t work_bytes, double* mean_out, double* cov_out, void* stream) {
-  if (!p) return fail(DGP_E_ARG, "null plan");
-  if (mode != 0 && mode != 1) return fail(DGP_E_ARG, "dgp_posterior_period_moments: mode must be 0 (linear) or 1 (log)");
-  if (!theta || !Xs || !mu || !scale2 || !w || !group || !mean_out || !cov_out)
-    return fail(DGP_E_ARG, "dgp_posterior_period_moments: null argument");
-  if (m <= 0 || m > (1 << 20) || ngroups <= 0 || ngroups > 65535)
-    return fail(DGP_E_ARG, "dgp_posterior_period_moments: bad size (1 <= m <= 2^20, 1 <= ngroups <= 65535)");
-  if (!p->have_factor) return fail(DGP_E_STATE, "dgp_posterior_period_moments: no factorisation in the plan (call dgp_factorize)");
-  DGP_CHECK_PLAN(p);
-  if (!work || work_bytes < dgp_posterior_period_moments_workspace_bytes(p, m, ngroups))
-    return fail(DGP_E_WORKSPACE, "dgp_posterior_period_moments: workspace missing or too small");
-  hipStream_t s = (hipStream_t)stream;
-  const int rc = DGP_BY_DTYPE(p, post_period<double>(p, theta, Xs, m, mode, mu, scale2, w, group, ngroups, extra_var, work, mean_out, cov_out, s),
-                              post_period<float>(p, theta, Xs, m, mode, mu, scale2, w, group, ngroups, extra_var, work, mean_out, cov_out, s));
-  return wrap(rc, "dgp_posterior_period_moments");
-}
-
-static bool wm_sizes_ok(int64_t m, int64_t q, int batch) {
-  return m > 0 && m <= (1 << 20) && q > 0 && q <= (1 << 20) && batch > 0 && batch <= DGP_MAX_BATCH_SITES;
-}
-size_t dgp_window_moments_workspace_bytes(int64_t m, int64_t q, int batch) {
-  if (!wm_sizes_ok(m, q, batch)) return 0;
-  return window_moments_workspace_bytes(m, q, batch);
-}
-
-int dgp_window_moments(int dtype, int mode, const void* cov, int64_t m, int batch, const void* mu, const double* scale2,
-                       const double* a, const int32_t* lo, const int32_t* hi, int64_t q, void* work, size_t work_bytes,
-                       double* mean_out, double* cov_out, void* stream) {
-  if (dtype != DGP_F64 && dtype != DGP_F32) return fail(DGP_E_ARG, "dgp_window_moments: dtype must be 0 (f64) or 1 (f32)");
-  if (mode != 0 && mode != 1) return fail(DGP_E_ARG, "dgp_window_moments: mode must be 0 (linear) or 1 (log)");
-  if (!cov || !mu || !lo || !hi || !mean_out || !cov_out || (mode == 1 && !scale2))
-    return fail(DGP_E_ARG, "dgp_window_moments: null argument");
-  if (!wm_sizes_ok(m, q, batch))
-    return fail(DGP_E_ARG, "dgp_window_moments: bad size (1 <= m <= 2^20, 1 <= q <= 2^20, 1 <= batch <= 1024)");
-  if (!work || work_bytes < window_moments_workspace_bytes(m, q, batch))
-    return fail(DGP_E_WORKSPACE, "dgp_window_moments: workspace missing or too small");
-  if (((uintptr_t)work & 7) != 0) return fail(DGP_E_ARG, "dgp_window_moments: the work area must be 8-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  const int rc = dtype == DGP_F64 ? window_moments<double>(mode, (const double*)cov, m, batch, (const double*)mu, scale2, a, lo, hi, q,
-                                                           (double*)work, mean_out, cov_out, s)
-                                  : window_moments<float>(mode, (const float*)cov, m, batch, (const float*)mu, scale2, a, lo, hi, q,
-                                                          (double*)work, mean_out, cov_out, s);
-  return wrap(rc, "dgp_window_moments");
-}
-
-static bool ex_sizes_ok(int64_t m, int ngroups, int nlevels, int batch) {
-  return m > 0 && m <= (1 << 20) && ngroups > 0 && ngroups <= 65535 && nlevels >= 1 && nlevels <= 64 && batch > 0 &&
-         batch <= DGP_MAX_BATCH_SITES;
-}
-size_t dgp_exceedance_moments_workspace_bytes(int64_t m, int ngroups, int nlevels, int batch) {
-  if (!ex_sizes_ok(m, ngroups, nlevels, batch)) return 0;
-  return exceedance_moments_workspace_bytes(m, ngroups, nlevels, batch);
-}
-
-int dgp_exceedance_moments(int dtype, const void* cov, int64_t m, int batch, const void* mu, const double* thresh, int nlevels,
-                           const double* w, const int32_t* group, int ngroups, const void* extra_var, void* work,
-                           size_t work_bytes, double* mean_out, double* cov_out, void* stream) {
-  if (dtype != DGP_F64 && dtype != DGP_F32) return fail(DGP_E_ARG, "dgp_exceedance_moments: dtype must be 0 (f64) or 1 (f32)");
-  if (!cov || !mu || !thresh || !w || !group || !mean_out || !cov_out)
-    return fail(DGP_E_ARG, "dgp_exceedance_moments: null argument");
-  if (!ex_sizes_ok(m, ngroups, nlevels, batch))
-    return fail(DGP_E_ARG,
-                "dgp_exceedance_moments: bad size (1 <= m <= 2^20, 1 <= ngroups <= 65535, 1 <= nlevels <= 64, 1 <= batch <= 1024)");
-  if (!work || work_bytes < exceedance_moments_workspace_bytes(m, ngroups, nlevels, batch))
-    return fail(DGP_E_WORKSPACE, "dgp_exceedance_moments: workspace missing or too small");
-  hipStream_t s = (hipStream_t)stream;
-  const int rc = dtype == DGP_F64
-                     ? exceedance_moments<double>((const double*)cov, m, batch, (const double*)mu, thresh, nlevels, w, group, ngroups,
-                                                  (const double*)extra_var, (double*)work, mean_out, cov_out, s)
-                     : exceedance_moments<float>((const float*)cov, m, batch, (const float*)mu, thresh, nlevels, w, group, ngroups,
-                                                 (const float*)extra_var, (double*)work, mean_out, cov_out, s);
-  return wrap(rc, "dgp_exceedance_moments");
-}
-
-size_t dgp_posterior_exceedance_moments_workspace_bytes(const dgp_plan* p, int64_t m, int ngroups, int nlevels, int panel_rows) {
-  if (!p || !ex_sizes_ok(m, ngroups, nlevels, p->B) || panel_rows <= 0 || panel_rows % DGP_TILE_HOST != 0) return 0;
-  return (predict_site_bytes(p, m) + exceed_panel_bytes(p, m, panel_rows)) * (size_t)p->B +
-         exceedance_moments_workspace_bytes(m, ngroups, nlevels, p->B);
-}
-
-int dgp_posterior_exceedance_moments(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const void* mu, const double* thresh,
-                                     int nlevels, const double* w, const int32_t* group, int ngroups, const void* extra_var,
-                                     int panel_rows, void* work, size_t work_bytes, double* mean_out, double* cov_out, void* stream) {
-  if (!p) return fail(DGP_E_ARG, "null plan");
-  if (!theta || !Xs || !mu || !thresh || !w || !group || !mean_out || !cov_out)
-    return fail(DGP_E_ARG, "dgp_posterior_exceedance_moments: null argument");
-  if (!ex_sizes_ok(m, ngroups, nlevels, p->B))
-    return fail(DGP_E_ARG, "dgp_posterior_exceedance_moments: bad size (1 <= m <= 2^20, 1 <= ngroups <= 65535, 1 <= nlevels <= 64)");
-  if (panel_rows <= 0 || panel_rows % DGP_TILE_HOST != 0)
-    return fail(DGP_E_ARG, "dgp_posterior_exceedance_moments: panel_rows must be a positive multiple of 128");
-  if (!p->have_factor)
-    return fail(DGP_E_STATE, "dgp_posterior_exceedance_moments: no factorisation in the plan (call dgp_factorize or dgp_fit_step)");
-  DGP_CHECK_PLAN(p);
-  if (!work || work_bytes < dgp_posterior_exceedance_moments_workspace_bytes(p, m, ngroups, nlevels, panel_rows))
-    return fail(DGP_E_WORKSPACE, "dgp_posterior_exceedance_moments: workspace missing or too small");
-  if (((uintptr_t)work & 255) != 0) return fail(DGP_E_ARG, "dgp_posterior_exceedance_moments: the work area must be 256-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  {  // a failed factorisation leaves no T to read: the sites' status words, before any launch
-    std::vector<int> info((size_t)p->B, 0);
-    hipError_t e = hipMemcpy2DAsync(info.data(), sizeof(int), p->info, p->site_bytes, sizeof(int), (size_t)p->B, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hipfail(e, "dgp_posterior_exceedance_moments");
-    for (int b = 0; b < p->B; ++b)
-      if (info[(size_t)b] != 0)
-        return fail(DGP_E_STATE, "dgp_posterior_exceedance_moments: the factorisation the plan holds failed (matrix not positive definite)");
-  }
-  const int rc = DGP_BY_DTYPE(p, post_exceed<double>(p, theta, Xs, m, mu, thresh, nlevels, w, group, ngroups, extra_var, panel_rows, work, mean_out, cov_out, s),
-                              post_exceed<float>(p, theta, Xs, m, mu, thresh, nlevels, w, group, ngroups, extra_var, panel_rows, work, mean_out, cov_out, s));
-  return wrap(rc, "dgp_posterior_exceedance_moments");
-}
-
-static bool sv_sizes_ok(int64_t m, int ngroups, int nrows, int nterms, int batch) {
-  return m > 0 && m <= (1 << 20) && ngroups > 0 && ngroups <= 65535 && nrows >= 0 && nrows <= 64 && nterms >= 1 && nterms <= 64 &&
-         batch > 0 && batch <= DGP_MAX_BATCH_SITES;
-}
-size_t dgp_sample_value_workspace_bytes(int64_t m, int ngroups, int nrows, int nterms, int batch) {
-  if (!sv_sizes_ok(m, ngroups, nrows, nterms, batch)) return 0;
-  return sample_value_workspace_bytes(m, ngroups, nterms, batch);
-}
-
-int dgp_sample_value(int dtype, const void* cov, int64_t m, int batch, const double* a, const double* scale2, const int32_t* group,
-                     int ngroups, const void* obs_var, const double* rows, int nrows, int nterms, void* work, size_t work_bytes,
-                     double* gain_out, double* var_out, void* stream) {
-  if (dtype != DGP_F64 && dtype != DGP_F32) return fail(DGP_E_ARG, "dgp_sample_value: dtype must be 0 (f64) or 1 (f32)");
-  if (!cov || !a || !scale2 || !group || !gain_out || !var_out) return fail(DGP_E_ARG, "dgp_sample_value: null argument");
-  if (!sv_sizes_ok(m, ngroups, nrows, nterms, batch))
-    return fail(DGP_E_ARG,
-                "dgp_sample_value: bad size (1 <= m <= 2^20, 1 <= ngroups <= 65535, 0 <= nrows <= 64, 1 <= nterms <= 64, "
-                "1 <= batch <= 1024)");
-  if (nrows > 0 && !rows) return fail(DGP_E_ARG, "dgp_sample_value: null argument (rows with nrows > 0)");
-  if (!work || work_bytes < sample_value_workspace_bytes(m, ngroups, nterms, batch))
-    return fail(DGP_E_WORKSPACE, "dgp_sample_value: workspace missing or too small");
-  hipStream_t s = (hipStream_t)stream;
-  const int rc = dtype == DGP_F64 ? sample_value<double>((const double*)cov, m, batch, a, scale2, group, ngroups, (const double*)obs_var,
-                                                         rows, nrows, nterms, (double*)work, gain_out, var_out, s)
-                                  : sample_value<float>((const float*)cov, m, batch, a, scale2, group, ngroups, (const float*)obs_var,
-                                                        rows, nrows, nterms, (double*)work, gain_out, var_out, s);
-  return wrap(rc, "dgp_sample_value");
-}
-
-int dgp_debug_bvn_excess(const double* h, const double* k, const double* rho, int64_t count, double* out, void* stream) {
-  if (!h || !k || !rho || !out || count <= 0 || count > (1ll << 31))
-    return fail(DGP_E_ARG, "dgp_debug_bvn_excess: null argument / bad count");
-  return wrap(debug_bvn_excess(h, k, rho, count, out, (hipStream_t)stream), "dgp_debug_bvn_excess");
-}
-
-static bool cv_sizes_ok(const dgp_plan* p, int ngroups, int64_t max_group) {
-  return p && ngroups >= 1 && ngroups <= p->n && max_group >= 1 && max_group <= p->n;
-}
-size_t dgp_cross_validate_workspace_bytes(const dgp_plan* p, int ngroups, int64_t max_group) {
-  if (!cv_sizes_ok(p, ngroups, max_group)) return 0;
-  return cross_validate_workspace_bytes(p->N, p->B, ngroups, max_group);
-}
-
-int dgp_cross_validate(dgp_plan* p, const int32_t* order, const int32_t* start, int ngroups, int64_t max_group, void* work,
-                       size_t work_bytes, double* resid, double* var, double* lpd, int32_t* info, void* stream) {
-  if (!p) return fail(DGP_E_ARG, "null plan");
-  if (!order || !start || !resid || !var || !lpd || !info) return fail(DGP_E_ARG, "dgp_cross_validate: null argument");
-  if (!cv_sizes_ok(p, ngroups, max_group))
-    return fail(DGP_E_ARG, "dgp_cross_validate: bad size (1 <= ngroups <= n, 1 <= max_group <= n)");
-  DGP_CHECK_PLAN(p);
-  if (!p->have_factor) return fail(DGP_E_STATE, "dgp_cross_validate: no factorisation in the plan (call dgp_factorize or dgp_fit_step)");
-  if (!work || work_bytes < dgp_cross_validate_workspace_bytes(p, ngroups, max_group))
-    return fail(DGP_E_WORKSPACE, "dgp_cross_validate: workspace missing or too small");
-  if (((uintptr_t)work & 255) != 0) return fail(DGP_E_ARG, "dgp_cross_validate: the work area must be 256-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  // K^^-1 (S) is read when the last step left it valid and never written; after a bare dgp_factorize it is dead and ignored
-  const void* S = p->have_inverse ? p->S : nullptr;
-  const int rc = DGP_BY_DTYPE(
-      p,
-      cross_validate<double>((const double*)p->Tm, (const double*)S, (const double*)p->alpha, p->N, (int)p->n, order, start, ngroups,
-                             max_group, work, resid, var, lpd, info, s, batch_of<double>(p)),
-      cross_validate<float>((const float*)p->Tm, (const float*)S, (const float*)p->alpha, p->N, (int)p->n, order, start, ngroups, max_group,
-                            work, resid, var, lpd, info, s, batch_of<float>(p)));
-  return wrap(rc, "dgp_cross_validate");
-}
-
-static bool lcv_plan_ok(const dgp_plan* p) { return p && p->dtype == DGP_F64 && p->B == 1; }
-size_t dgp_laplace_cross_validate_workspace_bytes(const dgp_plan* p, int ngroups, int64_t max_group) {
-  if (!lcv_plan_ok(p) || !cv_sizes_ok(p, ngroups, max_group)) return 0;
-  return laplace_cv_layout(p->N, p->n, ngroups, max_group).total;
-}
-
-int dgp_laplace_cross_validate(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise, const int32_t* side,
-                               const void* upper, const void* f, const int32_t* order, const int32_t* start, int ngroups,
-                               int64_t max_group, double shift, void* work, size_t work_bytes, double* out, int32_t* info, void* stream) {
-  const char* where = "dgp_laplace_cross_validate";
-  if (!p) return fail(DGP_E_ARG, "null plan");
-  if (!lcv_plan_ok(p))
-    return fail(DGP_E_ARG, "dgp_laplace_cross_validate: needs a float64 single-site plan (fp32 and batched plans are not supported)");
-  if (!theta || !y || !mean || !noise || !side || !f || !order || !start || !out || !info || !(shift == shift))
-    return fail(DGP_E_ARG, "dgp_laplace_cross_validate: null argument (f_dev included) or a NaN shift");
-  if (!cv_sizes_ok(p, ngroups, max_group))
-    return fail(DGP_E_ARG, "dgp_laplace_cross_validate: bad size (1 <= ngroups <= n, 1 <= max_group <= n)");
-  DGP_CHECK_PLAN(p);
-  if (!p->have_factor)
-    return fail(DGP_E_STATE, "dgp_laplace_cross_validate: no factorisation in the plan (call dgp_laplace_factorize or dgp_laplace_fit_step)");
-  if (!work || work_bytes < dgp_laplace_cross_validate_workspace_bytes(p, ngroups, max_group))
-    return fail(DGP_E_WORKSPACE, "dgp_laplace_cross_validate: workspace missing or too small");
-  if (((uintptr_t)work & 255) != 0) return fail(DGP_E_ARG, "dgp_laplace_cross_validate: the work area must be 256-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  const LaplaceCvLayout L = laplace_cv_layout(p->N, p->n, ngroups, max_group);
-  // the terms pass and its read-back first: the staging slot below is not held across the synchronisation
-  int rc = laplace_cv_terms(p->N, (int)p->n, (const double*)y, (const double*)mean, (const double*)noise, side, (const double*)upper,
-                            (const double*)f, (char*)work, L, s);
-  if (rc == 0) {
-    PreSlot slot(p, s);
-    rc = laplace_cross_validate(p->model, p->d, (const double*)p->Xt, (const double*)p->Tm, (const double*)p->alpha, p->N, (int)p->n, theta,
-                                (const double*)y, (const double*)noise, side, (const double*)upper, (const double*)f, order, start,
-                                ngroups, shift, (char*)work, L, out, info, s, batch_of<double>(p), p->pre, slot.staging);
-  }
-  if (rc == LCV_E_SIDE_NO_UPPER)
-    return fail(DGP_E_ARG, "dgp_laplace_cross_validate: a row of side 2 needs upper_dev; other side values must be -1, 0 or +1");
-  if (rc == LCV_E_SIDE) return fail(DGP_E_ARG, "dgp_laplace_cross_validate: side values must be -1, 0, +1 or 2");
-  if (rc == LCV_E_BRACKET)
-    return fail(DGP_E_ARG, "dgp_laplace_cross_validate: bad bracket(s): a row of side 2 needs a finite upper above its y");
-  return wrap(rc, where);
-}
-
-#define DGP_FISHER_MAX_DIAG 8
-size_t dgp_fisher_workspace_bytes(const dgp_plan* p, int ndiag) {
-  if (!p || ndiag < 0 || ndiag > DGP_FISHER_MAX_DIAG) return 0;
-  return fisher_site_bytes(p->N, p->ntheta + ndiag, p->elem) * (size_t)p->B;
-}
-
-int dgp_fisher(dgp_plan* p, const double* theta, const void* diag, int ndiag, void* work, size_t work_bytes, double* fisher_out,
-               void* stream) {
-  if (!p) return fail(DGP_E_ARG, "null plan");
-  if (!theta || !fisher_out) return fail(DGP_E_ARG, "dgp_fisher: null argument");
-  if (ndiag < 0 || ndiag > DGP_FISHER_MAX_DIAG) return fail(DGP_E_ARG, "dgp_fisher: ndiag must be 0..8");
-  if (ndiag > 0 && !diag) return fail(DGP_E_ARG, "dgp_fisher: ndiag > 0 needs the diagonal directions");
-  DGP_CHECK_PLAN(p);
-  if (!p->have_factor) return fail(DGP_E_STATE, "dgp_fisher: no factorisation in the plan (call dgp_factorize or dgp_fit_step)");
-  if (!work || work_bytes < dgp_fisher_workspace_bytes(p, ndiag)) return fail(DGP_E_WORKSPACE, "dgp_fisher: workspace missing or too small");
-  if (((uintptr_t)work & 255) != 0) return fail(DGP_E_ARG, "dgp_fisher: the work area must be 256-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  {  // a failed factorisation leaves no T to read: the sites' status words, before any launch
-    std::vector<int> info((size_t)p->B, 0);
-    hipError_t e = hipMemcpy2DAsync(info.data(), sizeof(int), p->info, p->site_bytes, sizeof(int), (size_t)p->B, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hipfail(e, "dgp_fisher");
-    for (int b = 0; b < p->B; ++b)
-      if (info[(size_t)b] != 0) return fail(DGP_E_STATE, "dgp_fisher: the factorisation the plan holds failed (matrix not positive definite)");
-  }
-  PreSlot slot(p, s);
-  const int rc = DGP_BY_DTYPE(
-      p,
-      fisher<double>(p->model, p->d, (const double*)p->Xt, (const double*)p->Tm, p->N, (int)p->n, theta, (const double*)diag, ndiag, work,
-                     fisher_out, s, batch_of<double>(p), p->pre, slot.staging),
-      fisher<float>(p->model, p->d, (const float*)p->Xt, (const float*)p->Tm, p->N, (int)p->n, theta, (const float*)diag, ndiag, work,
-                    fisher_out, s, batch_of<float>(p), p->pre, slot.staging));
-  return wrap(rc, "dgp_fisher");
-}
-
-}  // extern "C"
-
-#define DGP_SENS_MAX_COLS 8
-static bool sens_sizes_ok(const dgp_plan* p, int64_t m, int ndiag, int nrhs) {
-  return p && m > 0 && m <= 0x7fffffffLL - DGP_TILE_HOST && ndiag >= 0 && ndiag <= DGP_SENS_MAX_COLS && nrhs >= 0 && nrhs <= DGP_SENS_MAX_COLS;
-}
-template <typename T>
-static int sensitivity(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const void* diag, int ndiag, const void* rhs, int nrhs,
-                       void* work, double* dmean, double* dvar, hipStream_t s) {
-  const long M = round_up(m, DGP_TILE_HOST);
-  const SensLayout L = sens_layout(p->N, M, p->d, p->ntheta, ndiag, nrhs, p->elem);
-  char* w = (char*)work;
-  const int rc = cross<T>(p, theta, Xs, m, w + L.Xst, w + L.Ks, s, (long)(L.total / sizeof(T)));
-  if (rc) return rc;
-  return predict_sensitivity<T>(p->model, p->d, (const T*)p->Xt, (const T*)p->Tm, (const T*)p->alpha, p->N, (int)p->n, theta, M, (int)m,
-                                (const T*)diag, ndiag, (const T*)rhs, nrhs, work, L, dmean, dvar, s, batch_of<T>(p), p->pre);
-}
-
-extern "C" {
-
-size_t dgp_predict_sensitivity_workspace_bytes(const dgp_plan* p, int64_t m, int ndiag, int nrhs) {
-  if (!sens_sizes_ok(p, m, ndiag, nrhs)) return 0;
-  return sens_layout(p->N, round_up(m, DGP_TILE_HOST), p->d, p->ntheta, ndiag, nrhs, p->elem).total * (size_t)p->B;
-}
-
-int dgp_predict_sensitivity(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const void* diag, int ndiag, const void* rhs,
-                            int nrhs, void* work, size_t work_bytes, double* dmean, double* dvar, void* stream) {
-  if (!p) return fail(DGP_E_ARG, "null plan");
-  if (!theta || !Xs || !dmean) return fail(DGP_E_ARG, "dgp_predict_sensitivity: null argument");
-  if (m <= 0 || m > 0x7fffffffLL - DGP_TILE_HOST) return fail(DGP_E_ARG, "dgp_predict_sensitivity: m must be positive");
-  if (ndiag < 0 || ndiag > DGP_SENS_MAX_COLS) return fail(DGP_E_ARG, "dgp_predict_sensitivity: ndiag must be 0..8");
-  if (nrhs < 0 || nrhs > DGP_SENS_MAX_COLS) return fail(DGP_E_ARG, "dgp_predict_sensitivity: nrhs must be 0..8");
-  if (ndiag > 0 && !diag) return fail(DGP_E_ARG, "dgp_predict_sensitivity: ndiag > 0 needs the diagonal directions");
-  if (nrhs > 0 && !rhs) return fail(DGP_E_ARG, "dgp_predict_sensitivity: nrhs > 0 needs the right-hand-side columns");
-  DGP_CHECK_PLAN(p);
-  if (!p->have_factor)
-    return fail(DGP_E_STATE, "dgp_predict_sensitivity: no factorisation in the plan (call dgp_factorize or dgp_fit_step)");
-  if (!work || work_bytes < dgp_predict_sensitivity_workspace_bytes(p, m, ndiag, nrhs))
-    return fail(DGP_E_WORKSPACE, "dgp_predict_sensitivity: workspace missing or too small");
-  if (((uintptr_t)work & 255) != 0) return fail(DGP_E_ARG, "dgp_predict_sensitivity: the work area must be 256-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  {  // a failed factorisation leaves no T to read: the sites' status words, before any launch
-    std::vector<int> info((size_t)p->B, 0);
-    hipError_t e = hipMemcpy2DAsync(info.data(), sizeof(int), p->info, p->site_bytes, sizeof(int), (size_t)p->B, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hipfail(e, "dgp_predict_sensitivity");
-    for (int b = 0; b < p->B; ++b)
-      if (info[(size_t)b] != 0)
-        return fail(DGP_E_STATE, "dgp_predict_sensitivity: the factorisation the plan holds failed (matrix not positive definite)");
-  }
-  const int rc = DGP_BY_DTYPE(p, sensitivity<double>(p, theta, Xs, m, diag, ndiag, rhs, nrhs, work, dmean, dvar, s),
-                              sensitivity<float>(p, theta, Xs, m, diag, ndiag, rhs, nrhs, work, dmean, dvar, s));
-  return wrap(rc, "dgp_predict_sensitivity");
-}
-
-}  // extern "C"
-
-static bool influence_sizes_ok(const dgp_plan* p, int64_t m, int nfolds, int64_t max_fold, int ngroups) {
-  return p && m >= 1 && m <= (1 << 20) && nfolds >= 1 && nfolds <= p->n && max_fold >= 1 && max_fold <= p->n && ngroups >= 1 &&
-         ngroups <= 65535;
-}
-static InfluenceLayout influence_layout_of(const dgp_plan* p, int64_t m, int nfolds, int64_t max_fold, int ngroups) {
-  return influence_layout(p->N, p->B, (int)p->n, p->d, round_up(m, DGP_TILE_HOST), (int)m, nfolds, max_fold, ngroups, p->elem);
-}
-template <typename T>
-static int influence(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const int32_t* order, const int32_t* start, int nfolds,
-                     int64_t max_fold, int mode, const double* a, const double* scale, const int32_t* group, int ngroups,
-                     const double* inv_sd, void* work, double* dload, double* dvar, double* shift, int32_t* info, hipStream_t s) {
-  const InfluenceLayout L = influence_layout_of(p, m, nfolds, max_fold, ngroups);
-  char* w = (char*)work;
-  const int rc = cross<T>(p, theta, Xs, m, w + L.Xst, w + L.Ks, s, (long)(L.slice / sizeof(T)));
-  if (rc) return rc;
-  const void* S = p->have_inverse ? p->S : nullptr;  // as dgp_cross_validate: read when the last step left it valid
-  return deletion_influence<T>((const T*)p->Tm, (const T*)S, (const T*)p->alpha, p->N, (int)p->n, round_up(m, DGP_TILE_HOST), (int)m, order,
-                               start, nfolds, max_fold, mode, a, scale, group, ngroups, inv_sd, work, L, dload, dvar, shift, info, s,
-                               batch_of<T>(p));
-}
-
-extern "C" {
-
-size_t dgp_deletion_influence_workspace_bytes(const dgp_plan* p, int64_t m, int nfolds, int64_t max_fold, int ngroups) {
-  if (!influence_sizes_ok(p, m, nfolds, max_fold, ngroups)) return 0;
-  return influence_layout_of(p, m, nfolds, max_fold, ngroups).total;
-}
-
-int dgp_deletion_influence(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const int32_t* order, const int32_t* start,
-                           int nfolds, int64_t max_fold, int mode, const double* a, const double* scale, const int32_t* group, int ngroups,
-                           const double* inv_sd, void* work, size_t work_bytes, double* dload, double* dvar, double* shift,
-                           int32_t* info, void* stream) {
-  if (!p) return fail(DGP_E_ARG, "null plan");
-  if (!theta || !Xs || !order || !start || !a || !scale || !group || !dload || !info)
-    return fail(DGP_E_ARG, "dgp_deletion_influence: null argument");
-  if (!influence_sizes_ok(p, m, nfolds, max_fold, ngroups))
-    return fail(DGP_E_ARG, "dgp_deletion_influence: bad size (1 <= m <= 2^20, 1 <= nfolds <= n, 1 <= max_fold <= n, 1 <= ngroups <= 65535)");
-  if (mode != 0 && mode != 1) return fail(DGP_E_ARG, "dgp_deletion_influence: mode must be 0 (linear) or 1 (log)");
-  if (mode == 1 && dvar) return fail(DGP_E_ARG, "dgp_deletion_influence: the variance change is exact for mode 0 only (dvar_dev must be NULL)");
-  if (shift && !inv_sd) return fail(DGP_E_ARG, "dgp_deletion_influence: shift_dev needs inv_sd_dev");
-  DGP_CHECK_PLAN(p);
-  if (!p->have_factor) return fail(DGP_E_STATE, "dgp_deletion_influence: no factorisation in the plan (call dgp_factorize or dgp_fit_step)");
-  if (!work || work_bytes < dgp_deletion_influence_workspace_bytes(p, m, nfolds, max_fold, ngroups))
-    return fail(DGP_E_WORKSPACE, "dgp_deletion_influence: workspace missing or too small");
-  if (((uintptr_t)work & 255) != 0) return fail(DGP_E_ARG, "dgp_deletion_influence: the work area must be 256-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  {  // a failed factorisation leaves no T to read: the sites' status words, before any launch
-    std::vector<int> st((size_t)p->B, 0);
-    hipError_t e = hipMemcpy2DAsync(st.data(), sizeof(int), p->info, p->site_bytes, sizeof(int), (size_t)p->B, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hipfail(e, "dgp_deletion_influence");
-    for (int b = 0; b < p->B; ++b)
-      if (st[(size_t)b] != 0)
-        return fail(DGP_E_STATE, "dgp_deletion_influence: the factorisation the plan holds failed (matrix not positive definite)");
-  }
-  const int rc = DGP_BY_DTYPE(p,
-                              influence<double>(p, theta, Xs, m, order, start, nfolds, max_fold, mode, a, scale, group, ngroups, inv_sd, work,
-                                                dload, dvar, shift, info, s),
-                              influence<float>(p, theta, Xs, m, order, start, nfolds, max_fold, mode, a, scale, group, ngroups, inv_sd, work,
-                                               dload, dvar, shift, info, s));
-  return wrap(rc, "dgp_deletion_influence");
 }
 
 int dgp_plan_set_timing(dgp_plan* p, int enabled) {
@@ -2201,57 +920,6 @@ int dgp_debug_clock_probe(void* out_dev, int nwg, double seconds, void* stream) 
   if (rc) return rc;
   clock_probe_kernel<<<dim3((unsigned)nwg), 64, 0, st->early>>>((unsigned long long*)out_dev, (long long)(seconds * 1e8));
   return wrap((int)hipGetLastError(), "dgp_debug_clock_probe");
-}
-
-// ---- the leave-one-out predictive likelihood as a training objective (dgp_loo.hip): dgp_fit_step's launches, untouched, into a
-// scratch result row, then the passes that read the S and alpha it left.  The plan's A / T / S / z / alpha stay as the step left them.
-static LooLayout loo_layout_of(const dgp_plan* p, bool value_only) {
-  const Layout L = layout(p);
-  return loo_layout(p->N, p->B, value_only ? 0 : p->site_bytes, L.A, L.Tm, L.S, L.alpha, L.gpart);
-}
-static const char* const LOO_F64 =
-    "dgp_loo_*: the leave-one-out objective needs a float64 plan (its bilinear gradient pass exists for float64 only: fp32 plans are "
-    "not supported)";
-
-size_t dgp_loo_workspace_bytes(const dgp_plan* p) {
-  if (!p || p->dtype != DGP_F64) return 0;
-  return loo_layout_of(p, false).total;
-}
-size_t dgp_loo_value_workspace_bytes(const dgp_plan* p) {
-  if (!p || p->dtype != DGP_F64) return 0;
-  return loo_layout_of(p, true).total;
-}
-
-int dgp_loo_fit_step(dgp_plan* p, const double* theta, const void* r, const void* noise, void* work, size_t work_bytes, void* out,
-                     void* dr, void* dnoise, void* stream) {
-  if (!p) return fail(DGP_E_ARG, "null plan");
-  if (p->dtype != DGP_F64) return fail(DGP_E_ARG, LOO_F64);
-  DGP_CHECK_PLAN(p);
-  if (!theta || !r || !noise || !out) return fail(DGP_E_ARG, "dgp_loo_fit_step: null argument");
-  if (!p->have_inputs) return fail(DGP_E_STATE, "dgp_loo_fit_step: call dgp_set_inputs first");
-  if (!work || work_bytes < dgp_loo_workspace_bytes(p)) return fail(DGP_E_WORKSPACE, "dgp_loo_fit_step: workspace missing or too small");
-  if (((uintptr_t)work & 255) != 0) return fail(DGP_E_ARG, "dgp_loo_fit_step: the work area must be 256-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  const LooLayout L = loo_layout_of(p, false);
-  int rc = fit_step<double>(p, theta, r, noise, (char*)work + L.out0, dr, dnoise, 1, s);
-  if (rc) return wrap(rc, "dgp_loo_fit_step");
-  rc = loo_gradient(p->model, p->d, (const double*)p->Xt, (const double*)p->S, (const double*)p->alpha, p->N, (int)p->n, theta,
-                    (const double*)p->dr_w, (char*)work, L, (double*)out, (double*)dr, (double*)dnoise, s, batch_of<double>(p), p->pre);
-  return wrap(rc, "dgp_loo_fit_step");
-}
-
-int dgp_loo_value(dgp_plan* p, void* work, size_t work_bytes, void* out2, void* stream) {
-  if (!p) return fail(DGP_E_ARG, "null plan");
-  if (p->dtype != DGP_F64) return fail(DGP_E_ARG, LOO_F64);
-  DGP_CHECK_PLAN(p);
-  if (!out2) return fail(DGP_E_ARG, "dgp_loo_value: null argument");
-  if (!p->have_factor || !p->have_inverse)
-    return fail(DGP_E_STATE, "dgp_loo_value: needs the K^^-1 a fit step leaves in the plan (dgp_fit_step or dgp_loo_fit_step; dgp_factorize does not form it)");
-  if (!work || work_bytes < dgp_loo_value_workspace_bytes(p)) return fail(DGP_E_WORKSPACE, "dgp_loo_value: workspace missing or too small");
-  if (((uintptr_t)work & 255) != 0) return fail(DGP_E_ARG, "dgp_loo_value: the work area must be 256-byte aligned");
-  const int rc = loo_value((const double*)p->S, (const double*)p->alpha, p->info, p->N, (int)p->n, (char*)work, loo_layout_of(p, true),
-                           (double*)out2, (hipStream_t)stream, batch_of<double>(p));
-  return wrap(rc, "dgp_loo_value");
 }
 
 }  // extern "C"

@@ -24,9 +24,11 @@
 // A batch runs Newton's iterations in lockstep (each factorises all sites); a site that has finished is frozen (CEN_ST_DONE).
 // Roofline: the elementwise passes are O(n) and latency-bound; the sweep is VALU-bound like gram_grad (one derivative pair
 // evaluation per entry of the triangle, nothing streamed from HBM but the two vectors).
+#include <vector>
+
 #include "dgp_censored_fn.h"
 #include "dgp_gram_shared.h"
-#include "dgp_internal.h"
+#include "dgp_plan.h"
 #include "dgp_models.h"
 
 namespace dgp {
@@ -43,7 +45,7 @@ __global__ __launch_bounds__(256) void cen_debug_kernel(const double* __restrict
   out[3 * count + i] = o.c3;
 }
 
-int debug_censored_terms(const double* z, long count, double* out, hipStream_t s) {
+static int debug_censored_terms(const double* z, long count, double* out, hipStream_t s) {
   cen_debug_kernel<<<dim3((unsigned)((count + 255) / 256)), 256, 0, s>>>(z, count, out);
   return (int)hipGetLastError();
 }
@@ -59,7 +61,7 @@ __global__ __launch_bounds__(256) void iv_debug_kernel(const double* __restrict_
   out[3 * count + i] = o.d3;
 }
 
-int debug_interval_terms(const double* za, const double* delta, long count, double* out, hipStream_t s) {
+static int debug_interval_terms(const double* za, const double* delta, long count, double* out, hipStream_t s) {
   iv_debug_kernel<<<dim3((unsigned)((count + 255) / 256)), 256, 0, s>>>(za, delta, count, out);
   return (int)hipGetLastError();
 }
@@ -371,34 +373,33 @@ __global__ __launch_bounds__(256) void cen_result_finish_kernel(const double* __
 
 CensoredLayout censored_layout(long N, long n, int B) {
   CensoredLayout L;
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t vec = al(sizeof(double) * (size_t)B * (size_t)n);
-  size_t o = 0;
-  L.rt = o; o += vec;
-  L.nn = o; o += vec;
-  L.dnoise = o; o += vec;
-  L.g = o; o += vec;
-  L.W = o; o += vec;
-  L.d3 = o; o += vec;
-  L.corr = o; o += vec;
-  L.logp = o; o += vec;
-  L.delta = o; o += vec;
-  L.acur = o; o += vec;
+  const size_t vec = sizeof(double) * (size_t)B * (size_t)n;
+  Carve c;
+  L.rt = c.take(vec);
+  L.nn = c.take(vec);
+  L.dnoise = c.take(vec);
+  L.g = c.take(vec);
+  L.W = c.take(vec);
+  L.d3 = c.take(vec);
+  L.corr = c.take(vec);
+  L.logp = c.take(vec);
+  L.delta = c.take(vec);
+  L.acur = c.take(vec);
   L.nblk = (int)((n + 255) / 256);
-  L.part = o; o += al(sizeof(double) * (size_t)B * (size_t)L.nblk * CEN_PART);
-  L.status = o; o += al(sizeof(double) * (size_t)B * CEN_ST_LEN);
-  L.out = o; o += al(sizeof(double) * (size_t)B * 32);
-  L.slices = o;
-  const size_t nvec = al(sizeof(double) * (size_t)N);
-  size_t q = 0;
-  L.w = q; q += nvec;
-  L.u = q; q += nvec;
-  L.z = q; q += nvec;
-  L.spart = q; q += al(sizeof(double) * (size_t)solve_partials(N));
-  L.gpart = q; q += al(sizeof(double) * (size_t)gram_grad_partials(N));
-  L.quad = q; q += al(sizeof(double) * 8);
-  L.slice = q;
-  L.total = o + q * (size_t)B;
+  L.part = c.take(sizeof(double) * (size_t)B * (size_t)L.nblk * CEN_PART);
+  L.status = c.take(sizeof(double) * (size_t)B * CEN_ST_LEN);
+  L.out = c.take(sizeof(double) * (size_t)B * 32);
+  L.slices = c.o;
+  const size_t nvec = sizeof(double) * (size_t)N;
+  Carve q;  // inside a site's slice
+  L.w = q.take(nvec);
+  L.u = q.take(nvec);
+  L.z = q.take(nvec);
+  L.spart = q.take(sizeof(double) * (size_t)solve_partials(N));
+  L.gpart = q.take(sizeof(double) * (size_t)gram_grad_partials(N));
+  L.quad = q.take(sizeof(double) * 8);
+  L.slice = q.o;
+  L.total = c.o + q.o * (size_t)B;
   L.B = B;
   L.n = n;
   return L;
@@ -414,7 +415,7 @@ int censored_terms(const double* f, const double* y, const int* side, const doub
   return (int)hipGetLastError();
 }
 
-int censored_newton_update(double* f, const double* y, const int* side, const double* v, const double* m, const double* anew, int n,
+static int censored_newton_update(double* f, const double* y, const int* side, const double* v, const double* m, const double* anew, int n,
                            int it, double tol, char* work, const CensoredLayout& L, hipStream_t s, Batch bt, const double* upper) {
   auto D = [&](size_t off) { return (double*)(work + off); };
   const unsigned Bz = (unsigned)bt.B;
@@ -425,21 +426,21 @@ int censored_newton_update(double* f, const double* y, const int* side, const do
   return (int)hipGetLastError();
 }
 
-int censored_mode(double* f, const double* m, const double* alpha, int n, char* work, const CensoredLayout& L, hipStream_t s, Batch bt) {
+static int censored_mode(double* f, const double* m, const double* alpha, int n, char* work, const CensoredLayout& L, hipStream_t s, Batch bt) {
   cen_mode_kernel<<<dim3((unsigned)L.nblk, 1, (unsigned)bt.B), 256, 0, s>>>(f, m, (const double*)(work + L.rt),
                                                                             (const double*)(work + L.nn), alpha, bt.ws, n, bt.ns,
                                                                             (const double*)(work + L.status));
   return (int)hipGetLastError();
 }
 
-int censored_weights(const double* alpha, int n, long N, char* work, const CensoredLayout& L, hipStream_t s, Batch bt) {
+static int censored_weights(const double* alpha, int n, long N, char* work, const CensoredLayout& L, hipStream_t s, Batch bt) {
   auto D = [&](size_t off) { return (double*)(work + off); };
   cen_weight_kernel<<<dim3((unsigned)((N + 255) / 256), 1, (unsigned)bt.B), 256, 0, s>>>(
       D(L.nn), D(L.d3), D(L.dnoise), alpha, bt.ws, n, bt.ns, N, D(L.slices + L.w), (long)(L.slice / sizeof(double)));
   return (int)hipGetLastError();
 }
 
-int censored_result(const double* alpha, const int* side, const double* wts, int n, int with_grad, double* out, double* dr, char* work,
+static int censored_result(const double* alpha, const int* side, const double* wts, int n, int with_grad, double* out, double* dr, char* work,
                     const CensoredLayout& L, hipStream_t s, Batch bt) {
   auto D = [&](size_t off) { return (double*)(work + off); };
   const unsigned Bz = (unsigned)bt.B;
@@ -535,3 +536,227 @@ template int gram_bilinear<double>(int, int, const double*, long, int, const dou
                                    int, hipStream_t, Batch, long, long, long, long, void*, bool, void*);
 
 }  // namespace dgp
+
+using namespace dgp;
+
+// ---- the entries: Newton's mode search on the factorise path, then one step at the mode.
+// One code path for a single-site plan and for a batch: every Newton iteration factorises ALL sites in lockstep; a site is done when
+// it has no censored row, its proposal is within tol or its factorisation failed, and a done site is frozen on the device
+// (CEN_ST_DONE), so that it rides through the remaining factorisations on unchanged pseudo-data.  The host reads the B status
+// blocks in one copy per iteration.  stat: [B][4].  `batched`: the entry's texts name the site.
+// Returns 0, a HIP error (> 0), or DGP_E_ARG / DGP_E_NOCONV with the error text already set.
+static int laplace(dgp_plan* p, const double* theta, const double* y, const double* mean, const double* noise, const int* side,
+                   double* f, int maxit, double tol, char* work, double* out, double* dr, double* stat, int with_grad, int batched,
+                   const char* where, hipStream_t s, const double* upper = nullptr, int interval = 0) {
+  const int B = p->B;
+  const CensoredLayout L = censored_layout(p->N, p->n, B);
+  const Batch bt = batch_of<double>(p);
+  auto D = [&](size_t off) { return (double*)(work + off); };
+  const int n = (int)p->n;
+  const long wss = (long)(L.slice / sizeof(double));
+  const double* alpha = (const double*)p->alpha;
+  std::vector<double> st((size_t)B * CEN_ST_LEN);
+  auto S = [&](int b, int k) -> double { return st[(size_t)b * CEN_ST_LEN + k]; };
+  auto read_status = [&]() -> int {
+    hipError_t e = hipMemcpyAsync(st.data(), D(L.status), sizeof(double) * st.size(), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    return (int)e;
+  };
+  int rc;
+  for (int k = 0; k < 4 * B; ++k) stat[k] = 0.0;
+  if ((rc = censored_terms(f, y, side, noise, mean, n, 1, 0, work, L, s, bt, upper)) || (rc = read_status())) return rc;
+  bool any = false, any_plain = false;
+  for (int b = 0; b < B; ++b) {
+    if (interval && S(b, CEN_ST_BAD) != 0.0)
+      return failf(DGP_E_ARG,
+                   upper ? "%s: side values must be -1, 0, +1 or 2 (site %d)"
+                         : "%s: a row of side 2 needs upper_dev; other side values must be -1, 0 or +1 (site %d)",
+                   where, b);
+    if (S(b, CEN_ST_BADBRK) != 0.0)
+      return failf(DGP_E_ARG, "%s: %d bad bracket(s) in site %d: a row of side 2 needs a finite upper above its y", where,
+                   (int)S(b, CEN_ST_BADBRK), b);
+    if (S(b, CEN_ST_BAD) != 0.0)
+      return batched ? failf(DGP_E_ARG, "%s: side values must be -1, 0 or +1 (site %d)", where, b)
+                     : failf(DGP_E_ARG, "%s: side values must be -1, 0 or +1", where);
+    (S(b, CEN_ST_NCENS) != 0.0 ? any : any_plain) = true;
+  }
+  if (!any) {  // nothing censored: the plain step on (y - m, v), bit for bit
+    if ((rc = fit_step<double>(p, theta, D(L.rt), D(L.nn), out, with_grad ? dr : nullptr, with_grad ? D(L.dnoise) : nullptr, with_grad, s)))
+      return rc;
+    return censored_mode(f, mean, alpha, n, work, L, s, bt);
+  }
+  if ((rc = (int)hipMemsetAsync(D(L.acur), 0, sizeof(double) * (size_t)B * (size_t)n, s))) return rc;
+  std::vector<char> active((size_t)B);
+  for (int b = 0; b < B; ++b) active[b] = S(b, CEN_ST_DONE) == 0.0;
+  int it = 0;
+  for (;;) {
+    if ((rc = fit_step<double>(p, theta, D(L.rt), D(L.nn), D(L.out), nullptr, nullptr, 0, s))) return rc;
+    ++it;
+    // proposal, line search, update; then the next system (or the one at the mode) of every site that moved
+    if ((rc = censored_newton_update(f, y, side, noise, mean, alpha, n, it, tol, work, L, s, bt, upper)) ||
+        (rc = censored_terms(f, y, side, noise, mean, n, 0, it, work, L, s, bt, upper)) || (rc = read_status()))
+      return rc;
+    bool all_done = true;
+    for (int b = 0; b < B; ++b) {
+      if (!active[b]) continue;
+      stat[4 * b] = (double)it;
+      stat[4 * b + 1] = S(b, CEN_ST_DMAX);
+      stat[4 * b + 2] += S(b, CEN_ST_HALVINGS);
+      if (S(b, CEN_ST_DONE) != 0.0)
+        active[b] = 0;  // converged, or not positive definite: f did not move; the step below reports it through DGP_OUT_INFO
+      else
+        all_done = false;
+    }
+    if (all_done || it >= maxit) break;
+  }
+  if ((rc = fit_step<double>(p, theta, D(L.rt), D(L.nn), out, nullptr, with_grad ? D(L.dnoise) : nullptr, with_grad, s))) return rc;
+  if (with_grad) {
+    if ((rc = censored_weights(alpha, n, p->N, work, L, s, bt))) return rc;
+    // u = T^T (T w) in the work area: the plan's z, alpha and result rows stay as the step left them
+    if ((rc = solve_work<double>((const double*)p->Tm, p->N, D(L.slices + L.w), n, D(L.slices + L.z), D(L.slices + L.u),
+                                 D(L.slices + L.spart), D(L.slices + L.quad), wss, s, bt)))
+      return rc;
+    // (the step's Gram build left this theta in the plan's hyperparameter scratch)
+    if ((rc = gram_bilinear<double>(p->model, p->d, (const double*)p->Xt, p->N, n, theta, D(L.slices + L.u), alpha,
+                                    D(L.slices + L.gpart), out + DGP_OUT_DTHETA, 1, s, bt, wss, bt.ws, wss, DGP_OUT_LEN, p->pre, false,
+                                    nullptr)))
+      return rc;
+  }
+  if (any_plain && (rc = censored_mode(f, mean, alpha, n, work, L, s, bt))) return rc;  // the batch-mates without a censored row
+  if ((rc = censored_result(alpha, side, (const double*)p->dr_w, n, with_grad, out, dr, work, L, s, bt)) || (rc = read_status())) return rc;
+  int open_site = -1;
+  for (int b = 0; b < B; ++b) {
+    stat[4 * b + 3] = S(b, CEN_ST_CAPPED);
+    if (active[b] && open_site < 0) open_site = b;
+  }
+  if (open_site >= 0)
+    return batched ? failf(DGP_E_NOCONV, "%s: the mode search of site %d did not converge in %d Newton iterations (max |df| = %.3g)", where,
+                           open_site, it, stat[4 * open_site + 1])
+                   : failf(DGP_E_NOCONV, "%s: the mode search did not converge in %d Newton iterations (max |df| = %.3g)", where, it, stat[1]);
+  return 0;
+}
+static int laplace_entry(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise, const int32_t* side,
+                         void* f, int maxit, double tol, void* work, size_t work_bytes, void* out, void* dr, double* stat,
+                         int with_grad, int batched, const char* where, void* stream, const void* upper = nullptr, int interval = 0) {
+  if (!p) return fail(DGP_E_ARG, "null plan");
+  if (batched ? p->dtype != DGP_F64 : (p->dtype != DGP_F64 || p->B != 1))
+    return batched ? failf(DGP_E_ARG, "%s: censored fits need a float64 plan (fp32 plans are not supported)", where)
+                   : failf(DGP_E_ARG, "%s: censored fits need a float64 single-site plan (fp32 and batched plans are not supported)", where);
+  if (!theta || !y || !mean || !noise || !side || !f || !out || !stat || maxit < 1 || !(tol >= 0.0))
+    return failf(DGP_E_ARG, "%s: null argument (f_dev included), maxit < 1 or a negative tol", where);
+  DGP_CHECK_PLAN(p);
+  if (!p->have_inputs) return fail(DGP_E_STATE, "dgp_laplace_*: call dgp_set_inputs first");
+  if (!work || work_bytes < (batched ? dgp_laplace_batched_workspace_bytes(p) : dgp_laplace_workspace_bytes(p)))
+    return failf(DGP_E_WORKSPACE, "%s: workspace missing or too small", where);
+  if (((uintptr_t)work & 255) != 0) return fail(DGP_E_ARG, "dgp_laplace_*: the work area must be 256-byte aligned");
+  const int rc = laplace(p, theta, (const double*)y, (const double*)mean, (const double*)noise, (const int*)side, (double*)f, maxit, tol,
+                         (char*)work, (double*)out, (double*)dr, stat, with_grad, batched, where, (hipStream_t)stream,
+                         (const double*)upper, interval);
+  if (rc == DGP_E_ARG || rc == DGP_E_NOCONV) return rc;  // text set where it arose
+  return wrap(rc, where);
+}
+
+// u_dev / alpha_dev [B][n] -> dtheta_dev [B][ntheta]; B = 1: the single-site sweep
+static int debug_bilinear(dgp_plan* p, const double* theta, const void* u, const void* alpha, void* work, size_t work_bytes, double* dtheta,
+                          int batched, const char* where, void* stream) {
+  if (!p) return fail(DGP_E_ARG, "null plan");
+  if (p->dtype != DGP_F64 || (!batched && p->B != 1))
+    return failf(DGP_E_ARG, batched ? "%s: needs a float64 plan" : "%s: needs a float64 single-site plan", where);
+  if (!theta || !u || !alpha || !dtheta) return failf(DGP_E_ARG, "%s: null argument", where);
+  DGP_CHECK_PLAN(p);
+  if (!p->have_inputs) return failf(DGP_E_STATE, "%s: call dgp_set_inputs first", where);
+  if (int rc = need_work(work, work_bytes, batched ? dgp_laplace_batched_workspace_bytes(p) : dgp_laplace_workspace_bytes(p), where))
+    return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int B = p->B;
+  const CensoredLayout L = censored_layout(p->N, p->n, B);
+  char* slices = (char*)work + L.slices;
+  double *up = (double*)(slices + L.u), *ap = (double*)(slices + L.w);
+  const size_t nb = sizeof(double) * (size_t)p->n;
+  hipError_t e = hipMemsetAsync(slices, 0, L.slice * (size_t)B, s);
+  if (e == hipSuccess) e = hipMemcpy2DAsync(up, L.slice, u, nb, nb, (size_t)B, hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess) e = hipMemcpy2DAsync(ap, L.slice, alpha, nb, nb, (size_t)B, hipMemcpyDeviceToDevice, s);
+  if (e != hipSuccess) return hipfail(e, where);
+  const long wss = (long)(L.slice / sizeof(double));
+  void* staging = p->pre ? p->ring.acquire(pre_scratch_bytes(B)) : nullptr;
+  const int rc = gram_bilinear<double>(p->model, p->d, (const double*)p->Xt, p->N, (int)p->n, theta, up, ap, (double*)(slices + L.gpart),
+                                       dtheta, 0, s, batch_of<double>(p), wss, wss, wss, p->ntheta, p->pre, true, staging);
+  if (staging) p->ring.commit(s);
+  p->pre_ready = 0;
+  return wrap(rc, where);
+}
+
+extern "C" {
+
+size_t dgp_laplace_workspace_bytes(const dgp_plan* p) {
+  if (!p || p->dtype != DGP_F64 || p->B != 1) return 0;
+  return censored_layout(p->N, p->n, 1).total;
+}
+size_t dgp_laplace_batched_workspace_bytes(const dgp_plan* p) {
+  if (!p || p->dtype != DGP_F64) return 0;
+  return censored_layout(p->N, p->n, p->B).total;
+}
+
+int dgp_laplace_fit_step(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise, const int32_t* side,
+                         void* f, int maxit, double tol, void* work, size_t work_bytes, void* out, void* dr, double* stat,
+                         void* stream) {
+  return laplace_entry(p, theta, y, mean, noise, side, f, maxit, tol, work, work_bytes, out, dr, stat, 1, 0, "dgp_laplace_fit_step",
+                       stream);
+}
+
+int dgp_laplace_factorize(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise, const int32_t* side,
+                          void* f, int maxit, double tol, void* work, size_t work_bytes, void* out, double* stat, void* stream) {
+  return laplace_entry(p, theta, y, mean, noise, side, f, maxit, tol, work, work_bytes, out, nullptr, stat, 0, 0, "dgp_laplace_factorize",
+                       stream);
+}
+
+int dgp_laplace_batched_fit_step(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise,
+                                 const int32_t* side, void* f, int maxit, double tol, void* work, size_t work_bytes, void* out, void* dr,
+                                 double* stat, void* stream) {
+  return laplace_entry(p, theta, y, mean, noise, side, f, maxit, tol, work, work_bytes, out, dr, stat, 1, 1,
+                       "dgp_laplace_batched_fit_step", stream);
+}
+
+int dgp_laplace_batched_factorize(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise,
+                                  const int32_t* side, void* f, int maxit, double tol, void* work, size_t work_bytes, void* out,
+                                  double* stat, void* stream) {
+  return laplace_entry(p, theta, y, mean, noise, side, f, maxit, tol, work, work_bytes, out, nullptr, stat, 0, 1,
+                       "dgp_laplace_batched_factorize", stream);
+}
+
+int dgp_laplace_interval_fit_step(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise,
+                                  const int32_t* side, const void* upper, void* f, int maxit, double tol, void* work, size_t work_bytes,
+                                  void* out, void* dr, double* stat, void* stream) {
+  return laplace_entry(p, theta, y, mean, noise, side, f, maxit, tol, work, work_bytes, out, dr, stat, 1, 1,
+                       "dgp_laplace_interval_fit_step", stream, upper, 1);
+}
+
+int dgp_laplace_interval_factorize(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise,
+                                   const int32_t* side, const void* upper, void* f, int maxit, double tol, void* work,
+                                   size_t work_bytes, void* out, double* stat, void* stream) {
+  return laplace_entry(p, theta, y, mean, noise, side, f, maxit, tol, work, work_bytes, out, nullptr, stat, 0, 1,
+                       "dgp_laplace_interval_factorize", stream, upper, 1);
+}
+
+int dgp_debug_interval_terms(const double* za, const double* delta, int64_t count, double* out, void* stream) {
+  if (!za || !delta || !out || count <= 0 || count > (1ll << 29))
+    return fail(DGP_E_ARG, "dgp_debug_interval_terms: null argument / bad count");
+  return wrap(debug_interval_terms(za, delta, count, out, (hipStream_t)stream), "dgp_debug_interval_terms");
+}
+
+int dgp_debug_censored_terms(const double* z, int64_t count, double* out, void* stream) {
+  if (!z || !out || count <= 0 || count > (1ll << 29)) return fail(DGP_E_ARG, "dgp_debug_censored_terms: null argument / bad count");
+  return wrap(debug_censored_terms(z, count, out, (hipStream_t)stream), "dgp_debug_censored_terms");
+}
+
+int dgp_debug_bilinear(dgp_plan* p, const double* theta, const void* u, const void* alpha, void* work, size_t work_bytes, double* dtheta,
+                       void* stream) {
+  return debug_bilinear(p, theta, u, alpha, work, work_bytes, dtheta, 0, "dgp_debug_bilinear", stream);
+}
+
+int dgp_debug_bilinear_batched(dgp_plan* p, const double* theta, const void* u, const void* alpha, void* work, size_t work_bytes,
+                               double* dtheta, void* stream) {
+  return debug_bilinear(p, theta, u, alpha, work, work_bytes, dtheta, 1, "dgp_debug_bilinear_batched", stream);
+}
+
+}  // extern "C"

@@ -24,11 +24,16 @@
 #include "dgp_censored_fn.h"
 #include "dgp_gemm.h"
 #include "dgp_gemm_dma.h"
-#include "dgp_internal.h"
+#include "dgp_plan.h"
 
 namespace dgp {
 
 namespace {
+
+// out [LCV_PLANES][n] (== DGP_LCV_* of dgp_hip.h)
+enum { LCV_MU = 0, LCV_VAR, LCV_LPD, LCV_PLO, LCV_PHI, LCV_DLP, LCV_TILT, LCV_PLANES };
+// what the terms pass found, before any other launch: a bad side value (without / with `upper`), a bad bracket
+enum { LCV_E_SIDE_NO_UPPER = -100, LCV_E_SIDE = -101, LCV_E_BRACKET = -102 };
 
 // folds of 2 .. CV_SMALL_GROUP run on cross_validate's block route too (blocks of order 128): only that route calls the tap
 constexpr int LCV_MIN_BLOCK_GROUP = CV_SMALL_GROUP + 1;
@@ -192,36 +197,37 @@ int lcv_chunk(void* ctx_, const CvBlocks& cb) {
   return (int)hipGetLastError();
 }
 
-size_t lcv_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
-}  // namespace
-
+struct LaplaceCvLayout {
+  size_t cen, resid, var, lpd, Ks, V, kss, mean, svar, part, cvw, ginv, h, total;  // byte offsets into the work area
+  long route_group, M;  // the bound handed to cross_validate (1: leave-one-out; else >= 65: its block route) and the block order
+  int C;                // folds per chunk of the block route
+};
 LaplaceCvLayout laplace_cv_layout(long N, long n, int ngroups, long max_group) {
   LaplaceCvLayout L;
-  const size_t d = sizeof(double), vecN = lcv_align(d * (size_t)N);
+  const size_t d = sizeof(double), vecN = d * (size_t)N;
   L.route_group = max_group <= 1 ? 1 : (max_group < LCV_MIN_BLOCK_GROUP ? LCV_MIN_BLOCK_GROUP : max_group);
   L.M = max_group <= 1 ? 0 : round_up(L.route_group, DGP_TILE_HOST);
   L.C = max_group <= 1 ? 0 : cross_validate_chunk_groups(N, 1, ngroups, L.route_group);
-  size_t o = 0;
-  L.cen = o; o += lcv_align(censored_layout(N, n, 1).total);
-  L.resid = o; o += lcv_align(d * (size_t)n);
-  L.var = o; o += lcv_align(d * (size_t)n);
-  L.lpd = o; o += lcv_align(d * (size_t)ngroups);
-  L.Ks = o; o += lcv_align(d * (size_t)N * (size_t)N);
-  L.V = o; o += lcv_align(d * (size_t)N * (size_t)N);
-  L.kss = o; o += vecN;
-  L.mean = o; o += vecN;
-  L.svar = o; o += vecN;
-  L.part = o; o += lcv_align(d * 2 * PREDICT_SPLIT * (size_t)N);
-  L.cvw = o; o += lcv_align(cross_validate_workspace_bytes(N, 1, ngroups, L.route_group));
-  L.ginv = o; o += lcv_align(d * (size_t)L.C * (size_t)L.M * (size_t)L.M);
-  L.h = o; o += lcv_align(d * (size_t)L.C * (size_t)L.M);
-  L.total = o;
+  Carve c;
+  L.cen = c.take(censored_layout(N, n, 1).total);
+  L.resid = c.take(d * (size_t)n);
+  L.var = c.take(d * (size_t)n);
+  L.lpd = c.take(d * (size_t)ngroups);
+  L.Ks = c.take(d * (size_t)N * (size_t)N);
+  L.V = c.take(d * (size_t)N * (size_t)N);
+  L.kss = c.take(vecN);
+  L.mean = c.take(vecN);
+  L.svar = c.take(vecN);
+  L.part = c.take(d * 2 * PREDICT_SPLIT * (size_t)N);
+  L.cvw = c.take(cross_validate_workspace_bytes(N, 1, ngroups, L.route_group));
+  L.ginv = c.take(d * (size_t)L.C * (size_t)L.M * (size_t)L.M);
+  L.h = c.take(d * (size_t)L.C * (size_t)L.M);
+  L.total = c.o;
   return L;
 }
 
 // W, g and the cap at the mode, by the fit's own pass, into the work area; its sums (read back: synchronises the stream) tell a bad
-// side value or bracket before anything else runs
+// side value or bracket before anything else runs: 0, a HIP error or LCV_E_*
 int laplace_cv_terms(long N, int n, const double* y, const double* mean, const double* noise, const int* side, const double* upper,
                      const double* f, char* work, const LaplaceCvLayout& L, hipStream_t s) {
   int rc;
@@ -281,4 +287,52 @@ int laplace_cross_validate(int model, int d, const double* Xt, const double* Tm,
                                 D(L.lpd), info, s, bt, &tap);
 }
 
+bool lcv_plan_ok(const dgp_plan* p) { return p && p->dtype == DGP_F64 && p->B == 1; }
+
+}  // namespace
+
 }  // namespace dgp
+
+using namespace dgp;
+
+extern "C" {
+
+size_t dgp_laplace_cross_validate_workspace_bytes(const dgp_plan* p, int ngroups, int64_t max_group) {
+  if (!lcv_plan_ok(p) || !cv_sizes_ok(p, ngroups, max_group)) return 0;
+  return laplace_cv_layout(p->N, p->n, ngroups, max_group).total;
+}
+
+int dgp_laplace_cross_validate(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise, const int32_t* side,
+                               const void* upper, const void* f, const int32_t* order, const int32_t* start, int ngroups,
+                               int64_t max_group, double shift, void* work, size_t work_bytes, double* out, int32_t* info, void* stream) {
+  const char* where = "dgp_laplace_cross_validate";
+  if (!p) return fail(DGP_E_ARG, "null plan");
+  if (!lcv_plan_ok(p))
+    return fail(DGP_E_ARG, "dgp_laplace_cross_validate: needs a float64 single-site plan (fp32 and batched plans are not supported)");
+  if (!theta || !y || !mean || !noise || !side || !f || !order || !start || !out || !info || !(shift == shift))
+    return fail(DGP_E_ARG, "dgp_laplace_cross_validate: null argument (f_dev included) or a NaN shift");
+  if (!cv_sizes_ok(p, ngroups, max_group))
+    return fail(DGP_E_ARG, "dgp_laplace_cross_validate: bad size (1 <= ngroups <= n, 1 <= max_group <= n)");
+  DGP_CHECK_PLAN(p);
+  int rc = need_factor(p, where, "call dgp_laplace_factorize or dgp_laplace_fit_step");
+  if (rc || (rc = need_work(work, work_bytes, dgp_laplace_cross_validate_workspace_bytes(p, ngroups, max_group), where))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const LaplaceCvLayout L = laplace_cv_layout(p->N, p->n, ngroups, max_group);
+  // the terms pass and its read-back first: the staging slot below is not held across the synchronisation
+  rc = laplace_cv_terms(p->N, (int)p->n, (const double*)y, (const double*)mean, (const double*)noise, side, (const double*)upper,
+                        (const double*)f, (char*)work, L, s);
+  if (rc == 0) {
+    PreSlot slot(p, s);
+    rc = laplace_cross_validate(p->model, p->d, (const double*)p->Xt, (const double*)p->Tm, (const double*)p->alpha, p->N, (int)p->n, theta,
+                                (const double*)y, (const double*)noise, side, (const double*)upper, (const double*)f, order, start,
+                                ngroups, shift, (char*)work, L, out, info, s, batch_of<double>(p), p->pre, slot.staging);
+  }
+  if (rc == LCV_E_SIDE_NO_UPPER)
+    return fail(DGP_E_ARG, "dgp_laplace_cross_validate: a row of side 2 needs upper_dev; other side values must be -1, 0 or +1");
+  if (rc == LCV_E_SIDE) return fail(DGP_E_ARG, "dgp_laplace_cross_validate: side values must be -1, 0, +1 or 2");
+  if (rc == LCV_E_BRACKET)
+    return fail(DGP_E_ARG, "dgp_laplace_cross_validate: bad bracket(s): a row of side 2 needs a finite upper above its y");
+  return wrap(rc, where);
+}
+
+}  // extern "C"

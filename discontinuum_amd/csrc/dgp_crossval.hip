@@ -21,7 +21,7 @@
 #include "dgp_common.h"
 #include "dgp_gemm.h"
 #include "dgp_gemm_dma.h"
-#include "dgp_internal.h"
+#include "dgp_plan.h"
 
 namespace dgp {
 
@@ -473,7 +473,6 @@ int cv_chunk_groups(long N, int B, int ngroups, long M) {
   if (C * B > 65535) C = 65535 / B;
   return C < 1 ? 1 : (int)C;
 }
-size_t cv_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
 
@@ -482,12 +481,12 @@ int cross_validate_chunk_groups(long N, int B, int ngroups, long max_group) {
 }
 
 size_t cross_validate_workspace_bytes(long N, int B, int ngroups, long max_group) {
-  if (max_group <= 1) return cv_align(sizeof(double) * (size_t)(N / CV_SLAB) * (size_t)N * (size_t)B);
+  if (max_group <= 1) return Carve::up(sizeof(double) * (size_t)(N / CV_SLAB) * (size_t)N * (size_t)B);
   if (max_group <= CV_SMALL) return 256;
   const long M = cv_block_order(max_group);
   const size_t nz = (size_t)cv_chunk_groups(N, B, ngroups, M) * (size_t)B;
   const CvSlots sl(M);
-  return cv_align(sizeof(double) * nz * (size_t)sl.elems) + cv_align(sizeof(double) * (nz * (size_t)N + 64) * (size_t)M) + cv_align(sizeof(int) * nz);
+  return Carve::up(sizeof(double) * nz * (size_t)sl.elems) + Carve::up(sizeof(double) * (nz * (size_t)N + 64) * (size_t)M) + Carve::up(sizeof(int) * nz);
 }
 
 template <typename T>
@@ -516,8 +515,8 @@ int cross_validate(const T* Tm, const T* S, const T* alpha, long N, int n, const
   const size_t nz = (size_t)C * Bz;
   const CvSlots sl(M);
   double* slots = (double*)work;
-  double* panels = (double*)((char*)work + cv_align(sizeof(double) * nz * (size_t)sl.elems));
-  int* meta = (int*)((char*)panels + cv_align(sizeof(double) * (nz * (size_t)N + 64) * (size_t)M));  // (64 rows of slack)
+  double* panels = (double*)((char*)work + Carve::up(sizeof(double) * nz * (size_t)sl.elems));
+  int* meta = (int*)((char*)panels + Carve::up(sizeof(double) * (nz * (size_t)N + 64) * (size_t)M));  // (64 rows of slack)
   Tuning tune = bt.tuning();
   tune.chain_yield = 0;
   Batch bb;  // the chunk's blocks as one ragged-free batch of the library's own factor-and-invert
@@ -558,3 +557,35 @@ template int cross_validate<float>(const float*, const float*, const float*, lon
                                    double*, double*, int*, hipStream_t, Batch, const CvTap*);
 
 }  // namespace dgp
+
+using namespace dgp;
+
+extern "C" {
+
+size_t dgp_cross_validate_workspace_bytes(const dgp_plan* p, int ngroups, int64_t max_group) {
+  if (!cv_sizes_ok(p, ngroups, max_group)) return 0;
+  return cross_validate_workspace_bytes(p->N, p->B, ngroups, max_group);
+}
+
+int dgp_cross_validate(dgp_plan* p, const int32_t* order, const int32_t* start, int ngroups, int64_t max_group, void* work,
+                       size_t work_bytes, double* resid, double* var, double* lpd, int32_t* info, void* stream) {
+  if (!p) return fail(DGP_E_ARG, "null plan");
+  if (!order || !start || !resid || !var || !lpd || !info) return fail(DGP_E_ARG, "dgp_cross_validate: null argument");
+  if (!cv_sizes_ok(p, ngroups, max_group))
+    return fail(DGP_E_ARG, "dgp_cross_validate: bad size (1 <= ngroups <= n, 1 <= max_group <= n)");
+  DGP_CHECK_PLAN(p);
+  int rc = need_factor(p, "dgp_cross_validate", "call dgp_factorize or dgp_fit_step");
+  if (rc || (rc = need_work(work, work_bytes, dgp_cross_validate_workspace_bytes(p, ngroups, max_group), "dgp_cross_validate"))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  // K^^-1 (S) is read when the last step left it valid and never written; after a bare dgp_factorize it is dead and ignored
+  const void* S = p->have_inverse ? p->S : nullptr;
+  rc = DGP_BY_DTYPE(
+      p,
+      cross_validate<double>((const double*)p->Tm, (const double*)S, (const double*)p->alpha, p->N, (int)p->n, order, start, ngroups,
+                             max_group, work, resid, var, lpd, info, s, batch_of<double>(p)),
+      cross_validate<float>((const float*)p->Tm, (const float*)S, (const float*)p->alpha, p->N, (int)p->n, order, start, ngroups, max_group,
+                            work, resid, var, lpd, info, s, batch_of<float>(p)));
+  return wrap(rc, "dgp_cross_validate");
+}
+
+}  // extern "C"

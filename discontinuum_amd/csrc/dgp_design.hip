@@ -26,7 +26,7 @@
 #include <climits>
 
 #include "dgp_common.h"
-#include "dgp_internal.h"
+#include "dgp_plan.h"
 
 namespace dgp {
 
@@ -247,13 +247,15 @@ void sv_launch_sums(const T* cov, long M, int m, int B, int P, int Q, int K, con
 
 }  // namespace
 
-size_t sample_value_workspace_bytes(long m, int P, int K, int B) {
+static size_t sample_value_workspace_bytes(long m, int P, int K, int B) {
   return sizeof(double) * (size_t)B * (size_t)sv_site_doubles(round_up(m, DGP_TILE_HOST), P, K);
 }
 
+// the expected reduction of Var(L_p) by one more sample on each day c, after `nrows` conditioning rows (rows [B][nrows][m], null
+// when nrows == 0; a [B][m] the A_i; ov: the candidates' noise variance or null).  gain_out [B][P][m], var_out [B][m]
 template <typename T>
-int sample_value(const T* cov, long m, int B, const double* a, const double* scale2, const int* group, int P, const T* ov,
-                 const double* rows, int nrows, int K, double* work, double* gain_out, double* var_out, hipStream_t s) {
+static int sample_value(const T* cov, long m, int B, const double* a, const double* scale2, const int* group, int P, const T* ov,
+                        const double* rows, int nrows, int K, double* work, double* gain_out, double* var_out, hipStream_t s) {
   static_assert(SV_DAYS * SV_LD * sizeof(double) % 16 == 0, "the LDS carve offsets must stay 16-byte aligned");
   const long M = round_up(m, DGP_TILE_HOST);
   const int Q = sv_slabs(M, P), mi = (int)m;
@@ -275,9 +277,40 @@ int sample_value(const T* cov, long m, int B, const double* a, const double* sca
   return (int)hipGetLastError();
 }
 
-template int sample_value<double>(const double*, long, int, const double*, const double*, const int*, int, const double*,
-                                  const double*, int, int, double*, double*, double*, hipStream_t);
-template int sample_value<float>(const float*, long, int, const double*, const double*, const int*, int, const float*,
-                                 const double*, int, int, double*, double*, double*, hipStream_t);
-
 }  // namespace dgp
+
+using namespace dgp;
+
+static bool sv_sizes_ok(int64_t m, int ngroups, int nrows, int nterms, int batch) {
+  return m > 0 && m <= (1 << 20) && ngroups > 0 && ngroups <= 65535 && nrows >= 0 && nrows <= 64 && nterms >= 1 && nterms <= 64 &&
+         batch > 0 && batch <= DGP_MAX_BATCH_SITES;
+}
+
+extern "C" {
+
+size_t dgp_sample_value_workspace_bytes(int64_t m, int ngroups, int nrows, int nterms, int batch) {
+  if (!sv_sizes_ok(m, ngroups, nrows, nterms, batch)) return 0;
+  return sample_value_workspace_bytes(m, ngroups, nterms, batch);
+}
+
+int dgp_sample_value(int dtype, const void* cov, int64_t m, int batch, const double* a, const double* scale2, const int32_t* group,
+                     int ngroups, const void* obs_var, const double* rows, int nrows, int nterms, void* work, size_t work_bytes,
+                     double* gain_out, double* var_out, void* stream) {
+  if (dtype != DGP_F64 && dtype != DGP_F32) return fail(DGP_E_ARG, "dgp_sample_value: dtype must be 0 (f64) or 1 (f32)");
+  if (!cov || !a || !scale2 || !group || !gain_out || !var_out) return fail(DGP_E_ARG, "dgp_sample_value: null argument");
+  if (!sv_sizes_ok(m, ngroups, nrows, nterms, batch))
+    return fail(DGP_E_ARG,
+                "dgp_sample_value: bad size (1 <= m <= 2^20, 1 <= ngroups <= 65535, 0 <= nrows <= 64, 1 <= nterms <= 64, "
+                "1 <= batch <= 1024)");
+  if (nrows > 0 && !rows) return fail(DGP_E_ARG, "dgp_sample_value: null argument (rows with nrows > 0)");
+  if (!work || work_bytes < sample_value_workspace_bytes(m, ngroups, nterms, batch))
+    return fail(DGP_E_WORKSPACE, "dgp_sample_value: workspace missing or too small");
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = dtype == DGP_F64 ? sample_value<double>((const double*)cov, m, batch, a, scale2, group, ngroups, (const double*)obs_var,
+                                                         rows, nrows, nterms, (double*)work, gain_out, var_out, s)
+                                  : sample_value<float>((const float*)cov, m, batch, a, scale2, group, ngroups, (const float*)obs_var,
+                                                        rows, nrows, nterms, (double*)work, gain_out, var_out, s);
+  return wrap(rc, "dgp_sample_value");
+}
+
+}  // extern "C"

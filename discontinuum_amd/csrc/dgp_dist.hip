@@ -275,7 +275,6 @@ struct dgp_dist {
   int owned_below(int g) const { return g <= rank ? 0 : (g - rank + world - 1) / world; }  // own groups with index < g
 };
 
-static size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 struct DistLayout {
   size_t Xt, A, Tm, S, z, part, gpart, scal, info, total;
 };
@@ -283,17 +282,17 @@ static DistLayout dist_layout(const dgp_dist* p) {
   DistLayout L;
   const size_t e = p->elem, N = (size_t)p->N, Cl = (size_t)p->Cl;
   const size_t nchunks = (N + DGP_SLAB_CHUNK - 1) / DGP_SLAB_CHUNK;
-  size_t o = 0;
-  L.Xt = o; o += align_up(e * N * p->d);
-  L.A = o; o += align_up(e * N * Cl);
-  L.Tm = o; o += align_up(e * N * Cl);
-  L.S = o; o += align_up(e * N * Cl);
-  L.z = o; o += align_up(e * N);
-  L.part = o; o += align_up(e * nchunks * Cl);
-  L.gpart = o; o += align_up(e * (size_t)gram_grad_slab_partials((long)N, (long)Cl));
-  L.scal = o; o += align_up(e * 16);
-  L.info = o; o += align_up(sizeof(int) * POTRF_INFO_INTS);
-  L.total = o;
+  Carve c;
+  L.Xt = c.take(e * N * p->d);
+  L.A = c.take(e * N * Cl);
+  L.Tm = c.take(e * N * Cl);
+  L.S = c.take(e * N * Cl);
+  L.z = c.take(e * N);
+  L.part = c.take(e * nchunks * Cl);
+  L.gpart = c.take(e * (size_t)gram_grad_slab_partials((long)N, (long)Cl));
+  L.scal = c.take(e * 16);
+  L.info = c.take(sizeof(int) * POTRF_INFO_INTS);
+  L.total = c.o;
   return L;
 }
 

@@ -28,9 +28,30 @@
 //                       partials (added to out[DGP_OUT_NLL] in a fixed order by ep_result_finish_kernel) and the optional cavity outputs
 // No floating-point atomics; every result repeats bitwise.
 #include "dgp_censored_fn.h"
-#include "dgp_internal.h"
+#include "dgp_plan.h"
 
 namespace dgp {
+
+// The work area is an EpLayout: a CensoredLayout first (the terms pass at f = m validates the rows and gives the cold start; its
+// rt holds r~, its `out` the result row of the sweep's factorisation), then the proposals, the previous means, k and the partials.
+#define EP_PART 8  // doubles per workgroup of the block partials
+enum {
+  EP_ST_DMU = 0,  // max |mu - mu_prev| of the sweep (first sweep: max v |nu' - nu~|); inf when the factorisation failed
+  EP_ST_DTAU,     // max v |tau' - tau~|
+  EP_ST_CAPPED,   // proposals at the cap
+  EP_ST_HELD,     // rows held back by the guard (v_c <= 0 or 1 - W v_c <= 0)
+  EP_ST_NCENS,
+  EP_ST_DONE,     // 0: the sweeps go on; k > 0: ended in sweep k (converged, or not positive definite)
+  EP_ST_INFO,     // DGP_OUT_INFO of the sweep's factorisation
+  EP_ST_CONV,     // 1: both tests passed
+  EP_ST_CORR,     // NLL_EP - NLL_engine (ep_result)
+  EP_ST_LEN = 16
+};
+struct EpLayout {
+  CensoredLayout cen;
+  size_t yprop, nprop, muprev, kdiag, kpart, part, status, total;  // byte offsets
+  int nchunk, nblk;
+};
 
 #define EP_DIAG_ROWS 256  // rows per partial sum of ep_diag_kernel
 #define EP_LOG2PI 1.83787706640934548356
@@ -287,42 +308,47 @@ __global__ __launch_bounds__(256) void ep_result_finish_kernel(const double* __r
   status[EP_ST_CORR] = tot[0];
 }
 
-EpLayout ep_layout(long N, long n) {
+static EpLayout ep_layout(long N, long n) {
   EpLayout L;
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
   L.cen = censored_layout(N, n, 1);
-  const size_t vec = al(sizeof(double) * (size_t)n);
-  size_t o = L.cen.total;
-  L.yprop = o; o += vec;
-  L.nprop = o; o += vec;
-  L.muprev = o; o += vec;
-  L.kdiag = o; o += vec;
+  const size_t vec = sizeof(double) * (size_t)n;
+  Carve c;
+  c.o = L.cen.total;
+  L.yprop = c.take(vec);
+  L.nprop = c.take(vec);
+  L.muprev = c.take(vec);
+  L.kdiag = c.take(vec);
   L.nchunk = (int)((n + EP_DIAG_ROWS - 1) / EP_DIAG_ROWS);
-  L.kpart = o; o += al(sizeof(double) * (size_t)L.nchunk * (size_t)N);
+  L.kpart = c.take(sizeof(double) * (size_t)L.nchunk * (size_t)N);
   L.nblk = (int)((n + 255) / 256);
-  L.part = o; o += al(sizeof(double) * (size_t)L.nblk * EP_PART);
-  L.status = o; o += al(sizeof(double) * EP_ST_LEN);
-  L.total = o;
+  L.part = c.take(sizeof(double) * (size_t)L.nblk * EP_PART);
+  L.status = c.take(sizeof(double) * EP_ST_LEN);
+  L.total = c.o;
   return L;
 }
 
-int ep_init(const double* y, const int* side, const double* v, const double* m, double* yt, double* nt, int n, int cold, char* work,
+// the sites before the first sweep, after censored_terms(f = m, init) has filled L.cen: cold != 0: every censored row from the
+// Laplace terms at m; else the caller's (a row without a usable site starts cold).  Rows of side 0: (y, v).  Writes r~ to L.cen.rt.
+static int ep_init(const double* y, const int* side, const double* v, const double* m, double* yt, double* nt, int n, int cold, char* work,
             const EpLayout& L, hipStream_t s) {
   double* rt = (double*)(work + L.cen.rt);
   ep_init_kernel<<<dim3((unsigned)L.nblk), 256, 0, s>>>(y, side, v, m, rt, (const double*)(work + L.cen.nn), yt, nt, rt, n, cold);
   return (int)hipGetLastError();
 }
 
-int ep_diag(const double* Tm, long N, int n, double* k, char* work, const EpLayout& L, hipStream_t s) {
+// k_i = sum_{j >= i} T_ji^2, i < n, from the row-major lower triangle T = L^-1 (leading dimension N)
+static int ep_diag(const double* Tm, long N, int n, double* k, char* work, const EpLayout& L, hipStream_t s) {
   double* kpart = (double*)(work + L.kpart);
   ep_diag_kernel<<<dim3((unsigned)((n + 63) / 64), (unsigned)L.nchunk), 256, 0, s>>>(Tm, N, n, kpart);
   ep_diag_sum_kernel<<<dim3((unsigned)L.nblk), 256, 0, s>>>(kpart, N, n, k);
   return (int)hipGetLastError();
 }
 
-int ep_sweep(const double* Tm, long N, const double* alpha, const double* y, const int* side, const double* v, const double* m,
-             const double* upper, double* yt, double* nt, int n, int sweep, int last, double tol, double damping, char* work,
-             const EpLayout& L, hipStream_t s) {
+// after the factorisation at (r~, n~) left T and alpha in the plan and its result row in L.cen.out: k, proposals, test, status; the
+// proposals replace the sites (and r~) only when the sweep neither converged nor is the last
+static int ep_sweep(const double* Tm, long N, const double* alpha, const double* y, const int* side, const double* v, const double* m,
+                    const double* upper, double* yt, double* nt, int n, int sweep, int last, double tol, double damping, char* work,
+                    const EpLayout& L, hipStream_t s) {
   auto D = [&](size_t off) { return (double*)(work + off); };
   int rc;
   if ((rc = ep_diag(Tm, N, n, D(L.kdiag), work, L, s))) return rc;
@@ -333,9 +359,10 @@ int ep_sweep(const double* Tm, long N, const double* alpha, const double* y, con
   return (int)hipGetLastError();
 }
 
-int ep_result(const double* alpha, const double* y, const int* side, const double* v, const double* upper, const double* yt,
-              const double* nt, int n, double* out, double* cav_mean, double* cav_var, double* logz, char* work, const EpLayout& L,
-              hipStream_t s) {
+// out[DGP_OUT_NLL] += NLL_EP - NLL_engine (out null: not wanted) from alpha and L.kdiag; cavities and log Z^ (n doubles each, nullable)
+static int ep_result(const double* alpha, const double* y, const int* side, const double* v, const double* upper, const double* yt,
+                     const double* nt, int n, double* out, double* cav_mean, double* cav_var, double* logz, char* work, const EpLayout& L,
+                     hipStream_t s) {
   auto D = [&](size_t off) { return (double*)(work + off); };
   ep_result_kernel<<<dim3((unsigned)L.nblk), 256, 0, s>>>(y, side, v, upper, yt, nt, alpha, D(L.kdiag), n, cav_mean, cav_var, logz,
                                                           D(L.part));
@@ -344,3 +371,132 @@ int ep_result(const double* alpha, const double* y, const int* side, const doubl
 }
 
 }  // namespace dgp
+
+using namespace dgp;
+
+// ---- the entries: parallel sweeps on the factorise path, then (fit step) one step at the final sites, whose explicit gradient IS
+// the gradient at the fixed point.  The host reads one status block per sweep.  The sites that were factorised last are the result
+// (a converged or last sweep's proposal is not applied), so the plan's factorisation, k, the cavities and log Z^ belong to one
+// state.  stat: [6].
+static int ep(dgp_plan* p, const double* theta, const double* y, const double* mean, const double* noise, const int* side,
+              const double* upper, double* yt, double* nt, int cold, int maxit, double tol, double damping, char* work, double* out,
+              double* dr, double* stat, double* cav_mean, double* cav_var, double* logz, int with_grad, const char* where, hipStream_t s) {
+  const EpLayout L = ep_layout(p->N, p->n);
+  const Batch bt = batch_of<double>(p);
+  auto D = [&](size_t off) { return (double*)(work + off); };
+  const int n = (int)p->n;
+  const double* alpha = (const double*)p->alpha;
+  const double* Tm = (const double*)p->Tm;
+  double st[CEN_ST_LEN > EP_ST_LEN ? CEN_ST_LEN : EP_ST_LEN];
+  auto read_status = [&](size_t off, int len) -> int {
+    hipError_t e = hipMemcpyAsync(st, D(off), sizeof(double) * (size_t)len, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    return (int)e;
+  };
+  int rc;
+  for (int k = 0; k < 6; ++k) stat[k] = 0.0;
+  // the Laplace terms at f = m: the rows are checked as the Laplace entries check them, and a cold start is their pseudo-data
+  if ((rc = censored_terms(mean, y, side, noise, mean, n, 1, 0, work, L.cen, s, bt, upper)) || (rc = read_status(L.cen.status, CEN_ST_LEN)))
+    return rc;
+  if (st[CEN_ST_BAD] != 0.0)
+    return failf(DGP_E_ARG,
+                 upper ? "%s: side values must be -1, 0, +1 or 2" : "%s: a row of side 2 needs upper_dev; other side values must be -1, 0 or +1",
+                 where);
+  if (st[CEN_ST_BADBRK] != 0.0)
+    return failf(DGP_E_ARG, "%s: %d bad bracket(s): a row of side 2 needs a finite upper above its y", where, (int)st[CEN_ST_BADBRK]);
+  const double ncens = st[CEN_ST_NCENS];
+  stat[5] = ncens;
+  const bool aux = cav_mean || cav_var || logz;
+  if (ncens == 0.0) {  // nothing censored: the plain step on (y - m, v), bit for bit; the sites are (y, v)
+    if ((rc = fit_step<double>(p, theta, D(L.cen.rt), D(L.cen.nn), out, with_grad ? dr : nullptr, with_grad ? D(L.cen.dnoise) : nullptr,
+                               with_grad, s)) ||
+        (rc = ep_init(y, side, noise, mean, yt, nt, n, 1, work, L, s)))
+      return rc;
+    if (aux && ((rc = ep_diag(Tm, p->N, n, D(L.kdiag), work, L, s)) ||
+                (rc = ep_result(alpha, y, side, noise, upper, yt, nt, n, nullptr, cav_mean, cav_var, logz, work, L, s))))
+      return rc;
+    return 0;
+  }
+  if ((rc = ep_init(y, side, noise, mean, yt, nt, n, cold, work, L, s))) return rc;
+  int it = 0;
+  bool conv = false;
+  for (;;) {
+    if ((rc = fit_step<double>(p, theta, D(L.cen.rt), nt, D(L.cen.out), nullptr, nullptr, 0, s))) return rc;
+    ++it;
+    if ((rc = ep_sweep(Tm, p->N, alpha, y, side, noise, mean, upper, yt, nt, n, it, it >= maxit, tol, damping, work, L, s)) ||
+        (rc = read_status(L.status, EP_ST_LEN)))
+      return rc;
+    stat[0] = (double)it;
+    stat[1] = st[EP_ST_DMU];
+    stat[2] = st[EP_ST_DTAU];
+    stat[3] = st[EP_ST_CAPPED];
+    stat[4] = st[EP_ST_HELD];
+    conv = st[EP_ST_DONE] != 0.0;  // converged, or not positive definite: the result row reports that through DGP_OUT_INFO
+    if (conv || it >= maxit) break;
+  }
+  if (with_grad) {
+    // the same system once more with K^^-1 and the gradient contraction: the same T and alpha, so k stays valid
+    if ((rc = fit_step<double>(p, theta, D(L.cen.rt), nt, out, dr, D(L.cen.dnoise), 1, s))) return rc;
+  } else if ((rc = (int)hipMemcpyAsync(out, D(L.cen.out), sizeof(double) * DGP_OUT_LEN, hipMemcpyDeviceToDevice, s))) {
+    return rc;
+  }
+  if ((rc = ep_result(alpha, y, side, noise, upper, yt, nt, n, out, cav_mean, cav_var, logz, work, L, s)) || (rc = (int)hipStreamSynchronize(s)))
+    return rc;
+  if (!conv)
+    return failf(DGP_E_NOCONV, "%s: expectation propagation did not converge in %d sweeps (max |dmu| = %.3g, max v |dtau| = %.3g)", where, it,
+                 stat[1], stat[2]);
+  return 0;
+}
+static int ep_entry(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise, const int32_t* side,
+                    const void* upper, void* yt, void* nt, int cold, int maxit, double tol, double damping, void* work, size_t work_bytes,
+                    void* out, void* dr, double* stat, void* cav_mean, void* cav_var, void* logz, int with_grad, const char* where,
+                    void* stream) {
+  if (!p) return fail(DGP_E_ARG, "null plan");
+  if (p->dtype != DGP_F64 || p->B != 1)
+    return failf(DGP_E_ARG, "%s: expectation propagation needs a float64 single-site plan (fp32 and batched plans are not supported)", where);
+  if (!theta || !y || !mean || !noise || !side || !yt || !nt || !out || !stat || maxit < 1 || !(tol >= 0.0))
+    return failf(DGP_E_ARG, "%s: null argument (ytilde_dev / ntilde_dev included), maxit < 1 or a negative tol", where);
+  if (!(damping > 0.0 && damping <= 1.0)) return failf(DGP_E_ARG, "%s: damping must lie in (0, 1]", where);
+  DGP_CHECK_PLAN(p);
+  if (!p->have_inputs) return fail(DGP_E_STATE, "dgp_ep_*: call dgp_set_inputs first");
+  if (!work || work_bytes < dgp_ep_workspace_bytes(p)) return failf(DGP_E_WORKSPACE, "%s: workspace missing or too small", where);
+  if (((uintptr_t)work & 255) != 0) return fail(DGP_E_ARG, "dgp_ep_*: the work area must be 256-byte aligned");
+  const int rc = ep(p, theta, (const double*)y, (const double*)mean, (const double*)noise, (const int*)side, (const double*)upper,
+                    (double*)yt, (double*)nt, cold, maxit, tol, damping, (char*)work, (double*)out, (double*)dr, stat, (double*)cav_mean,
+                    (double*)cav_var, (double*)logz, with_grad, where, (hipStream_t)stream);
+  if (rc == DGP_E_ARG || rc == DGP_E_NOCONV) return rc;  // text set where it arose
+  return wrap(rc, where);
+}
+
+extern "C" {
+
+size_t dgp_ep_workspace_bytes(const dgp_plan* p) {
+  if (!p || p->dtype != DGP_F64 || p->B != 1) return 0;
+  return ep_layout(p->N, p->n).total;
+}
+
+int dgp_ep_fit_step(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise, const int32_t* side,
+                    const void* upper, void* ytilde, void* ntilde, int cold_start, int maxit, double tol, double damping, void* work,
+                    size_t work_bytes, void* out, void* dr, double* stat, void* cav_mean, void* cav_var, void* logz, void* stream) {
+  return ep_entry(p, theta, y, mean, noise, side, upper, ytilde, ntilde, cold_start, maxit, tol, damping, work, work_bytes, out, dr, stat,
+                  cav_mean, cav_var, logz, 1, "dgp_ep_fit_step", stream);
+}
+
+int dgp_ep_factorize(dgp_plan* p, const double* theta, const void* y, const void* mean, const void* noise, const int32_t* side,
+                     const void* upper, void* ytilde, void* ntilde, int cold_start, int maxit, double tol, double damping, void* work,
+                     size_t work_bytes, void* out, double* stat, void* cav_mean, void* cav_var, void* logz, void* stream) {
+  return ep_entry(p, theta, y, mean, noise, side, upper, ytilde, ntilde, cold_start, maxit, tol, damping, work, work_bytes, out, nullptr,
+                  stat, cav_mean, cav_var, logz, 0, "dgp_ep_factorize", stream);
+}
+
+int dgp_ep_diag(dgp_plan* p, void* k, void* work, size_t work_bytes, void* stream) {
+  if (!p || p->dtype != DGP_F64 || p->B != 1) return fail(DGP_E_ARG, "dgp_ep_diag: needs a float64 single-site plan");
+  if (!k) return fail(DGP_E_ARG, "dgp_ep_diag: null argument");
+  DGP_CHECK_PLAN(p);
+  int rc = need_factor(p, "dgp_ep_diag", nullptr);
+  if (rc || (rc = need_work(work, work_bytes, dgp_ep_workspace_bytes(p), "dgp_ep_diag"))) return rc;
+  return wrap(ep_diag((const double*)p->Tm, p->N, (int)p->n, (double*)k, (char*)work, ep_layout(p->N, p->n), (hipStream_t)stream),
+              "dgp_ep_diag");
+}
+
+}  // extern "C"

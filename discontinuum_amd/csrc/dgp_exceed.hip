@@ -35,7 +35,7 @@
 #include <climits>
 
 #include "dgp_bvn.h"
-#include "dgp_internal.h"
+#include "dgp_plan.h"
 
 namespace dgp {
 
@@ -282,9 +282,11 @@ void exceedance_reduce(long M, int B, int P, int L, int l0, int LC, double* work
                                                                                                   cov_out);
 }
 
+// exact mean / covariance of the counts sum_{i in g} w_i 1[f_i > u_il], f ~ N(mu, C), per level l.  thresh [B][L][m] in model
+// space; mean_out [B][L][P], cov_out [B][L][P][P]; `work`: exceedance_moments_workspace_bytes
 template <typename T>
-int exceedance_moments(const T* cov, long m, int B, const T* mu, const double* thresh, int L, const double* w, const int* group,
-                       int P, const T* ev, double* work, double* mean_out, double* cov_out, hipStream_t s) {
+static int exceedance_moments(const T* cov, long m, int B, const T* mu, const double* thresh, int L, const double* w, const int* group,
+                              int P, const T* ev, double* work, double* mean_out, double* cov_out, hipStream_t s) {
   const long M = round_up(m, DGP_TILE_HOST);
   const long ws = ex_site_doubles(M, P, L);
   exceedance_prepare<T>(cov, M * M, M + 1, m, B, mu, thresh, L, w, group, P, ev, work, s);
@@ -311,14 +313,48 @@ template void exceedance_prepare<double>(const double*, long, long, long, int, c
                                          int, const double*, double*, hipStream_t);
 template void exceedance_prepare<float>(const float*, long, long, long, int, const float*, const double*, int, const double*, const int*,
                                         int, const float*, double*, hipStream_t);
-template int exceedance_moments<double>(const double*, long, int, const double*, const double*, int, const double*, const int*, int,
-                                        const double*, double*, double*, double*, hipStream_t);
-template int exceedance_moments<float>(const float*, long, int, const float*, const double*, int, const double*, const int*, int,
-                                       const float*, double*, double*, double*, hipStream_t);
 
-int debug_bvn_excess(const double* h, const double* k, const double* rho, long count, double* out, hipStream_t s) {
+// out[i] = Phi2(h_i, k_i; rho_i) - Phi(h_i) Phi(k_i): the pair function of the pass above, pointwise
+static int debug_bvn_excess(const double* h, const double* k, const double* rho, long count, double* out, hipStream_t s) {
   ex_debug_kernel<<<dim3((unsigned)((count + 255) / 256)), 256, 0, s>>>(h, k, rho, count, out);
   return (int)hipGetLastError();
 }
 
 }  // namespace dgp
+
+using namespace dgp;
+
+extern "C" {
+
+size_t dgp_exceedance_moments_workspace_bytes(int64_t m, int ngroups, int nlevels, int batch) {
+  if (!ex_sizes_ok(m, ngroups, nlevels, batch)) return 0;
+  return exceedance_moments_workspace_bytes(m, ngroups, nlevels, batch);
+}
+
+int dgp_exceedance_moments(int dtype, const void* cov, int64_t m, int batch, const void* mu, const double* thresh, int nlevels,
+                           const double* w, const int32_t* group, int ngroups, const void* extra_var, void* work,
+                           size_t work_bytes, double* mean_out, double* cov_out, void* stream) {
+  if (dtype != DGP_F64 && dtype != DGP_F32) return fail(DGP_E_ARG, "dgp_exceedance_moments: dtype must be 0 (f64) or 1 (f32)");
+  if (!cov || !mu || !thresh || !w || !group || !mean_out || !cov_out)
+    return fail(DGP_E_ARG, "dgp_exceedance_moments: null argument");
+  if (!ex_sizes_ok(m, ngroups, nlevels, batch))
+    return fail(DGP_E_ARG,
+                "dgp_exceedance_moments: bad size (1 <= m <= 2^20, 1 <= ngroups <= 65535, 1 <= nlevels <= 64, 1 <= batch <= 1024)");
+  if (!work || work_bytes < exceedance_moments_workspace_bytes(m, ngroups, nlevels, batch))
+    return fail(DGP_E_WORKSPACE, "dgp_exceedance_moments: workspace missing or too small");
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = dtype == DGP_F64
+                     ? exceedance_moments<double>((const double*)cov, m, batch, (const double*)mu, thresh, nlevels, w, group, ngroups,
+                                                  (const double*)extra_var, (double*)work, mean_out, cov_out, s)
+                     : exceedance_moments<float>((const float*)cov, m, batch, (const float*)mu, thresh, nlevels, w, group, ngroups,
+                                                 (const float*)extra_var, (double*)work, mean_out, cov_out, s);
+  return wrap(rc, "dgp_exceedance_moments");
+}
+
+int dgp_debug_bvn_excess(const double* h, const double* k, const double* rho, int64_t count, double* out, void* stream) {
+  if (!h || !k || !rho || !out || count <= 0 || count > (1ll << 31))
+    return fail(DGP_E_ARG, "dgp_debug_bvn_excess: null argument / bad count");
+  return wrap(debug_bvn_excess(h, k, rho, count, out, (hipStream_t)stream), "dgp_debug_bvn_excess");
+}
+
+}  // extern "C"

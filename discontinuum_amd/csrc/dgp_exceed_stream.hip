@@ -21,7 +21,7 @@
 // Repeated calls are bitwise equal and a site's numbers do not depend on its batch; different R regroup the sums over j.
 // The quadrature never runs beside live MFMA accumulators: it reads C back from the panel (L2 / HBM, R M elements).
 #include "dgp_bvn.h"
-#include "dgp_internal.h"
+#include "dgp_plan.h"
 
 namespace dgp {
 
@@ -155,16 +155,19 @@ int exs_chunk(int model, int d, const T* V, long N, long M, int m, int B, const 
 
 }  // namespace
 
-long exceedance_panel_rows(long m, long R) {
+static long exceedance_panel_rows(long m, long R) {
   const long M = round_up(m, DGP_TILE_HOST);
   return R < M ? R : M;
 }
 
+// The exceedance moments with C = K(Xs, Xs) - V^T V produced R rows at a time (R a multiple of 128; the pass uses
+// exceedance_panel_rows(m, R) = min(R, M)) into `panel` (R x M elements per site, site stride pstride) and never stored whole.
+// V, Xst, var (overwritten), wbs, pre_scratch as the prediction leaves them; `work` as for exceedance_moments
 template <typename T>
-int posterior_exceedance_moments(int model, int d, const T* V, long N, long m, int B, const T* Xst, T* var, long wbs,
-                                 const double* theta, const T* mu, const double* thresh, int L, const double* w, const int* group,
-                                 int P, const T* ev, long R, T* panel, long pstride, double* work, double* mean_out, double* cov_out,
-                                 hipStream_t s, void* pre_scratch) {
+static int posterior_exceedance_moments(int model, int d, const T* V, long N, long m, int B, const T* Xst, T* var, long wbs,
+                                        const double* theta, const T* mu, const double* thresh, int L, const double* w,
+                                        const int* group, int P, const T* ev, long R, T* panel, long pstride, double* work,
+                                        double* mean_out, double* cov_out, hipStream_t s, void* pre_scratch) {
   const long M = round_up(m, DGP_TILE_HOST);
   const long ws = (long)(exceedance_moments_workspace_bytes(m, P, L, 1) / sizeof(double));
   R = exceedance_panel_rows(m, R);
@@ -196,11 +199,58 @@ int posterior_exceedance_moments(int model, int d, const T* V, long N, long m, i
   return rc ? rc : (int)hipGetLastError();
 }
 
-template int posterior_exceedance_moments<double>(int, int, const double*, long, long, int, const double*, double*, long, const double*,
-                                                  const double*, const double*, int, const double*, const int*, int, const double*,
-                                                  long, double*, long, double*, double*, double*, hipStream_t, void*);
-template int posterior_exceedance_moments<float>(int, int, const float*, long, long, int, const float*, float*, long, const double*,
-                                                 const float*, const double*, int, const double*, const int*, int, const float*, long,
-                                                 float*, long, double*, double*, double*, hipStream_t, void*);
-
 }  // namespace dgp
+
+using namespace dgp;
+
+// streamed exceedance moments: the prediction's work area, one covariance panel of R x M elements per site, then the moment
+// pass's work area
+static size_t exceed_panel_bytes(const dgp_plan* p, int64_t m, int panel_rows) {
+  return Carve::up(p->elem * (size_t)exceedance_panel_rows((long)m, panel_rows) * (size_t)round_up(m, DGP_TILE_HOST));
+}
+template <typename T>
+static int post_exceed(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const void* mu, const double* thresh, int L,
+                       const double* w, const int32_t* group, int P, const void* ev, int panel_rows, void* work, double* mean_out,
+                       double* cov_out, hipStream_t s) {
+  const size_t pb = exceed_panel_bytes(p, m, panel_rows);
+  T* panel = (T*)((char*)work + predict_layout(p, m).total * (size_t)p->B);
+  double* ex = (double*)((char*)panel + pb * (size_t)p->B);
+  T *V, *Xst, *vpad;
+  long wbs;
+  // the latent mean the prediction also writes (B x m elements) lands in the moment pass's area, which its first launches reset
+  int rc = predict_common<T>(p, theta, Xs, m, work, ex, &V, &Xst, &vpad, &wbs, s);
+  if (rc) return rc;
+  return posterior_exceedance_moments<T>(p->model, p->d, V, p->N, (long)m, p->B, Xst, vpad, wbs, theta, (const T*)mu, thresh, L, w, group,
+                                         P, (const T*)ev, panel_rows, panel, (long)(pb / sizeof(T)), ex, mean_out, cov_out, s, p->pre);
+}
+
+extern "C" {
+
+size_t dgp_posterior_exceedance_moments_workspace_bytes(const dgp_plan* p, int64_t m, int ngroups, int nlevels, int panel_rows) {
+  if (!p || !ex_sizes_ok(m, ngroups, nlevels, p->B) || panel_rows <= 0 || panel_rows % DGP_TILE_HOST != 0) return 0;
+  return (predict_layout(p, m).total + exceed_panel_bytes(p, m, panel_rows)) * (size_t)p->B +
+         exceedance_moments_workspace_bytes(m, ngroups, nlevels, p->B);
+}
+
+int dgp_posterior_exceedance_moments(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const void* mu, const double* thresh,
+                                     int nlevels, const double* w, const int32_t* group, int ngroups, const void* extra_var,
+                                     int panel_rows, void* work, size_t work_bytes, double* mean_out, double* cov_out, void* stream) {
+  const char* where = "dgp_posterior_exceedance_moments";
+  if (!p) return fail(DGP_E_ARG, "null plan");
+  if (!theta || !Xs || !mu || !thresh || !w || !group || !mean_out || !cov_out)
+    return fail(DGP_E_ARG, "dgp_posterior_exceedance_moments: null argument");
+  if (!ex_sizes_ok(m, ngroups, nlevels, p->B))
+    return fail(DGP_E_ARG, "dgp_posterior_exceedance_moments: bad size (1 <= m <= 2^20, 1 <= ngroups <= 65535, 1 <= nlevels <= 64)");
+  if (panel_rows <= 0 || panel_rows % DGP_TILE_HOST != 0)
+    return fail(DGP_E_ARG, "dgp_posterior_exceedance_moments: panel_rows must be a positive multiple of 128");
+  if (int rc = need_factor(p, where, "call dgp_factorize or dgp_fit_step")) return rc;
+  DGP_CHECK_PLAN(p);
+  hipStream_t s = (hipStream_t)stream;
+  int rc = need_work(work, work_bytes, dgp_posterior_exceedance_moments_workspace_bytes(p, m, ngroups, nlevels, panel_rows), where);
+  if (rc || (rc = factor_ok(p, s, where))) return rc;
+  rc = DGP_BY_DTYPE(p, post_exceed<double>(p, theta, Xs, m, mu, thresh, nlevels, w, group, ngroups, extra_var, panel_rows, work, mean_out, cov_out, s),
+                    post_exceed<float>(p, theta, Xs, m, mu, thresh, nlevels, w, group, ngroups, extra_var, panel_rows, work, mean_out, cov_out, s));
+  return wrap(rc, where);
+}
+
+}  // extern "C"

@@ -23,7 +23,7 @@
 // fit step are never touched.  Flops: (P + E) (4/3) N^3 on the matrix cores (2/3 N^3 for a diagonal direction).
 #include "dgp_gemm.h"
 #include "dgp_gemm_dma.h"
-#include "dgp_internal.h"
+#include "dgp_plan.h"
 #include "dgp_models.h"
 #include "dgp_gram_shared.h"
 
@@ -201,13 +201,20 @@ __global__ __launch_bounds__(256) void fisher_reduce_kernel(const double* __rest
 // work area per site: nd + 1 matrices of N x N plan-dtype elements (the nd directions' slots, then V) and
 // (N/64)(N/64 + 1)/2 x nd x nd doubles of tile partials.  D_a lives in G_a's slot until its own product overwrites it, so
 // no separate buffer for the derivative matrix is needed.
-static size_t fisher_align(size_t x) { return (x + 255) & ~(size_t)255; }
 static long fisher_tiles(long N) { return (N / 64) * (N / 64 + 1) / 2; }
 
-size_t fisher_site_bytes(long N, int nd, size_t elem) {
-  return (size_t)(nd + 1) * fisher_align(elem * (size_t)N * (size_t)N) +
-         fisher_align(sizeof(double) * (size_t)fisher_tiles(N) * (size_t)nd * (size_t)nd);
+struct FisherLayout {
+  size_t part, total;  // the matrices come first: slot a at a x Carve::up(elem N^2)
+};
+static FisherLayout fisher_layout(long N, int nd, size_t elem) {
+  FisherLayout L;
+  Carve c;
+  for (int a = 0; a <= nd; ++a) c.take(elem * (size_t)N * (size_t)N);
+  L.part = c.take(sizeof(double) * (size_t)fisher_tiles(N) * (size_t)nd * (size_t)nd);
+  L.total = c.o;
+  return L;
 }
+static size_t fisher_site_bytes(long N, int nd, size_t elem) { return fisher_layout(N, nd, elem).total; }
 
 // the sweep's launch, shared with dgp_sensitivity.hip: slot p of G (slot stride N^2, site stride wbs) <- D_p, p < ntheta.
 // upload = false: the hyperparameters of a batch of more than 8 are already in pre_scratch (an earlier launcher of the same call).
@@ -223,9 +230,11 @@ int fisher_dk(int model, int d, const T* Xt, long N, int n, const double* theta,
   return (int)hipGetLastError();
 }
 
+// F_ab = 1/2 tr(K^^-1 D_a K^^-1 D_b) over the nt kernel directions dK/dtheta_p and `ndiag` diagonal directions diag [B][ndiag][n],
+// from T = L^-1.  `work`: fisher_site_bytes per site; F [B][nt + ndiag][nt + ndiag] doubles.  Reads Xt and T only.
 template <typename T>
-int fisher(int model, int d, const T* Xt, const T* Tm, long N, int n, const double* theta, const T* diag, int ndiag, void* work,
-           double* F, hipStream_t s, Batch bt, void* pre_scratch, void* pre_staging) {
+static int fisher(int model, int d, const T* Xt, const T* Tm, long N, int n, const double* theta, const T* diag, int ndiag, void* work,
+                  double* F, hipStream_t s, Batch bt, void* pre_scratch, void* pre_staging) {
   const int nt = model_ntheta(model, d);
   if (nt < 0) return -2;
   const int nd = nt + ndiag;
@@ -235,7 +244,7 @@ int fisher(int model, int d, const T* Xt, const T* Tm, long N, int n, const doub
   const long slot = N * N;
   T* G = (T*)work;
   T* V = G + (long)nd * slot;
-  double* part = (double*)((char*)work + (size_t)(nd + 1) * fisher_align(sizeof(T) * (size_t)slot));
+  double* part = (double*)((char*)work + fisher_layout(N, nd, sizeof(T)).part);
   const unsigned Bz = (unsigned)bt.B;
   int rc = fisher_dk<T>(model, d, Xt, N, n, theta, G, s, bt, wbs, pre_scratch, pre_staging, true);
   if (rc) return rc;
@@ -260,9 +269,39 @@ int fisher(int model, int d, const T* Xt, const T* Tm, long N, int n, const doub
 
 template int fisher_dk<double>(int, int, const double*, long, int, const double*, double*, hipStream_t, Batch, long, void*, void*, bool);
 template int fisher_dk<float>(int, int, const float*, long, int, const double*, float*, hipStream_t, Batch, long, void*, void*, bool);
-template int fisher<double>(int, int, const double*, const double*, long, int, const double*, const double*, int, void*, double*,
-                            hipStream_t, Batch, void*, void*);
-template int fisher<float>(int, int, const float*, const float*, long, int, const double*, const float*, int, void*, double*,
-                           hipStream_t, Batch, void*, void*);
 
 }  // namespace dgp
+
+using namespace dgp;
+
+#define DGP_FISHER_MAX_DIAG 8
+
+extern "C" {
+
+size_t dgp_fisher_workspace_bytes(const dgp_plan* p, int ndiag) {
+  if (!p || ndiag < 0 || ndiag > DGP_FISHER_MAX_DIAG) return 0;
+  return fisher_site_bytes(p->N, p->ntheta + ndiag, p->elem) * (size_t)p->B;
+}
+
+int dgp_fisher(dgp_plan* p, const double* theta, const void* diag, int ndiag, void* work, size_t work_bytes, double* fisher_out,
+               void* stream) {
+  if (!p) return fail(DGP_E_ARG, "null plan");
+  if (!theta || !fisher_out) return fail(DGP_E_ARG, "dgp_fisher: null argument");
+  if (ndiag < 0 || ndiag > DGP_FISHER_MAX_DIAG) return fail(DGP_E_ARG, "dgp_fisher: ndiag must be 0..8");
+  if (ndiag > 0 && !diag) return fail(DGP_E_ARG, "dgp_fisher: ndiag > 0 needs the diagonal directions");
+  DGP_CHECK_PLAN(p);
+  hipStream_t s = (hipStream_t)stream;
+  int rc = need_factor(p, "dgp_fisher", "call dgp_factorize or dgp_fit_step");
+  if (rc || (rc = need_work(work, work_bytes, dgp_fisher_workspace_bytes(p, ndiag), "dgp_fisher")) || (rc = factor_ok(p, s, "dgp_fisher")))
+    return rc;
+  PreSlot slot(p, s);
+  rc = DGP_BY_DTYPE(
+      p,
+      fisher<double>(p->model, p->d, (const double*)p->Xt, (const double*)p->Tm, p->N, (int)p->n, theta, (const double*)diag, ndiag, work,
+                     fisher_out, s, batch_of<double>(p), p->pre, slot.staging),
+      fisher<float>(p->model, p->d, (const float*)p->Xt, (const float*)p->Tm, p->N, (int)p->n, theta, (const float*)diag, ndiag, work,
+                    fisher_out, s, batch_of<float>(p), p->pre, slot.staging));
+  return wrap(rc, "dgp_fisher");
+}
+
+}  // extern "C"

@@ -32,7 +32,7 @@
 // its single-site plan bitwise under the same nfolds, max_fold and tile selector of beta, and to rounding otherwise.  order / start / group are clamped wherever
 // they index: bad content gives wrong numbers, never an access out of bounds.  Reads T, S, alpha only.
 #include "dgp_common.h"
-#include "dgp_internal.h"
+#include "dgp_plan.h"
 
 namespace dgp {
 
@@ -283,7 +283,6 @@ __global__ __launch_bounds__(256) void inf_finish_kernel(const double* __restric
   }
 }
 
-size_t inf_align(size_t x) { return (x + 255) & ~(size_t)255; }
 int inf_route(long max_fold) { return max_fold <= 1 ? ROUTE_LOO : (max_fold <= INF_SMALL ? ROUTE_LDS : ROUTE_BLOCK); }
 
 template <typename T>
@@ -329,15 +328,22 @@ int inf_chunk(void* ctx, const CvBlocks& cb) {
 
 }  // namespace
 
-InfluenceLayout influence_layout(long N, int B, int n, int d, long Mp, int m, int nfolds, long max_fold, int ngroups, size_t elem) {
+// `work`: the B per-site slices (Xst and Ks filled by pack_x + gram_cross), then the shared areas
+struct InfluenceLayout {
+  size_t Xst, Ks, V, beta, slice;                                   // byte offsets inside a site's slice, and its size
+  size_t resid, var, lpd, part, pmax, bg, cv, minv, panel, z, total;  // byte offsets of the shared areas behind the B slices
+  int nslab, slab_len, chunk;                                       // slabs of test points per fold; folds per chunk (block route)
+  long order;                                                       // block order of the block route
+};
+static InfluenceLayout influence_layout(long N, int B, int n, int d, long Mp, int m, int nfolds, long max_fold, int ngroups, size_t elem) {
   InfluenceLayout L;
-  const size_t nm = inf_align(elem * (size_t)N * (size_t)Mp), Bz = (size_t)B, P = (size_t)ngroups, F = (size_t)nfolds;
-  size_t o = 0;
-  L.Xst = o; o += inf_align(elem * (size_t)Mp * (size_t)d);
-  L.Ks = o; o += nm;
-  L.V = o; o += nm;
-  L.beta = o; o += nm;
-  L.slice = o;
+  const size_t nm = elem * (size_t)N * (size_t)Mp, Bz = (size_t)B, P = (size_t)ngroups, F = (size_t)nfolds;
+  Carve c;
+  L.Xst = c.take(elem * (size_t)Mp * (size_t)d);
+  L.Ks = c.take(nm);
+  L.V = c.take(nm);
+  L.beta = c.take(nm);
+  L.slice = c.o;
   const int route = inf_route(max_fold);
   // slabs of test points per fold: enough (fold, slab) waves to fill the device; a function of (m, nfolds) alone, not of the batch size
   const int chunks = (m + 63) / 64;
@@ -346,29 +352,31 @@ InfluenceLayout influence_layout(long N, int B, int n, int d, long Mp, int m, in
   L.slab_len = (int)round_up((m + nslab - 1) / nslab, 64);
   nslab = (m + L.slab_len - 1) / L.slab_len;
   L.nslab = route == ROUTE_LOO ? nslab : (int)round_up(nslab, 4);  // a workgroup of the other routes takes four slabs of one fold
-  o = Bz * L.slice;
-  L.resid = o; o += inf_align(sizeof(double) * Bz * (size_t)n);
-  L.var = o; o += inf_align(sizeof(double) * Bz * (size_t)n);
-  L.lpd = o; o += inf_align(sizeof(double) * Bz * F);
-  L.part = o; o += inf_align(sizeof(double) * Bz * F * (size_t)L.nslab * P);
-  L.pmax = o; o += inf_align(sizeof(double) * Bz * F * (size_t)L.nslab);
-  L.bg = o; o += inf_align(sizeof(double) * Bz * (size_t)n * P);
-  L.cv = o; o += inf_align(cross_validate_workspace_bytes(N, B, nfolds, max_fold));
-  L.minv = o; o += route == ROUTE_LDS ? inf_align(sizeof(double) * Bz * F * (size_t)(max_fold * max_fold)) : 0;
+  c.o = Bz * L.slice;
+  L.resid = c.take(sizeof(double) * Bz * (size_t)n);
+  L.var = c.take(sizeof(double) * Bz * (size_t)n);
+  L.lpd = c.take(sizeof(double) * Bz * F);
+  L.part = c.take(sizeof(double) * Bz * F * (size_t)L.nslab * P);
+  L.pmax = c.take(sizeof(double) * Bz * F * (size_t)L.nslab);
+  L.bg = c.take(sizeof(double) * Bz * (size_t)n * P);
+  L.cv = c.take(cross_validate_workspace_bytes(N, B, nfolds, max_fold));
+  L.minv = c.take(route == ROUTE_LDS ? sizeof(double) * Bz * F * (size_t)(max_fold * max_fold) : 0);
   L.chunk = route == ROUTE_BLOCK ? cross_validate_chunk_groups(N, B, nfolds, max_fold) : 0;
   L.order = route == ROUTE_BLOCK ? round_up(max_fold, DGP_TILE_HOST) : 0;
-  const size_t pz = inf_align(sizeof(double) * (size_t)L.chunk * Bz * (size_t)L.order * (size_t)Mp);
-  L.panel = o; o += pz;
-  L.z = o; o += pz;
-  L.total = o;
+  const size_t pz = sizeof(double) * (size_t)L.chunk * Bz * (size_t)L.order * (size_t)Mp;
+  L.panel = c.take(pz);
+  L.z = c.take(pz);
+  L.total = c.o;
   return L;
 }
 
+// The exact change of every period sum (and, for a linear target, of its variance) when a fold of observations is deleted at fixed
+// hyperparameters.  Reads Tm, S (when valid, else null) and alpha only; every result is double.
 template <typename T>
-int deletion_influence(const T* Tm, const T* S, const T* alpha, long N, int n, long Mp, int m, const int* order, const int* start,
-                       int nfolds, long max_fold, int mode, const double* a, const double* scale, const int* group, int ngroups,
-                       const double* inv_sd, void* work, const InfluenceLayout& L, double* dload, double* dvar, double* shift,
-                       int* info, hipStream_t s, Batch bt) {
+static int deletion_influence(const T* Tm, const T* S, const T* alpha, long N, int n, long Mp, int m, const int* order, const int* start,
+                              int nfolds, long max_fold, int mode, const double* a, const double* scale, const int* group, int ngroups,
+                              const double* inv_sd, void* work, const InfluenceLayout& L, double* dload, double* dvar, double* shift,
+                              int* info, hipStream_t s, Batch bt) {
   const int route = inf_route(max_fold);
   const unsigned Bz = (unsigned)bt.B;
   if ((long)L.nslab / 4 * nfolds > 0x7fffffffL || ngroups > 65535) return -2;  // (grid sizes)
@@ -445,11 +453,63 @@ int deletion_influence(const T* Tm, const T* S, const T* alpha, long N, int n, l
   return (int)hipGetLastError();
 }
 
-template int deletion_influence<double>(const double*, const double*, const double*, long, int, long, int, const int*, const int*, int,
-                                        long, int, const double*, const double*, const int*, int, const double*, void*,
-                                        const InfluenceLayout&, double*, double*, double*, int*, hipStream_t, Batch);
-template int deletion_influence<float>(const float*, const float*, const float*, long, int, long, int, const int*, const int*, int, long,
-                                       int, const double*, const double*, const int*, int, const double*, void*, const InfluenceLayout&,
-                                       double*, double*, double*, int*, hipStream_t, Batch);
-
 }  // namespace dgp
+
+using namespace dgp;
+
+static bool influence_sizes_ok(const dgp_plan* p, int64_t m, int nfolds, int64_t max_fold, int ngroups) {
+  return p && m >= 1 && m <= (1 << 20) && nfolds >= 1 && nfolds <= p->n && max_fold >= 1 && max_fold <= p->n && ngroups >= 1 &&
+         ngroups <= 65535;
+}
+static InfluenceLayout influence_layout_of(const dgp_plan* p, int64_t m, int nfolds, int64_t max_fold, int ngroups) {
+  return influence_layout(p->N, p->B, (int)p->n, p->d, round_up(m, DGP_TILE_HOST), (int)m, nfolds, max_fold, ngroups, p->elem);
+}
+template <typename T>
+static int influence(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const int32_t* order, const int32_t* start, int nfolds,
+                     int64_t max_fold, int mode, const double* a, const double* scale, const int32_t* group, int ngroups,
+                     const double* inv_sd, void* work, double* dload, double* dvar, double* shift, int32_t* info, hipStream_t s) {
+  const InfluenceLayout L = influence_layout_of(p, m, nfolds, max_fold, ngroups);
+  char* w = (char*)work;
+  const int rc = cross<T>(p, theta, Xs, m, w + L.Xst, w + L.Ks, s, (long)(L.slice / sizeof(T)));
+  if (rc) return rc;
+  const void* S = p->have_inverse ? p->S : nullptr;  // as dgp_cross_validate: read when the last step left it valid
+  return deletion_influence<T>((const T*)p->Tm, (const T*)S, (const T*)p->alpha, p->N, (int)p->n, round_up(m, DGP_TILE_HOST), (int)m, order,
+                               start, nfolds, max_fold, mode, a, scale, group, ngroups, inv_sd, work, L, dload, dvar, shift, info, s,
+                               batch_of<T>(p));
+}
+
+extern "C" {
+
+size_t dgp_deletion_influence_workspace_bytes(const dgp_plan* p, int64_t m, int nfolds, int64_t max_fold, int ngroups) {
+  if (!influence_sizes_ok(p, m, nfolds, max_fold, ngroups)) return 0;
+  return influence_layout_of(p, m, nfolds, max_fold, ngroups).total;
+}
+
+int dgp_deletion_influence(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const int32_t* order, const int32_t* start,
+                           int nfolds, int64_t max_fold, int mode, const double* a, const double* scale, const int32_t* group, int ngroups,
+                           const double* inv_sd, void* work, size_t work_bytes, double* dload, double* dvar, double* shift,
+                           int32_t* info, void* stream) {
+  const char* where = "dgp_deletion_influence";
+  if (!p) return fail(DGP_E_ARG, "null plan");
+  if (!theta || !Xs || !order || !start || !a || !scale || !group || !dload || !info)
+    return fail(DGP_E_ARG, "dgp_deletion_influence: null argument");
+  if (!influence_sizes_ok(p, m, nfolds, max_fold, ngroups))
+    return fail(DGP_E_ARG, "dgp_deletion_influence: bad size (1 <= m <= 2^20, 1 <= nfolds <= n, 1 <= max_fold <= n, 1 <= ngroups <= 65535)");
+  if (mode != 0 && mode != 1) return fail(DGP_E_ARG, "dgp_deletion_influence: mode must be 0 (linear) or 1 (log)");
+  if (mode == 1 && dvar) return fail(DGP_E_ARG, "dgp_deletion_influence: the variance change is exact for mode 0 only (dvar_dev must be NULL)");
+  if (shift && !inv_sd) return fail(DGP_E_ARG, "dgp_deletion_influence: shift_dev needs inv_sd_dev");
+  DGP_CHECK_PLAN(p);
+  hipStream_t s = (hipStream_t)stream;
+  int rc = need_factor(p, where, "call dgp_factorize or dgp_fit_step");
+  if (rc || (rc = need_work(work, work_bytes, dgp_deletion_influence_workspace_bytes(p, m, nfolds, max_fold, ngroups), where)) ||
+      (rc = factor_ok(p, s, where)))
+    return rc;
+  rc = DGP_BY_DTYPE(p,
+                    influence<double>(p, theta, Xs, m, order, start, nfolds, max_fold, mode, a, scale, group, ngroups, inv_sd, work, dload,
+                                      dvar, shift, info, s),
+                    influence<float>(p, theta, Xs, m, order, start, nfolds, max_fold, mode, a, scale, group, ngroups, inv_sd, work, dload,
+                                     dvar, shift, info, s));
+  return wrap(rc, where);
+}
+
+}  // extern "C"

@@ -8,6 +8,16 @@
 namespace dgp {
 
 inline long round_up(long n, long q) { return (n + q - 1) / q * q; }
+// The one workspace carver: every *_layout() takes its areas in order, each rounded up to 256 bytes; `o` is the running total.
+struct Carve {
+  size_t o = 0;
+  static size_t up(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+  size_t take(size_t bytes) {
+    const size_t at = o;
+    o += up(bytes);
+    return at;
+  }
+};
 
 // A batched plan carries B <= DGP_MAX_BATCH_SITES sites in lockstep: every fit-step kernel is launched once with
 // gridDim.z = B and finds its site's buffers at blockIdx.z * stride (workspace buffers: `ws` elements of the plan's
@@ -229,58 +239,15 @@ int posterior_cov_panel(const T* V, long N, long M, T* panel, long row0, long ro
 template <typename T>
 int sample_draws(const T* L, long M, const T* Z, long Q, const T* mean, int m, int ndraw, T* out, hipStream_t s);
 
-// ---- dgp_aggregate.hip: exact mean / covariance of period sums of exp(s f + t) (mode 1) or s f + t (mode 0), f ~ N(mu, C)
-size_t period_moments_workspace_bytes(long m, int P, int B);
-template <typename T>
-int period_moments(int mode, const T* cov, long m, int B, const T* mu, const double* scale2, const double* w, const int* group,
-                   int P, const T* ev, double* work, double* mean_out, double* cov_out, hipStream_t s);
-// the same moments with C = K(Xs, Xs) - V^T V never stored: V (N x M), the test points' SoA coordinates Xst (d x M) and their
-// predicted variance var (M) as the prediction leaves them in its work area (site stride wbs elements); `work` as above
-// (period_moments_workspace_bytes); pre_scratch: the plan's hyperparameter scratch, already filled by this call's gram_cross
-template <typename T>
-int posterior_period_moments(int mode, int model, int d, const T* V, long N, long m, int B, const T* Xst, const T* var, long wbs,
-                             const double* theta, const T* mu, const double* scale2, const double* w, const int* group, int P,
-                             const T* ev, double* work, double* mean_out, double* cov_out, hipStream_t s, void* pre_scratch);
-
-// ---- dgp_window.hip: exact mean / covariance of rolling-window means W f (mode 0) or W exp(f) (mode 1), f ~ N(mu, C); windows
-// [lo_i, hi_i) per site ([B][q], non-decreasing), weights a [B][m] or null; mean_out [B][q], cov_out [B][Q][Q] in the layout of
-// posterior_cov (Q = round_up(q, 128)); `work`: window_moments_workspace_bytes
-size_t window_moments_workspace_bytes(long m, long q, int B);
-template <typename T>
-int window_moments(int mode, const T* cov, long m, int B, const T* mu, const double* scale2, const double* a, const int* lo,
-                   const int* hi, long q, double* work, double* mean_out, double* cov_out, hipStream_t s);
-
 // ---- dgp_exceed.hip: exact mean / covariance of the counts sum_{i in g} w_i 1[f_i > u_il], f ~ N(mu, C), per level l.  thresh
 // [B][L][m] in model space; mean_out [B][L][P], cov_out [B][L][P][P]; `work`: exceedance_moments_workspace_bytes
 size_t exceedance_moments_workspace_bytes(long m, int P, int L, int B);
-template <typename T>
-int exceedance_moments(const T* cov, long m, int B, const T* mu, const double* thresh, int L, const double* w, const int* group,
-                       int P, const T* ev, double* work, double* mean_out, double* cov_out, hipStream_t s);
 // the passes before and after the pairs pass, for dgp_exceed_stream.hip: init + prep (C_jj of site z at diag[z dsite + j dstep]),
 // and the reduce pass of the levels l0 .. l0 + LC
 template <typename T>
 void exceedance_prepare(const T* diag, long dsite, long dstep, long m, int B, const T* mu, const double* thresh, int L, const double* w,
                         const int* group, int P, const T* ev, double* work, hipStream_t s);
 void exceedance_reduce(long M, int B, int P, int L, int l0, int LC, double* work, double* mean_out, double* cov_out, hipStream_t s);
-// ---- dgp_exceed_stream.hip: the same moments with C = K(Xs, Xs) - V^T V produced R rows at a time (R a multiple of 128; the
-// pass uses exceedance_panel_rows(m, R) = min(R, M)) into `panel` (R x M elements per site, site stride pstride) and never
-// stored whole.  V, Xst, var (overwritten), wbs, pre_scratch as for posterior_period_moments; `work` as for exceedance_moments
-long exceedance_panel_rows(long m, long R);
-template <typename T>
-int posterior_exceedance_moments(int model, int d, const T* V, long N, long m, int B, const T* Xst, T* var, long wbs,
-                                 const double* theta, const T* mu, const double* thresh, int L, const double* w, const int* group,
-                                 int P, const T* ev, long R, T* panel, long pstride, double* work, double* mean_out, double* cov_out,
-                                 hipStream_t s, void* pre_scratch);
-// out[i] = Phi2(h_i, k_i; rho_i) - Phi(h_i) Phi(k_i): the pair function of the pass above, pointwise
-int debug_bvn_excess(const double* h, const double* k, const double* rho, long count, double* out, hipStream_t s);
-
-// ---- dgp_design.hip: the expected reduction of Var(L_p) by one more sample on each day c, after `nrows` conditioning rows
-// (rows [B][nrows][m], null when nrows == 0; a [B][m] the A_i; ov: the candidates' noise variance or null).  gain_out [B][P][m],
-// var_out [B][m]; `work`: sample_value_workspace_bytes
-size_t sample_value_workspace_bytes(long m, int P, int K, int B);
-template <typename T>
-int sample_value(const T* cov, long m, int B, const double* a, const double* scale2, const int* group, int P, const T* ov,
-                 const double* rows, int nrows, int K, double* work, double* gain_out, double* var_out, hipStream_t s);
 
 // ---- dgp_terms.hip: the posterior of the covariance's additive parts (C = model_nterms).  Ks / V: N x (C Mp) row-major, term c
 // of test point j in column c Mp + j; kss: C Mp; part: terms_partials(C, Mp) elements; mean [B][C][m], cov [B][C (C + 1) / 2][m]
@@ -358,54 +325,15 @@ __device__ __forceinline__ void cv_bounds(const int* __restrict__ start, int g, 
 __device__ __forceinline__ int cv_index(const int* __restrict__ order, int p, int n) { return min(max(order[p], 0), n - 1); }
 #endif
 
-// ---- dgp_fisher.hip: F_ab = 1/2 tr(K^^-1 D_a K^^-1 D_b) over the nt kernel directions dK/dtheta_p and `ndiag` diagonal
-// directions diag [B][ndiag][n], from T = L^-1.  `work`: fisher_site_bytes per site; F [B][nt + ndiag][nt + ndiag] doubles.
-// Reads Xt and T only.
-size_t fisher_site_bytes(long N, int nd, size_t elem);
-template <typename T>
-int fisher(int model, int d, const T* Xt, const T* Tm, long N, int n, const double* theta, const T* diag, int ndiag, void* work,
-           double* F, hipStream_t s, Batch bt, void* pre_scratch, void* pre_staging);
-// its first pass alone: D_p = dK/dtheta_p for every p < ntheta, slot p (N^2 elements) of G at site stride wbs
+// ---- dgp_fisher.hip: the Fisher information's first pass alone (for dgp_sensitivity.hip): D_p = dK/dtheta_p for every p < ntheta,
+// slot p (N^2 elements) of G at site stride wbs
 template <typename T>
 int fisher_dk(int model, int d, const T* Xt, long N, int n, const double* theta, T* G, hipStream_t s, Batch bt, long wbs,
               void* pre_scratch, void* pre_staging, bool upload);
 
-// ---- dgp_sensitivity.hip: dmean [B][nt + ndiag + nrhs][m] and dvar [B][nt + ndiag][m] (null: not wanted) = the Jacobians of the
-// posterior mean / variance at the m test points with respect to the nt kernel directions, `ndiag` diagonal directions diag
-// [B][ndiag][n] and `nrhs` right-hand-side columns rhs [B][nrhs][n], from T = L^-1 and alpha.  `work`: a sens_layout slice per site,
-// its Xst (the test points, SoA, padded to Mp) and Ks (K(X, X*), N x Mp) already filled.  Reads Xt, T and alpha only.
-#define SENS_SPLIT 32  // row slabs of its column reductions
-struct SensLayout {
-  size_t Xst, D, Ks, V, beta, G, pc, pg, pq, total;  // byte offsets into a site's slice
-};
-SensLayout sens_layout(long N, long Mp, int d, int nt, int ndiag, int nrhs, size_t elem);
-// its beta = T^T V alone (V, beta: N x Mp row-major at site stride wbs): 128 x 128 tiles, 64 x 64 ones while the launch has too few
-// (sens_small_tiles: lauum's rule and selector)
-inline bool sens_small_tiles(long N, long Mp, const Batch& bt) {
-  return (N / DGP_TILE_HOST) * (Mp / DGP_TILE_HOST) * bt.B <= bt.tuning().lauum64_max_tiles;
-}
+// ---- dgp_sensitivity.hip: its beta = T^T V alone (for dgp_influence.hip; V, beta: N x Mp row-major at site stride wbs)
 template <typename T>
 int sens_beta(const T* Tm, long N, const T* V, long Mp, T* beta, hipStream_t s, Batch bt, long wbs);
-template <typename T>
-int predict_sensitivity(int model, int d, const T* Xt, const T* Tm, const T* alpha, long N, int n, const double* theta, long Mp, int m,
-                        const T* diag, int ndiag, const T* rhs, int nrhs, void* work, const SensLayout& L, double* dmean, double* dvar,
-                        hipStream_t s, Batch bt, void* pre_scratch);
-
-// ---- dgp_influence.hip: the exact change of every period sum (and, for a linear target, of its variance) when a fold of
-// observations is deleted at fixed hyperparameters.  `work`: an influence_layout; its per-site slices' Xst and Ks are already
-// filled (pack_x + gram_cross).  Reads Tm, S (when valid, else null) and alpha only; every result is double.
-struct InfluenceLayout {
-  size_t Xst, Ks, V, beta, slice;                                   // byte offsets inside a site's slice, and its size
-  size_t resid, var, lpd, part, pmax, bg, cv, minv, panel, z, total;  // byte offsets of the shared areas behind the B slices
-  int nslab, slab_len, chunk;                                       // slabs of test points per fold; folds per chunk (block route)
-  long order;                                                       // block order of the block route
-};
-InfluenceLayout influence_layout(long N, int B, int n, int d, long Mp, int m, int nfolds, long max_fold, int ngroups, size_t elem);
-template <typename T>
-int deletion_influence(const T* Tm, const T* S, const T* alpha, long N, int n, long Mp, int m, const int* order, const int* start,
-                       int nfolds, long max_fold, int mode, const double* a, const double* scale, const int* group, int ngroups,
-                       const double* inv_sd, void* work, const InfluenceLayout& L, double* dload, double* dvar, double* shift,
-                       int* info, hipStream_t s, Batch bt);
 
 // ---- dgp_censored.hip: censored rows (Tobit likelihood) by the Laplace approximation -- a GP regression on pseudo-data (r~, n~).
 // fp64 plans, single-site or batched (blockIdx.z = site, ragged sizes through site_n).  The caller's work area is a
@@ -449,18 +377,6 @@ CensoredLayout censored_layout(long N, long n, int B = 1);
 // `upper` 2 is a bad side value and both passes give the bits they gave before brackets existed
 int censored_terms(const double* f, const double* y, const int* side, const double* v, const double* m, int n, int init, int it,
                    char* work, const CensoredLayout& L, hipStream_t s, Batch bt = Batch(), const double* upper = nullptr);
-// after the factorisation at (r~, n~) left `anew` in the plan: proposal, line search, f and the work area's a updated in place
-// (Newton iteration `it`, 1-based; frozen sites untouched)
-int censored_newton_update(double* f, const double* y, const int* side, const double* v, const double* m, const double* anew, int n,
-                           int it, double tol, char* work, const CensoredLayout& L, hipStream_t s, Batch bt = Batch(),
-                           const double* upper = nullptr);
-// f = m + r~ - n~ o alpha for the sites without a censored row
-int censored_mode(double* f, const double* m, const double* alpha, int n, char* work, const CensoredLayout& L, hipStream_t s,
-                  Batch bt = Batch());
-int censored_weights(const double* alpha, int n, long N, char* work, const CensoredLayout& L, hipStream_t s,
-                     Batch bt = Batch());  // w = n~ o t
-int censored_result(const double* alpha, const int* side, const double* wts, int n, int with_grad, double* out, double* dr, char* work,
-                    const CensoredLayout& L, hipStream_t s, Batch bt = Batch());
 // dtheta[p] (+)= sum_ij u_i dK_ij/dtheta_p alpha_j per site (dtheta at site stride dstride); u, alpha and the partials
 // (gram_grad_partials(N) elements) at the site strides us / as / ps.  pre_scratch / upload / staging as for gram_grad (a batch of
 // more than 8).  Reads Xt, u, alpha only.
@@ -468,92 +384,5 @@ template <typename T>
 int gram_bilinear(int model, int d, const T* Xt, long N, int n, const double* theta, const T* u, const T* alpha, T* partials,
                   T* dtheta, int accumulate, hipStream_t s, Batch bt = Batch(), long us = 0, long as = 0, long ps = 0, long dstride = 0,
                   void* pre_scratch = nullptr, bool upload = false, void* pre_staging = nullptr);
-// out [4][count]: log Phi(z), h = phi / Phi, h (z + h), h [1 - (z + h)(z + 2 h)]
-int debug_censored_terms(const double* z, long count, double* out, hipStream_t s);
-// out [4][count]: log P, sigma g, W v, sigma^3 d3 of the bracket [za, za + delta]
-int debug_interval_terms(const double* za, const double* delta, long count, double* out, hipStream_t s);
-
-// ---- dgp_censored_cv.hip: cross-validation of a censored fit by cavity folds, from the factorisation of the pseudo-data system
-// at the mode `f`.  fp64, one site.  out [LCV_PLANES][n] (== DGP_LCV_* of dgp_hip.h), info [ngroups]; folds as for cross_validate.
-enum { LCV_MU = 0, LCV_VAR, LCV_LPD, LCV_PLO, LCV_PHI, LCV_DLP, LCV_TILT, LCV_PLANES };
-// what the terms pass found, before any other launch: a bad side value (without / with `upper`), a bad bracket
-enum { LCV_E_SIDE_NO_UPPER = -100, LCV_E_SIDE = -101, LCV_E_BRACKET = -102 };
-struct LaplaceCvLayout {
-  size_t cen, resid, var, lpd, Ks, V, kss, mean, svar, part, cvw, ginv, h, total;  // byte offsets into the work area
-  long route_group, M;  // the bound handed to cross_validate (1: leave-one-out; else >= 65: its block route) and the block order
-  int C;                // folds per chunk of the block route
-};
-LaplaceCvLayout laplace_cv_layout(long N, long n, int ngroups, long max_group);
-// first the terms pass (W, g at f into the work area; reads its sums back, which synchronises the stream: 0, a HIP error or LCV_E_*),
-// then everything else, asynchronous on the stream
-int laplace_cv_terms(long N, int n, const double* y, const double* mean, const double* noise, const int* side, const double* upper,
-                     const double* f, char* work, const LaplaceCvLayout& L, hipStream_t s);
-int laplace_cross_validate(int model, int d, const double* Xt, const double* Tm, const double* alpha, long N, int n, const double* theta,
-                           const double* y, const double* noise, const int* side, const double* upper,
-                           const double* f, const int* order, const int* start, int ngroups, double shift, char* work,
-                           const LaplaceCvLayout& L, double* out, int* info, hipStream_t s, Batch bt, void* pre_scratch,
-                           void* pre_staging);
-
-// ---- dgp_ep.hip: censored rows by expectation propagation -- Gaussian sites (y~, n~) found by parallel sweeps, each ONE
-// factorisation of the pseudo-data system plus O(n) passes and the diagonal of the inverse.  fp64, one site.  The work area is an
-// EpLayout: a CensoredLayout first (the terms pass at f = m validates the rows and gives the cold start; its rt holds r~, its
-// `out` the result row of the sweep's factorisation), then the proposals, the previous means, k and the partials.
-#define EP_PART 8  // doubles per workgroup of the block partials
-enum {
-  EP_ST_DMU = 0,  // max |mu - mu_prev| of the sweep (first sweep: max v |nu' - nu~|); inf when the factorisation failed
-  EP_ST_DTAU,     // max v |tau' - tau~|
-  EP_ST_CAPPED,   // proposals at the cap
-  EP_ST_HELD,     // rows held back by the guard (v_c <= 0 or 1 - W v_c <= 0)
-  EP_ST_NCENS,
-  EP_ST_DONE,     // 0: the sweeps go on; k > 0: ended in sweep k (converged, or not positive definite)
-  EP_ST_INFO,     // DGP_OUT_INFO of the sweep's factorisation
-  EP_ST_CONV,     // 1: both tests passed
-  EP_ST_CORR,     // NLL_EP - NLL_engine (ep_result)
-  EP_ST_LEN = 16
-};
-struct EpLayout {
-  CensoredLayout cen;
-  size_t yprop, nprop, muprev, kdiag, kpart, part, status, total;  // byte offsets
-  int nchunk, nblk;
-};
-EpLayout ep_layout(long N, long n);
-// the sites before the first sweep, after censored_terms(f = m, init) has filled L.cen: cold != 0: every censored row from the
-// Laplace terms at m; else the caller's (a row without a usable site starts cold).  Rows of side 0: (y, v).  Writes r~ to L.cen.rt.
-int ep_init(const double* y, const int* side, const double* v, const double* m, double* yt, double* nt, int n, int cold, char* work,
-            const EpLayout& L, hipStream_t s);
-// k_i = sum_{j >= i} T_ji^2, i < n, from the row-major lower triangle T = L^-1 (leading dimension N)
-int ep_diag(const double* Tm, long N, int n, double* k, char* work, const EpLayout& L, hipStream_t s);
-// after the factorisation at (r~, n~) left T and alpha in the plan and its result row in L.cen.out: k, proposals, test, status; the
-// proposals replace the sites (and r~) only when the sweep neither converged nor is the last
-int ep_sweep(const double* Tm, long N, const double* alpha, const double* y, const int* side, const double* v, const double* m,
-             const double* upper, double* yt, double* nt, int n, int sweep, int last, double tol, double damping, char* work,
-             const EpLayout& L, hipStream_t s);
-// out[DGP_OUT_NLL] += NLL_EP - NLL_engine (out null: not wanted) from alpha and L.kdiag; cavities and log Z^ (n doubles each, nullable)
-int ep_result(const double* alpha, const double* y, const int* side, const double* v, const double* upper, const double* yt,
-              const double* nt, int n, double* out, double* cav_mean, double* cav_var, double* logz, char* work, const EpLayout& L,
-              hipStream_t s);
-
-// ---- dgp_loo.hip: the leave-one-out predictive likelihood L_LOO = -elpd of cross_validate("loo") and its gradient, from S = K^^-1
-// and alpha as a fit step leaves them.  fp64, single-site or batched.  The work area holds one SLICE per site that mirrors the plan's
-// site (same size, same offsets: F where the plan has A, G where it has T, 2 M where it has S, a zero vector where it has alpha, the
-// contraction's partials where it has its own -- gram_grad addresses all of them at ONE site stride), then the sites' vectors, then
-// the step's own result rows.
-struct LooLayout {
-  size_t slice, F, G, M, zero, gpart;          // a site's slice and the byte offsets inside it
-  size_t w, c, b, negb, spart, part, vec;      // byte offsets inside a site's vectors, and their size
-  size_t vecs, out0, total;                    // byte offsets of the vectors and of the scratch result rows [B][DGP_OUT_LEN]
-  int nblk;                                    // workgroups per site of the row passes
-};
-LooLayout loo_layout(long N, int B, size_t site_bytes, size_t offA, size_t offT, size_t offS, size_t offalpha, size_t offgpart);
-// out2 [B][2] = (L_LOO, info): info = the factorisation's status `info` ([0] of a site's block) if non-zero, else the 1-based index of
-// the first row whose k_i is not a positive finite number (0: none); the value is NaN unless info == 0.  Reads S and alpha only.
-int loo_value(const double* S, const double* alpha, const int* info, long N, int n, char* work, const LooLayout& L, double* out2,
-              hipStream_t s, Batch bt);
-// after fit_step(with_grad) wrote its result rows to work + L.out0: the LOO result rows `out` (NLL = L_LOO, DTHETA and the reduced
-// slots those of L_LOO; QUAD, LOGDET, INFO the step's own unless a row is bad), dr = b, dnoise.  wts: the plan's dr weights or null.
-// Reads Xt, S and alpha only; the step's Gram build must have left theta in pre_scratch (a batch of more than 8).
-int loo_gradient(int model, int d, const double* Xt, const double* S, const double* alpha, long N, int n, const double* theta,
-                 const double* wts, char* work, const LooLayout& L, double* out, double* dr, double* dnoise, hipStream_t s, Batch bt,
-                 void* pre_scratch);
 
 }  // namespace dgp

@@ -23,7 +23,7 @@
 // the batch it is in.
 #include "../../include/dgp_hip.h"
 #include "dgp_gemm_dma.h"
-#include "dgp_internal.h"
+#include "dgp_plan.h"
 
 namespace dgp {
 
@@ -31,27 +31,39 @@ namespace dgp {
 #define LOO_PART 8  // doubles per workgroup of the block partials: [0] sum of the summands, [1] first bad row + 1 (0: none);
                     // [2..5] sum b, sum b w0, sum b w1, sum dnoise
 
-LooLayout loo_layout(long N, int B, size_t site_bytes, size_t offA, size_t offT, size_t offS, size_t offalpha, size_t offgpart) {
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+// The work area holds one SLICE per site that mirrors the plan's site (same size, same offsets: F where the plan has A, G where it
+// has T, 2 M where it has S, a zero vector where it has alpha, the contraction's partials where it has its own -- gram_grad
+// addresses all of them at ONE site stride), then the sites' vectors, then the step's own result rows.  value_only: no slices.
+struct LooLayout {
+  size_t slice, F, G, M, zero, gpart;          // a site's slice and the byte offsets inside it
+  size_t w, c, b, negb, spart, part, vec;      // byte offsets inside a site's vectors, and their size
+  size_t vecs, out0, total;                    // byte offsets of the vectors and of the scratch result rows [B][DGP_OUT_LEN]
+  int nblk;                                    // workgroups per site of the row passes
+};
+static LooLayout loo_layout(const dgp_plan* p, bool value_only) {
+  const Layout P = layout(p);
+  const size_t N = (size_t)p->N, B = (size_t)p->B;
   LooLayout L;
-  L.slice = site_bytes;
-  L.F = offA;
-  L.G = offT;
-  L.M = offS;
-  L.zero = offalpha;
-  L.gpart = offgpart;
+  L.slice = value_only ? 0 : p->site_bytes;
+  L.F = P.A;
+  L.G = P.Tm;
+  L.M = P.S;
+  L.zero = P.alpha;
+  L.gpart = P.gpart;
   L.nblk = (int)((N + 255) / 256);
-  size_t o = 0;
-  L.w = o; o += up(sizeof(double) * (size_t)N);
-  L.c = o; o += up(sizeof(double) * (size_t)N);
-  L.b = o; o += up(sizeof(double) * (size_t)N);
-  L.negb = o; o += up(sizeof(double) * (size_t)N);
-  L.spart = o; o += up(sizeof(double) * (size_t)solve_partials(N));
-  L.part = o; o += up(sizeof(double) * (size_t)L.nblk * LOO_PART);
-  L.vec = o;
-  L.vecs = (size_t)B * site_bytes;
-  L.out0 = L.vecs + (size_t)B * L.vec;
-  L.total = L.out0 + up(sizeof(double) * (size_t)B * DGP_OUT_LEN);
+  Carve v;  // a site's vectors
+  L.w = v.take(sizeof(double) * N);
+  L.c = v.take(sizeof(double) * N);
+  L.b = v.take(sizeof(double) * N);
+  L.negb = v.take(sizeof(double) * N);
+  L.spart = v.take(sizeof(double) * (size_t)solve_partials(p->N));
+  L.part = v.take(sizeof(double) * (size_t)L.nblk * LOO_PART);
+  L.vec = v.o;
+  L.vecs = B * L.slice;
+  Carve c;
+  c.o = L.vecs + B * L.vec;
+  L.out0 = c.take(sizeof(double) * B * DGP_OUT_LEN);
+  L.total = c.o;
   return L;
 }
 
@@ -268,7 +280,7 @@ static int loo_terms(const double* S, const double* alpha, long N, int n, char* 
   return (int)hipGetLastError();
 }
 
-int loo_value(const double* S, const double* alpha, const int* info, long N, int n, char* work, const LooLayout& L, double* out2,
+static int loo_value(const double* S, const double* alpha, const int* info, long N, int n, char* work, const LooLayout& L, double* out2,
               hipStream_t s, Batch bt) {
   int rc;
   if ((rc = loo_terms(S, alpha, N, n, work, L, s, bt))) return rc;
@@ -278,7 +290,7 @@ int loo_value(const double* S, const double* alpha, const int* info, long N, int
   return (int)hipGetLastError();
 }
 
-int loo_gradient(int model, int d, const double* Xt, const double* S, const double* alpha, long N, int n, const double* theta,
+static int loo_gradient(int model, int d, const double* Xt, const double* S, const double* alpha, long N, int n, const double* theta,
                  const double* wts, char* work, const LooLayout& L, double* out, double* dr, double* dnoise, hipStream_t s, Batch bt,
                  void* pre_scratch) {
   const int nt = model_ntheta(model, d);
@@ -316,3 +328,55 @@ int loo_gradient(int model, int d, const double* Xt, const double* S, const doub
 }
 
 }  // namespace dgp
+
+using namespace dgp;
+
+// ---- the entries: dgp_fit_step's launches, untouched, into a scratch result row, then the passes that read the S and alpha it
+// left.  The plan's A / T / S / z / alpha stay as the step left them.
+static const char* const LOO_F64 =
+    "dgp_loo_*: the leave-one-out objective needs a float64 plan (its bilinear gradient pass exists for float64 only: fp32 plans are "
+    "not supported)";
+
+extern "C" {
+
+size_t dgp_loo_workspace_bytes(const dgp_plan* p) {
+  if (!p || p->dtype != DGP_F64) return 0;
+  return loo_layout(p, false).total;
+}
+size_t dgp_loo_value_workspace_bytes(const dgp_plan* p) {
+  if (!p || p->dtype != DGP_F64) return 0;
+  return loo_layout(p, true).total;
+}
+
+int dgp_loo_fit_step(dgp_plan* p, const double* theta, const void* r, const void* noise, void* work, size_t work_bytes, void* out,
+                     void* dr, void* dnoise, void* stream) {
+  if (!p) return fail(DGP_E_ARG, "null plan");
+  if (p->dtype != DGP_F64) return fail(DGP_E_ARG, LOO_F64);
+  DGP_CHECK_PLAN(p);
+  if (!theta || !r || !noise || !out) return fail(DGP_E_ARG, "dgp_loo_fit_step: null argument");
+  if (!p->have_inputs) return fail(DGP_E_STATE, "dgp_loo_fit_step: call dgp_set_inputs first");
+  int rc = need_work(work, work_bytes, dgp_loo_workspace_bytes(p), "dgp_loo_fit_step");
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const LooLayout L = loo_layout(p, false);
+  rc = fit_step<double>(p, theta, r, noise, (char*)work + L.out0, dr, dnoise, 1, s);
+  if (rc) return wrap(rc, "dgp_loo_fit_step");
+  rc = loo_gradient(p->model, p->d, (const double*)p->Xt, (const double*)p->S, (const double*)p->alpha, p->N, (int)p->n, theta,
+                    (const double*)p->dr_w, (char*)work, L, (double*)out, (double*)dr, (double*)dnoise, s, batch_of<double>(p), p->pre);
+  return wrap(rc, "dgp_loo_fit_step");
+}
+
+int dgp_loo_value(dgp_plan* p, void* work, size_t work_bytes, void* out2, void* stream) {
+  if (!p) return fail(DGP_E_ARG, "null plan");
+  if (p->dtype != DGP_F64) return fail(DGP_E_ARG, LOO_F64);
+  DGP_CHECK_PLAN(p);
+  if (!out2) return fail(DGP_E_ARG, "dgp_loo_value: null argument");
+  if (!p->have_factor || !p->have_inverse)
+    return fail(DGP_E_STATE, "dgp_loo_value: needs the K^^-1 a fit step leaves in the plan (dgp_fit_step or dgp_loo_fit_step; dgp_factorize does not form it)");
+  if (int rc = need_work(work, work_bytes, dgp_loo_value_workspace_bytes(p), "dgp_loo_value")) return rc;
+  const int rc = loo_value((const double*)p->S, (const double*)p->alpha, p->info, p->N, (int)p->n, (char*)work, loo_layout(p, true),
+                           (double*)out2, (hipStream_t)stream, batch_of<double>(p));
+  return wrap(rc, "dgp_loo_value");
+}
+
+}  // extern "C"

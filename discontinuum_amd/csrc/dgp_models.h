@@ -769,7 +769,7 @@ struct PreBatch {
 #define DGP_PRE_SLOT_BYTES 512
 // upload = false reuses what an earlier launcher of the same fit step put into `scratch`.  `staging` is PINNED host
 // memory of at least B slots that stays untouched until the copy has run (the API layer hands out a ring slot per step,
-// dgp_api.hip::PinnedRing); without it the upload is a blocking copy -- never an asynchronous copy from pageable memory
+// dgp_plan.h::PinnedRing); without it the upload is a blocking copy -- never an asynchronous copy from pageable memory
 // whose lifetime ends with this call.
 template <typename M>
 inline PreBatch<M> prepare_batch(const double* theta, int ntheta, int B, void* scratch, bool upload, hipStream_t s,

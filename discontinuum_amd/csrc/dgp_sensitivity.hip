@@ -35,7 +35,7 @@
 // plan's dtype).  Reads Xt, T and alpha only.
 #include "dgp_gemm.h"
 #include "dgp_gemm_dma.h"
-#include "dgp_internal.h"
+#include "dgp_plan.h"
 #include "dgp_models.h"
 #include "dgp_gram_shared.h"
 
@@ -43,23 +43,30 @@ namespace dgp {
 
 static constexpr int SENS_CHUNK = 8;  // directions per register set of sens_bg
 
-static size_t sens_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
-SensLayout sens_layout(long N, long Mp, int d, int nt, int ndiag, int nrhs, size_t elem) {
+#define SENS_SPLIT 32  // row slabs of its column reductions
+struct SensLayout {
+  size_t Xst, D, Ks, V, beta, G, pc, pg, pq, total;  // byte offsets into a site's slice
+};
+static SensLayout sens_layout(long N, long Mp, int d, int nt, int ndiag, int nrhs, size_t elem) {
   SensLayout L;
   const size_t R = (size_t)(nt + ndiag + nrhs), n = (size_t)N, m = (size_t)Mp;
-  size_t o = 0;
-  L.Xst = o; o += sens_align(elem * m * (size_t)d);
-  L.D = o; o += (size_t)nt * sens_align(elem * n * n);
-  L.Ks = o; o += sens_align(elem * n * m);
-  L.V = o; o += sens_align(elem * n * m);
-  L.beta = o; o += sens_align(elem * n * m);
-  L.G = o; o += sens_align(sizeof(double) * R * n);
-  L.pc = o; o += sens_align(sizeof(double) * SENS_SPLIT * 2 * (size_t)nt * m);
-  L.pg = o; o += sens_align(sizeof(double) * SENS_SPLIT * (R + (size_t)ndiag) * m);
-  L.pq = o; o += sens_align(sizeof(double) * (size_t)nt * (n / 64) * m);
-  L.total = o;
+  Carve c;
+  L.Xst = c.take(elem * m * (size_t)d);
+  L.D = c.o;
+  for (int p = 0; p < nt; ++p) c.take(elem * n * n);
+  L.Ks = c.take(elem * n * m);
+  L.V = c.take(elem * n * m);
+  L.beta = c.take(elem * n * m);
+  L.G = c.take(sizeof(double) * R * n);
+  L.pc = c.take(sizeof(double) * SENS_SPLIT * 2 * (size_t)nt * m);
+  L.pg = c.take(sizeof(double) * SENS_SPLIT * (R + (size_t)ndiag) * m);
+  L.pq = c.take(sizeof(double) * (size_t)nt * (n / 64) * m);
+  L.total = c.o;
   return L;
+}
+// beta = T^T V in 128 x 128 tiles, 64 x 64 ones while the launch has too few (lauum's rule and selector)
+static bool sens_small_tiles(long N, long Mp, const Batch& bt) {
+  return (N / DGP_TILE_HOST) * (Mp / DGP_TILE_HOST) * bt.B <= bt.tuning().lauum64_max_tiles;
 }
 
 // beta[i][j] = sum_{k >= i} T[k][i] V[k][j].  Operand A = T read k-major from its diagonal block down, operand B = rows of V.
@@ -380,9 +387,9 @@ template int sens_beta<float>(const float*, long, const float*, long, float*, hi
 // `work`: one site's slice (sens_layout), Xst and Ks already filled by the caller (pack_x + gram_cross: the hyperparameters of a
 // batch of more than 8 are in pre_scratch).  wbs / ps: the slices' stride in plan-dtype elements / doubles.
 template <typename T>
-int predict_sensitivity(int model, int d, const T* Xt, const T* Tm, const T* alpha, long N, int n, const double* theta, long Mp, int m,
-                        const T* diag, int ndiag, const T* rhs, int nrhs, void* work, const SensLayout& L, double* dmean, double* dvar,
-                        hipStream_t s, Batch bt, void* pre_scratch) {
+static int predict_sensitivity(int model, int d, const T* Xt, const T* Tm, const T* alpha, long N, int n, const double* theta, long Mp, int m,
+                               const T* diag, int ndiag, const T* rhs, int nrhs, void* work, const SensLayout& L, double* dmean,
+                               double* dvar, hipStream_t s, Batch bt, void* pre_scratch) {
   const int nt = model_ntheta(model, d);
   if (nt < 0) return -2;
   const int R = nt + ndiag + nrhs;
@@ -429,10 +436,52 @@ int predict_sensitivity(int model, int d, const T* Xt, const T* Tm, const T* alp
   return (int)hipGetLastError();
 }
 
-template int predict_sensitivity<double>(int, int, const double*, const double*, const double*, long, int, const double*, long, int,
-                                         const double*, int, const double*, int, void*, const SensLayout&, double*, double*, hipStream_t,
-                                         Batch, void*);
-template int predict_sensitivity<float>(int, int, const float*, const float*, const float*, long, int, const double*, long, int, const float*,
-                                        int, const float*, int, void*, const SensLayout&, double*, double*, hipStream_t, Batch, void*);
-
 }  // namespace dgp
+
+using namespace dgp;
+
+#define DGP_SENS_MAX_COLS 8
+static bool sens_sizes_ok(const dgp_plan* p, int64_t m, int ndiag, int nrhs) {
+  return p && m > 0 && m <= 0x7fffffffLL - DGP_TILE_HOST && ndiag >= 0 && ndiag <= DGP_SENS_MAX_COLS && nrhs >= 0 && nrhs <= DGP_SENS_MAX_COLS;
+}
+template <typename T>
+static int sensitivity(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const void* diag, int ndiag, const void* rhs, int nrhs,
+                       void* work, double* dmean, double* dvar, hipStream_t s) {
+  const long M = round_up(m, DGP_TILE_HOST);
+  const SensLayout L = sens_layout(p->N, M, p->d, p->ntheta, ndiag, nrhs, p->elem);
+  char* w = (char*)work;
+  const int rc = cross<T>(p, theta, Xs, m, w + L.Xst, w + L.Ks, s, (long)(L.total / sizeof(T)));
+  if (rc) return rc;
+  return predict_sensitivity<T>(p->model, p->d, (const T*)p->Xt, (const T*)p->Tm, (const T*)p->alpha, p->N, (int)p->n, theta, M, (int)m,
+                                (const T*)diag, ndiag, (const T*)rhs, nrhs, work, L, dmean, dvar, s, batch_of<T>(p), p->pre);
+}
+
+extern "C" {
+
+size_t dgp_predict_sensitivity_workspace_bytes(const dgp_plan* p, int64_t m, int ndiag, int nrhs) {
+  if (!sens_sizes_ok(p, m, ndiag, nrhs)) return 0;
+  return sens_layout(p->N, round_up(m, DGP_TILE_HOST), p->d, p->ntheta, ndiag, nrhs, p->elem).total * (size_t)p->B;
+}
+
+int dgp_predict_sensitivity(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const void* diag, int ndiag, const void* rhs,
+                            int nrhs, void* work, size_t work_bytes, double* dmean, double* dvar, void* stream) {
+  const char* where = "dgp_predict_sensitivity";
+  if (!p) return fail(DGP_E_ARG, "null plan");
+  if (!theta || !Xs || !dmean) return fail(DGP_E_ARG, "dgp_predict_sensitivity: null argument");
+  if (m <= 0 || m > 0x7fffffffLL - DGP_TILE_HOST) return fail(DGP_E_ARG, "dgp_predict_sensitivity: m must be positive");
+  if (ndiag < 0 || ndiag > DGP_SENS_MAX_COLS) return fail(DGP_E_ARG, "dgp_predict_sensitivity: ndiag must be 0..8");
+  if (nrhs < 0 || nrhs > DGP_SENS_MAX_COLS) return fail(DGP_E_ARG, "dgp_predict_sensitivity: nrhs must be 0..8");
+  if (ndiag > 0 && !diag) return fail(DGP_E_ARG, "dgp_predict_sensitivity: ndiag > 0 needs the diagonal directions");
+  if (nrhs > 0 && !rhs) return fail(DGP_E_ARG, "dgp_predict_sensitivity: nrhs > 0 needs the right-hand-side columns");
+  DGP_CHECK_PLAN(p);
+  hipStream_t s = (hipStream_t)stream;
+  int rc = need_factor(p, where, "call dgp_factorize or dgp_fit_step");
+  if (rc || (rc = need_work(work, work_bytes, dgp_predict_sensitivity_workspace_bytes(p, m, ndiag, nrhs), where)) ||
+      (rc = factor_ok(p, s, where)))
+    return rc;
+  rc = DGP_BY_DTYPE(p, sensitivity<double>(p, theta, Xs, m, diag, ndiag, rhs, nrhs, work, dmean, dvar, s),
+                    sensitivity<float>(p, theta, Xs, m, diag, ndiag, rhs, nrhs, work, dmean, dvar, s));
+  return wrap(rc, where);
+}
+
+}  // extern "C"

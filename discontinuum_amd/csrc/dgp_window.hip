@@ -21,7 +21,7 @@
 // thread in ascending order: no atomics, bitwise repeatable, and a site's numbers do not depend on its batch.  The output pad
 // (rows / columns >= q) is the identity; blocks above the block diagonal are not written, as in dgp_posterior_cov.
 #include "dgp_common.h"
-#include "dgp_internal.h"
+#include "dgp_plan.h"
 
 namespace dgp {
 
@@ -205,21 +205,54 @@ int window_moments_mode(const T* cov, long M, int m, int B, const T* mu, const d
 
 }  // namespace
 
-size_t window_moments_workspace_bytes(long m, long q, int B) {
+static size_t window_moments_workspace_bytes(long m, long q, int B) {
   return sizeof(double) * (size_t)B * (size_t)wm_site_doubles(round_up(m, DGP_TILE_HOST), round_up(q, DGP_TILE_HOST));
 }
 
+// exact mean / covariance of rolling-window means W f (mode 0) or W exp(f) (mode 1), f ~ N(mu, C); windows [lo_i, hi_i) per site
+// ([B][q], non-decreasing), weights a [B][m] or null; mean_out [B][q], cov_out [B][Q][Q] in the layout of posterior_cov
+// (Q = round_up(q, 128)); `work`: window_moments_workspace_bytes
 template <typename T>
-int window_moments(int mode, const T* cov, long m, int B, const T* mu, const double* scale2, const double* a, const int* lo,
-                   const int* hi, long q, double* work, double* mean_out, double* cov_out, hipStream_t s) {
+static int window_moments(int mode, const T* cov, long m, int B, const T* mu, const double* scale2, const double* a, const int* lo,
+                          const int* hi, long q, double* work, double* mean_out, double* cov_out, hipStream_t s) {
   const long M = round_up(m, DGP_TILE_HOST), Q = round_up(q, DGP_TILE_HOST);
   return mode == 1 ? window_moments_mode<T, 1>(cov, M, (int)m, B, mu, scale2, a, lo, hi, Q, (int)q, work, mean_out, cov_out, s)
                    : window_moments_mode<T, 0>(cov, M, (int)m, B, mu, scale2, a, lo, hi, Q, (int)q, work, mean_out, cov_out, s);
 }
 
-template int window_moments<double>(int, const double*, long, int, const double*, const double*, const double*, const int*,
-                                    const int*, long, double*, double*, double*, hipStream_t);
-template int window_moments<float>(int, const float*, long, int, const float*, const double*, const double*, const int*, const int*,
-                                   long, double*, double*, double*, hipStream_t);
-
 }  // namespace dgp
+
+using namespace dgp;
+
+static bool wm_sizes_ok(int64_t m, int64_t q, int batch) {
+  return m > 0 && m <= (1 << 20) && q > 0 && q <= (1 << 20) && batch > 0 && batch <= DGP_MAX_BATCH_SITES;
+}
+
+extern "C" {
+
+size_t dgp_window_moments_workspace_bytes(int64_t m, int64_t q, int batch) {
+  if (!wm_sizes_ok(m, q, batch)) return 0;
+  return window_moments_workspace_bytes(m, q, batch);
+}
+
+int dgp_window_moments(int dtype, int mode, const void* cov, int64_t m, int batch, const void* mu, const double* scale2,
+                       const double* a, const int32_t* lo, const int32_t* hi, int64_t q, void* work, size_t work_bytes,
+                       double* mean_out, double* cov_out, void* stream) {
+  if (dtype != DGP_F64 && dtype != DGP_F32) return fail(DGP_E_ARG, "dgp_window_moments: dtype must be 0 (f64) or 1 (f32)");
+  if (mode != 0 && mode != 1) return fail(DGP_E_ARG, "dgp_window_moments: mode must be 0 (linear) or 1 (log)");
+  if (!cov || !mu || !lo || !hi || !mean_out || !cov_out || (mode == 1 && !scale2))
+    return fail(DGP_E_ARG, "dgp_window_moments: null argument");
+  if (!wm_sizes_ok(m, q, batch))
+    return fail(DGP_E_ARG, "dgp_window_moments: bad size (1 <= m <= 2^20, 1 <= q <= 2^20, 1 <= batch <= 1024)");
+  if (!work || work_bytes < window_moments_workspace_bytes(m, q, batch))
+    return fail(DGP_E_WORKSPACE, "dgp_window_moments: workspace missing or too small");
+  if (((uintptr_t)work & 7) != 0) return fail(DGP_E_ARG, "dgp_window_moments: the work area must be 8-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const int rc = dtype == DGP_F64 ? window_moments<double>(mode, (const double*)cov, m, batch, (const double*)mu, scale2, a, lo, hi, q,
+                                                           (double*)work, mean_out, cov_out, s)
+                                  : window_moments<float>(mode, (const float*)cov, m, batch, (const float*)mu, scale2, a, lo, hi, q,
+                                                          (double*)work, mean_out, cov_out, s);
+  return wrap(rc, "dgp_window_moments");
+}
+
+}  // extern "C"

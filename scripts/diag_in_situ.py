@@ -5,7 +5,8 @@ the workgroup's first and last instruction and the CU it ran on.  Run under `roc
 duration of the same launch minus the in-kernel span is the time the launch waited to be placed.
   run:      rocprofv3 --kernel-trace --output-format csv -d OUT -- python3 scripts/diag_in_situ.py run MODEL N DTYPE LOG.json [SITES]
   combine:  python3 scripts/diag_in_situ.py combine OUT/.../*_kernel_trace.csv LOG.json
-  build:    for f in dgp_gram dgp_chol dgp_api dgp_dist dgp_selftest: hipcc <Makefile flags> -DDGP_DIAG_LOG -c f.hip; link -> libdgp_hip_log.so"""
+  build:    for every object of csrc/Makefile's OBJS (the entry points live beside their kernels, so the library needs all of them):
+            hipcc <Makefile flags> -DDGP_DIAG_LOG -c f.hip; link -> libdgp_hip_log.so"""
 import csv
 import ctypes as C
 import json

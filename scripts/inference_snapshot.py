@@ -3,7 +3,9 @@
 move a number: seeded inputs, one fit, and the outputs of ``fit_step``, ``factorize``, ``predict``, ``predict_mean``,
 ``mean_vjp``, ``predict_terms`` / ``predict_slopes`` (with and without ``return_cov``), ``posterior_cov``,
 ``posterior_period_moments``, ``period_moments``, ``exceedance_moments``, ``posterior_exceedance_moments``, ``sample_value``,
-``window_moments`` and ``cross_validate``.
+``window_moments`` and ``cross_validate``; and, for one site and the ragged batch of three, ``fisher``, ``predict_sensitivity``,
+``deletion_influence``, ``loo_fit_step`` / ``loo_value``, ``laplace_fit_step`` (with and without an interval row),
+``laplace_cross_validate`` and ``ep_fit_step`` cold and warm (``extra_products``).
 
     python scripts/inference_snapshot.py --write before.pt      # on the commit to compare against
     python scripts/inference_snapshot.py --compare before.pt    # on the new one: exit status 1 unless every tensor is equal
@@ -95,8 +97,82 @@ def run_config(torch, GPPlan, backend, make_case, model, d, dtype, sizes, dev):
     keep("posterior_period_moments_linear",
          plan.posterior_period_moments(theta, Xs, mu, scale2, w, groups, GROUPS, backend.MODE_LINEAR, extra_var=extra))
     keep("cross_validate", plan.cross_validate(folds))
+    if B <= 3:  # the products whose host glue lives beside their kernels: one site and the ragged batch of three
+        extra_products(torch, plan, backend, keep, theta, X, r, noise, Xs, w, folds, groups, extra, dtype, dev)
     torch.cuda.synchronize(dev)
     return out
+
+
+def extra_products(torch, plan, backend, keep, theta, X, r, noise, Xs, w, folds, groups, extra, dtype, dev):
+    """fisher, predict_sensitivity, deletion_influence on the held factorisation; then, float64 only, the steps that replace it:
+    loo_fit_step / loo_value, laplace_fit_step (a third of the rows censored; then with one interval row and ``upper``),
+    laplace_cross_validate and ep_fit_step cold and warm (the last two: one site)."""
+    from discontinuum_amd._lib import DGPError
+
+    B, n = plan.batch, plan.n
+    lead = () if B == 1 else (B,)
+    g = torch.Generator().manual_seed(11)
+    cols = torch.randn(lead + (2, n), generator=g, dtype=torch.float64).to(dtype).to(dev)
+    rhs = torch.randn(lead + (2, n), generator=g, dtype=torch.float64).to(dtype).to(dev)
+
+    def attempt(name, call):  # a refusal is part of the record: its code, and what the call left behind is compared by the next rows
+        try:
+            keep(name, call())
+        except DGPError as e:
+            keep(name + ".error", torch.tensor([e.code]))
+
+    def stat_tensor(value):
+        return torch.tensor(value, dtype=torch.float64)
+
+    keep("fisher", plan.fisher(theta, diag=cols))
+    keep("predict_sensitivity", plan.predict_sensitivity(theta, Xs, diag=cols, rhs=rhs))
+    inv_sd = (1.0 + w).to(torch.float64)
+    scale = 0.5 if B == 1 else [0.5 + 0.1 * b for b in range(B)]
+    keep("deletion_influence_linear",
+         plan.deletion_influence(theta, Xs, folds, w, scale, groups, GROUPS, backend.MODE_LINEAR, inv_sd=inv_sd))
+    keep("deletion_influence_log", plan.deletion_influence(theta, Xs, folds, w, scale, groups, GROUPS, backend.MODE_LOG))
+    if dtype != torch.float64:
+        return
+    keep("loo_fit_step", plan.loo_fit_step(theta, r, noise))
+    keep("loo_value", plan.loo_value())
+    side = torch.zeros(lead + (n,), dtype=torch.int32)
+    side[..., ::3] = -1  # a third of the rows: the truth lies below the recorded value
+    mean = torch.zeros_like(r)
+
+    def laplace(upper):
+        res = plan.laplace_fit_step(theta, r, mean, noise, side.to(dev).contiguous(), upper=upper)
+        return res[:3] + (stat_tensor(res[3]),)
+
+    attempt("laplace_fit_step", lambda: laplace(None))
+    side[..., 1] = 2  # one interval row: the truth in [y, y + 0.5]
+    upper = r + 0.5
+    side_dev = side.to(dev).contiguous()
+    attempt("laplace_interval_fit_step", lambda: laplace(upper))
+    if B != 1:
+        return
+    f_hat = out_f = None
+    try:
+        out_f = plan.laplace_factorize(theta, r, mean, noise, side_dev, upper=upper)
+        f_hat = out_f[1]
+        keep("laplace_factorize", out_f[:2] + (stat_tensor(out_f[2]),))
+    except DGPError as e:
+        keep("laplace_factorize.error", torch.tensor([e.code]))
+    if f_hat is not None:
+        def lcv():
+            res = plan.laplace_cross_validate(theta, r, mean, noise, side_dev, f_hat, folds, upper=upper, shift=0.5)
+            return tuple(res[k] for k in sorted(res))
+
+        attempt("laplace_cross_validate", lcv)
+
+    def ep(sites):
+        res = plan.ep_fit_step(theta, r, mean, noise, side_dev, sites=sites, upper=upper)
+        aux = plan.ep_aux
+        return (res[0], res[1], res[2][0], res[2][1], stat_tensor(res[3]), aux["cav_mean"], aux["cav_var"], aux["logz"])
+
+    attempt("ep_fit_step_cold", lambda: ep(None))
+    if getattr(plan, "ep_sites", None) is not None:
+        warm = tuple(t.clone() for t in plan.ep_sites)
+        attempt("ep_fit_step_warm", lambda: ep(warm))
 
 
 def same_bits(torch, a, b):
