@@ -809,6 +809,12 @@ class GPPlan:
         with torch.cuda.device(self.device):
             return period_moments(cov, m, mu, scale2, w, groups, ngroups, mode, extra_var)
 
+    def period_third_moments(self, cov, m: int, mu, scale2, w, groups, ngroups: int, extra_var=None, tile: int = 0):
+        """Exact third central moment of the period sums of a log-transformed posterior (``dgp_period_third_moments``): see
+        the module-level ``period_third_moments``.  Unbatched -> k3 (P,); batched -> (B, P); fp64 device tensors."""
+        with torch.cuda.device(self.device):
+            return period_third_moments(cov, m, mu, scale2, w, groups, ngroups, extra_var, tile)
+
     def exceedance_moments(self, cov, m: int, mu, thresh, w, groups, ngroups: int, extra_var=None):
         """Exact mean and covariance of threshold-exceedance counts of the posterior (``dgp_exceedance_moments``): see the
         module-level ``exceedance_moments``.  Unbatched (cov (M, M), vectors (m,), thresh (L, m)) -> mean (L, P), cov
@@ -1064,6 +1070,33 @@ def period_moments(cov: torch.Tensor, m: int, mu: torch.Tensor, scale2, w: torch
         "dgp_period_moments",
     )
     return mean_out, cov_out
+
+
+def period_third_moments(cov: torch.Tensor, m: int, mu: torch.Tensor, scale2, w: torch.Tensor, groups: torch.Tensor, ngroups: int,
+                         extra_var: torch.Tensor | None = None, tile: int = 0):
+    """Exact third central moment k3_g = E[(L_g - E L_g)^3] of the period sums of a LOG-transformed posterior
+    (``period_moments``' setting with ``mode`` = MODE_LOG, and its arguments) through one ``dgp_period_third_moments`` call:
+    skewness_g = k3_g / cov_gg^1.5.  ``tile``: 0 picks the tile core by size, 64 / 128 force one.  The work area -- 2 M^2
+    doubles per site -- is allocated for the call.  -> k3 (P,) or (B, P), a float64 device tensor."""
+    lib = _lib.load()
+    batched = cov.dim() == 3
+    B = cov.shape[0] if batched else 1
+    M = int(lib.dgp_padded_n(int(m)))
+    lead = (B,) if batched else ()
+    if cov.dtype not in _DTYPES or not cov.is_cuda or not cov.is_contiguous() or tuple(cov.shape) != lead + (M, M):
+        raise ValueError(f"cov must be a contiguous {lead + (M, M)} float64 / float32 CUDA tensor")
+    dev = cov.device
+    mu_t, w_t, g_t, ev_t, s2 = _moment_inputs(dev, cov.dtype, lead, int(m), mu, w, groups, extra_var, scale2)
+    P = int(ngroups)
+    need = int(lib.dgp_period_third_moments_workspace_bytes(int(m), P, B))
+    work = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    k3 = torch.empty(lead + (P,), dtype=torch.float64, device=dev)
+    _lib.check(
+        lib.dgp_period_third_moments(_DTYPES[cov.dtype], _ptr(cov), int(m), B, _ptr(mu_t), _ptr(s2), _ptr(w_t), _ptr(g_t), P,
+                                     _ptr(ev_t), int(tile), _ptr(work), need, _ptr(k3), _stream()),
+        "dgp_period_third_moments",
+    )
+    return k3
 
 
 def stream_panel_rows(need128: int, step: int, M: int, max_bytes: int) -> int:

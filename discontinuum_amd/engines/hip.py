@@ -910,7 +910,7 @@ class MarginalHIP(BaseModel):
 
     @is_fitted
     def aggregate(self, covariates, weights, freq="YE", ci=0.95, pred_noise=False, return_cov=False, max_bytes=None,
-                  hyperparameters=False, prior=True):
+                  hyperparameters=False, prior=True, interval="lognormal"):
         """Exact mean and covariance of the period sums sum_{i in period} weights_i target_i over the points of
         ``covariates`` (``freq``: a resample alias -- "YE", "YE-SEP" for water years, "QE", "ME"), from the latent
         posterior (``pred_noise=True`` adds the likelihood's predictive noise to its diagonal): what ``sample()``, a
@@ -922,13 +922,17 @@ class MarginalHIP(BaseModel):
         m x m covariance does not fit it takes the streamed ``dgp_posterior_period_moments``.  ``hyperparameters=True`` adds
         ``se_hyper``, ``se_total`` and ``lower_total`` / ``upper_total`` (with ``return_cov`` also ``cov_hyper``): the
         hyperparameters' uncertainty propagated to FIRST ORDER (delta method) through the exact period Jacobian and the exact
-        inverse Fisher information (``prior``: with the priors' curvature).  See ``discontinuum_amd.loads``."""
+        inverse Fisher information (``prior``: with the priors' curvature).  ``interval="three-moment"`` adds ``skewness`` -- the
+        exact skewness of every period sum, from one ``dgp_period_third_moments`` on the dense covariance -- and fits ``lower`` /
+        ``upper`` to three exact moments instead of two (a shifted lognormal; still a fitted shape).  See
+        ``discontinuum_amd.loads``."""
         from ..loads import DEFAULT_MAX_BYTES, aggregate
 
         if hyperparameters:
             self._refuse_censored("aggregate(hyperparameters=True)")
         return aggregate(self, covariates, weights, freq=freq, ci=ci, pred_noise=pred_noise, return_cov=return_cov,
-                         max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes, hyperparameters=hyperparameters, prior=prior)
+                         max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes, hyperparameters=hyperparameters, prior=prior,
+                         interval=interval)
 
     @is_fitted
     def exceedance(self, covariates, threshold=None, threshold_series=None, freq="YE", above=True, fraction=False, ci=0.95,

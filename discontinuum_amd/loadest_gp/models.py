@@ -107,19 +107,20 @@ class LoadestGPMarginalHIP(LoadestDataMixin, MarginalHIP):
 
     @is_fitted
     def annual_flux(self, covariates, freq="YE", ci=0.95, pred_noise=False, return_cov=False, max_bytes=None,
-                    hyperparameters=False, prior=True):
+                    hyperparameters=False, prior=True, interval="lognormal"):
         """Exact period loads in kilograms -- sum over each period of concentration (mg/l) x flow (m^3/s) x time step --
         with their standard errors and approximate ``ci`` intervals; ``covariates`` on a regular time grid (an irregular
         one raises ``ValueError``), ``freq`` a resample alias ("YE", "YE-SEP" for water years, "QE", "ME").  Replaces
         ``concentration_to_flux(model.sample(daily, n), daily["flow"]).resample(time="YE").sum()``
         (src/loadest_gp/utils.py:14-103) without its sampling noise; see ``MarginalHIP.aggregate`` (also for
         ``max_bytes``, and for ``hyperparameters=True``: ``se_hyper`` / ``se_total`` with the hyperparameters' uncertainty
-        propagated to first order)."""
+        propagated to first order, and for ``interval="three-moment"``: the loads' exact ``skewness`` and intervals fitted
+        to three exact moments)."""
         from ..loads import DEFAULT_MAX_BYTES, annual_flux
 
         return annual_flux(self, covariates, freq=freq, ci=ci, pred_noise=pred_noise, return_cov=return_cov,
                            max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes, hyperparameters=hyperparameters,
-                           prior=prior)
+                           prior=prior, interval=interval)
 
     @is_fitted
     def exceedance(self, covariates, threshold=None, threshold_series=None, kind="concentration", freq="YE", above=True,

@@ -91,9 +91,61 @@ def target_transform(dm):
     raise NotImplementedError(f"period moments are exact for the log and standard transforms only, not {type(pipe).__name__}")
 
 
-def intervals(mode, mean, var, ci=0.95):
-    """Approximate central ``ci`` intervals from exact moments: a lognormal with the same mean and variance
-    (Fenton-Wilkinson) for log-mode sums of lognormals, the normal for linear-mode sums."""
+INTERVALS = ("lognormal", "three-moment")
+
+
+def _check_interval(interval):
+    if interval not in INTERVALS:
+        raise ValueError(f"interval must be one of {INTERVALS}, not {interval!r}")
+    return interval
+
+
+def three_moment_fit(skew):
+    """The shifted lognormal X = shift + scale exp(sigma Z) with a given skewness gamma > 0, in units of the standard
+    deviation: omega = exp(sigma^2) solves (omega + 2) sqrt(omega - 1) = gamma, in closed form
+    omega = A + 1 / A - 1, A = cbrt(1 + gamma^2 / 2 + sqrt(gamma^2 + gamma^4 / 4)) (the two cube roots of Cardano's formula
+    multiply to 1).  Evaluated through u = omega - 1 = (A - 1)^2 / A with A - 1 from expm1 / log1p, which keeps full relative
+    precision as gamma -> 0 (u ~ gamma^2 / 9).  -> (u, sigma, scale / sd); mean = shift + scale sqrt(omega)."""
+    g = np.asarray(skew, dtype=np.float64)
+    g2 = g * g
+    d = np.expm1(np.log1p(0.5 * g2 + np.sqrt(g2 + 0.25 * g2 * g2)) / 3.0)
+    u = d * d / (1.0 + d)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return u, np.sqrt(np.log1p(u)), 1.0 / np.sqrt(u * (1.0 + u))
+
+
+SKEW_NORMAL_BELOW = 1e-8  # a skewness below this takes the normal interval, the fit's limit
+
+
+def three_moment_intervals(mean, var, skew, ci=0.95):
+    """Central ``ci`` intervals of the shifted lognormal with the given mean, variance and skewness (``three_moment_fit``):
+    lower / upper = shift + scale exp(-/+ z sigma), written as mean + scale (expm1(-/+ z sigma) - expm1(sigma^2 / 2)) so that
+    the normal limit is reached continuously.  A skewness below ``SKEW_NORMAL_BELOW`` gives the normal interval; a lower end
+    below 0 (a negative shift) is clipped to 0.  -> (lower, upper, number of clipped lower ends)."""
+    lo_q, hi_q = (1 - ci) / 2, 1 - (1 - ci) / 2
+    mean, var = np.asarray(mean, dtype=np.float64), np.clip(np.asarray(var, dtype=np.float64), 0.0, None)
+    skew = np.nan_to_num(np.asarray(skew, dtype=np.float64), nan=0.0, posinf=0.0, neginf=0.0)
+    se = np.sqrt(var)
+    fitted = skew >= SKEW_NORMAL_BELOW
+    u, sigma, rel = three_moment_fit(np.where(fitted, skew, 1.0))
+    scale, centre = rel * se, np.expm1(0.5 * sigma * sigma)
+    lower = np.where(fitted, mean + scale * (np.expm1(norm.ppf(lo_q) * sigma) - centre), mean + norm.ppf(lo_q) * se)
+    upper = np.where(fitted, mean + scale * (np.expm1(norm.ppf(hi_q) * sigma) - centre), mean + norm.ppf(hi_q) * se)
+    clipped = lower < 0.0
+    return np.where(clipped, 0.0, lower), upper, int(np.count_nonzero(clipped))
+
+
+def intervals(mode, mean, var, ci=0.95, interval="lognormal", skew=None):
+    """Approximate central ``ci`` intervals from exact moments.  ``interval="lognormal"``: a lognormal with the same mean and
+    variance (Fenton-Wilkinson) for log-mode sums of lognormals, the normal for linear-mode sums.  ``"three-moment"``: for
+    log-mode sums the shifted lognormal with the same mean, variance and skewness ``skew``
+    (``three_moment_intervals``); linear-mode sums are Gaussian and keep the normal interval."""
+    _check_interval(interval)
+    if interval == "three-moment" and mode != MODE_LINEAR:
+        if skew is None:
+            raise ValueError('interval="three-moment" needs the skewness')
+        lower, upper, _clipped = three_moment_intervals(mean, var, skew, ci)
+        return lower, upper
     lo_q, hi_q = (1 - ci) / 2, 1 - (1 - ci) / 2
     mean, var = np.asarray(mean, dtype=np.float64), np.clip(np.asarray(var, dtype=np.float64), 0.0, None)
     if mode == MODE_LINEAR:
@@ -108,12 +160,25 @@ def intervals(mode, mean, var, ci=0.95):
     return np.where(pos, lower, mean), np.where(pos, upper, mean)
 
 
-def _dataset(mode, mean, cov, labels, n_points, attrs, ci, freq=None, cov_hyper=None):
+def _dataset(mode, mean, cov, labels, n_points, attrs, ci, freq=None, cov_hyper=None, interval="lognormal", k3=None):
     """-> the result Dataset; its own attrs also carry the period ``freq`` (``period_change`` reads it).  ``cov_hyper``: the
     first-order contribution of the hyperparameters' uncertainty (``hyperparameters=True``), which adds ``se_hyper``,
-    ``se_total`` and ``lower_total`` / ``upper_total`` (the same interval rule at the summed variance)."""
+    ``se_total`` and ``lower_total`` / ``upper_total`` (the two-moment interval rule at the summed variance, whatever
+    ``interval`` is).  ``interval="three-moment"``: ``k3`` holds the periods' exact third central moments (None for a linear
+    target: skewness 0); the Dataset gains ``skewness``, ``lower`` / ``upper`` come from ``three_moment_intervals`` and the
+    attrs carry ``interval`` and ``clipped_lower``, the number of lower ends clipped to 0."""
     var = np.clip(np.diagonal(cov), 0.0, None)
-    lower, upper = intervals(mode, mean, var, ci)
+    extra = {}
+    if interval == "three-moment":
+        with np.errstate(divide="ignore", invalid="ignore"):
+            skew = np.zeros_like(var) if k3 is None else np.where(var > 0, np.asarray(k3, dtype=np.float64) / var ** 1.5, 0.0)
+        if mode == MODE_LINEAR:
+            (lower, upper), clipped = intervals(mode, mean, var, ci), 0
+        else:
+            lower, upper, clipped = three_moment_intervals(mean, var, skew, ci)
+        extra = {"interval": interval, "clipped_lower": clipped}
+    else:
+        lower, upper = intervals(mode, mean, var, ci)
     attrs = dict(attrs)
     data = {
         "mean": ("time", mean, attrs),
@@ -122,13 +187,15 @@ def _dataset(mode, mean, cov, labels, n_points, attrs, ci, freq=None, cov_hyper=
         "upper": ("time", upper, dict(attrs, ci=ci)),
         "n_points": ("time", n_points),
     }
+    if interval == "three-moment":
+        data["skewness"] = ("time", skew)
     if cov_hyper is not None:
         var_h = np.clip(np.diagonal(cov_hyper), 0.0, None)
         lower_t, upper_t = intervals(mode, mean, var + var_h, ci)
         note = dict(attrs, order="first (delta method)")
         data.update({"se_hyper": ("time", np.sqrt(var_h), note), "se_total": ("time", np.sqrt(var + var_h), note),
                      "lower_total": ("time", lower_t, dict(note, ci=ci)), "upper_total": ("time", upper_t, dict(note, ci=ci))})
-    return Dataset(data, coords={"time": labels}, attrs=attrs if freq is None else dict(attrs, freq=freq))
+    return Dataset(data, coords={"time": labels}, attrs=dict(attrs if freq is None else dict(attrs, freq=freq), **extra))
 
 
 def _target_attrs(dm):
@@ -138,7 +205,7 @@ def _target_attrs(dm):
 
 # ---------------------------------------------------------------------------------------------------- one site
 def aggregate(model, covariates, weights, freq="YE", ci=0.95, pred_noise=False, return_cov=False, attrs=None,
-              max_bytes: int = DEFAULT_MAX_BYTES, hyperparameters=False, prior=True):
+              max_bytes: int = DEFAULT_MAX_BYTES, hyperparameters=False, prior=True, interval="lognormal"):
     """``MarginalHIP.aggregate``: exact mean / covariance of sum_{i in period} w_i c_i over the points of
     ``covariates`` (c = the model's target in data space).  A site whose dense footprint (``_site_bytes``) fits
     ``max_bytes`` takes one ``dgp_posterior_cov`` + one ``dgp_period_moments``; a larger one the streamed
@@ -150,19 +217,31 @@ def aggregate(model, covariates, weights, freq="YE", ci=0.95, pred_noise=False, 
     cov_hyper = G Sigma_raw G^T.  It adds ``se_hyper``, ``se_total`` = sqrt(se^2 + se_hyper^2) and ``lower_total`` /
     ``upper_total``; with ``return_cov`` the result is (ds, cov, cov_hyper).  It works on the dense and the streamed path
     alike (the Jacobian needs no m x m buffer).  Second-order terms are not included; ``flow_normalized``, ``exceedance`` and
-    the ``*_many`` wrappers do not propagate.  ``False`` returns exactly the variables it always did."""
+    the ``*_many`` wrappers do not propagate.  ``False`` returns exactly the variables it always did.
+
+    ``interval``: ``"lognormal"`` (the default) fits ``lower`` / ``upper`` to the two exact moments (Fenton-Wilkinson).
+    ``"three-moment"`` also computes every period's exact third central moment (one ``dgp_period_third_moments`` on the dense
+    covariance), adds ``skewness`` and takes ``lower`` / ``upper`` from the shifted lognormal with the exact mean, variance and
+    skewness (``three_moment_intervals``): the three moments are exact, the interval is still a fitted shape.  The dense
+    footprint then includes the product's work area (2 M^2 doubles); a record that fits ``max_bytes`` for two moments but not
+    for three raises ``ValueError``, one that would take the streamed path ``NotImplementedError``.  With
+    ``hyperparameters=True`` ``lower`` / ``upper`` are the three-moment ones and ``lower_total`` / ``upper_total`` stay the
+    two-moment intervals at the summed variance (the hyperparameters' effect on the skewness is not propagated)."""
+    _check_interval(interval)
     order, groups, labels, n_points, _dropped = _kept(*period_groups(covariates.coords["time"].values, np.asarray(weights), freq))
     w = np.asarray(weights, dtype=np.float64).reshape(-1)[order]
     Xnew = torch.tensor(model.dm.Xnew(covariates), dtype=model.dtype)[torch.as_tensor(order)]
     return point_moments(model, Xnew, w, groups, labels, n_points, ci=ci, pred_noise=pred_noise, return_cov=return_cov,
-                         attrs=attrs, max_bytes=max_bytes, freq=freq, hyperparameters=hyperparameters, prior=prior)
+                         attrs=attrs, max_bytes=max_bytes, freq=freq, hyperparameters=hyperparameters, prior=prior,
+                         interval=interval)
 
 
 def point_moments(model, Xnew, w, groups, labels, n_points, ci=0.95, pred_noise=False, return_cov=False, attrs=None,
-                  max_bytes: int = DEFAULT_MAX_BYTES, freq=None, hyperparameters=False, prior=True):
+                  max_bytes: int = DEFAULT_MAX_BYTES, freq=None, hyperparameters=False, prior=True, interval="lognormal"):
     """The moment core of ``aggregate`` on model-space inputs: design rows ``Xnew`` (m, d), weights ``w`` (m,), int32
     period ids ``groups`` (non-decreasing, -1 = excluded), period ``labels`` and ``n_points`` per period -- what
     ``aggregate`` builds from a covariates record and ``flow_normalized`` from its (day, flow) pairs."""
+    _check_interval(interval)
     if hyperparameters and hasattr(model, "_refuse_censored"):
         model._refuse_censored("the hyperparameters' uncertainty of period sums (hyperparameters=True)")
     mode, s, t = target_transform(model.dm)
@@ -170,6 +249,10 @@ def point_moments(model, Xnew, w, groups, labels, n_points, ci=0.95, pred_noise=
     m = Xnew.shape[0]
     model._eval_ready(Xnew)
     esz = torch.empty((), dtype=model.dtype).element_size()
+    third = interval == "three-moment" and mode == MODE_LOG  # (a linear target is Gaussian: skewness 0, nothing to compute)
+    k3_d = None
+    if third:
+        _third_moment_budget(_site_bytes(model.dm.X.shape[0], m, esz), m, len(labels), max_bytes)
     with torch.no_grad():
         if _site_bytes(model.dm.X.shape[0], m, esz) <= max_bytes:
             kmean, cov = model._plan.posterior_cov(model._factor_theta, Xnew)
@@ -177,6 +260,9 @@ def point_moments(model, Xnew, w, groups, labels, n_points, ci=0.95, pred_noise=
             extra = model.likelihood.predictive_noise(m, Xnew.device, model.dtype) if pred_noise else None
             mean_d, cov_d = model._plan.period_moments(cov, m, (s * mu + t).contiguous(), s * s, w, groups, len(labels),
                                                        mode, extra_var=extra)
+            if third:
+                k3_d = model._plan.period_third_moments(cov, m, (s * mu + t).contiguous(), s * s, w, groups, len(labels),
+                                                        extra_var=extra)
         else:
             mu = model._plan.predict_mean(model._factor_theta, Xnew) + model.model.prior_mean(Xnew)
             extra = model.likelihood.predictive_noise(m, Xnew.device, model.dtype) if pred_noise else None
@@ -196,7 +282,8 @@ def point_moments(model, Xnew, w, groups, labels, n_points, ci=0.95, pred_noise=
         from .hyperpar import period_hyper_covariance
 
         cov_hyper, _G = period_hyper_covariance(model, Xnew, a_pt, groups, len(labels), mode, s, prior=prior, pred_noise=pred_noise)
-    ds = _dataset(mode, mean, pcov, labels, n_points, _target_attrs(model.dm) if attrs is None else attrs, ci, freq, cov_hyper)
+    ds = _dataset(mode, mean, pcov, labels, n_points, _target_attrs(model.dm) if attrs is None else attrs, ci, freq, cov_hyper,
+                  interval=interval, k3=None if k3_d is None else k3_d.cpu().numpy())
     if return_cov:
         return (ds, pcov, cov_hyper) if hyperparameters else (ds, pcov)
     return ds
@@ -207,6 +294,27 @@ def _site_bytes(n, m, esz):
     """Device bytes of the dense path for one site: the (M, M) covariance, the prediction's cross terms, the plan."""
     N, M = -(-n // 128) * 128, -(-m // 128) * 128
     return esz * (M * M + 2 * N * M + 3 * N * N) + 8 * M * 8
+
+
+def _third_moment_bytes(m, P):
+    """Device bytes of ``dgp_period_third_moments``' work area for one site (``dgp_period_third_moments_workspace_bytes``, area
+    by area, each rounded up to 256 bytes): a, the row totals, the points' periods, the periods' and the 64-row blocks' column
+    ranges, the per-(tile, row) partials, and the two M x M double matrices."""
+    M, up = -(-m // 128) * 128, lambda b: -(-b // 256) * 256
+    nb = M // 64
+    return 2 * up(8 * M) + up(4 * M) + up(8 * P) + up(8 * nb) + up(8 * 64 * (nb * (nb + 1) // 2)) + 2 * up(8 * M * M)
+
+
+def _third_moment_budget(dense_bytes, m, P, max_bytes):
+    """The footprint check of ``interval="three-moment"`` for one site whose two-moment dense path needs ``dense_bytes``."""
+    if dense_bytes > max_bytes:
+        raise NotImplementedError(f'interval="three-moment" needs the dense m x m covariance: this record ({dense_bytes} bytes '
+                                  f"dense, max_bytes = {max_bytes}) takes the streamed dgp_posterior_period_moments, for "
+                                  "which no third-moment pass exists")
+    need = dense_bytes + _third_moment_bytes(m, P)
+    if need > max_bytes:
+        raise ValueError(f'interval="three-moment" needs {need} bytes on the device ({dense_bytes} for the dense two-moment '
+                         f"path + {need - dense_bytes} for the third-moment work area), max_bytes = {max_bytes}")
 
 
 def _streamed_bytes(n, m, P, d, esz):
@@ -234,7 +342,7 @@ def _batches(idx, nbytes, sizes, max_bytes):
 
 
 def aggregate_many(models, covariates_list, weights_list, freq="YE", ci=0.95, pred_noise=False, return_cov=False,
-                   max_bytes: int = DEFAULT_MAX_BYTES, attrs_list=None):
+                   max_bytes: int = DEFAULT_MAX_BYTES, attrs_list=None, interval="lognormal"):
     """``aggregate`` for many fitted sites (different n and m allowed) like ``multisite_fit.predict_many``: per batch of
     sites ONE batched plan, one batched ``dgp_factorize``, one batched ``dgp_posterior_cov`` and one
     ``dgp_period_moments`` launch (gridDim.z = sites); pad points carry group -1.  Sites are cut into consecutive
@@ -243,10 +351,13 @@ def aggregate_many(models, covariates_list, weights_list, freq="YE", ci=0.95, pr
     Sites whose dense footprint alone exceeds ``max_bytes`` take the streamed ``dgp_posterior_period_moments`` instead,
     in batches of their own cut by the streamed footprint (``_streamed_bytes``: nothing of order M^2).  A batch in which a
     model carries censoring (``fit(censored=)`` / ``fit_many(censored=)``) builds its cache with the batched
-    ``laplace_factorize`` (``multisite_fit.censored_cache_build``): the Laplace posterior, not the limits taken for samples."""
+    ``laplace_factorize`` (``multisite_fit.censored_cache_build``): the Laplace posterior, not the limits taken for samples.
+    ``interval="three-moment"`` (see ``aggregate``): one batched ``dgp_period_third_moments`` per dense batch, whose footprint
+    then counts the product's work area; a site that would go the streamed way raises ``NotImplementedError``."""
     from .backend import GPPlan
     from . import _lib
 
+    _check_interval(interval)
     if not (len(models) == len(covariates_list) == len(weights_list)) or not models:
         raise ValueError("aggregate_many needs one covariates object and one weight vector per model")
     for mdl in models:
@@ -283,7 +394,12 @@ def aggregate_many(models, covariates_list, weights_list, freq="YE", ci=0.95, pr
     dense = [b for b, (n, m) in enumerate(sizes) if _site_bytes(n, m, esz) <= max_bytes]
     rest = [b for b in range(len(sites)) if b not in set(dense)]
     P_all, d_all = max(len(st["labels"]) for st in sites), sites[0]["name"][1]
-    batches = [(idx, False) for idx in _batches(dense, lambda n, m: _site_bytes(n, m, esz), sizes, max_bytes)]
+    third = interval == "three-moment" and sites[0]["mode"] == MODE_LOG
+    if third:
+        for n, m in sizes:
+            _third_moment_budget(_site_bytes(n, m, esz), m, P_all, max_bytes)
+    dense_bytes = (lambda n, m: _site_bytes(n, m, esz) + _third_moment_bytes(m, P_all)) if third else (lambda n, m: _site_bytes(n, m, esz))
+    batches = [(idx, False) for idx in _batches(dense, dense_bytes, sizes, max_bytes)]
     batches += [(idx, True) for idx in _batches(rest, lambda n, m: _streamed_bytes(n, m, P_all, d_all, esz), sizes, max_bytes)]
 
     results = [None] * len(sites)
@@ -342,13 +458,18 @@ def aggregate_many(models, covariates_list, weights_list, freq="YE", ci=0.95, pr
             else:
                 mean_d, cov_d = plan.period_moments(cov, mm, one(mapped), (sv.double() ** 2).cpu(), one(W), one(G), P, mode,
                                                     extra_var=one(EV) if EV is not None else None)
+            k3_h = None
+            if third:
+                k3_h = plan.period_third_moments(cov, mm, one(mapped), (sv.double() ** 2).cpu(), one(W), one(G), P,
+                                                 extra_var=one(EV) if EV is not None else None).reshape(B, P).cpu().numpy()
         mean_h, cov_h = mean_d.reshape(B, P).cpu().numpy(), cov_d.reshape(B, P, P).cpu().numpy()
         del plan, cov
         for k, b in enumerate(idx):
             st = sites[b]
             p = len(st["labels"])
             attrs = _target_attrs(models[b].dm) if attrs_list is None else attrs_list[b]
-            ds = _dataset(mode, mean_h[k, :p], cov_h[k, :p, :p], st["labels"], st["n_points"], attrs, ci, freq)
+            ds = _dataset(mode, mean_h[k, :p], cov_h[k, :p, :p], st["labels"], st["n_points"], attrs, ci, freq, interval=interval,
+                          k3=None if k3_h is None else k3_h[k, :p])
             results[b] = (ds, cov_h[k, :p, :p].copy()) if return_cov else ds
     return results
 
@@ -383,12 +504,15 @@ def _flux_attrs(model):
 
 
 def annual_flux(model, covariates, freq="YE", ci=0.95, pred_noise=False, return_cov=False, max_bytes: int = DEFAULT_MAX_BYTES,
-                hyperparameters=False, prior=True):
+                hyperparameters=False, prior=True, interval="lognormal"):
     """``LoadestGP.annual_flux``: exact period loads (kg) and their uncertainty.  ``hyperparameters=True``: also the
-    first-order (delta method) contribution of the hyperparameters' uncertainty, see ``aggregate``."""
+    first-order (delta method) contribution of the hyperparameters' uncertainty, see ``aggregate``.
+    ``interval="three-moment"``: the exact skewness of every load and intervals fitted to three moments, see ``aggregate``."""
+    _check_interval(interval)
     w = flux_weights(covariates, _target_attrs(model.dm))
     return aggregate(model, covariates, w, freq=freq, ci=ci, pred_noise=pred_noise, return_cov=return_cov,
-                     attrs=_flux_attrs(model), max_bytes=max_bytes, hyperparameters=hyperparameters, prior=prior)
+                     attrs=_flux_attrs(model), max_bytes=max_bytes, hyperparameters=hyperparameters, prior=prior,
+                     interval=interval)
 
 
 # ---------------------------------------------------------------------------------------------------- flow normalization
@@ -501,13 +625,15 @@ def period_change(ds, cov, start, end, ci=0.95, freq=None):
 
 
 def annual_flux_many(models, covariates_list, freq="YE", ci=0.95, pred_noise=False, return_cov=False,
-                     max_bytes: int = DEFAULT_MAX_BYTES):
-    """``annual_flux`` for many sites through ``aggregate_many`` (batched device work, byte-budgeted batches)."""
+                     max_bytes: int = DEFAULT_MAX_BYTES, interval="lognormal"):
+    """``annual_flux`` for many sites through ``aggregate_many`` (batched device work, byte-budgeted batches);
+    ``interval="three-moment"``: one batched ``dgp_period_third_moments`` per dense batch."""
+    _check_interval(interval)
     weights = [flux_weights(cov, _target_attrs(m.dm)) for m, cov in zip(models, covariates_list)]
     return aggregate_many(models, covariates_list, weights, freq=freq, ci=ci, pred_noise=pred_noise, return_cov=return_cov,
-                          max_bytes=max_bytes, attrs_list=[_flux_attrs(m) for m in models])
+                          max_bytes=max_bytes, attrs_list=[_flux_attrs(m) for m in models], interval=interval)
 
 
 __all__ = ["aggregate", "aggregate_many", "annual_flux", "annual_flux_many", "period_groups", "target_transform",
-           "intervals", "point_moments", "day_keys", "flow_normalized_points", "flow_normalized", "period_change",
+           "intervals", "three_moment_fit", "three_moment_intervals", "point_moments", "day_keys", "flow_normalized_points", "flow_normalized", "period_change",
            "DEFAULT_MAX_BYTES"]

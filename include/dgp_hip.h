@@ -933,6 +933,10 @@ int dgp_debug_solve(int dtype, int capacity, const void* Tm_dev, int64_t N, cons
                     void* alpha_dev, void* partials_dev, void* quad_dev, void* stream);
 int64_t dgp_debug_solve_partials(int64_t N);
 
+/* Entry points added after the host layer's contract (tests/abi_contract.json) was recorded: declared in dgp_hip_ext.h, part of
+ * this header for every caller. */
+#include "dgp_hip_ext.h"
+
 #ifdef __cplusplus
 }
 #endif
