@@ -153,11 +153,6 @@ SIGNATURES = {
     "dgp_debug_solve": (_i, [_i, _i, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "dgp_debug_solve_partials": (_i64, [_i64]),
     "dgp_debug_tile_gemm": (_i, [_i, _i, _i, _i, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i, _i, _i, _i, _vp]),
-}
-
-# Entry points declared in include/dgp_hip_ext.h: added after the host layer's contract (tests/abi_contract.json, which walks
-# SIGNATURES) was recorded, and outside it -- their own tests check their sizes and refusals.
-EXT_SIGNATURES = {
     "dgp_period_third_moments_workspace_bytes": (_sz, [_i64, _i, _i]),
     "dgp_period_third_moments": (_i, [_i, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _sz, _vp, _vp]),
 }
@@ -179,7 +174,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise DGPLibraryError(f"could not load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
+    for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

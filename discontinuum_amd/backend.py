@@ -44,6 +44,11 @@ def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _call(name, *args):
+    """The checked call ``name(*args, stream)`` of a library entry that takes no plan, on the current stream."""
+    _lib.check(getattr(_lib.load(), name)(*args, _stream()), name)
+
+
 class GPPlan:
     """Fixed (model, dtype, n, d) exact-GP problem resident on one GPU."""
 
@@ -70,16 +75,15 @@ class GPPlan:
         _lib.check(self.lib.dgp_plan_create(mid, _DTYPES[dtype], self.n, self.d, C.byref(handle)), "dgp_plan_create")
         self._h = handle
         self.batch = int(batch)
+        self._lead = () if self.batch == 1 else (self.batch,)  # the batch dimensions every result starts with
+        self._site_sizes = [self.n] * self.batch  # rows every site uses (``set_site_sizes``)
         if self.batch != 1:
-            _lib.check(self.lib.dgp_plan_set_batch(self._h, self.batch), "dgp_plan_set_batch")
+            self._host("dgp_plan_set_batch", self.batch)
         nbytes = int(self.lib.dgp_plan_workspace_bytes(self._h))
         with torch.cuda.device(self.device):
             self._ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
             off = (-self._ws.data_ptr()) % 256
-            _lib.check(
-                self.lib.dgp_plan_set_workspace(self._h, C.c_void_p(self._ws.data_ptr() + off), nbytes),
-                "dgp_plan_set_workspace",
-            )
+            self._host("dgp_plan_set_workspace", C.c_void_p(self._ws.data_ptr() + off), nbytes)
         self.set_lookahead(lookahead)
 
     def __del__(self):
@@ -95,16 +99,16 @@ class GPPlan:
     # ------------------------------------------------------------------ helpers
     def set_lookahead(self, level):
         level = 2 if level is True else int(level)
-        _lib.check(self.lib.dgp_plan_set_lookahead(self._h, level), "dgp_plan_set_lookahead")
+        self._host("dgp_plan_set_lookahead", level)
 
     def set_option(self, key: int, value: int):
         """Plan-level option (``_lib.OPT_*``; include/dgp_hip.h ``dgp_plan_set_option``): tile-shape selectors of the
         O(n^3) stages and the float32 refinement switch."""
-        _lib.check(self.lib.dgp_plan_set_option(self._h, int(key), int(value)), "dgp_plan_set_option")
+        self._host("dgp_plan_set_option", int(key), int(value))
 
     def get_option(self, key: int) -> int:
         v = C.c_int64()
-        _lib.check(self.lib.dgp_plan_get_option(self._h, int(key), C.byref(v)), "dgp_plan_get_option")
+        self._host("dgp_plan_get_option", int(key), C.byref(v))
         return int(v.value)
 
     def _check_vec(self, t, name, length=None):
@@ -112,14 +116,29 @@ class GPPlan:
         if not (torch.is_tensor(t) and t.is_cuda and t.dtype == self.dtype and t.is_contiguous() and t.numel() == length):
             raise ValueError(f"{name} must be a contiguous {self.dtype} CUDA tensor with {length} elements")
 
+    def _host(self, name, *args):
+        """The checked library call ``name(plan, *args)`` of an entry that takes no stream."""
+        _lib.check(getattr(self.lib, name)(self._h, *args), name)
+
+    def _call(self, name, *args):
+        """The checked library call ``name(plan, *args, stream)`` on the current stream."""
+        _lib.check(getattr(self.lib, name)(self._h, *args, _stream()), name)
+
+    def _empty(self, *tail, dtype=None):
+        """An uninitialised result of shape ``self._lead + tail`` on the plan's device, in the plan's dtype unless given."""
+        return torch.empty(self._lead + tail, dtype=dtype or self.dtype, device=self.device)
+
+    def _theta(self, theta):
+        return _theta_array(theta, self.ntheta * self.batch)
+
     def _check_xs(self, Xs):
         """The test points of an inference call: (m, d) -- (batch, m, d) for a batched plan -- in the plan's dtype, on the
-        device.  -> (lead, m), ``lead`` = the batch dimensions every result of the call starts with."""
-        lead = () if self.batch == 1 else (self.batch,)
+        device.  -> m."""
+        lead = self._lead
         if not (torch.is_tensor(Xs) and Xs.is_cuda and Xs.dtype == self.dtype and Xs.dim() == 2 + len(lead)
                 and Xs.shape[-1] == self.d and tuple(Xs.shape[:-2]) == lead):
             raise ValueError(f"Xs must be a {lead + ('m', self.d)} {self.dtype} CUDA tensor")
-        return lead, int(Xs.shape[-2])
+        return int(Xs.shape[-2])
 
     def _work_area(self, attr, need, what, check_free=False):
         """256-byte aligned base of the entry point's cached work area ``self.<attr>``, grown to ``need`` bytes: an area
@@ -143,10 +162,16 @@ class GPPlan:
         base = ws.data_ptr()
         return C.c_void_p(base + (-base) % 256)
 
+    def _sized_work(self, attr, what, query, *sizes):
+        """(base, bytes) of the work area ``self.<attr>`` at the size the library's ``query(plan, *sizes)`` reports: the
+        ``work_dev, work_bytes`` pair of the entry point."""
+        need = int(getattr(self.lib, query)(self._h, *sizes))
+        return self._work_area(attr, need, what), need
+
     def buffer(self, which: int, site: int = 0) -> torch.Tensor:
         """Tensor view of a plan buffer (tests / profiling); ``site``: which site's copy of a batched plan."""
         p, ld = C.c_void_p(), C.c_int64()
-        _lib.check(self.lib.dgp_plan_buffer(self._h, which, C.byref(p), C.byref(ld)), "dgp_plan_buffer")
+        self._host("dgp_plan_buffer", which, C.byref(p), C.byref(ld))
         if not 0 <= site < self.batch:
             raise ValueError(f"site must be in 0..{self.batch - 1}")
         esz = torch.empty((), dtype=self.dtype).element_size()
@@ -165,7 +190,7 @@ class GPPlan:
             raise ValueError(f"expected {self.batch} site sizes")
         arr = (C.c_int64 * self.batch)(*vals)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.dgp_plan_set_site_sizes(self._h, arr, _stream()), "dgp_plan_set_site_sizes")
+            self._call("dgp_plan_set_site_sizes", arr)
         self._site_sizes = vals
 
     # ------------------------------------------------------------------ hot path
@@ -173,44 +198,38 @@ class GPPlan:
         """Two device vectors (2, n) -- (batch, 2, n) for a batched plan -- for which every following fit step also
         returns sum_i dNLL/dr_i w_k[i] in ``out[..., OUT_DR_W0 + k]`` (None clears).  The plan keeps the tensor alive."""
         if w is not None:
-            shape = (2, self.n) if self.batch == 1 else (self.batch, 2, self.n)
+            shape = self._lead + (2, self.n)
             if not (torch.is_tensor(w) and w.is_cuda and w.dtype == self.dtype and tuple(w.shape) == shape
                     and w.is_contiguous()):
                 raise ValueError(f"dr weights must be a contiguous {shape} {self.dtype} CUDA tensor")
         self._dr_w = w
-        _lib.check(self.lib.dgp_plan_set_dr_weights(self._h, _ptr(w)), "dgp_plan_set_dr_weights")
+        self._host("dgp_plan_set_dr_weights", _ptr(w))
 
     def set_inputs(self, X: torch.Tensor):
         self._check_vec(X, "X", self.n * self.d)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.dgp_set_inputs(self._h, _ptr(X), _stream()), "dgp_set_inputs")
+            self._call("dgp_set_inputs", _ptr(X))
         self._X = X  # keep alive until the async pack has certainly run
+
+    def _fit(self, name, theta, r, noise, ws_query=None, grads=True):
+        """The one shape of a fit step: ``name(plan, theta, r, noise[, work, bytes], out[, dr, dnoise], stream)`` ->
+        (out[32],) or (out[32], dr[n], dnoise[n]).  ``ws_query``: the size query of an entry that takes a work area (kept in
+        ``self._loo_ws``)."""
+        self._check_vec(r, "r")
+        self._check_vec(noise, "noise")
+        th = self._theta(theta)
+        with torch.cuda.device(self.device):
+            work = () if ws_query is None else self._sized_work("_loo_ws", name, ws_query)
+            res = (self._empty(_lib.OUT_LEN),) + ((self._empty(self.n), self._empty(self.n)) if grads else ())
+            self._call(name, th, _ptr(r), _ptr(noise), *work, *map(_ptr, res))
+        return res
 
     def fit_step(self, theta, r: torch.Tensor, noise: torch.Tensor):
         """-> (out[32], alpha[n], dnoise[n]) device tensors; see include/dgp_hip.h DGP_OUT_*."""
-        self._check_vec(r, "r")
-        self._check_vec(noise, "noise")
-        th = _theta_array(theta, self.ntheta * self.batch)
-        shape = (lambda k: (k,)) if self.batch == 1 else (lambda k: (self.batch, k))
-        with torch.cuda.device(self.device):
-            out = torch.empty(shape(_lib.OUT_LEN), dtype=self.dtype, device=self.device)
-            dr = torch.empty(shape(self.n), dtype=self.dtype, device=self.device)
-            dnoise = torch.empty(shape(self.n), dtype=self.dtype, device=self.device)
-            _lib.check(
-                self.lib.dgp_fit_step(self._h, th, _ptr(r), _ptr(noise), _ptr(out), _ptr(dr), _ptr(dnoise), _stream()),
-                "dgp_fit_step",
-            )
-        return out, dr, dnoise
+        return self._fit("dgp_fit_step", theta, r, noise)
 
     def factorize(self, theta, r: torch.Tensor, noise: torch.Tensor):
-        self._check_vec(r, "r")
-        self._check_vec(noise, "noise")
-        th = _theta_array(theta, self.ntheta * self.batch)
-        with torch.cuda.device(self.device):
-            out = torch.empty(_lib.OUT_LEN if self.batch == 1 else (self.batch, _lib.OUT_LEN), dtype=self.dtype,
-                              device=self.device)
-            _lib.check(self.lib.dgp_factorize(self._h, th, _ptr(r), _ptr(noise), _ptr(out), _stream()), "dgp_factorize")
-        return out
+        return self._fit("dgp_factorize", theta, r, noise, grads=False)[0]
 
     # ------------------------------------------------------------------ leave-one-out training objective
     def loo_fit_step(self, theta, r: torch.Tensor, noise: torch.Tensor):
@@ -218,34 +237,30 @@ class GPPlan:
         -> (out, dr, dnoise) with exactly the shapes and slots of ``fit_step``, ``out[OUT_NLL]`` = L_LOO and every gradient
         slot that of L_LOO; QUAD, LOGDET, INFO are the factorisation's.  The plan holds afterwards what ``fit_step`` with the
         same arguments leaves.  float64 plans (include/dgp_hip.h ``dgp_loo_fit_step``)."""
-        self._check_vec(r, "r")
-        self._check_vec(noise, "noise")
-        th = _theta_array(theta, self.ntheta * self.batch)
-        shape = (lambda k: (k,)) if self.batch == 1 else (lambda k: (self.batch, k))
-        with torch.cuda.device(self.device):
-            need = int(self.lib.dgp_loo_workspace_bytes(self._h))
-            work = self._work_area("_loo_ws", need, "dgp_loo_fit_step")
-            out = torch.empty(shape(_lib.OUT_LEN), dtype=self.dtype, device=self.device)
-            dr = torch.empty(shape(self.n), dtype=self.dtype, device=self.device)
-            dnoise = torch.empty(shape(self.n), dtype=self.dtype, device=self.device)
-            _lib.check(
-                self.lib.dgp_loo_fit_step(self._h, th, _ptr(r), _ptr(noise), work, need, _ptr(out), _ptr(dr), _ptr(dnoise),
-                                          _stream()),
-                "dgp_loo_fit_step",
-            )
-        return out, dr, dnoise
+        return self._fit("dgp_loo_fit_step", theta, r, noise, ws_query="dgp_loo_workspace_bytes")
 
     def loo_value(self):
         """(L_LOO, info) -- (batch, 2) for a batched plan -- as float64 device tensor, from the factorisation the plan holds
         when the last step left K^^-1 in it (``fit_step`` / ``loo_fit_step``)."""
         with torch.cuda.device(self.device):
-            need = int(self.lib.dgp_loo_value_workspace_bytes(self._h))
-            work = self._work_area("_loo_ws", need, "dgp_loo_value")
-            out = torch.empty(2 if self.batch == 1 else (self.batch, 2), dtype=torch.float64, device=self.device)
-            _lib.check(self.lib.dgp_loo_value(self._h, work, need, _ptr(out), _stream()), "dgp_loo_value")
+            work = self._sized_work("_loo_ws", "dgp_loo_value", "dgp_loo_value_workspace_bytes")
+            out = self._empty(2, dtype=torch.float64)
+            self._call("dgp_loo_value", *work, _ptr(out))
         return out
 
     # ------------------------------------------------------------------ censored observations (Laplace)
+    def _check_side(self, side):
+        if not (torch.is_tensor(side) and side.is_cuda and side.dtype == torch.int32 and side.is_contiguous()
+                and side.numel() == self.n * self.batch):
+            raise ValueError(f"side must be a contiguous int32 CUDA tensor with {self.n * self.batch} elements")
+
+    def _check_censored(self, side, **vectors):
+        """``side`` and the named per-row vectors of a censored fit; only ``upper`` may be None."""
+        for what, t in vectors.items():
+            if not (what == "upper" and t is None):
+                self._check_vec(t, what)
+        self._check_side(side)
+
     def _laplace(self, with_grad, theta, y, mean, noise, side, f, maxit, tol, upper=None):
         B = self.batch
         name = ("dgp_laplace_fit_step" if with_grad else "dgp_laplace_factorize") if B == 1 else (
@@ -254,32 +269,24 @@ class GPPlan:
             name = "dgp_laplace_interval_fit_step" if with_grad else "dgp_laplace_interval_factorize"
         if self.dtype != torch.float64:
             raise ValueError(f"{name}: censored fits need a float64 " + ("single-site plan" if B == 1 else "plan"))
-        for t, what in ((y, "y"), (mean, "mean"), (noise, "noise")) + (() if upper is None else ((upper, "upper"),)):
-            self._check_vec(t, what)
-        if not (torch.is_tensor(side) and side.is_cuda and side.dtype == torch.int32 and side.is_contiguous()
-                and side.numel() == self.n * B):
-            raise ValueError(f"side must be a contiguous int32 CUDA tensor with {self.n * B} elements")
+        self._check_censored(side, y=y, mean=mean, noise=noise, upper=upper)
         if f is None:
             f = mean.clone()  # cold start
         else:
             self._check_vec(f, "f")
             f = f.clone()
-        th = _theta_array(theta, self.ntheta * B)
+        th = self._theta(theta)
         stat = (C.c_double * (4 * B))()
-        shape = (lambda k: (k,)) if B == 1 else (lambda k: (B, k))
-        fn = getattr(self.lib, name)
         with torch.cuda.device(self.device):
-            need = int((self.lib.dgp_laplace_workspace_bytes if B == 1 else self.lib.dgp_laplace_batched_workspace_bytes)(self._h))
-            work = self._work_area("_laplace_ws", need, name)
-            out = torch.empty(shape(_lib.OUT_LEN), dtype=self.dtype, device=self.device)
-            dr = torch.empty(shape(self.n), dtype=self.dtype, device=self.device) if with_grad else None
-            args = (self._h, th, _ptr(y), _ptr(mean), _ptr(noise), _ptr(side)) + (() if upper is None else (_ptr(upper),)) + (
-                _ptr(f), int(maxit), float(tol), work, need, _ptr(out))
-            rc = fn(*args, _ptr(dr), stat, _stream()) if with_grad else fn(*args, stat, _stream())
-        vals = [float(v) for v in stat]
-        # kept for a caller that catches E_NOCONV; a batched plan: one 4-tuple per site
-        self.laplace_stat = tuple(vals) if B == 1 else tuple(tuple(vals[4 * b:4 * b + 4]) for b in range(B))
-        _lib.check(rc, name)
+            work = self._sized_work("_laplace_ws", name, "dgp_laplace_workspace_bytes" if B == 1 else "dgp_laplace_batched_workspace_bytes")
+            out = self._empty(_lib.OUT_LEN)
+            dr = self._empty(self.n) if with_grad else None
+            try:
+                self._call(name, th, *(_ptr(t) for t in (y, mean, noise, side, upper, f) if t is not None), int(maxit), float(tol), *work,
+                           *(_ptr(t) for t in (out, dr) if t is not None), stat)
+            finally:  # kept for a caller that catches E_NOCONV; a batched plan: one 4-tuple per site
+                vals = [float(v) for v in stat]
+                self.laplace_stat = tuple(vals) if B == 1 else tuple(tuple(vals[4 * b:4 * b + 4]) for b in range(B))
         return (out, dr, f, self.laplace_stat) if with_grad else (out, f, self.laplace_stat)
 
     def laplace_fit_step(self, theta, y, mean, noise, side, f=None, maxit=50, tol=1e-10, upper=None):
@@ -308,11 +315,7 @@ class GPPlan:
         name = "dgp_ep_fit_step" if with_grad else "dgp_ep_factorize"
         if self.dtype != torch.float64 or self.batch != 1:
             raise ValueError(f"{name}: expectation propagation needs a float64 single-site plan")
-        for t, what in ((y, "y"), (mean, "mean"), (noise, "noise")) + (() if upper is None else ((upper, "upper"),)):
-            self._check_vec(t, what)
-        if not (torch.is_tensor(side) and side.is_cuda and side.dtype == torch.int32 and side.is_contiguous()
-                and side.numel() == self.n):
-            raise ValueError(f"side must be a contiguous int32 CUDA tensor with {self.n} elements")
+        self._check_censored(side, y=y, mean=mean, noise=noise, upper=upper)
         if sites is None:  # cold start
             yt, nt = torch.empty_like(y), torch.empty_like(noise)
         else:
@@ -320,22 +323,21 @@ class GPPlan:
             self._check_vec(yt, "sites[0]")
             self._check_vec(nt, "sites[1]")
             yt, nt = yt.clone(), nt.clone()
-        th = _theta_array(theta, self.ntheta)
+        th = self._theta(theta)
         stat = (C.c_double * 6)()
         with torch.cuda.device(self.device):
-            need = int(self.lib.dgp_ep_workspace_bytes(self._h))
-            work = self._work_area("_ep_ws", need, name)
-            out = torch.empty(_lib.OUT_LEN, dtype=self.dtype, device=self.device)
-            dr = torch.empty(self.n, dtype=self.dtype, device=self.device) if with_grad else None
-            aux = torch.empty((3, self.n), dtype=self.dtype, device=self.device)
-            args = (self._h, th, _ptr(y), _ptr(mean), _ptr(noise), _ptr(side), _ptr(upper), _ptr(yt), _ptr(nt), int(sites is None),
-                    int(maxit), float(tol), float(damping), work, need, _ptr(out))
-            tail = (stat, _ptr(aux[0]), _ptr(aux[1]), _ptr(aux[2]), _stream())
-            rc = getattr(self.lib, name)(*args, _ptr(dr), *tail) if with_grad else getattr(self.lib, name)(*args, *tail)
-        self.ep_stat = tuple(float(v) for v in stat)  # kept for a caller that catches E_NOCONV
-        self.ep_aux = {"cav_mean": aux[0], "cav_var": aux[1], "logz": aux[2]}
-        self.ep_sites = (yt, nt)
-        _lib.check(rc, name)
+            work = self._sized_work("_ep_ws", name, "dgp_ep_workspace_bytes")
+            out = self._empty(_lib.OUT_LEN)
+            dr = self._empty(self.n) if with_grad else None
+            aux = self._empty(3, self.n)
+            try:
+                self._call(name, th, _ptr(y), _ptr(mean), _ptr(noise), _ptr(side), _ptr(upper), _ptr(yt), _ptr(nt), int(sites is None),
+                           int(maxit), float(tol), float(damping), *work, *(_ptr(t) for t in (out, dr) if t is not None), stat,
+                           _ptr(aux[0]), _ptr(aux[1]), _ptr(aux[2]))
+            finally:  # kept for a caller that catches E_NOCONV
+                self.ep_stat = tuple(float(v) for v in stat)
+                self.ep_aux = {"cav_mean": aux[0], "cav_var": aux[1], "logz": aux[2]}
+                self.ep_sites = (yt, nt)
         return (out, dr, (yt, nt), self.ep_stat) if with_grad else (out, (yt, nt), self.ep_stat)
 
     def ep_fit_step(self, theta, y, mean, noise, side, sites=None, maxit=100, tol=1e-10, damping=1.0, upper=None):
@@ -356,10 +358,9 @@ class GPPlan:
     def ep_diag(self):
         """diag((K^)^-1) (n,) of the factorisation the plan holds, as an EP sweep computes it from L^-1 (``dgp_ep_diag``)."""
         with torch.cuda.device(self.device):
-            need = int(self.lib.dgp_ep_workspace_bytes(self._h))
-            work = self._work_area("_ep_ws", need, "dgp_ep_diag")
-            k = torch.empty(self.n, dtype=self.dtype, device=self.device)
-            _lib.check(self.lib.dgp_ep_diag(self._h, _ptr(k), work, need, _stream()), "dgp_ep_diag")
+            work = self._sized_work("_ep_ws", "dgp_ep_diag", "dgp_ep_workspace_bytes")
+            k = self._empty(self.n)
+            self._call("dgp_ep_diag", _ptr(k), *work)
         return k
 
     def interval_terms(self, za: torch.Tensor, delta: torch.Tensor):
@@ -372,8 +373,7 @@ class GPPlan:
             raise ValueError("za and delta must have the same length and device")
         with torch.cuda.device(za.device):
             out = torch.empty((4, za.numel()), dtype=torch.float64, device=za.device)
-            _lib.check(self.lib.dgp_debug_interval_terms(_ptr(za), _ptr(delta), za.numel(), _ptr(out), _stream()),
-                       "dgp_debug_interval_terms")
+            _call("dgp_debug_interval_terms", _ptr(za), _ptr(delta), za.numel(), _ptr(out))
         return out
 
     def censored_terms(self, z: torch.Tensor):
@@ -382,7 +382,7 @@ class GPPlan:
             raise ValueError("z must be a non-empty contiguous 1-d float64 CUDA tensor")
         with torch.cuda.device(z.device):
             out = torch.empty((4, z.numel()), dtype=torch.float64, device=z.device)
-            _lib.check(self.lib.dgp_debug_censored_terms(_ptr(z), z.numel(), _ptr(out), _stream()), "dgp_debug_censored_terms")
+            _call("dgp_debug_censored_terms", _ptr(z), z.numel(), _ptr(out))
         return out
 
     def bilinear(self, theta, u: torch.Tensor, alpha: torch.Tensor):
@@ -391,14 +391,37 @@ class GPPlan:
         self._check_vec(u, "u")
         self._check_vec(alpha, "alpha")
         B = self.batch
-        th = _theta_array(theta, self.ntheta * B)
+        th = self._theta(theta)
         name = "dgp_debug_bilinear" if B == 1 else "dgp_debug_bilinear_batched"
         with torch.cuda.device(self.device):
-            need = int((self.lib.dgp_laplace_workspace_bytes if B == 1 else self.lib.dgp_laplace_batched_workspace_bytes)(self._h))
-            work = self._work_area("_laplace_ws", need, name)
-            out = torch.empty(self.ntheta if B == 1 else (B, self.ntheta), dtype=self.dtype, device=self.device)
-            _lib.check(getattr(self.lib, name)(self._h, th, _ptr(u), _ptr(alpha), work, need, _ptr(out), _stream()), name)
+            work = self._sized_work("_laplace_ws", name, "dgp_laplace_workspace_bytes" if B == 1 else "dgp_laplace_batched_workspace_bytes")
+            out = self._empty(self.ntheta)
+            self._call(name, th, _ptr(u), _ptr(alpha), *work, _ptr(out))
         return out
+
+    def _chunks(self, Xs, outs, chunk, planes, ws_attr, what, ws_query, sizes, call):
+        """The chunk loop of every per-point product.  ``outs``: the result tensors, the m test points their last dimension,
+        None for a result that was not asked for (a null pointer for the library).  For every ``chunk`` points -- None:
+        16384 // (batch planes) rounded down to a multiple of 128, at least 128; the work areas are batch x 2 planes N x
+        chunk elements -- the work area ``self.<ws_attr>`` is grown to ``ws_query(plan, points, *sizes)`` bytes and
+        ``call(xs, points, work, bytes, *pointers)`` makes the checked library call.  A chunk's columns ``out[..., lo:hi]``
+        are written in place where they are contiguous (the whole range; a range of an unbatched (m,) result) and staged in
+        a fresh tensor and copied back otherwise.  -> ``outs``."""
+        if chunk is None:
+            chunk = max(128, (16384 // (self.batch * planes)) // 128 * 128)
+        m = int(Xs.shape[-2])
+        with torch.cuda.device(self.device):
+            for lo in range(0, m, chunk):
+                hi = min(lo + chunk, m)
+                xs = Xs[..., lo:hi, :].contiguous()
+                work = self._sized_work(ws_attr, what, ws_query, hi - lo, *sizes)
+                cols = [None if t is None else t[..., lo:hi] for t in outs]
+                stage = [c if c is None or c.is_contiguous() else torch.empty(c.shape, dtype=c.dtype, device=c.device) for c in cols]
+                call(xs, hi - lo, *work, *map(_ptr, stage))
+                for c, s in zip(cols, stage):
+                    if s is not c:
+                        c.copy_(s)
+        return outs
 
     def predict(self, theta, Xs: torch.Tensor, chunk: int | None = None):
         """Latent posterior (K*^T alpha, diag(K** - K*^T K^^-1 K*)) at Xs (m, d) from the held factorisation.
@@ -407,59 +430,12 @@ class GPPlan:
         ``chunk`` = prediction points per launch sequence.  The work area is batch x 2 N x chunk elements (cross Gram and
         V = L^-1 K* per site), so the default is 16384 // batch rounded down to a multiple of 128 (at least 128): a
         batched prediction then needs no more work memory than a single site's (n = 8192 fp64: 2.1 GB)."""
-        if chunk is None:
-            chunk = max(128, (16384 // self.batch) // 128 * 128)
-        lead, m = self._check_xs(Xs)
-        th = _theta_array(theta, self.ntheta * self.batch)
-        mean = torch.empty(lead + (m,), dtype=self.dtype, device=self.device)
-        var = torch.empty(lead + (m,), dtype=self.dtype, device=self.device)
-        with torch.cuda.device(self.device):
-            for lo in range(0, m, chunk):
-                hi = min(lo + chunk, m)
-                whole = lo == 0 and hi == m
-                xs = Xs[..., lo:hi, :].contiguous()
-                need = int(self.lib.dgp_predict_workspace_bytes(self._h, hi - lo))
-                work = self._work_area("_pred_ws", need, "prediction")
-                # a chunk of a batched prediction is not contiguous inside (batch, m): stage it
-                mo = mean if (whole or not lead) else torch.empty(lead + (hi - lo,), dtype=self.dtype, device=self.device)
-                vo = var if (whole or not lead) else torch.empty_like(mo)
-                mp = mo if (whole or lead) else mean[lo:hi]
-                vp = vo if (whole or lead) else var[lo:hi]
-                _lib.check(self.lib.dgp_predict(self._h, th, _ptr(xs), hi - lo, work, need, _ptr(mp), _ptr(vp), _stream()),
-                           "dgp_predict")
-                if lead and not whole:
-                    mean[:, lo:hi] = mo
-                    var[:, lo:hi] = vo
-        return mean, var
+        m, th = self._check_xs(Xs), self._theta(theta)
 
-    def _predict_planes(self, call, ws_attr, ws_bytes, theta, Xs, planes, packed, chunk, return_cov):
-        """The chunk loop of the per-point posterior products that return ``planes`` mean rows and ``packed`` rows of a packed
-        covariance per point: -> (mean (..., planes, m), cov (..., packed, m) or None).  ``ws_bytes(m)``: bytes of the work
-        area for m points, kept in ``self.<ws_attr>``; ``call(th, xs, m, work, need, mean_ptr, cov_ptr)``: the checked
-        library call for one chunk.  ``chunk`` None: 16384 // (batch planes) rounded down to a multiple of 128 (at least
-        128) -- the work area is batch x 2 planes N x chunk elements."""
-        if chunk is None:
-            chunk = max(128, (16384 // (self.batch * planes)) // 128 * 128)
-        lead, m = self._check_xs(Xs)
-        th = _theta_array(theta, self.ntheta * self.batch)
-        mean = torch.empty(lead + (planes, m), dtype=self.dtype, device=self.device)
-        cov = torch.empty(lead + (packed, m), dtype=self.dtype, device=self.device) if return_cov else None
-        with torch.cuda.device(self.device):
-            for lo in range(0, m, chunk):
-                hi = min(lo + chunk, m)
-                whole = lo == 0 and hi == m
-                xs = Xs[..., lo:hi, :].contiguous()
-                need = int(ws_bytes(hi - lo))
-                work = self._work_area(ws_attr, need, "prediction")
-                # a chunk is a column range of the (..., planes, m) results: stage it
-                mo = mean if whole else torch.empty(lead + (planes, hi - lo), dtype=self.dtype, device=self.device)
-                co = cov if (whole or cov is None) else torch.empty(lead + (packed, hi - lo), dtype=self.dtype, device=self.device)
-                call(th, xs, hi - lo, work, need, _ptr(mo), _ptr(co))
-                if not whole:
-                    mean[..., lo:hi] = mo
-                    if cov is not None:
-                        cov[..., lo:hi] = co
-        return mean, cov
+        def call(xs, k, work, need, mean_ptr, var_ptr):
+            self._call("dgp_predict", th, _ptr(xs), k, work, need, mean_ptr, var_ptr)
+
+        return self._chunks(Xs, (self._empty(m), self._empty(m)), chunk, 1, "_pred_ws", "prediction", "dgp_predict_workspace_bytes", (), call)
 
     def predict_terms(self, theta, Xs: torch.Tensor, chunk: int | None = None, return_cov: bool = True):
         """Latent posterior of every ADDITIVE PART of the covariance at Xs (m, d) from the held factorisation
@@ -470,14 +446,13 @@ class GPPlan:
         theta (batch, ntheta) -> (batch, C, m), (batch, C (C + 1) / 2, m).  ``return_cov=False`` -> (mean, None).
         ``chunk`` = points per launch sequence; the work area is batch x 2 C N x chunk elements, so the default is
         16384 // (batch C) rounded down to a multiple of 128 (at least 128)."""
-        Cn = self.nterms
+        Cn, m, th = self.nterms, self._check_xs(Xs), self._theta(theta)
+        outs = self._empty(Cn, m), self._empty(Cn * (Cn + 1) // 2, m) if return_cov else None
 
-        def call(th, xs, m, work, need, mean_ptr, cov_ptr):
-            _lib.check(self.lib.dgp_predict_terms(self._h, th, _ptr(xs), m, work, need, mean_ptr, cov_ptr, _stream()),
-                       "dgp_predict_terms")
+        def call(xs, k, work, need, mean_ptr, cov_ptr):
+            self._call("dgp_predict_terms", th, _ptr(xs), k, work, need, mean_ptr, cov_ptr)
 
-        return self._predict_planes(call, "_terms_ws", lambda m: self.lib.dgp_predict_terms_workspace_bytes(self._h, m),
-                                    theta, Xs, Cn, Cn * (Cn + 1) // 2, chunk, return_cov)
+        return self._chunks(Xs, outs, chunk, Cn, "_terms_ws", "prediction", "dgp_predict_terms_workspace_bytes", (), call)
 
     def predict_slopes(self, theta, Xs: torch.Tensor, cols, chunk: int | None = None, return_cov: bool = True):
         """Latent posterior of the fit and of its DERIVATIVES with respect to the raw input columns ``cols`` (distinct, in
@@ -496,13 +471,13 @@ class GPPlan:
             if int(self.lib.dgp_model_input_differentiable(mid, self.d, c)) != 1:
                 raise ValueError(f"the covariance is not differentiable in column {c} (Matern-1/2 factor)")
         Pn, carr = 1 + len(cols), (C.c_int * len(cols))(*cols)
+        m, th = self._check_xs(Xs), self._theta(theta)
+        outs = self._empty(Pn, m), self._empty(Pn * (Pn + 1) // 2, m) if return_cov else None
 
-        def call(th, xs, m, work, need, mean_ptr, cov_ptr):
-            _lib.check(self.lib.dgp_predict_slopes(self._h, th, _ptr(xs), m, carr, len(cols), work, need, mean_ptr, cov_ptr,
-                                                   _stream()), "dgp_predict_slopes")
+        def call(xs, k, work, need, mean_ptr, cov_ptr):
+            self._call("dgp_predict_slopes", th, _ptr(xs), k, carr, len(cols), work, need, mean_ptr, cov_ptr)
 
-        return self._predict_planes(call, "_slopes_ws", lambda m: self.lib.dgp_predict_slopes_workspace_bytes(self._h, m, len(cols)),
-                                    theta, Xs, Pn, Pn * (Pn + 1) // 2, chunk, return_cov)
+        return self._chunks(Xs, outs, chunk, Pn, "_slopes_ws", "prediction", "dgp_predict_slopes_workspace_bytes", (len(cols),), call)
 
     # ------------------------------------------------------------------ cross-validation
     def cross_validate(self, groups, max_group=None):
@@ -519,7 +494,6 @@ class GPPlan:
         return cross_validate_folds(self, groups, self._cv_launch, max_group)
 
     def _cv_launch(self, order, start, ngroups, max_group):
-        lead = () if self.batch == 1 else (self.batch,)
         need = int(self.lib.dgp_cross_validate_workspace_bytes(self._h, ngroups, max_group))
         if need == 0:
             raise ValueError(f"bad size: ngroups = {ngroups}, max_group = {max_group} (both in 1..n)")
@@ -527,15 +501,10 @@ class GPPlan:
             work = self._work_area("_cv_ws", need, "cross-validation")
             order = order.to(self.device).contiguous()
             start = start.to(self.device).contiguous()
-            resid = torch.empty(lead + (self.n,), dtype=torch.float64, device=self.device)
-            var = torch.empty_like(resid)
-            lpd = torch.empty(lead + (ngroups,), dtype=torch.float64, device=self.device)
-            info = torch.empty(lead + (ngroups,), dtype=torch.int32, device=self.device)
-            _lib.check(
-                self.lib.dgp_cross_validate(self._h, _ptr(order), _ptr(start), ngroups, max_group, work, need,
-                                            _ptr(resid), _ptr(var), _ptr(lpd), _ptr(info), _stream()),
-                "dgp_cross_validate",
-            )
+            resid, var = self._empty(self.n, dtype=torch.float64), self._empty(self.n, dtype=torch.float64)
+            lpd, info = self._empty(ngroups, dtype=torch.float64), self._empty(ngroups, dtype=torch.int32)
+            self._call("dgp_cross_validate", _ptr(order), _ptr(start), ngroups, max_group, work, need, _ptr(resid), _ptr(var),
+                       _ptr(lpd), _ptr(info))
         return resid, var, lpd, info
 
     def laplace_cross_validate(self, theta, y, mean, noise, side, f, groups, upper=None, shift=0.0, max_group=None):
@@ -552,11 +521,8 @@ class GPPlan:
             raise NotImplementedError("laplace_cross_validate: batched plans are not supported (validate each site on its own plan)")
         if self.dtype != torch.float64:
             raise ValueError("laplace_cross_validate: censored fits need a float64 single-site plan")
-        for t, what in ((y, "y"), (mean, "mean"), (noise, "noise"), (f, "f")) + (() if upper is None else ((upper, "upper"),)):
-            self._check_vec(t, what)
-        if not (torch.is_tensor(side) and side.is_cuda and side.dtype == torch.int32 and side.is_contiguous() and side.numel() == self.n):
-            raise ValueError(f"side must be a contiguous int32 CUDA tensor with {self.n} elements")
-        th = _theta_array(theta, self.ntheta)
+        self._check_censored(side, y=y, mean=mean, noise=noise, f=f, upper=upper)
+        th = self._theta(theta)
 
         def launch(order, start, ngroups, mg):
             need = int(self.lib.dgp_laplace_cross_validate_workspace_bytes(self._h, ngroups, mg))
@@ -566,14 +532,10 @@ class GPPlan:
                 work = self._work_area("_lcv_ws", need, "cross-validation of a censored fit")
                 order = order.to(self.device).contiguous()
                 start = start.to(self.device).contiguous()
-                out = torch.empty((len(_lib.LCV_PLANE_NAMES), self.n), dtype=torch.float64, device=self.device)
-                info = torch.empty(ngroups, dtype=torch.int32, device=self.device)
-                _lib.check(
-                    self.lib.dgp_laplace_cross_validate(self._h, th, _ptr(y), _ptr(mean), _ptr(noise), _ptr(side), _ptr(upper), _ptr(f),
-                                                        _ptr(order), _ptr(start), ngroups, mg, float(shift), work, need, _ptr(out),
-                                                        _ptr(info), _stream()),
-                    "dgp_laplace_cross_validate",
-                )
+                out = self._empty(len(_lib.LCV_PLANE_NAMES), self.n, dtype=torch.float64)
+                info = self._empty(ngroups, dtype=torch.int32)
+                self._call("dgp_laplace_cross_validate", th, _ptr(y), _ptr(mean), _ptr(noise), _ptr(side), _ptr(upper), _ptr(f),
+                           _ptr(order), _ptr(start), ngroups, mg, float(shift), work, need, _ptr(out), _ptr(info))
             res = {name: out[k] for k, name in enumerate(_lib.LCV_PLANE_NAMES)}
             res["info"] = info
             return res
@@ -589,17 +551,8 @@ class GPPlan:
         (derivatives of learned noise terms; None: none).  -> (P + E, P + E) -- (batch, P + E, P + E) -- float64 device
         tensor, bitwise symmetric, in un-normalised log-likelihood units.  The work area of (P + E + 1) N^2 elements per
         site is kept between calls; ``max_bytes``: raise ``ValueError`` naming the bytes instead of allocating more."""
-        lead = () if self.batch == 1 else (self.batch,)
-        th = _theta_array(theta, self.ntheta * self.batch)
-        E = 0
-        if diag is not None:
-            if not (torch.is_tensor(diag) and diag.is_cuda and diag.dtype == self.dtype and diag.dim() == 2 + len(lead)
-                    and tuple(diag.shape[:-2]) == lead and diag.shape[-1] == self.n):
-                raise ValueError(f"diag must be a {lead + ('E', self.n)} {self.dtype} CUDA tensor")
-            E = int(diag.shape[-2])
-            if E > 8:
-                raise ValueError(f"at most 8 diagonal directions, got {E}")
-            diag = diag.contiguous() if E else None
+        th = self._theta(theta)
+        diag, E = self._check_columns(diag, "diag")
         need = int(self.lib.dgp_fisher_workspace_bytes(self._h, E))
         if max_bytes is not None and need > int(max_bytes):
             raise ValueError(f"the Fisher information of {self.ntheta + E} directions at n = {self.n} (batch {self.batch}) needs a "
@@ -607,15 +560,16 @@ class GPPlan:
         nd = self.ntheta + E
         with torch.cuda.device(self.device):
             work = self._work_area("_fisher_ws", need, "dgp_fisher")
-            out = torch.empty(lead + (nd, nd), dtype=torch.float64, device=self.device)
-            _lib.check(self.lib.dgp_fisher(self._h, th, _ptr(diag), E, work, need, _ptr(out), _stream()), "dgp_fisher")
+            out = self._empty(nd, nd, dtype=torch.float64)
+            self._call("dgp_fisher", th, _ptr(diag), E, work, need, _ptr(out))
         return out
 
     # ------------------------------------------------------------------ Jacobians of the prediction w.r.t. the hyperparameters
-    def _check_columns(self, cols, name, lead):
+    def _check_columns(self, cols, name):
         """A (K, n) -- (batch, K, n) -- device tensor of per-training-row columns in the plan's dtype, K <= 8 -> (tensor or None, K)."""
         if cols is None:
             return None, 0
+        lead = self._lead
         if not (torch.is_tensor(cols) and cols.is_cuda and cols.dtype == self.dtype and cols.dim() == 2 + len(lead)
                 and tuple(cols.shape[:-2]) == lead and cols.shape[-1] == self.n):
             raise ValueError(f"{name} must be a {lead + ('K', self.n)} {self.dtype} CUDA tensor")
@@ -636,32 +590,17 @@ class GPPlan:
         caller builds from them and a covariance of the hyperparameters is first order in that covariance (delta method).
         ``chunk`` = points per launch sequence: the chunks' results are independent, so their concatenation is exact.  The
         work area is batch x (P N^2 + 3 N chunk) elements; default chunk as for ``predict``."""
-        if chunk is None:
-            chunk = max(128, (16384 // self.batch) // 128 * 128)
-        lead, m = self._check_xs(Xs)
-        th = _theta_array(theta, self.ntheta * self.batch)
-        diag, E = self._check_columns(diag, "diag", lead)
-        rhs, Cn = self._check_columns(rhs, "rhs", lead)
-        R, Rv = self.ntheta + E + Cn, self.ntheta + E
-        dmean = torch.empty(lead + (R, m), dtype=torch.float64, device=self.device)
-        dvar = torch.empty(lead + (Rv, m), dtype=torch.float64, device=self.device) if return_var else None
-        with torch.cuda.device(self.device):
-            for lo in range(0, m, chunk):
-                hi = min(lo + chunk, m)
-                whole = lo == 0 and hi == m
-                xs = Xs[..., lo:hi, :].contiguous()
-                need = int(self.lib.dgp_predict_sensitivity_workspace_bytes(self._h, hi - lo, E, Cn))
-                work = self._work_area("_sens_ws", need, "dgp_predict_sensitivity")
-                # a chunk is a column range of the (..., rows, m) results: stage it
-                mo = dmean if whole else torch.empty(lead + (R, hi - lo), dtype=torch.float64, device=self.device)
-                vo = dvar if (whole or dvar is None) else torch.empty(lead + (Rv, hi - lo), dtype=torch.float64, device=self.device)
-                _lib.check(self.lib.dgp_predict_sensitivity(self._h, th, _ptr(xs), hi - lo, _ptr(diag), E, _ptr(rhs), Cn, work, need,
-                                                            _ptr(mo), _ptr(vo), _stream()), "dgp_predict_sensitivity")
-                if not whole:
-                    dmean[..., lo:hi] = mo
-                    if dvar is not None:
-                        dvar[..., lo:hi] = vo
-        return dmean, dvar
+        m, th = self._check_xs(Xs), self._theta(theta)
+        diag, E = self._check_columns(diag, "diag")
+        rhs, Cn = self._check_columns(rhs, "rhs")
+        dmean = self._empty(self.ntheta + E + Cn, m, dtype=torch.float64)
+        dvar = self._empty(self.ntheta + E, m, dtype=torch.float64) if return_var else None
+
+        def call(xs, k, work, need, dmean_ptr, dvar_ptr):
+            self._call("dgp_predict_sensitivity", th, _ptr(xs), k, _ptr(diag), E, _ptr(rhs), Cn, work, need, dmean_ptr, dvar_ptr)
+
+        return self._chunks(Xs, (dmean, dvar), chunk, 1, "_sens_ws", "dgp_predict_sensitivity",
+                            "dgp_predict_sensitivity_workspace_bytes", (E, Cn), call)
 
     # ------------------------------------------------------------------ influence of the held samples on the period sums
     def deletion_influence(self, theta, Xs: torch.Tensor, groups, a, scale, periods, nperiods: int, mode: int, inv_sd=None,
@@ -680,8 +619,7 @@ class GPPlan:
         fold id, with a leading batch dimension for a batched plan; float64.  Sign: the sum WITHOUT the fold minus the sum with
         it.  The call is never cut into chunks of test points (sums over chunks would not be bitwise chunk-invariant): a work
         area above ``max_bytes`` raises ``ValueError`` naming the bytes."""
-        lead, m = self._check_xs(Xs)
-        th = _theta_array(theta, self.ntheta * self.batch)
+        lead, m, th = self._lead, self._check_xs(Xs), self._theta(theta)
         P, mode = int(nperiods), int(mode)
         if mode not in (MODE_LINEAR, MODE_LOG):
             raise ValueError(f"mode must be {MODE_LINEAR} (linear) or {MODE_LOG} (log)")
@@ -702,16 +640,12 @@ class GPPlan:
                     raise ValueError(f"inv_sd must have shape {lead + (m,)}")
                 work = self._work_area("_influence_ws", need, "dgp_deletion_influence", check_free=True)
                 order, start, xs = order.to(dev).contiguous(), start.to(dev).contiguous(), Xs.contiguous()
-                dload = torch.empty(lead + (nfolds, P), dtype=torch.float64, device=dev)
+                dload = self._empty(nfolds, P, dtype=torch.float64)
                 dvar = torch.empty_like(dload) if mode == MODE_LINEAR else None
-                shift = torch.empty(lead + (nfolds,), dtype=torch.float64, device=dev) if sd_t is not None else None
-                info = torch.empty(lead + (nfolds,), dtype=torch.int32, device=dev)
-                _lib.check(
-                    self.lib.dgp_deletion_influence(self._h, th, _ptr(xs), m, _ptr(order), _ptr(start), nfolds, max_fold, mode, _ptr(a_t),
-                                                    _ptr(s_t), _ptr(g_t), P, _ptr(sd_t), work, need, _ptr(dload), _ptr(dvar), _ptr(shift),
-                                                    _ptr(info), _stream()),
-                    "dgp_deletion_influence",
-                )
+                shift = self._empty(nfolds, dtype=torch.float64) if sd_t is not None else None
+                info = self._empty(nfolds, dtype=torch.int32)
+                self._call("dgp_deletion_influence", th, _ptr(xs), m, _ptr(order), _ptr(start), nfolds, max_fold, mode, _ptr(a_t),
+                           _ptr(s_t), _ptr(g_t), P, _ptr(sd_t), work, need, _ptr(dload), _ptr(dvar), _ptr(shift), _ptr(info))
             return dload, dvar, shift, info
 
         return cross_validate_folds(self, groups, launch, max_group)
@@ -720,7 +654,7 @@ class GPPlan:
         """L^-1 cols through the inverse factor T the plan holds, for the few columns of a prior-mean Jacobian:
         (L^-1 J)^T (L^-1 J) = J^T K^^-1 J, the mean block of the Fisher information.  ``cols`` (n_site, k) on the device
         -> (n_site, k) float64.  One triangular n x n by n x k product; reads T only."""
-        ns = int((getattr(self, "_site_sizes", None) or [self.n] * self.batch)[site])
+        ns = self._site_sizes[site]
         if not (torch.is_tensor(cols) and cols.is_cuda and cols.dim() == 2 and cols.shape[0] == ns):
             raise ValueError(f"cols must be a ({ns}, k) CUDA tensor")
         with torch.cuda.device(self.device):
@@ -738,19 +672,13 @@ class GPPlan:
         """(K*^T alpha, latent posterior covariance K** - V^T V) at Xs (m, d): the covariance as an (M, M) tensor,
         M = padded m, lower triangle valid (diagonal 128-blocks complete), identity pad -- ``dgp_posterior_cov``.
         Batched plans: Xs (batch, m, d), theta (batch, ntheta) -> mean (batch, m), cov (batch, M, M), one launch sequence."""
-        lead, m = self._check_xs(Xs)
-        th = _theta_array(theta, self.ntheta * self.batch)
+        m, th = self._check_xs(Xs), self._theta(theta)
         M = int(self.lib.dgp_padded_n(m))
         with torch.cuda.device(self.device):
             xs = Xs.contiguous()
-            need = int(self.lib.dgp_predict_workspace_bytes(self._h, m))
-            work = self._work_area("_pred_ws", need, "prediction")
-            mean = torch.empty(lead + (m,), dtype=self.dtype, device=self.device)
-            cov = torch.empty(lead + (M, M), dtype=self.dtype, device=self.device)
-            _lib.check(
-                self.lib.dgp_posterior_cov(self._h, th, _ptr(xs), m, work, need, _ptr(mean), _ptr(cov), _stream()),
-                "dgp_posterior_cov",
-            )
+            work = self._sized_work("_pred_ws", "prediction", "dgp_predict_workspace_bytes", m)
+            mean, cov = self._empty(m), self._empty(M, M)
+            self._call("dgp_posterior_cov", th, _ptr(xs), m, *work, _ptr(mean), _ptr(cov))
         return mean, cov
 
     def psd_safe_factor(self, cov: torch.Tensor, m: int):
@@ -797,52 +725,36 @@ class GPPlan:
             z = torch.randn(M, Q, dtype=self.dtype, device=self.device, generator=generator)
             out = torch.empty(ndraw, m, dtype=self.dtype, device=self.device)
             mp = _ptr(mean.contiguous() if mean is not None else None)
-            _lib.check(self.lib.dgp_sample_draws(_DTYPES[self.dtype], _ptr(Lbuf), m, _ptr(z), ndraw, mp, _ptr(out), _stream()),
-                       "dgp_sample_draws")
+            _call("dgp_sample_draws", _DTYPES[self.dtype], _ptr(Lbuf), m, _ptr(z), ndraw, mp, _ptr(out))
         self._last_z = z
         return out
 
     def period_moments(self, cov, m: int, mu, scale2, w, groups, ngroups: int, mode: int, extra_var=None):
-        """Exact mean and covariance of period sums of the transformed posterior (``dgp_period_moments``): see the
-        module-level ``period_moments``.  Unbatched (cov (M, M), vectors (m,)) -> mean (P,), cov (P, P); batched
-        (cov (B, M, M), vectors (B, m)) -> (B, P), (B, P, P); all fp64 device tensors."""
-        with torch.cuda.device(self.device):
-            return period_moments(cov, m, mu, scale2, w, groups, ngroups, mode, extra_var)
+        """The module-level ``period_moments``."""
+        return period_moments(cov, m, mu, scale2, w, groups, ngroups, mode, extra_var)
 
     def period_third_moments(self, cov, m: int, mu, scale2, w, groups, ngroups: int, extra_var=None, tile: int = 0):
-        """Exact third central moment of the period sums of a log-transformed posterior (``dgp_period_third_moments``): see
-        the module-level ``period_third_moments``.  Unbatched -> k3 (P,); batched -> (B, P); fp64 device tensors."""
-        with torch.cuda.device(self.device):
-            return period_third_moments(cov, m, mu, scale2, w, groups, ngroups, extra_var, tile)
+        """The module-level ``period_third_moments``."""
+        return period_third_moments(cov, m, mu, scale2, w, groups, ngroups, extra_var, tile)
 
     def exceedance_moments(self, cov, m: int, mu, thresh, w, groups, ngroups: int, extra_var=None):
-        """Exact mean and covariance of threshold-exceedance counts of the posterior (``dgp_exceedance_moments``): see the
-        module-level ``exceedance_moments``.  Unbatched (cov (M, M), vectors (m,), thresh (L, m)) -> mean (L, P), cov
-        (L, P, P); batched (cov (B, M, M), vectors (B, m), thresh (B, L, m)) -> (B, L, P), (B, L, P, P); fp64 device tensors."""
-        with torch.cuda.device(self.device):
-            return exceedance_moments(cov, m, mu, thresh, w, groups, ngroups, extra_var)
+        """The module-level ``exceedance_moments``."""
+        return exceedance_moments(cov, m, mu, thresh, w, groups, ngroups, extra_var)
 
     def window_moments(self, cov, m: int, mu, lo, hi, a=None, mode: int = 0, scale2=None):
-        """Exact mean and covariance of rolling-window means of the posterior (``dgp_window_moments``): see the module-level
-        ``window_moments``.  Unbatched (cov (M, M), mu (m,), lo / hi (q,)) -> mean (q,), cov (Q, Q); batched (cov (B, M, M),
-        vectors (B, .)) -> (B, q), (B, Q, Q); fp64 device tensors, ``cov`` in the layout of ``posterior_cov``."""
-        with torch.cuda.device(self.device):
-            return window_moments(cov, m, mu, lo, hi, a=a, mode=mode, scale2=scale2)
+        """The module-level ``window_moments``."""
+        return window_moments(cov, m, mu, lo, hi, a=a, mode=mode, scale2=scale2)
 
     def sample_value(self, cov, m: int, a, scale2, groups, ngroups: int, obs_var=None, rows=None, nterms=None):
-        """Expected reduction of every period sum's variance by one more sample on each day (``dgp_sample_value``): see the
-        module-level ``sample_value``.  Unbatched (cov (M, M), vectors (m,), rows (nrows, m)) -> gain (P, m), var (m,);
-        batched (cov (B, M, M), vectors (B, m), rows (B, nrows, m)) -> (B, P, m), (B, m); fp64 device tensors."""
-        with torch.cuda.device(self.device):
-            return sample_value(cov, m, a, scale2, groups, ngroups, obs_var=obs_var, rows=rows, nterms=nterms)
+        """The module-level ``sample_value``."""
+        return sample_value(cov, m, a, scale2, groups, ngroups, obs_var=obs_var, rows=rows, nterms=nterms)
 
     def posterior_period_moments(self, theta, Xs: torch.Tensor, mu, scale2, w, groups, ngroups: int, mode: int, extra_var=None):
         """``period_moments`` of the posterior at Xs straight from the held factorisation (``dgp_posterior_period_moments``):
         the (M, M) covariance is never formed.  Xs (m, d) -- (batch, m, d) for a batched plan, theta (batch, ntheta) --; the
         other arguments as for ``period_moments``.  The work area (2 N M plan-dtype elements + M P doubles per site) is kept
         between calls; a ``RuntimeError`` names its bytes when it exceeds the free device memory."""
-        lead, m = self._check_xs(Xs)
-        th = _theta_array(theta, self.ntheta * self.batch)
+        lead, m, th = self._lead, self._check_xs(Xs), self._theta(theta)
         P = int(ngroups)
         need = int(self.lib.dgp_posterior_period_moments_workspace_bytes(self._h, m, P))
         if need == 0:
@@ -852,13 +764,9 @@ class GPPlan:
             mu_t, w_t, g_t, ev_t, s2 = _moment_inputs(dev, self.dtype, lead, m, mu, w, groups, extra_var, scale2)
             work = self._work_area("_ppm_ws", need, "dgp_posterior_period_moments", check_free=True)
             xs = Xs.contiguous()
-            mean_out = torch.empty(lead + (P,), dtype=torch.float64, device=dev)
-            cov_out = torch.empty(lead + (P, P), dtype=torch.float64, device=dev)
-            _lib.check(
-                self.lib.dgp_posterior_period_moments(self._h, th, _ptr(xs), m, int(mode), _ptr(mu_t), _ptr(s2), _ptr(w_t), _ptr(g_t), P,
-                                                      _ptr(ev_t), work, need, _ptr(mean_out), _ptr(cov_out), _stream()),
-                "dgp_posterior_period_moments",
-            )
+            mean_out, cov_out = self._empty(P, dtype=torch.float64), self._empty(P, P, dtype=torch.float64)
+            self._call("dgp_posterior_period_moments", th, _ptr(xs), m, int(mode), _ptr(mu_t), _ptr(s2), _ptr(w_t), _ptr(g_t), P,
+                       _ptr(ev_t), work, need, _ptr(mean_out), _ptr(cov_out))
         return mean_out, cov_out
 
     def posterior_exceedance_moments(self, theta, Xs: torch.Tensor, mu, thresh, w, groups, ngroups: int, extra_var=None,
@@ -873,15 +781,12 @@ class GPPlan:
         parallelism of its own rows -- measured 3 x the dense path's time with 512-row panels at m = 14 610 (EXPERIMENTS.md) --
         so give ``max_bytes`` what the device can spare, above all with many levels.  The work area (2 N M + R M plan-dtype elements and M P min(L, 8) + 2 M (L + 1) doubles per
         site) is kept between calls; a ``RuntimeError`` names its bytes when it exceeds the free device memory."""
-        lead, m = self._check_xs(Xs)
-        th = _theta_array(theta, self.ntheta * self.batch)
+        lead, m, th = self._lead, self._check_xs(Xs), self._theta(theta)
         P = int(ngroups)
         dev = self.device
         with torch.cuda.device(dev):
             mu_t, w_t, g_t, ev_t, _ = _moment_inputs(dev, self.dtype, lead, m, mu, w, groups, extra_var)
-            u_t = torch.as_tensor(thresh).to(dev, torch.float64).contiguous()
-            if u_t.dim() != len(lead) + 2 or tuple(u_t.shape[:-2]) != lead or u_t.shape[-1] != m:
-                raise ValueError(f"thresh must have shape {lead + ('L', m)}")
+            u_t = _row_matrix(thresh, "thresh", "L", lead, m, dev)
             L = int(u_t.shape[-2])
             R = self.exceedance_panel_rows(m, P, L, max_bytes) if panel_rows is None else int(panel_rows)
             if R <= 0 or R % 128:
@@ -892,13 +797,9 @@ class GPPlan:
                                  "1 <= levels <= 64)")
             work = self._work_area("_pex_ws", need, "dgp_posterior_exceedance_moments", check_free=True)
             xs = Xs.contiguous()
-            mean_out = torch.empty(lead + (L, P), dtype=torch.float64, device=dev)
-            cov_out = torch.empty(lead + (L, P, P), dtype=torch.float64, device=dev)
-            _lib.check(
-                self.lib.dgp_posterior_exceedance_moments(self._h, th, _ptr(xs), m, _ptr(mu_t), _ptr(u_t), L, _ptr(w_t), _ptr(g_t), P,
-                                                          _ptr(ev_t), R, work, need, _ptr(mean_out), _ptr(cov_out), _stream()),
-                "dgp_posterior_exceedance_moments",
-            )
+            mean_out, cov_out = self._empty(L, P, dtype=torch.float64), self._empty(L, P, P, dtype=torch.float64)
+            self._call("dgp_posterior_exceedance_moments", th, _ptr(xs), m, _ptr(mu_t), _ptr(u_t), L, _ptr(w_t), _ptr(g_t), P,
+                       _ptr(ev_t), R, work, need, _ptr(mean_out), _ptr(cov_out))
         return mean_out, cov_out
 
     def exceedance_panel_rows(self, m: int, ngroups: int, nlevels: int, max_bytes=None) -> int:
@@ -914,38 +815,28 @@ class GPPlan:
         M = int(self.lib.dgp_padded_n(int(m)))
         return stream_panel_rows(size(128), size(256) - size(128) if M > 128 else 0, M, max_bytes)
 
-    def _vjp_workspace(self, m):
-        need = int(self.lib.dgp_mean_vjp_workspace_bytes(self._h, m))
-        return self._work_area("_vjp_ws", need, "mean / vjp"), need
-
     def predict_mean(self, theta, Xs: torch.Tensor):
         """K(X*, X) alpha from the held factorisation (no variance work).  Batched plans: Xs (batch, m, d) -> (batch, m)."""
-        th = _theta_array(theta, self.ntheta * self.batch)
-        lead, m = self._check_xs(Xs)
+        th, m = self._theta(theta), self._check_xs(Xs)
         with torch.cuda.device(self.device):
             xs = Xs.contiguous()
-            work, need = self._vjp_workspace(m)
-            mean = torch.empty(lead + (m,), dtype=self.dtype, device=self.device)
-            _lib.check(self.lib.dgp_predict_mean(self._h, th, _ptr(xs), m, work, need, _ptr(mean), _stream()), "dgp_predict_mean")
+            work = self._sized_work("_vjp_ws", "mean / vjp", "dgp_mean_vjp_workspace_bytes", m)
+            mean = self._empty(m)
+            self._call("dgp_predict_mean", th, _ptr(xs), m, *work, _ptr(mean))
         return mean
 
     def mean_vjp(self, theta, Xs: torch.Tensor, w: torch.Tensor):
         """Vector-Jacobian product of ``predict_mean``: (dtheta[P], dr[n], dnoise[n]) for upstream w[m].  Batched plans:
         Xs (batch, m, d), w (batch, m) -> dtheta (batch, P), dr (batch, n), dnoise (batch, n), one launch sequence for all sites."""
-        th = _theta_array(theta, self.ntheta * self.batch)
-        lead, m = self._check_xs(Xs)
+        th, m = self._theta(theta), self._check_xs(Xs)
         self._check_vec(w, "w", m)
         with torch.cuda.device(self.device):
             xs = Xs.contiguous()
-            work, need = self._vjp_workspace(m)
+            work = self._sized_work("_vjp_ws", "mean / vjp", "dgp_mean_vjp_workspace_bytes", m)
             width = _lib.OUT_LEN if self.batch == 1 else self.ntheta
-            dtheta = torch.zeros(lead + (width,), dtype=self.dtype, device=self.device)
-            dr = torch.empty(lead + (self.n,), dtype=self.dtype, device=self.device)
-            dnoise = torch.empty(lead + (self.n,), dtype=self.dtype, device=self.device)
-            _lib.check(
-                self.lib.dgp_mean_vjp(self._h, th, _ptr(xs), m, _ptr(w), work, need, _ptr(dtheta), _ptr(dr), _ptr(dnoise), _stream()),
-                "dgp_mean_vjp",
-            )
+            dtheta = torch.zeros(self._lead + (width,), dtype=self.dtype, device=self.device)
+            dr, dnoise = self._empty(self.n), self._empty(self.n)
+            self._call("dgp_mean_vjp", th, _ptr(xs), m, _ptr(w), *work, _ptr(dtheta), _ptr(dr), _ptr(dnoise))
         return dtheta[..., : self.ntheta], dr, dnoise
 
     def potrf_info(self) -> int:
@@ -954,48 +845,45 @@ class GPPlan:
         return int(self._ws[off:off + 4].view(torch.int32)[0].item())
 
     def _info_offset(self):
-        # the int info slot sits right after the 16-element scalar block that follows the partials;
-        # recover it from the ALPHA buffer pointer is fragile, so the library exposes it as buffer BUF_INFO
         p, ld = C.c_void_p(), C.c_int64()
-        _lib.check(self.lib.dgp_plan_buffer(self._h, _lib.BUF_INFO, C.byref(p), C.byref(ld)), "dgp_plan_buffer")
+        self._host("dgp_plan_buffer", _lib.BUF_INFO, C.byref(p), C.byref(ld))
         return p.value - self._ws.data_ptr()
 
     def set_timing(self, enabled: bool):
-        _lib.check(self.lib.dgp_plan_set_timing(self._h, int(bool(enabled))), "dgp_plan_set_timing")
+        self._host("dgp_plan_set_timing", int(bool(enabled)))
 
     def get_timing(self):
         """Per-stage HIP-event milliseconds of the most recent fit step (include/dgp_hip.h DGP_TIME_*)."""
         ms = (C.c_double * _lib.TIME_COUNT)()
-        _lib.check(self.lib.dgp_plan_get_timing(self._h, ms), "dgp_plan_get_timing")
+        self._host("dgp_plan_get_timing", ms)
         return list(ms)
 
     # ------------------------------------------------------------------ single stages (tests, profiling)
+    def _stage(self, name, *args):
+        with torch.cuda.device(self.device):
+            self._call("dgp_stage_" + name, *args)
+
     def stage_gram(self, theta, noise):
         self._check_vec(noise, "noise")
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.dgp_stage_gram(self._h, _theta_array(theta, self.ntheta * self.batch), _ptr(noise), _stream()), "dgp_stage_gram")
+        self._stage("gram", self._theta(theta), _ptr(noise))
 
     def stage_potrf(self):
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.dgp_stage_potrf(self._h, _stream()), "dgp_stage_potrf")
+        self._stage("potrf")
 
     def stage_trtri(self):
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.dgp_stage_trtri(self._h, _stream()), "dgp_stage_trtri")
+        self._stage("trtri")
 
     def stage_lauum(self):
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.dgp_stage_lauum(self._h, _stream()), "dgp_stage_lauum")
+        self._stage("lauum")
 
     def stage_solve(self, r):
         self._check_vec(r, "r")
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.dgp_stage_solve(self._h, _ptr(r), _stream()), "dgp_stage_solve")
+        self._stage("solve", _ptr(r))
 
     def stage_grad(self, theta):
         with torch.cuda.device(self.device):
             out = torch.zeros(_lib.OUT_LEN, dtype=self.dtype, device=self.device)
-            _lib.check(self.lib.dgp_stage_grad(self._h, _theta_array(theta, self.ntheta), _ptr(out), _stream()), "dgp_stage_grad")
+            self._call("dgp_stage_grad", _theta_array(theta, self.ntheta), _ptr(out))
         return out[: self.ntheta]
 
     def cross_gram(self, theta, Xs):
@@ -1005,10 +893,7 @@ class GPPlan:
             work = torch.empty(self.d * M, dtype=self.dtype, device=self.device)
             Ks = torch.empty(self.N, M, dtype=self.dtype, device=self.device)
             xs = Xs.contiguous()
-            _lib.check(
-                self.lib.dgp_cross_gram(self._h, _theta_array(theta, self.ntheta), _ptr(xs), m, _ptr(work), _ptr(Ks), _stream()),
-                "dgp_cross_gram",
-            )
+            self._call("dgp_cross_gram", _theta_array(theta, self.ntheta), _ptr(xs), m, _ptr(work), _ptr(Ks))
         return Ks[: self.n, :m]
 
 
@@ -1038,6 +923,25 @@ def _moment_inputs(dev, dtype, lead, m, mu, w, groups, extra_var, scale2=None):
     return mu_t, w_t, g_t, ev_t, s2
 
 
+def _cov_layout(cov, m):
+    """The covariance argument of the stateless moment passes, (M, M) or (B, M, M) with M = padded m: -> (lib, lead, B,
+    dev), ``lead`` = () or (B,).  ``ValueError`` unless it is a contiguous float64 / float32 device tensor of that shape."""
+    lib = _lib.load()
+    lead = (cov.shape[0],) if cov.dim() == 3 else ()
+    M = int(lib.dgp_padded_n(int(m)))
+    if cov.dtype not in _DTYPES or not cov.is_cuda or not cov.is_contiguous() or tuple(cov.shape) != lead + (M, M):
+        raise ValueError(f"cov must be a contiguous {lead + (M, M)} float64 / float32 CUDA tensor")
+    return lib, lead, (lead[0] if lead else 1), cov.device
+
+
+def _row_matrix(t, name, rows, lead, m, dev):
+    """``t`` as a contiguous float64 device tensor of shape ``lead + (rows, m)``, any number of rows; ``ValueError`` otherwise."""
+    t = torch.as_tensor(t).to(dev, torch.float64).contiguous()
+    if t.dim() != len(lead) + 2 or tuple(t.shape[:-2]) != lead or t.shape[-1] != m:
+        raise ValueError(f"{name} must have shape {lead + (rows, m)}")
+    return t
+
+
 def period_moments(cov: torch.Tensor, m: int, mu: torch.Tensor, scale2, w: torch.Tensor, groups: torch.Tensor, ngroups: int,
                    mode: int, extra_var: torch.Tensor | None = None):
     """Exact mean and covariance of the period sums L_g = sum_{i in g} w_i c_i of a transformed latent posterior
@@ -1049,26 +953,16 @@ def period_moments(cov: torch.Tensor, m: int, mu: torch.Tensor, scale2, w: torch
     number, or (B,) values; ``w``: weights (m,) / (B, m); ``groups``: int32 ids (m,) / (B, m) in 0 .. ngroups-1,
     non-decreasing except for -1 (excluded) anywhere; ``extra_var``: None or (m,) / (B, m) added to the diagonal of C.
     -> (mean (P,), cov (P, P)) or ((B, P), (B, P, P)), float64 device tensors."""
-    lib = _lib.load()
-    batched = cov.dim() == 3
-    B = cov.shape[0] if batched else 1
-    M = int(lib.dgp_padded_n(int(m)))
-    lead = (B,) if batched else ()
-    if cov.dtype not in _DTYPES or not cov.is_cuda or not cov.is_contiguous() or tuple(cov.shape) != lead + (M, M):
-        raise ValueError(f"cov must be a contiguous {lead + (M, M)} float64 / float32 CUDA tensor")
-    dev = cov.device
-    mu_t, w_t, g_t, ev_t, s2 = _moment_inputs(dev, cov.dtype, lead, int(m), mu, w, groups, extra_var, scale2)
-    P = int(ngroups)
-    need = int(lib.dgp_period_moments_workspace_bytes(int(m), P, B))
-    work = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-    mean_out = torch.empty(lead + (P,), dtype=torch.float64, device=dev)
-    cov_out = torch.empty(lead + (P, P), dtype=torch.float64, device=dev)
-    _lib.check(
-        lib.dgp_period_moments(_DTYPES[cov.dtype], int(mode), _ptr(cov), int(m), B, _ptr(mu_t), _ptr(s2), _ptr(w_t), _ptr(g_t), P,
-                               _ptr(ev_t), _ptr(work), need, _ptr(mean_out), _ptr(cov_out),
-                               _stream()),
-        "dgp_period_moments",
-    )
+    lib, lead, B, dev = _cov_layout(cov, m)
+    m, P = int(m), int(ngroups)
+    with torch.cuda.device(dev):
+        mu_t, w_t, g_t, ev_t, s2 = _moment_inputs(dev, cov.dtype, lead, m, mu, w, groups, extra_var, scale2)
+        need = int(lib.dgp_period_moments_workspace_bytes(m, P, B))
+        work = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        mean_out = torch.empty(lead + (P,), dtype=torch.float64, device=dev)
+        cov_out = torch.empty(lead + (P, P), dtype=torch.float64, device=dev)
+        _call("dgp_period_moments", _DTYPES[cov.dtype], int(mode), _ptr(cov), m, B, _ptr(mu_t), _ptr(s2), _ptr(w_t), _ptr(g_t), P,
+              _ptr(ev_t), _ptr(work), need, _ptr(mean_out), _ptr(cov_out))
     return mean_out, cov_out
 
 
@@ -1078,24 +972,15 @@ def period_third_moments(cov: torch.Tensor, m: int, mu: torch.Tensor, scale2, w:
     (``period_moments``' setting with ``mode`` = MODE_LOG, and its arguments) through one ``dgp_period_third_moments`` call:
     skewness_g = k3_g / cov_gg^1.5.  ``tile``: 0 picks the tile core by size, 64 / 128 force one.  The work area -- 2 M^2
     doubles per site -- is allocated for the call.  -> k3 (P,) or (B, P), a float64 device tensor."""
-    lib = _lib.load()
-    batched = cov.dim() == 3
-    B = cov.shape[0] if batched else 1
-    M = int(lib.dgp_padded_n(int(m)))
-    lead = (B,) if batched else ()
-    if cov.dtype not in _DTYPES or not cov.is_cuda or not cov.is_contiguous() or tuple(cov.shape) != lead + (M, M):
-        raise ValueError(f"cov must be a contiguous {lead + (M, M)} float64 / float32 CUDA tensor")
-    dev = cov.device
-    mu_t, w_t, g_t, ev_t, s2 = _moment_inputs(dev, cov.dtype, lead, int(m), mu, w, groups, extra_var, scale2)
-    P = int(ngroups)
-    need = int(lib.dgp_period_third_moments_workspace_bytes(int(m), P, B))
-    work = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-    k3 = torch.empty(lead + (P,), dtype=torch.float64, device=dev)
-    _lib.check(
-        lib.dgp_period_third_moments(_DTYPES[cov.dtype], _ptr(cov), int(m), B, _ptr(mu_t), _ptr(s2), _ptr(w_t), _ptr(g_t), P,
-                                     _ptr(ev_t), int(tile), _ptr(work), need, _ptr(k3), _stream()),
-        "dgp_period_third_moments",
-    )
+    lib, lead, B, dev = _cov_layout(cov, m)
+    m, P = int(m), int(ngroups)
+    with torch.cuda.device(dev):
+        mu_t, w_t, g_t, ev_t, s2 = _moment_inputs(dev, cov.dtype, lead, m, mu, w, groups, extra_var, scale2)
+        need = int(lib.dgp_period_third_moments_workspace_bytes(m, P, B))
+        work = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        k3 = torch.empty(lead + (P,), dtype=torch.float64, device=dev)
+        _call("dgp_period_third_moments", _DTYPES[cov.dtype], _ptr(cov), m, B, _ptr(mu_t), _ptr(s2), _ptr(w_t), _ptr(g_t), P,
+              _ptr(ev_t), int(tile), _ptr(work), need, _ptr(k3))
     return k3
 
 
@@ -1126,32 +1011,21 @@ def exceedance_moments(cov: torch.Tensor, m: int, mu: torch.Tensor, thresh: torc
     (m,) / (B, m) in 0 .. ngroups-1, non-decreasing except for -1 (excluded) anywhere; ``extra_var``: None or (m,) / (B, m)
     added to the variances (never to the covariances).
     -> (mean (L, P), cov (L, P, P)) or ((B, L, P), (B, L, P, P)), float64 device tensors; levels do not interact."""
-    lib = _lib.load()
-    batched = cov.dim() == 3
-    B = cov.shape[0] if batched else 1
-    M = int(lib.dgp_padded_n(int(m)))
-    lead = (B,) if batched else ()
-    if cov.dtype not in _DTYPES or not cov.is_cuda or not cov.is_contiguous() or tuple(cov.shape) != lead + (M, M):
-        raise ValueError(f"cov must be a contiguous {lead + (M, M)} float64 / float32 CUDA tensor")
-    dev = cov.device
-    mu_t, w_t, g_t, ev_t, _ = _moment_inputs(dev, cov.dtype, lead, int(m), mu, w, groups, extra_var)
-    u_t = torch.as_tensor(thresh).to(dev, torch.float64).contiguous()
-    if u_t.dim() != len(lead) + 2 or tuple(u_t.shape[:-2]) != lead or u_t.shape[-1] != int(m):
-        raise ValueError(f"thresh must have shape {lead + ('L', int(m))}")
-    P, L = int(ngroups), int(u_t.shape[-2])
-    need = int(lib.dgp_exceedance_moments_workspace_bytes(int(m), P, L, B))
-    if need == 0:
-        raise ValueError(f"bad size: m = {int(m)}, ngroups = {P}, levels = {L}, batch = {B} "
-                         "(1 <= m <= 2^20, 1 <= ngroups <= 65535, 1 <= levels <= 64, 1 <= batch <= 1024)")
-    work = torch.empty(need, dtype=torch.uint8, device=dev)
-    mean_out = torch.empty(lead + (L, P), dtype=torch.float64, device=dev)
-    cov_out = torch.empty(lead + (L, P, P), dtype=torch.float64, device=dev)
-    _lib.check(
-        lib.dgp_exceedance_moments(_DTYPES[cov.dtype], _ptr(cov), int(m), B, _ptr(mu_t), _ptr(u_t), L, _ptr(w_t), _ptr(g_t), P,
-                                   _ptr(ev_t), _ptr(work), need, _ptr(mean_out), _ptr(cov_out),
-                                   _stream()),
-        "dgp_exceedance_moments",
-    )
+    lib, lead, B, dev = _cov_layout(cov, m)
+    m, P = int(m), int(ngroups)
+    with torch.cuda.device(dev):
+        mu_t, w_t, g_t, ev_t, _ = _moment_inputs(dev, cov.dtype, lead, m, mu, w, groups, extra_var)
+        u_t = _row_matrix(thresh, "thresh", "L", lead, m, dev)
+        L = int(u_t.shape[-2])
+        need = int(lib.dgp_exceedance_moments_workspace_bytes(m, P, L, B))
+        if need == 0:
+            raise ValueError(f"bad size: m = {m}, ngroups = {P}, levels = {L}, batch = {B} "
+                             "(1 <= m <= 2^20, 1 <= ngroups <= 65535, 1 <= levels <= 64, 1 <= batch <= 1024)")
+        work = torch.empty(need, dtype=torch.uint8, device=dev)
+        mean_out = torch.empty(lead + (L, P), dtype=torch.float64, device=dev)
+        cov_out = torch.empty(lead + (L, P, P), dtype=torch.float64, device=dev)
+        _call("dgp_exceedance_moments", _DTYPES[cov.dtype], _ptr(cov), m, B, _ptr(mu_t), _ptr(u_t), L, _ptr(w_t), _ptr(g_t), P,
+              _ptr(ev_t), _ptr(work), need, _ptr(mean_out), _ptr(cov_out))
     return mean_out, cov_out
 
 
@@ -1189,33 +1063,25 @@ def window_moments(cov: torch.Tensor, m: int, mu: torch.Tensor, lo, hi, a=None, 
     -> (mean (q,), cov (Q, Q)) or ((B, q), (B, Q, Q)), float64 device tensors; ``cov`` has the layout of ``posterior_cov``
     (Q = padded q, lower triangle and diagonal 128-blocks valid, identity pad; blocks above the block diagonal hold zeros) and
     goes into ``exceedance_moments`` / ``period_moments`` / ``sample_value`` as a float64 covariance."""
-    lib = _lib.load()
-    batched = cov.dim() == 3
-    B = cov.shape[0] if batched else 1
-    M = int(lib.dgp_padded_n(int(m)))
-    lead = (B,) if batched else ()
-    lo_h, hi_h, q = _window_bounds(lo, hi, lead, int(m))
+    m = int(m)
+    lo_h, hi_h, q = _window_bounds(lo, hi, tuple(cov.shape[:-2]), m)  # the windows are checked before the covariance
     if mode not in (MODE_LINEAR, MODE_LOG):
         raise ValueError(f"mode must be MODE_LINEAR or MODE_LOG, not {mode!r}")
     if mode == MODE_LOG and scale2 is None:
         raise ValueError("MODE_LOG needs scale2 = s^2")
-    if cov.dtype not in _DTYPES or not cov.is_cuda or not cov.is_contiguous() or tuple(cov.shape) != lead + (M, M):
-        raise ValueError(f"cov must be a contiguous {lead + (M, M)} float64 / float32 CUDA tensor")
-    dev = cov.device
-    mu_t, a_t, _g, _ev, s2 = _moment_inputs(dev, cov.dtype, lead, int(m), mu, a, None, None, scale2 if mode == MODE_LOG else None)
-    need = int(lib.dgp_window_moments_workspace_bytes(int(m), q, B))
-    if need == 0:
-        raise ValueError(f"bad size: m = {int(m)}, q = {q}, batch = {B} (1 <= m, q <= 2^20, 1 <= batch <= 1024)")
-    Q = int(lib.dgp_padded_n(q))
-    lo_t, hi_t = lo_h.to(dev), hi_h.to(dev)
-    work = torch.empty(need, dtype=torch.uint8, device=dev)
-    mean_out = torch.empty(lead + (q,), dtype=torch.float64, device=dev)
-    cov_out = torch.zeros(lead + (Q, Q), dtype=torch.float64, device=dev)
-    _lib.check(
-        lib.dgp_window_moments(_DTYPES[cov.dtype], int(mode), _ptr(cov), int(m), B, _ptr(mu_t), _ptr(s2), _ptr(a_t), _ptr(lo_t),
-                               _ptr(hi_t), q, _ptr(work), need, _ptr(mean_out), _ptr(cov_out), _stream()),
-        "dgp_window_moments",
-    )
+    lib, lead, B, dev = _cov_layout(cov, m)
+    with torch.cuda.device(dev):
+        mu_t, a_t, _g, _ev, s2 = _moment_inputs(dev, cov.dtype, lead, m, mu, a, None, None, scale2 if mode == MODE_LOG else None)
+        need = int(lib.dgp_window_moments_workspace_bytes(m, q, B))
+        if need == 0:
+            raise ValueError(f"bad size: m = {m}, q = {q}, batch = {B} (1 <= m, q <= 2^20, 1 <= batch <= 1024)")
+        Q = int(lib.dgp_padded_n(q))
+        lo_t, hi_t = lo_h.to(dev), hi_h.to(dev)
+        work = torch.empty(need, dtype=torch.uint8, device=dev)
+        mean_out = torch.empty(lead + (q,), dtype=torch.float64, device=dev)
+        cov_out = torch.zeros(lead + (Q, Q), dtype=torch.float64, device=dev)
+        _call("dgp_window_moments", _DTYPES[cov.dtype], int(mode), _ptr(cov), m, B, _ptr(mu_t), _ptr(s2), _ptr(a_t), _ptr(lo_t),
+              _ptr(hi_t), q, _ptr(work), need, _ptr(mean_out), _ptr(cov_out))
     return mean_out, cov_out
 
 
@@ -1265,53 +1131,40 @@ def sample_value(cov: torch.Tensor, m: int, a: torch.Tensor, scale2, groups: tor
     beta = s^2 max C_ii over the included days, read from the buffer's diagonal.
     -> (gain (P, m), var (m,)) or ((B, P, m), (B, m)), float64 device tensors; var is v'_c (0 where it is not > 0: such a
     candidate has gain 0)."""
-    lib = _lib.load()
-    batched = cov.dim() == 3
-    B = cov.shape[0] if batched else 1
-    M = int(lib.dgp_padded_n(int(m)))
-    lead = (B,) if batched else ()
-    if cov.dtype not in _DTYPES or not cov.is_cuda or not cov.is_contiguous() or tuple(cov.shape) != lead + (M, M):
-        raise ValueError(f"cov must be a contiguous {lead + (M, M)} float64 / float32 CUDA tensor")
-    dev = cov.device
-    _, a_t, g_t, ov_t, s2 = _moment_inputs(dev, cov.dtype, lead, int(m), None, a, groups, obs_var, scale2)
-    nrows, rows_t = 0, None
-    if rows is not None:
-        rows_t = torch.as_tensor(rows).to(dev, torch.float64).contiguous()
-        if rows_t.dim() != len(lead) + 2 or tuple(rows_t.shape[:-2]) != lead or rows_t.shape[-1] != int(m):
-            raise ValueError(f"rows must have shape {lead + ('nrows', int(m))}")
-        nrows = int(rows_t.shape[-2])
+    lib, lead, B, dev = _cov_layout(cov, m)
+    m = int(m)
+    with torch.cuda.device(dev):
+        _, a_t, g_t, ov_t, s2 = _moment_inputs(dev, cov.dtype, lead, m, None, a, groups, obs_var, scale2)
+        rows_t = None if rows is None else _row_matrix(rows, "rows", "nrows", lead, m, dev)
+        nrows = 0 if rows_t is None else int(rows_t.shape[-2])
         if nrows == 0:
             rows_t = None
-    if nterms is None:
-        diag = torch.diagonal(cov, dim1=-2, dim2=-1)[..., : int(m)].double()
-        top = torch.where(g_t >= 0, diag, torch.zeros_like(diag)).reshape(B, -1).amax(dim=1)
-        nterms = series_terms(float((s2 * top).max()))
-    P, K = int(ngroups), int(nterms)
-    need = int(lib.dgp_sample_value_workspace_bytes(int(m), P, nrows, K, B))
-    if need == 0:
-        raise ValueError(f"bad size: m = {int(m)}, ngroups = {P}, nrows = {nrows}, nterms = {K}, batch = {B} (1 <= m <= 2^20, "
-                         "1 <= ngroups <= 65535, 0 <= nrows <= 64, 1 <= nterms <= 64, 1 <= batch <= 1024)")
-    work = torch.empty(need, dtype=torch.uint8, device=dev)
-    gain = torch.empty(lead + (P, int(m)), dtype=torch.float64, device=dev)
-    var = torch.empty(lead + (int(m),), dtype=torch.float64, device=dev)
-    _lib.check(
-        lib.dgp_sample_value(_DTYPES[cov.dtype], _ptr(cov), int(m), B, _ptr(a_t), _ptr(s2), _ptr(g_t), P, _ptr(ov_t), _ptr(rows_t),
-                             nrows, K, _ptr(work), need, _ptr(gain), _ptr(var), _stream()),
-        "dgp_sample_value",
-    )
+        if nterms is None:
+            diag = torch.diagonal(cov, dim1=-2, dim2=-1)[..., :m].double()
+            top = torch.where(g_t >= 0, diag, torch.zeros_like(diag)).reshape(B, -1).amax(dim=1)
+            nterms = series_terms(float((s2 * top).max()))
+        P, K = int(ngroups), int(nterms)
+        need = int(lib.dgp_sample_value_workspace_bytes(m, P, nrows, K, B))
+        if need == 0:
+            raise ValueError(f"bad size: m = {m}, ngroups = {P}, nrows = {nrows}, nterms = {K}, batch = {B} (1 <= m <= 2^20, "
+                             "1 <= ngroups <= 65535, 0 <= nrows <= 64, 1 <= nterms <= 64, 1 <= batch <= 1024)")
+        work = torch.empty(need, dtype=torch.uint8, device=dev)
+        gain = torch.empty(lead + (P, m), dtype=torch.float64, device=dev)
+        var = torch.empty(lead + (m,), dtype=torch.float64, device=dev)
+        _call("dgp_sample_value", _DTYPES[cov.dtype], _ptr(cov), m, B, _ptr(a_t), _ptr(s2), _ptr(g_t), P, _ptr(ov_t), _ptr(rows_t),
+              nrows, K, _ptr(work), need, _ptr(gain), _ptr(var))
     return gain, var
 
 
 def bvn_excess(h: torch.Tensor, k: torch.Tensor, rho: torch.Tensor):
     """Phi2(h, k; rho) - Phi(h) Phi(k) pointwise on the device (``dgp_debug_bvn_excess``): the pair function of
     ``exceedance_moments``, for tests.  Float64 CUDA tensors of one shape."""
-    lib = _lib.load()
     if not (h.is_cuda and h.dtype == k.dtype == rho.dtype == torch.float64 and h.shape == k.shape == rho.shape):
         raise ValueError("h, k, rho must be float64 CUDA tensors of one shape")
     h, k, rho = h.contiguous(), k.contiguous(), rho.contiguous()
     out = torch.empty_like(h)
     with torch.cuda.device(h.device):
-        _lib.check(lib.dgp_debug_bvn_excess(_ptr(h), _ptr(k), _ptr(rho), h.numel(), _ptr(out), _stream()), "dgp_debug_bvn_excess")
+        _call("dgp_debug_bvn_excess", _ptr(h), _ptr(k), _ptr(rho), h.numel(), _ptr(out))
     return out
 
 
@@ -1327,9 +1180,8 @@ def cross_validate_folds(plan, groups, launch, max_group_bound=None):
     if tuple(g.shape) != ((n,) if batch == 1 else (batch, n)):
         raise ValueError(f"groups must have shape {(n,) if batch == 1 else (batch, n)}, got {tuple(g.shape)}")
     g = g.reshape(batch, n).clone()
-    sizes = getattr(plan, "_site_sizes", None) or getattr(plan, "_sizes", None) or [n] * batch
     for b in range(batch):
-        g[b, int(sizes[b]):] = -1
+        g[b, int(plan._site_sizes[b]):] = -1
     if int(g.min()) < -1:
         raise ValueError("fold ids must be >= 0, or -1 for observations that are never held out")
     if int(g.max()) < 0:

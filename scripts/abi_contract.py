@@ -80,6 +80,7 @@ PLAN_QUERIES = {
 }
 STATELESS_QUERIES = {
     "dgp_period_moments_workspace_bytes": ("m", "ngroups", "sbatch"),
+    "dgp_period_third_moments_workspace_bytes": ("m", "ngroups", "sbatch"),
     "dgp_window_moments_workspace_bytes": ("m", "q", "sbatch"),
     "dgp_exceedance_moments_workspace_bytes": ("m", "ngroups", "nlevels", "sbatch"),
     "dgp_sample_value_workspace_bytes": ("m", "ngroups", "nrows", "nterms", "sbatch"),

@@ -26,9 +26,8 @@ def child(n, S, steps, dtype):
         import ctypes
 
         probe = ctypes.CDLL(_lib.LIB_PATH)  # an older build may lack entry points added since: bind what it has
-        for table in (_lib.SIGNATURES, _lib.EXT_SIGNATURES):
-            for name in [k for k in table if not hasattr(probe, k)]:
-                del table[name]
+        for name in [k for k in _lib.SIGNATURES if not hasattr(probe, k)]:
+            del _lib.SIGNATURES[name]
     import bench
 
     dev = torch.device("cuda:0")

@@ -2,10 +2,13 @@
 """Bitwise record of everything a ``GPPlan`` computes from a held factorisation, for refactors of the host glue that must not
 move a number: seeded inputs, one fit, and the outputs of ``fit_step``, ``factorize``, ``predict``, ``predict_mean``,
 ``mean_vjp``, ``predict_terms`` / ``predict_slopes`` (with and without ``return_cov``), ``posterior_cov``,
-``posterior_period_moments``, ``period_moments``, ``exceedance_moments``, ``posterior_exceedance_moments``, ``sample_value``,
-``window_moments`` and ``cross_validate``; and, for one site and the ragged batch of three, ``fisher``, ``predict_sensitivity``,
-``deletion_influence``, ``loo_fit_step`` / ``loo_value``, ``laplace_fit_step`` (with and without an interval row),
-``laplace_cross_validate`` and ``ep_fit_step`` cold and warm (``extra_products``).
+``posterior_period_moments``, ``period_moments``, ``period_third_moments`` (tile 0, 64, 128), ``exceedance_moments``,
+``posterior_exceedance_moments``, ``sample_value``, ``window_moments``, ``whiten`` and ``cross_validate``; for one site and the
+ragged batch of three, ``fisher``, ``predict_sensitivity`` (also means only in chunks), ``deletion_influence``, ``loo_fit_step`` /
+``loo_value``, ``bilinear``, ``laplace_factorize``, ``laplace_fit_step`` (with and without an interval row),
+``laplace_cross_validate``, ``ep_fit_step`` cold and warm, ``ep_factorize``, ``ep_diag`` and the pointwise ``censored_terms`` /
+``interval_terms`` / ``bvn_excess`` (``extra_products``); and, for one site, ``posterior_factor`` + ``sample_draws`` from a seeded
+device generator, ``cross_gram`` and the single stages with their buffers (``single_site_products``).
 
     python scripts/inference_snapshot.py --write before.pt      # on the commit to compare against
     python scripts/inference_snapshot.py --compare before.pt    # on the new one: exit status 1 unless every tensor is equal
@@ -66,6 +69,9 @@ def run_config(torch, GPPlan, backend, make_case, model, d, dtype, sizes, dev):
                 out[f"{name}.{i}"] = t.detach().cpu()
 
     keep("fit_step", plan.fit_step(theta, r, noise))
+    for site in sorted({0, B - 1}):  # the inverse factor the step left: site 0, and the shortest site of the ragged batch
+        jac = torch.randn(sizes[site], 2, generator=torch.Generator().manual_seed(13), dtype=torch.float64).to(dev)
+        keep(f"whiten_site{site}", plan.whiten(jac, site))
     keep("mean_vjp", plan.mean_vjp(theta, Xs, wv))
     keep("cross_validate_after_fit_step", plan.cross_validate(folds))
     keep("factorize", plan.factorize(theta, r, noise))
@@ -80,6 +86,8 @@ def run_config(torch, GPPlan, backend, make_case, model, d, dtype, sizes, dev):
     kmean, cov = plan.posterior_cov(theta, Xs)
     keep("posterior_cov", (kmean, torch.tril(cov)[..., :m, :m]))  # the part the layout defines
     keep("period_moments", plan.period_moments(cov, m, mu, scale2, w, groups, GROUPS, backend.MODE_LOG, extra_var=extra))
+    for tile in (0, 64, 128):
+        keep(f"period_third_moments_tile{tile}", plan.period_third_moments(cov, m, mu, scale2, w, groups, GROUPS, extra_var=extra, tile=tile))
     keep("exceedance_moments", plan.exceedance_moments(cov, m, mu, thresh, w, groups, GROUPS, extra_var=extra))
     keep("posterior_exceedance_moments",  # two panels of 128 rows
          plan.posterior_exceedance_moments(theta, Xs, mu, thresh, w, groups, GROUPS, extra_var=extra, panel_rows=128))
@@ -99,8 +107,36 @@ def run_config(torch, GPPlan, backend, make_case, model, d, dtype, sizes, dev):
     keep("cross_validate", plan.cross_validate(folds))
     if B <= 3:  # the products whose host glue lives beside their kernels: one site and the ragged batch of three
         extra_products(torch, plan, backend, keep, theta, X, r, noise, Xs, w, folds, groups, extra, dtype, dev)
+    if B == 1:
+        single_site_products(torch, plan, keep, theta, r, noise, Xs, dev)
     torch.cuda.synchronize(dev)
     return out
+
+
+def single_site_products(torch, plan, keep, theta, r, noise, Xs, dev):
+    """posterior_factor + sample_draws (seeded device generator) and cross_gram on whatever factorisation the plan holds, then
+    the single stages, which replace it: the defined part of every buffer after its stage, and stage_grad."""
+    from discontinuum_amd import _lib
+
+    n, m = plan.n, Xs.shape[0]
+    try:
+        mean, Lbuf, jitter = plan.posterior_factor(theta, Xs)
+        keep("posterior_factor", (mean, torch.tril(Lbuf)[:m, :m], torch.tensor([jitter], dtype=torch.float64)))
+        draws = plan.sample_draws(Lbuf, m, mean, 8, generator=torch.Generator(device=dev).manual_seed(5))
+        keep("sample_draws", (draws, plan._last_z))
+    except RuntimeError as e:  # not positive definite after the last jitter: part of the record
+        keep("posterior_factor.error", torch.tensor([len(str(e)) > 0]))
+    keep("cross_gram", plan.cross_gram(theta, Xs))
+    stages = (("gram", _lib.BUF_A, (theta, noise)), ("potrf", _lib.BUF_A, ()), ("trtri", _lib.BUF_T, ()), ("lauum", _lib.BUF_S, ()),
+              ("solve", _lib.BUF_ALPHA, (r,)))
+    try:
+        for name, which, args in stages:
+            getattr(plan, "stage_" + name)(*args)
+            buf = plan.buffer(which)
+            keep("stage_" + name, buf[:n] if buf.dim() == 1 else torch.tril(buf)[:n, :n])
+        keep("stage_grad", plan.stage_grad(theta))
+    except _lib.DGPError as e:  # a refusal is part of the record
+        keep("stage.error", torch.tensor([e.code]))
 
 
 def extra_products(torch, plan, backend, keep, theta, X, r, noise, Xs, w, folds, groups, extra, dtype, dev):
@@ -126,6 +162,7 @@ def extra_products(torch, plan, backend, keep, theta, X, r, noise, Xs, w, folds,
 
     keep("fisher", plan.fisher(theta, diag=cols))
     keep("predict_sensitivity", plan.predict_sensitivity(theta, Xs, diag=cols, rhs=rhs))
+    keep("predict_sensitivity_mean_chunk128", plan.predict_sensitivity(theta, Xs, diag=cols, rhs=rhs, chunk=128, return_var=False))
     inv_sd = (1.0 + w).to(torch.float64)
     scale = 0.5 if B == 1 else [0.5 + 0.1 * b for b in range(B)]
     keep("deletion_influence_linear",
@@ -135,9 +172,17 @@ def extra_products(torch, plan, backend, keep, theta, X, r, noise, Xs, w, folds,
         return
     keep("loo_fit_step", plan.loo_fit_step(theta, r, noise))
     keep("loo_value", plan.loo_value())
+    u, al = (torch.randn(lead + (n,), generator=g, dtype=torch.float64).to(dev) for _ in range(2))
+    keep("bilinear", plan.bilinear(theta, u, al))
     side = torch.zeros(lead + (n,), dtype=torch.int32)
     side[..., ::3] = -1  # a third of the rows: the truth lies below the recorded value
     mean = torch.zeros_like(r)
+
+    def factorized(res):  # (out, f_hat or (y~, n~), stat) of a *_factorize as tensors
+        mid = res[1] if isinstance(res[1], tuple) else (res[1],)
+        return (res[0],) + mid + (stat_tensor(res[2]),)
+
+    attempt("laplace_factorize_censored", lambda: factorized(plan.laplace_factorize(theta, r, mean, noise, side.to(dev).contiguous())))
 
     def laplace(upper):
         res = plan.laplace_fit_step(theta, r, mean, noise, side.to(dev).contiguous(), upper=upper)
@@ -173,6 +218,14 @@ def extra_products(torch, plan, backend, keep, theta, X, r, noise, Xs, w, folds,
     if getattr(plan, "ep_sites", None) is not None:
         warm = tuple(t.clone() for t in plan.ep_sites)
         attempt("ep_fit_step_warm", lambda: ep(warm))
+    attempt("ep_factorize", lambda: factorized(plan.ep_factorize(theta, r, mean, noise, side_dev, upper=upper)))
+    attempt("ep_diag", plan.ep_diag)
+    z = 3.0 * torch.randn(500, generator=g, dtype=torch.float64).to(dev)  # the pointwise functions of the censored fits
+    delta = torch.rand(500, generator=g, dtype=torch.float64).to(dev)
+    rho = (2.0 * torch.rand(500, generator=g, dtype=torch.float64) - 1.0).to(dev)
+    keep("censored_terms", plan.censored_terms(z))
+    keep("interval_terms", plan.interval_terms(z, delta))
+    keep("bvn_excess", backend.bvn_excess(z, z.flip(0).contiguous(), rho))
 
 
 def same_bits(torch, a, b):

@@ -21,10 +21,10 @@ class OraclePlan:
         self.batch = int(batch)
         # batch > 1 (``GPPlan(batch=B)``'s surface for ``fit_many``): one single-site double per site, ragged sizes
         self._sites = [OraclePlan(model, n, d, dtype) for _ in range(self.batch)] if self.batch > 1 else None
-        self._sizes = [n] * self.batch
+        self._sizes = self._site_sizes = [n] * self.batch
 
     def set_site_sizes(self, sizes):
-        self._sizes = [int(v) for v in sizes]
+        self._sizes = self._site_sizes = [int(v) for v in sizes]
 
     def set_inputs(self, X):
         if self._sites:

@@ -74,7 +74,7 @@ def test_cv_folds_schemes():
 
 def test_fold_sorting_for_the_device():
     class Plan:
-        batch, n = 1, 7
+        batch, n, _site_sizes = 1, 7, [7]
 
     seen = {}
 

@@ -276,18 +276,18 @@ def test_linear_targets_and_hyperparameter_totals():
 
 # ------------------------------------------------------------------------------------------------ 5. the ABI without a device
 def test_third_moments_abi_without_a_device():
-    """The entry points are declared in include/dgp_hip_ext.h (which dgp_hip.h includes), bound through ``_lib.EXT_SIGNATURES``
-    and exported; sizes and every refusal with null device addresses: each call is refused before a launch."""
+    """Every entry point that include/dgp_hip.h declares -- these two among them -- is bound through ``_lib.SIGNATURES`` and
+    exported, and the table binds nothing else; sizes and every refusal with null device addresses: each call is refused before
+    a launch."""
     import os
     import re
 
     lib = _lib.load()
     inc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
-    ext = re.sub(r"/\*.*?\*/", "", open(os.path.join(inc, "dgp_hip_ext.h")).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(dgp_[a-z_0-9]+)\s*\(", ext)))
-    assert names == sorted(_lib.EXT_SIGNATURES) and "dgp_period_third_moments" in names
-    assert all(hasattr(lib, name) for name in names) and not set(names) & set(_lib.SIGNATURES)
-    assert '#include "dgp_hip_ext.h"' in open(os.path.join(inc, "dgp_hip.h")).read()
+    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(inc, "dgp_hip.h")).read(), flags=re.S)
+    names = set(re.findall(r"\b(dgp_[a-z_0-9]+)\s*\(", header))
+    assert names == set(_lib.SIGNATURES) and "dgp_period_third_moments" in names
+    assert all(hasattr(lib, name) for name in names)
     size = lib.dgp_period_third_moments_workspace_bytes
     need = size(1000, 3, 2)
     M = lib.dgp_padded_n(1000)
