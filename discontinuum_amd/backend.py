@@ -741,6 +741,10 @@ class GPPlan:
         """The module-level ``exceedance_moments``."""
         return exceedance_moments(cov, m, mu, thresh, w, groups, ngroups, extra_var)
 
+    def excess_moments(self, cov, m: int, mu, scale2, thresh, w, groups, ngroups: int, above: bool = True, extra_var=None):
+        """The module-level ``excess_moments``."""
+        return excess_moments(cov, m, mu, scale2, thresh, w, groups, ngroups, above, extra_var)
+
     def window_moments(self, cov, m: int, mu, lo, hi, a=None, mode: int = 0, scale2=None):
         """The module-level ``window_moments``."""
         return window_moments(cov, m, mu, lo, hi, a=a, mode=mode, scale2=scale2)
@@ -1027,6 +1031,37 @@ def exceedance_moments(cov: torch.Tensor, m: int, mu: torch.Tensor, thresh: torc
         _call("dgp_exceedance_moments", _DTYPES[cov.dtype], _ptr(cov), m, B, _ptr(mu_t), _ptr(u_t), L, _ptr(w_t), _ptr(g_t), P,
               _ptr(ev_t), _ptr(work), need, _ptr(mean_out), _ptr(cov_out))
     return mean_out, cov_out
+
+
+def excess_moments(cov: torch.Tensor, m: int, mu: torch.Tensor, scale2, thresh: torch.Tensor, w: torch.Tensor, groups: torch.Tensor,
+                   ngroups: int, above: bool = True, extra_var: torch.Tensor | None = None):
+    """Exact mean and covariance of the period sums E_g = sum_{i in g} w_i (c_i - tau_i)^+ -- ``above=False``: the deficit
+    sum w_i (tau_i - c_i)^+ -- of a LOG-transformed latent posterior, c_i = exp(s f_i + t), f ~ N(mu, C), per threshold level,
+    through one ``dgp_excess_moments`` call (no factorisation, no draws): the per-point mean is of Black-Scholes type, the
+    covariance of two points a combination of four bivariate normal orthant probabilities (``include/dgp_hip_ext.h``).
+
+    ``cov``, ``mu`` (the MAPPED mean s mu + t), ``scale2``, ``w``, ``groups``, ``ngroups``, ``extra_var``: as for
+    ``period_moments`` with ``mode`` = MODE_LOG; ``thresh``: ln tau, (L, m) / (B, L, m) with 1 <= L <= 64, -inf (tau = 0: the
+    excess is c_i itself, the deficit 0) and +inf allowed.
+    -> (mean (L, P), cov (L, P, P), total (P,)) or with a leading B, float64 device tensors; ``total`` is the period's expected
+    sum of w_i c_i (``period_moments``' mean); levels do not interact."""
+    lib, lead, B, dev = _cov_layout(cov, m)
+    m, P = int(m), int(ngroups)
+    with torch.cuda.device(dev):
+        mu_t, w_t, g_t, ev_t, s2 = _moment_inputs(dev, cov.dtype, lead, m, mu, w, groups, extra_var, scale2)
+        a_t = _row_matrix(thresh, "thresh", "L", lead, m, dev)
+        L = int(a_t.shape[-2])
+        need = int(lib.dgp_excess_moments_workspace_bytes(m, P, L, B))
+        if need == 0:
+            raise ValueError(f"bad size: m = {m}, ngroups = {P}, levels = {L}, batch = {B} "
+                             "(1 <= m <= 2^20, 1 <= ngroups <= 65535, 1 <= levels <= 64, 1 <= batch <= 1024)")
+        work = torch.empty(need, dtype=torch.uint8, device=dev)
+        mean_out = torch.empty(lead + (L, P), dtype=torch.float64, device=dev)
+        cov_out = torch.empty(lead + (L, P, P), dtype=torch.float64, device=dev)
+        total_out = torch.empty(lead + (P,), dtype=torch.float64, device=dev)
+        _call("dgp_excess_moments", _DTYPES[cov.dtype], _ptr(cov), m, B, _ptr(mu_t), _ptr(s2), _ptr(a_t), _ptr(w_t), _ptr(g_t), P, L,
+              _ptr(ev_t), int(bool(above)), _ptr(work), need, _ptr(mean_out), _ptr(cov_out), _ptr(total_out))
+    return mean_out, cov_out, total_out
 
 
 def _window_bounds(lo, hi, lead, m):

@@ -1059,6 +1059,22 @@ class MarginalHIP(BaseModel):
                                       min_periods=min_periods, max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes)
 
     @is_fitted
+    def excess(self, covariates, threshold=None, threshold_series=None, weights=None, freq="YE", above=True, ci=0.95,
+               pred_noise=False, return_cov=False, max_bytes=None):
+        """BY HOW MUCH a threshold is overshot: per period of ``freq`` the expected sum_i w_i (c_i - tau_i)^+ of the
+        data-space target over the points of ``covariates`` -- ``above=False``: the deficit sum_i w_i (tau_i - c_i)^+ -- with
+        its exact standard error, in one posterior covariance and one ``dgp_excess_moments`` pass (log targets).  With
+        ``weights`` = seconds per step over a stage record: the flood volume above bankfull, or the deficit volume below a
+        low-flow threshold.  -> Dataset on (``level``, ``time``): ``mean``, ``se``, approximate ``lower`` / ``upper``,
+        ``total``, ``share`` (a ratio of expectations), ``n_points``.  See ``discontinuum_amd.excess.excess``."""
+        from ..excess import excess
+        from ..loads import DEFAULT_MAX_BYTES
+
+        return excess(self, covariates, threshold=threshold, threshold_series=threshold_series, weights=weights, freq=freq,
+                      above=above, ci=ci, pred_noise=pred_noise, return_cov=return_cov,
+                      max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes)
+
+    @is_fitted
     def cross_validate(self, folds="loo", ci=0.95, return_folds=False, laplace=None):
         """Exact leave-one-out / leave-group-out cross-validation of the training observations at the fitted
         hyperparameters, from the factorisation the engine holds (no refit; ``dgp_cross_validate``).  ``folds``: "loo", a

@@ -958,6 +958,8 @@ int dgp_period_third_moments(int dtype, const void* cov_dev, int64_t m, int batc
                              const void* extra_var_dev, int tile, void* work_dev, size_t work_bytes,
                              double* k3_out_dev /* batch x ngroups */, void* stream);
 
+#include "dgp_hip_ext.h"
+
 #ifdef __cplusplus
 }
 #endif
