@@ -163,6 +163,13 @@ EXT_SIGNATURES = {
     "dgp_excess_moments": (_i, [_i, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
 }
 
+# the same for include/dgp_hip_ext2.h; later entry points are appended here
+EXT2_SIGNATURES = {
+    "dgp_posterior_excess_moments_workspace_bytes": (_sz, [_vp, _i64, _i, _i, _i]),
+    "dgp_posterior_excess_moments": (_i, [_vp, _dp, _vp, _i64, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _sz, _vp, _vp, _vp,
+                                          _vp]),
+}
+
 _lib = None
 
 
@@ -180,7 +187,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise DGPLibraryError(f"could not load {LIB_PATH}: {e}") from e
-    for name, (res, args) in (*SIGNATURES.items(), *EXT_SIGNATURES.items()):
+    for name, (res, args) in (*SIGNATURES.items(), *EXT_SIGNATURES.items(), *EXT2_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -819,6 +819,53 @@ class GPPlan:
         M = int(self.lib.dgp_padded_n(int(m)))
         return stream_panel_rows(size(128), size(256) - size(128) if M > 128 else 0, M, max_bytes)
 
+    def posterior_excess_moments(self, theta, Xs: torch.Tensor, mu, scale2, thresh, w, groups, ngroups: int, above: bool = True,
+                                 extra_var=None, panel_rows=None, max_bytes=None):
+        """``excess_moments`` of the posterior at Xs straight from the held factorisation (``dgp_posterior_excess_moments``):
+        the covariance is produced ``panel_rows`` rows at a time and the (M, M) matrix is never formed.  Xs (m, d) --
+        (batch, m, d) for a batched plan, theta (batch, ntheta) --; ``mu`` (the MAPPED mean), ``scale2``, ``thresh`` = ln tau
+        (L, m) with 1 <= L <= 64, ``w``, ``groups``, ``ngroups``, ``above``, ``extra_var`` and the results (mean, cov, total) as
+        for ``excess_moments``.  ``panel_rows``: a positive multiple of 128, or None: ``excess_panel_rows`` of ``max_bytes`` --
+        the largest panel, at most M rows, whose work area fits; a ``ValueError`` names the bytes when 128 rows do not.  Short
+        panels cost time: every group of 8 levels produces all panels again, and a panel launch only has the parallelism of its
+        own rows, so give ``max_bytes`` what the device can spare.  The work area (2 N M + R M plan-dtype elements and
+        M (3 + 6 L + P min(L, 8)) + P doubles per site) is kept between calls; a ``RuntimeError`` names its bytes when it
+        exceeds the free device memory."""
+        lead, m, th = self._lead, self._check_xs(Xs), self._theta(theta)
+        P = int(ngroups)
+        dev = self.device
+        with torch.cuda.device(dev):
+            mu_t, w_t, g_t, ev_t, s2 = _moment_inputs(dev, self.dtype, lead, m, mu, w, groups, extra_var, scale2)
+            a_t = _row_matrix(thresh, "thresh", "L", lead, m, dev)
+            L = int(a_t.shape[-2])
+            R = self.excess_panel_rows(m, P, L, max_bytes) if panel_rows is None else int(panel_rows)
+            if R <= 0 or R % 128:
+                raise ValueError(f"panel_rows must be a positive multiple of 128, not {panel_rows}")
+            need = int(self.lib.dgp_posterior_excess_moments_workspace_bytes(self._h, m, P, L, R))
+            if need == 0:
+                raise ValueError(f"bad size: m = {m}, ngroups = {P}, levels = {L} (1 <= m <= 2^20, 1 <= ngroups <= 65535, "
+                                 "1 <= levels <= 64)")
+            work = self._work_area("_pxs_ws", need, "dgp_posterior_excess_moments", check_free=True)
+            xs = Xs.contiguous()
+            mean_out, cov_out = self._empty(L, P, dtype=torch.float64), self._empty(L, P, P, dtype=torch.float64)
+            total_out = self._empty(P, dtype=torch.float64)
+            self._call("dgp_posterior_excess_moments", th, _ptr(xs), m, _ptr(mu_t), _ptr(s2), _ptr(a_t), L, _ptr(w_t), _ptr(g_t), P,
+                       _ptr(ev_t), int(bool(above)), R, work, need, _ptr(mean_out), _ptr(cov_out), _ptr(total_out))
+        return mean_out, cov_out, total_out
+
+    def excess_panel_rows(self, m: int, ngroups: int, nlevels: int, max_bytes=None) -> int:
+        """The panel height ``posterior_excess_moments`` picks for m points, ``ngroups`` groups and ``nlevels`` levels under
+        ``max_bytes`` (default ``loads.DEFAULT_MAX_BYTES``): ``stream_panel_rows`` on the sizes
+        ``dgp_posterior_excess_moments_workspace_bytes`` reports."""
+        if max_bytes is None:
+            from .loads import DEFAULT_MAX_BYTES as max_bytes
+        size = lambda R: int(self.lib.dgp_posterior_excess_moments_workspace_bytes(self._h, int(m), int(ngroups), int(nlevels), R))  # noqa: E731
+        if size(128) == 0:
+            raise ValueError(f"bad size: m = {m}, ngroups = {ngroups}, levels = {nlevels} (1 <= m <= 2^20, 1 <= ngroups <= 65535, "
+                             "1 <= levels <= 64)")
+        M = int(self.lib.dgp_padded_n(int(m)))
+        return stream_panel_rows(size(128), size(256) - size(128) if M > 128 else 0, M, max_bytes, "the streamed excess pass")
+
     def predict_mean(self, theta, Xs: torch.Tensor):
         """K(X*, X) alpha from the held factorisation (no variance work).  Batched plans: Xs (batch, m, d) -> (batch, m)."""
         th, m = self._theta(theta), self._check_xs(Xs)
@@ -988,14 +1035,15 @@ def period_third_moments(cov: torch.Tensor, m: int, mu: torch.Tensor, scale2, w:
     return k3
 
 
-def stream_panel_rows(need128: int, step: int, M: int, max_bytes: int) -> int:
-    """Rows of the covariance panel ``GPPlan.posterior_exceedance_moments`` picks for a byte budget: the work area is
+def stream_panel_rows(need128: int, step: int, M: int, max_bytes: int, what: str = "the streamed exceedance pass") -> int:
+    """Rows of the covariance panel ``GPPlan.posterior_exceedance_moments`` (``posterior_excess_moments``, which names itself
+    in ``what`` for the error text) picks for a byte budget: the work area is
     ``need128`` bytes with a panel of 128 rows and grows by ``step`` bytes per further 128 rows (one panel row block of
     every site), so the answer is 128 min(M / 128, 1 + (max_bytes - need128) // step) -- the largest multiple of 128, at
     most the padded record length ``M``, whose work area fits ``max_bytes``.  ``ValueError`` naming the bytes when
     ``need128`` itself exceeds the budget."""
     if need128 > max_bytes:
-        raise ValueError(f"the streamed exceedance pass needs a work area of {need128} bytes with the smallest panel (128 "
+        raise ValueError(f"{what} needs a work area of {need128} bytes with the smallest panel (128 "
                          f"rows), which exceeds max_bytes = {max_bytes}")
     blocks = M // 128
     if step > 0:

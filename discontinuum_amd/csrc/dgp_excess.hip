@@ -39,58 +39,36 @@
 //           sum_i W_i^2 V_i for h = g, written to (g, h) and (h, g) from one value; mean_g and (level 0) total_g beside it.
 // Every sum runs in a fixed order: bitwise repeatable, and a site's numbers do not depend on its batch.  All arithmetic after
 // the loads of C and mu is double.
+//
+// The work area's layout, XsPoint and the pair function xs_pair live in dgp_excess.h, shared with the panel cut of the pairs pass
+// (dgp_excess_stream.hip), which reaches init + prep and the reduce here through excess_prepare / excess_reduce (dgp_internal.h).
 #include <climits>
 
-#include "dgp_bvn.h"
+#include "dgp_excess.h"
 #include "dgp_plan.h"
 
 namespace dgp {
 
 namespace {
 
-constexpr int XS_CHUNK = 2;  // most levels a pairs / reduce pass takes at once: 4 tilts each in bvn_excess's 8 slots
-
-// per-site work area, in doubles: W[M], sigma[M], 1 / sigma[M], then h0, kappa, A0, A1, E, V as [L][M] each,
-// Y[min(L, XS_CHUNK)][M][P], then 2 P ints
-__host__ __device__ inline long xs_site_doubles(long M, int P, int L) {
-  return 3 * M + 6 * (long)L * M + (long)(L < XS_CHUNK ? L : XS_CHUNK) * M * P + P;
-}
-
-struct XsWork {  // the parts of a site's work area
-  double *W, *sig, *sinv, *h0, *kap, *A0, *A1, *E, *V, *Y;
-  int* se;
-  __device__ XsWork(double* work, long ws, long M, int P, int L) {
-    W = work + (long)blockIdx.z * ws;
-    sig = W + M;
-    sinv = sig + M;
-    h0 = sinv + M;
-    kap = h0 + (long)L * M;
-    A0 = kap + (long)L * M;
-    A1 = A0 + (long)L * M;
-    E = A1 + (long)L * M;
-    V = E + (long)L * M;
-    Y = V + (long)L * M;
-    se = (int*)(Y + (long)(L < XS_CHUNK ? L : XS_CHUNK) * M * P);
-  }
-};
-
-__global__ __launch_bounds__(256) void xs_init_kernel(double* work, long ws, long M, int P, int L) {
+__global__ __launch_bounds__(256) void xs_init_kernel(double* work, long ws, long M, int P, int L, int YL) {
   const int g = blockIdx.x * 256 + threadIdx.x;
   if (g >= P) return;
-  const XsWork wk(work, ws, M, P, L);
+  const XsWork wk(work, ws, M, P, L, YL);
   wk.se[2 * g] = INT_MAX;
   wk.se[2 * g + 1] = 0;
 }
 
 template <typename T>
-__global__ __launch_bounds__(256) void xs_prep_kernel(const T* __restrict__ cov, long M, int m, int P, int L, const T* __restrict__ mu,
-                                                      const double* __restrict__ scale2, const double* __restrict__ thresh,
-                                                      const double* __restrict__ w, const int* __restrict__ group,
-                                                      const T* __restrict__ ev, double sg, double* work, long ws) {
+__global__ __launch_bounds__(256) void xs_prep_kernel(const T* __restrict__ diag, long dsite, long dstep, long M, int m, int P, int L,
+                                                      const T* __restrict__ mu, const double* __restrict__ scale2,
+                                                      const double* __restrict__ thresh, const double* __restrict__ w,
+                                                      const int* __restrict__ group, const T* __restrict__ ev, double sg, int YL,
+                                                      double* work, long ws) {
   const long j = (long)blockIdx.x * 256 + threadIdx.x;
   const int z = blockIdx.z;
   if (j >= M) return;
-  const XsWork wk(work, ws, M, P, L);
+  const XsWork wk(work, ws, M, P, L, YL);
   bool in = false;
   double Wj = 0.0, sj = 0.0, sinv = 0.0, vp = 0.0, muj = 0.0, Mj = 0.0;
   if (j < m) {
@@ -99,7 +77,7 @@ __global__ __launch_bounds__(256) void xs_prep_kernel(const T* __restrict__ cov,
     if (g >= 0 && g < P) {
       in = true;
       muj = (double)mu[k];
-      double var = (double)cov[(long)z * M * M + j * (M + 1)];
+      double var = (double)diag[(long)z * dsite + j * dstep];
       if (ev) var += (double)ev[k];
       var *= scale2[z];
       vp = var > 0.0 ? var : (var != var ? var : 0.0);
@@ -144,63 +122,6 @@ __global__ __launch_bounds__(256) void xs_prep_kernel(const T* __restrict__ cov,
   }
 }
 
-template <int LV>
-struct XsPoint {  // what the pair function reads of a point: sigma, 1 / sigma and, per level of the chunk, h0, kappa, A0, A1
-  double s, sinv, h[LV], kap[LV], a0[LV], a1[LV];
-  __device__ __forceinline__ void load(const XsWork& wk, long M, int l0, long i) {
-    s = wk.sig[i];
-    sinv = wk.sinv[i];
-#pragma unroll
-    for (int l = 0; l < LV; ++l) {
-      const long o = (long)(l0 + l) * M + i;
-      h[l] = wk.h0[o];
-      kap[l] = wk.kap[o];
-      a0[l] = wk.A0[o];
-      a1[l] = wk.A1[o];
-    }
-  }
-};
-
-// n_ij of the file header for the LV levels of a chunk; cij = C_ij s^2 as loaded
-template <int LV>
-__device__ __forceinline__ void xs_pair(double sg, const XsPoint<LV>& pi, const XsPoint<LV>& pj, double cij, double (&out)[LV]) {
-  constexpr int LC = 4 * LV;
-  double r = cij * pi.sinv * pj.sinv;
-  r = r > 1.0 ? 1.0 : (r < -1.0 ? -1.0 : r);  // (comparisons: a NaN stays)
-  const double ec = exp(r * pi.s * pj.s);
-  const double ti = sg * pi.s, tj = sg * pj.s, ui = (sg * r) * pj.s, uj = (sg * r) * pi.s;
-  double h[LC], k[LC], ph[LC], pk[LC], D[LC];
-#pragma unroll
-  for (int l = 0; l < LV; ++l) {  // slots 4 l + (00, 10, 01, 11)
-    const double hi = pi.h[l], kj = pj.h[l];
-    h[4 * l] = hi;
-    k[4 * l] = kj;
-    ph[4 * l] = pi.a0[l];
-    pk[4 * l] = pj.a0[l];
-    h[4 * l + 1] = hi + ti;
-    k[4 * l + 1] = kj + uj;
-    ph[4 * l + 1] = pi.a1[l];
-    pk[4 * l + 1] = ex_phi(k[4 * l + 1]);
-    h[4 * l + 2] = hi + ui;
-    k[4 * l + 2] = kj + tj;
-    ph[4 * l + 2] = ex_phi(h[4 * l + 2]);
-    pk[4 * l + 2] = pj.a1[l];
-    h[4 * l + 3] = hi + ti + ui;
-    k[4 * l + 3] = kj + tj + uj;
-    ph[4 * l + 3] = ex_phi(h[4 * l + 3]);
-    pk[4 * l + 3] = ex_phi(k[4 * l + 3]);
-  }
-  bvn_excess<LC>(h, k, ph, pk, r, D);
-#pragma unroll
-  for (int l = 0; l < LV; ++l) {
-    const double ki = pi.kap[l], kj = pj.kap[l];
-    const double dpart = (ec * D[4 * l + 3] - kj * D[4 * l + 1]) - ki * D[4 * l + 2] + (ki * kj) * D[4 * l];
-    const double bracket = (ec * ph[4 * l + 3] * pk[4 * l + 3] - pi.a1[l] * pj.a1[l]) -
-                           kj * pi.a1[l] * (pk[4 * l + 1] - pj.a0[l]) - ki * pj.a1[l] * (ph[4 * l + 2] - pi.a0[l]);
-    out[l] = dpart + bracket;
-  }
-}
-
 // levels l0 .. l0 + LV of Y; see the file header
 template <typename T, int LV>
 __global__ __launch_bounds__(256) void xs_pairs_kernel(const T* __restrict__ cov, long M, int m, int P, int L, int l0,
@@ -208,7 +129,7 @@ __global__ __launch_bounds__(256) void xs_pairs_kernel(const T* __restrict__ cov
                                                        double* __restrict__ work, long ws) {
   const int rb = blockIdx.x, h = blockIdx.y, z = blockIdx.z;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const XsWork wk(work, ws, M, P, L);
+  const XsWork wk(work, ws, M, P, L, XS_CHUNK);
   const int r0 = rb * EX_ROWS;
   int c0, c1;
   ex_range(wk.se, h, c0, c1);
@@ -284,13 +205,13 @@ __global__ __launch_bounds__(256) void xs_pairs_kernel(const T* __restrict__ cov
 }
 
 // blockIdx.x = (64-column chunk of h) * LV + level of the chunk
-__global__ __launch_bounds__(256) void xs_reduce_kernel(long M, int P, int L, int l0, int LV, double* __restrict__ work, long ws,
+__global__ __launch_bounds__(256) void xs_reduce_kernel(long M, int P, int L, int l0, int LV, int YL, double* __restrict__ work, long ws,
                                                         double* __restrict__ mean_out, double* __restrict__ cov_out,
                                                         double* __restrict__ total_out) {
   const int hc = blockIdx.x / LV, lc = blockIdx.x % LV, g = blockIdx.y, z = blockIdx.z;
   if (hc > 0 && hc * 64 + 63 < g) return;  // every h of this chunk is < g: the (h, g) workgroup writes those entries
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const XsWork wk(work, ws, M, P, L);
+  const XsWork wk(work, ws, M, P, L, YL);
   const double* Y = wk.Y + (long)lc * M * P;
   const double* E = wk.E + (long)(l0 + lc) * M;
   const double* V = wk.V + (long)(l0 + lc) * M;
@@ -347,24 +268,39 @@ void xs_chunk(const T* cov, long M, int m, int B, int P, int L, int l0, const do
               long ws, double* mean_out, double* cov_out, double* total_out, hipStream_t s) {
   xs_pairs_kernel<T, LV><<<dim3((unsigned)(M / EX_ROWS), (unsigned)P, (unsigned)B), 256, 0, s>>>(cov, M, m, P, L, l0, scale2, group, sg,
                                                                                                  work, ws);
-  xs_reduce_kernel<<<dim3((unsigned)(((P + 63) / 64) * LV), (unsigned)P, (unsigned)B), 256, 0, s>>>(M, P, L, l0, LV, work, ws, mean_out,
-                                                                                                  cov_out, total_out);
+  excess_reduce(M, B, P, L, l0, LV, XS_CHUNK, work, mean_out, cov_out, total_out, s);
 }
 
-size_t excess_moments_workspace_bytes(long m, int P, int L, int B) {
-  return sizeof(double) * (size_t)B * (size_t)xs_site_doubles(round_up(m, DGP_TILE_HOST), P, L);
+}  // namespace
+
+size_t excess_moments_workspace_bytes(long m, int P, int L, int B, int YL) {
+  return sizeof(double) * (size_t)B * (size_t)xs_site_doubles(round_up(m, DGP_TILE_HOST), P, L, YL);
 }
 
 template <typename T>
-int excess_moments(const T* cov, long m, int B, const T* mu, const double* scale2, const double* thresh, int L, const double* w,
-                   const int* group, int P, const T* ev, int above, double* work, double* mean_out, double* cov_out,
-                   double* total_out, hipStream_t s) {
+void excess_prepare(const T* diag, long dsite, long dstep, long m, int B, const T* mu, const double* scale2, const double* thresh, int L,
+                    const double* w, const int* group, int P, const T* ev, double sg, int YL, double* work, hipStream_t s) {
   const long M = round_up(m, DGP_TILE_HOST);
-  const long ws = xs_site_doubles(M, P, L);
+  const long ws = xs_site_doubles(M, P, L, YL);
+  xs_init_kernel<<<dim3((unsigned)((P + 255) / 256), 1, (unsigned)B), 256, 0, s>>>(work, ws, M, P, L, YL);
+  xs_prep_kernel<T><<<dim3((unsigned)((M + 255) / 256), 1, (unsigned)B), 256, 0, s>>>(diag, dsite, dstep, M, (int)m, P, L, mu, scale2,
+                                                                                    thresh, w, group, ev, sg, YL, work, ws);
+}
+
+void excess_reduce(long M, int B, int P, int L, int l0, int LV, int YL, double* work, double* mean_out, double* cov_out,
+                   double* total_out, hipStream_t s) {
+  xs_reduce_kernel<<<dim3((unsigned)(((P + 63) / 64) * LV), (unsigned)P, (unsigned)B), 256, 0, s>>>(
+      M, P, L, l0, LV, YL, work, xs_site_doubles(M, P, L, YL), mean_out, cov_out, total_out);
+}
+
+template <typename T>
+static int excess_moments(const T* cov, long m, int B, const T* mu, const double* scale2, const double* thresh, int L, const double* w,
+                          const int* group, int P, const T* ev, int above, double* work, double* mean_out, double* cov_out,
+                          double* total_out, hipStream_t s) {
+  const long M = round_up(m, DGP_TILE_HOST);
+  const long ws = xs_site_doubles(M, P, L, XS_CHUNK);
   const double sg = above ? 1.0 : -1.0;
-  xs_init_kernel<<<dim3((unsigned)((P + 255) / 256), 1, (unsigned)B), 256, 0, s>>>(work, ws, M, P, L);
-  xs_prep_kernel<T><<<dim3((unsigned)((M + 255) / 256), 1, (unsigned)B), 256, 0, s>>>(cov, M, (int)m, P, L, mu, scale2, thresh, w, group,
-                                                                                    ev, sg, work, ws);
+  excess_prepare<T>(cov, M * M, M + 1, m, B, mu, scale2, thresh, L, w, group, P, ev, sg, XS_CHUNK, work, s);
   for (int l0 = 0; l0 < L;) {  // chunks of 2 levels, then 1: a function of L alone
     if (L - l0 >= 2) {
       xs_chunk<T, 2>(cov, M, (int)m, B, P, L, l0, scale2, group, sg, work, ws, mean_out, cov_out, total_out, s);
@@ -377,7 +313,10 @@ int excess_moments(const T* cov, long m, int B, const T* mu, const double* scale
   return (int)hipGetLastError();
 }
 
-}  // namespace
+template void excess_prepare<double>(const double*, long, long, long, int, const double*, const double*, const double*, int,
+                                     const double*, const int*, int, const double*, double, int, double*, hipStream_t);
+template void excess_prepare<float>(const float*, long, long, long, int, const float*, const double*, const double*, int, const double*,
+                                    const int*, int, const float*, double, int, double*, hipStream_t);
 
 }  // namespace dgp
 
@@ -387,7 +326,7 @@ extern "C" {
 
 size_t dgp_excess_moments_workspace_bytes(int64_t m, int ngroups, int nlevels, int batch) {
   if (!ex_sizes_ok(m, ngroups, nlevels, batch)) return 0;
-  return excess_moments_workspace_bytes(m, ngroups, nlevels, batch);
+  return excess_moments_workspace_bytes(m, ngroups, nlevels, batch, XS_CHUNK);
 }
 
 int dgp_excess_moments(int dtype, const void* cov, int64_t m, int batch, const void* mu, const double* scale2, const double* thresh,
@@ -400,7 +339,7 @@ int dgp_excess_moments(int dtype, const void* cov, int64_t m, int batch, const v
     return fail(DGP_E_ARG,
                 "dgp_excess_moments: bad size (1 <= m <= 2^20, 1 <= ngroups <= 65535, 1 <= nlevels <= 64, 1 <= batch <= 1024)");
   if (above != 0 && above != 1) return fail(DGP_E_ARG, "dgp_excess_moments: above must be 0 (deficit) or 1 (excess)");
-  if (int rc = need_work(work, work_bytes, excess_moments_workspace_bytes(m, ngroups, nlevels, batch), "dgp_excess_moments")) return rc;
+  if (int rc = need_work(work, work_bytes, excess_moments_workspace_bytes(m, ngroups, nlevels, batch, XS_CHUNK), "dgp_excess_moments")) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int rc = dtype == DGP_F64
                      ? excess_moments<double>((const double*)cov, m, batch, (const double*)mu, scale2, thresh, nlevels, w, group, ngroups,

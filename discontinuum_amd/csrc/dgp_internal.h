@@ -249,6 +249,17 @@ void exceedance_prepare(const T* diag, long dsite, long dstep, long m, int B, co
                         const int* group, int P, const T* ev, double* work, hipStream_t s);
 void exceedance_reduce(long M, int B, int P, int L, int l0, int LC, double* work, double* mean_out, double* cov_out, hipStream_t s);
 
+// ---- dgp_excess.hip: exact mean / covariance of the period sums of the excess (deficit) of a log-transformed posterior over a
+// threshold; the work area's layout, with Y holding min(L, YL) levels, is dgp_excess.h's (YL = XS_CHUNK dense, XS_GROUP streamed)
+size_t excess_moments_workspace_bytes(long m, int P, int L, int B, int YL);
+// the passes before and after the pairs pass, for dgp_excess_stream.hip: init + prep (C_jj of site z at diag[z dsite + j dstep];
+// sg = +1 excess, -1 deficit), and the reduce pass of the levels l0 .. l0 + LV, which reads Y's levels 0 .. LV
+template <typename T>
+void excess_prepare(const T* diag, long dsite, long dstep, long m, int B, const T* mu, const double* scale2, const double* thresh, int L,
+                    const double* w, const int* group, int P, const T* ev, double sg, int YL, double* work, hipStream_t s);
+void excess_reduce(long M, int B, int P, int L, int l0, int LV, int YL, double* work, double* mean_out, double* cov_out,
+                   double* total_out, hipStream_t s);
+
 // ---- dgp_terms.hip: the posterior of the covariance's additive parts (C = model_nterms).  Ks / V: N x (C Mp) row-major, term c
 // of test point j in column c Mp + j; kss: C Mp; part: terms_partials(C, Mp) elements; mean [B][C][m], cov [B][C (C + 1) / 2][m]
 // (entry (c, c'), c' <= c, at c (c + 1) / 2 + c'; null: not wanted) in the caller's arrays.

@@ -1060,19 +1060,22 @@ class MarginalHIP(BaseModel):
 
     @is_fitted
     def excess(self, covariates, threshold=None, threshold_series=None, weights=None, freq="YE", above=True, ci=0.95,
-               pred_noise=False, return_cov=False, max_bytes=None):
+               pred_noise=False, return_cov=False, max_bytes=None, streamed=False):
         """BY HOW MUCH a threshold is overshot: per period of ``freq`` the expected sum_i w_i (c_i - tau_i)^+ of the
         data-space target over the points of ``covariates`` -- ``above=False``: the deficit sum_i w_i (tau_i - c_i)^+ -- with
         its exact standard error, in one posterior covariance and one ``dgp_excess_moments`` pass (log targets).  With
         ``weights`` = seconds per step over a stage record: the flood volume above bankfull, or the deficit volume below a
         low-flow threshold.  -> Dataset on (``level``, ``time``): ``mean``, ``se``, approximate ``lower`` / ``upper``,
-        ``total``, ``share`` (a ratio of expectations), ``n_points``.  See ``discontinuum_amd.excess.excess``."""
+        ``total``, ``share`` (a ratio of expectations), ``n_points``.  A record whose dense footprint exceeds ``max_bytes``
+        (default ``loads.DEFAULT_MAX_BYTES``; a 15-minute stage record of sixteen months already does) is refused;
+        ``streamed=True`` (never chosen automatically) produces the covariance a panel of rows at a time instead
+        (``dgp_posterior_excess_moments``) and ``max_bytes`` then bounds its work area.  See ``discontinuum_amd.excess.excess``."""
         from ..excess import excess
         from ..loads import DEFAULT_MAX_BYTES
 
         return excess(self, covariates, threshold=threshold, threshold_series=threshold_series, weights=weights, freq=freq,
                       above=above, ci=ci, pred_noise=pred_noise, return_cov=return_cov,
-                      max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes)
+                      max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes, streamed=streamed)
 
     @is_fitted
     def cross_validate(self, folds="loo", ci=0.95, return_folds=False, laplace=None):

@@ -14,7 +14,10 @@ noise), sigma_i = sqrt(v_i), c_ij = s^2 C_ij, M_i = m_i + v_i / 2 and a_i = ln t
 (the opposite orthants for the deficit), computed on the device by ``dgp_excess_moments`` straight from the covariance
 ``dgp_posterior_cov`` writes: no factorisation, no draws, no sampling noise.  It reads the latent posterior covariance
 alone, so Laplace and EP censored fits take the same path.  The pipelines' clip of the data-space value is not part of the
-statistics.  Linear targets and records over ``max_bytes`` are refused (there is no streamed form)."""
+statistics.  Linear targets are refused.  A record whose dense footprint exceeds ``max_bytes`` -- sixteen months of a
+15-minute stage record already do -- is refused too unless ``streamed=True`` is passed: ``dgp_posterior_excess_moments`` then
+produces the covariance a panel of rows at a time from the held factorisation and never stores it whole, and ``max_bytes``
+bounds its work area instead.  The streamed form is never chosen automatically: short panels cost time."""
 from __future__ import annotations
 
 import numpy as np
@@ -60,23 +63,42 @@ def _work_bytes(m, P, L):
     return 8 * (M * (3 + 6 * L + P * min(L, 2)) + P)
 
 
-def excess_sums(model, Xnew, a, w, groups, ngroups, above=True, pred_noise=False, max_bytes: int = DEFAULT_MAX_BYTES):
+def excess_sums(model, Xnew, a, w, groups, ngroups, above=True, pred_noise=False, max_bytes: int = DEFAULT_MAX_BYTES,
+                streamed=False):
     """The device core: design rows ``Xnew`` (m, d), thresholds ``a`` = ln tau (L, m), weights ``w`` (m,), int32 group ids
     (non-decreasing, -1 = excluded) -> numpy (mean (L, P), cov (L, P, P), total (P,)) from ONE ``posterior_cov`` and one
     ``excess_moments`` per 64 levels.  ``NotImplementedError`` for a linear target, and for a record whose dense footprint --
-    ``loads._site_bytes`` plus the pass's own work area -- exceeds ``max_bytes``: there is no streamed form."""
+    ``loads._site_bytes`` plus the pass's own work area -- exceeds ``max_bytes``.  ``streamed=True`` (never chosen
+    automatically): the latent mean from ``predict_mean`` like ``exceedance.count_moments``' streamed branch, then one
+    ``posterior_excess_moments`` per 64 levels, whose work area -- with the largest covariance panel that fits -- ``max_bytes``
+    bounds instead (``ValueError`` naming the bytes when 128 panel rows do not fit)."""
     mode, s, t = target_transform(model.dm)
     if mode != MODE_LOG:
         raise NotImplementedError(LINEAR_REFUSAL)
     Xnew = Xnew.to(model.device).contiguous()
     m = Xnew.shape[0]
     a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1, m))
+    means, covs, total = [], [], None
+    if streamed:
+        model._eval_ready(Xnew)
+        with torch.no_grad():
+            latent = model._plan.predict_mean(model._factor_theta, Xnew) + model.model.prior_mean(Xnew)
+            mapped = (s * latent + t).contiguous()
+            extra = model.likelihood.predictive_noise(m, Xnew.device, model.dtype) if pred_noise else None
+            for l0 in range(0, a.shape[0], MAX_LEVELS):
+                mean_d, cov_d, total_d = model._plan.posterior_excess_moments(
+                    model._factor_theta, Xnew, mapped, s * s, torch.from_numpy(a[l0:l0 + MAX_LEVELS]), w, groups, ngroups,
+                    above=above, extra_var=extra, max_bytes=max_bytes)
+                means.append(mean_d.cpu().numpy())
+                covs.append(cov_d.cpu().numpy())
+                total = total_d.cpu().numpy()
+        return np.concatenate(means), np.concatenate(covs), total
     esz = torch.empty((), dtype=model.dtype).element_size()
     need = _site_bytes(model.dm.X.shape[0], m, esz) + _work_bytes(m, ngroups, min(a.shape[0], MAX_LEVELS))
     if need > max_bytes:
         raise NotImplementedError(f"the excess over a threshold needs the dense posterior covariance: a footprint of {need} bytes "
-                                  f"for m = {m} points exceeds max_bytes = {max_bytes}, and there is no streamed form")
-    means, covs, total = [], [], None
+                                  f"for m = {m} points exceeds max_bytes = {max_bytes}; no streamed form is chosen "
+                                  "automatically: pass streamed=True")
     model._eval_ready(Xnew)
     with torch.no_grad():
         kmean, cov = model._plan.posterior_cov(model._factor_theta, Xnew)
@@ -92,7 +114,7 @@ def excess_sums(model, Xnew, a, w, groups, ngroups, above=True, pred_noise=False
 
 
 def excess(model, covariates, threshold=None, threshold_series=None, weights=None, freq="YE", above=True, ci=0.95,
-           pred_noise=False, return_cov=False, max_bytes: int = DEFAULT_MAX_BYTES, level_labels=None, attrs=None):
+           pred_noise=False, return_cov=False, max_bytes: int = DEFAULT_MAX_BYTES, level_labels=None, attrs=None, streamed=False):
     """``MarginalHIP.excess``: per period of ``freq`` the expected sum over the points of ``covariates`` of the target's
     excess over a threshold, sum_i w_i (c_i - tau_i)^+ -- ``above=False``: of its deficit sum_i w_i (tau_i - c_i)^+ -- with
     its exact standard error.
@@ -107,7 +129,8 @@ def excess(model, covariates, threshold=None, threshold_series=None, weights=Non
     Mean and se are exact; ``lower`` / ``upper`` are APPROXIMATE ``ci`` intervals: the quantiles of a gamma distribution
     matched to the exact mean and variance (the mean itself where the variance is 0).  With ``return_cov`` also the
     (L, P, P) covariance between the periods, level by level.  ``NotImplementedError``: a linear (non-log) target, and a
-    record whose dense footprint exceeds ``max_bytes`` (there is no streamed form)."""
+    record whose dense footprint exceeds ``max_bytes`` unless ``streamed=True`` (never chosen automatically): the covariance
+    is then produced a panel of rows at a time (``excess_sums``) and ``max_bytes`` bounds that pass's work area."""
     if (threshold is None) == (threshold_series is None):
         raise ValueError("give exactly one of threshold and threshold_series")
     if target_transform(model.dm)[0] != MODE_LOG:
@@ -132,7 +155,7 @@ def excess(model, covariates, threshold=None, threshold_series=None, weights=Non
     a = log_threshold(series[:, order])
     Xnew = torch.tensor(model.dm.Xnew(covariates), dtype=model.dtype)[torch.as_tensor(order)]
     mean, cov, total = excess_sums(model, Xnew, a, w_all[order], groups, len(labels), above=above, pred_noise=pred_noise,
-                                   max_bytes=max_bytes)
+                                   max_bytes=max_bytes, streamed=streamed)
     var = np.clip(np.diagonal(cov, axis1=1, axis2=2), 0.0, None)
     lower, upper = excess_intervals(mean, var, ci)
     with np.errstate(divide="ignore", invalid="ignore"):
@@ -177,7 +200,7 @@ def excess_load(model, covariates, criterion=None, limit=None, **kwargs):
     ``limit``: a load in kg per day; tau_i = limit_i / w_i with w_i the flux weights of ``annual_flux``, as in
     ``flux_exceedance``.
     Each a number, a list of levels, or a per-day series ((m,) array, or (L, m)).  The weights are the flux weights; a day
-    with w_i <= 0 (or a missing flow) is excluded.  The other keywords go to ``excess``."""
+    with w_i <= 0 (or a missing flow) is excluded.  ``streamed`` and the other keywords go to ``excess``."""
     if (criterion is None) == (limit is None):
         raise ValueError("give exactly one of criterion and limit")
     attrs = _target_attrs(model.dm)

@@ -152,16 +152,18 @@ class LoadestGPMarginalHIP(LoadestDataMixin, MarginalHIP):
 
     @is_fitted
     def excess_load(self, daily, criterion=None, limit=None, freq="YE", above=True, ci=0.95, pred_noise=False, return_cov=False,
-                    max_bytes=None):
+                    max_bytes=None, streamed=False):
         """The mass per period (kg) carried ABOVE an allowable load -- the load reduction a TMDL asks for -- with its exact
         standard error.  Exactly one of ``criterion`` (a concentration, mg/l: the allowable load of a day is criterion x
         flow) and ``limit`` (kg per day); each a number, a list of levels or a per-day series.  ``above=False``: the mass by
-        which the load stays below it.  See ``discontinuum_amd.excess.excess_load`` and ``MarginalHIP.excess``."""
+        which the load stays below it.  ``max_bytes`` / ``streamed``: as for ``MarginalHIP.excess``.  See
+        ``discontinuum_amd.excess.excess_load``."""
         from ..excess import excess_load
         from ..loads import DEFAULT_MAX_BYTES
 
         return excess_load(self, daily, criterion=criterion, limit=limit, freq=freq, above=above, ci=ci, pred_noise=pred_noise,
-                           return_cov=return_cov, max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes)
+                           return_cov=return_cov, max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes,
+                           streamed=streamed)
 
     def _flux_weights(self, daily):
         from ..loads import _target_attrs, flux_weights

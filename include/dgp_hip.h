@@ -959,6 +959,7 @@ int dgp_period_third_moments(int dtype, const void* cov_dev, int64_t m, int batc
                              double* k3_out_dev /* batch x ngroups */, void* stream);
 
 #include "dgp_hip_ext.h"
+#include "dgp_hip_ext2.h"
 
 #ifdef __cplusplus
 }
