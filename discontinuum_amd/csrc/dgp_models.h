@@ -12,6 +12,7 @@
 // Matern52 (1+sqrt5 r+5r^2/3)exp(-sqrt5 r); Periodic exp(-2 sin^2(pi dx/p)/l).
 // Parameter order = oracle/gp_oracle.py::loadest_gram / rating_gram.
 #pragma once
+#include <type_traits>
 #include <vector>
 #include "dgp_common.h"
 
@@ -297,7 +298,7 @@ struct Loadest {
 template <typename T>
 struct Rating {
   static constexpr int NX = 2;  // (time, stage)
-  static constexpr int NF = 5;  // (time, log(stage + 1e-6), gate g(stage), sin and cos of pi t / p)
+  static constexpr int NF = 5;  // (time, log(stage + 1e-6), signed gate feature, sin and cos of pi t / p)
   static constexpr int NTHETA = 16;
   struct Pre {
     T b;
@@ -327,16 +328,30 @@ struct Rating {
     p.inv_lm = (T)(1.0 / th[15]);
     return p;
   }
+  // (g, 1 - g) of a point from its signed gate feature (features()); a NaN stays a NaN in both.  Decoded on the SIGN BIT: far
+  // above the switch point the stored 1 - g underflows and the feature is -0.0, which must still read (g, 1 - g) = (1, 0)
+  static __device__ __forceinline__ void gates(T f, T* g, T* h) {
+    const bool inverted = __builtin_signbit(f);
+    *g = inverted ? T(1) + f : f;
+    *h = inverted ? -f : T(1) - f;
+  }
   static __device__ __forceinline__ void features(const T (&x)[NX], const Pre& p, T (&f)[NF]) {
     f[0] = x[0];
     f[1] = log(x[1] + T(1e-6));                        // LogWarpKernel, kernels.py:374-382
-    f[2] = T(1) / (T(1) + exp(T(20) * (x[1] - p.b)));  // SigmoidKernel, kernels.py:311-312 (a = 20)
+    // SigmoidKernel, kernels.py:311-312 (a = 20): the gate g = 1 / (1 + e^a) and the inverted gate h = 1 - g.  The feature
+    // carries whichever of the two is at most 1/2, from its own exponential -- g as it is, h NEGATED (gates() decodes) --
+    // so that a saturated gate keeps the relative accuracy of its small side: 1 - g of a g that rounds to 1 is 0, and
+    // with it every derivative of the bend and of b
+    const T a = T(20) * (x[1] - p.b);
+    f[2] = a > T(0) ? T(1) / (T(1) + exp(a)) : -(T(1) / (T(1) + exp(-a)));
     phase_features<T>(x[0], p.inv_p_d, &f[3], &f[4]);
   }
   template <bool GRAD>
   static __device__ __forceinline__ T pair(const T (&fi)[NF], const T (&fj)[NF], const Pre& p, T w, T (&acc)[NTHETA]) {
     const T dt = fi[0] - fj[0], adt = fabs(dt), adw = fabs(fi[1] - fj[1]);
-    const T gi = fi[2], gj = fj[2], hi = T(1) - gi, hj = T(1) - gj;
+    T gi, gj, hi, hj;
+    gates(fi[2], &gi, &hi);
+    gates(fj[2], &gj, &hj);
     const T gg = gi * gj, hh = hi * hj;
     T lower = T(0);
 #pragma unroll
@@ -390,7 +405,9 @@ struct Rating {
   static constexpr int NTERMS = 5;
   static __device__ __forceinline__ void terms(const T (&fi)[NF], const T (&fj)[NF], const Pre& p, T (&k)[NTERMS]) {
     const T dt = fi[0] - fj[0], adt = fabs(dt), adw = fabs(fi[1] - fj[1]);
-    const T gi = fi[2], gj = fj[2], hi = T(1) - gi, hj = T(1) - gj;
+    T gi, gj, hi, hj;
+    gates(fi[2], &gi, &hi);
+    gates(fj[2], &gj, &hj);
     const T gg = gi * gj, hh = hi * hj;
 #pragma unroll
     for (int a = 0; a < 2; ++a) {
@@ -419,12 +436,16 @@ struct Rating {
   static constexpr int NSF = 2;
   static __device__ __forceinline__ void slope_features(const T (&x)[NX], const T (&f)[NF], const Pre&, T (&g)[NSF]) {
     g[0] = T(1) / (x[1] + T(1e-6));
-    g[1] = T(-20) * f[2] * (T(1) - f[2]);
+    T gv, hv;
+    gates(f[2], &gv, &hv);
+    g[1] = T(-20) * gv * hv;
   }
   static __device__ __forceinline__ void slopes(const T (&fi)[NF], const T (&fj)[NF], const T (&gj)[NSF], const Pre& p,
                                                 T (&k)[1 + NX]) {
     const T dt = fi[0] - fj[0], adt = fabs(dt), dw = fi[1] - fj[1], adw = fabs(dw);
-    const T gi = fi[2], gjv = fj[2], hi = T(1) - gi, hj = T(1) - gjv;
+    T gi, gjv, hi, hj;
+    gates(fi[2], &gi, &hi);
+    gates(fj[2], &gjv, &hj);
     const T gg = gi * gjv, hh = hi * hj;
     T lo = T(0), lo_t = T(0), lo_w = T(0);
 #pragma unroll
@@ -459,7 +480,9 @@ struct Rating {
   // stationary, d/ds'[g(s) g(s') A] at s' = s is g g' A(0), so the value and the stage slope are correlated a priori.
   static constexpr int NPRIOR = 6;
   static __device__ __forceinline__ void prior_slopes(const T (&f)[NF], const T (&g)[NSF], const Pre& p, T (&pr)[NPRIOR]) {
-    const T gv = f[2], hv = T(1) - gv, wp = g[0], gp = g[1];
+    T gv, hv;
+    gates(f[2], &gv, &hv);
+    const T wp = g[0], gp = g[1];
     const T lo0 = p.os_a[0] + p.os_a[1];
     const T lo_tt = T(3) * (p.os_a[0] * p.inv_lt_a[0] * p.inv_lt_a[0] + p.os_a[1] * p.inv_lt_a[1] * p.inv_lt_a[1]);
     const T lo_ww = T(5.0 / 3.0) * (p.os_a[0] * p.inv_ls_a[0] * p.inv_ls_a[0] + p.os_a[1] * p.inv_ls_a[1] * p.inv_ls_a[1]);
@@ -520,21 +543,31 @@ const CompositeDesc* composite_current();  // descriptor of the model being disp
 template <typename T, int D>
 struct Composite {
   static constexpr int NX = D, NF = D, NTHETA = DGP_MAX_THETA;
-  struct Pre {
+  // float plans also keep what the rounding of 1 / p to float dropped (phase()); double plans carry nothing more
+  struct PeriodLo { float plo[DGP_MAX_THETA]; };
+  struct NoPeriodLo {};
+  struct Pre : std::conditional<sizeof(T) == 4, PeriodLo, NoPeriodLo>::type {
     CompositeDesc desc;
     T pv[DGP_MAX_THETA];  // outputscale -> sigma^2, lengthscale -> 1 / l, period -> 1 / p
   };
   static Pre prepare(const double* th) {
+    static_assert(sizeof(T) == 4 || sizeof(Pre) == sizeof(CompositeDesc) + sizeof(T) * DGP_MAX_THETA,
+                  "double plans: Pre as before");
     Pre p;
     p.desc = *composite_current();
     for (int i = 0; i < DGP_MAX_THETA; ++i) p.pv[i] = T(0);
+    if constexpr (sizeof(T) == 4)
+      for (int i = 0; i < DGP_MAX_THETA; ++i) p.plo[i] = 0.0f;
     for (int t = 0; t < p.desc.nterms; ++t) {
       const CompositeDesc::Term& tm = p.desc.term[t];
       if (tm.os >= 0) p.pv[tm.os] = (T)th[tm.os];
       for (int f = 0; f < tm.nfac; ++f) {
         const CompositeDesc::Fac& fc = tm.fac[f];
         for (int j = 0; j < (fc.ard ? fc.ndims : 1); ++j) p.pv[fc.ls + j] = (T)(1.0 / th[fc.ls + j]);
-        if (fc.period >= 0) p.pv[fc.period] = (T)(1.0 / th[fc.period]);
+        if (fc.period >= 0) {
+          p.pv[fc.period] = (T)(1.0 / th[fc.period]);
+          if constexpr (sizeof(T) == 4) p.plo[fc.period] = (float)(1.0 / th[fc.period] - (double)p.pv[fc.period]);
+        }
       }
     }
     return p;
@@ -543,20 +576,30 @@ struct Composite {
 #pragma unroll
     for (int j = 0; j < D; ++j) f[j] = x[j];
   }
+  // sin and cos of pi (x_i - x_j) / p of a Periodic factor (its period at theta index q), in double whatever T is.  The
+  // difference of two float coordinates is exact in double and 1 / p has its dropped part back: the sine of a float
+  // DIFFERENCE times a float 1 / p is off by pi |dx| 2^-24 -- 3e-6 at |dx| = 30 --, which a short periodic lengthscale beside
+  // long Matern ones turns into 4 / l times that in the entry (the fused models' per-point phase features avoid the same)
+  static __device__ __forceinline__ void phase(T xi, T xj, const Pre& p, int q, T* s, T* c) {
+    double inv_p = (double)p.pv[q];
+    if constexpr (sizeof(T) == 4) inv_p += (double)p.plo[q];
+    double sd, cd;
+    sincospi(((double)xi - (double)xj) * inv_p, &sd, &cd);
+    *s = (T)sd;
+    *c = (T)cd;
+  }
   // value of one factor; *aux = the factor's common derivative weight: d v / d l_j = aux * z_j^2 * inv_l_j (stationary
   // factors, z_j = delta_j / l_j); for the periodic factor aux = v and the caller uses s, c
-  static __device__ __forceinline__ T factor(const CompositeDesc::Fac& fc, const T (&fi)[NF], const T (&fj)[NF], const T* pv,
+  static __device__ __forceinline__ T factor(const CompositeDesc::Fac& fc, const T (&fi)[NF], const T (&fj)[NF], const Pre& p,
                                              T* aux, T* sper, T* cper, T* dper) {
+    const T* pv = p.pv;
     if (fc.type == DGP_FAC_PERIODIC) {
-      const T dt = fi[fc.dims[0]] - fj[fc.dims[0]];
-      double sd, cd;
-      sincospi((double)dt * (double)pv[fc.period], &sd, &cd);
-      const T s = (T)sd;
+      T s;
+      phase(fi[fc.dims[0]], fj[fc.dims[0]], p, fc.period, &s, cper);
       const T v = exp_nonpos(T(-2) * s * s * pv[fc.ls]);
       *aux = v;
       *sper = s;
-      *cper = (T)cd;
-      *dper = dt;
+      *dper = fi[fc.dims[0]] - fj[fc.dims[0]];
       return v;
     }
     T sq = T(0);
@@ -594,7 +637,7 @@ struct Composite {
       T v[DGP_C_FMAX], aux[DGP_C_FMAX], sp[DGP_C_FMAX], cp[DGP_C_FMAX], dp[DGP_C_FMAX];
       T prod = T(1);
       for (int f = 0; f < tm.nfac; ++f) {
-        v[f] = factor(tm.fac[f], fi, fj, p.pv, &aux[f], &sp[f], &cp[f], &dp[f]);
+        v[f] = factor(tm.fac[f], fi, fj, p, &aux[f], &sp[f], &cp[f], &dp[f]);
         prod *= v[f];
       }
       const T os = tm.os >= 0 ? p.pv[tm.os] : T(1);
@@ -625,12 +668,11 @@ struct Composite {
   // accessors fi(column), fj(column): the column is a descriptor entry, and a register array indexed by it lives in scratch
   // memory from D = 3 on in double -- kernels hand in accessors that read their LDS strips instead.
   template <typename FI, typename FJ>
-  static __device__ __forceinline__ T factor_value(const CompositeDesc::Fac& fc, const FI& fi, const FJ& fj, const T* pv) {
+  static __device__ __forceinline__ T factor_value(const CompositeDesc::Fac& fc, const FI& fi, const FJ& fj, const Pre& p) {
+    const T* pv = p.pv;
     if (fc.type == DGP_FAC_PERIODIC) {
-      const T dt = fi(fc.dims[0]) - fj(fc.dims[0]);
-      double sd, cd;
-      sincospi((double)dt * (double)pv[fc.period], &sd, &cd);
-      const T s = (T)sd;
+      T s, c;
+      phase(fi(fc.dims[0]), fj(fc.dims[0]), p, fc.period, &s, &c);
       return exp_nonpos(T(-2) * s * s * pv[fc.ls]);
     }
     T sq = T(0);
@@ -654,7 +696,7 @@ struct Composite {
   static __device__ __forceinline__ T term(int t, const FI& fi, const FJ& fj, const Pre& p) {
     const CompositeDesc::Term& tm = p.desc.term[t];
     T prod = T(1);
-    for (int f = 0; f < tm.nfac; ++f) prod *= factor_value(tm.fac[f], fi, fj, p.pv);
+    for (int f = 0; f < tm.nfac; ++f) prod *= factor_value(tm.fac[f], fi, fj, p);
     return (tm.os >= 0 ? p.pv[tm.os] : T(1)) * prod;
   }
   // One requested column at a time for the interpreter (posterior slopes): -> d k / d x*_col of the test point j, *kval =
@@ -673,12 +715,10 @@ struct Composite {
         const CompositeDesc::Fac& fc = tm.fac[f];
         T v, dv = T(0);
         if (fc.type == DGP_FAC_PERIODIC) {
-          const T dt = fi(fc.dims[0]) - fj(fc.dims[0]);
-          double sd, cd;
-          sincospi((double)dt * (double)p.pv[fc.period], &sd, &cd);
-          const T s = (T)sd;
+          T s, c;
+          phase(fi(fc.dims[0]), fj(fc.dims[0]), p, fc.period, &s, &c);
           v = exp_nonpos(T(-2) * s * s * p.pv[fc.ls]);
-          if (fc.dims[0] == col) dv = v * (T(4.0 * 3.14159265358979323846) * p.pv[fc.ls] * p.pv[fc.period]) * (s * (T)cd);
+          if (fc.dims[0] == col) dv = v * (T(4.0 * 3.14159265358979323846) * p.pv[fc.ls] * p.pv[fc.period]) * (s * c);
         } else {
           T sq = T(0), zl = T(0);
           for (int j = 0; j < fc.ndims; ++j) {

@@ -16,7 +16,8 @@ from discontinuum_amd import _lib
 
 pytestmark = pytest.mark.gpu
 
-GOLD = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "*.npz")))
+# the objective fixtures of make_golden.py (<model>_d<d>_n<n>_p<k>.npz); golden/ also holds the domain_*.npz of make_domain_pairs.py
+GOLD = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "*_d[0-9]*_n[0-9]*_p[0-9]*.npz")))
 
 
 @pytest.mark.parametrize("path", GOLD, ids=[os.path.basename(p)[:-4] for p in GOLD])

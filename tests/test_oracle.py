@@ -13,7 +13,8 @@ from sklearn.gaussian_process import kernels as sk
 
 from oracle import gp_oracle as orc
 
-GOLD = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "*.npz")))
+# the objective fixtures of make_golden.py (<model>_d<d>_n<n>_p<k>.npz); golden/ also holds the domain_*.npz of make_domain_pairs.py
+GOLD = sorted(glob.glob(os.path.join(os.path.dirname(__file__), "golden", "*_d[0-9]*_n[0-9]*_p[0-9]*.npz")))
 
 
 def test_golden_fixtures_exist():
