@@ -866,6 +866,84 @@ class GPPlan:
         M = int(self.lib.dgp_padded_n(int(m)))
         return stream_panel_rows(size(128), size(256) - size(128) if M > 128 else 0, M, max_bytes, "the streamed excess pass")
 
+    _SV_SIZES = ("(1 <= m <= 2^20, 1 <= ngroups <= 65535, 0 <= nrows <= 64, 1 <= nterms <= 64)")
+
+    def posterior_sample_value(self, theta, Xs: torch.Tensor, a, scale2, groups, ngroups: int, obs_var=None, rows=None, nterms=None,
+                               panel_rows=None, max_bytes=None):
+        """``sample_value`` of the posterior at Xs straight from the held factorisation (``dgp_posterior_sample_value``): the
+        covariance is produced ``panel_rows`` rows at a time and the (M, M) matrix is never formed.  Xs (m, d) -- (batch, m, d)
+        for a batched plan, theta (batch, ntheta) --; ``a``, ``scale2``, ``groups``, ``ngroups``, ``obs_var`` (the plan's dtype),
+        ``rows`` and the results (gain, var) as for ``sample_value``.  C_cc is the predicted variance, never a panel's diagonal.
+        ``nterms``: the series length; None picks ``series_terms`` of s^2 max predicted variance over the included days (one
+        ``predict``).  ``panel_rows``: a positive multiple of 128, or None: ``sample_value_panel_rows`` of ``max_bytes`` -- the
+        largest panel, at most M rows, whose work area fits; a ``ValueError`` names the bytes when 128 rows do not.  The work
+        area (2 N M + R M plan-dtype elements and M (2 + P K) + P doubles per site) is kept between calls; a ``RuntimeError``
+        names its bytes when it exceeds the free device memory."""
+        lead, m, th = self._lead, self._check_xs(Xs), self._theta(theta)
+        P = int(ngroups)
+        dev = self.device
+        with torch.cuda.device(dev):
+            _, a_t, g_t, ov_t, s2 = _moment_inputs(dev, self.dtype, lead, m, None, a, groups, obs_var, scale2)
+            rows_t = None if rows is None else _row_matrix(rows, "rows", "nrows", lead, m, dev)
+            nrows = 0 if rows_t is None else int(rows_t.shape[-2])
+            if nrows == 0:
+                rows_t = None
+            if nterms is None:
+                var = self.predict(theta, Xs)[1].double()
+                top = torch.where(g_t >= 0, var, torch.zeros_like(var)).reshape(self.batch, -1).amax(dim=1)
+                nterms = series_terms(float((s2 * top).max()))
+            K = int(nterms)
+            if int(self.lib.dgp_posterior_sample_value_workspace_bytes(self._h, m, P, nrows, K, 128)) == 0:
+                raise ValueError(f"bad size: m = {m}, ngroups = {P}, nrows = {nrows}, nterms = {K} {self._SV_SIZES}")
+            R = self.sample_value_panel_rows(m, P, nrows, K, max_bytes) if panel_rows is None else int(panel_rows)
+            if R <= 0 or R % 128:
+                raise ValueError(f"panel_rows must be a positive multiple of 128, not {panel_rows}")
+            need = int(self.lib.dgp_posterior_sample_value_workspace_bytes(self._h, m, P, nrows, K, R))
+            work = self._work_area("_psv_ws", need, "dgp_posterior_sample_value", check_free=True)
+            xs = Xs.contiguous()
+            gain, var_out = self._empty(P, m, dtype=torch.float64), self._empty(m, dtype=torch.float64)
+            self._call("dgp_posterior_sample_value", th, _ptr(xs), m, _ptr(a_t), _ptr(s2), _ptr(g_t), P, _ptr(ov_t), _ptr(rows_t), nrows,
+                       K, R, work, need, _ptr(gain), _ptr(var_out))
+        return gain, var_out
+
+    def sample_value_panel_rows(self, m: int, ngroups: int, nrows: int, nterms: int, max_bytes=None) -> int:
+        """The panel height ``posterior_sample_value`` picks for m points, ``ngroups`` groups, ``nrows`` conditioning rows and
+        ``nterms`` series terms under ``max_bytes`` (default ``loads.DEFAULT_MAX_BYTES``): ``stream_panel_rows`` on the sizes
+        ``dgp_posterior_sample_value_workspace_bytes`` reports."""
+        if max_bytes is None:
+            from .loads import DEFAULT_MAX_BYTES as max_bytes
+        size = lambda R: int(self.lib.dgp_posterior_sample_value_workspace_bytes(self._h, int(m), int(ngroups), int(nrows), int(nterms), R))  # noqa: E731
+        if size(128) == 0:
+            raise ValueError(f"bad size: m = {m}, ngroups = {ngroups}, nrows = {nrows}, nterms = {nterms} {self._SV_SIZES}")
+        M = int(self.lib.dgp_padded_n(int(m)))
+        return stream_panel_rows(size(128), size(256) - size(128) if M > 128 else 0, M, max_bytes, "the streamed value of samples")
+
+    def posterior_cov_columns(self, theta, Xs: torch.Tensor, idx):
+        """Columns C[:, idx] of the latent posterior covariance at Xs (``dgp_posterior_cov_columns``) as (ncols, m) float64 --
+        (batch, ncols, m) for a batched plan, ``idx`` (batch, ncols) --, 1 <= ncols <= 64 indices in 0 .. m-1, from the held
+        factorisation: the prediction's front end plus one read of V per column.  The dense matrix is never formed."""
+        lead, m, th = self._lead, self._check_xs(Xs), self._theta(theta)
+        idx_t = torch.as_tensor(idx).to(torch.int64).reshape(lead + (-1,)) if lead else torch.as_tensor(idx).to(torch.int64).reshape(-1)
+        ncols = int(idx_t.shape[-1])
+        if not 1 <= ncols <= 64:
+            raise ValueError(f"posterior_cov_columns takes 1 .. 64 columns, not {ncols}")
+        if int(idx_t.min()) < 0 or int(idx_t.max()) >= m:
+            raise ValueError(f"column index out of range for {m} points")
+        need = int(self.lib.dgp_posterior_cov_columns_workspace_bytes(self._h, m, ncols))
+        if need == 0:
+            raise ValueError(f"bad size: m = {m}, ncols = {ncols} (1 <= m <= 2^20, 1 <= ncols <= 64)")
+        with torch.cuda.device(self.device):
+            i32 = idx_t.to(self.device, torch.int32).contiguous()
+            work = self._work_area("_pcc_ws", need, "dgp_posterior_cov_columns", check_free=True)
+            xs = Xs.contiguous()
+            cols = self._empty(ncols, m, dtype=torch.float64)
+            self._call("dgp_posterior_cov_columns", th, _ptr(xs), m, _ptr(i32), ncols, work, need, _ptr(cols))
+        return cols
+
+    def lowrank_period_moments(self, rows, m: int, mu, scale2, w, groups, ngroups: int, mode: int):
+        """The module-level ``lowrank_period_moments``."""
+        return lowrank_period_moments(rows, m, mu, scale2, w, groups, ngroups, mode)
+
     def predict_mean(self, theta, Xs: torch.Tensor):
         """K(X*, X) alpha from the held factorisation (no variance work).  Batched plans: Xs (batch, m, d) -> (batch, m)."""
         th, m = self._theta(theta), self._check_xs(Xs)
@@ -1014,6 +1092,34 @@ def period_moments(cov: torch.Tensor, m: int, mu: torch.Tensor, scale2, w: torch
         cov_out = torch.empty(lead + (P, P), dtype=torch.float64, device=dev)
         _call("dgp_period_moments", _DTYPES[cov.dtype], int(mode), _ptr(cov), m, B, _ptr(mu_t), _ptr(s2), _ptr(w_t), _ptr(g_t), P,
               _ptr(ev_t), _ptr(work), need, _ptr(mean_out), _ptr(cov_out))
+    return mean_out, cov_out
+
+
+def lowrank_period_moments(rows: torch.Tensor, m: int, mu: torch.Tensor, scale2, w: torch.Tensor, groups: torch.Tensor, ngroups: int,
+                           mode: int):
+    """``period_moments`` on the low-rank covariance R = rows^T rows without ever forming R (``dgp_lowrank_period_moments``):
+    ``rows`` (nrows, m) or (B, nrows, m) float64 on the device, 1 <= nrows <= 64 -- the conditioning rows of a sampling
+    design, whose R is the covariance the samples explain; ``mu`` (the MAPPED mean; float64), ``scale2``, ``w``, ``groups``,
+    ``ngroups``, ``mode`` as for ``period_moments``.  -> (mean (P,), cov (P, P)) or ((B, P), (B, P, P)), float64 device
+    tensors; cov is exactly symmetric."""
+    if not (torch.is_tensor(rows) and rows.is_cuda and rows.dtype == torch.float64 and rows.dim() in (2, 3) and rows.shape[-1] == int(m)
+            and 1 <= rows.shape[-2] <= 64):
+        raise ValueError(f"rows must be a float64 CUDA tensor of shape (nrows, {int(m)}) or (B, nrows, {int(m)}) with 1 <= nrows <= 64")
+    lib = _lib.load()
+    lead = (rows.shape[0],) if rows.dim() == 3 else ()
+    B, dev = (lead[0] if lead else 1), rows.device
+    m, P, nrows = int(m), int(ngroups), int(rows.shape[-2])
+    with torch.cuda.device(dev):
+        mu_t, w_t, g_t, _, s2 = _moment_inputs(dev, torch.float64, lead, m, mu, w, groups, None, scale2)
+        need = int(lib.dgp_period_moments_workspace_bytes(m, P, B))
+        if need == 0:
+            raise ValueError(f"bad size: m = {m}, ngroups = {P}, batch = {B} (1 <= m <= 2^20, 1 <= ngroups <= 65535, 1 <= batch <= 1024)")
+        rows_t = rows.contiguous()
+        work = torch.empty(need, dtype=torch.uint8, device=dev)
+        mean_out = torch.empty(lead + (P,), dtype=torch.float64, device=dev)
+        cov_out = torch.empty(lead + (P, P), dtype=torch.float64, device=dev)
+        _call("dgp_lowrank_period_moments", int(mode), _ptr(rows_t), nrows, m, B, _ptr(mu_t), _ptr(s2), _ptr(w_t), _ptr(g_t), P,
+              _ptr(work), need, _ptr(mean_out), _ptr(cov_out))
     return mean_out, cov_out
 
 

@@ -362,6 +362,95 @@ int period_moments_mode(const T* cov, long M, int m, int B, const T* mu, const d
   return (int)hipGetLastError();
 }
 
+// ---- the same moments on R = B^T B (B: nrows x m conditioning rows) without ever forming R (dgp_lowrank_period_moments).
+// R_ij is a product of nrows terms, so nothing is read twice and nothing is stored: one thread per point forms R_ii for the
+// prep pass (left where Y will be), then one workgroup per (64-row block I, group h) -- a block past h's last column writes
+// zeros and leaves, as in the streamed pass -- holds its rows' B_ti in LDS, lanes along i, and walks h's columns 8 at a time,
+// the four waves taking the 8-column tiles in turn: the columns' B_tj are wave-uniform loads, 8 accumulators per lane, t
+// ascending (fused multiply-adds: R_ij and R_ji are the same bits), then a_j phi(R_ij) into the lane's sum; the waves' sums are
+// added in a fixed order.  The reduce pass is pm_reduce_kernel.
+constexpr int LR_ROWS = 64;  // rows of a workgroup
+constexpr int LR_COLS = 8;   // columns of a wave's tile
+
+__global__ __launch_bounds__(256) void lr_diag_kernel(const double* __restrict__ rows, int nrows, long M, int m, int P, double* work,
+                                                      long ws) {
+  const long j = (long)blockIdx.x * 256 + threadIdx.x;
+  const int z = blockIdx.z;
+  if (j >= M) return;
+  double r = 0.0;
+  if (j < m)
+    for (int t = 0; t < nrows; ++t) {
+      const double b = rows[((long)z * nrows + t) * m + j];
+      r = __builtin_fma(b, b, r);
+    }
+  work[(long)z * ws + 2 * M + j] = r;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void lr_rows_kernel(const double* __restrict__ rows, int nrows, long M, int m, int P,
+                                                      const double* __restrict__ scale2, const int* __restrict__ group,
+                                                      double* __restrict__ work, long ws) {
+  const int rb = blockIdx.x, h = blockIdx.y, z = blockIdx.z;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  double* base = work + (long)z * ws;
+  const double* a = base;
+  double* Y = base + 2 * M;
+  int c0, c1;
+  pm_range((const int*)(base + 2 * M + M * (long)P), h, c0, c1);
+  const int r0 = rb * LR_ROWS, i = r0 + lane;
+  if (r0 >= c1) {  // every row lies in a group above h, is excluded or is pad: the reduce pass reads these times a_i = 0 or not at all
+    if (tid < LR_ROWS) Y[(long)i * P + h] = 0.0;
+    return;
+  }
+  extern __shared__ __attribute__((aligned(16))) char lr_smem[];
+  double* bi = (double*)lr_smem;        // [nrows][LR_ROWS]: B[t][r0 + lane]
+  double* part = bi + nrows * LR_ROWS;  // [4][LR_ROWS]
+  const double* bz = rows + (long)z * nrows * m;
+  for (int t = wave; t < nrows; t += 4) bi[t * LR_ROWS + lane] = i < m ? bz[(long)t * m + i] : 0.0;
+  __syncthreads();
+  const double s2 = scale2[z];
+  double acc = 0.0;
+  for (int j0 = c0 / LR_COLS * LR_COLS + wave * LR_COLS; j0 < c1; j0 += 4 * LR_COLS) {
+    double x[LR_COLS];
+#pragma unroll
+    for (int u = 0; u < LR_COLS; ++u) x[u] = 0.0;
+    const bool whole = j0 + LR_COLS <= m;
+    for (int t = 0; t < nrows; ++t) {
+      const double bv = bi[t * LR_ROWS + lane];
+      const double* br = bz + (long)t * m + j0;
+#pragma unroll
+      for (int u = 0; u < LR_COLS; ++u) x[u] = __builtin_fma(bv, whole || j0 + u < m ? br[u] : 0.0, x[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < LR_COLS; ++u) {
+      const int j = j0 + u;
+      if (j >= c0 && j < c1) acc += a[j] * pm_phi<MODE>(s2, x[u]);  // wave-uniform
+    }
+  }
+  part[wave * LR_ROWS + lane] = acc;
+  __syncthreads();
+  if (tid < LR_ROWS) {
+    const double v = ((part[lane] + part[LR_ROWS + lane]) + part[2 * LR_ROWS + lane]) + part[3 * LR_ROWS + lane];
+    Y[(long)i * P + h] = i < m && group[(long)z * m + i] >= 0 ? v : 0.0;
+  }
+}
+
+template <int MODE>
+int lowrank_period_moments_mode(const double* rows, int nrows, long M, int m, int B, const double* mu, const double* scale2,
+                                const double* w, const int* group, int P, double* work, double* mean_out, double* cov_out,
+                                hipStream_t s) {
+  const long ws = pm_site_doubles(M, P);
+  pm_init_kernel<<<dim3((unsigned)((P + 255) / 256), 1, (unsigned)B), 256, 0, s>>>(work, ws, M, P);
+  lr_diag_kernel<<<dim3((unsigned)((M + 255) / 256), 1, (unsigned)B), 256, 0, s>>>(rows, nrows, M, m, P, work, ws);
+  // R_ii sits at the head of Y (site stride ws, step 1) until the rows pass overwrites it
+  pm_prep_kernel<double, MODE><<<dim3((unsigned)((M + 255) / 256), 1, (unsigned)B), 256, 0, s>>>(work + 2 * M, ws, 1, M, m, P, mu, scale2, w,
+                                                                                               group, nullptr, work, ws);
+  const size_t lds = ((size_t)nrows + 4) * LR_ROWS * sizeof(double);
+  lr_rows_kernel<MODE><<<dim3((unsigned)(M / LR_ROWS), (unsigned)P, (unsigned)B), 256, lds, s>>>(rows, nrows, M, m, P, scale2, group, work, ws);
+  pm_reduce_kernel<<<dim3((unsigned)((P + 63) / 64), (unsigned)P, (unsigned)B), 256, 0, s>>>(M, P, work, ws, mean_out, cov_out);
+  return (int)hipGetLastError();
+}
+
 }  // namespace
 
 static size_t period_moments_workspace_bytes(long m, int P, int B) {
@@ -456,6 +545,27 @@ int dgp_period_moments(int dtype, int mode, const void* cov, int64_t m, int batc
                      : period_moments<float>(mode, (const float*)cov, m, batch, (const float*)mu, scale2, w, group, ngroups,
                                              (const float*)extra_var, (double*)work, mean_out, cov_out, s);
   return wrap(rc, "dgp_period_moments");
+}
+
+int dgp_lowrank_period_moments(int mode, const double* rows, int nrows, int64_t m, int batch, const double* mu, const double* scale2,
+                               const double* w, const int32_t* group, int ngroups, void* work, size_t work_bytes, double* mean_out,
+                               double* cov_out, void* stream) {
+  if (mode != 0 && mode != 1) return fail(DGP_E_ARG, "dgp_lowrank_period_moments: mode must be 0 (linear) or 1 (log)");
+  if (!rows || !mu || !scale2 || !w || !group || !mean_out || !cov_out)
+    return fail(DGP_E_ARG, "dgp_lowrank_period_moments: null argument");
+  if (m <= 0 || m > (1 << 20) || ngroups <= 0 || ngroups > 65535 || nrows < 1 || nrows > 64 || batch <= 0 || batch > DGP_MAX_BATCH_SITES)
+    return fail(DGP_E_ARG,
+                "dgp_lowrank_period_moments: bad size (1 <= m <= 2^20, 1 <= ngroups <= 65535, 1 <= nrows <= 64, 1 <= batch <= 1024)");
+  if (!work || work_bytes < period_moments_workspace_bytes(m, ngroups, batch))
+    return fail(DGP_E_WORKSPACE, "dgp_lowrank_period_moments: workspace missing or too small");
+  if (((uintptr_t)work & 7) != 0) return fail(DGP_E_ARG, "dgp_lowrank_period_moments: the work area must be 8-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const long M = round_up(m, DGP_TILE_HOST);
+  const int rc = mode == 1 ? lowrank_period_moments_mode<1>(rows, nrows, M, (int)m, batch, mu, scale2, w, group, ngroups, (double*)work,
+                                                            mean_out, cov_out, s)
+                           : lowrank_period_moments_mode<0>(rows, nrows, M, (int)m, batch, mu, scale2, w, group, ngroups, (double*)work,
+                                                            mean_out, cov_out, s);
+  return wrap(rc, "dgp_lowrank_period_moments");
 }
 
 size_t dgp_posterior_period_moments_workspace_bytes(const dgp_plan* p, int64_t m, int ngroups) {

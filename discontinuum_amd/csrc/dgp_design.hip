@@ -25,17 +25,14 @@
 // No floating-point atomics, every sum in a fixed order: bitwise repeatable.  All arithmetic after the loads is double.
 #include <climits>
 
-#include "dgp_common.h"
+#include "dgp_design.h"
 #include "dgp_plan.h"
 
 namespace dgp {
 
 namespace {
 
-constexpr int SV_CAND = 64;           // candidates of a workgroup: one wave, a lane each
-constexpr int SV_DAYS = 16;           // days of a tile
-constexpr int SV_LD = SV_CAND + 1;    // leading dimension of the staged tile [SV_DAYS][SV_LD]
-constexpr int SV_FILL = 4096;         // workgroups per site the slab count aims for
+constexpr int SV_FILL = 4096;         // workgroups per site the slab count aims for (the tile shape: dgp_design.h)
 
 // slabs per group: a function of (M, P) alone
 __host__ __device__ inline int sv_slabs(long M, int P) {
@@ -51,10 +48,6 @@ __host__ __device__ inline int sv_slabs(long M, int P) {
 __host__ __device__ inline long sv_site_doubles(long M, int P, int K) {
   const int Q = sv_slabs(M, P);
   return M + (Q > 1 ? (long)P * Q * K * M : 0) + P;
-}
-
-__device__ __forceinline__ double sv_readlane(double v, int l) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
 }
 
 __global__ __launch_bounds__(256) void sv_init_kernel(double* work, long ws, int P) {
@@ -89,12 +82,7 @@ __global__ __launch_bounds__(256) void sv_prep_kernel(const T* __restrict__ cov,
       v -= b * b;
     }
     if (ov) v += (double)ov[k];
-    if (v > 0.0)
-      r = 1.0 / sqrt(v);
-    else if (v != v)
-      r = v;  // NaN in, NaN out
-    else
-      v = 0.0;
+    sv_inv_sd(v, r);  // NaN in, NaN out
     var_out[k] = v;
   }
   rs[j] = r;

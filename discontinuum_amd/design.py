@@ -46,8 +46,12 @@ def default_sample_var(model):
     return 0.0 if second is None else float(second.detach().reshape(-1)[0])
 
 
-def _prepare(model, covariates, weights, freq, sample_var, max_bytes, extra_buffers=0):
-    """The shared front half: groups, the posterior covariance, the current moments, A_i, tau^2 and the series length."""
+def _prepare(model, covariates, weights, freq, sample_var, max_bytes, extra_buffers=0, streamed=False):
+    """The shared front half: groups, the posterior covariance, the current moments, A_i, tau^2 and the series length.
+    ``streamed``: no covariance -- the latent mean and variance from ``predict``, the current moments from
+    ``posterior_period_moments``, a column provider (``posterior_cov_columns``) where the dense path carries ``cov``, and
+    the panel height ``max_bytes`` leaves ``posterior_sample_value`` (a ``ValueError`` naming the bytes when 128 rows do
+    not fit)."""
     time_all = np.asarray(covariates.coords["time"].values).reshape(-1).astype("datetime64[ns]")
     m_all = len(time_all)
     w_all = np.asarray(weights, dtype=np.float64).reshape(-1)
@@ -69,11 +73,13 @@ def _prepare(model, covariates, weights, freq, sample_var, max_bytes, extra_buff
     esz = torch.empty((), dtype=model.dtype).element_size()
     M = int(_lib.load().dgp_padded_n(m))
     need = _site_bytes(model.dm.X.shape[0], m, esz) + extra_buffers * 8 * M * M
-    if need > max_bytes:
+    if not streamed and need > max_bytes:
         raise ValueError(f"the value of samples needs the dense posterior covariance{' and a second (M, M) buffer' if extra_buffers else ''}"
                          f": a footprint of {need} bytes for m = {m} points exceeds max_bytes = {max_bytes}")
     Xnew = torch.tensor(model.dm.Xnew(covariates), dtype=model.dtype)[torch.as_tensor(order)].to(model.device).contiguous()
     model._eval_ready(Xnew)
+    if streamed:
+        return _prepare_streamed(model, Xnew, time_all, m_all, w_all, order, groups, labels, n_points, tau2, mode, s, t, freq, max_bytes)
     with torch.no_grad():
         kmean, cov = model._plan.posterior_cov(model._factor_theta, Xnew)
         dev = cov.device
@@ -86,10 +92,37 @@ def _prepare(model, covariates, weights, freq, sample_var, max_bytes, extra_buff
         # tau^2 as the kernel reads it (the buffer's dtype): the rows formed on the host divide by the same variance
         obs_var = torch.as_tensor(tau2, dtype=cov.dtype, device=dev)
     return SimpleNamespace(
-        model=model, cov=cov, m=m, P=P, mode=mode, s2=s * s, mapped=mapped, diag=diag, w=w_all[order], groups=groups,
+        model=model, cov=cov, dev=dev, streamed=False, m=m, P=P, mode=mode, s2=s * s, mapped=mapped, diag=diag, w=w_all[order], groups=groups,
         labels=labels, n_points=n_points, order=order, time=time_all[order], m_all=m_all, a=a.contiguous(),
         tau2=obs_var.double(), obs_var=obs_var, nterms=series_terms(beta) if mode == MODE_LOG else 1,
         mean_now=mean_d.cpu().numpy(), cov_now=cov_d.cpu().numpy(), freq=freq)
+
+
+def _prepare_streamed(model, Xnew, time_all, m_all, w_all, order, groups, labels, n_points, tau2, mode, s, t, freq, max_bytes):
+    """``_prepare`` without the dense covariance (``streamed=True``): the same fields, ``cov`` = None, plus ``columns``
+    (index list -> C[:, idx] as (len, m) float64), ``gain`` (rows -> ``posterior_sample_value``) and ``panel_rows``."""
+    plan, theta = model._plan, model._factor_theta
+    m, P = len(order), len(labels)
+    with torch.no_grad():
+        kmean, var = plan.predict(theta, Xnew)
+        dev = var.device
+        mapped = (s * (kmean + model.model.prior_mean(Xnew)) + t).contiguous()
+        mean_d, cov_d = plan.posterior_period_moments(theta, Xnew, mapped, s * s, w_all[order], groups, P, mode)
+        w_t = torch.as_tensor(w_all[order], dtype=torch.float64, device=dev)
+        diag = var.double()
+        a = w_t * torch.exp(mapped.double() + 0.5 * s * s * diag) if mode == MODE_LOG else w_t
+        beta = s * s * float(diag.max()) if mode == MODE_LOG else 0.0
+        obs_var = torch.as_tensor(tau2, dtype=var.dtype, device=dev)
+    nterms = series_terms(beta) if mode == MODE_LOG else 1
+    panel_rows = plan.sample_value_panel_rows(m, P, MAX_ROWS, nterms, max_bytes)
+    fit = SimpleNamespace(
+        model=model, cov=None, dev=dev, streamed=True, m=m, P=P, mode=mode, s2=s * s, mapped=mapped, diag=diag, w=w_all[order],
+        groups=groups, labels=labels, n_points=n_points, order=order, time=time_all[order], m_all=m_all, a=a.contiguous(),
+        tau2=obs_var.double(), obs_var=obs_var, nterms=nterms, mean_now=mean_d.cpu().numpy(), cov_now=cov_d.cpu().numpy(), freq=freq,
+        panel_rows=panel_rows, columns=lambda idx: plan.posterior_cov_columns(theta, Xnew, idx))
+    fit.gain = lambda rows: plan.posterior_sample_value(theta, Xnew, fit.a, fit.s2, groups, P, obs_var=obs_var, rows=rows,
+                                                        nterms=nterms, panel_rows=panel_rows)
+    return fit
 
 
 def _day_indices(fit, days, what):
@@ -116,13 +149,16 @@ def _day_indices(fit, days, what):
 
 def _column(fit, c):
     """Column c of the symmetric covariance from the buffer's lower triangle, in double."""
+    if fit.streamed:
+        return fit.columns([int(c)])[0]
     return torch.cat([fit.cov[c, :c], fit.cov[c:fit.m, c]]).double()
 
 
-def _next_row(fit, rows, c, var=None):
+def _next_row(fit, rows, c, var=None, col=None):
     """The conditioning row of a sample on day c after ``rows``: (C[:, c] - rows^T rows[:, c]) / sqrt(v'_c); ``var``: v'_c
-    as ``dgp_sample_value`` returned it (default: computed here).  A sample with v'_c not > 0 carries nothing: a zero row."""
-    col = _column(fit, c)
+    as ``dgp_sample_value`` returned it (default: computed here); ``col``: C[:, c] when the caller already holds it.  A
+    sample with v'_c not > 0 carries nothing: a zero row."""
+    col = _column(fit, c) if col is None else col
     if rows.shape[0]:
         col = col - rows.T @ rows[:, c]
     v = col[c] + fit.tau2[c] if var is None else var
@@ -131,9 +167,14 @@ def _next_row(fit, rows, c, var=None):
 
 def conditioning_rows(fit, picks):
     """Rows B (len(picks), m) of the pivoted-Cholesky recurrence for the samples ``picks`` (positions, in order)."""
-    rows = torch.zeros(len(picks), fit.m, dtype=torch.float64, device=fit.cov.device)
+    rows = torch.zeros(len(picks), fit.m, dtype=torch.float64, device=fit.dev)
+    cols = None
+    if fit.streamed and len(picks):  # every distinct day's column in calls of up to MAX_ROWS columns
+        days = sorted({int(c) for c in picks})
+        got = torch.cat([fit.columns(days[lo:lo + MAX_ROWS]) for lo in range(0, len(days), MAX_ROWS)])
+        cols = {c: got[k] for k, c in enumerate(days)}
     for k, c in enumerate(picks):
-        rows[k] = _next_row(fit, rows[:k], int(c))
+        rows[k] = _next_row(fit, rows[:k], int(c), col=None if cols is None else cols[int(c)])
     return rows
 
 
@@ -153,11 +194,32 @@ def _explained(fit, R):
     return V.cpu().numpy()
 
 
+def _explained_rows(fit, rows):
+    """V(S) (P, P) of the design with conditioning rows ``rows``.  Dense: ``_explained`` on R = rows^T rows.  Streamed:
+    ``lowrank_period_moments`` on the rows, the mean shifted by s^2 (C_ii - R_ii) / 2 in the same way -- no (M, M) buffer."""
+    if not fit.streamed:
+        return _explained(fit, _explained_cov(fit, rows))
+    if rows.shape[0] == 0:
+        return np.zeros((fit.P, fit.P))
+    shifted = (fit.mapped.double() + 0.5 * fit.s2 * (fit.diag - (rows * rows).sum(dim=0))).contiguous()
+    _mean, V = fit.model._plan.lowrank_period_moments(rows.contiguous(), fit.m, shifted, fit.s2, fit.w, fit.groups, fit.P, fit.mode)
+    return V.cpu().numpy()
+
+
+def _gain(fit, rows):
+    """(gain, var) of one more sample after ``rows`` (None: none): ``sample_value`` on the dense covariance, or the streamed
+    ``posterior_sample_value``."""
+    if fit.streamed:
+        return fit.gain(rows)
+    return fit.model._plan.sample_value(fit.cov, fit.m, fit.a, fit.s2, fit.groups, fit.P, obs_var=fit.obs_var, rows=rows, nterms=fit.nterms)
+
+
 def _se(var):
     return np.sqrt(np.clip(var, 0.0, None))
 
 
-def sample_value(model, covariates, weights, freq="YE", sample_var=None, given=None, ci=0.95, max_bytes: int = DEFAULT_MAX_BYTES):
+def sample_value(model, covariates, weights, freq="YE", sample_var=None, given=None, ci=0.95, max_bytes: int = DEFAULT_MAX_BYTES,
+                 streamed=False):
     """``MarginalHIP.sample_value``: for every day of ``covariates`` the expected reduction of the variance of every period
     sum sum_{i in period} weights_i target_i, had that day been sampled -- one ``posterior_cov`` and one
     ``dgp_sample_value``.  "Expected": the hyperparameters stay fixed, and the expectation is over the not-yet-seen value
@@ -171,17 +233,21 @@ def sample_value(model, covariates, weights, freq="YE", sample_var=None, given=N
     ``lower`` / ``upper`` of the current sums as ``aggregate`` gives them, ``se_given`` (the exact expected standard error
     after the ``given`` samples; = ``se_now`` without them), ``se_expected`` = sqrt max(Var - explained(given) - gain, 0)
     (period, time), ``score`` (time) = sum_p gain / Var_p and ``n_points``.  A record whose dense footprint exceeds
-    ``max_bytes`` raises ``ValueError``."""
-    fit = _prepare(model, covariates, weights, freq, sample_var, max_bytes, extra_buffers=0 if given is None else 1)
+    ``max_bytes`` raises ``ValueError``.
+
+    ``streamed=True`` (never chosen automatically) is the path for such LONG RECORDS: the covariance is produced in row
+    panels and never stored -- ``predict``, ``posterior_period_moments`` and one ``posterior_sample_value`` whose work area,
+    and with it the panel height, ``max_bytes`` bounds (``ValueError`` naming the bytes when a 128-row panel does not fit);
+    ``given`` costs ``posterior_cov_columns`` and ``lowrank_period_moments``, no (M, M) buffer."""
+    fit = _prepare(model, covariates, weights, freq, sample_var, max_bytes, extra_buffers=0 if given is None else 1, streamed=streamed)
     picks = _day_indices(fit, given, "given")
     if len(picks) > MAX_ROWS:
         raise ValueError(f"at most {MAX_ROWS} given samples")
     var_now = np.clip(np.diagonal(fit.cov_now), 0.0, None)
     with torch.no_grad():
         rows = conditioning_rows(fit, picks) if len(picks) else None
-        explained = np.diagonal(_explained(fit, _explained_cov(fit, rows))) if len(picks) else np.zeros(fit.P)
-        gain_d, _var = model._plan.sample_value(fit.cov, fit.m, fit.a, fit.s2, fit.groups, fit.P, obs_var=fit.obs_var,
-                                                rows=rows, nterms=fit.nterms)
+        explained = np.diagonal(_explained_rows(fit, rows)) if len(picks) else np.zeros(fit.P)
+        gain_d, _var = _gain(fit, rows)
     gain = gain_d.cpu().numpy()
     with np.errstate(divide="ignore", invalid="ignore"):
         score = np.where(var_now[:, None] > 0, gain / var_now[:, None], 0.0).sum(axis=0)
@@ -221,18 +287,22 @@ def _value_dataset(fit, V, extra=None):
 
 
 def design_value(model, covariates, weights, samples, freq="YE", sample_var=None, return_cov=False,
-                 max_bytes: int = DEFAULT_MAX_BYTES):
+                 max_bytes: int = DEFAULT_MAX_BYTES, streamed=False):
     """``MarginalHIP.design_value``: the EXACT value V(S) of a given sampling design ``samples`` (dates or indices into
     ``covariates``; a day may repeat: replicate samples): how much of each period sum's variance the samples are expected
     to explain, at fixed hyperparameters, the expectation taken over the not-yet-seen sample values.  The conditioning rows
     are built on the device, R = B^T B goes into a second (M, M) buffer and ``dgp_period_moments`` runs on it.
     -> Dataset on ``time`` (period labels) with ``variance_explained`` = V_pp, ``se_now``, ``se_expected`` =
     sqrt max(Var - V_pp, 0), ``fraction`` = V_pp / Var and ``n_points``; with ``return_cov`` also the (P, P) matrix V.  The
-    two (M, M) buffers must fit ``max_bytes``, else ``ValueError``."""
-    fit = _prepare(model, covariates, weights, freq, sample_var, max_bytes, extra_buffers=1)
+    two (M, M) buffers must fit ``max_bytes``, else ``ValueError`` -- unless ``streamed=True`` (long records; see
+    ``sample_value``): the rows come from ``posterior_cov_columns``, V(S) from ``lowrank_period_moments`` on them (at most 64
+    samples), and no (M, M) buffer exists."""
+    fit = _prepare(model, covariates, weights, freq, sample_var, max_bytes, extra_buffers=1, streamed=streamed)
     picks = _day_indices(fit, samples, "samples")
+    if streamed and len(picks) > MAX_ROWS:
+        raise ValueError(f"at most {MAX_ROWS} samples with streamed=True")
     with torch.no_grad():
-        V = _explained(fit, _explained_cov(fit, conditioning_rows(fit, picks)))
+        V = _explained_rows(fit, conditioning_rows(fit, picks))
     ds = _value_dataset(fit, V, {"n_samples": len(picks)})
     return (ds, V) if return_cov else ds
 
@@ -255,7 +325,7 @@ def _objective_weights(fit, objective):
 
 
 def design(model, covariates, weights, k, objective="relative", candidates=None, replicates=False, given=None, freq="YE",
-           sample_var=None, max_bytes: int = DEFAULT_MAX_BYTES):
+           sample_var=None, max_bytes: int = DEFAULT_MAX_BYTES, streamed=False):
     """``MarginalHIP.design``: GREEDY choice of ``k`` days to sample.  Each step runs ``dgp_sample_value`` with the rows of
     the samples so far, scores every day by sum_p omega_p gain[p, c] -- omega_p = 1 / Var_p (``objective="relative"``), 1
     (``"absolute"``) or one period's label alone --, masks the days outside ``candidates`` (a boolean mask, dates or
@@ -269,9 +339,11 @@ def design(model, covariates, weights, k, objective="relative", candidates=None,
     means: hyperparameters held fixed, the expectation taken over the not-yet-seen sample values.
     -> Dataset on (``pick``, ``period``): ``time`` and ``index`` (into ``covariates``) of each pick, its ``score``,
     ``variance_explained`` and ``se_expected`` (pick, period) of the design ``given`` + picks[: j + 1], ``se_now`` (period).
-    ``given`` plus ``k`` may not exceed 64 samples; ``k`` larger than the number of candidates raises ``ValueError``."""
+    ``given`` plus ``k`` may not exceed 64 samples; ``k`` larger than the number of candidates raises ``ValueError``.
+    ``streamed=True``: the long-record path of ``sample_value`` -- one ``posterior_sample_value`` per step, each pick's column
+    from ``posterior_cov_columns``, every prefix's value from ``lowrank_period_moments``; no (M, M) buffer."""
     k = int(k)
-    fit = _prepare(model, covariates, weights, freq, sample_var, max_bytes, extra_buffers=1)
+    fit = _prepare(model, covariates, weights, freq, sample_var, max_bytes, extra_buffers=1, streamed=streamed)
     taken = _day_indices(fit, given, "given")
     if k < 1 or len(taken) + k > MAX_ROWS:
         raise ValueError(f"k must be at least 1 and given + k at most {MAX_ROWS} samples")
@@ -289,17 +361,17 @@ def design(model, covariates, weights, k, objective="relative", candidates=None,
         allowed[taken] = False
     if (k > int(allowed.sum())) if not replicates else not allowed.any():
         raise ValueError(f"k = {k} exceeds the {int(allowed.sum())} candidate days")
-    omega = torch.as_tensor(_objective_weights(fit, objective), dtype=torch.float64, device=fit.cov.device)
-    allowed_t = torch.as_tensor(allowed, device=fit.cov.device)
+    omega = torch.as_tensor(_objective_weights(fit, objective), dtype=torch.float64, device=fit.dev)
+    allowed_t = torch.as_tensor(allowed, device=fit.dev)
     picks, scores, values = [], [], []
     with torch.no_grad():
-        rows = torch.zeros(len(taken) + k, fit.m, dtype=torch.float64, device=fit.cov.device)
+        rows = torch.zeros(len(taken) + k, fit.m, dtype=torch.float64, device=fit.dev)
         rows[: len(taken)] = conditioning_rows(fit, taken)
         n = len(taken)
-        R = _explained_cov(fit, rows[:n])  # kept up to date by rank-one updates: one (M, M) buffer for every prefix
+        # dense: R kept up to date by rank-one updates, one (M, M) buffer for every prefix; streamed: the rows themselves
+        R = None if streamed else _explained_cov(fit, rows[:n])
         for _step in range(k):
-            gain, var = model._plan.sample_value(fit.cov, fit.m, fit.a, fit.s2, fit.groups, fit.P, obs_var=fit.obs_var,
-                                                 rows=rows[:n] if n else None, nterms=fit.nterms)
+            gain, var = _gain(fit, rows[:n] if n else None)
             score = torch.where(allowed_t, omega @ gain, torch.full_like(var, -float("inf")))
             if bool(torch.isnan(score).any()):
                 day = int(torch.nonzero(torch.isnan(score))[0])
@@ -307,13 +379,14 @@ def design(model, covariates, weights, k, objective="relative", candidates=None,
                                  "the posterior covariance or the weights hold a NaN")
             c = int(torch.nonzero(score == score.max())[0])  # ties: the lowest index
             rows[n] = _next_row(fit, rows[:n], c, var=var[c])
-            R[: fit.m, : fit.m].addr_(rows[n], rows[n])
+            if not streamed:
+                R[: fit.m, : fit.m].addr_(rows[n], rows[n])
             n += 1
             picks.append(c)
             scores.append(float(score[c]))
             if not replicates:
                 allowed_t[c] = False
-            values.append(np.diagonal(_explained(fit, R)).copy())
+            values.append(np.diagonal(_explained_rows(fit, rows[:n]) if streamed else _explained(fit, R)).copy())
     picks = np.asarray(picks, dtype=np.int64)
     var_now = np.clip(np.diagonal(fit.cov_now), 0.0, None)
     ve = np.stack(values)

@@ -979,22 +979,24 @@ class MarginalHIP(BaseModel):
                             return_cov=return_cov, max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes)
 
     @is_fitted
-    def sample_value(self, covariates, weights, freq="YE", sample_var=None, given=None, ci=0.95, max_bytes=None):
+    def sample_value(self, covariates, weights, freq="YE", sample_var=None, given=None, ci=0.95, max_bytes=None, streamed=False):
         """For every day of ``covariates``: by how much one more sample on that day is expected to reduce the variance of
         each period sum sum_{i in period} weights_i target_i (hyperparameters held fixed, the expectation over the
         not-yet-seen sample value) -- one posterior covariance and one ``dgp_sample_value`` pass, where the reference would
         refit on simulated data.  ``sample_var``: the sample's model-space noise variance (default: the likelihood's
         learned noise); ``given``: dates or indices of samples to condition on first.  -> Dataset on (``period``, ``time``)
-        with ``variance_reduction``, ``se_now``, ``se_expected`` and a per-day ``score``.  See
+        with ``variance_reduction``, ``se_now``, ``se_expected`` and a per-day ``score``.  ``streamed=True``: the path for
+        records whose dense covariance exceeds ``max_bytes`` (row panels, never the whole matrix).  See
         ``discontinuum_amd.design.sample_value``."""
         from ..design import sample_value
         from ..loads import DEFAULT_MAX_BYTES
 
         return sample_value(self, covariates, weights, freq=freq, sample_var=sample_var, given=given, ci=ci,
-                            max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes)
+                            max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes, streamed=streamed)
 
     @is_fitted
-    def design_value(self, covariates, weights, samples, freq="YE", sample_var=None, return_cov=False, max_bytes=None):
+    def design_value(self, covariates, weights, samples, freq="YE", sample_var=None, return_cov=False, max_bytes=None,
+                     streamed=False):
         """The exact expected value of a sampling design: per period the variance of the period sum that samples on the days
         ``samples`` (dates or indices) explain, with ``se_now``, ``se_expected`` and the explained ``fraction``; with
         ``return_cov`` also the (P, P) matrix.  See ``discontinuum_amd.design.design_value``."""
@@ -1002,11 +1004,11 @@ class MarginalHIP(BaseModel):
         from ..loads import DEFAULT_MAX_BYTES
 
         return design_value(self, covariates, weights, samples, freq=freq, sample_var=sample_var, return_cov=return_cov,
-                            max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes)
+                            max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes, streamed=streamed)
 
     @is_fitted
     def design(self, covariates, weights, k, objective="relative", candidates=None, replicates=False, given=None, freq="YE",
-               sample_var=None, max_bytes=None):
+               sample_var=None, max_bytes=None, streamed=False):
         """Greedy choice of ``k`` days to sample for the period sums' uncertainty: exact for linear targets and for the
         first pick of log targets, a plug-in approximation of the marginal gain after that; the reported value of every
         nested prefix of the chosen design is exact.  -> Dataset along ``pick``.  See ``discontinuum_amd.design.design``."""
@@ -1014,7 +1016,8 @@ class MarginalHIP(BaseModel):
         from ..loads import DEFAULT_MAX_BYTES
 
         return design(self, covariates, weights, k, objective=objective, candidates=candidates, replicates=replicates,
-                      given=given, freq=freq, sample_var=sample_var, max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes)
+                      given=given, freq=freq, sample_var=sample_var, max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes,
+                      streamed=streamed)
 
     @is_fitted
     def influence(self, covariates, weights, folds="loo", freq="YE", max_bytes=None):

@@ -171,11 +171,11 @@ class LoadestGPMarginalHIP(LoadestDataMixin, MarginalHIP):
         return flux_weights(daily, _target_attrs(self.dm))
 
     @is_fitted
-    def sample_value(self, daily, freq="YE", sample_var=None, given=None, ci=0.95, max_bytes=None):
+    def sample_value(self, daily, freq="YE", sample_var=None, given=None, ci=0.95, max_bytes=None, streamed=False):
         """By how much one more concentration sample on each day of ``daily`` is expected to reduce the variance of each
         period's LOAD (kg; the flux weights of ``annual_flux``): ``MarginalHIP.sample_value``."""
         return super().sample_value(daily, self._flux_weights(daily), freq=freq, sample_var=sample_var, given=given, ci=ci,
-                                    max_bytes=max_bytes)
+                                    max_bytes=max_bytes, streamed=streamed)
 
     @is_fitted
     def sample_influence(self, daily, folds="loo", freq="YE", max_bytes=None):
@@ -186,17 +186,18 @@ class LoadestGPMarginalHIP(LoadestDataMixin, MarginalHIP):
         return super().influence(daily, self._flux_weights(daily), folds=folds, freq=freq, max_bytes=max_bytes)
 
     @is_fitted
-    def design_value(self, daily, samples, freq="YE", sample_var=None, return_cov=False, max_bytes=None):
+    def design_value(self, daily, samples, freq="YE", sample_var=None, return_cov=False, max_bytes=None, streamed=False):
         """The exact expected value of sampling the days ``samples`` for the period loads (kg): ``MarginalHIP.design_value``."""
         return super().design_value(daily, self._flux_weights(daily), samples, freq=freq, sample_var=sample_var,
-                                    return_cov=return_cov, max_bytes=max_bytes)
+                                    return_cov=return_cov, max_bytes=max_bytes, streamed=streamed)
 
     @is_fitted
     def design(self, daily, k, objective="relative", candidates=None, replicates=False, given=None, freq="YE", sample_var=None,
-               max_bytes=None):
+               max_bytes=None, streamed=False):
         """Greedy choice of ``k`` sampling days for the period loads (kg): ``MarginalHIP.design``."""
         return super().design(daily, self._flux_weights(daily), k, objective=objective, candidates=candidates,
-                              replicates=replicates, given=given, freq=freq, sample_var=sample_var, max_bytes=max_bytes)
+                              replicates=replicates, given=given, freq=freq, sample_var=sample_var, max_bytes=max_bytes,
+                              streamed=streamed)
 
     @is_fitted
     def flux_bias(self, cv=None, folds="loo", laplace=None):

@@ -3,7 +3,8 @@
 move a number: seeded inputs, one fit, and the outputs of ``fit_step``, ``factorize``, ``predict``, ``predict_mean``,
 ``mean_vjp``, ``predict_terms`` / ``predict_slopes`` (with and without ``return_cov``), ``posterior_cov``,
 ``posterior_period_moments``, ``period_moments``, ``period_third_moments`` (tile 0, 64, 128), ``exceedance_moments``,
-``posterior_exceedance_moments``, ``sample_value``, ``window_moments``, ``whiten`` and ``cross_validate``; for one site and the
+``posterior_exceedance_moments``, ``sample_value``, ``posterior_sample_value``, ``posterior_cov_columns``,
+``lowrank_period_moments``, ``window_moments``, ``whiten`` and ``cross_validate``; for one site and the
 ragged batch of three, ``fisher``, ``predict_sensitivity`` (also means only in chunks), ``deletion_influence``, ``loo_fit_step`` /
 ``loo_value``, ``bilinear``, ``laplace_factorize``, ``laplace_fit_step`` (with and without an interval row),
 ``laplace_cross_validate``, ``ep_fit_step`` cold and warm, ``ep_factorize``, ``ep_diag`` and the pointwise ``censored_terms`` /
@@ -104,6 +105,10 @@ def run_config(torch, GPPlan, backend, make_case, model, d, dtype, sizes, dev):
     keep("posterior_period_moments_log", plan.posterior_period_moments(theta, Xs, mu, scale2, w, groups, GROUPS, backend.MODE_LOG))
     keep("posterior_period_moments_linear",
          plan.posterior_period_moments(theta, Xs, mu, scale2, w, groups, GROUPS, backend.MODE_LINEAR, extra_var=extra))
+    keep("posterior_sample_value",  # two panels of 128 rows
+         plan.posterior_sample_value(theta, Xs, w, scale2, groups, GROUPS, obs_var=extra, rows=given, nterms=12, panel_rows=128))
+    keep("posterior_cov_columns", plan.posterior_cov_columns(theta, Xs, torch.tensor([0, 127, 128, m - 1]).expand(lead + (4,))))
+    keep("lowrank_period_moments", plan.lowrank_period_moments(given.to(dev), m, mu.double(), scale2, w, groups, GROUPS, backend.MODE_LOG))
     keep("cross_validate", plan.cross_validate(folds))
     if B <= 3:  # the products whose host glue lives beside their kernels: one site and the ragged batch of three
         extra_products(torch, plan, backend, keep, theta, X, r, noise, Xs, w, folds, groups, extra, dtype, dev)
