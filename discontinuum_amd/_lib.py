@@ -173,6 +173,12 @@ EXT2_SIGNATURES = {
     "dgp_posterior_cov_columns_workspace_bytes": (_sz, [_vp, _i64, _i]),
     "dgp_posterior_cov_columns": (_i, [_vp, _dp, _vp, _i64, _vp, _i, _vp, _sz, _vp, _vp]),
     "dgp_lowrank_period_moments": (_i, [_i, _vp, _i, _i64, _i, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp, _vp, _vp]),
+    "dgp_posterior_cov_block_workspace_bytes": (_sz, [_vp, _i64, _i64, _i64, _i64]),
+    "dgp_posterior_cov_block": (_i, [_vp, _dp, _vp, _i64, _i64, _i64, _i64, _vp, _sz, _vp, _vp]),
+    "dgp_window_variances_workspace_bytes": (_sz, [_i64, _i64, _i]),
+    "dgp_window_variances": (_i, [_i, _i, _vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _sz, _vp, _vp, _vp]),
+    "dgp_posterior_window_variances_workspace_bytes": (_sz, [_vp, _i64, _i64, _i64, _i]),
+    "dgp_posterior_window_variances": (_i, [_vp, _dp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i64, _i, _vp, _sz, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -749,6 +749,10 @@ class GPPlan:
         """The module-level ``window_moments``."""
         return window_moments(cov, m, mu, lo, hi, a=a, mode=mode, scale2=scale2)
 
+    def window_variances(self, cov, m: int, mu, lo, hi, a=None, mode: int = 0, scale2=None):
+        """The module-level ``window_variances``."""
+        return window_variances(cov, m, mu, lo, hi, a=a, mode=mode, scale2=scale2)
+
     def sample_value(self, cov, m: int, a, scale2, groups, ngroups: int, obs_var=None, rows=None, nterms=None):
         """The module-level ``sample_value``."""
         return sample_value(cov, m, a, scale2, groups, ngroups, obs_var=obs_var, rows=rows, nterms=nterms)
@@ -939,6 +943,83 @@ class GPPlan:
             cols = self._empty(ncols, m, dtype=torch.float64)
             self._call("dgp_posterior_cov_columns", th, _ptr(xs), m, _ptr(i32), ncols, work, need, _ptr(cols))
         return cols
+
+    def posterior_cov_block(self, theta, Xs: torch.Tensor, row0: int, row1: int, col0: int):
+        """Rows [row0, row1) x columns [col0, row1) of the latent posterior covariance at Xs (``dgp_posterior_cov_block``) as a
+        (row1 - row0, row1 - col0) tensor in the plan's dtype -- with a leading batch dimension for a batched plan --, from the
+        held factorisation: a block of the covariance of a record too long to hold whole.  ``row0``, ``row1``, ``col0``:
+        multiples of 128 with 0 <= col0 <= row0 < row1 <= M (M = padded m).  Entry [r, c] is C[row0 + r, col0 + c] with the bits
+        ``posterior_cov`` gives it (float64); 128 x 128 tiles above the diagonal are not written (they hold zeros here), and
+        inside a diagonal tile the entries on and below the diagonal are valid."""
+        m, th = self._check_xs(Xs), self._theta(theta)
+        row0, row1, col0 = int(row0), int(row1), int(col0)
+        need = int(self.lib.dgp_posterior_cov_block_workspace_bytes(self._h, m, row0, row1, col0))
+        if need == 0:
+            raise ValueError(f"bad block: rows [{row0}, {row1}), first column {col0} for m = {m} (multiples of 128 with "
+                             "0 <= col0 <= row0 < row1 <= padded m, 1 <= m <= 2^20)")
+        with torch.cuda.device(self.device):
+            xs = Xs.contiguous()
+            work = self._work_area("_pcb_ws", need, "dgp_posterior_cov_block", check_free=True)
+            out = torch.zeros(self._lead + (row1 - row0, row1 - col0), dtype=self.dtype, device=self.device)
+            self._call("dgp_posterior_cov_block", th, _ptr(xs), m, row0, row1, col0, work, need, _ptr(out))
+        return out
+
+    def posterior_window_variances(self, theta, Xs: torch.Tensor, mu, lo, hi, a=None, mode: int = 0, scale2=None, panel_rows=None,
+                                   max_bytes=None):
+        """``window_variances`` of the posterior at Xs straight from the held factorisation
+        (``dgp_posterior_window_variances``): only a band of the covariance is produced, ``panel_rows`` rows at a time -- the
+        panel of rows [p0, p1) holds the columns from 128 floor(max(0, p0 - reach + 1) / 128) on, ``reach`` = the largest point
+        count of a window, computed here from ``lo`` / ``hi`` -- and the (M, M) matrix is never formed.  Xs (m, d) --
+        (batch, m, d) for a batched plan, theta (batch, ntheta) --; ``mu`` (the plan's dtype; MODE_LOG: the MAPPED mean), ``lo``,
+        ``hi``, ``a``, ``mode``, ``scale2`` and the results (mean, var) as for ``window_variances``.  C_jj is the predicted
+        variance, never a panel's diagonal.  ``panel_rows``: a positive multiple of 128, or None: ``window_panel_rows`` of
+        ``max_bytes`` -- the largest panel, at most M rows, whose work area fits; a ``ValueError`` names the bytes when 128 rows
+        do not.  The work area (2 N M + R (R + round_up(reach, 128)) plan-dtype elements and 3 M + 3 Q doubles per site) is kept
+        between calls; a ``RuntimeError`` names its bytes when it exceeds the free device memory."""
+        lead, m, th = self._lead, self._check_xs(Xs), self._theta(theta)
+        lo_h, hi_h, q = _window_bounds(lo, hi, lead, m)
+        _window_mode(mode, scale2)
+        reach = max(1, int((hi_h - lo_h).max()))
+        dev = self.device
+        with torch.cuda.device(dev):
+            mu_t, a_t, _g, _ev, s2 = _moment_inputs(dev, self.dtype, lead, m, mu, a, None, None, scale2 if mode == MODE_LOG else None)
+            R = self.window_panel_rows(m, q, reach, max_bytes) if panel_rows is None else int(panel_rows)
+            if R <= 0 or R % 128:
+                raise ValueError(f"panel_rows must be a positive multiple of 128, not {panel_rows}")
+            need = int(self.lib.dgp_posterior_window_variances_workspace_bytes(self._h, m, q, reach, R))
+            if need == 0:
+                raise ValueError(f"bad size: m = {m}, q = {q} (1 <= m, q <= 2^20)")
+            work = self._work_area("_pwv_ws", need, "dgp_posterior_window_variances", check_free=True)
+            xs = Xs.contiguous()
+            lo_t, hi_t = lo_h.to(dev), hi_h.to(dev)
+            mean_out, var_out = self._empty(q, dtype=torch.float64), self._empty(q, dtype=torch.float64)
+            self._call("dgp_posterior_window_variances", th, _ptr(xs), m, _ptr(mu_t), _ptr(s2), _ptr(a_t), _ptr(lo_t), _ptr(hi_t), q,
+                       int(mode), reach, R, work, need, _ptr(mean_out), _ptr(var_out))
+        return mean_out, var_out
+
+    def window_panel_rows(self, m: int, q: int, reach: int, max_bytes=None) -> int:
+        """The panel height ``posterior_window_variances`` picks for m points, q windows of at most ``reach`` points under
+        ``max_bytes`` (default ``loads.DEFAULT_MAX_BYTES``).  The band of R x (R + round_up(reach, 128)) elements grows
+        quadratically in R, so ``stream_panel_rows``' linear rule does not apply: a bisection on the sizes
+        ``dgp_posterior_window_variances_workspace_bytes`` reports for the largest multiple of 128, at most the padded record
+        length M, whose work area fits.  ``ValueError`` naming the bytes when 128 rows do not fit."""
+        if max_bytes is None:
+            from .loads import DEFAULT_MAX_BYTES as max_bytes
+        size = lambda R: int(self.lib.dgp_posterior_window_variances_workspace_bytes(self._h, int(m), int(q), int(reach), R))  # noqa: E731
+        need128 = size(128)
+        if need128 == 0:
+            raise ValueError(f"bad size: m = {m}, q = {q}, reach = {reach} (1 <= m, q, reach <= 2^20)")
+        if need128 > max_bytes:
+            raise ValueError(f"the streamed rolling-mean pass needs a work area of {need128} bytes with the smallest panel (128 "
+                             f"rows), which exceeds max_bytes = {max_bytes}")
+        good, bad = 1, int(self.lib.dgp_padded_n(int(m))) // 128 + 1  # in blocks of 128 rows: size(good) fits, size(bad) does not
+        while bad - good > 1:
+            mid = (good + bad) // 2
+            if size(128 * mid) <= max_bytes:
+                good = mid
+            else:
+                bad = mid
+        return 128 * good
 
     def lowrank_period_moments(self, rows, m: int, mu, scale2, w, groups, ngroups: int, mode: int):
         """The module-level ``lowrank_period_moments``."""
@@ -1272,6 +1353,36 @@ def window_moments(cov: torch.Tensor, m: int, mu: torch.Tensor, lo, hi, a=None, 
         _call("dgp_window_moments", _DTYPES[cov.dtype], int(mode), _ptr(cov), m, B, _ptr(mu_t), _ptr(s2), _ptr(a_t), _ptr(lo_t),
               _ptr(hi_t), q, _ptr(work), need, _ptr(mean_out), _ptr(cov_out))
     return mean_out, cov_out
+
+
+def _window_mode(mode, scale2):
+    if mode not in (MODE_LINEAR, MODE_LOG):
+        raise ValueError(f"mode must be MODE_LINEAR or MODE_LOG, not {mode!r}")
+    if mode == MODE_LOG and scale2 is None:
+        raise ValueError("MODE_LOG needs scale2 = s^2")
+
+
+def window_variances(cov: torch.Tensor, m: int, mu: torch.Tensor, lo, hi, a=None, mode: int = MODE_LINEAR, scale2=None):
+    """The means of ``window_moments`` and the DIAGONAL of its covariance -- the variance of every rolling-window mean --
+    through one ``dgp_window_variances`` call: the same arguments and rules, a work area of 3 M + 3 Q doubles per site instead
+    of M Q, and no (Q, Q) result.  Entries of ``cov`` on and below the diagonal are read, the diagonal included.
+    -> (mean (q,), var (q,)) or ((B, q), (B, q)), float64 device tensors."""
+    m = int(m)
+    lo_h, hi_h, q = _window_bounds(lo, hi, tuple(cov.shape[:-2]), m)  # the windows are checked before the covariance
+    _window_mode(mode, scale2)
+    lib, lead, B, dev = _cov_layout(cov, m)
+    with torch.cuda.device(dev):
+        mu_t, a_t, _g, _ev, s2 = _moment_inputs(dev, cov.dtype, lead, m, mu, a, None, None, scale2 if mode == MODE_LOG else None)
+        need = int(lib.dgp_window_variances_workspace_bytes(m, q, B))
+        if need == 0:
+            raise ValueError(f"bad size: m = {m}, q = {q}, batch = {B} (1 <= m, q <= 2^20, 1 <= batch <= 1024)")
+        lo_t, hi_t = lo_h.to(dev), hi_h.to(dev)
+        work = torch.empty(need, dtype=torch.uint8, device=dev)
+        mean_out = torch.empty(lead + (q,), dtype=torch.float64, device=dev)
+        var_out = torch.empty(lead + (q,), dtype=torch.float64, device=dev)
+        _call("dgp_window_variances", _DTYPES[cov.dtype], int(mode), _ptr(cov), m, B, _ptr(mu_t), _ptr(s2), _ptr(a_t), _ptr(lo_t),
+              _ptr(hi_t), q, _ptr(work), need, _ptr(mean_out), _ptr(var_out))
+    return mean_out, var_out
 
 
 MAX_SERIES_TERMS = 64  # the largest ``nterms`` of ``dgp_sample_value``

@@ -1729,6 +1729,35 @@ int posterior_cov_panel(const T* V, long N, long M, T* panel, long row0, long ro
   return (int)hipGetLastError();
 }
 
+// A rectangular block of the same update: tile (bi0 + blockIdx.y, bj0 + blockIdx.x) of the triangle -- a tile above the diagonal
+// returns at once -- into a band buffer whose first element is cov[bi0 NB][bj0 NB] (leading dimension ld, site stride cs).
+// posterior_cov_kernel's tile core, k range and begin / end, so an entry has the value it has there.
+template <typename T>
+__global__ __launch_bounds__(256, (TileCore<T, false, false>::OCC)) void posterior_cov_band_kernel(const T* __restrict__ V, long N, long M, T* __restrict__ band,
+                                                                                                  long wbs, long cs, int bi0, int bj0, long ld) {
+  using K = TileCore<T, false, false>;
+  using G = typename K::G;
+  __shared__ T smem[K::SMEM_ELEMS];
+  const int bi = bi0 + (int)blockIdx.y, bj = bj0 + (int)blockIdx.x;
+  if (bj > bi) return;
+  V = site(V, wbs);
+  band = site(band, cs);
+  typename G::acc_t acc[G::MI][G::NI];
+  T* C = band + (long)(bi - bi0) * NB * ld + (long)(bj - bj0) * NB;
+  typename G::acc_t keep[G::MI][G::NI];
+  trailing_begin<T, G, K::DMA>(acc, keep, C, ld);
+  K::run(V + (long)bi * NB, M, V + (long)bj * NB, M, (int)(N / 16), smem, acc);
+  trailing_end<T, G, K::DMA>(acc, keep, C, ld);
+}
+
+template <typename T>
+int posterior_cov_band(const T* V, long N, long M, T* band, long row0, long row1, long col0, long ld, long band_stride, hipStream_t s,
+                       int B, long wbs) {
+  const dim3 grid((unsigned)((row1 - col0) / NB), (unsigned)((row1 - row0) / NB), (unsigned)B);
+  posterior_cov_band_kernel<T><<<grid, 256, 0, s>>>(V, N, M, band, wbs, band_stride, (int)(row0 / NB), (int)(col0 / NB), ld);
+  return (int)hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------
 // Draws from N(mean, L L^T) for sample() (src/discontinuum/engines/gpytorch.py:575-580, `f_preds.sample`):
 //     out[q][j] = mean[j] + sum_{k <= j} L[j][k] Z[k][q]
@@ -1762,6 +1791,7 @@ int sample_draws(const T* L, long M, const T* Z, long Q, const T* mean, int m, i
 #define DGP_INST(T)                                                                                              \
   template int posterior_cov<T>(const T*, long, long, T*, hipStream_t, int, long);                                          \
   template int posterior_cov_panel<T>(const T*, long, long, T*, long, long, long, hipStream_t, int, long);                                          \
+  template int posterior_cov_band<T>(const T*, long, long, T*, long, long, long, long, long, hipStream_t, int, long);                             \
   template int sample_draws<T>(const T*, long, const T*, long, const T*, int, int, T*, hipStream_t);             \
   template int symv_lower<T>(const T*, long, const T*, int, const T*, T*, T*, T*, hipStream_t, Batch, long);     \
   template int potrf<T>(T*, long, T*, T*, int*, int, hipStream_t, hipStream_t, hipEvent_t*, PotrfObservers*, Batch, int);               \

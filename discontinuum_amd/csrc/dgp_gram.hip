@@ -176,6 +176,59 @@ __global__ __launch_bounds__(256) void gram_sym_kernel(const T* __restrict__ Xt,
   }
 }
 
+// BAND: the 64 x 64 tiles of the block rows [row0, ..) x columns [col0, ..) of the same triangle (blockIdx.y / blockIdx.x count
+// tiles from tile row bi0 / tile column bj0; a tile above the diagonal returns at once) into a buffer whose first element is
+// K[row0][col0], leading dimension ld.  gram_sym_kernel's evaluation, selects and stores, entry by entry.
+template <typename T, typename M>
+__global__ __launch_bounds__(256) void gram_sym_band_kernel(const T* __restrict__ Xt, long N, int n, const PreBatch<M> pb,
+                                                            const T* __restrict__ noise, T* __restrict__ K, long bs,
+                                                            const int* __restrict__ ns, long ks, long noise_stride, int bi0, int bj0,
+                                                            long ld) {
+  const int bi = bi0 + (int)blockIdx.y, bj = bj0 + (int)blockIdx.x;
+  if (bj > bi) return;
+  const typename M::Pre& pre = pb.get();
+  Xt = site(Xt, bs);
+  K = site(K, ks);
+  noise = site(noise, noise_stride);
+  n = site_n(ns, n);
+  __shared__ T sfi[M::NF][64], sfj[M::NF][64];
+  const int t = threadIdx.x;
+  exp_table_init<T>();
+  if (t < 64) stage_strip<T, M>(Xt, N, (long)bi * 64, pre, sfi, t);
+  else if (t < 128) stage_strip<T, M>(Xt, N, (long)bj * 64, pre, sfj, t - 64);
+  __syncthreads();
+  const int ty = t >> 4, tx = t & 15;
+  T fj[4][M::NF];
+#pragma unroll
+  for (int b = 0; b < 4; ++b)
+#pragma unroll
+    for (int c = 0; c < M::NF; ++c) fj[b][c] = sfj[c][tx * 4 + b];
+  T dummy[M::NTHETA];
+  const bool interior = bi != bj && (long)bi * 64 + 64 <= n;
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    const long gi = (long)bi * 64 + ty * 4 + a;
+    T fi[M::NF];
+#pragma unroll
+    for (int c = 0; c < M::NF; ++c) fi[c] = sfi[c][ty * 4 + a];
+    T out[4];
+    if (interior) {
+#pragma unroll
+      for (int b = 0; b < 4; ++b) out[b] = M::template pair<false>(fi, fj[b], pre, T(0), dummy);
+    } else {
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const long gj = (long)bj * 64 + tx * 4 + b;
+        T v = M::template pair<false>(fi, fj[b], pre, T(0), dummy);
+        if (gi >= n || gj >= n) v = (gi == gj) ? T(1) : T(0);  // identity pad
+        else if (gi == gj) v += noise[gi];
+        out[b] = v;
+      }
+    }
+    store4<T>(K + (gi - (long)bi0 * 64) * ld + ((long)(bj - bj0) * 64 + tx * 4), out);
+  }
+}
+
 // Batched plans (blockIdx.z = site): the training coordinates sit at the plan's site stride `bs`, the test coordinates
 // and the output in the caller's work area at its own site stride `wbs`; ragged sites have n = ns[site] rows.
 template <typename T, typename M>
@@ -684,6 +737,18 @@ int gram_sym_panel(int model, int d, const T* Xt, long N, int n, const double* t
 }
 
 template <typename T>
+int gram_sym_band(int model, int d, const T* Xt, long N, int n, const double* theta, const T* noise, T* K, long row0, long row1,
+                  long col0, long ld, hipStream_t s, Batch bt, void* pre_scratch, long k_stride, long noise_stride) {
+  const int nt = model_ntheta(model, d);
+  if (nt < 0) return -2;
+  const dim3 grid((unsigned)((row1 - col0) / 64), (unsigned)((row1 - row0) / 64), (unsigned)bt.B);
+  DGP_DISPATCH_MODEL(model, d, (gram_sym_band_kernel<T, M><<<grid, dim3(256), 0, s>>>(
+                                   Xt, N, n, prepare_batch<M>(theta, nt, bt.B, pre_scratch, false, s), noise, K, bt.ws, bt.ns, k_stride,
+                                   noise_stride, (int)(row0 / 64), (int)(col0 / 64), ld)));
+  return (int)hipGetLastError();
+}
+
+template <typename T>
 int gram_cross(int model, int d, const T* Xt, long N, int n, const T* Xst, long Mp, int m, const double* theta,
                T* Ks, hipStream_t s, Batch bt, long wbs, void* pre_scratch, void* pre_staging) {
   const int nt = model_ntheta(model, d);
@@ -811,6 +876,7 @@ template int gram_residual<float>(int, int, const float*, long, int, const doubl
   template int pack_x<T>(const T*, int, int, long, T*, hipStream_t, Batch);                                      \
   template int gram_sym<T>(int, int, const T*, long, int, const double*, const T*, T*, hipStream_t, Batch, void*, void*, long, long, bool); \
   template int gram_sym_panel<T>(int, int, const T*, long, int, const double*, const T*, T*, long, long, hipStream_t, Batch, void*, long, long); \
+  template int gram_sym_band<T>(int, int, const T*, long, int, const double*, const T*, T*, long, long, long, long, hipStream_t, Batch, void*, long, long); \
   template int gram_cross<T>(int, int, const T*, long, int, const T*, long, int, const double*, T*, hipStream_t, Batch, long, void*, void*); \
   template int gram_diag<T>(int, int, const T*, long, int, const double*, T*, hipStream_t, Batch, long, void*);    \
   template int gram_grad<T>(int, int, const T*, long, int, const double*, const T*, const T*, T*, T*, hipStream_t, Batch, \

@@ -78,6 +78,12 @@ int gram_sym(int model, int d, const T* Xt, long N, int n, const double* theta, 
 template <typename T>
 int gram_sym_panel(int model, int d, const T* Xt, long N, int n, const double* theta, const T* noise, T* K, long row0, long row1,
                    hipStream_t s, Batch bt, void* pre_scratch, long k_stride, long noise_stride);
+// The rectangular block rows [row0, row1) x columns [col0, row1) (multiples of 64, col0 <= row0) of the same lower triangle
+// into a band buffer whose first element is K[row0][col0] (leading dimension ld, site stride k_stride): gram_sym's evaluation
+// and values; tiles above the diagonal are not written.  The hyperparameters as for gram_sym_panel.
+template <typename T>
+int gram_sym_band(int model, int d, const T* Xt, long N, int n, const double* theta, const T* noise, T* K, long row0, long row1,
+                  long col0, long ld, hipStream_t s, Batch bt, void* pre_scratch, long k_stride, long noise_stride);
 // The inference launchers take a Batch like the fit-step ones (gridDim.z = sites): training-side arrays at the plan's
 // site stride bt.ws, everything in the caller's work area (test coordinates, cross Gram, partials ...) at `wbs` elements.
 template <typename T>
@@ -234,6 +240,12 @@ int posterior_cov(const T* V, long N, long M, T* cov, hipStream_t s, int B = 1, 
 template <typename T>
 int posterior_cov_panel(const T* V, long N, long M, T* panel, long row0, long row1, long panel_stride, hipStream_t s, int B = 1,
                         long wbs = 0);
+// the block rows [row0, row1) x columns [col0, row1) (multiples of 128, col0 <= row0) of the same update, into a band buffer
+// whose first element is C[row0][col0] (leading dimension ld, site stride band_stride elements): the same tile core, k order
+// and values; tiles above the diagonal are not touched
+template <typename T>
+int posterior_cov_band(const T* V, long N, long M, T* band, long row0, long row1, long col0, long ld, long band_stride,
+                       hipStream_t s, int B = 1, long wbs = 0);
 
 // out (ndraw x m) = mean + (L Z)^T : L is M x M lower (identity pad), Z is M x Q standard normals, Q % 128 == 0
 template <typename T>

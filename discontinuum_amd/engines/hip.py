@@ -961,7 +961,7 @@ class MarginalHIP(BaseModel):
 
     @is_fitted
     def rolling_mean(self, covariates, window, statistic=None, align="right", min_periods=None, ci=0.95, return_cov=False,
-                     max_bytes=None):
+                     max_bytes=None, streamed=False):
         """The rolling mean of the target over ``window`` ("30D", "7D", "96h" or a ``numpy.timedelta64``; membership by time,
         so gaps and irregular records are handled) with its exact uncertainty: what ``sample()`` and a rolling mean of every
         draw estimate by Monte Carlo, in one posterior covariance and one ``dgp_window_moments`` pass.  ``statistic=None`` is
@@ -970,13 +970,15 @@ class MarginalHIP(BaseModel):
         interval approximate).  ``align="right"``: the trailing window (t - window, t]; ``"center"``: [t - window / 2,
         t + window / 2).  ``min_periods=None``: the largest point count any window of the record holds, so that leading
         partial windows and windows over gaps are left out.  -> Dataset on the qualifying outputs' ``time`` with ``mean``,
-        ``se``, ``lower``, ``upper`` and ``n_points``; with ``return_cov`` also the (q, q) covariance.  See
-        ``discontinuum_amd.rolling``."""
+        ``se``, ``lower``, ``upper`` and ``n_points``; with ``return_cov`` also the (q, q) covariance.  ``streamed=True``
+        (never chosen automatically): the same Dataset without the dense covariance, from the band of it the windows reach
+        (``dgp_posterior_window_variances``), for records of any length; ``max_bytes`` bounds its work area and ``return_cov``
+        is refused.  See ``discontinuum_amd.rolling``."""
         from ..loads import DEFAULT_MAX_BYTES
         from ..rolling import rolling_mean
 
         return rolling_mean(self, covariates, window, statistic=statistic, align=align, min_periods=min_periods, ci=ci,
-                            return_cov=return_cov, max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes)
+                            return_cov=return_cov, max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes, streamed=streamed)
 
     @is_fitted
     def sample_value(self, covariates, weights, freq="YE", sample_var=None, given=None, ci=0.95, max_bytes=None, streamed=False):
@@ -1050,16 +1052,18 @@ class MarginalHIP(BaseModel):
 
     @is_fitted
     def exceedance_probability(self, covariates, threshold, above=True, pred_noise=False, window=None, align="right",
-                               min_periods=None, max_bytes=None):
+                               min_periods=None, max_bytes=None, streamed=False):
         """Pointwise probability that the target exceeds ``threshold`` (a data-space number or one value per point) at each
         point of ``covariates``, from the prediction's mean and variance.  -> DataArray on the covariates' coordinate.  See
         ``discontinuum_amd.exceedance.exceedance_probability``.  ``window``: the same for the rolling mean over that window, on the
-        qualifying outputs' ``time``."""
+        qualifying outputs' ``time``; ``streamed=True`` (with ``window``): from the streamed band pass, without the dense
+        covariance."""
         from ..exceedance import exceedance_probability
         from ..loads import DEFAULT_MAX_BYTES
 
         return exceedance_probability(self, covariates, threshold, above=above, pred_noise=pred_noise, window=window, align=align,
-                                      min_periods=min_periods, max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes)
+                                      min_periods=min_periods, max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes,
+                                      streamed=streamed)
 
     @is_fitted
     def excess(self, covariates, threshold=None, threshold_series=None, weights=None, freq="YE", above=True, ci=0.95,

@@ -407,10 +407,12 @@ def duration_curve(model, covariates, levels=None, above=True, ci=0.95, pred_noi
     )
 
 
-def _windowed_exceedance_probability(model, covariates, threshold, above, pred_noise, window, align, min_periods, max_bytes):
+def _windowed_exceedance_probability(model, covariates, threshold, above, pred_noise, window, align, min_periods, max_bytes,
+                                     streamed=False):
     """``exceedance_probability`` of the rolling mean: Phi(((W mu)_i - u_i) / sqrt(S_ii)) from the diagonal of S = W C W^T,
-    on the qualifying outputs' ``time`` coordinate; a per-point threshold is read at the output's own time stamp."""
-    from .rolling import check_window_budget, time_windows
+    on the qualifying outputs' ``time`` coordinate; a per-point threshold is read at the output's own time stamp.
+    ``streamed``: (W mu, diag S) from ``rolling.streamed_window_variances`` instead of the dense pair."""
+    from .rolling import check_window_budget, streamed_window_variances, time_windows
 
     if pred_noise:
         raise ValueError(WINDOW_REFUSALS["pred_noise"])
@@ -425,15 +427,18 @@ def _windowed_exceedance_probability(model, covariates, threshold, above, pred_n
     u = model_space_threshold(model.dm, tau)
     Xnew = torch.tensor(Xall[order], dtype=model.dtype).to(model.device).contiguous()
     m, q = Xnew.shape[0], len(out)
-    check_window_budget(model, m, q, 0, max_bytes, "the exceedance probability of a rolling mean")
-    model._eval_ready(Xnew)
-    with torch.no_grad():
-        kmean, cov = model._plan.posterior_cov(model._factor_theta, Xnew)
-        mu = (kmean + model.model.prior_mean(Xnew)).contiguous()
-        wmean, S = model._plan.window_moments(cov, m, mu, torch.from_numpy(np.ascontiguousarray(lo[out])),
-                                              torch.from_numpy(np.ascontiguousarray(hi[out])))
-        wm = wmean.double().cpu().numpy()
-        var = torch.diagonal(S)[:q].double().cpu().numpy()
+    if streamed:
+        wm, var = streamed_window_variances(model, Xnew, lo[out], hi[out], max_bytes=max_bytes)
+    else:
+        check_window_budget(model, m, q, 0, max_bytes, "the exceedance probability of a rolling mean", streamable=True)
+        model._eval_ready(Xnew)
+        with torch.no_grad():
+            kmean, cov = model._plan.posterior_cov(model._factor_theta, Xnew)
+            mu = (kmean + model.model.prior_mean(Xnew)).contiguous()
+            wmean, S = model._plan.window_moments(cov, m, mu, torch.from_numpy(np.ascontiguousarray(lo[out])),
+                                                  torch.from_numpy(np.ascontiguousarray(hi[out])))
+            wm = wmean.double().cpu().numpy()
+            var = torch.diagonal(S)[:q].double().cpu().numpy()
     with np.errstate(divide="ignore", invalid="ignore"):
         z = np.where(var > 0, (wm - u) / np.sqrt(np.where(var > 0, var, 1.0)), np.where(wm > u, np.inf, -np.inf))
     z = np.where(np.isinf(u), np.where(u < 0, np.inf, -np.inf), z)
@@ -444,14 +449,19 @@ def _windowed_exceedance_probability(model, covariates, threshold, above, pred_n
 
 
 def exceedance_probability(model, covariates, threshold, above=True, pred_noise=False, window=None, align="right",
-                           min_periods=None, max_bytes: int = DEFAULT_MAX_BYTES):
+                           min_periods=None, max_bytes: int = DEFAULT_MAX_BYTES, streamed=False):
     """``MarginalHIP.exceedance_probability``: the pointwise probability Phi((mu_i - u_i) / sigma_i) that the target
     exceeds ``threshold`` (a data-space number, or one value per point) at each point of ``covariates`` -- host-side, from
     the plan's existing prediction.  A point with zero variance gives 1 or 0 (a tie counts as not exceeded).
     -> DataArray on the covariates' coordinate.  ``window`` (with ``align``, ``min_periods``): the probability that the ROLLING
-    mean over that window exceeds it, from the diagonal of the windowed covariance, on the qualifying outputs' ``time``."""
+    mean over that window exceeds it, from the diagonal of the windowed covariance, on the qualifying outputs' ``time``.
+    ``streamed=True`` (with ``window`` only; never chosen automatically): that diagonal from the streamed band pass of
+    ``rolling_mean(streamed=True)``, without the dense covariance; ``max_bytes`` then bounds its work area."""
+    if streamed and window is None:
+        raise ValueError("streamed=True applies to the rolling mean: give window=; the pointwise probability needs no covariance")
     if window is not None:
-        return _windowed_exceedance_probability(model, covariates, threshold, above, pred_noise, window, align, min_periods, max_bytes)
+        return _windowed_exceedance_probability(model, covariates, threshold, above, pred_noise, window, align, min_periods, max_bytes,
+                                                streamed)
     mu, var = _latent_predict(model, covariates, pred_noise)
     tau = np.broadcast_to(np.asarray(threshold, dtype=np.float64), mu.shape)
     u = model_space_threshold(model.dm, tau)

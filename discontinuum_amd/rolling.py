@@ -91,17 +91,36 @@ def record_windows(model, covariates, window, align="right", min_periods=None):
     return Xnew, time[order].astype("datetime64[ns]"), np.ascontiguousarray(lo[out]), np.ascontiguousarray(hi[out]), out
 
 
-def check_window_budget(model, m, q, extra_bytes, max_bytes, what):
-    """``ValueError`` naming the bytes when the dense footprint plus the windowed product's own exceeds ``max_bytes``."""
+def check_window_budget(model, m, q, extra_bytes, max_bytes, what, streamable=False):
+    """``ValueError`` naming the bytes when the dense footprint plus the windowed product's own exceeds ``max_bytes``;
+    ``streamable``: the product has a streamed form, and the text ends by naming it."""
     esz = torch.empty((), dtype=model.dtype).element_size()
     need = _site_bytes(model.dm.X.shape[0], m, esz) + window_bytes(m, q) + int(extra_bytes)
     if need > max_bytes:
         raise ValueError(f"{what} needs the dense posterior covariance and its windowed product: a footprint of {need} bytes for "
-                         f"m = {m} points and {q} windows exceeds max_bytes = {max_bytes}")
+                         f"m = {m} points and {q} windows exceeds max_bytes = {max_bytes}" + ("; pass streamed=True" if streamable else ""))
+
+
+def streamed_window_variances(model, Xnew, lo, hi, mode=MODE_LINEAR, s=1.0, t=0.0, max_bytes: int = DEFAULT_MAX_BYTES):
+    """The streamed core of ``rolling_mean`` and ``exceedance_probability(window=)``: the latent mean from ``predict_mean``
+    (as ``exceedance.count_moments``' streamed branch takes it), then ONE ``posterior_window_variances``, whose work area --
+    with the tallest band panel that fits -- ``max_bytes`` bounds.  ``mode`` = MODE_LOG maps the mean by s mu + t first.
+    -> numpy (mean (q,), var (q,))."""
+    model._eval_ready(Xnew)
+    with torch.no_grad():
+        mu = (model._plan.predict_mean(model._factor_theta, Xnew) + model.model.prior_mean(Xnew)).contiguous()
+        lo_t, hi_t = torch.from_numpy(np.ascontiguousarray(lo)), torch.from_numpy(np.ascontiguousarray(hi))
+        if mode == MODE_LOG:
+            mean_d, var_d = model._plan.posterior_window_variances(model._factor_theta, Xnew, (s * mu + t).contiguous(), lo_t, hi_t,
+                                                                   mode=MODE_LOG, scale2=s * s, max_bytes=max_bytes)
+        else:
+            mean_d, var_d = model._plan.posterior_window_variances(model._factor_theta, Xnew, mu, lo_t, hi_t, mode=MODE_LINEAR,
+                                                                   max_bytes=max_bytes)
+    return mean_d.double().cpu().numpy(), var_d.double().cpu().numpy()
 
 
 def rolling_mean(model, covariates, window, statistic=None, align="right", min_periods=None, ci=0.95, return_cov=False,
-                 max_bytes: int = DEFAULT_MAX_BYTES):
+                 max_bytes: int = DEFAULT_MAX_BYTES, streamed=False):
     """``MarginalHIP.rolling_mean``: the rolling-window mean of the target over the record ``covariates`` with its exact
     uncertainty, from one ``posterior_cov`` and one ``window_moments``.
 
@@ -112,7 +131,14 @@ def rolling_mean(model, covariates, window, statistic=None, align="right", min_p
     ``window``, ``align``, ``min_periods``: see ``time_windows``.
     -> Dataset on the qualifying outputs' ``time`` with ``mean``, ``se``, ``lower``, ``upper`` and ``n_points``; with
     ``return_cov`` also the (q, q) covariance -- of the model-space means for the model-space statistic, of the data-space
-    means for the arithmetic one.  A record over ``max_bytes`` raises ``ValueError`` naming the bytes."""
+    means for the arithmetic one.  A record over ``max_bytes`` raises ``ValueError`` naming the bytes.
+    ``streamed=True`` (never chosen automatically): the same Dataset, to rounding, without the dense covariance -- the latent
+    mean from ``predict_mean`` and one ``posterior_window_variances``, which produces only the band of the covariance the
+    windows reach and whose work area ``max_bytes`` bounds instead -- for records of any length.  The covariance BETWEEN the
+    outputs needs the dense path: ``return_cov=True`` is refused."""
+    if streamed and return_cov:
+        raise ValueError("the covariance between outputs needs the dense path: the streamed pass computes the variance of every "
+                         "rolling mean alone; drop streamed=True or return_cov=True")
     mode, s, t = target_transform(model.dm)
     if statistic is None:
         statistic = "geometric_mean" if mode == MODE_LOG else "mean"
@@ -123,21 +149,26 @@ def rolling_mean(model, covariates, window, statistic=None, align="right", min_p
     Xnew, times, lo, hi, out = record_windows(model, covariates, window, align, min_periods)
     Xnew = Xnew.to(model.device).contiguous()
     m, q = Xnew.shape[0], len(out)
-    check_window_budget(model, m, q, 0, max_bytes, "a rolling mean")
     pass_mode = MODE_LOG if (mode == MODE_LOG and statistic == "mean") else MODE_LINEAR
-    model._eval_ready(Xnew)
-    with torch.no_grad():
-        kmean, cov = model._plan.posterior_cov(model._factor_theta, Xnew)
-        mu = (kmean + model.model.prior_mean(Xnew)).contiguous()
-        lo_t, hi_t = torch.from_numpy(lo), torch.from_numpy(hi)
-        if pass_mode == MODE_LOG:
-            mean_d, cov_d = model._plan.window_moments(cov, m, (s * mu + t).contiguous(), lo_t, hi_t, mode=MODE_LOG, scale2=s * s)
-        else:
-            mean_d, cov_d = model._plan.window_moments(cov, m, mu, lo_t, hi_t, mode=MODE_LINEAR)
-    wm = mean_d.double().cpu().numpy()
-    S = cov_d.double().cpu().numpy()[:q, :q]
-    S = np.tril(S) + np.tril(S, -1).T
-    var = np.clip(np.diagonal(S), 0.0, None)
+    if streamed:
+        wm, var = streamed_window_variances(model, Xnew, lo, hi, pass_mode, s, t, max_bytes)
+        var = np.clip(var, 0.0, None)
+        S = None
+    else:
+        check_window_budget(model, m, q, 0, max_bytes, "a rolling mean", streamable=True)
+        model._eval_ready(Xnew)
+        with torch.no_grad():
+            kmean, cov = model._plan.posterior_cov(model._factor_theta, Xnew)
+            mu = (kmean + model.model.prior_mean(Xnew)).contiguous()
+            lo_t, hi_t = torch.from_numpy(lo), torch.from_numpy(hi)
+            if pass_mode == MODE_LOG:
+                mean_d, cov_d = model._plan.window_moments(cov, m, (s * mu + t).contiguous(), lo_t, hi_t, mode=MODE_LOG, scale2=s * s)
+            else:
+                mean_d, cov_d = model._plan.window_moments(cov, m, mu, lo_t, hi_t, mode=MODE_LINEAR)
+        wm = mean_d.double().cpu().numpy()
+        S = cov_d.double().cpu().numpy()[:q, :q]
+        S = np.tril(S) + np.tril(S, -1).T
+        var = np.clip(np.diagonal(S), 0.0, None)
     attrs = dict(_target_attrs(model.dm), statistic=statistic, window=str(window), align=align)
     z_lo, z_hi = norm.ppf((1 - ci) / 2), norm.ppf(1 - (1 - ci) / 2)
     if pass_mode == MODE_LOG:
@@ -171,4 +202,4 @@ def rolling_mean(model, covariates, window, statistic=None, align="right", min_p
     return (ds, S) if return_cov else ds
 
 
-__all__ = ["time_windows", "rolling_mean", "record_windows", "window_bytes", "check_window_budget"]
+__all__ = ["time_windows", "rolling_mean", "record_windows", "window_bytes", "check_window_budget", "streamed_window_variances"]

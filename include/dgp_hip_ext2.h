@@ -84,4 +84,71 @@ int dgp_lowrank_period_moments(int mode, const double* rows_dev, int nrows, int6
                                const double* scale2_dev, const double* w_dev, const int32_t* group_dev, int ngroups, void* work_dev,
                                size_t work_bytes, double* mean_dev, double* cov_dev_out, void* stream);
 
+/* A BLOCK OF THE POSTERIOR COVARIANCE: rows [row0, row1) x columns [col0, row1) of C = K(Xs, Xs) - V^T V of the plan's posterior
+ * at Xs, straight from the factorisation the plan holds -- a piece of the covariance of a record too long to hold whole, and the
+ * band producer of dgp_posterior_window_variances on its own.
+ * p, theta, Xs_dev, m and the padding: as for dgp_posterior_exceedance_moments (batched and ragged plans: one call for all
+ *            sites, every array with a leading site dimension);
+ * row0, row1, col0  multiples of 128 with 0 <= col0 <= row0 < row1 <= M (M = padded m);
+ * out_dev    sites x (row1 - row0) x (row1 - col0) in the plan's dtype: out[site][r][c] = C[row0 + r][col0 + c].  128 x 128 tiles
+ *            above the diagonal are not written; inside a diagonal tile the entries on and below the diagonal are valid.
+ * The launches are dgp_posterior_cov's restricted to the block's tiles -- the same pair evaluator and pad selects, the same tile
+ * core with k ascending over all N rows of V -- so an fp64 entry has the bits it has there.
+ * work_dev: dgp_posterior_cov_block_workspace_bytes(p, m, row0, row1, col0) bytes, 256-byte aligned (the prediction's layout
+ * plus m plan-dtype elements per site); 0 for a null plan or a bad block.
+ * DGP_E_ARG: null arguments, 1 <= m <= 2^20 violated, a bad block, a misaligned work area; DGP_E_WORKSPACE: work area missing or
+ * too small; DGP_E_STATE: no factorisation, or a failed one -- all before any launch.  The plan's A, T, K^^-1 and alpha stay
+ * bitwise intact. */
+size_t dgp_posterior_cov_block_workspace_bytes(const dgp_plan* p, int64_t m, int64_t row0, int64_t row1, int64_t col0);
+int dgp_posterior_cov_block(dgp_plan* p, const double* theta, const void* Xs_dev, int64_t m, int64_t row0, int64_t row1, int64_t col0,
+                            void* work_dev, size_t work_bytes, void* out_dev, void* stream);
+
+/* VARIANCES OF ROLLING-WINDOW MEANS: mean_i and var_i = (W C W^T)_ii of dgp_window_moments (dgp_hip.h: its notation, modes,
+ * weights a, window rules and the meaning of mu / scale2), without the M x Q + Q x Q work area and result: per window
+ *     var_i = d_i^-2 sum_{j in win_i} b_j ( b_j phi(C_jj) + 2 sum_{l in [lo_i, j)} b_l phi(C_jl) ),   phi = id / expm1(s^2 .)
+ * cov_dev    batch x M x M in dtype (0 f64 / 1 f32), the layout of dgp_posterior_cov: entries on and below the diagonal are read,
+ *            the diagonal included;   mu_dev batch x m in dtype;   scale2_dev one double per site (mode 1; may be null in mode 0);
+ * a_dev      null (= 1) or batch x m doubles >= 0;   lo_dev, hi_dev batch x q int32, both non-decreasing; clamped to [0, m];
+ * mean_dev, var_dev  batch x q doubles; an empty window or a zero weight sum gives 0 and 0.
+ * work_dev: dgp_window_variances_workspace_bytes(m, q, batch) bytes, 8-byte aligned: 3 M + 3 Q doubles per site (M, Q the padded
+ * sizes) and one int per site; 0 for bad sizes.  Stateless (no plan).  Four launches (points, windows, contraction, finish);
+ * every sum runs in one owner in a fixed order in double, no floating-point atomics: repeated calls are bitwise equal and a
+ * site's numbers do not depend on its batch.
+ * DGP_E_ARG: bad dtype / mode, null arguments, bad sizes (1 <= m, q <= 2^20, 1 <= batch <= 1024), a misaligned work area;
+ * DGP_E_WORKSPACE: work area missing or too small. */
+size_t dgp_window_variances_workspace_bytes(int64_t m, int64_t q, int batch);
+int dgp_window_variances(int dtype, int mode, const void* cov_dev, int64_t m, int batch, const void* mu_dev, const double* scale2_dev,
+                         const double* a_dev, const int32_t* lo_dev, const int32_t* hi_dev, int64_t q, void* work_dev,
+                         size_t work_bytes, double* mean_dev, double* var_dev, void* stream);
+
+/* STREAMED ROLLING-WINDOW VARIANCES: dgp_window_variances of the plan's posterior at Xs, straight from the factorisation the plan
+ * holds.  Only a BAND of C = K(Xs, Xs) - V^T V is ever produced: two points share a window only if |j - l| < reach, so the panel
+ * of rows [p0, p1) needs the columns [c0, p1), c0 = 128 floor(max(0, p0 - reach + 1) / 128); every unordered pair (j >= l) lies
+ * in exactly one panel, j's, and var_i d_i^2 is accumulated panel by panel in ascending order.
+ * p, theta, Xs_dev, m and the padding: as for dgp_posterior_exceedance_moments (batched and ragged plans: one call for all
+ *            sites, every array with a leading site dimension);
+ * mu_dev     sites x m in the plan's dtype (mode 1: the MAPPED mean);   scale2_dev, a_dev, lo_dev, hi_dev, q, mode, mean_dev,
+ *            var_dev: as for dgp_window_variances.  C_jj is the PREDICTED variance (dgp_predict's), in b_j and as the diagonal
+ *            term, never a panel's diagonal;
+ * reach      >= max_i (hi_i - lo_i) over all sites, 1 .. 2^20.  A window that holds more points is detected on the device:
+ *            every column index is clamped into the band, so nothing outside it is read, and the call returns DGP_E_ARG
+ *            ("a window holds more than reach points") AFTER the pass; the outputs are then unspecified;
+ * panel_rows a positive multiple of 128; the pass uses R = min(panel_rows, M) rows.
+ * work_dev: dgp_posterior_window_variances_workspace_bytes(p, m, q, reach, panel_rows) bytes, 256-byte aligned -- per site the
+ * prediction's layout, one band of R x (R + round_up(reach, 128)) plan-dtype elements and 3 M + 3 Q doubles, plus one int per
+ * site; 0 for a null plan or bad sizes.  Its contents before the call do not matter.
+ * Launches (gridDim.z = sites, one stream), no floating-point atomics: the prediction's front end, points, windows, per panel
+ * (ascending) the band Gram, the band update (dgp_posterior_cov's evaluator and tile core on the band's tiles) and one
+ * contraction, then finish; the call synchronises the stream to read the reach flags.  Every sum runs in one owner in a fixed
+ * order: repeated calls are bitwise equal and a site's numbers do not depend on its batch; another panel_rows regroups the
+ * sums over j (agreement to rounding).  The plan's A, T, K^^-1 and alpha stay bitwise intact.
+ * DGP_E_ARG: null arguments, bad mode, bad sizes (1 <= m, q <= 2^20), reach outside 1 .. 2^20, panel_rows not a positive multiple
+ * of 128, a misaligned work area; DGP_E_WORKSPACE: work area missing or too small; DGP_E_STATE: no factorisation, or a failed
+ * one -- all before any launch; the reach flag alone is raised after the pass. */
+size_t dgp_posterior_window_variances_workspace_bytes(const dgp_plan* p, int64_t m, int64_t q, int64_t reach, int panel_rows);
+int dgp_posterior_window_variances(dgp_plan* p, const double* theta, const void* Xs_dev, int64_t m, const void* mu_dev,
+                                   const double* scale2_dev, const double* a_dev, const int32_t* lo_dev, const int32_t* hi_dev,
+                                   int64_t q, int mode, int64_t reach, int panel_rows, void* work_dev, size_t work_bytes,
+                                   double* mean_dev, double* var_dev, void* stream);
+
 #endif /* DGP_HIP_EXT2_H */
