@@ -168,6 +168,37 @@ class GPPlan:
         need = int(getattr(self.lib, query)(self._h, *sizes))
         return self._work_area(attr, need, what), need
 
+    def _stream_work(self, attr, name, sizes, panel_rows, pick, bad_size):
+        """(R, base, bytes) for the streamed entry point ``name``: the panel height -- ``panel_rows``, or ``pick()`` when it
+        is None --, which must be a positive multiple of 128, and the cached work area ``self.<attr>`` at the size
+        ``<name>_workspace_bytes(plan, *sizes, R)`` reports; a ``ValueError`` with the text ``bad_size`` when that is 0."""
+        R = pick() if panel_rows is None else int(panel_rows)
+        if R <= 0 or R % 128:
+            raise ValueError(f"panel_rows must be a positive multiple of 128, not {panel_rows}")
+        need = int(getattr(self.lib, name + "_workspace_bytes")(self._h, *sizes, R))
+        if need == 0:
+            raise ValueError(bad_size)
+        return R, self._work_area(attr, need, name, check_free=True), need
+
+    def _panel_sizes(self, name, sizes, max_bytes, bad_size):
+        """(size, max_bytes) for the ``*_panel_rows`` methods: ``size(R)`` = ``<name>_workspace_bytes(plan, *sizes, R)``, the
+        budget with its default ``loads.DEFAULT_MAX_BYTES``; a ``ValueError`` with the text ``bad_size`` when ``size(128)`` is 0."""
+        if max_bytes is None:
+            from .loads import DEFAULT_MAX_BYTES as max_bytes
+        query = getattr(self.lib, name + "_workspace_bytes")
+        sizes = tuple(int(v) for v in sizes)
+        size = lambda R: int(query(self._h, *sizes, R))  # noqa: E731
+        if size(128) == 0:
+            raise ValueError(bad_size)
+        return size, max_bytes
+
+    def _linear_panel_rows(self, name, sizes, max_bytes, bad_size, what):
+        """``stream_panel_rows`` on the sizes ``<name>_workspace_bytes`` reports for ``sizes`` (m first): a work area that
+        grows linearly in the panel height."""
+        size, max_bytes = self._panel_sizes(name, sizes, max_bytes, bad_size)
+        M = int(self.lib.dgp_padded_n(int(sizes[0])))
+        return stream_panel_rows(size(128), size(256) - size(128) if M > 128 else 0, M, max_bytes, what)
+
     def buffer(self, which: int, site: int = 0) -> torch.Tensor:
         """Tensor view of a plan buffer (tests / profiling); ``site``: which site's copy of a batched plan."""
         p, ld = C.c_void_p(), C.c_int64()
@@ -796,14 +827,8 @@ class GPPlan:
             mu_t, w_t, g_t, ev_t, _ = _moment_inputs(dev, self.dtype, lead, m, mu, w, groups, extra_var)
             u_t = _row_matrix(thresh, "thresh", "L", lead, m, dev)
             L = int(u_t.shape[-2])
-            R = self.exceedance_panel_rows(m, P, L, max_bytes) if panel_rows is None else int(panel_rows)
-            if R <= 0 or R % 128:
-                raise ValueError(f"panel_rows must be a positive multiple of 128, not {panel_rows}")
-            need = int(self.lib.dgp_posterior_exceedance_moments_workspace_bytes(self._h, m, P, L, R))
-            if need == 0:
-                raise ValueError(f"bad size: m = {m}, ngroups = {P}, levels = {L} (1 <= m <= 2^20, 1 <= ngroups <= 65535, "
-                                 "1 <= levels <= 64)")
-            work = self._work_area("_pex_ws", need, "dgp_posterior_exceedance_moments", check_free=True)
+            R, work, need = self._stream_work("_pex_ws", "dgp_posterior_exceedance_moments", (m, P, L), panel_rows,
+                                              lambda: self.exceedance_panel_rows(m, P, L, max_bytes), _levels_bad_size(m, P, L))
             xs = Xs.contiguous()
             mean_out, cov_out = self._empty(L, P, dtype=torch.float64), self._empty(L, P, P, dtype=torch.float64)
             self._call("dgp_posterior_exceedance_moments", th, _ptr(xs), m, _ptr(mu_t), _ptr(u_t), L, _ptr(w_t), _ptr(g_t), P,
@@ -814,14 +839,8 @@ class GPPlan:
         """The panel height ``posterior_exceedance_moments`` picks for m points, ``ngroups`` groups and ``nlevels`` levels under
         ``max_bytes`` (default ``loads.DEFAULT_MAX_BYTES``): ``stream_panel_rows`` on the sizes
         ``dgp_posterior_exceedance_moments_workspace_bytes`` reports."""
-        if max_bytes is None:
-            from .loads import DEFAULT_MAX_BYTES as max_bytes
-        size = lambda R: int(self.lib.dgp_posterior_exceedance_moments_workspace_bytes(self._h, int(m), int(ngroups), int(nlevels), R))  # noqa: E731
-        if size(128) == 0:
-            raise ValueError(f"bad size: m = {m}, ngroups = {ngroups}, levels = {nlevels} (1 <= m <= 2^20, 1 <= ngroups <= 65535, "
-                             "1 <= levels <= 64)")
-        M = int(self.lib.dgp_padded_n(int(m)))
-        return stream_panel_rows(size(128), size(256) - size(128) if M > 128 else 0, M, max_bytes)
+        return self._linear_panel_rows("dgp_posterior_exceedance_moments", (m, ngroups, nlevels), max_bytes,
+                                       _levels_bad_size(m, ngroups, nlevels), "the streamed exceedance pass")
 
     def posterior_excess_moments(self, theta, Xs: torch.Tensor, mu, scale2, thresh, w, groups, ngroups: int, above: bool = True,
                                  extra_var=None, panel_rows=None, max_bytes=None):
@@ -842,14 +861,8 @@ class GPPlan:
             mu_t, w_t, g_t, ev_t, s2 = _moment_inputs(dev, self.dtype, lead, m, mu, w, groups, extra_var, scale2)
             a_t = _row_matrix(thresh, "thresh", "L", lead, m, dev)
             L = int(a_t.shape[-2])
-            R = self.excess_panel_rows(m, P, L, max_bytes) if panel_rows is None else int(panel_rows)
-            if R <= 0 or R % 128:
-                raise ValueError(f"panel_rows must be a positive multiple of 128, not {panel_rows}")
-            need = int(self.lib.dgp_posterior_excess_moments_workspace_bytes(self._h, m, P, L, R))
-            if need == 0:
-                raise ValueError(f"bad size: m = {m}, ngroups = {P}, levels = {L} (1 <= m <= 2^20, 1 <= ngroups <= 65535, "
-                                 "1 <= levels <= 64)")
-            work = self._work_area("_pxs_ws", need, "dgp_posterior_excess_moments", check_free=True)
+            R, work, need = self._stream_work("_pxs_ws", "dgp_posterior_excess_moments", (m, P, L), panel_rows,
+                                              lambda: self.excess_panel_rows(m, P, L, max_bytes), _levels_bad_size(m, P, L))
             xs = Xs.contiguous()
             mean_out, cov_out = self._empty(L, P, dtype=torch.float64), self._empty(L, P, P, dtype=torch.float64)
             total_out = self._empty(P, dtype=torch.float64)
@@ -861,14 +874,8 @@ class GPPlan:
         """The panel height ``posterior_excess_moments`` picks for m points, ``ngroups`` groups and ``nlevels`` levels under
         ``max_bytes`` (default ``loads.DEFAULT_MAX_BYTES``): ``stream_panel_rows`` on the sizes
         ``dgp_posterior_excess_moments_workspace_bytes`` reports."""
-        if max_bytes is None:
-            from .loads import DEFAULT_MAX_BYTES as max_bytes
-        size = lambda R: int(self.lib.dgp_posterior_excess_moments_workspace_bytes(self._h, int(m), int(ngroups), int(nlevels), R))  # noqa: E731
-        if size(128) == 0:
-            raise ValueError(f"bad size: m = {m}, ngroups = {ngroups}, levels = {nlevels} (1 <= m <= 2^20, 1 <= ngroups <= 65535, "
-                             "1 <= levels <= 64)")
-        M = int(self.lib.dgp_padded_n(int(m)))
-        return stream_panel_rows(size(128), size(256) - size(128) if M > 128 else 0, M, max_bytes, "the streamed excess pass")
+        return self._linear_panel_rows("dgp_posterior_excess_moments", (m, ngroups, nlevels), max_bytes,
+                                       _levels_bad_size(m, ngroups, nlevels), "the streamed excess pass")
 
     _SV_SIZES = ("(1 <= m <= 2^20, 1 <= ngroups <= 65535, 0 <= nrows <= 64, 1 <= nterms <= 64)")
 
@@ -897,13 +904,11 @@ class GPPlan:
                 top = torch.where(g_t >= 0, var, torch.zeros_like(var)).reshape(self.batch, -1).amax(dim=1)
                 nterms = series_terms(float((s2 * top).max()))
             K = int(nterms)
+            bad_size = f"bad size: m = {m}, ngroups = {P}, nrows = {nrows}, nterms = {K} {self._SV_SIZES}"
             if int(self.lib.dgp_posterior_sample_value_workspace_bytes(self._h, m, P, nrows, K, 128)) == 0:
-                raise ValueError(f"bad size: m = {m}, ngroups = {P}, nrows = {nrows}, nterms = {K} {self._SV_SIZES}")
-            R = self.sample_value_panel_rows(m, P, nrows, K, max_bytes) if panel_rows is None else int(panel_rows)
-            if R <= 0 or R % 128:
-                raise ValueError(f"panel_rows must be a positive multiple of 128, not {panel_rows}")
-            need = int(self.lib.dgp_posterior_sample_value_workspace_bytes(self._h, m, P, nrows, K, R))
-            work = self._work_area("_psv_ws", need, "dgp_posterior_sample_value", check_free=True)
+                raise ValueError(bad_size)  # (before panel_rows is looked at)
+            R, work, need = self._stream_work("_psv_ws", "dgp_posterior_sample_value", (m, P, nrows, K), panel_rows,
+                                              lambda: self.sample_value_panel_rows(m, P, nrows, K, max_bytes), bad_size)
             xs = Xs.contiguous()
             gain, var_out = self._empty(P, m, dtype=torch.float64), self._empty(m, dtype=torch.float64)
             self._call("dgp_posterior_sample_value", th, _ptr(xs), m, _ptr(a_t), _ptr(s2), _ptr(g_t), P, _ptr(ov_t), _ptr(rows_t), nrows,
@@ -914,13 +919,9 @@ class GPPlan:
         """The panel height ``posterior_sample_value`` picks for m points, ``ngroups`` groups, ``nrows`` conditioning rows and
         ``nterms`` series terms under ``max_bytes`` (default ``loads.DEFAULT_MAX_BYTES``): ``stream_panel_rows`` on the sizes
         ``dgp_posterior_sample_value_workspace_bytes`` reports."""
-        if max_bytes is None:
-            from .loads import DEFAULT_MAX_BYTES as max_bytes
-        size = lambda R: int(self.lib.dgp_posterior_sample_value_workspace_bytes(self._h, int(m), int(ngroups), int(nrows), int(nterms), R))  # noqa: E731
-        if size(128) == 0:
-            raise ValueError(f"bad size: m = {m}, ngroups = {ngroups}, nrows = {nrows}, nterms = {nterms} {self._SV_SIZES}")
-        M = int(self.lib.dgp_padded_n(int(m)))
-        return stream_panel_rows(size(128), size(256) - size(128) if M > 128 else 0, M, max_bytes, "the streamed value of samples")
+        return self._linear_panel_rows("dgp_posterior_sample_value", (m, ngroups, nrows, nterms), max_bytes,
+                                       f"bad size: m = {m}, ngroups = {ngroups}, nrows = {nrows}, nterms = {nterms} {self._SV_SIZES}",
+                                       "the streamed value of samples")
 
     def posterior_cov_columns(self, theta, Xs: torch.Tensor, idx):
         """Columns C[:, idx] of the latent posterior covariance at Xs (``dgp_posterior_cov_columns``) as (ncols, m) float64 --
@@ -983,13 +984,9 @@ class GPPlan:
         dev = self.device
         with torch.cuda.device(dev):
             mu_t, a_t, _g, _ev, s2 = _moment_inputs(dev, self.dtype, lead, m, mu, a, None, None, scale2 if mode == MODE_LOG else None)
-            R = self.window_panel_rows(m, q, reach, max_bytes) if panel_rows is None else int(panel_rows)
-            if R <= 0 or R % 128:
-                raise ValueError(f"panel_rows must be a positive multiple of 128, not {panel_rows}")
-            need = int(self.lib.dgp_posterior_window_variances_workspace_bytes(self._h, m, q, reach, R))
-            if need == 0:
-                raise ValueError(f"bad size: m = {m}, q = {q} (1 <= m, q <= 2^20)")
-            work = self._work_area("_pwv_ws", need, "dgp_posterior_window_variances", check_free=True)
+            R, work, need = self._stream_work("_pwv_ws", "dgp_posterior_window_variances", (m, q, reach), panel_rows,
+                                              lambda: self.window_panel_rows(m, q, reach, max_bytes),
+                                              f"bad size: m = {m}, q = {q} (1 <= m, q <= 2^20)")
             xs = Xs.contiguous()
             lo_t, hi_t = lo_h.to(dev), hi_h.to(dev)
             mean_out, var_out = self._empty(q, dtype=torch.float64), self._empty(q, dtype=torch.float64)
@@ -1003,12 +1000,9 @@ class GPPlan:
         quadratically in R, so ``stream_panel_rows``' linear rule does not apply: a bisection on the sizes
         ``dgp_posterior_window_variances_workspace_bytes`` reports for the largest multiple of 128, at most the padded record
         length M, whose work area fits.  ``ValueError`` naming the bytes when 128 rows do not fit."""
-        if max_bytes is None:
-            from .loads import DEFAULT_MAX_BYTES as max_bytes
-        size = lambda R: int(self.lib.dgp_posterior_window_variances_workspace_bytes(self._h, int(m), int(q), int(reach), R))  # noqa: E731
+        size, max_bytes = self._panel_sizes("dgp_posterior_window_variances", (m, q, reach), max_bytes,
+                                            f"bad size: m = {m}, q = {q}, reach = {reach} (1 <= m, q, reach <= 2^20)")
         need128 = size(128)
-        if need128 == 0:
-            raise ValueError(f"bad size: m = {m}, q = {q}, reach = {reach} (1 <= m, q, reach <= 2^20)")
         if need128 > max_bytes:
             raise ValueError(f"the streamed rolling-mean pass needs a work area of {need128} bytes with the smallest panel (128 "
                              f"rows), which exceeds max_bytes = {max_bytes}")
@@ -1220,6 +1214,11 @@ def period_third_moments(cov: torch.Tensor, m: int, mu: torch.Tensor, scale2, w:
         _call("dgp_period_third_moments", _DTYPES[cov.dtype], _ptr(cov), m, B, _ptr(mu_t), _ptr(s2), _ptr(w_t), _ptr(g_t), P,
               _ptr(ev_t), int(tile), _ptr(work), need, _ptr(k3))
     return k3
+
+
+def _levels_bad_size(m, ngroups, nlevels):
+    return (f"bad size: m = {m}, ngroups = {ngroups}, levels = {nlevels} (1 <= m <= 2^20, 1 <= ngroups <= 65535, "
+            "1 <= levels <= 64)")
 
 
 def stream_panel_rows(need128: int, step: int, M: int, max_bytes: int, what: str = "the streamed exceedance pass") -> int:

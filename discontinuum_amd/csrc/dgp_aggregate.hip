@@ -36,7 +36,7 @@
 #include "dgp_common.h"
 #include "dgp_gemm_dma.h"
 #include "dgp_gram_shared.h"
-#include "dgp_plan.h"
+#include "dgp_stream.h"
 #include "dgp_models.h"
 
 namespace dgp {
@@ -504,19 +504,16 @@ static int posterior_period_moments(int mode, int model, int d, const T* V, long
 
 using namespace dgp;
 
-// streamed period moments: the prediction's work area (its first stages leave V, Xs's SoA copy and the predicted variance
-// there), then the moment pass's work area
+// streamed period moments: dgp_stream.h's areas without a panel (the pass forms its rows of C on the fly), then the moment
+// pass's work area
 template <typename T>
 static int post_period(dgp_plan* p, const double* theta, const void* Xs, int64_t m, int mode, const void* mu, const double* scale2,
                        const double* w, const int32_t* group, int P, const void* ev, void* work, double* mean_out, double* cov_out,
                        hipStream_t s) {
-  double* pm = (double*)((char*)work + predict_layout(p, m).total * (size_t)p->B);
-  T *V, *Xst, *vpad;
-  long wbs;
-  // the latent mean the prediction also writes (B x m elements) lands in the moment pass's area, which its first launch resets
-  int rc = predict_common<T>(p, theta, Xs, m, work, pm, &V, &Xst, &vpad, &wbs, s);
-  if (rc) return rc;
-  return posterior_period_moments<T>(mode, p->model, p->d, V, p->N, (long)m, p->B, Xst, vpad, wbs, theta, (const T*)mu, scale2, w,
+  double* pm = (double*)posterior_areas<T>(p, m, work, 0).own;
+  Posterior<T> ps;
+  if (int rc = ps.fill(p, theta, Xs, m, work, pm, s)) return rc;
+  return posterior_period_moments<T>(mode, p->model, p->d, ps.V, p->N, (long)m, p->B, ps.Xst, ps.var, ps.wbs, theta, (const T*)mu, scale2, w,
                                      group, P, (const T*)ev, pm, mean_out, cov_out, s, p->pre);
 }
 
@@ -570,7 +567,7 @@ int dgp_lowrank_period_moments(int mode, const double* rows, int nrows, int64_t 
 
 size_t dgp_posterior_period_moments_workspace_bytes(const dgp_plan* p, int64_t m, int ngroups) {
   if (!p || m <= 0 || m > (1 << 20) || ngroups <= 0 || ngroups > 65535) return 0;
-  return predict_layout(p, m).total * (size_t)p->B + period_moments_workspace_bytes(m, ngroups, p->B);
+  return posterior_head_bytes(p, m, 0) + period_moments_workspace_bytes(m, ngroups, p->B);
 }
 
 int dgp_posterior_period_moments(dgp_plan* p, const double* theta, const void* Xs, int64_t m, int mode, const void* mu,

@@ -2,10 +2,7 @@
 // C = K(Xs, Xs) - V^T V produced R rows at a time and never stored whole (dgp_posterior_sample_value), and single columns of C
 // for the host's conditioning rows (dgp_posterior_cov_columns).
 //
-// The front end and the panels are dgp_exceed_stream.hip's: V = L^-1 K(X, Xs), the test points' SoA coordinates and the
-// predicted variance are what the prediction's first stages leave in the work area; panel q holds the rows [q R, (q + 1) R) of C
-// and the columns 0 .. (q + 1) R - 1 in a buffer of R x M elements, from gram_sym's tiles followed by posterior_cov's trailing
-// update on the tile rows of the panel only.  Notation of dgp_design.hip.  The power sums S[p][k][c] = sum_{i in p} A_i b_ic^k
+// The front end, the panels and their invariants are dgp_stream.h's.  Notation of dgp_design.hip.  The power sums S[p][k][c] = sum_{i in p} A_i b_ic^k
 // live in the work area, [P][K][M] doubles per site.  Every ORDERED pair (day i, candidate c) is counted exactly once:
 //   i >= c   in the panel that holds row i, read as C[i][c] (row segments, coalesced)
 //   i <  c   in the panel that holds row c, read as C[c][i] (transposed on the way into LDS, as sv_sums_kernel does it)
@@ -25,7 +22,7 @@
 #include <climits>
 
 #include "dgp_design.h"
-#include "dgp_plan.h"
+#include "dgp_stream.h"
 
 namespace dgp {
 
@@ -260,39 +257,23 @@ __global__ __launch_bounds__(256) void cc_cols_kernel(const T* __restrict__ Kc, 
 
 }  // namespace
 
-static long sample_value_panel_rows(long m, long R) {
-  const long M = round_up(m, DGP_TILE_HOST);
-  return R < M ? R : M;
-}
-
-// The gain map with C = K(Xs, Xs) - V^T V produced R rows at a time (R a multiple of 128; the pass uses min(R, M)) into `panel`
-// (R x M elements per site, site stride pstride) and never stored whole.  V, Xst, var (overwritten), wbs, pre_scratch as the
-// prediction leaves them; `work`: svs_site_doubles per site
+// The gain map with C produced R rows at a time into `panel` (site stride pstride) and never stored whole.  `work`:
+// svs_site_doubles per site
 template <typename T>
-static int posterior_sample_value(int model, int d, const T* V, long N, long m, int B, const T* Xst, T* var, long wbs,
-                                  const double* theta, const double* a, const double* scale2, const int* group, int P, const T* ov,
-                                  const double* rows, int nrows, int K, long R, T* panel, long pstride, double* work,
-                                  double* gain_out, double* var_out, hipStream_t s, void* pre_scratch) {
+static int posterior_sample_value(const Posterior<T>& ps, const double* a, const double* scale2, const int* group, int P, const T* ov,
+                                  const double* rows, int nrows, int K, long R, T* panel, long pstride, double* work, double* gain_out,
+                                  double* var_out) {
   static_assert(SVS_WAVES * SV_DAYS * SV_LD * sizeof(double) % 16 == 0, "the LDS carve offsets must stay 16-byte aligned");
-  const long M = round_up(m, DGP_TILE_HOST);
+  const long M = ps.M, m = ps.m;
   const long ws = svs_site_doubles(M, P, K);
-  const int mi = (int)m;
-  R = sample_value_panel_rows(m, R);
+  const int mi = (int)m, B = ps.p->B;
+  hipStream_t s = ps.s;
   const long count = (long)P * K * M, zb = (count + 255) / 256;
   svs_init_kernel<<<dim3((unsigned)(zb < 65536 ? zb : 65536), 1, (unsigned)B), 256, 0, s>>>(work, ws, M, P, K);
-  svs_prep_kernel<T><<<dim3((unsigned)((M + 255) / 256), 1, (unsigned)B), 256, 0, s>>>(var, wbs, M, mi, P, group, ov, rows, nrows, work, ws,
-                                                                                     var_out);
-  // the variances are read: their place now holds the zero "noise" of K(Xs, Xs), as for dgp_posterior_cov
-  hipError_t he = hipMemset2DAsync(var, sizeof(T) * (size_t)(wbs > 0 ? wbs : M), 0, sizeof(T) * M, (size_t)B, s);
-  if (he != hipSuccess) return (int)he;
-  Batch wb;
-  wb.B = B;
-  wb.ws = wbs;
-  for (long p0 = 0; p0 < M; p0 += R) {
-    const long p1 = p0 + R < M ? p0 + R : M;
-    int rc = gram_sym_panel<T>(model, d, Xst, M, mi, theta, var, panel, p0, p1, s, wb, pre_scratch, pstride, wbs);
-    if (rc) return rc;
-    if ((rc = posterior_cov_panel<T>(V, N, M, panel, p0, p1, pstride, s, B, wbs))) return rc;
+  svs_prep_kernel<T><<<dim3((unsigned)((M + 255) / 256), 1, (unsigned)B), 256, 0, s>>>(ps.var, ps.wbs, M, mi, P, group, ov, rows, nrows, work,
+                                                                                     ws, var_out);
+  if (int rc = ps.zero_noise()) return rc;
+  const int rc = ps.panels(R, panel, pstride, [&](long p0, long p1) {
     if (K <= 4)
       svs_launch_sums<T, 4>(panel, pstride, M, mi, B, P, K, (int)p0, (int)p1, a, group, rows, nrows, work, ws, s);
     else if (K <= 16)
@@ -301,7 +282,8 @@ static int posterior_sample_value(int model, int d, const T* V, long N, long m, 
       svs_launch_sums<T, 32>(panel, pstride, M, mi, B, P, K, (int)p0, (int)p1, a, group, rows, nrows, work, ws, s);
     else
       svs_launch_sums<T, 64>(panel, pstride, M, mi, B, P, K, (int)p0, (int)p1, a, group, rows, nrows, work, ws, s);
-  }
+  });
+  if (rc) return rc;
   svs_fold_kernel<<<dim3((unsigned)((m + 255) / 256), (unsigned)P, (unsigned)B), 256, 0, s>>>(M, mi, P, K, scale2, work, ws, gain_out);
   return (int)hipGetLastError();
 }
@@ -312,52 +294,42 @@ using namespace dgp;
 
 static bool svs_sizes_ok(const dgp_plan* p, int64_t m, int ngroups, int nrows, int nterms, int panel_rows) {
   return p && m > 0 && m <= (1 << 20) && ngroups > 0 && ngroups <= 65535 && nrows >= 0 && nrows <= 64 && nterms >= 1 && nterms <= 64 &&
-         panel_rows > 0 && panel_rows % DGP_TILE_HOST == 0;
+         panel_rows_ok(panel_rows);
 }
 
-// streamed gain map: the prediction's work area, one covariance panel of R x M elements per site, then the pass's own area
+// streamed gain map: dgp_stream.h's areas with one covariance panel of R x M elements per site, then the pass's own area
 static size_t svs_panel_bytes(const dgp_plan* p, int64_t m, int panel_rows) {
-  return Carve::up(p->elem * (size_t)sample_value_panel_rows((long)m, panel_rows) * (size_t)round_up(m, DGP_TILE_HOST));
+  return panel_bytes(p, m, panel_rows, round_up(m, DGP_TILE_HOST));
 }
 template <typename T>
 static int post_sample_value(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const double* a, const double* scale2,
                              const int32_t* group, int P, const void* ov, const double* rows, int nrows, int K, int panel_rows, void* work,
                              double* gain_out, double* var_out, hipStream_t s) {
-  const size_t pb = svs_panel_bytes(p, m, panel_rows);
-  T* panel = (T*)((char*)work + predict_layout(p, m).total * (size_t)p->B);
-  double* sv = (double*)((char*)panel + pb * (size_t)p->B);
-  T *V, *Xst, *vpad;
-  long wbs;
-  // the latent mean the prediction also writes (B x m elements) lands in the pass's area, which its first launches reset
-  int rc = predict_common<T>(p, theta, Xs, m, work, sv, &V, &Xst, &vpad, &wbs, s);
-  if (rc) return rc;
-  return posterior_sample_value<T>(p->model, p->d, V, p->N, (long)m, p->B, Xst, vpad, wbs, theta, a, scale2, group, P, (const T*)ov, rows,
-                                   nrows, K, panel_rows, panel, (long)(pb / sizeof(T)), sv, gain_out, var_out, s, p->pre);
+  const PosteriorAreas<T> A = posterior_areas<T>(p, m, work, svs_panel_bytes(p, m, panel_rows));
+  Posterior<T> ps;
+  if (int rc = ps.fill(p, theta, Xs, m, work, A.own, s)) return rc;
+  return posterior_sample_value<T>(ps, a, scale2, group, P, (const T*)ov, rows, nrows, K, panel_rows, A.panel, A.pstride, (double*)A.own,
+                                   gain_out, var_out);
 }
 
-// columns of C: the prediction's work area (K(X, Xs)'s place, free once V is formed, takes the columns' cross Gram), then per
-// site the gathered points (d x 128), then the latent mean the prediction also writes
+// columns of C: dgp_stream.h's areas (K(X, Xs)'s place, free once V is formed, takes the columns' cross Gram) with the gathered
+// points (d x 128) per site, then the latent mean the prediction also writes
 static size_t cc_points_bytes(const dgp_plan* p) { return Carve::up(p->elem * (size_t)DGP_TILE_HOST * (size_t)p->d); }
 template <typename T>
 static int post_cov_columns(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const int32_t* idx, int ncols, void* work,
                             double* out, hipStream_t s) {
-  const long M = round_up(m, DGP_TILE_HOST);
-  const PredictLayout L = predict_layout(p, m);
-  const size_t xb = cc_points_bytes(p);
-  T* Xc = (T*)((char*)work + L.total * (size_t)p->B);
-  T* mean = (T*)((char*)Xc + xb * (size_t)p->B);
-  T* Kc = (T*)((char*)work + L.Ks);
-  T *V, *Xst, *vpad;
-  long wbs;
-  int rc = predict_common<T>(p, theta, Xs, m, work, mean, &V, &Xst, &vpad, &wbs, s);
-  if (rc) return rc;
-  const long xstride = (long)(xb / sizeof(T));
-  cc_gather_kernel<T><<<dim3(1, 1, (unsigned)p->B), DGP_TILE_HOST, 0, s>>>(Xst, wbs, M, (int)m, p->d, idx, ncols, Xc, xstride);
+  const PosteriorAreas<T> A = posterior_areas<T>(p, m, work, cc_points_bytes(p));
+  T* Xc = A.panel;
+  T* Kc = (T*)((char*)work + predict_layout(p, m).Ks);
+  Posterior<T> ps;
+  if (int rc = ps.fill(p, theta, Xs, m, work, A.own, s)) return rc;
+  const long M = ps.M, wbs = ps.wbs;
+  cc_gather_kernel<T><<<dim3(1, 1, (unsigned)p->B), DGP_TILE_HOST, 0, s>>>(ps.Xst, wbs, M, (int)m, p->d, idx, ncols, Xc, A.pstride);
   Batch bt;
   bt.B = p->B;
-  bt.ws = xstride;
-  if ((rc = gram_cross<T>(p->model, p->d, Xc, DGP_TILE_HOST, ncols, Xst, M, (int)m, theta, Kc, s, bt, wbs, p->pre, nullptr))) return rc;
-  cc_cols_kernel<T><<<dim3((unsigned)((m + 255) / 256), (unsigned)ncols, (unsigned)p->B), 256, 0, s>>>(Kc, V, p->N, M, (int)m, idx, ncols, wbs,
+  bt.ws = A.pstride;
+  if (int rc = gram_cross<T>(p->model, p->d, Xc, DGP_TILE_HOST, ncols, ps.Xst, M, (int)m, theta, Kc, s, bt, wbs, p->pre, nullptr)) return rc;
+  cc_cols_kernel<T><<<dim3((unsigned)((m + 255) / 256), (unsigned)ncols, (unsigned)p->B), 256, 0, s>>>(Kc, ps.V, p->N, M, (int)m, idx, ncols, wbs,
                                                                                                     out);
   return (int)hipGetLastError();
 }
@@ -366,52 +338,42 @@ extern "C" {
 
 size_t dgp_posterior_sample_value_workspace_bytes(const dgp_plan* p, int64_t m, int ngroups, int nrows, int nterms, int panel_rows) {
   if (!svs_sizes_ok(p, m, ngroups, nrows, nterms, panel_rows)) return 0;
-  return (predict_layout(p, m).total + svs_panel_bytes(p, m, panel_rows)) * (size_t)p->B +
+  return posterior_head_bytes(p, m, svs_panel_bytes(p, m, panel_rows)) +
          sizeof(double) * (size_t)p->B * (size_t)svs_site_doubles(round_up(m, DGP_TILE_HOST), ngroups, nterms);
 }
 
 int dgp_posterior_sample_value(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const double* a, const double* scale2,
                                const int32_t* group, int ngroups, const void* obs_var, const double* rows, int nrows, int nterms,
                                int panel_rows, void* work, size_t work_bytes, double* gain_out, double* var_out, void* stream) {
-  const char* where = "dgp_posterior_sample_value";
   if (!p) return fail(DGP_E_ARG, "null plan");
   if (!theta || !Xs || !a || !scale2 || !group || !gain_out || !var_out) return fail(DGP_E_ARG, "dgp_posterior_sample_value: null argument");
   if (!svs_sizes_ok(p, m, ngroups, nrows, nterms, DGP_TILE_HOST))
     return fail(DGP_E_ARG,
                 "dgp_posterior_sample_value: bad size (1 <= m <= 2^20, 1 <= ngroups <= 65535, 0 <= nrows <= 64, 1 <= nterms <= 64)");
-  if (panel_rows <= 0 || panel_rows % DGP_TILE_HOST != 0)
+  if (!panel_rows_ok(panel_rows))
     return fail(DGP_E_ARG, "dgp_posterior_sample_value: panel_rows must be a positive multiple of 128");
   if (nrows > 0 && !rows) return fail(DGP_E_ARG, "dgp_posterior_sample_value: null argument (rows with nrows > 0)");
-  if (int rc = need_factor(p, where, "call dgp_factorize or dgp_fit_step")) return rc;
-  DGP_CHECK_PLAN(p);
-  hipStream_t s = (hipStream_t)stream;
-  int rc = need_work(work, work_bytes, dgp_posterior_sample_value_workspace_bytes(p, m, ngroups, nrows, nterms, panel_rows), where);
-  if (rc || (rc = factor_ok(p, s, where))) return rc;
-  rc = DGP_BY_DTYPE(p, post_sample_value<double>(p, theta, Xs, m, a, scale2, group, ngroups, obs_var, rows, nrows, nterms, panel_rows, work, gain_out, var_out, s),
-                    post_sample_value<float>(p, theta, Xs, m, a, scale2, group, ngroups, obs_var, rows, nrows, nterms, panel_rows, work, gain_out, var_out, s));
-  return wrap(rc, where);
+  return posterior_entry(p, "dgp_posterior_sample_value", work, work_bytes,
+                         dgp_posterior_sample_value_workspace_bytes(p, m, ngroups, nrows, nterms, panel_rows), stream,
+                         [&](auto t, hipStream_t s) {
+                           return post_sample_value<decltype(t)>(p, theta, Xs, m, a, scale2, group, ngroups, obs_var, rows, nrows, nterms,
+                                                                 panel_rows, work, gain_out, var_out, s);
+                         });
 }
 
 size_t dgp_posterior_cov_columns_workspace_bytes(const dgp_plan* p, int64_t m, int ncols) {
   if (!p || m <= 0 || m > (1 << 20) || ncols < 1 || ncols > 64) return 0;
-  return (predict_layout(p, m).total + cc_points_bytes(p)) * (size_t)p->B + Carve::up(p->elem * (size_t)p->B * (size_t)m);
+  return posterior_head_bytes(p, m, cc_points_bytes(p)) + Carve::up(p->elem * (size_t)p->B * (size_t)m);
 }
 
 int dgp_posterior_cov_columns(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const int32_t* idx, int ncols, void* work,
                               size_t work_bytes, double* cols_out, void* stream) {
-  const char* where = "dgp_posterior_cov_columns";
   if (!p) return fail(DGP_E_ARG, "null plan");
   if (!theta || !Xs || !idx || !cols_out) return fail(DGP_E_ARG, "dgp_posterior_cov_columns: null argument");
   if (m <= 0 || m > (1 << 20) || ncols < 1 || ncols > 64)
     return fail(DGP_E_ARG, "dgp_posterior_cov_columns: bad size (1 <= m <= 2^20, 1 <= ncols <= 64)");
-  if (int rc = need_factor(p, where, "call dgp_factorize or dgp_fit_step")) return rc;
-  DGP_CHECK_PLAN(p);
-  hipStream_t s = (hipStream_t)stream;
-  int rc = need_work(work, work_bytes, dgp_posterior_cov_columns_workspace_bytes(p, m, ncols), where);
-  if (rc || (rc = factor_ok(p, s, where))) return rc;
-  rc = DGP_BY_DTYPE(p, post_cov_columns<double>(p, theta, Xs, m, idx, ncols, work, cols_out, s),
-                    post_cov_columns<float>(p, theta, Xs, m, idx, ncols, work, cols_out, s));
-  return wrap(rc, where);
+  return posterior_entry(p, "dgp_posterior_cov_columns", work, work_bytes, dgp_posterior_cov_columns_workspace_bytes(p, m, ncols), stream,
+                         [&](auto t, hipStream_t s) { return post_cov_columns<decltype(t)>(p, theta, Xs, m, idx, ncols, work, cols_out, s); });
 }
 
 }  // extern "C"

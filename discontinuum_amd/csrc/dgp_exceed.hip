@@ -290,22 +290,10 @@ static int exceedance_moments(const T* cov, long m, int B, const T* mu, const do
   const long M = round_up(m, DGP_TILE_HOST);
   const long ws = ex_site_doubles(M, P, L);
   exceedance_prepare<T>(cov, M * M, M + 1, m, B, mu, thresh, L, w, group, P, ev, work, s);
-  for (int l0 = 0; l0 < L;) {  // chunks of 8, then 4, 2, 1 levels: a function of L alone
-    const int left = L - l0;
-    if (left >= 8) {
-      ex_chunk<T, 8>(cov, M, (int)m, B, P, L, l0, group, work, ws, mean_out, cov_out, s);
-      l0 += 8;
-    } else if (left >= 4) {
-      ex_chunk<T, 4>(cov, M, (int)m, B, P, L, l0, group, work, ws, mean_out, cov_out, s);
-      l0 += 4;
-    } else if (left >= 2) {
-      ex_chunk<T, 2>(cov, M, (int)m, B, P, L, l0, group, work, ws, mean_out, cov_out, s);
-      l0 += 2;
-    } else {
-      ex_chunk<T, 1>(cov, M, (int)m, B, P, L, l0, group, work, ws, mean_out, cov_out, s);
-      l0 += 1;
-    }
-  }
+  level_chunks(L, [&](int l0, auto width) {
+    ex_chunk<T, decltype(width)::value>(cov, M, (int)m, B, P, L, l0, group, work, ws, mean_out, cov_out, s);
+    return 0;
+  });
   return (int)hipGetLastError();
 }
 

@@ -1,11 +1,8 @@
 // dgp_exceed_stream.hip -- the moments of dgp_exceedance_moments straight from the held factorisation, with the posterior
 // covariance C = K(Xs, Xs) - V^T V produced R rows at a time and never stored whole (dgp_posterior_exceedance_moments).
 //
-// V = L^-1 K(X, Xs), the test points' SoA coordinates and the predicted variance are what the prediction's first stages leave in
-// the work area (as for dgp_posterior_period_moments).  Panel q holds the rows [q R, (q + 1) R) of C and the columns
-// 0 .. (q + 1) R - 1, in a buffer of R x M elements: gram_sym's tiles of K(Xs, Xs) followed by posterior_cov's trailing update,
-// both on the tile rows of the panel only -- the launches, the k order and hence (fp64) the bits of dgp_posterior_cov.  Every
-// unordered pair (i < j) lies in exactly one panel, j's.  Launches (gridDim.z = sites, one stream, no floating-point atomics):
+// The front end, the panels and their invariants are dgp_stream.h's.  Launches (gridDim.z = sites, one stream, no
+// floating-point atomics):
 //   init, prep   dgp_exceed.hip's, once; the diagonal is the predicted variance (sigma never comes from the panel)
 //   per chunk of levels (8 / 4 / 2 / 1, a function of L alone):
 //     zero       Y[l][i][h] = 0 for the levels of the chunk: the reduce pass finds numbers wherever it reads, whatever the work
@@ -21,7 +18,7 @@
 // Repeated calls are bitwise equal and a site's numbers do not depend on its batch; different R regroup the sums over j.
 // The quadrature never runs beside live MFMA accumulators: it reads C back from the panel (L2 / HBM, R M elements).
 #include "dgp_bvn.h"
-#include "dgp_plan.h"
+#include "dgp_stream.h"
 
 namespace dgp {
 
@@ -132,70 +129,37 @@ __global__ __launch_bounds__(256) void exs_pairs_kernel(const T* __restrict__ pa
 }
 
 template <typename T, int LC>
-int exs_chunk(int model, int d, const T* V, long N, long M, int m, int B, const T* Xst, const T* zero, long wbs, const double* theta,
-              long R, T* panel, long pstride, int P, int L, int l0, const int* group, double* work, long ws, double* mean_out,
-              double* cov_out, hipStream_t s, void* pre_scratch) {
+int exs_chunk(const Posterior<T>& ps, long R, T* panel, long pstride, int P, int L, int l0, const int* group, double* work, long ws,
+              double* mean_out, double* cov_out) {
+  const long M = ps.M;
+  const int B = ps.p->B;
+  hipStream_t s = ps.s;
   const long count = (long)LC * M * P;
   const long zb = (count + 255) / 256;
   exs_zero_kernel<<<dim3((unsigned)(zb < 65536 ? zb : 65536), 1, (unsigned)B), 256, 0, s>>>(work, ws, M, P, L, LC);
-  Batch wb;
-  wb.B = B;
-  wb.ws = wbs;
-  for (long p0 = 0; p0 < M; p0 += R) {
-    const long p1 = p0 + R < M ? p0 + R : M;
-    int rc = gram_sym_panel<T>(model, d, Xst, M, m, theta, zero, panel, p0, p1, s, wb, pre_scratch, pstride, wbs);
-    if (rc) return rc;
-    if ((rc = posterior_cov_panel<T>(V, N, M, panel, p0, p1, pstride, s, B, wbs))) return rc;
-    exs_pairs_kernel<T, LC><<<dim3((unsigned)(p1 / EX_ROWS), (unsigned)P, (unsigned)B), 256, 0, s>>>(panel, pstride, M, m, P, L, l0,
+  const int rc = ps.panels(R, panel, pstride, [&](long p0, long p1) {
+    exs_pairs_kernel<T, LC><<<dim3((unsigned)(p1 / EX_ROWS), (unsigned)P, (unsigned)B), 256, 0, s>>>(panel, pstride, M, (int)ps.m, P, L, l0,
                                                                                                    (int)p0, (int)p1, group, work, ws);
-  }
+  });
+  if (rc) return rc;
   exceedance_reduce(M, B, P, L, l0, LC, work, mean_out, cov_out, s);
   return (int)hipGetLastError();
 }
 
 }  // namespace
 
-static long exceedance_panel_rows(long m, long R) {
-  const long M = round_up(m, DGP_TILE_HOST);
-  return R < M ? R : M;
-}
-
-// The exceedance moments with C = K(Xs, Xs) - V^T V produced R rows at a time (R a multiple of 128; the pass uses
-// exceedance_panel_rows(m, R) = min(R, M)) into `panel` (R x M elements per site, site stride pstride) and never stored whole.
-// V, Xst, var (overwritten), wbs, pre_scratch as the prediction leaves them; `work` as for exceedance_moments
+// The exceedance moments with C produced R rows at a time into `panel` (site stride pstride) and never stored whole; every
+// chunk of levels produces all panels again.  `work` as for exceedance_moments
 template <typename T>
-static int posterior_exceedance_moments(int model, int d, const T* V, long N, long m, int B, const T* Xst, T* var, long wbs,
-                                        const double* theta, const T* mu, const double* thresh, int L, const double* w,
+static int posterior_exceedance_moments(const Posterior<T>& ps, const T* mu, const double* thresh, int L, const double* w,
                                         const int* group, int P, const T* ev, long R, T* panel, long pstride, double* work,
-                                        double* mean_out, double* cov_out, hipStream_t s, void* pre_scratch) {
-  const long M = round_up(m, DGP_TILE_HOST);
-  const long ws = (long)(exceedance_moments_workspace_bytes(m, P, L, 1) / sizeof(double));
-  R = exceedance_panel_rows(m, R);
-  exceedance_prepare<T>(var, wbs, 1, m, B, mu, thresh, L, w, group, P, ev, work, s);
-  // the variances are read: their place now holds the zero "noise" of K(Xs, Xs), as for dgp_posterior_cov
-  hipError_t he = hipMemset2DAsync(var, sizeof(T) * (size_t)(wbs > 0 ? wbs : M), 0, sizeof(T) * M, (size_t)B, s);
-  if (he != hipSuccess) return (int)he;
-  int rc = 0;
-  for (int l0 = 0; l0 < L && !rc;) {  // chunks of 8, then 4, 2, 1 levels: a function of L alone
-    const int left = L - l0;
-    if (left >= 8) {
-      rc = exs_chunk<T, 8>(model, d, V, N, M, (int)m, B, Xst, var, wbs, theta, R, panel, pstride, P, L, l0, group, work, ws, mean_out,
-                           cov_out, s, pre_scratch);
-      l0 += 8;
-    } else if (left >= 4) {
-      rc = exs_chunk<T, 4>(model, d, V, N, M, (int)m, B, Xst, var, wbs, theta, R, panel, pstride, P, L, l0, group, work, ws, mean_out,
-                           cov_out, s, pre_scratch);
-      l0 += 4;
-    } else if (left >= 2) {
-      rc = exs_chunk<T, 2>(model, d, V, N, M, (int)m, B, Xst, var, wbs, theta, R, panel, pstride, P, L, l0, group, work, ws, mean_out,
-                           cov_out, s, pre_scratch);
-      l0 += 2;
-    } else {
-      rc = exs_chunk<T, 1>(model, d, V, N, M, (int)m, B, Xst, var, wbs, theta, R, panel, pstride, P, L, l0, group, work, ws, mean_out,
-                           cov_out, s, pre_scratch);
-      l0 += 1;
-    }
-  }
+                                        double* mean_out, double* cov_out) {
+  const long ws = (long)(exceedance_moments_workspace_bytes(ps.m, P, L, 1) / sizeof(double));
+  exceedance_prepare<T>(ps.var, ps.wbs, 1, ps.m, ps.p->B, mu, thresh, L, w, group, P, ev, work, ps.s);
+  if (int rc = ps.zero_noise()) return rc;
+  const int rc = level_chunks(L, [&](int l0, auto width) {
+    return exs_chunk<T, decltype(width)::value>(ps, R, panel, pstride, P, L, l0, group, work, ws, mean_out, cov_out);
+  });
   return rc ? rc : (int)hipGetLastError();
 }
 
@@ -203,54 +167,45 @@ static int posterior_exceedance_moments(int model, int d, const T* V, long N, lo
 
 using namespace dgp;
 
-// streamed exceedance moments: the prediction's work area, one covariance panel of R x M elements per site, then the moment
-// pass's work area
+// streamed exceedance moments: dgp_stream.h's areas with one covariance panel of R x M elements per site, then the moment pass's
+// work area
 static size_t exceed_panel_bytes(const dgp_plan* p, int64_t m, int panel_rows) {
-  return Carve::up(p->elem * (size_t)exceedance_panel_rows((long)m, panel_rows) * (size_t)round_up(m, DGP_TILE_HOST));
+  return panel_bytes(p, m, panel_rows, round_up(m, DGP_TILE_HOST));
 }
 template <typename T>
 static int post_exceed(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const void* mu, const double* thresh, int L,
                        const double* w, const int32_t* group, int P, const void* ev, int panel_rows, void* work, double* mean_out,
                        double* cov_out, hipStream_t s) {
-  const size_t pb = exceed_panel_bytes(p, m, panel_rows);
-  T* panel = (T*)((char*)work + predict_layout(p, m).total * (size_t)p->B);
-  double* ex = (double*)((char*)panel + pb * (size_t)p->B);
-  T *V, *Xst, *vpad;
-  long wbs;
-  // the latent mean the prediction also writes (B x m elements) lands in the moment pass's area, which its first launches reset
-  int rc = predict_common<T>(p, theta, Xs, m, work, ex, &V, &Xst, &vpad, &wbs, s);
-  if (rc) return rc;
-  return posterior_exceedance_moments<T>(p->model, p->d, V, p->N, (long)m, p->B, Xst, vpad, wbs, theta, (const T*)mu, thresh, L, w, group,
-                                         P, (const T*)ev, panel_rows, panel, (long)(pb / sizeof(T)), ex, mean_out, cov_out, s, p->pre);
+  const PosteriorAreas<T> A = posterior_areas<T>(p, m, work, exceed_panel_bytes(p, m, panel_rows));
+  Posterior<T> ps;
+  if (int rc = ps.fill(p, theta, Xs, m, work, A.own, s)) return rc;
+  return posterior_exceedance_moments<T>(ps, (const T*)mu, thresh, L, w, group, P, (const T*)ev, panel_rows, A.panel, A.pstride,
+                                         (double*)A.own, mean_out, cov_out);
 }
 
 extern "C" {
 
 size_t dgp_posterior_exceedance_moments_workspace_bytes(const dgp_plan* p, int64_t m, int ngroups, int nlevels, int panel_rows) {
-  if (!p || !ex_sizes_ok(m, ngroups, nlevels, p->B) || panel_rows <= 0 || panel_rows % DGP_TILE_HOST != 0) return 0;
-  return (predict_layout(p, m).total + exceed_panel_bytes(p, m, panel_rows)) * (size_t)p->B +
-         exceedance_moments_workspace_bytes(m, ngroups, nlevels, p->B);
+  if (!p || !ex_sizes_ok(m, ngroups, nlevels, p->B) || !panel_rows_ok(panel_rows)) return 0;
+  return posterior_head_bytes(p, m, exceed_panel_bytes(p, m, panel_rows)) + exceedance_moments_workspace_bytes(m, ngroups, nlevels, p->B);
 }
 
 int dgp_posterior_exceedance_moments(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const void* mu, const double* thresh,
                                      int nlevels, const double* w, const int32_t* group, int ngroups, const void* extra_var,
                                      int panel_rows, void* work, size_t work_bytes, double* mean_out, double* cov_out, void* stream) {
-  const char* where = "dgp_posterior_exceedance_moments";
   if (!p) return fail(DGP_E_ARG, "null plan");
   if (!theta || !Xs || !mu || !thresh || !w || !group || !mean_out || !cov_out)
     return fail(DGP_E_ARG, "dgp_posterior_exceedance_moments: null argument");
   if (!ex_sizes_ok(m, ngroups, nlevels, p->B))
     return fail(DGP_E_ARG, "dgp_posterior_exceedance_moments: bad size (1 <= m <= 2^20, 1 <= ngroups <= 65535, 1 <= nlevels <= 64)");
-  if (panel_rows <= 0 || panel_rows % DGP_TILE_HOST != 0)
+  if (!panel_rows_ok(panel_rows))
     return fail(DGP_E_ARG, "dgp_posterior_exceedance_moments: panel_rows must be a positive multiple of 128");
-  if (int rc = need_factor(p, where, "call dgp_factorize or dgp_fit_step")) return rc;
-  DGP_CHECK_PLAN(p);
-  hipStream_t s = (hipStream_t)stream;
-  int rc = need_work(work, work_bytes, dgp_posterior_exceedance_moments_workspace_bytes(p, m, ngroups, nlevels, panel_rows), where);
-  if (rc || (rc = factor_ok(p, s, where))) return rc;
-  rc = DGP_BY_DTYPE(p, post_exceed<double>(p, theta, Xs, m, mu, thresh, nlevels, w, group, ngroups, extra_var, panel_rows, work, mean_out, cov_out, s),
-                    post_exceed<float>(p, theta, Xs, m, mu, thresh, nlevels, w, group, ngroups, extra_var, panel_rows, work, mean_out, cov_out, s));
-  return wrap(rc, where);
+  return posterior_entry(p, "dgp_posterior_exceedance_moments", work, work_bytes,
+                         dgp_posterior_exceedance_moments_workspace_bytes(p, m, ngroups, nlevels, panel_rows), stream,
+                         [&](auto t, hipStream_t s) {
+                           return post_exceed<decltype(t)>(p, theta, Xs, m, mu, thresh, nlevels, w, group, ngroups, extra_var, panel_rows, work,
+                                                           mean_out, cov_out, s);
+                         });
 }
 
 }  // extern "C"

@@ -1,11 +1,8 @@
 // dgp_excess_stream.hip -- the moments of dgp_excess_moments straight from the held factorisation, with the posterior covariance
 // C = K(Xs, Xs) - V^T V produced R rows at a time and never stored whole (dgp_posterior_excess_moments).
 //
-// The front end and the panels are dgp_exceed_stream.hip's: V = L^-1 K(X, Xs), the test points' SoA coordinates and the
-// predicted variance are what the prediction's first stages leave in the work area; panel q holds the rows [q R, (q + 1) R) of C
-// and the columns 0 .. (q + 1) R - 1 in a buffer of R x M elements, from gram_sym's tiles followed by posterior_cov's trailing
-// update on the tile rows of the panel only.  Every unordered pair (i < j) lies in exactly one panel, j's.  Launches
-// (gridDim.z = sites, one stream, no floating-point atomics):
+// The front end, the panels and their invariants are dgp_stream.h's.  Launches (gridDim.z = sites, one stream, no
+// floating-point atomics):
 //   init, prep   dgp_excess.hip's, once; the diagonal is the predicted variance (sigma never comes from the panel)
 //   per group of up to 8 levels (a function of L alone):
 //     zero       Y[l][i][h] = 0 for the levels of the group: the reduce pass finds numbers wherever it reads, whatever the work
@@ -21,7 +18,7 @@
 //     reduce     dgp_excess.hip's, on the group's levels of Y
 // Repeated calls are bitwise equal and a site's numbers do not depend on its batch; different R regroup the sums over j.
 #include "dgp_excess.h"
-#include "dgp_plan.h"
+#include "dgp_stream.h"
 
 namespace dgp {
 
@@ -118,20 +115,15 @@ __global__ __launch_bounds__(256) void xss_pairs_kernel(const T* __restrict__ pa
 
 // the levels g0 .. g0 + GL (GL <= XS_GROUP) of the call: every panel once, the 2-level and 1-level pair launches against it
 template <typename T>
-int xss_group(int model, int d, const T* V, long N, long M, int m, int B, const T* Xst, const T* zero, long wbs, const double* theta,
-              long R, T* panel, long pstride, int P, int L, int g0, int GL, const double* scale2, const int* group, double sg,
-              double* work, long ws, double* mean_out, double* cov_out, double* total_out, hipStream_t s, void* pre_scratch) {
+int xss_group(const Posterior<T>& ps, long R, T* panel, long pstride, int P, int L, int g0, int GL, const double* scale2, const int* group,
+              double sg, double* work, long ws, double* mean_out, double* cov_out, double* total_out) {
+  const long M = ps.M;
+  const int B = ps.p->B, m = (int)ps.m;
+  hipStream_t s = ps.s;
   const long count = (long)GL * M * P;
   const long zb = (count + 255) / 256;
   xss_zero_kernel<<<dim3((unsigned)(zb < 65536 ? zb : 65536), 1, (unsigned)B), 256, 0, s>>>(work, ws, M, P, L, GL);
-  Batch wb;
-  wb.B = B;
-  wb.ws = wbs;
-  for (long p0 = 0; p0 < M; p0 += R) {
-    const long p1 = p0 + R < M ? p0 + R : M;
-    int rc = gram_sym_panel<T>(model, d, Xst, M, m, theta, zero, panel, p0, p1, s, wb, pre_scratch, pstride, wbs);
-    if (rc) return rc;
-    if ((rc = posterior_cov_panel<T>(V, N, M, panel, p0, p1, pstride, s, B, wbs))) return rc;
+  const int rc = ps.panels(R, panel, pstride, [&](long p0, long p1) {
     const dim3 grid((unsigned)(p1 / EX_ROWS), (unsigned)P, (unsigned)B);
     for (int y0 = 0; y0 < GL;) {
       if (GL - y0 >= 2) {
@@ -142,39 +134,28 @@ int xss_group(int model, int d, const T* V, long N, long M, int m, int B, const 
         y0 += 1;
       }
     }
-  }
+  });
+  if (rc) return rc;
   excess_reduce(M, B, P, L, g0, GL, XS_GROUP, work, mean_out, cov_out, total_out, s);
   return (int)hipGetLastError();
 }
 
 }  // namespace
 
-static long excess_panel_rows(long m, long R) {
-  const long M = round_up(m, DGP_TILE_HOST);
-  return R < M ? R : M;
-}
-
-// The excess moments with C = K(Xs, Xs) - V^T V produced R rows at a time (R a multiple of 128; the pass uses
-// excess_panel_rows(m, R) = min(R, M)) into `panel` (R x M elements per site, site stride pstride) and never stored whole.
-// V, Xst, var (overwritten), wbs, pre_scratch as the prediction leaves them; `work`: excess_moments_workspace_bytes with XS_GROUP
+// The excess moments with C produced R rows at a time into `panel` (site stride pstride) and never stored whole; every group of
+// levels produces all panels once.  `work`: excess_moments_workspace_bytes with XS_GROUP
 template <typename T>
-static int posterior_excess_moments(int model, int d, const T* V, long N, long m, int B, const T* Xst, T* var, long wbs,
-                                    const double* theta, const T* mu, const double* scale2, const double* thresh, int L,
+static int posterior_excess_moments(const Posterior<T>& ps, const T* mu, const double* scale2, const double* thresh, int L,
                                     const double* w, const int* group, int P, const T* ev, int above, long R, T* panel, long pstride,
-                                    double* work, double* mean_out, double* cov_out, double* total_out, hipStream_t s,
-                                    void* pre_scratch) {
-  const long M = round_up(m, DGP_TILE_HOST);
-  const long ws = xs_site_doubles(M, P, L, XS_GROUP);
+                                    double* work, double* mean_out, double* cov_out, double* total_out) {
+  const long ws = xs_site_doubles(ps.M, P, L, XS_GROUP);
   const double sg = above ? 1.0 : -1.0;
-  R = excess_panel_rows(m, R);
-  excess_prepare<T>(var, wbs, 1, m, B, mu, scale2, thresh, L, w, group, P, ev, sg, XS_GROUP, work, s);
-  // the variances are read: their place now holds the zero "noise" of K(Xs, Xs), as for dgp_posterior_cov
-  hipError_t he = hipMemset2DAsync(var, sizeof(T) * (size_t)(wbs > 0 ? wbs : M), 0, sizeof(T) * M, (size_t)B, s);
-  if (he != hipSuccess) return (int)he;
+  excess_prepare<T>(ps.var, ps.wbs, 1, ps.m, ps.p->B, mu, scale2, thresh, L, w, group, P, ev, sg, XS_GROUP, work, ps.s);
+  if (int rc = ps.zero_noise()) return rc;
   int rc = 0;
   for (int g0 = 0; g0 < L && !rc; g0 += XS_GROUP)
-    rc = xss_group<T>(model, d, V, N, M, (int)m, B, Xst, var, wbs, theta, R, panel, pstride, P, L, g0,
-                      L - g0 < XS_GROUP ? L - g0 : XS_GROUP, scale2, group, sg, work, ws, mean_out, cov_out, total_out, s, pre_scratch);
+    rc = xss_group<T>(ps, R, panel, pstride, P, L, g0, L - g0 < XS_GROUP ? L - g0 : XS_GROUP, scale2, group, sg, work, ws, mean_out,
+                      cov_out, total_out);
   return rc ? rc : (int)hipGetLastError();
 }
 
@@ -182,33 +163,27 @@ static int posterior_excess_moments(int model, int d, const T* V, long N, long m
 
 using namespace dgp;
 
-// streamed excess moments: the prediction's work area, one covariance panel of R x M elements per site, then the moment pass's
+// streamed excess moments: dgp_stream.h's areas with one covariance panel of R x M elements per site, then the moment pass's
 // work area
 static size_t excess_panel_bytes(const dgp_plan* p, int64_t m, int panel_rows) {
-  return Carve::up(p->elem * (size_t)excess_panel_rows((long)m, panel_rows) * (size_t)round_up(m, DGP_TILE_HOST));
+  return panel_bytes(p, m, panel_rows, round_up(m, DGP_TILE_HOST));
 }
 template <typename T>
 static int post_excess(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const void* mu, const double* scale2,
                        const double* thresh, int L, const double* w, const int32_t* group, int P, const void* ev, int above,
                        int panel_rows, void* work, double* mean_out, double* cov_out, double* total_out, hipStream_t s) {
-  const size_t pb = excess_panel_bytes(p, m, panel_rows);
-  T* panel = (T*)((char*)work + predict_layout(p, m).total * (size_t)p->B);
-  double* xs = (double*)((char*)panel + pb * (size_t)p->B);
-  T *V, *Xst, *vpad;
-  long wbs;
-  // the latent mean the prediction also writes (B x m elements) lands in the moment pass's area, which its first launches reset
-  int rc = predict_common<T>(p, theta, Xs, m, work, xs, &V, &Xst, &vpad, &wbs, s);
-  if (rc) return rc;
-  return posterior_excess_moments<T>(p->model, p->d, V, p->N, (long)m, p->B, Xst, vpad, wbs, theta, (const T*)mu, scale2, thresh, L, w,
-                                     group, P, (const T*)ev, above, panel_rows, panel, (long)(pb / sizeof(T)), xs, mean_out, cov_out,
-                                     total_out, s, p->pre);
+  const PosteriorAreas<T> A = posterior_areas<T>(p, m, work, excess_panel_bytes(p, m, panel_rows));
+  Posterior<T> ps;
+  if (int rc = ps.fill(p, theta, Xs, m, work, A.own, s)) return rc;
+  return posterior_excess_moments<T>(ps, (const T*)mu, scale2, thresh, L, w, group, P, (const T*)ev, above, panel_rows, A.panel, A.pstride,
+                                     (double*)A.own, mean_out, cov_out, total_out);
 }
 
 extern "C" {
 
 size_t dgp_posterior_excess_moments_workspace_bytes(const dgp_plan* p, int64_t m, int ngroups, int nlevels, int panel_rows) {
-  if (!p || !ex_sizes_ok(m, ngroups, nlevels, p->B) || panel_rows <= 0 || panel_rows % DGP_TILE_HOST != 0) return 0;
-  return (predict_layout(p, m).total + excess_panel_bytes(p, m, panel_rows)) * (size_t)p->B +
+  if (!p || !ex_sizes_ok(m, ngroups, nlevels, p->B) || !panel_rows_ok(panel_rows)) return 0;
+  return posterior_head_bytes(p, m, excess_panel_bytes(p, m, panel_rows)) +
          excess_moments_workspace_bytes(m, ngroups, nlevels, p->B, XS_GROUP);
 }
 
@@ -216,23 +191,20 @@ int dgp_posterior_excess_moments(dgp_plan* p, const double* theta, const void* X
                                  const double* thresh, int nlevels, const double* w, const int32_t* group, int ngroups,
                                  const void* extra_var, int above, int panel_rows, void* work, size_t work_bytes, double* mean_out,
                                  double* cov_out, double* total_out, void* stream) {
-  const char* where = "dgp_posterior_excess_moments";
   if (!p) return fail(DGP_E_ARG, "null plan");
   if (!theta || !Xs || !mu || !scale2 || !thresh || !w || !group || !mean_out || !cov_out || !total_out)
     return fail(DGP_E_ARG, "dgp_posterior_excess_moments: null argument");
   if (!ex_sizes_ok(m, ngroups, nlevels, p->B))
     return fail(DGP_E_ARG, "dgp_posterior_excess_moments: bad size (1 <= m <= 2^20, 1 <= ngroups <= 65535, 1 <= nlevels <= 64)");
-  if (panel_rows <= 0 || panel_rows % DGP_TILE_HOST != 0)
+  if (!panel_rows_ok(panel_rows))
     return fail(DGP_E_ARG, "dgp_posterior_excess_moments: panel_rows must be a positive multiple of 128");
   if (above != 0 && above != 1) return fail(DGP_E_ARG, "dgp_posterior_excess_moments: above must be 0 (deficit) or 1 (excess)");
-  if (int rc = need_factor(p, where, "call dgp_factorize or dgp_fit_step")) return rc;
-  DGP_CHECK_PLAN(p);
-  hipStream_t s = (hipStream_t)stream;
-  int rc = need_work(work, work_bytes, dgp_posterior_excess_moments_workspace_bytes(p, m, ngroups, nlevels, panel_rows), where);
-  if (rc || (rc = factor_ok(p, s, where))) return rc;
-  rc = DGP_BY_DTYPE(p, post_excess<double>(p, theta, Xs, m, mu, scale2, thresh, nlevels, w, group, ngroups, extra_var, above, panel_rows, work, mean_out, cov_out, total_out, s),
-                    post_excess<float>(p, theta, Xs, m, mu, scale2, thresh, nlevels, w, group, ngroups, extra_var, above, panel_rows, work, mean_out, cov_out, total_out, s));
-  return wrap(rc, where);
+  return posterior_entry(p, "dgp_posterior_excess_moments", work, work_bytes,
+                         dgp_posterior_excess_moments_workspace_bytes(p, m, ngroups, nlevels, panel_rows), stream,
+                         [&](auto t, hipStream_t s) {
+                           return post_excess<decltype(t)>(p, theta, Xs, m, mu, scale2, thresh, nlevels, w, group, ngroups, extra_var, above,
+                                                           panel_rows, work, mean_out, cov_out, total_out, s);
+                         });
 }
 
 }  // extern "C"

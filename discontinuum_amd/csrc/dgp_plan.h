@@ -4,6 +4,8 @@
 #pragma once
 #include <stdarg.h>
 
+#include <type_traits>
+
 #include "../../include/dgp_hip.h"
 #include "dgp_internal.h"
 
@@ -178,7 +180,7 @@ struct PreSlot {
 
 // ---- the prediction's work area, per site (a batched plan: one slice per site at the single-site size): the test points' SoA
 // copy, K(X, X*) and V = T K(X, X*) (N x M each), the prior variances, the padded mean and variance, the slab partials.
-// dgp_predict.hip fills it; the streamed moment passes (dgp_aggregate.hip, dgp_exceed_stream.hip) put their own areas behind it.
+// dgp_predict.hip fills it; the posterior entries put their own areas behind it (dgp_stream.h).
 struct PredictLayout {
   size_t Xst, Ks, V, kss, mean, var, part, total;
 };
@@ -206,6 +208,24 @@ inline bool cv_sizes_ok(const dgp_plan* p, int ngroups, int64_t max_group) {
 inline bool ex_sizes_ok(int64_t m, int ngroups, int nlevels, int batch) {
   return m > 0 && m <= (1 << 20) && ngroups > 0 && ngroups <= 65535 && nlevels >= 1 && nlevels <= 64 && batch > 0 &&
          batch <= DGP_MAX_BATCH_SITES;
+}
+// their L levels in chunks of 8, then 4, 2, 1 -- a function of L alone --: rc = f(l0, width), the width a compile-time constant
+// (std::integral_constant); stops at the first non-zero rc and returns it
+template <typename F>
+inline int level_chunks(int L, F f) {
+  int rc = 0, l0 = 0;
+  auto chunk = [&](auto width) {
+    rc = f(l0, width);
+    l0 += width;
+  };
+  while (l0 < L && !rc) {
+    const int left = L - l0;
+    if (left >= 8) chunk(std::integral_constant<int, 8>());
+    else if (left >= 4) chunk(std::integral_constant<int, 4>());
+    else if (left >= 2) chunk(std::integral_constant<int, 2>());
+    else chunk(std::integral_constant<int, 1>());
+  }
+  return rc;
 }
 
 // ---- what crosses units (explicitly instantiated for double and float where it is defined)

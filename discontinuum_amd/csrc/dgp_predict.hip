@@ -3,7 +3,7 @@
 // Batched plans run every launch once for all sites (gridDim.z = sites, like the fit step): the caller's work area holds one
 // slice per site (site stride = the single-site size).
 #include "dgp_common.h"
-#include "dgp_plan.h"
+#include "dgp_stream.h"
 
 using namespace dgp;
 
@@ -62,19 +62,12 @@ static int predict(dgp_plan* p, const double* theta, const void* Xs, int64_t m, 
 template <typename T>
 static int post_cov(dgp_plan* p, const double* theta, const void* Xs, int64_t m, void* work, void* mean, void* cov,
                     hipStream_t s) {
-  const long M = round_up(m, DGP_TILE_HOST);
-  T *V, *Xst, *vpad;
-  long wbs;
-  int rc = predict_common<T>(p, theta, Xs, m, work, mean, &V, &Xst, &vpad, &wbs, s);
-  if (rc) return rc;
-  // zero "noise" for K(Xs, Xs); a batched plan's sites keep theirs at the work area's site stride
-  hipError_t he = hipMemset2DAsync(vpad, sizeof(T) * (size_t)(wbs > 0 ? wbs : M), 0, sizeof(T) * M, (size_t)p->B, s);
-  if (he != hipSuccess) return (int)he;
-  Batch wb;
-  wb.B = p->B;
-  wb.ws = wbs;
-  if ((rc = gram_sym<T>(p->model, p->d, Xst, M, (int)m, theta, vpad, (T*)cov, s, wb, p->pre, nullptr, M * M, wbs, true))) return rc;
-  return posterior_cov<T>(V, p->N, M, (T*)cov, s, p->B, wbs);
+  Posterior<T> ps;
+  if (int rc = ps.fill(p, theta, Xs, m, work, mean, s)) return rc;
+  if (int rc = ps.zero_noise()) return rc;
+  const long M = ps.M;
+  if (int rc = gram_sym<T>(p->model, p->d, ps.Xst, M, (int)m, theta, ps.var, (T*)cov, s, ps.batch(), p->pre, nullptr, M * M, ps.wbs, true)) return rc;
+  return posterior_cov<T>(ps.V, p->N, M, (T*)cov, s, p->B, ps.wbs);
 }
 
 struct VjpLayout {

@@ -8,7 +8,8 @@
 // Every unordered pair (j >= l) lies in exactly one row panel, j's, so var_i d_i^2 is a sum of per-panel partials and needs no
 // halo, only one accumulator per window.  Two points share a window only if |j - l| < reach = max_i (hi_i - lo_i): the panel of
 // rows [p0, p1) needs the columns [c0, p1), c0 = 128 floor(max(0, p0 - reach + 1) / 128), and the band buffer holds exactly
-// those (first element C[p0][c0]).  On the streamed path C_jj is the PREDICTED variance, never a panel's diagonal.
+// those (first element C[p0][c0]).  The front end, the band loop and their invariants are dgp_stream.h's: on the streamed path
+// C_jj is the PREDICTED variance, never a panel's diagonal.
 // Launches (gridDim.z = sites, one stream, no floating-point atomics):
 //   points    one thread per point: b_j, the mean term, C_jj as a double; the site's reach flag is reset
 //   windows   one thread per window: the clamped ends, 1 / d_i, mean_i (ascending j), acc_i = 0, and the site's flag when a
@@ -27,7 +28,7 @@
 #include <vector>
 
 #include "dgp_common.h"
-#include "dgp_plan.h"
+#include "dgp_stream.h"
 
 namespace dgp {
 
@@ -257,43 +258,27 @@ int window_variances_mode(const T* cov, long m, int B, const T* mu, const double
 
 }  // namespace
 
-static long window_band_rows(long m, long R) {
-  const long M = round_up(m, DGP_TILE_HOST);
-  return R < M ? R : M;
-}
-static long window_band_ld(long m, long R, long reach) { return window_band_rows(m, R) + round_up(reach, DGP_TILE_HOST); }
-static long window_band_col0(long p0, long reach) {
-  const long c = p0 - reach + 1;
-  return c > 0 ? c / DGP_TILE_HOST * DGP_TILE_HOST : 0;
-}
+static long window_band_ld(long m, long R, long reach) { return panel_rows(m, R) + round_up(reach, DGP_TILE_HOST); }
 
-// The streamed pass.  V, Xst, var (read, then overwritten), wbs, pre_scratch as the prediction leaves them; `band`: R x ld
-// elements per site at site stride bstride; flags_host: B ints, valid after the stream has been synchronised by the caller
+// The streamed pass.  `band`: R x ld elements per site at site stride bstride; flags_host: B ints, valid after the stream has
+// been synchronised by the caller
 template <typename T, int MODE>
-static int posterior_window_variances(int model, int d, const T* V, long N, long m, int B, const T* Xst, T* var, long wbs,
-                                      const double* theta, const T* mu, const double* scale2, const double* a, const int* lo,
+static int posterior_window_variances(const Posterior<T>& ps, const T* mu, const double* scale2, const double* a, const int* lo,
                                       const int* hi, long q, long reach, long R, T* band, long bstride, void* area, double* mean_out,
-                                      double* var_out, hipStream_t s, void* pre_scratch, int* flags_host) {
-  const long M = round_up(m, DGP_TILE_HOST), Q = round_up(q, DGP_TILE_HOST);
-  const long ld = window_band_ld(m, R, reach);
-  R = window_band_rows(m, R);
+                                      double* var_out, int* flags_host) {
+  const long M = ps.M, Q = round_up(q, DGP_TILE_HOST);
+  const long ld = window_band_ld(ps.m, R, reach);
+  const int m = (int)ps.m, B = ps.p->B;
+  hipStream_t s = ps.s;
   const WsArea A = ws_area(area, M, Q, B);
-  ws_begin<T, MODE>(var, wbs, 1, M, (int)m, B, mu, scale2, a, lo, hi, Q, (int)q, reach, A, mean_out, s);
-  // the variances are read: their place now holds the zero "noise" of K(Xs, Xs), as for dgp_posterior_cov
-  hipError_t he = hipMemset2DAsync(var, sizeof(T) * (size_t)(wbs > 0 ? wbs : M), 0, sizeof(T) * M, (size_t)B, s);
-  if (he != hipSuccess) return (int)he;
-  Batch wb;
-  wb.B = B;
-  wb.ws = wbs;
-  for (long p0 = 0; p0 < M; p0 += R) {
-    const long p1 = p0 + R < M ? p0 + R : M, c0 = window_band_col0(p0, reach);
-    int rc = gram_sym_band<T>(model, d, Xst, M, (int)m, theta, var, band, p0, p1, c0, ld, s, wb, pre_scratch, bstride, wbs);
-    if (rc) return rc;
-    if ((rc = posterior_cov_band<T>(V, N, M, band, p0, p1, c0, ld, bstride, s, B, wbs))) return rc;
-    ws_contract<T, MODE>(band, bstride, ld, p0, p1, c0, scale2, M, (int)m, B, Q, (int)q, A, s);
-  }
+  ws_begin<T, MODE>(ps.var, ps.wbs, 1, M, m, B, mu, scale2, a, lo, hi, Q, (int)q, reach, A, mean_out, s);
+  if (int rc = ps.zero_noise()) return rc;
+  const int rc = ps.bands(R, reach, ld, band, bstride, [&](long p0, long p1, long c0) {
+    ws_contract<T, MODE>(band, bstride, ld, p0, p1, c0, scale2, M, m, B, Q, (int)q, A, s);
+  });
+  if (rc) return rc;
   ws_finish(M, B, Q, (int)q, A, var_out, s);
-  he = hipMemcpyAsync(flags_host, A.flags, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, s);
+  const hipError_t he = hipMemcpyAsync(flags_host, A.flags, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, s);
   if (he != hipSuccess) return (int)he;
   return (int)hipGetLastError();
 }
@@ -306,33 +291,26 @@ static bool wv_sizes_ok(int64_t m, int64_t q, int batch) {
   return m > 0 && m <= (1 << 20) && q > 0 && q <= (1 << 20) && batch > 0 && batch <= DGP_MAX_BATCH_SITES;
 }
 static bool wv_panel_ok(int64_t reach, int panel_rows) {
-  return reach >= 1 && reach <= (1 << 20) && panel_rows > 0 && panel_rows % DGP_TILE_HOST == 0;
+  return reach >= 1 && reach <= (1 << 20) && panel_rows_ok(panel_rows);
 }
 static size_t wv_band_bytes(const dgp_plan* p, int64_t m, int64_t reach, int panel_rows) {
-  return Carve::up(p->elem * (size_t)window_band_rows((long)m, panel_rows) * (size_t)window_band_ld((long)m, panel_rows, (long)reach));
+  return panel_bytes(p, m, panel_rows, window_band_ld((long)m, panel_rows, (long)reach));
 }
 
 template <typename T>
 static int post_window(dgp_plan* p, const double* theta, const void* Xs, int64_t m, const void* mu, const double* scale2, const double* a,
                        const int32_t* lo, const int32_t* hi, int64_t q, int mode, int64_t reach, int panel_rows, void* work,
                        double* mean_out, double* var_out, hipStream_t s, int* flags_host) {
-  const size_t bb = wv_band_bytes(p, m, reach, panel_rows);
-  T* band = (T*)((char*)work + predict_layout(p, m).total * (size_t)p->B);
-  void* area = (char*)band + bb * (size_t)p->B;
-  T *V, *Xst, *vpad;
-  long wbs;
-  // the latent mean the prediction also writes (B x m elements) lands in the window pass's area, which its first launch resets
-  int rc = predict_common<T>(p, theta, Xs, m, work, area, &V, &Xst, &vpad, &wbs, s);
-  if (rc) return rc;
-  return mode == 1 ? posterior_window_variances<T, 1>(p->model, p->d, V, p->N, (long)m, p->B, Xst, vpad, wbs, theta, (const T*)mu, scale2, a,
-                                                      lo, hi, (long)q, (long)reach, panel_rows, band, (long)(bb / sizeof(T)), area, mean_out,
-                                                      var_out, s, p->pre, flags_host)
-                   : posterior_window_variances<T, 0>(p->model, p->d, V, p->N, (long)m, p->B, Xst, vpad, wbs, theta, (const T*)mu, scale2, a,
-                                                      lo, hi, (long)q, (long)reach, panel_rows, band, (long)(bb / sizeof(T)), area, mean_out,
-                                                      var_out, s, p->pre, flags_host);
+  const PosteriorAreas<T> A = posterior_areas<T>(p, m, work, wv_band_bytes(p, m, reach, panel_rows));
+  Posterior<T> ps;
+  if (int rc = ps.fill(p, theta, Xs, m, work, A.own, s)) return rc;
+  return mode == 1 ? posterior_window_variances<T, 1>(ps, (const T*)mu, scale2, a, lo, hi, (long)q, (long)reach, panel_rows, A.panel, A.pstride,
+                                                      A.own, mean_out, var_out, flags_host)
+                   : posterior_window_variances<T, 0>(ps, (const T*)mu, scale2, a, lo, hi, (long)q, (long)reach, panel_rows, A.panel, A.pstride,
+                                                      A.own, mean_out, var_out, flags_host);
 }
 
-// a block of the covariance: the prediction's front end, then the band Gram and the band update straight into `out`
+// a block of the covariance: the front end, then one band straight into `out`; the latent mean goes behind the prediction's area
 static bool block_ok(int64_t m, int64_t row0, int64_t row1, int64_t col0) {
   if (m <= 0 || m > (1 << 20)) return false;
   const int64_t M = round_up(m, DGP_TILE_HOST);
@@ -342,45 +320,31 @@ static bool block_ok(int64_t m, int64_t row0, int64_t row1, int64_t col0) {
 template <typename T>
 static int post_block(dgp_plan* p, const double* theta, const void* Xs, int64_t m, long row0, long row1, long col0, void* work, void* out,
                       hipStream_t s) {
-  const long M = round_up(m, DGP_TILE_HOST), ld = row1 - col0;
-  void* mean = (char*)work + predict_layout(p, m).total * (size_t)p->B;  // the latent mean the prediction also writes
-  T *V, *Xst, *vpad;
-  long wbs;
-  int rc = predict_common<T>(p, theta, Xs, m, work, mean, &V, &Xst, &vpad, &wbs, s);
-  if (rc) return rc;
-  hipError_t he = hipMemset2DAsync(vpad, sizeof(T) * (size_t)(wbs > 0 ? wbs : M), 0, sizeof(T) * M, (size_t)p->B, s);
-  if (he != hipSuccess) return (int)he;
-  Batch wb;
-  wb.B = p->B;
-  wb.ws = wbs;
-  const long bstride = (row1 - row0) * ld;
-  if ((rc = gram_sym_band<T>(p->model, p->d, Xst, M, (int)m, theta, vpad, (T*)out, row0, row1, col0, ld, s, wb, p->pre, bstride, wbs))) return rc;
-  return posterior_cov_band<T>(V, p->N, M, (T*)out, row0, row1, col0, ld, bstride, s, p->B, wbs);
+  const long ld = row1 - col0;
+  Posterior<T> ps;
+  if (int rc = ps.fill(p, theta, Xs, m, work, posterior_areas<T>(p, m, work, 0).own, s)) return rc;
+  if (int rc = ps.zero_noise()) return rc;
+  return ps.band((T*)out, row0, row1, col0, ld, (row1 - row0) * ld);
 }
 
 extern "C" {
 
 size_t dgp_posterior_cov_block_workspace_bytes(const dgp_plan* p, int64_t m, int64_t row0, int64_t row1, int64_t col0) {
   if (!p || !block_ok(m, row0, row1, col0)) return 0;
-  return (predict_layout(p, m).total + Carve::up(p->elem * (size_t)m)) * (size_t)p->B;
+  return posterior_head_bytes(p, m, Carve::up(p->elem * (size_t)m));
 }
 
 int dgp_posterior_cov_block(dgp_plan* p, const double* theta, const void* Xs, int64_t m, int64_t row0, int64_t row1, int64_t col0,
                             void* work, size_t work_bytes, void* out, void* stream) {
-  const char* where = "dgp_posterior_cov_block";
   if (!p) return fail(DGP_E_ARG, "null plan");
   if (!theta || !Xs || !out) return fail(DGP_E_ARG, "dgp_posterior_cov_block: null argument");
   if (!block_ok(m, row0, row1, col0))
     return fail(DGP_E_ARG, "dgp_posterior_cov_block: bad block (1 <= m <= 2^20; row0, row1, col0 multiples of 128 with "
                            "0 <= col0 <= row0 < row1 <= padded m)");
-  if (int rc = need_factor(p, where, "call dgp_factorize or dgp_fit_step")) return rc;
-  DGP_CHECK_PLAN(p);
-  hipStream_t s = (hipStream_t)stream;
-  int rc = need_work(work, work_bytes, dgp_posterior_cov_block_workspace_bytes(p, m, row0, row1, col0), where);
-  if (rc || (rc = factor_ok(p, s, where))) return rc;
-  rc = DGP_BY_DTYPE(p, post_block<double>(p, theta, Xs, m, (long)row0, (long)row1, (long)col0, work, out, s),
-                    post_block<float>(p, theta, Xs, m, (long)row0, (long)row1, (long)col0, work, out, s));
-  return wrap(rc, where);
+  return posterior_entry(p, "dgp_posterior_cov_block", work, work_bytes, dgp_posterior_cov_block_workspace_bytes(p, m, row0, row1, col0), stream,
+                         [&](auto t, hipStream_t s) {
+                           return post_block<decltype(t)>(p, theta, Xs, m, (long)row0, (long)row1, (long)col0, work, out, s);
+                         });
 }
 
 size_t dgp_window_variances_workspace_bytes(int64_t m, int64_t q, int batch) {
@@ -413,7 +377,7 @@ int dgp_window_variances(int dtype, int mode, const void* cov, int64_t m, int ba
 
 size_t dgp_posterior_window_variances_workspace_bytes(const dgp_plan* p, int64_t m, int64_t q, int64_t reach, int panel_rows) {
   if (!p || !wv_sizes_ok(m, q, p->B) || !wv_panel_ok(reach, panel_rows)) return 0;
-  return (predict_layout(p, m).total + wv_band_bytes(p, m, reach, panel_rows)) * (size_t)p->B +
+  return posterior_head_bytes(p, m, wv_band_bytes(p, m, reach, panel_rows)) +
          ws_area_bytes(round_up(m, DGP_TILE_HOST), round_up(q, DGP_TILE_HOST), p->B);
 }
 
@@ -428,7 +392,7 @@ int dgp_posterior_window_variances(dgp_plan* p, const double* theta, const void*
   if (!wv_sizes_ok(m, q, p->B))
     return fail(DGP_E_ARG, "dgp_posterior_window_variances: bad size (1 <= m <= 2^20, 1 <= q <= 2^20)");
   if (reach < 1 || reach > (1 << 20)) return fail(DGP_E_ARG, "dgp_posterior_window_variances: reach must be in 1 .. 2^20");
-  if (panel_rows <= 0 || panel_rows % DGP_TILE_HOST != 0)
+  if (!panel_rows_ok(panel_rows))
     return fail(DGP_E_ARG, "dgp_posterior_window_variances: panel_rows must be a positive multiple of 128");
   if (int rc = need_factor(p, where, "call dgp_factorize or dgp_fit_step")) return rc;
   DGP_CHECK_PLAN(p);

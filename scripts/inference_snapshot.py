@@ -4,7 +4,8 @@ move a number: seeded inputs, one fit, and the outputs of ``fit_step``, ``factor
 ``mean_vjp``, ``predict_terms`` / ``predict_slopes`` (with and without ``return_cov``), ``posterior_cov``,
 ``posterior_period_moments``, ``period_moments``, ``period_third_moments`` (tile 0, 64, 128), ``exceedance_moments``,
 ``posterior_exceedance_moments``, ``sample_value``, ``posterior_sample_value``, ``posterior_cov_columns``,
-``lowrank_period_moments``, ``window_moments``, ``whiten`` and ``cross_validate``; for one site and the
+``lowrank_period_moments``, ``window_moments``, ``whiten`` and ``cross_validate``, the dense and streamed exceedance, excess and
+rolling-window passes with every chunk width of their level loops and ``posterior_cov_block`` (``streamed_products``); for one site and the
 ragged batch of three, ``fisher``, ``predict_sensitivity`` (also means only in chunks), ``deletion_influence``, ``loo_fit_step`` /
 ``loo_value``, ``bilinear``, ``laplace_factorize``, ``laplace_fit_step`` (with and without an interval row),
 ``laplace_cross_validate``, ``ep_fit_step`` cold and warm, ``ep_factorize``, ``ep_diag`` and the pointwise ``censored_terms`` /
@@ -109,6 +110,7 @@ def run_config(torch, GPPlan, backend, make_case, model, d, dtype, sizes, dev):
          plan.posterior_sample_value(theta, Xs, w, scale2, groups, GROUPS, obs_var=extra, rows=given, nterms=12, panel_rows=128))
     keep("posterior_cov_columns", plan.posterior_cov_columns(theta, Xs, torch.tensor([0, 127, 128, m - 1]).expand(lead + (4,))))
     keep("lowrank_period_moments", plan.lowrank_period_moments(given.to(dev), m, mu.double(), scale2, w, groups, GROUPS, backend.MODE_LOG))
+    streamed_products(torch, plan, backend, keep, stack, theta, Xs, cov, mu, extra, w, groups, scale2, lo, hi, dtype, make_case)
     keep("cross_validate", plan.cross_validate(folds))
     if B <= 3:  # the products whose host glue lives beside their kernels: one site and the ragged batch of three
         extra_products(torch, plan, backend, keep, theta, X, r, noise, Xs, w, folds, groups, extra, dtype, dev)
@@ -116,6 +118,42 @@ def run_config(torch, GPPlan, backend, make_case, model, d, dtype, sizes, dev):
         single_site_products(torch, plan, keep, theta, r, noise, Xs, dev)
     torch.cuda.synchronize(dev)
     return out
+
+
+def streamed_products(torch, plan, backend, keep, stack, theta, Xs, cov, mu, extra, w, groups, scale2, lo, hi, dtype, make_case):
+    """The dense and streamed passes with every chunk width of their level loops -- the exceedance pair with 15 levels (chunks
+    of 8, 4, 2, 1), the excess pair with 11 (a group of 8, then 3 as 2 + 1), the streamed ones with two panels of 128 rows --,
+    ``window_variances`` dense and streamed in both modes, and blocks of the covariance; then the band products on a second
+    set of 300 test points (M = 384) with windows of at most 7 points: the third panel's band starts at column 128."""
+    B, m = plan.batch, M_POINTS
+    lead = () if B == 1 else (B,)
+    g = torch.Generator().manual_seed(9)
+    t15, t11 = (stack([torch.randn(L, m, generator=g, dtype=torch.float64) for _ in range(B)], torch.float64) for L in (15, 11))
+    keep("exceedance_moments_L15", plan.exceedance_moments(cov, m, mu, t15, w, groups, GROUPS, extra_var=extra))
+    keep("posterior_exceedance_moments_L15",
+         plan.posterior_exceedance_moments(theta, Xs, mu, t15, w, groups, GROUPS, extra_var=extra, panel_rows=128))
+    for above in (True, False):
+        tag = "above" if above else "below"
+        keep(f"excess_moments_L11_{tag}", plan.excess_moments(cov, m, mu, scale2, t11, w, groups, GROUPS, above=above, extra_var=extra))
+        keep(f"posterior_excess_moments_L11_{tag}",
+             plan.posterior_excess_moments(theta, Xs, mu, scale2, t11, w, groups, GROUPS, above=above, extra_var=extra, panel_rows=128))
+    modes = (("linear", backend.MODE_LINEAR, None), ("log", backend.MODE_LOG, scale2))
+    for tag, mode, s2 in modes:
+        keep(f"window_variances_{tag}", plan.window_variances(cov, m, mu, lo, hi, a=w, mode=mode, scale2=s2))
+        keep(f"posterior_window_variances_{tag}",
+             plan.posterior_window_variances(theta, Xs, mu, lo, hi, a=w, mode=mode, scale2=s2, panel_rows=128))
+    keep("posterior_cov_block", torch.tril(plan.posterior_cov_block(theta, Xs, 128, 256, 0), diagonal=128))  # the defined part
+    m3 = 300
+    Xs3 = stack([make_case(plan.model, plan.d, m3, seed=70 + b)[0] for b in range(B)], dtype)
+    mu3 = stack([0.3 * torch.randn(m3, generator=g, dtype=torch.float64) for _ in range(B)], dtype)
+    w3 = stack([0.5 + torch.rand(m3, generator=g, dtype=torch.float64) for _ in range(B)], torch.float64)
+    i = torch.arange(m3)
+    lo3 = (i - 6).clamp_min(0).to(torch.int32).expand(lead + (m3,)).contiguous()  # trailing windows of 7 points
+    hi3 = (i + 1).to(torch.int32).expand(lead + (m3,)).contiguous()
+    for tag, mode, s2 in modes:
+        keep(f"posterior_window_variances_m300_{tag}",
+             plan.posterior_window_variances(theta, Xs3, mu3, lo3, hi3, a=w3, mode=mode, scale2=s2, panel_rows=128))
+    keep("posterior_cov_block_m300", torch.tril(plan.posterior_cov_block(theta, Xs3, 256, 384, 128), diagonal=128))
 
 
 def single_site_products(torch, plan, keep, theta, r, noise, Xs, dev):
