@@ -242,17 +242,18 @@ class GPPlan:
             self._call("dgp_set_inputs", _ptr(X))
         self._X = X  # keep alive until the async pack has certainly run
 
-    def _fit(self, name, theta, r, noise, ws_query=None, grads=True):
-        """The one shape of a fit step: ``name(plan, theta, r, noise[, work, bytes], out[, dr, dnoise], stream)`` ->
+    def _fit(self, name, theta, r, noise, ws_query=None, grads=True, extra=()):
+        """The one shape of a fit step: ``name(plan, theta, r, noise, *extra[, work, bytes], out[, dr, dnoise], stream)`` ->
         (out[32],) or (out[32], dr[n], dnoise[n]).  ``ws_query``: the size query of an entry that takes a work area (kept in
-        ``self._loo_ws``)."""
+        ``self._loo_ws``): a name, or (name, *sizes) when the query takes sizes."""
         self._check_vec(r, "r")
         self._check_vec(noise, "noise")
         th = self._theta(theta)
         with torch.cuda.device(self.device):
-            work = () if ws_query is None else self._sized_work("_loo_ws", name, ws_query)
+            query = (ws_query,) if isinstance(ws_query, str) else ws_query
+            work = () if query is None else self._sized_work("_loo_ws", name, *query)
             res = (self._empty(_lib.OUT_LEN),) + ((self._empty(self.n), self._empty(self.n)) if grads else ())
-            self._call(name, th, _ptr(r), _ptr(noise), *work, *map(_ptr, res))
+            self._call(name, th, _ptr(r), _ptr(noise), *extra, *work, *map(_ptr, res))
         return res
 
     def fit_step(self, theta, r: torch.Tensor, noise: torch.Tensor):
@@ -277,6 +278,47 @@ class GPPlan:
             work = self._sized_work("_loo_ws", "dgp_loo_value", "dgp_loo_value_workspace_bytes")
             out = self._empty(2, dtype=torch.float64)
             self._call("dgp_loo_value", *work, _ptr(out))
+        return out
+
+    # ------------------------------------------------------------------ leave-group-out training objective
+    def set_folds(self, groups):
+        """The folds of ``lgo_fit_step`` / ``lgo_value``: fold ids per observation as ``cross_validate`` takes them -- (n,),
+        or (batch, n) for a batched plan, integers >= 0, -1 = never held out; a site's folds may be empty.  Validated and
+        sorted on the host as there; the plan keeps ``order`` / ``start`` on the device, with ``ngroups`` and ``max_group``.
+        None clears them."""
+        if groups is None:
+            self._folds = None
+            return
+
+        def keep(order, start, ngroups, max_group):
+            dev = lambda t: t.contiguous().to(self.device)  # noqa: E731
+            return dev(order), dev(start), int(ngroups), int(max_group)
+
+        self._folds = cross_validate_folds(self, groups, keep)
+
+    def _lgo_folds(self, what):
+        folds = getattr(self, "_folds", None)
+        if folds is None:
+            raise ValueError(f"{what}: no folds in the plan (call set_folds first)")
+        order, start, ngroups, max_group = folds
+        return (_ptr(order), _ptr(start), ngroups, max_group), (ngroups, max_group)
+
+    def lgo_fit_step(self, theta, r: torch.Tensor, noise: torch.Tensor):
+        """The fit step of the leave-group-out predictive likelihood L_LGO = -sum of ``cross_validate``'s ``lpd`` on the
+        folds of ``set_folds``: -> (out, dr, dnoise) with exactly the shapes and slots of ``fit_step``, ``out[OUT_NLL]`` =
+        L_LGO and every gradient slot that of L_LGO; QUAD, LOGDET, INFO are the factorisation's.  The plan holds afterwards
+        what ``fit_step`` with the same arguments leaves.  float64 plans (include/dgp_hip_ext2.h ``dgp_lgo_fit_step``)."""
+        extra, sizes = self._lgo_folds("lgo_fit_step")
+        return self._fit("dgp_lgo_fit_step", theta, r, noise, ws_query=("dgp_lgo_workspace_bytes", *sizes), extra=extra)
+
+    def lgo_value(self):
+        """(L_LGO, info) -- (batch, 2) for a batched plan -- as float64 device tensor, from the factorisation the plan holds
+        when the last step left K^^-1 in it, on the folds of ``set_folds``."""
+        extra, sizes = self._lgo_folds("lgo_value")
+        with torch.cuda.device(self.device):
+            work = self._sized_work("_loo_ws", "dgp_lgo_value", "dgp_lgo_value_workspace_bytes", *sizes)
+            out = self._empty(2, dtype=torch.float64)
+            self._call("dgp_lgo_value", *extra, *work, _ptr(out))
         return out
 
     # ------------------------------------------------------------------ censored observations (Laplace)

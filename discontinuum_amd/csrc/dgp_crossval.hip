@@ -91,7 +91,8 @@ __global__ __launch_bounds__(256) void cv_small_kernel(const T* __restrict__ Tm,
                                                        const T* __restrict__ alpha, const int* __restrict__ ns, int n,
                                                        const int* __restrict__ order, const int* __restrict__ start, int ngroups,
                                                        double* __restrict__ resid, double* __restrict__ var, double* __restrict__ lpd,
-                                                       int* __restrict__ info, double* __restrict__ minv, long ld) {
+                                                       int* __restrict__ info, double* __restrict__ minv, long ld,
+                                                       double* __restrict__ wblk, long wld, long wsite) {
   constexpr int LD = CV_SMALL + 1;
   __shared__ double sG[CV_SMALL * LD];  // G_B, then M (lower) with M^-1 transposed above the diagonal
   __shared__ double sP[16 * CV_SMALL];  // 16 rows of the group's columns of T
@@ -241,6 +242,16 @@ __global__ __launch_bounds__(256) void cv_small_kernel(const T* __restrict__ Tm,
     resid[sIdx[t]] = e;
   }
   __syncthreads();
+  if (wblk && b <= wld) {  // the tap: W_g = M^-T M^-1 + e e^T, full, k from the last row to the first that reaches (i, j)
+    double* out = wblk + (long)blockIdx.z * wsite + (long)s0 * wld + cv_wblock_shift(N, s0, b);
+    for (int e = t; e < b * b; e += 256) {
+      const int i = e / b, j = e % b, lo = min(i, j), hi = max(i, j);
+      double c = 0.0;
+      for (int k = b - 1; k > hi; --k) c += sG[lo * LD + k] * sG[hi * LD + k];
+      c += (lo == hi ? sD[hi] : sG[lo * LD + hi]) * sD[hi];
+      out[(long)i * wld + j] = c + sE[i] * sE[j];
+    }
+  }
   if (t == 0) {
     double q = 0.0;
     for (int j = 0; j < b; ++j) q += sA[j] * sE[j];
@@ -507,7 +518,9 @@ int cross_validate(const T* Tm, const T* S, const T* alpha, long N, int n, const
   }
   if (max_group <= CV_SMALL) {
     cv_small_kernel<T><<<dim3((unsigned)ngroups, 1, Bz), 256, 0, s>>>(Tm, S, N, bt.ws, alpha, bt.ns, n, order, start, ngroups, resid, var,
-                                                                      lpd, info, tap ? tap->minv : nullptr, tap ? tap->ld : 0);
+                                                                      lpd, info, tap ? tap->minv : nullptr, tap ? tap->ld : 0,
+                                                                      tap ? tap->wblk : nullptr, tap ? tap->wld : 0,
+                                                                      tap ? tap->wsite : 0);
     return (int)hipGetLastError();
   }
   const long M = cv_block_order(max_group);
@@ -544,7 +557,7 @@ int cross_validate(const T* Tm, const T* S, const T* alpha, long N, int n, const
     cv_lpd_kernel<<<dim3(1, 1, Z), 256, 0, s>>>(ck, sl, bt.ns, order, start, slots, lpd, info);
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     if (tap && tap->chunk) {  // the chunk's blocks are complete on the stream: the caller's passes on them, before the next chunk
-      const CvBlocks cb{slots + sl.Tm, slots + sl.e, sl.elems, M, g0, C};
+      const CvBlocks cb{slots + sl.Tm, slots + sl.e, sl.elems, M, g0, C, slots + sl.W};
       if ((rc = tap->chunk(tap->ctx, cb))) return rc;
     }
   }

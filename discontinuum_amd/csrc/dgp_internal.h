@@ -318,18 +318,24 @@ size_t cross_validate_workspace_bytes(long N, int B, int ngroups, long max_group
 // minv[(site ngroups + g) ld ld ...] (ld >= max_group; a failed fold writes nothing).  Larger groups (the block route): `chunk`
 // is called once per chunk of C folds g0 .. g0 + C - 1, after the chunk's launches are on the stream and before the next chunk
 // reuses the blocks; it enqueues its own work on the same stream and returns 0 or an error.  Neither changes what
-// cross_validate computes.
+// cross_validate computes.  For dgp_lgo.hip the LDS route also writes, when `wblk` is set, the fold's FULL weight block
+// W_g = G_B^-1 + e_B e_B^T (b x b, symmetric, leading dimension wld, cv_wblock_shift columns in) at wblk + site wsite + start[g] wld -- the folds of a site are
+// disjoint, so its blocks stack into at most n rows -- and the block route lends `scratch`, M x M per slot that nothing reads
+// any more, to the chunk's callback.
 struct CvBlocks {
   const double* minv;  // slot z = site C + c: M^-1 (M x M row-major, lower, identity pad) at minv + z stride
   const double* e;     // e_B = G_B^-1 alpha_B in the fold's own order (M entries) at e + z stride
   long stride, M;
   int g0, C;
+  double* scratch;     // M x M at scratch + z stride (the inverse's work block)
 };
 struct CvTap {
   double* minv = nullptr;
   long ld = 0;
   int (*chunk)(void* ctx, const CvBlocks& blocks) = nullptr;
   void* ctx = nullptr;
+  double* wblk = nullptr;
+  long wld = 0, wsite = 0;
 };
 int cross_validate_chunk_groups(long N, int B, int ngroups, long max_group);  // folds per chunk of the block route (0: another route)
 template <typename T>
@@ -346,6 +352,10 @@ __device__ __forceinline__ void cv_bounds(const int* __restrict__ start, int g, 
   b = min(e - a, cap);
 }
 __device__ __forceinline__ int cv_index(const int* __restrict__ order, int p, int n) { return min(max(order[p], 0), n - 1); }
+// dgp_lgo.hip reads a fold's weight block against the rows s0 .. of an N-row operand in k-tiles of 16.  A fold whose last tile
+// would pass row N is read from `shift` rows earlier instead, and its block is stored `shift` columns to the right (zeros in
+// front of it): shift + b <= round_up(b, 16), so the row still fits, and no operand row beyond N - 1 is ever read
+__device__ __forceinline__ int cv_wblock_shift(long N, int s0, int b) { return max(0, s0 + ((b + 15) & ~15) - (int)N); }
 #endif
 
 // ---- dgp_fisher.hip: the Fisher information's first pass alone (for dgp_sensitivity.hip): D_p = dK/dtheta_p for every p < ntheta,

@@ -23,24 +23,13 @@
 // the batch it is in.
 #include "../../include/dgp_hip.h"
 #include "dgp_gemm_dma.h"
+#include "dgp_loo.h"
 #include "dgp_plan.h"
 
 namespace dgp {
 
 #define LOO_LOG2PI 1.83787706640934548356
-#define LOO_PART 8  // doubles per workgroup of the block partials: [0] sum of the summands, [1] first bad row + 1 (0: none);
-                    // [2..5] sum b, sum b w0, sum b w1, sum dnoise
-
-// The work area holds one SLICE per site that mirrors the plan's site (same size, same offsets: F where the plan has A, G where it
-// has T, 2 M where it has S, a zero vector where it has alpha, the contraction's partials where it has its own -- gram_grad
-// addresses all of them at ONE site stride), then the sites' vectors, then the step's own result rows.  value_only: no slices.
-struct LooLayout {
-  size_t slice, F, G, M, zero, gpart;          // a site's slice and the byte offsets inside it
-  size_t w, c, b, negb, spart, part, vec;      // byte offsets inside a site's vectors, and their size
-  size_t vecs, out0, total;                    // byte offsets of the vectors and of the scratch result rows [B][DGP_OUT_LEN]
-  int nblk;                                    // workgroups per site of the row passes
-};
-static LooLayout loo_layout(const dgp_plan* p, bool value_only) {
+LooLayout loo_layout(const dgp_plan* p, bool value_only) {
   const Layout P = layout(p);
   const size_t N = (size_t)p->N, B = (size_t)p->B;
   LooLayout L;
@@ -280,30 +269,38 @@ static int loo_terms(const double* S, const double* alpha, long N, int n, char* 
   return (int)hipGetLastError();
 }
 
-static int loo_value(const double* S, const double* alpha, const int* info, long N, int n, char* work, const LooLayout& L, double* out2,
-              hipStream_t s, Batch bt) {
-  int rc;
-  if ((rc = loo_terms(S, alpha, N, n, work, L, s, bt))) return rc;
+int loo_finish_value(const int* info, char* work, const LooLayout& L, double* out2, hipStream_t s, const Batch& bt) {
   loo_finish_kernel<<<dim3(1, 1, (unsigned)bt.B), 256, 0, s>>>((const double*)(work + L.vecs + L.part), L.nblk,
                                                               (long)(L.vec / sizeof(double)), 0, 0, nullptr, info,
                                                               bt.ws * (long)sizeof(double) / (long)sizeof(int), out2);
   return (int)hipGetLastError();
 }
 
-static int loo_gradient(int model, int d, const double* Xt, const double* S, const double* alpha, long N, int n, const double* theta,
-                 const double* wts, char* work, const LooLayout& L, double* out, double* dr, double* dnoise, hipStream_t s, Batch bt,
-                 void* pre_scratch) {
+static int loo_value(const double* S, const double* alpha, const int* info, long N, int n, char* work, const LooLayout& L, double* out2,
+              hipStream_t s, Batch bt) {
+  int rc;
+  if ((rc = loo_terms(S, alpha, N, n, work, L, s, bt))) return rc;
+  return loo_finish_value(info, work, L, out2, s, bt);
+}
+
+int loo_mirror(const double* S, long N, const double* w2, char* work, const LooLayout& L, hipStream_t s, const Batch& bt) {
+  const long nb64 = N / 64;
+  loo_mirror_kernel<<<dim3((unsigned)(nb64 * (nb64 + 1) / 2), 1, (unsigned)bt.B), 256, 0, s>>>(
+      S, N, bt.ws, w2, (long)(L.vec / sizeof(double)), (double*)(work + L.F), (double*)(work + L.G));
+  return (int)hipGetLastError();
+}
+
+int loo_tail(int model, int d, const double* Xt, const double* S, const double* alpha, long N, int n, const double* theta,
+             const double* wts, char* work, const LooLayout& L, double* out, double* dr, double* dnoise, hipStream_t s, const Batch& bt,
+             void* pre_scratch) {
   const int nt = model_ntheta(model, d);
   if (nt < 0) return -2;
-  if ((size_t)bt.ws * sizeof(double) != L.slice) return (int)hipErrorInvalidValue;  // the work slices mirror the plan's site stride
   auto W = [&](size_t off) { return (double*)(work + off); };
   auto V = [&](size_t off) { return (double*)(work + L.vecs + off); };
   const long vs = (long)(L.vec / sizeof(double));
   const unsigned Bz = (unsigned)bt.B;
   int rc;
-  if ((rc = loo_terms(S, alpha, N, n, work, L, s, bt))) return rc;
   const long nb64 = N / 64;
-  loo_mirror_kernel<<<dim3((unsigned)(nb64 * (nb64 + 1) / 2), 1, Bz), 256, 0, s>>>(S, N, bt.ws, V(L.w), vs, W(L.F), W(L.G));
   const long nbk = N / DGP_TILE_HOST, tiles = nbk * (nbk + 1) / 2;
   if (tiles * bt.B <= bt.tuning().lauum64_max_tiles)  // fewer 128-tiles than fill the CUs: lauum's rule
     loo_sandwich_kernel<64><<<dim3((unsigned)(nb64 * (nb64 + 1) / 2), 1, Bz), 256, 0, s>>>(W(L.F), W(L.G), W(L.M), N, bt.ws);
@@ -325,6 +322,17 @@ static int loo_gradient(int model, int d, const double* Xt, const double* S, con
                                                                   vs);
   loo_finish_kernel<<<dim3(1, 1, Bz), 256, 0, s>>>(V(L.part), L.nblk, vs, nt, 1, (const double*)(work + L.out0), nullptr, 0, out);
   return (int)hipGetLastError();
+}
+
+static int loo_gradient(int model, int d, const double* Xt, const double* S, const double* alpha, long N, int n, const double* theta,
+                 const double* wts, char* work, const LooLayout& L, double* out, double* dr, double* dnoise, hipStream_t s, Batch bt,
+                 void* pre_scratch) {
+  if (model_ntheta(model, d) < 0) return -2;
+  if ((size_t)bt.ws * sizeof(double) != L.slice) return (int)hipErrorInvalidValue;  // the work slices mirror the plan's site stride
+  int rc;
+  if ((rc = loo_terms(S, alpha, N, n, work, L, s, bt))) return rc;
+  if ((rc = loo_mirror(S, N, (const double*)(work + L.vecs + L.w), work, L, s, bt))) return rc;
+  return loo_tail(model, d, Xt, S, alpha, N, n, theta, wts, work, L, out, dr, dnoise, s, bt, pre_scratch);
 }
 
 }  // namespace dgp

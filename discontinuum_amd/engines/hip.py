@@ -342,7 +342,8 @@ class MarginalHIP(BaseModel):
         self.laplace_status_ = None
         self.ep_status_ = None
         self._approximation = "laplace"
-        self.objective_ = "mll"  # the training objective of the last fit: "mll" or "loo"
+        self.objective_ = "mll"  # the training objective of the last fit: "mll", "loo" or "lgo"
+        self.objective_folds_ = None  # "lgo": the fold id of every training observation (-1 = never held out)
 
     # ------------------------------------------------------------------ device plumbing
     def _tensor(self, a):
@@ -359,6 +360,8 @@ class MarginalHIP(BaseModel):
         self._train_x = train_x.to(self.device, self.dtype).contiguous()
         self._train_y = train_y.to(self.device, self.dtype).contiguous()
         self._plan.set_inputs(self._train_x)
+        if getattr(self, "objective_", "mll") == "lgo":
+            self._plan.set_folds(torch.as_tensor(np.asarray(self.objective_folds_, dtype=np.int64)))
         self._factor_key = None
         self._pending_device = None
 
@@ -518,6 +521,8 @@ class MarginalHIP(BaseModel):
                              else torch.as_tensor(self._upper_host, dtype=torch.float64)),
             "approximation": getattr(self, "_approximation", "laplace"),
             **({} if getattr(self, "objective_", "mll") == "mll" else {"objective": self.objective_}),
+            **({} if getattr(self, "objective_", "mll") != "lgo" else
+               {"objective_folds": torch.as_tensor(np.asarray(self.objective_folds_, dtype=np.int64))}),
             "optimizer_state_dict": None, "optimizer_name": None, "optimizer_lr": None,
             "scheduler_state_dict": None, "scheduler_name": None,
         }
@@ -583,6 +588,8 @@ class MarginalHIP(BaseModel):
         if approximation is None:
             approximation = record.get("approximation") or "laplace"
         self.objective_ = objective_name(record.get("objective"))  # a checkpoint without the key was trained on "mll"
+        if self.objective_ == "lgo":
+            self.objective_folds_ = record["objective_folds"].numpy().astype(np.int64)
         y = self._set_censoring(censored, y.shape[0], target_upper, y, approximation)
         self._setup_device(x, y)
         self.is_fitted = True
@@ -611,7 +618,7 @@ class MarginalHIP(BaseModel):
     def fit(self, covariates, target, target_unc=None, iterations: int = 100, optimizer: str | None = None,
             learning_rate: float | None = None, early_stopping: bool = False, patience: int = 60,
             scheduler: bool = True, resume: bool = False, penalty_callback=None, penalty_weight: float = 0.0, censored=None,
-            target_upper=None, approximation="laplace", objective="mll"):
+            target_upper=None, approximation="laplace", objective="mll", folds=None):
         """Train the hyperparameters; arguments and behaviour as ``MarginalGPyTorch.fit``
         (engines/gpytorch.py:162-458): Adam (default lr 0.05) or AdamW, gradient clipping to norm 1, optional
         ReduceLROnPlateau, NaN iterations skipped (more than ten in a row raise), optional early stopping, resume from a
@@ -647,11 +654,24 @@ class MarginalHIP(BaseModel):
         likelihood (``dgp_loo_fit_step``; minus the ``elpd`` that ``cross_validate("loo")`` reports) -- the more robust choice
         when the noise is fixed rather than learned to fit.  Priors, constraints, clamps, the jitter retries, the optimiser, the
         scheduler, early stopping and the penalty are the same; ``objective_`` records the choice.  Together with ``censored``
-        it is refused: the pseudo-data of a censored fit are not samples, and leaving one out predicts nothing observed."""
+        it is refused: the pseudo-data of a censored fit are not samples, and leaving one out predicts nothing observed.
+        "lgo" minimises (L_LGO - log prior) / n with L_LGO = -sum_g log p(y_g | y_-g, theta) over the folds of ``folds``, the
+        exact leave-group-out predictive likelihood (``dgp_lgo_fit_step``; minus the ``elpd`` that ``cross_validate(folds)``
+        reports): the criterion for records sampled in clusters, whose neighbours a few hours away make leave-one-out
+        optimistic.  Folds of one give "loo", one fold of every row gives "mll".  Refused with ``censored`` like "loo".
+
+        ``folds``: with ``objective="lgo"`` only, and required there: any scheme ``validation.cv_folds`` accepts -- a resample
+        alias ("YE", "YE-SEP", "QE", "ME"), an int k, ``("random", k, seed)``, "loo" or explicit fold ids (-1 = never held
+        out) -- evaluated on the training times as ``cross_validate`` does.  ``objective_folds_`` keeps the fold ids; a resumed
+        fit states the keyword again."""
         approximation = _approximation_name(approximation)
         objective = objective_name(objective)
-        if objective == "loo" and censored is not None and np.asarray(getattr(censored, "values", censored)).any():
-            raise NotImplementedError('objective="loo" is not available together with censored observations: the pseudo-data of '
+        if objective == "lgo" and folds is None:
+            raise ValueError('objective="lgo" needs folds=<scheme>: what is held out together (see validation.cv_folds)')
+        if objective != "lgo" and folds is not None:
+            raise ValueError(f'folds belongs to objective="lgo", not to objective={objective!r}')
+        if objective in ("loo", "lgo") and censored is not None and np.asarray(getattr(censored, "values", censored)).any():
+            raise NotImplementedError(f'objective="{objective}" is not available together with censored observations: the pseudo-data of '
                                       "a censored fit are not samples, so their leave-one-out predictive likelihood is not the "
                                       "likelihood of anything observed (the reason influence() refuses them)")
         trained = bool(getattr(self, "model", None) is not None and getattr(self, "likelihood", None) is not None
@@ -673,10 +693,15 @@ class MarginalHIP(BaseModel):
             y = self._set_censoring(self._censor_host, y.shape[0], self._upper_host, y, approximation)
         elif self._censor is not None and self._censor.approximation != approximation:
             y = self._set_censoring(self._censor_host, y.shape[0], None, y, approximation)
-        if objective == "loo" and self._censor is not None:  # (the censoring a resumed fit or a checkpoint carries)
-            raise NotImplementedError('objective="loo" is not available together with censored observations: the pseudo-data of '
+        if objective in ("loo", "lgo") and self._censor is not None:  # (the censoring a resumed fit or a checkpoint carries)
+            raise NotImplementedError(f'objective="{objective}" is not available together with censored observations: the pseudo-data of '
                                       "a censored fit are not samples")
         self.objective_ = objective
+        self.objective_folds_ = None
+        if objective == "lgo":
+            from ..validation import cv_folds
+
+            self.objective_folds_ = cv_folds(np.asarray(self.dm.data.target.coords["time"].values), folds)[0]
         self._setup_device(x, y)
         if self._censor is not None:
             self._censor.f = None

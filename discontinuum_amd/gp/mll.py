@@ -189,11 +189,11 @@ def _with_jitter_retries(plan, first, again):
         raise
 
 
-OBJECTIVES = ("mll", "loo")
+OBJECTIVES = ("mll", "loo", "lgo")
 
 
 def objective_name(objective):
-    """``fit(objective=...)`` as "mll" (the default; None means the same) or "loo"."""
+    """``fit(objective=...)`` as "mll" (the default; None means the same), "loo" or "lgo"."""
     name = "mll" if objective is None else str(objective).lower()
     if name not in OBJECTIVES:
         raise ValueError(f"objective must be one of {OBJECTIVES}, got {objective!r}")
@@ -202,13 +202,16 @@ def objective_name(objective):
 
 def data_step(plan, objective="mll"):
     """The plan method that evaluates the data term of ``objective`` and its gradients into one result row: ``fit_step`` (the
-    marginal likelihood) or ``loo_fit_step`` (the leave-one-out predictive likelihood; same arguments, same row layout)."""
+    marginal likelihood), ``loo_fit_step`` (the leave-one-out predictive likelihood) or ``lgo_fit_step`` (the leave-group-out
+    one, on the folds the plan holds: ``set_folds``); same arguments, same row layout."""
+    if objective == "lgo":
+        return plan.lgo_fit_step
     return plan.loo_fit_step if objective == "loo" else plan.fit_step
 
 
 def exact_gp_nll(plan, theta, r, noise, pending=None, objective="mll"):
     """Differentiable data term with gpytorch's jitter-retry policy. Returns a 0-dim CPU float64 tensor."""
-    if objective == "loo":  # the same autograd function on the other step's (out, dr, dnoise)
+    if objective in ("loo", "lgo"):  # the same autograd function on the other step's (out, dr, dnoise)
         step = data_step(plan, objective)
         return _with_jitter_retries(plan, lambda: _ExactGPNLL.apply(plan, theta, r, noise, pending),
                                     lambda jitter: _ExactGPNLL.apply(plan, theta, r, noise + jitter,

@@ -439,13 +439,39 @@ class FitManyState:
             if k == "nan_run" and k not in kw:  # a state saved before the counter travelled: start it at zero
                 kw[k] = torch.zeros_like(kw["step"], dtype=torch.float64)
             setattr(self, k, kw[k])
+        # objective="lgo" only: the fold ids (B, n) int64 the run trained on (-1: never held out, and every unused tail), so that
+        # a resumed call need not state ``folds`` again; absent from ``as_dict()`` otherwise
+        self.folds = kw.get("folds")
 
     def as_dict(self):
-        return {k: getattr(self, k) for k in self.FIELDS}
+        d = {k: getattr(self, k) for k in self.FIELDS}
+        if self.folds is not None:
+            d["folds"] = self.folds
+        return d
 
     @classmethod
     def from_dict(cls, d):
-        return cls(**{k: d[k] for k in cls.FIELDS if k in d})
+        return cls(**{k: d[k] for k in cls.FIELDS + ("folds",) if k in d})
+
+
+def _site_fold_ids(models, folds, sizes, n, resume):
+    """The (B, n) int64 fold ids of an ``objective="lgo"`` run: ``folds`` is one ``validation.cv_folds`` scheme applied to every
+    site's own training times, or a list with one scheme per site; None takes the ids a resumed state carries."""
+    from .validation import cv_folds
+
+    B = len(models)
+    if folds is None:
+        ids = None if resume is None else getattr(resume, "folds", None)
+        if ids is None or tuple(ids.shape) != (B, n):
+            raise ValueError('fit_many: objective="lgo" needs folds=<scheme> (or a resumed state of the same sites that carries them)')
+        return ids.to(torch.int64).clone()
+    per_site = folds if isinstance(folds, list) else [folds] * B
+    if len(per_site) != B:
+        raise ValueError("fit_many: a list of folds needs one scheme per site")
+    ids = torch.full((B, n), -1, dtype=torch.int64)
+    for b, (m, scheme) in enumerate(zip(models, per_site)):
+        ids[b, : sizes[b]] = torch.as_tensor(cv_folds(np.asarray(m.dm.data.target.coords["time"].values), scheme)[0])
+    return ids
 
 
 def _fresh_seeded(m, tx, ty, tu, seed):
@@ -520,7 +546,7 @@ def fit_many(models, datasets, iterations: int = 100, learning_rate: float = 0.0
              resume: FitManyState | None = None, return_state: bool = False, generator: torch.Generator | None = None,
              optimizer: str = "adam", penalty_callback=None, penalty_weight: float = 0.0, site_seeds=None,
              closed_form: bool = True, censored=None, target_upper=None, approximation="laplace", objective="mll",
-             _penalty_uniforms=None):
+             _penalty_uniforms=None, folds=None):
     """Fit ``models[i]`` to ``datasets[i] = (covariates, target[, target_unc])`` for all i at once.  Returns the
     per-site final objectives (a float64 tensor) -- with ``return_state=True`` the pair (objectives, ``FitManyState``);
     the models are updated in place (``is_fitted``, parameters, device state).
@@ -575,9 +601,19 @@ def fit_many(models, datasets, iterations: int = 100, learning_rate: float = 0.0
 
     ``objective``: "mll" (the default; None means the same) or "loo", as ``MarginalHIP.fit(objective=...)``: with "loo" the device
     step of an iteration is ONE batched ``dgp_loo_fit_step`` and every site minimises (L_LOO - log prior) / n, in both host paths;
-    every model then records it in ``objective_``.  Refused together with a censored row (``NotImplementedError``)."""
+    every model then records it in ``objective_``.  Refused together with a censored row (``NotImplementedError``).
+    "lgo" with ``folds``: the leave-group-out predictive likelihood, ONE batched ``dgp_lgo_fit_step`` per iteration.  ``folds``
+    is one scheme of ``validation.cv_folds`` applied to every site's own training times ("YE", an int k, ``("random", k,
+    seed)``, explicit ids ...), or a Python list with one scheme per site; the batched plan gets (batch, n) fold ids with a
+    common number of folds (a site's missing folds are empty).  Every model records its ids in ``objective_folds_``; the
+    returned ``FitManyState`` carries them, so a resumed call may leave ``folds`` out.  ``folds`` with another objective is a
+    ``ValueError``."""
     _refuse_ep(approximation, "fit_many")
     objective = objective_name(objective)
+    if objective == "lgo" and folds is None and getattr(resume, "folds", None) is None:
+        raise ValueError('fit_many: objective="lgo" needs folds=<scheme>: what is held out together (see validation.cv_folds)')
+    if objective != "lgo" and folds is not None:
+        raise ValueError(f'fit_many: folds belongs to objective="lgo", not to objective={objective!r}')
     if site_seeds is not None and len(site_seeds) != len(models):
         raise ValueError("site_seeds needs one seed per model")
     _refuse_censored_records(datasets, "fit_many")
@@ -632,9 +668,13 @@ def fit_many(models, datasets, iterations: int = 100, learning_rate: float = 0.0
     if B > 1:
         plan.set_site_sizes(sizes)
     cstate = None
-    if objective == "loo" and any(sd is not None for sd in sides):
-        raise NotImplementedError('fit_many: objective="loo" is not available together with censored observations: the '
+    if objective in ("loo", "lgo") and any(sd is not None for sd in sides):
+        raise NotImplementedError(f'fit_many: objective="{objective}" is not available together with censored observations: the '
                                   "pseudo-data of a censored fit are not samples")
+    fold_ids = None
+    if objective == "lgo":
+        fold_ids = _site_fold_ids(models, folds, sizes, n, resume)
+        plan.set_folds(fold_ids if B > 1 else fold_ids[0])
     if any(sd is not None for sd in sides):
         side_all = torch.zeros((B, n), dtype=torch.int32)
         for b, sd in enumerate(sides):
@@ -902,13 +942,15 @@ def fit_many(models, datasets, iterations: int = 100, learning_rate: float = 0.0
     for b, (m, own) in enumerate(zip(models, own_params)):
         _hand_back(m, own, {k: v[b] for k, v in params.items()}, int(last_iteration[b]), xs[b], ys[b])
         m.objective_ = objective
+        m.objective_folds_ = None if fold_ids is None else fold_ids[b, : sizes[b]].numpy().copy()
         if censored is not None:
             _hand_back_censoring(m, censored[b] if target_upper is not None else sides[b], sizes[b], cstate, b,
                                  None if target_upper is None else target_upper[b], ys_given[b])
     if return_state:
         state = FitManyState(params={k: v.detach().clone() for k, v in params.items()}, m1=m1, m2=m2, step=step, lr=lr, best=best,
                              num_bad=num_bad, cooldown=cooldown, es_best=es_best, stale=stale, live=live, last_obj=last_obj,
-                             last_iteration=last_iteration, iterations_done=torch.tensor(it0 + iterations), nan_run=nan_run)
+                             last_iteration=last_iteration, iterations_done=torch.tensor(it0 + iterations), nan_run=nan_run,
+                             folds=fold_ids)
         return last_obj, state
     return last_obj
 
@@ -995,6 +1037,9 @@ def fit_many_distributed(models, datasets, group=None, load: str = "all", seed: 
     _refuse_censored_records(datasets, "fit_many_distributed")
     _refuse_ep(kw.get("approximation"), "fit_many_distributed")
     objective = objective_name(kw.get("objective"))  # passed on to fit_many with the other keywords
+    folds = kw.pop("folds", None)  # one scheme for every site, or a list with one per site: each rank takes its sites' share
+    if isinstance(folds, list) and len(folds) != len(models):
+        raise ValueError("fit_many_distributed: a list of folds needs one scheme per site")
     if "resume" in kw or kw.get("return_state") or "site_seeds" in kw:
         raise ValueError("fit_many_distributed: resume / return_state are per-rank; use fit_many on each rank's share")
     if len(models) != len(datasets) or not models:
@@ -1016,7 +1061,9 @@ def fit_many_distributed(models, datasets, group=None, load: str = "all", seed: 
             objs, state = fit_many([models[i] for i in mine], [datasets[i] for i in mine], return_state=True,
                                    site_seeds=None if seed is None else [seed + i for i in mine],
                                    censored=None if censored is None else [censored[i] for i in mine],
-                                   target_upper=None if target_upper is None else [target_upper[i] for i in mine], **kw)
+                                   target_upper=None if target_upper is None else [target_upper[i] for i in mine],
+                                   **({} if folds is None else {"folds": [folds[i] for i in mine] if isinstance(folds, list) else folds}),
+                                   **kw)
         except Exception as e:  # noqa: BLE001 -- reported after the collective, on every rank
             error = e
 
@@ -1074,6 +1121,10 @@ def fit_many_distributed(models, datasets, group=None, load: str = "all", seed: 
                 o += w
             _hand_back(models[i], own, values, int(table[i, P + 1]) - 1, tx, ty)
             models[i].objective_ = objective
+            models[i].objective_folds_ = None
+            if objective == "lgo":
+                scheme = folds[i] if isinstance(folds, list) else folds
+                models[i].objective_folds_ = _site_fold_ids([models[i]], [scheme], [tx.shape[0]], tx.shape[0], None)[0].numpy()
             if censored is not None:
                 up = None if target_upper is None else target_upper[i]
                 _site_sides([models[i]], [censored[i]], [tx.shape[0]], "fit_many_distributed", None if up is None else [up])

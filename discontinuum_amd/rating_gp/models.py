@@ -285,7 +285,7 @@ class RatingGPMarginalHIP(RatingDataMixin, MarginalHIP):
     def fit(self, covariates, target, target_unc=None, iterations=100, optimizer=None, learning_rate=None,
             early_stopping=False, patience=60, scheduler=True, resume=False,
             monotonic_penalty_weight: float = 0.0, grid_size: int = 64, monotonic_penalty_interval: int = 1, censored=None, approximation="laplace",
-            objective="mll"):
+            objective="mll", folds=None):
         """The engine's ``fit`` plus the optional monotonicity penalty (signature of gpytorch.py:81-128).  ``censored`` (and
         ``approximation``) is passed on so that the engine can refuse it: the learned noise term has no gradient in a censored fit."""
         callback, weight = None, 0.0
@@ -295,4 +295,5 @@ class RatingGPMarginalHIP(RatingDataMixin, MarginalHIP):
         return super().fit(covariates=covariates, target=target, target_unc=target_unc, iterations=iterations,
                            optimizer=optimizer, learning_rate=learning_rate, early_stopping=early_stopping,
                            patience=patience, scheduler=scheduler, resume=resume, penalty_callback=callback,
-                           penalty_weight=weight, censored=censored, approximation=approximation, objective=objective)
+                           penalty_weight=weight, censored=censored, approximation=approximation, objective=objective,
+                           folds=folds)

@@ -151,4 +151,36 @@ int dgp_posterior_window_variances(dgp_plan* p, const double* theta, const void*
                                    int64_t q, int mode, int64_t reach, int panel_rows, void* work_dev, size_t work_bytes,
                                    double* mean_dev, double* var_dev, void* stream);
 
+/* ---- The exact leave-group-out predictive likelihood as a training objective (csrc/dgp_lgo.hip).
+ * With S = (K^)^-1, alpha = S r and disjoint folds B_g (rows in no fold and empty folds are allowed):
+ *     G_g = S[B_g, B_g],  C_g = G_g^-1,  e_g = C_g alpha[B_g]                         (as dgp_cross_validate)
+ *     L_LGO = sum_g [ 1/2 alpha_g^T e_g - 1/2 log|G_g| + b_g / 2 log 2 pi ]           (minus the sum of dgp_cross_validate's lpd)
+ *     c = e_g scattered to the rows' own positions,  b = S c,  W = blockdiag(C_g + e_g e_g^T),  M2 = S W S
+ *     dL/dtheta_p = 1/2 tr((M2 - b alpha^T - alpha b^T) dK/dtheta_p),  dL/dr = b,  dL/dnoise_i = 1/2 (M2)_ii - b_i alpha_i
+ * Folds of one give dgp_loo_fit_step's objective; one fold of every row gives dgp_fit_step's marginal likelihood.
+ * dgp_lgo_fit_step has the arguments, shapes and batching of dgp_fit_step plus the folds and a work area.  order_dev / start_dev
+ * ([batch][n] / [batch][ngroups + 1] int32), ngroups and max_group are exactly dgp_cross_validate's; the kernels clamp what they
+ * read from them.  It runs dgp_fit_step's launches unchanged into a result row of its own, dgp_cross_validate's fold algebra on
+ * the inverse (its three routes by max_group) for e_g, log|G_g| and the pivots, and in addition the full blocks W_g; then
+ * G = F W (F = S made full; per fold a product on the MFMA tile cores, 128 x 128 tiles when max_group > 64, 64 x 64 otherwise; for
+ * max_group = 1 the column scaling of dgp_loo_fit_step), M2 = F G^T, b = S c and the contraction exactly as dgp_loo_fit_step.
+ * out_dev: DGP_OUT_* layout with NLL = L_LGO and DTHETA, SUM_DR, DR_W0.., SUM_DNOISE its gradients; QUAD, LOGDET and INFO are those
+ * of the factorisation.  A site one of whose G_g is not positive definite reports 1 + the index of the first such fold in its INFO
+ * (when the factorisation's own status is 0) and NaN as its value: the return code stays 0 and the other sites are unaffected.
+ * The plan holds afterwards exactly what dgp_fit_step with the same arguments leaves.  No floating-point atomics: bitwise
+ * repeatable; a site's result does not depend on its batch (at the same max_group, which picks the route).
+ * dgp_lgo_value: out2_dev [batch][2] doubles = (L_LGO, info) from the factorisation the plan holds, when the last step left S in it.
+ * Work areas: dgp_lgo_workspace_bytes (three N x N matrices per site, the blocks W_g -- N round_up(max_group, 128) doubles per
+ * site and one tile of rows -- and dgp_cross_validate's own area) / dgp_lgo_value_workspace_bytes; 0 for a null or float32 plan
+ * or bad sizes.  float64 plans, single-site or batched.  Before any launch: DGP_E_ARG (null plan / argument; a float32 plan -- the
+ * text says so; ngroups or max_group outside 1 .. n; misaligned work area), DGP_E_WORKSPACE (work area missing or too small),
+ * DGP_E_STATE (no inputs / no inverse). */
+size_t dgp_lgo_workspace_bytes(const dgp_plan* p, int ngroups, int64_t max_group);
+size_t dgp_lgo_value_workspace_bytes(const dgp_plan* p, int ngroups, int64_t max_group);
+int dgp_lgo_fit_step(dgp_plan* p, const double* theta_host, const void* r_dev, const void* noise_dev, const int32_t* order_dev,
+                     const int32_t* start_dev, int ngroups, int64_t max_group, void* work_dev, size_t work_bytes, void* out_dev,
+                     void* dr_dev, void* dnoise_dev, void* stream);
+int dgp_lgo_value(dgp_plan* p, const int32_t* order_dev, const int32_t* start_dev, int ngroups, int64_t max_group, void* work_dev,
+                  size_t work_bytes, void* out2_dev, void* stream);
+
 #endif /* DGP_HIP_EXT2_H */
