@@ -754,12 +754,14 @@ class GPPlan:
             self._call("dgp_posterior_cov", th, _ptr(xs), m, *work, _ptr(mean), _ptr(cov))
         return mean, cov
 
-    def psd_safe_factor(self, cov: torch.Tensor, m: int):
+    def psd_safe_factor(self, cov: torch.Tensor, m: int, ladder=None):
         """Lower Cholesky factor of the (M, M) matrix ``cov`` (layout of ``posterior_cov``; left untouched) by the
         blocked HIP potrf of an order-m plan, with ``psd_safe_cholesky``'s jitter policy: the matrix itself first, then
         + 1e-8 I, 1e-7 I, 1e-6 I (fp32: 1e-6 .. 1e-4), each attempt restarting from the kept matrix; raises after the
         last.  -> (Lbuf, jitter): Lbuf is that plan's (M, M) buffer -- zeros above the diagonal inside the diagonal
-        128-blocks, identity pad, blocks above the block diagonal undefined -- valid until the next call."""
+        128-blocks, identity pad, blocks above the block diagonal undefined -- valid until the next call.  ``ladder``: other
+        jitters to try in order (``extremes`` factors a float32 plan's covariance in float64 with the float32 ladder: the
+        matrix carries float32 rounding, which 1e-6 does not cover)."""
         M = int(self.lib.dgp_padded_n(m))
         if tuple(cov.shape) != (M, M) or cov.dtype != self.dtype or not cov.is_cuda or not cov.is_contiguous():
             raise ValueError(f"cov must be a contiguous ({M}, {M}) {self.dtype} CUDA tensor")
@@ -770,7 +772,7 @@ class GPPlan:
         Lbuf = fac.buffer(_lib.BUF_A)
         info = -1
         with torch.cuda.device(self.device):
-            for jitter in self._jitter_ladder():
+            for jitter in (self._jitter_ladder() if ladder is None else tuple(ladder)):
                 Lbuf.copy_(cov)
                 if jitter:
                     Lbuf.diagonal()[:m].add_(jitter)
@@ -825,6 +827,12 @@ class GPPlan:
     def window_variances(self, cov, m: int, mu, lo, hi, a=None, mode: int = 0, scale2=None):
         """The module-level ``window_variances``."""
         return window_variances(cov, m, mu, lo, hi, a=a, mode=mode, scale2=scale2)
+
+    def orthant_probability(self, L, m: int, lo, hi, npoints: int = 4096, nshifts: int = 16, seed: int = 0, max_bytes=None):
+        """The module-level ``orthant_probability``; ``self._orthant_hook``, when set, is its ``hook`` (the tests capture the
+        device's own factor and limits through it, the way ``sample_draws`` keeps ``_last_z``)."""
+        return orthant_probability(L, m, lo, hi, npoints=npoints, nshifts=nshifts, seed=seed, max_bytes=max_bytes,
+                                   hook=getattr(self, "_orthant_hook", None))
 
     def sample_value(self, cov, m: int, a, scale2, groups, ngroups: int, obs_var=None, rows=None, nterms=None):
         """The module-level ``sample_value``."""
@@ -1507,6 +1515,105 @@ def bvn_excess(h: torch.Tensor, k: torch.Tensor, rho: torch.Tensor):
     with torch.cuda.device(h.device):
         _call("dgp_debug_bvn_excess", _ptr(h), _ptr(k), _ptr(rho), h.numel(), _ptr(out))
     return out
+
+
+ORTHANT_MAX_DIM = 16384     # the largest m of ``dgp_orthant_probability``
+ORTHANT_MAX_LEVELS = 64     # levels of one call; longer lists go in several
+ORTHANT_DEFAULT_MAX_BYTES = 8 * 2 ** 30  # the work area ``orthant_probability`` allows itself when ``max_bytes`` is None
+_orthant_ws = {}            # device -> the cached work area (grown, never shrunk)
+
+
+def richtmyer_generators(m: int):
+    """The generators g_i = frac(sqrt(p_i)), p_i the i-th prime, i = 0 .. m-1, of the Richtmyer rule ``orthant_probability``
+    runs over (a numpy sieve; plumbing).  -> float64 numpy array (m,)."""
+    import numpy as np
+
+    m = int(m)
+    if m < 1:
+        raise ValueError("m must be at least 1")
+    bound = 16
+    while True:
+        sieve = np.ones(bound + 1, dtype=bool)
+        sieve[:2] = False
+        for k in range(2, int(bound ** 0.5) + 1):
+            if sieve[k]:
+                sieve[k * k::k] = False
+        primes = np.nonzero(sieve)[0]
+        if primes.size >= m:
+            break
+        bound *= 2
+    root = np.sqrt(primes[:m].astype(np.float64))
+    return root - np.floor(root)
+
+
+def orthant_shifts(m: int, nshifts: int, seed: int = 0):
+    """The random shifts of ``orthant_probability``: (nshifts, m) float64 in [0, 1) from torch's CPU generator seeded with
+    ``seed``.  One set serves every level of a call, so a level's shifts cannot depend on how the levels are chunked."""
+    return torch.rand(int(nshifts), int(m), dtype=torch.float64, generator=torch.Generator().manual_seed(int(seed)))
+
+
+def orthant_level_chunks(m: int, nlevels: int, nshifts: int, npoints: int, max_bytes=None):
+    """How ``orthant_probability`` splits ``nlevels`` levels into calls: the most levels (at most 64) whose work area fits
+    ``max_bytes`` (None: ``ORTHANT_DEFAULT_MAX_BYTES``).  -> (levels per call, bytes of one level's work area).  ``ValueError``
+    naming the bytes when one level does not fit, or the sizes when they are out of range.  Needs no device."""
+    lib = _lib.load()
+    m, nlevels, nshifts, npoints = int(m), int(nlevels), int(nshifts), int(npoints)
+    one = int(lib.dgp_orthant_probability_workspace_bytes(m, 1, nshifts, npoints))
+    if one == 0 or nlevels < 1:
+        raise ValueError(f"bad size: m = {m}, levels = {nlevels}, nshifts = {nshifts}, npoints = {npoints} "
+                         f"(1 <= m <= {ORTHANT_MAX_DIM}, 1 <= levels, 2 <= nshifts <= 64, 1 <= npoints <= 2^20)")
+    budget = ORTHANT_DEFAULT_MAX_BYTES if max_bytes is None else int(max_bytes)
+    if one > budget:
+        raise ValueError(f"orthant_probability needs a work area of {one} bytes for ONE level (m = {m}, {nshifts} shifts x "
+                         f"{npoints} points), which exceeds max_bytes = {budget}")
+    return min(nlevels, ORTHANT_MAX_LEVELS, budget // one), one
+
+
+def orthant_probability(L: torch.Tensor, m: int, lo, hi, npoints: int = 4096, nshifts: int = 16, seed: int = 0, max_bytes=None,
+                        hook=None):
+    """Orthant probabilities P(lo_l <= f <= hi_l), f ~ N(0, L L^T) in ``m`` dimensions, one per level l, through
+    ``dgp_orthant_probability``: Genz's separation of variables over ``nshifts`` randomly shifted Richtmyer rules of
+    ``npoints`` points.  NOT exact: unbiased, with its own standard error.
+
+    ``L``: the lower factor as ``GPPlan.psd_safe_factor`` leaves it -- (M, M) float64 CUDA, M = padded m; blocks above the
+    block diagonal are never read; ``lo`` / ``hi``: the CENTRED limits, (m,) or (levels, m), +-inf allowed.  The generators
+    (``richtmyer_generators``) and the shifts (``orthant_shifts``: torch's CPU generator with ``seed``) come from the host.
+    The work area is cached per device; when it would exceed ``max_bytes`` the levels go in several calls
+    (``orthant_level_chunks``) -- every level sees the same shifts either way.  ``hook``: called with a dict of the call's
+    device inputs (``L``, ``m``, ``lo``, ``hi``, ``gen``, ``shifts``, ``npoints``) before the launches, for tests.
+    -> (prob (levels,), se (levels,)) float64 device tensors."""
+    m = int(m)
+    if not (torch.is_tensor(L) and L.is_cuda and L.dtype == torch.float64 and L.dim() == 2 and L.stride(1) == 1):
+        raise ValueError("L must be a 2-D float64 CUDA tensor with contiguous rows")
+    dev = L.device
+    lo_t = torch.as_tensor(lo, dtype=torch.float64).reshape(-1, m).to(dev).contiguous()
+    hi_t = torch.as_tensor(hi, dtype=torch.float64).reshape(-1, m).to(dev).contiguous()
+    if lo_t.shape != hi_t.shape:
+        raise ValueError("lo and hi must have the same shape, (m,) or (levels, m)")
+    nlev = int(lo_t.shape[0])
+    per_call, one = orthant_level_chunks(m, nlev, nshifts, npoints, max_bytes)
+    M = int(_lib.load().dgp_padded_n(m))
+    if L.shape[0] < M or L.shape[1] < M:
+        raise ValueError(f"L must hold the padded ({M}, {M}) factor")
+    with torch.cuda.device(dev):
+        gen = torch.from_numpy(richtmyer_generators(m)).to(dev)
+        shifts = orthant_shifts(m, nshifts, seed).to(dev)
+        if hook is not None:
+            hook(dict(L=L, m=m, lo=lo_t, hi=hi_t, gen=gen, shifts=shifts, npoints=int(npoints)))
+        need = one * per_call
+        ws = _orthant_ws.get(dev)
+        if ws is None or ws.numel() < need + 256:
+            _orthant_ws[dev] = None
+            _orthant_ws[dev] = ws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
+        off = (-ws.data_ptr()) % 256
+        prob = torch.empty(nlev, dtype=torch.float64, device=dev)
+        se = torch.empty(nlev, dtype=torch.float64, device=dev)
+        for l0 in range(0, nlev, per_call):
+            n = min(per_call, nlev - l0)
+            _call("dgp_orthant_probability", _ptr(L), m, int(L.stride(0)), _ptr(lo_t[l0:l0 + n]), _ptr(hi_t[l0:l0 + n]), n, _ptr(gen),
+                  _ptr(shifts), int(nshifts), int(npoints), C.c_void_p(ws.data_ptr() + off), one * n, _ptr(prob[l0:l0 + n]),
+                  _ptr(se[l0:l0 + n]))
+    return prob, se
 
 
 def cross_validate_folds(plan, groups, launch, max_group_bound=None):

@@ -985,6 +985,41 @@ class MarginalHIP(BaseModel):
                           align=align, min_periods=min_periods, statistic=statistic)
 
     @is_fitted
+    def extreme_probability(self, covariates, threshold=None, threshold_series=None, kind="max", freq="YE", window=None,
+                            align="right", min_periods=None, npoints=4096, nshifts=16, seed=0, max_bytes=None, pred_noise=False,
+                            streamed=False, statistic=None):
+        """Per period of ``freq`` the probability that the target stays below (``kind="max"``) or above (``"min"``) a
+        data-space threshold at EVERY point of the period -- "not exceeded once in the year" -- as ``prob_never``, with
+        ``prob_any`` = 1 - prob_never: the distribution function of the period's maximum (survival function of its minimum) at
+        that level.  An orthant probability of the period's block of the posterior covariance, by a randomly shifted
+        quasi-Monte-Carlo sweep on the device (``dgp_orthant_probability``): the one product that is NOT exact -- unbiased, with
+        its own standard error ``error`` (about 1e-3 for a daily year at the defaults).  ``window``: the extreme of the rolling
+        mean (``kind="min"``, ``window="7D"``: the 7-day low flow).  -> Dataset on (``level``, ``time``) with ``prob_never``,
+        ``prob_any``, ``error``, ``n_points``.  See ``discontinuum_amd.extremes`` (also for the refusals)."""
+        from ..extremes import extreme_probability
+        from ..loads import DEFAULT_MAX_BYTES
+
+        return extreme_probability(self, covariates, threshold=threshold, threshold_series=threshold_series, kind=kind, freq=freq,
+                                   window=window, align=align, min_periods=min_periods, npoints=npoints, nshifts=nshifts, seed=seed,
+                                   max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes, pred_noise=pred_noise,
+                                   streamed=streamed, statistic=statistic)
+
+    @is_fitted
+    def extreme_quantiles(self, covariates, q=(0.05, 0.5, 0.95), kind="max", freq="YE", window=None, align="right",
+                          min_periods=None, npoints=4096, nshifts=16, seed=0, max_bytes=None, grid=None, rounds=3, pred_noise=False,
+                          streamed=False, statistic=None):
+        """The ``q``-quantiles of every period's maximum (``kind="max"``) or minimum (``"min"``) of the target in data space --
+        the annual peak with its interval, the annual minimum of a 7-day mean (``window="7D"``) -- by a bracketing search over
+        levels on ``extreme_probability``'s sweep.  -> Dataset on (``quantile``, ``time``) with ``value``, ``bracket`` (the
+        final bracket's width), ``bracket_prob``, ``error`` and ``n_points``.  NOT exact; see ``discontinuum_amd.extremes``."""
+        from ..extremes import extreme_quantiles
+        from ..loads import DEFAULT_MAX_BYTES
+
+        return extreme_quantiles(self, covariates, q=q, kind=kind, freq=freq, window=window, align=align, min_periods=min_periods,
+                                 npoints=npoints, nshifts=nshifts, seed=seed, max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes,
+                                 grid=grid, rounds=rounds, pred_noise=pred_noise, streamed=streamed, statistic=statistic)
+
+    @is_fitted
     def rolling_mean(self, covariates, window, statistic=None, align="right", min_periods=None, ci=0.95, return_cov=False,
                      max_bytes=None, streamed=False):
         """The rolling mean of the target over ``window`` ("30D", "7D", "96h" or a ``numpy.timedelta64``; membership by time,

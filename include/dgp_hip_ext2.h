@@ -183,4 +183,29 @@ int dgp_lgo_fit_step(dgp_plan* p, const double* theta_host, const void* r_dev, c
 int dgp_lgo_value(dgp_plan* p, const int32_t* order_dev, const int32_t* start_dev, int ngroups, int64_t max_group, void* work_dev,
                   size_t work_bytes, void* out2_dev, void* stream);
 
+/* ORTHANT PROBABILITIES (csrc/dgp_orthant.hip): prob[l] ~ P(lo_l <= f <= hi_l componentwise), f ~ N(0, L L^T) in m dimensions -- the
+ * distribution function of a period's maximum (lo = -inf) or the survival function of its minimum (hi = +inf) of a latent
+ * posterior whose block of the covariance has the lower factor L and whose mean has been subtracted from the limits.  NOT exact:
+ * Genz's separation of variables over nshifts randomly shifted Richtmyer rules of npoints points with the tent transform, unbiased,
+ * with its own standard error se[l] (the sample standard deviation of the shifts' estimates / sqrt(nshifts)).  The recurrence,
+ * its tail rules and its clamps are stated at the head of csrc/dgp_orthant.hip; a host restatement on the same generators and
+ * shifts walks the same points.
+ * L_dev      the factor as psd_safe_factor leaves it: row-major, leading dimension ld >= M (M = m rounded up to 128), ld even,
+ *            16-byte aligned; read inside the lower triangle of the diagonal 128-blocks and in the blocks below the block
+ *            diagonal only, rows < M; the sweep stops at m (the pad is never conditioned on);
+ * lo_dev, hi_dev  nlevels x m doubles, the CENTRED limits a - mu and b - mu; -inf / +inf allowed; lo > hi anywhere gives 0;
+ * gen_dev    m doubles, the rule's generators (frac sqrt(p_i));   shift_dev  nshifts x m doubles in [0, 1): both come from the host;
+ * prob_dev, se_dev  nlevels doubles.  An unconstrained level gives exactly 1 and 0.
+ * work_dev: dgp_orthant_probability_workspace_bytes(m, nlevels, nshifts, npoints) bytes, 256-byte aligned: per workgroup -- 128
+ * points of one (level, shift) -- its y values, round_up(m, 64) x 128 doubles, and one partial sum; 0 for bad sizes.  Its
+ * contents before the call do not matter.
+ * Two launches (grid = point chunks x shifts x levels, then one reduce), no floating-point atomics, every sum in a fixed order:
+ * repeated calls are bitwise equal, and a level's numbers do not depend on the other levels of the call.
+ * DGP_E_ARG: null arguments, bad sizes (1 <= m <= 16384, 1 <= nlevels <= 64, 2 <= nshifts <= 64, 1 <= npoints <= 2^20), ld < M or
+ * odd, a misaligned factor or work area; DGP_E_WORKSPACE: work area missing or too small -- all before any launch. */
+size_t dgp_orthant_probability_workspace_bytes(int64_t m, int nlevels, int nshifts, int64_t npoints);
+int dgp_orthant_probability(const double* L_dev, int64_t m, int64_t ld, const double* lo_dev, const double* hi_dev, int nlevels,
+                            const double* gen_dev, const double* shift_dev, int nshifts, int64_t npoints, void* work_dev,
+                            size_t work_bytes, double* prob_dev, double* se_dev, void* stream);
+
 #endif /* DGP_HIP_EXT2_H */
