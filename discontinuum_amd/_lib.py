@@ -185,6 +185,8 @@ EXT2_SIGNATURES = {
     "dgp_lgo_value": (_i, [_vp, _vp, _vp, _i, _i64, _vp, _sz, _vp, _vp]),
     "dgp_orthant_probability_workspace_bytes": (_sz, [_i64, _i, _i, _i64]),
     "dgp_orthant_probability": (_i, [_vp, _i64, _i64, _vp, _vp, _i, _vp, _vp, _i, _i64, _vp, _sz, _vp, _vp, _vp]),
+    "dgp_path_counts_workspace_bytes": (_sz, [_i64, _i, _i, _i64]),
+    "dgp_path_counts": (_i, [_vp, _i64, _i64, _vp, _i, _i, _vp, _vp, _vp, _i, _i64, _vp, _sz, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -834,6 +834,12 @@ class GPPlan:
         return orthant_probability(L, m, lo, hi, npoints=npoints, nshifts=nshifts, seed=seed, max_bytes=max_bytes,
                                    hook=getattr(self, "_orthant_hook", None))
 
+    def path_counts(self, L, m: int, thr, above: bool = True, link=None, npoints: int = 4096, nshifts: int = 16, seed: int = 0,
+                    max_bytes=None):
+        """The module-level ``path_counts``; ``self._counts_hook``, when set, is its ``hook``."""
+        return path_counts(L, m, thr, above=above, link=link, npoints=npoints, nshifts=nshifts, seed=seed, max_bytes=max_bytes,
+                           hook=getattr(self, "_counts_hook", None))
+
     def sample_value(self, cov, m: int, a, scale2, groups, ngroups: int, obs_var=None, rows=None, nterms=None):
         """The module-level ``sample_value``."""
         return sample_value(cov, m, a, scale2, groups, ngroups, obs_var=obs_var, rows=rows, nterms=nterms)
@@ -1614,6 +1620,78 @@ def orthant_probability(L: torch.Tensor, m: int, lo, hi, npoints: int = 4096, ns
                   _ptr(shifts), int(nshifts), int(npoints), C.c_void_p(ws.data_ptr() + off), one * n, _ptr(prob[l0:l0 + n]),
                   _ptr(se[l0:l0 + n]))
     return prob, se
+
+
+PATH_COUNT_LEVEL_GROUP = 16  # levels that share one workgroup's draws in ``dgp_path_counts``: 1 .. 16 levels cost one work area
+_counts_ws = {}              # device -> the cached work area of ``path_counts`` (grown, never shrunk)
+
+
+def path_count_level_chunks(m: int, nlevels: int, nshifts: int, npoints: int, max_bytes=None):
+    """How ``path_counts`` splits ``nlevels`` levels into calls: the most levels (at most 64) whose work area fits
+    ``max_bytes`` (None: ``ORTHANT_DEFAULT_MAX_BYTES``).  The draws of a workgroup serve up to 16 levels, so the work area
+    grows by one level's bytes per 16 levels.  -> (levels per call, bytes of one level's work area).  ``ValueError`` naming the
+    bytes when one level does not fit, or the sizes when they are out of range.  Needs no device."""
+    lib = _lib.load()
+    m, nlevels, nshifts, npoints = int(m), int(nlevels), int(nshifts), int(npoints)
+    one = int(lib.dgp_path_counts_workspace_bytes(m, 1, nshifts, npoints))
+    if one == 0 or nlevels < 1:
+        raise ValueError(f"bad size: m = {m}, levels = {nlevels}, nshifts = {nshifts}, npoints = {npoints} "
+                         f"(1 <= m <= {ORTHANT_MAX_DIM}, 1 <= levels, 2 <= nshifts <= 64, 1 <= npoints <= 2^20)")
+    budget = ORTHANT_DEFAULT_MAX_BYTES if max_bytes is None else int(max_bytes)
+    if one > budget:
+        raise ValueError(f"path_counts needs a work area of {one} bytes for ONE level (m = {m}, {nshifts} shifts x "
+                         f"{npoints} points), which exceeds max_bytes = {budget}")
+    return min(nlevels, ORTHANT_MAX_LEVELS, (budget // one) * PATH_COUNT_LEVEL_GROUP), one
+
+
+def path_counts(L: torch.Tensor, m: int, thr, above: bool = True, link=None, npoints: int = 4096, nshifts: int = 16, seed: int = 0,
+                max_bytes=None, hook=None):
+    """Histograms of the exceedance count N and of the longest spell R of joint paths f ~ N(0, L L^T) in ``m`` dimensions
+    through ``dgp_path_counts``: per level l and shift s, over the ``npoints`` points of the s-th randomly shifted Richtmyer
+    rule, how many paths have N = k points beyond ``thr[l]`` (``above``: f_i > thr, else f_i < thr; a NaN threshold never
+    counts) and how many have a longest run of R = k consecutive such points.  NOT exact: unbiased; the caller forms the pmf
+    (hist / npoints), its functionals per shift and their standard errors over the shifts.
+
+    ``L``: the lower factor as ``GPPlan.psd_safe_factor`` leaves it (see ``orthant_probability``); ``thr``: the CENTRED
+    thresholds, (m,) or (levels, m); ``link``: (m,) flags, ``link[i] == 0`` breaks a run between points i - 1 and i (None: no
+    breaks).  Generators, shifts, ``seed`` and ``hook`` (keys ``L``, ``m``, ``thr``, ``above``, ``link``, ``gen``, ``shifts``,
+    ``npoints``) as for ``orthant_probability``.  The work area is cached per device; lists of more than 64 levels, or over
+    ``max_bytes``, go in several calls on the same shifts (``path_count_level_chunks``): a level's integers do not change.
+    -> (count_hist, spell_hist) int32 device tensors (levels, nshifts, m + 1)."""
+    m = int(m)
+    if not (torch.is_tensor(L) and L.is_cuda and L.dtype == torch.float64 and L.dim() == 2 and L.stride(1) == 1):
+        raise ValueError("L must be a 2-D float64 CUDA tensor with contiguous rows")
+    dev = L.device
+    thr_t = torch.as_tensor(thr, dtype=torch.float64).reshape(-1, m).to(dev).contiguous()
+    nlev = int(thr_t.shape[0])
+    link_t = None
+    if link is not None:
+        link_t = (torch.as_tensor(link).reshape(-1) != 0).to(torch.int32).to(dev).contiguous()
+        if link_t.numel() != m:
+            raise ValueError(f"link must hold m = {m} flags")
+    per_call, one = path_count_level_chunks(m, nlev, nshifts, npoints, max_bytes)
+    M = int(_lib.load().dgp_padded_n(m))
+    if L.shape[0] < M or L.shape[1] < M:
+        raise ValueError(f"L must hold the padded ({M}, {M}) factor")
+    with torch.cuda.device(dev):
+        gen = torch.from_numpy(richtmyer_generators(m)).to(dev)
+        shifts = orthant_shifts(m, nshifts, seed).to(dev)
+        if hook is not None:
+            hook(dict(L=L, m=m, thr=thr_t, above=bool(above), link=link_t, gen=gen, shifts=shifts, npoints=int(npoints)))
+        need = one * (-(-per_call // PATH_COUNT_LEVEL_GROUP))
+        ws = _counts_ws.get(dev)
+        if ws is None or ws.numel() < need + 256:
+            _counts_ws[dev] = None
+            _counts_ws[dev] = ws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
+        off = (-ws.data_ptr()) % 256
+        count = torch.empty(nlev, int(nshifts), m + 1, dtype=torch.int32, device=dev)
+        spell = torch.empty(nlev, int(nshifts), m + 1, dtype=torch.int32, device=dev)
+        for l0 in range(0, nlev, per_call):
+            n = min(per_call, nlev - l0)
+            _call("dgp_path_counts", _ptr(L), m, int(L.stride(0)), _ptr(thr_t[l0:l0 + n]), n, 1 if above else 0,
+                  _ptr(link_t) if link_t is not None else None, _ptr(gen), _ptr(shifts), int(nshifts), int(npoints),
+                  C.c_void_p(ws.data_ptr() + off), need, _ptr(count[l0:l0 + n]), _ptr(spell[l0:l0 + n]))
+    return count, spell
 
 
 def cross_validate_folds(plan, groups, launch, max_group_bound=None):

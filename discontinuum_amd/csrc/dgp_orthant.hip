@@ -30,6 +30,7 @@
 #include "../../include/dgp_hip.h"
 #include "dgp_gemm.h"
 #include "dgp_plan.h"
+#include "dgp_qmc.h"  // or_weight, OR_YMAX, the size limits
 
 namespace dgp {
 
@@ -37,25 +38,11 @@ namespace {
 
 constexpr int OR_DB = 64;    // dimensions per block (divides the factor's 128-blocks)
 constexpr int OR_PC = 128;   // points per workgroup
-constexpr long OR_MAX_M = 16384;
-constexpr long OR_MAX_POINTS = 1L << 20;
-constexpr double OR_YMAX = 38.0;  // |y| clamp: Phi(-38) = 3e-316
 
 using OrG = TileGemm<double, true, false, OR_DB, OR_PC>;
 static_assert(OrG::SMEM_ELEMS <= OR_DB * OR_PC, "the tile core's operand image must fit the stage it shares");
 
 __device__ __forceinline__ double or_phi(double x) { return 0.5 * erfc(-0.70710678118654752440 * x); }
-
-// The weight of point n in dimension i: |2 frac(n g + D) - 1| with the product and the sum rounded once each, as numpy rounds
-// them.  The pragma, not the _rn intrinsics: those are plain operators here and contract to one fma like any others, which
-// moved x by an ulp -- 6e-12 of a weight near 0 -- and an estimate by 2e-10 relative.
-__device__ __forceinline__ double or_weight(double n, double g, double shift) {
-#pragma clang fp contract(off)
-  double x = n * g;
-  x = x + shift;
-  x = x - floor(x);
-  return fabs(2.0 * x - 1.0);
-}
 
 // One step of the recurrence from the standardised limits a <= b and the weight w: -> d, and y by reference.  No contraction
 // either: every operation is rounded as the restatement rounds it.  Kept out of line: inlined into the sweep's loops the
@@ -165,11 +152,6 @@ __global__ void orthant_reduce_kernel(const double* __restrict__ partial, int nc
   }
   prob[lev] = mean;
   se[lev] = sqrt(ss / (double)(nshifts - 1)) / sqrt((double)nshifts);
-}
-
-inline bool or_sizes_ok(int64_t m, int nlevels, int nshifts, int64_t npoints) {
-  return m >= 1 && m <= OR_MAX_M && nlevels >= 1 && nlevels <= 64 && nshifts >= 2 && nshifts <= 64 && npoints >= 1 &&
-         npoints <= OR_MAX_POINTS;
 }
 
 }  // namespace

@@ -1020,6 +1020,44 @@ class MarginalHIP(BaseModel):
                                  grid=grid, rounds=rounds, pred_noise=pred_noise, streamed=streamed, statistic=statistic)
 
     @is_fitted
+    def exceedance_distribution(self, covariates, threshold=None, threshold_series=None, freq="YE", above=True, window=None,
+                                align="right", min_periods=None, npoints=4096, nshifts=16, seed=0, max_bytes=None, pred_noise=False,
+                                streamed=False, kind=None, statistic=None):
+        """Per period of ``freq`` the DISTRIBUTION of the number N of points at which the target lies above (``above=False``:
+        below) a data-space threshold -- P(N <= k), for "no more than k exceedances in the year" -- and of the longest spell R
+        of consecutive such points.  Joint paths of the period's block of the posterior are drawn, compared and counted on the
+        device (``dgp_path_counts``) over the orthant sweep's randomly shifted rules: NOT exact -- unbiased, every value with its
+        own standard error.  -> Dataset on (``level``, ``time``, ``count``) with ``pmf``, ``cdf``, ``cdf_error``, ``spell_pmf``,
+        ``spell_cdf``, ``spell_cdf_error``, and on (``level``, ``time``) ``mean``, ``mean_error``, ``variance``,
+        ``variance_error``, ``n_points``.  Spells are cut at period boundaries and at gaps of the record.  See
+        ``discontinuum_amd.frequency`` (also for the refusals)."""
+        from ..frequency import exceedance_distribution
+        from ..loads import DEFAULT_MAX_BYTES
+
+        return exceedance_distribution(self, covariates, threshold=threshold, threshold_series=threshold_series, freq=freq,
+                                       above=above, window=window, align=align, min_periods=min_periods, npoints=npoints,
+                                       nshifts=nshifts, seed=seed, max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes,
+                                       pred_noise=pred_noise, streamed=streamed, kind=kind, statistic=statistic)
+
+    @is_fitted
+    def compliance_probability(self, covariates, threshold=None, threshold_series=None, allowed=None, allowed_fraction=None,
+                               max_spell=None, freq="YE", above=True, window=None, align="right", min_periods=None, npoints=4096,
+                               nshifts=16, seed=0, max_bytes=None, pred_noise=False, streamed=False, kind=None, statistic=None):
+        """Per period of ``freq`` the probability that a frequency rule is met: ``prob`` = P(N <= ``allowed``), or
+        P(N <= floor(``allowed_fraction`` x the period's points)), N the points beyond the threshold; with ``max_spell`` also
+        ``prob_spell`` = P(longest spell <= ``max_spell``).  Exactly one of ``allowed`` / ``allowed_fraction``.  Read from
+        ``exceedance_distribution``'s sweep: NOT exact, with ``error`` / ``error_spell``.  -> Dataset on (``level``, ``time``),
+        with ``allowed_count`` and ``n_points`` on ``time``.  See ``discontinuum_amd.frequency``."""
+        from ..frequency import compliance_probability
+        from ..loads import DEFAULT_MAX_BYTES
+
+        return compliance_probability(self, covariates, threshold=threshold, threshold_series=threshold_series, allowed=allowed,
+                                      allowed_fraction=allowed_fraction, max_spell=max_spell, freq=freq, above=above, window=window,
+                                      align=align, min_periods=min_periods, npoints=npoints, nshifts=nshifts, seed=seed,
+                                      max_bytes=DEFAULT_MAX_BYTES if max_bytes is None else max_bytes, pred_noise=pred_noise,
+                                      streamed=streamed, kind=kind, statistic=statistic)
+
+    @is_fitted
     def rolling_mean(self, covariates, window, statistic=None, align="right", min_periods=None, ci=0.95, return_cov=False,
                      max_bytes=None, streamed=False):
         """The rolling mean of the target over ``window`` ("30D", "7D", "96h" or a ``numpy.timedelta64``; membership by time,

@@ -208,4 +208,27 @@ int dgp_orthant_probability(const double* L_dev, int64_t m, int64_t ld, const do
                             const double* gen_dev, const double* shift_dev, int nshifts, int64_t npoints, void* work_dev,
                             size_t work_bytes, double* prob_dev, double* se_dev, void* stream);
 
+/* EXCEEDANCE COUNTS AND SPELLS OF JOINT PATHS (csrc/dgp_counts.hip): for f ~ N(0, L L^T) in m dimensions, drawn over the orthant
+ * sweep's nshifts randomly shifted Richtmyer rules of npoints points (f = L y, y_i = clamp(Phi^-1(w_i), -38, 38), nothing
+ * truncated), per level l and shift s the histograms over the points of
+ *   N = #{i : f_i beyond thr[l][i]}  (above != 0: f_i > thr, else f_i < thr; a NaN threshold never counts)   -> count_hist, and
+ *   R = the longest run of consecutive such i, a run being broken at i where link[i] == 0                      -> spell_hist.
+ * NOT exact: plain integration of an indicator over the rules, unbiased; the host forms pmf, distribution function, moments and
+ * their standard errors over the shifts.  The estimator is stated at the head of csrc/dgp_counts.hip; a host restatement on the
+ * same generators and shifts reproduces the integers unless a path lies within rounding of a threshold.
+ * L_dev, gen_dev, shift_dev  as for dgp_orthant_probability; the tile core loads rows [m, round_up(m, 128)) of the padded buffer
+ *            with the last block and discards their products: no value in a row >= m reaches a result;
+ * thr_dev    nlevels x m doubles, the CENTRED thresholds u - mu;
+ * link_dev   m int32 (link[0] is ignored), or null: every point continues the run of the point before it;
+ * count_hist_dev, spell_hist_dev  nlevels x nshifts x (m + 1) int32 each, zeroed by the call; every [l][s] row sums to npoints.
+ * work_dev: dgp_path_counts_workspace_bytes(m, nlevels, nshifts, npoints) bytes, 256-byte aligned: per workgroup -- 128 points of
+ * one shift and up to 16 levels -- its draws, round_up(m, 128) x 128 doubles; so 1 .. 16 levels cost the same; 0 for bad sizes.
+ * One launch after the two memsets (grid = point chunks x shifts x level chunks); integer atomics only: repeated calls give
+ * identical integers, and a level's histograms depend neither on the other levels of the call nor on how they are chunked.
+ * Errors: those of dgp_orthant_probability (link_dev may be null), all before any launch. */
+size_t dgp_path_counts_workspace_bytes(int64_t m, int nlevels, int nshifts, int64_t npoints);
+int dgp_path_counts(const double* L_dev, int64_t m, int64_t ld, const double* thr_dev, int nlevels, int above, const int32_t* link_dev,
+                    const double* gen_dev, const double* shift_dev, int nshifts, int64_t npoints, void* work_dev, size_t work_bytes,
+                    int32_t* count_hist_dev, int32_t* spell_hist_dev, void* stream);
+
 #endif /* DGP_HIP_EXT2_H */
